@@ -26,6 +26,7 @@ Tiers: kernels only on the resident shard (`value`), the device
 compared, with the host thread counts of both sides stated and a matched-thread comparison.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR    # + the last timed step's rows as DIR/<column>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -97,6 +98,36 @@ def gen_bam(prefix, contigs, n_reads, seed, flags, threads):
         with open(meta, "w") as f:
             f.write(out.decode())
     return prefix + ".bam", prefix + ".fa", json.load(open(meta))
+
+
+def generator_digest():
+    """Short sha256 of tools/gen_modbam.cpp: part of the cached BAM's name, so that a BAM written by another version of the generator is
+    never taken for this run's input (the output is a function of the flags, the seed and this source, whatever --threads is)."""
+    return sh256(os.path.join(ROOT, "tools", "gen_modbam.cpp"))[:12]
+
+
+DUMP_BYTES = 64_000_000   # --dump-outputs budget (all files together)
+
+
+def dump_outputs(d, rows, seed=0):
+    """--dump-outputs: the row columns the timed path produced in its last step (what mkp_shard_rerun(0, fetch) or the bedMethyl file of the
+    last pass hands a caller), one float64 .npy per column (exact for the u32 / i32 columns).  Above the budget a fixed seeded sample of
+    rows is written, in row order; row_index.npy says which rows and n_rows.npy how many there were."""
+    import numpy as np
+    import modkit_amd
+    fields = [f for f in modkit_amd.ROW_FIELDS if f in rows]
+    os.makedirs(d, exist_ok=True)
+    for f in list(modkit_amd.ROW_FIELDS) + ["row_index", "n_rows"]:   # (no column of an earlier dump is left to be compared)
+        if os.path.exists(os.path.join(d, f + ".npy")):
+            os.remove(os.path.join(d, f + ".npy"))
+    n = len(rows["pos"])
+    cap = (DUMP_BYTES - (1 << 16)) // (8 * (len(fields) + 1))
+    idx = np.arange(n) if n <= cap else np.sort(np.random.default_rng(seed).choice(n, cap, replace=False))
+    np.save(os.path.join(d, "n_rows.npy"), np.array([n], dtype=np.float64))
+    np.save(os.path.join(d, "row_index.npy"), idx.astype(np.float64))
+    for f in fields:
+        np.save(os.path.join(d, f + ".npy"), np.asarray(rows[f])[idx].astype(np.float64))
+    return {"dir": d, "rows": n, "rows_written": int(len(idx)), "columns": fields}
 
 
 def gen_bed(path, contigs, n, seed=5, width=2000):
@@ -189,15 +220,31 @@ def device_e2e_subprocess(bam, out, flags, pool_threads, hemi=False):
     return {"host_threads": pool_threads, "total_ms": float(m.group(1)) if m else None, "process_wall_s": wall}
 
 
+_abi_client_exe = None
+
+
+def abi_client():
+    """tests/abi_client.c compiled against this tree's library, once per bench process into a directory of its own (a client an earlier
+    build left behind would run that build's library through its rpath)."""
+    global _abi_client_exe
+    if _abi_client_exe is None:
+        import atexit
+        import shutil
+        import tempfile
+        d = tempfile.mkdtemp(prefix="mkp_abi_", dir=os.environ.get("MKP_BENCH_DIR", "/tmp"))
+        atexit.register(shutil.rmtree, d, True)
+        exe, lib_dir = os.path.join(d, "mkp_abi_client"), os.path.join(ROOT, "modkit_amd", "csrc")
+        subprocess.check_call(["gcc", "-O2", "-std=c99", "-D_POSIX_C_SOURCE=200809L", "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tests", "abi_client.c"),
+                               "-L", lib_dir, "-lmkpileup", "-lz", "-Wl,-rpath," + lib_dir])
+        _abi_client_exe = exe
+    return _abi_client_exe
+
+
 def seam_per_interval(bam, fa, out, thr, per_batch=None):
     """The seam a Rust maintainer would call: tests/abi_client.c drives mkp_shard_begin / add_records / run once per
     100 kb interval on the bench BAM; its own stderr line carries intervals, rows and the time inside the API calls."""
-    exe = os.path.join(os.environ.get("MKP_BENCH_DIR", "/tmp"), "mkp_abi_client")
-    lib_dir = os.path.join(ROOT, "modkit_amd", "csrc")
     try:
-        if not os.path.exists(exe):
-            subprocess.check_call(["gcc", "-O2", "-std=c99", "-D_POSIX_C_SOURCE=200809L", "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tests", "abi_client.c"),
-                                   "-L", lib_dir, "-lmkpileup", "-lz", "-Wl,-rpath," + lib_dir])
+        exe = abi_client()
         t0 = time.time()
         p = subprocess.run([exe, bam, fa, out, "cpg", repr(float(thr))] + (["100000", str(per_batch)] if per_batch else []), capture_output=True, text=True, timeout=600)
         wall = time.time() - t0
@@ -281,7 +328,14 @@ def main():
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl", help="nccl (= RCCL over xGMI, one GPU per rank) or gloo (tests: several ranks may share a GPU)")
     ap.add_argument("--no-full-data", action="store_true", help="c4 / chr1: skip the extra -f 1.0 run (and, with --cpu-whole, the oracle's)")
     ap.add_argument("--skip-e2e", action="store_true", help="profiling runs: skip the sharded end-to-end pass so that every kernel launch is the full-size one the timed region repeats")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the rows the last one produced as DIR/<column>.npy (float64; a fixed seeded sample above 64 MB)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if a.dump_outputs and a.workload == "hemi":
+        ap.error("--dump-outputs: a pileup-hemi re-launch leaves no rows to fetch (mkp_shard_rerun takes out = NULL on a hemi shard)")
+    if a.dump_outputs and a.gpus > 1:
+        ap.error("--dump-outputs is a single-GPU option (--gpus 1)")
     if a.skip_e2e or a.inner:
         a.no_cpu_baseline = True   # no sharded output to compare with
 
@@ -331,7 +385,7 @@ def main():
         n_reads = nr * world
         seed = {"c3": 20, "hemi": 30}.get(a.workload, 1)
         tag = "mkp_%s_L%d_N%d_x%d" % (a.workload, cl, nr, world)
-    prefix = os.path.join(tmp, "%s_seed%d" % (tag, seed))
+    prefix = os.path.join(tmp, "%s_seed%d_g%s" % (tag, seed, generator_digest()))
     t0 = time.time()
     if rank == 0:
         if not os.path.exists(os.path.join(ROOT, "tools", "gen_modbam")):
@@ -354,7 +408,7 @@ def main():
         return ctx.pileup_hemi_run([bam, "-o", out] + flags + extra) if hemi else ctx.pileup_run([bam, out] + flags + extra)
 
     out_bed = bam + ".device.bed"
-    extra_cfg, tiers = {}, {}
+    extra_cfg, tiers, dumped = {}, {}, None
     if multi:
         # ---- multi-shard workloads: K passes of the whole subcommand; device times are the library's HIP-event sums over the shards
         ctx = modkit_amd.Context(device=local_rank, tile_positions=a.tile)
@@ -362,21 +416,25 @@ def main():
         thr_h = [float(rep.threshold[i]) if rep.has_threshold[i] else 0.0 for i in range(4)]
         kms, walls = [], []
         for k in range(a.warmup + a.steps):
+            t_pass = time.perf_counter()
             r = run_subcommand(ctx, out_bed + ".rep", threshold_argv(thr_h))
             if k >= a.warmup:
-                kms.append(r.kernel_ms); walls.append(r.total_ms)
+                kms.append(r.kernel_ms); walls.append((time.perf_counter() - t_pass) * 1e3)
         if a.steps and sh256(out_bed + ".rep") != sh256(out_bed):
             raise SystemExit("repeat pass with explicit thresholds differs from the sampled run")
         st = ctx.stats()
-        ms_per_step = sum(kms) / max(1, len(kms))
+        kernel_ms = sum(kms) / max(1, len(kms))
+        ms_per_step = sum(walls) / max(1, len(walls))   # a timed step is one whole pass of the subcommand
         n_rows, total_positions, total_rows = int(rep.n_rows), float(rep.n_positions), float(rep.n_rows)
-        value = total_positions / (ms_per_step * 1e-3)
-        extra_cfg = {"genome_scale": a.genome_scale, "shards": int(rep.n_shards), "timing": "multi-shard workload: value = positions / device kernel time summed over the shards of one pass (HIP events inside the library, mean over the timed passes), NOT a wall-clock bracket; walls are in tiers.end_to_end",
-                     "pass_wall_ms_mean": sum(walls) / max(1, len(walls)), "kernel_ms_last_shard": {"decode": st.decode_kernel_ms, "pileup": st.pileup_kernel_ms, "gather": st.gather_kernel_ms}}
+        value = total_positions / (kernel_ms * 1e-3)
+        extra_cfg = {"genome_scale": a.genome_scale, "shards": int(rep.n_shards), "timing": "multi-shard workload: value = positions / device kernel time summed over the shards of one pass (HIP events inside the library, mean over the timed passes, kernel_ms_per_step), NOT a wall-clock bracket; ms_per_step = wall of one timed pass",
+                     "kernel_ms_per_step": kernel_ms, "pass_wall_ms_mean": ms_per_step, "kernel_ms_last_shard": {"decode": st.decode_kernel_ms, "pileup": st.pileup_kernel_ms, "gather": st.gather_kernel_ms}}
         if a.workload in ("c4", "chr1") and not a.no_full_data:   # the full-data percentile (-f 1.0) next to the default sampled threshold
             rf = run_subcommand(ctx, out_bed + ".f1", ["-f", "1.0"])
             extra_cfg["full_data_threshold_run"] = {"flag": "-f 1.0", "total_ms": rf.total_ms, "threshold_ms": rf.threshold_ms, "thresholds": {"ACGT"[i]: float(rf.threshold[i]) for i in range(4) if rf.has_threshold[i]}, "rows": int(rf.n_rows)}
-        rep1, elapsed = rep, ms_per_step * 1e-3 * a.steps
+        rep1, elapsed = rep, kernel_ms * 1e-3 * a.steps
+        if a.dump_outputs:
+            dumped = dump_outputs(a.dump_outputs, modkit_amd.read_bedmethyl(out_bed + ".rep"))   # the bedMethyl file of the last timed pass
         ctxs = [ctx]
     elif world == 1:
         ctx = modkit_amd.Context(device=local_rank, tile_positions=a.tile)
@@ -464,11 +522,14 @@ def main():
         # the rows the LAST timed re-launch left in HBM, fetched now (rerun(0): no further launch) and compared with the checked output: the
         # kernels the timed region ran are the kernels whose rows are bit-exact, on this very pass
         timed_rows_checked = None
+        timed_rows = [modkit_amd.rows_to_numpy(c.rerun(0, fetch=True)) for c in ctxs] if expected_row_digests is not None else None
+        if a.dump_outputs:
+            dumped = dump_outputs(a.dump_outputs, timed_rows[0])
         if os.environ.get("MKP_DEBUG_SKIP", "0") not in ("", "0"):
             timed_rows_checked = {"equal": None, "what": "skipped: MKP_DEBUG_SKIP ablation run of a -DMKP_DEBUG build (the kernels leave parts out on purpose)"}
-        elif expected_row_digests is not None and a.steps > 0:
-            for c, want in zip(ctxs, expected_row_digests):
-                got = modkit_amd.rows_digest(modkit_amd.rows_to_numpy(c.rerun(0, fetch=True)))
+        elif timed_rows is not None:
+            for rows, want in zip(timed_rows, expected_row_digests):
+                got = modkit_amd.rows_digest(rows)
                 if got != want:
                     raise SystemExit("rows of the last timed re-launch differ from the checked bedMethyl output (digest %s vs %s)" % (got, want))
             timed_rows_checked = {"equal": True, "contexts": len(ctxs), "sha256_of_row_columns": expected_row_digests[0],
@@ -552,7 +613,7 @@ def main():
             whole["what"] = "SURVEY §8(d) one-pass B_alg (reads + calls + 44 B rows, every byte counted once) over the driver-timed step"
         dev_ms = rep1.pack_ms + rep1.h2d_ms + rep1.kernel_ms + rep1.d2h_ms
         tiers.update({
-            "kernels_only": {"positions_per_s": value, "rows_per_s": total_rows * a.steps / elapsed if elapsed else 0.0, "ms": ms_per_step, "what": "timed region: K re-launches on the HBM-resident shard(s)"},
+            "kernels_only": {"positions_per_s": value, "rows_per_s": total_rows * a.steps / elapsed if elapsed else 0.0, "ms": elapsed / a.steps * 1e3, "what": "timed region: K re-launches on the HBM-resident shard(s)"},
             "device_pipeline": {"positions_per_s": rep1.n_positions / (dev_ms * 1e-3), "rows_per_s": rep1.n_rows / (dev_ms * 1e-3), "ms": dev_ms,
                                 "stages_ms": {"pack": rep1.pack_ms, "h2d": rep1.h2d_ms, "kernels": rep1.kernel_ms, "d2h": rep1.d2h_ms},
                                 "what": "rank 0: planner + uploads of the plan + kernels + D2H of rows for a pass whose reads the device ingest has already packed in HBM (the BAM side of the pass is tiers.end_to_end's ingest_wait)" + ("" if multi else ", one shard")},
@@ -585,7 +646,7 @@ def main():
                             "kernel_ms": {"decode": st.decode_kernel_ms, "pileup": st.pileup_kernel_ms, "rows": st.rows_kernel_ms, "gather": st.gather_kernel_ms},
                             "generator_s": gen_s, "arithmetic": "u32 tallies in LDS; f32 threshold caller (bit-exact vs the reference's f32)",
                             "parity": "bit-exact vs the restated CPU path (oracle/) on this BAM; the oracle is pinned on the reference's golden files; ties / >=3 codes / QC-fail / N ops are reference-unpinned and sample-probs has no reference pin (DESIGN.md §7)",
-                            "slowest_kernel": slowest_name, "timed_rows_checked": locals().get("timed_rows_checked"),
+                            "slowest_kernel": slowest_name, "timed_rows_checked": locals().get("timed_rows_checked"), "outputs_dumped": dumped,
                             "ingest": "device (compressed BGZF blocks up; inflate, record cut, MM/ML tokeniser and packing in HBM)" if not os.environ.get("MKP_HOST_INGEST") == "1" else "host",
                             "env_overrides": {k: v for k, v in sorted(os.environ.items()) if k.startswith("MKP_") and k != "MKP_BENCH_DIR"}}, **extra_cfg),
             "tiers": tiers,
