@@ -25,11 +25,13 @@ hipError_t mkp_launch_pileup(hipStream_t, uint32_t /*LDS bytes*/, int /*focus mo
                                  const MkpRowsDev*, uint32_t* /*row cursor*/,
                              uint32_t* /*tile row offsets*/, uint32_t* /*tile row counts*/, const uint32_t* /*chunk offsets*/,
                                  uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/);
-hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads: long | short*/, uint32_t, uint32_t, const MkpReadHdr*,
+hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_t, const void* /*call plane*/, const MkpReadHdr*,
     const uint32_t* /*cover read ids*/,
     uint32_t, const uint32_t*, const uint8_t*, const MkpTagRef*,
                             const uint32_t*, const uint8_t*, const MkpLayout*, const MkpFusedDesc*, const MkpRunParams*,
                                 const uint32_t* /*slot positions*/, uint8_t* /*feature stream*/, MkpVisit*, MkpEvent*, MkpReadOut*, uint32_t*);
+hipError_t mkp_launch_call_plane(hipStream_t, MkpWork*, uint32_t, const uint8_t* /*SEQ*/, const uint32_t* /*ranks*/, const MkpFusedDesc*,
+    void* /*call plane*/);
 hipError_t mkp_stream_set_lds(uint32_t bytes);
 hipError_t mkp_launch_dup_restore(hipStream_t, MkpReadHdr*, const MkpDupCons*, uint32_t);
 hipError_t mkp_launch_dup_events(hipStream_t, MkpReadHdr*, const uint32_t*, const uint8_t*, MkpEvent*, MkpReadOut*, MkpDupCons*, const MkpDupSeg*,
@@ -678,13 +680,12 @@ void make_resident(mkp_ctx* c) {
       }
       const uint32_t nf = c->n_class[0] + c->n_class[1];
       for (uint32_t k = 0; k < nf; k++) is_fused[class_list[k]] = 1;
-      // one list for both SPARSE classes, longest first; the reads of more than one base window (mkp_decode_slots_long) lead it
+      // one list for both SPARSE classes, longest first (the longest reads start first: they do not make the launch's tail)
       slot_ids.resize(nf);
       auto longer = [&](uint32_t x, uint32_t y) { return S.hdr[x].l_seq > S.hdr[y].l_seq; };
       std::merge(class_list.begin(), class_list.begin() + c->n_class[0], class_list.begin() + c->n_class[0], class_list.begin() + nf,
           slot_ids.begin(), longer);
-      uint32_t n_long = 0; while (n_long < nf && S.hdr[slot_ids[n_long]].l_seq > MKP_SLOT_WB) n_long++;
-      c->n_slot_class[0] = n_long; c->n_slot_class[1] = nf - n_long;
+      c->n_slot_class[0] = nf;
       c->read_ids_dec_off = nf; c->n_class[0] = dup_forced[0]; c->n_class[1] = dup_forced[1];
     }
     std::vector<uint32_t> rest; rest.reserve(n);
@@ -718,13 +719,16 @@ void make_resident(mkp_ctx* c) {
   c->d_readout.ensure(std::max<size_t>(2 * S.hdr.size(), 1) * sizeof(MkpReadOut));   // second half: second-group summaries of duplex reads
   c->d_misc.ensure(64);
   lap("upload: focus + event buffers");
+  // the fused reads' terms of the decoder's algorithmic bytes (below): what the SEQ sweep and rank marking read, what the plane lookups read
+  std::atomic<uint64_t> fused_swept{0}, fused_looked_up{0};
   if (stream) {
     if (!preplanned) upload(c->d_slot_pos, slot_pos_h);
     upload(c->d_stiles, stiles);
     {   // the fused decoder's work records, in launch order; the cover kernel keeps a read-id list
-      const uint32_t nf = c->n_slot_class[0] + c->n_slot_class[1];
+      const uint32_t nf = c->n_slot_class[0];
       std::vector<MkpWork> work(nf);
       host_parallel(nf, 8192, [&](size_t lo, size_t hi) {
+        uint64_t swept = 0, looked_up = 0;
         for (size_t k = lo; k < hi; k++) {
           const MkpReadHdr& h = S.hdr[slot_ids[k]]; MkpWork& w = work[k]; memset(&w, 0, sizeof(w));
           w.ref_start = h.ref_start; w.l_seq = h.l_seq; w.n_cigar = h.n_cigar; w.cigar_off = h.cigar_off; w.seq_off = h.seq_off; w.flags = h.flags;
@@ -734,13 +738,26 @@ void make_resident(mkp_ctx* c) {
           if (!(h.flags & MKP_RF_BAD) && h.n_tags) { const MkpTagRef& t0 = S.tagref[h.tag_off]; w.rank_off = t0.rank_off; w.n_calls = t0.n;
             w.ml_off0 = t0.ml_off;
               if (h.n_tags > 1) w.ml_off1 = S.tagref[h.tag_off + 1].ml_off; }
+          uint64_t n_rk = 0; if (!(h.flags & MKP_RF_BAD)) for (uint32_t t = 0; t < h.n_tags; t++) n_rk += S.tagref[h.tag_off + t].n;
+          swept += (h.l_seq + 1) / 2 + 2ull * n_rk;
+          looked_up += std::min<uint64_t>((h.l_seq + 1) / 2, h.n_sl) + (n_rk ? 8ull * std::min<uint64_t>(MKP_PLANE_WORDS(h.l_seq), h.n_sl) : 0);
         }
+        fused_swept += swept; fused_looked_up += looked_up;
       });
+      // the call plane: MKP_PLANE_WORDS(l_seq) 8-byte entries per fused read, in launch order
+      uint64_t pw = 0;
+      for (uint32_t k = 0; k < nf; k++) { if (pw > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "shard exceeds 2^32 call-plane words; use smaller shards");
+        work[k].pad = (uint32_t)pw; pw += MKP_PLANE_WORDS(work[k].l_seq); }
+      c->plane_bytes = pw * 8;
+      c->d_plane.ensure(std::max<uint64_t>(c->plane_bytes, 16));
       upload(c->d_work, work);
       std::vector<uint32_t> cover(slot_ids.begin() + nf, slot_ids.end()); upload(c->d_slot_ids, cover);
     }
     { std::vector<MkpFusedDesc> fd(c->tables.dev.size()); for (size_t i = 0; i < fd.size(); i++) fd[i] = fused_desc(c->tables.dev[i]);
       upload(c->d_fdesc, fd); }
+    // once per resident shard (a re-launch on the shard reuses it): counted in the upload step
+    hip_check(mkp_launch_call_plane(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], c->d_seq.as<uint8_t>(), c->d_ranks.as<uint32_t>(),
+        c->d_fdesc.as<MkpFusedDesc>(), c->d_plane.p), "call plane launch");
     c->d_cov.ensure(c->cov_bytes + 256); c->d_visits.ensure(std::max<size_t>(S.hdr.size(), 1) * sizeof(MkpVisit));
     hip_check(mkp_stream_set_lds(c->lds_bytes), "hipFuncSetAttribute(max dynamic LDS, stream)");
   }
@@ -769,6 +786,9 @@ void make_resident(mkp_ctx* c) {
     uint64_t n_rs = 0; for (auto& h : S.hdr) n_rs += h.n_sl;
     c->stats.stream_bytes = n_rs;
     c->stats.alg_bytes_decode += 4ull * n_rs + n_rs + 32ull * S.hdr.size();
+    // the fused decoder reads neither a read's whole SEQ nor its rank list: the SEQ byte and the call-plane entry under each slot (the
+    // plane, resolved from SEQ and ranks once per resident shard, is not part of the pass)
+    c->stats.alg_bytes_decode = c->stats.alg_bytes_decode - fused_swept.load() + fused_looked_up.load();
     c->stats.alg_bytes_pileup = n_rs + 32ull * S.hdr.size();               // + 44*rows added after the run
     c->stats.alg_bytes_agg_survey = 8ull * n_rs;                            // 8 B per coverage event at a candidate position (+ call events, + 44*rows)
   }
@@ -830,7 +850,7 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
         c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>(),
                                                        c->d_dupcons.as<MkpDupCons>(), c->d_dupsegs.as<MkpDupSeg>(), c->n_dup_cons, misc + 2),
                                                            "dup events launch");
-    if (c->slot_mode) hip_check(mkp_launch_slots(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], c->n_slot_class[1],
+    if (c->slot_mode) hip_check(mkp_launch_slots(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], c->d_plane.p,
         c->d_hdr.as<MkpReadHdr>(),
         c->d_slot_ids.as<uint32_t>(), c->n_slot_class[2],
                                               c->d_cigar.as<uint32_t>(), c->d_seq.as<uint8_t>(), c->d_tagref.as<MkpTagRef>(),
@@ -1030,7 +1050,7 @@ void mkp_ctx_destroy(mkp_ctx* c) {
       &c->d_focus, &c->d_combos, &c->d_tiles,
                     &c->d_slotbm, &c->d_prm, &c->d_read_ids, &c->d_chunk, &c->d_store, &c->d_hist0, &c->d_hist1, &c->d_sample_cursor, &c->d_take,
                         &c->d_tile_row_off, &c->d_tile_row_cnt, &c->d_tile_dst, &c->d_misc, &c->d_rows_src, &c->d_rows_dst, &c->d_hemi_iv,
-                        &c->d_slot_pos, &c->d_cov, &c->d_visits, &c->d_stiles, &c->d_slot_ids, &c->d_fdesc, &c->d_work, &c->d_zin, &c->d_zout,
+                        &c->d_slot_pos, &c->d_cov, &c->d_visits, &c->d_stiles, &c->d_slot_ids, &c->d_fdesc, &c->d_work, &c->d_plane, &c->d_zin, &c->d_zout,
                         &c->d_zblk, &c->d_zstat, &c->d_summary, &c->d_bedmask, &c->d_hist64}) b->release();
   mkp_internal_ingest_destroy(c->ingest); c->ingest = nullptr;
   c->h_rows.release();

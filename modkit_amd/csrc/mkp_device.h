@@ -18,6 +18,7 @@
 //   uint32      slotbm[]            focus runs only: one bit per reference position of the window (+64 positions of margin each
 //                                   side), set where the position is in focus — the positions that get a tally column ("slot")
 //   MkpRowsDev  rows                SoA row buffers (per tile, then gathered into genome order)
+//   uint2       plane[]             slot pipeline: the call plane of the fused reads (MKP_PLANE_WORDS below), built once per resident shard
 #pragma once
 #include <stdint.h>
 
@@ -55,6 +56,7 @@ struct MkpReadHdr {
 #define MKP_RF_REVERSE 1u
 #define MKP_RF_BAD 2u
 #define MKP_RF_SUMERR 4u   // host planner: some call's probabilities over the read's two tags add up to more than 1.01 (combine_checked, mod_bam.rs:629-656)
+#define MKP_RF_RUNOVER 8u  // mkp_call_plane (work records only): the delta list runs past the last occurrence of its base (mod_bam.rs:705-727)
 #define MKP_RF_KEY_SHIFT 8
 #define MKP_NO_KEY_FILTER 0xffffffffu
 
@@ -190,12 +192,10 @@ struct MkpTile { int32_t r0, r1; uint32_t first, last; };
 // stream into LDS tallies.  Feature byte = what FeatureVector::add_feature receives for this alignment at this column
 // (pileup/mod.rs:783-939): [0:4] counter id (MKP_C_*), [5] tally strand, [6:7] the read base as tallied (so that a call of a
 // record that later fails can be counted as NoCall(base)).
-#ifndef MKP_SLOT_WB
-// mkp_decode_slots*: stored bases per base window; longer reads take the *_long instances.  13 312 bases = 5 052 bytes of LDS per wave: eight
-// 4-wave workgroups per CU (16 384: six), which — together with the 80-SGPR cap of the short-read kernel, see mkp_slots.hip — is what lets the
-// hardware keep eight waves per SIMD resident (round 6: 0.75 -> 0.70 ms on C3)
-#define MKP_SLOT_WB 13312u
-#endif
+// mkp_decode_slots reads whether a call is listed at a stored base from the CALL PLANE (mkp_call_plane, built once when the shard becomes
+// resident): per fused read and 32 stored bases one uint2 {bit b = "a listed call of the read sits at base 32 w + b", listed calls at the
+// bases before 32 w} — two bits per base, stored order; the read's plane starts at plane[MkpWork.pad]
+#define MKP_PLANE_WORDS(l_seq) (((l_seq) + 31u) >> 5)
 #define MKP_STREAM_ROWMAP_WORDS 2048u   // mkp_pileup_stream: rows of a tile placed per emission round (a dword of LDS each)
 #define MKP_FB_NONE 0xffu    // the read is not in this column (ref-skip)
 #define MKP_FB_BLANK 0xfeu   // in the column, no feature (non-ACGT base: pileup/mod.rs:864-874)
@@ -233,7 +233,7 @@ struct MkpWork {             // 64 B
   int32_t ref_start; uint32_t l_seq, n_cigar, cigar_off, seq_off, flags, gs0, n_sl, cov_off;
   uint16_t n_tags, layout;
   uint32_t rank_off, n_calls, ml_off0, ml_off1;   // the shared rank list, the tags' ML bytes
-  uint32_t rid, pad;
+  uint32_t rid, pad;                              // pad: the read's first call-plane entry (MKP_PLANE_WORDS(l_seq) of them)
 };
 // Records that share a read NAME inside one interval of the reference's grid (unmarked duplicates, mates, split reads that kept the primary flag).
 // The reference keeps ONE cache entry per name and interval (ReadCache, read_cache.rs:24-43): the record asked about first — the first focus

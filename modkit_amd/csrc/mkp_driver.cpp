@@ -872,8 +872,9 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
       hbm_budget = (uint64_t)((double)tot * 0.55); }
   }
   // packed arrays of a shard ~ 1.9 x its compressed blocks on ONT-like data (SEQ nibbles + CIGAR words + 5 bytes per call; names and
-  // qualities are not kept), the inflated window of the ingest object in flight on top: 2.5 x as the estimate
-  auto est_of = [](uint64_t comp_bytes) { return comp_bytes * 5 / 2 + (64ull << 20); };
+  // qualities are not kept), the inflated window of the ingest object in flight on top: 2.5 x; and once the shard is resident, the slot
+  // decoder's call plane (two bits per stored base = half the SEQ nibbles, ~0.5 x): 3 x as the estimate
+  auto est_of = [](uint64_t comp_bytes) { return comp_bytes * 3 + (64ull << 20); };
   auto start_ahead = [&]() {
     if (ahead.empty() || !aworkers.empty()) return;
     ahead_est_total = 0; for (auto& A : ahead) { A.est = est_of(A.bytes); ahead_est_total += A.est; }

@@ -3,15 +3,15 @@
 // the host numbers the window's slots in genome order (slot_pos[g] = position of global slot g) and gives every read the slot
 // range [gs0, gs0 + n_sl) of its reference span.  One device pass:
 //
-//   mkp_decode_slots[_long]  one wave per read, reads whose MM tags form one explicit-mode ('?') group with one shared delta list
+//   mkp_call_plane        once per resident shard: per fused read, one bit per stored base "a listed call sits here" and the number
+//                         of listed calls before every 32 bases (the rank list resolved against the SEQ: it does not depend on the pass)
+//   mkp_decode_slots      one wave per read, reads whose MM tags form one explicit-mode ('?') group with one shared delta list
 //                         (`C+m?`, `C+hm?`, `C+h?;C+m?` as basecallers write them), no edge filter.  The walk is driven by the
-//                         read's SLOTS, not by its calls: the SEQ is swept once into LDS (a flag bit per base "is the fundamental
-//                         base" + a running count per 32 bases), the delta list is marked into a bitmap over the base's
-//                         occurrences, and then, 64 slots per step: CIGAR (128-op register window, reference -> query), the base,
-//                         its occurrence number (2 LDS reads), whether that occurrence is listed and as which call (2 LDS reads),
+//                         read's SLOTS, not by its calls, 64 slots per step: CIGAR (128-op register window, reference -> query), the
+//                         base, whether a call is listed there and as which call (one 8-byte call-plane gather beside the SEQ byte),
 //                         ML -> f32 probabilities -> MultipleThresholdModCaller::call, and ONE FEATURE BYTE per slot goes to the
 //                         read's run of the feature stream.  Calls on non-focus positions are never located (their rows would be
-//                         dropped, pileup/mod.rs:570-604); SEQ and CIGAR are read once per pass.
+//                         dropped, pileup/mod.rs:570-604); CIGAR is read once per pass, SEQ and the plane only under the slots.
 //   mkp_cover_reads       every other read (implicit-mode / multi-group / duplex / `N` tags / failed tags, or any read when an edge
 //                         filter is set): the decode kernels of mkp_kernels.hip leave position-sorted call events; this kernel walks
 //                         the read's slots (coverage features) and merges the events into the stream.
@@ -27,16 +27,9 @@
 #include "mkp_dev_common.hpp"
 #include "mkp_dev_rows.hpp"
 
-#define SL_WB MKP_SLOT_WB      // stored bases per base window of the fused decoder
-#define SL_FW (SL_WB / 32u)    // words of the window's flag bitmaps
-
-// per-wave LDS of mkp_decode_slots*: F = "base is the fundamental base" (bit = nibble index inside the dword, dword k of a word at
-// bits 8k..), P = occurrences before the word (inside the window), B = "occurrence is listed" over the window's occurrences,
-// WP = listed occurrences before the B word
-// ck_* = the read's caller constants per code (integer pass threshold, offset and stride of its ML bytes, counter of Modified(code)):
-// uniform, but the kernel is short of
-// scalar registers — every lane reads them back as vectors once per slot batch
-struct SlotLds { int32_t ck_thr[4]; uint32_t ck_off[4]; uint32_t ck_str[4]; uint32_t ck_cid[4]; uint32_t F[SL_FW]; uint32_t B[SL_FW + 2]; uint16_t P[SL_FW]; uint16_t WP[SL_FW + 2]; };
+// per-wave LDS of mkp_decode_slots: the read's caller constants per code (integer pass threshold, offset and stride of its ML bytes,
+// counter of Modified(code)) — uniform, but the kernel is short of scalar registers: every lane reads them back as vectors once per slot batch
+struct SlotLds { int32_t ck_thr[4]; uint32_t ck_off[4]; uint32_t ck_str[4]; uint32_t ck_cid[4]; };
 
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
@@ -218,24 +211,115 @@ __device__ __forceinline__ uint32_t cover_feature(uint32_t kind, uint32_t nib, u
 }
 
 // ----------------------------------------------------------------------------------------------------------------------
+// mkp_call_plane: the call plane of the fused reads (MKP_PLANE_WORDS in mkp_device.h), built once when the shard becomes resident — what
+// it answers (is a listed call at this stored base, and which one) depends on the SEQ, the rank list, the strand and the tag's fundamental
+// base only, never on the pass.  One wave per work record:
+//   1. occurrences of the fundamental base in the stored read (four 16-byte SEQ loads per lane at a time) -> tot; a delta list whose
+//      last entry is not below tot runs past the base's last occurrence (mod_bam.rs:705-727): MKP_RF_RUNOVER in the work record, no plane;
+//   2. 64 plane words (2 048 bases) per step: the words' flag bitmaps and their occurrence counts (a wave scan), then the rank list's
+//      entries that fall on the step's occurrences, in stored order (a reverse read's forward rank e is stored ordinal tot - 1 - e: its list
+//      is consumed from the end), each placed on its word (a search over the lanes' counts) and its bit (the (o - count)-th flag of the
+//      word); the word's listed calls before it are the running count plus a wave scan.
+// Reference: DeltaListConverter::new / to_positions (mod_bam.rs:667-733).
+extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __restrict__ work, uint32_t n_reads, const uint8_t* __restrict__ seqs,
+    const uint32_t* __restrict__ ranks, const MkpFusedDesc* __restrict__ fdesc, uint2* __restrict__ plane) {
+  __shared__ uint32_t bm_all[4][64];
+  const int lane = lane_id();
+  const uint32_t wib = rfl(threadIdx.x >> 6);
+  const uint32_t widx = rfl(blockIdx.x * (blockDim.x >> 6)) + wib;
+  if (widx >= n_reads) return;
+  const MkpWork h = work[widx];
+  const uint32_t t_n = h.n_calls;
+  if ((h.flags & MKP_RF_BAD) || h.n_tags == 0 || t_n == 0) return;   // no calls: the decoder never reads the plane
+  uint32_t* __restrict__ bm = bm_all[wib];
+  const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
+  const uint32_t L = h.l_seq, nd = (L + 7u) >> 3, nw = MKP_PLANE_WORDS(L);
+  const uint8_t* __restrict__ seqb = seqs + h.seq_off;
+  const uint32_t* __restrict__ rk = ranks + h.rank_off;
+  const uint32_t fb = fdesc[h.layout].misc & 3u;
+  const uint32_t pat = 0x11111111u << (rev ? 3u - fb : fb);   // the stored base the tags count (its BAM code in every nibble)
+  const uint32_t e_last = rk[t_n - 1u];
+  // flag bitmap of plane word w: bit b = stored base 32 w + b is the base (base 2j of a SEQ byte is its high nibble); bases at or past L
+  // (the pad nibble of an odd L, the zero padding) are cleared
+  auto word_flags = [&](uint32_t w) {
+    const uint32_t d = 4u * w;
+    uint4 x = ldo<uint4>(seqb, 4u * min(d, nd - 1u));   // (clamped to the read's last dword: the SEQ buffer has slack behind the last read)
+    if (d + 1u >= nd) x.y = 0u; if (d + 2u >= nd) x.z = 0u; if (d + 3u >= nd) x.w = 0u; if (d >= nd) x.x = 0u;
+    const uint32_t xw[4] = {x.x, x.y, x.z, x.w};
+    uint32_t f = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const uint32_t g = gather8(nib_eq(xw[k], pat)); f |= (((g & 0x55u) << 1) | ((g >> 1) & 0x55u)) << (8 * k); }
+    const uint32_t b0 = 32u * w;
+    return b0 >= L ? 0u : L - b0 >= 32u ? f : f & ((1u << (L - b0)) - 1u);
+  };
+  uint32_t acc = 0;
+  for (uint32_t w0 = 0; w0 < nw; w0 += 256u) {
+    uint32_t f[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { const uint32_t w = w0 + 64u * (uint32_t)j + (uint32_t)lane; f[j] = w < nw ? word_flags(w) : 0u; }
+#pragma unroll
+    for (int j = 0; j < 4; j++) acc += (uint32_t)__popc(f[j]);
+  }
+  const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(acc), 63);
+  if (rfl(e_last) >= tot) { if (lane == 0) work[widx].flags = h.flags | MKP_RF_RUNOVER; return; }
+  uint2* __restrict__ pl = plane + h.pad;
+  uint32_t occ = 0, j = 0;   // occurrences before the step, listed calls before the step (both stored order)
+  for (uint32_t w0 = 0; w0 < nw; w0 += 64u) {
+    const uint32_t w = w0 + (uint32_t)lane;
+    const uint32_t f = w < nw ? word_flags(w) : 0u, c = (uint32_t)__popc(f);
+    const uint32_t incl = wave_incl_scan(c), cnt = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    const uint32_t j0 = j;
+    bm[lane] = 0u;
+    wave_lds_fence();
+    for (;;) {
+      const uint32_t i = j + (uint32_t)lane;
+      const bool valid = i < t_n;
+      const uint32_t e = valid ? ldo<uint32_t>(rk, 4u * (rev ? t_n - 1u - i : i)) : 0u;
+      const uint32_t rel = (rev ? tot - 1u - e : e) - occ;   // (entries below the step were consumed by the steps before)
+      const bool hit = valid && rel < cnt;
+      const uint32_t rq = hit ? rel : 0u;
+      // the word: the number of lanes whose inclusive count is <= rel (six probes)
+      uint32_t probe = 31u << 2;
+#pragma unroll
+      for (int hstep = 16; hstep >= 1; hstep >>= 1) {
+        const uint32_t vv = (uint32_t)__builtin_amdgcn_ds_bpermute((int)probe, (int)incl);
+        probe = vv <= rq ? probe + 4u * (uint32_t)hstep : probe - 4u * (uint32_t)hstep;
+      }
+      { const uint32_t vv = (uint32_t)__builtin_amdgcn_ds_bpermute((int)probe, (int)incl); probe = vv <= rq ? probe + 4u : probe; }
+      const int oa = (int)(probe & 255u);
+      const uint32_t fo = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)f), io = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)incl);
+      // the bit: the n-th flag of the word (halving select)
+      uint32_t n = rq - (io - (uint32_t)__popc(fo)), pos = 0;
+#pragma unroll
+      for (int s = 16; s >= 1; s >>= 1) {
+        const uint32_t lo = (uint32_t)__popc((fo >> pos) & ((1u << s) - 1u));
+        if (n >= lo) { n -= lo; pos += (uint32_t)s; }
+      }
+      if (hit) atomicOr(&bm[probe >> 2], 1u << pos);
+      const uint32_t nh = (uint32_t)__popcll(__ballot(hit));
+      j += nh;
+      if (nh < 64u) break;
+    }
+    wave_lds_fence();
+    const uint32_t lw = bm[lane], lc = (uint32_t)__popc(lw), li = wave_incl_scan(lc);
+    if (w < nw) pl[w] = make_uint2(lw, j0 + li - lc);
+    occ += cnt;
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------------------------
 // mkp_decode_slots: MM/ML decode + threshold caller + coverage, slot-driven (see the head of the file).
 // Reference: DeltaListConverter (mod_bam.rs:667-733), get_base_mod_probs (1213-1295), combine_checked (629-656),
 // into_collapsed (530-627), MultipleThresholdModCaller::call (threshold_mod_caller.rs:28-63), ReadCache::add_record
 // (read_cache.rs:111-211), get_aligned_pairs_forward (util.rs:122-145), process_region's alignment loop (pileup/mod.rs:783-939).
-// One wave runs one read start to end, so what bounds the kernel is the chain of dependent memory round trips per read, not
-// instruction issue: everything that depends only on the header (first slots, first CIGAR window, the first 8192 bases) is
-// requested before the layout tables are looked at and the sweep issues four 16-byte loads per lane at a time.  Measured (SQ
-// counters, C3): the kernel is VALU-issue bound (~80 % of the SIMD cycles), so the per-base and per-slot instruction counts matter:
-// three VALU per SEQ dword for the flags, one popcount per 32 bases, the caller resolved to a fixed walk per read.
-// MULTI = false: reads of at most SL_WB bases — one base window, swept before the slot loop, and a straight-line slot step;
-// MULTI = true: longer reads — the windows are swept as the slots reach them.  (Two instances: the window-advance code inside the
-// slot loop costs the short-read kernel registers it never uses, and uniform values that do not fit the SGPR file are spilled to
-// VGPR lanes — VALU instructions in a VALU-bound kernel.)
+// One wave runs one read start to end.  Measured (SQ counters, C3): the kernel is VALU-issue bound, so the per-slot instruction count
+// matters: the rank list was resolved into the call plane when the shard became resident (mkp_call_plane), so that a slot learns whether a
+// call is listed at its base, and as which call, from one 8-byte gather issued beside its SEQ byte and a popcount; the caller is resolved to
+// a fixed walk per read.  No per-read LDS beyond the caller constants and no base windows: reads of every length take the same code.
 #define FUSED_PARAMS(PRM) const MkpWork* __restrict__ work, uint32_t n_reads, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ seqs, \
-    const uint32_t* __restrict__ ranks, const uint8_t* __restrict__ ml, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const uint32_t* __restrict__ slot_pos, \
+    const uint2* __restrict__ plane, const uint8_t* __restrict__ ml, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const uint32_t* __restrict__ slot_pos, \
     uint8_t* __restrict__ cov, MkpVisit* __restrict__ visits, MkpReadOut* __restrict__ readout
-#define FUSED_PASS work, n_reads, cigar, seqs, ranks, ml, fdesc, prm, slot_pos, cov, visits, readout
-template <bool MULTI>
+#define FUSED_PASS work, n_reads, cigar, seqs, plane, ml, fdesc, prm, slot_pos, cov, visits, readout
 __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParams&), SlotLds* __restrict__ lds_all) {
   const int lane = lane_id();
   const uint32_t wib = rfl(threadIdx.x >> 6);
@@ -245,31 +329,19 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   SlotLds& W = lds_all[wib];
   const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
   const uint32_t aln = rev ? 1u : 0u;
-  const uint32_t L = h.l_seq, nd = (L + 7u) >> 3;
-  const uint8_t* __restrict__ seqb = seqs + h.seq_off;   // reads start 4-byte aligned, zero-padded to a dword
+  const uint32_t L = h.l_seq;
+  const uint8_t* __restrict__ seqb = seqs + h.seq_off;
+  const uint2* __restrict__ pl = plane + h.pad;
   const uint32_t* __restrict__ cg = cigar + h.cigar_off;
   bool have_calls = !(h.flags & MKP_RF_BAD) && h.n_tags != 0;
-  // combine_checked's sum test (mod_bam.rs:629-656) — two tags on one base: the probabilities of a call add up to more than 1.01 —
-  // is made by the host planner over the ML bytes (the f32 sums are exact multiples of 1/512: an integer comparison)
-  const bool err_sum = (h.flags & MKP_RF_SUMERR) != 0;
+  // combine_checked's sum test (mod_bam.rs:629-656) — two tags on one base: the probabilities of a call add up to more than 1.01 — is
+  // made by the host planner over the ML bytes (the f32 sums are exact multiples of 1/512: an integer comparison); a delta list that runs
+  // past the last occurrence of its base (mod_bam.rs:705-727) by mkp_call_plane
+  const bool err_rec = (h.flags & (MKP_RF_SUMERR | MKP_RF_RUNOVER)) != 0;
   const uint32_t n_sl = h.n_sl;
   const uint32_t* __restrict__ spos = slot_pos + h.gs0;
-
-  // ---- requests that depend on the header alone (per-read bases are uniform: scalar base + 32-bit lane offset)
-  // 16 bytes of SEQ at dword d.  The address is clamped to the read's last dword (the SEQ buffer has slack behind the last read)
-  // and dwords past the read come back as zero: no divergent tail path.
-  auto load4 = [&](uint32_t d) {
-    uint4 x = ldo<uint4>(seqb, 4u * min(d, nd - 1u));
-    if (__any(d + 4u > nd)) { if (d >= nd) x.x = 0u; if (d + 1u >= nd) x.y = 0u; if (d + 2u >= nd) x.z = 0u; if (d + 3u >= nd) x.w = 0u; }
-    return x;
-  };
   uint32_t p_next = (uint32_t)lane < n_sl ? ldo<uint32_t>(spos, 4u * (uint32_t)lane) : 0u;
   RefWinS rw; refwin_s_init(rw, cg, h.n_cigar, h.ref_start);
-  uint4 xpre[4];   // stored bases [0, 8192): a 16-byte vector per lane and 2048 bases
-#pragma unroll
-  for (int j = 0; j < 4; j++) xpre[j] = (have_calls && 2048u * (uint32_t)j < L) ? load4(4u * (64u * (uint32_t)j + (uint32_t)lane)) : make_uint4(0u,
-      0u, 0u, 0u);
-  const uint32_t pad_nib = (L & 1u) ? ((uint32_t)seqb[L >> 1] & 15u) : 0u;   // the low nibble of the last byte is not a base when L is odd
 
   // ---- the read's one (mod strand, base) group.  The caller's walk over a call's map in iteration order is resolved once per
   // layout by the host (MkpFusedDesc: one scalar load): where the ML byte of the i-th code sits (tag + index: offset and stride
@@ -281,16 +353,8 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   // where the ML byte of the i-th code of call j sits: ml[W.ck_off[i] + j * W.ck_str[i]] (tag + index inside the tag: offset and stride)
   uint32_t mlx_o = 0, mlx_s = 0;
   uint32_t t_n = 0;
-  uint32_t e_pre = 0, e_last = 0;   // the first 64 entries of the rank list as the first window consumes it, and its last entry
-  const uint32_t* __restrict__ rk = ranks;
   if (have_calls) {
     t_n = h.n_calls;
-    rk = ranks + h.rank_off;
-    if (t_n) {
-      const uint32_t i = rev ? t_n - 64u + (uint32_t)lane : (uint32_t)lane;
-      e_pre = ((int32_t)i >= 0 && i < t_n) ? ldo<uint32_t>(rk, 4u * i) : (rev ? 0u : 0xffffffffu);
-      e_last = rk[t_n - 1u];
-    }
     const MkpFusedDesc fd = fdesc[h.layout];
     fmisc = fd.misc; i_can = fd.i_can;
     if (lane < MKP_KMAX) {
@@ -309,124 +373,15 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   const uint32_t sg0u = (fmisc >> 2) & 1u, n_post = (fmisc >> 3) & 7u;
   const bool int_caller = (fmisc >> (collapse ? 7 : 6)) & 1u;     // the exact integer form of the caller applies (fused_desc)
   const uint32_t red_shift = (f_col >> 5) & 3u;                   // log2 of the number of codes a collapsed code's probability is shared among
-  const uint32_t xs = rev ? 3u - (fmisc & 3u) : (fmisc & 3u);     // the stored base the tags count
-  bool err = have_calls && err_sum;
-  const uint32_t pat = 0x11111111u << xs;
-  const bool pad_hit = (L & 1u) && pad_nib == (1u << xs);
-
-  // ---- base windows: stored bases [w0, w0 + SL_WB) swept into F / P.
-  // F word = 32 bases = 4 SEQ dwords: the flag of nibble n of dword k sits at bit 4n + 3 - k (base 2j of a dword is nibble 2j+1).
-  uint32_t w0 = 0, cntW = 0, cum = 0, tot = 0, t_cur = 0, t_base = 0;
-  bool bw_loaded = false, first_mark = true;
-  auto flags4 = [&](const uint4& x) {   // "nibble != base" lands on bit 3 of the nibble after two shift-ors; the four dwords interleave
-    uint32_t n0 = x.x ^ pat, n1 = x.y ^ pat, n2 = x.z ^ pat, n3 = x.w ^ pat;
-    n0 |= n0 << 1; n1 |= n1 << 1; n2 |= n2 << 1; n3 |= n3 << 1;
-    n0 |= n0 << 2; n1 |= n1 << 2; n2 |= n2 << 2; n3 |= n3 << 2;
-    const uint32_t a = (n0 & 0x88888888u) | ((n1 >> 1) & ~0x88888888u), b = ((n2 >> 2) & 0x22222222u) | ((n3 >> 3) & ~0x22222222u);
-    return ~((a & 0xccccccccu) | (b & ~0xccccccccu));
-  };
-  auto sweep = [&]() {   // F, P, cntW of the window at w0; four vectors per lane (8192 bases) in flight at a time
-    const uint32_t nwords = min(SL_FW, (L - w0 + 31u) >> 5);
-    const uint32_t dbase = w0 >> 3;
-    uint32_t carry = 0;
-    if (MULTI) wave_lds_fence();   // the previous window's readers are done (same wave)
-    for (uint32_t i0 = 0; i0 < nwords; i0 += 256) {
-      uint4* x = xpre;   // (the vectors requested at the top serve the first 8192 bases)
-      if (!(w0 == 0 && i0 == 0)) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) x[j] = (i0 + 64u * (uint32_t)j < nwords) ? load4(dbase + 4u * (i0 + 64u * (uint32_t)j + (uint32_t)lane))
-            : make_uint4(0u, 0u, 0u, 0u);
-      }
-#pragma unroll
-      // two vectors per prefix sum: a word holds at most 32 occurrences, 64 words 2 048 — both running counts fit 16 bits
-      for (int jp = 0; jp < 4; jp += 2) {
-        if (i0 + 64u * (uint32_t)jp < nwords) {
-          const bool has1 = i0 + 64u * (uint32_t)(jp + 1) < nwords;   // (uniform)
-          const uint32_t wi0 = i0 + 64u * (uint32_t)jp + (uint32_t)lane, wi1 = wi0 + 64u;
-          // (a window of 416 words ends inside a vector: the words behind it belong to the next window)
-          const uint32_t Fw0 = flags4(x[jp]), c0 = wi0 < nwords ? (uint32_t)__popc(Fw0) : 0u;
-          uint32_t Fw1 = 0, c1 = 0;
-          if (has1) { Fw1 = flags4(x[jp + 1]); c1 = wi1 < nwords ? (uint32_t)__popc(Fw1) : 0u; }
-          const uint32_t sc = wave_incl_scan(c0 | (c1 << 16));
-          const uint32_t tot01 = (uint32_t)__builtin_amdgcn_readlane((int)sc, 63), tot0 = tot01 & 0xffffu;
-          if (wi0 < nwords) { W.F[wi0] = Fw0; W.P[wi0] = (uint16_t)(carry + (sc & 0xffffu) - c0); }
-          if (has1 && wi1 < nwords) { W.F[wi1] = Fw1; W.P[wi1] = (uint16_t)(carry + tot0 + (sc >> 16) - c1); }
-          carry += tot0 + (tot01 >> 16);
-        }
-      }
-    }
-    wave_lds_fence();
-    if (pad_hit && L - w0 < (nwords << 5)) {   // the pad nibble matched: take its flag back (it lies behind every base)
-      const uint32_t qr = L - w0;
-      if (lane == 0) W.F[qr >> 5] &= ~(1u << (4u * ((qr & 7u) ^ 1u) + 3u - ((qr >> 3) & 3u)));
-      carry -= 1u;
-      wave_lds_fence();
-    }
-    cntW = carry; bw_loaded = true;
-  };
-  auto mark = [&]() {   // B, WP of the window: the listed ranks among its occurrences (stored-order ordinals cum .. cum + cntW)
-    const uint32_t nbw = (cntW + 31u) >> 5;
-    for (uint32_t k = (uint32_t)lane; k < nbw + 1u; k += 64) W.B[k] = 0;
-    wave_lds_fence();
-    t_base = t_cur;
-    if (!rev) {
-      const uint32_t whi = cum + cntW;
-      for (;;) {
-        const uint32_t i = t_cur + (uint32_t)lane; const bool valid = i < t_n;
-        const uint32_t e = first_mark ? e_pre : (valid ? ldo<uint32_t>(rk, 4u * i) : 0xffffffffu);
-        first_mark = false;
-        const bool hit = valid && e < whi;
-        const uint32_t o = e - cum;
-        if (hit) atomicOr(&W.B[o >> 5], 1u << (o & 31u));
-        const uint32_t nh = (uint32_t)__popcll(__ballot(hit));
-        t_cur += nh;
-        if (nh < 64u) break;
-      }
-    } else {   // forward rank of a stored ordinal o: tot - 1 - o; the list is consumed from its end
-      const uint32_t wlo = tot - cum - cntW;
-      for (;;) {
-        const uint32_t i = t_cur - 64u + (uint32_t)lane; const bool valid = (int32_t)i >= 0 && i < t_cur;
-        const uint32_t e = first_mark ? e_pre : (valid ? ldo<uint32_t>(rk, 4u * i) : 0u);
-        first_mark = false;
-        const bool hit = valid && e >= wlo;
-        const uint32_t o = (tot - 1u - e) - cum;
-        if (hit) atomicOr(&W.B[o >> 5], 1u << (o & 31u));
-        const uint32_t nh = (uint32_t)__popcll(__ballot(hit));
-        t_cur -= nh;
-        if (nh < 64u) break;
-      }
-    }
-    wave_lds_fence();
-    uint32_t carry = 0;
-    for (uint32_t k0 = 0; k0 < nbw; k0 += 64) {
-      const uint32_t k = k0 + (uint32_t)lane;
-      const uint32_t c = k < nbw ? (uint32_t)__popc(W.B[k]) : 0u;
-      const uint32_t inc = wave_incl_scan(c);
-      if (k < nbw) W.WP[k] = (uint16_t)(carry + inc - c);
-      carry += (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-    }
-    wave_lds_fence();
-  };
 #ifdef MKP_DEBUG
-  if (prm.debug_skip & 256u) have_calls = false;   // ablation: no sweep, no calls
+  if (prm.debug_skip & 256u) have_calls = false;   // ablation: no calls (the read as if it had none)
 #endif
-  if (have_calls && !err) {
-    if (MULTI) {   // several windows: the total is needed up front (reverse reads; the list's last entry)
-      uint32_t acc = 0;
-      for (uint32_t d0 = 0; d0 < nd; d0 += 1024) {
-        uint4 x[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) x[j] = d0 == 0 ? xpre[j] : load4(d0 + 256u * (uint32_t)j + 4u * (uint32_t)lane);
-#pragma unroll
-        for (int j = 0; j < 4; j++) acc += (uint32_t)__popc(flags4(x[j]));
-      }
-      tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(acc), 63) - (pad_hit ? 1u : 0u);
-    } else { sweep(); tot = cntW; }
-    // a delta list must not run past the last occurrence of its base (mod_bam.rs:705-727)
-    if (rfl(e_last) >= tot) err = true;
-    else { t_cur = rev ? t_n : 0u; if (!MULTI) mark(); }
-  }
-  if (err) have_calls = false;   // the record only contributes coverage (skip_set, read_cache.rs:272-277)
+  if (have_calls && err_rec) have_calls = false;   // the record only contributes coverage (skip_set, read_cache.rs:272-277)
+#ifdef MKP_DEBUG
+  const bool plane_calls = have_calls && !(prm.debug_skip & 128u);   // ablation: no plane lookups, no calls
+#else
+  const bool plane_calls = have_calls;
+#endif
 
   // ---- the read's slots, 64 per step
   bool gaps = false; uint32_t n_callfeat = 0;
@@ -447,110 +402,82 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
     refwin_s_map(rw, cg, h.n_cigar, h.ref_start, valid, p, &kind, &q);
     const bool is_match = valid && kind == 0u && q < L;
     const uint32_t byte = is_match ? (uint32_t)ldo<uint8_t>(seqb, q >> 1) : 0u;
+    // the plane word of the base: bit q & 31 = a listed call sits here, .y + the listed bits below it = its stored-order ordinal
+    const uint2 pw = (plane_calls && is_match) ? ldo<uint2>(pl, 8u * (q >> 5)) : make_uint2(0u, 0u);
     uint32_t call_fb = 0xffffffffu;
-#ifdef MKP_DEBUG
-    if (have_calls && !(prm.debug_skip & 128u)) {   // ablation: no rank lookups, no calls
-#else
-    if (have_calls) {
-#endif
-      bool pend = is_match;
-      for (;;) {
-        bool inw = pend;
-        if (MULTI) {
-          if (!__any(pend)) break;
-          inw = pend && bw_loaded && (q - w0) < SL_WB;
-          if (!__any(inw)) {   // the next base window (never skipped: the occurrence counts run on)
-            if (bw_loaded) { w0 += SL_WB; cum += cntW; }
-            if (w0 >= L) break;
-            sweep(); mark();
-            continue;
-          }
+    if (plane_calls) {
+      const uint32_t qb = q & 31u;
+      const bool listed = (pw.x >> qb) & 1u;
+      if (__any(listed)) {
+        // calls are listed in forward order: a reverse read's stored ordinal j is call n_calls - 1 - j
+        const uint32_t jrel = pw.y + (uint32_t)__popc(pw.x & ((1u << qb) - 1u));
+        const uint32_t jl = listed ? (rev ? t_n - 1u - jrel : jrel) : 0u;
+        // MultipleThresholdModCaller::call (threshold_mod_caller.rs:28-63) on the map of this call, entries in the map's
+        // iteration order: pass threshold, Iterator::max keeps the last maximum, canonical pushed last.  ReDistribute runs
+        // (--ignore, --preset traditional) first add the collapsed code's share to every entry (mod_bam.rs:558-600).
+        // All ML bytes of the call are requested before any is looked at (round 5 waited for each in turn: two to five dependent
+        // memory round trips per 64 slots, the longest chain of the wave's life).
+        const uint4 off4 = *reinterpret_cast<const uint4*>(W.ck_off), str4 = *reinterpret_cast<const uint4*>(W.ck_str);
+        const uint32_t ml_o[MKP_KMAX] = {off4.x, off4.y, off4.z, off4.w}, ml_s[MKP_KMAX] = {str4.x, str4.y, str4.z, str4.w};
+        uint32_t mlb[MKP_KMAX] = {0u, 0u, 0u, 0u}, mlx = 0;
+        auto mlq = [&](int k) { return (uint32_t)ldo<uint8_t>(ml, __umul24(jl, ml_s[k]) + ml_o[k]); };
+        switch (n_post) {   // (uniform)
+          case 1: mlb[0] = mlq(0); break;
+          case 2: mlb[0] = mlq(0); mlb[1] = mlq(1); break;
+          case 3: mlb[0] = mlq(0); mlb[1] = mlq(1); mlb[2] = mlq(2); break;
+          case 4: mlb[0] = mlq(0); mlb[1] = mlq(1); mlb[2] = mlq(2); mlb[3] = mlq(3); break;
+          default: break;
         }
-        const uint32_t qr = inw ? q - w0 : 0u, wv = qr >> 5;
-        const uint32_t Fw = W.F[wv], Pw = W.P[wv];
-        const uint32_t r = qr & 7u, kd = (qr >> 3) & 3u, sh = 3u - kd;
-        const bool cand = inw && ((Fw >> (4u * (r ^ 1u) + sh)) & 1u);
-        // occurrences before q inside the word: the dwords below (bit offsets above 3 - kd in every nibble), then the nibbles of
-        // the bases before q in its own dword (base 2j sits in nibble 2j+1)
-        const uint32_t m_dw = ~((0x11111111u << (4u - kd)) - 0x11111111u);
-        const uint32_t re4 = (r & 6u) << 2;
-        const uint32_t m_in = (((1u << re4) - 1u) & 0x11111111u) | ((r & 1u) << (4u * r));
-        const uint32_t ord = Pw + (uint32_t)__popc(Fw & (m_dw | (m_in << sh)));               // ordinal inside the window, stored order
-        const uint32_t Bw = cand ? W.B[ord >> 5] : 0u;
-        const bool listed = cand && ((Bw >> (ord & 31u)) & 1u);
-        if (__any(listed)) {
-          const uint32_t jrel = (uint32_t)W.WP[listed ? (ord >> 5) : 0u] + (uint32_t)__popc(Bw & ((1u << (ord & 31u)) - 1u));
-          const uint32_t jx = listed ? (rev ? (t_base - 1u - jrel) : (t_base + jrel)) : 0u;
-          // MultipleThresholdModCaller::call (threshold_mod_caller.rs:28-63) on the map of this call, entries in the map's
-          // iteration order: pass threshold, Iterator::max keeps the last maximum, canonical pushed last.  ReDistribute runs
-          // (--ignore, --preset traditional) first add the collapsed code's share to every entry (mod_bam.rs:558-600).
-          // All ML bytes of the call are requested before any is looked at (round 5 waited for each in turn: two to five dependent
-          // memory round trips per 64 slots, the longest chain of the wave's life).
-          const uint32_t jl = listed ? jx : 0u;
-          const uint4 off4 = *reinterpret_cast<const uint4*>(W.ck_off), str4 = *reinterpret_cast<const uint4*>(W.ck_str);
-          const uint32_t ml_o[MKP_KMAX] = {off4.x, off4.y, off4.z, off4.w}, ml_s[MKP_KMAX] = {str4.x, str4.y, str4.z, str4.w};
-          uint32_t mlb[MKP_KMAX] = {0u, 0u, 0u, 0u}, mlx = 0;
-          auto mlq = [&](int k) { return (uint32_t)ldo<uint8_t>(ml, __umul24(jl, ml_s[k]) + ml_o[k]); };
-          switch (n_post) {   // (uniform)
-            case 1: mlb[0] = mlq(0); break;
-            case 2: mlb[0] = mlq(0); mlb[1] = mlq(1); break;
-            case 3: mlb[0] = mlq(0); mlb[1] = mlq(1); mlb[2] = mlq(2); break;
-            case 4: mlb[0] = mlq(0); mlb[1] = mlq(1); mlb[2] = mlq(2); mlb[3] = mlq(3); break;
+        if (f_col & 1u) mlx = (uint32_t)ldo<uint8_t>(ml, __umul24(jl, mlx_s) + mlx_o);
+        uint32_t cid = MKP_C_FAIL;
+        if (int_caller) {
+          // The same walk in integers, exactly: q -> (q + 0.5) / 256 is a multiple of 2^-9, the share of a collapsed code (its
+          // probability over 1, 2 or 4 codes) a multiple of 2^-11, every sum of up to five of them and 1 - sum are exact in f32 — so
+          // the f32 comparisons of the reference are comparisons of integers in units of 2^-11, thresholds rounded up to the next
+          // multiple by the host (fused_desc: the least integer T with T / 2048 >= threshold).  One straight-line instance per number
+          // of codes (uniform switch): no per-code masks held in scalar registers.
+          const int4 thr4 = *reinterpret_cast<const int4*>(W.ck_thr);
+          const uint4 cid4 = *reinterpret_cast<const uint4*>(W.ck_cid);
+          const int32_t red4 = (f_col & 1u) ? (int32_t)(((2u * mlx + 1u) << 2) >> red_shift) + 4 : 4;
+          int32_t sum = 0, best = INT32_MIN;
+          auto step = [&](uint32_t b, int32_t thr, uint32_t c) {
+            const int32_t v = (int32_t)(b << 3) + red4;
+            sum += v;
+            const bool take = v >= max(thr, best);   // passes, and no entry before it is larger (the last maximum wins)
+            cid = take ? c : cid; best = take ? v : best;
+          };
+          switch (n_post) {
+            case 1: step(mlb[0], thr4.x, cid4.x); break;
+            case 2: step(mlb[0], thr4.x, cid4.x); step(mlb[1], thr4.y, cid4.y); break;
+            case 3: step(mlb[0], thr4.x, cid4.x); step(mlb[1], thr4.y, cid4.y); step(mlb[2], thr4.z, cid4.z); break;
+            case 4: step(mlb[0], thr4.x, cid4.x); step(mlb[1], thr4.y, cid4.y); step(mlb[2], thr4.z, cid4.z); step(mlb[3], thr4.w, cid4.w); break;
             default: break;
           }
-          if (f_col & 1u) mlx = (uint32_t)ldo<uint8_t>(ml, __umul24(jl, mlx_s) + mlx_o);
-          uint32_t cid = MKP_C_FAIL;
-          if (int_caller) {
-            // The same walk in integers, exactly: q -> (q + 0.5) / 256 is a multiple of 2^-9, the share of a collapsed code (its
-            // probability over 1, 2 or 4 codes) a multiple of 2^-11, every sum of up to five of them and 1 - sum are exact in f32 — so
-            // the f32 comparisons of the reference are comparisons of integers in units of 2^-11, thresholds rounded up to the next
-            // multiple by the host (fused_desc: the least integer T with T / 2048 >= threshold).  One straight-line instance per number
-            // of codes (uniform switch): no per-code masks held in scalar registers.
-            const int4 thr4 = *reinterpret_cast<const int4*>(W.ck_thr);
-            const uint4 cid4 = *reinterpret_cast<const uint4*>(W.ck_cid);
-            const int32_t red4 = (f_col & 1u) ? (int32_t)(((2u * mlx + 1u) << 2) >> red_shift) + 4 : 4;
-            int32_t sum = 0, best = INT32_MIN;
-            auto step = [&](uint32_t b, int32_t thr, uint32_t c) {
-              const int32_t v = (int32_t)(b << 3) + red4;
-              sum += v;
-              const bool take = v >= max(thr, best);   // passes, and no entry before it is larger (the last maximum wins)
-              cid = take ? c : cid; best = take ? v : best;
-            };
-            switch (n_post) {
-              case 1: step(mlb[0], thr4.x, cid4.x); break;
-              case 2: step(mlb[0], thr4.x, cid4.x); step(mlb[1], thr4.y, cid4.y); break;
-              case 3: step(mlb[0], thr4.x, cid4.x); step(mlb[1], thr4.y, cid4.y); step(mlb[2], thr4.z, cid4.z); break;
-              case 4: step(mlb[0], thr4.x, cid4.x); step(mlb[1], thr4.y, cid4.y); step(mlb[2], thr4.z, cid4.z); step(mlb[3], thr4.w, cid4.w); break;
-              default: break;
-            }
-            const int32_t pc = 2048 - sum;
-            if (pc >= max(i_can, best)) cid = (fmisc >> 8) & 0xffu;
-          // (a share over three codes: the f32 walk; its thresholds are read here — this is the rare path — not held in registers by every read)
-          } else {
-          const MkpFusedDesc& fdr = fdesc[h.layout];
-          float f_thr[MKP_KMAX]; const float thr_can = fdr.thr_can;
+          const int32_t pc = 2048 - sum;
+          if (pc >= max(i_can, best)) cid = (fmisc >> 8) & 0xffu;
+        // (a share over three codes: the f32 walk; its thresholds are read here — this is the rare path — not held in registers by every read)
+        } else {
+        const MkpFusedDesc& fdr = fdesc[h.layout];
+        float f_thr[MKP_KMAX]; const float thr_can = fdr.thr_can;
 #pragma unroll
-          for (int k = 0; k < MKP_KMAX; k++) f_thr[k] = fdr.it_thr[k];
-          float red = 0.f;
-          if (f_col & 1u) red = (((float)mlx + 0.5f) / 256.0f) / fdr.n_other;
-          float s = 0.f, best_p = 0.f; bool have = false;
+        for (int k = 0; k < MKP_KMAX; k++) f_thr[k] = fdr.it_thr[k];
+        float red = 0.f;
+        if (f_col & 1u) red = (((float)mlx + 0.5f) / 256.0f) / fdr.n_other;
+        float s = 0.f, best_p = 0.f; bool have = false;
 #pragma unroll
-          for (int k = 0; k < MKP_KMAX; k++) {
-            if ((uint32_t)k < n_post) {
-              float pr = ((float)mlb[k] + 0.5f) / 256.0f;   // quals_to_probs (mod_bam.rs:808-816)
-              if (f_col & 1u) pr = pr + red;
-              s = s + pr;
-              const bool take = pr >= f_thr[k] && (!have || !(pr < best_p));
-              cid = take ? W.ck_cid[k] : cid; best_p = take ? pr : best_p; have = have || take;
-            }
+        for (int k = 0; k < MKP_KMAX; k++) {
+          if ((uint32_t)k < n_post) {
+            float pr = ((float)mlb[k] + 0.5f) / 256.0f;   // quals_to_probs (mod_bam.rs:808-816)
+            if (f_col & 1u) pr = pr + red;
+            s = s + pr;
+            const bool take = pr >= f_thr[k] && (!have || !(pr < best_p));
+            cid = take ? W.ck_cid[k] : cid; best_p = take ? pr : best_p; have = have || take;
           }
-          const float pc = 1.0f - s;
-          if (pc >= thr_can && (!have || !(pc < best_p))) cid = (fmisc >> 8) & 0xffu;
-          }
-          if (listed) call_fb = feat(cid, aln ^ sg0u);   // FeatureVector::add_feature's tally (pileup/mod.rs:238-281)
         }
-        if (!MULTI) break;
-        pend = pend && !inw;
+        const float pc = 1.0f - s;
+        if (pc >= thr_can && (!have || !(pc < best_p))) cid = (fmisc >> 8) & 0xffu;
+        }
+        if (listed) call_fb = feat(cid, aln ^ sg0u);   // FeatureVector::add_feature's tally (pileup/mod.rs:238-281)
       }
     }
     const uint32_t nib = (q & 1u) ? (byte & 15u) : (byte >> 4);
@@ -580,23 +507,13 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
 }
 
 // Residency on gfx950 is also bounded by the SIMD's 800 scalar registers: a wave is charged ceil(sgprs / 16) * 16 + 16 of them
-// (MI355X_MICROARCH.md, "Residency and cooperative launch"), so the 105 the compiler takes when left alone admit six waves per SIMD whatever
-// the LDS and VGPR budgets say (the compiler's own occupancy figure says eight).  The short-read kernel is capped at 80 — eight waves; the
-// spilled scalars cost ~26 v_readlane / v_writelane per slot batch (+7 % VALU) against +33 % resident waves: 0.75 -> 0.70 ms on C3
-// (A/B on one box: tools/dbg/ab.sh, MKP_DECODE_SGPRS=96 gives seven waves and 0.705).  The long-read kernel (several slot windows per read,
-// 106 SGPRs / 79 VGPRs left alone: six waves) is bounded to seven waves — 94 SGPRs, 72 VGPRs, 12 B of scratch: C3 decode 0.694 -> 0.682 ms on
-// one box; eight waves (MKP_LONG_WAVES=8) spills enough to lose: 0.725.
+// (MI355X_MICROARCH.md, "Residency and cooperative launch"), so a kernel left to take 105 admits six waves per SIMD whatever the LDS and
+// VGPR budgets say.  The decoder is capped at 80 — eight waves.
 #ifndef MKP_DECODE_SGPRS
 #define MKP_DECODE_SGPRS 80
 #endif
-#ifndef MKP_LONG_WAVES
-#define MKP_LONG_WAVES 7
-#endif
-#define MKP_LONG_LB __launch_bounds__(256, MKP_LONG_WAVES)
-#define MKP_SLOT_KERNEL(NAME, MULTI, ...) extern "C" __global__ void __VA_ARGS__ NAME(FUSED_PARAMS(MkpRunParams)) { \
-    __shared__ __attribute__((aligned(16))) SlotLds lds_all[4]; decode_slots_body<MULTI>(FUSED_PASS, lds_all); }
-MKP_SLOT_KERNEL(mkp_decode_slots, false, __attribute__((amdgpu_num_sgpr(MKP_DECODE_SGPRS))) __launch_bounds__(256))
-MKP_SLOT_KERNEL(mkp_decode_slots_long, true, MKP_LONG_LB)
+extern "C" __global__ void __attribute__((amdgpu_num_sgpr(MKP_DECODE_SGPRS))) __launch_bounds__(256) mkp_decode_slots(FUSED_PARAMS(MkpRunParams)) {
+  __shared__ __attribute__((aligned(16))) SlotLds lds_all[4]; decode_slots_body(FUSED_PASS, lds_all); }
 
 // ----------------------------------------------------------------------------------------------------------------------
 // mkp_cover_reads: coverage features of the reads the event-producing decode kernels handled, with their call events merged in.
@@ -1098,18 +1015,23 @@ extern "C" __global__ void __launch_bounds__(64) mkp_dup_events(const MkpReadHdr
 
 // ----------------------------------------------------------------------------------------------------------------------
 // host-side launchers (called from mkp_api.cpp)
-// work = the fused decoder's reads [longer than one base window | the others], cover_ids = the reads of mkp_cover_reads
-extern "C" hipError_t mkp_launch_slots(hipStream_t st, const MkpWork* work, uint32_t n_long, uint32_t n_short, const MkpReadHdr* hdrs,
+// work = the fused decoder's reads (longest first), cover_ids = the reads of mkp_cover_reads
+extern "C" hipError_t mkp_launch_slots(hipStream_t st, const MkpWork* work, uint32_t n_fused, const void* plane, const MkpReadHdr* hdrs,
     const uint32_t* cover_ids, uint32_t n_cover, const uint32_t* cigar,
                                        const uint8_t* seqs, const MkpTagRef* tagref, const uint32_t* ranks, const uint8_t* ml,
                                            const MkpLayout* layouts, const MkpFusedDesc* fdesc, const MkpRunParams* prm,
                                        const uint32_t* slot_pos, uint8_t* cov, MkpVisit* visits, MkpEvent* events, MkpReadOut* readout,
                                            uint32_t* dev_err) {
-#define MKP_FUSED_LAUNCH(K, W, N) hipLaunchKernelGGL(K, dim3(((N) + 3u) / 4u), dim3(256), 0, st, W, N, cigar, seqs, ranks, ml, fdesc, *prm, slot_pos, cov, visits, readout)
-  if (n_long) MKP_FUSED_LAUNCH(mkp_decode_slots_long, work, n_long);
-  if (n_short) MKP_FUSED_LAUNCH(mkp_decode_slots, work + n_long, n_short);
+  if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, cigar, seqs, static_cast<const uint2*>(plane), ml, fdesc, *prm,
+      slot_pos, cov, visits, readout);
   if (n_cover) hipLaunchKernelGGL(mkp_cover_reads, dim3((n_cover + 3u) / 4u), dim3(256), 0, st, hdrs, n_cover, cover_ids, cigar, seqs, tagref, ranks,
       ml, layouts, fdesc, *prm, slot_pos, cov, visits, events, readout, dev_err);
+  return hipGetLastError();
+}
+// the call plane of the fused reads (once per resident shard; it also marks the work records whose delta list runs past its base)
+extern "C" hipError_t mkp_launch_call_plane(hipStream_t st, MkpWork* work, uint32_t n_fused, const uint8_t* seqs, const uint32_t* ranks,
+    const MkpFusedDesc* fdesc, void* plane) {
+  if (n_fused) hipLaunchKernelGGL(mkp_call_plane, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, seqs, ranks, fdesc, static_cast<uint2*>(plane));
   return hipGetLastError();
 }
 

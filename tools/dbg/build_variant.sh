@@ -1,6 +1,6 @@
 #!/bin/bash
 # another build of the library with extra compile flags -> tools/dbg/lib/libmkpileup_<name>.so; used through MKP_LIB_PATH (tools/dbg/ab.sh)
-# usage: tools/dbg/build_variant.sh wb12k "-DMKP_SLOT_WB=12288u"
+# usage: tools/dbg/build_variant.sh sg96 "-DMKP_DECODE_SGPRS=96"
 set -e
 NAME=$1; EXTRA=$2
 cd "$(dirname "$0")/../.."; B=/tmp/mkp_variant_$NAME; rm -rf $B; mkdir -p $B/modkit_amd tools/dbg/lib
