@@ -146,6 +146,8 @@ IdxStats idxstats(const BamSource& bam, const RegionSpec* region, const BedFilte
   return st;
 }
 
+void must(mkp_ctx* ctx, int r) { if (r != MKP_OK) throw Error(r, mkp_last_error(ctx)); }
+
 struct Quota { bool all = false; size_t n = 0; };
 // SamplingSchedule::from_num_reads (sampling_schedule.rs:171-273): per contig ceil(N * its share of the reads), capped by its count; while the
 // sum overshoots N by more than half, contigs at or under a rising floor are dropped (the reference walks an FxHashMap there; ascending tid
@@ -200,6 +202,16 @@ struct RecSet {
   }
 };
 
+// --include-bed: the sampling kernels' per-contig masks (BedFilter::mask), built on first use; none without a BED
+struct BedMasks {
+  const BedFilter* bf; const BamSource& bam; std::map<uint32_t, std::vector<uint8_t>> by_tid;
+  const uint8_t* operator()(uint32_t tid) {
+    if (!bf) return nullptr;
+    auto it = by_tid.find(tid); if (it == by_tid.end()) it = by_tid.emplace(tid, bf->mask(tid, bam.ref_lens[tid])).first;
+    return it->second.data();
+  }
+};
+
 // what `bam::IndexedReader::from_path` finds (htslib: <bam>.bai, <bam>.csi, or the extension replaced)
 bool bam_index_file_exists(const std::string& path) {
   std::vector<std::string> c = {path + ".bai", path + ".csi"};
@@ -229,16 +241,7 @@ void sample_serial(mkp_ctx* ctx, const BamSource& bam, const Args& a, const Regi
   SeededSampler rng(a.seed);
   const long limit = a.have_frac ? -1 : (long)a.num_reads;
   std::set<std::string> seen; size_t used = 0;
-  std::map<uint32_t, std::vector<uint8_t>> masks;   // --include-bed: bit 0 / 1 = the position is listed for the '+' / '-' strand
-  auto mask_of = [&](uint32_t tid) -> const uint8_t* {
-    if (!bf) return nullptr;
-    auto it = masks.find(tid); if (it != masks.end()) return it->second.data();
-    std::vector<uint8_t> m(bam.ref_lens[tid], 0);
-    auto mark = [&](const std::map<uint32_t, std::vector<Span>>& mp, uint8_t bit) { auto f = mp.find(tid); if (f == mp.end()) return;
-        for (auto& x : f->second) for (uint64_t q = x.s; q < std::min<uint64_t>(x.e, m.size()); q++) m[q] |= bit; };
-    mark(bf->pos, 1); mark(bf->neg, 2);
-    return masks.emplace(tid, std::move(m)).first->second.data();
-  };
+  BedMasks mask_of{bf, bam, {}};
   auto round = [&](const RecSet& set, int64_t tid) {
     const BamBatch& b = *set.b;
     std::vector<size_t> cand;
@@ -250,10 +253,9 @@ void sample_serial(mkp_ctx* ctx, const BamSource& bam, const Args& a, const Regi
       const size_t hi = std::min(cand.size(), next + want);
       std::vector<mkp_record> recs; recs.reserve(hi - next); for (size_t i = next; i < hi; i++) recs.push_back(b.view(b.recs[cand[i]]));
       std::vector<uint32_t> nv;
-      int rc = mkp_internal_sample(ctx, mapped ? (int32_t)tid : -1, 0, mapped ? bam.ref_lens[(size_t)tid] : 1, mask, recs.data(),
+      must(ctx, mkp_internal_sample(ctx, mapped ? (int32_t)tid : -1, 0, mapped ? bam.ref_lens[(size_t)tid] : 1, mask, recs.data(),
           (uint32_t)recs.size(),
-          only_mapped, &nv);
-      if (rc != MKP_OK) throw Error(rc, mkp_last_error(ctx));
+          only_mapped, &nv));
       std::vector<uint8_t> keep(recs.size(), 0);
       for (size_t i = next; i < hi; i++) {
         if (limit >= 0 && used >= (size_t)limit) break;                               // RecordSampler::ask -> Done
@@ -263,8 +265,7 @@ void sample_serial(mkp_ctx* ctx, const BamSource& bam, const Args& a, const Regi
         if (seen.count(name) || nv[k] == 0) continue;                                 // seen(); a record that keeps no value is not recorded
         seen.insert(name); used++; keep[k] = 1;
       }
-      rc = mkp_internal_sample_take(ctx, keep);
-      if (rc != MKP_OK) throw Error(rc, mkp_last_error(ctx));
+      must(ctx, mkp_internal_sample_take(ctx, keep));
       next = hi;
     }
   };
@@ -273,6 +274,62 @@ void sample_serial(mkp_ctx* ctx, const BamSource& bam, const Args& a, const Regi
     round(set, (int64_t)t);
   }
   if (limit < 0 || used < (size_t)limit) { RecSet set; set.b.reset(new BamBatch()); bam.fetch_unmapped(set.b.get()); round(set, -1); }
+}
+
+struct Iv { uint32_t tid, start, end; };
+// ReferenceIntervalsFeeder over the sampling grid (interval_chunks.rs:563-643): the intervals of every super-batch of `batch_size` feeder
+// batches (MultiChromCoordinates in feeder order), by contig and start
+std::vector<std::vector<Iv>> sampling_super_batches(const std::vector<Contig>& contigs, uint32_t interval_size, size_t batch_size) {
+  std::vector<std::vector<Iv>> groups;
+  { std::vector<Iv> batch; uint32_t blen = 0;
+    for (auto& c : contigs) for (uint32_t p = c.start; p < c.end();) {
+      uint32_t e = (uint32_t)std::min<uint64_t>((uint64_t)p + interval_size, c.end());
+        batch.push_back({c.tid, p, e}); blen += e - p; if (blen >= interval_size) { groups.push_back(batch); batch.clear(); blen = 0;
+          } p = e; }
+    if (!batch.empty()) groups.push_back(batch); }
+  std::vector<std::vector<Iv>> out;
+  for (size_t g0 = 0; g0 < groups.size(); g0 += std::max<size_t>(batch_size, 1)) {
+    std::vector<Iv> all;
+      for (size_t g = g0; g < std::min(groups.size(), g0 + std::max<size_t>(batch_size, 1)); g++) for (auto& iv : groups[g]) all.push_back(iv);
+    std::stable_sort(all.begin(), all.end(), [](const Iv& x, const Iv& y) { return x.tid != y.tid ? x.tid < y.tid : x.start < y.start; });
+    out.push_back(std::move(all));
+  }
+  return out;
+}
+
+// accumulate_sample_counts (sampling_schedule.rs:440-615): the intervals of one super-batch with their quotas — what is left of each contig's
+// quota spread over its intervals by length, intervals whose share is under 50 reads merged with their neighbours
+struct SampleIv { Iv iv; Quota q; };
+std::vector<SampleIv> group_super_batch(const std::vector<Iv>& all, const std::map<uint32_t, uint32_t>& contig_size,
+    const std::map<uint32_t, Quota>& quota, const std::map<uint32_t, size_t>& sampled_so_far) {
+  std::map<uint32_t, uint32_t> len_per; for (auto& iv : all) len_per[iv.tid] += iv.end - iv.start;
+  std::map<uint32_t, Quota> per_chrom;
+  for (auto& kv : len_per) { auto cs = contig_size.find(kv.first); auto q = quota.find(kv.first);
+    if (cs == contig_size.end() || q == quota.end()) continue;
+      auto sf = sampled_so_far.find(kv.first); size_t so_far = sf != sampled_so_far.end() ? sf->second : 0;
+      float f = (float)kv.second / (float)cs->second;
+    if (q->second.all) per_chrom[kv.first] = q->second; else if (q->second.n > so_far) { Quota x;
+      x.n = (size_t)ceilf(f * (float)(q->second.n - so_far));
+        per_chrom[kv.first] = x; } }
+  std::vector<SampleIv> grouped; bool have_slack = false; Iv slack{0, 0, 0}; size_t slack_n = 0;
+  auto merged = [](const Iv& x, const Iv& y) { return Iv{x.tid, std::min(x.start, y.start), std::max(x.end, y.end)}; };
+  for (auto& iv : all) {
+    auto pc = per_chrom.find(iv.tid); if (pc == per_chrom.end()) continue;
+    if (pc->second.all) { grouped.push_back({iv, pc->second}); continue; }
+    float f = (float)(iv.end - iv.start) / (float)len_per[iv.tid]; size_t x = (size_t)ceilf((float)pc->second.n * f); Quota qx; qx.n = x;
+    if (x < 50) {
+      if (have_slack) { if (slack.tid == iv.tid) { Iv m = merged(slack, iv); size_t tot = x + slack_n; if (tot < 50) { slack = m; slack_n = tot;
+          } else { Quota q;
+          q.n = tot; grouped.push_back({m, q}); have_slack = false; } } else { Quota q; q.n = slack_n; grouped.push_back({slack, q}); slack = iv;
+            slack_n = x; } }
+      else { have_slack = true; slack = iv; slack_n = x; }
+    } else if (have_slack) { have_slack = false; if (slack.tid == iv.tid) { Quota q; q.n = slack_n + x; grouped.push_back({merged(slack, iv), q});
+      } else { Quota q;
+        q.n = slack_n; grouped.push_back({slack, q}); grouped.push_back({iv, qx}); } }
+    else grouped.push_back({iv, qx});
+  }
+  if (have_slack) { Quota q; q.n = slack_n; grouped.push_back({slack, q}); }
+  return grouped;
 }
 
 // `resident_of` (optional): the device-packed shard holding contig `tid`, bound to the context (mkp_internal_sample_bind) — the estimate then
@@ -317,10 +374,7 @@ void sample_probabilities(mkp_ctx* ctx, const BamSource& bam, const Args& a, con
       // yields nothing, is not counted and not recorded — so only the records that can meet one are fetched (a sparse BED used to make
       // the estimate inflate every sampling interval whole), all of them: there is no head to extend afterwards.  A record of the interval
       // meets a span inside it, or reaches a span outside it — then it crosses the interval's first or last position.
-      std::vector<Span> sp;
-      for (auto* m : {&bf->pos, &bf->neg}) { auto it = m->find(tid); if (it == m->end()) continue;
-        for (auto& x : it->second) if (x.e > s && x.s < e) sp.push_back({std::max<uint64_t>(x.s, s), std::min<uint64_t>(x.e, e)});
-        }
+      std::vector<Span> sp = bf->spans_in(tid, s, e);
       sp.push_back({s, (uint64_t)s + 1}); if (e > s + 1) sp.push_back({(uint64_t)e - 1, e});
       std::sort(sp.begin(), sp.end(), [](const Span& x, const Span& y) { return x.s < y.s; });
       merge_spans(sp);
@@ -344,19 +398,7 @@ void sample_probabilities(mkp_ctx* ctx, const BamSource& bam, const Args& a, con
     const float f = (float)a.sampling_frac;
     for (auto& kv : st.mapped_by_tid) if (kv.second) { Quota q; if (f == 1.0f) q.all = true; else q.n = (size_t)ceilf((float)kv.second * f);
         quota[(uint32_t)kv.first] = q; }
-  } else {  // from_num_reads (171-273)
-    const float total = (float)total_u; size_t sum = 0;
-    for (auto& kv : st.mapped_by_tid) if (kv.second) { Quota q;
-      q.n = std::min<size_t>((size_t)ceilf((float)a.num_reads * ((float)kv.second / total)), (size_t)kv.second);
-        sum += q.n; quota[(uint32_t)kv.first] = q; }
-    if (!only_mapped) sum += (size_t)ceilf((float)a.num_reads * ((float)st.unmapped / total));
-    size_t floor = 1;
-    while ((double)sum / (double)a.num_reads > 1.5) {  // pruning walks an FxHashMap in the reference; ascending tid here (order unpinned)
-      for (auto& kv : quota) { if (kv.second.n <= floor) { sum -= kv.second.n; kv.second.n = 0; } if (sum <= a.num_reads) break; }
-      sum = 0; for (auto& kv : quota) sum += kv.second.n; floor++;
-    }
-    for (auto it = quota.begin(); it != quota.end();) { if (!it->second.all && it->second.n == 0) it = quota.erase(it); else ++it; }
-  }
+  } else quota = quota_from_num_reads(st, a.num_reads, !only_mapped);
   const size_t batch_size = (size_t)floorf((float)a.threads * 1.5f);
   std::vector<Contig> contigs; for (auto& c : targets(bam, region)) if (quota.count(c.tid)) contigs.push_back(c);
   std::map<uint32_t, uint32_t> contig_size; for (auto& c : contigs) contig_size[c.tid] = c.length;
@@ -364,16 +406,7 @@ void sample_probabilities(mkp_ctx* ctx, const BamSource& bam, const Args& a, con
     contig_start[c.tid] = c.start;
       grid_bp += c.length; }
   std::set<std::string> taken; std::map<uint32_t, size_t> sampled_so_far;
-  std::map<uint32_t, std::vector<uint8_t>> bedmasks;
-  auto bedmask_for = [&](uint32_t tid) -> const uint8_t* {
-    if (!bf) return nullptr;
-    auto it = bedmasks.find(tid); if (it != bedmasks.end()) return it->second.data();
-    std::vector<uint8_t> m(bam.ref_lens[tid], 0);
-    auto mark = [&](const std::map<uint32_t, std::vector<Span>>& mp, uint8_t bit) { auto f = mp.find(tid); if (f == mp.end()) return;
-        for (auto& s : f->second) for (uint64_t p = s.s; p < std::min<uint64_t>(s.e, m.size()); p++) m[p] |= bit; };
-    mark(bf->pos, 1); mark(bf->neg, 2);
-    return bedmasks.emplace(tid, std::move(m)).first->second.data();
-  };
+  BedMasks bedmask_for{bf, bam, {}};
   // process_records (read_ids_to_base_mod_probs.rs:223-362) over the candidate records, first-N semantics
   // One fetched batch of an interval: `cand` = indices into batch.recs that pass `candidates`, processed from cand[from] on.
   // `skip` (rank-sharded mode): candidates an earlier interval already took.  State across calls: used / n_reads_out.
@@ -423,8 +456,7 @@ void sample_probabilities(mkp_ctx* ctx, const BamSource& bam, const Args& a, con
       std::vector<uint32_t> nv; sample_round(which, tid, mapped_contig, &nv);
       std::vector<uint8_t> mask(which.size(), 0);
       decide(batch, cand, next, hi, nv.data(), limit, interval_seen, ts, skip, mask.data(), draws, frac);
-      int rc = mkp_internal_sample_take(ctx, mask);
-      if (rc != MKP_OK) throw Error(rc, mkp_last_error(ctx));
+      must(ctx, mkp_internal_sample_take(ctx, mask));
       next = hi;
     }
   };
@@ -433,46 +465,9 @@ void sample_probabilities(mkp_ctx* ctx, const BamSource& bam, const Args& a, con
     for (size_t i = 0; i < batch.size(); i++) if (batch.candidate(i, only_mapped || a.edge_filter.size())) out->push_back(i);
   };
   if (!contigs.empty()) {
-    // ReferenceIntervalsFeeder over the sampling grid, batch_size super-batches (interval_chunks.rs:563-643)
-    struct Iv { uint32_t tid, start, end; };
-    std::vector<std::vector<Iv>> groups;  // MultiChromCoordinates in feeder order
-    { std::vector<Iv> batch; uint32_t blen = 0;
-      for (auto& c : contigs) for (uint32_t p = c.start; p < c.end();) {
-        uint32_t e = (uint32_t)std::min<uint64_t>((uint64_t)p + a.sampling_interval_size, c.end());
-          batch.push_back({c.tid, p, e}); blen += e - p; if (blen >= a.sampling_interval_size) { groups.push_back(batch); batch.clear(); blen = 0;
-            } p = e; }
-      if (!batch.empty()) groups.push_back(batch); }
-    for (size_t g0 = 0; g0 < groups.size(); g0 += std::max<size_t>(batch_size, 1)) {
-      std::vector<Iv> all;
-        for (size_t g = g0; g < std::min(groups.size(), g0 + std::max<size_t>(batch_size, 1)); g++) for (auto& iv : groups[g]) all.push_back(iv);
-      std::stable_sort(all.begin(), all.end(), [](const Iv& x, const Iv& y) { return x.tid != y.tid ? x.tid < y.tid : x.start < y.start; });
-      // accumulate_sample_counts (sampling_schedule.rs:440-615)
-      std::map<uint32_t, uint32_t> len_per; for (auto& iv : all) len_per[iv.tid] += iv.end - iv.start;
-      std::map<uint32_t, Quota> per_chrom;
-      for (auto& kv : len_per) { auto cs = contig_size.find(kv.first); auto q = quota.find(kv.first);
-        if (cs == contig_size.end() || q == quota.end()) continue;
-          size_t so_far = sampled_so_far.count(kv.first) ? sampled_so_far[kv.first] : 0; float f = (float)kv.second / (float)cs->second;
-        if (q->second.all) per_chrom[kv.first] = q->second; else if (q->second.n > so_far) { Quota x;
-          x.n = (size_t)ceilf(f * (float)(q->second.n - so_far));
-            per_chrom[kv.first] = x; } }
-      struct G { Iv iv; Quota q; }; std::vector<G> grouped; bool have_slack = false; Iv slack{0, 0, 0}; size_t slack_n = 0;
-      auto merged = [](const Iv& x, const Iv& y) { return Iv{x.tid, std::min(x.start, y.start), std::max(x.end, y.end)}; };
-      for (auto& iv : all) {
-        auto pc = per_chrom.find(iv.tid); if (pc == per_chrom.end()) continue;
-        if (pc->second.all) { grouped.push_back({iv, pc->second}); continue; }
-        float f = (float)(iv.end - iv.start) / (float)len_per[iv.tid]; size_t x = (size_t)ceilf((float)pc->second.n * f); Quota qx; qx.n = x;
-        if (x < 50) {
-          if (have_slack) { if (slack.tid == iv.tid) { Iv m = merged(slack, iv); size_t tot = x + slack_n; if (tot < 50) { slack = m; slack_n = tot;
-              } else { Quota q;
-              q.n = tot; grouped.push_back({m, q}); have_slack = false; } } else { Quota q; q.n = slack_n; grouped.push_back({slack, q}); slack = iv;
-                slack_n = x; } }
-          else { have_slack = true; slack = iv; slack_n = x; }
-        } else if (have_slack) { have_slack = false; if (slack.tid == iv.tid) { Quota q; q.n = slack_n + x; grouped.push_back({merged(slack, iv), q});
-          } else { Quota q;
-            q.n = slack_n; grouped.push_back({slack, q}); grouped.push_back({iv, qx}); } }
-        else grouped.push_back({iv, qx});
-      }
-      if (have_slack) { Quota q; q.n = slack_n; grouped.push_back({slack, q}); }
+    for (const std::vector<Iv>& all : sampling_super_batches(contigs, a.sampling_interval_size, batch_size)) {
+      using G = SampleIv;
+      const std::vector<G> grouped = group_super_batch(all, contig_size, quota, sampled_so_far);
       std::map<uint32_t, size_t> batch_counts;
       // intervals this rank samples, in order; the head of the next one is fetched while the current one is decoded
       std::vector<size_t> mine;
@@ -564,7 +559,7 @@ void sample_probabilities(mkp_ctx* ctx, const BamSource& bam, const Args& a, con
           }
           g_sample_times.decide_ms += ms_since(t_h);
           t_d = std::chrono::steady_clock::now();
-          { const int rc = mkp_internal_sample_take(ctx, mask); if (rc != MKP_OK) throw Error(rc, mkp_last_error(ctx)); }
+          must(ctx, mkp_internal_sample_take(ctx, mask));
           g_sample_times.device_ms += ms_since(t_d);
           if (unsatisfied == pend.size()) break;
           Pending& P = pend[unsatisfied];
@@ -607,16 +602,7 @@ struct NameKeyHash { size_t operator()(const NameKey& k) const { return (size_t)
 void sample_resident_full(mkp_ctx* ctx, const BamSource& bam, const BedFilter* bf, std::vector<FullShard>& shards) {
   mkp_internal_bedmask_reset(ctx);
   struct MaskSession { mkp_ctx* c; ~MaskSession() { mkp_internal_bedmask_reset(c); } } mask_session{ctx};
-  std::map<uint32_t, std::vector<uint8_t>> bedmasks;
-  auto bedmask_for = [&](uint32_t tid) -> const uint8_t* {
-    if (!bf) return nullptr;
-    auto it = bedmasks.find(tid); if (it != bedmasks.end()) return it->second.data();
-    std::vector<uint8_t> m(bam.ref_lens[tid], 0);
-    auto mark = [&](const std::map<uint32_t, std::vector<Span>>& mp, uint8_t bit) { auto f = mp.find(tid); if (f == mp.end()) return;
-        for (auto& sp : f->second) for (uint64_t p = sp.s; p < std::min<uint64_t>(sp.e, m.size()); p++) m[p] |= bit; };
-    mark(bf->pos, 1); mark(bf->neg, 2);
-    return bedmasks.emplace(tid, std::move(m)).first->second.data();
-  };
+  BedMasks bedmask_for{bf, bam, {}};
   std::unordered_set<NameKey, NameKeyHash> taken;
   for (auto& fs : shards) {
     auto t_f = std::chrono::steady_clock::now();
@@ -636,8 +622,7 @@ void sample_resident_full(mkp_ctx* ctx, const BamSource& bam, const BedFilter* b
       const size_t hi = std::min(ids.size(), at + ((size_t)1 << 18));
       std::vector<uint32_t> nv;
       auto t_d = std::chrono::steady_clock::now();
-      int rc = mkp_internal_sample_resident(ctx, 0, bam.ref_lens[fs.tid], mask, ids.data() + at, (uint32_t)(hi - at), true, &nv);
-      if (rc != MKP_OK) throw Error(rc, mkp_last_error(ctx));
+      must(ctx, mkp_internal_sample_resident(ctx, 0, bam.ref_lens[fs.tid], mask, ids.data() + at, (uint32_t)(hi - at), true, &nv));
       g_sample_times.device_ms += ms_since(t_d); g_sample_times.rounds++; g_sample_times.reads += hi - at;
       auto t_h = std::chrono::steady_clock::now();
       std::vector<uint8_t> take(hi - at, 0);
@@ -649,7 +634,7 @@ void sample_resident_full(mkp_ctx* ctx, const BamSource& bam, const BedFilter* b
       }
       g_sample_times.decide_ms += ms_since(t_h);
       t_d = std::chrono::steady_clock::now();
-      rc = mkp_internal_sample_take(ctx, take); if (rc != MKP_OK) throw Error(rc, mkp_last_error(ctx));
+      must(ctx, mkp_internal_sample_take(ctx, take));
       g_sample_times.device_ms += ms_since(t_d);
       at = hi;
     }
@@ -697,38 +682,63 @@ void parse_base_thresholds(const std::vector<std::string>& raws, mkp_caller* k) 
   }
 }
 
-int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
-  auto t_all = std::chrono::steady_clock::now();
-  // BAI next to the BAM: only the blocks of the shards (and sampling intervals) this run touches are read and inflated; otherwise
-  // the whole file is loaded once.  (inflate threads: --threads only steers the sampling schedule)
-  std::unique_ptr<BamSource> src = BamSource::open(a.in_bam, std::max(std::max<unsigned>((unsigned)a.threads, 1u), HostPool::host_cpus()),
-      !a.no_index);
-  const BamSource& bam = *src;
-  double load_ms = ms_since(t_all);
-  const bool trace = getenv("MKP_TRACE_PLAN") != nullptr;   // wall-clock marks of the subcommand's phases on stderr
-  auto mark = [&](const char* what) { if (trace) fprintf(stderr, "[mkpileup run] %-36s at %.1f ms\n", what, ms_since(t_all)); };
-  mark("BAM opened (header, index)");
-  RegionSpec region, sregion; const bool have_region = !a.region.empty(), have_sregion = !a.sample_region.empty();
+// The pileup driver's environment knobs, read from the environment when constructed.  The `MKP_NO_*` ones count when set to anything, the
+// two ingest switches only when set to "1".
+struct Knobs {
+  static bool set(const char* k) { return getenv(k) != nullptr; }
+  static bool one(const char* k) { const char* v = getenv(k); return v && !strcmp(v, "1"); }
+  const bool trace = set("MKP_TRACE_PLAN");               // wall-clock marks of the subcommand's phases on stderr
+  const bool device_inflate = one("MKP_DEVICE_INFLATE"), host_ingest = one("MKP_HOST_INGEST");   // as --device-inflate / --host-ingest
+  const bool no_early_fetch = set("MKP_NO_EARLY_FETCH"), no_ahead = set("MKP_NO_AHEAD"), no_resident_sampling = set("MKP_NO_RESIDENT_SAMPLING"),
+      no_bed_merge = set("MKP_NO_BED_MERGE");
+  const char* const hbm_budget_mb = getenv("MKP_HBM_BUDGET_MB");   // overrides --hbm-budget-mb (0: 55 % of the device)
+  // two shards in flight: a shard's own upload, block table and inflate overlap since the staged ingest, a second shard fills the gaps, and
+  // more only crowd the short kernels of the threshold estimate beside them (C4 scale model, CLI: 1 worker 1.42 s, 2 1.22, 4 1.35, 8 1.34)
+  const size_t ahead_workers = set("MKP_AHEAD_WORKERS") ? (size_t)std::max(1, atoi(getenv("MKP_AHEAD_WORKERS"))) : 2;
+};
+
+// --trace-plan marks: wall-clock time of the subcommand's phases on stderr
+struct Marks {
+  bool on; std::chrono::steady_clock::time_point t0;
+  void operator()(const char* what) const { if (on) fprintf(stderr, "[mkpileup run] %-36s at %.1f ms\n", what, ms_since(t0)); }
+};
+
+// Option resolution (subcommand.rs:382-523): the flags checked in the reference's order (when several are wrong, the first check's message
+// is the one the user sees), the caller config, the focus builder (motifs, BED, strand combining) and the writer's motif labels.  The
+// reference FASTA loads on a thread of its own, joined where the grid walk needs it (load_fasta) or when this object dies.
+struct Options {
+  RegionSpec region, sregion; bool have_region = false, have_sregion = false;
+  mkp_caller kc; std::vector<mkp_mod_threshold> per_mod;
+  std::vector<Contig> records;   // the target records; under --include-bed the BED's (optimize_reference_records)
+  BedFilter bed_store; const BedFilter* bf = nullptr;
+  FocusBuilder fb; std::vector<std::string> labels;
+  Fasta fasta; std::future<Fasta> fasta_load;
+  Options(const Args& a, const BamSource& bam);
+  ~Options() { if (fasta_load.valid()) fasta_load.wait(); }
+  const RegionSpec* region_or_null() const { return have_region ? &region : nullptr; }
+  void load_fasta(const Marks& mark) { if (fasta_load.valid()) { fasta = fasta_load.get(); fb.fasta = &fasta; mark("reference FASTA loaded"); } }
+};
+
+Options::Options(const Args& a, const BamSource& bam) {
+  have_region = !a.region.empty(); have_sregion = !a.sample_region.empty();
   if (have_region) region = parse_region(a.region, bam);
   if (have_sregion) sregion = parse_region(a.sample_region, bam);
-  mkp_caller kc; memset(&kc, 0, sizeof(kc)); kc.max_depth = a.max_depth; kc.force_allow_implicit = a.force_allow;
+  memset(&kc, 0, sizeof(kc)); kc.max_depth = a.max_depth; kc.force_allow_implicit = a.force_allow;
   if (!a.edge_filter.empty()) {  // parse_edge_filter_input (command_utils.rs:243-277)
     kc.edge_filter = 1; kc.edge_inverted = a.invert_edge; size_t c = a.edge_filter.find(',');
     if (c != std::string::npos) { kc.edge_start = (uint32_t)strtoul(a.edge_filter.c_str(), nullptr, 10);
         kc.edge_end = (uint32_t)strtoul(a.edge_filter.c_str() + c + 1, nullptr, 10); }
     else kc.edge_start = kc.edge_end = (uint32_t)strtoul(a.edge_filter.c_str(), nullptr, 10);
   }
-  std::vector<mkp_mod_threshold> per_mod;
   for (auto& raw : a.mod_thresholds) { size_t c = raw.find(':'); uint32_t code;
       if (c == std::string::npos || raw.find(':', c + 1) != std::string::npos || !parse_code(raw.substr(0, c), &code)) throw Error(MKP_E_INVALID,
       "encountered illegal per-mod threshold: " + raw);
       per_mod.push_back({code, strtof(raw.c_str() + c + 1, nullptr)}); }
-  std::vector<Contig> records = targets(bam, have_region ? &region : nullptr);
-  BedFilter bed_store; const BedFilter* bf = nullptr;
+  records = targets(bam, region_or_null());
   if (!a.include_bed.empty()) { std::map<std::string, uint32_t> c2t; for (auto& r : records) c2t[r.name] = r.tid;
     bed_store = BedFilter::load(a.include_bed, c2t);
       bf = &bed_store; }
-  if (idxstats(bam, have_region ? &region : nullptr, bf).mapped == 0) throw Error(MKP_E_INVALID,
+  if (idxstats(bam, region_or_null(), bf).mapped == 0) throw Error(MKP_E_INVALID,
       "did not find any mapped reads, perform alignment first or use modkit extract and/or modkit summary to inspect unaligned modBAMs");
   if (a.filter_percentile > 1.0f) throw Error(MKP_E_INVALID, "filter percentile must be <= 1.0");
   if (a.combine_strands && !(a.cpg || !a.motif_parts.empty())) throw Error(MKP_E_INVALID,
@@ -750,9 +760,7 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
   kc.combine_strands = combine_strands;
   if (a.hemi) combine_strands = true;
       // the interval feeder runs with combine_strands = true ("must be true for duplex", subcommand.rs:1383-1390); the caller's flag stays off
-  FocusBuilder fb; fb.combine = combine_strands; fb.mask = a.mask; fb.bed = bf;
-  Fasta fasta; std::future<Fasta> fasta_load;
-  struct JoinFasta { std::future<Fasta>* f; ~JoinFasta() { if (f->valid()) f->wait(); } } join_fasta{&fasta_load};
+  fb.combine = combine_strands; fb.mask = a.mask; fb.bed = bf;
   if (!a.motif_parts.empty()) {  // RegexMotif::from_raw_parts (motif_bed.rs:152-195)
     if (!a.preset.empty()) throw Error(MKP_E_INVALID, "cannot use presets and motifs together");
     std::vector<std::string> parts = a.motif_parts;
@@ -763,391 +771,443 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
         if (!has) { parts.push_back("CG"); parts.push_back("0"); } }
     for (size_t i = 0; i + 1 < parts.size(); i += 2) fb.motifs.push_back(Motif::parse(parts[i], strtoul(parts[i + 1].c_str(), nullptr, 10)));
   } else if (a.preset == "traditional" || a.cpg) fb.motifs.push_back(Motif::parse("CG", 0));
-  RowWriter wr; wr.mixed = a.mixed_delim; for (auto& m : fb.motifs) wr.labels.push_back(m.label());
+  for (auto& m : fb.motifs) labels.push_back(m.label());
   if (!fb.motifs.empty()) {
     if (a.ref_fasta.empty()) throw Error(MKP_E_INVALID, "reference fasta is required for using --motif or --cpg options");
     if (combine_strands) for (auto& m : fb.motifs) if (!m.palindrome) throw Error(MKP_E_INVALID,
         a.hemi ? "motif must be palindromic for pileup-hemi" : "cannot combine strands with a motif that is not a palindrome");
     // joined where the grid walk needs it: the device ingest of the first shard starts meanwhile
-    fasta_load = std::async(std::launch::async, [&]() { return Fasta::load(a.ref_fasta); });
+    fasta_load = std::async(std::launch::async, [&a]() { return Fasta::load(a.ref_fasta); });
   }
-  mkp_config cfg; memset(&cfg, 0, sizeof(cfg)); cfg.device = a.device; cfg.tile_positions = a.tile;
-  mkp_ctx* ctx = ext_ctx;
-  int rc = (a.plan_only || ext_ctx) ? MKP_OK : mkp_ctx_create(&cfg, &ctx);   // --plan-only: shard plan of this rank, no device work
-  if (rc != MKP_OK) throw Error(rc, "no usable gfx950 device (libmkpileup has no CPU path)");
-  struct Guard { mkp_ctx* c; ~Guard() { if (c) mkp_ctx_destroy(c); } } guard{ext_ctx ? nullptr : ctx};
-  auto must = [&](int r) { if (r != MKP_OK) throw Error(r, mkp_last_error(ctx)); };
-  // --device-inflate (or MKP_DEVICE_INFLATE=1): the shard windows' BGZF blocks are inflated on the GPU; destroyed after the last fetch (declared
-  // before everything that fetches, so it outlives the prefetch threads on every path out of here)
-  struct InflaterGuard { mkp_dev_inflater* d = nullptr; BamSource* src = nullptr; ~InflaterGuard() { if (src) { src->dev_inflate = nullptr;
-        src->dev_inflate_user = nullptr; } mkp_internal_inflater_destroy(d); } } inflater;
-  if ((a.device_inflate || (getenv("MKP_DEVICE_INFLATE") && !strcmp(getenv("MKP_DEVICE_INFLATE"), "1"))) && !a.plan_only && bam.indexed()) {
-    inflater.d = mkp_internal_inflater_create(a.device);
-    if (!inflater.d) throw Error(MKP_E_DEVICE, "--device-inflate: cannot create a stream on the device");
-    inflater.src = src.get(); src->dev_inflate = mkp_internal_device_inflate; src->dev_inflate_user = inflater.d;
-  }
-  // The interval grid and the focus bytes need the reference and the BED only: with one rank they are built on a second thread
-  // while the thresholds are being estimated (both are all-cores work in short bursts; neither waits for the other's results).
   if (bf) records = bed_contigs(*bf, records, a.interval_size);
-  std::vector<std::vector<uint8_t>> focus_of(records.size()); std::vector<char> focus_done(records.size(), 0);
-  std::vector<std::vector<Interval>> grid_of(records.size()); std::vector<char> grid_done(records.size(), 0);
-  double focus_ms = 0;
-  // shards: pieces of the contig records cut at interval boundaries, bounded in positions (tally / focus buffers) and in BAM bytes
-  // (host memory: a shard's blocks are inflated and packed as a unit)
-  uint64_t total_bp = 0; for (auto& r : records) total_bp += r.length;
-  const uint64_t shard_bp = a.shard_bp ? a.shard_bp : (a.world > 1 ? std::max<uint64_t>(a.interval_size, std::min<uint64_t>(1ull << 27,
-      (total_bp + a.world * 8 - 1) / (a.world * 8))) : (1ull << 27));
-  // 2^27 positions per shard keeps the per-shard focus / slot buffers small
-  // BAM bytes per shard: the device ingest's inflate pays a fixed latency per launch and HBM holds the window many times over — 1 GiB of
-  // compressed blocks at a time; the host path keeps 256 MiB (its inflated window lives in host memory)
-  const bool dev_ingest_plan = !a.no_index && !a.plan_only && !a.host_ingest && a.partition_tags.empty() && !a.device_inflate
-      && !(getenv("MKP_HOST_INGEST") && !strcmp(getenv("MKP_HOST_INGEST"), "1"));
-  const uint64_t shard_bytes = (a.shard_bytes_set || !dev_ingest_plan) ? a.shard_bytes : (1ull << 30);
-  auto shard_cut = [&](const Contig& rec, const std::vector<Interval>& ivs, size_t i0, uint64_t* bp_out) {   // -> one past the shard's last interval
-    size_t i1 = i0; uint64_t bp = 0; const uint64_t o0 = bam.offset_at(rec.tid, ivs[i0].start);
-    while (i1 < ivs.size() && (bp == 0 || (bp + (ivs[i1].end - ivs[i1].start) <= shard_bp && (!bam.indexed() || bam.offset_at(rec.tid,
-        ivs[i1].end) - o0 <= shard_bytes)))) { bp += ivs[i1].end - ivs[i1].start; i1++; }
-    *bp_out = bp; return i1;
-  };
-  // Shard records come from the device ingest (mkp_ingest_host.cpp: compressed blocks up, inflate + record cut + tag tokeniser + packing in
-  // HBM, a digest back) whenever the BAM is indexed; --host-ingest / MKP_HOST_INGEST=1, --partition-tag (keys are read from aux fields on
-  // the host) and --plan-only keep the host reader + packer.
-  struct ShardInput { std::unique_ptr<BamBatch> batch; std::unique_ptr<DevShard> dev; };
-  const bool host_ingest_env = getenv("MKP_HOST_INGEST") && !strcmp(getenv("MKP_HOST_INGEST"), "1");
-  const bool dev_ingest = bam.indexed() && !a.plan_only && !a.host_ingest && a.partition_tags.empty() && !inflater.d && !host_ingest_env;
-  if (dev_ingest && !ctx->ingest) { ctx->ingest = mkp_internal_ingest_create(ctx->device);
-    if (!ctx->ingest) throw Error(MKP_E_DEVICE, "device ingest: cannot create streams on the device");
-    }
-  double ingest_ms[5] = {0, 0, 0, 0, 0}, ingest_kernel_ms = 0; uint64_t ingest_blocks = 0, ingest_records = 0, ingest_comp = 0, ingest_raw = 0;
-  // the records of a shard: those overlapping any of its windows (one window, or the BED spans of a merged shard), each +- the halo
-  auto fetch_windows = [&](uint32_t tid, const std::vector<std::pair<uint32_t, uint32_t>>& wins, mkp_dev_ingest* ing = nullptr) {
+}
+
+// --device-inflate (or MKP_DEVICE_INFLATE=1): the shard windows' BGZF blocks are inflated on the GPU; the hook is removed and the inflater
+// destroyed with this object
+struct DeviceInflater {
+  mkp_dev_inflater* d = nullptr; BamSource* src = nullptr;
+  DeviceInflater(const Args& a, const Knobs& kn, BamSource& bam) {
+    if (!((a.device_inflate || kn.device_inflate) && !a.plan_only && bam.indexed())) return;
+    d = mkp_internal_inflater_create(a.device);
+    if (!d) throw Error(MKP_E_DEVICE, "--device-inflate: cannot create a stream on the device");
+    src = &bam; src->dev_inflate = mkp_internal_device_inflate; src->dev_inflate_user = d;
+  }
+  DeviceInflater(const DeviceInflater&) = delete;
+  ~DeviceInflater() { if (src) { src->dev_inflate = nullptr; src->dev_inflate_user = nullptr; } mkp_internal_inflater_destroy(d); }
+};
+
+using Windows = std::vector<std::pair<uint32_t, uint32_t>>;
+struct ShardInput { std::unique_ptr<BamBatch> batch; std::unique_ptr<DevShard> dev; };
+
+// Reads the records of shards.  They come from the device ingest (mkp_ingest_host.cpp: compressed blocks up, inflate + record cut + tag
+// tokeniser + packing in HBM, a digest back) whenever the BAM is indexed; --host-ingest / MKP_HOST_INGEST=1, --partition-tag (keys are read
+// from aux fields on the host), --device-inflate and --plan-only keep the host reader + packer.  Owns the device inflater, so that it
+// outlives every fetch made through this reader.
+struct ShardReader {
+  const BamSource& bam; mkp_ctx* ctx; DeviceInflater inflater; bool dev_ingest;
+  ShardReader(const Args& a, const Knobs& kn, BamSource& src, mkp_ctx* c)
+      : bam(src), ctx(c), inflater(a, kn, src),
+        dev_ingest(src.indexed() && !a.plan_only && !a.host_ingest && a.partition_tags.empty() && !inflater.d && !kn.host_ingest) {
+    if (dev_ingest && !ctx->ingest) { ctx->ingest = mkp_internal_ingest_create(ctx->device);
+      if (!ctx->ingest) throw Error(MKP_E_DEVICE, "device ingest: cannot create streams on the device");
+      }
+  }
+  // the records overlapping any of the windows (one window, or the BED spans of a merged shard), each +- the halo
+  ShardInput fetch(uint32_t tid, const Windows& wins, mkp_dev_ingest* ing = nullptr) const {
     ShardInput in; FetchParts parts;
     for (auto& w : wins) { const int64_t lo = w.first > MKP_HALO ? (int64_t)w.first - MKP_HALO : 0, hi = (int64_t)w.second + MKP_HALO;
       if (!parts.empty() && lo <= parts.back().second) parts.back().second = std::max(parts.back().second, hi); else parts.push_back({lo, hi}); }
     // foreground: the upload feeds the GPU's longest job of the run
     if (dev_ingest) { in.dev = mkp_internal_ingest_run(ing ? ing : ctx->ingest, bam, tid, parts); return in; }
-    HostPool::background() = true; in.batch.reset(new BamBatch()); bam.fetch_parts(tid, parts, in.batch.get()); return in; };
-  auto fetch_range = [&](uint32_t tid, uint32_t s0, uint32_t s1) { return fetch_windows(tid, {{s0, s1}}); };
+    HostPool::background() = true; in.batch.reset(new BamBatch()); bam.fetch_parts(tid, parts, in.batch.get()); return in;
+  }
   // compressed bytes a set of fetch windows stands for (the index's 16 kb granularity: a short window costs at least its blocks)
-  auto win_bytes = [&](uint32_t tid, const std::vector<std::pair<uint32_t, uint32_t>>& wins) { uint64_t b = 0;
+  uint64_t win_bytes(uint32_t tid, const Windows& wins) const { uint64_t b = 0;
     for (auto& w : wins) b += bam.offset_at(tid, (uint64_t)w.second + 16384) - bam.offset_at(tid, w.first > 16384 ? w.first - 16384 : 0) + (1u << 16);
-    return b; };
-  // The first shard's blocks are read and inflated behind the threshold estimate (background priority on the host pool: the estimate's
-  // own bursts go first), as soon as the first contig's grid is known.
-  std::future<ShardInput> early_fetch; uint32_t early_s0 = 0, early_s1 = 0; bool early_set = false;
-  // One target contig that fits one shard whatever its grid turns out to be: the device ingest of that window starts now, before the
-  // reference is read and the grid walked (if the grid's one shard is not this window after all, the ingest is repeated for the plan's)
-  bool early_whole = false;
-  if (dev_ingest && a.world == 1 && records.size() == 1 && records[0].length > 0 && !getenv("MKP_NO_EARLY_FETCH")) {
-    const Contig& r0 = records[0];
-    if (r0.length <= shard_bp && bam.offset_at(r0.tid, r0.end()) - bam.offset_at(r0.tid, r0.start) <= shard_bytes) {
-      early_s0 = r0.start; early_s1 = r0.end(); early_set = true; early_whole = true;
-      early_fetch = std::async(std::launch::async, fetch_range, r0.tid, early_s0, early_s1);
-    }
+    return b; }
+};
+
+// Shards: pieces of the contig records cut at interval boundaries, bounded in positions (tally / focus buffers) and in BAM bytes (host
+// memory: a shard's blocks are inflated and packed as a unit)
+struct ShardSize {
+  const BamSource& bam; uint64_t bp, bytes;
+  ShardSize(const Args& a, const Knobs& kn, const BamSource& b, const std::vector<Contig>& records) : bam(b) {
+    uint64_t total_bp = 0; for (auto& r : records) total_bp += r.length;
+    bp = a.shard_bp ? a.shard_bp : (a.world > 1 ? std::max<uint64_t>(a.interval_size, std::min<uint64_t>(1ull << 27,
+        (total_bp + a.world * 8 - 1) / (a.world * 8))) : (1ull << 27));
+    // 2^27 positions per shard keeps the per-shard focus / slot buffers small
+    // BAM bytes per shard: the device ingest's inflate pays a fixed latency per launch and HBM holds the window many times over — 1 GiB of
+    // compressed blocks at a time; the host path keeps 256 MiB (its inflated window lives in host memory).  This predicate is not
+    // ShardReader::dev_ingest: with MKP_DEVICE_INFLATE=1 and no --device-inflate it holds, and the 1 GiB shards go to the host packer.
+    const bool dev_ingest_plan = !a.no_index && !a.plan_only && !a.host_ingest && a.partition_tags.empty() && !a.device_inflate
+        && !kn.host_ingest;
+    bytes = (a.shard_bytes_set || !dev_ingest_plan) ? a.shard_bytes : (1ull << 30);
   }
-  struct JoinFetch { std::future<ShardInput>* f; ~JoinFetch() { if (f->valid()) f->wait(); } } join_fetch{&early_fetch};
-  // Several target contigs (or the BED records of several contigs), each fitting one shard: all of them are ingested AHEAD, one after the
-  // other on a worker thread, and stay packed in HBM (288 GB hold a 30x genome's packed reads) — the threshold estimate then samples from
-  // them (every contig's interval heads are scans of a digest, no second read of the file), and the pileup pass finds its shards already
-  // there.  Budget: the compressed bytes under the shards; beyond it the shards are fetched as the loop reaches them (host sampler).
-  struct Ahead { size_t rec0 = 0, rec1 = 0; uint32_t tid = 0, s0 = 0, s1 = 0; std::vector<std::pair<uint32_t,
-      uint32_t>> wins; ShardInput in; bool ready = false; std::exception_ptr err; uint64_t bytes = 0, est = 0; };
-  // Several shards are in flight at once, each on an ingest object of its own (its streams, staging and scratch): one shard's inflate is a
-  // launch that fills a fraction of the chip for most of its time, and its host half (pread into staging) leaves the GPU idle —
-  // shards side by side fill both.  What they may hold is bounded by an HBM BUDGET (round 5; round 4 had an all-or-nothing 24 GiB gate on
-  // the compressed size): a shard is admitted — in plan order — while the estimated bytes of the admitted, not yet consumed shards fit the
-  // budget (one shard is always admitted), and the shard loop gives a shard's bytes back when it is through with it.  A run whose shards
-  // fit together keeps them all (and may sample its threshold estimate from them); a larger one streams.
-  std::vector<Ahead> ahead; std::mutex amu; std::condition_variable acv; std::vector<std::thread> aworkers; std::atomic<bool> astop{false};
-    std::atomic<size_t> anext{0};
-  size_t admit_next = 0; uint64_t hbm_used = 0, hbm_budget = 0, ahead_est_total = 0;   // (under amu)
-  std::vector<mkp_dev_ingest*> aingest;
-  struct FreeIngest { std::vector<mkp_dev_ingest*>* v; ~FreeIngest() { for (auto* d : *v) mkp_internal_ingest_destroy(d); } } free_ingest{&aingest};
-  struct JoinAhead { std::vector<std::thread>* t; std::atomic<bool>* stop; std::condition_variable* cv; ~JoinAhead() { stop->store(true);
-      cv->notify_all(); for (auto& x : *t) if (x.joinable()) x.join(); } } join_ahead{&aworkers, &astop, &acv};
-  if (dev_ingest) {
-    uint64_t mb = a.hbm_budget_mb; if (const char* e = getenv("MKP_HBM_BUDGET_MB")) mb = strtoull(e, nullptr, 10);
-    if (mb) hbm_budget = mb << 20;
+  // -> one past the shard's last interval
+  size_t cut(const Contig& rec, const std::vector<Interval>& ivs, size_t i0, uint64_t* bp_out) const {
+    size_t i1 = i0; uint64_t n = 0; const uint64_t o0 = bam.offset_at(rec.tid, ivs[i0].start);
+    while (i1 < ivs.size() && (n == 0 || (n + (ivs[i1].end - ivs[i1].start) <= bp && (!bam.indexed() || bam.offset_at(rec.tid,
+        ivs[i1].end) - o0 <= bytes)))) { n += ivs[i1].end - ivs[i1].start; i1++; }
+    *bp_out = n; return i1;
+  }
+};
+
+// The fetch windows of a shard made of `pieces` (ascending, disjoint) of contig `tid`: the pieces, or under --include-bed the BED spans
+// inside them (rows exist at BED positions only; the records of optimize_reference_records run from one span to the next, most of what lies
+// under them is never looked at).  Merged, ascending; empty when no BED position lies inside.
+Windows shard_windows(const BedFilter* bf, uint32_t tid, const std::vector<Span>& pieces) {
+  std::vector<Span> sp;
+  if (!bf) sp = pieces;
+  else if (!pieces.empty()) {   // the spans inside the hull, then what of them lies inside the pieces: one sweep
+    size_t p = 0;
+    for (auto& x : bf->spans_in(tid, pieces.front().s, pieces.back().e)) { while (p < pieces.size() && pieces[p].e <= x.s) p++;
+      for (size_t q = p; q < pieces.size() && pieces[q].s < x.e; q++) {
+        const uint64_t lo = std::max<uint64_t>(x.s, pieces[q].s), hi = std::min<uint64_t>(x.e, pieces[q].e);
+        if (lo < hi) sp.push_back({lo, hi});
+        } }
+  }
+  merge_spans(sp);
+  Windows w; for (auto& x : sp) w.push_back({(uint32_t)x.s, (uint32_t)x.e});
+  return w;
+}
+
+struct ShardPart { size_t rec; uint32_t s0, s1; };
+struct ShardPlan { size_t rec; uint32_t s0, s1; uint64_t bp; std::vector<uint32_t> iv_starts; /* pileup-hemi: starts of the shard's intervals */
+                   std::vector<ShardPart> parts; /* --include-bed: the BED-span records merged into this shard (empty: one window) */
+                   int64_t own_from = INT64_MIN;
+                     /* full-data sampling from the shards: reads starting before this position lie in the previous shard of the contig too, and are sampled there */ };
+
+// the fetch windows of the shard [s0, s1) (made of `parts`, when merged)
+Windows plan_windows(const BedFilter* bf, uint32_t tid, uint32_t s0, uint32_t s1, const std::vector<ShardPart>& parts = {}) {
+  std::vector<Span> pieces; if (parts.empty()) pieces.push_back({s0, s1}); else for (auto& pt : parts) pieces.push_back({pt.s0, pt.s1});
+  Windows w = shard_windows(bf, tid, pieces);
+  if (w.empty()) w.push_back({s0, s0 + 1});   // (no BED position inside: nothing to fetch but an empty window)
+  return w;
+}
+
+// Shards ingested AHEAD of the shard loop on worker threads, and kept packed in HBM (288 GB hold a 30x genome's packed reads): several target
+// contigs (or the BED records of several contigs) each fitting one shard, or the plan's shards.  The threshold estimate may then sample from
+// them (every contig's interval heads are scans of a digest, no second read of the file), and the pileup pass finds its shards already there.
+// Several shards are in flight at once, each on an ingest object of its own (its streams, staging and scratch): one shard's inflate is a
+// launch that fills a fraction of the chip for most of its time, and its host half (pread into staging) leaves the GPU idle — shards side by
+// side fill both.  What they may hold is bounded by an HBM BUDGET (round 5; round 4 had an all-or-nothing 24 GiB gate on the compressed
+// size): a shard is admitted — in plan order — while the estimated bytes of the admitted, not yet consumed shards fit the budget (one shard
+// is always admitted), and the shard loop gives a shard's bytes back when it is through with it (release).  A run whose shards fit together
+// keeps them all (and may sample its threshold estimate from them); a larger one streams.  The destructor stops and joins the workers, then
+// destroys their ingest objects.
+class AheadIngest {
+ public:
+  struct Shard { uint32_t tid = 0, s0 = 0, s1 = 0; Windows wins; ShardInput in; bool ready = false; std::exception_ptr err; uint64_t bytes = 0,
+      est = 0; };
+  std::vector<Shard> list;
+  uint64_t budget = 0, est_total = 0;
+  bool whole_contigs = false;   // the list holds whole contigs (from_contigs); the plan's shards may be pieces of them
+
+  AheadIngest(const ShardReader& reader, mkp_ctx* ctx, uint64_t budget_mb, const Knobs& kn) : rd(reader), ctx(ctx), workers_wanted(kn.ahead_workers) {
+    if (!rd.dev_ingest) return;
+    const uint64_t mb = kn.hbm_budget_mb ? strtoull(kn.hbm_budget_mb, nullptr, 10) : budget_mb;
+    if (mb) budget = mb << 20;
     else { size_t fr = 0, tot = 0; if (hipMemGetInfo(&fr, &tot) != hipSuccess || !tot) tot = (size_t)64 << 30;
-      hbm_budget = (uint64_t)((double)tot * 0.55); }
+      budget = (uint64_t)((double)tot * 0.55); }
   }
+  ~AheadIngest() {
+    { std::lock_guard<std::mutex> g(mu); stop.store(true); }
+    cv.notify_all();
+    for (auto& t : workers) if (t.joinable()) t.join();
+    for (auto* d : extra_ingest) mkp_internal_ingest_destroy(d);
+  }
+  bool empty() const { return list.empty(); }
+  size_t size() const { return list.size(); }
+
   // packed arrays of a shard ~ 1.9 x its compressed blocks on ONT-like data (SEQ nibbles + CIGAR words + 5 bytes per call; names and
   // qualities are not kept), the inflated window of the ingest object in flight on top: 2.5 x; and once the shard is resident, the slot
   // decoder's call plane (two bits per stored base = half the SEQ nibbles, ~0.5 x): 3 x as the estimate
-  auto est_of = [](uint64_t comp_bytes) { return comp_bytes * 3 + (64ull << 20); };
-  auto start_ahead = [&]() {
-    if (ahead.empty() || !aworkers.empty()) return;
-    ahead_est_total = 0; for (auto& A : ahead) { A.est = est_of(A.bytes); ahead_est_total += A.est; }
-    // two shards in flight: a shard's own upload, block table and inflate overlap since the staged ingest, a second shard fills the gaps, and
-    // more only crowd the short kernels of the threshold estimate beside them (C4 scale model, CLI: 1 worker 1.42 s, 2 1.22, 4 1.35, 8 1.34)
-    size_t nw = 2; if (const char* e = getenv("MKP_AHEAD_WORKERS")) nw = (size_t)std::max(1, atoi(e));
-    nw = std::min(nw, ahead.size());
-    for (size_t w = 1; w < nw; w++) { mkp_dev_ingest* d = mkp_internal_ingest_create(ctx->device); if (!d) break; aingest.push_back(d); }
-    nw = aingest.size() + 1;
-    for (size_t w = 0; w < nw; w++) aworkers.emplace_back([&, w]() {
-      mkp_dev_ingest* ing = w == 0 ? ctx->ingest : aingest[w - 1];
-      for (;;) {
-        const size_t k = anext.fetch_add(1); if (k >= ahead.size()) break;
-        { std::unique_lock<std::mutex> lk(amu);   // admission in plan order, under the budget
-          acv.wait(lk, [&] { return astop.load() || (admit_next == k && (hbm_used == 0 || hbm_used + ahead[k].est <= hbm_budget)); });
-          if (!astop.load()) { hbm_used += ahead[k].est; admit_next = k + 1; } }
-        acv.notify_all();
-        ShardInput in; std::exception_ptr err;
-        if (astop.load()) err = std::make_exception_ptr(Error(MKP_E_INVALID, "internal: shard ingest cancelled"));
-        else try { in = fetch_windows(ahead[k].tid, ahead[k].wins, ing); } catch (...) { err = std::current_exception(); astop.store(true); }
-        { std::lock_guard<std::mutex> g(amu); ahead[k].in = std::move(in); ahead[k].err = err; ahead[k].ready = true; }
-        acv.notify_all();
-      }
-    });
-  };
-  // the shard loop is through with shard k
-  auto ahead_release = [&](size_t k) { { std::lock_guard<std::mutex> g(amu); hbm_used -= std::min(hbm_used, ahead[k].est); } acv.notify_all(); };
-  // the fetch windows of a shard made of BED records [r0, r1) of one contig: the BED spans inside them (rows exist at BED positions only,
-  // so only records reaching a span matter), not the records, which run from one span to the next
-  auto bed_windows = [&](size_t r0, size_t r1) {
-    std::vector<std::pair<uint32_t, uint32_t>> w; const uint32_t tid = records[r0].tid; std::vector<Span> sp;
-    for (auto* m : {&bf->pos, &bf->neg}) { auto it = m->find(tid); if (it == m->end()) continue;
-      for (auto& x : it->second) {
-        const uint64_t lo = std::max<uint64_t>(x.s, records[r0].start), hi = std::min<uint64_t>(x.e, records[r1 - 1].end());
-        if (lo < hi) sp.push_back({lo, hi});
-        } }
-    merge_spans(sp);
-    // keep what lies inside the records (sorted, disjoint): one sweep
-    { std::vector<Span> in; size_t r = r0;
-      for (auto& x : sp) { while (r < r1 && records[r].end() <= x.s) r++;
-        for (size_t q = r; q < r1 && records[q].start < x.e; q++) {
-          const uint64_t lo = std::max<uint64_t>(x.s, records[q].start), hi = std::min<uint64_t>(x.e, records[q].end());
-          if (lo < hi) in.push_back({lo, hi});
-          } }
-      sp.swap(in); merge_spans(sp); } for (auto& x : sp) w.push_back({(uint32_t)x.s, (uint32_t)x.e});
-    return w;
-  };
-  if (dev_ingest && !early_whole && a.world == 1 && !records.empty() && !getenv("MKP_NO_EARLY_FETCH") && !getenv("MKP_NO_AHEAD")) {
-    uint64_t total = 0; bool fits = true;
+  static uint64_t est_of(uint64_t comp_bytes) { return comp_bytes * 3 + (64ull << 20); }
+
+  // every target record as one shard, its records grouped by contig under --include-bed; nothing when one of them does not fit a shard
+  // (a contig larger than a shard: the shards are cut on the grid and ingested ahead once the plan is known, from_plan)
+  void from_contigs(const std::vector<Contig>& records, const BedFilter* bf, const ShardSize& size) {
+    bool fits = true;
     for (size_t r0 = 0; r0 < records.size() && fits;) {
       size_t r1 = r0 + 1; if (bf) while (r1 < records.size() && records[r1].tid == records[r0].tid) r1++;
-      Ahead A; A.rec0 = r0; A.rec1 = r1; A.tid = records[r0].tid; A.s0 = records[r0].start; A.s1 = records[r1 - 1].end();
-      if (bf) A.wins = bed_windows(r0, r1); else A.wins.push_back({A.s0, A.s1});
-      A.bytes = bf ? win_bytes(A.tid, A.wins) : bam.offset_at(A.tid, A.s1) - bam.offset_at(A.tid, A.s0);
-      if ((uint64_t)A.s1 - A.s0 > shard_bp || A.bytes > shard_bytes || (bf && r1 - r0 > 65536) || records[r0].length == 0
+      Shard A; A.tid = records[r0].tid; A.s0 = records[r0].start; A.s1 = records[r1 - 1].end();
+      std::vector<Span> pieces; for (size_t r = r0; r < r1; r++) pieces.push_back({records[r].start, records[r].end()});
+      A.wins = shard_windows(bf, A.tid, pieces);
+      A.bytes = bf ? rd.win_bytes(A.tid, A.wins) : rd.bam.offset_at(A.tid, A.s1) - rd.bam.offset_at(A.tid, A.s0);
+      if ((uint64_t)A.s1 - A.s0 > size.bp || A.bytes > size.bytes || (bf && r1 - r0 > 65536) || records[r0].length == 0
           || A.wins.empty()) fits = false;
-      total += A.bytes; ahead.push_back(std::move(A)); r0 = r1;
+      list.push_back(std::move(A)); r0 = r1;
     }
-    (void)total;
-    if (!fits) ahead.clear();   // a contig larger than a shard: the shards are cut on the grid and ingested ahead once the plan is known (below)
-    start_ahead();
+    if (!fits) list.clear();
+    whole_contigs = !list.empty();
+    start();
   }
-  auto ahead_wait = [&](size_t k) -> Ahead& { std::unique_lock<std::mutex> lk(amu); acv.wait(lk,
-      [&] { return ahead[k].ready; }); if (ahead[k].err) std::rethrow_exception(ahead[k].err); return ahead[k]; };
-  if (fasta_load.valid()) { fasta = fasta_load.get(); fb.fasta = &fasta; mark("reference FASTA loaded"); }
-  std::future<void> early_walk;
-  if (fb.has_focus() && a.world == 1 && !a.plan_only && a.filter_threshold.empty() && !a.no_filtering)
-    early_walk = std::async(std::launch::async, [&]() {
-      auto t_focus = std::chrono::steady_clock::now();
-      for (size_t ri = 0; ri < records.size(); ri++) {
-        grid_of[ri] = fb.walk(records[ri], a.interval_size, &focus_of[ri]); grid_done[ri] = 1; focus_done[ri] = 1;
-        // (--include-bed: the first shard is a merge of records, known only with the plan)
-        if (ri == 0 && !early_whole && !bf && ahead.empty() && !grid_of[0].empty() && !getenv("MKP_NO_EARLY_FETCH")) {
-          uint64_t bp; const size_t i1 = shard_cut(records[0], grid_of[0], 0, &bp);
-          early_s0 = grid_of[0][0].start; early_s1 = grid_of[0][i1 - 1].end; early_set = true;
-          early_fetch = std::async(std::launch::async, fetch_range, records[0].tid, early_s0, early_s1);
-        }
-      }
-      focus_ms += ms_since(t_focus);
-    });
-  struct JoinWalk { std::future<void>* f; ~JoinWalk() { if (f->valid()) f->wait(); } } join_walk{&early_walk};
-      // (an exception below must not leave the walker running on dead locals)
-  // ---- shard plan (shard_cut above); ranks take contiguous runs, balanced by the bytes the index puts under them (by length
-  // without an index)
-  struct ShardPart { size_t rec; uint32_t s0, s1; };
-  struct ShardPlan { size_t rec; uint32_t s0, s1; uint64_t bp; std::vector<uint32_t> iv_starts; /* pileup-hemi: starts of the shard's intervals */
-                     std::vector<ShardPart> parts; /* --include-bed: the BED-span records merged into this shard (empty: one window) */
-                     int64_t own_from = INT64_MIN;
-                       /* full-data sampling from the shards: reads starting before this position lie in the previous shard of the contig too, and are sampled there */ };
-  std::vector<ShardPlan> plan;
+  // the plan's shards (several ranks, contigs larger than a shard, full-data sampling from the shards): same workers, same budget
+  void from_plan(const std::vector<ShardPlan>& plan, const std::vector<Contig>& records, const BedFilter* bf) {
+    if (!rd.dev_ingest || !list.empty() || plan.empty()) return;
+    for (auto& sp : plan) { Shard A; A.tid = records[sp.rec].tid; A.s0 = sp.s0; A.s1 = sp.s1;
+      A.wins = plan_windows(bf, A.tid, sp.s0, sp.s1, sp.parts);
+      A.bytes = bf ? rd.win_bytes(A.tid, A.wins) : rd.bam.offset_at(A.tid, A.s1) - rd.bam.offset_at(A.tid, A.s0) + (1u << 16);
+      list.push_back(std::move(A)); }
+    start();
+  }
+  // shard k once its ingest is done (rethrows what the ingest threw)
+  Shard& wait(size_t k) { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return list[k].ready; });
+    if (list[k].err) std::rethrow_exception(list[k].err); return list[k]; }
+  // the shard loop is through with shard k
+  void release(size_t k) { { std::lock_guard<std::mutex> g(mu); hbm_used -= std::min(hbm_used, list[k].est); } cv.notify_all(); }
+
+ private:
+  const ShardReader& rd; mkp_ctx* ctx; size_t workers_wanted;
+  std::mutex mu; std::condition_variable cv; std::vector<std::thread> workers; std::atomic<bool> stop{false}; std::atomic<size_t> next{0};
+  size_t admit_next = 0; uint64_t hbm_used = 0;   // (under mu)
+  std::vector<mkp_dev_ingest*> extra_ingest;   // workers 1 ..; worker 0 ingests through the context's own
+
+  void start() {
+    if (list.empty() || !workers.empty()) return;
+    est_total = 0; for (auto& A : list) { A.est = est_of(A.bytes); est_total += A.est; }
+    size_t nw = std::min(workers_wanted, list.size());
+    for (size_t w = 1; w < nw; w++) { mkp_dev_ingest* d = mkp_internal_ingest_create(ctx->device); if (!d) break; extra_ingest.push_back(d); }
+    nw = extra_ingest.size() + 1;
+    for (size_t w = 0; w < nw; w++) workers.emplace_back([this, w]() { work(w == 0 ? ctx->ingest : extra_ingest[w - 1]); });
+  }
+  void work(mkp_dev_ingest* ing) {
+    for (;;) {
+      const size_t k = next.fetch_add(1); if (k >= list.size()) break;
+      { std::unique_lock<std::mutex> lk(mu);   // admission in plan order, under the budget
+        cv.wait(lk, [&] { return stop.load() || (admit_next == k && (hbm_used == 0 || hbm_used + list[k].est <= budget)); });
+        if (!stop.load()) { hbm_used += list[k].est; admit_next = k + 1; } }
+      cv.notify_all();
+      ShardInput in; std::exception_ptr err;
+      if (stop.load()) err = std::make_exception_ptr(Error(MKP_E_INVALID, "internal: shard ingest cancelled"));
+      else try { in = rd.fetch(list[k].tid, list[k].wins, ing); } catch (...) { err = std::current_exception(); stop.store(true); }
+      { std::lock_guard<std::mutex> g(mu); list[k].in = std::move(in); list[k].err = err; list[k].ready = true; }
+      cv.notify_all();
+    }
+  }
+};
+
+// The interval grid and focus bytes of every record — filled by the early walk (with one rank, on a thread of its own while the thresholds
+// are estimated: both are all-cores work in short bursts, neither waits for the other's results) or where first needed — and the first
+// shard's records, read and inflated early (behind the threshold estimate; background priority on the host pool, the estimate's own
+// bursts go first).  The destructor joins the walk, then the early fetch the walk may have started.
+struct Grid {
+  std::vector<std::vector<uint8_t>> focus_of; std::vector<char> focus_done;
+  std::vector<std::vector<Interval>> grid_of; std::vector<char> grid_done;
+  double focus_ms = 0;
+  std::future<ShardInput> early_fetch; uint32_t early_s0 = 0, early_s1 = 0; bool early_set = false;
+  bool early_whole = false;   // the early fetch is the one target contig, begun before the grid was walked
+  std::future<void> walk;
+  explicit Grid(size_t n) : focus_of(n), focus_done(n, 0), grid_of(n), grid_done(n, 0) {}
+  ~Grid() { if (walk.valid()) walk.wait(); if (early_fetch.valid()) early_fetch.wait(); }
+  void join_walk() { if (walk.valid()) walk.get(); }   // rethrows what the walk threw
+  void fetch_early(const ShardReader& rd, uint32_t tid, uint32_t s0, uint32_t s1) {
+    early_s0 = s0; early_s1 = s1; early_set = true;
+    early_fetch = std::async(std::launch::async, [&rd, tid, s0, s1]() { return rd.fetch(tid, {{s0, s1}}); });
+  }
+};
+
+// The shard plan (ShardSize::cut); ranks take contiguous runs, balanced by the bytes the index puts under them (by length without an index).
+// Built once, after the early walk is joined (the walker owns grid_of / focus_of until it is done).
+struct Plan {
+  std::vector<ShardPlan> shards;
   // what every rank's shards would hold in HBM if they were all ingested ahead (est_of of each shard's bytes under the index), computed by
   // every rank for every rank: the one thing a rank of a multi-GPU run may base a choice on that the other ranks must make the same way
-  std::vector<uint64_t> est_by_rank(std::max<uint32_t>(a.world, 1u), 0);
-  const bool hf = fb.has_focus();
-  uint64_t positions = 0, processed = 0, skipped = 0, n_shards = 0;
-      double kernel_ms = 0, pack_ms = 0, h2d_ms = 0, d2h_ms = 0, dec_ms = 0, pil_ms = 0, row_ms = 0, write_ms = 0, fetch_wait_ms = 0;
-  bool plan_built = false;
-  auto build_plan = [&]() {
-    if (plan_built) return; plan_built = true;
-    if (early_walk.valid()) early_walk.get();   // (the walker owns grid_of / focus_of until it is done; rethrows what it threw)
+  std::vector<uint64_t> est_by_rank;
+  bool built = false;
+};
+void build_plan(Plan& p, const Args& a, const Knobs& kn, const BamSource& bam, Options& o, Grid& g, const ShardSize& size, bool ahead_listed,
+    const Marks& mark) {
+  if (p.built) return; p.built = true;
+  g.join_walk();
+  const std::vector<Contig>& records = o.records; const BedFilter* bf = o.bf; const bool hf = o.fb.has_focus();
+  std::vector<ShardPlan>& plan = p.shards;
+  p.est_by_rank.assign(std::max<uint32_t>(a.world, 1u), 0);
   {
-      const uint64_t off_lo = records.empty() ? 0 : bam.offset_at(records.front().tid,
-          records.front().start), off_hi = records.empty() ? 0 : bam.offset_at(records.back().tid, records.back().end());
-      bool have_prev = false; uint32_t prev_tid = 0; int64_t prev_fetch_hi = 0;   // the shard before, over ALL ranks' shards: where its fetch ends
-      // end of the last fetch window of a shard [w0, w1) (plan_windows below, before the halo)
-      auto last_window_end = [&](uint32_t tid, uint32_t w0, uint32_t w1) -> int64_t {
-        if (!bf) return w1;
-        uint64_t last = 0; for (auto* m : {&bf->pos, &bf->neg}) { auto it = m->find(tid); if (it == m->end()) continue;
-          for (auto& x : it->second) { const uint64_t lo = std::max<uint64_t>(x.s, w0), hi = std::min<uint64_t>(x.e, w1);
-            if (lo < hi) last = std::max(last, hi);
-            } }
-        return last ? (int64_t)last : (int64_t)w0 + 1;
-      };
-      for (size_t ri = 0; ri < records.size(); ri++) {
-        const Contig& rec = records[ri];
-        auto t_focus = std::chrono::steady_clock::now();
-        // the grid; with one rank the focus bytes are filled in the same walk, otherwise only for the contigs this rank owns (below)
-        std::vector<Interval> ivs;
-        if (grid_done[ri]) ivs.swap(grid_of[ri]);
-        else { ivs = fb.walk(rec, a.interval_size, (hf && a.world == 1) ? &focus_of[ri] : nullptr); if (hf && a.world == 1) focus_done[ri] = 1;
-            focus_ms += ms_since(t_focus); }
-        size_t i0 = 0;
-        while (i0 < ivs.size()) {
-          uint64_t bp = 0; const size_t i1 = shard_cut(rec, ivs, i0, &bp); const uint64_t o0 = bam.offset_at(rec.tid, ivs[i0].start);
-          const uint32_t s0 = ivs[i0].start, s1 = ivs[i1 - 1].end;
-          const uint64_t mid = (o0 + bam.offset_at(rec.tid, s1)) / 2;
-          const uint32_t owner = off_hi > off_lo ? (uint32_t)std::min<uint64_t>(a.world - 1,
-              (mid > off_lo ? mid - off_lo : 0) * a.world / (off_hi - off_lo)) : 0;
-          // the shard's intervals (pileup-hemi: per-interval NoCalls; always: the duplicate-name rule)
-          std::vector<uint32_t> iv_starts; for (size_t k = i0; k < i1; k++) iv_starts.push_back(ivs[k].start);
-          i0 = i1;
-          const int64_t own_from = have_prev && prev_tid == rec.tid ? prev_fetch_hi : INT64_MIN;
-          have_prev = true; prev_tid = rec.tid; prev_fetch_hi = last_window_end(rec.tid, s0, s1) + MKP_HALO;
-          est_by_rank[owner] += est_of(bam.indexed() ? bam.offset_at(rec.tid, s1) - o0 + (1u << 16) : 0);
-          if (owner == a.rank) { plan.push_back({ri, s0, s1, bp, std::move(iv_starts)}); plan.back().own_from = own_from; }
-        }
+    const uint64_t off_lo = records.empty() ? 0 : bam.offset_at(records.front().tid,
+        records.front().start), off_hi = records.empty() ? 0 : bam.offset_at(records.back().tid, records.back().end());
+    bool have_prev = false; uint32_t prev_tid = 0; int64_t prev_fetch_hi = 0;   // the shard before, over ALL ranks' shards: where its fetch ends
+    for (size_t ri = 0; ri < records.size(); ri++) {
+      const Contig& rec = records[ri];
+      auto t_focus = std::chrono::steady_clock::now();
+      // the grid; with one rank the focus bytes are filled in the same walk, otherwise only for the contigs this rank owns (below)
+      std::vector<Interval> ivs;
+      if (g.grid_done[ri]) ivs.swap(g.grid_of[ri]);
+      else { ivs = o.fb.walk(rec, a.interval_size, (hf && a.world == 1) ? &g.focus_of[ri] : nullptr); if (hf && a.world == 1) g.focus_done[ri] = 1;
+          g.focus_ms += ms_since(t_focus); }
+      size_t i0 = 0;
+      while (i0 < ivs.size()) {
+        uint64_t bp = 0; const size_t i1 = size.cut(rec, ivs, i0, &bp); const uint64_t o0 = bam.offset_at(rec.tid, ivs[i0].start);
+        const uint32_t s0 = ivs[i0].start, s1 = ivs[i1 - 1].end;
+        const uint64_t mid = (o0 + bam.offset_at(rec.tid, s1)) / 2;
+        const uint32_t owner = off_hi > off_lo ? (uint32_t)std::min<uint64_t>(a.world - 1,
+            (mid > off_lo ? mid - off_lo : 0) * a.world / (off_hi - off_lo)) : 0;
+        // the shard's intervals (pileup-hemi: per-interval NoCalls; always: the duplicate-name rule)
+        std::vector<uint32_t> iv_starts; for (size_t k = i0; k < i1; k++) iv_starts.push_back(ivs[k].start);
+        i0 = i1;
+        const int64_t own_from = have_prev && prev_tid == rec.tid ? prev_fetch_hi : INT64_MIN;
+        // (where the shard's last fetch window ends, before the halo)
+        have_prev = true; prev_tid = rec.tid; prev_fetch_hi = (int64_t)plan_windows(bf, rec.tid, s0, s1).back().second + MKP_HALO;
+        p.est_by_rank[owner] += AheadIngest::est_of(bam.indexed() ? bam.offset_at(rec.tid, s1) - o0 + (1u << 16) : 0);
+        if (owner == a.rank) { plan.push_back({ri, s0, s1, bp, std::move(iv_starts)}); plan.back().own_from = own_from; }
       }
     }
-    // --include-bed: optimize_reference_records (position_filter.rs:103-210) turns every run of BED spans into a reference record of its own —
-    // hundreds per contig for a sparse BED.  Rows only depend on the focus bytes (BED positions inside the records), not on how records are
-    // grouped, so consecutive records of one contig share a shard: one hull window whose focus is zero between the records, fed by a
-    // multi-window fetch of the records' spans only (what lies between them is neither read nor inflated).
-    if (bf && plan.size() > 1 && !getenv("MKP_NO_BED_MERGE")) {
-      std::vector<ShardPlan> merged; uint64_t bytes = 0;
-      for (auto& sp : plan) {
-        const uint32_t tid = records[sp.rec].tid;
-        const uint64_t sp_bytes = bam.indexed() ? bam.offset_at(tid, sp.s1) - bam.offset_at(tid, sp.s0) + (1u << 16) : 0;
-        const bool join = !merged.empty() && records[merged.back().rec].tid == tid && sp.s0 >= merged.back().s1
-            && (uint64_t)sp.s1 - merged.back().s0 <= shard_bp
-            && (bytes + sp_bytes <= shard_bytes || !ahead.empty() /* its spans were sized when it was ingested ahead */) &&
-                          merged.back().parts.size() < 65536;
-        if (!join) { ShardPlan m = sp; m.parts.assign(1, {sp.rec, sp.s0, sp.s1}); merged.push_back(std::move(m)); bytes = sp_bytes; continue; }
-        ShardPlan& m = merged.back(); m.s1 = sp.s1; m.bp += sp.bp; m.iv_starts.insert(m.iv_starts.end(), sp.iv_starts.begin(), sp.iv_starts.end());
-          m.parts.push_back({sp.rec, sp.s0, sp.s1}); bytes += sp_bytes;
-      }
-      for (auto& m : merged) if (m.parts.size() == 1) m.parts.clear();
-      plan.swap(merged);
+  }
+  // --include-bed: optimize_reference_records (position_filter.rs:103-210) turns every run of BED spans into a reference record of its own —
+  // hundreds per contig for a sparse BED.  Rows only depend on the focus bytes (BED positions inside the records), not on how records are
+  // grouped, so consecutive records of one contig share a shard: one hull window whose focus is zero between the records, fed by a
+  // multi-window fetch of the records' spans only (what lies between them is neither read nor inflated).
+  if (bf && plan.size() > 1 && !kn.no_bed_merge) {
+    std::vector<ShardPlan> merged; uint64_t bytes = 0;
+    for (auto& sp : plan) {
+      const uint32_t tid = records[sp.rec].tid;
+      const uint64_t sp_bytes = bam.indexed() ? bam.offset_at(tid, sp.s1) - bam.offset_at(tid, sp.s0) + (1u << 16) : 0;
+      const bool join = !merged.empty() && records[merged.back().rec].tid == tid && sp.s0 >= merged.back().s1
+          && (uint64_t)sp.s1 - merged.back().s0 <= size.bp
+          && (bytes + sp_bytes <= size.bytes || ahead_listed /* its spans were sized when it was ingested ahead */) &&
+                        merged.back().parts.size() < 65536;
+      if (!join) { ShardPlan m = sp; m.parts.assign(1, {sp.rec, sp.s0, sp.s1}); merged.push_back(std::move(m)); bytes = sp_bytes; continue; }
+      ShardPlan& m = merged.back(); m.s1 = sp.s1; m.bp += sp.bp; m.iv_starts.insert(m.iv_starts.end(), sp.iv_starts.begin(), sp.iv_starts.end());
+        m.parts.push_back({sp.rec, sp.s0, sp.s1}); bytes += sp_bytes;
     }
-    mark("shard plan done");
-  };
-  // the fetch windows of a shard: its window — or, under --include-bed, the BED spans inside its pieces (rows exist at BED positions only;
-  // the records of optimize_reference_records run from one span to the next, most of what lies under them is never looked at)
-  auto plan_windows = [&](const ShardPlan& sp) {
-    std::vector<std::pair<uint32_t, uint32_t>> w;
-    if (!bf) { w.push_back({sp.s0, sp.s1}); return w; }
-    const uint32_t tid = records[sp.rec].tid; std::vector<Span> spn;
-    auto clip = [&](uint32_t a0, uint32_t a1) { for (auto* m : {&bf->pos, &bf->neg}) { auto it = m->find(tid); if (it == m->end()) continue;
-        for (auto& x : it->second) { const uint64_t lo = std::max<uint64_t>(x.s, a0), hi = std::min<uint64_t>(x.e, a1);
-          if (lo < hi) spn.push_back({lo, hi});
-          } } };
-    if (sp.parts.empty()) clip(sp.s0, sp.s1); else for (auto& pt : sp.parts) clip(pt.s0, pt.s1);
-    merge_spans(spn); for (auto& x : spn) w.push_back({(uint32_t)x.s, (uint32_t)x.e});
-    if (w.empty()) w.push_back({sp.s0, sp.s0 + 1});   // (no BED position inside: nothing to fetch but an empty window)
-    return w;
-  };
-  auto fetch_shard = [&](const ShardPlan& sp) { return fetch_windows(records[sp.rec].tid, plan_windows(sp)); };
-  // the plan's shards as the list ingested ahead (several ranks, contigs larger than a shard, full-data sampling from the shards): same
-  // workers, same budget as the contig list above
-  auto ahead_from_plan = [&]() {
-    if (!dev_ingest || !ahead.empty() || plan.empty()) return;
-    for (auto& sp : plan) { Ahead A; A.rec0 = sp.rec; A.rec1 = sp.rec + 1; A.tid = records[sp.rec].tid; A.s0 = sp.s0; A.s1 = sp.s1;
-      A.wins = plan_windows(sp);
-      A.bytes = bf ? win_bytes(A.tid, A.wins) : bam.offset_at(A.tid, A.s1) - bam.offset_at(A.tid, A.s0) + (1u << 16); ahead.push_back(std::move(A)); }
-    start_ahead();
-  };
-  // thresholds (subcommand.rs:615-638)
-  kc.per_mod = per_mod.data(); kc.n_per_mod = (uint32_t)per_mod.size();
-  double thr_ms = 0, fetch_wait_early_ms = 0, grid_wait_ms = 0, callback_ms = 0;
-  // the first shard's records, taken before the loop
-  ShardInput early_in; bool early_in_ready = false, pre_attached = false; std::unique_ptr<DevShard> pre_dev;
+    for (auto& m : merged) if (m.parts.size() == 1) m.parts.clear();
+    plan.swap(merged);
+  }
+  mark("shard plan done");
+}
+
+// Where the run's time and work went: mkp_run_report and the --stats lines
+struct Counters {
+  std::chrono::steady_clock::time_point t_all;
+  double load_ms = 0, thr_ms = 0, fetch_wait_early_ms = 0, grid_wait_ms = 0, callback_ms = 0, fetch_wait_ms = 0;
+  double kernel_ms = 0, pack_ms = 0, h2d_ms = 0, d2h_ms = 0, dec_ms = 0, pil_ms = 0, row_ms = 0, write_ms = 0;
+  uint64_t positions = 0, processed = 0, skipped = 0, n_shards = 0;
+  double ingest_ms[5] = {0, 0, 0, 0, 0}, ingest_kernel_ms = 0; uint64_t ingest_blocks = 0, ingest_records = 0, ingest_comp = 0, ingest_raw = 0;
+  bool resident_used = false;   // the threshold sample came from shards in HBM
+
+  void add_ingest(const DevShard& d) {
+    ingest_ms[0] += d.ms_plan; ingest_ms[1] += d.ms_upload; ingest_ms[2] += d.ms_inflate; ingest_ms[3] += d.ms_pack; ingest_ms[4] += d.ms_digest;
+    ingest_blocks += d.n_blocks; ingest_records += d.n_records; ingest_kernel_ms += d.ms_kernel; ingest_comp += d.comp_bytes; ingest_raw += d.raw_bytes;
+  }
+  void add_shard(mkp_ctx* ctx, uint64_t bp, const mkp_rows& rows) {
+    n_shards++;
+    mkp_stats st; mkp_get_stats(ctx, &st); kernel_ms += st.kernel_ms; dec_ms += st.decode_kernel_ms; pil_ms += st.pileup_kernel_ms;
+      row_ms += st.rows_kernel_ms;
+        pack_ms += st.pack_ms; h2d_ms += st.h2d_ms; d2h_ms += st.d2h_ms;
+    positions += bp; processed += rows.processed_records; skipped += rows.skipped_records;
+  }
+  void report(mkp_run_report* rep, uint64_t n_rows, double focus_ms, const mkp_caller& kc) const {
+    memset(rep, 0, sizeof(*rep));
+    rep->load_ms = load_ms; rep->threshold_ms = thr_ms; rep->focus_ms = focus_ms; rep->pack_ms = pack_ms; rep->h2d_ms = h2d_ms;
+      rep->kernel_ms = kernel_ms;
+        rep->d2h_ms = d2h_ms; rep->write_ms = write_ms;
+    rep->total_ms = ms_since(t_all); rep->n_rows = n_rows; rep->n_positions = positions; rep->n_shards = n_shards; rep->processed_records = processed;
+        rep->skipped_records = skipped;
+    for (int b = 0; b < 4; b++) { rep->threshold[b] = kc.per_base_threshold[b]; rep->has_threshold[b] = kc.has_per_base[b]; }
+    rep->grid_wait_ms = grid_wait_ms; rep->callback_ms = callback_ms; rep->ingest_kernel_ms = ingest_kernel_ms; rep->ingest_upload_ms = ingest_ms[1];
+      rep->ingest_table_ms = ingest_ms[0];
+    rep->ingest_pack_ms = ingest_ms[3]; rep->ingest_comp_bytes = ingest_comp; rep->ingest_raw_bytes = ingest_raw; rep->ingest_blocks = ingest_blocks;
+      rep->ingest_records = ingest_records;
+  }
+  void print_stats(const Args& a, const BamSource& bam, uint64_t n_rows, double focus_ms, bool dev_ingest, const AheadIngest& ahead) const {
+    fprintf(stderr,
+      "[mkpileup] rows=%llu positions=%llu processed~%llu skipped~%llu load_ms=%.1f threshold_ms=%.1f focus_ms=%.1f pack_ms=%.1f h2d_ms=%.1f kernel_ms=%.3f (decode %.3f pileup %.3f rows %.3f) d2h_ms=%.1f write_ms=%.1f total_ms=%.1f shards=%llu indexed=%d bam_bytes_read=%llu bam_bytes_inflated=%llu (on the device %llu) peak_rss_kb=%llu\n",
+                       (unsigned long long)n_rows, (unsigned long long)positions, (unsigned long long)processed, (unsigned long long)skipped, load_ms,
+                           thr_ms, focus_ms, pack_ms, h2d_ms, kernel_ms, dec_ms, pil_ms, row_ms, d2h_ms, write_ms, ms_since(t_all),
+                       (unsigned long long)n_shards, bam.indexed() ? 1 : 0, (unsigned long long)bam.bytes_read.load(),
+                           (unsigned long long)bam.bytes_inflated.load(), (unsigned long long)bam.bytes_inflated_device.load(),
+                           (unsigned long long)peak_rss_kb());
+    // every MKP_* variable that is set: they pick kernels and paths and would otherwise leave no trace in a measurement
+    std::string ov; for (char** e = ::environ; e && *e; e++) if (!strncmp(*e, "MKP_", 4)) { ov += ' '; ov += *e; }
+    fprintf(stderr,
+        "[mkpileup] ingest=%s resident_sampling=%d ahead=%zu shards (estimated %.0f MB, HBM budget %.0f MB) rank=%u/%u env overrides:%s\n",
+        dev_ingest ? "device" : "host", resident_used ? 1 : 0,
+        ahead.size(), (double)ahead.est_total / 1048576.0, (double)ahead.budget / 1048576.0, a.rank, a.world, ov.empty() ? " none" : ov.c_str());
+    if (dev_ingest) fprintf(stderr,
+      "[mkpileup] device ingest: %llu BGZF blocks, %llu records; block plan %.1f ms, upload %.1f, inflate + CRC + chains %.1f, parse + pack %.1f, digest %.1f (overlapped with the threshold estimate / the shard in hand)\n",
+      (unsigned long long)ingest_blocks, (unsigned long long)ingest_records, ingest_ms[0], ingest_ms[1], ingest_ms[2], ingest_ms[3], ingest_ms[4]);
+  }
+};
+
+// The first shard when the threshold estimate took it in hand: its records, or its device records already attached to the context
+struct EarlyShard { ShardInput in; bool in_ready = false, attached = false; std::unique_ptr<DevShard> dev; };
+
+// The one shard of the run is being ingested on the device and every read the schedule can ask for lies in it: the estimate waits for it and
+// samples from HBM (the heads are scans of the shard's digest, a round is one launch over reads that are already packed) instead of fetching,
+// inflating and packing interval heads on the host next to the ingest.  -> the shard attached to the context, or null
+const ShardHost* attach_resident_shard(const Args& a, const BamSource& bam, Options& o, mkp_ctx* ctx, Grid& g, const ShardSize& size,
+    const RegionSpec* sr, EarlyShard& early, Counters& c, const Marks& mark) {
+  const std::vector<Contig>& records = o.records;
+  { const IdxStats stx = idxstats(bam, sr, o.bf);
+    for (auto& kv : stx.mapped_by_tid) if (kv.second && kv.first != (int64_t)records[0].tid) return nullptr; }
+  mark("resident sampling: waiting for the grid");
+  auto t_gw = std::chrono::steady_clock::now();
+  if (g.walk.valid()) g.join_walk();
+  else if (!g.grid_done[0]) { auto t_focus = std::chrono::steady_clock::now();
+    g.grid_of[0] = o.fb.walk(records[0], a.interval_size, o.fb.has_focus() ? &g.focus_of[0] : nullptr); g.grid_done[0] = 1;
+    if (o.fb.has_focus()) g.focus_done[0] = 1; g.focus_ms += ms_since(t_focus); }
+  c.grid_wait_ms += ms_since(t_gw);
+  const std::vector<Interval>& ivs = g.grid_of[0]; uint64_t bp = 0;
+  if (ivs.empty() || size.cut(records[0], ivs, 0, &bp) != ivs.size() || ivs.front().start != g.early_s0 || ivs.back().end != g.early_s1)
+    return nullptr;
+  // the shard is begun and everything of its plan that needs the window alone (slot bitmap, slot positions, their uploads) is made now,
+  // while the ingest is still running
+  mkp_shard sh; memset(&sh, 0, sizeof(sh)); sh.tid = (int32_t)records[0].tid; sh.start = g.early_s0; sh.end = g.early_s1;
+  if (o.fb.has_focus()) { sh.focus = g.focus_of[0].data() + (g.early_s0 - records[0].start); sh.combos = o.fb.combos.data();
+    sh.n_combos = (uint32_t)o.fb.combos.size(); }
+  must(ctx, mkp_shard_begin(ctx, &sh));
+  { std::vector<uint32_t> st; st.reserve(ivs.size()); for (auto& iv : ivs) st.push_back(iv.start);
+    must(ctx, mkp_shard_set_intervals(ctx, st.data(), (uint32_t)st.size())); }
+  if (o.fb.has_focus() && !a.hemi) must(ctx, mkp_internal_shard_preplan(ctx));
+  auto t_w = std::chrono::steady_clock::now();
+  mark("resident sampling: waiting for the ingest");
+  early.in = g.early_fetch.get(); early.in_ready = true;
+  c.fetch_wait_early_ms = ms_since(t_w);
+  mark("resident sampling: ingest in hand");
+  if (!early.in.dev) return nullptr;
+  early.dev = std::move(early.in.dev); early.in_ready = false;
+  must(ctx, mkp_internal_shard_attach(ctx, early.dev.get())); mkp_internal_ingest_recycle(ctx->ingest, early.dev.get());
+  early.attached = true;
+  mark("first shard attached (resident sampling)");
+  return &ctx->shard;
+}
+
+// The threshold estimate (subcommand.rs:615-638) -> kc's per-base thresholds.  The sample comes from the shard attached for it, from the
+// shards ingested ahead (full-data mode: whatever their cut; count-based: when they are the whole contigs), or through the host sampler —
+// unless mkp_pileup_run_cb's callback supplies the thresholds.
+void estimate_thresholds(const Args& a, const Knobs& kn, const BamSource& bam, Options& o, mkp_ctx* ctx, Grid& g, AheadIngest& ahead,
+    const Plan& plan, const ShardSize& size, bool dev_ingest, bool resident_ok, EarlyShard& early, Counters& c, const Marks& mark) {
   const bool full_mode = a.have_frac && a.sampling_frac >= 1.0;
-  const bool want_estimate = a.filter_threshold.empty() && !a.no_filtering && !a.plan_only;
-  const bool resident_ok = !have_sregion && !a.include_unmapped && !getenv("MKP_NO_RESIDENT_SAMPLING");
-  const bool ahead_whole_contigs = !ahead.empty();   // (the list made above holds whole contigs; the plan's shards may be pieces of them)
-  bool resident_used = pre_attached;
-  // The plan comes before the thresholds — and its shards go ahead — when nothing is gained by waiting for them: several ranks (a rank needs
-  // its own shards whatever the thresholds turn out to be, and the others' estimate or all-reduce is time to ingest in), thresholds given,
-  // or a full-data estimate, which samples from the shards themselves.
-  if (dev_ingest && !early_whole && ahead.empty() && !getenv("MKP_NO_AHEAD") && (a.world > 1 || !want_estimate || (full_mode && resident_ok))) {
-    build_plan(); ahead_from_plan(); }
-  if (!a.filter_threshold.empty()) parse_base_thresholds(a.filter_threshold, &kc);
-  else if (a.no_filtering || a.plan_only) { kc.n_per_mod = 0; }  // MultipleThresholdModCaller::new_passthrough
-  else {
-    auto t0 = std::chrono::steady_clock::now();
-    must(mkp_set_caller(ctx, &kc));  // collapse + edge filter apply to the sampled probabilities too
-    const RegionSpec* sr = have_sregion ? &sregion : (have_region ? &region : nullptr);
-    // a rank of a multi-GPU run that was not handed thresholds (--filter-threshold from the all-reduced histograms, see
-    // modkit_amd.distributed) estimates them alone over the whole file: correct, but every rank repeats the work
-    Args as = a; as.world = 1; as.rank = 0;
-    must(mkp_histogram_begin(ctx));
-    g_sample_times = SampleTimes();
-    // mkp_pileup_run_cb: in the count-based modes the caller supplies the thresholds (one rank estimates, all ranks receive: the schedule
-    // carries quotas from interval to interval and does not shard) — nothing is sampled here, and this rank's shards are being ingested
-    // meanwhile; in the full-data mode this rank samples its own shards and the caller reduces the histograms over the ranks
-    const bool cb_supplies = a.thr_cb && !full_mode;
-    if (!cb_supplies) {
-    // The one shard of the run is being ingested on the device and every read the schedule can ask for lies in it: the estimate waits for
-    // it and samples from HBM (the heads are scans of the shard's digest, a round is one launch over reads that are already packed)
-    // instead of fetching, inflating and packing interval heads on the host next to the ingest.
-    const ShardHost* resident = nullptr;
-    if (early_whole && !have_sregion && !a.include_unmapped && !getenv("MKP_NO_RESIDENT_SAMPLING")) {
-      bool only_this = true; { const IdxStats stx = idxstats(bam, sr, bf);
-        for (auto& kv : stx.mapped_by_tid) if (kv.second && kv.first != (int64_t)records[0].tid) only_this = false;
-        }
-      if (only_this) {
-        mark("resident sampling: waiting for the grid");
-        auto t_gw = std::chrono::steady_clock::now();
-        if (early_walk.valid()) early_walk.get();
-        else if (!grid_done[0]) { auto t_focus = std::chrono::steady_clock::now();
-          grid_of[0] = fb.walk(records[0], a.interval_size, fb.has_focus() ? &focus_of[0] : nullptr); grid_done[0] = 1;
-          if (fb.has_focus()) focus_done[0] = 1; focus_ms += ms_since(t_focus); }
-        grid_wait_ms += ms_since(t_gw);
-        const std::vector<Interval>& ivs = grid_of[0]; uint64_t bp = 0;
-        if (!ivs.empty() && shard_cut(records[0], ivs, 0, &bp) == ivs.size() && ivs.front().start == early_s0 && ivs.back().end == early_s1) {
-          // the shard is begun and everything of its plan that needs the window alone (slot bitmap, slot positions, their uploads) is
-          // made now, while the ingest is still running
-          mkp_shard sh; memset(&sh, 0, sizeof(sh)); sh.tid = (int32_t)records[0].tid; sh.start = early_s0; sh.end = early_s1;
-          if (fb.has_focus()) { sh.focus = focus_of[0].data() + (early_s0 - records[0].start); sh.combos = fb.combos.data();
-            sh.n_combos = (uint32_t)fb.combos.size(); }
-          must(mkp_shard_begin(ctx, &sh));
-          { std::vector<uint32_t> st; st.reserve(ivs.size()); for (auto& iv : ivs) st.push_back(iv.start);
-            must(mkp_shard_set_intervals(ctx, st.data(), (uint32_t)st.size())); }
-          if (fb.has_focus() && !a.hemi) must(mkp_internal_shard_preplan(ctx));
-          auto t_w = std::chrono::steady_clock::now();
-          mark("resident sampling: waiting for the ingest");
-          early_in = early_fetch.get(); early_in_ready = true;
-          fetch_wait_early_ms = ms_since(t_w);
-          mark("resident sampling: ingest in hand");
-          if (early_in.dev) {
-            pre_dev = std::move(early_in.dev); early_in_ready = false;
-            must(mkp_internal_shard_attach(ctx, pre_dev.get())); mkp_internal_ingest_recycle(ctx->ingest, pre_dev.get());
-            pre_attached = true; resident = &ctx->shard;
-            mark("first shard attached (resident sampling)");
-          }
-        }
-      }
-    }
+  auto t0 = std::chrono::steady_clock::now();
+  must(ctx, mkp_set_caller(ctx, &o.kc));  // collapse + edge filter apply to the sampled probabilities too
+  const RegionSpec* sr = o.have_sregion ? &o.sregion : o.region_or_null();
+  // a rank of a multi-GPU run that was not handed thresholds (--filter-threshold from the all-reduced histograms, see
+  // modkit_amd.distributed) estimates them alone over the whole file: correct, but every rank repeats the work
+  Args as = a; as.world = 1; as.rank = 0;
+  must(ctx, mkp_histogram_begin(ctx));
+  g_sample_times = SampleTimes();
+  // mkp_pileup_run_cb: in the count-based modes the caller supplies the thresholds (one rank estimates, all ranks receive: the schedule
+  // carries quotas from interval to interval and does not shard) — nothing is sampled here, and this rank's shards are being ingested
+  // meanwhile; in the full-data mode this rank samples its own shards and the caller reduces the histograms over the ranks
+  const bool cb_supplies = a.thr_cb && !full_mode;
+  if (!cb_supplies) {
+    const ShardHost* resident = g.early_whole && resident_ok ? attach_resident_shard(a, bam, o, ctx, g, size, sr, early, c, mark) : nullptr;
     ResidentOf resident_of;
     DevShard* bound = nullptr;   // multi-shard resident sampling: the shard currently swapped into the context
     struct Unbind { mkp_ctx* c; DevShard** b; ~Unbind() { if (*b) { (void)mkp_internal_sample_bind(c, *b); *b = nullptr; } } } unbind{ctx, &bound};
     auto bind_ahead = [&](size_t k) -> const ShardHost* {
       auto t_w = std::chrono::steady_clock::now();
-      Ahead& A = ahead_wait(k);
-      fetch_wait_early_ms += ms_since(t_w);
+      AheadIngest::Shard& A = ahead.wait(k);
+      c.fetch_wait_early_ms += ms_since(t_w);
       if (!A.in.dev) throw Error(MKP_E_INVALID, "internal: shard ingested ahead without device records");
-      if (bound != A.in.dev.get()) { if (bound) must(mkp_internal_sample_bind(ctx, bound)); bound = nullptr;
-        must(mkp_internal_sample_bind(ctx, A.in.dev.get())); bound = A.in.dev.get(); }
+      if (bound != A.in.dev.get()) { if (bound) must(ctx, mkp_internal_sample_bind(ctx, bound)); bound = nullptr;
+        must(ctx, mkp_internal_sample_bind(ctx, A.in.dev.get())); bound = A.in.dev.get(); }
       return &ctx->shard;
     };
     // every shard stays in HBM until the loop takes it: the sample can come from them
-    const bool ahead_fits = !ahead.empty() && ahead_est_total <= hbm_budget;
+    const bool ahead_fits = !ahead.empty() && ahead.est_total <= ahead.budget;
     // the extent the sampler covers on a contig: the region, or all of it
-    auto ext_of = [&](uint32_t tid, int64_t* lo, int64_t* hi) { if (have_region) { *lo = region.start; *hi = region.end; } else { *lo = 0;
+    auto ext_of = [&](uint32_t tid, int64_t* lo, int64_t* hi) { if (o.have_region) { *lo = o.region.start; *hi = o.region.end; } else { *lo = 0;
         *hi = bam.ref_lens[tid]; } };
     // Several ranks in the full-data mode (mkp_pileup_run_cb): the ranks' samples are summed by the caller, so every rank must cut the reads the
     // same way — by shard ownership (own_from) when the shards are the source, by sampling intervals when the host reader is.  The two cuts do
@@ -1155,28 +1215,28 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
     // its budget (est_by_rank: the same arithmetic on the same index on every rank; the budget and MKP_NO_AHEAD must be the ranks' common
     // setting, like the flags).  A rank without shards then contributes an empty sample (it used to sample its bp-share of the
     // sampling intervals, reads the other ranks' shards had already counted).
-    bool all_ranks_resident = dev_ingest && plan_built && !getenv("MKP_NO_AHEAD") && !early_whole;
-    for (uint64_t e : est_by_rank) if (e > hbm_budget) all_ranks_resident = false;
+    bool all_ranks_resident = dev_ingest && plan.built && !kn.no_ahead && !g.early_whole;
+    for (uint64_t e : plan.est_by_rank) if (e > ahead.budget) all_ranks_resident = false;
     const bool shards_are_the_sample = a.world > 1 ? (a.thr_cb && all_ranks_resident) : ahead_fits;
     if (full_mode && resident_ok && (resident || shards_are_the_sample)) {
       // full-data mode: the shards themselves are the sample's source, whatever their cut — with several ranks (mkp_pileup_run_cb) each
       // rank its own, the caller sums the histograms
       std::vector<FullShard> fs;
-      if (resident) { FullShard f; f.tid = records[0].tid; f.own_from = INT64_MIN; ext_of(f.tid, &f.ext_lo, &f.ext_hi); f.bind = [&]() {
+      if (resident) { FullShard f; f.tid = o.records[0].tid; f.own_from = INT64_MIN; ext_of(f.tid, &f.ext_lo, &f.ext_hi); f.bind = [&]() {
           return resident; }; fs.push_back(std::move(f)); }
-      else for (size_t k = 0; k < ahead.size(); k++) { FullShard f; f.tid = ahead[k].tid;
-        f.own_from = ahead_whole_contigs ? INT64_MIN : plan[k].own_from; ext_of(f.tid, &f.ext_lo, &f.ext_hi);
+      else for (size_t k = 0; k < ahead.size(); k++) { FullShard f; f.tid = ahead.list[k].tid;
+        f.own_from = ahead.whole_contigs ? INT64_MIN : plan.shards[k].own_from; ext_of(f.tid, &f.ext_lo, &f.ext_hi);
           f.bind = [&, k]() { return bind_ahead(k); }; fs.push_back(std::move(f)); }
-      sample_resident_full(ctx, bam, bf, fs);
-      resident_used = true;
+      sample_resident_full(ctx, bam, o.bf, fs);
+      c.resident_used = true;
       if (a.stats) fprintf(stderr, "[mkpileup] full-data threshold sample taken from %zu resident shard(s)%s\n", fs.size(),
           a.world > 1 ? " of this rank" : "");
     } else {
     if (resident) resident_of = [&](uint32_t) { return resident; };
-    else if (ahead_fits && ahead_whole_contigs && resident_ok && a.world == 1) {
+    else if (ahead_fits && ahead.whole_contigs && resident_ok && a.world == 1) {
       // every contig the schedule can visit must be among the shards ingested ahead
-      std::map<uint32_t, size_t> by_tid; for (size_t k = 0; k < ahead.size(); k++) by_tid[ahead[k].tid] = k;
-      bool covered = true; { const IdxStats stx = idxstats(bam, sr, bf);
+      std::map<uint32_t, size_t> by_tid; for (size_t k = 0; k < ahead.size(); k++) by_tid[ahead.list[k].tid] = k;
+      bool covered = true; { const IdxStats stx = idxstats(bam, sr, o.bf);
         for (auto& kv : stx.mapped_by_tid) if (kv.second && !by_tid.count((uint32_t)kv.first)) covered = false;
         }
       // (a region run: the one record is the region; a BED run: a contig's shard holds the records reaching its BED spans, which are the only ones
@@ -1188,59 +1248,87 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
     }
     // (a rank of mkp_pileup_run_cb's full-data mode whose shards are not resident — an unindexed BAM, a budget too small — samples its own
     // sampling intervals through the host reader, as round 4 did)
-    sample_probabilities(ctx, bam, (a.thr_cb && full_mode) ? a : as, sr, bf, resident_of);
-    if (resident_of) resident_used = true;
+    sample_probabilities(ctx, bam, (a.thr_cb && full_mode) ? a : as, sr, o.bf, resident_of);
+    if (resident_of) c.resident_used = true;
     if (a.stats && resident_of && !resident) fprintf(stderr, "[mkpileup] threshold estimate sampled from %zu shards ingested ahead (resident)\n",
         ahead.size());
     }
-    if (bound) { must(mkp_internal_sample_bind(ctx, bound)); bound = nullptr; }
+    if (bound) { must(ctx, mkp_internal_sample_bind(ctx, bound)); bound = nullptr; }
     mark("schedule walked, sample in HBM");
     if (a.stats) fprintf(stderr,
         "[mkpileup] threshold sampling: head fetch wait %.1f ms, device rounds %llu (%llu reads) %.1f ms, first-N logic %.1f ms\n",
         g_sample_times.fetch_ms, (unsigned long long)g_sample_times.rounds, (unsigned long long)g_sample_times.reads, g_sample_times.device_ms,
         g_sample_times.decide_ms);
+  }
+  { float thr[4] = {0, 0, 0, 0}; uint8_t has[4] = {0, 0, 0, 0};
+    if (a.thr_cb) { auto t_cb = std::chrono::steady_clock::now(); const int rc = a.thr_cb(a.thr_cb_user, ctx, cb_supplies ? 0 : 1, thr, has);
+      c.callback_ms = ms_since(t_cb);
+      if (rc != MKP_OK) throw Error(rc, "the threshold callback failed"); mark("thresholds from the callback"); }
+    else thresholds_from_sample(ctx, a.filter_percentile, thr, has, a.stats);
+    for (int b = 0; b < 4; b++) if (has[b]) { o.kc.has_per_base[b] = 1; o.kc.per_base_threshold[b] = thr[b]; } }
+  c.thr_ms = ms_since(t0) - c.fetch_wait_early_ms - c.grid_wait_ms - c.callback_ms;
+}
+
+// Where the rows go: one bedMethyl file (plain or BGZF + index), one per --partition-tag key in a directory, or --bedgraph files
+class Outputs {
+ public:
+  // the checks throw in the order of the flags' resolution (subcommand.rs:328-363 for --bedgraph)
+  Outputs(const Args& a, mkp_ctx* ctx, const std::vector<std::string>& labels) : a(a), partitioned(!a.partition_tags.empty()) {
+    wr.mixed = a.mixed_delim; wr.labels = labels;
+    if (a.bedgraph) {   // (no header, no mixed delimiters; the path is a directory)
+      if (a.with_header || a.mixed_delim || a.bgzf || a.hemi || a.plan_only) throw Error(MKP_E_INVALID,
+          "--bedgraph cannot be combined with --with-header, --mixed-delim, --bgzf or --plan-only");
+      if (a.out_bed.empty() || a.out_bed == "-" || a.out_bed == "stdout") throw Error(MKP_E_INVALID, "--bedgraph needs an output directory");
+      if (partitioned) set_partition_tags(ctx);
+      make_dir();
+      bg.dir = a.out_bed; bg.prefix = a.prefix; bg.groupings = partitioned; bg.labels = wr.labels;
+    } else if (partitioned) {   // a directory with one bedMethyl per key, `[<prefix>_]<key>.bed` (PartitioningBedMethylWriter, writers.rs:1005-1082)
+      if (a.with_header) throw Error(MKP_E_INVALID, "--with-header cannot be combined with --partition-tag");
+      if (a.plan_only) throw Error(MKP_E_INVALID, "--plan-only has no partitioned form");
+      set_partition_tags(ctx);
+      make_dir();
+    } else {
+      wr.f = (a.out_bed == "-" || a.out_bed == "stdout" || (a.hemi && a.out_bed.empty())) ? stdout : fopen(a.out_bed.c_str(), "w+");
+      if (!wr.f) throw Error(MKP_E_IO, "failed to make output file " + a.out_bed);
+      if (a.bgzf) {
+        if (wr.f == stdout || a.with_header || a.plan_only) throw Error(MKP_E_INVALID,
+            "--bgzf writes a file and its index: it needs an output path and goes without --with-header");
+        wr.bz.reset(new BgzfTabixSink()); wr.bz->f = wr.f; wr.bz->index_path = a.out_bed + ".tbi";
+      }
     }
-    { float thr[4] = {0, 0, 0, 0}; uint8_t has[4] = {0, 0, 0, 0};
-      if (a.thr_cb) { auto t_cb = std::chrono::steady_clock::now(); const int rc = a.thr_cb(a.thr_cb_user, ctx, cb_supplies ? 0 : 1, thr, has);
-        callback_ms = ms_since(t_cb);
-        if (rc != MKP_OK) throw Error(rc, "the threshold callback failed"); mark("thresholds from the callback"); }
-      else thresholds_from_sample(ctx, a.filter_percentile, thr, has, a.stats);
-      for (int b = 0; b < 4; b++) if (has[b]) { kc.has_per_base[b] = 1; kc.per_base_threshold[b] = thr[b]; } }
-    thr_ms = ms_since(t0) - fetch_wait_early_ms - grid_wait_ms - callback_ms;
+    if (a.bgzf && partitioned) throw Error(MKP_E_INVALID, "--bgzf has no partitioned form");
+    if (a.with_header) fputs("chrom\tchromStart\tchromEnd\tname\tscore\tstrand\tthickStart\tthickEnd\tcolor\tvalid_coverage\tpercent_modified\tcount_modified\tcount_canonical\tcount_other_mod\tcount_delete\tcount_fail\tcount_diff\tcount_nocall\n",
+        wr.f);
   }
-  mark("thresholds done");
-  if (!a.plan_only) must(mkp_set_caller(ctx, &kc));
-  if (early_walk.valid()) early_walk.get();   // rethrows what the walk threw
-  // --partition-tag: the output path is a directory with one bedMethyl per key, `[<prefix>_]<key>.bed` (PartitioningBedMethylWriter,
-  // writers.rs:1005-1082)
-  const bool partitioned = !a.partition_tags.empty();
-  std::map<std::string, std::unique_ptr<RowWriter>> key_writers;
-  BedGraphOut bg;
-  if (a.bedgraph) {   // (subcommand.rs:328-363: no header, no mixed delimiters; the path is a directory)
-    if (a.with_header || a.mixed_delim || a.bgzf || a.hemi || a.plan_only) throw Error(MKP_E_INVALID,
-        "--bedgraph cannot be combined with --with-header, --mixed-delim, --bgzf or --plan-only");
-    if (a.out_bed.empty() || a.out_bed == "-" || a.out_bed == "stdout") throw Error(MKP_E_INVALID, "--bedgraph needs an output directory");
-    if (partitioned) { std::vector<const char*> tp; for (auto& t : a.partition_tags) tp.push_back(t.c_str());
-      must(mkp_set_partition_tags(ctx, tp.data(), (uint32_t)tp.size())); }
-    if (mkdir(a.out_bed.c_str(), 0777) != 0 && errno != EEXIST) throw Error(MKP_E_IO, "failed to make output directory " + a.out_bed);
-    bg.dir = a.out_bed; bg.prefix = a.prefix; bg.groupings = partitioned; bg.labels = wr.labels;
-  } else if (partitioned) {
-    if (a.with_header) throw Error(MKP_E_INVALID, "--with-header cannot be combined with --partition-tag");
-    if (a.plan_only) throw Error(MKP_E_INVALID, "--plan-only has no partitioned form");
-    { std::vector<const char*> tp; for (auto& t : a.partition_tags) tp.push_back(t.c_str());
-      must(mkp_set_partition_tags(ctx, tp.data(), (uint32_t)tp.size())); }
-    if (mkdir(a.out_bed.c_str(), 0777) != 0 && errno != EEXIST) throw Error(MKP_E_IO, "failed to make output directory " + a.out_bed);
-  } else {
-  wr.f = (a.out_bed == "-" || a.out_bed == "stdout" || (a.hemi && a.out_bed.empty())) ? stdout : fopen(a.out_bed.c_str(), "w+");
-  if (!wr.f) throw Error(MKP_E_IO, "failed to make output file " + a.out_bed);
-  if (a.bgzf) {
-    if (wr.f == stdout || a.with_header || a.plan_only) throw Error(MKP_E_INVALID,
-        "--bgzf writes a file and its index: it needs an output path and goes without --with-header");
-    wr.bz.reset(new BgzfTabixSink()); wr.bz->f = wr.f; wr.bz->index_path = a.out_bed + ".tbi";
+  FILE* file() const { return wr.f; }   // (--plan-only: the plan TSV)
+  uint64_t rows() const { return wr.n; }
+  void write(const std::string& chrom, const mkp_rows& rows) {
+    if (a.bedgraph) { bg.write(chrom, rows); wr.n += rows.n_rows; }
+    else if (!partitioned) wr.write(chrom, rows);
+    else for (uint64_t i0r = 0; i0r < rows.n_rows;) {   // rows come grouped by key: one slice per key
+      uint64_t i1r = i0r; while (i1r < rows.n_rows && rows.partition_key[i1r] == rows.partition_key[i0r]) i1r++;
+      mkp_rows v = rows; v.n_rows = i1r - i0r; v.pos += i0r; v.strand += i0r; v.code_repr += i0r; v.motif_idx += i0r; v.n_valid += i0r;
+        v.n_mod += i0r;
+          v.n_canonical += i0r; v.n_other += i0r;
+      v.n_delete += i0r; v.n_fail += i0r; v.n_diff += i0r; v.n_nocall += i0r; v.partition_key += i0r;
+      const uint32_t k = rows.partition_key[i0r];
+      RowWriter& kw = writer_for(k < rows.n_partition_keys ? rows.partition_key_names[k] : "not_found"); kw.write(chrom, v); wr.n += v.n_rows;
+      i0r = i1r;
+    }
   }
+  void write_hemi(const std::string& chrom, const mkp_hemi_rows& rows) { wr.write_hemi(chrom, rows); }
+  void finish() {
+    bg.finish(); wr.finish(); for (auto& kv : key_writers) { kv.second->finish(); fclose(kv.second->f); }
   }
-  if (a.bgzf && partitioned) throw Error(MKP_E_INVALID, "--bgzf has no partitioned form");
-  auto writer_for = [&](const std::string& key) -> RowWriter& {
+  void close() { if (wr.f && wr.f != stdout) fclose(wr.f); }
+
+ private:
+  const Args& a; const bool partitioned;
+  RowWriter wr; BedGraphOut bg; std::map<std::string, std::unique_ptr<RowWriter>> key_writers;
+  void set_partition_tags(mkp_ctx* ctx) { std::vector<const char*> tp; for (auto& t : a.partition_tags) tp.push_back(t.c_str());
+    must(ctx, mkp_set_partition_tags(ctx, tp.data(), (uint32_t)tp.size())); }
+  void make_dir() { if (mkdir(a.out_bed.c_str(), 0777) != 0 && errno != EEXIST) throw Error(MKP_E_IO, "failed to make output directory " + a.out_bed); }
+  RowWriter& writer_for(const std::string& key) {
     auto it = key_writers.find(key);
     if (it == key_writers.end()) {
       std::unique_ptr<RowWriter> w(new RowWriter()); w->mixed = a.mixed_delim; w->labels = wr.labels;
@@ -1249,167 +1337,195 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
       it = key_writers.emplace(key, std::move(w)).first;
     }
     return *it->second;
-  };
-  if (a.with_header) fputs("chrom\tchromStart\tchromEnd\tname\tscore\tstrand\tthickStart\tthickEnd\tcolor\tvalid_coverage\tpercent_modified\tcount_modified\tcount_canonical\tcount_other_mod\tcount_delete\tcount_fail\tcount_diff\tcount_nocall\n",
-      wr.f);
-  build_plan();
-  // (thresholds known before the plan: the shards go ahead of the loop from here)
-  if (ahead.empty() && plan.size() > 1 && !getenv("MKP_NO_AHEAD")) ahead_from_plan();
+  }
+};
+
+// --plan-only: a host-only dry run of one shard — its plan line, plus the packer over its records (no device)
+void plan_only_shard(const Args& a, const Contig& rec, uint32_t s0, uint32_t s1, const std::vector<mkp_record>& recs, FILE* out, Counters& c) {
+  static std::vector<ShardHost> kept_pieces;   // the all-cores pack's per-thread buffers persist across shards, as they do in a context
+  Packer pk; pk.pieces.swap(kept_pieces); ShardHost S; S.tid = (int32_t)rec.tid; S.win_start = (int32_t)s0; S.win_end = (int32_t)s1;
+  const int32_t tid = (int32_t)rec.tid; auto t_pk = std::chrono::steady_clock::now();
+  // --plan-pack-min N: records from which the packer runs on all cores (0 = always; default as in mkp_shard_add_records)
+  pack_records(pk, S, recs.data(), (uint32_t)recs.size(), [tid](const mkp_record& r) { return r.tid == tid && Packer::keep(r);
+    }, a.plan_pack_min);
+  c.pack_ms += ms_since(t_pk); kept_pieces.swap(pk.pieces);
+  // digest of everything the packer hands to the device: a parallel pack must equal the sequential one byte for byte
+  uint64_t dg = 1469598103934665603ull;
+  auto mix = [&](const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for (size_t i = 0; i < n; i++) { dg ^= b[i];
+      dg *= 1099511628211ull; } };
+  mix(S.hdr.data(), S.hdr.size() * sizeof(MkpReadHdr)); mix(S.cigar.data(), S.cigar.size() * 4);
+    mix(S.chunk_pfx.data(), S.chunk_pfx.size() * 4);
+      mix(S.seq.data(), S.seq.size());
+  mix(S.tagref.data(), S.tagref.size() * sizeof(MkpTagRef)); mix(S.ranks.data(), S.ranks.size() * 4); mix(S.ml.data(), S.ml.size());
+      mix(S.name_hash.data(), S.name_hash.size() * 8);
+  for (auto& k : pk.layout_keys) mix(k.data(), k.size());
+  fprintf(out, "%s\t%u\t%u\t%zu\t%llu\t%016llx\n", rec.name.c_str(), s0, s1, S.hdr.size(), (unsigned long long)S.n_calls,
+      (unsigned long long)dg);
+}
+
+// The shard loop: every shard of the plan fetched (or taken from those ingested ahead / the one attached for the estimate), packed, run on
+// the device and written.  Double buffering: the next shard's blocks are read and inflated while this one is packed, run and written.
+void run_shards(const Args& a, Options& o, mkp_ctx* ctx, const ShardReader& reader, Grid& g, AheadIngest& ahead, const Plan& p,
+    EarlyShard& early, Outputs& out, Counters& c, const Marks& mark) {
+  const std::vector<ShardPlan>& plan = p.shards; const std::vector<Contig>& records = o.records; const bool hf = o.fb.has_focus();
+  auto fetch_shard = [&](const ShardPlan& sp) { const uint32_t tid = records[sp.rec].tid;
+    return reader.fetch(tid, plan_windows(o.bf, tid, sp.s0, sp.s1, sp.parts)); };
   // shards that were ingested ahead: same contig, same hull, same windows
   std::vector<long> plan_ahead(plan.size(), -1);
-  for (size_t pi = 0; pi < plan.size(); pi++) for (size_t k = 0; k < ahead.size(); k++)
-    if (ahead[k].tid == records[plan[pi].rec].tid && ahead[k].s0 == plan[pi].s0 && ahead[k].s1 == plan[pi].s1
-        && ahead[k].wins == plan_windows(plan[pi])) {
-      plan_ahead[pi] = (long)k; break; }
-  // double buffering: the next shard's blocks are read and inflated while this one is packed, run and written
+  for (size_t pi = 0; pi < plan.size(); pi++) for (size_t k = 0; k < ahead.size(); k++) {
+    const AheadIngest::Shard& A = ahead.list[k]; const uint32_t tid = records[plan[pi].rec].tid;
+    if (A.tid == tid && A.s0 == plan[pi].s0 && A.s1 == plan[pi].s1 && A.wins == plan_windows(o.bf, tid, plan[pi].s0, plan[pi].s1, plan[pi].parts)) {
+      plan_ahead[pi] = (long)k; break; } }
   std::future<ShardInput> next_batch;
-  const bool early_match = early_set && !plan.empty() && plan[0].rec == 0 && plan[0].s0 == early_s0 && plan[0].s1 == early_s1;
-  if (pre_attached && !(early_match && plan.size() == 1)) throw Error(MKP_E_INVALID,
+  const bool early_match = g.early_set && !plan.empty() && plan[0].rec == 0 && plan[0].s0 == g.early_s0 && plan[0].s1 == g.early_s1;
+  if (early.attached && !(early_match && plan.size() == 1)) throw Error(MKP_E_INVALID,
       "internal: the shard attached for resident sampling is not the plan's");
   // (what the estimate waited for shards ingested ahead is load time too)
-  if (pre_attached || !ahead.empty()) { fetch_wait_ms += fetch_wait_early_ms; }
-  else if (early_match && early_in_ready) { fetch_wait_ms += fetch_wait_early_ms; next_batch = std::async(std::launch::deferred, [&]() {
-      return std::move(early_in); }); }
-  else if (early_match && early_fetch.valid()) next_batch = std::move(early_fetch);
-  else { if (early_fetch.valid()) early_fetch.wait();
+  if (early.attached || !ahead.empty()) { c.fetch_wait_ms += c.fetch_wait_early_ms; }
+  else if (early_match && early.in_ready) { c.fetch_wait_ms += c.fetch_wait_early_ms; next_batch = std::async(std::launch::deferred, [&]() {
+      return std::move(early.in); }); }
+  else if (early_match && g.early_fetch.valid()) next_batch = std::move(g.early_fetch);
+  else { if (g.early_fetch.valid()) g.early_fetch.wait();
     if (!plan.empty() && plan_ahead[0] < 0) next_batch = std::async(std::launch::async, fetch_shard, plan[0]);
     }
   for (size_t pi = 0; pi < plan.size(); pi++) {
-    const ShardPlan& sp = plan[pi]; const Contig& rec = records[sp.rec]; const uint32_t s0 = sp.s0, s1 = sp.s1; const uint64_t bp = sp.bp;
+    const ShardPlan& sp = plan[pi]; const Contig& rec = records[sp.rec]; const uint32_t s0 = sp.s0, s1 = sp.s1;
     std::unique_ptr<BamBatch> batch; std::unique_ptr<DevShard> dev;
-    const bool attached_already = pre_attached && pi == 0;
+    const bool attached_already = early.attached && pi == 0;
     // the shard's bytes go back to the budget when this iteration is over
-    struct Release { decltype(ahead_release)& rel; long k; ~Release() { if (k >= 0) rel((size_t)k); } } release_shard{ahead_release, plan_ahead[pi]};
-    if (attached_already) dev = std::move(pre_dev);
-    else if (plan_ahead[pi] >= 0) { auto t_f = std::chrono::steady_clock::now(); Ahead& A = ahead_wait((size_t)plan_ahead[pi]);
-      batch = std::move(A.in.batch); dev = std::move(A.in.dev); fetch_wait_ms += ms_since(t_f); }
+    struct Release { AheadIngest& ahead; long k; ~Release() { if (k >= 0) ahead.release((size_t)k); } } release_shard{ahead, plan_ahead[pi]};
+    if (attached_already) dev = std::move(early.dev);
+    else if (plan_ahead[pi] >= 0) { auto t_f = std::chrono::steady_clock::now(); AheadIngest::Shard& A = ahead.wait((size_t)plan_ahead[pi]);
+      batch = std::move(A.in.batch); dev = std::move(A.in.dev); c.fetch_wait_ms += ms_since(t_f); }
     else { auto t_f = std::chrono::steady_clock::now(); ShardInput in = next_batch.get(); batch = std::move(in.batch); dev = std::move(in.dev);
-      fetch_wait_ms += ms_since(t_f); }
-    if (dev) { ingest_ms[0] += dev->ms_plan; ingest_ms[1] += dev->ms_upload; ingest_ms[2] += dev->ms_inflate; ingest_ms[3] += dev->ms_pack;
-      ingest_ms[4] += dev->ms_digest; ingest_blocks += dev->n_blocks;
-               ingest_records += dev->n_records; ingest_kernel_ms += dev->ms_kernel; ingest_comp += dev->comp_bytes; ingest_raw += dev->raw_bytes; }
+      c.fetch_wait_ms += ms_since(t_f); }
+    if (dev) c.add_ingest(*dev);
     if (pi + 1 < plan.size() && plan_ahead[pi + 1] < 0) next_batch = std::async(std::launch::async, fetch_shard, plan[pi + 1]);
     std::vector<uint8_t> merged_focus;   // a merged shard: its records' focus bytes at their places in the hull, zero in between
     if (hf) for (size_t k = 0; k < std::max<size_t>(sp.parts.size(), 1); k++) { const size_t ri = sp.parts.empty() ? sp.rec : sp.parts[k].rec;
-      if (!focus_done[ri]) { auto t_focus = std::chrono::steady_clock::now(); fb.walk(records[ri], a.interval_size, &focus_of[ri]);
-        focus_done[ri] = 1; focus_ms += ms_since(t_focus); } }
-    if (sp.rec > 0 && (pi == 0 || plan[pi - 1].rec != sp.rec)) for (size_t r2 = 0; r2 < sp.rec; r2++) { std::vector<uint8_t>().swap(focus_of[r2]);
+      if (!g.focus_done[ri]) { auto t_focus = std::chrono::steady_clock::now(); o.fb.walk(records[ri], a.interval_size, &g.focus_of[ri]);
+        g.focus_done[ri] = 1; g.focus_ms += ms_since(t_focus); } }
+    if (sp.rec > 0 && (pi == 0 || plan[pi - 1].rec != sp.rec)) for (size_t r2 = 0; r2 < sp.rec; r2++) { std::vector<uint8_t>().swap(g.focus_of[r2]);
         }   // earlier contigs are done
     if (hf && !sp.parts.empty()) { merged_focus.assign((size_t)(s1 - s0), 0);
-      for (auto& pt : sp.parts) memcpy(merged_focus.data() + (pt.s0 - s0), focus_of[pt.rec].data() + (pt.s0 - records[pt.rec].start),
+      for (auto& pt : sp.parts) memcpy(merged_focus.data() + (pt.s0 - s0), g.focus_of[pt.rec].data() + (pt.s0 - records[pt.rec].start),
           (size_t)(pt.s1 - pt.s0));
         }
-    const std::vector<uint8_t>& focus = focus_of[sp.rec];
+    const std::vector<uint8_t>& focus = g.focus_of[sp.rec];
     std::vector<mkp_record> recs; if (batch) { recs.reserve(batch->recs.size()); for (auto& e : batch->recs) recs.push_back(batch->view(e)); }
-    {
-      if (a.plan_only) {  // host-only dry run: the shard plan, plus the packer over the shard's records (no device)
-        static std::vector<ShardHost> kept_pieces;   // the all-cores pack's per-thread buffers persist across shards, as they do in a context
-        Packer pk; pk.pieces.swap(kept_pieces); ShardHost S; S.tid = (int32_t)rec.tid; S.win_start = (int32_t)s0; S.win_end = (int32_t)s1;
-        const int32_t tid = (int32_t)rec.tid; auto t_pk = std::chrono::steady_clock::now();
-        // --plan-pack-min N: records from which the packer runs on all cores (0 = always; default as in mkp_shard_add_records)
-        pack_records(pk, S, recs.data(), (uint32_t)recs.size(), [tid](const mkp_record& r) { return r.tid == tid && Packer::keep(r);
-          }, a.plan_pack_min);
-        pack_ms += ms_since(t_pk); kept_pieces.swap(pk.pieces);
-        // digest of everything the packer hands to the device: a parallel pack must equal the sequential one byte for byte
-        uint64_t dg = 1469598103934665603ull;
-        auto mix = [&](const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for (size_t i = 0; i < n; i++) { dg ^= b[i];
-            dg *= 1099511628211ull; } };
-        mix(S.hdr.data(), S.hdr.size() * sizeof(MkpReadHdr)); mix(S.cigar.data(), S.cigar.size() * 4);
-          mix(S.chunk_pfx.data(), S.chunk_pfx.size() * 4);
-            mix(S.seq.data(), S.seq.size());
-        mix(S.tagref.data(), S.tagref.size() * sizeof(MkpTagRef)); mix(S.ranks.data(), S.ranks.size() * 4); mix(S.ml.data(), S.ml.size());
-            mix(S.name_hash.data(), S.name_hash.size() * 8);
-        for (auto& k : pk.layout_keys) mix(k.data(), k.size());
-        fprintf(wr.f, "%s\t%u\t%u\t%zu\t%llu\t%016llx\n", rec.name.c_str(), s0, s1, S.hdr.size(), (unsigned long long)S.n_calls,
-            (unsigned long long)dg);
-          positions += bp;
-            continue;
-      }
-      mkp_shard sh; memset(&sh, 0, sizeof(sh)); sh.tid = (int32_t)rec.tid; sh.start = s0; sh.end = s1;
-      if (hf) { sh.focus = sp.parts.empty() ? focus.data() + (s0 - rec.start) : merged_focus.data(); sh.combos = fb.combos.data();
-        sh.n_combos = (uint32_t)fb.combos.size(); }
-      mark("shard blocks in hand");
-      if (attached_already) dev.reset();   // begun and attached before the threshold estimate, which sampled from it
-      else {
-        must(mkp_shard_begin(ctx, &sh));
-        must(mkp_shard_set_intervals(ctx, sp.iv_starts.data(), (uint32_t)sp.iv_starts.size()));
-        if (dev) { must(mkp_internal_shard_attach(ctx, dev.get())); mkp_internal_ingest_recycle(ctx->ingest, dev.get()); dev.reset(); }
-        else must(mkp_shard_add_records(ctx, recs.data(), (uint32_t)recs.size()));
-      }
-      mark("shard packed");
-      batch.reset();   // packed: the inflated blocks are no longer needed (their mappings are parked for the next fetch, ByteBuf::spares)
-      mkp_rows rows; memset(&rows, 0, sizeof(rows));
-      if (a.hemi) {
-        int hoff = 0; fb.motifs[0].neg_delta(&hoff);
-        mkp_hemi_rows hrows; must(mkp_hemi_shard_run(ctx, hoff, sp.iv_starts.data(), (uint32_t)sp.iv_starts.size(), &hrows));
-        if (a.rerun) must(mkp_shard_rerun(ctx, a.rerun, nullptr));
-        auto t_w = std::chrono::steady_clock::now();
-        wr.write_hemi(rec.name, hrows);
-        write_ms += ms_since(t_w);
-        rows.processed_records = hrows.processed_records; rows.skipped_records = hrows.skipped_records;
-      } else {
-      must(mkp_shard_run(ctx, &rows));
-      mark("  mkp_shard_run returned");
-      if (a.rerun) must(mkp_shard_rerun(ctx, a.rerun, &rows));   // measurement aid: warm, averaged kernel times in --stats
-      { auto t_w = std::chrono::steady_clock::now();
-        if (a.bedgraph) { bg.write(rec.name, rows); wr.n += rows.n_rows; }
-        else if (!partitioned) wr.write(rec.name, rows);
-        else for (uint64_t i0r = 0; i0r < rows.n_rows;) {   // rows come grouped by key: one slice per key
-          uint64_t i1r = i0r; while (i1r < rows.n_rows && rows.partition_key[i1r] == rows.partition_key[i0r]) i1r++;
-          mkp_rows v = rows; v.n_rows = i1r - i0r; v.pos += i0r; v.strand += i0r; v.code_repr += i0r; v.motif_idx += i0r; v.n_valid += i0r;
-            v.n_mod += i0r;
-              v.n_canonical += i0r; v.n_other += i0r;
-          v.n_delete += i0r; v.n_fail += i0r; v.n_diff += i0r; v.n_nocall += i0r; v.partition_key += i0r;
-          const uint32_t k = rows.partition_key[i0r];
-          RowWriter& kw = writer_for(k < rows.n_partition_keys ? rows.partition_key_names[k] : "not_found"); kw.write(rec.name, v); wr.n += v.n_rows;
-          i0r = i1r;
-        }
-        write_ms += ms_since(t_w); }
-      }
-      n_shards++;
-      mark("shard run, rows with the writer");
-      mkp_stats st; mkp_get_stats(ctx, &st); kernel_ms += st.kernel_ms; dec_ms += st.decode_kernel_ms; pil_ms += st.pileup_kernel_ms;
-        row_ms += st.rows_kernel_ms;
-          pack_ms += st.pack_ms; h2d_ms += st.h2d_ms; d2h_ms += st.d2h_ms;
-      positions += bp; processed += rows.processed_records; skipped += rows.skipped_records;
+    if (a.plan_only) { plan_only_shard(a, rec, s0, s1, recs, out.file(), c); c.positions += sp.bp; continue; }
+    mkp_shard sh; memset(&sh, 0, sizeof(sh)); sh.tid = (int32_t)rec.tid; sh.start = s0; sh.end = s1;
+    if (hf) { sh.focus = sp.parts.empty() ? focus.data() + (s0 - rec.start) : merged_focus.data(); sh.combos = o.fb.combos.data();
+      sh.n_combos = (uint32_t)o.fb.combos.size(); }
+    mark("shard blocks in hand");
+    if (attached_already) dev.reset();   // begun and attached before the threshold estimate, which sampled from it
+    else {
+      must(ctx, mkp_shard_begin(ctx, &sh));
+      must(ctx, mkp_shard_set_intervals(ctx, sp.iv_starts.data(), (uint32_t)sp.iv_starts.size()));
+      if (dev) { must(ctx, mkp_internal_shard_attach(ctx, dev.get())); mkp_internal_ingest_recycle(ctx->ingest, dev.get()); dev.reset(); }
+      else must(ctx, mkp_shard_add_records(ctx, recs.data(), (uint32_t)recs.size()));
     }
+    mark("shard packed");
+    batch.reset();   // packed: the inflated blocks are no longer needed (their mappings are parked for the next fetch, ByteBuf::spares)
+    mkp_rows rows; memset(&rows, 0, sizeof(rows));
+    if (a.hemi) {
+      int hoff = 0; o.fb.motifs[0].neg_delta(&hoff);
+      mkp_hemi_rows hrows; must(ctx, mkp_hemi_shard_run(ctx, hoff, sp.iv_starts.data(), (uint32_t)sp.iv_starts.size(), &hrows));
+      if (a.rerun) must(ctx, mkp_shard_rerun(ctx, a.rerun, nullptr));
+      auto t_w = std::chrono::steady_clock::now();
+      out.write_hemi(rec.name, hrows);
+      c.write_ms += ms_since(t_w);
+      rows.processed_records = hrows.processed_records; rows.skipped_records = hrows.skipped_records;
+    } else {
+      must(ctx, mkp_shard_run(ctx, &rows));
+      mark("  mkp_shard_run returned");
+      if (a.rerun) must(ctx, mkp_shard_rerun(ctx, a.rerun, &rows));   // measurement aid: warm, averaged kernel times in --stats
+      auto t_w = std::chrono::steady_clock::now();
+      out.write(rec.name, rows);
+      c.write_ms += ms_since(t_w);
+    }
+    mark("shard run, rows with the writer");
+    c.add_shard(ctx, sp.bp, rows);
   }
-  load_ms += fetch_wait_ms;   // what the shard loop waited for blocks to be read and inflated (the rest overlapped with pack / run / write)
-  { auto t_w = std::chrono::steady_clock::now(); bg.finish(); wr.finish(); for (auto& kv : key_writers) { kv.second->finish(); fclose(kv.second->f);
-    } write_ms += ms_since(t_w); }
-  if (wr.f && wr.f != stdout) fclose(wr.f);
+}
+
+int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
+  Counters c; c.t_all = std::chrono::steady_clock::now();
+  // BAI next to the BAM: only the blocks of the shards (and sampling intervals) this run touches are read and inflated; otherwise
+  // the whole file is loaded once.  (inflate threads: --threads only steers the sampling schedule)
+  std::unique_ptr<BamSource> src = BamSource::open(a.in_bam, std::max(std::max<unsigned>((unsigned)a.threads, 1u), HostPool::host_cpus()),
+      !a.no_index);
+  const BamSource& bam = *src;
+  c.load_ms = ms_since(c.t_all);
+  const Knobs kn;
+  const Marks mark{kn.trace, c.t_all};
+  mark("BAM opened (header, index)");
+  Options o(a, bam);
+  const std::vector<Contig>& records = o.records;
+  mkp_config cfg; memset(&cfg, 0, sizeof(cfg)); cfg.device = a.device; cfg.tile_positions = a.tile;
+  mkp_ctx* ctx = ext_ctx;
+  int rc = (a.plan_only || ext_ctx) ? MKP_OK : mkp_ctx_create(&cfg, &ctx);   // --plan-only: shard plan of this rank, no device work
+  if (rc != MKP_OK) throw Error(rc, "no usable gfx950 device (libmkpileup has no CPU path)");
+  // destroyed last: every object below that runs threads on the context joins them when it dies
+  struct OwnedCtx { mkp_ctx* c; ~OwnedCtx() { if (c) mkp_ctx_destroy(c); } } owned_ctx{ext_ctx ? nullptr : ctx};
+  const ShardReader reader(a, kn, *src, ctx);
+  const bool dev_ingest = reader.dev_ingest;
+  const ShardSize size(a, kn, bam, records);
+  AheadIngest ahead(reader, ctx, a.hbm_budget_mb, kn);
+  Grid g(records.size());
+  // One target contig that fits one shard whatever its grid turns out to be: the device ingest of that window starts now, before the
+  // reference is read and the grid walked (if the grid's one shard is not this window after all, the ingest is repeated for the plan's)
+  if (dev_ingest && a.world == 1 && records.size() == 1 && records[0].length > 0 && !kn.no_early_fetch && size.bp >= records[0].length
+      && bam.offset_at(records[0].tid, records[0].end()) - bam.offset_at(records[0].tid, records[0].start) <= size.bytes) {
+    g.early_whole = true; g.fetch_early(reader, records[0].tid, records[0].start, records[0].end()); }
+  // several target contigs (or the BED records of several contigs), each fitting one shard: all of them are ingested ahead
+  if (dev_ingest && !g.early_whole && a.world == 1 && !records.empty() && !kn.no_early_fetch && !kn.no_ahead) ahead.from_contigs(records, o.bf, size);
+  o.load_fasta(mark);
+  if (o.fb.has_focus() && a.world == 1 && !a.plan_only && a.filter_threshold.empty() && !a.no_filtering) {
+    const bool first_shard_early = !g.early_whole && !o.bf && ahead.empty() && !kn.no_early_fetch;
+    g.walk = std::async(std::launch::async, [&, first_shard_early]() {
+      auto t_focus = std::chrono::steady_clock::now();
+      for (size_t ri = 0; ri < records.size(); ri++) {
+        g.grid_of[ri] = o.fb.walk(records[ri], a.interval_size, &g.focus_of[ri]); g.grid_done[ri] = 1; g.focus_done[ri] = 1;
+        // (--include-bed: the first shard is a merge of records, known only with the plan)
+        if (ri == 0 && first_shard_early && !g.grid_of[0].empty()) {
+          uint64_t bp; const size_t i1 = size.cut(records[0], g.grid_of[0], 0, &bp);
+          g.fetch_early(reader, records[0].tid, g.grid_of[0][0].start, g.grid_of[0][i1 - 1].end);
+        }
+      }
+      g.focus_ms += ms_since(t_focus);
+    });
+  }
+  Plan plan;
+  o.kc.per_mod = o.per_mod.data(); o.kc.n_per_mod = (uint32_t)o.per_mod.size();
+  EarlyShard early;   // the first shard's records, taken before the loop
+  const bool full_mode = a.have_frac && a.sampling_frac >= 1.0;
+  const bool want_estimate = a.filter_threshold.empty() && !a.no_filtering && !a.plan_only;
+  const bool resident_ok = !o.have_sregion && !a.include_unmapped && !kn.no_resident_sampling;
+  // The plan comes before the thresholds — and its shards go ahead — when nothing is gained by waiting for them: several ranks (a rank needs
+  // its own shards whatever the thresholds turn out to be, and the others' estimate or all-reduce is time to ingest in), thresholds given,
+  // or a full-data estimate, which samples from the shards themselves.
+  if (dev_ingest && !g.early_whole && ahead.empty() && !kn.no_ahead && (a.world > 1 || !want_estimate || (full_mode && resident_ok))) {
+    build_plan(plan, a, kn, bam, o, g, size, !ahead.empty(), mark); ahead.from_plan(plan.shards, records, o.bf); }
+  // thresholds (subcommand.rs:615-638)
+  if (!a.filter_threshold.empty()) parse_base_thresholds(a.filter_threshold, &o.kc);
+  else if (a.no_filtering || a.plan_only) { o.kc.n_per_mod = 0; }  // MultipleThresholdModCaller::new_passthrough
+  else estimate_thresholds(a, kn, bam, o, ctx, g, ahead, plan, size, dev_ingest, resident_ok, early, c, mark);
+  c.resident_used = c.resident_used || early.attached;
+  mark("thresholds done");
+  if (!a.plan_only) must(ctx, mkp_set_caller(ctx, &o.kc));
+  g.join_walk();
+  Outputs out(a, ctx, o.labels);
+  build_plan(plan, a, kn, bam, o, g, size, !ahead.empty(), mark);
+  // (thresholds known before the plan: the shards go ahead of the loop from here)
+  if (ahead.empty() && plan.shards.size() > 1 && !kn.no_ahead) ahead.from_plan(plan.shards, records, o.bf);
+  run_shards(a, o, ctx, reader, g, ahead, plan, early, out, c, mark);
+  c.load_ms += c.fetch_wait_ms;   // what the shard loop waited for blocks to be read and inflated (the rest overlapped with pack / run / write)
+  { auto t_w = std::chrono::steady_clock::now(); out.finish(); c.write_ms += ms_since(t_w); }
+  out.close();
   mark("output closed");
-  if (rep) {
-    memset(rep, 0, sizeof(*rep));
-    rep->load_ms = load_ms; rep->threshold_ms = thr_ms; rep->focus_ms = focus_ms; rep->pack_ms = pack_ms; rep->h2d_ms = h2d_ms;
-      rep->kernel_ms = kernel_ms;
-        rep->d2h_ms = d2h_ms; rep->write_ms = write_ms;
-    rep->total_ms = ms_since(t_all); rep->n_rows = wr.n; rep->n_positions = positions; rep->n_shards = n_shards; rep->processed_records = processed;
-        rep->skipped_records = skipped;
-    for (int b = 0; b < 4; b++) { rep->threshold[b] = kc.per_base_threshold[b]; rep->has_threshold[b] = kc.has_per_base[b]; }
-    rep->grid_wait_ms = grid_wait_ms; rep->callback_ms = callback_ms; rep->ingest_kernel_ms = ingest_kernel_ms; rep->ingest_upload_ms = ingest_ms[1];
-      rep->ingest_table_ms = ingest_ms[0];
-    rep->ingest_pack_ms = ingest_ms[3]; rep->ingest_comp_bytes = ingest_comp; rep->ingest_raw_bytes = ingest_raw; rep->ingest_blocks = ingest_blocks;
-      rep->ingest_records = ingest_records;
-  }
-  if (a.stats) fprintf(stderr,
-      "[mkpileup] rows=%llu positions=%llu processed~%llu skipped~%llu load_ms=%.1f threshold_ms=%.1f focus_ms=%.1f pack_ms=%.1f h2d_ms=%.1f kernel_ms=%.3f (decode %.3f pileup %.3f rows %.3f) d2h_ms=%.1f write_ms=%.1f total_ms=%.1f shards=%llu indexed=%d bam_bytes_read=%llu bam_bytes_inflated=%llu (on the device %llu) peak_rss_kb=%llu\n",
-                       (unsigned long long)wr.n, (unsigned long long)positions, (unsigned long long)processed, (unsigned long long)skipped, load_ms,
-                           thr_ms, focus_ms, pack_ms, h2d_ms, kernel_ms, dec_ms, pil_ms, row_ms, d2h_ms, write_ms, ms_since(t_all),
-                       (unsigned long long)n_shards, bam.indexed() ? 1 : 0, (unsigned long long)bam.bytes_read.load(),
-                           (unsigned long long)bam.bytes_inflated.load(), (unsigned long long)bam.bytes_inflated_device.load(),
-                           (unsigned long long)peak_rss_kb());
-  if (a.stats) {   // every MKP_* variable that is set: they pick kernels and paths and would otherwise leave no trace in a measurement
-    std::string ov; for (char** e = ::environ; e && *e; e++) if (!strncmp(*e, "MKP_", 4)) { ov += ' '; ov += *e; }
-    fprintf(stderr,
-        "[mkpileup] ingest=%s resident_sampling=%d ahead=%zu shards (estimated %.0f MB, HBM budget %.0f MB) rank=%u/%u env overrides:%s\n",
-        dev_ingest ? "device" : "host", (pre_attached || resident_used) ? 1 : 0,
-        ahead.size(), (double)ahead_est_total / 1048576.0, (double)hbm_budget / 1048576.0, a.rank, a.world, ov.empty() ? " none" : ov.c_str());
-  }
-  if (a.stats
-      && dev_ingest) fprintf(stderr,
-      "[mkpileup] device ingest: %llu BGZF blocks, %llu records; block plan %.1f ms, upload %.1f, inflate + CRC + chains %.1f, parse + pack %.1f, digest %.1f (overlapped with the threshold estimate / the shard in hand)\n",
-      (unsigned long long)ingest_blocks, (unsigned long long)ingest_records, ingest_ms[0], ingest_ms[1], ingest_ms[2], ingest_ms[3], ingest_ms[4]);
+  if (rep) c.report(rep, out.rows(), g.focus_ms, o.kc);
+  if (a.stats) c.print_stats(a, bam, out.rows(), g.focus_ms, dev_ingest, ahead);
   return MKP_OK;
 }
 
@@ -1566,7 +1682,7 @@ void sample_bam(mkp_ctx* ctx, const char* bam_path, int argc, const char* const*
   if (thresholds) { kc.default_threshold = thresholds->default_threshold; kc.per_mod = thresholds->per_mod; kc.n_per_mod = thresholds->n_per_mod;
                     for (int b = 0; b < 4; b++) { kc.per_base_threshold[b] = thresholds->per_base_threshold[b];
                       kc.has_per_base[b] = thresholds->has_per_base[b]; } }
-  int rc = mkp_set_caller(ctx, &kc); if (rc != MKP_OK) throw Error(rc, mkp_last_error(ctx));
+  must(ctx, mkp_set_caller(ctx, &kc));
   a.serial_sampler = serial_without_index && a.world <= 1 && !bam_index_file_exists(a.in_bam);
   sample_probabilities(ctx, bam, a, hs ? &sregion : (hr ? &region : nullptr), bf);
   if (q_out) *q_out = a.filter_percentile;
@@ -1708,8 +1824,7 @@ extern "C" int mkp_process_region(mkp_ctx* ctx, const char* bam_path, const mkp_
   if (!ctx || !bam_path || !shard || !out) return MKP_E_INVALID;
   try {
     std::unique_ptr<BamSource> src = BamSource::open(bam_path, 0);
-    const bool host_ingest_env = getenv("MKP_HOST_INGEST") && !strcmp(getenv("MKP_HOST_INGEST"), "1");
-    if (src->indexed() && ctx->partition_tags.empty() && !host_ingest_env && shard->tid >= 0 && shard->end > shard->start) {
+    if (src->indexed() && ctx->partition_tags.empty() && !Knobs().host_ingest && shard->tid >= 0 && shard->end > shard->start) {
       if (!ctx->ingest) { ctx->ingest = mkp_internal_ingest_create(ctx->device);
         if (!ctx->ingest) throw Error(MKP_E_DEVICE, "device ingest: cannot create streams on the device");
         }

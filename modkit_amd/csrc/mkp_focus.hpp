@@ -38,6 +38,22 @@ struct BedFilter {
   bool overlaps(uint32_t tid, uint64_t s, uint64_t e) const { auto a = pos.find(tid); if (a != pos.end() && spans_hit(a->second, s, e)) return true;
     auto b = neg.find(tid); return b != neg.end() && spans_hit(b->second, s, e); }
   bool has_chrom(int64_t tid) const { return tid >= 0 && (pos.count((uint32_t)tid) || neg.count((uint32_t)tid)); }
+  // one byte per position of contig `tid` (length `len`): bit 0 / 1 = the position is listed for the '+' / '-' strand
+  std::vector<uint8_t> mask(uint32_t tid, size_t len) const {
+    std::vector<uint8_t> m(len, 0);
+    auto mark = [&](const std::map<uint32_t, std::vector<Span>>& mp, uint8_t bit) { auto f = mp.find(tid); if (f == mp.end()) return;
+        for (auto& x : f->second) for (uint64_t q = x.s; q < std::min<uint64_t>(x.e, len); q++) m[q] |= bit; };
+    mark(pos, 1); mark(neg, 2);
+    return m;
+  }
+  // the spans of contig `tid` on either strand, clipped to [lo, hi), merged
+  std::vector<Span> spans_in(uint32_t tid, uint64_t lo, uint64_t hi) const {
+    std::vector<Span> v;
+    for (auto* m : {&pos, &neg}) { auto it = m->find(tid); if (it == m->end()) continue;
+      for (auto& x : it->second) { const uint64_t a = std::max<uint64_t>(x.s, lo), b = std::min<uint64_t>(x.e, hi); if (a < b) v.push_back({a, b}); } }
+    merge_spans(v);
+    return v;
+  }
   static BedFilter load(const std::string& path, const std::map<std::string, uint32_t>& c2t) {
     std::ifstream in(path); if (!in) throw Error(MKP_E_IO, "cannot open BED " + path);
     BedFilter bf; std::string line; std::map<std::string, bool> unknown;
