@@ -24,7 +24,7 @@ hipError_t mkp_launch_pileup(hipStream_t, uint32_t /*LDS bytes*/, int /*focus mo
                              const MkpRunParams* /*device*/, const uint32_t* /*slot bitmap*/, const uint8_t* /*focus bytes*/, const MkpCombo*,
                                  const MkpRowsDev*, uint32_t* /*row cursor*/,
                              uint32_t* /*tile row offsets*/, uint32_t* /*tile row counts*/, const uint32_t* /*chunk offsets*/,
-                                 uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/);
+                                 uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, bool /*wide tallies*/);
 hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_t, const void* /*call plane*/, const MkpReadHdr*,
     const uint32_t* /*cover read ids*/,
     uint32_t, const uint32_t*, const uint8_t*, const MkpTagRef*,
@@ -41,7 +41,7 @@ hipError_t mkp_launch_stream(hipStream_t, uint32_t /*LDS bytes*/, const MkpVisit
                              const uint8_t* /*focus bytes*/, const MkpCombo*, const MkpRowsDev*, uint32_t* /*row cursor*/, uint32_t*, uint32_t*,
                                  uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, uint32_t /*motif combos*/,
                                  uint32_t /*row runs of the launch sequence*/,
-                             uint32_t /*slot capacity of a tile*/, uint32_t /*tally words per slot*/);
+                             uint32_t /*slot capacity of a tile*/, uint32_t /*tally words per slot*/, bool /*wide tallies*/);
 hipError_t mkp_launch_gather(hipStream_t, const uint32_t*, const uint32_t*, uint32_t*, uint32_t, uint32_t*, const MkpRowsDev*, const MkpRowsDev*);
 hipError_t mkp_launch_hemi_failed(hipStream_t, const MkpReadHdr*, const uint32_t*, const uint8_t*, MkpEvent*, MkpReadOut*, uint32_t,
     const uint32_t* /*slot bitmap*/,
@@ -187,22 +187,41 @@ template <class F> void host_parallel(size_t n, size_t grain, F f) {   // f(lo, 
 // that overlap it.  Dropping per (record, interval) is not reproduced on the device; what is decided here, exactly, is whether ANY
 // record would be dropped: an interval [a, e) and a start b shared by two or more of its records with
 //     #{records of the interval: start <= b and end >= b}  >  max_depth        (end > a where b <= a: the fetch's own condition).
-// If there is none, htslib keeps every record at any depth and the device result is exact (up to the tallies' 65 535).  The population
-// is htslib's: every record passing BAM_DEF_MASK (kept reads and supplementary ones), by reference span (ref-skips included).
-void depth_guard(const ShardHost& S, uint32_t max_depth, const std::vector<uint32_t>& iv_starts) {
+// If there is none, htslib keeps every record at any depth and the device result is exact.  The population is htslib's: every record
+// passing BAM_DEF_MASK (kept reads and supplementary ones), by reference span (ref-skips included).
+// Returns whether the shard needs the wide tallies: a column that may hold more than 65 535 records overflows the 16-bit strand halves
+// of the packed ones.  No (counter, strand, column) tally exceeds its column's record count — a record adds at most one feature per
+// tally strand at a position (a second feature at one base is the other mod strand's call, on the other tally strand), one observed-code
+// mark per slot and strand, one deletion — so the column depth is the bound.  Decided whenever the shard holds more than 65 535 records,
+// whatever max_depth says.  pileup-hemi has no wide kernel: such a shard is refused there.
+bool depth_guard(const ShardHost& S, uint32_t max_depth, const std::vector<uint32_t>& iv_starts, bool hemi) {
   const size_t n = S.hdr.size() + S.extra_spans.size();
-  if (n <= max_depth) return;
+  constexpr size_t kNarrowDepth = 65535;
+  if (n <= max_depth && n <= kNarrowDepth) return false;
   std::vector<std::pair<uint32_t, uint32_t>> sp; sp.reserve(n);   // (start, end), starts ascending (alignment starts and ends are non-negative)
   for (auto& h : S.hdr) sp.push_back({(uint32_t)h.ref_start, (uint32_t)std::max(h.ref_end, h.ref_start + 1)});
   for (auto& x : S.extra_spans) sp.push_back({(uint32_t)x.first, (uint32_t)std::max(x.second, x.first + 1)});
   if (!std::is_sorted(sp.begin(), sp.end(), [](auto& x, auto& y) { return x.first < y.first; }))
     std::stable_sort(sp.begin(), sp.end(), [](auto& x, auto& y) { return x.first < y.first; });
-  std::vector<uint32_t> en(n); for (size_t i = 0; i < n; i++) en[i] = sp[i].second;
-  sort_u32(en);
-  size_t j = 0, cur = 0, best = 0;
-  for (size_t i = 0; i < n; i++) { while (j < n && en[j] <= sp[i].first) { j++; cur--; } cur++; best = std::max(best, cur); }
-  if (best > 65535) throw Error(MKP_E_UNSUPPORTED,
-      "more than 65535 reads over one position: columns this deep are outside the device path (16-bit packed tallies)");
+  std::vector<uint32_t> en;   // ends ascending (built on first use)
+  auto sorted_ends = [&]() { if (en.size() != n) { en.resize(n); for (size_t i = 0; i < n; i++) en[i] = sp[i].second; sort_u32(en); } };
+  bool wide = false;
+  if (n > kNarrowDepth) {
+    // O(n) upper bound first: the records over a column p start in (p - L, p], L = the longest span — the most starts in any L positions
+    uint64_t L = 0; for (auto& x : sp) L = std::max<uint64_t>(L, x.second - x.first);
+    size_t bound = 0;
+    for (size_t i = 0, j = 0; i < n; i++) { while ((uint64_t)sp[j].first + L <= sp[i].first) j++; bound = std::max(bound, i - j + 1); }
+    if (bound > kNarrowDepth) {   // the exact deepest column: a sweep over starts and ends
+      sorted_ends();
+      size_t j = 0, cur = 0, best = 0;
+      for (size_t i = 0; i < n; i++) { while (j < n && en[j] <= sp[i].first) { j++; cur--; } cur++; best = std::max(best, cur); }
+      wide = best > kNarrowDepth;
+    }
+    if (wide && hemi) throw Error(MKP_E_UNSUPPORTED,
+        "more than 65535 reads over one position: pileup-hemi columns this deep are outside the device path (16-bit packed tallies)");
+  }
+  if (n <= max_depth) return wide;
+  sorted_ends();
   auto refuse = [&](uint32_t b, size_t held) {
     throw Error(MKP_E_UNSUPPORTED, "htslib would drop records here: " + std::to_string(held) + " buffered records at position " + std::to_string(b) +
         ", where several records start, exceed max_depth (" + std::to_string(max_depth) + "); bam_plp_push's maxcnt read dropping is not reproduced"); };
@@ -233,6 +252,7 @@ void depth_guard(const ShardHost& S, uint32_t max_depth, const std::vector<uint3
       i = r;
     }
   }
+  return wide;
 }
 
 // BGZF inflate on the device: mkp_inflate_wave4, one wave per block — speculative token decode, a scalar walk that only marks the chain,
@@ -453,14 +473,15 @@ void make_resident(mkp_ctx* c) {
   lap("decode classes + event slices");
   const size_t n = S.hdr.size();
   for (size_t i = 1; i < n; i++) if (S.hdr[i].ref_start < S.hdr[i - 1].ref_start) throw Error(MKP_E_INVALID, "records must be coordinate sorted");
-  depth_guard(S, c->caller.max_depth, c->iv_starts);
-  lap("sortedness + depth guard");
+  c->wide = depth_guard(S, c->caller.max_depth, c->iv_starts, c->hemi);
+  lap(c->wide ? "sortedness + depth guard (wide tallies)" : "sortedness + depth guard (16-bit tallies)");
 
   // ---- tile plan.  The accumulate kernel runs two 1024-thread workgroups per CU, each holding one tile in LDS: 76 KiB per
   // workgroup including ~3.5 KiB of static LDS leaves slack for the allocation granule (at 80 KiB each one GPU box ran them one
   // per CU and the kernel took 1.9x as long).  A tile = a run of reference positions; its tally columns ("slots") are all of
-  // its positions, or — when the run has focus positions — only those, so a --cpg tile spans ~50x more reference.
-  const uint32_t words_per_slot = c->hemi ? P.hemi_counters : P.n_counters + P.n_slots;
+  // its positions, or — when the run has focus positions — only those, so a --cpg tile spans ~50x more reference.  A wide shard holds
+  // two u32 planes per counter (one per strand): twice the tally words per slot, so about half the slots per tile.
+  const uint32_t words_per_slot = (c->hemi ? P.hemi_counters : P.n_counters + P.n_slots) * (c->wide ? 2u : 1u);
   const uint32_t budget_words = (76u * 1024u - 3584u) / 4u;
   const int64_t win = (int64_t)S.win_end - (int64_t)S.win_start;
   std::vector<MkpTile> tiles; std::vector<uint32_t> slotbm; uint32_t Scap = 0, Wcap = 0;
@@ -865,14 +886,16 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
           c->d_stiles.as<MkpSTile>(), c->n_tiles, c->d_prm.as<MkpRunParams>(),
                                                  c->d_slot_pos.as<uint32_t>(), c->d_focus.as<uint8_t>(), c->d_combos.as<MkpCombo>(), &c->rows_src,
                                                      misc, row_off, c->d_tile_row_cnt.as<uint32_t>(), misc + 2,
-                                                 c->key_passes[kp], kp, (uint32_t)c->combos.size(), n_runs, P.slot_cap, P.n_counters + P.n_slots),
+                                                 c->key_passes[kp], kp, (uint32_t)c->combos.size(), n_runs, P.slot_cap,
+                                                     (P.n_counters + P.n_slots) * (c->wide ? 2u : 1u), c->wide),
                                                      "stream pileup launch");
       else hip_check(mkp_launch_pileup(c->stream, c->lds_bytes, c->hemi ? 2 : c->has_focus ? 1 : 0, c->d_hdr.as<MkpReadHdr>(),
           c->d_cigar.as<uint32_t>(),
           c->d_seq.as<uint8_t>(), c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>(),
                                   c->d_tiles.as<MkpTile>(), c->n_tiles, c->d_prm.as<MkpRunParams>(), c->d_slotbm.as<uint32_t>(),
                                       c->d_focus.as<uint8_t>(), c->d_combos.as<MkpCombo>(), &c->rows_src, misc,
-                                  row_off, c->d_tile_row_cnt.as<uint32_t>(), c->d_chunk.as<uint32_t>(), misc + 2, c->key_passes[kp], kp),
+                                  row_off, c->d_tile_row_cnt.as<uint32_t>(), c->d_chunk.as<uint32_t>(), misc + 2, c->key_passes[kp], kp,
+                                      c->wide),
                                       "pileup launch");
     if (time_kernels) hip_check(hipEventRecord(c->ev[2], c->stream), "event");
     if (c->slot_mode) c->rows_dst = c->rows_src;   // already in genome order

@@ -6,6 +6,7 @@
 struct RowAcc { uint32_t n_valid, n_mod, n_can, n_other, n_del, n_fail, n_diff, n_nocall; };
 
 // packed tallies of a tile in LDS: [counter | observed-code slot][S], '+' tally in the low, '-' in the high 16 bits; column = tally slot
+// (the focus / pileup-hemi tiles: these never run wide)
 struct TileView {
   const uint32_t* pk;
   uint32_t W, n_counters;
@@ -172,33 +173,40 @@ struct StreamProg {
                            //          code)
 };
 
+// Tally k of strand s in column i.  Narrow shards (every column at most 65 535 records deep): one u32 per (k, column), '+' in the low and
+// '-' in the high 16 bits.  WIDE shards: one u32 plane per (k, strand), plane 2k + s.
+template <bool WIDE = false>
 __device__ __forceinline__ uint32_t col_get(const uint32_t* __restrict__ tal, uint32_t S, uint32_t i, uint32_t s, uint32_t k) {
+  if (WIDE) return tal[(2u * k + s) * S + i];
   return (tal[k * S + i] >> (16u * s)) & 0xffffu; }
+template <bool WIDE = false>
 __device__ __forceinline__ uint32_t col_sum(const uint32_t* __restrict__ tal, uint32_t S, uint32_t i, uint32_t s, uint32_t mask) {
   uint32_t t = 0;
-  while (mask) { const uint32_t k = (uint32_t)__ffs((int)mask) - 1u; mask &= mask - 1u; t += col_get(tal, S, i, s, k); }
+  while (mask) { const uint32_t k = (uint32_t)__ffs((int)mask) - 1u; mask &= mask - 1u; t += col_get<WIDE>(tal, S, i, s, k); }
   return t;
 }
 // does (strand tally s, column i, group g) yield a row — add_tally_to_counts's early returns (pileup/mod.rs:283-410): the primary base has
 // filtered coverage, and (per-code rows) the code was observed in a record over this column
+template <bool WIDE = false>
 __device__ __forceinline__ bool stream_row_exists(const uint32_t* __restrict__ tal, uint32_t S, uint32_t n_counters, const StreamProg& P, uint32_t s,
     uint32_t i, uint32_t g) {
   const uint32_t inf = P.info[g];
   if (!((inf >> 17) & 1u)) return false;
-  const uint32_t cov = col_get(tal, S, i, s, (inf >> 12) & 31u) + col_sum(tal, S, i, s, P.modmask[inf & 3u]);
+  const uint32_t cov = col_get<WIDE>(tal, S, i, s, (inf >> 12) & 31u) + col_sum<WIDE>(tal, S, i, s, P.modmask[inf & 3u]);
   if (!cov) return false;
   const uint32_t osl = (inf >> 2) & 31u;
-  return !osl || col_get(tal, S, i, s, n_counters + osl - 1u) != 0u;
+  return !osl || col_get<WIDE>(tal, S, i, s, n_counters + osl - 1u) != 0u;
 }
 // the row itself, added into `r`
+template <bool WIDE = false>
 __device__ __forceinline__ void stream_row_add(const uint32_t* __restrict__ tal, uint32_t S, const StreamProg& P, uint32_t s, uint32_t i, uint32_t g,
     RowAcc& r) {
   const uint32_t inf = P.info[g], pb = inf & 3u;
-  const uint32_t n_can = col_get(tal, S, i, s, (inf >> 12) & 31u), mods = col_sum(tal, S, i, s, P.modmask[pb]);
-  const uint32_t n_mod = ((inf >> 2) & 31u) ? col_get(tal, S, i, s, (inf >> 7) & 31u) : mods;
-  const uint32_t total = col_sum(tal, S, i, s, P.totmask), nocall = col_get(tal, S, i, s, MKP_C_NC + pb), cov = n_can + mods;
+  const uint32_t n_can = col_get<WIDE>(tal, S, i, s, (inf >> 12) & 31u), mods = col_sum<WIDE>(tal, S, i, s, P.modmask[pb]);
+  const uint32_t n_mod = ((inf >> 2) & 31u) ? col_get<WIDE>(tal, S, i, s, (inf >> 7) & 31u) : mods;
+  const uint32_t total = col_sum<WIDE>(tal, S, i, s, P.totmask), nocall = col_get<WIDE>(tal, S, i, s, MKP_C_NC + pb), cov = n_can + mods;
   r.n_valid += cov; r.n_mod += n_mod; r.n_can += n_can; r.n_other += mods - n_mod;
-  r.n_del += col_get(tal, S, i, s, MKP_C_DEL); r.n_fail += col_get(tal, S, i, s, MKP_C_FAIL);
+  r.n_del += col_get<WIDE>(tal, S, i, s, MKP_C_DEL); r.n_fail += col_get<WIDE>(tal, S, i, s, MKP_C_FAIL);
   r.n_diff += total - (nocall + cov); r.n_nocall += nocall;
 }
 
@@ -231,6 +239,7 @@ __device__ __forceinline__ void rowprog_build(const MkpRunParams& prm, uint32_t 
 // the threads scatter (column, strand, group) words into `rowmap` (LDS, `map_words` dwords: the accumulate phase's per-wave scratch, dead
 // by now) and then every thread fills and stores whole rows.  Existence is evaluated twice (count, scatter) — a handful of LDS reads —
 // instead of keeping a mask per column.  (Rounds 1-5: the interpreter of rows_at three times per column, 119 spilled registers.)
+template <bool WIDE>
 __device__ __forceinline__ void emit_dense_rows(const uint32_t* __restrict__ tal, uint32_t S, uint32_t n_counters, uint32_t n_tslots, int32_t T0h,
     const MkpTile& tl, uint32_t run, uint32_t key,
                                                 const MkpRunParams& prm, StreamProg& prog, uint32_t* __restrict__ rowmap, uint32_t map_words,
@@ -251,7 +260,7 @@ __device__ __forceinline__ void emit_dense_rows(const uint32_t* __restrict__ tal
   uint32_t cnt = 0;
   for (uint32_t i = i0; i < i1; i++) {
     if (!in_rows(i)) continue;
-    for (uint32_t s = 0; s < 2; s++) for (uint32_t g = 0; g < n_groups; g++) cnt += stream_row_exists(tal, S, n_counters, P, s, i, g) ? 1u : 0u;
+    for (uint32_t s = 0; s < 2; s++) for (uint32_t g = 0; g < n_groups; g++) cnt += stream_row_exists<WIDE>(tal, S, n_counters, P, s, i, g) ? 1u : 0u;
   }
   const uint32_t inc2 = wave_incl_scan(cnt);
   if (lane == 63) wave_tot[wave] = inc2;
@@ -276,7 +285,7 @@ __device__ __forceinline__ void emit_dense_rows(const uint32_t* __restrict__ tal
       for (uint32_t i = i0; i < i1; i++) {
         if (!in_rows(i)) continue;
         for (uint32_t s = 0; s < 2; s++) for (uint32_t g = 0; g < n_groups; g++) {
-          if (!stream_row_exists(tal, S, n_counters, P, s, i, g)) continue;
+          if (!stream_row_exists<WIDE>(tal, S, n_counters, P, s, i, g)) continue;
           if (r >= r0 && r < r0 + map_words) rowmap[r - r0] = i | (g << 13) | (s << 17);
           r++;
         }
@@ -287,7 +296,7 @@ __device__ __forceinline__ void emit_dense_rows(const uint32_t* __restrict__ tal
     for (uint32_t rr = threadIdx.x; rr < n_here; rr += PILEUP_THREADS) {
       const uint32_t e = rowmap[rr], si = e & 8191u, g = (e >> 13) & 15u, s = (e >> 17) & 1u;
       RowAcc acc = {0, 0, 0, 0, 0, 0, 0, 0};
-      stream_row_add(tal, S, P, s, si, g, acc);
+      stream_row_add<WIDE>(tal, S, P, s, si, g, acc);
       const size_t at = (size_t)*row_base_p + r0 + rr;
       rows.pos[at] = (uint32_t)(T0h + (int32_t)si); rows.info[at] = s | (key << 16); rows.code[at] = P.code[g];   // (no motif: info[8:15] = 0)
       rows.n_valid[at] = acc.n_valid; rows.n_mod[at] = acc.n_mod; rows.n_can[at] = acc.n_can; rows.n_other[at] = acc.n_other;

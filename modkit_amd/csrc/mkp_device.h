@@ -172,7 +172,8 @@ struct MkpTile { int32_t r0, r1; uint32_t first, last; };
 #define MKP_SLOTBM_MARGIN 64   // slot bitmap origin = win_start - MKP_SLOTBM_MARGIN
 
 // mkp_pileup_tiles geometry: 16 waves per tile.  Dynamic LDS, in dwords:
-//   tallies  [words_per_slot][S]            S = slot capacity of a tile (multiple of 64), 16-bit-packed strand tallies
+//   tallies  [words_per_slot][S]            S = slot capacity of a tile (multiple of 64), 16-bit-packed strand tallies (wide shards:
+//                                           words_per_slot doubled, one u32 plane per strand)
 //   focus runs: bm[W] + pfx[W] (slot bitmap of the tile's reference range and its running popcount), fpos[S] (slot -> position)
 //   per wave: an op-start bitmap over the tile's slots (even number of dwords, 2 spare for the 64-bit window read) and a
 //   64 x 8-byte compaction buffer

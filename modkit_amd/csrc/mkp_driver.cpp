@@ -1082,6 +1082,7 @@ struct Counters {
   double load_ms = 0, thr_ms = 0, fetch_wait_early_ms = 0, grid_wait_ms = 0, callback_ms = 0, fetch_wait_ms = 0;
   double kernel_ms = 0, pack_ms = 0, h2d_ms = 0, d2h_ms = 0, dec_ms = 0, pil_ms = 0, row_ms = 0, write_ms = 0;
   uint64_t positions = 0, processed = 0, skipped = 0, n_shards = 0;
+  uint64_t n_wide = 0;   // shards that ran the wide-tally accumulate kernels (a column over 65 535 records deep)
   double ingest_ms[5] = {0, 0, 0, 0, 0}, ingest_kernel_ms = 0; uint64_t ingest_blocks = 0, ingest_records = 0, ingest_comp = 0, ingest_raw = 0;
   bool resident_used = false;   // the threshold sample came from shards in HBM
 
@@ -1090,7 +1091,7 @@ struct Counters {
     ingest_blocks += d.n_blocks; ingest_records += d.n_records; ingest_kernel_ms += d.ms_kernel; ingest_comp += d.comp_bytes; ingest_raw += d.raw_bytes;
   }
   void add_shard(mkp_ctx* ctx, uint64_t bp, const mkp_rows& rows) {
-    n_shards++;
+    n_shards++; n_wide += ctx->wide ? 1u : 0u;
     mkp_stats st; mkp_get_stats(ctx, &st); kernel_ms += st.kernel_ms; dec_ms += st.decode_kernel_ms; pil_ms += st.pileup_kernel_ms;
       row_ms += st.rows_kernel_ms;
         pack_ms += st.pack_ms; h2d_ms += st.h2d_ms; d2h_ms += st.d2h_ms;
@@ -1123,6 +1124,8 @@ struct Counters {
         "[mkpileup] ingest=%s resident_sampling=%d ahead=%zu shards (estimated %.0f MB, HBM budget %.0f MB) rank=%u/%u env overrides:%s\n",
         dev_ingest ? "device" : "host", resident_used ? 1 : 0,
         ahead.size(), (double)ahead.est_total / 1048576.0, (double)ahead.budget / 1048576.0, a.rank, a.world, ov.empty() ? " none" : ov.c_str());
+    if (n_wide) fprintf(stderr, "[mkpileup] wide tallies: %llu of %llu shards (columns deeper than 65535 records)\n", (unsigned long long)n_wide,
+        (unsigned long long)n_shards);
     if (dev_ingest) fprintf(stderr,
       "[mkpileup] device ingest: %llu BGZF blocks, %llu records; block plan %.1f ms, upload %.1f, inflate + CRC + chains %.1f, parse + pack %.1f, digest %.1f (overlapped with the threshold estimate / the shard in hand)\n",
       (unsigned long long)ingest_blocks, (unsigned long long)ingest_records, ingest_ms[0], ingest_ms[1], ingest_ms[2], ingest_ms[3], ingest_ms[4]);

@@ -1174,9 +1174,10 @@ extern "C" __global__ void __launch_bounds__(256) mkp_sample_sparse2(DECODE_PARA
 // ----------------------------------------------------------------------------------------------
 
 // mkp_pileup_tiles — accumulate + emit.  Persistent 1024-thread workgroups, two per CU (8 waves per SIMD).  LDS holds one
-// tile's tallies as [row][slot] u32 with the '+' strand tally in the low and the '-' strand tally in the high 16 bits (the host
-// refuses shards in which more than 65535 reads overlap one position); rows = the strand tally's counters followed by the
-// observed-code slots; consecutive slots sit on consecutive banks.  Waves draw the tile's reads from an LDS ticket:
+// tile's tallies as [row][slot] u32 with the '+' strand tally in the low and the '-' strand tally in the high 16 bits; rows = the
+// strand tally's counters followed by the observed-code slots; consecutive slots sit on consecutive banks.  WIDE (_wide kernels: the
+// host picks them for a shard whose deepest column may hold more than 65 535 records) gives every row one u32 plane per strand
+// instead, row r strand s at plane 2r + s, at twice the LDS per slot; pileup-hemi keeps its plain counters and has no wide kernel.  Waves draw the tile's reads from an LDS ticket:
 //   * observed codes: +1 / -1 at the slots bounding the read's span (and around ref-skips) — an interval-OR as a difference array;
 //   * the read's call events inside the tile (position-sorted slice): one LDS atomic on the call's counter and -1 on NoCall(read base);
 //   * depth walk (htslib pileup columns, pileup/mod.rs:783-939): per 64-op CIGAR window the reference-consuming ops that
@@ -1191,7 +1192,7 @@ extern "C" __global__ void __launch_bounds__(256) mkp_sample_sparse2(DECODE_PARA
 // put the tiles' row runs in genome order.
 // HEMI (pileup-hemi, duplex.rs:241-339): the tally columns are the '+' motif positions; a read's '+' tally call at such a position
 // and its '-' tally call at the partner position form one pattern count; everything else about the walk is the focus kernel's.
-template <bool FOCUS, int UNROLL, bool KEYED, bool HEMI = false>
+template <bool FOCUS, int UNROLL, bool KEYED, bool HEMI = false, bool WIDE = false>
 __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__ hdrs, const uint32_t* __restrict__ cigar,
     const uint8_t* __restrict__ seqs,
                  const MkpEvent* __restrict__ events, const MkpReadOut* __restrict__ readout, const MkpTile* __restrict__ tiles, uint32_t n_tiles,
@@ -1202,6 +1203,7 @@ __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__
                  const uint2* __restrict__ chunk_pfx, uint32_t* __restrict__ dev_err, uint32_t key_arg) {
   // --partition-tag (KEYED kernels): low 16 bits = the key this pass tallies, high 16 bits = index of the pass; otherwise unused
   const uint32_t key_filter = KEYED ? (key_arg & 0xffffu) : 0u, key_run = KEYED ? (key_arg >> 16) : 0u;
+  static_assert(!WIDE || (!FOCUS && !HEMI), "wide tallies: dense tiles only");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ uint32_t next_read;
   __shared__ uint32_t wave_tot[PILEUP_WAVES];
@@ -1231,9 +1233,9 @@ __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__
   constexpr uint32_t dbg = 0;
 #endif
   const uint32_t n_counters = HEMI ? prm.hemi_counters : prm.n_counters, n_oslots = HEMI ? 0u : prm.n_slots;
-  const uint32_t tal_words = (n_counters + n_oslots) * S;
-  uint32_t* __restrict__ tal = lds;                       // [n_counters + n_oslots][S], packed
-  uint32_t* __restrict__ obs = lds + n_counters * S;      // observed-code difference arrays
+  const uint32_t tal_words = (n_counters + n_oslots) * S * (WIDE ? 2u : 1u);
+  uint32_t* __restrict__ tal = lds;                       // [n_counters + n_oslots][S], packed (WIDE: [n_counters + n_oslots][2][S])
+  uint32_t* __restrict__ obs = lds + n_counters * S * (WIDE ? 2u : 1u);   // observed-code difference arrays
   uint32_t* __restrict__ fbm = lds + tal_words;           // FOCUS: bitmap words [W], running popcount [W], slot -> position [S]
   uint32_t* __restrict__ fpfx = fbm + W;
   int32_t* __restrict__ fpos = reinterpret_cast<int32_t*>(fpfx + W);
@@ -1342,8 +1344,13 @@ __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__
       uint32_t m = lane ? ro.obs[1] : ro.obs[0];
       while (m) {
         const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
+        if (WIDE) {
+          atomicAdd(&obs[(2u * sl + (uint32_t)lane) * S + rs_a], 1u);
+          if (rs_b < n_tslots) atomicAdd(&obs[(2u * sl + (uint32_t)lane) * S + rs_b], 0u - 1u);
+        } else {
         atomicAdd(&obs[sl * S + rs_a], lane ? 0x10000u : 1u);
         if (rs_b < n_tslots) atomicAdd(&obs[sl * S + rs_b], 0u - (lane ? 0x10000u : 1u));
+        }
       }
     }
     if (HEMI) {
@@ -1402,14 +1409,21 @@ __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__
         if (in) { e = ev[k]; in = (int32_t)e.pos < T1h; }
         if (in && sm.is_slot((int32_t)e.pos)) {
           const uint32_t i = sm.rank((int32_t)e.pos);
+          if (WIDE) {   // [8] tally strand of the call, [11] of the read's base
+            atomicAdd(&tal[(2u * (e.info & 0xffu) + ((e.info >> 8) & 1u)) * S + i], 1u);
+            if (e.info & (1u << 12)) atomicAdd(&tal[(2u * (MKP_C_NC + ((e.info >> 9) & 3u)) + ((e.info >> 11) & 1u)) * S + i], 0u - 1u);
+          } else {
           atomicAdd(&tal[(e.info & 0xffu) * S + i], (e.info & 0x100u) ? 0x10000u : 1u);
           if (e.info & (1u << 12))  // the base is a call, not a NoCall (pileup/mod.rs:889-938)
             atomicAdd(&tal[(MKP_C_NC + ((e.info >> 9) & 3u)) * S + i], 0u - ((e.info & 0x800u) ? 0x10000u : 1u));
+          }
         }
         if (!__any(in)) break;
       }
     }
-    const uint32_t inc = HEMI ? 1u : (aln ? 0x10000u : 1u);   // this alignment strand's half of the packed tallies (hemi: plain counters)
+    const uint32_t inc = HEMI || WIDE ? 1u : (aln ? 0x10000u : 1u);   // this alignment strand's half of the packed tallies (hemi: plain counters)
+    // WIDE: this alignment strand's plane of a row (byte offset) and the distance between two rows' planes
+    const uint32_t aln_plane = WIDE ? aln * S * 4u : 0u, row_bytes = WIDE ? S * 8u : S * 4u;
     const uint8_t* __restrict__ lut = &rowlut[0][0][0];
     const uint32_t aln2 = HEMI ? 0u : aln << 1;   // hemi: the primary base is the SEQ base as stored, whatever the strand (duplex.rs:308-313)
     const uint32_t lanebase = lds_addr(tal) + 4u * (uint32_t)lane;   // LDS byte address of (row 0, slot `lane`)
@@ -1499,14 +1513,20 @@ __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__
             uint32_t m = ro.obs[s];
             while (m) {
               const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
+              if (WIDE) {
+                atomicAdd(&obs[(2u * sl + s) * S + sa], 0u - 1u);
+                if (sb < n_tslots) atomicAdd(&obs[(2u * sl + s) * S + sb], 1u);
+              } else {
               atomicAdd(&obs[sl * S + sa], 0u - (s ? 0x10000u : 1u));
               if (sb < n_tslots) atomicAdd(&obs[sl * S + sb], s ? 0x10000u : 1u);
+              }
             }
           }
         }
         if (op == 2 && covers) {  // deletion columns (alignment.is_del()): +1/-1 on the strand's DEL row, summed after the barrier
-          atomicAdd(&tal[MKP_C_DEL * S + sa], inc);
-          if (sb < n_tslots) atomicAdd(&tal[MKP_C_DEL * S + sb], 0u - inc);
+          const uint32_t del_row = WIDE ? (2u * MKP_C_DEL + aln) * S : MKP_C_DEL * S;
+          atomicAdd(&tal[del_row + sa], inc);
+          if (sb < n_tslots) atomicAdd(&tal[del_row + sb], 0u - inc);
         }
         const uint32_t S_lo = sm.rank(c_lo), S_hi = sm.rank(c_hi);   // the chunk's slots
         if (S_lo < S_hi) {
@@ -1573,7 +1593,7 @@ __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__
             const uint32_t la = lanebase + 256u * kk[j];
             bool ok = rowt < 8u;
             if (EDGE) ok = ok && (la - e_lo) < e_span && kb + (uint32_t)j <= k1;
-            if (ok) lds_add(la + __umul24(rowt, TS4), inc);
+            if (ok) lds_add(la + (WIDE ? __umul24(rowt, row_bytes) + aln_plane : __umul24(rowt, TS4)), inc);
           }
         };
         for (uint32_t kb = k0; kb <= k1; kb += UNROLL) {
@@ -1611,9 +1631,10 @@ __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__
     }
   }
   __syncthreads();
-  // difference arrays -> counts, in place and still packed (the sums are exact): deletions, then observed codes per slot
-  for (uint32_t a = wave + (FOCUS ? 1u : 0u); a < n_oslots + 1u; a += PILEUP_WAVES) {   // (focus runs count deletions directly)
-    uint32_t* __restrict__ arr = a == 0 ? tal + MKP_C_DEL * S : obs + (a - 1u) * S;
+  // difference arrays -> counts, in place and still packed (the sums are exact): deletions, then observed codes per slot (WIDE: per plane)
+  constexpr uint32_t NP = WIDE ? 2u : 1u;   // planes per row
+  for (uint32_t a = wave + (FOCUS ? 1u : 0u); a < NP * (n_oslots + 1u); a += PILEUP_WAVES) {   // (focus runs count deletions directly)
+    uint32_t* __restrict__ arr = WIDE ? (a < 2u ? tal + (2u * MKP_C_DEL + a) * S : obs + (a - 2u) * S) : a == 0 ? tal + MKP_C_DEL * S : obs + (a - 1u) * S;
     uint32_t carry = 0;
     for (uint32_t b0 = 0; b0 < n_tslots; b0 += 64) {
       const uint32_t v = (b0 + lane < n_tslots) ? arr[b0 + lane] : 0u;
@@ -1629,7 +1650,7 @@ __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__
   if (dbg & 4u) {}
   // dense tiles: row-major emission; the row map lives in the per-wave scratch of the accumulate phase (dead behind the barrier above)
   else if (!FOCUS && !HEMI)
-    emit_dense_rows(tal, S, n_counters, n_tslots, T0h, tl, KEYED ? key_run * n_tiles + tix : tix, key_filter, prm, rowprog,
+    emit_dense_rows<WIDE>(tal, S, n_counters, n_tslots, T0h, tl, KEYED ? key_run * n_tiles + tix : tix, key_filter, prm, rowprog,
         lds + tal_words + focus_total, min(8192u, PILEUP_WAVES * wave_words),
                     rows_base, row_cursor, tile_row_off, tile_row_cnt, dev_err, wave_tot, &row_base, &scan_carry);
   else emit_tile_rows<FOCUS, HEMI>(tal, sm, n_tslots, tl, KEYED ? key_run * n_tiles + tix : tix, key_filter, &prm, focus, combos_l, rows_base,
@@ -1650,6 +1671,11 @@ extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles
 // --partition-tag: the same kernel tallying only the reads of one partition key per launch
 extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_keyed(PILEUP_PARAMS) {
   pileup_tiles_body<false, 4, true>(PILEUP_PASS); }
+// shards whose deepest column may hold more than 65 535 records: u32 tallies per strand
+extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_wide(PILEUP_PARAMS) {
+  pileup_tiles_body<false, 4, false, false, true>(PILEUP_PASS); }
+extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_keyed_wide(PILEUP_PARAMS) {
+  pileup_tiles_body<false, 4, true, false, true>(PILEUP_PASS); }
 // pileup-hemi: the focus kernel with duplex pattern tallies
 extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_hemi(PILEUP_PARAMS) {
   pileup_tiles_body<true, 1, false, true>(PILEUP_PASS); }
@@ -1967,7 +1993,8 @@ extern "C" hipError_t mkp_launch_decode(hipStream_t st, const MkpReadHdr* hdrs, 
 
 // per device: both accumulate kernels may use the whole per-workgroup LDS budget the host planned for
 extern "C" hipError_t mkp_pileup_set_lds(uint32_t accum_bytes) {
-  for (const void* k : {(const void*)mkp_pileup_tiles, (const void*)mkp_pileup_tiles_keyed, (const void*)mkp_pileup_tiles_hemi}) {
+  for (const void* k : {(const void*)mkp_pileup_tiles, (const void*)mkp_pileup_tiles_keyed, (const void*)mkp_pileup_tiles_hemi,
+                        (const void*)mkp_pileup_tiles_wide, (const void*)mkp_pileup_tiles_keyed_wide}) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)accum_bytes);
     if (e != hipSuccess) return e;
   }
@@ -1981,7 +2008,7 @@ extern "C" hipError_t mkp_launch_pileup(hipStream_t st, uint32_t lds_bytes, int 
                                         const uint32_t* slotbm, const uint8_t* focus, const MkpCombo* combos, const MkpRowsDev* rows,
                                             uint32_t* row_cursor,
                                         uint32_t* tile_row_off, uint32_t* tile_row_cnt, const uint32_t* chunk_pfx, uint32_t* dev_err,
-                                            uint32_t key_filter, uint32_t key_slot) {
+                                            uint32_t key_filter, uint32_t key_slot, bool wide) {
   if (!n_tiles) return hipSuccess;
   const bool keyed = key_filter != MKP_NO_KEY_FILTER;
   const uint32_t key_arg = keyed ? ((key_filter & 0xffffu) | (key_slot << 16)) : 0u;
@@ -1991,6 +2018,7 @@ extern "C" hipError_t mkp_launch_pileup(hipStream_t st, uint32_t lds_bytes, int 
                        row_cursor, tile_row_off, tile_row_cnt, reinterpret_cast<const uint2*>(chunk_pfx), dev_err, key_arg)
   if (focus_mode == 2) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_hemi);   // pileup-hemi
   else if (focus_mode) return hipErrorInvalidValue;   // (focus runs are the slot pipeline's: mkp_launch_stream)
+  else if (wide) { if (keyed) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_keyed_wide); else MKP_PILEUP_LAUNCH(mkp_pileup_tiles_wide); }   // u32 tallies
   else { if (keyed) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_keyed); else MKP_PILEUP_LAUNCH(mkp_pileup_tiles); }
   return hipGetLastError();
 }

@@ -599,8 +599,8 @@ extern "C" __global__ void __launch_bounds__(256) mkp_cover_reads(SLOT_PARAMS(Mk
 
 // ----------------------------------------------------------------------------------------------------------------------
 // mkp_pileup_stream: accumulate + emit over the feature stream.  LDS: [counter | observed-code slot][S] packed tallies ('+' tally
-// in the low, '-' in the high 16 bits; the host refuses shards with more than 65535 records over one position), the tile's slot
-// positions, a word per slot for the emission (focus byte | strand-combining partners) and the row map.  Waves draw the tile's candidate
+// in the low, '-' in the high 16 bits; WIDE — the _wide kernels, for shards whose deepest column may hold more than 65 535 records — one
+// u32 plane per strand instead, [counter | observed-code slot][strand][S]), the tile's slot positions, a word per slot for the emission (focus byte | strand-combining partners) and the row map.  Waves draw the tile's candidate
 // reads from an LDS ticket; a visit = the read's MkpVisit (scalar loads), its bytes for the tile's slots (a dword per lane), one LDS
 // atomic per feature.  Observed codes: +1 / -1 at the ends of the read's slot range (and at every change between covered and not
 // covered when the read holds ref-skips).
@@ -613,7 +613,7 @@ extern "C" __global__ void __launch_bounds__(256) mkp_cover_reads(SLOT_PARAMS(Mk
 //       order) while every thread scatters (slot, candidate) words of its rows into the ROW MAP in LDS;
 //   E3  one thread per ROW fills its row from the tallies and stores it: every store instruction writes 64 consecutive rows of one column.
 // MkpRunParams is resolved once per workgroup into a small table (StreamProg) so that neither pass walks slot lists.
-template <bool KEYED, uint32_t VB /* visits drawn per ticket, their records and first stream dwords requested together */>
+template <bool KEYED, uint32_t VB /* visits drawn per ticket, their records and first stream dwords requested together */, bool WIDE = false>
 __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ visits, const uint8_t* __restrict__ cov,
     const MkpEvent* __restrict__ events,
                  const MkpSTile* __restrict__ tiles, uint32_t n_tiles, const MkpRunParams* __restrict__ prmp, const uint32_t* __restrict__ slot_pos,
@@ -646,7 +646,7 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
   const MkpCombo* combos_l = reinterpret_cast<const MkpCombo*>(combo_lds);
   const uint32_t n_counters = rfl(prm.n_counters), n_oslots = rfl(prm.n_slots);
   uint32_t* __restrict__ tal = lds;
-  uint32_t* __restrict__ obs = lds + n_counters * S;
+  uint32_t* __restrict__ obs = lds + n_counters * S * (WIDE ? 2u : 1u);
   int32_t* __restrict__ fpos = reinterpret_cast<int32_t*>(lds + tal_words);
   // per slot: [0:7] focus byte, [8 + 6m ..] partner column of the m-th '+' motif (strand combining)
   uint32_t* __restrict__ aux = lds + tal_words + S;
@@ -679,7 +679,7 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
       if (!(v.flags & MKP_VF_GAPS)) {
         const uint32_t sl = (uint32_t)lane >> 1, st = (uint32_t)lane & 1u;
         if (sl < n_oslots && (((st ? v.obs1 : v.obs0) >> sl) & 1u)) {
-          const uint32_t inc = st ? 0x10000u : 1u, at = __umul24(sl, S) + (a - gh0);
+          const uint32_t inc = WIDE ? 1u : st ? 0x10000u : 1u, at = __umul24(WIDE ? 2u * sl + st : sl, S) + (a - gh0);
           atomicAdd(&obs[at], inc);
           if (b - gh0 < n_tslots) atomicAdd(&obs[at + (b - a)], 0u - inc);
         }
@@ -689,8 +689,9 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
           const uint32_t col = col0 + k;
           if (cur != prev && col < n_tslots) for (uint32_t s = 0; s < 2; s++) {
             uint32_t m = s ? v.obs1 : v.obs0;
-            const uint32_t inc = s ? 0x10000u : 1u;
-            while (m) { const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u; atomicAdd(&obs[sl * S + col], cur ? inc : 0u - inc); }
+            const uint32_t inc = WIDE ? 1u : s ? 0x10000u : 1u;
+            while (m) { const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
+              atomicAdd(&obs[(WIDE ? 2u * sl + s : sl) * S + col], cur ? inc : 0u - inc); }
           }
         }
       }
@@ -708,11 +709,16 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
 #pragma unroll
       for (uint32_t j = 0; j < 4; j++) {
         // feature byte: [0:4] counter, [5] tally strand, >= 0x40 none.  One multiply-add for the row address (the byte's column goes into the
-        // instruction's offset field), one for the increment (1 or 1 << 16)
+        // instruction's offset field), one for the increment (1 or 1 << 16; WIDE: 1 on the strand's plane 2 * counter + strand)
         const uint32_t row = (w >> (8u * j)) & 31u, st = (w >> (8u * j + 5u)) & 1u;
         if (!(w & (0xc0u << (8u * j)))) {
+          if (WIDE) {
+            lds_u32* col = (lds_u32*)(uintptr_t)(lane_base + __umul24(2u * row + st, S4));
+            __hip_atomic_fetch_add(col + j, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          } else {
           lds_u32* col = (lds_u32*)(uintptr_t)(lane_base + __umul24(row, S4));
           __hip_atomic_fetch_add(col + j, __umul24(st, 0xffffu) + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
         }
       }
       if (!__any(kn < k_hi)) break;
@@ -720,6 +726,8 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
     if (v.n_over) {   // second features on one column
       for (uint32_t k = (uint32_t)lane; k < v.n_over; k += 64) {
         const MkpEvent e = events[v.over_off + k];
+        if (WIDE) { if (e.pos >= gh0 && e.pos < gh1) lds_add(talbase + 4u * (e.pos - gh0) + __umul24(2u * (e.info & 31u) + ((e.info >> 5) & 1u), S4), 1u); }
+        else
         if (e.pos >= gh0 && e.pos < gh1) lds_add(talbase + 4u * (e.pos - gh0) + __umul24(e.info & 31u, S4), (e.info & 32u) ? 0x10000u : 1u);
       }
     }
@@ -768,8 +776,8 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
   uint32_t my_fv = 0;
   if (threadIdx.x < n_tslots) { fpos[threadIdx.x] = my_pos; my_fv = prm.has_focus ? (uint32_t)focus[my_pos - prm.win_start] : 3u; }
   __syncthreads();
-  // observed-code difference arrays -> counts, in place and still packed
-  for (uint32_t a = wave; a < n_oslots; a += PILEUP_WAVES) {
+  // observed-code difference arrays -> counts, in place and still packed (WIDE: one array per strand plane)
+  for (uint32_t a = wave; a < (WIDE ? 2u * n_oslots : n_oslots); a += PILEUP_WAVES) {
     uint32_t* __restrict__ arr = obs + a * S;
     uint32_t carry = 0;
     for (uint32_t b0 = 0; b0 < n_tslots; b0 += 64) {
@@ -799,7 +807,7 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
       if (combo) { const MkpCombo& cb = combos_l[combo]; mult0 = cb.n_pos ? cb.n_pos : 1u; mult1 = cb.n_neg ? cb.n_neg : 1u; }
       for (uint32_t s = 0; s < 2; s++) {
         if (!((rule >> s) & 1u)) continue;
-        for (uint32_t g = 0; g < n_groups; g++) if (stream_row_exists(tal, S, n_counters, P, s, i, g)) em |= 1ull << (16u * s + g);
+        for (uint32_t g = 0; g < n_groups; g++) if (stream_row_exists<WIDE>(tal, S, n_counters, P, s, i, g)) em |= 1ull << (16u * s + g);
       }
       cnt = (uint32_t)__popc((uint32_t)em & 0xffffu) * mult0 + (uint32_t)__popc((uint32_t)(em >> 16) & 0xffffu) * mult1;
     } else if (combo) {   // only '+' motif positions produce rows
@@ -827,8 +835,8 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
           if (!((P.info[g] >> 18) & 1u)) continue;   // grouped by code (BTreeMap)
           bool any = false;
           for (uint32_t gj = g; gj < n_groups && (gj == g || !((P.info[gj] >> 18) & 1u)); gj++)
-            any = any || (pos_ok && stream_row_exists(tal, S, n_counters, P, 0, i, gj))
-                || (neg_ok && stream_row_exists(tal, S, n_counters, P, 1, iq, gj));
+            any = any || (pos_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 0, i, gj))
+                || (neg_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 1, iq, gj));
           if (any) { em |= 1ull << (16u * m + g); cnt++; }
         }
       }
@@ -889,7 +897,7 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
       RowAcc acc = {0, 0, 0, 0, 0, 0, 0, 0};
       uint32_t strand, motif1;   // motif1 = motif id + 1 (0: none)
       if (!combine) {
-        stream_row_add(tal, S, P, sm, si, g, acc);
+        stream_row_add<WIDE>(tal, S, P, sm, si, g, acc);
         strand = sm; motif1 = 0;
         if (combo) { const MkpCombo& cb = combos_l[combo]; const uint32_t n_ids = sm ? cb.n_neg : cb.n_pos;
           if (n_ids) motif1 = (uint32_t)(sm ? cb.neg_ids[k] : cb.pos_ids[k]) + 1u;
@@ -899,8 +907,8 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
         const uint32_t pd = (ax >> (8u + 6u * sm)) & 63u, iq = si + pd - 32u;
         const bool pos_ok = (ax & 1u) != 0, neg_ok = pd != 0u;
         for (uint32_t gj = g; gj < n_groups && (gj == g || !((P.info[gj] >> 18) & 1u)); gj++) {
-          if (pos_ok && stream_row_exists(tal, S, n_counters, P, 0, si, gj)) stream_row_add(tal, S, P, 0, si, gj, acc);
-          if (neg_ok && stream_row_exists(tal, S, n_counters, P, 1, iq, gj)) stream_row_add(tal, S, P, 1, iq, gj, acc);
+          if (pos_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 0, si, gj)) stream_row_add<WIDE>(tal, S, P, 0, si, gj, acc);
+          if (neg_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 1, iq, gj)) stream_row_add<WIDE>(tal, S, P, 1, iq, gj, acc);
         }
         strand = 2; motif1 = (uint32_t)cb.pos_ids[sm] + 1u;
       }
@@ -923,6 +931,11 @@ extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_strea
   pileup_stream_body<false, MKP_STREAM_VB>(STREAM_PASS); }
 extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_stream_keyed(STREAM_PARAMS) {
   pileup_stream_body<true, MKP_STREAM_VB>(STREAM_PASS); }
+// shards whose deepest column may hold more than 65 535 records: u32 tallies per strand (tal_words = twice the narrow kernels')
+extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_stream_wide(STREAM_PARAMS) {
+  pileup_stream_body<false, MKP_STREAM_VB, true>(STREAM_PASS); }
+extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_stream_keyed_wide(STREAM_PARAMS) {
+  pileup_stream_body<true, MKP_STREAM_VB, true>(STREAM_PASS); }
 
 // ----------------------------------------------------------------------------------------------------------------------
 // Records sharing a read name inside one interval (MkpDupCons / MkpDupSeg, mkp_device.h).  Rare: a handful of records per shard.
@@ -1049,7 +1062,8 @@ extern "C" hipError_t mkp_launch_dup_events(hipStream_t st, MkpReadHdr* hdrs, co
 }
 
 extern "C" hipError_t mkp_stream_set_lds(uint32_t bytes) {
-  for (const void* k : {(const void*)mkp_pileup_stream, (const void*)mkp_pileup_stream_keyed}) {
+  for (const void* k : {(const void*)mkp_pileup_stream, (const void*)mkp_pileup_stream_keyed, (const void*)mkp_pileup_stream_wide,
+                        (const void*)mkp_pileup_stream_keyed_wide}) {
     hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return e;
   }
@@ -1061,7 +1075,7 @@ extern "C" hipError_t mkp_launch_stream(hipStream_t st, uint32_t lds_bytes, cons
                                         const MkpRunParams* prm_dev, const uint32_t* slot_pos, const uint8_t* focus, const MkpCombo* combos,
                                             const MkpRowsDev* rows, uint32_t* row_cursor,
                                         uint32_t* tile_row_off, uint32_t* tile_row_cnt, uint32_t* dev_err, uint32_t key_filter, uint32_t key_slot,
-                                            uint32_t n_combos, uint32_t n_runs, uint32_t slot_cap, uint32_t words_per_slot) {
+                                            uint32_t n_combos, uint32_t n_runs, uint32_t slot_cap, uint32_t words_per_slot, bool wide) {
   if (!n_tiles) return hipSuccess;
   (void)tile_row_cnt;
   const bool keyed = key_filter != MKP_NO_KEY_FILTER;
@@ -1069,6 +1083,8 @@ extern "C" hipError_t mkp_launch_stream(hipStream_t st, uint32_t lds_bytes, cons
 #define MKP_STREAM_LAUNCH(K) hipLaunchKernelGGL(K, dim3(n_tiles), dim3(PILEUP_THREADS), lds_bytes, st, visits, cov, events, tiles, n_tiles, prm_dev, slot_pos, focus, combos, rows->pos, row_cursor, \
                                                 tile_row_off, dev_err, key_arg, n_combos > 64u ? 64u : n_combos, n_runs, slot_cap, words_per_slot * slot_cap)
   // ONE build per kernel: a one-shot shard pass and a re-launch on the resident shard run the same code object
-  if (keyed) MKP_STREAM_LAUNCH(mkp_pileup_stream_keyed); else MKP_STREAM_LAUNCH(mkp_pileup_stream);
+  // wide shards: words_per_slot counts both strand planes
+  if (wide) { if (keyed) MKP_STREAM_LAUNCH(mkp_pileup_stream_keyed_wide); else MKP_STREAM_LAUNCH(mkp_pileup_stream_wide); }
+  else if (keyed) MKP_STREAM_LAUNCH(mkp_pileup_stream_keyed); else MKP_STREAM_LAUNCH(mkp_pileup_stream);
   return hipGetLastError();
 }
