@@ -16,17 +16,28 @@ N > 1 (`--gpus N`, one process per GPU): ONE BAM of N chr20-sized contigs (C3's 
 by modkit_amd.distributed.pileup_sharded — contiguous runs of the reference's interval grid balanced by the bytes the BAI puts under
 them, every rank reading only its own BGZF blocks, thresholds from the histogram all-reduce over RCCL (the path's one collective,
 thresholds.rs:121-159) — and the timed region re-launches every rank's HBM-resident windows.  Per-GPU work is fixed as N grows
-("scaling": "weak"), the file and the sharding are north_star's.  The concatenated output is sha256-compared with a single-GPU
-run of the same file.
+("scaling": "weak"), the file and the sharding are north_star's.  With --full, the concatenated output is sha256-compared with a
+single-GPU run of the same file.
 
-Tiers: kernels only on the resident shard (`value`), the device pipeline (pack + H2D + kernels + D2H), end to end
-(`modkit pileup` wall: BGZF inflate, threshold sampling, focus, device pipeline, bedMethyl text) and the per-interval C-ABI seam
-(tests/abi_client.c: one mkp_shard_begin/add_records/run per 100 kb interval), next to the CPU restatement of the reference's path
-(oracle/, NOT the modkit binary: no Rust toolchain here) timed on the same BAM on this box's host cores, sha256 of both outputs
-compared, with the host thread counts of both sides stated and a matched-thread comparison.
+A plain run does what the headline needs: it generates the workload's BAM, runs the subcommand once end to end (its sampled
+thresholds are the timed steps' thresholds) and once with the whole contig as ONE HBM-resident shard, warms up, times the steps,
+writes --dump-outputs and prints the result line.  Tiers it reports from those runs alone: kernels only on the
+resident shard (`value`), the device pipeline (pack + H2D + kernels + D2H) and end to end (`modkit pileup` wall: BGZF inflate,
+threshold sampling, focus, device pipeline, bedMethyl text).
+
+`--full` adds every other measurement and check: the end-to-end pass again on a warm context, the sharded output against the
+one-shard output and the rows of the last timed step against both, the rocprofv3 --pmc traffic passes of the roofline, the C-ABI
+seams (tests/abi_client.c: one mkp_shard_begin/add_records/run per 100 kb interval, batches, whole file), the -f 1.0 run of c4 /
+chr1, the N-GPU parity run on one GPU, and the CPU restatement of the reference's path (oracle/, NOT the modkit binary: no Rust
+toolchain here) timed on the same BAM on the host's cores, sha256 of both outputs compared, with the host thread counts of both
+sides stated and a matched-thread comparison.
+
+Every run generates its BAM into a temporary directory of its own (under TMPDIR) and removes it at exit, SIGTERM included; with
+MKP_BENCH_DIR set, the BAMs are kept there and reused by later runs of the same workload (development only).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR    # + the last timed step's rows as DIR/<column>.npy
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                # + every other tier, baseline and parity check
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -260,9 +271,10 @@ def seam_per_interval(bam, fa, out, thr, per_batch=None):
         return {"error": str(e)[-300:]}
 
 
-def pmc_traffic(argv_tail, timeout_s=420):
+def pmc_traffic(argv_tail, bench_dir, timeout_s=420):
     """HBM bytes per launch of every mkp_* kernel from two separate rocprofv3 --pmc passes (FETCH_SIZE doubled per the gfx950
-    note of MI355X_MICROARCH.md, WRITE_SIZE as reported; KiB -> bytes) over a short inner run of this same bench on this build."""
+    note of MI355X_MICROARCH.md, WRITE_SIZE as reported; KiB -> bytes) over a short inner run of this same bench on this build,
+    which reads the BAM this run generated in `bench_dir`."""
     import csv
     import glob
     import shutil
@@ -272,7 +284,7 @@ def pmc_traffic(argv_tail, timeout_s=420):
     res = {}
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="mkp_pmc_", dir="/tmp")
-        env = dict(os.environ, TMPDIR="/tmp")
+        env = dict(os.environ, TMPDIR="/tmp", MKP_BENCH_DIR=bench_dir)
         cmd = ["rocprofv3", "--pmc", counter, "--output-format", "csv", "-d", d, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__), "--inner", "--steps", "2", "--warmup", "1"] + argv_tail
         try:
             p = subprocess.run(cmd, cwd="/tmp", env=env, capture_output=True, text=True, timeout=timeout_s)
@@ -303,6 +315,23 @@ def pmc_traffic(argv_tail, timeout_s=420):
                  "bytes = (2*FETCH + WRITE) * 1024; the factor 2 is calibrated on this GPU for streams and byte walks alike (profiles/r02_pmc_calibration.txt)")
 
 
+def run_dir():
+    """A directory of this run's own under TMPDIR, removed at exit: on return, on an exception and on SIGTERM / SIGHUP (what `timeout`
+    and torch.distributed.run send first).  No run reads the BAM (or any other file) an earlier run left behind."""
+    import atexit
+    import shutil
+    import signal
+    import tempfile
+    d = tempfile.mkdtemp(prefix="mkp_bench_")
+    atexit.register(shutil.rmtree, d, True)
+
+    def leave(signum, frame):
+        raise SystemExit(128 + signum)   # unwinds to the atexit handlers
+    for sig in (signal.SIGTERM, signal.SIGHUP):
+        signal.signal(sig, leave)
+    return d
+
+
 def threshold_argv(thr_h):
     t = []
     for i in range(4):
@@ -319,14 +348,15 @@ def main():
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink a single-contig workload (debug only; the JSON says so)")
     ap.add_argument("--genome-scale", type=float, default=0.1, help="c4 / c5: fraction of the hg38 contig lengths (the JSON states it next to every number)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", choices=["full", "region"], default="full", help="CPU baseline + parity on the whole bench BAM (default) or on its first eighth")
-    ap.add_argument("--cpu-whole", action="store_true", help="c4 / c5: CPU baseline + sha256 parity on the WHOLE scale model (all usable CPUs; minutes), not on its last contig")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc passes that measure roofline.traffic")
+    ap.add_argument("--full", action="store_true", help="also run every other tier, baseline and parity check (module docstring); a plain run times the headline only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-sample", choices=["full", "region"], default="full", help="--full: CPU baseline + parity on the whole bench BAM (default) or on its first eighth")
+    ap.add_argument("--cpu-whole", action="store_true", help="--full, c4 / c5: CPU baseline + sha256 parity on the WHOLE scale model (all usable CPUs; minutes), not on its last contig")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the rocprofv3 --pmc passes that measure roofline.traffic")
     ap.add_argument("--inner", action="store_true", help=argparse.SUPPRESS)  # the short run the --pmc passes profile
     ap.add_argument("--tile", type=int, default=0, help="experiments: reference positions per accumulate tile (0 = the library's plan)")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl", help="nccl (= RCCL over xGMI, one GPU per rank) or gloo (tests: several ranks may share a GPU)")
-    ap.add_argument("--no-full-data", action="store_true", help="c4 / chr1: skip the extra -f 1.0 run (and, with --cpu-whole, the oracle's)")
+    ap.add_argument("--no-full-data", action="store_true", help="--full, c4 / chr1: skip the extra -f 1.0 run (and, with --cpu-whole, the oracle's)")
     ap.add_argument("--skip-e2e", action="store_true", help="profiling runs: skip the sharded end-to-end pass so that every kernel launch is the full-size one the timed region repeats")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the rows the last one produced as DIR/<column>.npy (float64; a fixed seeded sample above 64 MB)")
     a = ap.parse_args()
@@ -369,7 +399,12 @@ def main():
     hemi = a.workload == "hemi"
     if multi and world > 1:
         raise SystemExit("--workload %s is a single-process run (the multi-GPU line shards the C3 generator's BAM)" % a.workload)
-    tmp = os.environ.get("MKP_BENCH_DIR", "/tmp")
+    tmp = os.environ.get("MKP_BENCH_DIR")
+    if not tmp:
+        box = [run_dir() if rank == 0 else None]
+        if dist:
+            dist.broadcast_object_list(box, src=0)
+        tmp = box[0]
     # ---- the workload's BAM (rank 0 generates; the generator binary normally ships prebuilt, __graft_entry__.build())
     if multi:
         contigs = [(n, max(100_000, int(l * a.genome_scale))) for n, l in (HG38[:1] if a.workload == "chr1" else HG38)]
@@ -420,7 +455,7 @@ def main():
             r = run_subcommand(ctx, out_bed + ".rep", threshold_argv(thr_h))
             if k >= a.warmup:
                 kms.append(r.kernel_ms); walls.append((time.perf_counter() - t_pass) * 1e3)
-        if a.steps and sh256(out_bed + ".rep") != sh256(out_bed):
+        if a.full and sh256(out_bed + ".rep") != sh256(out_bed):
             raise SystemExit("repeat pass with explicit thresholds differs from the sampled run")
         st = ctx.stats()
         kernel_ms = sum(kms) / max(1, len(kms))
@@ -429,7 +464,7 @@ def main():
         value = total_positions / (kernel_ms * 1e-3)
         extra_cfg = {"genome_scale": a.genome_scale, "shards": int(rep.n_shards), "timing": "multi-shard workload: value = positions / device kernel time summed over the shards of one pass (HIP events inside the library, mean over the timed passes, kernel_ms_per_step), NOT a wall-clock bracket; ms_per_step = wall of one timed pass",
                      "kernel_ms_per_step": kernel_ms, "pass_wall_ms_mean": ms_per_step, "kernel_ms_last_shard": {"decode": st.decode_kernel_ms, "pileup": st.pileup_kernel_ms, "gather": st.gather_kernel_ms}}
-        if a.workload in ("c4", "chr1") and not a.no_full_data:   # the full-data percentile (-f 1.0) next to the default sampled threshold
+        if a.full and a.workload in ("c4", "chr1") and not a.no_full_data:   # the full-data percentile (-f 1.0) next to the default sampled threshold
             rf = run_subcommand(ctx, out_bed + ".f1", ["-f", "1.0"])
             extra_cfg["full_data_threshold_run"] = {"flag": "-f 1.0", "total_ms": rf.total_ms, "threshold_ms": rf.threshold_ms, "thresholds": {"ACGT"[i]: float(rf.threshold[i]) for i in range(4) if rf.has_threshold[i]}, "rows": int(rf.n_rows)}
         rep1, elapsed = rep, kernel_ms * 1e-3 * a.steps
@@ -444,11 +479,12 @@ def main():
             # bedMethyl text), with the driver's default sharding (the next shard's blocks inflate while this one is packed and run)
             rep = run_subcommand(ctx, out_bed, [])
             thr_h = [float(rep.threshold[i]) if rep.has_threshold[i] else 0.0 for i in range(4)]
-            # the same call again on the same context: staging, window and row buffers exist now (what a long-lived caller pays per file)
-            rep_warm = run_subcommand(ctx, out_bed + ".warm", [])
-            if sh256(out_bed) != sh256(out_bed + ".warm"):
-                raise SystemExit("second end-to-end pass on the same context differs from the first")
-            os.remove(out_bed + ".warm")
+            if a.full:
+                # the same call again on the same context: staging, window and row buffers exist now (what a long-lived caller pays per file)
+                rep_warm = run_subcommand(ctx, out_bed + ".warm", [])
+                if sh256(out_bed) != sh256(out_bed + ".warm"):
+                    raise SystemExit("second end-to-end pass on the same context differs from the first")
+                os.remove(out_bed + ".warm")
         else:
             thr = ctx.estimate_thresholds(bam, ["-t", "8"])
             thr_h = [float(thr.get(b, 0.0)) for b in "ACGT"]
@@ -456,10 +492,10 @@ def main():
         rep1 = run_subcommand(ctx, out_bed + ".oneshard", threshold_argv(thr_h) + ["--shard-bytes", str(1 << 40)])
         if rep is None:
             rep = rep1
-        elif sh256(out_bed) != sh256(out_bed + ".oneshard"):
+        elif a.full and sh256(out_bed) != sh256(out_bed + ".oneshard"):
             raise SystemExit("sharded and single-shard bedMethyl differ")
-        # the rows the timed re-launches must reproduce: the one-shard output (sha256-equal to the end-to-end file, which the CPU baseline leg compares with the oracle's)
-        expected_row_digests = None if hemi else [modkit_amd.rows_digest(modkit_amd.read_bedmethyl(out_bed + ".oneshard"))]
+        # --full: the rows the timed re-launches must reproduce: the one-shard output (sha256-equal to the end-to-end file, which the CPU baseline leg compares with the oracle's)
+        expected_row_digests = None if hemi or not a.full else [modkit_amd.rows_digest(modkit_amd.read_bedmethyl(out_bed + ".oneshard"))]
         if rep is rep1:
             os.replace(out_bed + ".oneshard", out_bed)
         else:
@@ -484,21 +520,24 @@ def main():
         thr_h = [float(thr.get(b, 0.0)) for b in "ACGT"]
         # the rank's windows, each resident in HBM on its own context (a window = a piece of one contig; cuts sit on the interval grid)
         plan = mkd.shard_plan([bam, out_bed] + flags, rank, world)
-        ctxs, rep1, n_rows_rank, parts, expected_row_digests = [], None, 0, [], []
+        ctxs, rep1, n_rows_rank, parts, expected_row_digests = [], None, 0, [], ([] if a.full else None)
         for k, (cname, s, e) in enumerate(plan):
             c = modkit_amd.Context(device=local_rank, tile_positions=a.tile)
             part = "%s.rank%d.win%d" % (out_bed, rank, k)
             r = run_subcommand(c, part, threshold_argv(thr_h) + ["--region", "%s:%d-%d" % (cname, s, e), "--shard-bytes", str(1 << 40)])
             n_rows_rank += int(r.n_rows); parts.append(part); ctxs.append(c)
-            expected_row_digests.append(modkit_amd.rows_digest(modkit_amd.read_bedmethyl(part)))
+            if a.full:
+                expected_row_digests.append(modkit_amd.rows_digest(modkit_amd.read_bedmethyl(part)))
             rep1 = r if rep1 is None else rep1
         rep = rep1
-        # the windows' rows = the rank's part of the sharded run (validated below through the concatenation)
-        with open("%s.rank%d.windows" % (out_bed, rank), "wb") as f:
-            for p_ in parts:
-                with open(p_, "rb") as g:
-                    f.write(g.read())
-                os.remove(p_)
+        # the windows' rows = the rank's part of the sharded run (--full: validated below through the concatenation)
+        if a.full:
+            with open("%s.rank%d.windows" % (out_bed, rank), "wb") as f:
+                for p_ in parts:
+                    with open(p_, "rb") as g:
+                        f.write(g.read())
+        for p_ in parts:
+            os.remove(p_)
         n_rows = n_rows_rank
 
     if not multi:
@@ -522,12 +561,12 @@ def main():
         # the rows the LAST timed re-launch left in HBM, fetched now (rerun(0): no further launch) and compared with the checked output: the
         # kernels the timed region ran are the kernels whose rows are bit-exact, on this very pass
         timed_rows_checked = None
-        timed_rows = [modkit_amd.rows_to_numpy(c.rerun(0, fetch=True)) for c in ctxs] if expected_row_digests is not None else None
+        timed_rows = [modkit_amd.rows_to_numpy(c.rerun(0, fetch=True)) for c in ctxs] if expected_row_digests is not None or a.dump_outputs else None
         if a.dump_outputs:
             dumped = dump_outputs(a.dump_outputs, timed_rows[0])
         if os.environ.get("MKP_DEBUG_SKIP", "0") not in ("", "0"):
             timed_rows_checked = {"equal": None, "what": "skipped: MKP_DEBUG_SKIP ablation run of a -DMKP_DEBUG build (the kernels leave parts out on purpose)"}
-        elif timed_rows is not None:
+        elif expected_row_digests is not None:
             for rows, want in zip(timed_rows, expected_row_digests):
                 got = modkit_amd.rows_digest(rows)
                 if got != want:
@@ -559,23 +598,25 @@ def main():
             gathered = [None] * world
             dist.all_gather_object(gathered, mine)
             if rank == 0:
-                # parity of the split: concatenation of the ranks' parts == a single-GPU run of the same file with the same thresholds;
-                # and the per-window resident runs reproduce the parts
-                single = out_bed + ".single"
-                modkit_amd.pileup([bam, single, "--device", str(local_rank)] + flags + threshold_argv(thr_h))
-                win_cat = hashlib.sha256()
-                for r_ in range(world):
-                    with open("%s.rank%d.windows" % (out_bed, r_), "rb") as g:
-                        win_cat.update(g.read())
                 walls = [g_["pileup_s"] for g_ in gathered if g_["pileup_s"]]
                 e2e_wall = max(g_["sharded_wall_s"] for g_ in gathered)
                 tiers["end_to_end_sharded"] = {"positions_per_s": total_positions / e2e_wall, "rows_per_s": total_rows / e2e_wall, "ms": e2e_wall * 1e3,
                                                "per_rank_total_s": [g_["total_s"] for g_ in gathered], "per_rank_threshold_s": [g_["threshold_s"] for g_ in gathered],
                                                "what": "the N-GPU job end to end, max over ranks between two barriers: per rank ONE mkp_pileup_run_cb (device ingest of its shards ahead, full-data sample from HBM, histogram all-reduce in the threshold callback, pileup pass on the resident shards, bedMethyl text) + the concatenation on rank 0; page cache warm"}
                 extra_cfg = {"sharding": "ONE BAM (%d contigs), contiguous runs of the interval grid per rank balanced by BAI bytes (mkp_pileup_main --gpus-rank/--gpus-world via modkit_amd.distributed.pileup_sharded), thresholds: two-level histogram all-reduce over RCCL (-f 1.0)" % len(contigs),
-                             "per_rank": gathered, "imbalance_pileup_wall_max_over_mean": (max(walls) / (sum(walls) / len(walls))) if walls else None,
-                             "sharded_sha256": sh256(out_bed), "sharded_equals_single_gpu": sh256(out_bed) == sh256(single), "resident_windows_equal_sharded": win_cat.hexdigest() == sh256(out_bed)}
-                os.remove(single)
+                             "per_rank": gathered, "imbalance_pileup_wall_max_over_mean": (max(walls) / (sum(walls) / len(walls))) if walls else None}
+                if a.full:
+                    # parity of the split: concatenation of the ranks' parts == a single-GPU run of the same file with the same thresholds;
+                    # and the per-window resident runs reproduce the parts
+                    single = out_bed + ".single"
+                    modkit_amd.pileup([bam, single, "--device", str(local_rank)] + flags + threshold_argv(thr_h))
+                    win_cat = hashlib.sha256()
+                    for r_ in range(world):
+                        with open("%s.rank%d.windows" % (out_bed, r_), "rb") as g:
+                            win_cat.update(g.read())
+                    extra_cfg.update({"sharded_sha256": sh256(out_bed), "sharded_equals_single_gpu": sh256(out_bed) == sh256(single),
+                                      "resident_windows_equal_sharded": win_cat.hexdigest() == sh256(out_bed)})
+                    os.remove(single)
             dist.barrier()
 
     if rank == 0:
@@ -588,9 +629,9 @@ def main():
         else:
             b_alg = st.alg_bytes_decode - 8 * st.n_events + 44 * st.n_rows
         traffic_all, traffic_src = None, None
-        if world == 1 and not a.no_pmc and not multi:
+        if a.full and world == 1 and not a.no_pmc and not multi:
             tail = ["--workload", a.workload, "--scale", str(a.scale), "--no-cpu-baseline", "--no-pmc"]
-            traffic_all, traffic_src = pmc_traffic(tail)
+            traffic_all, traffic_src = pmc_traffic(tail, tmp)
         def kernel_traffic(prefixes):
             if not traffic_all:
                 return None
@@ -626,7 +667,7 @@ def main():
             tiers["end_to_end_warm_context"] = {"positions_per_s": rw.n_positions / (rw.total_ms * 1e-3), "rows_per_s": rw.n_rows / (rw.total_ms * 1e-3), "ms": rw.total_ms,
                                                 "stages_ms": stages_of(rw),
                                                 "what": "the same mkp_pileup_run again on the same context (page-locked staging, ingest windows and row buffers already allocated); tiers.end_to_end is the first call on a fresh context"}
-        if world == 1 and a.workload == "c3" and not (a.inner or a.skip_e2e):
+        if a.full and world == 1 and a.workload == "c3" and not (a.inner or a.skip_e2e):
             tiers["seam_per_interval"] = seam_per_interval(bam, fa, bam + ".seam.bed", thr_h[1] if thr_h[1] > 0 else 0.7)
             # the batch seam (mkp_batch_run): the reference's default chunk of floor(1.5 * threads) intervals at 8 and 64 threads, and a whole contig per call
             tiers["seam_batch"] = {str(n): seam_per_interval(bam, fa, bam + ".seam.bed", thr_h[1] if thr_h[1] > 0 else 0.7, per_batch=n) for n in (12, 96, 1000)}
@@ -653,7 +694,7 @@ def main():
             # `roofline` itself = the aggregation kernel (north_star's target); `dominant` = the kernel that takes most of the step
             "roofline": dict(agg, slowest=slow, dominant=dict(slow, share_of_step=(slow["avg_launch_ms"] / ms_per_step) if ms_per_step else None), whole_pass=whole, ingest=ingest_roofline(rep)),
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             workers = min(usable_cpus(), 8)
             region = None
             if multi and a.cpu_whole:

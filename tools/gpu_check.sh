@@ -1,5 +1,5 @@
 #!/bin/bash
-# One GPU-box pass: parity tests, bench line (with its own --pmc traffic passes), rocprofv3 kernel-trace summary.
+# One GPU-box pass: parity tests, --full bench line (with its own --pmc traffic passes), rocprofv3 kernel-trace summary.
 # Usage: tools/gpu_check.sh <tag> [pytest|nopytest|"pytest args"] [bench args...]
 set -u
 TAG=${1:-r02}
@@ -17,7 +17,7 @@ elif [ "$PT" != "nopytest" ]; then
   timeout 1500 python -m pytest $PT > $OUT/pytest.log 2>&1; echo "pytest exit $?" | tee -a $OUT/pytest.log
   tail -15 $OUT/pytest.log
 fi
-timeout 1200 python bench.py --steps 20 --warmup 3 "$@" > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
+timeout 1200 python bench.py --steps 20 --warmup 3 --full "$@" > $OUT/bench.json 2> $OUT/bench.err; echo "bench exit $?"
 cat $OUT/bench.json; tail -5 $OUT/bench.err
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -o bench -- python $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-pmc --skip-e2e "$@" > $OUT/bench_rocprof.json 2> $OUT/rocprof.err; echo "rocprof exit $?"

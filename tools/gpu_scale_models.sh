@@ -5,9 +5,9 @@
 TAG=${1:-r04s}; OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG; mkdir -p $OUT; cd $GRAFT_REPO_ROOT
 export MKP_BENCH_DIR=/tmp
 for W in c5 c4; do
-  ( time timeout 1500 python bench.py --workload $W --steps 2 --warmup 1 --no-pmc ) > $OUT/${W}_bench.json 2> $OUT/${W}_bench.err; echo "bench $W exit $?"; tail -3 $OUT/${W}_bench.err | cut -c1-300
+  ( time timeout 1500 python bench.py --workload $W --steps 2 --warmup 1 --full --no-pmc ) > $OUT/${W}_bench.json 2> $OUT/${W}_bench.err; echo "bench $W exit $?"; tail -3 $OUT/${W}_bench.err | cut -c1-300
 done
-( time timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --dist-backend gloo ) > $OUT/n2_gloo_bench.json 2> $OUT/n2_gloo_bench.err; echo "n2 exit $?"
+( time timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --steps 5 --warmup 2 --dist-backend gloo --full ) > $OUT/n2_gloo_bench.json 2> $OUT/n2_gloo_bench.err; echo "n2 exit $?"
 python - <<PY
 import json
 for w in ("n2_gloo","c4","c5"):

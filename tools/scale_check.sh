@@ -16,7 +16,7 @@ for N in 1 2 4 8; do
   if [ "$N" -gt "$NGPU" ]; then echo "skip N=$N (only $NGPU GPU(s) visible)"; continue; fi
   OUT=/tmp/mkp_scale_N$N.json
   if [ "$N" -eq 1 ]; then python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARMUP" --no-pmc --no-cpu-baseline > "$OUT" || rc=1
-  else python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "$PORT" bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARMUP" > "$OUT" || rc=1; fi
+  else python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port "$PORT" bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARMUP" --full > "$OUT" || rc=1; fi
   python - "$OUT" "$N" <<'PY' || rc=1
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1]); n = int(sys.argv[2])
