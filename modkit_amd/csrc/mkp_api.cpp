@@ -25,13 +25,13 @@ hipError_t mkp_launch_pileup(hipStream_t, uint32_t /*LDS bytes*/, int /*focus mo
                                  const MkpRowsDev*, uint32_t* /*row cursor*/,
                              uint32_t* /*tile row offsets*/, uint32_t* /*tile row counts*/, const uint32_t* /*chunk offsets*/,
                                  uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, bool /*wide tallies*/);
-hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_t, const void* /*call plane*/, const MkpReadHdr*,
+hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_t, const void* /*base-and-call plane*/, const MkpReadHdr*,
     const uint32_t* /*cover read ids*/,
     uint32_t, const uint32_t*, const uint8_t*, const MkpTagRef*,
                             const uint32_t*, const uint8_t*, const MkpLayout*, const MkpFusedDesc*, const MkpRunParams*,
                                 const uint32_t* /*slot positions*/, uint8_t* /*feature stream*/, MkpVisit*, MkpEvent*, MkpReadOut*, uint32_t*);
 hipError_t mkp_launch_call_plane(hipStream_t, MkpWork*, uint32_t, const uint8_t* /*SEQ*/, const uint32_t* /*ranks*/, const MkpFusedDesc*,
-    void* /*call plane*/);
+    void* /*plane*/, unsigned long long* /*SEQ bytes the decoder reads of MKP_RF_SEQN reads*/);
 hipError_t mkp_stream_set_lds(uint32_t bytes);
 hipError_t mkp_launch_dup_restore(hipStream_t, MkpReadHdr*, const MkpDupCons*, uint32_t);
 hipError_t mkp_launch_dup_events(hipStream_t, MkpReadHdr*, const uint32_t*, const uint8_t*, MkpEvent*, MkpReadOut*, MkpDupCons*, const MkpDupSeg*,
@@ -742,6 +742,7 @@ void make_resident(mkp_ctx* c) {
   lap("upload: focus + event buffers");
   // the fused reads' terms of the decoder's algorithmic bytes (below): what the SEQ sweep and rank marking read, what the plane lookups read
   std::atomic<uint64_t> fused_swept{0}, fused_looked_up{0};
+  unsigned long long* d_seqn_bytes = nullptr;   // the plane builder's count of the SEQ bytes the decoder reads (MKP_RF_SEQN reads only)
   if (stream) {
     if (!preplanned) upload(c->d_slot_pos, slot_pos_h);
     upload(c->d_stiles, stiles);
@@ -761,16 +762,18 @@ void make_resident(mkp_ctx* c) {
               if (h.n_tags > 1) w.ml_off1 = S.tagref[h.tag_off + 1].ml_off; }
           uint64_t n_rk = 0; if (!(h.flags & MKP_RF_BAD)) for (uint32_t t = 0; t < h.n_tags; t++) n_rk += S.tagref[h.tag_off + t].n;
           swept += (h.l_seq + 1) / 2 + 2ull * n_rk;
-          looked_up += std::min<uint64_t>((h.l_seq + 1) / 2, h.n_sl) + (n_rk ? 8ull * std::min<uint64_t>(MKP_PLANE_WORDS(h.l_seq), h.n_sl) : 0);
+          looked_up += 16ull * std::min<uint64_t>(MKP_PLANE_WORDS(h.l_seq), h.n_sl);
         }
         fused_swept += swept; fused_looked_up += looked_up;
       });
-      // the call plane: MKP_PLANE_WORDS(l_seq) 8-byte entries per fused read, in launch order
+      // the base-and-call plane: MKP_PLANE_WORDS(l_seq) 16-byte entries per fused read, in launch order
       uint64_t pw = 0;
       for (uint32_t k = 0; k < nf; k++) { if (pw > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "shard exceeds 2^32 call-plane words; use smaller shards");
         work[k].pad = (uint32_t)pw; pw += MKP_PLANE_WORDS(work[k].l_seq); }
-      c->plane_bytes = pw * 8;
-      c->d_plane.ensure(std::max<uint64_t>(c->plane_bytes, 16));
+      c->plane_bytes = pw * sizeof(MkpPlaneEnt);
+      c->d_plane.ensure(c->plane_bytes + 16);   // + the builder's SEQN byte count behind the entries
+      d_seqn_bytes = reinterpret_cast<unsigned long long*>(c->d_plane.as<char>() + c->plane_bytes);
+      hip_check(hipMemsetAsync(d_seqn_bytes, 0, sizeof(unsigned long long), c->stream), "plane counter reset");
       upload(c->d_work, work);
       std::vector<uint32_t> cover(slot_ids.begin() + nf, slot_ids.end()); upload(c->d_slot_ids, cover);
     }
@@ -778,7 +781,7 @@ void make_resident(mkp_ctx* c) {
       upload(c->d_fdesc, fd); }
     // once per resident shard (a re-launch on the shard reuses it): counted in the upload step
     hip_check(mkp_launch_call_plane(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], c->d_seq.as<uint8_t>(), c->d_ranks.as<uint32_t>(),
-        c->d_fdesc.as<MkpFusedDesc>(), c->d_plane.p), "call plane launch");
+        c->d_fdesc.as<MkpFusedDesc>(), c->d_plane.p, d_seqn_bytes), "call plane launch");
     c->d_cov.ensure(c->cov_bytes + 256); c->d_visits.ensure(std::max<size_t>(S.hdr.size(), 1) * sizeof(MkpVisit));
     hip_check(mkp_stream_set_lds(c->lds_bytes), "hipFuncSetAttribute(max dynamic LDS, stream)");
   }
@@ -807,9 +810,13 @@ void make_resident(mkp_ctx* c) {
     uint64_t n_rs = 0; for (auto& h : S.hdr) n_rs += h.n_sl;
     c->stats.stream_bytes = n_rs;
     c->stats.alg_bytes_decode += 4ull * n_rs + n_rs + 32ull * S.hdr.size();
-    // the fused decoder reads neither a read's whole SEQ nor its rank list: the SEQ byte and the call-plane entry under each slot (the
-    // plane, resolved from SEQ and ranks once per resident shard, is not part of the pass)
-    c->stats.alg_bytes_decode = c->stats.alg_bytes_decode - fused_swept.load() + fused_looked_up.load();
+    // the fused decoder reads neither a read's whole SEQ nor its rank list: the 16-byte plane entry under each slot, and the SEQ byte
+    // only for a read with a base that is not A/C/G/T (the plane, resolved from SEQ and ranks once per resident shard, is not part of
+    // the pass)
+    unsigned long long seqn_bytes = 0;
+    hip_check(hipMemcpyAsync(&seqn_bytes, d_seqn_bytes, sizeof(seqn_bytes), hipMemcpyDeviceToHost, c->stream), "plane counter readback");
+    hip_check(hipStreamSynchronize(c->stream), "plane counter readback");   // (the shard's own stream: idle here, not the ingest ahead)
+    c->stats.alg_bytes_decode = c->stats.alg_bytes_decode - fused_swept.load() + fused_looked_up.load() + seqn_bytes;
     c->stats.alg_bytes_pileup = n_rs + 32ull * S.hdr.size();               // + 44*rows added after the run
     c->stats.alg_bytes_agg_survey = 8ull * n_rs;                            // 8 B per coverage event at a candidate position (+ call events, + 44*rows)
   }

@@ -57,6 +57,7 @@ struct MkpReadHdr {
 #define MKP_RF_BAD 2u
 #define MKP_RF_SUMERR 4u   // host planner: some call's probabilities over the read's two tags add up to more than 1.01 (combine_checked, mod_bam.rs:629-656)
 #define MKP_RF_RUNOVER 8u  // mkp_call_plane (work records only): the delta list runs past the last occurrence of its base (mod_bam.rs:705-727)
+#define MKP_RF_SEQN 16u    // mkp_call_plane (work records only): the stored read holds a base that is not A/C/G/T (the decoder reads its SEQ)
 #define MKP_RF_KEY_SHIFT 8
 #define MKP_NO_KEY_FILTER 0xffffffffu
 
@@ -193,10 +194,17 @@ struct MkpTile { int32_t r0, r1; uint32_t first, last; };
 // stream into LDS tallies.  Feature byte = what FeatureVector::add_feature receives for this alignment at this column
 // (pileup/mod.rs:783-939): [0:4] counter id (MKP_C_*), [5] tally strand, [6:7] the read base as tallied (so that a call of a
 // record that later fails can be counted as NoCall(base)).
-// mkp_decode_slots reads whether a call is listed at a stored base from the CALL PLANE (mkp_call_plane, built once when the shard becomes
-// resident): per fused read and 32 stored bases one uint2 {bit b = "a listed call of the read sits at base 32 w + b", listed calls at the
-// bases before 32 w} — two bits per base, stored order; the read's plane starts at plane[MkpWork.pad]
+// mkp_decode_slots takes the base under a slot, and whether a call is listed there, from the BASE-AND-CALL PLANE (mkp_call_plane, built
+// once when the shard becomes resident): per fused read and 32 stored bases one 16-byte MkpPlaneEnt, stored order, four bits per base; the
+// read's plane starts at plane[MkpWork.pad].  A read whose SEQ holds a base that is not A/C/G/T (MKP_RF_SEQN) has code 0 there: the
+// decoder reads such a read's bases from the SEQ instead.
 #define MKP_PLANE_WORDS(l_seq) (((l_seq) + 31u) >> 5)
+struct MkpPlaneEnt {         // 16 B: one global_load_dwordx4 per slot
+  uint32_t base_lo, base_hi; // 2-bit codes of stored bases 32 w + b (A=0 C=1 G=2 T=3, not complemented): b < 16 at bits 2 b of base_lo,
+                             // b >= 16 at bits 2 (b - 16) of base_hi (mkp_pack_bases32, mkp_base_pack.hpp)
+  uint32_t listed;           // bit b = a listed call of the read sits at base 32 w + b (0 for a read without calls or a run-over list)
+  uint32_t before;           // listed calls at the bases before 32 w
+};
 #define MKP_STREAM_ROWMAP_WORDS 2048u   // mkp_pileup_stream: rows of a tile placed per emission round (a dword of LDS each)
 #define MKP_FB_NONE 0xffu    // the read is not in this column (ref-skip)
 #define MKP_FB_BLANK 0xfeu   // in the column, no feature (non-ACGT base: pileup/mod.rs:864-874)
@@ -234,7 +242,7 @@ struct MkpWork {             // 64 B
   int32_t ref_start; uint32_t l_seq, n_cigar, cigar_off, seq_off, flags, gs0, n_sl, cov_off;
   uint16_t n_tags, layout;
   uint32_t rank_off, n_calls, ml_off0, ml_off1;   // the shared rank list, the tags' ML bytes
-  uint32_t rid, pad;                              // pad: the read's first call-plane entry (MKP_PLANE_WORDS(l_seq) of them)
+  uint32_t rid, pad;                              // pad: the read's first plane entry (MKP_PLANE_WORDS(l_seq) of them)
 };
 // Records that share a read NAME inside one interval of the reference's grid (unmarked duplicates, mates, split reads that kept the primary flag).
 // The reference keeps ONE cache entry per name and interval (ReadCache, read_cache.rs:24-43): the record asked about first — the first focus
@@ -267,5 +275,5 @@ struct MkpRowsDev {  // SoA row buffers (44 B / row)
 };
 #ifdef __cplusplus
 static_assert(sizeof(MkpWork) == 64, "work record is 16 dwords");
-static_assert(sizeof(MkpFusedDesc) == 64 && sizeof(MkpVisit) == 32, "slot pipeline records");
+static_assert(sizeof(MkpFusedDesc) == 64 && sizeof(MkpVisit) == 32 && sizeof(MkpPlaneEnt) == 16, "slot pipeline records");
 #endif

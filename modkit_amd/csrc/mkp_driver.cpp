@@ -921,8 +921,8 @@ class AheadIngest {
 
   // packed arrays of a shard ~ 1.9 x its compressed blocks on ONT-like data (SEQ nibbles + CIGAR words + 5 bytes per call; names and
   // qualities are not kept), the inflated window of the ingest object in flight on top: 2.5 x; and once the shard is resident, the slot
-  // decoder's call plane (two bits per stored base = half the SEQ nibbles, ~0.5 x): 3 x as the estimate
-  static uint64_t est_of(uint64_t comp_bytes) { return comp_bytes * 3 + (64ull << 20); }
+  // decoder's base-and-call plane (four bits per stored base = as many bytes as the SEQ nibbles, ~1 x): 3.5 x as the estimate
+  static uint64_t est_of(uint64_t comp_bytes) { return comp_bytes * 7 / 2 + (64ull << 20); }
 
   // every target record as one shard, its records grouped by contig under --include-bed; nothing when one of them does not fit a shard
   // (a contig larger than a shard: the shards are cut on the grid and ingested ahead once the plan is known, from_plan)

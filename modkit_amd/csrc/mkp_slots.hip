@@ -3,15 +3,17 @@
 // the host numbers the window's slots in genome order (slot_pos[g] = position of global slot g) and gives every read the slot
 // range [gs0, gs0 + n_sl) of its reference span.  One device pass:
 //
-//   mkp_call_plane        once per resident shard: per fused read, one bit per stored base "a listed call sits here" and the number
-//                         of listed calls before every 32 bases (the rank list resolved against the SEQ: it does not depend on the pass)
+//   mkp_call_plane        once per resident shard: per fused read and 32 stored bases one 16-byte entry — the bases' 2-bit codes, one
+//                         bit per base "a listed call sits here" and the number of listed calls before the 32 bases (the SEQ and the
+//                         rank list resolved against each other: nothing of it depends on the pass)
 //   mkp_decode_slots      one wave per read, reads whose MM tags form one explicit-mode ('?') group with one shared delta list
 //                         (`C+m?`, `C+hm?`, `C+h?;C+m?` as basecallers write them), no edge filter.  The walk is driven by the
-//                         read's SLOTS, not by its calls, 64 slots per step: CIGAR (128-op register window, reference -> query), the
-//                         base, whether a call is listed there and as which call (one 8-byte call-plane gather beside the SEQ byte),
+//                         read's SLOTS, not by its calls, 64 slots per step: CIGAR (256-op register window, reference -> query), the
+//                         base, whether a call is listed there and as which call (one 16-byte plane gather; the SEQ byte only for a
+//                         read with a base that is not A/C/G/T),
 //                         ML -> f32 probabilities -> MultipleThresholdModCaller::call, and ONE FEATURE BYTE per slot goes to the
 //                         read's run of the feature stream.  Calls on non-focus positions are never located (their rows would be
-//                         dropped, pileup/mod.rs:570-604); CIGAR is read once per pass, SEQ and the plane only under the slots.
+//                         dropped, pileup/mod.rs:570-604); CIGAR is read once per pass, the plane only under the slots.
 //   mkp_cover_reads       every other read (implicit-mode / multi-group / duplex / `N` tags / failed tags, or any read when an edge
 //                         filter is set): the decode kernels of mkp_kernels.hip leave position-sorted call events; this kernel walks
 //                         the read's slots (coverage features) and merges the events into the stream.
@@ -24,6 +26,7 @@
 // Semantics follow /root/reference/src (cited inline).  f32 arithmetic is the reference's (contraction off, IEEE division).
 #include <cstdlib>
 
+#include "mkp_base_pack.hpp"
 #include "mkp_dev_common.hpp"
 #include "mkp_dev_rows.hpp"
 
@@ -34,10 +37,6 @@ struct SlotLds { int32_t ck_thr[4]; uint32_t ck_off[4]; uint32_t ck_str[4]; uint
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
-// flag word of a SEQ dword: bit 4n set where nibble n equals the BAM code in `pat`
-__device__ __forceinline__ uint32_t nib_eq(uint32_t x, uint32_t pat) { uint32_t t = x ^ pat; t |= t >> 1; t |= t >> 2; return ~t & 0x11111111u; }
-// the eight flags (bits 4n) gathered into bits n
-__device__ __forceinline__ uint32_t gather8(uint32_t t) { return (((t | (t >> 3)) & 0x03030303u) * 0x01041040u) >> 24; }
 __device__ __forceinline__ uint32_t feat(uint32_t cid, uint32_t tally) { return cid | (tally << 5); }
 
 #define SLOT_PARAMS(PRM) const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads, const uint32_t* __restrict__ read_ids, const uint32_t* __restrict__ cigar, \
@@ -211,18 +210,21 @@ __device__ __forceinline__ uint32_t cover_feature(uint32_t kind, uint32_t nib, u
 }
 
 // ----------------------------------------------------------------------------------------------------------------------
-// mkp_call_plane: the call plane of the fused reads (MKP_PLANE_WORDS in mkp_device.h), built once when the shard becomes resident — what
-// it answers (is a listed call at this stored base, and which one) depends on the SEQ, the rank list, the strand and the tag's fundamental
-// base only, never on the pass.  One wave per work record:
-//   1. occurrences of the fundamental base in the stored read (four 16-byte SEQ loads per lane at a time) -> tot; a delta list whose
-//      last entry is not below tot runs past the base's last occurrence (mod_bam.rs:705-727): MKP_RF_RUNOVER in the work record, no plane;
-//   2. 64 plane words (2 048 bases) per step: the words' flag bitmaps and their occurrence counts (a wave scan), then the rank list's
-//      entries that fall on the step's occurrences, in stored order (a reverse read's forward rank e is stored ordinal tot - 1 - e: its list
-//      is consumed from the end), each placed on its word (a search over the lanes' counts) and its bit (the (o - count)-th flag of the
-//      word); the word's listed calls before it are the running count plus a wave scan.
+// mkp_call_plane: the base-and-call plane of the fused reads (MkpPlaneEnt, mkp_device.h), built once when the shard becomes resident —
+// what it answers (the base at this stored index; is a listed call there, and which one) depends on the SEQ, the rank list, the strand and
+// the tag's fundamental base only, never on the pass.  One wave per work record; every fused read gets its bases, the call fields are zero
+// for a read without calls:
+//   one walk over the read's words in the order the tag counts its base (a reverse read from its last word, its flag bitmaps bit-reversed),
+//   64 plane entries (2 048 bases) per step: the entries' 2-bit base codes (mkp_pack_bases32; a base that is not A/C/G/T sets MKP_RF_SEQN)
+//   and, for a read with calls, the words' flag bitmaps (mkp_bases_eq) and their occurrence counts (a wave scan), then the rank list's
+//   entries that fall on the step's occurrences, in list order, each placed on its word (a search over the lanes' counts) and its bit (the
+//   (o - count)-th flag of the word); the word's listed calls before it in stored order follow from the running count and a wave scan.  A
+//   delta list whose last entry is not below the base's occurrence count runs past its last occurrence (mod_bam.rs:705-727): entries are
+//   left unplaced, MKP_RF_RUNOVER in the work record.
+// seqn_bytes collects what the decoder will read of the SEQN reads' SEQ (one byte per slot, at most the read's bytes): algorithmic bytes.
 // Reference: DeltaListConverter::new / to_positions (mod_bam.rs:667-733).
 extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __restrict__ work, uint32_t n_reads, const uint8_t* __restrict__ seqs,
-    const uint32_t* __restrict__ ranks, const MkpFusedDesc* __restrict__ fdesc, uint2* __restrict__ plane) {
+    const uint32_t* __restrict__ ranks, const MkpFusedDesc* __restrict__ fdesc, uint4* __restrict__ plane, unsigned long long* __restrict__ seqn_bytes) {
   __shared__ uint32_t bm_all[4][64];
   const int lane = lane_id();
   const uint32_t wib = rfl(threadIdx.x >> 6);
@@ -230,80 +232,118 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
   if (widx >= n_reads) return;
   const MkpWork h = work[widx];
   const uint32_t t_n = h.n_calls;
-  if ((h.flags & MKP_RF_BAD) || h.n_tags == 0 || t_n == 0) return;   // no calls: the decoder never reads the plane
+  bool calls = !(h.flags & MKP_RF_BAD) && h.n_tags != 0 && t_n != 0;   // without calls the decoder reads only the bases
+  uint32_t flags = h.flags;
   uint32_t* __restrict__ bm = bm_all[wib];
   const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
   const uint32_t L = h.l_seq, nd = (L + 7u) >> 3, nw = MKP_PLANE_WORDS(L);
   const uint8_t* __restrict__ seqb = seqs + h.seq_off;
   const uint32_t* __restrict__ rk = ranks + h.rank_off;
-  const uint32_t fb = fdesc[h.layout].misc & 3u;
-  const uint32_t pat = 0x11111111u << (rev ? 3u - fb : fb);   // the stored base the tags count (its BAM code in every nibble)
-  const uint32_t e_last = rk[t_n - 1u];
-  // flag bitmap of plane word w: bit b = stored base 32 w + b is the base (base 2j of a SEQ byte is its high nibble); bases at or past L
-  // (the pad nibble of an odd L, the zero padding) are cleared
-  auto word_flags = [&](uint32_t w) {
+  // the four SEQ dwords of plane word w; dwords at or past the read's end read as 0
+  auto word_seq = [&](uint32_t w) {
     const uint32_t d = 4u * w;
     uint4 x = ldo<uint4>(seqb, 4u * min(d, nd - 1u));   // (clamped to the read's last dword: the SEQ buffer has slack behind the last read)
     if (d + 1u >= nd) x.y = 0u; if (d + 2u >= nd) x.z = 0u; if (d + 3u >= nd) x.w = 0u; if (d >= nd) x.x = 0u;
-    const uint32_t xw[4] = {x.x, x.y, x.z, x.w};
-    uint32_t f = 0;
-#pragma unroll
-    for (int k = 0; k < 4; k++) { const uint32_t g = gather8(nib_eq(xw[k], pat)); f |= (((g & 0x55u) << 1) | ((g >> 1) & 0x55u)) << (8 * k); }
-    const uint32_t b0 = 32u * w;
-    return b0 >= L ? 0u : L - b0 >= 32u ? f : f & ((1u << (L - b0)) - 1u);
+    return x;
   };
-  uint32_t acc = 0;
-  for (uint32_t w0 = 0; w0 < nw; w0 += 256u) {
-    uint32_t f[4];
+  const uint32_t fb = calls ? fdesc[h.layout].misc & 3u : 0u;
+  const uint32_t sb = rev ? 3u - fb : fb;   // the stored base the tags count
+  // The words are walked in the order the tag counts its base: a forward read from its first word, a reverse read from its last (word
+  // w = nw - 1 - k at walk index k, its flag bitmap bit-reversed), so that the rank list is consumed from its start and the walk's running
+  // occurrence count IS the rank — no pass that counts the base first.  256 words per chunk, four per lane (k = k0 + 64 j + lane): four
+  // 16-byte SEQ loads in flight, packed into the entries' base codes and, for a read with calls, the flag bitmaps taken from the codes.
+  uint32_t lo[4], hi[4], f[4];
+  bool seqn = false;
+  auto word_of = [&](uint32_t k) { return rev ? nw - 1u - k : k; };
+  auto load_chunk = [&](uint32_t k0) {
+    uint4 x[4];
 #pragma unroll
-    for (int j = 0; j < 4; j++) { const uint32_t w = w0 + 64u * (uint32_t)j + (uint32_t)lane; f[j] = w < nw ? word_flags(w) : 0u; }
-#pragma unroll
-    for (int j = 0; j < 4; j++) acc += (uint32_t)__popc(f[j]);
-  }
-  const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(acc), 63);
-  if (rfl(e_last) >= tot) { if (lane == 0) work[widx].flags = h.flags | MKP_RF_RUNOVER; return; }
-  uint2* __restrict__ pl = plane + h.pad;
-  uint32_t occ = 0, j = 0;   // occurrences before the step, listed calls before the step (both stored order)
-  for (uint32_t w0 = 0; w0 < nw; w0 += 64u) {
-    const uint32_t w = w0 + (uint32_t)lane;
-    const uint32_t f = w < nw ? word_flags(w) : 0u, c = (uint32_t)__popc(f);
-    const uint32_t incl = wave_incl_scan(c), cnt = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    const uint32_t j0 = j;
-    bm[lane] = 0u;
-    wave_lds_fence();
-    for (;;) {
-      const uint32_t i = j + (uint32_t)lane;
-      const bool valid = i < t_n;
-      const uint32_t e = valid ? ldo<uint32_t>(rk, 4u * (rev ? t_n - 1u - i : i)) : 0u;
-      const uint32_t rel = (rev ? tot - 1u - e : e) - occ;   // (entries below the step were consumed by the steps before)
-      const bool hit = valid && rel < cnt;
-      const uint32_t rq = hit ? rel : 0u;
-      // the word: the number of lanes whose inclusive count is <= rel (six probes)
-      uint32_t probe = 31u << 2;
-#pragma unroll
-      for (int hstep = 16; hstep >= 1; hstep >>= 1) {
-        const uint32_t vv = (uint32_t)__builtin_amdgcn_ds_bpermute((int)probe, (int)incl);
-        probe = vv <= rq ? probe + 4u * (uint32_t)hstep : probe - 4u * (uint32_t)hstep;
-      }
-      { const uint32_t vv = (uint32_t)__builtin_amdgcn_ds_bpermute((int)probe, (int)incl); probe = vv <= rq ? probe + 4u : probe; }
-      const int oa = (int)(probe & 255u);
-      const uint32_t fo = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)f), io = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)incl);
-      // the bit: the n-th flag of the word (halving select)
-      uint32_t n = rq - (io - (uint32_t)__popc(fo)), pos = 0;
-#pragma unroll
-      for (int s = 16; s >= 1; s >>= 1) {
-        const uint32_t lo = (uint32_t)__popc((fo >> pos) & ((1u << s) - 1u));
-        if (n >= lo) { n -= lo; pos += (uint32_t)s; }
-      }
-      if (hit) atomicOr(&bm[probe >> 2], 1u << pos);
-      const uint32_t nh = (uint32_t)__popcll(__ballot(hit));
-      j += nh;
-      if (nh < 64u) break;
+    for (int j = 0; j < 4; j++) {
+      const uint32_t k = k0 + 64u * (uint32_t)j + (uint32_t)lane;
+      x[j] = k < nw ? word_seq(word_of(k)) : make_uint4(0u, 0u, 0u, 0u);
     }
-    wave_lds_fence();
-    const uint32_t lw = bm[lane], lc = (uint32_t)__popc(lw), li = wave_incl_scan(lc);
-    if (w < nw) pl[w] = make_uint2(lw, j0 + li - lc);
-    occ += cnt;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const uint32_t k = k0 + 64u * (uint32_t)j + (uint32_t)lane, w = word_of(k);
+      uint32_t l = 0u, hh = 0u, fl = 0u;
+      if (k0 + 64u * (uint32_t)j < nw && k < nw) {   // (the first test is uniform: a quarter without a word of the read is not packed)
+        const uint32_t b0 = 32u * w, nv = b0 >= L ? 0u : min(L - b0, 32u);
+        const uint32_t bad = mkp_pack_bases32(x[j].x, x[j].y, x[j].z, x[j].w, nv, &l, &hh);
+        seqn = seqn || bad != 0u;
+        if (calls) {
+          fl = mkp_bases_eq(l, hh, sb) & ~bad & (nv >= 32u ? 0xffffffffu : (1u << nv) - 1u);
+          if (rev) fl = __brev(fl);
+        }
+      }
+      lo[j] = l; hi[j] = hh; f[j] = fl;
+    }
+  };
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  uint4* __restrict__ pl = plane + h.pad;
+  uint32_t occ = 0, j = 0;   // occurrences before the step, listed calls before the step (both in walk order)
+  for (uint32_t k0 = 0; k0 < nw; k0 += 256u) {
+    load_chunk(k0);
+#pragma unroll
+    for (int jj = 0; jj < 4; jj++) {   // 64 words per step
+      if (k0 + 64u * (uint32_t)jj >= nw) break;
+      const uint32_t k = k0 + 64u * (uint32_t)jj + (uint32_t)lane, w = word_of(k);
+      uint32_t lw = 0, before = 0;
+      if (calls) {
+        const uint32_t fw = f[jj], c = (uint32_t)__popc(fw);
+        const uint32_t incl = wave_incl_scan(c), cnt = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const uint32_t j0 = j;
+        bm[lane] = 0u;
+        wave_lds_fence();
+        for (;;) {
+          const uint32_t i = j + (uint32_t)lane;
+          const bool valid = i < t_n;
+          const uint32_t e = valid ? ldo<uint32_t>(rk, 4u * i) : 0u;
+          const uint32_t rel = e - occ;   // (entries below the step were consumed by the steps before)
+          const bool hit = valid && rel < cnt;
+          const uint32_t rq = hit ? rel : 0u;
+          // the word: the number of lanes whose inclusive count is <= rel (six probes)
+          uint32_t probe = 31u << 2;
+#pragma unroll
+          for (int hstep = 16; hstep >= 1; hstep >>= 1) {
+            const uint32_t vv = (uint32_t)__builtin_amdgcn_ds_bpermute((int)probe, (int)incl);
+            probe = vv <= rq ? probe + 4u * (uint32_t)hstep : probe - 4u * (uint32_t)hstep;
+          }
+          { const uint32_t vv = (uint32_t)__builtin_amdgcn_ds_bpermute((int)probe, (int)incl); probe = vv <= rq ? probe + 4u : probe; }
+          const int oa = (int)(probe & 255u);
+          const uint32_t fo = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)fw), io = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)incl);
+          // the bit: the n-th flag of the word (halving select)
+          uint32_t n = rq - (io - (uint32_t)__popc(fo)), pos = 0;
+#pragma unroll
+          for (int s = 16; s >= 1; s >>= 1) {
+            const uint32_t lo_n = (uint32_t)__popc((fo >> pos) & ((1u << s) - 1u));
+            if (n >= lo_n) { n -= lo_n; pos += (uint32_t)s; }
+          }
+          if (hit) atomicOr(&bm[probe >> 2], 1u << pos);
+          const uint32_t nh = (uint32_t)__popcll(__ballot(hit));
+          j += nh;
+          if (nh < 64u) break;
+        }
+        wave_lds_fence();
+        lw = bm[lane];
+        const uint32_t lc = (uint32_t)__popc(lw), li = wave_incl_scan(lc);
+        // listed calls at the stored bases before word w: on a forward read those walked before it; on a reverse read all of them but the
+        // ones at w and behind it (every entry is placed unless the list runs over, and then the call fields are never read)
+        before = rev ? t_n - (j0 + li) : j0 + li - lc;
+        if (rev) lw = __brev(lw);
+        occ += cnt;
+      }
+      // (non-temporal: the entries are written once here and read by the decoder passes much later; through the cache they only
+      // displace the SEQ and the rank lists the builder is still reading)
+      if (k < nw) { const u32x4 v = {lo[jj], hi[jj], lw, before}; __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(pl) + w); }
+    }
+  }
+  // a delta list runs past the base's last occurrence (mod_bam.rs:705-727) iff the walk leaves entries unplaced: MKP_RF_RUNOVER, and the
+  // record contributes coverage only (its call fields are never read)
+  if (calls && j < t_n) flags |= MKP_RF_RUNOVER;
+  if (__any(seqn)) flags |= MKP_RF_SEQN;
+  if (lane == 0) {
+    if (flags != h.flags) work[widx].flags = flags;
+    if (flags & MKP_RF_SEQN) atomicAdd(seqn_bytes, (unsigned long long)min((L + 1u) >> 1, h.n_sl));
   }
 }
 
@@ -313,11 +353,11 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
 // into_collapsed (530-627), MultipleThresholdModCaller::call (threshold_mod_caller.rs:28-63), ReadCache::add_record
 // (read_cache.rs:111-211), get_aligned_pairs_forward (util.rs:122-145), process_region's alignment loop (pileup/mod.rs:783-939).
 // One wave runs one read start to end.  Measured (SQ counters, C3): the kernel is VALU-issue bound, so the per-slot instruction count
-// matters: the rank list was resolved into the call plane when the shard became resident (mkp_call_plane), so that a slot learns whether a
-// call is listed at its base, and as which call, from one 8-byte gather issued beside its SEQ byte and a popcount; the caller is resolved to
+// matters: the SEQ and the rank list were resolved into the plane when the shard became resident (mkp_call_plane), so that a slot learns its
+// base, whether a call is listed there and as which call from one 16-byte gather and a popcount; the caller is resolved to
 // a fixed walk per read.  No per-read LDS beyond the caller constants and no base windows: reads of every length take the same code.
 #define FUSED_PARAMS(PRM) const MkpWork* __restrict__ work, uint32_t n_reads, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ seqs, \
-    const uint2* __restrict__ plane, const uint8_t* __restrict__ ml, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const uint32_t* __restrict__ slot_pos, \
+    const uint4* __restrict__ plane, const uint8_t* __restrict__ ml, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const uint32_t* __restrict__ slot_pos, \
     uint8_t* __restrict__ cov, MkpVisit* __restrict__ visits, MkpReadOut* __restrict__ readout
 #define FUSED_PASS work, n_reads, cigar, seqs, plane, ml, fdesc, prm, slot_pos, cov, visits, readout
 __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParams&), SlotLds* __restrict__ lds_all) {
@@ -330,9 +370,10 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
   const uint32_t aln = rev ? 1u : 0u;
   const uint32_t L = h.l_seq;
-  const uint8_t* __restrict__ seqb = seqs + h.seq_off;
-  const uint2* __restrict__ pl = plane + h.pad;
+  const uint4* __restrict__ pl = plane + h.pad;
   const uint32_t* __restrict__ cg = cigar + h.cigar_off;
+  // a read with a base that is not A/C/G/T takes its bases from the SEQ (its offset; ~0 for every other read: one scalar register)
+  const uint32_t seqn_off = (h.flags & MKP_RF_SEQN) ? h.seq_off : 0xffffffffu;
   bool have_calls = !(h.flags & MKP_RF_BAD) && h.n_tags != 0;
   // combine_checked's sum test (mod_bam.rs:629-656) — two tags on one base: the probabilities of a call add up to more than 1.01 — is
   // made by the host planner over the ML bytes (the f32 sums are exact multiples of 1/512: an integer comparison); a delta list that runs
@@ -378,7 +419,7 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
 #endif
   if (have_calls && err_rec) have_calls = false;   // the record only contributes coverage (skip_set, read_cache.rs:272-277)
 #ifdef MKP_DEBUG
-  const bool plane_calls = have_calls && !(prm.debug_skip & 128u);   // ablation: no plane lookups, no calls
+  const bool plane_calls = have_calls && !(prm.debug_skip & 128u);   // ablation: no calls (the base is still read from the plane)
 #else
   const bool plane_calls = have_calls;
 #endif
@@ -401,16 +442,18 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
 #endif
     refwin_s_map(rw, cg, h.n_cigar, h.ref_start, valid, p, &kind, &q);
     const bool is_match = valid && kind == 0u && q < L;
-    const uint32_t byte = is_match ? (uint32_t)ldo<uint8_t>(seqb, q >> 1) : 0u;
-    // the plane word of the base: bit q & 31 = a listed call sits here, .y + the listed bits below it = its stored-order ordinal
-    const uint2 pw = (plane_calls && is_match) ? ldo<uint2>(pl, 8u * (q >> 5)) : make_uint2(0u, 0u);
+    // the plane entry of the base: its 2-bit code, bit q & 31 of .listed = a listed call sits here, .before + the listed bits below it =
+    // its stored-order ordinal
+    const uint4 pe = is_match ? ldo<uint4>(pl, 16u * (q >> 5)) : make_uint4(0u, 0u, 0u, 0u);
+    uint32_t code = (((q & 16u) ? pe.y : pe.x) >> (2u * (q & 15u))) & 3u;
+    asm volatile("" : "+v"(code));   // (formed here: left to itself the compiler carries .x and .y through the caller below)
     uint32_t call_fb = 0xffffffffu;
     if (plane_calls) {
       const uint32_t qb = q & 31u;
-      const bool listed = (pw.x >> qb) & 1u;
+      const bool listed = (pe.z >> qb) & 1u;
       if (__any(listed)) {
         // calls are listed in forward order: a reverse read's stored ordinal j is call n_calls - 1 - j
-        const uint32_t jrel = pw.y + (uint32_t)__popc(pw.x & ((1u << qb) - 1u));
+        const uint32_t jrel = pe.w + (uint32_t)__popc(pe.z & ((1u << qb) - 1u));
         const uint32_t jl = listed ? (rev ? t_n - 1u - jrel : jrel) : 0u;
         // MultipleThresholdModCaller::call (threshold_mod_caller.rs:28-63) on the map of this call, entries in the map's
         // iteration order: pass threshold, Iterator::max keeps the last maximum, canonical pushed last.  ReDistribute runs
@@ -480,7 +523,10 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
         if (listed) call_fb = feat(cid, aln ^ sg0u);   // FeatureVector::add_feature's tally (pileup/mod.rs:238-281)
       }
     }
-    const uint32_t nib = (q & 1u) ? (byte & 15u) : (byte >> 4);
+    // the BAM code of the base (one-hot for A/C/G/T); a SEQN read's from its SEQ byte, so that a non-ACGT base stays one
+    uint32_t nib = 1u << code;
+    if (seqn_off != 0xffffffffu) {
+      const uint32_t byte = is_match ? (uint32_t)ldo<uint8_t>(seqs, seqn_off + (q >> 1)) : 0u; nib = (q & 1u) ? (byte & 15u) : (byte >> 4); }
     uint32_t fb = cover_feature(valid ? kind : 2u, nib, aln);
     if (valid && kind == 0u && q >= L) fb = MKP_FB_NONE;   // (a CIGAR longer than SEQ is refused by the packer)
     // (a scalar count: no per-lane counter, no scan at the end)
@@ -1035,16 +1081,18 @@ extern "C" hipError_t mkp_launch_slots(hipStream_t st, const MkpWork* work, uint
                                            const MkpLayout* layouts, const MkpFusedDesc* fdesc, const MkpRunParams* prm,
                                        const uint32_t* slot_pos, uint8_t* cov, MkpVisit* visits, MkpEvent* events, MkpReadOut* readout,
                                            uint32_t* dev_err) {
-  if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, cigar, seqs, static_cast<const uint2*>(plane), ml, fdesc, *prm,
+  if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, cigar, seqs, static_cast<const uint4*>(plane), ml, fdesc, *prm,
       slot_pos, cov, visits, readout);
   if (n_cover) hipLaunchKernelGGL(mkp_cover_reads, dim3((n_cover + 3u) / 4u), dim3(256), 0, st, hdrs, n_cover, cover_ids, cigar, seqs, tagref, ranks,
       ml, layouts, fdesc, *prm, slot_pos, cov, visits, events, readout, dev_err);
   return hipGetLastError();
 }
-// the call plane of the fused reads (once per resident shard; it also marks the work records whose delta list runs past its base)
+// the base-and-call plane of the fused reads (once per resident shard; it also marks the work records whose delta list runs past its base
+// and those with a base that is not A/C/G/T, and adds the SEQ bytes the decoder reads of the latter to *seqn_bytes)
 extern "C" hipError_t mkp_launch_call_plane(hipStream_t st, MkpWork* work, uint32_t n_fused, const uint8_t* seqs, const uint32_t* ranks,
-    const MkpFusedDesc* fdesc, void* plane) {
-  if (n_fused) hipLaunchKernelGGL(mkp_call_plane, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, seqs, ranks, fdesc, static_cast<uint2*>(plane));
+    const MkpFusedDesc* fdesc, void* plane, unsigned long long* seqn_bytes) {
+  if (n_fused) hipLaunchKernelGGL(mkp_call_plane, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, seqs, ranks, fdesc, static_cast<uint4*>(plane),
+      seqn_bytes);
   return hipGetLastError();
 }
 
