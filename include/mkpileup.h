@@ -205,6 +205,14 @@ int mkp_batch_run(mkp_ctx* ctx, const mkp_shard* intervals, uint32_t n_intervals
  * what bench.py times.  `iters` launches; rows of the last one are returned. */
 int mkp_shard_rerun(mkp_ctx* ctx, uint32_t iters, mkp_rows* out);
 int mkp_get_stats(const mkp_ctx* ctx, mkp_stats* out);
+/* DIAGNOSTIC (tests and debugging; no caller needs it to run a pileup, and the bits may grow): what the packer decided per read of the
+ * shard that is open or resident, in file order (the reads the pileup keeps): MKP_READ_REVERSE reverse strand, MKP_READ_TAG_ERROR the
+ * read only contributes coverage, MKP_READ_WIDE_CIGAR a CIGAR op longer than 4 095 bases — the slot decoder walks the read's 32-bit
+ * CIGAR words instead of the 16-bit ones.  *n_reads = reads of the shard; at most `cap` flags are written. */
+#define MKP_READ_REVERSE 1u
+#define MKP_READ_TAG_ERROR 2u
+#define MKP_READ_WIDE_CIGAR 32u
+int mkp_shard_read_flags(const mkp_ctx* ctx, uint32_t* flags, uint32_t cap, uint32_t* n_reads);
 
 /* ---- same, reading the BAM itself: direct stand-in for process_region_batch(bam_fp, ...)
  * (src/pileup/mod.rs:684-716; the IndexedReader fetch + pileup of :732-759).  With a .bai next to the file the window's

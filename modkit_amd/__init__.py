@@ -89,13 +89,14 @@ def lib():
 
 
 ABI_VERSION = 3   # MKP_ABI_VERSION of include/mkpileup.h
+READ_WIDE_CIGAR = 32   # MKP_READ_WIDE_CIGAR
 
 
 # mkp_threshold_fn (include/mkpileup.h): int fn(void* user, mkp_ctx* ctx, int have_sample, float thresholds[4], uint8_t has[4])
 THRESHOLD_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint8))
 
 EXPORTS = ["mkp_ctx_create", "mkp_ctx_destroy", "mkp_last_error", "mkp_version", "mkp_abi_version", "mkp_run_report_size", "mkp_host_threads", "mkp_set_caller", "mkp_shard_begin",
-           "mkp_shard_add_records", "mkp_shard_set_intervals", "mkp_shard_run", "mkp_batch_run", "mkp_shard_rerun", "mkp_get_stats", "mkp_process_region", "mkp_pileup_main",
+           "mkp_shard_add_records", "mkp_shard_set_intervals", "mkp_shard_run", "mkp_batch_run", "mkp_shard_rerun", "mkp_get_stats", "mkp_shard_read_flags", "mkp_process_region", "mkp_pileup_main",
            "mkp_pileup_run", "mkp_pileup_run_cb", "mkp_percentile", "mkp_estimate_thresholds", "mkp_host_mm_ranks", "mkp_host_map_order",
            "mkp_set_partition_tags", "mkp_histogram_begin", "mkp_histogram_add_bam", "mkp_histogram_get", "mkp_histogram_allreduce", "mkp_histogram_from_values", "mkp_histogram_locate",
            "mkp_histogram_resolve", "mkp_percentile_from_histogram", "mkp_hemi_shard_run", "mkp_pileup_hemi_main", "mkp_pileup_hemi_run", "mkp_bgzf_inflate", "mkp_sample_probs", "mkp_summary", "mkp_extract_calls_main"]
@@ -389,6 +390,14 @@ class Context:
         rows = Rows()
         self._check(self.L.mkp_shard_rerun(self.h, int(iters), ctypes.byref(rows) if fetch else None))
         return rows
+
+    def read_flags(self):
+        """the packer's flags of the reads of the open / resident shard, file order (READ_WIDE_CIGAR: mkp_shard_read_flags)"""
+        n = ctypes.c_uint32(0)
+        self._check(self.L.mkp_shard_read_flags(self.h, None, 0, ctypes.byref(n)))
+        buf = (ctypes.c_uint32 * max(n.value, 1))()
+        self._check(self.L.mkp_shard_read_flags(self.h, buf, n.value, ctypes.byref(n)))
+        return list(buf[:n.value])
 
     def stats(self):
         s = Stats()

@@ -25,7 +25,8 @@ hipError_t mkp_launch_pileup(hipStream_t, uint32_t /*LDS bytes*/, int /*focus mo
                                  const MkpRowsDev*, uint32_t* /*row cursor*/,
                              uint32_t* /*tile row offsets*/, uint32_t* /*tile row counts*/, const uint32_t* /*chunk offsets*/,
                                  uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, bool /*wide tallies*/);
-hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_t, const void* /*base-and-call plane*/, const MkpReadHdr*,
+hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_t, const void* /*base-and-call plane*/,
+    const uint16_t* /*16-bit CIGAR*/, const MkpReadHdr*,
     const uint32_t* /*cover read ids*/,
     uint32_t, const uint32_t*, const uint8_t*, const MkpTagRef*,
                             const uint32_t*, const uint8_t*, const MkpLayout*, const MkpFusedDesc*, const MkpRunParams*,
@@ -513,7 +514,7 @@ void make_resident(mkp_ctx* c) {
       auto crank = [&](int64_t p) { return rank(std::min(std::max(p, lo_clamp), hi_clamp)); };
       const uint32_t total = wpfx[nwords];
       host_parallel(S.hdr.size(), 8192, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; i++) { MkpReadHdr& h = S.hdr[i];
-          const uint32_t a = crank(h.ref_start), b = std::max(a, crank(h.ref_end)); h.gs0 = a; h.n_sl = b - a; h.pad = 0; } });
+          const uint32_t a = crank(h.ref_start), b = std::max(a, crank(h.ref_end)); h.gs0 = a; h.n_sl = b - a; } });
       uint64_t off = 0;
       for (auto& h : S.hdr) {   // (the stream offsets are a running sum: serial, but nothing else is left in the loop)
         h.cov_off = (uint32_t)off;
@@ -725,7 +726,7 @@ void make_resident(mkp_ctx* c) {
   auto t1 = std::chrono::steady_clock::now();
   hip_check(hipSetDevice(c->device), "hipSetDevice");
   upload(c->d_hdr, S.hdr);
-  if (!S.dev_packed) { upload(c->d_cigar, S.cigar); upload(c->d_chunk, S.chunk_pfx); upload(c->d_seq, S.seq); upload(c->d_tagref, S.tagref);
+  if (!S.dev_packed) { upload(c->d_cigar, S.cigar); upload(c->d_cigar16, S.cigar16); upload(c->d_chunk, S.chunk_pfx); upload(c->d_seq, S.seq); upload(c->d_tagref, S.tagref);
     upload(c->d_ranks, S.ranks); upload(c->d_ml, S.ml); }
   // (device ingest: those arrays were written in HBM by mkp_ingest_pack and handed over by mkp_internal_shard_attach)
   lap("upload: packed reads");
@@ -753,7 +754,9 @@ void make_resident(mkp_ctx* c) {
         uint64_t swept = 0, looked_up = 0;
         for (size_t k = lo; k < hi; k++) {
           const MkpReadHdr& h = S.hdr[slot_ids[k]]; MkpWork& w = work[k]; memset(&w, 0, sizeof(w));
-          w.ref_start = h.ref_start; w.l_seq = h.l_seq; w.n_cigar = h.n_cigar; w.cigar_off = h.cigar_off; w.seq_off = h.seq_off; w.flags = h.flags;
+          w.ref_start = h.ref_start; w.l_seq = h.l_seq; w.n_cigar = h.n_cigar;
+          w.cigar_off = (h.flags & MKP_RF_CIGW) ? h.cigar_off : h.cigar16_off;   // the decoder's array of this read (MkpWork, mkp_device.h)
+          w.seq_off = h.seq_off; w.flags = h.flags;
             w.gs0 = h.gs0;
               w.n_sl = h.n_sl;
           w.cov_off = h.cov_off; w.n_tags = h.n_tags; w.layout = h.layout; w.rid = slot_ids[k];
@@ -761,7 +764,7 @@ void make_resident(mkp_ctx* c) {
             w.ml_off0 = t0.ml_off;
               if (h.n_tags > 1) w.ml_off1 = S.tagref[h.tag_off + 1].ml_off; }
           uint64_t n_rk = 0; if (!(h.flags & MKP_RF_BAD)) for (uint32_t t = 0; t < h.n_tags; t++) n_rk += S.tagref[h.tag_off + t].n;
-          swept += (h.l_seq + 1) / 2 + 2ull * n_rk;
+          swept += (h.l_seq + 1) / 2 + 2ull * n_rk + ((h.flags & MKP_RF_CIGW) ? 0ull : 2ull * h.n_cigar);   // (16-bit CIGAR: 2 of the 4 bytes per op)
           looked_up += 16ull * std::min<uint64_t>(MKP_PLANE_WORDS(h.l_seq), h.n_sl);
         }
         fused_swept += swept; fused_looked_up += looked_up;
@@ -810,8 +813,8 @@ void make_resident(mkp_ctx* c) {
     uint64_t n_rs = 0; for (auto& h : S.hdr) n_rs += h.n_sl;
     c->stats.stream_bytes = n_rs;
     c->stats.alg_bytes_decode += 4ull * n_rs + n_rs + 32ull * S.hdr.size();
-    // the fused decoder reads neither a read's whole SEQ nor its rank list: the 16-byte plane entry under each slot, and the SEQ byte
-    // only for a read with a base that is not A/C/G/T (the plane, resolved from SEQ and ranks once per resident shard, is not part of
+    // the fused decoder reads neither a read's whole SEQ nor its rank list, and 2 bytes per CIGAR op (4 of a read with an op longer than
+    // 4 095 bases): the 16-byte plane entry under each slot, and the SEQ byte only for a read with a base that is not A/C/G/T (the plane, resolved from SEQ and ranks once per resident shard, is not part of
     // the pass)
     unsigned long long seqn_bytes = 0;
     hip_check(hipMemcpyAsync(&seqn_bytes, d_seqn_bytes, sizeof(seqn_bytes), hipMemcpyDeviceToHost, c->stream), "plane counter readback");
@@ -879,7 +882,7 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
                                                        c->d_dupcons.as<MkpDupCons>(), c->d_dupsegs.as<MkpDupSeg>(), c->n_dup_cons, misc + 2),
                                                            "dup events launch");
     if (c->slot_mode) hip_check(mkp_launch_slots(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], c->d_plane.p,
-        c->d_hdr.as<MkpReadHdr>(),
+        c->d_cigar16.as<uint16_t>(), c->d_hdr.as<MkpReadHdr>(),
         c->d_slot_ids.as<uint32_t>(), c->n_slot_class[2],
                                               c->d_cigar.as<uint32_t>(), c->d_seq.as<uint8_t>(), c->d_tagref.as<MkpTagRef>(),
                                               c->d_ranks.as<uint32_t>(), c->d_ml.as<uint8_t>(), c->d_layouts.as<MkpLayout>(),
@@ -1076,7 +1079,7 @@ int mkp_ctx_create(const mkp_config* cfg, mkp_ctx** out) {
 void mkp_ctx_destroy(mkp_ctx* c) {
   if (!c) return;
   (void)hipSetDevice(c->device);
-  for (DevBuf* b : {&c->d_vals, &c->d_hdr, &c->d_cigar, &c->d_seq, &c->d_tagref, &c->d_ranks, &c->d_ml, &c->d_layouts, &c->d_events, &c->d_readout,
+  for (DevBuf* b : {&c->d_vals, &c->d_hdr, &c->d_cigar, &c->d_cigar16, &c->d_seq, &c->d_tagref, &c->d_ranks, &c->d_ml, &c->d_layouts, &c->d_events, &c->d_readout,
       &c->d_focus, &c->d_combos, &c->d_tiles,
                     &c->d_slotbm, &c->d_prm, &c->d_read_ids, &c->d_chunk, &c->d_store, &c->d_hist0, &c->d_hist1, &c->d_sample_cursor, &c->d_take,
                         &c->d_tile_row_off, &c->d_tile_row_cnt, &c->d_tile_dst, &c->d_misc, &c->d_rows_src, &c->d_rows_dst, &c->d_hemi_iv,
@@ -1229,11 +1232,11 @@ int mkp_internal_sample_bind(mkp_ctx* c, DevShard* sh) {
   return guarded(c, [&]() {
     if (!sh->bound) adopt_layouts(c, sh);
     std::swap(c->shard, sh->S);
-    std::swap(c->d_cigar, sh->d_cigar); std::swap(c->d_chunk, sh->d_chunk); std::swap(c->d_seq, sh->d_seq); std::swap(c->d_tagref, sh->d_tagref);
+    std::swap(c->d_cigar, sh->d_cigar); std::swap(c->d_cigar16, sh->d_cigar16); std::swap(c->d_chunk, sh->d_chunk); std::swap(c->d_seq, sh->d_seq); std::swap(c->d_tagref, sh->d_tagref);
       std::swap(c->d_ranks, sh->d_ranks); std::swap(c->d_ml, sh->d_ml);
     sh->bound = !sh->bound;
     c->shard_open = sh->bound; c->resident = false; c->wplan.valid = false;
-    if (sh->bound) for (DevBuf* b : {&c->d_cigar, &c->d_chunk, &c->d_seq, &c->d_tagref, &c->d_ranks, &c->d_ml}) b->ensure(16);
+    if (sh->bound) for (DevBuf* b : {&c->d_cigar, &c->d_cigar16, &c->d_chunk, &c->d_seq, &c->d_tagref, &c->d_ranks, &c->d_ml}) b->ensure(16);
   });
 }
 // Device ingest hand-over (mkp_ingest_host.cpp): the open shard takes the records the device packed.  Their big arrays are swapped into
@@ -1250,11 +1253,11 @@ int mkp_internal_shard_attach(mkp_ctx* c, DevShard* sh) {
     adopt_layouts(c, sh);
     const int32_t tid = c->shard.tid, ws = c->shard.win_start, we = c->shard.win_end;
     c->shard = std::move(sh->S); c->shard.tid = tid; c->shard.win_start = ws; c->shard.win_end = we; c->shard.dev_packed = true;
-    std::swap(c->d_cigar, sh->d_cigar); std::swap(c->d_chunk, sh->d_chunk); std::swap(c->d_seq, sh->d_seq); std::swap(c->d_tagref, sh->d_tagref);
+    std::swap(c->d_cigar, sh->d_cigar); std::swap(c->d_cigar16, sh->d_cigar16); std::swap(c->d_chunk, sh->d_chunk); std::swap(c->d_seq, sh->d_seq); std::swap(c->d_tagref, sh->d_tagref);
       std::swap(c->d_ranks, sh->d_ranks);
         std::swap(c->d_ml, sh->d_ml);
     // (an empty shard: the kernels still take valid pointers)
-    for (DevBuf* b : {&c->d_cigar, &c->d_chunk, &c->d_seq, &c->d_tagref, &c->d_ranks, &c->d_ml}) b->ensure(16);
+    for (DevBuf* b : {&c->d_cigar, &c->d_cigar16, &c->d_chunk, &c->d_seq, &c->d_tagref, &c->d_ranks, &c->d_ml}) b->ensure(16);
     c->resident = false; c->row_cap = 0;
     c->stats.pack_ms += ms_since(t0);
   });
@@ -1395,6 +1398,14 @@ uint32_t mkp_abi_version(void) { return MKP_ABI_VERSION; }
 size_t mkp_run_report_size(void) { return sizeof(mkp_run_report); }
 
 int mkp_get_stats(const mkp_ctx* c, mkp_stats* out) { if (!c || !out) return MKP_E_INVALID; *out = c->stats; return MKP_OK; }
+int mkp_shard_read_flags(const mkp_ctx* c, uint32_t* flags, uint32_t cap, uint32_t* n_reads) {
+  if (!c || !n_reads || (cap && !flags)) return MKP_E_INVALID;
+  const auto& hdr = c->shard.hdr;
+  *n_reads = (uint32_t)hdr.size();
+  for (size_t i = 0; i < hdr.size() && i < cap; i++) { const uint32_t f = hdr[i].flags;   // (the public bits are named, not the internal ones passed on)
+    flags[i] = ((f & MKP_RF_REVERSE) ? MKP_READ_REVERSE : 0u) | ((f & MKP_RF_BAD) ? MKP_READ_TAG_ERROR : 0u) | ((f & MKP_RF_CIGW) ? MKP_READ_WIDE_CIGAR : 0u); }
+  return MKP_OK;
+}
 
 int mkp_percentile(const float* xs, uint64_t n, float q, float* out) {  // percentile_linear_interp (thresholds.rs:17-38)
   if (!xs || !out || n < 2 || !(q >= 0.0f) || q > 1.0f) return MKP_E_THRESHOLD;

@@ -141,7 +141,7 @@ struct mkp_ctx {
   MkpRunParams prm; uint32_t lds_bytes = 0, n_tiles = 0; uint64_t row_cap = 0, n_slots_total = 0;
   // the resident shard runs the _wide accumulate kernels (a column may hold more than 65 535 records: u32 tallies per strand)
   bool wide = false;
-  mkp::DevBuf d_hdr, d_vals, d_cigar, d_seq, d_tagref, d_ranks, d_ml, d_layouts, d_events, d_readout, d_focus, d_combos, d_tiles, d_slotbm,
+  mkp::DevBuf d_hdr, d_vals, d_cigar, d_cigar16, d_seq, d_tagref, d_ranks, d_ml, d_layouts, d_events, d_readout, d_focus, d_combos, d_tiles, d_slotbm,
       d_tile_row_off, d_tile_row_cnt, d_tile_dst, d_misc, d_rows_src, d_rows_dst, d_prm, d_read_ids, d_chunk;
   uint32_t n_class[7] = {0, 0, 0, 0, 0, 0, 0};   // reads per decode kernel class (class_ids) launched through mkp_launch_decode
   // slot pipeline (focus runs, mkp_slots.hip): slot positions, feature stream, per-read visit records, stream tiles;

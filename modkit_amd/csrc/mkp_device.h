@@ -2,6 +2,8 @@
 // Data layout in HBM for one shard (a reference window of one contig):
 //   MkpReadHdr  hdr[n_reads]        64 B each, coordinate order
 //   uint32      cigar[]             BAM cigar words (len<<4|op)
+//   uint16      cigar16[]           the same ops in 16 bits (len<<4|op, len <= 4095: mkp_cigar_pack.hpp), each read at an offset of its own
+//                                   that is a multiple of four entries; what mkp_decode_slots reads of a read without MKP_RF_CIGW
 //   uint2       chunk_pfx[]         per read, per 64 CIGAR ops: query / reference offsets at the chunk start (the host walks the
 //                                   CIGAR anyway to get the read's reference span), so a tile starts its walk at the right chunk
 //   uint8       seq[]               BAM 4-bit packed bases, each read 4-byte aligned
@@ -44,20 +46,23 @@ struct MkpReadHdr {
   uint32_t tag_off;     // index into tagref[]
   uint16_t n_tags;
   uint16_t layout;
-  uint32_t flags;       // bit0 reverse; bit1 host-detected tag error (coverage-only read); bit2 MKP_RF_SUMERR; bits 8.. partition key id (0 = ungrouped)
+  uint32_t flags;       // bit0 reverse; bit1 host-detected tag error (coverage-only read); bit2 MKP_RF_SUMERR; bit5 MKP_RF_CIGW; bits 8.. partition key id (0 = ungrouped)
   uint32_t event_off;   // index into events[]
   uint32_t event_cap;
   uint32_t chunk_off;   // index into chunk_pfx[]: one {query offset, reference offset} per 64 CIGAR ops of this read
   // focus runs (slot pipeline, mkp_slots.hip): the read's focus positions ("slots") are the global slots [gs0, gs0 + n_sl) of
   // slot_pos[]; its features go to cov[cov_off .. cov_off + n_sl) (4-byte aligned).  Filled by the host planner (make_resident).
   uint32_t gs0, n_sl, cov_off;
-  uint32_t pad;
+  // index into cigar16[] (a multiple of 4; straight from the device ingest, bit 0 carries the probability-sum test until the host moves it
+  // into dev_sum2).  `pad` is the field's name from before it had a use: the ingest test harness still reads it under that name.
+  union { uint32_t cigar16_off; uint32_t pad; };
 };
 #define MKP_RF_REVERSE 1u
 #define MKP_RF_BAD 2u
 #define MKP_RF_SUMERR 4u   // host planner: some call's probabilities over the read's two tags add up to more than 1.01 (combine_checked, mod_bam.rs:629-656)
 #define MKP_RF_RUNOVER 8u  // mkp_call_plane (work records only): the delta list runs past the last occurrence of its base (mod_bam.rs:705-727)
 #define MKP_RF_SEQN 16u    // mkp_call_plane (work records only): the stored read holds a base that is not A/C/G/T (the decoder reads its SEQ)
+#define MKP_RF_CIGW 32u    // both packers: some CIGAR op is longer than 4 095 bases (MKP_CIGAR16_MAX_LEN): the slot decoder reads the read's 32-bit CIGAR
 #define MKP_RF_KEY_SHIFT 8
 #define MKP_NO_KEY_FILTER 0xffffffffu
 
@@ -239,6 +244,7 @@ static_assert(sizeof(MkpFusedDesc) == 64, "MkpFusedDesc is one 64-byte scalar lo
 // one read as mkp_decode_slots* takes it: the header and tag fields the kernel needs, in launch order (longest reads first), so that a
 // wave starts from ONE 64-byte scalar load instead of the chain read id -> header -> tag table
 struct MkpWork {             // 64 B
+  // cigar_off: index into cigar16[] (the header's cigar16_off), into cigar[] for a read with MKP_RF_CIGW
   int32_t ref_start; uint32_t l_seq, n_cigar, cigar_off, seq_off, flags, gs0, n_sl, cov_off;
   uint16_t n_tags, layout;
   uint32_t rank_off, n_calls, ml_off0, ml_off1;   // the shared rank list, the tags' ML bytes

@@ -920,9 +920,10 @@ class AheadIngest {
   size_t size() const { return list.size(); }
 
   // packed arrays of a shard ~ 1.9 x its compressed blocks on ONT-like data (SEQ nibbles + CIGAR words + 5 bytes per call; names and
-  // qualities are not kept), the inflated window of the ingest object in flight on top: 2.5 x; and once the shard is resident, the slot
-  // decoder's base-and-call plane (four bits per stored base = as many bytes as the SEQ nibbles, ~1 x): 3.5 x as the estimate
-  static uint64_t est_of(uint64_t comp_bytes) { return comp_bytes * 7 / 2 + (64ull << 20); }
+  // qualities are not kept), the inflated window of the ingest object in flight on top: 2.5 x; once the shard is resident, the slot
+  // decoder's base-and-call plane (four bits per stored base = as many bytes as the SEQ nibbles, ~1 x): 3.5 x; and the 16-bit CIGAR next
+  // to the 32-bit one (half the CIGAR words' bytes, ~0.25 x): 3.75 x as the estimate
+  static uint64_t est_of(uint64_t comp_bytes) { return comp_bytes * 15 / 4 + (64ull << 20); }
 
   // every target record as one shard, its records grouped by contig under --include-bed; nothing when one of them does not fit a shard
   // (a contig larger than a shard: the shards are cut on the grid and ingested ahead once the plan is known, from_plan)
@@ -1356,7 +1357,7 @@ void plan_only_shard(const Args& a, const Contig& rec, uint32_t s0, uint32_t s1,
   uint64_t dg = 1469598103934665603ull;
   auto mix = [&](const void* p, size_t n) { const uint8_t* b = (const uint8_t*)p; for (size_t i = 0; i < n; i++) { dg ^= b[i];
       dg *= 1099511628211ull; } };
-  mix(S.hdr.data(), S.hdr.size() * sizeof(MkpReadHdr)); mix(S.cigar.data(), S.cigar.size() * 4);
+  mix(S.hdr.data(), S.hdr.size() * sizeof(MkpReadHdr)); mix(S.cigar.data(), S.cigar.size() * 4); mix(S.cigar16.data(), S.cigar16.size() * 2);
     mix(S.chunk_pfx.data(), S.chunk_pfx.size() * 4);
       mix(S.seq.data(), S.seq.size());
   mix(S.tagref.data(), S.tagref.size() * sizeof(MkpTagRef)); mix(S.ranks.data(), S.ranks.size() * 4); mix(S.ml.data(), S.ml.size());

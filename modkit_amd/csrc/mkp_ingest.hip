@@ -213,8 +213,8 @@ mkp_ingest_write(const uint8_t* __restrict__ raw, MkpIngestParams P, const MkpSe
   ingest_walk_segment(raw, P.raw_len, segs[i], rec_off + seg_base[i], &tot->err);
 }
 
-// per record: checks, region test, aux walk; sizes of the packed ones into sz[6][rec_cap] (kept, CIGAR words, chunk pairs, SEQ bytes, ML bytes,
-// sampler-only)
+// per record: checks, region test, aux walk; sizes of the packed ones into sz[7][rec_cap] (kept, CIGAR words, chunk pairs, SEQ bytes, ML bytes,
+// sampler-only, 16-bit CIGAR entries)
 extern "C" __global__ void __launch_bounds__(256)
 mkp_ingest_parse(const uint8_t* __restrict__ raw, MkpIngestParams P, const int32_t* __restrict__ parts,
     const unsigned long long* __restrict__ rec_off, MkpRecInfo* __restrict__ info,
@@ -230,13 +230,14 @@ mkp_ingest_parse(const uint8_t* __restrict__ raw, MkpIngestParams P, const int32
     sz[3 * (size_t)P.rec_cap + i] = pk ? ingest_seq_bytes(R.l_seq) : 0u;
     sz[4 * (size_t)P.rec_cap + i] = pk ? R.ml_n : 0u;
     sz[5 * (size_t)P.rec_cap + i] = R.kind == 3 ? 1u : 0u;
+    sz[6 * (size_t)P.rec_cap + i] = pk ? mkp_cigar16_room(ingest_cigar_words(R.n_cigar)) : 0u;
     if (R.kind == 2) { const uint32_t at = atomicAdd(&tot->n_extra, 1u); extra[2 * (size_t)at] = R.pos;
       const long long e = (long long)R.pos + (R.reflen > 0 ? R.reflen : 1);
         extra[2 * (size_t)at + 1] = (int32_t)(e > 0x7fffffffll ? 0x7fffffffll : e); }
   }
 }
 
-// exclusive scans of the six size arrays in place, one workgroup per array; totals into tot
+// exclusive scans of the seven size arrays in place, one workgroup per array; totals into tot
 extern "C" __global__ void __launch_bounds__(1024)
 mkp_ingest_scan_sizes(uint32_t* __restrict__ sz, uint32_t rec_cap, MkpIngestTotals* tot) {
   const uint32_t n = min(tot->n_all, rec_cap), q = blockIdx.x;
@@ -246,7 +247,8 @@ mkp_ingest_scan_sizes(uint32_t* __restrict__ sz, uint32_t rec_cap, MkpIngestTota
     if (q == 0) tot->n_kept = (uint32_t)total; else if (q == 1) tot->cigar_words = total; else if (q == 2) tot->chunk_pairs = total;
       else if (q == 3) tot->seq_bytes = total;
       else if (q == 4) tot->ml_bytes = total;
-      else tot->n_sample_only = (uint32_t)total;
+      else if (q == 5) tot->n_sample_only = (uint32_t)total;
+      else tot->cigar16_entries = total;
   }
 }
 
@@ -262,20 +264,22 @@ mkp_ingest_pack(const uint8_t* __restrict__ raw, uint32_t rec_cap, const MkpRecI
     // headers: the kept records in file order, then the sampler-only ones
     const uint32_t j = R.kind == 1 ? sz[i] : tot->n_kept + sz[5 * (size_t)rec_cap + i];
     ingest_pack_record(raw, R, i, j, sz[(size_t)rec_cap + i], sz[2 * (size_t)rec_cap + i], sz[3 * (size_t)rec_cap + i], sz[4 * (size_t)rec_cap + i],
-                       hdr, chunk_pfx, tagref, ranks, dig, tot);
+                       hdr, chunk_pfx, tagref, ranks, dig, tot, sz[6 * (size_t)rec_cap + i]);
   }
 }
 
-// the bulk half, one wave per record: CIGAR words, SEQ and ML bytes, a dword per lane and step (round 4 moved them byte by byte inside
+// the bulk half, one wave per record: CIGAR words (32-bit and 16-bit), SEQ and ML bytes, a dword per lane and step (round 4 moved them byte by byte inside
 // the thread above: the longest read's 25 000 SEQ bytes were the kernel's 10 ms)
 extern "C" __global__ void __launch_bounds__(256)
 mkp_ingest_copy(const uint8_t* __restrict__ raw, uint32_t rec_cap, const MkpRecInfo* __restrict__ info, const uint32_t* __restrict__ sz,
-                uint32_t* __restrict__ cigar, uint8_t* __restrict__ seq, uint8_t* __restrict__ ml, const MkpIngestTotals* tot) {
+                uint32_t* __restrict__ cigar, uint16_t* __restrict__ cigar16, uint8_t* __restrict__ seq, uint8_t* __restrict__ ml,
+                const MkpIngestTotals* tot) {
   const uint32_t n = min(tot->n_all, rec_cap), lane = threadIdx.x & 63u, waves = gridDim.x * (blockDim.x >> 6);
   for (uint32_t i = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); i < n; i += waves) {
     const MkpRecInfo R = info[i];
     if (R.kind != 1 && R.kind != 3) continue;
-    ingest_copy_record(raw, R, sz[(size_t)rec_cap + i], sz[3 * (size_t)rec_cap + i], sz[4 * (size_t)rec_cap + i], cigar, seq, ml, lane, 64u);
+    ingest_copy_record(raw, R, sz[(size_t)rec_cap + i], sz[3 * (size_t)rec_cap + i], sz[4 * (size_t)rec_cap + i], cigar, seq, ml, lane, 64u,
+                       cigar16, sz[6 * (size_t)rec_cap + i]);
   }
 }
 
@@ -322,17 +326,17 @@ hipError_t mkp_launch_ingest_parse(hipStream_t st, const uint8_t* raw, const Mkp
   if (P->n_seg) hipLaunchKernelGGL(mkp_ingest_write, dim3((P->n_seg + 255u) / 256u), dim3(256), 0, st, raw, *P, segs, seg_base, rec_off, tot);
   const uint32_t grid = P->rec_cap ? (uint32_t)((P->rec_cap + 255u) / 256u < 8192u ? (P->rec_cap + 255u) / 256u : 8192u) : 1u;
   hipLaunchKernelGGL(mkp_ingest_parse, dim3(grid), dim3(256), 0, st, raw, *P, parts, rec_off, info, sz, extra, tot);
-  hipLaunchKernelGGL(mkp_ingest_scan_sizes, dim3(6), dim3(1024), 0, st, sz, P->rec_cap, tot);
+  hipLaunchKernelGGL(mkp_ingest_scan_sizes, dim3(7), dim3(1024), 0, st, sz, P->rec_cap, tot);
   return hipGetLastError();
 }
 hipError_t mkp_launch_ingest_pack(hipStream_t st, const uint8_t* raw, uint32_t rec_cap, const MkpRecInfo* info, const uint32_t* sz, MkpReadHdr* hdr,
-    uint32_t* cigar,
+    uint32_t* cigar, uint16_t* cigar16,
                                   uint32_t* chunk_pfx, uint8_t* seq, MkpTagRef* tagref, uint32_t* ranks, uint8_t* ml, MkpRecDigest* dig,
                                       MkpIngestTotals* tot) {
   const uint32_t grid = rec_cap ? (uint32_t)((rec_cap + 255u) / 256u < 8192u ? (rec_cap + 255u) / 256u : 8192u) : 1u;
   hipLaunchKernelGGL(mkp_ingest_pack, dim3(grid), dim3(256), 0, st, raw, rec_cap, info, sz, hdr, chunk_pfx, tagref, ranks, dig, tot);
   const uint32_t cgrid = rec_cap ? (uint32_t)((rec_cap + 3u) / 4u < 16384u ? (rec_cap + 3u) / 4u : 16384u) : 1u;
-  hipLaunchKernelGGL(mkp_ingest_copy, dim3(cgrid), dim3(256), 0, st, raw, rec_cap, info, sz, cigar, seq, ml, tot);
+  hipLaunchKernelGGL(mkp_ingest_copy, dim3(cgrid), dim3(256), 0, st, raw, rec_cap, info, sz, cigar, cigar16, seq, ml, tot);
   return hipGetLastError();
 }
 }

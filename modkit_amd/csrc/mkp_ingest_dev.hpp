@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "mkp_device.h"
+#include "mkp_cigar_pack.hpp"
 
 #ifdef MKP_INGEST_HOST_SHIM
 #define MKP_IDEV static inline
@@ -67,6 +68,7 @@ struct MkpIngestTotals {
   unsigned long long cigar_words, chunk_pairs, seq_bytes, ml_bytes;   // capacities of the packed arrays (exclusive-scan totals)
   unsigned long long n_calls, n_ml_used;
   uint32_t n_sample_only, pad;   // records of the region only the threshold sampler takes (QC-fail, no CIGAR): packed behind the kept ones
+  unsigned long long cigar16_entries;   // capacity of the 16-bit CIGAR array (mkp_cigar16_room per packed record)
 };
 
 // ---- CRC-32 joins (mkp_crc32_blocks): GF(2) polynomial arithmetic mod the gzip polynomial, bit-reflected operands (bit 31 = x^0)
@@ -342,15 +344,18 @@ struct MkpRecDigest { unsigned long long name_hash, key_hash, name_hash2, win_id
 // the offsets the scan gave.  The bulk copies are ingest_copy_record's.
 MKP_IDEV void ingest_pack_record(const uint8_t* raw, const MkpRecInfo& R, uint32_t win_idx, uint32_t j, uint32_t cigar_off, uint32_t chunk_off,
     uint32_t seq_off, uint32_t ml_off,
-                                 MkpReadHdr* hdr, uint32_t* chunk_pfx, MkpTagRef* tagref, uint32_t* ranks, MkpRecDigest* dig, MkpIngestTotals* tot) {
+                                 MkpReadHdr* hdr, uint32_t* chunk_pfx, MkpTagRef* tagref, uint32_t* ranks, MkpRecDigest* dig, MkpIngestTotals* tot,
+                                 uint32_t cigar16_off = 0) {
   const uint8_t* c = raw + R.core;
   const uint8_t* cg = c + 32 + R.l_qname;
   MkpReadHdr h;
   h.cigar_off = cigar_off; h.chunk_off = chunk_off; h.seq_off = seq_off; h.tag_off = j * MKP_MAX_TAGS;
   long long reflen = 0, qlen = 0;
+  bool wide = R.n_cigar == 0 && !mkp_cigar16_fits(R.l_seq << 4);   // (the one soft clip of a record without a CIGAR)
   for (uint32_t k = 0; k < R.n_cigar; k++) {
     const uint32_t w = ld_u32(cg + 4 * k), op = w & 15u;
     if ((k & 63u) == 0) { chunk_pfx[2 * (chunk_off + (k >> 6))] = (uint32_t)qlen; chunk_pfx[2 * (chunk_off + (k >> 6)) + 1] = (uint32_t)reflen; }
+    wide = wide || !mkp_cigar16_fits(w);
     if ((0x18du >> op) & 1u) reflen += w >> 4;
     if ((0x193u >> op) & 1u) qlen += w >> 4;   // M I S = X consume the query
   }
@@ -359,7 +364,7 @@ MKP_IDEV void ingest_pack_record(const uint8_t* raw, const MkpRecInfo& R, uint32
   if (qlen != (long long)R.l_seq) MKP_ATOMIC_OR(&tot->err, MKP_IE_QLEN);
   if (qlen >= (1 << 26) || reflen >= (1 << 26)) MKP_ATOMIC_OR(&tot->err, MKP_IE_SPAN);
   h.ref_start = R.pos; h.ref_end = R.pos + (int32_t)reflen; h.l_seq = R.l_seq; h.n_cigar = ingest_cigar_words(R.n_cigar);
-  h.flags = (R.flag & 16u) ? MKP_RF_REVERSE : 0u;
+  h.flags = ((R.flag & 16u) ? MKP_RF_REVERSE : 0u) | (wide ? MKP_RF_CIGW : 0u);
   { unsigned long long hh = 1469598103934665603ull, h2 = 0x9e3779b97f4a7c15ull; for (int i = 0; i + 1 < (int)R.l_qname; i++) { hh ^= c[32 + i];
       hh *= 1099511628211ull; h2 = (h2 ^ c[32 + i]) * 0xff51afd7ed558ccdull; h2 ^= h2 >> 29; }
     dig[j].name_hash = hh; dig[j].name_hash2 = h2; dig[j].win_idx = win_idx; }
@@ -370,25 +375,36 @@ MKP_IDEV void ingest_pack_record(const uint8_t* raw, const MkpRecInfo& R, uint32
   if (t.cap > 0xfffffff0ull) { MKP_ATOMIC_OR(&tot->err, MKP_IE_4G); t.cap = 0; }
   h.n_tags = (uint16_t)t.n_tags; h.layout = 0;
   h.event_off = 0; h.event_cap = (uint32_t)t.cap;
-  // pad: bit 0 = the two tags' probabilities of some call add up to more than 1.01 (the planner moves it into flags)
-  h.gs0 = 0; h.n_sl = 0; h.cov_off = 0; h.pad = t.sum2;
+  // cigar16_off: the read's place in cigar16[] (a multiple of 4) and, in bit 0: the two tags' probabilities of some call add up to more than 1.01 (the planner moves it into flags)
+  h.gs0 = 0; h.n_sl = 0; h.cov_off = 0; h.cigar16_off = cigar16_off | (t.sum2 & 1u);
   dig[j].key_hash = t.key_hash;
   hdr[j] = h;
   if (t.n_calls) MKP_ATOMIC_ADD64(&tot->n_calls, (unsigned long long)t.n_calls);
   if (t.ml_used) MKP_ATOMIC_ADD64(&tot->n_ml_used, (unsigned long long)t.ml_used);
 }
 
-// Packer::add for one kept record, the bulk half: CIGAR words, SEQ bytes (zero-padded to a dword), the ML array — by `nlanes` lanes that
-// share the record (a wave on the device; the test harness calls it lane after lane).  No lane reads what another wrote.  The whole B:C
-// array is moved (the record's slice has room for it; the tags only ever point at the bytes their calls use).
+// Packer::add for one kept record, the bulk half: CIGAR words (and, into cigar16 when given, their 16-bit form: mkp_cigar_pack.hpp), SEQ
+// bytes (zero-padded to a dword), the ML array — by `nlanes` lanes that share the record (a wave on the device; the test harness calls it
+// lane after lane).  No lane reads what another wrote.  The whole B:C array is moved (the record's slice has room for it; the tags only
+// ever point at the bytes their calls use).
 MKP_IDEV void ingest_copy_record(const uint8_t* raw, const MkpRecInfo& R, uint32_t cigar_off, uint32_t seq_off, uint32_t ml_off, uint32_t* cigar,
     uint8_t* seq, uint8_t* ml,
-                                 uint32_t lane, uint32_t nlanes) {
+                                 uint32_t lane, uint32_t nlanes, uint16_t* cigar16 = nullptr, uint32_t cigar16_off = 0) {
   const uint8_t* c = raw + R.core;
   const uint8_t* cg = c + 32 + R.l_qname;
   const uint8_t* sq = cg + 4 * (uint32_t)R.n_cigar;
-  for (uint32_t k = lane; k < R.n_cigar; k += nlanes) cigar[cigar_off + k] = ld_u32(cg + 4 * k);
-  if (R.n_cigar == 0 && lane == 0) cigar[cigar_off] = (R.l_seq << 4) | 4u;   // one soft clip over the bases, as Packer::add does
+  // two ops per lane and step: the pair's 16-bit forms leave as one dword (cigar16_off is a multiple of 4: the pairs are dword aligned)
+  const uint32_t n_pairs = (uint32_t)R.n_cigar >> 1;
+  for (uint32_t k = lane; k < n_pairs; k += nlanes) {
+    const uint32_t w0 = ld_u32(cg + 8 * k), w1 = ld_u32(cg + 8 * k + 4);
+    cigar[cigar_off + 2 * k] = w0; cigar[cigar_off + 2 * k + 1] = w1;
+    if (cigar16) { const uint32_t e = (uint32_t)mkp_cigar16_pack(w0) | ((uint32_t)mkp_cigar16_pack(w1) << 16);
+      __builtin_memcpy(cigar16 + cigar16_off + 2 * k, &e, 4); }
+  }
+  if ((R.n_cigar & 1u) && lane == 0) { const uint32_t k = R.n_cigar - 1u, w = ld_u32(cg + 4 * k); cigar[cigar_off + k] = w;
+    if (cigar16) cigar16[cigar16_off + k] = mkp_cigar16_pack(w); }
+  if (R.n_cigar == 0 && lane == 0) { const uint32_t w = (R.l_seq << 4) | 4u;   // one soft clip over the bases, as Packer::add does
+    cigar[cigar_off] = w; if (cigar16) cigar16[cigar16_off] = mkp_cigar16_pack(w); }
   const uint32_t nb = (R.l_seq + 1u) / 2u, nd = ingest_seq_bytes(R.l_seq) / 4u;
   uint32_t* sd = (uint32_t*)(seq + seq_off);   // (seq_off is a multiple of 4: every record's room is)
   for (uint32_t k = lane; k < nd; k += nlanes) {

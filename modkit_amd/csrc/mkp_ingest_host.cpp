@@ -24,10 +24,11 @@ hipError_t mkp_launch_bgzf_layout(hipStream_t, const MkpZBlk*, uint32_t, unsigne
 hipError_t mkp_launch_ingest_count(hipStream_t, const uint8_t*, const MkpIngestParams*, const MkpSeg*, uint32_t*, MkpIngestTotals*);
 hipError_t mkp_launch_ingest_parse(hipStream_t, const uint8_t*, const MkpIngestParams*, const int32_t*, const MkpSeg*, const uint32_t*,
     unsigned long long*, MkpRecInfo*, uint32_t*, int32_t*, MkpIngestTotals*);
-hipError_t mkp_launch_ingest_pack(hipStream_t, const uint8_t*, uint32_t, const MkpRecInfo*, const uint32_t*, MkpReadHdr*, uint32_t*, uint32_t*,
-    uint8_t*, MkpTagRef*, uint32_t*, uint8_t*, MkpRecDigest*, MkpIngestTotals*);
+hipError_t mkp_launch_ingest_pack(hipStream_t, const uint8_t*, uint32_t, const MkpRecInfo*, const uint32_t*, MkpReadHdr*, uint32_t*, uint16_t*,
+    uint32_t*, uint8_t*, MkpTagRef*, uint32_t*, uint8_t*, MkpRecDigest*, MkpIngestTotals*);
 }
 
+#define MKP_INGEST_SPARES 20
 namespace {
 struct Pinned {
   void* p = nullptr; size_t cap = 0;
@@ -64,7 +65,8 @@ struct mkp_dev_ingest {
   Pinned chain_host;
   DevBuf zin, zblk, zstat, raw, segs, seg_cnt, rec_off, info, sz, extra, tot, dig, parts;
   std::mutex mu;                                                   // one ingest at a time per object
-  std::mutex spare_mu; std::vector<DevBuf> spares;                 // buffers the contexts handed back (mkp_internal_ingest_recycle)
+  // buffers the contexts handed back (mkp_internal_ingest_recycle): room for the seven packed arrays and the header buffer of two shards, and four
+  std::mutex spare_mu; std::vector<DevBuf> spares;
   DevBuf take(size_t bytes) {
     DevBuf b;
     { std::lock_guard<std::mutex> g(spare_mu); size_t best = SIZE_MAX;
@@ -130,12 +132,12 @@ void mkp_internal_ingest_destroy(mkp_dev_ingest* d) {
   delete d;
 }
 
-DevShard::~DevShard() { for (DevBuf* b : {&d_cigar, &d_chunk, &d_seq, &d_tagref, &d_ranks, &d_ml}) b->release(); }
+DevShard::~DevShard() { for (DevBuf* b : {&d_cigar, &d_cigar16, &d_chunk, &d_seq, &d_tagref, &d_ranks, &d_ml}) b->release(); }
 
 void mkp_internal_ingest_recycle(mkp_dev_ingest* d, DevShard* sh) {
   if (!d || !sh) return;
   std::lock_guard<std::mutex> g(d->spare_mu);
-  for (DevBuf* b : {&sh->d_cigar, &sh->d_chunk, &sh->d_seq, &sh->d_tagref, &sh->d_ranks, &sh->d_ml}) { if (b->p && d->spares.size() < 16) {
+  for (DevBuf* b : {&sh->d_cigar, &sh->d_cigar16, &sh->d_chunk, &sh->d_seq, &sh->d_tagref, &sh->d_ranks, &sh->d_ml}) { if (b->p && d->spares.size() < MKP_INGEST_SPARES) {
       d->spares.push_back(*b); b->p = nullptr; b->cap = 0; } }
 }
 
@@ -483,7 +485,7 @@ std::unique_ptr<DevShard> mkp_internal_ingest_run(mkp_dev_ingest* d, const BamSo
   auto t_scan = std::chrono::steady_clock::now();
   const uint32_t n_all = tot->n_all;
   P.rec_cap = std::max<uint32_t>(n_all, 1u);
-  d->rec_off.ensure((size_t)P.rec_cap * 8); d->info.ensure((size_t)P.rec_cap * sizeof(MkpRecInfo)); d->sz.ensure(6 * (size_t)P.rec_cap * 4);
+  d->rec_off.ensure((size_t)P.rec_cap * 8); d->info.ensure((size_t)P.rec_cap * sizeof(MkpRecInfo)); d->sz.ensure(7 * (size_t)P.rec_cap * 4);
     d->extra.ensure(2 * (size_t)P.rec_cap * 4);
   const int32_t* d_parts = nullptr;
   if (parts.size() > 1) {   // the windows of a multi-part fetch, next to the params
@@ -501,17 +503,17 @@ std::unique_ptr<DevShard> mkp_internal_ingest_run(mkp_dev_ingest* d, const BamSo
   check(tot->err);
   const uint32_t n = tot->n_kept, n_so = tot->n_sample_only, n_pk = n + n_so;
   // ---- pack
-  out->d_cigar = d->take((tot->cigar_words + 16) * 4); out->d_chunk = d->take((tot->chunk_pairs + 4) * 8); out->d_seq = d->take(tot->seq_bytes + 64);
+  out->d_cigar = d->take((tot->cigar_words + 16) * 4); out->d_cigar16 = d->take((tot->cigar16_entries + 16) * 2); out->d_chunk = d->take((tot->chunk_pairs + 4) * 8); out->d_seq = d->take(tot->seq_bytes + 64);
   out->d_tagref = d->take(((size_t)n_pk * MKP_MAX_TAGS + 1) * sizeof(MkpTagRef)); out->d_ranks = d->take((tot->ml_bytes + 16) * 4);
     out->d_ml = d->take(tot->ml_bytes + 64);
   DevBuf d_hdr = d->take(((size_t)n_pk + 1) * sizeof(MkpReadHdr));
   struct Back { mkp_dev_ingest* d; DevBuf b; ~Back() { std::lock_guard<std::mutex> g(d->spare_mu); if (b.p) {
-        if (d->spares.size() < 16) d->spares.push_back(b);
+        if (d->spares.size() < MKP_INGEST_SPARES) d->spares.push_back(b);
         else b.release();
       } } } back{d, d_hdr};
   d->dig.ensure(((size_t)n_pk + 1) * sizeof(MkpRecDigest));
   ok(mkp_launch_ingest_pack(d->stream, d->raw.as<uint8_t>(), P.rec_cap, d->info.as<MkpRecInfo>(), d->sz.as<uint32_t>(), d_hdr.as<MkpReadHdr>(),
-      out->d_cigar.as<uint32_t>(), out->d_chunk.as<uint32_t>(),
+      out->d_cigar.as<uint32_t>(), out->d_cigar16.as<uint16_t>(), out->d_chunk.as<uint32_t>(),
                             out->d_seq.as<uint8_t>(), out->d_tagref.as<MkpTagRef>(), out->d_ranks.as<uint32_t>(), out->d_ml.as<uint8_t>(),
                                 d->dig.as<MkpRecDigest>(), d->tot.as<MkpIngestTotals>()), "pack launch");
   S.hdr.resize(n); S.so_hdr.resize(n_so); S.tagref.resize((size_t)n_pk * MKP_MAX_TAGS); S.name_hash.resize(n);
@@ -541,9 +543,9 @@ std::unique_ptr<DevShard> mkp_internal_ingest_run(mkp_dev_ingest* d, const BamSo
     const bool so = j >= n;
     MkpReadHdr& h = so ? S.so_hdr[j - n] : S.hdr[j];
     if (so) { S.so_name_hash[j - n] = dig[j].name_hash; S.so_name_hash2[j - n] = dig[j].name_hash2; S.so_win_idx[j - n] = (uint32_t)dig[j].win_idx;
-      h.pad = 0; }
+      h.cigar16_off &= ~3u; }
     else { S.name_hash[j] = dig[j].name_hash; S.dev_name_hash2[j] = dig[j].name_hash2; S.dev_win_idx[j] = (uint32_t)dig[j].win_idx;
-      S.dev_sum2[j] = (uint8_t)(h.pad & 1u); h.pad = 0; ev_cap += h.event_cap; }
+      S.dev_sum2[j] = (uint8_t)(h.cigar16_off & 1u); h.cigar16_off &= ~3u; ev_cap += h.event_cap; }
     if (!h.n_tags || (h.flags & MKP_RF_BAD)) continue;
     if (have_last && dig[j].key_hash == last_hash) { h.layout = last_id; continue; }   // (runs of one structure: most of a file)
     auto it = by_hash.find(dig[j].key_hash);

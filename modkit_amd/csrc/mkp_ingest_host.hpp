@@ -10,7 +10,7 @@ namespace mkp {
 struct DevShard {
   ShardHost S;                 // hdr, tagref (MKP_MAX_TAGS per read), name_hash, extra_spans, dev_sum2; dev_packed = true; hdr[i].layout indexes `layouts`
   Packer layouts;              // MM header structures of this shard, in order of first appearance
-  DevBuf d_cigar, d_chunk, d_seq, d_tagref, d_ranks, d_ml;
+  DevBuf d_cigar, d_cigar16, d_chunk, d_seq, d_tagref, d_ranks, d_ml;
   std::vector<MkpRecInfo> info_host;   // scratch of the layout interning
   bool layouts_adopted = false, bound = false;   // layout ids already mapped into a context's table; currently swapped into a context for sampling
   uint64_t n_blocks = 0, n_segments = 0, n_records = 0, raw_bytes = 0, comp_bytes = 0;

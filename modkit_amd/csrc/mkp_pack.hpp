@@ -15,6 +15,7 @@
 
 #include "mkp_bam.hpp"
 #include "mkp_device.h"
+#include "mkp_cigar_pack.hpp"
 
 namespace mkp {
 
@@ -225,7 +226,7 @@ template <class T> using PodVec = std::vector<T, DefaultInitAlloc<T>>;
 
 struct ShardHost {
   int32_t tid = -1; int32_t win_start = 0, win_end = 0;
-  PodVec<MkpReadHdr> hdr; PodVec<uint32_t> cigar; PodVec<uint32_t> chunk_pfx; PodVec<uint8_t> seq; PodVec<MkpTagRef> tagref;
+  PodVec<MkpReadHdr> hdr; PodVec<uint32_t> cigar; PodVec<uint16_t> cigar16 /* mkp_cigar_pack.hpp; a multiple of 4 entries */; PodVec<uint32_t> chunk_pfx; PodVec<uint8_t> seq; PodVec<MkpTagRef> tagref;
   PodVec<uint32_t> ranks; PodVec<uint8_t> ml;
   uint64_t n_events_cap = 0, n_calls = 0;
   PodVec<uint64_t> name_hash;  // for duplicate-qname detection (read cache is keyed by name, read_cache.rs:28-35)
@@ -243,31 +244,32 @@ struct ShardHost {
   // append shard pieces packed independently (parallel packing), in order: offsets are rebased, layout ids remapped.  Sizes
   // are fixed first, then every piece is copied into place by its own thread.
   void append_all(const std::vector<ShardHost>& ps, const std::vector<std::vector<uint16_t>>& layout_maps) {
-    struct Base { size_t hdr, cigar, chunk, seq, tag, rank, ml, name; uint64_t ev; };
+    struct Base { size_t hdr, cigar, chunk, seq, tag, rank, ml, name; uint64_t ev; size_t c16; };
     std::vector<Base> b(ps.size() + 1);
-    b[0] = {hdr.size(), cigar.size(), chunk_pfx.size(), seq.size(), tagref.size(), ranks.size(), ml.size(), name_hash.size(), n_events_cap};
+    b[0] = {hdr.size(), cigar.size(), chunk_pfx.size(), seq.size(), tagref.size(), ranks.size(), ml.size(), name_hash.size(), n_events_cap, cigar16.size()};
     uint64_t calls = n_calls;
     for (size_t i = 0; i < ps.size(); i++) {
       const ShardHost& o = ps[i];
       b[i + 1] = {b[i].hdr + o.hdr.size(), b[i].cigar + o.cigar.size(), b[i].chunk + o.chunk_pfx.size(), b[i].seq + o.seq.size(),
           b[i].tag + o.tagref.size(),
-                  b[i].rank + o.ranks.size(), b[i].ml + o.ml.size(), b[i].name + o.name_hash.size(), b[i].ev + o.n_events_cap};
+                  b[i].rank + o.ranks.size(), b[i].ml + o.ml.size(), b[i].name + o.name_hash.size(), b[i].ev + o.n_events_cap,
+                  b[i].c16 + o.cigar16.size()};
       calls += o.n_calls;
     }
     const Base& e = b[ps.size()];
-    if (e.seq > 0xfffffff0ull || e.cigar > 0xfffffff0ull || e.rank > 0xfffffff0ull || e.ml > 0xfffffff0ull) throw Error(MKP_E_UNSUPPORTED,
+    if (e.seq > 0xfffffff0ull || e.cigar > 0xfffffff0ull || e.c16 > 0xfffffff0ull || e.rank > 0xfffffff0ull || e.ml > 0xfffffff0ull) throw Error(MKP_E_UNSUPPORTED,
         "shard exceeds 4 GiB of packed bases; use smaller shards");
     if (e.ev > 0xfffffff0ull) throw Error(MKP_E_UNSUPPORTED, "shard exceeds 4 Gi call events; use smaller shards");
-    hdr.resize(e.hdr); cigar.resize(e.cigar); chunk_pfx.resize(e.chunk); seq.resize(e.seq); tagref.resize(e.tag); ranks.resize(e.rank);
+    hdr.resize(e.hdr); cigar.resize(e.cigar); cigar16.resize(e.c16); chunk_pfx.resize(e.chunk); seq.resize(e.seq); tagref.resize(e.tag); ranks.resize(e.rank);
       ml.resize(e.ml); name_hash.resize(e.name);
     auto place = [&](size_t i) {
       const ShardHost& o = ps[i]; const Base& at = b[i]; const std::vector<uint16_t>& lm = layout_maps[i];
       auto cp = [](auto& dst, size_t off, const auto& src) { if (!src.empty()) memcpy(dst.data() + off, src.data(), src.size() * sizeof(src[0])); };
-      cp(cigar, at.cigar, o.cigar); cp(chunk_pfx, at.chunk, o.chunk_pfx); cp(seq, at.seq, o.seq); cp(ranks, at.rank, o.ranks); cp(ml, at.ml, o.ml);
+      cp(cigar, at.cigar, o.cigar); cp(cigar16, at.c16, o.cigar16); cp(chunk_pfx, at.chunk, o.chunk_pfx); cp(seq, at.seq, o.seq); cp(ranks, at.rank, o.ranks); cp(ml, at.ml, o.ml);
         cp(name_hash, at.name, o.name_hash);
       for (size_t k = 0; k < o.hdr.size(); k++) {
         MkpReadHdr h = o.hdr[k];
-        h.cigar_off += (uint32_t)at.cigar; h.chunk_off += (uint32_t)(at.chunk / 2); h.seq_off += (uint32_t)at.seq; h.tag_off += (uint32_t)at.tag;
+        h.cigar_off += (uint32_t)at.cigar; h.cigar16_off += (uint32_t)at.c16; h.chunk_off += (uint32_t)(at.chunk / 2); h.seq_off += (uint32_t)at.seq; h.tag_off += (uint32_t)at.tag;
           h.event_off += (uint32_t)at.ev;
         if (h.n_tags) h.layout = lm[h.layout];
         hdr[at.hdr + k] = h;
@@ -278,7 +280,7 @@ struct ShardHost {
     HostPool::get().parallel(ps.size(), place);
     n_events_cap = e.ev; n_calls = calls;
   }
-  void clear() { hdr.clear(); cigar.clear(); chunk_pfx.clear(); seq.clear(); tagref.clear(); ranks.clear(); ml.clear(); n_events_cap = 0; n_calls = 0;
+  void clear() { hdr.clear(); cigar.clear(); cigar16.clear(); chunk_pfx.clear(); seq.clear(); tagref.clear(); ranks.clear(); ml.clear(); n_events_cap = 0; n_calls = 0;
     name_hash.clear(); extra_spans.clear();
                dev_packed = false; dev_sum2.clear(); dev_n_ranks = dev_n_ml = 0; dev_name_hash2.clear(); dev_win_idx.clear(); so_hdr.clear();
                  so_name_hash.clear(); so_name_hash2.clear(); so_win_idx.clear(); }
@@ -374,27 +376,31 @@ class Packer {
     if (aux > r.data + r.l_data) throw Error(MKP_E_INVALID, "record data shorter than its fields");
     size_t aux_n = (size_t)(r.data + r.l_data - aux);
     int64_t reflen = 0, qlen = 0;
-    h.cigar_off = (uint32_t)S.cigar.size();
+    h.cigar_off = (uint32_t)S.cigar.size(); h.cigar16_off = (uint32_t)S.cigar16.size();
     uint32_t n_cigar = r.n_cigar;
+    bool wide = false;   // some op does not fit the 16-bit form (MKP_RF_CIGW)
     // unaligned record (sampling only): one soft clip
-    if (n_cigar == 0) { S.cigar.push_back(((uint32_t)r.l_qseq << 4) | 4u); n_cigar = 1; qlen = r.l_qseq; }
+    if (n_cigar == 0) { const uint32_t w = ((uint32_t)r.l_qseq << 4) | 4u; S.cigar.push_back(w); S.cigar16.push_back(mkp_cigar16_pack(w));
+      wide = !mkp_cigar16_fits(w); n_cigar = 1; qlen = r.l_qseq; }
     h.chunk_off = (uint32_t)(S.chunk_pfx.size() / 2);
     if (r.n_cigar == 0) { S.chunk_pfx.push_back(0); S.chunk_pfx.push_back(0); }
     for (uint32_t k = 0; k < r.n_cigar; k++) { uint32_t w; memcpy(&w, cg + 4 * k, 4); S.cigar.push_back(w); uint32_t op = w & 15;
+      S.cigar16.push_back(mkp_cigar16_pack(w)); wide = wide || !mkp_cigar16_fits(w);
       if ((k & 63u) == 0) { S.chunk_pfx.push_back((uint32_t)qlen); S.chunk_pfx.push_back((uint32_t)reflen);
         } if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) reflen += w >> 4;
         if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) qlen += w >> 4;
         }
+    while (S.cigar16.size() & 3) S.cigar16.push_back(0);   // every read starts on a multiple of four entries: one aligned 8-byte load per lane
     if (qlen != r.l_qseq) throw Error(MKP_E_INVALID, "CIGAR query length does not match SEQ length");
     if (qlen >= (1 << 26) || reflen >= (1 << 26)) throw Error(MKP_E_UNSUPPORTED,
         "a read or its alignment spans 2^26 bases or more (the depth walk packs query offsets in 27 bits)");
     h.ref_start = r.pos; h.ref_end = r.pos + (int32_t)reflen; h.l_seq = (uint32_t)r.l_qseq; h.n_cigar = n_cigar;
-    if (S.seq.size() + (size_t)r.l_qseq / 2 + 8 > 0xfffffff0ull || S.cigar.size() > 0xfffffff0ull) throw Error(MKP_E_UNSUPPORTED,
+    if (S.seq.size() + (size_t)r.l_qseq / 2 + 8 > 0xfffffff0ull || S.cigar.size() > 0xfffffff0ull || S.cigar16.size() > 0xfffffff0ull) throw Error(MKP_E_UNSUPPORTED,
         "shard exceeds 4 GiB of packed bases; use smaller shards");
     h.seq_off = (uint32_t)S.seq.size();
     S.seq.insert(S.seq.end(), sq, sq + ((size_t)r.l_qseq + 1) / 2);
     while (S.seq.size() & 3) S.seq.push_back(0);
-    h.flags = (r.flag & 16) ? MKP_RF_REVERSE : 0;
+    h.flags = ((r.flag & 16) ? MKP_RF_REVERSE : 0) | (wide ? MKP_RF_CIGW : 0);
     h.tag_off = (uint32_t)S.tagref.size();
     h.event_off = (uint32_t)S.n_events_cap;
     { uint64_t hh = 1469598103934665603ull; for (int i = 0; i + 1 < r.l_qname; i++) { hh ^= r.data[i]; hh *= 1099511628211ull;
@@ -524,7 +530,7 @@ template <class Keep> void pack_records(Packer& packer, ShardHost& dst, const mk
     {   // room for the piece's bases and CIGARs up front (known from the record cores): no regrowth copies while packing
       size_t seq_b = 0, cig = 0;
       for (uint32_t i = lo; i < hi; i++) { seq_b += (((size_t)std::max(recs[i].l_qseq, 0) + 1) / 2 + 3) & ~(size_t)3; cig += recs[i].n_cigar; }
-      sh[t].seq.reserve(seq_b + 64); sh[t].cigar.reserve(cig + 64); sh[t].hdr.reserve(hi - lo); sh[t].name_hash.reserve(hi - lo);
+      sh[t].seq.reserve(seq_b + 64); sh[t].cigar.reserve(cig + 64); sh[t].cigar16.reserve(cig + 4 * (size_t)(hi - lo) + 64); sh[t].hdr.reserve(hi - lo); sh[t].name_hash.reserve(hi - lo);
     }
     try { for (uint32_t i = lo; i < hi; i++) if (keep(recs[i])) pk[t].add(recs[i], sh[t]); }
     catch (const Error& e) { errs[t].reset(new Error(e)); }

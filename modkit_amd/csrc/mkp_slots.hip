@@ -8,7 +8,8 @@
 //                         rank list resolved against each other: nothing of it depends on the pass)
 //   mkp_decode_slots      one wave per read, reads whose MM tags form one explicit-mode ('?') group with one shared delta list
 //                         (`C+m?`, `C+hm?`, `C+h?;C+m?` as basecallers write them), no edge filter.  The walk is driven by the
-//                         read's SLOTS, not by its calls, 64 slots per step: CIGAR (256-op register window, reference -> query), the
+//                         read's SLOTS, not by its calls, 64 slots per step: CIGAR (256-op register window, reference -> query; read from
+//                         the 16-bit array, 8 bytes per lane and window, unless an op of the read is longer than 4 095 bases), the
 //                         base, whether a call is listed there and as which call (one 16-byte plane gather; the SEQ byte only for a
 //                         read with a base that is not A/C/G/T),
 //                         ML -> f32 probabilities -> MultipleThresholdModCaller::call, and ONE FEATURE BYTE per slot goes to the
@@ -27,6 +28,7 @@
 #include <cstdlib>
 
 #include "mkp_base_pack.hpp"
+#include "mkp_cigar_pack.hpp"
 #include "mkp_dev_common.hpp"
 #include "mkp_dev_rows.hpp"
 
@@ -131,17 +133,43 @@ __device__ __forceinline__ void refwin_map(RefWin& w, const uint32_t* __restrict
 // no flag, no conditional advance — and the slot step maps its lanes in a pass of straight-line code, with the loop only behind it for
 // the steps that straddle windows (the one loop of refwin_map kept every window register twice and copied 14 of them per iteration).
 struct RefWinS { uint32_t c0, q_run, Rtot, Qtot; int32_t r_run; uint32_t re, m1, m2, m3, pk[4]; uint4 pref; };
-__device__ __forceinline__ void refwin_s_init(RefWinS& w, const uint32_t* __restrict__ cg, uint32_t n_cigar, int32_t ref_start) {
+// Their four ops per lane come from the read's 16-bit CIGAR (mkp_cigar_pack.hpp) as ONE 8-byte load — the read starts on a multiple of four
+// entries, and so does every lane; a read with an op that does not fit 16 bits (MKP_RF_CIGW: `wide`, uniform over the wave) takes the 16-byte
+// load of its 32-bit words instead.  cg = the read's first op in the array it is read from.  The address is clamped to the read's last quad
+// (inside its own room) / last op.  The branch is at the load only, and nothing touches the loaded registers before the window is opened
+// (the request stays one window ahead): cigar_quad_s_ops then widens the 16-bit ops back to BAM words — ops past the end read as 0H, as
+// cigar_quad's.
+typedef const __attribute__((address_space(1))) char* MkpCigarPtr;   // (a pointer into global memory, whichever of the two arrays it came from)
+__device__ __forceinline__ uint4 cigar_quad_s_load(MkpCigarPtr cg, bool wide, uint32_t n_cigar, uint32_t c) {
+  typedef uint32_t U2 __attribute__((ext_vector_type(2)));
+  typedef const __attribute__((address_space(1))) U2* P2;
+  const uint32_t k = c + 4u * (uint32_t)lane_id();
+  // the first eight bytes of either form are one load (the clamp and the entry size are scalars); the BAM words' other eight follow
+  const uint32_t off = min(k, wide ? n_cigar - 1u : (n_cigar - 1u) & ~3u) << (wide ? 2u : 1u);
+  const U2 lo = *reinterpret_cast<P2>(cg + off);
+  uint4 r; r.x = lo.x; r.y = lo.y;   // (.z, .w are read of a wide read only)
+  if (wide) { const U2 hi = *reinterpret_cast<P2>(cg + off + 8u); r.z = hi.x; r.w = hi.y; }
+  return r;
+}
+__device__ __forceinline__ uint4 cigar_quad_s_ops(uint4 r, bool wide, uint32_t n_cigar, uint32_t c) {
+  const uint32_t k = c + 4u * (uint32_t)lane_id();
+  if (!wide) r = make_uint4(mkp_cigar16_unpack(r.x), mkp_cigar16_unpack(r.x >> 16), mkp_cigar16_unpack(r.y), mkp_cigar16_unpack(r.y >> 16));
+  if (__any(k + 4u > n_cigar)) { if (k >= n_cigar) r.x = 5u; if (k + 1u >= n_cigar) r.y = 5u; if (k + 2u >= n_cigar) r.z = 5u;
+    if (k + 3u >= n_cigar) r.w = 5u;
+    }
+  return r;
+}
+__device__ __forceinline__ void refwin_s_init(RefWinS& w, MkpCigarPtr cg, bool wide, uint32_t n_cigar, int32_t ref_start) {
   w.c0 = 0u - 256u; w.q_run = 0; w.r_run = ref_start; w.Rtot = 0; w.Qtot = 0; w.re = w.m1 = w.m2 = w.m3 = 0;
     w.pk[0] = w.pk[1] = w.pk[2] = w.pk[3] = 0;
-  w.pref = cigar_quad(cg, n_cigar, 0);
+  w.pref = cigar_quad_s_load(cg, wide, n_cigar, 0);
 }
 // the next 256 ops; false behind the last op
-__device__ __forceinline__ bool refwin_s_next(RefWinS& w, const uint32_t* __restrict__ cg, uint32_t n_cigar, int32_t ref_start) {
+__device__ __forceinline__ bool refwin_s_next(RefWinS& w, MkpCigarPtr cg, bool wide, uint32_t n_cigar, int32_t ref_start) {
   w.c0 = rfl(w.c0 + 256u); w.q_run = rfl(w.q_run + w.Qtot); w.r_run = (int32_t)rfl((uint32_t)w.r_run + w.Rtot);
   if (w.c0 >= n_cigar) { w.Rtot = 0; w.Qtot = 0; return false; }
-  const uint4 v = w.pref;
-  w.pref = cigar_quad(cg, n_cigar, w.c0 + 256u);   // requested one window ahead
+  const uint4 v = cigar_quad_s_ops(w.pref, wide, n_cigar, w.c0);
+  w.pref = cigar_quad_s_load(cg, wide, n_cigar, w.c0 + 256u);   // requested one window ahead
   const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
   uint32_t ql[4], rl[4], kind[4];
 #pragma unroll
@@ -188,12 +216,12 @@ __device__ __forceinline__ void refwin_s_pass(const RefWinS& w, int32_t ref_star
   const uint32_t pk = rel < o_m1 ? o0 : rel < o_m2 ? o1 : rel < o_m3 ? o2 : o3;
   if (inw) { kind = pk & 3u; q = (uint32_t)((p - ref_start) + ((int32_t)pk >> 2)); pending = false; }
 }
-__device__ __forceinline__ void refwin_s_map(RefWinS& w, const uint32_t* __restrict__ cg, uint32_t n_cigar, int32_t ref_start, bool valid, int32_t p,
+__device__ __forceinline__ void refwin_s_map(RefWinS& w, MkpCigarPtr cg, bool wide, uint32_t n_cigar, int32_t ref_start, bool valid, int32_t p,
     uint32_t* kind_out, uint32_t* q_out) {
   bool pending = valid; uint32_t kind = 2u, q = 0u;
   refwin_s_pass(w, ref_start, pending, p, kind, q);
   while (__any(pending)) {
-    if (!refwin_s_next(w, cg, n_cigar, ref_start)) break;   // (cannot happen for positions inside the span)
+    if (!refwin_s_next(w, cg, wide, n_cigar, ref_start)) break;   // (cannot happen for positions inside the span)
     refwin_s_pass(w, ref_start, pending, p, kind, q);
   }
   *kind_out = kind; *q_out = q;
@@ -356,10 +384,11 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
 // matters: the SEQ and the rank list were resolved into the plane when the shard became resident (mkp_call_plane), so that a slot learns its
 // base, whether a call is listed there and as which call from one 16-byte gather and a popcount; the caller is resolved to
 // a fixed walk per read.  No per-read LDS beyond the caller constants and no base windows: reads of every length take the same code.
-#define FUSED_PARAMS(PRM) const MkpWork* __restrict__ work, uint32_t n_reads, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ seqs, \
+#define FUSED_PARAMS(PRM) const MkpWork* __restrict__ work, uint32_t n_reads, const uint32_t* __restrict__ cigar, const uint16_t* __restrict__ cigar16, \
+    const uint8_t* __restrict__ seqs, \
     const uint4* __restrict__ plane, const uint8_t* __restrict__ ml, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const uint32_t* __restrict__ slot_pos, \
     uint8_t* __restrict__ cov, MkpVisit* __restrict__ visits, MkpReadOut* __restrict__ readout
-#define FUSED_PASS work, n_reads, cigar, seqs, plane, ml, fdesc, prm, slot_pos, cov, visits, readout
+#define FUSED_PASS work, n_reads, cigar, cigar16, seqs, plane, ml, fdesc, prm, slot_pos, cov, visits, readout
 __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParams&), SlotLds* __restrict__ lds_all) {
   const int lane = lane_id();
   const uint32_t wib = rfl(threadIdx.x >> 6);
@@ -371,7 +400,10 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   const uint32_t aln = rev ? 1u : 0u;
   const uint32_t L = h.l_seq;
   const uint4* __restrict__ pl = plane + h.pad;
-  const uint32_t* __restrict__ cg = cigar + h.cigar_off;
+  // the read's ops: 16 bits each, or its BAM words when one of them does not fit (the work record's offset is into the array it reads)
+  const bool cg_wide = (h.flags & MKP_RF_CIGW) != 0;
+  MkpCigarPtr cg = cg_wide ? (MkpCigarPtr)(cigar + h.cigar_off) : (MkpCigarPtr)(cigar16 + h.cigar_off);
+  asm volatile("" : "+s"(cg));   // (one pointer: left to itself the compiler keeps both arrays' addresses through the slot loop)
   // a read with a base that is not A/C/G/T takes its bases from the SEQ (its offset; ~0 for every other read: one scalar register)
   const uint32_t seqn_off = (h.flags & MKP_RF_SEQN) ? h.seq_off : 0xffffffffu;
   bool have_calls = !(h.flags & MKP_RF_BAD) && h.n_tags != 0;
@@ -382,7 +414,7 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   const uint32_t n_sl = h.n_sl;
   const uint32_t* __restrict__ spos = slot_pos + h.gs0;
   uint32_t p_next = (uint32_t)lane < n_sl ? ldo<uint32_t>(spos, 4u * (uint32_t)lane) : 0u;
-  RefWinS rw; refwin_s_init(rw, cg, h.n_cigar, h.ref_start);
+  RefWinS rw; refwin_s_init(rw, cg, cg_wide, h.n_cigar, h.ref_start);
 
   // ---- the read's one (mod strand, base) group.  The caller's walk over a call's map in iteration order is resolved once per
   // layout by the host (MkpFusedDesc: one scalar load): where the ML byte of the i-th code sits (tag + index: offset and stride
@@ -440,7 +472,7 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
 #ifdef MKP_DEBUG
     if (prm.debug_skip & 64u) { kind = 0u; q = min((uint32_t)(p - h.ref_start), L - 1u); } else   // ablation: no CIGAR mapping
 #endif
-    refwin_s_map(rw, cg, h.n_cigar, h.ref_start, valid, p, &kind, &q);
+    refwin_s_map(rw, cg, cg_wide, h.n_cigar, h.ref_start, valid, p, &kind, &q);
     const bool is_match = valid && kind == 0u && q < L;
     // the plane entry of the base: its 2-bit code, bit q & 31 of .listed = a listed call sits here, .before + the listed bits below it =
     // its stored-order ordinal
@@ -1075,13 +1107,14 @@ extern "C" __global__ void __launch_bounds__(64) mkp_dup_events(const MkpReadHdr
 // ----------------------------------------------------------------------------------------------------------------------
 // host-side launchers (called from mkp_api.cpp)
 // work = the fused decoder's reads (longest first), cover_ids = the reads of mkp_cover_reads
-extern "C" hipError_t mkp_launch_slots(hipStream_t st, const MkpWork* work, uint32_t n_fused, const void* plane, const MkpReadHdr* hdrs,
+extern "C" hipError_t mkp_launch_slots(hipStream_t st, const MkpWork* work, uint32_t n_fused, const void* plane, const uint16_t* cigar16,
+    const MkpReadHdr* hdrs,
     const uint32_t* cover_ids, uint32_t n_cover, const uint32_t* cigar,
                                        const uint8_t* seqs, const MkpTagRef* tagref, const uint32_t* ranks, const uint8_t* ml,
                                            const MkpLayout* layouts, const MkpFusedDesc* fdesc, const MkpRunParams* prm,
                                        const uint32_t* slot_pos, uint8_t* cov, MkpVisit* visits, MkpEvent* events, MkpReadOut* readout,
                                            uint32_t* dev_err) {
-  if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, cigar, seqs, static_cast<const uint4*>(plane), ml, fdesc, *prm,
+  if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, cigar, cigar16, seqs, static_cast<const uint4*>(plane), ml, fdesc, *prm,
       slot_pos, cov, visits, readout);
   if (n_cover) hipLaunchKernelGGL(mkp_cover_reads, dim3((n_cover + 3u) / 4u), dim3(256), 0, st, hdrs, n_cover, cover_ids, cigar, seqs, tagref, ranks,
       ml, layouts, fdesc, *prm, slot_pos, cov, visits, events, readout, dev_err);
