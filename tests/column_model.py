@@ -1,4 +1,5 @@
-"""A plain per-base model of a pileup column, for the CIGAR-edge tests (tests/cigar_edge_cases.py).
+"""A plain per-base model of a pileup column, for the CIGAR-edge tests (tests/cigar_edge_cases.py) and the multi-tag, duplex-tag and
+edge-filter tests (tests/multi_feature_cases.py).
 
 Pure Python + numpy; it imports neither the oracle nor modkit_amd.  It restates the reference's column loop (src/pileup/mod.rs) in one
 obvious walk: for every CIGAR op of every record, for every reference base of the op, one feature.  No windows, no chunks of ops, no
@@ -11,13 +12,30 @@ What it restates, with the reference's lines:
     deletion     Feature::Delete on the alignment's strand (mod.rs:851-859), after the record's codes were noted (mod.rs:831-835)
     base         SEQ[qpos], complemented for a reverse record (mod.rs:612-624, 862-869); a base that is not ACGT gives no feature
                  (mod.rs:870-874)
-    call         the read's call at that reference position when the read base is the tag's base, else NoCall(base)
-                 (read_cache.rs:214-297); a record whose tags fail to parse gives NoCall everywhere and notes no codes
+    call         get_mod_call (read_cache.rs:214-297): the read's calls are kept per read strand and per base of SEQ (the tag's base; for an
+                 `N` tag whatever base sits there, mod_bam.rs:1245-1248); the column asks with the read's base.  The four arms
+                 (mod.rs:876-938): no call -> NoCall(base); a '+' call -> a feature of the read's base on the alignment's strand; a '-'
+                 call -> a feature of the COMPLEMENT of the read's base on the OTHER strand's tally (mod.rs:254-259); both -> both,
+                 two features of one read on one column.  A '-' tag is called with the complement's thresholds (read_cache.rs:147-150).
+                 A record whose tags fail to parse gives NoCall everywhere and notes no codes
+    codes        observed codes are per reference strand and primary base (add_mod_codes_for_record, read_cache.rs:299-355): a '+' tag's
+                 on the alignment's strand, a '-' tag's on the other one, under the complement (read_cache.rs:181-194)
+    edge filter  --edge-filter a[,b] / --invert-edge-filter: EdgeFilter::keep_position and read_can_be_trimmed (mod_bam.rs:1642-1671) over
+                 forward-read positions and the SEQ length (soft clips included), applied per (strand, base) by edge_filter_positions
+                 (mod_bam.rs:1075-1102).  The inferred calls of a '.' tag were made before the filter and the filtered map is Explicit,
+                 so a filtered position of a '.' tag is NO call (NoCall of the base), not a canonical one.  A (strand, base) left with
+                 nothing is dropped: its bases give NoCall and its codes are not observed (read_cache.rs:159-165).  A read too short
+                 to trim (L <= a or L <= b), or with nothing left at all, is an error to add_record (read_cache.rs:206-210): it joins
+                 the skip set, so it still counts on every column it covers — NoCall of its base, Delete under a deletion — and
+                 notes no observed codes (read_cache.rs:239-240, 308-309)
     tally        Tally / add_feature (mod.rs:167-281): a forward record counts on '+', a reverse one on '-'; the focus position's
                  strand rule keeps one or both
-    rows         one row per (strand, observed code) where the strand's tally holds at least one call of the primary base
-                 (mod.rs:283-365), ordered by strand then code (mod.rs:440-443); N_diff = the NoCalls of other bases, N_nocall = the
-                 NoCalls of the primary base
+    rows         per strand and per primary base whose tally holds at least one call: one row per observed code of that base
+                 (mod.rs:283-365), ordered by strand then code (mod.rs:440-443); N_diff = the NoCalls and the calls of every other base
+                 (mod.rs:198-223), N_nocall = the NoCalls of the row's base.  One (position, strand) may give rows of two primary bases.
+                 Where two of them share a code (an `N` tag's) their order is the reference's map order: the model raises
+    combine-mods one row per (position, strand, primary base), coded with the base: N_mod = every modified call, N_other = 0
+                 (PileupNumericOptions::Combine, mod.rs:366-407); the calls themselves are unchanged
     --include-bed  the BED's spans replace the contigs (and a --region's ends) as the stretches to work on (position_filter.rs:103-210)
     focus        the reference works in intervals of `-i` bases (interval_chunks.rs:563-632) and looks for motif hits in the text of
                  one interval only (fasta.rs:190-228), so a motif cut by an interval or region end is not a focus position; with
@@ -25,9 +43,10 @@ What it restates, with the reference's lines:
     combine      --combine-strands adds the '-' rows at the motif's other position to the '+' rows, per code, inside one interval
                  (mod.rs:469-561)
 
-Scope: tags of one primary base on the read's own strand (`C+m?`, `C+h?;C+m?`, `C+m.`, `C+m?;C+21839?;C+h?`, ...), a caller that is
---no-filtering or one --filter-threshold (the call class comes from tests/caller_model.py), unique read names.  Sampling, edge filter,
-partition tags, --combine-mods, --ignore and max-depth are not modelled.
+Scope: tags of any number of primary bases on either read strand (`C+m?`, `C+h?;C+m?;A+a?`, `C+m?;G-m?`, `C+m?;C-g?`, `N+b?`, ...),
+'?' and '.' modes, a caller that is --no-filtering or one --filter-threshold (the call class comes from tests/caller_model.py; a call
+whose class depends on the map's iteration order raises), --edge-filter / --invert-edge-filter, --combine-mods, unique read names.
+Out of scope: two motifs, --ignore, sampling, partition tags and max-depth.
 """
 import bisect
 import re
@@ -41,8 +60,11 @@ COUNTS = ("n_valid", "n_mod", "n_canonical", "n_other", "n_delete", "n_fail", "n
 DROP_FLAGS = 4 | 256 | 512 | 1024 | 2048
 
 # feature kinds of one (position, strand)
-K_SKIP, K_DELETE, K_FAIL, K_NOCALL, K_CANONICAL, K_MOD, K_OBSERVED = -1, 0, 1, 2, 6, 7, 32   # K_NOCALL + "ACGT".index(base); K_MOD + code index
-N_KINDS = 64
+K_SKIP, K_DELETE, K_FAIL, K_NOCALL, K_CANONICAL, K_MOD, K_OBSERVED = -1, 0, 1, 2, 6, 10, 64   # K_NOCALL / K_CANONICAL + "ACGT".index(base); K_MOD / K_OBSERVED + index of the (base, code) pair
+N_KINDS = 128
+
+
+QUAL_PROBS = caller_model.quals_to_probs(np.arange(256))   # the probability of every ML byte
 
 
 def code_key(code):
@@ -50,55 +72,86 @@ def code_key(code):
     return (1, int(code), "") if code.isdigit() else (0, 0, code)
 
 
+class EdgeFilter:
+    """EdgeFilter (mod_bam.rs:1634-1672) over forward-read positions and the SEQ length."""
+
+    def __init__(self, start, end, inverted=False):
+        self.start, self.end, self.inverted = int(start), int(end), bool(inverted)
+
+    def read_can_be_trimmed(self, length):          # mod_bam.rs:1668-1671
+        return not (length <= self.start or length <= self.end)
+
+    def keep_position(self, p, length):             # mod_bam.rs:1642-1665 (the caller has checked read_can_be_trimmed)
+        if self.inverted:
+            return p < self.start or p >= length - self.end
+        return p >= self.start and p < length - self.end
+
+    def __hash__(self):
+        return hash((self.start, self.end, self.inverted))
+
+    def __eq__(self, o):
+        return isinstance(o, EdgeFilter) and (self.start, self.end, self.inverted) == (o.start, o.end, o.inverted)
+
+
 def parse_tags(mm, ml, fwd):
-    """MM / ML of one record over its as-sequenced bases `fwd` -> (base, {forward position: {code: f32 probability}}) or None when the
-    record is one the reference skips (no tags, a mode it does not allow, an ML of the wrong length, a list that runs past the read,
-    probabilities of several tags summing above 1.01)."""
+    """MM / ML of one record over its as-sequenced bases `fwd` -> {(read strand '+' | '-', base of SEQ): {forward position: {code: f32
+    probability}}} (ModBaseInfo::new, get_base_mod_probs, mod_bam.rs:1213-1295, 1488-1535), or None when the record is one the
+    reference skips: no tags, a mode it does not allow, a list that runs past the read or the ML, a listed base of SEQ that is not ACGT,
+    an inferred ('.' mode) call meeting a listed one of another tag, probabilities of several tags summing above 1.01, ML bytes left
+    over.  A call is filed under the base SEQ holds at its position, which for an `N` tag is whatever base is there."""
     if not mm:
         return None
-    calls, base, at = {}, None, 0
+    groups, at = {}, 0
     for part in [p for p in mm.split(";") if p]:
         head, _, rest = part.partition(",")
-        m = re.fullmatch(r"([ACGT])\+([a-z]+|[0-9]+)([?.]?)", head)
-        if m is None or m.group(3) == "":          # (no mode: implicit by default, refused without --force-allow-implicit)
+        m = re.fullmatch(r"([ACGTN])([+-])([a-z]+|[0-9]+)([?.]?)", head)
+        if m is None or m.group(4) == "":          # (no mode: implicit by default, refused without --force-allow-implicit)
             return None
-        if base is not None and m.group(1) != base:
-            raise ValueError("out of the model's scope: tags of two bases")
-        base = m.group(1)
-        codes = [m.group(2)] if m.group(2).isdigit() else list(m.group(2))
+        fb, strand = m.group(1), m.group(2)
+        codes = [m.group(3)] if m.group(3).isdigit() else list(m.group(3))
+        if len(set(codes)) != len(codes):
+            raise ValueError("out of the model's scope: a code listed twice in one tag")
         deltas = [int(x) for x in rest.split(",")] if rest else []
-        occ = [i for i, c in enumerate(fwd) if c == base]
-        tag, rank = {}, -1
+        occ = range(len(fwd)) if fb == "N" else [i for i, c in enumerate(fwd) if c == fb]
+        tag, rank = {}, -1                          # forward position -> (probabilities, inferred)
         for d in deltas:
             rank += d + 1
             if rank >= len(occ) or at + len(codes) > len(ml):
                 return None
-            tag[occ[rank]] = {c: caller_model.quals_to_probs(ml[at + j]) for j, c in enumerate(codes)}
+            if fwd[occ[rank]] not in COMP:          # DnaBase::try_from(forward_sequence[position])? (mod_bam.rs:1245)
+                return None
+            tag[occ[rank]] = ({c: QUAL_PROBS[ml[at + j]] for j, c in enumerate(codes)}, False)
             at += len(codes)
-        if m.group(3) == ".":
+        if m.group(4) == "." and fb != "N":         # (an `N` tag's converter holds no counts: nothing is inferred, mod_bam.rs:668-669)
             for p in occ:
-                tag.setdefault(p, {c: np.float32(0) for c in codes})
-        for p, probs in tag.items():
-            have = calls.setdefault(p, {})
-            fresh = not have
+                tag.setdefault(p, ({c: np.float32(0) for c in codes}, True))
+        for p, (probs, inferred) in tag.items():
+            group = groups.setdefault((strand, fwd[p]), {})
+            if p not in group:
+                group[p] = (dict(probs), inferred)
+                continue
+            have, was_inferred = group[p]
+            if was_inferred != inferred:            # combine_checked: ExplicitConflictInferred (mod_bam.rs:630-634)
+                return None
             for c, v in probs.items():
                 have[c] = np.float32(have.get(c, np.float32(0)) + v)
-            if not fresh and np.float32(sum(have.values(), np.float32(0))) > caller_model.MAX_PROB:
+            if np.float32(sum(have.values(), np.float32(0))) > caller_model.MAX_PROB:
                 return None
     if at != len(ml):
         return None
-    return base, calls
+    return {k: {p: probs for p, (probs, _) in g.items()} for k, g in groups.items()}
 
 
-def call_classes(calls, threshold):
-    """{forward position: 'F' (filtered) | '-' (canonical) | code} through caller_model.evaluate, grouped by the codes a call lists."""
+def call_classes(calls, threshold, base="C"):
+    """{forward position: 'F' (filtered) | '-' (canonical) | code} through caller_model.evaluate, grouped by the codes a call lists.
+    base: the base the calls are made on (the tag's base, complemented for a '-' tag: read_cache.rs:147-150)."""
     groups = {}
     for p, probs in calls.items():
         groups.setdefault(tuple(probs), []).append(p)
     out = {}
     for codes, ps in groups.items():
         P = np.array([[calls[p][c] for c in codes] for p in ps], dtype=np.float32)
-        ev = caller_model.evaluate(list(codes), P, base="C", default=0.0 if threshold is None else threshold)
+        ev = caller_model.evaluate(list(codes), P, base=base, default=0.0 if threshold is None else threshold)
         if ev["order_dep"].any():
             raise ValueError("a call's class depends on the map's iteration order; the model does not decide it")
         for p, c in zip(ps, ev["cls"]):
@@ -173,34 +226,104 @@ def bed_regions(bed, interval):
     return [tuple(x) for x in out]
 
 
-def walk(records, threshold):
-    """The column loop without the focus filter: {(pos, strand): int64[N_KINDS] counts per feature kind}, and the codes seen.
-    records: (start, flag, cigar, seq, mm, ml) of one contig."""
-    all_codes, parsed = [], []
-    for start, flag, cigar, seq, mm, ml in records:
+def filter_groups(groups, length, edge_filter):
+    """edge_filter_positions per (strand, base) (mod_bam.rs:1075-1102) as add_record applies it (read_cache.rs:151-165): a group left
+    with nothing is dropped; a read too short to trim loses every group, which makes it a skipped read (read_cache.rs:206-210): NoCall
+    on every column, no observed codes."""
+    if edge_filter is None:
+        return groups
+    kept = {}
+    if edge_filter.read_can_be_trimmed(length):
+        for k, calls in groups.items():
+            calls = {p: v for p, v in calls.items() if edge_filter.keep_position(p, length)}
+            if calls:
+                kept[k] = calls
+    return kept
+
+
+def call_stats(records, edge_filter=None, cache=None):
+    """(calls listed by the records the column loop keeps, calls the edge filter removed, aligned bases that carry a call of the read's '+'
+    and of its '-' strand after the filter), for the floors of the tests.  cache: as for walk()."""
+    listed = removed = two = 0
+    for ri, (start, flag, cigar, seq, mm, ml) in enumerate(records):
+        if flag & DROP_FLAGS or not seq:
+            continue
+        if cache is not None and ri in cache:
+            groups = cache[ri]
+        else:
+            rev = bool(flag & 16)
+            fwd = "".join(COMP.get(c, "N") for c in reversed(seq)) if rev else seq
+            groups = parse_tags(mm, list(ml), fwd) or {}
+            if cache is not None:
+                cache[ri] = groups
+        kept = filter_groups(groups, len(seq), edge_filter)
+        listed += sum(len(g) for g in groups.values())
+        removed += sum(len(g) for g in groups.values()) - sum(len(g) for g in kept.values())
+        both = set()
+        for (strand, base), calls in kept.items():
+            if strand == "+" and ("-", base) in kept:
+                both |= set(calls) & set(kept[("-", base)])
+        if both:
+            L, q = len(seq), 0
+            for n, op in cigar:
+                if op in "M=X":
+                    two += sum(1 for p in both if q <= (L - 1 - p if flag & 16 else p) < q + n)
+                if op in "MIS=X":
+                    q += n
+    return listed, removed, two
+
+
+def walk(records, threshold, edge_filter=None, cache=None):
+    """The column loop without the focus filter: {(pos, strand): int64[N_KINDS] counts per feature kind}, and the (primary base, code)
+    pairs seen.  records: (start, flag, cigar, seq, mm, ml) of one contig; edge_filter: an EdgeFilter or None; cache: a dict that keeps
+    the records' parsed tags from one walk of these records to the next (they depend on neither the threshold nor the filter)."""
+    pairs, parsed = [], []
+    for ri, (start, flag, cigar, seq, mm, ml) in enumerate(records):
         if flag & DROP_FLAGS or not seq:
             continue
         rev = bool(flag & 16)
         fwd = "".join(COMP.get(c, "N") for c in reversed(seq)) if rev else seq
-        tags = parse_tags(mm, list(ml), fwd)
-        cls = call_classes(tags[1], threshold) if tags else {}
-        seen = sorted({c for probs in tags[1].values() for c in probs}, key=code_key) if tags else []
-        for c in seen:
-            if c not in all_codes:
-                all_codes.append(c)
-        parsed.append((start, rev, cigar, seq, tags[0] if tags else None, cls, seen))
+        if cache is not None and ri in cache:
+            groups = cache[ri]
+        else:
+            groups = parse_tags(mm, list(ml), fwd) or {}
+            if cache is not None:
+                cache[ri] = groups
+        groups = filter_groups(groups, len(seq), edge_filter)
+        own, opp, seen = {}, {}, ([], [])            # calls on the read's own strand / its other one; pairs seen by alignment-relative strand
+        for (strand, base), calls in sorted(groups.items()):
+            on = base if strand == "+" else COMP[base]       # threshold_base (read_cache.rs:147-150), the feature's primary base
+            cls = call_classes(calls, threshold, on)
+            for p, c in cls.items():
+                (own if strand == "+" else opp)[p] = (on, c)
+            for c in sorted({c for probs in calls.values() for c in probs}, key=code_key):
+                if (on, c) not in pairs:
+                    pairs.append((on, c))
+                seen[strand == "-"].append((on, c))
+        parsed.append((start, rev, cigar, seq, own, opp, seen))
+    assert len(pairs) <= N_KINDS - K_OBSERVED and K_MOD + len(pairs) <= K_OBSERVED, "too many (base, code) pairs for the key layout"
     keys = []
-    for start, rev, cigar, seq, base, cls, seen in parsed:
+
+    def kind_of(on, c):
+        return K_FAIL if c == "F" else K_CANONICAL + "ACGT".index(on) if c == "-" else K_MOD + pairs.index((on, c))
+    for start, rev, cigar, seq, own, opp, seen in parsed:
         L = len(seq)
         stored = np.frombuffer(seq.encode(), dtype=np.uint8)
         lut = np.full(256, K_SKIP, dtype=np.int64)
         for i, b in enumerate("ACGT"):
             lut[ord(COMP[b] if rev else b)] = K_NOCALL + i       # the read's own base: SEQ complemented for a reverse record
-        feat = lut[stored]
-        for p, c in cls.items():
+        feat = lut[stored]                                       # the feature of the read's own strand (mod.rs:889-937) ...
+        other = np.full(L, K_SKIP, dtype=np.int64)               # ... and of its other strand, counted on the opposite tally (mod.rs:254-259)
+        for p, (on, c) in own.items():
             q = L - 1 - p if rev else p
-            assert feat[q] == K_NOCALL + "ACGT".index(base)
-            feat[q] = K_FAIL if c == "F" else K_CANONICAL if c == "-" else K_MOD + all_codes.index(c)
+            assert feat[q] == K_NOCALL + "ACGT".index(on)
+            feat[q] = kind_of(on, c)
+        for p, (on, c) in opp.items():
+            q = L - 1 - p if rev else p
+            assert feat[q] == K_NOCALL + "ACGT".index(COMP[on]) or p in own
+            if p not in own:
+                feat[q] = K_SKIP                                 # (None, Some): the negative feature alone (mod.rs:919-931)
+            other[q] = kind_of(on, c)                            # its base is read_base.complement()
         strand = 1 if rev else 0
         r, q = int(start), 0
         for n, op in cigar:
@@ -208,12 +331,16 @@ def walk(records, threshold):
                 pos = np.arange(r, r + n, dtype=np.int64)
                 f = feat[q:q + n]
                 keys.append(((pos * 2 + strand) * N_KINDS + f)[f != K_SKIP])
+                if opp:
+                    f = other[q:q + n]
+                    keys.append(((pos * 2 + (1 - strand)) * N_KINDS + f)[f != K_SKIP])
             elif op == "D":
                 pos = np.arange(r, r + n, dtype=np.int64)
                 keys.append((pos * 2 + strand) * N_KINDS + K_DELETE)
             if op in "M=XD":          # (not N: a ref-skip alignment never reaches add_mod_codes_for_record)
-                for c in seen:
-                    keys.append((pos * 2 + strand) * N_KINDS + K_OBSERVED + all_codes.index(c))
+                for flip in (0, 1):   # the codes of '+' tags on the alignment's strand, of '-' tags on the other (read_cache.rs:181-188)
+                    for pair in seen[flip]:
+                        keys.append((pos * 2 + (strand ^ flip)) * N_KINDS + K_OBSERVED + pairs.index(pair))
             if op in "M=XDN":
                 r += n
             if op in "MIS=X":
@@ -222,35 +349,55 @@ def walk(records, threshold):
     cols = {}
     if keys:
         k, cnt = np.unique(np.concatenate(keys), return_counts=True)
-        for key, c in zip(k.tolist(), cnt.tolist()):
-            ps, kind = divmod(key, N_KINDS)
-            cols.setdefault((ps >> 1, "+-"[ps & 1]), np.zeros(N_KINDS, dtype=np.int64))[kind] = c
-    return cols, all_codes
+        ps, at = np.unique(k // N_KINDS, return_inverse=True)
+        tallies = np.zeros((len(ps), N_KINDS), dtype=np.int64)
+        tallies[at, k % N_KINDS] = cnt
+        cols = {(v >> 1, "+-"[v & 1]): tallies[i] for i, v in enumerate(ps.tolist())}
+    return cols, pairs
 
 
-def rows_of(t, codes, base="C"):
-    """add_tally_to_counts for one (position, strand) tally -> {code: counts tuple in COUNTS order}"""
-    n_can = int(t[K_CANONICAL])
-    mods = {c: int(t[K_MOD + i]) for i, c in enumerate(codes)}
-    total = sum(mods.values())
-    if n_can + total == 0:
+def rows_of(t, pairs, combine_mods=False):
+    """add_tally_to_counts (mod.rs:283-410) for one (position, strand) tally -> {code: counts tuple in COUNTS order}.  pairs: the
+    (primary base, code) pairs of the run, in the order walk() numbered them.  One row per observed code of every primary base whose
+    tally holds a call; N_diff = the NoCalls and the calls of every other base (diff_calls_count, mod.rs:198-223), N_nocall = the
+    NoCalls of the row's base.  combine_mods: one row per primary base, coded with the base (PileupNumericOptions::Combine,
+    mod.rs:366-407)."""
+    t = t.tolist()
+    if not any(t[K_CANONICAL:K_OBSERVED]):                       # no call of any base: no row
         return {}
-    bi = "ACGT".index(base)
-    n_diff = sum(int(t[K_NOCALL + i]) for i in range(4) if i != bi)
+    calls = {}                                                   # primary base -> (n_canonical, {code: n})
+    for bi, b in enumerate("ACGT"):
+        mods = {c: t[K_MOD + i] for i, (pb, c) in enumerate(pairs) if pb == b and t[K_MOD + i]}
+        if t[K_CANONICAL + bi] or mods:
+            calls[b] = (t[K_CANONICAL + bi], mods)
     out = {}
-    for i, c in enumerate(codes):
-        if t[K_OBSERVED + i]:
-            out[c] = (n_can + total, mods[c], n_can, total - mods[c], int(t[K_DELETE]), int(t[K_FAIL]), n_diff, int(t[K_NOCALL + bi]))
+    for b, (n_can, mods) in calls.items():
+        bi = "ACGT".index(b)
+        total = sum(mods.values())
+        n_diff = sum(t[K_NOCALL + i] for i in range(4) if i != bi) + sum(c + sum(m.values()) for ob, (c, m) in calls.items() if ob != b)
+        tail = (t[K_DELETE], t[K_FAIL], n_diff, t[K_NOCALL + bi])
+        if combine_mods:
+            rows = {b: (n_can + total, total, n_can, 0) + tail}
+        else:
+            rows = {c: (n_can + total, mods.get(c, 0), n_can, total - mods.get(c, 0)) + tail
+                    for i, (pb, c) in enumerate(pairs) if pb == b and t[K_OBSERVED + i]}
+        for c, v in rows.items():
+            if c in out:
+                raise ValueError("two primary bases give a row of code %r on one (position, strand): their order is not decided" % c)
+            out[c] = v
     return out
 
 
-def pileup(records, ref, threshold=None, motif=None, bed=None, combine_strands=False, region=None, interval=100000, walked=None):
+def pileup(records, ref, threshold=None, motif=None, bed=None, combine_strands=False, region=None, interval=100000, walked=None,
+           edge_filter=None, combine_mods=False):
     """The bedMethyl rows of one contig: {(pos, strand, code): counts tuple in COUNTS order}.
     records: [(start, flag, cigar, seq, MM text, ML bytes)]; ref: the contig's text (upper case); threshold: None for --no-filtering,
     else the one --filter-threshold; motif: (text, offset) (--cpg is ("CG", 0)); bed: [(start, end, '+' | '-' | '.')] of --include-bed;
-    region: (start, end) of --region; interval: -i; walked: walk(records, threshold) when the caller already holds it."""
+    region: (start, end) of --region; interval: -i; walked: walk(records, threshold, edge_filter) when the caller already holds it;
+    edge_filter: an EdgeFilter (--edge-filter, --invert-edge-filter); combine_mods: --combine-mods."""
     assert not (combine_strands and motif is None)
-    cols, codes = walked or walk(records, threshold)
+    cols, pairs = walked or walk(records, threshold, edge_filter)
+    codes = sorted({b for b, _ in pairs} if combine_mods else {c for _, c in pairs}, key=code_key)
     by_pos = {}
     for (pos, strand), t in cols.items():
         by_pos.setdefault(pos, {})[strand] = t
@@ -268,7 +415,7 @@ def pileup(records, ref, threshold=None, motif=None, bed=None, combine_strands=F
                 allowed = allowed & inside
             for strand in sorted(allowed):
                 if strand in by_pos[pos]:
-                    for code, counts in rows_of(by_pos[pos][strand], codes).items():
+                    for code, counts in rows_of(by_pos[pos][strand], pairs, combine_mods).items():
                         here[(pos, strand, code)] = counts
         if not combine_strands:
             rows.update(here)

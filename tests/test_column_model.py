@@ -1,12 +1,10 @@
 """Pins tests/column_model.py on the CPU: against the reference's own golden bedMethyl files (the fixture BAMs read with a minimal BAM
-reader, gzip + struct), and against the oracle on every directed BAM of tests/cigar_edge_cases.py under every flag set the GPU test
-(tests/test_gpu_cigar_edges.py) runs.  Every count column and the row set must be equal; no row is left out.
+reader, gzip + struct), and against the oracle on every directed BAM of tests/cigar_edge_cases.py and tests/multi_feature_cases.py under
+every flag set the GPU tests (tests/test_gpu_cigar_edges.py, tests/test_gpu_multi_feature.py) run.  Every count column and the row set
+must be equal; no row is left out.
 
 Goldens outside the model's scope, left out by name:
     test_pileup_with_filt, ..._position_filter, ..._positions_and_traditional   the threshold is estimated from a sample (-p)
-    test_pileup_combine                 --combine-mods
-    test_pileup_duplex_reads            tags on both strands of a read
-    test_pileup_edge_filter_*           --edge-filter
     test_pileup_motifs_cg0_cgcg2*       two motifs (rows carry a motif label each)
     test_pileup_with_header             the same rows as test_pileup_no_filt under a header; included (the reader skips the header)
 """
@@ -18,10 +16,12 @@ import pytest
 
 import cigar_edge_cases as cases
 import column_model as cm
+import multi_feature_cases as mf
 from pileup_cases import GOLDEN_CASES, REF, fixture
 
 GOLDENS_IN_SCOPE = ["test_pileup_no_filt:23", "test_pileup_with_header:900", "test_pileup_with_region:194", "test_pileup_cpg_motif_filtering:237"] + \
-    ["test_pileup_cpg_motif_filtering_strand_combine:257[i=%s]" % i for i in ("10", "88", "89", "90", "91", "92", "93", "94", "10000")]
+    ["test_pileup_cpg_motif_filtering_strand_combine:257[i=%s]" % i for i in ("10", "88", "89", "90", "91", "92", "93", "94", "10000")] + \
+    ["test_pileup_duplex_reads:217", "test_pileup_edge_filter_regression:360", "test_pileup_edge_filter_asymmetric_regression:418", "test_pileup_combine:71"]
 
 
 def read_bam(path):
@@ -75,7 +75,7 @@ def read_fasta(path):
 
 def model_flags(flags, contigs, refs):
     """The reference's command line -> the model's arguments, plus the contigs to run."""
-    kw, k, only = dict(threshold=None, interval=100000), 0, None
+    kw, k, only, edge, inverted = dict(threshold=None, interval=100000), 0, None, None, False
     while k < len(flags):
         f = flags[k]
         if f == "-i":
@@ -101,11 +101,20 @@ def model_flags(flags, contigs, refs):
                 c = ln.split()
                 kw["bed"].setdefault(c[0], []).append((int(c[1]), int(c[2]), c[5] if len(c) > 5 else "."))
             k += 1
+        elif f == "--edge-filter":            # parse_edge_filter_input (command_utils.rs:243-277): one number trims both ends
+            a, _, b = flags[k + 1].partition(",")
+            edge = (int(a), int(b) if b else int(a)); k += 1
+        elif f == "--invert-edge-filter":
+            inverted = True
+        elif f == "--combine-mods":
+            kw["combine_mods"] = True
         elif f == "--ref":
             k += 1
         else:
             assert f in ("--no-filtering", "--only-tabs", "--mixed-delim", "--with-header"), f
         k += 1
+    if edge is not None:
+        kw["edge_filter"] = cm.EdgeFilter(edge[0], edge[1], inverted)
     return kw, [c for c in contigs if only in (None, c[0])]
 
 
@@ -203,3 +212,38 @@ def test_directed_cigars_reach_both_decoders(built):
         if layout is not None:
             shapes.setdefault(tuple(cigar), set()).add(cases.LAYOUTS[layout][1] in cases.FUSED_CLASSES)
     assert len(shapes) >= 14 and all(v == {True, False} for v in shapes.values())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# several primary bases, '-' strand tags, `N` tags, the edge filter and --combine-mods: model vs oracle on tests/multi_feature_cases.py
+
+@pytest.fixture(scope="module")
+def built_mf(tmp_path_factory):
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            cache[name] = mf.BUILDERS[name](str(tmp_path_factory.mktemp(name) / name))
+        return cache[name]
+    return get
+
+
+@pytest.mark.parametrize("name", sorted(mf.BUILDERS))
+def test_model_equals_oracle_on_multi_feature_bams(oracle_bin, built_mf, tmp_path, name):
+    """Every flag set of the GPU test, both files; and the floors of multi_feature_cases.FLOORS are the model's own numbers."""
+    case = built_mf(name)
+    walked, parsed, numbers = {}, {}, []
+    for fi, flags in enumerate(mf.flag_sets(case)):
+        want, stats = mf.model_rows(cm, case, flags, walked, parsed)
+        numbers.append(stats)
+        for bam in (case.bam, case.bam_unindexed):
+            got = oracle_rows(oracle_bin, bam, str(tmp_path / ("o%d.bed" % fi)), cases.oracle_flags(flags))
+            try:
+                assert_same(got, {case.contig: want} if want else {}, "oracle", {case.contig: case.records})
+            except AssertionError as e:
+                raise AssertionError("%s under %s: %s" % (name, " ".join(flags), e))
+        assert len(want) > 100
+    assert numbers == mf.FLOORS[name], numbers
+    if name == "edge_filter":
+        assert all(n[3] > 0 for n in numbers)
+    assert all(n[1] > 0 for n in numbers) and any(n[2] > 0 for n in numbers)
