@@ -8,8 +8,9 @@
 //     mkp_decode_fast1/2     one group, any mode / differing delta lists: 1024-base steps, ordinal bitmap in LDS + 4-bit deposit
 //     mkp_decode_reads       everything else (<= 8 tags, `N` tags, duplex, repeated codes): combine_positions_to_probs per group
 //     mkp_merge_duplex       duplex reads decoded one group per wave: interleave the two position-sorted event lists
-//   all share the consumer: per 64 queued calls ML -> f32 BaseModProbs, edge filter, ReDistribute collapse,
-//   MultipleThresholdModCaller::call, CIGAR mapping (register window) and one packed 8-byte event per mapped call.
+//   The three decoders differ in how they locate calls; the per-call work (ML -> f32 BaseModProbs, edge filter, ReDistribute
+//   collapse, MultipleThresholdModCaller::call, CIGAR mapping, one packed 8-byte event per mapped call), the read prologue and
+//   epilogue are the shared helpers in front of them.  FAST and SPARSE run it on full batches of 64 queued calls.
 //   mkp_sample_* = the same walks emitting argmax probabilities / summary classes (threshold estimate, sample-probs, summary).
 //
 //   mkp_pileup_tiles[_focus|_hemi][_keyed]   accumulate + emit: one 1024-thread workgroup per tile, two per CU; LDS holds the
@@ -25,8 +26,260 @@
 #include "mkp_dev_common.hpp"
 #include "mkp_dev_rows.hpp"
 
+// ----------------------------------------------------------------------------------------------
+// What the three wave-per-read decoders share.  They differ in how they locate a read's calls (the producers); the read
+// prologue and epilogue, the per-call rules of the reference and the event append are written once, here.
+__device__ __forceinline__ uint32_t rfl_u(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ float rfl_f(float v) { return __uint_as_float(rfl_u(__float_as_uint(v))); }
+__device__ __forceinline__ void wave_lds_sync() {   // LDS written by some lanes of the wave is read by others
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
-// One wave per read.  The read is walked 512 bases at a time (one SEQ dword = 8 bases per lane):
+// Read prologue: the wave's read and its header; the read's layout (1216 B) goes to the wave's LDS slice once, every table
+// lookup afterwards is an LDS read.  False = nothing to decode: no read for this wave, or a bad / tag-less read, whose empty
+// summary is written here.  Wave-uniform values are made provably uniform (readfirstlane) so they live in SGPRs and load
+// through the scalar cache.  id_mask strips the flag bits a read list may carry in its ids (rid_raw keeps them).
+__device__ __forceinline__ bool read_prologue(const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads, const uint32_t* __restrict__ read_ids,
+    const MkpLayout* __restrict__ layouts, MkpReadOut* __restrict__ readout, uint32_t* __restrict__ lds_layouts, uint32_t id_mask,
+    uint32_t& wib, uint32_t& rid_raw, MkpReadHdr& h, uint32_t*& lds_lay) {
+  const int lane = lane_id();
+  wib = rfl_u(threadIdx.x >> 6);
+  const uint32_t widx = rfl_u(blockIdx.x * (blockDim.x >> 6)) + wib;
+  if (widx >= n_reads) return false;
+  rid_raw = rfl_u(read_ids[widx]);
+  const uint32_t rid = rid_raw & id_mask;
+  h = hdrs[rid];
+  if ((h.flags & MKP_RF_BAD) || h.n_tags == 0) {
+    MkpReadOut out; out.n_events = 0; out.ok = 0; out.obs[0] = 0; out.obs[1] = 0;
+    if (lane == 0) readout[rid] = out;
+    return false;
+  }
+  lds_lay = lds_layouts + wib * MKP_LAYOUT_DWORDS;
+  const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(&layouts[h.layout]);
+  for (int i = lane; i < MKP_LAYOUT_DWORDS; i += 64) lds_lay[i] = src[i];
+  __builtin_amdgcn_wave_barrier();
+  return true;
+}
+
+// a group descriptor that is the same for the whole wave: every field in SGPRs
+__device__ __forceinline__ GroupRegs load_group_uniform(const uint32_t* gp) {
+  GroupRegs g = load_group(gp);
+  g.misc = rfl_u(g.misc); g.slots = rfl_u(g.slots); g.cids = rfl_u(g.cids); g.member_tags = rfl_u(g.member_tags);
+#pragma unroll
+  for (int k = 0; k < MKP_KMAX; k++) at(g.thr, k) = rfl_f(at(g.thr, k));
+  g.thr_can = rfl_f(g.thr_can);
+  return g;
+}
+
+// Per-tag constants of a single-group decoder, tags tb .. tb+n_tags of the layout, all on base b0: number of codes, the tag's
+// map ([0:3] member index, [4+4i : 8+4i) local code of the tag's i-th code) and the set of its local codes.  Wave-uniform.
+template <int NT>
+__device__ __forceinline__ void tag_setup(const MkpLayout* lay, int tb, int n_tags, int b0, uint32_t (&t_nc)[NT], uint32_t (&tmu)[NT],
+    uint32_t (&codes_t)[NT]) {
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    t_nc[t] = 0; tmu[t] = 0; codes_t[t] = 0;
+    if (t < n_tags) {
+      t_nc[t] = rfl_u(lay->tags[tb + t].n_codes);
+      tmu[t] = rfl_u(lay->tagmap[tb + t][b0]);
+      for (uint32_t i = 0; i < t_nc[t]; i++) codes_t[t] |= 1u << ((tmu[t] >> (4 + 4 * i)) & 15u);
+    }
+  }
+}
+
+__device__ __forceinline__ bool read_trimmable(const MkpRunParams& prm, uint32_t L) {   // read_can_be_trimmed (mod_bam.rs:1668-1671)
+  return !prm.edge_filter || !(L <= prm.edge_start || L <= prm.edge_end);
+}
+__device__ __forceinline__ bool collapse_on(const MkpRunParams& prm) { return prm.numeric_mode == 2; }
+// --edge-filter on the forward (as-sequenced) position f of a call
+__device__ __forceinline__ bool edge_keep(const MkpRunParams& prm, uint32_t f, uint32_t L) {
+  return !prm.edge_filter || (prm.edge_inverted ? (f < prm.edge_start || f >= L - prm.edge_end) : (f >= prm.edge_start && f < L - prm.edge_end));
+}
+// SeqPosBaseModProbs::filter_positions (read_ids_to_base_mod_probs.rs:966-1070); strand = the strand the call is tallied on
+__device__ __forceinline__ bool sample_keep(const MkpRunParams& prm, const uint8_t* __restrict__ bedmask, bool mapped, int32_t rpos, uint32_t strand) {
+  bool keep = !prm.only_mapped || mapped;
+  if (prm.has_focus) keep = keep && mapped && rpos >= prm.win_start && rpos < prm.win_end && ((bedmask[rpos - prm.win_start] >> strand) & 1u);
+  return keep;
+}
+// Which hit pattern of its group a call falls under: the members whose tags list it (SH) or, listed by none, the group's
+// implicit-mode members, every occurrence of whose base is a call (implicit fill, mod_bam.rs:1265-1292).  False = no call here.
+__device__ __forceinline__ bool call_pattern(uint32_t SH, uint32_t impl, bool& err, int& pat, uint32_t& members) {
+  if (SH) { if (impl & ~SH) err = true; pat = (int)SH; members = SH; return true; }   // ExplicitConflictInferred
+  pat = MKP_PAT_INFERRED; members = impl;
+  return impl != 0u;
+}
+// counter id of a call: cls as call_group returns it
+__device__ __forceinline__ uint32_t call_cid(const GroupRegs& g, int cls) {
+  return cls == 0 ? (uint32_t)MKP_C_FAIL : cls == 1 ? MKP_G_CIDCAN(g.misc) : ((g.cids >> (8 * (cls - 2))) & 0xffu);
+}
+// the tags (bit per tag index) behind a set of group members
+__device__ __forceinline__ uint32_t member_tagbits(uint32_t members, uint32_t member_tags) {
+  uint32_t tagbits = 0;
+#pragma unroll
+  for (int mi = 0; mi < MKP_MAX_MEMBERS; mi++) if (members & (1u << mi)) tagbits |= 1u << ((member_tags >> (4 * mi)) & 15u);
+  return tagbits;
+}
+// InvalidImplicitMode: a group all of whose contributing tags have no mode character (read_cache.rs:122-137)
+__device__ __forceinline__ bool lacks_mode(uint32_t tagbits, uint32_t default_mask) { return tagbits && (tagbits & ~default_mask) == 0; }
+// a delta list must not run past the last occurrence of its base / the end of the read: every entry must have been consumed
+// by the join (mod_bam.rs:705-727, 750-756).  Reverse reads consume their list from its end.
+__device__ __forceinline__ bool list_left_over(bool rev, uint32_t cur, uint32_t n) { return rev ? (cur != 0u) : (cur != n); }
+
+// What a read's calls add up to.  Per-lane while the read is walked; read_epilogue reduces it over the wave.
+struct ReadAcc { bool err = false, any_surviving = false; uint32_t obs0 = 0, obs1 = 0, n_ev = 0; };
+
+// Reference position through a 64-op CIGAR window held in registers, one op per lane, advanced as the walk moves along the read
+// (aligned pairs: M/=/X only, util.rs:122-145).  Per op the inclusive query end and (reference start - query start): rpos = q + dl.
+struct CigarWin { uint32_t c0 = 0, wq0 = 0, wq1 = 0; int32_t wr0; uint32_t w_op = 5u, w_qe = 0; int32_t w_dl = 0; uint32_t w_rtot = 0; bool loaded = false; };
+// maps the query positions q of the lanes with `pending`; positions ascend from call to call, none lies before the window
+__device__ __forceinline__ void cigar_map(CigarWin& w, const MkpReadHdr& h, const uint32_t* __restrict__ cigar, bool pending, uint32_t q,
+    bool& mapped, int32_t& rpos) {
+  const int lane = lane_id();
+  for (;;) {
+    if (!w.loaded || (__any(pending && q >= w.wq1) && !__any(pending && q < w.wq1))) {   // load / advance the window
+      if (w.loaded) { w.c0 += 64; w.wq0 = w.wq1; w.wr0 += (int32_t)w.w_rtot; }
+      if (w.c0 >= h.n_cigar) break;
+      const uint32_t cw = (w.c0 + lane < h.n_cigar) ? cigar[h.cigar_off + w.c0 + lane] : 5u /*0H*/;
+      w.w_op = cw & 15u; const uint32_t len = cw >> 4;
+      const uint32_t qlen = op_consumes_query(w.w_op) ? len : 0u, rlen = op_consumes_ref(w.w_op) ? len : 0u;
+      w.w_qe = wave_incl_scan(qlen); const uint32_t re = wave_incl_scan(rlen);
+      w.w_dl = (w.wr0 + (int32_t)(re - rlen)) - (int32_t)(w.wq0 + w.w_qe - qlen);
+      w.wq1 = w.wq0 + (uint32_t)__builtin_amdgcn_readlane((int)w.w_qe, 63); w.w_rtot = (uint32_t)__builtin_amdgcn_readlane((int)re, 63);
+      w.loaded = true;
+      continue;
+    }
+    const bool ready = pending && q < w.wq1;
+    const int oi = find_op(w.w_qe, ready ? q - w.wq0 : 0u) & 63;
+    const uint32_t my_op = __shfl(w.w_op, oi, 64);
+    const int32_t my_dl = __shfl(w.w_dl, oi, 64);
+    if (ready) { mapped = op_is_match(my_op); rpos = (int32_t)q + my_dl; pending = false; }
+    if (!__any(pending)) break;
+  }
+}
+
+// Call queue of the single-group decoders (N SoA columns of `stride` entries in LDS): move the (< 64) unconsumed entries to the front
+template <int N> __device__ __forceinline__ void queue_to_front(uint32_t* __restrict__ q, uint32_t stride, uint32_t& qhead, uint32_t& qcount) {
+  const uint32_t lane = (uint32_t)lane_id(), n_left = qcount - qhead;
+  const bool mv = lane < n_left;
+  uint32_t v[N];
+#pragma unroll
+  for (int c = 0; c < N; c++) v[c] = mv ? q[c * stride + qhead + lane] : 0u;
+  wave_lds_sync();
+#pragma unroll
+  for (int c = 0; c < N; c++) if (mv) q[c * stride + lane] = v[c];
+  qcount = n_left; qhead = 0;
+}
+
+// The ML bytes of one queued call per lane (up to MKP_KMAX per tag; get_base_mod_probs, mod_bam.rs:1242-1263: stride = #codes of
+// the tag).  Requested first and converted after the CIGAR mapping, whose latency they overlap.  found[t]: tag t lists the
+// lane's call, as its jx[t]-th.
+template <int NT>
+__device__ __forceinline__ void ml_prefetch(const uint8_t* __restrict__ ml, int n_tags, const uint32_t (&t_ml)[NT], const uint32_t (&t_nc)[NT],
+    const bool (&found)[NT], const uint32_t (&jx)[NT], uint32_t (&mlq)[NT][MKP_KMAX]) {
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+#pragma unroll
+    for (int i = 0; i < MKP_KMAX; i++) mlq[t][i] = 0;
+    if (t < n_tags) {
+      const uint32_t nc = t_nc[t], base = found[t] ? (t_ml[t] + jx[t] * nc) : 0u;
+#pragma unroll
+      for (int i = 0; i < MKP_KMAX; i++) if ((uint32_t)i < nc) mlq[t][i] = ml[base + (found[t] ? (uint32_t)i : 0u)];
+    }
+  }
+}
+// ... and the call's probability map from them.  `check` (two or more tags list the call) asks for combine_checked's sum test
+// over the local codes `setmask`, once on the final map (partial sums of positive terms cannot exceed it); true = it failed.
+template <int NT>
+__device__ __forceinline__ bool ml_to_probs(const uint32_t (&mlq)[NT][MKP_KMAX], int n_tags, const uint32_t (&t_nc)[NT], const uint32_t (&tmu)[NT],
+    const bool (&found)[NT], uint32_t setmask, bool check, F4& pk) {
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    if (t >= n_tags) break;
+#pragma unroll
+    for (int i = 0; i < MKP_KMAX; i++) {
+      if ((uint32_t)i >= t_nc[t]) break;
+      const float p = ((float)mlq[t][i] + 0.5f) / 256.0f;   // quals_to_probs (mod_bam.rs:808-816)
+      const uint32_t kk = (tmu[t] >> (4 + 4 * i)) & 15u;     // wave-uniform local code
+      setk(pk, kk, found[t], p);
+    }
+  }
+  if (NT == 1) return false;
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < MKP_KMAX; k++) if (setmask & (1u << k)) s = s + at(pk, k);
+  return check && s > 1.01f;
+}
+
+// One call of a single-group decoder (group g, descriptor words at gp, on base b0 / mod strand sg0): SH = the members whose
+// tags list it, impl = the group's implicit-mode members, pk = its probabilities, f / rpos = its forward and reference
+// positions.  True = the lane has an event (info, position in rpos, sample value in sv).  INFER = false: the group has no
+// implicit members (impl is not looked at), so SH is never empty.
+template <bool SAMPLE, bool INFER>
+__device__ __forceinline__ bool classify_call(const MkpRunParams& prm, const uint8_t* __restrict__ bedmask, const GroupRegs& g,
+    const uint32_t* gp, int kcodes, int b0, int sg0, uint32_t aln, uint32_t L, bool trimmable, uint32_t SH, uint32_t impl, F4& pk,
+    uint32_t f, bool mapped, int32_t& rpos, ReadAcc& acc, uint32_t& contribH, uint32_t& ev_info, float& sv) {
+  int pat = (int)SH; uint32_t member_contrib = SH;
+  if (INFER) call_pattern(SH, impl, acc.err, pat, member_contrib);   // the caller saw to SH | impl
+  const uint32_t pv = gp[12 + pat];
+  contribH |= member_contrib;
+  if (!trimmable || !edge_keep(prm, f, L)) return false;
+  const bool collapse = collapse_on(prm);
+  const uint32_t tally = aln ^ (uint32_t)sg0;  // read_cache.rs:181-188 / FeatureVector::add_feature
+  uint32_t ob = 0;
+  if (SAMPLE) {
+    if (!sample_keep(prm, bedmask, mapped, rpos, tally)) return false;
+    acc.any_surviving = true;
+    if (prm.sample_mode < 2) { sv = argmax_group(g, pv, pk, collapse, kcodes); ev_info = MKP_G_TB(g.misc); return true; }
+    // 2 `summary`: thresholded + argmax class; 3 `extract calls`: + forward position, mod strand, inferred, call_prob
+    if (prm.sample_mode == 3 && ((pv >> 3) & 7u) == 0u) return false;   // the collapse left no code in the map: no profile row
+    float am = 0.f;
+    ev_info = summary_info(g, pv, pk, collapse, &ob, kcodes, &am); acc.obs0 |= ob;
+    if (prm.sample_mode == 3) { ev_info |= ((uint32_t)sg0 << 2) | ((INFER && pat == MKP_PAT_INFERRED ? 1u : 0u) << 3); sv = am; rpos = (int32_t)f; }
+    return true;
+  }
+  acc.any_surviving = true;
+  const int cls = call_group(g, pv, pk, collapse, &ob, kcodes);
+  if (tally) acc.obs1 |= ob; else acc.obs0 |= ob;
+  if (mapped) ev_info = call_cid(g, cls) | (tally << 8) | ((uint32_t)b0 << 9) | (aln << 11) | (1u << 12);
+  return mapped;
+}
+
+// Ballot-compacted, position-ordered append of one batch's events, up to N per lane (cnt of them, all at pos), to the read's
+// event slice [ev_base, ev_base + ev_cap).  A slice too small is an error of the run (ERR_EVENT_CAP) and of the read.
+template <bool SAMPLE, int N>
+__device__ __forceinline__ void append_events(MkpEvent* __restrict__ events, float* __restrict__ sample_vals, uint32_t* __restrict__ dev_err,
+    uint32_t ev_base, uint32_t ev_cap, uint32_t cnt, uint32_t pos, const uint32_t (&info)[N], const float (&sv)[N], ReadAcc& acc) {
+  uint32_t step_total = 0, off = acc.n_ev;
+#pragma unroll
+  for (int k = 0; k < N; k++) {
+    const unsigned long long b = __ballot(cnt > (uint32_t)k);
+    step_total += (uint32_t)__popcll(b); off += (uint32_t)__popcll(b & lanemask_lt());
+  }
+  if (!step_total) return;
+  if (acc.n_ev + step_total > ev_cap) { acc.err = true; if (lane_id() == 0) atomicOr(dev_err, ERR_EVENT_CAP); }
+  else {
+#pragma unroll
+    for (int k = 0; k < N; k++) if ((uint32_t)k < cnt) {
+      MkpEvent ev; ev.pos = pos; ev.info = info[k]; events[ev_base + off + k] = ev;
+      if (SAMPLE) sample_vals[ev_base + off + k] = sv[k];
+    }
+  }
+  acc.n_ev += step_total;
+}
+
+// Read epilogue: the wave agrees on the outcome and lane 0 writes the read's summary.  ok = 1: decoded, with n_ev events;
+// ok = 2 (idle_ok: a duplex half): this group added nothing (all of it edge-filtered) — the record still stands if the other group did.
+__device__ __forceinline__ void read_epilogue(MkpReadOut* __restrict__ readout, uint32_t ro_idx, ReadAcc acc, bool idle_ok) {
+  const bool err = __any(acc.err), any_surviving = __any(acc.any_surviving);
+  MkpReadOut out; out.n_events = 0; out.ok = 0; out.obs[0] = 0; out.obs[1] = 0;
+  if (!err && any_surviving) { out.ok = 1; out.n_events = acc.n_ev; out.obs[0] = wave_or(acc.obs0); out.obs[1] = wave_or(acc.obs1); }
+  else if (!err && idle_ok) out.ok = 2;
+  if (lane_id() == 0) readout[ro_idx] = out;
+}
+
+
+// ----------------------------------------------------------------------------------------------
+// Decode, general layouts.  One wave per read.  The read is walked 512 bases at a time (one SEQ dword = 8 bases per lane):
 //   1. per lane: match masks of the stored bases the read's MM tags count, popcounts, wave prefix sums
 //      (DeltaListConverter's cumulative counts, mod_bam.rs:667-684, 8 bases per instruction);
 //   2. per tag: the calls whose rank falls into the chunk's rank window are located (prefix search + select)
@@ -54,22 +307,11 @@ __device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ 
                  const uint8_t* __restrict__ bedmask, float* __restrict__ sample_vals, const uint32_t* __restrict__ read_ids,
                      uint32_t* __restrict__ lds_layouts, uint32_t (*__restrict__ lds_marks)[64], const uint8_t* __restrict__ pdep4) {
   const int lane = lane_id();
-  // wave-uniform values are made provably uniform (readfirstlane) so they live in SGPRs and load through the scalar cache
-  const uint32_t wib = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t widx = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6))) + wib;
-  if (widx >= n_reads) return;
-  const uint32_t rid = (uint32_t)__builtin_amdgcn_readfirstlane((int)read_ids[widx]);
-  const MkpReadHdr h = hdrs[rid];
-  MkpReadOut out; out.n_events = 0; out.ok = 0; out.obs[0] = 0; out.obs[1] = 0;
-  if ((h.flags & MKP_RF_BAD) || h.n_tags == 0) { if (lane == 0) readout[rid] = out; return; }
-  // the read's layout (1216 B) goes to LDS once; every table lookup below is an LDS read
+  uint32_t wib, rid; MkpReadHdr h; uint32_t* lds_lay;
+  if (!read_prologue(hdrs, n_reads, read_ids, layouts, readout, lds_layouts, ~0u, wib, rid, h, lds_lay)) return;
   constexpr int NB = NT < 4 ? NT : 4;   // distinct stored bases the tags can count
-  uint32_t* __restrict__ lds_lay = lds_layouts + wib * MKP_LAYOUT_DWORDS;
   uint32_t* __restrict__ ordb = &lds_marks[wib * 7][0];                        // [NT][18] ordinal / position bitmaps of the chunk
   uint16_t* __restrict__ slots = reinterpret_cast<uint16_t*>(ordb + 192);                 // 512 compacted {lane, bit} entries
-  { const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(&layouts[h.layout]);
-    for (int i = lane; i < MKP_LAYOUT_DWORDS; i += 64) lds_lay[i] = src[i]; }
-  __builtin_amdgcn_wave_barrier();
   const MkpLayout* lay = reinterpret_cast<const MkpLayout*>(lds_lay);
   const uint32_t* __restrict__ seqw = reinterpret_cast<const uint32_t*>(seqs + h.seq_off);  // reads start 4-byte aligned
   const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
@@ -133,21 +375,14 @@ __device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ 
 #pragma unroll
     for (int j = 0; j < NB; j++) if ((uint32_t)j < nb) tot[j] = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(acc[j]), 63);
   }
-  bool err = false;
-  const bool trimmable = !prm.edge_filter || !(L <= prm.edge_start || L <= prm.edge_end);  // read_can_be_trimmed (mod_bam.rs:1668-1671)
-  const bool collapse = prm.numeric_mode == 2;
-
-  uint32_t obs0 = 0, obs1 = 0, contrib_lo = 0, contrib_hi = 0;  // contrib: 8 groups x 8 tag bits
-  bool any_surviving = false;
-  uint32_t n_ev = 0;
+  ReadAcc acc; bool& err = acc.err;
+  const bool trimmable = read_trimmable(prm, L), collapse = collapse_on(prm);
+  uint32_t contrib_lo = 0, contrib_hi = 0;  // contrib: 8 groups x 8 tag bits
   uint32_t cum[NB];
 #pragma unroll
   for (int j = 0; j < NB; j++) cum[j] = 0;
   uint32_t x_next = (uint32_t)lane < nd ? seqw[lane] : 0u;   // the next step's SEQ dword is always in flight
-  // CIGAR window: 64 ops in registers, advanced as the walk moves along the read
-  uint32_t c0 = 0, wq0 = 0, wq1 = 0; int32_t wr0 = h.ref_start;
-  uint32_t w_op = 5u, w_qe = 0, w_qs = 0; int32_t w_rs = 0; uint32_t w_rtot = 0;
-  bool win_loaded = false;
+  CigarWin win; win.wr0 = h.ref_start;
 
   for (uint32_t d0 = 0; d0 < nd && !err; d0 += 64) {
     const uint32_t d = d0 + lane;
@@ -173,7 +408,10 @@ __device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ 
     // ---- 2. mark the calls of every tag that fall into this chunk
 #pragma unroll
     for (int t = 0; t < NT; t++) {
-      if (t >= n_tags || (prm.debug_skip & 32u)) break;
+      if (t >= n_tags) break;
+#ifdef MKP_DEBUG
+      if (prm.debug_skip & 32u) break;   // ablation: no calls marked
+#endif
       const MkpTagDesc dsc = t_desc[t];
       const uint32_t sj = tslot[t];
       uint32_t wlo, whi;   // window of keys this chunk can ask for (windows of successive chunks tile the key space)
@@ -194,9 +432,7 @@ __device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ 
         if (nh < 64) break;
       }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     uint32_t pack_t[NT];
 #pragma unroll
     for (int t = 0; t < NT; t++) {
@@ -220,11 +456,12 @@ __device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ 
     // compaction: every lane writes {lane, bit} of its called positions into the wave's slot list, in read order
     { uint32_t ut = U, sidx = uincl - ucnt;
       while (ut) { slots[sidx++] = (uint16_t)(((uint32_t)lane << 3) | ((uint32_t)__ffs((int)ut) - 1u)); ut &= ut - 1u; } }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     // ---- 3. the called positions, 64 per batch, in read order
-    for (uint32_t g0 = 0; g0 < H && !err && !(prm.debug_skip & 16u); g0 += 64) {
+    for (uint32_t g0 = 0; g0 < H && !err; g0 += 64) {
+#ifdef MKP_DEBUG
+      if (prm.debug_skip & 16u) break;   // ablation: producer only
+#endif
       const uint32_t g = g0 + lane;
       const bool active = g < H;
       const uint32_t slot = active ? (uint32_t)slots[g] : 0u;
@@ -266,36 +503,12 @@ __device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ 
         if (dsc.neg) { if (merge_tag(S1, ts, seen, mi)) err = true; } else { if (merge_tag(S0, ts, seen, mi)) err = true; }
       }
       }
-      // reference position through the CIGAR window (aligned pairs: M/=/X only, util.rs:122-145)
+      // reference position of the call's base (CigarWin)
       bool mapped = false; int32_t rpos = 0;
-      {
-        bool pending = active && x >= 0;
-        for (;;) {
-          if (!win_loaded || (__any(pending && q >= wq1) && !__any(pending && q < wq1))) {
-            // load / advance the window
-            if (win_loaded) { c0 += 64; wq0 = wq1; wr0 += (int32_t)w_rtot; }
-            if (c0 >= h.n_cigar) break;
-            const uint32_t w = (c0 + lane < h.n_cigar) ? cigar[h.cigar_off + c0 + lane] : 5u /*0H*/;
-            w_op = w & 15u; const uint32_t len = w >> 4;
-            const uint32_t qlen = op_consumes_query(w_op) ? len : 0u, rlen = op_consumes_ref(w_op) ? len : 0u;
-            w_qe = wave_incl_scan(qlen); const uint32_t re = wave_incl_scan(rlen);
-            w_qs = wq0 + w_qe - qlen; w_rs = wr0 + (int32_t)(re - rlen);
-            wq1 = wq0 + (uint32_t)__builtin_amdgcn_readlane((int)w_qe, 63); w_rtot = (uint32_t)__builtin_amdgcn_readlane((int)re, 63);
-            win_loaded = true;
-            continue;
-          }
-          const bool ready = pending && q < wq1;
-          const int oi = find_op(w_qe, ready ? q - wq0 : 0u) & 63;
-          const uint32_t my_qs = __shfl(w_qs, oi, 64), my_op = __shfl(w_op, oi, 64);
-          const int32_t my_rs = __shfl(w_rs, oi, 64);
-          if (ready) { mapped = op_is_match(my_op); rpos = my_rs + (int32_t)(q - my_qs); pending = false; }
-          if (!__any(pending)) break;
-        }
-      }
+      cigar_map(win, h, cigar, active && x >= 0, q, mapped, rpos);
       uint32_t ev_info[2]; float sv[2] = {0.f, 0.f}; uint32_t ev_cnt = 0; int32_t ev_pos = 0;
       if (active && x >= 0) {
-        const bool edge_keep = !prm.edge_filter ||
-            (prm.edge_inverted ? (f < prm.edge_start || f >= L - prm.edge_end) : (f >= prm.edge_start && f < L - prm.edge_end));
+        const bool keep_edge = edge_keep(prm, f, L);
         bool dec_done = false;
 #pragma unroll
         for (int sg = 0; sg < 2; sg++) {
@@ -306,91 +519,56 @@ __device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ 
           F4& spk = sg ? S1.pk : S0.pk;
           const uint32_t SH = sg ? S1.H : S0.H;
           const uint32_t impl = MKP_G_IMPL(gmisc);
-          int pat;
-          uint32_t member_contrib;
-          if (SH) {
-            if (impl & ~SH) err = true;  // ExplicitConflictInferred
-            pat = (int)SH; member_contrib = SH;
-          } else if (impl) {
-            pat = MKP_PAT_INFERRED; member_contrib = impl;  // implicit fill (mod_bam.rs:1265-1292)
-          } else continue;
+          int pat; uint32_t member_contrib;
+          if (!call_pattern(SH, impl, err, pat, member_contrib)) continue;
           const GroupRegs gr = load_group(gp);
           const uint32_t pv = gp[12 + pat];
-          uint32_t tagbits = 0;
-#pragma unroll
-          for (int mi = 0; mi < MKP_MAX_MEMBERS; mi++) if (member_contrib & (1u << mi)) tagbits |= 1u << ((gr.member_tags >> (4 * mi)) & 15u);
+          const uint32_t tagbits = member_tagbits(member_contrib, gr.member_tags);
           const int gi = sg * 4 + b;
           if (gi < 4) contrib_lo |= tagbits << (8 * gi); else contrib_hi |= tagbits << (8 * (gi - 4));
-          if (!trimmable || !edge_keep) continue;
-          if (SAMPLE) {  // SeqPosBaseModProbs::filter_positions (read_ids_to_base_mod_probs.rs:966-1070)
-            bool keep = !prm.only_mapped || mapped;
-            if (prm.has_focus) keep = keep && mapped && rpos >= prm.win_start && rpos < prm.win_end
-                && ((bedmask[rpos - prm.win_start] >> (aln ^ (uint32_t)sg)) & 1u);
-            if (!keep) continue;
-            any_surviving = true;
+          if (!trimmable || !keep_edge) continue;
+          const uint32_t tally = aln ^ (uint32_t)sg;  // read_cache.rs:181-188 / FeatureVector::add_feature
+          if (SAMPLE) {
+            if (!sample_keep(prm, bedmask, mapped, rpos, tally)) continue;
+            acc.any_surviving = true;
             // 2 `summary`: thresholded + argmax class; 3 `extract calls`: + forward position, mod strand, inferred, call_prob
             if (prm.sample_mode >= 2) {
               // the collapse left no code in the map: no profile row (iter_probs is empty)
               if (prm.sample_mode == 3 && ((pv >> 3) & 7u) == 0u) continue;
               uint32_t ob = 0; float am = 0.f; uint32_t inf = summary_info(gr, pv, spk, collapse, &ob, MKP_KMAX, &am);
               if (prm.sample_mode == 3) { inf |= ((uint32_t)sg << 2) | ((pat == MKP_PAT_INFERRED ? 1u : 0u) << 3); ev_pos = (int32_t)f; }
-              sv[ev_cnt] = prm.sample_mode == 3 ? am : 0.f; ev_info[ev_cnt++] = inf; obs0 |= ob; continue;
+              sv[ev_cnt] = prm.sample_mode == 3 ? am : 0.f; ev_info[ev_cnt++] = inf; acc.obs0 |= ob; continue;
             }
             sv[ev_cnt] = argmax_group(gr, pv, spk, collapse);
             ev_info[ev_cnt++] = MKP_G_TB(gr.misc);
             continue;
           }
-          any_surviving = true;
+          acc.any_surviving = true;
           uint32_t ob = 0;
           const int cls = call_group(gr, pv, spk, collapse, &ob);
-          const uint32_t tally = aln ^ (uint32_t)sg;  // read_cache.rs:181-188 / FeatureVector::add_feature
-          if (tally) obs1 |= ob; else obs0 |= ob;
+          if (tally) acc.obs1 |= ob; else acc.obs0 |= ob;
           if (mapped) {
-            const uint32_t cid = cls == 0 ? (uint32_t)MKP_C_FAIL : cls == 1 ? MKP_G_CIDCAN(gr.misc) : ((gr.cids >> (8 * (cls - 2))) & 0xffu);
-            ev_info[ev_cnt++] = cid | (tally << 8) | ((uint32_t)b << 9) | (aln << 11) | (dec_done ? 0u : (1u << 12));
+            ev_info[ev_cnt++] = call_cid(gr, cls) | (tally << 8) | ((uint32_t)b << 9) | (aln << 11) | (dec_done ? 0u : (1u << 12));
             dec_done = true;
             ev_pos = rpos;
           }
         }
       }
-      // ballot-compacted, position-ordered append of this batch's events
-      unsigned long long b1 = __ballot(ev_cnt >= 1), b2 = __ballot(ev_cnt >= 2);
-      uint32_t step_total = (uint32_t)__popcll(b1) + (uint32_t)__popcll(b2);
-      if (step_total) {
-        unsigned long long mlt = lanemask_lt();
-        uint32_t off = n_ev + (uint32_t)__popcll(b1 & mlt) + (uint32_t)__popcll(b2 & mlt);
-        if (n_ev + step_total > h.event_cap) { err = true; if (lane == 0) atomicOr(dev_err, ERR_EVENT_CAP); }
-        else for (uint32_t e2 = 0; e2 < ev_cnt; e2++) {
-          MkpEvent ev; ev.pos = (uint32_t)ev_pos; ev.info = ev_info[e2]; events[h.event_off + off + e2] = ev;
-          if (SAMPLE) sample_vals[h.event_off + off + e2] = sv[e2];
-        }
-        n_ev += step_total;
-      }
+      append_events<SAMPLE, 2>(events, sample_vals, dev_err, h.event_off, h.event_cap, ev_cnt, (uint32_t)ev_pos, ev_info, sv, acc);
       err = __any(err);
     }
 #pragma unroll
     for (int j = 0; j < NB; j++) cum[j] += cnt[j];
     err = __any(err);
   }
-  // a delta list must not run past the last occurrence of its base / the end of the read: every entry must have
-  // been consumed by the join (mod_bam.rs:705-727, 750-756)
 #pragma unroll
-  for (int t = 0; t < NT; t++) if (t < n_tags) { if (rev ? (t_cur[t] != 0u) : (t_cur[t] != t_n[t])) err = true; }
-  err = __any(err);
-  obs0 = wave_or(obs0); obs1 = wave_or(obs1);
-  contrib_lo = wave_or(contrib_lo); contrib_hi = wave_or(contrib_hi);
-  any_surviving = __any(any_surviving);
-  // InvalidImplicitMode: a group all of whose contributing tags have no mode character (read_cache.rs:122-137)
-  if (!prm.force_allow && !SAMPLE) {
-    for (int gi = 0; gi < 8; gi++) {
-      uint32_t m = ((gi < 4 ? contrib_lo >> (8 * gi) : contrib_hi >> (8 * (gi - 4)))) & 0xffu;
-      if (m && (m & ~(uint32_t)lay->default_mask) == 0) err = true;
-    }
+  for (int t = 0; t < NT; t++) if (t < n_tags && list_left_over(rev, t_cur[t], t_n[t])) err = true;
+  if (!prm.force_allow && !SAMPLE) {   // InvalidImplicitMode, per group
+    contrib_lo = wave_or(contrib_lo); contrib_hi = wave_or(contrib_hi);
+    for (int gi = 0; gi < 8; gi++)
+      if (lacks_mode(((gi < 4 ? contrib_lo >> (8 * gi) : contrib_hi >> (8 * (gi - 4)))) & 0xffu, lay->default_mask)) err = true;
   }
-  if (lane == 0) {
-    if (!err && any_surviving) { out.ok = 1; out.n_events = n_ev; out.obs[0] = obs0; out.obs[1] = obs1; }
-    readout[rid] = out;
-  }
+  read_epilogue(readout, rid, acc, false);
 }
 
 
@@ -398,8 +576,8 @@ __device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ 
 // Decode, FAST layouts (MkpLayout::fast: every tag on the same specific base and mod strand, no code listed twice —
 // `C+m?`, `C+hm?`, `C+h?;C+m?`, ...; NT <= 2 tags).  Same semantics as decode_read_body, restructured as a
 // producer/consumer inside the wave: the 1024-base steps (16 bases per lane) only *locate* calls and append {stored position, ML index per
-// tag} to a queue in LDS; whenever 64 calls are queued one full batch runs the per-call work (ML -> f32, collapse,
-// threshold caller, CIGAR mapping, event append).  With CpG data a step finds ~13 calls, so batches run at full
+// tag} to a queue in LDS; whenever 64 calls are queued one full batch runs the per-call work: ml_prefetch, cigar_map,
+// ml_to_probs, classify_call<SAMPLE, INFER = true>, append_events.  With CpG data a step finds ~13 calls, so batches run at full
 // lane occupancy instead of ~20 %.  The group descriptor, thresholds and code maps are wave-uniform (SGPRs).
 #define MKP_QCAP 576   // 63 left over + up to 512 from half a step (32 lanes x 16 bases)
 #define MKP_ORD_WORDS 34   // ordinal bitmap of a 1024-base step: 32 words + 2 for the 64-bit window read
@@ -413,22 +591,13 @@ __device__ __forceinline__ void decode_read_fast(const MkpReadHdr* __restrict__ 
                      uint32_t* __restrict__ lds_queue) {
   static_assert(NT <= 2, "the call queue holds two ML indices per entry");
   const int lane = lane_id();
-  const uint32_t wib = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t widx = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6))) + wib;
-  if (widx >= n_reads) return;
-  const uint32_t rid = (uint32_t)__builtin_amdgcn_readfirstlane((int)read_ids[widx]);
-  const MkpReadHdr h = hdrs[rid];
-  MkpReadOut out; out.n_events = 0; out.ok = 0; out.obs[0] = 0; out.obs[1] = 0;
-  if ((h.flags & MKP_RF_BAD) || h.n_tags == 0) { if (lane == 0) readout[rid] = out; return; }
-  uint32_t* __restrict__ lds_lay = lds_layouts + wib * MKP_LAYOUT_DWORDS;
+  uint32_t wib, rid; MkpReadHdr h; uint32_t* lds_lay;
+  if (!read_prologue(hdrs, n_reads, read_ids, layouts, readout, lds_layouts, ~0u, wib, rid, h, lds_lay)) return;
   uint32_t* __restrict__ ordb = lds_ord + wib * (NT * MKP_ORD_WORDS);   // [NT][MKP_ORD_WORDS] ordinal bitmaps of the step
   // queue, SoA: stored position, ML call index of tag 0 / 1 (~0 = not listed)
   uint32_t* __restrict__ q_pos = lds_queue + wib * ((1 + NT) * MKP_QCAP);
   uint32_t* __restrict__ q_j0 = q_pos + MKP_QCAP;
   uint32_t* __restrict__ q_j1 = q_pos + (NT > 1 ? 2 : 1) * MKP_QCAP;
-  { const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(&layouts[h.layout]);
-    for (int i = lane; i < MKP_LAYOUT_DWORDS; i += 64) lds_lay[i] = src[i]; }
-  __builtin_amdgcn_wave_barrier();
   const MkpLayout* lay = reinterpret_cast<const MkpLayout*>(lds_lay);
   const uint32_t* __restrict__ seqw = reinterpret_cast<const uint32_t*>(seqs + h.seq_off);
   const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
@@ -437,26 +606,15 @@ __device__ __forceinline__ void decode_read_fast(const MkpReadHdr* __restrict__ 
   const int b0 = (int)lay->tags[0].fb & 3, sg0 = (int)lay->tags[0].neg & 1;
   const int xs = rev ? 3 - b0 : b0;                                   // the stored base the tags count
   const uint32_t* gp0 = lds_lay + MKP_LAYOUT_GROUP_DW + (sg0 * 4 + b0) * 32;
-  GroupRegs grp0 = load_group(gp0);
-  grp0.misc = (uint32_t)__builtin_amdgcn_readfirstlane((int)grp0.misc); grp0.slots = (uint32_t)__builtin_amdgcn_readfirstlane((int)grp0.slots);
-  grp0.cids = (uint32_t)__builtin_amdgcn_readfirstlane((int)grp0.cids);
-    grp0.member_tags = (uint32_t)__builtin_amdgcn_readfirstlane((int)grp0.member_tags);
-#pragma unroll
-  for (int kq = 0; kq < MKP_KMAX; kq++) at(grp0.thr,
-      kq) = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(at(grp0.thr, kq))));
-  grp0.thr_can = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(grp0.thr_can)));
+  const GroupRegs grp0 = load_group_uniform(gp0);
   const uint32_t impl0 = MKP_G_IMPL(grp0.misc);
   const int kcodes0 = (int)((grp0.misc >> 20) & 7u);   // codes of the group: bounds every per-code loop
   uint32_t t_off[NT], t_n[NT], t_ml[NT], t_cur[NT], t_nc[NT], tmu[NT], codes_t[NT];
+  tag_setup<NT>(lay, 0, n_tags, b0, t_nc, tmu, codes_t);
 #pragma unroll
   for (int t = 0; t < NT; t++) {
-    t_off[t] = 0; t_n[t] = 0; t_ml[t] = 0; t_cur[t] = 0; t_nc[t] = 0; tmu[t] = 0; codes_t[t] = 0;
-    if (t < n_tags) {
-      const MkpTagRef tr = tagref[h.tag_off + t]; t_off[t] = tr.rank_off; t_n[t] = tr.n; t_ml[t] = tr.ml_off; t_cur[t] = rev ? tr.n : 0u;
-      t_nc[t] = (uint32_t)__builtin_amdgcn_readfirstlane((int)lay->tags[t].n_codes);
-      tmu[t] = (uint32_t)__builtin_amdgcn_readfirstlane((int)lay->tagmap[t][b0]);
-      for (uint32_t i = 0; i < t_nc[t]; i++) codes_t[t] |= 1u << ((tmu[t] >> (4 + 4 * i)) & 15u);
-    }
+    t_off[t] = 0; t_n[t] = 0; t_ml[t] = 0; t_cur[t] = 0;
+    if (t < n_tags) { const MkpTagRef tr = tagref[h.tag_off + t]; t_off[t] = tr.rank_off; t_n[t] = tr.n; t_ml[t] = tr.ml_off; t_cur[t] = rev ? tr.n : 0u; }
   }
   // reverse reads need the total up front (forward rank = total - inclusive count in stored order); 4 loads in flight
   uint32_t tot = 0;
@@ -475,15 +633,10 @@ __device__ __forceinline__ void decode_read_fast(const MkpReadHdr* __restrict__ 
     }
     tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(acc), 63);
   }
-  bool err = false;
-  const bool trimmable = !prm.edge_filter || !(L <= prm.edge_start || L <= prm.edge_end);  // read_can_be_trimmed (mod_bam.rs:1668-1671)
-  const bool collapse = prm.numeric_mode == 2;
-  uint32_t obs0 = 0, obs1 = 0, contribH = 0, n_ev = 0, cum = 0;
-  bool any_surviving = false;
-  // CIGAR window: 64 ops in registers, advanced as the batches move along the read
-  uint32_t c0 = 0, wq0 = 0, wq1 = 0; int32_t wr0 = h.ref_start;
-  uint32_t w_op = 5u, w_qe = 0; int32_t w_dl = 0; uint32_t w_rtot = 0;
-  bool win_loaded = false;
+  ReadAcc acc; bool& err = acc.err;
+  const bool trimmable = read_trimmable(prm, L);
+  uint32_t contribH = 0, cum = 0;
+  CigarWin win; win.wr0 = h.ref_start;
   uint32_t qhead = 0, qcount = 0, d0 = 0;
   // the next step's SEQ dwords (two per lane = 16 bases) are always in flight
   uint32_t x_next0 = 2u * (uint32_t)lane < nd ? seqw[2u * lane] : 0u, x_next1 = 2u * (uint32_t)lane + 1u < nd ? seqw[2u * lane + 1u] : 0u;
@@ -499,14 +652,7 @@ __device__ __forceinline__ void decode_read_fast(const MkpReadHdr* __restrict__ 
     if (err) break;
     if (qcount - qhead < 64u && (pend || d0 < nd)) {
       // ---- producer: one 1024-base step locates its calls; each half of the lanes appends them to the queue
-      if (qhead) {  // move the (< 64) unconsumed entries to the front
-        const uint32_t n_left = qcount - qhead;
-        const bool mv = (uint32_t)lane < n_left;
-        const uint32_t a = mv ? q_pos[qhead + lane] : 0u, b = mv ? q_j0[qhead + lane] : 0u, c = (NT > 1 && mv) ? q_j1[qhead + lane] : 0u;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        if (mv) { q_pos[lane] = a; q_j0[lane] = b; if (NT > 1) q_j1[lane] = c; }
-        qcount = n_left; qhead = 0;
-      }
+      if (qhead) queue_to_front<1 + NT>(q_pos, MKP_QCAP, qhead, qcount);
       if (!pend) {
         const uint32_t d = d0 + 2u * (uint32_t)lane;          // this lane's first dword: bases [8d, 8d+16)
         const uint32_t xl0 = linearize(x_next0), xl1 = linearize(x_next1);
@@ -546,7 +692,7 @@ __device__ __forceinline__ void decode_read_fast(const MkpReadHdr* __restrict__ 
             if (nh < 64) break;
           }
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         uint32_t U = impl0 ? m16 : 0u, uincl = 0, ucnt = 0;
         const uint32_t ex = incl - c;
         const uint32_t n0 = m16 & 15u, n1 = (m16 >> 4) & 15u, n2 = (m16 >> 8) & 15u, n3 = m16 >> 12;
@@ -582,7 +728,7 @@ __device__ __forceinline__ void decode_read_fast(const MkpReadHdr* __restrict__ 
           }
           sidx++; ut &= ut - 1u;
         }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         qcount += pend ? (st_H - st_HA) : st_HA;
         if (!pend && st_H > st_HA) pend = true;                  // the upper lanes still hold calls
         else { pend = false; cum += st_cntT; d0 += 128; }        // step done
@@ -590,143 +736,40 @@ __device__ __forceinline__ void decode_read_fast(const MkpReadHdr* __restrict__ 
       continue;
     }
     if (qcount == qhead) break;
-    if (prm.debug_skip & 16u) { qhead = qcount; continue; }
+#ifdef MKP_DEBUG
+    if (prm.debug_skip & 16u) { qhead = qcount; continue; }   // ablation: producer only
+#endif
     // ---- consumer: up to 64 queued calls, in read order
     const uint32_t nb = min(64u, qcount - qhead);
     const bool active = (uint32_t)lane < nb;
     const uint32_t q = active ? q_pos[qhead + lane] : 0u;
     const uint32_t f = rev ? (L - 1 - q) : q;  // forward (as-sequenced) position
-    // the ML bytes are requested first (up to MKP_KMAX per tag) and converted after the CIGAR mapping, whose latency they overlap
-    uint32_t mlq[NT][MKP_KMAX]; bool found_t[NT];
+    uint32_t mlq[NT][MKP_KMAX], jx[NT]; bool found_t[NT];
 #pragma unroll
     for (int t = 0; t < NT; t++) {
-      found_t[t] = false;
-#pragma unroll
-      for (int i = 0; i < MKP_KMAX; i++) mlq[t][i] = 0;
-      if (t < n_tags) {
-        const uint32_t jx = active ? (t == 0 ? q_j0 : q_j1)[qhead + lane] : 0xffffffffu;
-        found_t[t] = jx != 0xffffffffu;
-        const uint32_t nc = t_nc[t], base = found_t[t] ? (t_ml[t] + jx * nc) : 0u;
-#pragma unroll
-        for (int i = 0; i < MKP_KMAX; i++) if ((uint32_t)i < nc) mlq[t][i] = ml[base + (found_t[t] ? (uint32_t)i : 0u)];
-      }
+      jx[t] = (t < n_tags && active) ? (t == 0 ? q_j0 : q_j1)[qhead + lane] : 0xffffffffu;
+      found_t[t] = jx[t] != 0xffffffffu;
     }
-    // reference position through the CIGAR window (aligned pairs: M/=/X only, util.rs:122-145)
+    ml_prefetch<NT>(ml, n_tags, t_ml, t_nc, found_t, jx, mlq);
     bool mapped = false; int32_t rpos = 0;
-    {
-      bool pending = active;
-      for (;;) {
-        if (!win_loaded || (__any(pending && q >= wq1) && !__any(pending && q < wq1))) {
-          if (win_loaded) { c0 += 64; wq0 = wq1; wr0 += (int32_t)w_rtot; }
-          if (c0 >= h.n_cigar) break;
-          const uint32_t w = (c0 + lane < h.n_cigar) ? cigar[h.cigar_off + c0 + lane] : 5u /*0H*/;
-          w_op = w & 15u; const uint32_t len = w >> 4;
-          const uint32_t qlen = op_consumes_query(w_op) ? len : 0u, rlen = op_consumes_ref(w_op) ? len : 0u;
-          w_qe = wave_incl_scan(qlen); const uint32_t re = wave_incl_scan(rlen);
-          w_dl = (wr0 + (int32_t)(re - rlen)) - (int32_t)(wq0 + w_qe - qlen);   // ref start - query start of the op
-          wq1 = wq0 + (uint32_t)__builtin_amdgcn_readlane((int)w_qe, 63); w_rtot = (uint32_t)__builtin_amdgcn_readlane((int)re, 63);
-          win_loaded = true;
-          continue;
-        }
-        const bool ready = pending && q < wq1;
-        const int oi = find_op(w_qe, ready ? q - wq0 : 0u) & 63;
-        const uint32_t my_op = __shfl(w_op, oi, 64);
-        const int32_t my_dl = __shfl(w_dl, oi, 64);
-        if (ready) { mapped = op_is_match(my_op); rpos = (int32_t)q + my_dl; pending = false; }
-        if (!__any(pending)) break;
-      }
-    }
+    cigar_map(win, h, cigar, active, q, mapped, rpos);
     F4 pk = {0.f, 0.f, 0.f, 0.f};
-    uint32_t SH = 0, setmask = 0;
+    uint32_t SH = 0, setmask = 0;   // the members whose tags list the call, their local codes
 #pragma unroll
-    for (int t = 0; t < NT; t++) {
-      if (t >= n_tags) break;
-      const bool found = found_t[t];
-#pragma unroll
-      for (int i = 0; i < MKP_KMAX; i++) {
-        if ((uint32_t)i >= t_nc[t]) break;
-        const float p = ((float)mlq[t][i] + 0.5f) / 256.0f;   // quals_to_probs (mod_bam.rs:808-816)
-        const uint32_t kk = (tmu[t] >> (4 + 4 * i)) & 15u;   // wave-uniform local code
-        setk(pk, kk, found, p);
-      }
-      SH |= found ? (1u << (tmu[t] & 15u)) : 0u;
-      setmask |= found ? codes_t[t] : 0u;
-    }
-    if (NT > 1 && __popc(SH) >= 2) {  // combine_checked's sum test, once on the final map (partial sums of positive terms cannot exceed it)
-      float s = 0.f;
-#pragma unroll
-      for (int k2 = 0; k2 < MKP_KMAX; k2++) if (setmask & (1u << k2)) s = s + at(pk, k2);
-      if (s > 1.01f) err = true;
-    }
-    uint32_t ev_info = 0; float sv = 0.f; bool has_ev = false;
-    if (active && (SH | impl0)) {
-      const bool edge_keep = !prm.edge_filter ||
-          (prm.edge_inverted ? (f < prm.edge_start || f >= L - prm.edge_end) : (f >= prm.edge_start && f < L - prm.edge_end));
-      int pat; uint32_t member_contrib;
-      if (SH) { if (impl0 & ~SH) err = true; pat = (int)SH; member_contrib = SH; }      // ExplicitConflictInferred
-      else { pat = MKP_PAT_INFERRED; member_contrib = impl0; }                          // implicit fill (mod_bam.rs:1265-1292)
-      const uint32_t pv = gp0[12 + pat];
-      contribH |= member_contrib;
-      if (trimmable && edge_keep) {
-        if (SAMPLE) {  // SeqPosBaseModProbs::filter_positions (read_ids_to_base_mod_probs.rs:966-1070)
-          bool keep = !prm.only_mapped || mapped;
-          if (prm.has_focus) keep = keep && mapped && rpos >= prm.win_start && rpos < prm.win_end
-              && ((bedmask[rpos - prm.win_start] >> (aln ^ (uint32_t)sg0)) & 1u);
-          // `extract calls`: the collapse left no code in the map: no profile row
-          if (keep && prm.sample_mode == 3 && ((pv >> 3) & 7u) == 0u) any_surviving = true;
-          else if (keep && prm.sample_mode >= 2) {
-            any_surviving = true; uint32_t ob = 0; float am = 0.f; ev_info = summary_info(grp0, pv, pk, collapse, &ob, kcodes0, &am); obs0 |= ob;
-              has_ev = true;
-            // `extract calls`: the event carries the forward position
-            if (prm.sample_mode == 3) { ev_info |= ((uint32_t)sg0 << 2) | ((pat == MKP_PAT_INFERRED ? 1u : 0u) << 3); sv = am; rpos = (int32_t)f; }
-          }
-          else if (keep) { any_surviving = true; sv = argmax_group(grp0, pv, pk, collapse, kcodes0); ev_info = MKP_G_TB(grp0.misc); has_ev = true; }
-        } else {
-          any_surviving = true;
-          uint32_t ob = 0;
-          const int cls = call_group(grp0, pv, pk, collapse, &ob, kcodes0);
-          const uint32_t tally = aln ^ (uint32_t)sg0;  // read_cache.rs:181-188 / FeatureVector::add_feature
-          if (tally) obs1 |= ob; else obs0 |= ob;
-          if (mapped) {
-            const uint32_t cid = cls == 0 ? (uint32_t)MKP_C_FAIL : cls == 1 ? MKP_G_CIDCAN(grp0.misc) : ((grp0.cids >> (8 * (cls - 2))) & 0xffu);
-            ev_info = cid | (tally << 8) | ((uint32_t)b0 << 9) | (aln << 11) | (1u << 12);
-            has_ev = true;
-          }
-        }
-      }
-    }
-    // ballot-compacted, position-ordered append of this batch's events
-    const unsigned long long b1 = __ballot(has_ev);
-    const uint32_t step_total = (uint32_t)__popcll(b1);
-    if (step_total) {
-      const uint32_t off = n_ev + (uint32_t)__popcll(b1 & lanemask_lt());
-      if (n_ev + step_total > h.event_cap) { err = true; if (lane == 0) atomicOr(dev_err, ERR_EVENT_CAP); }
-      else if (has_ev) {
-        MkpEvent ev; ev.pos = (uint32_t)rpos; ev.info = ev_info; events[h.event_off + off] = ev;
-        if (SAMPLE) sample_vals[h.event_off + off] = sv;
-      }
-      n_ev += step_total;
-    }
+    for (int t = 0; t < NT; t++) { SH |= found_t[t] ? (1u << (tmu[t] & 15u)) : 0u; setmask |= found_t[t] ? codes_t[t] : 0u; }
+    if (ml_to_probs<NT>(mlq, n_tags, t_nc, tmu, found_t, setmask, __popc(SH) >= 2, pk)) err = true;
+    uint32_t ev_info[1] = {0}; float sv[1] = {0.f}; bool has_ev = false;
+    if (active && (SH | impl0))
+      has_ev = classify_call<SAMPLE, true>(prm, bedmask, grp0, gp0, kcodes0, b0, sg0, aln, L, trimmable, SH, impl0, pk, f, mapped, rpos, acc,
+                                           contribH, ev_info[0], sv[0]);
+    append_events<SAMPLE, 1>(events, sample_vals, dev_err, h.event_off, h.event_cap, has_ev ? 1u : 0u, (uint32_t)rpos, ev_info, sv, acc);
     err = __any(err);
     qhead += nb;
   }
-  // a delta list must not run past the last occurrence of its base: every entry must have been consumed (mod_bam.rs:705-727)
 #pragma unroll
-  for (int t = 0; t < NT; t++) if (t < n_tags) { if (rev ? (t_cur[t] != 0u) : (t_cur[t] != t_n[t])) err = true; }
-  err = __any(err);
-  obs0 = wave_or(obs0); obs1 = wave_or(obs1);
-  any_surviving = __any(any_surviving);
-  // InvalidImplicitMode: the group's contributing tags all lack a mode character (read_cache.rs:122-137)
-  if (!prm.force_allow && !SAMPLE) {
-    const uint32_t mc = wave_or(contribH); uint32_t tagbits = 0;
-#pragma unroll
-    for (int mi = 0; mi < MKP_MAX_MEMBERS; mi++) if (mc & (1u << mi)) tagbits |= 1u << ((grp0.member_tags >> (4 * mi)) & 15u);
-    if (tagbits && (tagbits & ~(uint32_t)lay->default_mask) == 0) err = true;
-  }
-  if (lane == 0) {
-    if (!err && any_surviving) { out.ok = 1; out.n_events = n_ev; out.obs[0] = obs0; out.obs[1] = obs1; }
-    readout[rid] = out;
-  }
+  for (int t = 0; t < NT; t++) if (t < n_tags && list_left_over(rev, t_cur[t], t_n[t])) err = true;
+  if (!prm.force_allow && !SAMPLE && lacks_mode(member_tagbits(wave_or(contribH), grp0.member_tags), lay->default_mask)) err = true;
+  read_epilogue(readout, rid, acc, false);
 }
 
 // ----------------------------------------------------------------------------------------------
@@ -738,15 +781,15 @@ __device__ __forceinline__ void decode_read_fast(const MkpReadHdr* __restrict__ 
 // time from the sorted rank list; every lane owning one finds the lane whose bases contain that occurrence (6 ds_bpermute steps
 // over the prefix sums), the dword inside that lane (one SWAR compare over the packed counts) and the base inside the dword
 // (select on the flag word read back from LDS) — {stored position, call index} goes straight into the call queue, in read
-// order.  No per-base marks, no bitmap deposit, no per-bit loops.  The consumer (per-call work on full batches of 64) is the
-// one of the FAST kernels.
+// order.  No per-base marks, no bitmap deposit, no per-bit loops.  The consumer (per-call work on full batches of 64) calls the
+// helpers the FAST kernels call, as the case "every tag lists every call, no implicit members" (classify_call<SAMPLE, INFER = false>)
+// and on descriptor words made opaque per batch; the CIGAR mapping is its own (a scalar 128-op window).
 // flag word of a SEQ dword: bit 4i set where nibble i equals the BAM code of base k (A,C,G,T = 1,2,4,8)
 __device__ __forceinline__ uint32_t nibble_eq(uint32_t x, uint32_t pat) {
   uint32_t t = x ^ pat;
   t |= t >> 1; t |= t >> 2;
   return ~t & 0x11111111u;
 }
-__device__ __forceinline__ uint32_t rfl_u(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 #define MKP_SQCAP 128   // call queue of the SPARSE kernels: < 64 left over + one round of <= 64
 template <bool SAMPLE, int NT>
 __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads, const uint32_t* __restrict__ cigar,
@@ -757,30 +800,21 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
                  const uint32_t* __restrict__ read_ids, uint32_t* __restrict__ lds_queue, uint32_t* __restrict__ lds_flags) {
   static_assert(NT <= 2, "one or two tags");
   const int lane = lane_id();
-  const uint32_t wib = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const uint32_t widx = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6))) + wib;
-  if (widx >= n_reads) return;
   // Duplex reads (layout.fast == 2: two (strand, base) groups on different bases) are listed twice, once per group (bit 31 = the
   // second); each listing decodes its group's tags exactly like a single-group read, into its own half of the read's event slice
   // behind the room for the merged list, with its own summary; mkp_merge_duplex interleaves the two by position afterwards.
-  const uint32_t rid_raw = (uint32_t)__builtin_amdgcn_readfirstlane((int)read_ids[widx]);
+  uint32_t wib, rid_raw; MkpReadHdr h; uint32_t* lds_lay;
+  if (!read_prologue(hdrs, n_reads, read_ids, layouts, readout, lds_layouts, 0x7fffffffu, wib, rid_raw, h, lds_lay)) return;
   const uint32_t rid = rid_raw & 0x7fffffffu; const bool half_b = (rid_raw >> 31) != 0u;
-  const MkpReadHdr h = hdrs[rid];
-  MkpReadOut out; out.n_events = 0; out.ok = 0; out.obs[0] = 0; out.obs[1] = 0;
-  if ((h.flags & MKP_RF_BAD) || h.n_tags == 0) { if (lane == 0) readout[rid] = out; return; }
-  uint32_t* __restrict__ lds_lay = lds_layouts + wib * MKP_LAYOUT_DWORDS;
   uint32_t* __restrict__ q_pos = lds_queue + wib * (2 * MKP_SQCAP);   // queue, SoA: stored position, call index (the same for both tags)
   uint32_t* __restrict__ q_j = q_pos + MKP_SQCAP;
   uint32_t* __restrict__ flg = lds_flags + wib * 512u;                 // the step's 512 flag words
-  { const uint32_t* __restrict__ src = reinterpret_cast<const uint32_t*>(&layouts[h.layout]);
-    for (int i = lane; i < MKP_LAYOUT_DWORDS; i += 64) lds_lay[i] = src[i]; }
-  __builtin_amdgcn_wave_barrier();
   const MkpLayout* lay = reinterpret_cast<const MkpLayout*>(lds_lay);
   const uint32_t* __restrict__ seqw = reinterpret_cast<const uint32_t*>(seqs + h.seq_off);
   const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
   const uint32_t L = h.l_seq, nd = (L + 7u) >> 3, aln = rev ? 1u : 0u;
-  const bool duplex = (uint32_t)__builtin_amdgcn_readfirstlane((int)lay->fast) == 2u;
-  const int n_first = (int)__builtin_amdgcn_readfirstlane((int)lay->pad);
+  const bool duplex = rfl_u(lay->fast) == 2u;
+  const int n_first = (int)rfl_u(lay->pad);
   const int tb = (duplex && half_b) ? n_first : 0;                     // first tag of the group this wave decodes
   const int n_tags = duplex ? (half_b ? (int)h.n_tags - n_first : n_first) : (int)h.n_tags;
   uint32_t ev_base = h.event_off, ev_cap = h.event_cap, ro_idx = rid;
@@ -792,31 +826,21 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
   const int b0 = (int)lay->tags[tb].fb & 3, sg0 = (int)lay->tags[tb].neg & 1;
   const int xs = rev ? 3 - b0 : b0;                                   // the stored base the tags count
   const uint32_t* gp0 = lds_lay + MKP_LAYOUT_GROUP_DW + (sg0 * 4 + b0) * 32;
-  GroupRegs grp0 = load_group(gp0);
-  grp0.misc = (uint32_t)__builtin_amdgcn_readfirstlane((int)grp0.misc); grp0.slots = (uint32_t)__builtin_amdgcn_readfirstlane((int)grp0.slots);
-  grp0.cids = (uint32_t)__builtin_amdgcn_readfirstlane((int)grp0.cids);
-    grp0.member_tags = (uint32_t)__builtin_amdgcn_readfirstlane((int)grp0.member_tags);
-#pragma unroll
-  for (int kq = 0; kq < MKP_KMAX; kq++) at(grp0.thr,
-      kq) = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(at(grp0.thr, kq))));
-  grp0.thr_can = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(grp0.thr_can)));
+  const GroupRegs grp0 = load_group_uniform(gp0);
   const int kcodes0 = (int)((grp0.misc >> 20) & 7u);   // codes of the group: bounds every per-code loop
   uint32_t t_ml[NT], t_nc[NT], tmu[NT], codes_t[NT];
+  tag_setup<NT>(lay, tb, n_tags, b0, t_nc, tmu, codes_t);
   uint32_t t_off = 0, t_n = 0, t_cur = 0;   // the (shared) rank list
+  uint32_t SH_all = 0, setmask_all = 0;     // every call is listed by every tag: hit pattern and code set are wave constants
 #pragma unroll
   for (int t = 0; t < NT; t++) {
-    t_ml[t] = 0; t_nc[t] = 0; tmu[t] = 0; codes_t[t] = 0;
+    t_ml[t] = 0;
     if (t < n_tags) {
       const MkpTagRef tr = tagref[h.tag_off + tb + t]; t_ml[t] = tr.ml_off;
       if (t == 0) { t_off = tr.rank_off; t_n = tr.n; t_cur = rev ? tr.n : 0u; }
-      t_nc[t] = (uint32_t)__builtin_amdgcn_readfirstlane((int)lay->tags[tb + t].n_codes);
-      tmu[t] = (uint32_t)__builtin_amdgcn_readfirstlane((int)lay->tagmap[tb + t][b0]);
-      for (uint32_t i = 0; i < t_nc[t]; i++) codes_t[t] |= 1u << ((tmu[t] >> (4 + 4 * i)) & 15u);
+      SH_all |= 1u << (tmu[t] & 15u); setmask_all |= codes_t[t];
     }
   }
-  uint32_t SH_all = 0, setmask_all = 0;   // every call is listed by every tag: hit pattern and code set are wave constants
-#pragma unroll
-  for (int t = 0; t < NT; t++) if (t < n_tags) { SH_all |= 1u << (tmu[t] & 15u); setmask_all |= codes_t[t]; }
   const uint32_t pat = 0x11111111u << xs;
   // the low nibble of the last byte is not a base when L is odd: its flag is cleared wherever that dword is looked at
   const uint32_t odd_dw = (L & 1u) ? ((L - 1u) >> 3) : 0xffffffffu, odd_clear = ~(1u << (8u * (((L - 1u) >> 1) & 3u)));
@@ -838,15 +862,13 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
     }
     tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(acc), 63);
   }
-  bool err = false;
+  ReadAcc acc; bool& err = acc.err;
   // reverse reads consume the (ascending) rank list from its end: a last entry past the last occurrence of the base
   // (mod_bam.rs:705-727) would never be consumed — the read is rejected here so that hits always form a suffix of the cursor window
   if (rev && t_n && ranks[t_off + t_n - 1u] >= tot) err = true;
-  const bool trimmable = !prm.edge_filter || !(L <= prm.edge_start || L <= prm.edge_end);  // read_can_be_trimmed (mod_bam.rs:1668-1671)
-  const bool collapse = prm.numeric_mode == 2;
-  uint32_t obs0 = 0, obs1 = 0, contribH = 0, n_ev = 0, cum = 0;
-  bool any_surviving = false;
-  // CIGAR window: 64 ops in registers, advanced as the batches move along the read
+  const bool trimmable = read_trimmable(prm, L);
+  uint32_t contribH = 0, cum = 0;
+  // CIGAR window of this decoder, advanced as the batches move along the read
   // (128 ops per window, two per lane: w_qe = inclusive query end of the lane's pair, w_mid = where its second op starts,
   //  w_a / w_b = (reference start - query start) << 1 | is-match of the two ops)
   // The window's running values (first op, query / reference offsets, totals) are kept in scalar registers — read back through readfirstlane
@@ -861,7 +883,6 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
   // the next step's SEQ dwords (eight per lane = 64 bases, two 16-byte loads) are always in flight; SEQ buffers end with
   // slack, so whole vectors are loaded and the dwords past the read are discarded when the flags are made
   // reads start 4-byte aligned: vector loads may be unaligned (fine on global memory)
-  const uint4* __restrict__ seqv = reinterpret_cast<const uint4*>(seqw);
   uint4 xa = make_uint4(0, 0, 0, 0), xb = make_uint4(0, 0, 0, 0);
   auto load_step = [&](uint32_t dstep) {
     const uint32_t d = dstep + 8u * (uint32_t)lane;
@@ -870,7 +891,6 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
     if (d + 8u <= nd) xb = *reinterpret_cast<const uint4*>(seqw + d + 4u);
     else { xb.x = d + 4u < nd ? seqw[d + 4u] : 0u; xb.y = d + 5u < nd ? seqw[d + 5u] : 0u; xb.z = d + 6u < nd ? seqw[d + 6u] : 0u; xb.w = 0u; }
   };
-  (void)seqv;
   load_step(0);
   // the current step: per-lane counts (byte-packed running counts of its 8 dwords), wave prefix sums, the step's rank window
   bool step_loaded = false;
@@ -909,22 +929,14 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
         st_cntT = (uint32_t)__builtin_amdgcn_readlane((int)st_incl, 63);
         st_wlo = rev ? (tot - cum - st_cntT) : cum; st_whi = st_wlo + st_cntT;   // rank window of this step
         step_loaded = true;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
       }
       // (reverse reads: the list's last entry was checked against the total, so every entry is below the first window's end)
       const bool hit = valid && (rev ? (e >= st_wlo) : (e < st_whi));
       const unsigned long long hb = __ballot(hit);
       const uint32_t nh = (uint32_t)__popcll(hb);
       if (nh) {
-        if (qhead) {  // move the (< 64) unconsumed entries to the front
-          const uint32_t n_left = qcount - qhead;
-          const bool mv = (uint32_t)lane < n_left;
-          const uint32_t a = mv ? q_pos[qhead + lane] : 0u, b = mv ? q_j[qhead + lane] : 0u;
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-          if (mv) { q_pos[lane] = a; q_j[lane] = b; }
-          qcount = n_left; qhead = 0;
-        }
+        if (qhead) queue_to_front<2>(q_pos, MKP_SQCAP, qhead, qcount);
         const uint32_t ib = hit ? ((rev ? (tot - 1u - e) : e) - cum) : 0u;   // step-relative stored ordinal of the called base (< cntT)
         const int owner = find_op(st_incl, ib) & 63;                          // the lane whose 64 bases hold that occurrence
         const uint32_t o_excl = (uint32_t)__shfl((int)st_excl, owner, 64), o_lo = (uint32_t)__shfl((int)st_cumlo, owner, 64),
@@ -946,7 +958,7 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
         const uint32_t slot = qcount + (uint32_t)__popcll(rev ? (hb & ~lanemask_le()) : (hb & lanemask_lt()));
         if (hit) { q_pos[slot] = 8u * (d0 + 8u * (uint32_t)owner + jd) + bpos;
           q_j[slot] = rev ? (t_cur - 64u + (uint32_t)lane) : (t_cur + (uint32_t)lane); }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_sync();
         qcount += nh;
         if (rev) t_cur -= nh; else t_cur += nh;
       }
@@ -959,7 +971,7 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
     // ---- consumer: up to 64 queued calls, in read order
     const uint32_t nb = min(64u, qcount - qhead);
 #ifdef MKP_DEBUG
-    if (prm.debug_skip & 16u) { qhead += nb; any_surviving = true; continue; }   // ablation: producer only
+    if (prm.debug_skip & 16u) { qhead += nb; acc.any_surviving = true; continue; }   // ablation: producer only
 #endif
     const bool active = (uint32_t)lane < nb;
     // The descriptor words the per-call code branches on are made opaque here, once per batch: left visible as loop invariants, every
@@ -971,21 +983,12 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
 #pragma unroll
     for (int t = 0; t < NT; t++) { tmu_l[t] = tmu[t]; tnc_l[t] = t_nc[t]; asm volatile("" : "+s"(tmu_l[t]), "+s"(tnc_l[t])); }
     const uint32_t q = active ? q_pos[qhead + lane] : 0u;
-    const uint32_t jx = active ? q_j[qhead + lane] : 0u;
     const uint32_t f = rev ? (L - 1 - q) : q;  // forward (as-sequenced) position
-    // the ML bytes are requested first (up to MKP_KMAX per tag) and converted after the CIGAR mapping, whose latency they overlap
-    uint32_t mlq[NT][MKP_KMAX];
+    uint32_t mlq[NT][MKP_KMAX], jx[NT]; bool listed[NT];   // every tag lists every call, as its jx-th
 #pragma unroll
-    for (int t = 0; t < NT; t++) {
-#pragma unroll
-      for (int i = 0; i < MKP_KMAX; i++) mlq[t][i] = 0;
-      if (t < n_tags) {
-        const uint32_t nc = tnc_l[t], base = active ? (t_ml[t] + jx * nc) : 0u;
-#pragma unroll
-        for (int i = 0; i < MKP_KMAX; i++) if ((uint32_t)i < nc) mlq[t][i] = ml[base + (active ? (uint32_t)i : 0u)];
-      }
-    }
-    // reference position through the CIGAR window (aligned pairs: M/=/X only, util.rs:122-145)
+    for (int t = 0; t < NT; t++) { jx[t] = active ? q_j[qhead + lane] : 0u; listed[t] = active; }
+    ml_prefetch<NT>(ml, n_tags, t_ml, tnc_l, listed, jx, mlq);
+    // reference position through this decoder's own CIGAR window (aligned pairs: M/=/X only, util.rs:122-145)
     bool mapped = false; int32_t rpos = 0;
 #ifdef MKP_DEBUG
     if (prm.debug_skip & 32u) { mapped = active; rpos = h.ref_start + (int32_t)q; } else   // ablation: no CIGAR mapping
@@ -1023,89 +1026,19 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
       while (__any(pending)) { if (!win_next()) break; win_pass(); }
     }
     F4 pk = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-      if (t >= n_tags) break;
-#pragma unroll
-      for (int i = 0; i < MKP_KMAX; i++) {
-        if ((uint32_t)i >= tnc_l[t]) break;
-        const float p = ((float)mlq[t][i] + 0.5f) / 256.0f;   // quals_to_probs (mod_bam.rs:808-816)
-        const uint32_t kk = (tmu_l[t] >> (4 + 4 * i)) & 15u;   // wave-uniform local code
-        setk(pk, kk, true, p);
-      }
-    }
-    if (NT > 1 && n_tags > 1) {  // combine_checked's sum test, once on the final map (partial sums of positive terms cannot exceed it)
-      float s = 0.f;
-#pragma unroll
-      for (int k2 = 0; k2 < MKP_KMAX; k2++) if (sm_l & (1u << k2)) s = s + at(pk, k2);
-      if (active && s > 1.01f) err = true;
-    }
-    uint32_t ev_info = 0; float sv = 0.f; bool has_ev = false;
-    if (active) {
-      const bool edge_keep = !prm.edge_filter ||
-          (prm.edge_inverted ? (f < prm.edge_start || f >= L - prm.edge_end) : (f >= prm.edge_start && f < L - prm.edge_end));
-      const uint32_t pv = gp0[12 + SH_l];
-      contribH |= SH_l;
-      if (trimmable && edge_keep) {
-        if (SAMPLE) {  // SeqPosBaseModProbs::filter_positions (read_ids_to_base_mod_probs.rs:966-1070)
-          bool keep = !prm.only_mapped || mapped;
-          if (prm.has_focus) keep = keep && mapped && rpos >= prm.win_start && rpos < prm.win_end
-              && ((bedmask[rpos - prm.win_start] >> (aln ^ (uint32_t)sg0)) & 1u);
-          // `extract calls`: the collapse left no code in the map: no profile row
-          if (keep && prm.sample_mode == 3 && ((pv >> 3) & 7u) == 0u) any_surviving = true;
-          else if (keep && prm.sample_mode >= 2) {
-            any_surviving = true; uint32_t ob = 0; float am = 0.f; ev_info = summary_info(g0, pv, pk, collapse, &ob, (int)kc_l, &am); obs0 |= ob;
-              has_ev = true;
-            // `extract calls`: the event carries the forward position (explicit tags: never inferred)
-            if (prm.sample_mode == 3) { ev_info |= (uint32_t)sg0 << 2; sv = am; rpos = (int32_t)f; }
-          }
-          else if (keep) { any_surviving = true; sv = argmax_group(g0, pv, pk, collapse, (int)kc_l); ev_info = MKP_G_TB(g0.misc); has_ev = true; }
-        } else {
-          any_surviving = true;
-          uint32_t ob = 0;
-          const int cls = call_group(g0, pv, pk, collapse, &ob, (int)kc_l);
-          const uint32_t tally = aln ^ (uint32_t)sg0;  // read_cache.rs:181-188 / FeatureVector::add_feature
-          if (tally) obs1 |= ob; else obs0 |= ob;
-          if (mapped) {
-            const uint32_t cid = cls == 0 ? (uint32_t)MKP_C_FAIL : cls == 1 ? MKP_G_CIDCAN(g0.misc) : ((g0.cids >> (8 * (cls - 2))) & 0xffu);
-            ev_info = cid | (tally << 8) | ((uint32_t)b0 << 9) | (aln << 11) | (1u << 12);
-            has_ev = true;
-          }
-        }
-      }
-    }
-    // ballot-compacted, position-ordered append of this batch's events
-    const unsigned long long b1 = __ballot(has_ev);
-    const uint32_t step_total = (uint32_t)__popcll(b1);
-    if (step_total) {
-      const uint32_t off = n_ev + (uint32_t)__popcll(b1 & lanemask_lt());
-      if (n_ev + step_total > ev_cap) { err = true; if (lane == 0) atomicOr(dev_err, ERR_EVENT_CAP); }
-      else if (has_ev) {
-        MkpEvent ev; ev.pos = (uint32_t)rpos; ev.info = ev_info; events[ev_base + off] = ev;
-        if (SAMPLE) sample_vals[ev_base + off] = sv;
-      }
-      n_ev += step_total;
-    }
+    if (ml_to_probs<NT>(mlq, n_tags, tnc_l, tmu_l, listed, sm_l, active && n_tags > 1, pk)) err = true;
+    uint32_t ev_info[1] = {0}; float sv[1] = {0.f}; bool has_ev = false;
+    if (active)   // explicit tags: no implicit members, never inferred
+      has_ev = classify_call<SAMPLE, false>(prm, bedmask, g0, gp0, (int)kc_l, b0, sg0, aln, L, trimmable, SH_l, 0u, pk, f, mapped, rpos, acc,
+                                            contribH, ev_info[0], sv[0]);
+    append_events<SAMPLE, 1>(events, sample_vals, dev_err, ev_base, ev_cap, has_ev ? 1u : 0u, (uint32_t)rpos, ev_info, sv, acc);
     err = __any(err);
     qhead += nb;
   }
-  // a delta list must not run past the last occurrence of its base: every entry must have been consumed (mod_bam.rs:705-727)
-  if (rev ? (t_cur != 0u) : (t_cur != t_n)) err = true;
-  err = __any(err);
-  obs0 = wave_or(obs0); obs1 = wave_or(obs1);
-  any_surviving = __any(any_surviving);
-  // InvalidImplicitMode cannot arise (every tag carries '?'), kept for symmetry with the FAST kernels (read_cache.rs:122-137)
-  if (!prm.force_allow && !SAMPLE) {
-    const uint32_t mc = wave_or(contribH); uint32_t tagbits = 0;
-#pragma unroll
-    for (int mi = 0; mi < MKP_MAX_MEMBERS; mi++) if (mc & (1u << mi)) tagbits |= 1u << ((grp0.member_tags >> (4 * mi)) & 15u);
-    if (tagbits && (tagbits & ~(uint32_t)lay->default_mask) == 0) err = true;
-  }
-  if (lane == 0) {
-    if (!err && any_surviving) { out.ok = 1; out.n_events = n_ev; out.obs[0] = obs0; out.obs[1] = obs1; }
-    else if (!err && duplex) out.ok = 2;   // this group added nothing (all of it edge-filtered): the record still stands if the other group did
-    readout[ro_idx] = out;
-  }
+  if (list_left_over(rev, t_cur, t_n)) err = true;
+  // InvalidImplicitMode cannot arise (every tag carries '?'), kept for symmetry with the FAST kernels
+  if (!prm.force_allow && !SAMPLE && lacks_mode(member_tagbits(wave_or(contribH), grp0.member_tags), lay->default_mask)) err = true;
+  read_epilogue(readout, ro_idx, acc, duplex);
 }
 
 #define DECODE_PARAMS(PRM) const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ seqs, \
@@ -1156,7 +1089,7 @@ extern "C" __global__ void __launch_bounds__(256) mkp_decode_fast2(DECODE_PARAMS
 // Waves per SIMD of the SPARSE event decoders.  Left alone the compiler took 77 / 85 VGPRs and 106 SGPRs = six / five waves; seven
 // (72 VGPRs, <= 96 SGPRs: the scalar file admits seven, MI355X_MICROARCH.md "Residency") gave C2 decode 0.509 -> 0.481 ms, hemi 2.40 -> 2.28,
 // and eight spilled (0.57 / 2.60).  Since the producer runs as a loop of its own and the consumer's descriptor words are opaque (both
-// in decode_read_sparse) the kernels need 59 / 60 VGPRs, and EIGHT waves (<= 64 VGPRs, <= 80 SGPRs) win: C2 decode 0.428 -> 0.405 ms, hemi
+// in decode_read_sparse) the kernels need 59 / 60 VGPRs (55 / 61 with the consumer folded into the shared helpers), and EIGHT waves (<= 64 VGPRs, <= 80 SGPRs) win: C2 decode 0.428 -> 0.405 ms, hemi
 // decode 1.955 -> 1.859 (0.452 / 2.03 before both changes).  A/B on one box, tools/dbg/ab.sh.
 #ifndef MKP_SPARSE_WAVES
 #define MKP_SPARSE_WAVES 8

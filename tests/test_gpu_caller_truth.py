@@ -82,7 +82,7 @@ EXTRACT_SPECS = [tc.Spec(), tc.Spec(default=0.6, per_mod={"m": 0.7}), tc.Spec(de
                  tc.Spec(default=0.5, ignore="h"), tc.Spec(default=1.5)]
 
 
-@pytest.mark.parametrize("name", ["m", "hm", "h_m", "m_dot", "hmfc", "chebi"])
+@pytest.mark.parametrize("name", ["m", "hm", "h_m", "m_dot", "h_m_dot", "hmfc", "chebi"])
 def test_extract_calls_match_model(oracle_bin, tmp_path_factory, name):
     ml, solo, bam, fa, calls, d = _bam(tmp_path_factory, name)
     for si, spec in enumerate(EXTRACT_SPECS):
