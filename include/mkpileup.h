@@ -224,7 +224,10 @@ int mkp_process_region(mkp_ctx* ctx, const char* bam_path, const mkp_shard* shar
 
 /* ---- whole subcommand: `modkit pileup` (ModBamPileup::run, src/pileup/subcommand.rs:382-816).
  * argv carries the reference's own flags (in.bam out.bed --cpg --ref ... ), see DESIGN.md for the
- * covered set; plus --device N, --gpus-rank R --gpus-world W for interval sharding. */
+ * covered set; plus --device N, --gpus-rank R --gpus-world W for interval sharding; plus --region-stats <regions.bed> --region-stats-out
+ * <table.tsv> [--region-stats-codes m,h] [--region-stats-min-coverage N] [--region-stats-no-header] [--region-stats-only]: `modkit stats`
+ * over the run's rows while they are in HBM (mkp_stats_* below); with --region-stats-only the rows are neither read back nor written
+ * (the out.bed positional is still required, the file is not created). */
 int mkp_pileup_main(int argc, const char* const* argv, char* errbuf, size_t errbuf_len);
 
 /* The same subcommand on a context the caller owns (so the device named by the ctx is used and --device is ignored):
@@ -390,6 +393,55 @@ int mkp_summary(mkp_ctx* ctx, const char* bam_path, int argc, const char* const*
  * over the whole contigs, intersected with --include-bed (load_regions, util.rs:157-277).  --seed goes to the estimate.  --bgzf writes the table as
  * BGZF blocks (SAM spec 4.1) closed by the EOF block. */
 int mkp_extract_calls_main(int argc, const char* const* argv, char* errbuf, size_t errbuf_len);
+
+/* ---- `modkit stats <in.bed.gz> --regions <bed>` (EntryStats::run, src/stats/subcommand.rs:65-206; GenomeRegion::into_stats,
+ * src/stats/mod.rs:53-101): per region and mod code the sums of N_mod and N_valid_cov over the bedMethyl rows whose start lies in
+ * [start, end), whose strand overlaps the region's rule (StrandRule::overlaps, src/util.rs:310-318: either side '.', or equal) and whose
+ * N_valid_cov >= min_coverage — reduced on the device from row columns that are in HBM (mkp_stats.hip), so that a pileup run can be
+ * aggregated without its rows ever being read back, written as text, compressed and indexed.  The table lives in HBM from
+ * mkp_stats_begin to mkp_stats_get and every add call adds into it: a region that straddles shard seams gets each row once.
+ *   mkp_stats_begin         regions in the caller's order (tid < 0: a contig the rows cannot be on), start <= end (start == end: an empty
+ *                           region, all zeros); codes = `--mod-codes` (only these are counted; duplicates collapse), n_codes = 0: every
+ *                           code met.  At most 16 distinct codes per run, more is MKP_E_UNSUPPORTED (reported by mkp_stats_get at the
+ *                           latest).  min_coverage = `--min-coverage` (the reference's default is 1).
+ *   mkp_stats_add_resident  the rows the last mkp_shard_run / mkp_shard_rerun on this ctx left in HBM (the shard's contig and window);
+ *                           MKP_E_INVALID with partition tags set (rows grouped by key are not in genome order) or after a hemi run.
+ *   mkp_stats_add_rows      rows the caller holds (the bedMethyl-file form: fetch_region of src/tabix.rs:103-154 + BedMethylLine,
+ *                           src/dmr/bedmethyl.rs:40-86), one contig per call, ascending pos (MKP_E_INVALID otherwise): pos, strand,
+ *                           code_repr, n_valid and n_mod are read, uploaded, and go through the same kernels.
+ *   mkp_stats_get           waits for the device and returns the table: columns = the given codes, sorted, or the codes that had a counted
+ *                           row in some region (a counted row with N_mod == 0, or with N_valid_cov == 0 under min_coverage 0, still
+ *                           makes the column; a code met only outside the regions does not), in ModCodeRepr order.  contig_has_rows[r]
+ *                           = an add call brought at least one row (before any filter) on region r's contig: the reference drops the
+ *                           other regions (HtsTabixHandler::has_contig, subcommand.rs:127-140).  Arrays owned by the ctx until its next
+ *                           mkp_stats_begin.  percent_modified = (n_mod as f32 / n_valid as f32) * 100 (ModPositionInfo, util.rs:920-936)
+ *                           is left to the table writer. */
+typedef struct { int32_t tid; uint32_t start, end; uint8_t strand_rule; /* 1 '+', 2 '-', 3 both */ uint8_t pad[3]; } mkp_region;
+typedef struct { uint32_t n_regions, n_codes; const uint32_t* code_repr;      /* sorted */
+                 const uint64_t* n_mod; const uint64_t* n_valid;              /* [region * n_codes + code] */
+                 const uint8_t* contig_has_rows;                              /* per region: 0 = the reference would drop it */ } mkp_stats_out;
+int mkp_stats_begin(mkp_ctx* ctx, const mkp_region* regions, uint32_t n, const uint32_t* codes, uint32_t n_codes /*0 = all observed*/, uint64_t min_coverage);
+int mkp_stats_add_resident(mkp_ctx* ctx);
+int mkp_stats_add_rows(mkp_ctx* ctx, int32_t tid, const mkp_rows* rows);
+int mkp_stats_get(mkp_ctx* ctx, mkp_stats_out* out);
+/* Host-only halves of the same subcommand (no device needed).
+ * mkp_host_parse_regions: the regions BED as EntryStats::run reads it (subcommand.rs:79-110; GenomeRegion::parse_unstranded_bed_line /
+ *   parse_stranded_bed_line, src/util.rs:864-909): the first line that does not start with '#' picks the parser by its number of
+ *   tab-separated fields (<= 4: chrom start end [name], both strands; otherwise chrom start end name score strand with score a float or
+ *   '.'), then EVERY line goes through it — a '#' line, an empty file or any other unparsable line fails (MKP_E_INVALID), as does
+ *   start > end.  contig_names give the tids (a chrom that is not among them gets tid -1).  A name holding a quote, or a coordinate
+ *   beyond 2^32 - 1, is MKP_E_UNSUPPORTED.  The set is freed with mkp_region_set_free.
+ * mkp_host_stats_table: the table EntryStats::run writes (MethylationStats::header / into_row, src/stats/mod.rs:24-51, through the csv
+ *   writer with a tab delimiter): `chrom start end name strand` then count_<c> count_valid_<c> percent_<c> per code, regions in file order
+ *   without those whose contig_has_rows is 0, an absent name as '.', the percentage through f32 Display. */
+typedef struct mkp_region_set mkp_region_set;
+int mkp_host_parse_regions(const char* bed_path, const char* const* contig_names, uint32_t n_contigs, mkp_region_set** out, char* errbuf, size_t errbuf_len);
+uint32_t mkp_region_set_size(const mkp_region_set* set);
+const mkp_region* mkp_region_set_regions(const mkp_region_set* set);
+const char* mkp_region_set_chrom(const mkp_region_set* set, uint32_t i);
+const char* mkp_region_set_name(const mkp_region_set* set, uint32_t i);   /* "." when the line has none */
+void mkp_region_set_free(mkp_region_set* set);
+int mkp_host_stats_table(const mkp_region_set* set, const mkp_stats_out* counts, int with_header, const char* out_path);
 
 /* ---- BGZF inflate on the device as a call of its own.  On the pileup path the same kernels run inside the device ingest
  * (`mkp_pileup_main` on an indexed BAM: compressed blocks up, inflate + CRC-32 + record cut + MM/ML tokeniser + packing in HBM, a digest

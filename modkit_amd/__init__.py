@@ -75,6 +75,24 @@ def lib():
         L.mkp_histogram_locate.argtypes = [u64p, ctypes.c_float, ctypes.POINTER(ctypes.c_uint32), u64p, u64p]
         L.mkp_histogram_resolve.argtypes = [ctypes.c_uint32, u64p, ctypes.c_uint64, f32p]
         L.mkp_percentile_from_histogram.argtypes = [ctypes.c_uint64, ctypes.c_float, ctypes.c_float, ctypes.c_float, f32p]
+        if hasattr(L, "mkp_stats_begin"):   # (absent from an older build loaded through MKP_LIB_PATH)
+            L.mkp_stats_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.c_uint64]
+            L.mkp_stats_add_resident.argtypes = [ctypes.c_void_p]
+            L.mkp_stats_add_rows.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+            L.mkp_stats_get.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            L.mkp_set_partition_tags.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32]
+            L.mkp_host_parse_regions.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.c_size_t]
+            L.mkp_region_set_size.argtypes = [ctypes.c_void_p]
+            L.mkp_region_set_size.restype = ctypes.c_uint32
+            L.mkp_region_set_regions.argtypes = [ctypes.c_void_p]
+            L.mkp_region_set_regions.restype = ctypes.POINTER(Region)
+            L.mkp_region_set_chrom.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+            L.mkp_region_set_chrom.restype = ctypes.c_char_p
+            L.mkp_region_set_name.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+            L.mkp_region_set_name.restype = ctypes.c_char_p
+            L.mkp_region_set_free.argtypes = [ctypes.c_void_p]
+            L.mkp_region_set_free.restype = None
+            L.mkp_host_stats_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p]
         # the structs this binding allocates mirror ONE revision of include/mkpileup.h: a library of another revision would write past them
         if os.environ.get("MKP_LIB_PATH") and not hasattr(L, "mkp_abi_version"):
             _lib = L   # (A/B runs against a build from before the query existed, tools/dbg/ab.sh)
@@ -99,7 +117,9 @@ EXPORTS = ["mkp_ctx_create", "mkp_ctx_destroy", "mkp_last_error", "mkp_version",
            "mkp_shard_add_records", "mkp_shard_set_intervals", "mkp_shard_run", "mkp_batch_run", "mkp_shard_rerun", "mkp_get_stats", "mkp_shard_read_flags", "mkp_process_region", "mkp_pileup_main",
            "mkp_pileup_run", "mkp_pileup_run_cb", "mkp_percentile", "mkp_estimate_thresholds", "mkp_host_mm_ranks", "mkp_host_map_order",
            "mkp_set_partition_tags", "mkp_histogram_begin", "mkp_histogram_add_bam", "mkp_histogram_get", "mkp_histogram_allreduce", "mkp_histogram_from_values", "mkp_histogram_locate",
-           "mkp_histogram_resolve", "mkp_percentile_from_histogram", "mkp_hemi_shard_run", "mkp_pileup_hemi_main", "mkp_pileup_hemi_run", "mkp_bgzf_inflate", "mkp_sample_probs", "mkp_summary", "mkp_extract_calls_main"]
+           "mkp_histogram_resolve", "mkp_percentile_from_histogram", "mkp_hemi_shard_run", "mkp_pileup_hemi_main", "mkp_pileup_hemi_run", "mkp_bgzf_inflate", "mkp_sample_probs", "mkp_summary", "mkp_extract_calls_main",
+           "mkp_stats_begin", "mkp_stats_add_resident", "mkp_stats_add_rows", "mkp_stats_get", "mkp_host_parse_regions", "mkp_region_set_size",
+           "mkp_region_set_chrom", "mkp_region_set_name", "mkp_region_set_free", "mkp_host_stats_table"]
 
 
 def pileup(argv):
@@ -171,6 +191,86 @@ class Rows(ctypes.Structure):
                 ("processed_records", ctypes.c_uint64), ("skipped_records", ctypes.c_uint64),
                 ("partition_key", ctypes.POINTER(ctypes.c_uint32)), ("n_partition_keys", ctypes.c_uint32),
                 ("partition_key_names", ctypes.POINTER(ctypes.c_char_p))]
+
+
+class Region(ctypes.Structure):
+    """mkp_region: one line of a regions BED (GenomeRegion, src/util.rs:850-857); strand_rule 1 '+', 2 '-', 3 both."""
+    _fields_ = [("tid", ctypes.c_int32), ("start", ctypes.c_uint32), ("end", ctypes.c_uint32), ("strand_rule", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 3)]
+
+
+class StatsOut(ctypes.Structure):
+    """mkp_stats_out: the per-region, per-code totals of `modkit stats`."""
+    _fields_ = [("n_regions", ctypes.c_uint32), ("n_codes", ctypes.c_uint32), ("code_repr", ctypes.POINTER(ctypes.c_uint32)),
+                ("n_mod", ctypes.POINTER(ctypes.c_uint64)), ("n_valid", ctypes.POINTER(ctypes.c_uint64)), ("contig_has_rows", ctypes.POINTER(ctypes.c_uint8))]
+
+
+STRAND_RULES = {"+": 1, "-": 2, ".": 3}
+
+
+def code_repr(code):
+    """ModCodeRepr as the library's u32: a one-character code's code point, or a ChEBI number | 1 << 31 (ModCodeRepr::parse)."""
+    if isinstance(code, str):
+        return ord(code) if len(code) == 1 else (int(code) | (1 << 31))
+    return int(code)
+
+
+class RegionSet:
+    """A parsed regions BED (mkp_host_parse_regions): `regions` = [(chrom, start, end, name or ".", strand "+-."), ...], tids by `contig_names`."""
+
+    def __init__(self, bed_path, contig_names):
+        self.L = lib()
+        names = [str(n).encode() for n in contig_names]
+        arr = (ctypes.c_char_p * max(1, len(names)))(*names)
+        self.h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(2048)
+        rc = self.L.mkp_host_parse_regions(str(bed_path).encode(), arr, len(names), ctypes.byref(self.h), err, len(err))
+        if rc != MKP_OK:
+            raise MkpError(rc, err.value.decode(errors="replace"))
+        self.n = self.L.mkp_region_set_size(self.h)
+        self.array = self.L.mkp_region_set_regions(self.h)
+
+    @property
+    def regions(self):
+        return [(self.L.mkp_region_set_chrom(self.h, i).decode(), int(self.array[i].start), int(self.array[i].end),
+                 self.L.mkp_region_set_name(self.h, i).decode(), "?+-."[self.array[i].strand_rule]) for i in range(self.n)]
+
+    @property
+    def tids(self):
+        return [int(self.array[i].tid) for i in range(self.n)]
+
+    def write_table(self, counts, out_path, header=True):
+        """The `modkit stats` table of `counts` (a StatsOut, or the dict Context.stats_get returns) for these regions (mkp_host_stats_table)."""
+        keep = None
+        if isinstance(counts, dict):
+            counts, keep = stats_out_from(counts)
+        rc = self.L.mkp_host_stats_table(self.h, ctypes.byref(counts), int(bool(header)), str(out_path).encode())
+        del keep
+        if rc != MKP_OK:
+            raise MkpError(rc, "mkp_host_stats_table failed")
+
+    def close(self):
+        if self.h:
+            self.L.mkp_region_set_free(self.h)
+            self.h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def stats_out_from(d):
+    """A StatsOut over numpy copies of {"codes", "n_mod", "n_valid", "contig_has_rows"}; returns (struct, arrays to keep alive)."""
+    import numpy as np
+    codes = np.ascontiguousarray(np.asarray(d["codes"], dtype=np.uint32))
+    n_mod = np.ascontiguousarray(np.asarray(d["n_mod"], dtype=np.uint64))
+    n_valid = np.ascontiguousarray(np.asarray(d["n_valid"], dtype=np.uint64))
+    has = np.ascontiguousarray(np.asarray(d["contig_has_rows"], dtype=np.uint8))
+    o = StatsOut(n_regions=len(has), n_codes=len(codes), code_repr=codes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                 n_mod=n_mod.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n_valid=n_valid.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                 contig_has_rows=has.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    return o, (codes, n_mod, n_valid, has)
 
 
 class HemiRows(ctypes.Structure):
@@ -386,6 +486,54 @@ class Context:
         self._check(self.L.mkp_bgzf_inflate(self.h, data, len(data), ctypes.byref(out), ctypes.byref(n), ctypes.byref(ms)))
         return ctypes.string_at(out, n.value) if n.value else b"", ms.value
 
+    def set_partition_tags(self, tags):
+        """mkp_set_partition_tags: two-character SAM tag names; an empty list clears."""
+        enc = [str(t).encode() for t in tags]
+        arr = (ctypes.c_char_p * max(1, len(enc)))(*enc)
+        self._check(self.L.mkp_set_partition_tags(self.h, arr, len(enc)))
+
+    def stats_begin(self, regions, codes=None, min_coverage=1):
+        """mkp_stats_begin: regions = a RegionSet, or [(tid, start, end, strand "+-." or rule 1..3), ...]; codes = the `--mod-codes` list
+        (letters, ChEBI numbers as text, or code_repr ints) or None for every code met; min_coverage = `--min-coverage`."""
+        if isinstance(regions, RegionSet):
+            arr, n = regions.array, regions.n
+        else:
+            n = len(regions)
+            arr = (Region * max(1, n))()
+            for i, (tid, start, end, rule) in enumerate(regions):
+                arr[i].tid, arr[i].start, arr[i].end = int(tid), int(start), int(end)
+                arr[i].strand_rule = STRAND_RULES[rule] if isinstance(rule, str) else int(rule)
+        cs = [code_repr(c) for c in (codes or [])]
+        carr = (ctypes.c_uint32 * max(1, len(cs)))(*cs)
+        self._check(self.L.mkp_stats_begin(self.h, arr, n, carr, len(cs), int(min_coverage)))
+
+    def stats_add_resident(self):
+        """mkp_stats_add_resident: add the rows the last shard run left in HBM to the region table."""
+        self._check(self.L.mkp_stats_add_resident(self.h))
+
+    def stats_add_rows(self, tid, rows):
+        """mkp_stats_add_rows: rows of ONE contig, ascending pos, as a dict of arrays (pos, strand as bytes '+-.', code_repr, n_valid, n_mod:
+        what read_bedmethyl / rows_to_numpy give); they are uploaded and reduced by the same kernels."""
+        import numpy as np
+        cols = {f: np.ascontiguousarray(np.asarray(rows[f], dtype=np.uint8 if f == "strand" else np.uint32))
+                for f in ("pos", "strand", "code_repr", "n_valid", "n_mod")}
+        r = Rows()
+        r.n_rows = len(cols["pos"])
+        for f, a in cols.items():
+            setattr(r, f, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8 if f == "strand" else ctypes.c_uint32)))
+        self._check(self.L.mkp_stats_add_rows(self.h, int(tid), ctypes.byref(r)))
+
+    def stats_get(self):
+        """mkp_stats_get: {"codes": u32[n_codes] sorted, "n_mod" / "n_valid": u64[n_regions, n_codes], "contig_has_rows": u8[n_regions]}."""
+        import numpy as np
+        o = StatsOut()
+        self._check(self.L.mkp_stats_get(self.h, ctypes.byref(o)))
+        n, k = int(o.n_regions), int(o.n_codes)
+        def arr(p, shape, dt):
+            return np.ctypeslib.as_array(p, shape=shape).copy() if all(shape) else np.zeros(shape, dtype=dt)
+        return {"codes": arr(o.code_repr, (k,), np.uint32), "n_mod": arr(o.n_mod, (n, k), np.uint64), "n_valid": arr(o.n_valid, (n, k), np.uint64),
+                "contig_has_rows": arr(o.contig_has_rows, (n,), np.uint8)}
+
     def rerun(self, iters, fetch=False):
         rows = Rows()
         self._check(self.L.mkp_shard_rerun(self.h, int(iters), ctypes.byref(rows) if fetch else None))
@@ -443,3 +591,46 @@ def rows_to_numpy(rows):
         p = getattr(rows, f)
         out[f] = np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype=np.uint32)
     return out
+
+
+def read_bedmethyl_for_stats(path):
+    """What `stats` reads of a bedMethyl file: plain text (not bgzip-compressed), no header line, columns separated by tabs and / or blanks
+    (both the default and the --mixed-delim form): column 1 chrom, 2 start, 4 name — the mod code is the name up to its first comma, so the
+    `m,CG,0` names of multi-motif runs are taken too —, 6 strand, 10 N_valid_cov, 12 N_mod (BedMethylLine, src/dmr/bedmethyl.rs:40-86).
+    Returns [(chrom, rows dict), ...]: one entry per run of lines on one contig, file order."""
+    import numpy as np
+    import pandas as pd
+    if os.path.getsize(path) == 0:
+        return []
+    df = pd.read_csv(path, sep=r"\s+", header=None, usecols=[0, 1, 3, 5, 9, 11], dtype={0: str, 3: str, 5: str}, engine="c")
+    chrom = df[0].to_numpy()
+    cut = [0] + [i for i in range(1, len(chrom)) if chrom[i] != chrom[i - 1]] + [len(chrom)]
+    code = df[3].map(lambda c: code_repr(c.split(",", 1)[0])).to_numpy().astype(np.uint32)
+    strand = df[5].map(ord).to_numpy().astype(np.uint8)
+    out = []
+    for a, b in zip(cut[:-1], cut[1:]):
+        out.append((chrom[a], {"pos": df[1].to_numpy()[a:b].astype(np.uint32), "strand": strand[a:b], "code_repr": code[a:b],
+                               "n_valid": df[9].to_numpy()[a:b].astype(np.uint32), "n_mod": df[11].to_numpy()[a:b].astype(np.uint32)}))
+    return out
+
+
+def stats(bedmethyl_path, regions_bed, out_table, codes=None, min_coverage=1, header=True, device=0):
+    """`modkit stats <bedmethyl> --regions <bed> -o <table>` (EntryStats::run, src/stats/subcommand.rs:65-206) on the device: the file's rows
+    are uploaded contig by contig and reduced by the kernels a fused `pileup --region-stats` run uses (Context.stats_add_rows).  Reads what
+    read_bedmethyl_for_stats reads: a PLAIN-TEXT bedMethyl without header (no bgzip / tabix needed); a region whose contig has no line in
+    the file is dropped, as the reference drops contigs its tabix index does not list.  codes = `--mod-codes`, header=False = `--no-header`."""
+    pieces = read_bedmethyl_for_stats(bedmethyl_path)
+    names = []
+    for chrom, _ in pieces:
+        if chrom not in names:
+            names.append(chrom)
+    rs = RegionSet(regions_bed, names)
+    ctx = Context(device=device)
+    try:
+        ctx.stats_begin(rs, codes=codes, min_coverage=min_coverage)
+        for chrom, rows in pieces:
+            ctx.stats_add_rows(names.index(chrom), rows)
+        rs.write_table(ctx.stats_get(), out_table, header=header)
+    finally:
+        ctx.close()
+        rs.close()

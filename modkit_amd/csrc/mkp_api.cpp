@@ -939,7 +939,7 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
 
 // row columns and per-read outcome counts, device -> host
 void fetch_row_columns(mkp_ctx* c) {
-  const uint64_t n = c->stats.n_rows;
+  const uint64_t n = c->skip_row_fetch ? 0 : c->stats.n_rows;   // (`--region-stats-only`: the columns stay in HBM, the read summaries still come back)
   const uint32_t* src[11] = {c->rows_dst.pos, c->rows_dst.info, c->rows_dst.code, c->rows_dst.n_valid, c->rows_dst.n_mod, c->rows_dst.n_can,
       c->rows_dst.n_other,
                              c->rows_dst.n_del, c->rows_dst.n_fail, c->rows_dst.n_diff, c->rows_dst.n_nocall};
@@ -976,7 +976,7 @@ void fetch_hemi_rows(mkp_ctx* c, mkp_hemi_rows* out) {
 void fetch_rows(mkp_ctx* c, mkp_rows* out) {
   auto t0 = std::chrono::steady_clock::now();
   fetch_row_columns(c);
-  const uint64_t n = c->stats.n_rows;
+  const uint64_t n = c->skip_row_fetch ? 0 : c->stats.n_rows;
   c->h_strand.resize(n); c->h_motif.resize(n); c->h_key.resize(n);
   host_parallel(n, (size_t)1 << 17, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; i++) { const uint32_t inf = c->h_rows.col[1][i];
       c->h_strand[i] = "+-."[inf & 3u]; c->h_motif[i] = (int32_t)((inf >> 8) & 0xffu) - 1;
@@ -1084,7 +1084,9 @@ void mkp_ctx_destroy(mkp_ctx* c) {
                     &c->d_slotbm, &c->d_prm, &c->d_read_ids, &c->d_chunk, &c->d_store, &c->d_hist0, &c->d_hist1, &c->d_sample_cursor, &c->d_take,
                         &c->d_tile_row_off, &c->d_tile_row_cnt, &c->d_tile_dst, &c->d_misc, &c->d_rows_src, &c->d_rows_dst, &c->d_hemi_iv,
                         &c->d_slot_pos, &c->d_cov, &c->d_visits, &c->d_stiles, &c->d_slot_ids, &c->d_fdesc, &c->d_work, &c->d_plane, &c->d_zin, &c->d_zout,
-                        &c->d_zblk, &c->d_zstat, &c->d_summary, &c->d_bedmask, &c->d_hist64}) b->release();
+                        &c->d_zblk, &c->d_zstat, &c->d_summary, &c->d_bedmask, &c->d_hist64, &c->rstats.d_regions, &c->rstats.d_out, &c->rstats.d_seen,
+                        &c->rstats.d_misc, &c->rstats.d_lo, &c->rstats.d_hi, &c->rstats.d_cnt, &c->rstats.d_off, &c->rstats.d_rows}) b->release();
+  for (auto& e : c->rstats.ev) if (e) (void)hipEventDestroy(e);
   mkp_internal_ingest_destroy(c->ingest); c->ingest = nullptr;
   c->h_rows.release();
   for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
@@ -1884,6 +1886,168 @@ int mkp_percentile_from_histogram(uint64_t n, float q, float y0, float y1, float
   const float l = (float)(n - 1), lq = l * q, g = lq - truncf(lq);
   *out = y0 * (1.0f - g) + y1 * g;
   return MKP_OK;
+}
+
+}  // extern "C"
+
+// ---- region statistics (`modkit stats`, include/mkpileup.h): the table stays in HBM between mkp_stats_begin and mkp_stats_get
+extern "C" hipError_t mkp_launch_region_stats(hipStream_t, const uint32_t* /*pos*/, const uint32_t* /*info*/, const uint32_t* /*code*/,
+    const uint32_t* /*n_valid*/, const uint32_t* /*n_mod*/, uint32_t /*rows*/, const MkpStatsRegion*, uint32_t, uint32_t* /*first row*/,
+    uint32_t* /*row behind the last*/, uint32_t* /*chunks*/, unsigned long long* /*chunk offsets*/, unsigned long long* /*their total*/,
+    unsigned long long* /*table*/, uint32_t* /*seen masks*/, uint32_t* /*slot codes*/, uint32_t* /*error bits*/, unsigned long long /*min coverage*/,
+    uint32_t /*fixed code list*/, hipEvent_t* /*3 timing events or NULL*/);
+
+namespace {
+// d_misc: 16 slot codes, the error word, a pad word, the chunk total (u64)
+constexpr size_t kStatsMiscBytes = 4 * MKP_STATS_MAX_CODES + 16;
+void stats_launch(mkp_ctx* c, int32_t tid, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
+    const uint32_t* n_mod, uint64_t n_rows) {
+  mkp_ctx::RegionStats& R = c->rstats;
+  if (n_rows > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one piece");
+  if (n_rows) R.tids_with_rows.insert(tid);
+  auto it = R.tid_range.find(tid);
+  if (!n_rows || it == R.tid_range.end()) return;
+  const uint32_t first = it->second.first, n = it->second.second - first;
+  uint32_t* misc = R.d_misc.as<uint32_t>();
+  hip_check(mkp_launch_region_stats(c->stream, pos, info, code, n_valid, n_mod, (uint32_t)n_rows, R.d_regions.as<MkpStatsRegion>() + first, n,
+      R.d_lo.as<uint32_t>(), R.d_hi.as<uint32_t>(), R.d_cnt.as<uint32_t>(), R.d_off.as<unsigned long long>(),
+      reinterpret_cast<unsigned long long*>(misc + MKP_STATS_MAX_CODES + 2), R.d_out.as<unsigned long long>(), R.d_seen.as<uint32_t>(), misc,
+      misc + MKP_STATS_MAX_CODES, (unsigned long long)R.min_cov, R.fixed ? 1u : 0u, R.timing ? R.ev : nullptr), "region stats launch");
+  if (R.timing) {
+    hip_check(hipEventSynchronize(R.ev[2]), "region stats sync");
+    float a = 0, b = 0; hip_check(hipEventElapsedTime(&a, R.ev[0], R.ev[1]), "event"); hip_check(hipEventElapsedTime(&b, R.ev[1], R.ev[2]), "event");
+    R.kernel_ms[0] += a; R.kernel_ms[1] += b;
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int mkp_internal_stats_timing(mkp_ctx* c, int on, double ms_out[2]) {
+  if (!c) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::RegionStats& R = c->rstats;
+    if (ms_out) { ms_out[0] = R.kernel_ms[0]; ms_out[1] = R.kernel_ms[1]; }
+    if (on) for (auto& e : R.ev) if (!e) hip_check(hipEventCreate(&e), "hipEventCreate");
+    R.timing = on != 0; if (on) R.kernel_ms[0] = R.kernel_ms[1] = 0;
+  });
+}
+int mkp_internal_skip_row_fetch(mkp_ctx* c, int on) { if (!c) return MKP_E_INVALID; c->skip_row_fetch = on != 0; return MKP_OK; }
+
+int mkp_stats_begin(mkp_ctx* c, const mkp_region* regions, uint32_t n, const uint32_t* codes, uint32_t n_codes, uint64_t min_coverage) {
+  if (!c || (!regions && n) || (!codes && n_codes)) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::RegionStats& R = c->rstats;
+    R.open = false;
+    for (uint32_t i = 0; i < n; i++) {
+      if (regions[i].start > regions[i].end) throw Error(MKP_E_INVALID, "region " + std::to_string(i) + ": start > end");
+      if (regions[i].strand_rule < 1 || regions[i].strand_rule > 3) throw Error(MKP_E_INVALID, "region " + std::to_string(i)
+          + ": strand_rule must be 1 ('+'), 2 ('-') or 3 (both)");
+    }
+    R.fixed_codes.assign(codes, codes + n_codes); std::sort(R.fixed_codes.begin(), R.fixed_codes.end());
+    R.fixed_codes.erase(std::unique(R.fixed_codes.begin(), R.fixed_codes.end()), R.fixed_codes.end());
+    for (uint32_t k : R.fixed_codes) if (!k) throw Error(MKP_E_INVALID, "0 is not a mod code");
+    if (R.fixed_codes.size() > MKP_STATS_MAX_CODES) throw Error(MKP_E_UNSUPPORTED, "region statistics hold at most "
+        + std::to_string(MKP_STATS_MAX_CODES) + " distinct mod codes per run");
+    R.fixed = n_codes != 0; R.min_cov = min_coverage; R.n_regions = n;
+    R.region_tid.resize(n); R.tid_range.clear(); R.tids_with_rows.clear(); R.most_per_tid = 0;
+    // the regions grouped by contig, caller order inside a contig; `out` = the caller's index
+    std::vector<uint32_t> order(n); for (uint32_t i = 0; i < n; i++) { order[i] = i; R.region_tid[i] = regions[i].tid; }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return regions[a].tid < regions[b].tid; });
+    std::vector<MkpStatsRegion> dev(n);
+    for (uint32_t k = 0; k < n; k++) { const mkp_region& g = regions[order[k]]; dev[k] = {g.start, g.end, g.strand_rule, order[k]};
+      if (g.tid < 0) continue;
+      auto it = R.tid_range.find(g.tid);
+      if (it == R.tid_range.end()) R.tid_range[g.tid] = {k, k + 1}; else it->second.second = k + 1;
+    }
+    for (auto& kv : R.tid_range) R.most_per_tid = std::max(R.most_per_tid, kv.second.second - kv.second.first);
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    hip_check(hipStreamSynchronize(c->stream), "sync");   // (a previous session's kernels)
+    const size_t n1 = std::max<size_t>(n, 1), m1 = std::max<size_t>(R.most_per_tid, 1);
+    R.d_regions.ensure(n1 * sizeof(MkpStatsRegion)); R.d_out.ensure(n1 * 2 * MKP_STATS_MAX_CODES * 8); R.d_seen.ensure(n1 * 4);
+    R.d_misc.ensure(kStatsMiscBytes); R.d_lo.ensure(m1 * 4); R.d_hi.ensure(m1 * 4); R.d_cnt.ensure(m1 * 4); R.d_off.ensure((m1 + 1) * 8);
+    h2d_copy(R.d_regions.p, dev.data(), (size_t)n * sizeof(MkpStatsRegion));
+    uint32_t misc[kStatsMiscBytes / 4] = {0}; for (size_t k = 0; k < R.fixed_codes.size(); k++) misc[k] = R.fixed_codes[k];
+    h2d_copy(R.d_misc.p, misc, sizeof(misc));
+    hip_check(hipMemsetAsync(R.d_out.p, 0, n1 * 2 * MKP_STATS_MAX_CODES * 8, c->stream), "memset");
+    hip_check(hipMemsetAsync(R.d_seen.p, 0, n1 * 4, c->stream), "memset");
+    hip_check(hipStreamSynchronize(c->stream), "sync");
+    R.open = true;
+  });
+}
+
+int mkp_stats_add_resident(mkp_ctx* c) {
+  if (!c) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    if (!c->rstats.open) throw Error(MKP_E_INVALID, "mkp_stats_begin first");
+    if (!c->partition_tags.empty()) throw Error(MKP_E_INVALID,
+        "region statistics need the rows in genome order: with partition tags set they come grouped by key");
+    if (!c->resident || c->resident_hemi || c->hemi) throw Error(MKP_E_INVALID,
+        "no pileup rows are resident: call mkp_shard_run first (pileup-hemi rows are pattern counts, not bedMethyl rows)");
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    const MkpRowsDev& r = c->rows_dst;
+    stats_launch(c, c->shard.tid, r.pos, r.info, r.code, r.n_valid, r.n_mod, c->stats.n_rows);
+  });
+}
+
+int mkp_stats_add_rows(mkp_ctx* c, int32_t tid, const mkp_rows* rows) {
+  if (!c || !rows) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::RegionStats& R = c->rstats;
+    if (!R.open) throw Error(MKP_E_INVALID, "mkp_stats_begin first");
+    const uint64_t n = rows->n_rows;
+    if (n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
+    if (n && (!rows->pos || !rows->strand || !rows->code_repr || !rows->n_valid || !rows->n_mod)) throw Error(MKP_E_INVALID,
+        "pos, strand, code_repr, n_valid and n_mod are needed");
+    std::vector<uint32_t> info(n);
+    for (uint64_t i = 0; i < n; i++) {
+      if (i && rows->pos[i] < rows->pos[i - 1]) throw Error(MKP_E_INVALID, "rows must be ascending in pos (row " + std::to_string(i) + ")");
+      const uint8_t s = rows->strand[i];
+      if (s != '+' && s != '-' && s != '.') throw Error(MKP_E_INVALID, "strand must be '+', '-' or '.' (row " + std::to_string(i) + ")");
+      if (!rows->code_repr[i]) throw Error(MKP_E_INVALID, "0 is not a mod code (row " + std::to_string(i) + ")");
+      info[i] = s == '+' ? 0u : s == '-' ? 1u : 2u;
+    }
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    hip_check(hipStreamSynchronize(c->stream), "sync");   // the previous call's kernels read the upload buffer
+    const size_t col = ((size_t)n + 63) & ~(size_t)63;
+    R.d_rows.ensure(std::max<size_t>(col, 64) * 20);
+    uint32_t* d = R.d_rows.as<uint32_t>();
+    const uint32_t* src[5] = {rows->pos, info.data(), rows->code_repr, rows->n_valid, rows->n_mod};
+    for (int k = 0; k < 5; k++) h2d_copy(d + (size_t)k * col, src[k], (size_t)n * 4);
+    stats_launch(c, tid, d, d + col, d + 2 * col, d + 3 * col, d + 4 * col, n);
+  });
+}
+
+int mkp_stats_get(mkp_ctx* c, mkp_stats_out* out) {
+  if (!c || !out) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::RegionStats& R = c->rstats;
+    if (!R.open) throw Error(MKP_E_INVALID, "mkp_stats_begin first");
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    uint32_t misc[kStatsMiscBytes / 4];
+    d2h_copy(misc, R.d_misc.p, sizeof(misc), c->stream);
+    if (misc[MKP_STATS_MAX_CODES] & MKP_STATS_ERR_CODES) throw Error(MKP_E_UNSUPPORTED, "the rows inside the regions carry more than "
+        + std::to_string(MKP_STATS_MAX_CODES) + " distinct mod codes: region statistics hold at most that many per run");
+    const uint32_t n = R.n_regions;
+    std::vector<uint64_t> tab((size_t)n * 2 * MKP_STATS_MAX_CODES); std::vector<uint32_t> seen(n);
+    d2h_copy(tab.data(), R.d_out.p, tab.size() * 8, c->stream); d2h_copy(seen.data(), R.d_seen.p, (size_t)n * 4, c->stream);
+    // columns: the given codes (slot = place in the sorted list), or the slots some region counted a row in, by code
+    std::vector<std::pair<uint32_t, uint32_t>> cols;   // code, slot
+    if (R.fixed) for (uint32_t k = 0; k < R.fixed_codes.size(); k++) cols.push_back({R.fixed_codes[k], k});
+    else { uint32_t any = 0; for (uint32_t m : seen) any |= m;
+      for (uint32_t s = 0; s < MKP_STATS_MAX_CODES; s++) if ((any >> s) & 1u) cols.push_back({misc[s], s});
+      std::sort(cols.begin(), cols.end()); }
+    const size_t nc = cols.size();
+    R.h_codes.resize(nc); R.h_mod.assign((size_t)n * nc, 0); R.h_valid.assign((size_t)n * nc, 0); R.h_has.resize(n);
+    for (size_t k = 0; k < nc; k++) R.h_codes[k] = cols[k].first;
+    for (uint32_t r = 0; r < n; r++) {
+      R.h_has[r] = R.tids_with_rows.count(R.region_tid[r]) && R.region_tid[r] >= 0 ? 1 : 0;
+      for (size_t k = 0; k < nc; k++) { const uint64_t* e = &tab[((size_t)r * MKP_STATS_MAX_CODES + cols[k].second) * 2];
+        R.h_mod[(size_t)r * nc + k] = e[0]; R.h_valid[(size_t)r * nc + k] = e[1]; }
+    }
+    out->n_regions = n; out->n_codes = (uint32_t)nc; out->code_repr = R.h_codes.data(); out->n_mod = R.h_mod.data();
+    out->n_valid = R.h_valid.data(); out->contig_has_rows = R.h_has.data();
+  });
 }
 
 }  // extern "C"

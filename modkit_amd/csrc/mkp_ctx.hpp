@@ -4,7 +4,9 @@
 #include <hip/hip_runtime_api.h>
 
 #include <chrono>
+#include <map>
 #include <mutex>
+#include <set>
 #include <vector>
 
 #include "mkp_pack.hpp"
@@ -183,6 +185,19 @@ struct mkp_ctx {
   // the read-independent part of a focus shard's plan (slot bitmap, its running popcount, the slot positions, their uploads), made ahead
   // of the reads by mkp_internal_shard_preplan while the device ingest of the same shard is still running
   struct WindowPlan { bool valid = false; std::vector<uint32_t> slotbm, wpfx, slot_pos; } wplan;
+  // region statistics (mkp_stats_begin .. mkp_stats_get, mkp_stats.hip): the run-long table out[region][slot] = {n_mod, n_valid} (u64), the
+  // per-region mask of slots with a counted row and the slots' codes stay in HBM between the calls; regions are uploaded once, grouped by contig
+  struct RegionStats {
+    bool open = false, fixed = false, timing = false; uint32_t n_regions = 0, most_per_tid = 0; uint64_t min_cov = 1;
+    std::vector<uint32_t> fixed_codes;                                  // sorted, distinct
+    std::vector<int32_t> region_tid;                                    // caller order
+    std::map<int32_t, std::pair<uint32_t, uint32_t>> tid_range;         // contig -> [first, last) of d_regions
+    std::set<int32_t> tids_with_rows;
+    mkp::DevBuf d_regions, d_out, d_seen, d_misc /* codes[16], error word, pad, chunk total (u64) */, d_lo, d_hi, d_cnt, d_off, d_rows;
+    std::vector<uint32_t> h_codes; std::vector<uint64_t> h_mod, h_valid; std::vector<uint8_t> h_has;   // mkp_stats_get
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; double kernel_ms[2] = {0, 0};   // timing: bounds + scan, reduce (summed over the calls)
+  } rstats;
+  bool skip_row_fetch = false;   // `--region-stats-only`: mkp_shard_run leaves the rows in HBM (no column read-back, n_rows = 0 in its output)
   // device ingest of indexed BAMs (mkp_ingest_host.cpp): created on first use, lives with the context (staging + window buffers are reused)
   struct mkp_dev_ingest* ingest = nullptr;
   mkp_stats stats;
@@ -216,3 +231,7 @@ struct mkp_dev_inflater;
 mkp_dev_inflater* mkp_internal_inflater_create(int device);
 void mkp_internal_inflater_destroy(mkp_dev_inflater* d);
 bool mkp_internal_device_inflate(void* user, const mkp::InflateJob& job);
+// region statistics: time the kernels with events (one stream sync per call) / the summed times [bounds + scan, reduce] in ms;
+// `--region-stats-only`: the runs that follow leave their rows in HBM
+extern "C" int mkp_internal_stats_timing(mkp_ctx* c, int on, double ms_out[2]);
+extern "C" int mkp_internal_skip_row_fetch(mkp_ctx* c, int on);

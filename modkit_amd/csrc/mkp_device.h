@@ -279,6 +279,13 @@ struct MkpRowsDev {  // SoA row buffers (44 B / row)
   uint32_t* n_valid; uint32_t* n_mod; uint32_t* n_can; uint32_t* n_other;
   uint32_t* n_del; uint32_t* n_fail; uint32_t* n_diff; uint32_t* n_nocall;
 };
+// ---- region statistics (mkp_stats.hip): a region of the contig whose rows are being added, and where its totals go.  The run-long
+// table holds MKP_STATS_MAX_CODES slots of {n_mod, n_valid} (u64) per region, a 32-bit mask of the slots with a counted row per region,
+// and the code of every slot (0 = free) in a table of its own.
+#define MKP_STATS_CHUNK 4096u       // rows per (region, chunk) work item of mkp_stats_reduce
+#define MKP_STATS_MAX_CODES 16      // distinct mod codes per run (the pileup itself allows MKP_MAX_SLOTS (base, code) pairs)
+#define MKP_STATS_ERR_CODES 1u      // device error bit: a seventeenth code
+struct MkpStatsRegion { uint32_t start, end; uint32_t rule /* 1 '+', 2 '-', 3 both */; uint32_t out /* index into the run's table */; };
 #ifdef __cplusplus
 static_assert(sizeof(MkpWork) == 64, "work record is 16 dwords");
 static_assert(sizeof(MkpFusedDesc) == 64 && sizeof(MkpVisit) == 32 && sizeof(MkpPlaneEnt) == 16, "slot pipeline records");

@@ -20,6 +20,7 @@
 #include "mkp_ctx.hpp"
 #include "mkp_ingest_host.hpp"
 #include "mkp_focus.hpp"
+#include "mkp_regions.hpp"
 #include "mkp_writer.hpp"
 #include "mkp_rand.hpp"
 
@@ -93,6 +94,11 @@ struct Args {
   bool bedgraph = false;
     /* --bedgraph: the output path is a directory of <code>[_<motif>]_<strand>.bedgraph files (BedGraphWriter, writers.rs:264-381) */
   bool bgzf = false;   /* write the bedMethyl as BGZF + a .tbi index (what `bgzip` + `tabix -p bed` make of the reference's output) */
+  /* --region-stats <bed>: `modkit stats` over this run's rows, reduced on the device from the rows in HBM (mkp_stats.hip); the table goes to
+     --region-stats-out; --region-stats-codes / -min-coverage / -no-header = its --mod-codes / --min-coverage / --no-header;
+     --region-stats-only: the rows are neither read back nor written (the out.bed positional is not created) */
+  std::string region_stats, region_stats_out; std::vector<uint32_t> region_stats_codes; uint64_t region_stats_min_cov = 1;
+  bool region_stats_no_header = false, region_stats_only = false;
 };
 
 struct RegionSpec { std::string name; uint32_t start, end; };
@@ -1083,6 +1089,7 @@ struct Counters {
   double load_ms = 0, thr_ms = 0, fetch_wait_early_ms = 0, grid_wait_ms = 0, callback_ms = 0, fetch_wait_ms = 0;
   double kernel_ms = 0, pack_ms = 0, h2d_ms = 0, d2h_ms = 0, dec_ms = 0, pil_ms = 0, row_ms = 0, write_ms = 0;
   uint64_t positions = 0, processed = 0, skipped = 0, n_shards = 0;
+  uint64_t dev_rows = 0;   // rows the device produced (--region-stats-only: they never reach the writer, whose count is the report's otherwise)
   uint64_t n_wide = 0;   // shards that ran the wide-tally accumulate kernels (a column over 65 535 records deep)
   double ingest_ms[5] = {0, 0, 0, 0, 0}, ingest_kernel_ms = 0; uint64_t ingest_blocks = 0, ingest_records = 0, ingest_comp = 0, ingest_raw = 0;
   bool resident_used = false;   // the threshold sample came from shards in HBM
@@ -1095,7 +1102,7 @@ struct Counters {
     n_shards++; n_wide += ctx->wide ? 1u : 0u;
     mkp_stats st; mkp_get_stats(ctx, &st); kernel_ms += st.kernel_ms; dec_ms += st.decode_kernel_ms; pil_ms += st.pileup_kernel_ms;
       row_ms += st.rows_kernel_ms;
-        pack_ms += st.pack_ms; h2d_ms += st.h2d_ms; d2h_ms += st.d2h_ms;
+        pack_ms += st.pack_ms; h2d_ms += st.h2d_ms; d2h_ms += st.d2h_ms; dev_rows += st.n_rows;
     positions += bp; processed += rows.processed_records; skipped += rows.skipped_records;
   }
   void report(mkp_run_report* rep, uint64_t n_rows, double focus_ms, const mkp_caller& kc) const {
@@ -1279,6 +1286,7 @@ class Outputs {
   // the checks throw in the order of the flags' resolution (subcommand.rs:328-363 for --bedgraph)
   Outputs(const Args& a, mkp_ctx* ctx, const std::vector<std::string>& labels) : a(a), partitioned(!a.partition_tags.empty()) {
     wr.mixed = a.mixed_delim; wr.labels = labels;
+    if (a.region_stats_only) return;   // no rows reach the host: nothing is opened (every shard hands write() zero rows)
     if (a.bedgraph) {   // (no header, no mixed delimiters; the path is a directory)
       if (a.with_header || a.mixed_delim || a.bgzf || a.hemi || a.plan_only) throw Error(MKP_E_INVALID,
           "--bedgraph cannot be combined with --with-header, --mixed-delim, --bgzf or --plan-only");
@@ -1444,6 +1452,7 @@ void run_shards(const Args& a, Options& o, mkp_ctx* ctx, const ShardReader& read
       must(ctx, mkp_shard_run(ctx, &rows));
       mark("  mkp_shard_run returned");
       if (a.rerun) must(ctx, mkp_shard_rerun(ctx, a.rerun, &rows));   // measurement aid: warm, averaged kernel times in --stats
+      if (!a.region_stats.empty()) must(ctx, mkp_stats_add_resident(ctx));   // the rows are still in HBM: this shard's share of every region
       auto t_w = std::chrono::steady_clock::now();
       out.write(rec.name, rows);
       c.write_ms += ms_since(t_w);
@@ -1520,6 +1529,17 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
   if (!a.plan_only) must(ctx, mkp_set_caller(ctx, &o.kc));
   g.join_walk();
   Outputs out(a, ctx, o.labels);
+  // --region-stats: the regions (contigs by the BAM header's names) and the run-long table in HBM; --region-stats-only: no row read-back
+  mkp_region_set rset;
+  struct RowFetchGuard { mkp_ctx* c; ~RowFetchGuard() { if (c) { mkp_internal_skip_row_fetch(c, 0); mkp_internal_stats_timing(c, 0, nullptr); } } } fetch_guard{nullptr};
+  if (!a.region_stats.empty()) {
+    rset = parse_regions_bed(a.region_stats, [&](const std::string& chrom) { return bam.tid_of(chrom); });
+    must(ctx, mkp_stats_begin(ctx, rset.regions.data(), (uint32_t)rset.regions.size(), a.region_stats_codes.data(),
+        (uint32_t)a.region_stats_codes.size(), a.region_stats_min_cov));
+    fetch_guard.c = ctx;
+    if (a.stats) must(ctx, mkp_internal_stats_timing(ctx, 1, nullptr));
+    if (a.region_stats_only) must(ctx, mkp_internal_skip_row_fetch(ctx, 1));
+  }
   build_plan(plan, a, kn, bam, o, g, size, !ahead.empty(), mark);
   // (thresholds known before the plan: the shards go ahead of the loop from here)
   if (ahead.empty() && plan.shards.size() > 1 && !kn.no_ahead) ahead.from_plan(plan.shards, records, o.bf);
@@ -1528,8 +1548,19 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
   { auto t_w = std::chrono::steady_clock::now(); out.finish(); c.write_ms += ms_since(t_w); }
   out.close();
   mark("output closed");
-  if (rep) c.report(rep, out.rows(), g.focus_ms, o.kc);
-  if (a.stats) c.print_stats(a, bam, out.rows(), g.focus_ms, dev_ingest, ahead);
+  if (!a.region_stats.empty()) {
+    auto t_w = std::chrono::steady_clock::now();
+    mkp_stats_out table; must(ctx, mkp_stats_get(ctx, &table));
+    write_text_file(a.region_stats_out, stats_table_text(rset, table, !a.region_stats_no_header, f32_display));
+    c.write_ms += ms_since(t_w);
+    if (a.stats) { double ms[2] = {0, 0}; mkp_internal_stats_timing(ctx, 0, ms);
+      fprintf(stderr, "[mkpileup] region stats: %zu regions, %u codes; kernels bounds+scan %.3f ms, reduce %.3f ms (summed over the shards)\n",
+          rset.regions.size(), table.n_codes, ms[0], ms[1]); }
+    mark("region stats table written");
+  }
+  const uint64_t n_rows_out = a.region_stats_only ? c.dev_rows : out.rows();
+  if (rep) c.report(rep, n_rows_out, g.focus_ms, o.kc);
+  if (a.stats) c.print_stats(a, bam, n_rows_out, g.focus_ms, dev_ingest, ahead);
   return MKP_OK;
 }
 
@@ -1540,7 +1571,7 @@ void parse_args(int argc, const char* const* argv, Args* out, bool need_position
     std::string s = argv[i];
     auto val = [&]() { if (i + 1 >= argc) throw Error(MKP_E_INVALID, "missing value for " + s); return std::string(argv[++i]); };
     if (hemi && (s == "--preset" || s == "--combine-strands" || s == "--with-header" || s == "--header" || s == "--partition-tag" || s == "--prefix"
-        || s == "--bedgraph" || s == "--plan-only"))
+        || s == "--bedgraph" || s == "--plan-only" || s.compare(0, 14, "--region-stats") == 0))
       throw Error(MKP_E_INVALID, "unexpected argument '" + s + "' for pileup-hemi");
     if (hemi && (s == "-o" || s == "--out-bed")) { a.out_bed = val(); continue; }
     if (s == "--region") a.region = val(); else if (s == "--max-depth") a.max_depth = (uint32_t)std::stoul(val());
@@ -1576,6 +1607,13 @@ void parse_args(int argc, const char* const* argv, Args* out, bool need_position
     else if (s == "--partition-tag") a.partition_tags.push_back(val()); else if (s == "--prefix") a.prefix = val();
     else if (s == "--bgzf") a.bgzf = true;
     else if (s == "--bedgraph") a.bedgraph = true;
+    else if (s == "--region-stats") a.region_stats = val(); else if (s == "--region-stats-out") a.region_stats_out = val();
+    else if (s == "--region-stats-codes") { const std::string v = val();   // comma-delimited, repeatable (ModCodeRepr::parse each)
+      for (size_t p0 = 0;;) { const size_t p1 = v.find(',', p0); const std::string one = v.substr(p0, p1 == std::string::npos ? p1 : p1 - p0);
+        uint32_t code; if (!parse_code(one, &code)) throw Error(MKP_E_INVALID, "bad mod code '" + one + "' in --region-stats-codes");
+        a.region_stats_codes.push_back(code); if (p1 == std::string::npos) break; p0 = p1 + 1; } }
+    else if (s == "--region-stats-min-coverage") a.region_stats_min_cov = std::stoull(val());
+    else if (s == "--region-stats-no-header") a.region_stats_no_header = true; else if (s == "--region-stats-only") a.region_stats_only = true;
     else if (!s.empty() && s[0] == '-' && s != "-") throw Error(MKP_E_INVALID, "unknown flag " + s);
     else pos.push_back(s);
   }
@@ -1586,6 +1624,17 @@ void parse_args(int argc, const char* const* argv, Args* out, bool need_position
       a.out_bed = pos[1]; }
   else if (!pos.empty()) throw Error(MKP_E_INVALID, "unexpected positional argument " + pos[0]);
   if (a.world == 0 || a.rank >= a.world) throw Error(MKP_E_INVALID, "bad --gpus-rank/--gpus-world");
+  if (a.region_stats.empty()) { if (!a.region_stats_out.empty() || !a.region_stats_codes.empty() || a.region_stats_no_header || a.region_stats_only
+      || a.region_stats_min_cov != 1) throw Error(MKP_E_INVALID, "the --region-stats-* flags need --region-stats <regions.bed>"); }
+  else {
+    if (a.region_stats_out.empty()) throw Error(MKP_E_INVALID, "--region-stats needs --region-stats-out <table.tsv>");
+    if (!a.partition_tags.empty()) throw Error(MKP_E_INVALID,
+        "--region-stats cannot be combined with --partition-tag: the rows of a partitioned run come grouped by key, not in genome order");
+    if (a.plan_only) throw Error(MKP_E_INVALID, "--region-stats cannot be combined with --plan-only");
+    if (a.region_stats_only && (a.bedgraph || a.bgzf)) throw Error(MKP_E_INVALID, "--region-stats-only writes no rows: drop --bedgraph / --bgzf");
+    if (a.world > 1) throw Error(MKP_E_UNSUPPORTED,
+        "--region-stats with --gpus-world > 1: the ranks' tables would have to be summed (an all-reduce that is not implemented)");
+  }
 }
 
 }  // namespace
@@ -1600,6 +1649,32 @@ extern "C" int mkp_internal_bedgraph_write(const char* dir, const char* prefix, 
     bg.write(chrom, *rows); bg.finish();
     return MKP_OK;
   } catch (const Error& e) { return e.status; } catch (const std::exception&) { return MKP_E_INVALID; }
+}
+
+// `modkit stats`, host halves (include/mkpileup.h): the regions BED and the table, no device involved
+extern "C" int mkp_host_parse_regions(const char* bed_path, const char* const* contig_names, uint32_t n_contigs, mkp_region_set** out, char* errbuf,
+    size_t errbuf_len) {
+  auto fail = [&](int st, const std::string& m) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", m.c_str()); } return st; };
+  if (!bed_path || !out || (!contig_names && n_contigs)) return fail(MKP_E_INVALID, "bad argument");
+  *out = nullptr;
+  try {
+    std::map<std::string, int> tids; for (uint32_t k = 0; k < n_contigs; k++) tids.emplace(contig_names[k], (int)k);
+    std::unique_ptr<mkp_region_set> set(new mkp_region_set(parse_regions_bed(bed_path, [&](const std::string& chrom) { auto it = tids.find(chrom);
+      return it == tids.end() ? -1 : it->second; })));
+    *out = set.release();
+    return MKP_OK;
+  } catch (const Error& e) { return fail(e.status, e.what()); }
+  catch (const std::exception& e) { return fail(MKP_E_INVALID, e.what()); }
+}
+extern "C" uint32_t mkp_region_set_size(const mkp_region_set* set) { return set ? (uint32_t)set->regions.size() : 0u; }
+extern "C" const mkp_region* mkp_region_set_regions(const mkp_region_set* set) { return set ? set->regions.data() : nullptr; }
+extern "C" const char* mkp_region_set_chrom(const mkp_region_set* set, uint32_t i) { return set && i < set->chrom.size() ? set->chrom[i].c_str() : nullptr; }
+extern "C" const char* mkp_region_set_name(const mkp_region_set* set, uint32_t i) { return set && i < set->name.size() ? set->name[i].c_str() : nullptr; }
+extern "C" void mkp_region_set_free(mkp_region_set* set) { delete set; }
+extern "C" int mkp_host_stats_table(const mkp_region_set* set, const mkp_stats_out* counts, int with_header, const char* out_path) {
+  if (!set || !counts || !out_path) return MKP_E_INVALID;
+  try { write_text_file(out_path, stats_table_text(*set, *counts, with_header != 0, f32_display)); return MKP_OK; }
+  catch (const Error& e) { return e.status; } catch (const std::exception&) { return MKP_E_INVALID; }
 }
 
 extern "C" int mkp_pileup_main(int argc, const char* const* argv, char* errbuf, size_t errbuf_len) {

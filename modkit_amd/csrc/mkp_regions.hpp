@@ -1,0 +1,137 @@
+// Host halves of `modkit stats` (EntryStats::run, src/stats/subcommand.rs:65-206): the regions BED and the table text.  No device here.
+#pragma once
+#include <cstdio>
+#include <fstream>
+#include <string>
+#include <vector>
+
+#include "mkp_pack.hpp"
+
+struct mkp_region_set {
+  std::vector<mkp_region> regions;          // tid = index into the contig names given to the parser, -1 = not among them
+  std::vector<std::string> chrom, name;     // name "." = the line has none
+};
+
+namespace mkp {
+
+// One line through GenomeRegion::parse_bed_line (src/util.rs:864-878) and, for the stranded form, the score and strand that follow
+// (880-909).  The reference's pieces (src/parsing_utils.rs): a string = one or more characters that are no blank, tab, CR or LF; a number =
+// at least one of those four ("multispace") and then decimal digits that fit a u64; the name = any run of the four, then one or more
+// characters that are no tab, CR or LF (so a name may hold blanks) — when that fails the line has no name and nothing is consumed.
+struct BedLineParser {
+  const std::string& l; size_t i = 0;
+  explicit BedLineParser(const std::string& line) : l(line) {}
+  static bool ms(char c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n'; }
+  bool string(std::string* out) { const size_t s = i; while (i < l.size() && !ms(l[i])) i++; out->assign(l, s, i - s); return i > s; }
+  bool multispace1() { const size_t s = i; while (i < l.size() && ms(l[i])) i++; return i > s; }
+  bool digits(uint64_t* out) {
+    if (!multispace1()) return false;
+    const size_t s = i; uint64_t v = 0;
+    while (i < l.size() && l[i] >= '0' && l[i] <= '9') { const uint64_t d = (uint64_t)(l[i] - '0');
+      if (v > (0xffffffffffffffffull - d) / 10) return false;
+      v = v * 10 + d; i++; }
+    *out = v; return i > s;
+  }
+  bool name(std::string* out) {
+    const size_t keep = i; while (i < l.size() && ms(l[i])) i++;
+    const size_t s = i; while (i < l.size() && l[i] != '\t' && l[i] != '\r' && l[i] != '\n') i++;
+    if (i == s) { i = keep; return false; }
+    out->assign(l, s, i - s); return true;
+  }
+  // nom's `float` after multispace, or a lone '.': [+-] then digits [. digits] | . digits, an optional exponent; or inf / infinity / nan
+  bool score() {
+    const size_t keep = i;
+    if (!multispace1()) return false;
+    const size_t s0 = i; size_t j = i;
+    if (j < l.size() && (l[j] == '+' || l[j] == '-')) j++;
+    auto word = [&](const char* w) { size_t k = 0; while (w[k] && j + k < l.size() && (l[j + k] | 0x20) == w[k]) k++; return w[k] == 0 ? k : (size_t)0; };
+    size_t w;
+    if ((w = word("infinity")) || (w = word("inf")) || (w = word("nan"))) { i = j + w; return true; }
+    auto dig = [&](size_t k) { return k < l.size() && l[k] >= '0' && l[k] <= '9'; };
+    size_t e = j; while (dig(e)) e++;
+    bool num = e > j;
+    if (num) { if (e < l.size() && l[e] == '.') { e++; while (dig(e)) e++; } }
+    else if (e < l.size() && l[e] == '.' && dig(e + 1)) { e++; while (dig(e)) e++; num = true; }
+    if (num) {
+      if (e < l.size() && (l[e] == 'e' || l[e] == 'E')) { size_t x = e + 1; if (x < l.size() && (l[x] == '+' || l[x] == '-')) x++;
+        const size_t d = x; while (dig(x)) x++; if (x > d) e = x; }
+      i = e; return true;
+    }
+    if (s0 < l.size() && l[s0] == '.') { i = s0 + 1; return true; }   // consume_dot
+    i = keep; return false;
+  }
+  bool strand(uint8_t* rule) {
+    if (!multispace1() || i >= l.size()) return false;
+    const char c = l[i++]; *rule = c == '+' ? 1 : c == '-' ? 2 : c == '.' ? 3 : 0; return *rule != 0;
+  }
+};
+
+template <class TidOf> mkp_region_set parse_regions_bed(const std::string& path, TidOf tid_of) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) throw Error(MKP_E_IO, "failed to open regions BED " + path);
+  std::vector<std::string> lines; std::string line;
+  while (std::getline(f, line)) { if (!line.empty() && line.back() == '\r') line.pop_back(); lines.push_back(line); }   // BufRead::lines
+  size_t first = 0; while (first < lines.size() && !lines[first].empty() && lines[first][0] == '#') first++;
+  if (first >= lines.size()) throw Error(MKP_E_INVALID, "failed to inspect regions BED, no valid lines: " + path);
+  size_t fields = 1; for (char c : lines[first]) if (c == '\t') fields++;
+  const bool stranded = fields > 4;
+  mkp_region_set out;
+  for (size_t k = 0; k < lines.size(); k++) {
+    BedLineParser p(lines[k]); std::string chrom, name; uint64_t s = 0, e = 0; uint8_t rule = 3;
+    bool ok = p.string(&chrom) && p.digits(&s) && p.digits(&e);
+    bool has_name = false;
+    if (ok) { has_name = p.name(&name); if (stranded) ok = p.score() && p.strand(&rule); }
+    if (!ok) throw Error(MKP_E_INVALID, std::string("failed to parse ") + (stranded ? "stranded (bed4+)" : "un-stranded (bed3/4)") + " line "
+        + std::to_string(k + 1) + " of " + path + ": " + lines[k]);
+    if (s > e) throw Error(MKP_E_INVALID, "line " + std::to_string(k + 1) + " of " + path + ": start > end");
+    if (e > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "line " + std::to_string(k + 1) + " of " + path + ": coordinate beyond 2^32 - 1");
+    for (const std::string* t : {&chrom, &name}) if (t->find('"') != std::string::npos) throw Error(MKP_E_UNSUPPORTED, "line "
+        + std::to_string(k + 1) + " of " + path + ": a quote in the contig or region name needs csv quoting, which is not written");
+    mkp_region g; memset(&g, 0, sizeof(g)); g.tid = (int32_t)tid_of(chrom); g.start = (uint32_t)s; g.end = (uint32_t)e; g.strand_rule = rule;
+    out.regions.push_back(g); out.chrom.push_back(chrom); out.name.push_back(has_name ? name : ".");
+  }
+  if (out.regions.empty()) throw Error(MKP_E_INVALID, "failed to load any regions from " + path);
+  return out;
+}
+
+inline std::string code_text(uint32_t code) { return (code & 0x80000000u) ? std::to_string(code & 0x7fffffffu) : std::string(1, (char)code); }
+
+// MethylationStats::header / into_row (src/stats/mod.rs:24-51) through a tab-delimited csv writer; `f32_text` = f32 Display
+template <class F32Text> std::string stats_table_text(const mkp_region_set& set, const mkp_stats_out& t, bool header, F32Text f32_text) {
+  if (t.n_regions != set.regions.size()) throw Error(MKP_E_INVALID, "the counts are not those of this region set");
+  std::string s;
+  if (header) { s = "chrom\tstart\tend\tname\tstrand";
+    for (uint32_t k = 0; k < t.n_codes; k++) { const std::string c = code_text(t.code_repr[k]);
+      s += "\tcount_" + c + "\tcount_valid_" + c + "\tpercent_" + c; }
+    s += '\n'; }
+  // (tens of thousands of regions: the shortest-digits search of the f32 text is a microsecond a cell — pieces on the host pool, joined in order)
+  const size_t n_pieces = t.n_regions >= 4096 ? 64 : 1;
+  std::vector<std::string> piece(n_pieces);
+  auto rows_of = [&](size_t pc) {
+    std::string& o = piece[pc];
+    for (uint32_t r = (uint32_t)((uint64_t)t.n_regions * pc / n_pieces), r1 = (uint32_t)((uint64_t)t.n_regions * (pc + 1) / n_pieces); r < r1; r++) {
+      if (!t.contig_has_rows[r]) continue;
+      const mkp_region& g = set.regions[r];
+      o += set.chrom[r]; o += '\t'; o += std::to_string(g.start); o += '\t'; o += std::to_string(g.end); o += '\t'; o += set.name[r]; o += '\t';
+      o += g.strand_rule == 1 ? '+' : g.strand_rule == 2 ? '-' : '.';
+      for (uint32_t k = 0; k < t.n_codes; k++) {
+        const uint64_t nm = t.n_mod[(size_t)r * t.n_codes + k], nv = t.n_valid[(size_t)r * t.n_codes + k];
+        const float pct = nv == 0 ? 0.0f : ((float)nm / (float)nv) * 100.0f;   // ModPositionInfo::percent_modified (src/util.rs:920-936)
+        o += '\t'; o += std::to_string(nm); o += '\t'; o += std::to_string(nv); o += '\t'; o += f32_text(pct);
+      }
+      o += '\n';
+    }
+  };
+  if (n_pieces > 1) HostPool::get().parallel(n_pieces, rows_of); else rows_of(0);
+  for (auto& o : piece) s += o;
+  return s;
+}
+
+inline void write_text_file(const std::string& path, const std::string& text) {
+  FILE* f = fopen(path.c_str(), "w");
+  if (!f) throw Error(MKP_E_IO, "failed to make output file " + path);
+  const bool ok = fwrite(text.data(), 1, text.size(), f) == text.size(); const bool closed = fclose(f) == 0;
+  if (!ok || !closed) throw Error(MKP_E_IO, "short write on " + path);
+}
+
+}  // namespace mkp

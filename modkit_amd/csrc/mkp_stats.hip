@@ -1,0 +1,167 @@
+// Region statistics (`modkit stats`, src/stats/mod.rs:53-101) over bedMethyl rows that are already in HBM: per region and mod code,
+// n_mod = sum of N_mod and n_valid = sum of N_valid_cov over the rows whose position lies in [start, end), whose strand overlaps the
+// region's rule (StrandRule::overlaps, src/util.rs:310-318) and whose N_valid_cov reaches --min-coverage.
+//
+// Input: the SoA row columns of one piece of one contig, ascending in `pos`, and the regions of that contig (any order; they may overlap,
+// nest and repeat, so this is not one segmented scan).  Three launches on the caller's stream, no host round trip between them:
+//   mkp_stats_bounds   one thread per region: lower_bound(start) / lower_bound(end) in `pos` and the number of 4096-row chunks in between
+//   mkp_stats_scan     one workgroup: exclusive prefix sum of the chunk counts (64-bit) and their total
+//   mkp_stats_reduce   one WAVE per (region, chunk) work item, four to a workgroup, a fixed grid striding over the items: 64 rounds of
+//                      64 coalesced rows (info, code, n_valid, n_mod: 16 of a row's 44 bytes), per-lane 64-bit sums per code slot, one
+//                      butterfly per touched slot and ONE 64-bit atomic add instruction per item: lane 2 s adds n_mod, lane 2 s + 1
+//                      n_valid of slot s — 256 contiguous bytes of the region's line of the run-long table.
+// A whole-chromosome region is 660 items spread over the grid; thirty thousand 50-row regions are 7 500 workgroups' worth of waves.
+// The table out[region][slot] lives for the whole run: pieces (shards) add into it, so a region that straddles seams gets every row once.
+// Code slots: at most MKP_STATS_MAX_CODES per run.  With a fixed list the host uploads the table and other codes are not counted; without
+// one, the first counted row of a code claims a free entry with a compare-and-swap (order does not matter, the host sorts).
+#include "mkp_dev_common.hpp"
+
+namespace {
+
+constexpr uint32_t kChunk = MKP_STATS_CHUNK;
+constexpr int kSlots = MKP_STATS_MAX_CODES;
+
+__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* __restrict__ a, uint32_t n, uint32_t key) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a[mid] < key) lo = mid + 1; else hi = mid; }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void mkp_stats_bounds(const uint32_t* __restrict__ pos, uint32_t n_rows, const MkpStatsRegion* __restrict__ regions,
+    uint32_t n_regions, uint32_t* __restrict__ row_lo, uint32_t* __restrict__ row_hi, uint32_t* __restrict__ n_chunks) {
+  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_regions) return;
+  const MkpStatsRegion g = regions[r];
+  uint32_t lo = 0, hi = 0;
+  if (g.end > g.start) { lo = lower_bound_u32(pos, n_rows, g.start); hi = lower_bound_u32(pos, n_rows, g.end); }
+  row_lo[r] = lo; row_hi[r] = hi; n_chunks[r] = (hi - lo + kChunk - 1) / kChunk;
+}
+
+// off[r] = chunks of the regions before r, off[n_regions] = *total = all of them (64-bit: a million regions of a whole chromosome each)
+__global__ __launch_bounds__(1024) void mkp_stats_scan(const uint32_t* __restrict__ n_chunks, uint32_t n_regions, unsigned long long* __restrict__ off,
+    unsigned long long* __restrict__ total) {
+  __shared__ unsigned long long part[1024];
+  const uint32_t t = threadIdx.x, per = (n_regions + 1023u) / 1024u;
+  const uint32_t r0 = min(t * per, n_regions), r1 = min(r0 + per, n_regions);
+  unsigned long long mine = 0;
+  for (uint32_t r = r0; r < r1; r++) mine += n_chunks[r];
+  part[t] = mine;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024u; d <<= 1) {
+    const unsigned long long add = t >= d ? part[t - d] : 0ull;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  unsigned long long run = part[t] - mine;
+  for (uint32_t r = r0; r < r1; r++) { off[r] = run; run += n_chunks[r]; }
+  if (t == 1023u) { off[n_regions] = part[t]; *total = part[t]; }
+}
+
+// the slot whose code is c in the wave's copy of the table (entry s in lane s), or -1
+__device__ __forceinline__ int find_slot(uint32_t tab, uint32_t c) {
+  int slot = -1;
+#pragma unroll
+  for (int s = 0; s < kSlots; s++) { const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)tab, s); if (e == c) slot = s; }
+  return slot;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) {
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
+    v += ((unsigned long long)hi << 32) | lo;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(256) void mkp_stats_reduce(const uint32_t* __restrict__ info, const uint32_t* __restrict__ code,
+    const uint32_t* __restrict__ n_valid, const uint32_t* __restrict__ n_mod, const MkpStatsRegion* __restrict__ regions, uint32_t n_regions,
+    const uint32_t* __restrict__ row_lo, const uint32_t* __restrict__ row_hi, const unsigned long long* __restrict__ off,
+    const unsigned long long* __restrict__ total_p, unsigned long long* __restrict__ out, uint32_t* __restrict__ seen, uint32_t* codes,
+    uint32_t* err, unsigned long long min_cov, uint32_t fixed_codes) {
+  const int lane = lane_id();
+  const unsigned long long n_waves = (unsigned long long)gridDim.x * (blockDim.x >> 6), total = *total_p;
+  // the code table as this wave last saw it: entry s in lane s
+  uint32_t tab = lane < kSlots ? __hip_atomic_load(&codes[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  for (unsigned long long w = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < total; w += n_waves) {
+    // the region of item w: the last one whose offset is <= w (regions without rows share their successor's offset and are never found)
+    uint32_t a = 0, b = n_regions;   // off[a] <= w < off[b]
+    while (b - a > 1) { const uint32_t mid = a + ((b - a) >> 1); if (off[mid] <= w) a = mid; else b = mid; }
+    const MkpStatsRegion g = regions[a];
+    const uint32_t first = row_lo[a] + (uint32_t)(w - off[a]) * kChunk, last = min(first + kChunk, row_hi[a]);
+    unsigned long long am[kSlots], av[kSlots];
+#pragma unroll
+    for (int s = 0; s < kSlots; s++) { am[s] = 0; av[s] = 0; }
+    uint32_t touched = 0;
+    for (uint32_t base = first; base < last; base += 64u) {
+      const uint32_t i = base + (uint32_t)lane;
+      bool pass = false; uint32_t c = 0, nv = 0, nm = 0;
+      if (i < last) {
+        const uint32_t sidx = info[i] & 3u;   // 0 '+', 1 '-', 2 '.'
+        c = code[i]; nv = n_valid[i]; nm = n_mod[i];
+        pass = (g.rule == 3u || sidx == 2u || sidx + 1u == g.rule) && (unsigned long long)nv >= min_cov;
+      }
+      int slot = find_slot(tab, c);
+      if (!pass) slot = -1;   // (c == 0 of an idle lane matches the free entries)
+      if (!fixed_codes && __ballot(pass && slot < 0)) {
+        // a code this wave has not met: look again (another wave has usually claimed it by now), then ONE lane per distinct code claims —
+        // every lane of every wave of a fresh launch meets an empty table, and their compare-and-swaps would all queue on one cache line
+        tab = lane < kSlots ? __hip_atomic_load(&codes[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        slot = find_slot(tab, c);
+        if (!pass) slot = -1;
+        bool missing = pass && slot < 0;
+        unsigned long long miss = __ballot(missing);
+        while (miss) {
+          const int leader = __ffsll((long long)miss) - 1;
+          const uint32_t c0 = (uint32_t)__shfl((int)c, leader, 64);
+          int s0 = -1;
+          if (lane == leader) {
+            for (int s = 0; s < kSlots && s0 < 0; s++) { const uint32_t old = atomicCAS(&codes[s], 0u, c0); if (old == 0u || old == c0) s0 = s; }
+            if (s0 < 0) atomicOr(err, MKP_STATS_ERR_CODES);
+          }
+          s0 = __shfl(s0, leader, 64);
+          if (missing && c == c0) { slot = s0; missing = false; }
+          miss = __ballot(missing);
+        }
+        tab = lane < kSlots ? __hip_atomic_load(&codes[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+      }
+      if (slot >= 0) touched |= 1u << slot;
+#pragma unroll
+      for (int s = 0; s < kSlots; s++) { const bool m = slot == s; am[s] += m ? nm : 0u; av[s] += m ? nv : 0u; }
+    }
+    touched = wave_or(touched);
+    if (!touched) continue;
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int s = 0; s < kSlots; s++) if ((touched >> s) & 1u) {   // (wave-uniform)
+      const unsigned long long sm = wave_sum_u64(am[s]), sv = wave_sum_u64(av[s]);
+      if (lane == 2 * s) mine = sm;
+      if (lane == 2 * s + 1) mine = sv;
+    }
+    if (lane < 2 * kSlots && ((touched >> (lane >> 1)) & 1u)) atomicAdd(&out[(size_t)g.out * (2 * kSlots) + (uint32_t)lane], mine);
+    if (lane == 0) atomicOr(&seen[g.out], touched);
+  }
+}
+
+}  // namespace
+
+// ev (may be NULL): three events recorded in front of the bounds kernel, in front of the reduce kernel and behind it
+extern "C" hipError_t mkp_launch_region_stats(hipStream_t st, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
+    const uint32_t* n_mod, uint32_t n_rows, const MkpStatsRegion* regions, uint32_t n_regions, uint32_t* row_lo, uint32_t* row_hi, uint32_t* n_chunks,
+    unsigned long long* off, unsigned long long* total, unsigned long long* out, uint32_t* seen, uint32_t* codes, uint32_t* err,
+    unsigned long long min_cov, uint32_t fixed_codes, hipEvent_t* ev) {
+  if (!n_rows || !n_regions) return hipSuccess;
+  hipError_t e;
+  if (ev && (e = hipEventRecord(ev[0], st)) != hipSuccess) return e;
+  mkp_stats_bounds<<<(n_regions + 255u) / 256u, 256, 0, st>>>(pos, n_rows, regions, n_regions, row_lo, row_hi, n_chunks);
+  mkp_stats_scan<<<1, 1024, 0, st>>>(n_chunks, n_regions, off, total);
+  if (ev && (e = hipEventRecord(ev[1], st)) != hipSuccess) return e;
+  // as many waves as there can be items, up to a grid that fills the chip a few times over
+  const unsigned long long most = (unsigned long long)n_regions * ((n_rows + MKP_STATS_CHUNK - 1u) / MKP_STATS_CHUNK);
+  const uint32_t blocks = (uint32_t)std::min<unsigned long long>((most + 3ull) / 4ull, 4096ull);
+  mkp_stats_reduce<<<blocks, 256, 0, st>>>(info, code, n_valid, n_mod, regions, n_regions, row_lo, row_hi, off, total, out, seen, codes, err, min_cov,
+      fixed_codes);
+  if (ev && (e = hipEventRecord(ev[2], st)) != hipSuccess) return e;
+  return hipGetLastError();
+}
