@@ -227,7 +227,9 @@ int mkp_process_region(mkp_ctx* ctx, const char* bam_path, const mkp_shard* shar
  * covered set; plus --device N, --gpus-rank R --gpus-world W for interval sharding; plus --region-stats <regions.bed> --region-stats-out
  * <table.tsv> [--region-stats-codes m,h] [--region-stats-min-coverage N] [--region-stats-no-header] [--region-stats-only]: `modkit stats`
  * over the run's rows while they are in HBM (mkp_stats_* below); with --region-stats-only the rows are neither read back nor written
- * (the out.bed positional is still required, the file is not created). */
+ * (the out.bed positional is still required, the file is not created); plus --localize <regions.bed> --localize-out <table.tsv>
+ * [--localize-window N (2000)] [--localize-stranded same|opposite] [--localize-stranded-features +|-|.] [--localize-only]: `modkit localize`
+ * over the run's rows (mkp_localize_* below; contig lengths from the BAM header), combinable with --region-stats. */
 int mkp_pileup_main(int argc, const char* const* argv, char* errbuf, size_t errbuf_len);
 
 /* The same subcommand on a context the caller owns (so the device named by the ctx is used and --device is ignored):
@@ -442,6 +444,64 @@ const char* mkp_region_set_chrom(const mkp_region_set* set, uint32_t i);
 const char* mkp_region_set_name(const mkp_region_set* set, uint32_t i);   /* "." when the line has none */
 void mkp_region_set_free(mkp_region_set* set);
 int mkp_host_stats_table(const mkp_region_set* set, const mkp_stats_out* counts, int with_header, const char* out_path);
+
+/* ---- `modkit localize <in.bed.gz> --regions <bed> --genome-sizes <tsv>` (EntryLocalize::run, src/localise/subcommand.rs:211-305;
+ * GenomeRegion::into_localized_mod_counts and LocalizedModCounts, src/localise/util.rs:25-82, 189-227): per mod code and offset from a
+ * feature's anchor the sums of N_mod and N_valid_cov over all features — an LDS-privatised histogram over row columns that are in HBM
+ * (mkp_localize.hip).  The table lives in HBM from mkp_localize_begin to mkp_localize_get and every add call adds into it: a window
+ * that straddles shard seams gets each row once.  A stats run and a localize run may be open on one ctx at the same time.
+ *   mkp_localize_begin         regions as parsed (start > end is allowed, as in the reference); contig_len_by_tid = the genome-sizes table
+ *                              (a region with tid < 0 or >= n_contigs is dropped: load_focus_regions, subcommand.rs:163-187).  The window
+ *                              arithmetic is done here, in 64 bits: mp = (start + end) / 2, ws = mp - (window + 1) or 0 when that
+ *                              underflows, we = min(mp + window, contig length), anchor = (ws + we) / 2 (GenomeRegion::midpoint of the
+ *                              EXPANDED region, src/util.rs:860-862: mp - 1 for an unclipped window); we <= ws is an empty window.  Every
+ *                              offset of a non-empty window lies in [-window, window] (checked per region).  stranded = `--stranded`
+ *                              (0 none, 1 same, 2 opposite), stranded_features = `--stranded-features` (0 = each region's own strand,
+ *                              1 '+', 2 '-', 3 '.').  window > 100 000 and a contig longer than 2^32 - 1 are MKP_E_UNSUPPORTED; no
+ *                              region on a listed contig is MKP_E_INVALID ("failed to find any valid regions").  `--min-coverage` is
+ *                              not offered: the reference parses and logs it and filters nothing by it (subcommand.rs:215-216).
+ *   mkp_localize_add_resident  the rows the last mkp_shard_run / mkp_shard_rerun on this ctx left in HBM; refusals as mkp_stats_add_resident.
+ *   mkp_localize_add_rows      rows the caller holds, one contig per call, ascending pos; as mkp_stats_add_rows (fetch_region,
+ *                              src/tabix.rs:141-154).
+ *   mkp_localize_get           waits for the device and returns the table.  A row is counted when pos is in [ws, we), its strand
+ *                              overlaps the fetch rule (stranded_features, else the region's strand: BedMethylLine::overlaps,
+ *                              src/tabix.rs:24-31, StrandRule::overlaps, src/util.rs:310-318) and, under `same`,
+ *                              region.strand.overlaps(row.strand) holds — under `opposite`, does not hold (a '.' region keeps nothing,
+ *                              a '.' row is always dropped).  offset = anchor - pos: upstream on the reference is positive, whatever
+ *                              the strand.  Codes = those with a counted row, in ModCodeRepr order; arrays [code * (2 window + 1) +
+ *                              offset + window]; n_rows = counted rows of the cell (the reference writes a line for every cell that
+ *                              had one, also with N_valid_cov 0).  A region whose contig no add call brought a row on is dropped; when
+ *                              none is left, MKP_E_INVALID, as the reference fails.  A seventeenth code inside a window is
+ *                              MKP_E_UNSUPPORTED.  Arrays owned by the ctx until its next mkp_localize_begin.
+ *   mkp_localize_tile_offsets  the offsets a workgroup of the reduce kernel owns (for tests that put a tile edge inside a table). */
+typedef struct { uint32_t n_codes, window; const uint32_t* code_repr;                      /* sorted */
+                 const uint64_t* n_mod; const uint64_t* n_valid; const uint64_t* n_rows;   /* [code * (2 window + 1) + offset + window] */
+               } mkp_localize_out;
+int mkp_localize_begin(mkp_ctx* ctx, const mkp_region* regions, uint32_t n, const uint64_t* contig_len_by_tid, uint32_t n_contigs, uint32_t window,
+    int stranded /*0 none, 1 same, 2 opposite*/, int stranded_features /*0 the region's own, 1 '+', 2 '-', 3 '.'*/);
+int mkp_localize_add_resident(mkp_ctx* ctx);
+int mkp_localize_add_rows(mkp_ctx* ctx, int32_t tid, const mkp_rows* rows);
+int mkp_localize_get(mkp_ctx* ctx, mkp_localize_out* out);
+uint32_t mkp_localize_tile_offsets(void);
+/* Host-only halves (no device needed).
+ * mkp_host_parse_localize_regions: the regions BED as load_focus_regions reads it (subcommand.rs:105-162): the first line that does not
+ *   start with '#' picks the parser by its number of WHITESPACE-separated fields (<= 4: bed3/4, both strands; otherwise chrom start end name
+ *   score strand), then every line goes through it; a line that fails is skipped and counted in *n_skipped, the load fails (MKP_E_INVALID)
+ *   only when no line parsed.  No start <= end check.  A coordinate beyond 2^32 - 1 is MKP_E_UNSUPPORTED.
+ * mkp_host_parse_genome_sizes: `chrom<whitespace>length` per line (read_sequence_lengths_file, src/util.rs:969-990); any line that does
+ *   not parse fails (MKP_E_INVALID); of two lines for one contig the later length holds, at the earlier one's place.
+ * mkp_host_localize_table: the table LocalizedModCounts::get_table gives (util.rs:48-82) through the tab-delimited csv writer:
+ *   `mod_code offset n_valid n_mod percent_modified`, a line per (code, offset) with n_rows > 0, codes in ModCodeRepr order, offsets
+ *   ascending, percent_modified = (n_mod as f32 / n_valid as f32) * 100 or 0 (ModPositionInfo, src/util.rs:920-936) through f32 Display. */
+int mkp_host_parse_localize_regions(const char* bed_path, const char* const* contig_names, uint32_t n_contigs, mkp_region_set** out,
+    uint32_t* n_skipped, char* errbuf, size_t errbuf_len);
+typedef struct mkp_genome_sizes mkp_genome_sizes;
+int mkp_host_parse_genome_sizes(const char* path, mkp_genome_sizes** out, char* errbuf, size_t errbuf_len);
+uint32_t mkp_genome_sizes_size(const mkp_genome_sizes* sizes);
+const char* mkp_genome_sizes_name(const mkp_genome_sizes* sizes, uint32_t i);
+uint64_t mkp_genome_sizes_length(const mkp_genome_sizes* sizes, uint32_t i);
+void mkp_genome_sizes_free(mkp_genome_sizes* sizes);
+int mkp_host_localize_table(const mkp_localize_out* counts, const char* out_path);
 
 /* ---- BGZF inflate on the device as a call of its own.  On the pileup path the same kernels run inside the device ingest
  * (`mkp_pileup_main` on an indexed BAM: compressed blocks up, inflate + CRC-32 + record cut + MM/ML tokeniser + packing in HBM, a digest

@@ -93,6 +93,25 @@ def lib():
             L.mkp_region_set_free.argtypes = [ctypes.c_void_p]
             L.mkp_region_set_free.restype = None
             L.mkp_host_stats_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p]
+        if hasattr(L, "mkp_localize_begin"):
+            L.mkp_localize_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, u64p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_int]
+            L.mkp_localize_add_resident.argtypes = [ctypes.c_void_p]
+            L.mkp_localize_add_rows.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+            L.mkp_localize_get.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            L.mkp_localize_tile_offsets.argtypes = []
+            L.mkp_localize_tile_offsets.restype = ctypes.c_uint32
+            L.mkp_host_parse_localize_regions.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p),
+                                                          ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_size_t]
+            L.mkp_host_parse_genome_sizes.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.c_size_t]
+            L.mkp_genome_sizes_size.argtypes = [ctypes.c_void_p]
+            L.mkp_genome_sizes_size.restype = ctypes.c_uint32
+            L.mkp_genome_sizes_name.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+            L.mkp_genome_sizes_name.restype = ctypes.c_char_p
+            L.mkp_genome_sizes_length.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+            L.mkp_genome_sizes_length.restype = ctypes.c_uint64
+            L.mkp_genome_sizes_free.argtypes = [ctypes.c_void_p]
+            L.mkp_genome_sizes_free.restype = None
+            L.mkp_host_localize_table.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
         # the structs this binding allocates mirror ONE revision of include/mkpileup.h: a library of another revision would write past them
         if os.environ.get("MKP_LIB_PATH") and not hasattr(L, "mkp_abi_version"):
             _lib = L   # (A/B runs against a build from before the query existed, tools/dbg/ab.sh)
@@ -119,7 +138,10 @@ EXPORTS = ["mkp_ctx_create", "mkp_ctx_destroy", "mkp_last_error", "mkp_version",
            "mkp_set_partition_tags", "mkp_histogram_begin", "mkp_histogram_add_bam", "mkp_histogram_get", "mkp_histogram_allreduce", "mkp_histogram_from_values", "mkp_histogram_locate",
            "mkp_histogram_resolve", "mkp_percentile_from_histogram", "mkp_hemi_shard_run", "mkp_pileup_hemi_main", "mkp_pileup_hemi_run", "mkp_bgzf_inflate", "mkp_sample_probs", "mkp_summary", "mkp_extract_calls_main",
            "mkp_stats_begin", "mkp_stats_add_resident", "mkp_stats_add_rows", "mkp_stats_get", "mkp_host_parse_regions", "mkp_region_set_size",
-           "mkp_region_set_chrom", "mkp_region_set_name", "mkp_region_set_free", "mkp_host_stats_table"]
+           "mkp_region_set_chrom", "mkp_region_set_name", "mkp_region_set_free", "mkp_host_stats_table",
+           "mkp_localize_begin", "mkp_localize_add_resident", "mkp_localize_add_rows", "mkp_localize_get", "mkp_localize_tile_offsets",
+           "mkp_host_parse_localize_regions", "mkp_host_parse_genome_sizes", "mkp_genome_sizes_size", "mkp_genome_sizes_name",
+           "mkp_genome_sizes_free", "mkp_host_localize_table"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
 
 
 def pileup(argv):
@@ -217,13 +239,20 @@ def code_repr(code):
 class RegionSet:
     """A parsed regions BED (mkp_host_parse_regions): `regions` = [(chrom, start, end, name or ".", strand "+-."), ...], tids by `contig_names`."""
 
-    def __init__(self, bed_path, contig_names):
+    def __init__(self, bed_path, contig_names, localize=False):
+        """localize=True: the tolerant loader of `modkit localize` (mkp_host_parse_localize_regions); `skipped` = the lines that failed to parse."""
         self.L = lib()
         names = [str(n).encode() for n in contig_names]
         arr = (ctypes.c_char_p * max(1, len(names)))(*names)
         self.h = ctypes.c_void_p()
+        self.skipped = 0
         err = ctypes.create_string_buffer(2048)
-        rc = self.L.mkp_host_parse_regions(str(bed_path).encode(), arr, len(names), ctypes.byref(self.h), err, len(err))
+        if localize:
+            skipped = ctypes.c_uint32(0)
+            rc = self.L.mkp_host_parse_localize_regions(str(bed_path).encode(), arr, len(names), ctypes.byref(self.h), ctypes.byref(skipped), err, len(err))
+            self.skipped = int(skipped.value)
+        else:
+            rc = self.L.mkp_host_parse_regions(str(bed_path).encode(), arr, len(names), ctypes.byref(self.h), err, len(err))
         if rc != MKP_OK:
             raise MkpError(rc, err.value.decode(errors="replace"))
         self.n = self.L.mkp_region_set_size(self.h)
@@ -271,6 +300,48 @@ def stats_out_from(d):
                  n_mod=n_mod.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n_valid=n_valid.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
                  contig_has_rows=has.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
     return o, (codes, n_mod, n_valid, has)
+
+
+class LocalizeOut(ctypes.Structure):
+    """mkp_localize_out: the per-code, per-offset totals of `modkit localize`; arrays [code * (2 window + 1) + offset + window]."""
+    _fields_ = [("n_codes", ctypes.c_uint32), ("window", ctypes.c_uint32), ("code_repr", ctypes.POINTER(ctypes.c_uint32)),
+                ("n_mod", ctypes.POINTER(ctypes.c_uint64)), ("n_valid", ctypes.POINTER(ctypes.c_uint64)), ("n_rows", ctypes.POINTER(ctypes.c_uint64))]
+
+
+STRANDED = {None: 0, "same": 1, "opposite": 2}
+STRANDED_FEATURES = {None: 0, "+": 1, "-": 2, ".": 3}
+
+
+def localize_tile_offsets():
+    """mkp_localize_tile_offsets: the offsets one workgroup of the localize kernel owns."""
+    return int(lib().mkp_localize_tile_offsets())
+
+
+def genome_sizes(path):
+    """mkp_host_parse_genome_sizes: [(contig, length), ...] of a `chrom<whitespace>length` file; a later line for a contig replaces its length."""
+    L = lib()
+    h = ctypes.c_void_p()
+    err = ctypes.create_string_buffer(2048)
+    rc = L.mkp_host_parse_genome_sizes(str(path).encode(), ctypes.byref(h), err, len(err))
+    if rc != MKP_OK:
+        raise MkpError(rc, err.value.decode(errors="replace"))
+    try:
+        return [(L.mkp_genome_sizes_name(h, i).decode(), int(L.mkp_genome_sizes_length(h, i))) for i in range(L.mkp_genome_sizes_size(h))]
+    finally:
+        L.mkp_genome_sizes_free(h)
+
+
+def write_localize_table(counts, out_path):
+    """mkp_host_localize_table: the `modkit localize` table of the dict Context.localize_get returns."""
+    import numpy as np
+    codes = np.ascontiguousarray(np.asarray(counts["codes"], dtype=np.uint32))
+    cols = [np.ascontiguousarray(np.asarray(counts[f], dtype=np.uint64)) for f in ("n_mod", "n_valid", "n_rows")]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    o = LocalizeOut(n_codes=len(codes), window=int(counts["window"]), code_repr=codes.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                    n_mod=cols[0].ctypes.data_as(u64p), n_valid=cols[1].ctypes.data_as(u64p), n_rows=cols[2].ctypes.data_as(u64p))
+    rc = lib().mkp_host_localize_table(ctypes.byref(o), str(out_path).encode())
+    if rc != MKP_OK:
+        raise MkpError(rc, "mkp_host_localize_table failed")
 
 
 class HemiRows(ctypes.Structure):
@@ -534,6 +605,47 @@ class Context:
         return {"codes": arr(o.code_repr, (k,), np.uint32), "n_mod": arr(o.n_mod, (n, k), np.uint64), "n_valid": arr(o.n_valid, (n, k), np.uint64),
                 "contig_has_rows": arr(o.contig_has_rows, (n,), np.uint8)}
 
+    def localize_begin(self, regions, contig_lengths, window=2000, stranded=None, stranded_features=None):
+        """mkp_localize_begin: regions = a RegionSet, or [(tid, start, end, strand "+-." or rule 1..3), ...] (start > end allowed);
+        contig_lengths[tid] = the genome-sizes table; stranded = None / "same" / "opposite"; stranded_features = None / "+" / "-" / "."."""
+        if isinstance(regions, RegionSet):
+            arr, n = regions.array, regions.n
+        else:
+            n = len(regions)
+            arr = (Region * max(1, n))()
+            for i, (tid, start, end, rule) in enumerate(regions):
+                arr[i].tid, arr[i].start, arr[i].end = int(tid), int(start), int(end)
+                arr[i].strand_rule = STRAND_RULES[rule] if isinstance(rule, str) else int(rule)
+        lens = (ctypes.c_uint64 * max(1, len(contig_lengths)))(*[int(x) for x in contig_lengths])
+        self._check(self.L.mkp_localize_begin(self.h, arr, n, lens, len(contig_lengths), int(window), STRANDED[stranded], STRANDED_FEATURES[stranded_features]))
+
+    def localize_add_resident(self):
+        """mkp_localize_add_resident: add the rows the last shard run left in HBM to the offset table."""
+        self._check(self.L.mkp_localize_add_resident(self.h))
+
+    def localize_add_rows(self, tid, rows):
+        """mkp_localize_add_rows: rows of ONE contig, ascending pos, as stats_add_rows takes them."""
+        import numpy as np
+        cols = {f: np.ascontiguousarray(np.asarray(rows[f], dtype=np.uint8 if f == "strand" else np.uint32))
+                for f in ("pos", "strand", "code_repr", "n_valid", "n_mod")}
+        r = Rows()
+        r.n_rows = len(cols["pos"])
+        for f, a in cols.items():
+            setattr(r, f, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8 if f == "strand" else ctypes.c_uint32)))
+        self._check(self.L.mkp_localize_add_rows(self.h, int(tid), ctypes.byref(r)))
+
+    def localize_get(self):
+        """mkp_localize_get: {"codes": u32[n_codes] sorted, "window": w, "n_mod" / "n_valid" / "n_rows": u64[n_codes, 2 w + 1]}, column
+        offset + w; a (code, offset) cell is a table line when its n_rows is not 0."""
+        import numpy as np
+        o = LocalizeOut()
+        self._check(self.L.mkp_localize_get(self.h, ctypes.byref(o)))
+        k, n = int(o.n_codes), 2 * int(o.window) + 1
+        def arr(p, shape, dt):
+            return np.ctypeslib.as_array(p, shape=shape).copy() if all(shape) else np.zeros(shape, dtype=dt)
+        return {"codes": arr(o.code_repr, (k,), np.uint32), "window": int(o.window), "n_mod": arr(o.n_mod, (k, n), np.uint64),
+                "n_valid": arr(o.n_valid, (k, n), np.uint64), "n_rows": arr(o.n_rows, (k, n), np.uint64)}
+
     def rerun(self, iters, fetch=False):
         rows = Rows()
         self._check(self.L.mkp_shard_rerun(self.h, int(iters), ctypes.byref(rows) if fetch else None))
@@ -631,6 +743,31 @@ def stats(bedmethyl_path, regions_bed, out_table, codes=None, min_coverage=1, he
         for chrom, rows in pieces:
             ctx.stats_add_rows(names.index(chrom), rows)
         rs.write_table(ctx.stats_get(), out_table, header=header)
+    finally:
+        ctx.close()
+        rs.close()
+
+
+def localize(bedmethyl_path, regions_bed, genome_sizes_path, out_table, window=2000, stranded=None, stranded_features=None, device=0):
+    """`modkit localize <bedmethyl> --regions <bed> --genome-sizes <tsv> -o <table>` (EntryLocalize::run, src/localise/subcommand.rs:211-305) on
+    the device: the file's rows are uploaded contig by contig and go through the kernels a fused `pileup --localize` run uses
+    (Context.localize_add_rows).  Reads what read_bedmethyl_for_stats reads: a PLAIN-TEXT bedMethyl without header; a region whose contig is
+    not in the sizes file or has no line in the bedMethyl is dropped.  window = `--window`, stranded = `--stranded` ("same" / "opposite"),
+    stranded_features = `--stranded-features` ("+", "-", ".").  There is no min_coverage: the reference only logs it."""
+    pieces = read_bedmethyl_for_stats(bedmethyl_path)
+    sizes = genome_sizes(genome_sizes_path)
+    names = [n for n, _ in sizes]
+    n_sized = len(names)
+    for chrom, _ in pieces:          # (contigs of the file that the sizes do not list: their rows bring nothing, no region can be on them)
+        if chrom not in names:
+            names.append(chrom)
+    rs = RegionSet(regions_bed, names[:n_sized], localize=True)
+    ctx = Context(device=device)
+    try:
+        ctx.localize_begin(rs, [l for _, l in sizes], window=window, stranded=stranded, stranded_features=stranded_features)
+        for chrom, rows in pieces:
+            ctx.localize_add_rows(names.index(chrom), rows)
+        write_localize_table(ctx.localize_get(), out_table)
     finally:
         ctx.close()
         rs.close()

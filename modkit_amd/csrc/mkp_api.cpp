@@ -1085,8 +1085,10 @@ void mkp_ctx_destroy(mkp_ctx* c) {
                         &c->d_tile_row_off, &c->d_tile_row_cnt, &c->d_tile_dst, &c->d_misc, &c->d_rows_src, &c->d_rows_dst, &c->d_hemi_iv,
                         &c->d_slot_pos, &c->d_cov, &c->d_visits, &c->d_stiles, &c->d_slot_ids, &c->d_fdesc, &c->d_work, &c->d_plane, &c->d_zin, &c->d_zout,
                         &c->d_zblk, &c->d_zstat, &c->d_summary, &c->d_bedmask, &c->d_hist64, &c->rstats.d_regions, &c->rstats.d_out, &c->rstats.d_seen,
-                        &c->rstats.d_misc, &c->rstats.d_lo, &c->rstats.d_hi, &c->rstats.d_cnt, &c->rstats.d_off, &c->rstats.d_rows}) b->release();
+                        &c->rstats.d_misc, &c->rstats.d_lo, &c->rstats.d_hi, &c->rstats.d_cnt, &c->rstats.d_off, &c->rstats.d_rows,
+                        &c->loc.d_regions, &c->loc.d_tab, &c->loc.d_misc, &c->loc.d_lo, &c->loc.d_hi, &c->loc.d_rows}) b->release();
   for (auto& e : c->rstats.ev) if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->loc.ev) if (e) (void)hipEventDestroy(e);
   mkp_internal_ingest_destroy(c->ingest); c->ingest = nullptr;
   c->h_rows.release();
   for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
@@ -2047,6 +2049,181 @@ int mkp_stats_get(mkp_ctx* c, mkp_stats_out* out) {
     }
     out->n_regions = n; out->n_codes = (uint32_t)nc; out->code_repr = R.h_codes.data(); out->n_mod = R.h_mod.data();
     out->n_valid = R.h_valid.data(); out->contig_has_rows = R.h_has.data();
+  });
+}
+
+}  // extern "C"
+
+// ---- localize (`modkit localize`, include/mkpileup.h): the offset table stays in HBM between mkp_localize_begin and mkp_localize_get
+extern "C" hipError_t mkp_launch_localize(hipStream_t, const uint32_t* /*pos*/, const uint32_t* /*info*/, const uint32_t* /*code*/,
+    const uint32_t* /*n_valid*/, const uint32_t* /*n_mod*/, uint32_t /*rows*/, const MkpLocRegion*, uint32_t, uint32_t* /*first row*/,
+    uint32_t* /*row behind the last*/, uint32_t /*window*/, uint32_t /*stranded*/, unsigned long long* /*table*/, uint32_t* /*slot codes*/,
+    uint32_t* /*error bits*/, hipEvent_t* /*3 timing events or NULL*/);
+
+namespace {
+// d_misc: 16 slot codes, the error word, a pad word
+constexpr size_t kLocMiscBytes = 4 * MKP_STATS_MAX_CODES + 8;
+size_t loc_table_cells(uint32_t window) { return (size_t)MKP_STATS_MAX_CODES * (2 * (size_t)window + 1) * 3; }
+void localize_launch(mkp_ctx* c, int32_t tid, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
+    const uint32_t* n_mod, uint64_t n_rows) {
+  mkp_ctx::Localize& L = c->loc;
+  if (n_rows > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one piece");
+  if (n_rows) L.tids_with_rows.insert(tid);
+  auto it = L.tid_range.find(tid);
+  if (!n_rows || it == L.tid_range.end()) return;
+  const uint32_t first = it->second.first, n = it->second.second - first;
+  uint32_t* misc = L.d_misc.as<uint32_t>();
+  hip_check(mkp_launch_localize(c->stream, pos, info, code, n_valid, n_mod, (uint32_t)n_rows, L.d_regions.as<MkpLocRegion>() + first, n,
+      L.d_lo.as<uint32_t>(), L.d_hi.as<uint32_t>(), L.window, L.stranded, L.d_tab.as<unsigned long long>(), misc, misc + MKP_STATS_MAX_CODES,
+      L.timing ? L.ev : nullptr), "localize launch");
+  if (L.timing) {
+    hip_check(hipEventSynchronize(L.ev[2]), "localize sync");
+    float a = 0, b = 0; hip_check(hipEventElapsedTime(&a, L.ev[0], L.ev[1]), "event"); hip_check(hipEventElapsedTime(&b, L.ev[1], L.ev[2]), "event");
+    L.kernel_ms[0] += a; L.kernel_ms[1] += b;
+  }
+}
+}  // namespace
+
+extern "C" {
+
+int mkp_internal_localize_timing(mkp_ctx* c, int on, double ms_out[2]) {
+  if (!c) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Localize& L = c->loc;
+    if (ms_out) { ms_out[0] = L.kernel_ms[0]; ms_out[1] = L.kernel_ms[1]; }
+    if (on) for (auto& e : L.ev) if (!e) hip_check(hipEventCreate(&e), "hipEventCreate");
+    L.timing = on != 0; if (on) L.kernel_ms[0] = L.kernel_ms[1] = 0;
+  });
+}
+
+int mkp_localize_begin(mkp_ctx* c, const mkp_region* regions, uint32_t n, const uint64_t* contig_len_by_tid, uint32_t n_contigs, uint32_t window,
+    int stranded, int stranded_features) {
+  if (!c || (!regions && n) || (!contig_len_by_tid && n_contigs)) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Localize& L = c->loc;
+    L.open = false;
+    if (window > MKP_LOC_MAX_WINDOW) throw Error(MKP_E_UNSUPPORTED, "localize: a window of more than " + std::to_string(MKP_LOC_MAX_WINDOW)
+        + " offsets to either side is not supported");
+    if (stranded < 0 || stranded > 2) throw Error(MKP_E_INVALID, "stranded must be 0 (none), 1 (same) or 2 (opposite)");
+    if (stranded_features < 0 || stranded_features > 3) throw Error(MKP_E_INVALID,
+        "stranded_features must be 0 (the region's own strand), 1 ('+'), 2 ('-') or 3 ('.')");
+    for (uint32_t k = 0; k < n_contigs; k++) if (contig_len_by_tid[k] > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED,
+        "contig " + std::to_string(k) + " is longer than 2^32 - 1");
+    // load_focus_regions (subcommand.rs:163-187) on the regions whose contig is in the sizes table, then grouped by contig
+    std::vector<uint32_t> order;
+    for (uint32_t i = 0; i < n; i++) {
+      if (regions[i].strand_rule < 1 || regions[i].strand_rule > 3) throw Error(MKP_E_INVALID, "region " + std::to_string(i)
+          + ": strand_rule must be 1 ('+'), 2 ('-') or 3 (both)");
+      if (regions[i].tid >= 0 && (uint32_t)regions[i].tid < n_contigs) order.push_back(i);
+    }
+    if (order.empty()) throw Error(MKP_E_INVALID, "failed to find any valid regions: none lies on a contig of the sizes table");
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return regions[a].tid < regions[b].tid; });
+    const uint64_t w = window;
+    std::vector<MkpLocRegion> dev(order.size());
+    L.kept_tid.resize(order.size()); L.tid_range.clear(); L.tids_with_rows.clear(); L.most_per_tid = 0;
+    for (uint32_t k = 0; k < order.size(); k++) {
+      const mkp_region& g = regions[order[k]];
+      const uint64_t mp = ((uint64_t)g.start + (uint64_t)g.end) / 2;
+      const uint64_t ws = mp >= w + 1 ? mp - (w + 1) : 0, we = std::min(mp + w, contig_len_by_tid[g.tid]);
+      const uint64_t anchor = (ws + we) / 2;
+      // every row of a non-empty window has its offset anchor - pos in [-window, window]: the table's 2 window + 1 cells hold them all
+      if (we > ws && (anchor - ws > w || (we - 1) - std::min(anchor, we - 1) > w)) throw Error(MKP_E_INVALID, "region " + std::to_string(order[k])
+          + ": an offset beyond the window");
+      const uint32_t fetch = stranded_features ? (uint32_t)stranded_features : (uint32_t)g.strand_rule;
+      dev[k] = {(uint32_t)ws, (uint32_t)we, (uint32_t)anchor, fetch | ((uint32_t)g.strand_rule << 8)};
+      L.kept_tid[k] = g.tid;
+      auto it = L.tid_range.find(g.tid);
+      if (it == L.tid_range.end()) L.tid_range[g.tid] = {k, k + 1}; else it->second.second = k + 1;
+    }
+    for (auto& kv : L.tid_range) L.most_per_tid = std::max(L.most_per_tid, kv.second.second - kv.second.first);
+    L.window = window; L.stranded = (uint32_t)stranded;
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    hip_check(hipStreamSynchronize(c->stream), "sync");   // (a previous session's kernels)
+    const size_t m1 = std::max<size_t>(L.most_per_tid, 1);
+    L.d_regions.ensure(dev.size() * sizeof(MkpLocRegion)); L.d_tab.ensure(loc_table_cells(window) * 8); L.d_misc.ensure(kLocMiscBytes);
+    L.d_lo.ensure(m1 * 4); L.d_hi.ensure(m1 * 4);
+    h2d_copy(L.d_regions.p, dev.data(), dev.size() * sizeof(MkpLocRegion));
+    hip_check(hipMemsetAsync(L.d_misc.p, 0, kLocMiscBytes, c->stream), "memset");
+    hip_check(hipMemsetAsync(L.d_tab.p, 0, loc_table_cells(window) * 8, c->stream), "memset");
+    hip_check(hipStreamSynchronize(c->stream), "sync");
+    L.open = true;
+  });
+}
+
+int mkp_localize_add_resident(mkp_ctx* c) {
+  if (!c) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    if (!c->loc.open) throw Error(MKP_E_INVALID, "mkp_localize_begin first");
+    if (!c->partition_tags.empty()) throw Error(MKP_E_INVALID,
+        "localize needs the rows in genome order: with partition tags set they come grouped by key");
+    if (!c->resident || c->resident_hemi || c->hemi) throw Error(MKP_E_INVALID,
+        "no pileup rows are resident: call mkp_shard_run first (pileup-hemi rows are pattern counts, not bedMethyl rows)");
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    const MkpRowsDev& r = c->rows_dst;
+    localize_launch(c, c->shard.tid, r.pos, r.info, r.code, r.n_valid, r.n_mod, c->stats.n_rows);
+  });
+}
+
+int mkp_localize_add_rows(mkp_ctx* c, int32_t tid, const mkp_rows* rows) {
+  if (!c || !rows) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Localize& L = c->loc;
+    if (!L.open) throw Error(MKP_E_INVALID, "mkp_localize_begin first");
+    const uint64_t n = rows->n_rows;
+    if (n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
+    if (n && (!rows->pos || !rows->strand || !rows->code_repr || !rows->n_valid || !rows->n_mod)) throw Error(MKP_E_INVALID,
+        "pos, strand, code_repr, n_valid and n_mod are needed");
+    std::vector<uint32_t> info(n);
+    for (uint64_t i = 0; i < n; i++) {
+      if (i && rows->pos[i] < rows->pos[i - 1]) throw Error(MKP_E_INVALID, "rows must be ascending in pos (row " + std::to_string(i) + ")");
+      const uint8_t s = rows->strand[i];
+      if (s != '+' && s != '-' && s != '.') throw Error(MKP_E_INVALID, "strand must be '+', '-' or '.' (row " + std::to_string(i) + ")");
+      if (!rows->code_repr[i]) throw Error(MKP_E_INVALID, "0 is not a mod code (row " + std::to_string(i) + ")");
+      info[i] = s == '+' ? 0u : s == '-' ? 1u : 2u;
+    }
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    hip_check(hipStreamSynchronize(c->stream), "sync");   // the previous call's kernels read the upload buffer
+    const size_t col = ((size_t)n + 63) & ~(size_t)63;
+    L.d_rows.ensure(std::max<size_t>(col, 64) * 20);
+    uint32_t* d = L.d_rows.as<uint32_t>();
+    const uint32_t* src[5] = {rows->pos, info.data(), rows->code_repr, rows->n_valid, rows->n_mod};
+    for (int k = 0; k < 5; k++) h2d_copy(d + (size_t)k * col, src[k], (size_t)n * 4);
+    localize_launch(c, tid, d, d + col, d + 2 * col, d + 3 * col, d + 4 * col, n);
+  });
+}
+
+int mkp_localize_get(mkp_ctx* c, mkp_localize_out* out) {
+  if (!c || !out) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Localize& L = c->loc;
+    if (!L.open) throw Error(MKP_E_INVALID, "mkp_localize_begin first");
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    uint32_t misc[kLocMiscBytes / 4];
+    d2h_copy(misc, L.d_misc.p, sizeof(misc), c->stream);
+    if (misc[MKP_STATS_MAX_CODES] & MKP_STATS_ERR_CODES) throw Error(MKP_E_UNSUPPORTED, "the rows inside the windows carry more than "
+        + std::to_string(MKP_STATS_MAX_CODES) + " distinct mod codes: localize holds at most that many per run");
+    bool any_region = false;
+    for (int32_t tid : L.kept_tid) if (L.tids_with_rows.count(tid)) { any_region = true; break; }
+    if (!any_region) throw Error(MKP_E_INVALID, "failed to find any valid regions: no row was added on a contig that has one");
+    const size_t n_off = 2 * (size_t)L.window + 1;
+    std::vector<uint64_t> tab(loc_table_cells(L.window));
+    d2h_copy(tab.data(), L.d_tab.p, tab.size() * 8, c->stream);
+    // columns: the slots with a counted row in some cell, by code
+    std::vector<std::pair<uint32_t, uint32_t>> cols;   // code, slot
+    for (uint32_t s = 0; s < MKP_STATS_MAX_CODES; s++) {
+      if (!misc[s]) continue;
+      bool any = false; for (size_t o = 0; o < n_off && !any; o++) any = tab[((size_t)s * n_off + o) * 3 + 2] != 0;
+      if (any) cols.push_back({misc[s], s});
+    }
+    std::sort(cols.begin(), cols.end());
+    const size_t nc = cols.size();
+    L.h_codes.resize(nc); L.h_mod.resize(nc * n_off); L.h_valid.resize(nc * n_off); L.h_rows.resize(nc * n_off);
+    for (size_t k = 0; k < nc; k++) { L.h_codes[k] = cols[k].first;
+      for (size_t o = 0; o < n_off; o++) { const uint64_t* e = &tab[((size_t)cols[k].second * n_off + o) * 3];
+        // the table's index is anchor + window - pos = offset + window already
+        L.h_mod[k * n_off + o] = e[0]; L.h_valid[k * n_off + o] = e[1]; L.h_rows[k * n_off + o] = e[2]; } }
+    out->n_codes = (uint32_t)nc; out->window = L.window; out->code_repr = L.h_codes.data(); out->n_mod = L.h_mod.data();
+    out->n_valid = L.h_valid.data(); out->n_rows = L.h_rows.data();
   });
 }
 

@@ -197,6 +197,17 @@ struct mkp_ctx {
     std::vector<uint32_t> h_codes; std::vector<uint64_t> h_mod, h_valid; std::vector<uint8_t> h_has;   // mkp_stats_get
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; double kernel_ms[2] = {0, 0};   // timing: bounds + scan, reduce (summed over the calls)
   } rstats;
+  // localize (mkp_localize_begin .. mkp_localize_get, mkp_localize.hip): the run-long table tab[slot][2 window + 1]{n_mod, n_valid, n_rows}
+  // (u64) and the slots' codes stay in HBM between the calls; the windows are uploaded once, grouped by contig
+  struct Localize {
+    bool open = false, timing = false; uint32_t window = 0, stranded = 0, most_per_tid = 0;
+    std::vector<int32_t> kept_tid;                                      // the contigs of the regions that passed the sizes filter
+    std::map<int32_t, std::pair<uint32_t, uint32_t>> tid_range;         // contig -> [first, last) of d_regions
+    std::set<int32_t> tids_with_rows;
+    mkp::DevBuf d_regions, d_tab, d_misc /* codes[16], error word, pad */, d_lo, d_hi, d_rows;
+    std::vector<uint32_t> h_codes; std::vector<uint64_t> h_mod, h_valid, h_rows;   // mkp_localize_get
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; double kernel_ms[2] = {0, 0};   // timing: bounds, reduce (summed over the calls)
+  } loc;
   bool skip_row_fetch = false;   // `--region-stats-only`: mkp_shard_run leaves the rows in HBM (no column read-back, n_rows = 0 in its output)
   // device ingest of indexed BAMs (mkp_ingest_host.cpp): created on first use, lives with the context (staging + window buffers are reused)
   struct mkp_dev_ingest* ingest = nullptr;
@@ -235,3 +246,5 @@ bool mkp_internal_device_inflate(void* user, const mkp::InflateJob& job);
 // `--region-stats-only`: the runs that follow leave their rows in HBM
 extern "C" int mkp_internal_stats_timing(mkp_ctx* c, int on, double ms_out[2]);
 extern "C" int mkp_internal_skip_row_fetch(mkp_ctx* c, int on);
+// localize: the same for its two kernels [bounds, reduce]
+extern "C" int mkp_internal_localize_timing(mkp_ctx* c, int on, double ms_out[2]);

@@ -286,6 +286,14 @@ struct MkpRowsDev {  // SoA row buffers (44 B / row)
 #define MKP_STATS_MAX_CODES 16      // distinct mod codes per run (the pileup itself allows MKP_MAX_SLOTS (base, code) pairs)
 #define MKP_STATS_ERR_CODES 1u      // device error bit: a seventeenth code
 struct MkpStatsRegion { uint32_t start, end; uint32_t rule /* 1 '+', 2 '-', 3 both */; uint32_t out /* index into the run's table */; };
+// ---- localize (mkp_localize.hip): one expanded window [ws, we) of the contig whose rows are being added and the anchor its offsets are
+// taken from (offset = anchor - pos).  The run-long table holds MKP_STATS_MAX_CODES slots of 2 * window + 1 cells {n_mod, n_valid, n_rows}
+// (u64 each); the codes of the slots (0 = free) are a table of the run's own.
+#define MKP_LOC_TILE 512u           // offsets per tile: a workgroup of mkp_localize_reduce keeps [MKP_LOC_LOCAL][MKP_LOC_TILE] cells in LDS
+#define MKP_LOC_LOCAL 4             // code slots with cells in LDS; a row of a later slot adds to HBM directly
+#define MKP_LOC_BATCH 256u          // regions per batch = threads per workgroup
+#define MKP_LOC_MAX_WINDOW 100000u
+struct MkpLocRegion { uint32_t ws, we, anchor; uint32_t rules /* fetch rule | region rule << 8, each 1 '+', 2 '-', 3 both */; };
 #ifdef __cplusplus
 static_assert(sizeof(MkpWork) == 64, "work record is 16 dwords");
 static_assert(sizeof(MkpFusedDesc) == 64 && sizeof(MkpVisit) == 32 && sizeof(MkpPlaneEnt) == 16, "slot pipeline records");

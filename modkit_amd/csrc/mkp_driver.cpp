@@ -99,6 +99,12 @@ struct Args {
      --region-stats-only: the rows are neither read back nor written (the out.bed positional is not created) */
   std::string region_stats, region_stats_out; std::vector<uint32_t> region_stats_codes; uint64_t region_stats_min_cov = 1;
   bool region_stats_no_header = false, region_stats_only = false;
+  /* --localize <bed>: `modkit localize` over this run's rows, an offset histogram built on the device from the rows in HBM
+     (mkp_localize.hip), contig lengths from the BAM header; the table goes to --localize-out; --localize-window / -stranded /
+     -stranded-features = its --window / --stranded / --stranded-features; --localize-only: as --region-stats-only */
+  std::string localize, localize_out; uint32_t localize_window = 2000; bool have_localize_window = false;
+  int localize_stranded = 0, localize_stranded_features = 0; bool localize_only = false;
+  bool rows_stay() const { return region_stats_only || localize_only; }   // the rows are neither read back nor written
 };
 
 struct RegionSpec { std::string name; uint32_t start, end; };
@@ -1286,7 +1292,7 @@ class Outputs {
   // the checks throw in the order of the flags' resolution (subcommand.rs:328-363 for --bedgraph)
   Outputs(const Args& a, mkp_ctx* ctx, const std::vector<std::string>& labels) : a(a), partitioned(!a.partition_tags.empty()) {
     wr.mixed = a.mixed_delim; wr.labels = labels;
-    if (a.region_stats_only) return;   // no rows reach the host: nothing is opened (every shard hands write() zero rows)
+    if (a.rows_stay()) return;   // no rows reach the host: nothing is opened (every shard hands write() zero rows)
     if (a.bedgraph) {   // (no header, no mixed delimiters; the path is a directory)
       if (a.with_header || a.mixed_delim || a.bgzf || a.hemi || a.plan_only) throw Error(MKP_E_INVALID,
           "--bedgraph cannot be combined with --with-header, --mixed-delim, --bgzf or --plan-only");
@@ -1453,6 +1459,7 @@ void run_shards(const Args& a, Options& o, mkp_ctx* ctx, const ShardReader& read
       mark("  mkp_shard_run returned");
       if (a.rerun) must(ctx, mkp_shard_rerun(ctx, a.rerun, &rows));   // measurement aid: warm, averaged kernel times in --stats
       if (!a.region_stats.empty()) must(ctx, mkp_stats_add_resident(ctx));   // the rows are still in HBM: this shard's share of every region
+      if (!a.localize.empty()) must(ctx, mkp_localize_add_resident(ctx));     // ... and of every window
       auto t_w = std::chrono::steady_clock::now();
       out.write(rec.name, rows);
       c.write_ms += ms_since(t_w);
@@ -1531,15 +1538,29 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
   Outputs out(a, ctx, o.labels);
   // --region-stats: the regions (contigs by the BAM header's names) and the run-long table in HBM; --region-stats-only: no row read-back
   mkp_region_set rset;
-  struct RowFetchGuard { mkp_ctx* c; ~RowFetchGuard() { if (c) { mkp_internal_skip_row_fetch(c, 0); mkp_internal_stats_timing(c, 0, nullptr); } } } fetch_guard{nullptr};
+  struct RowFetchGuard { mkp_ctx* c; ~RowFetchGuard() { if (c) { mkp_internal_skip_row_fetch(c, 0); mkp_internal_stats_timing(c, 0, nullptr);
+      mkp_internal_localize_timing(c, 0, nullptr); } } } fetch_guard{nullptr};
   if (!a.region_stats.empty()) {
     rset = parse_regions_bed(a.region_stats, [&](const std::string& chrom) { return bam.tid_of(chrom); });
     must(ctx, mkp_stats_begin(ctx, rset.regions.data(), (uint32_t)rset.regions.size(), a.region_stats_codes.data(),
         (uint32_t)a.region_stats_codes.size(), a.region_stats_min_cov));
     fetch_guard.c = ctx;
     if (a.stats) must(ctx, mkp_internal_stats_timing(ctx, 1, nullptr));
-    if (a.region_stats_only) must(ctx, mkp_internal_skip_row_fetch(ctx, 1));
   }
+  // --localize: the same hooks, the windows around the regions' midpoints (contig lengths from the BAM header)
+  size_t n_localize_regions = 0;
+  if (!a.localize.empty()) {
+    uint32_t skipped = 0;
+    const mkp_region_set lset = parse_localize_regions_bed(a.localize, [&](const std::string& chrom) { return bam.tid_of(chrom); }, &skipped);
+    n_localize_regions = lset.regions.size();
+    std::vector<uint64_t> lens(bam.ref_lens.begin(), bam.ref_lens.end());
+    must(ctx, mkp_localize_begin(ctx, lset.regions.data(), (uint32_t)lset.regions.size(), lens.data(), (uint32_t)lens.size(), a.localize_window,
+        a.localize_stranded, a.localize_stranded_features));
+    fetch_guard.c = ctx;
+    if (a.stats) must(ctx, mkp_internal_localize_timing(ctx, 1, nullptr));
+    if (skipped) mark("  localize: regions BED lines skipped");
+  }
+  if (a.rows_stay()) must(ctx, mkp_internal_skip_row_fetch(ctx, 1));
   build_plan(plan, a, kn, bam, o, g, size, !ahead.empty(), mark);
   // (thresholds known before the plan: the shards go ahead of the loop from here)
   if (ahead.empty() && plan.shards.size() > 1 && !kn.no_ahead) ahead.from_plan(plan.shards, records, o.bf);
@@ -1558,7 +1579,17 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
           rset.regions.size(), table.n_codes, ms[0], ms[1]); }
     mark("region stats table written");
   }
-  const uint64_t n_rows_out = a.region_stats_only ? c.dev_rows : out.rows();
+  if (!a.localize.empty()) {
+    auto t_w = std::chrono::steady_clock::now();
+    mkp_localize_out table; must(ctx, mkp_localize_get(ctx, &table));
+    write_text_file(a.localize_out, localize_table_text(table, f32_display));
+    c.write_ms += ms_since(t_w);
+    if (a.stats) { double ms[2] = {0, 0}; mkp_internal_localize_timing(ctx, 0, ms);
+      fprintf(stderr, "[mkpileup] localize: %zu regions, window %u, %u codes; kernels bounds %.3f ms, reduce %.3f ms (summed over the shards)\n",
+          n_localize_regions, a.localize_window, table.n_codes, ms[0], ms[1]); }
+    mark("localize table written");
+  }
+  const uint64_t n_rows_out = a.rows_stay() ? c.dev_rows : out.rows();
   if (rep) c.report(rep, n_rows_out, g.focus_ms, o.kc);
   if (a.stats) c.print_stats(a, bam, n_rows_out, g.focus_ms, dev_ingest, ahead);
   return MKP_OK;
@@ -1571,7 +1602,7 @@ void parse_args(int argc, const char* const* argv, Args* out, bool need_position
     std::string s = argv[i];
     auto val = [&]() { if (i + 1 >= argc) throw Error(MKP_E_INVALID, "missing value for " + s); return std::string(argv[++i]); };
     if (hemi && (s == "--preset" || s == "--combine-strands" || s == "--with-header" || s == "--header" || s == "--partition-tag" || s == "--prefix"
-        || s == "--bedgraph" || s == "--plan-only" || s.compare(0, 14, "--region-stats") == 0))
+        || s == "--bedgraph" || s == "--plan-only" || s.compare(0, 14, "--region-stats") == 0 || s.compare(0, 10, "--localize") == 0))
       throw Error(MKP_E_INVALID, "unexpected argument '" + s + "' for pileup-hemi");
     if (hemi && (s == "-o" || s == "--out-bed")) { a.out_bed = val(); continue; }
     if (s == "--region") a.region = val(); else if (s == "--max-depth") a.max_depth = (uint32_t)std::stoul(val());
@@ -1614,6 +1645,16 @@ void parse_args(int argc, const char* const* argv, Args* out, bool need_position
         a.region_stats_codes.push_back(code); if (p1 == std::string::npos) break; p0 = p1 + 1; } }
     else if (s == "--region-stats-min-coverage") a.region_stats_min_cov = std::stoull(val());
     else if (s == "--region-stats-no-header") a.region_stats_no_header = true; else if (s == "--region-stats-only") a.region_stats_only = true;
+    else if (s == "--localize") a.localize = val(); else if (s == "--localize-out") a.localize_out = val();
+    else if (s == "--localize-window") { const std::string v = val();
+      if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 9) throw Error(MKP_E_INVALID, "bad --localize-window " + v);
+      a.localize_window = (uint32_t)std::stoul(v); a.have_localize_window = true; }
+    else if (s == "--localize-stranded") { const std::string v = val(); a.localize_stranded = v == "same" ? 1 : v == "opposite" ? 2 : 0;
+      if (!a.localize_stranded) throw Error(MKP_E_INVALID, "--localize-stranded takes same or opposite, not '" + v + "'"); }
+    else if (s == "--localize-stranded-features") { const std::string v = val();   // (the reference's value names, and the strand characters)
+      a.localize_stranded_features = v == "+" || v == "positive" ? 1 : v == "-" || v == "negative" ? 2 : v == "." || v == "both" ? 3 : 0;
+      if (!a.localize_stranded_features) throw Error(MKP_E_INVALID, "--localize-stranded-features takes +, - or ., not '" + v + "'"); }
+    else if (s == "--localize-only") a.localize_only = true;
     else if (!s.empty() && s[0] == '-' && s != "-") throw Error(MKP_E_INVALID, "unknown flag " + s);
     else pos.push_back(s);
   }
@@ -1634,6 +1675,18 @@ void parse_args(int argc, const char* const* argv, Args* out, bool need_position
     if (a.region_stats_only && (a.bedgraph || a.bgzf)) throw Error(MKP_E_INVALID, "--region-stats-only writes no rows: drop --bedgraph / --bgzf");
     if (a.world > 1) throw Error(MKP_E_UNSUPPORTED,
         "--region-stats with --gpus-world > 1: the ranks' tables would have to be summed (an all-reduce that is not implemented)");
+  }
+  if (a.localize.empty()) { if (!a.localize_out.empty() || a.have_localize_window || a.localize_stranded || a.localize_stranded_features
+      || a.localize_only) throw Error(MKP_E_INVALID, "the --localize-* flags need --localize <regions.bed>"); }
+  else {
+    if (a.localize_out.empty()) throw Error(MKP_E_INVALID, "--localize needs --localize-out <table.tsv>");
+    if (!a.partition_tags.empty()) throw Error(MKP_E_INVALID,
+        "--localize cannot be combined with --partition-tag: the rows of a partitioned run come grouped by key, not in genome order");
+    if (a.plan_only) throw Error(MKP_E_INVALID, "--localize cannot be combined with --plan-only");
+    if (a.localize_only && (a.bedgraph || a.bgzf)) throw Error(MKP_E_INVALID, "--localize-only writes no rows: drop --bedgraph / --bgzf");
+    if (a.localize_window > MKP_LOC_MAX_WINDOW) throw Error(MKP_E_UNSUPPORTED, "--localize-window beyond " + std::to_string(MKP_LOC_MAX_WINDOW));
+    if (a.world > 1) throw Error(MKP_E_UNSUPPORTED,
+        "--localize with --gpus-world > 1: the ranks' tables would have to be summed (an all-reduce that is not implemented)");
   }
 }
 
@@ -1671,6 +1724,37 @@ extern "C" const mkp_region* mkp_region_set_regions(const mkp_region_set* set) {
 extern "C" const char* mkp_region_set_chrom(const mkp_region_set* set, uint32_t i) { return set && i < set->chrom.size() ? set->chrom[i].c_str() : nullptr; }
 extern "C" const char* mkp_region_set_name(const mkp_region_set* set, uint32_t i) { return set && i < set->name.size() ? set->name[i].c_str() : nullptr; }
 extern "C" void mkp_region_set_free(mkp_region_set* set) { delete set; }
+extern "C" int mkp_host_parse_localize_regions(const char* bed_path, const char* const* contig_names, uint32_t n_contigs, mkp_region_set** out,
+    uint32_t* n_skipped, char* errbuf, size_t errbuf_len) {
+  auto fail = [&](int st, const std::string& m) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", m.c_str()); } return st; };
+  if (!bed_path || !out || (!contig_names && n_contigs)) return fail(MKP_E_INVALID, "bad argument");
+  *out = nullptr;
+  try {
+    std::map<std::string, int> tids; for (uint32_t k = 0; k < n_contigs; k++) tids.emplace(contig_names[k], (int)k);
+    std::unique_ptr<mkp_region_set> set(new mkp_region_set(parse_localize_regions_bed(bed_path, [&](const std::string& chrom) {
+      auto it = tids.find(chrom); return it == tids.end() ? -1 : it->second; }, n_skipped)));
+    *out = set.release();
+    return MKP_OK;
+  } catch (const Error& e) { return fail(e.status, e.what()); }
+  catch (const std::exception& e) { return fail(MKP_E_INVALID, e.what()); }
+}
+extern "C" int mkp_host_parse_genome_sizes(const char* path, mkp_genome_sizes** out, char* errbuf, size_t errbuf_len) {
+  auto fail = [&](int st, const std::string& m) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", m.c_str()); } return st; };
+  if (!path || !out) return fail(MKP_E_INVALID, "bad argument");
+  *out = nullptr;
+  try { *out = new mkp_genome_sizes(parse_genome_sizes(path)); return MKP_OK; }
+  catch (const Error& e) { return fail(e.status, e.what()); }
+  catch (const std::exception& e) { return fail(MKP_E_INVALID, e.what()); }
+}
+extern "C" uint32_t mkp_genome_sizes_size(const mkp_genome_sizes* z) { return z ? (uint32_t)z->name.size() : 0u; }
+extern "C" const char* mkp_genome_sizes_name(const mkp_genome_sizes* z, uint32_t i) { return z && i < z->name.size() ? z->name[i].c_str() : nullptr; }
+extern "C" uint64_t mkp_genome_sizes_length(const mkp_genome_sizes* z, uint32_t i) { return z && i < z->length.size() ? z->length[i] : 0ull; }
+extern "C" void mkp_genome_sizes_free(mkp_genome_sizes* z) { delete z; }
+extern "C" int mkp_host_localize_table(const mkp_localize_out* counts, const char* out_path) {
+  if (!counts || !out_path) return MKP_E_INVALID;
+  try { write_text_file(out_path, localize_table_text(*counts, f32_display)); return MKP_OK; }
+  catch (const Error& e) { return e.status; } catch (const std::exception&) { return MKP_E_INVALID; }
+}
 extern "C" int mkp_host_stats_table(const mkp_region_set* set, const mkp_stats_out* counts, int with_header, const char* out_path) {
   if (!set || !counts || !out_path) return MKP_E_INVALID;
   try { write_text_file(out_path, stats_table_text(*set, *counts, with_header != 0, f32_display)); return MKP_OK; }

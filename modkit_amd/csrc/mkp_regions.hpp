@@ -1,4 +1,6 @@
-// Host halves of `modkit stats` (EntryStats::run, src/stats/subcommand.rs:65-206): the regions BED and the table text.  No device here.
+// Host halves of `modkit stats` (EntryStats::run, src/stats/subcommand.rs:65-206): the regions BED and the table text; and of
+// `modkit localize` (EntryLocalize, src/localise/subcommand.rs:104-305): its tolerant regions loader, the genome sizes and its table.
+// No device here.
 #pragma once
 #include <cstdio>
 #include <fstream>
@@ -7,6 +9,7 @@
 
 #include "mkp_pack.hpp"
 
+struct mkp_genome_sizes { std::vector<std::string> name; std::vector<uint64_t> length; };
 struct mkp_region_set {
   std::vector<mkp_region> regions;          // tid = index into the contig names given to the parser, -1 = not among them
   std::vector<std::string> chrom, name;     // name "." = the line has none
@@ -124,6 +127,73 @@ template <class F32Text> std::string stats_table_text(const mkp_region_set& set,
   };
   if (n_pieces > 1) HostPool::get().parallel(n_pieces, rows_of); else rows_of(0);
   for (auto& o : piece) s += o;
+  return s;
+}
+
+// ---- localize
+// load_focus_regions up to its contig filters (src/localise/subcommand.rs:105-162): the parser is picked by the WHITESPACE-separated
+// fields (split_whitespace: runs of any blank count once, leading ones not at all) of the first line that does not start with '#'; a line
+// that fails is counted, not fatal; there is no start <= end check.
+template <class TidOf> mkp_region_set parse_localize_regions_bed(const std::string& path, TidOf tid_of, uint32_t* n_skipped) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) throw Error(MKP_E_IO, "failed to open regions BED " + path);
+  std::vector<std::string> lines; std::string line;
+  while (std::getline(f, line)) { if (!line.empty() && line.back() == '\r') line.pop_back(); lines.push_back(line); }   // BufRead::lines
+  size_t first = 0; while (first < lines.size() && !lines[first].empty() && lines[first][0] == '#') first++;
+  if (first >= lines.size()) throw Error(MKP_E_INVALID, "failed to inspect regions BED, no valid lines: " + path);
+  // char::is_whitespace on what a BED line can hold: blank, tab, LF, VT, FF, CR (and the Unicode blanks, which count as field text here)
+  auto white = [](char c) { return c == ' ' || (c >= '\t' && c <= '\r'); };
+  size_t fields = 0; { bool in = false; for (char c : lines[first]) { const bool wsp = white(c); if (!wsp && !in) fields++; in = !wsp; } }
+  const bool stranded = fields > 4;
+  mkp_region_set out; uint32_t skipped = 0;
+  for (size_t k = 0; k < lines.size(); k++) {
+    BedLineParser p(lines[k]); std::string chrom, name; uint64_t s = 0, e = 0; uint8_t rule = 3;
+    bool ok = p.string(&chrom) && p.digits(&s) && p.digits(&e);
+    bool has_name = false;
+    if (ok) { has_name = p.name(&name); if (stranded) ok = p.score() && p.strand(&rule); }
+    if (!ok) { skipped++; continue; }
+    if (s > 0xffffffffull || e > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "line " + std::to_string(k + 1) + " of " + path
+        + ": coordinate beyond 2^32 - 1");
+    mkp_region g; memset(&g, 0, sizeof(g)); g.tid = (int32_t)tid_of(chrom); g.start = (uint32_t)s; g.end = (uint32_t)e; g.strand_rule = rule;
+    out.regions.push_back(g); out.chrom.push_back(chrom); out.name.push_back(has_name ? name : ".");
+  }
+  if (out.regions.empty()) throw Error(MKP_E_INVALID, "failed to load any regions from " + path + ": " + std::to_string(skipped)
+      + " lines failed to parse");
+  if (n_skipped) *n_skipped = skipped;
+  return out;
+}
+
+// read_sequence_lengths_file (src/util.rs:969-990): a contig name, blanks, a length; what follows is not looked at; any other line fails;
+// collected into an IndexMap: a later line for the same contig replaces the length and keeps the place
+inline mkp_genome_sizes parse_genome_sizes(const std::string& path) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) throw Error(MKP_E_IO, "failed to open genome sizes " + path);
+  mkp_genome_sizes out; std::string line;
+  while (std::getline(f, line)) {
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    BedLineParser p(line); std::string chrom; uint64_t len = 0;
+    if (!(p.string(&chrom) && p.digits(&len))) throw Error(MKP_E_INVALID, "failed to parse sizes " + line);
+    size_t k = 0; while (k < out.name.size() && out.name[k] != chrom) k++;
+    if (k < out.name.size()) out.length[k] = len; else { out.name.push_back(chrom); out.length.push_back(len); }
+  }
+  return out;
+}
+
+// LocalizedModCounts::get_table (src/localise/util.rs:48-82) through the tab-delimited csv writer; `f32_text` = f32 Display
+template <class F32Text> std::string localize_table_text(const mkp_localize_out& t, F32Text f32_text) {
+  std::string s = "mod_code\toffset\tn_valid\tn_mod\tpercent_modified\n";
+  const int64_t w = (int64_t)t.window; const size_t n_off = 2 * (size_t)t.window + 1;
+  for (uint32_t k = 0; k < t.n_codes; k++) {
+    const std::string c = code_text(t.code_repr[k]);
+    for (size_t o = 0; o < n_off; o++) {
+      const size_t i = (size_t)k * n_off + o;
+      if (!t.n_rows[i]) continue;
+      const uint64_t nm = t.n_mod[i], nv = t.n_valid[i];
+      const float pct = nv == 0 ? 0.0f : ((float)nm / (float)nv) * 100.0f;   // ModPositionInfo::percent_modified (src/util.rs:920-936)
+      s += c; s += '\t'; s += std::to_string((int64_t)o - w); s += '\t'; s += std::to_string(nv); s += '\t'; s += std::to_string(nm); s += '\t';
+      s += f32_text(pct); s += '\n';
+    }
+  }
   return s;
 }
 
