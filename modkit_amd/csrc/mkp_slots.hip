@@ -380,10 +380,16 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
 // Reference: DeltaListConverter (mod_bam.rs:667-733), get_base_mod_probs (1213-1295), combine_checked (629-656),
 // into_collapsed (530-627), MultipleThresholdModCaller::call (threshold_mod_caller.rs:28-63), ReadCache::add_record
 // (read_cache.rs:111-211), get_aligned_pairs_forward (util.rs:122-145), process_region's alignment loop (pileup/mod.rs:783-939).
-// One wave runs one read start to end.  Measured (SQ counters, C3): the kernel is VALU-issue bound, so the per-slot instruction count
-// matters: the SEQ and the rank list were resolved into the plane when the shard became resident (mkp_call_plane), so that a slot learns its
-// base, whether a call is listed there and as which call from one 16-byte gather and a popcount; the caller is resolved to
-// a fixed walk per read.  No per-read LDS beyond the caller constants and no base windows: reads of every length take the same code.
+// One wave runs one read start to end.  The per-slot instruction count matters (about 170 M VALU per C3 pass): the SEQ and the rank list
+// were resolved into the plane when the shard became resident (mkp_call_plane), so that a slot learns its base, whether a call is listed
+// there and as which call from one 16-byte gather and a popcount; the caller is resolved to a fixed walk per read.  No per-read LDS beyond
+// the caller constants and no base windows: reads of every length take the same code.
+// With every step waiting in full for its gather and then for its ML bytes a wave was parked on s_waitcnt for 70 % of its life (SQ counters,
+// C3, eight waves per SIMD) and the kernel ran well short of its issue rate.  The slot loop is therefore a two-deep software pipeline
+// over the 64-slot steps — A: map, request the plane gather; B: request the ML bytes; C: call, feature byte — run as B(s), A(s + 1),
+// C(s), so that the ML bytes of step s travel under the mapping of step s + 1 and the gather of step s + 1 under the caller of step s (the
+// comment at the loop has the details).  As it stands the kernel is bound by VALU issue again (profiles/decode_pipeline_c3.txt): what pays
+// now is fewer instructions per step, not more overlap.
 #define FUSED_PARAMS(PRM) const MkpWork* __restrict__ work, uint32_t n_reads, const uint32_t* __restrict__ cigar, const uint16_t* __restrict__ cigar16, \
     const uint8_t* __restrict__ seqs, \
     const uint4* __restrict__ plane, const uint8_t* __restrict__ ml, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const uint32_t* __restrict__ slot_pos, \
@@ -431,7 +437,9 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
     const MkpFusedDesc fd = fdesc[h.layout];
     fmisc = fd.misc; i_can = fd.i_can;
     if (lane < MKP_KMAX) {
-      const uint32_t src = (fd.it_src >> (4 * lane)) & 15u, tg = src & 1u;
+      // the ML byte of a code the layout does not have is that of its last code: B requests two bytes, or four, C reads n_post of them
+      const int lk = min(lane, (int)max((fd.misc >> 3) & 7u, 1u) - 1);
+      const uint32_t src = (fd.it_src >> (4 * lk)) & 15u, tg = src & 1u;
       W.ck_off[lane] = (tg ? h.ml_off1 : h.ml_off0) + (src >> 1); W.ck_str[lane] = (fd.nc >> (8u * tg)) & 0xffu;
       W.ck_thr[lane] = lane == 0 ? fd.i_thr[0] : lane == 1 ? fd.i_thr[1] : lane == 2 ? fd.i_thr[2] : fd.i_thr[3];
       W.ck_cid[lane] = (fd.it_cid >> (8 * lane)) & 0xffu;
@@ -463,47 +471,88 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
 #else
   const uint32_t n_sl_walk = n_sl;
 #endif
-  for (uint32_t s0 = 0; s0 < n_sl_walk; s0 += 64u) {
+  // The loop is a software pipeline, two steps deep.  A step is three stages:
+  //   A(s)  reference -> query of the step's 64 slots (refwin_s_map), then the plane gather pe(s) and the slot positions of step s + 1 are
+  //         requested.  Both addresses are unconditional — clamped into the read's own plane / slot run — and the entry is masked where it is
+  //         used: a load under a divergent branch is waited for on the spot.
+  //   B(s)  `listed` and the call ordinal from pe(s), then the ML bytes of the step's calls (and the SEQ byte of a SEQN read) are requested;
+  //         a step without a listed call requests nothing.  What C needs of the slot is packed into one register (st).
+  //   C(s)  the caller on the ML bytes, the feature byte, `gaps` / `n_callfeat`.  The byte is stored in B(s + 1), behind its requests (and
+  //         behind the loop for the last step): the wait for pe(s + 1) at the head of the next iteration is a full one — the compiler
+  //         counts the loop's entry edge, where nothing follows the gather — and a store issued just before it would be waited for.
+  // A(0) runs in front of the loop; an iteration runs B(s), A(s + 1), C(s): the ML round trip of step s passes under the mapping of step
+  // s + 1 — the longest VALU and LDS stretch of an iteration — and the gather of step s + 1 under the caller of step s.  Loads return in
+  // issue order, so the wait in front of C(s) is a counted one that leaves pe(s + 1) and the slot positions in flight.  A(s + 1) runs
+  // behind the last step as well (every lane invalid: no mapping, two loads of addresses inside the read's rooms): a branch around it would
+  // make that wait a full drain.  Carried across A(s + 1): the ML bytes, the SEQ byte and st; across C(s): pe(s + 1), kind, q.
+  const uint32_t pl_last = max(MKP_PLANE_WORDS(L), 1u) - 1u, sq_last = (max(L, 1u) - 1u) >> 1, sl_last = max(n_sl, 1u) - 1u;
+  uint32_t kind = 2u, q = 0u, fb_prev = 0u; uint4 pe = make_uint4(0u, 0u, 0u, 0u);
+  auto stage_a = [&](uint32_t s0) {
     const uint32_t i = s0 + (uint32_t)lane;
     const bool valid = i < n_sl;
     const int32_t p = (int32_t)p_next;
-    { const uint32_t in = i + 64u; p_next = in < n_sl ? ldo<uint32_t>(spos, 4u * in) : 0u; }
-    uint32_t kind, q;
 #ifdef MKP_DEBUG
     if (prm.debug_skip & 64u) { kind = 0u; q = min((uint32_t)(p - h.ref_start), L - 1u); } else   // ablation: no CIGAR mapping
 #endif
     refwin_s_map(rw, cg, cg_wide, h.n_cigar, h.ref_start, valid, p, &kind, &q);
-    const bool is_match = valid && kind == 0u && q < L;
     // the plane entry of the base: its 2-bit code, bit q & 31 of .listed = a listed call sits here, .before + the listed bits below it =
     // its stored-order ordinal
-    const uint4 pe = is_match ? ldo<uint4>(pl, 16u * (q >> 5)) : make_uint4(0u, 0u, 0u, 0u);
-    uint32_t code = (((q & 16u) ? pe.y : pe.x) >> (2u * (q & 15u))) & 3u;
-    asm volatile("" : "+v"(code));   // (formed here: left to itself the compiler carries .x and .y through the caller below)
+    pe = ldo<uint4>(pl, 16u * min(q >> 5, pl_last));
+    p_next = ldo<uint32_t>(spos, 4u * min(i + 64u, sl_last));   // (behind the gather: see the wait for pe at the head of B)
+  };
+  enum : uint32_t { ST_QODD = 1u << 8, ST_MATCH = 1u << 9, ST_LISTED = 1u << 10 };
+  if (n_sl_walk != 0u) stage_a(0u);
+  for (uint32_t s0 = 0; s0 < n_sl_walk; s0 += 64u) {
+    const uint32_t i = s0 + (uint32_t)lane;
+    const bool valid = i < n_sl;
+    // ---- B(s)
+    // (pe(s) and the slot positions were requested back to back: both are waited for here, in front of the ML requests, not behind them)
+    asm volatile("" : "+v"(p_next));
+    uint32_t st;   // the coverage feature byte | ST_*
+    uint32_t mlb[MKP_KMAX] = {0u, 0u, 0u, 0u}, mlx = 0, seq_byte = 0;
+    {
+      const bool is_match = valid && kind == 0u && q < L;
+      const uint32_t code = (((q & 16u) ? pe.y : pe.x) >> (2u * (q & 15u))) & 3u;
+      uint32_t fb = cover_feature(valid ? kind : 2u, 1u << code, aln);   // (the BAM code of the base is one-hot for A/C/G/T)
+      if (valid && kind == 0u && q >= L) fb = MKP_FB_NONE;   // (a CIGAR longer than SEQ is refused by the packer)
+      st = fb;
+      if (plane_calls) {
+        const uint32_t qb = q & 31u;
+        const bool listed = is_match && ((pe.z >> qb) & 1u);
+        if (__any(listed)) {
+          // calls are listed in forward order: a reverse read's stored ordinal j is call n_calls - 1 - j
+          const uint32_t jrel = pe.w + (uint32_t)__popc(pe.z & ((1u << qb) - 1u));
+          const uint32_t jl = listed ? (rev ? t_n - 1u - jrel : jrel) : 0u;
+          // All ML bytes of the call are requested before any is looked at (round 5 waited for each in turn: two to five dependent
+          // memory round trips per 64 slots, the longest chain of the wave's life).
+          const uint4 off4 = *reinterpret_cast<const uint4*>(W.ck_off), str4 = *reinterpret_cast<const uint4*>(W.ck_str);
+          // Two requests, or four: a branch per code made the compiler join the paths with copies of the loaded registers, each behind a
+          // wait of its own.  The entry of a code the read does not have repeats the read's last code (the caller constants above).
+          auto mlq = [&](uint32_t o, uint32_t st_k) { return (uint32_t)ldo<uint8_t>(ml, __umul24(jl, st_k) + o); };
+          mlb[0] = mlq(off4.x, str4.x); mlb[1] = mlq(off4.y, str4.y);
+          if (n_post > 2u) { mlb[2] = mlq(off4.z, str4.z); mlb[3] = mlq(off4.w, str4.w); }
+          if (f_col & 1u) mlx = (uint32_t)ldo<uint8_t>(ml, __umul24(jl, mlx_s) + mlx_o);
+          if (listed) st |= ST_LISTED;
+        }
+      }
+      // a SEQN read's base comes from its SEQ byte, so that a non-ACGT base stays one
+      if (seqn_off != 0xffffffffu) {
+        seq_byte = (uint32_t)ldo<uint8_t>(seqs, seqn_off + min(q >> 1, sq_last));
+        st |= ((q & 1u) ? ST_QODD : 0u) | (is_match ? ST_MATCH : 0u);
+      }
+    }
+    // the feature bytes of step s - 1 leave here, behind the ML requests: by the next wait for a gather the store is a whole iteration old
+    if (i - 64u < n_sl) cov[h.cov_off + i - 64u] = (uint8_t)fb_prev;
+    // ---- A(s + 1)
+    stage_a(s0 + 64u);
+    // ---- C(s)
     uint32_t call_fb = 0xffffffffu;
-    if (plane_calls) {
-      const uint32_t qb = q & 31u;
-      const bool listed = (pe.z >> qb) & 1u;
+    {
+      const bool listed = (st & ST_LISTED) != 0u;
       if (__any(listed)) {
-        // calls are listed in forward order: a reverse read's stored ordinal j is call n_calls - 1 - j
-        const uint32_t jrel = pe.w + (uint32_t)__popc(pe.z & ((1u << qb) - 1u));
-        const uint32_t jl = listed ? (rev ? t_n - 1u - jrel : jrel) : 0u;
         // MultipleThresholdModCaller::call (threshold_mod_caller.rs:28-63) on the map of this call, entries in the map's
         // iteration order: pass threshold, Iterator::max keeps the last maximum, canonical pushed last.  ReDistribute runs
         // (--ignore, --preset traditional) first add the collapsed code's share to every entry (mod_bam.rs:558-600).
-        // All ML bytes of the call are requested before any is looked at (round 5 waited for each in turn: two to five dependent
-        // memory round trips per 64 slots, the longest chain of the wave's life).
-        const uint4 off4 = *reinterpret_cast<const uint4*>(W.ck_off), str4 = *reinterpret_cast<const uint4*>(W.ck_str);
-        const uint32_t ml_o[MKP_KMAX] = {off4.x, off4.y, off4.z, off4.w}, ml_s[MKP_KMAX] = {str4.x, str4.y, str4.z, str4.w};
-        uint32_t mlb[MKP_KMAX] = {0u, 0u, 0u, 0u}, mlx = 0;
-        auto mlq = [&](int k) { return (uint32_t)ldo<uint8_t>(ml, __umul24(jl, ml_s[k]) + ml_o[k]); };
-        switch (n_post) {   // (uniform)
-          case 1: mlb[0] = mlq(0); break;
-          case 2: mlb[0] = mlq(0); mlb[1] = mlq(1); break;
-          case 3: mlb[0] = mlq(0); mlb[1] = mlq(1); mlb[2] = mlq(2); break;
-          case 4: mlb[0] = mlq(0); mlb[1] = mlq(1); mlb[2] = mlq(2); mlb[3] = mlq(3); break;
-          default: break;
-        }
-        if (f_col & 1u) mlx = (uint32_t)ldo<uint8_t>(ml, __umul24(jl, mlx_s) + mlx_o);
         uint32_t cid = MKP_C_FAIL;
         if (int_caller) {
           // The same walk in integers, exactly: q -> (q + 0.5) / 256 is a multiple of 2^-9, the share of a collapsed code (its
@@ -555,17 +604,15 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
         if (listed) call_fb = feat(cid, aln ^ sg0u);   // FeatureVector::add_feature's tally (pileup/mod.rs:238-281)
       }
     }
-    // the BAM code of the base (one-hot for A/C/G/T); a SEQN read's from its SEQ byte, so that a non-ACGT base stays one
-    uint32_t nib = 1u << code;
-    if (seqn_off != 0xffffffffu) {
-      const uint32_t byte = is_match ? (uint32_t)ldo<uint8_t>(seqs, seqn_off + (q >> 1)) : 0u; nib = (q & 1u) ? (byte & 15u) : (byte >> 4); }
-    uint32_t fb = cover_feature(valid ? kind : 2u, nib, aln);
-    if (valid && kind == 0u && q >= L) fb = MKP_FB_NONE;   // (a CIGAR longer than SEQ is refused by the packer)
+    uint32_t fb = st & 0xffu;
+    if (seqn_off != 0xffffffffu && (st & ST_MATCH)) {
+      const uint32_t nib = (st & ST_QODD) ? (seq_byte & 15u) : (seq_byte >> 4); fb = cover_feature(0u, nib, aln); }
     // (a scalar count: no per-lane counter, no scan at the end)
     { const bool cf = call_fb != 0xffffffffu; if (cf) fb = call_fb; n_callfeat += (uint32_t)__popcll(__ballot(cf)); }
-    if (valid) cov[h.cov_off + i] = (uint8_t)fb;
+    fb_prev = fb;
     gaps = gaps || (valid && fb == MKP_FB_NONE);
   }
+  if (n_sl_walk != 0u) { const uint32_t i = ((n_sl_walk - 1u) & ~63u) + (uint32_t)lane; if (i < n_sl) cov[h.cov_off + i] = (uint8_t)fb_prev; }
   gaps = __any(gaps);
   const bool ok = have_calls;
   const uint32_t tally = aln ^ sg0u, ob_const = fmisc >> 16;
