@@ -389,6 +389,36 @@ class RunReport(ctypes.Structure):
         return d
 
 
+def _region_array(regions):
+    """(Region array, n) of a RegionSet, or of [(tid, start, end, strand "+-." or rule 1..3), ...]."""
+    if isinstance(regions, RegionSet):
+        return regions.array, regions.n
+    n = len(regions)
+    arr = (Region * max(1, n))()
+    for i, (tid, start, end, rule) in enumerate(regions):
+        arr[i].tid, arr[i].start, arr[i].end = int(tid), int(start), int(end)
+        arr[i].strand_rule = STRAND_RULES[rule] if isinstance(rule, str) else int(rule)
+    return arr, n
+
+
+def _rows_struct(rows):
+    """(Rows over the five columns the row reducers read, the arrays it points into) of a dict of arrays."""
+    import numpy as np
+    cols = {f: np.ascontiguousarray(np.asarray(rows[f], dtype=np.uint8 if f == "strand" else np.uint32))
+            for f in ("pos", "strand", "code_repr", "n_valid", "n_mod")}
+    r = Rows()
+    r.n_rows = len(cols["pos"])
+    for f, a in cols.items():
+        setattr(r, f, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8 if f == "strand" else ctypes.c_uint32)))
+    return r, cols
+
+
+def _copy_out(p, shape, dt):
+    """A copy of the library's array behind p; an empty shape has no pointer to read."""
+    import numpy as np
+    return np.ctypeslib.as_array(p, shape=shape).copy() if all(shape) else np.zeros(shape, dtype=dt)
+
+
 class Context:
     """One mkp_ctx (one per host thread; binds to one GPU)."""
 
@@ -566,14 +596,7 @@ class Context:
     def stats_begin(self, regions, codes=None, min_coverage=1):
         """mkp_stats_begin: regions = a RegionSet, or [(tid, start, end, strand "+-." or rule 1..3), ...]; codes = the `--mod-codes` list
         (letters, ChEBI numbers as text, or code_repr ints) or None for every code met; min_coverage = `--min-coverage`."""
-        if isinstance(regions, RegionSet):
-            arr, n = regions.array, regions.n
-        else:
-            n = len(regions)
-            arr = (Region * max(1, n))()
-            for i, (tid, start, end, rule) in enumerate(regions):
-                arr[i].tid, arr[i].start, arr[i].end = int(tid), int(start), int(end)
-                arr[i].strand_rule = STRAND_RULES[rule] if isinstance(rule, str) else int(rule)
+        arr, n = _region_array(regions)
         cs = [code_repr(c) for c in (codes or [])]
         carr = (ctypes.c_uint32 * max(1, len(cs)))(*cs)
         self._check(self.L.mkp_stats_begin(self.h, arr, n, carr, len(cs), int(min_coverage)))
@@ -585,37 +608,21 @@ class Context:
     def stats_add_rows(self, tid, rows):
         """mkp_stats_add_rows: rows of ONE contig, ascending pos, as a dict of arrays (pos, strand as bytes '+-.', code_repr, n_valid, n_mod:
         what read_bedmethyl / rows_to_numpy give); they are uploaded and reduced by the same kernels."""
-        import numpy as np
-        cols = {f: np.ascontiguousarray(np.asarray(rows[f], dtype=np.uint8 if f == "strand" else np.uint32))
-                for f in ("pos", "strand", "code_repr", "n_valid", "n_mod")}
-        r = Rows()
-        r.n_rows = len(cols["pos"])
-        for f, a in cols.items():
-            setattr(r, f, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8 if f == "strand" else ctypes.c_uint32)))
+        r, _keep = _rows_struct(rows)
         self._check(self.L.mkp_stats_add_rows(self.h, int(tid), ctypes.byref(r)))
 
     def stats_get(self):
         """mkp_stats_get: {"codes": u32[n_codes] sorted, "n_mod" / "n_valid": u64[n_regions, n_codes], "contig_has_rows": u8[n_regions]}."""
-        import numpy as np
         o = StatsOut()
         self._check(self.L.mkp_stats_get(self.h, ctypes.byref(o)))
-        n, k = int(o.n_regions), int(o.n_codes)
-        def arr(p, shape, dt):
-            return np.ctypeslib.as_array(p, shape=shape).copy() if all(shape) else np.zeros(shape, dtype=dt)
-        return {"codes": arr(o.code_repr, (k,), np.uint32), "n_mod": arr(o.n_mod, (n, k), np.uint64), "n_valid": arr(o.n_valid, (n, k), np.uint64),
-                "contig_has_rows": arr(o.contig_has_rows, (n,), np.uint8)}
+        n, k, arr = int(o.n_regions), int(o.n_codes), _copy_out
+        return {"codes": arr(o.code_repr, (k,), "u4"), "n_mod": arr(o.n_mod, (n, k), "u8"), "n_valid": arr(o.n_valid, (n, k), "u8"),
+                "contig_has_rows": arr(o.contig_has_rows, (n,), "u1")}
 
     def localize_begin(self, regions, contig_lengths, window=2000, stranded=None, stranded_features=None):
         """mkp_localize_begin: regions = a RegionSet, or [(tid, start, end, strand "+-." or rule 1..3), ...] (start > end allowed);
         contig_lengths[tid] = the genome-sizes table; stranded = None / "same" / "opposite"; stranded_features = None / "+" / "-" / "."."""
-        if isinstance(regions, RegionSet):
-            arr, n = regions.array, regions.n
-        else:
-            n = len(regions)
-            arr = (Region * max(1, n))()
-            for i, (tid, start, end, rule) in enumerate(regions):
-                arr[i].tid, arr[i].start, arr[i].end = int(tid), int(start), int(end)
-                arr[i].strand_rule = STRAND_RULES[rule] if isinstance(rule, str) else int(rule)
+        arr, n = _region_array(regions)
         lens = (ctypes.c_uint64 * max(1, len(contig_lengths)))(*[int(x) for x in contig_lengths])
         self._check(self.L.mkp_localize_begin(self.h, arr, n, lens, len(contig_lengths), int(window), STRANDED[stranded], STRANDED_FEATURES[stranded_features]))
 
@@ -625,26 +632,17 @@ class Context:
 
     def localize_add_rows(self, tid, rows):
         """mkp_localize_add_rows: rows of ONE contig, ascending pos, as stats_add_rows takes them."""
-        import numpy as np
-        cols = {f: np.ascontiguousarray(np.asarray(rows[f], dtype=np.uint8 if f == "strand" else np.uint32))
-                for f in ("pos", "strand", "code_repr", "n_valid", "n_mod")}
-        r = Rows()
-        r.n_rows = len(cols["pos"])
-        for f, a in cols.items():
-            setattr(r, f, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8 if f == "strand" else ctypes.c_uint32)))
+        r, _keep = _rows_struct(rows)
         self._check(self.L.mkp_localize_add_rows(self.h, int(tid), ctypes.byref(r)))
 
     def localize_get(self):
         """mkp_localize_get: {"codes": u32[n_codes] sorted, "window": w, "n_mod" / "n_valid" / "n_rows": u64[n_codes, 2 w + 1]}, column
         offset + w; a (code, offset) cell is a table line when its n_rows is not 0."""
-        import numpy as np
         o = LocalizeOut()
         self._check(self.L.mkp_localize_get(self.h, ctypes.byref(o)))
-        k, n = int(o.n_codes), 2 * int(o.window) + 1
-        def arr(p, shape, dt):
-            return np.ctypeslib.as_array(p, shape=shape).copy() if all(shape) else np.zeros(shape, dtype=dt)
-        return {"codes": arr(o.code_repr, (k,), np.uint32), "window": int(o.window), "n_mod": arr(o.n_mod, (k, n), np.uint64),
-                "n_valid": arr(o.n_valid, (k, n), np.uint64), "n_rows": arr(o.n_rows, (k, n), np.uint64)}
+        k, n, arr = int(o.n_codes), 2 * int(o.window) + 1, _copy_out
+        return {"codes": arr(o.code_repr, (k,), "u4"), "window": int(o.window), "n_mod": arr(o.n_mod, (k, n), "u8"),
+                "n_valid": arr(o.n_valid, (k, n), "u8"), "n_rows": arr(o.n_rows, (k, n), "u8")}
 
     def rerun(self, iters, fetch=False):
         rows = Rows()

@@ -1084,11 +1084,12 @@ void mkp_ctx_destroy(mkp_ctx* c) {
                     &c->d_slotbm, &c->d_prm, &c->d_read_ids, &c->d_chunk, &c->d_store, &c->d_hist0, &c->d_hist1, &c->d_sample_cursor, &c->d_take,
                         &c->d_tile_row_off, &c->d_tile_row_cnt, &c->d_tile_dst, &c->d_misc, &c->d_rows_src, &c->d_rows_dst, &c->d_hemi_iv,
                         &c->d_slot_pos, &c->d_cov, &c->d_visits, &c->d_stiles, &c->d_slot_ids, &c->d_fdesc, &c->d_work, &c->d_plane, &c->d_zin, &c->d_zout,
-                        &c->d_zblk, &c->d_zstat, &c->d_summary, &c->d_bedmask, &c->d_hist64, &c->rstats.d_regions, &c->rstats.d_out, &c->rstats.d_seen,
-                        &c->rstats.d_misc, &c->rstats.d_lo, &c->rstats.d_hi, &c->rstats.d_cnt, &c->rstats.d_off, &c->rstats.d_rows,
-                        &c->loc.d_regions, &c->loc.d_tab, &c->loc.d_misc, &c->loc.d_lo, &c->loc.d_hi, &c->loc.d_rows}) b->release();
-  for (auto& e : c->rstats.ev) if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->loc.ev) if (e) (void)hipEventDestroy(e);
+                        &c->d_zblk, &c->d_zstat, &c->d_summary, &c->d_bedmask, &c->d_hist64, &c->rstats.d_out, &c->rstats.d_seen,
+                        &c->rstats.d_cnt, &c->rstats.d_off, &c->loc.d_tab}) b->release();
+  for (mkp_ctx::RowTable* t : {static_cast<mkp_ctx::RowTable*>(&c->rstats), static_cast<mkp_ctx::RowTable*>(&c->loc)}) {
+    for (DevBuf* b : {&t->d_regions, &t->d_misc, &t->d_lo, &t->d_hi, &t->d_rows}) b->release();
+    for (auto& e : t->ev) if (e) (void)hipEventDestroy(e);
+  }
   mkp_internal_ingest_destroy(c->ingest); c->ingest = nullptr;
   c->h_rows.release();
   for (auto& e : c->ev) if (e) (void)hipEventDestroy(e);
@@ -1892,6 +1893,101 @@ int mkp_percentile_from_histogram(uint64_t n, float q, float y0, float y1, float
 
 }  // extern "C"
 
+// ---- sessions over bedMethyl rows that are already in HBM (mkp_ctx::RowTable): what region statistics and localize share
+namespace {
+// what the shared steps say about the feature they run for
+struct RowTableWords { const char *begin, *needs, *launch, *inside, *holds; };
+constexpr RowTableWords kStatsWords = {"mkp_stats_begin", "region statistics need", "region stats", "regions", "region statistics hold"};
+constexpr RowTableWords kLocWords = {"mkp_localize_begin", "localize needs", "localize", "windows", "localize holds"};
+// the five columns the reducers read, on the device; info = 0 '+', 1 '-', 2 '.' in its low bits
+struct RowCols { const uint32_t *pos, *info, *code, *n_valid, *n_mod; uint64_t n; };
+
+void rt_need_open(const mkp_ctx::RowTable& T, const RowTableWords& W) { if (!T.open) throw Error(MKP_E_INVALID, std::string(W.begin) + " first"); }
+
+// a new session: tids = the contigs of the regions in device order (grouped by contig; < 0 = on none)
+void rt_group_by_tid(mkp_ctx::RowTable& T, const std::vector<int32_t>& tids) {
+  T.tid_range.clear(); T.tids_with_rows.clear(); T.most_per_tid = 0;
+  for (uint32_t k = 0; k < tids.size(); k++) {
+    if (tids[k] < 0) continue;
+    auto it = T.tid_range.find(tids[k]);
+    if (it == T.tid_range.end()) T.tid_range[tids[k]] = {k, k + 1}; else it->second.second = k + 1;
+  }
+  for (auto& kv : T.tid_range) T.most_per_tid = std::max(T.most_per_tid, kv.second.second - kv.second.first);
+}
+
+// the rows the last shard run left in HBM
+RowCols rt_resident_rows(mkp_ctx* c, const mkp_ctx::RowTable& T, const RowTableWords& W) {
+  rt_need_open(T, W);
+  if (!c->partition_tags.empty()) throw Error(MKP_E_INVALID, std::string(W.needs)
+      + " the rows in genome order: with partition tags set they come grouped by key");
+  if (!c->resident || c->resident_hemi || c->hemi) throw Error(MKP_E_INVALID,
+      "no pileup rows are resident: call mkp_shard_run first (pileup-hemi rows are pattern counts, not bedMethyl rows)");
+  hip_check(hipSetDevice(c->device), "hipSetDevice");
+  const MkpRowsDev& r = c->rows_dst;
+  return {r.pos, r.info, r.code, r.n_valid, r.n_mod, c->stats.n_rows};
+}
+
+// the caller's rows, checked and uploaded into the session's own buffer (five columns, each padded to 64 rows)
+RowCols rt_upload_rows(mkp_ctx* c, mkp_ctx::RowTable& T, const RowTableWords& W, const mkp_rows* rows) {
+  rt_need_open(T, W);
+  const uint64_t n = rows->n_rows;
+  if (n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
+  if (n && (!rows->pos || !rows->strand || !rows->code_repr || !rows->n_valid || !rows->n_mod)) throw Error(MKP_E_INVALID,
+      "pos, strand, code_repr, n_valid and n_mod are needed");
+  std::vector<uint32_t> info(n);
+  for (uint64_t i = 0; i < n; i++) {
+    if (i && rows->pos[i] < rows->pos[i - 1]) throw Error(MKP_E_INVALID, "rows must be ascending in pos (row " + std::to_string(i) + ")");
+    const uint8_t s = rows->strand[i];
+    if (s != '+' && s != '-' && s != '.') throw Error(MKP_E_INVALID, "strand must be '+', '-' or '.' (row " + std::to_string(i) + ")");
+    if (!rows->code_repr[i]) throw Error(MKP_E_INVALID, "0 is not a mod code (row " + std::to_string(i) + ")");
+    info[i] = s == '+' ? 0u : s == '-' ? 1u : 2u;
+  }
+  hip_check(hipSetDevice(c->device), "hipSetDevice");
+  hip_check(hipStreamSynchronize(c->stream), "sync");   // the previous call's kernels read the upload buffer
+  const size_t col = ((size_t)n + 63) & ~(size_t)63;
+  T.d_rows.ensure(std::max<size_t>(col, 64) * 20);
+  uint32_t* d = T.d_rows.as<uint32_t>();
+  const uint32_t* src[5] = {rows->pos, info.data(), rows->code_repr, rows->n_valid, rows->n_mod};
+  for (int k = 0; k < 5; k++) h2d_copy(d + (size_t)k * col, src[k], (size_t)n * 4);
+  return {d, d + col, d + 2 * col, d + 3 * col, d + 4 * col, n};
+}
+
+// one piece of contig `tid`: launch(first, n, ev) runs the feature's kernels over its regions [first, first + n) of d_regions
+template <class Launch> void rt_launch(mkp_ctx* c, mkp_ctx::RowTable& T, const RowTableWords& W, int32_t tid, uint64_t n_rows, Launch launch) {
+  if (n_rows > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one piece");
+  if (n_rows) T.tids_with_rows.insert(tid);
+  auto it = T.tid_range.find(tid);
+  if (!n_rows || it == T.tid_range.end()) return;
+  hip_check(launch(it->second.first, it->second.second - it->second.first, T.timing ? T.ev : nullptr), (std::string(W.launch) + " launch").c_str());
+  if (T.timing) {
+    hip_check(hipEventSynchronize(T.ev[2]), (std::string(W.launch) + " sync").c_str());
+    float a = 0, b = 0; hip_check(hipEventElapsedTime(&a, T.ev[0], T.ev[1]), "event"); hip_check(hipEventElapsedTime(&b, T.ev[1], T.ev[2]), "event");
+    T.kernel_ms[0] += a; T.kernel_ms[1] += b;
+  }
+}
+
+int rt_timing(mkp_ctx* c, mkp_ctx::RowTable& T, int on, double ms_out[2]) {
+  return guarded(c, [&]() {
+    if (ms_out) { ms_out[0] = T.kernel_ms[0]; ms_out[1] = T.kernel_ms[1]; }
+    if (on) for (auto& e : T.ev) if (!e) hip_check(hipEventCreate(&e), "hipEventCreate");
+    T.timing = on != 0; if (on) T.kernel_ms[0] = T.kernel_ms[1] = 0;
+  });
+}
+
+// misc = d_misc as read back: the slots' codes, then the error word
+void rt_check_codes(const uint32_t* misc, const RowTableWords& W) {
+  if (misc[MKP_STATS_MAX_CODES] & MKP_STATS_ERR_CODES) throw Error(MKP_E_UNSUPPORTED, std::string("the rows inside the ") + W.inside
+      + " carry more than " + std::to_string(MKP_STATS_MAX_CODES) + " distinct mod codes: " + W.holds + " at most that many per run");
+}
+// the output columns (code, slot) for the slots in `mask`, by code
+std::vector<std::pair<uint32_t, uint32_t>> rt_columns(const uint32_t* misc, uint32_t mask) {
+  std::vector<std::pair<uint32_t, uint32_t>> cols;
+  for (uint32_t s = 0; s < MKP_STATS_MAX_CODES; s++) if ((mask >> s) & 1u) cols.push_back({misc[s], s});
+  std::sort(cols.begin(), cols.end());
+  return cols;
+}
+}  // namespace
+
 // ---- region statistics (`modkit stats`, include/mkpileup.h): the table stays in HBM between mkp_stats_begin and mkp_stats_get
 extern "C" hipError_t mkp_launch_region_stats(hipStream_t, const uint32_t* /*pos*/, const uint32_t* /*info*/, const uint32_t* /*code*/,
     const uint32_t* /*n_valid*/, const uint32_t* /*n_mod*/, uint32_t /*rows*/, const MkpStatsRegion*, uint32_t, uint32_t* /*first row*/,
@@ -1902,38 +1998,21 @@ extern "C" hipError_t mkp_launch_region_stats(hipStream_t, const uint32_t* /*pos
 namespace {
 // d_misc: 16 slot codes, the error word, a pad word, the chunk total (u64)
 constexpr size_t kStatsMiscBytes = 4 * MKP_STATS_MAX_CODES + 16;
-void stats_launch(mkp_ctx* c, int32_t tid, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
-    const uint32_t* n_mod, uint64_t n_rows) {
+void stats_launch(mkp_ctx* c, int32_t tid, const RowCols& r) {
   mkp_ctx::RegionStats& R = c->rstats;
-  if (n_rows > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one piece");
-  if (n_rows) R.tids_with_rows.insert(tid);
-  auto it = R.tid_range.find(tid);
-  if (!n_rows || it == R.tid_range.end()) return;
-  const uint32_t first = it->second.first, n = it->second.second - first;
-  uint32_t* misc = R.d_misc.as<uint32_t>();
-  hip_check(mkp_launch_region_stats(c->stream, pos, info, code, n_valid, n_mod, (uint32_t)n_rows, R.d_regions.as<MkpStatsRegion>() + first, n,
-      R.d_lo.as<uint32_t>(), R.d_hi.as<uint32_t>(), R.d_cnt.as<uint32_t>(), R.d_off.as<unsigned long long>(),
-      reinterpret_cast<unsigned long long*>(misc + MKP_STATS_MAX_CODES + 2), R.d_out.as<unsigned long long>(), R.d_seen.as<uint32_t>(), misc,
-      misc + MKP_STATS_MAX_CODES, (unsigned long long)R.min_cov, R.fixed ? 1u : 0u, R.timing ? R.ev : nullptr), "region stats launch");
-  if (R.timing) {
-    hip_check(hipEventSynchronize(R.ev[2]), "region stats sync");
-    float a = 0, b = 0; hip_check(hipEventElapsedTime(&a, R.ev[0], R.ev[1]), "event"); hip_check(hipEventElapsedTime(&b, R.ev[1], R.ev[2]), "event");
-    R.kernel_ms[0] += a; R.kernel_ms[1] += b;
-  }
+  rt_launch(c, R, kStatsWords, tid, r.n, [&](uint32_t first, uint32_t n, hipEvent_t* ev) {
+    uint32_t* misc = R.d_misc.as<uint32_t>();
+    return mkp_launch_region_stats(c->stream, r.pos, r.info, r.code, r.n_valid, r.n_mod, (uint32_t)r.n, R.d_regions.as<MkpStatsRegion>() + first, n,
+        R.d_lo.as<uint32_t>(), R.d_hi.as<uint32_t>(), R.d_cnt.as<uint32_t>(), R.d_off.as<unsigned long long>(),
+        reinterpret_cast<unsigned long long*>(misc + MKP_STATS_MAX_CODES + 2), R.d_out.as<unsigned long long>(), R.d_seen.as<uint32_t>(), misc,
+        misc + MKP_STATS_MAX_CODES, (unsigned long long)R.min_cov, R.fixed ? 1u : 0u, ev);
+  });
 }
 }  // namespace
 
 extern "C" {
 
-int mkp_internal_stats_timing(mkp_ctx* c, int on, double ms_out[2]) {
-  if (!c) return MKP_E_INVALID;
-  return guarded(c, [&]() {
-    mkp_ctx::RegionStats& R = c->rstats;
-    if (ms_out) { ms_out[0] = R.kernel_ms[0]; ms_out[1] = R.kernel_ms[1]; }
-    if (on) for (auto& e : R.ev) if (!e) hip_check(hipEventCreate(&e), "hipEventCreate");
-    R.timing = on != 0; if (on) R.kernel_ms[0] = R.kernel_ms[1] = 0;
-  });
-}
+int mkp_internal_stats_timing(mkp_ctx* c, int on, double ms_out[2]) { return c ? rt_timing(c, c->rstats, on, ms_out) : MKP_E_INVALID; }
 int mkp_internal_skip_row_fetch(mkp_ctx* c, int on) { if (!c) return MKP_E_INVALID; c->skip_row_fetch = on != 0; return MKP_OK; }
 
 int mkp_stats_begin(mkp_ctx* c, const mkp_region* regions, uint32_t n, const uint32_t* codes, uint32_t n_codes, uint64_t min_coverage) {
@@ -1952,17 +2031,13 @@ int mkp_stats_begin(mkp_ctx* c, const mkp_region* regions, uint32_t n, const uin
     if (R.fixed_codes.size() > MKP_STATS_MAX_CODES) throw Error(MKP_E_UNSUPPORTED, "region statistics hold at most "
         + std::to_string(MKP_STATS_MAX_CODES) + " distinct mod codes per run");
     R.fixed = n_codes != 0; R.min_cov = min_coverage; R.n_regions = n;
-    R.region_tid.resize(n); R.tid_range.clear(); R.tids_with_rows.clear(); R.most_per_tid = 0;
+    R.region_tid.resize(n);
     // the regions grouped by contig, caller order inside a contig; `out` = the caller's index
     std::vector<uint32_t> order(n); for (uint32_t i = 0; i < n; i++) { order[i] = i; R.region_tid[i] = regions[i].tid; }
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return regions[a].tid < regions[b].tid; });
-    std::vector<MkpStatsRegion> dev(n);
-    for (uint32_t k = 0; k < n; k++) { const mkp_region& g = regions[order[k]]; dev[k] = {g.start, g.end, g.strand_rule, order[k]};
-      if (g.tid < 0) continue;
-      auto it = R.tid_range.find(g.tid);
-      if (it == R.tid_range.end()) R.tid_range[g.tid] = {k, k + 1}; else it->second.second = k + 1;
-    }
-    for (auto& kv : R.tid_range) R.most_per_tid = std::max(R.most_per_tid, kv.second.second - kv.second.first);
+    std::vector<MkpStatsRegion> dev(n); std::vector<int32_t> dev_tid(n);
+    for (uint32_t k = 0; k < n; k++) { const mkp_region& g = regions[order[k]]; dev[k] = {g.start, g.end, g.strand_rule, order[k]}; dev_tid[k] = g.tid; }
+    rt_group_by_tid(R, dev_tid);
     hip_check(hipSetDevice(c->device), "hipSetDevice");
     hip_check(hipStreamSynchronize(c->stream), "sync");   // (a previous session's kernels)
     const size_t n1 = std::max<size_t>(n, 1), m1 = std::max<size_t>(R.most_per_tid, 1);
@@ -1980,56 +2055,23 @@ int mkp_stats_begin(mkp_ctx* c, const mkp_region* regions, uint32_t n, const uin
 
 int mkp_stats_add_resident(mkp_ctx* c) {
   if (!c) return MKP_E_INVALID;
-  return guarded(c, [&]() {
-    if (!c->rstats.open) throw Error(MKP_E_INVALID, "mkp_stats_begin first");
-    if (!c->partition_tags.empty()) throw Error(MKP_E_INVALID,
-        "region statistics need the rows in genome order: with partition tags set they come grouped by key");
-    if (!c->resident || c->resident_hemi || c->hemi) throw Error(MKP_E_INVALID,
-        "no pileup rows are resident: call mkp_shard_run first (pileup-hemi rows are pattern counts, not bedMethyl rows)");
-    hip_check(hipSetDevice(c->device), "hipSetDevice");
-    const MkpRowsDev& r = c->rows_dst;
-    stats_launch(c, c->shard.tid, r.pos, r.info, r.code, r.n_valid, r.n_mod, c->stats.n_rows);
-  });
+  return guarded(c, [&]() { stats_launch(c, c->shard.tid, rt_resident_rows(c, c->rstats, kStatsWords)); });
 }
 
 int mkp_stats_add_rows(mkp_ctx* c, int32_t tid, const mkp_rows* rows) {
   if (!c || !rows) return MKP_E_INVALID;
-  return guarded(c, [&]() {
-    mkp_ctx::RegionStats& R = c->rstats;
-    if (!R.open) throw Error(MKP_E_INVALID, "mkp_stats_begin first");
-    const uint64_t n = rows->n_rows;
-    if (n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
-    if (n && (!rows->pos || !rows->strand || !rows->code_repr || !rows->n_valid || !rows->n_mod)) throw Error(MKP_E_INVALID,
-        "pos, strand, code_repr, n_valid and n_mod are needed");
-    std::vector<uint32_t> info(n);
-    for (uint64_t i = 0; i < n; i++) {
-      if (i && rows->pos[i] < rows->pos[i - 1]) throw Error(MKP_E_INVALID, "rows must be ascending in pos (row " + std::to_string(i) + ")");
-      const uint8_t s = rows->strand[i];
-      if (s != '+' && s != '-' && s != '.') throw Error(MKP_E_INVALID, "strand must be '+', '-' or '.' (row " + std::to_string(i) + ")");
-      if (!rows->code_repr[i]) throw Error(MKP_E_INVALID, "0 is not a mod code (row " + std::to_string(i) + ")");
-      info[i] = s == '+' ? 0u : s == '-' ? 1u : 2u;
-    }
-    hip_check(hipSetDevice(c->device), "hipSetDevice");
-    hip_check(hipStreamSynchronize(c->stream), "sync");   // the previous call's kernels read the upload buffer
-    const size_t col = ((size_t)n + 63) & ~(size_t)63;
-    R.d_rows.ensure(std::max<size_t>(col, 64) * 20);
-    uint32_t* d = R.d_rows.as<uint32_t>();
-    const uint32_t* src[5] = {rows->pos, info.data(), rows->code_repr, rows->n_valid, rows->n_mod};
-    for (int k = 0; k < 5; k++) h2d_copy(d + (size_t)k * col, src[k], (size_t)n * 4);
-    stats_launch(c, tid, d, d + col, d + 2 * col, d + 3 * col, d + 4 * col, n);
-  });
+  return guarded(c, [&]() { stats_launch(c, tid, rt_upload_rows(c, c->rstats, kStatsWords, rows)); });
 }
 
 int mkp_stats_get(mkp_ctx* c, mkp_stats_out* out) {
   if (!c || !out) return MKP_E_INVALID;
   return guarded(c, [&]() {
     mkp_ctx::RegionStats& R = c->rstats;
-    if (!R.open) throw Error(MKP_E_INVALID, "mkp_stats_begin first");
+    rt_need_open(R, kStatsWords);
     hip_check(hipSetDevice(c->device), "hipSetDevice");
     uint32_t misc[kStatsMiscBytes / 4];
     d2h_copy(misc, R.d_misc.p, sizeof(misc), c->stream);
-    if (misc[MKP_STATS_MAX_CODES] & MKP_STATS_ERR_CODES) throw Error(MKP_E_UNSUPPORTED, "the rows inside the regions carry more than "
-        + std::to_string(MKP_STATS_MAX_CODES) + " distinct mod codes: region statistics hold at most that many per run");
+    rt_check_codes(misc, kStatsWords);
     const uint32_t n = R.n_regions;
     std::vector<uint64_t> tab((size_t)n * 2 * MKP_STATS_MAX_CODES); std::vector<uint32_t> seen(n);
     d2h_copy(tab.data(), R.d_out.p, tab.size() * 8, c->stream); d2h_copy(seen.data(), R.d_seen.p, (size_t)n * 4, c->stream);
@@ -2037,8 +2079,7 @@ int mkp_stats_get(mkp_ctx* c, mkp_stats_out* out) {
     std::vector<std::pair<uint32_t, uint32_t>> cols;   // code, slot
     if (R.fixed) for (uint32_t k = 0; k < R.fixed_codes.size(); k++) cols.push_back({R.fixed_codes[k], k});
     else { uint32_t any = 0; for (uint32_t m : seen) any |= m;
-      for (uint32_t s = 0; s < MKP_STATS_MAX_CODES; s++) if ((any >> s) & 1u) cols.push_back({misc[s], s});
-      std::sort(cols.begin(), cols.end()); }
+      cols = rt_columns(misc, any); }
     const size_t nc = cols.size();
     R.h_codes.resize(nc); R.h_mod.assign((size_t)n * nc, 0); R.h_valid.assign((size_t)n * nc, 0); R.h_has.resize(n);
     for (size_t k = 0; k < nc; k++) R.h_codes[k] = cols[k].first;
@@ -2064,37 +2105,19 @@ namespace {
 // d_misc: 16 slot codes, the error word, a pad word
 constexpr size_t kLocMiscBytes = 4 * MKP_STATS_MAX_CODES + 8;
 size_t loc_table_cells(uint32_t window) { return (size_t)MKP_STATS_MAX_CODES * (2 * (size_t)window + 1) * 3; }
-void localize_launch(mkp_ctx* c, int32_t tid, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
-    const uint32_t* n_mod, uint64_t n_rows) {
+void localize_launch(mkp_ctx* c, int32_t tid, const RowCols& r) {
   mkp_ctx::Localize& L = c->loc;
-  if (n_rows > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one piece");
-  if (n_rows) L.tids_with_rows.insert(tid);
-  auto it = L.tid_range.find(tid);
-  if (!n_rows || it == L.tid_range.end()) return;
-  const uint32_t first = it->second.first, n = it->second.second - first;
-  uint32_t* misc = L.d_misc.as<uint32_t>();
-  hip_check(mkp_launch_localize(c->stream, pos, info, code, n_valid, n_mod, (uint32_t)n_rows, L.d_regions.as<MkpLocRegion>() + first, n,
-      L.d_lo.as<uint32_t>(), L.d_hi.as<uint32_t>(), L.window, L.stranded, L.d_tab.as<unsigned long long>(), misc, misc + MKP_STATS_MAX_CODES,
-      L.timing ? L.ev : nullptr), "localize launch");
-  if (L.timing) {
-    hip_check(hipEventSynchronize(L.ev[2]), "localize sync");
-    float a = 0, b = 0; hip_check(hipEventElapsedTime(&a, L.ev[0], L.ev[1]), "event"); hip_check(hipEventElapsedTime(&b, L.ev[1], L.ev[2]), "event");
-    L.kernel_ms[0] += a; L.kernel_ms[1] += b;
-  }
+  rt_launch(c, L, kLocWords, tid, r.n, [&](uint32_t first, uint32_t n, hipEvent_t* ev) {
+    uint32_t* misc = L.d_misc.as<uint32_t>();
+    return mkp_launch_localize(c->stream, r.pos, r.info, r.code, r.n_valid, r.n_mod, (uint32_t)r.n, L.d_regions.as<MkpLocRegion>() + first, n,
+        L.d_lo.as<uint32_t>(), L.d_hi.as<uint32_t>(), L.window, L.stranded, L.d_tab.as<unsigned long long>(), misc, misc + MKP_STATS_MAX_CODES, ev);
+  });
 }
 }  // namespace
 
 extern "C" {
 
-int mkp_internal_localize_timing(mkp_ctx* c, int on, double ms_out[2]) {
-  if (!c) return MKP_E_INVALID;
-  return guarded(c, [&]() {
-    mkp_ctx::Localize& L = c->loc;
-    if (ms_out) { ms_out[0] = L.kernel_ms[0]; ms_out[1] = L.kernel_ms[1]; }
-    if (on) for (auto& e : L.ev) if (!e) hip_check(hipEventCreate(&e), "hipEventCreate");
-    L.timing = on != 0; if (on) L.kernel_ms[0] = L.kernel_ms[1] = 0;
-  });
-}
+int mkp_internal_localize_timing(mkp_ctx* c, int on, double ms_out[2]) { return c ? rt_timing(c, c->loc, on, ms_out) : MKP_E_INVALID; }
 
 int mkp_localize_begin(mkp_ctx* c, const mkp_region* regions, uint32_t n, const uint64_t* contig_len_by_tid, uint32_t n_contigs, uint32_t window,
     int stranded, int stranded_features) {
@@ -2120,7 +2143,7 @@ int mkp_localize_begin(mkp_ctx* c, const mkp_region* regions, uint32_t n, const 
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return regions[a].tid < regions[b].tid; });
     const uint64_t w = window;
     std::vector<MkpLocRegion> dev(order.size());
-    L.kept_tid.resize(order.size()); L.tid_range.clear(); L.tids_with_rows.clear(); L.most_per_tid = 0;
+    L.kept_tid.resize(order.size());
     for (uint32_t k = 0; k < order.size(); k++) {
       const mkp_region& g = regions[order[k]];
       const uint64_t mp = ((uint64_t)g.start + (uint64_t)g.end) / 2;
@@ -2132,10 +2155,8 @@ int mkp_localize_begin(mkp_ctx* c, const mkp_region* regions, uint32_t n, const 
       const uint32_t fetch = stranded_features ? (uint32_t)stranded_features : (uint32_t)g.strand_rule;
       dev[k] = {(uint32_t)ws, (uint32_t)we, (uint32_t)anchor, fetch | ((uint32_t)g.strand_rule << 8)};
       L.kept_tid[k] = g.tid;
-      auto it = L.tid_range.find(g.tid);
-      if (it == L.tid_range.end()) L.tid_range[g.tid] = {k, k + 1}; else it->second.second = k + 1;
     }
-    for (auto& kv : L.tid_range) L.most_per_tid = std::max(L.most_per_tid, kv.second.second - kv.second.first);
+    rt_group_by_tid(L, L.kept_tid);
     L.window = window; L.stranded = (uint32_t)stranded;
     hip_check(hipSetDevice(c->device), "hipSetDevice");
     hip_check(hipStreamSynchronize(c->stream), "sync");   // (a previous session's kernels)
@@ -2152,56 +2173,23 @@ int mkp_localize_begin(mkp_ctx* c, const mkp_region* regions, uint32_t n, const 
 
 int mkp_localize_add_resident(mkp_ctx* c) {
   if (!c) return MKP_E_INVALID;
-  return guarded(c, [&]() {
-    if (!c->loc.open) throw Error(MKP_E_INVALID, "mkp_localize_begin first");
-    if (!c->partition_tags.empty()) throw Error(MKP_E_INVALID,
-        "localize needs the rows in genome order: with partition tags set they come grouped by key");
-    if (!c->resident || c->resident_hemi || c->hemi) throw Error(MKP_E_INVALID,
-        "no pileup rows are resident: call mkp_shard_run first (pileup-hemi rows are pattern counts, not bedMethyl rows)");
-    hip_check(hipSetDevice(c->device), "hipSetDevice");
-    const MkpRowsDev& r = c->rows_dst;
-    localize_launch(c, c->shard.tid, r.pos, r.info, r.code, r.n_valid, r.n_mod, c->stats.n_rows);
-  });
+  return guarded(c, [&]() { localize_launch(c, c->shard.tid, rt_resident_rows(c, c->loc, kLocWords)); });
 }
 
 int mkp_localize_add_rows(mkp_ctx* c, int32_t tid, const mkp_rows* rows) {
   if (!c || !rows) return MKP_E_INVALID;
-  return guarded(c, [&]() {
-    mkp_ctx::Localize& L = c->loc;
-    if (!L.open) throw Error(MKP_E_INVALID, "mkp_localize_begin first");
-    const uint64_t n = rows->n_rows;
-    if (n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
-    if (n && (!rows->pos || !rows->strand || !rows->code_repr || !rows->n_valid || !rows->n_mod)) throw Error(MKP_E_INVALID,
-        "pos, strand, code_repr, n_valid and n_mod are needed");
-    std::vector<uint32_t> info(n);
-    for (uint64_t i = 0; i < n; i++) {
-      if (i && rows->pos[i] < rows->pos[i - 1]) throw Error(MKP_E_INVALID, "rows must be ascending in pos (row " + std::to_string(i) + ")");
-      const uint8_t s = rows->strand[i];
-      if (s != '+' && s != '-' && s != '.') throw Error(MKP_E_INVALID, "strand must be '+', '-' or '.' (row " + std::to_string(i) + ")");
-      if (!rows->code_repr[i]) throw Error(MKP_E_INVALID, "0 is not a mod code (row " + std::to_string(i) + ")");
-      info[i] = s == '+' ? 0u : s == '-' ? 1u : 2u;
-    }
-    hip_check(hipSetDevice(c->device), "hipSetDevice");
-    hip_check(hipStreamSynchronize(c->stream), "sync");   // the previous call's kernels read the upload buffer
-    const size_t col = ((size_t)n + 63) & ~(size_t)63;
-    L.d_rows.ensure(std::max<size_t>(col, 64) * 20);
-    uint32_t* d = L.d_rows.as<uint32_t>();
-    const uint32_t* src[5] = {rows->pos, info.data(), rows->code_repr, rows->n_valid, rows->n_mod};
-    for (int k = 0; k < 5; k++) h2d_copy(d + (size_t)k * col, src[k], (size_t)n * 4);
-    localize_launch(c, tid, d, d + col, d + 2 * col, d + 3 * col, d + 4 * col, n);
-  });
+  return guarded(c, [&]() { localize_launch(c, tid, rt_upload_rows(c, c->loc, kLocWords, rows)); });
 }
 
 int mkp_localize_get(mkp_ctx* c, mkp_localize_out* out) {
   if (!c || !out) return MKP_E_INVALID;
   return guarded(c, [&]() {
     mkp_ctx::Localize& L = c->loc;
-    if (!L.open) throw Error(MKP_E_INVALID, "mkp_localize_begin first");
+    rt_need_open(L, kLocWords);
     hip_check(hipSetDevice(c->device), "hipSetDevice");
     uint32_t misc[kLocMiscBytes / 4];
     d2h_copy(misc, L.d_misc.p, sizeof(misc), c->stream);
-    if (misc[MKP_STATS_MAX_CODES] & MKP_STATS_ERR_CODES) throw Error(MKP_E_UNSUPPORTED, "the rows inside the windows carry more than "
-        + std::to_string(MKP_STATS_MAX_CODES) + " distinct mod codes: localize holds at most that many per run");
+    rt_check_codes(misc, kLocWords);
     bool any_region = false;
     for (int32_t tid : L.kept_tid) if (L.tids_with_rows.count(tid)) { any_region = true; break; }
     if (!any_region) throw Error(MKP_E_INVALID, "failed to find any valid regions: no row was added on a contig that has one");
@@ -2209,13 +2197,13 @@ int mkp_localize_get(mkp_ctx* c, mkp_localize_out* out) {
     std::vector<uint64_t> tab(loc_table_cells(L.window));
     d2h_copy(tab.data(), L.d_tab.p, tab.size() * 8, c->stream);
     // columns: the slots with a counted row in some cell, by code
-    std::vector<std::pair<uint32_t, uint32_t>> cols;   // code, slot
+    uint32_t counted = 0;
     for (uint32_t s = 0; s < MKP_STATS_MAX_CODES; s++) {
       if (!misc[s]) continue;
       bool any = false; for (size_t o = 0; o < n_off && !any; o++) any = tab[((size_t)s * n_off + o) * 3 + 2] != 0;
-      if (any) cols.push_back({misc[s], s});
+      if (any) counted |= 1u << s;
     }
-    std::sort(cols.begin(), cols.end());
+    const std::vector<std::pair<uint32_t, uint32_t>> cols = rt_columns(misc, counted);   // code, slot
     const size_t nc = cols.size();
     L.h_codes.resize(nc); L.h_mod.resize(nc * n_off); L.h_valid.resize(nc * n_off); L.h_rows.resize(nc * n_off);
     for (size_t k = 0; k < nc; k++) { L.h_codes[k] = cols[k].first;

@@ -185,28 +185,30 @@ struct mkp_ctx {
   // the read-independent part of a focus shard's plan (slot bitmap, its running popcount, the slot positions, their uploads), made ahead
   // of the reads by mkp_internal_shard_preplan while the device ingest of the same shard is still running
   struct WindowPlan { bool valid = false; std::vector<uint32_t> slotbm, wpfx, slot_pos; } wplan;
-  // region statistics (mkp_stats_begin .. mkp_stats_get, mkp_stats.hip): the run-long table out[region][slot] = {n_mod, n_valid} (u64), the
-  // per-region mask of slots with a counted row and the slots' codes stay in HBM between the calls; regions are uploaded once, grouped by contig
-  struct RegionStats {
-    bool open = false, fixed = false, timing = false; uint32_t n_regions = 0, most_per_tid = 0; uint64_t min_cov = 1;
+  // What the sessions that reduce rows already in HBM share (region statistics, localize): the regions uploaded once and grouped by contig, the
+  // slots' codes and error word in HBM between the calls, the per-call row ranges, the upload buffer of *_add_rows and the kernel timing
+  struct RowTable {
+    bool open = false, timing = false; uint32_t most_per_tid = 0;
+    std::map<int32_t, std::pair<uint32_t, uint32_t>> tid_range;         // contig -> [first, last) of d_regions
+    std::set<int32_t> tids_with_rows;
+    mkp::DevBuf d_regions, d_misc /* codes[16], error word, pad (stats: then the chunk total, u64) */, d_lo, d_hi, d_rows;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; double kernel_ms[2] = {0, 0};   // timing: bounds (+ scan), reduce (summed over the calls)
+  };
+  // region statistics (mkp_stats_begin .. mkp_stats_get, mkp_stats.hip): the run-long table out[region][slot] = {n_mod, n_valid} (u64) and the
+  // per-region mask of slots with a counted row
+  struct RegionStats : RowTable {
+    bool fixed = false; uint32_t n_regions = 0; uint64_t min_cov = 1;
     std::vector<uint32_t> fixed_codes;                                  // sorted, distinct
     std::vector<int32_t> region_tid;                                    // caller order
-    std::map<int32_t, std::pair<uint32_t, uint32_t>> tid_range;         // contig -> [first, last) of d_regions
-    std::set<int32_t> tids_with_rows;
-    mkp::DevBuf d_regions, d_out, d_seen, d_misc /* codes[16], error word, pad, chunk total (u64) */, d_lo, d_hi, d_cnt, d_off, d_rows;
+    mkp::DevBuf d_out, d_seen, d_cnt, d_off;
     std::vector<uint32_t> h_codes; std::vector<uint64_t> h_mod, h_valid; std::vector<uint8_t> h_has;   // mkp_stats_get
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; double kernel_ms[2] = {0, 0};   // timing: bounds + scan, reduce (summed over the calls)
   } rstats;
-  // localize (mkp_localize_begin .. mkp_localize_get, mkp_localize.hip): the run-long table tab[slot][2 window + 1]{n_mod, n_valid, n_rows}
-  // (u64) and the slots' codes stay in HBM between the calls; the windows are uploaded once, grouped by contig
-  struct Localize {
-    bool open = false, timing = false; uint32_t window = 0, stranded = 0, most_per_tid = 0;
+  // localize (mkp_localize_begin .. mkp_localize_get, mkp_localize.hip): the run-long table tab[slot][2 window + 1]{n_mod, n_valid, n_rows} (u64)
+  struct Localize : RowTable {
+    uint32_t window = 0, stranded = 0;
     std::vector<int32_t> kept_tid;                                      // the contigs of the regions that passed the sizes filter
-    std::map<int32_t, std::pair<uint32_t, uint32_t>> tid_range;         // contig -> [first, last) of d_regions
-    std::set<int32_t> tids_with_rows;
-    mkp::DevBuf d_regions, d_tab, d_misc /* codes[16], error word, pad */, d_lo, d_hi, d_rows;
+    mkp::DevBuf d_tab;
     std::vector<uint32_t> h_codes; std::vector<uint64_t> h_mod, h_valid, h_rows;   // mkp_localize_get
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; double kernel_ms[2] = {0, 0};   // timing: bounds, reduce (summed over the calls)
   } loc;
   bool skip_row_fetch = false;   // `--region-stats-only`: mkp_shard_run leaves the rows in HBM (no column read-back, n_rows = 0 in its output)
   // device ingest of indexed BAMs (mkp_ingest_host.cpp): created on first use, lives with the context (staging + window buffers are reused)

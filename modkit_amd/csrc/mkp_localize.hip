@@ -15,38 +15,24 @@
 //                         exact in 64 bits at 12 bytes a cell.  At the end the workgroup adds its non-zero cells to the HBM table with
 //                         contiguous 64-bit atomics.
 // The table tab[slot][2 w + 1][3] lives for the whole run: pieces (shards) add into it, so a window across a seam counts each row once.
-// Code slots are claimed as in mkp_stats_reduce (the first counted row of a code, one lane per wave and code); a code whose slot is
-// beyond the LDS ones adds to HBM per row (rare, exact); a seventeenth code sets the error bit.
-#include "mkp_dev_common.hpp"
+// Code slots are claimed by resolve_slot of mkp_dev_codeslots.hpp, shared with mkp_stats.hip (the first counted row of a code, one lane per
+// wave and code); a code whose slot is beyond the LDS ones adds to HBM per row (rare, exact); a seventeenth code sets the error bit.
+#include "mkp_dev_codeslots.hpp"
 
 namespace {
 
 constexpr uint32_t kTile = MKP_LOC_TILE, kBatch = MKP_LOC_BATCH;
-constexpr int kSlots = MKP_STATS_MAX_CODES, kLocal = MKP_LOC_LOCAL;
+constexpr int kLocal = MKP_LOC_LOCAL;
 constexpr uint32_t kCells = (uint32_t)kLocal * kTile * 3u;
-
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* __restrict__ a, uint32_t n, uint32_t key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
 
 __global__ __launch_bounds__(256) void mkp_localize_bounds(const uint32_t* __restrict__ pos, uint32_t n_rows, const MkpLocRegion* __restrict__ regions,
     uint32_t n_regions, uint32_t* __restrict__ row_lo, uint32_t* __restrict__ row_hi) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_regions) return;
   const MkpLocRegion g = regions[r];
-  uint32_t lo = 0, hi = 0;
-  if (g.we > g.ws) { lo = lower_bound_u32(pos, n_rows, g.ws); hi = lower_bound_u32(pos, n_rows, g.we); }
+  uint32_t lo, hi;
+  row_range(pos, n_rows, g.ws, g.we, &lo, &hi);
   row_lo[r] = lo; row_hi[r] = hi;
-}
-
-// the slot whose code is c in the wave's copy of the table (entry s in lane s), or -1
-__device__ __forceinline__ int find_slot(uint32_t tab, uint32_t c) {
-  int slot = -1;
-#pragma unroll
-  for (int s = 0; s < kSlots; s++) { const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)tab, s); if (e == c) slot = s; }
-  return slot;
 }
 
 // StrandRule::overlaps (src/util.rs:310-318) on rules 1 '+', 2 '-', 3 both
@@ -62,8 +48,7 @@ __global__ __launch_bounds__(256) void mkp_localize_reduce(const uint32_t* __res
   const uint32_t t = threadIdx.x, n_off = 2u * window + 1u, o0 = blockIdx.x * kTile;   // the tile holds the offset indices [o0, o0 + kTile)
   const int lane = lane_id();
   for (uint32_t i = t; i < kCells; i += kBatch) cell[i] = 0u;
-  // the code table as this wave last saw it: entry s in lane s
-  uint32_t ctab = lane < kSlots ? __hip_atomic_load(&codes[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  uint32_t ctab = load_codes(codes, lane);   // the code table as this wave last saw it
   const uint32_t n_batches = (n_regions + kBatch - 1u) / kBatch;
   for (uint32_t batch = blockIdx.y; batch < n_batches; batch += gridDim.y) {
     __syncthreads();   // the cells are zero / the sweep before this one has read its batch
@@ -106,29 +91,7 @@ __global__ __launch_bounds__(256) void mkp_localize_reduce(const uint32_t* __res
         if (stranded) pass = pass && (overlaps(rl >> 8, row_rule) == (stranded == 1u));
         pass = pass && o < kTile && o0 + o < n_off;
       }
-      int slot = find_slot(ctab, c);
-      if (!pass) slot = -1;   // (c == 0 of an idle lane matches the free entries)
-      if (__ballot(pass && slot < 0)) {
-        // a code this wave has not met: look again (another wave has usually claimed it by now), then ONE lane per distinct code claims
-        ctab = lane < kSlots ? __hip_atomic_load(&codes[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        slot = find_slot(ctab, c);
-        if (!pass) slot = -1;
-        bool missing = pass && slot < 0;
-        unsigned long long miss = __ballot(missing);
-        while (miss) {
-          const int leader = __ffsll((long long)miss) - 1;
-          const uint32_t c0 = (uint32_t)__shfl((int)c, leader, 64);
-          int s0 = -1;
-          if (lane == leader) {
-            for (int s = 0; s < kSlots && s0 < 0; s++) { const uint32_t old = atomicCAS(&codes[s], 0u, c0); if (old == 0u || old == c0) s0 = s; }
-            if (s0 < 0) atomicOr(err, MKP_STATS_ERR_CODES);
-          }
-          s0 = __shfl(s0, leader, 64);
-          if (missing && c == c0) { slot = s0; missing = false; }
-          miss = __ballot(missing);
-        }
-        ctab = lane < kSlots ? __hip_atomic_load(&codes[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-      }
+      const int slot = resolve_slot(ctab, codes, err, pass, c, true, lane);
       if (slot >= 0) {
         unsigned long long* hbm = tab + ((size_t)slot * n_off + o0 + o) * 3u;
         const uint32_t v[3] = {nm, nv, 1u};

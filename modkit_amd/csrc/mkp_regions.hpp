@@ -69,32 +69,55 @@ struct BedLineParser {
   }
 };
 
-template <class TidOf> mkp_region_set parse_regions_bed(const std::string& path, TidOf tid_of) {
+// The regions BED as the reference's two loaders read it: the same line loop under two sets of rules.
+//   stats (EntryStats::run): the parser is picked by the TAB-separated fields of the first line that does not start with '#'; a line that
+//     fails is fatal; start <= end is checked, and a quote in a name is refused (the table writer does not quote).
+//   localize (load_focus_regions up to its contig filters, src/localise/subcommand.rs:105-162): picked by the WHITESPACE-separated fields
+//     (split_whitespace: runs of any blank count once, leading ones not at all); a line that fails is counted, not fatal; there is no
+//     start <= end check, so start is held to 32 bits as well.
+template <class TidOf> mkp_region_set parse_bed_regions(const std::string& path, TidOf tid_of, bool localize, uint32_t* n_skipped) {
   std::ifstream f(path, std::ios::binary);
   if (!f) throw Error(MKP_E_IO, "failed to open regions BED " + path);
   std::vector<std::string> lines; std::string line;
   while (std::getline(f, line)) { if (!line.empty() && line.back() == '\r') line.pop_back(); lines.push_back(line); }   // BufRead::lines
   size_t first = 0; while (first < lines.size() && !lines[first].empty() && lines[first][0] == '#') first++;
   if (first >= lines.size()) throw Error(MKP_E_INVALID, "failed to inspect regions BED, no valid lines: " + path);
-  size_t fields = 1; for (char c : lines[first]) if (c == '\t') fields++;
+  size_t fields = 0;
+  if (localize) {
+    // char::is_whitespace on what a BED line can hold: blank, tab, LF, VT, FF, CR (and the Unicode blanks, which count as field text here)
+    auto white = [](char c) { return c == ' ' || (c >= '\t' && c <= '\r'); };
+    bool in = false; for (char c : lines[first]) { const bool wsp = white(c); if (!wsp && !in) fields++; in = !wsp; }
+  } else { fields = 1; for (char c : lines[first]) if (c == '\t') fields++; }
   const bool stranded = fields > 4;
-  mkp_region_set out;
+  mkp_region_set out; uint32_t skipped = 0;
   for (size_t k = 0; k < lines.size(); k++) {
     BedLineParser p(lines[k]); std::string chrom, name; uint64_t s = 0, e = 0; uint8_t rule = 3;
     bool ok = p.string(&chrom) && p.digits(&s) && p.digits(&e);
     bool has_name = false;
     if (ok) { has_name = p.name(&name); if (stranded) ok = p.score() && p.strand(&rule); }
-    if (!ok) throw Error(MKP_E_INVALID, std::string("failed to parse ") + (stranded ? "stranded (bed4+)" : "un-stranded (bed3/4)") + " line "
-        + std::to_string(k + 1) + " of " + path + ": " + lines[k]);
-    if (s > e) throw Error(MKP_E_INVALID, "line " + std::to_string(k + 1) + " of " + path + ": start > end");
-    if (e > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "line " + std::to_string(k + 1) + " of " + path + ": coordinate beyond 2^32 - 1");
-    for (const std::string* t : {&chrom, &name}) if (t->find('"') != std::string::npos) throw Error(MKP_E_UNSUPPORTED, "line "
-        + std::to_string(k + 1) + " of " + path + ": a quote in the contig or region name needs csv quoting, which is not written");
+    auto where = [&]() { return "line " + std::to_string(k + 1) + " of " + path; };
+    if (!ok) {
+      if (localize) { skipped++; continue; }
+      throw Error(MKP_E_INVALID, std::string("failed to parse ") + (stranded ? "stranded (bed4+)" : "un-stranded (bed3/4)") + " " + where() + ": "
+          + lines[k]);
+    }
+    if (!localize && s > e) throw Error(MKP_E_INVALID, where() + ": start > end");
+    if (e > 0xffffffffull || (localize && s > 0xffffffffull)) throw Error(MKP_E_UNSUPPORTED, where() + ": coordinate beyond 2^32 - 1");
+    if (!localize) for (const std::string* t : {&chrom, &name}) if (t->find('"') != std::string::npos) throw Error(MKP_E_UNSUPPORTED, where()
+        + ": a quote in the contig or region name needs csv quoting, which is not written");
     mkp_region g; memset(&g, 0, sizeof(g)); g.tid = (int32_t)tid_of(chrom); g.start = (uint32_t)s; g.end = (uint32_t)e; g.strand_rule = rule;
     out.regions.push_back(g); out.chrom.push_back(chrom); out.name.push_back(has_name ? name : ".");
   }
-  if (out.regions.empty()) throw Error(MKP_E_INVALID, "failed to load any regions from " + path);
+  if (out.regions.empty()) throw Error(MKP_E_INVALID, "failed to load any regions from " + path
+      + (localize ? ": " + std::to_string(skipped) + " lines failed to parse" : std::string()));
+  if (n_skipped) *n_skipped = skipped;
   return out;
+}
+template <class TidOf> mkp_region_set parse_regions_bed(const std::string& path, TidOf tid_of) {
+  return parse_bed_regions(path, tid_of, false, nullptr);
+}
+template <class TidOf> mkp_region_set parse_localize_regions_bed(const std::string& path, TidOf tid_of, uint32_t* n_skipped) {
+  return parse_bed_regions(path, tid_of, true, n_skipped);
 }
 
 inline std::string code_text(uint32_t code) { return (code & 0x80000000u) ? std::to_string(code & 0x7fffffffu) : std::string(1, (char)code); }
@@ -131,38 +154,6 @@ template <class F32Text> std::string stats_table_text(const mkp_region_set& set,
 }
 
 // ---- localize
-// load_focus_regions up to its contig filters (src/localise/subcommand.rs:105-162): the parser is picked by the WHITESPACE-separated
-// fields (split_whitespace: runs of any blank count once, leading ones not at all) of the first line that does not start with '#'; a line
-// that fails is counted, not fatal; there is no start <= end check.
-template <class TidOf> mkp_region_set parse_localize_regions_bed(const std::string& path, TidOf tid_of, uint32_t* n_skipped) {
-  std::ifstream f(path, std::ios::binary);
-  if (!f) throw Error(MKP_E_IO, "failed to open regions BED " + path);
-  std::vector<std::string> lines; std::string line;
-  while (std::getline(f, line)) { if (!line.empty() && line.back() == '\r') line.pop_back(); lines.push_back(line); }   // BufRead::lines
-  size_t first = 0; while (first < lines.size() && !lines[first].empty() && lines[first][0] == '#') first++;
-  if (first >= lines.size()) throw Error(MKP_E_INVALID, "failed to inspect regions BED, no valid lines: " + path);
-  // char::is_whitespace on what a BED line can hold: blank, tab, LF, VT, FF, CR (and the Unicode blanks, which count as field text here)
-  auto white = [](char c) { return c == ' ' || (c >= '\t' && c <= '\r'); };
-  size_t fields = 0; { bool in = false; for (char c : lines[first]) { const bool wsp = white(c); if (!wsp && !in) fields++; in = !wsp; } }
-  const bool stranded = fields > 4;
-  mkp_region_set out; uint32_t skipped = 0;
-  for (size_t k = 0; k < lines.size(); k++) {
-    BedLineParser p(lines[k]); std::string chrom, name; uint64_t s = 0, e = 0; uint8_t rule = 3;
-    bool ok = p.string(&chrom) && p.digits(&s) && p.digits(&e);
-    bool has_name = false;
-    if (ok) { has_name = p.name(&name); if (stranded) ok = p.score() && p.strand(&rule); }
-    if (!ok) { skipped++; continue; }
-    if (s > 0xffffffffull || e > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "line " + std::to_string(k + 1) + " of " + path
-        + ": coordinate beyond 2^32 - 1");
-    mkp_region g; memset(&g, 0, sizeof(g)); g.tid = (int32_t)tid_of(chrom); g.start = (uint32_t)s; g.end = (uint32_t)e; g.strand_rule = rule;
-    out.regions.push_back(g); out.chrom.push_back(chrom); out.name.push_back(has_name ? name : ".");
-  }
-  if (out.regions.empty()) throw Error(MKP_E_INVALID, "failed to load any regions from " + path + ": " + std::to_string(skipped)
-      + " lines failed to parse");
-  if (n_skipped) *n_skipped = skipped;
-  return out;
-}
-
 // read_sequence_lengths_file (src/util.rs:969-990): a contig name, blanks, a length; what follows is not looked at; any other line fails;
 // collected into an IndexMap: a later line for the same contig replaces the length and keeps the place
 inline mkp_genome_sizes parse_genome_sizes(const std::string& path) {

@@ -13,27 +13,21 @@
 // A whole-chromosome region is 660 items spread over the grid; thirty thousand 50-row regions are 7 500 workgroups' worth of waves.
 // The table out[region][slot] lives for the whole run: pieces (shards) add into it, so a region that straddles seams gets every row once.
 // Code slots: at most MKP_STATS_MAX_CODES per run.  With a fixed list the host uploads the table and other codes are not counted; without
-// one, the first counted row of a code claims a free entry with a compare-and-swap (order does not matter, the host sorts).
-#include "mkp_dev_common.hpp"
+// one, the first counted row of a code claims a free entry with a compare-and-swap (order does not matter, the host sorts): resolve_slot
+// of mkp_dev_codeslots.hpp, which also holds the two searches of the bounds kernel; both are shared with mkp_localize.hip.
+#include "mkp_dev_codeslots.hpp"
 
 namespace {
 
 constexpr uint32_t kChunk = MKP_STATS_CHUNK;
-constexpr int kSlots = MKP_STATS_MAX_CODES;
-
-__device__ __forceinline__ uint32_t lower_bound_u32(const uint32_t* __restrict__ a, uint32_t n, uint32_t key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (a[mid] < key) lo = mid + 1; else hi = mid; }
-  return lo;
-}
 
 __global__ __launch_bounds__(256) void mkp_stats_bounds(const uint32_t* __restrict__ pos, uint32_t n_rows, const MkpStatsRegion* __restrict__ regions,
     uint32_t n_regions, uint32_t* __restrict__ row_lo, uint32_t* __restrict__ row_hi, uint32_t* __restrict__ n_chunks) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n_regions) return;
   const MkpStatsRegion g = regions[r];
-  uint32_t lo = 0, hi = 0;
-  if (g.end > g.start) { lo = lower_bound_u32(pos, n_rows, g.start); hi = lower_bound_u32(pos, n_rows, g.end); }
+  uint32_t lo, hi;
+  row_range(pos, n_rows, g.start, g.end, &lo, &hi);
   row_lo[r] = lo; row_hi[r] = hi; n_chunks[r] = (hi - lo + kChunk - 1) / kChunk;
 }
 
@@ -58,14 +52,6 @@ __global__ __launch_bounds__(1024) void mkp_stats_scan(const uint32_t* __restric
   if (t == 1023u) { off[n_regions] = part[t]; *total = part[t]; }
 }
 
-// the slot whose code is c in the wave's copy of the table (entry s in lane s), or -1
-__device__ __forceinline__ int find_slot(uint32_t tab, uint32_t c) {
-  int slot = -1;
-#pragma unroll
-  for (int s = 0; s < kSlots; s++) { const uint32_t e = (uint32_t)__builtin_amdgcn_readlane((int)tab, s); if (e == c) slot = s; }
-  return slot;
-}
-
 __device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
@@ -82,8 +68,7 @@ __global__ __launch_bounds__(256) void mkp_stats_reduce(const uint32_t* __restri
     uint32_t* err, unsigned long long min_cov, uint32_t fixed_codes) {
   const int lane = lane_id();
   const unsigned long long n_waves = (unsigned long long)gridDim.x * (blockDim.x >> 6), total = *total_p;
-  // the code table as this wave last saw it: entry s in lane s
-  uint32_t tab = lane < kSlots ? __hip_atomic_load(&codes[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+  uint32_t tab = load_codes(codes, lane);   // the code table as this wave last saw it
   for (unsigned long long w = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < total; w += n_waves) {
     // the region of item w: the last one whose offset is <= w (regions without rows share their successor's offset and are never found)
     uint32_t a = 0, b = n_regions;   // off[a] <= w < off[b]
@@ -102,30 +87,7 @@ __global__ __launch_bounds__(256) void mkp_stats_reduce(const uint32_t* __restri
         c = code[i]; nv = n_valid[i]; nm = n_mod[i];
         pass = (g.rule == 3u || sidx == 2u || sidx + 1u == g.rule) && (unsigned long long)nv >= min_cov;
       }
-      int slot = find_slot(tab, c);
-      if (!pass) slot = -1;   // (c == 0 of an idle lane matches the free entries)
-      if (!fixed_codes && __ballot(pass && slot < 0)) {
-        // a code this wave has not met: look again (another wave has usually claimed it by now), then ONE lane per distinct code claims —
-        // every lane of every wave of a fresh launch meets an empty table, and their compare-and-swaps would all queue on one cache line
-        tab = lane < kSlots ? __hip_atomic_load(&codes[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-        slot = find_slot(tab, c);
-        if (!pass) slot = -1;
-        bool missing = pass && slot < 0;
-        unsigned long long miss = __ballot(missing);
-        while (miss) {
-          const int leader = __ffsll((long long)miss) - 1;
-          const uint32_t c0 = (uint32_t)__shfl((int)c, leader, 64);
-          int s0 = -1;
-          if (lane == leader) {
-            for (int s = 0; s < kSlots && s0 < 0; s++) { const uint32_t old = atomicCAS(&codes[s], 0u, c0); if (old == 0u || old == c0) s0 = s; }
-            if (s0 < 0) atomicOr(err, MKP_STATS_ERR_CODES);
-          }
-          s0 = __shfl(s0, leader, 64);
-          if (missing && c == c0) { slot = s0; missing = false; }
-          miss = __ballot(missing);
-        }
-        tab = lane < kSlots ? __hip_atomic_load(&codes[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-      }
+      const int slot = resolve_slot(tab, codes, err, pass, c, !fixed_codes, lane);
       if (slot >= 0) touched |= 1u << slot;
 #pragma unroll
       for (int s = 0; s < kSlots; s++) { const bool m = slot == s; am[s] += m ? nm : 0u; av[s] += m ? nv : 0u; }
