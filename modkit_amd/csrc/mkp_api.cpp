@@ -9,6 +9,7 @@
 
 #include "mkp_ctx.hpp"
 #include "mkp_ingest_host.hpp"
+#include "mkp_plan.hpp"
 
 using namespace mkp;
 
@@ -60,200 +61,10 @@ MkpRowsDev carve_rows(DevBuf& b, uint64_t cap) {
   return r;
 }
 
-// reads by decode kernel: [SPARSE one tag | SPARSE two tags | FAST one tag | FAST two tags | everything else].
-// FAST = one (strand, base) group, no code listed twice, at most two tags.  SPARSE = FAST with explicit ('?') tags only and,
-// for two tags, identical rank lists (`C+h?,d..;C+m?,d..` as basecallers write them): the calls are located per call, not per base.
-// With `duplex` (never for the threshold sampler): [.. | duplex one tag per group | duplex two]: reads whose layout has two groups on
-// different bases (`C+h?;C+m?;G-h?;G-m?`), every tag explicit and the tags of a group sharing one rank list; such a read is listed
-// twice (bit 31 = its second group), each listing decoded by a SPARSE wave, and mkp_merge_duplex interleaves the two event lists.
-template <class F> void host_parallel(size_t n, size_t grain, F f);
-// ids reordered by key(id) DESCENDING, equal keys keeping their order (what std::stable_sort with `>` gives): three 11-bit counting passes
-// — the planner sorts a shard's 200 000 reads by length three times, and comparison sorts were a third of its time
-template <class Key> void stable_sort_desc(std::vector<uint32_t>& ids, Key key) {
-  const size_t n = ids.size(); if (n < 2) return;
-  if (n < 2048) { std::stable_sort(ids.begin(), ids.end(), [&](uint32_t x, uint32_t y) { return key(x) > key(y); }); return; }
-  std::vector<uint32_t> k(n), tmp(n), ktmp(n);
-  for (size_t i = 0; i < n; i++) k[i] = ~key(ids[i]);   // ascending in the complement = descending in the key
-  for (int pass = 0; pass < 3; pass++) {
-    const int sh = 11 * pass; size_t cnt[2049] = {0};
-    for (size_t i = 0; i < n; i++) cnt[((k[i] >> sh) & 2047u) + 1]++;
-    bool trivial = false; for (size_t b = 1; b <= 2048; b++) if (cnt[b] == n) trivial = true;
-    if (trivial) continue;
-    for (size_t b = 0; b < 2048; b++) cnt[b + 1] += cnt[b];
-    for (size_t i = 0; i < n; i++) { const size_t at = cnt[(k[i] >> sh) & 2047u]++; tmp[at] = ids[i]; ktmp[at] = k[i]; }
-    ids.swap(tmp); k.swap(ktmp);
-  }
-}
-inline void sort_u32(std::vector<uint32_t>& v) {   // ascending, three 11-bit counting passes
-  const size_t n = v.size(); if (n < 4096) { std::sort(v.begin(), v.end()); return; }
-  std::vector<uint32_t> tmp(n);
-  for (int pass = 0; pass < 3; pass++) {
-    const int sh = 11 * pass; const uint32_t mask = pass == 2 ? 1023u : 2047u; size_t cnt[2049] = {0};
-    for (size_t i = 0; i < n; i++) cnt[((v[i] >> sh) & mask) + 1]++;
-    for (size_t b = 0; b < 2048; b++) cnt[b + 1] += cnt[b];
-    for (size_t i = 0; i < n; i++) tmp[cnt[(v[i] >> sh) & mask]++] = v[i];
-    v.swap(tmp);
-  }
-}
-void class_ids(const ShardHost& S, const LayoutTables& T, std::vector<uint32_t>* ids, uint32_t n_class[7], bool duplex) {
-  auto class_of = [&](size_t i) -> int {
-    const MkpReadHdr& h = S.hdr[i];
-    auto same = [&](uint32_t t0, uint32_t t1) { const MkpTagRef &a = S.tagref[h.tag_off + t0], &b = S.tagref[h.tag_off + t1];
-        // compared on the device while the lists were written (only neighbours are ever asked about)
-        if (S.dev_packed) return t1 == t0 + 1 && b.pad != 0;
-        return a.n == b.n && (a.n == 0 || memcmp(&S.ranks[a.rank_off], &S.ranks[b.rank_off], 4 * (size_t)a.n) == 0); };
-    if ((h.flags & MKP_RF_BAD) || !h.n_tags || h.layout >= T.dev.size()) return 4;
-    const MkpLayout& L = T.dev[h.layout];
-    bool explicit_tags = true;
-    for (uint32_t t = 0; t < h.n_tags; t++) if (L.tags[t].mode != 0) explicit_tags = false;
-    if (duplex && L.fast == 2) {
-      const uint32_t nA = L.pad;
-      if (explicit_tags && (nA != 2 || same(0, 1)) && (h.n_tags - nA != 2 || same(nA, nA + 1))) return (nA == 1 && h.n_tags - nA == 1) ? 5 : 6;
-      return 4;
-    }
-    if (L.fast == 1 && h.n_tags <= 2) {
-      const bool sparse = explicit_tags && (h.n_tags == 1 || same(0, 1));
-      return (sparse ? 0 : 2) + (int)(h.n_tags - 1);
-    }
-    return 4;
-  };
-  // classified on all cores (the rank-list comparisons touch every call of a two-tag read); then one list per class,
-  // one wave decodes one read start to end: the longest reads are launched first so that they do not form the kernel's tail
-  std::vector<uint8_t> cl(S.hdr.size());
-  host_parallel(S.hdr.size(), 4096, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; i++) cl[i] = (uint8_t)class_of(i); });
-  std::vector<uint32_t> cls[7];
-  for (size_t i = 0; i < cl.size(); i++) cls[cl[i]].push_back((uint32_t)i);
-  host_parallel(7, 1, [&](size_t lo, size_t hi) { for (size_t c = lo; c < hi; c++) stable_sort_desc(cls[c], [&](uint32_t x) { return S.hdr[x].l_seq;
-    }); });
-  ids->clear();
-  for (int c = 0; c < 5; c++) { n_class[c] = (uint32_t)cls[c].size(); ids->insert(ids->end(), cls[c].begin(), cls[c].end()); }
-  for (int c = 5; c < 7; c++) { n_class[c] = 2u * (uint32_t)cls[c].size(); for (uint32_t r : cls[c]) { ids->push_back(r);
-      ids->push_back(r | 0x80000000u); } }
-}
-
-// MkpFusedDesc of a layout whose tags form one explicit-mode group (decode class SPARSE): the walk of
-// MultipleThresholdModCaller::call (threshold_mod_caller.rs:28-63) over a call's map, resolved from the layout's caller tables
-MkpFusedDesc fused_desc(const MkpLayout& D) {
-  MkpFusedDesc f; memset(&f, 0, sizeof(f));
-  if (D.fast != 1 || D.n_tags == 0 || D.n_tags > 2) return f;
-  const uint32_t b0 = D.tags[0].fb & 3u, sg0 = D.tags[0].neg & 1u;
-  const MkpGroupDesc& G = D.groups[sg0 * 4 + b0];
-  uint32_t hit = 0; for (uint32_t t = 0; t < D.n_tags; t++) hit |= 1u << (D.tagmap[t][b0] & 15u);
-  const uint32_t pv = G.pat[hit < 20u ? hit : 0u], n_post = std::min<uint32_t>((pv >> 3) & 7u, MKP_KMAX);
-  uint32_t ob = 0;
-  for (uint32_t i = 0; i < n_post; i++) {
-    const uint32_t kq = (pv >> (16 + 2 * i)) & 3u;
-    ob |= 1u << ((G.slots >> (8 * kq)) & 0xffu);
-    f.it_cid |= ((G.cids >> (8 * kq)) & 0xffu) << (8 * i); f.it_thr[i] = G.thr_mod[kq];
-    for (uint32_t t = 0; t < D.n_tags; t++) for (uint32_t k = 0; k < D.tags[t].n_codes; k++)
-      if (((D.tagmap[t][b0] >> (4 + 4 * k)) & 15u) == kq) f.it_src |= (t | (k << 1)) << (4 * i);
-  }
-  f.misc = b0 | (sg0 << 2) | (n_post << 3) | (MKP_G_CIDCAN(G.misc) << 8) | (ob << 16);
-  f.nc = (uint32_t)D.tags[0].n_codes | ((D.n_tags > 1 ? (uint32_t)D.tags[1].n_codes : 0u) << 8);
-  f.thr_can = G.thr_can;
-  // the thresholds of the integer caller: least T with T / 2048 >= threshold (exact in double: a float times 2^11)
-  auto i_of = [](float thr) -> int32_t { if (!(thr == thr)) return INT32_MAX; const double t = std::ceil((double)thr * 2048.0); return (int32_t)std::max(-1073741824.0,
-      std::min(1073741824.0, t)); };
-  for (uint32_t i = 0; i < MKP_KMAX; i++) f.i_thr[i] = i_of(f.it_thr[i]);
-  f.i_can = i_of(f.thr_can);
-  f.misc |= 1u << 6;
-  const int x = MKP_G_COLL(G.misc); const uint32_t n_pre = pv & 7u;   // collapse_redistribute's inputs (only looked at in collapse runs)
-  bool col_exact = true;
-  for (uint32_t i = 0; i < n_pre && i < MKP_KMAX; i++) if ((int)((pv >> (8 + 2 * i)) & 3u) == x) {
-    f.col = 1u; f.n_other = (float)n_pre;
-    for (uint32_t t = 0; t < D.n_tags; t++) for (uint32_t k = 0; k < D.tags[t].n_codes; k++)
-      if ((int)((D.tagmap[t][b0] >> (4 + 4 * k)) & 15u) == x) f.col |= (t | (k << 1)) << 1;
-    // (a share over three codes is rounded: the f32 walk stays)
-    if (n_pre == 1 || n_pre == 2 || n_pre == 4) f.col |= (n_pre == 1 ? 0u : n_pre == 2 ? 1u : 2u) << 5; else col_exact = false;
-  }
-  if (col_exact) f.misc |= 1u << 7;
-  return f;
-}
-
 template <class V> void upload(DevBuf& b, const V& v) {
   const size_t bytes = v.size() * sizeof(v[0]);
   b.ensure(std::max<size_t>(bytes, 16));
   if (!v.empty()) h2d_copy(b.p, v.data(), bytes);   // (through the library's page-locked staging: mkp_ctx.hpp)
-}
-
-template <class F> void host_parallel(size_t n, size_t grain, F f) {   // f(lo, hi) over [0, n) in `grain`-sized pieces on the host pool
-  const size_t pieces = (n + grain - 1) / grain;
-  HostPool::get().parallel(pieces, [&](size_t i) { f(i * grain, std::min(n, (i + 1) * grain)); });
-}
-
-// htslib's pileup engine (bam_plp_push; `set_max_depth` = bam_plp_set_maxcnt, pileup/mod.rs:755-759) refuses a record when it starts
-// where the last buffered record started and the buffer — the records that end at or behind that position, plus the list's tail node —
-// holds more than max_depth entries (`iter->pos == b->core.pos && iter->mp->cnt > iter->maxcnt`); the first record of a start is always
-// taken, so depth alone drops nothing.  Every interval of the reference's grid is a fetch with an iterator of its own over the records
-// that overlap it.  Dropping per (record, interval) is not reproduced on the device; what is decided here, exactly, is whether ANY
-// record would be dropped: an interval [a, e) and a start b shared by two or more of its records with
-//     #{records of the interval: start <= b and end >= b}  >  max_depth        (end > a where b <= a: the fetch's own condition).
-// If there is none, htslib keeps every record at any depth and the device result is exact.  The population is htslib's: every record
-// passing BAM_DEF_MASK (kept reads and supplementary ones), by reference span (ref-skips included).
-// Returns whether the shard needs the wide tallies: a column that may hold more than 65 535 records overflows the 16-bit strand halves
-// of the packed ones.  No (counter, strand, column) tally exceeds its column's record count — a record adds at most one feature per
-// tally strand at a position (a second feature at one base is the other mod strand's call, on the other tally strand), one observed-code
-// mark per slot and strand, one deletion — so the column depth is the bound.  Decided whenever the shard holds more than 65 535 records,
-// whatever max_depth says.  pileup-hemi has no wide kernel: such a shard is refused there.
-bool depth_guard(const ShardHost& S, uint32_t max_depth, const std::vector<uint32_t>& iv_starts, bool hemi) {
-  const size_t n = S.hdr.size() + S.extra_spans.size();
-  constexpr size_t kNarrowDepth = 65535;
-  if (n <= max_depth && n <= kNarrowDepth) return false;
-  std::vector<std::pair<uint32_t, uint32_t>> sp; sp.reserve(n);   // (start, end), starts ascending (alignment starts and ends are non-negative)
-  for (auto& h : S.hdr) sp.push_back({(uint32_t)h.ref_start, (uint32_t)std::max(h.ref_end, h.ref_start + 1)});
-  for (auto& x : S.extra_spans) sp.push_back({(uint32_t)x.first, (uint32_t)std::max(x.second, x.first + 1)});
-  if (!std::is_sorted(sp.begin(), sp.end(), [](auto& x, auto& y) { return x.first < y.first; }))
-    std::stable_sort(sp.begin(), sp.end(), [](auto& x, auto& y) { return x.first < y.first; });
-  std::vector<uint32_t> en;   // ends ascending (built on first use)
-  auto sorted_ends = [&]() { if (en.size() != n) { en.resize(n); for (size_t i = 0; i < n; i++) en[i] = sp[i].second; sort_u32(en); } };
-  bool wide = false;
-  if (n > kNarrowDepth) {
-    // O(n) upper bound first: the records over a column p start in (p - L, p], L = the longest span — the most starts in any L positions
-    uint64_t L = 0; for (auto& x : sp) L = std::max<uint64_t>(L, x.second - x.first);
-    size_t bound = 0;
-    for (size_t i = 0, j = 0; i < n; i++) { while ((uint64_t)sp[j].first + L <= sp[i].first) j++; bound = std::max(bound, i - j + 1); }
-    if (bound > kNarrowDepth) {   // the exact deepest column: a sweep over starts and ends
-      sorted_ends();
-      size_t j = 0, cur = 0, best = 0;
-      for (size_t i = 0; i < n; i++) { while (j < n && en[j] <= sp[i].first) { j++; cur--; } cur++; best = std::max(best, cur); }
-      wide = best > kNarrowDepth;
-    }
-    if (wide && hemi) throw Error(MKP_E_UNSUPPORTED,
-        "more than 65535 reads over one position: pileup-hemi columns this deep are outside the device path (16-bit packed tallies)");
-  }
-  if (n <= max_depth) return wide;
-  sorted_ends();
-  auto refuse = [&](uint32_t b, size_t held) {
-    throw Error(MKP_E_UNSUPPORTED, "htslib would drop records here: " + std::to_string(held) + " buffered records at position " + std::to_string(b) +
-        ", where several records start, exceed max_depth (" + std::to_string(max_depth) + "); bam_plp_push's maxcnt read dropping is not reproduced"); };
-  auto ends_below = [&](uint32_t v) { return (size_t)(std::lower_bound(en.begin(), en.end(), v) - en.begin()); };   // #{end < v}
-  // interval starts of the shard (none given: the shard is one interval)
-  std::vector<uint32_t> A; A.push_back((uint32_t)std::max(S.win_start, 0));
-  for (size_t k = 1; k < iv_starts.size(); k++) if (iv_starts[k] > A.back()) A.push_back(iv_starts[k]);
-  // (1) starts b inside an interval (a <= b): the interval's fetch holds every record with start <= b <= end
-  for (size_t i = 0; i < n;) {
-    size_t r = i; while (r < n && sp[r].first == sp[i].first) r++;
-    const uint32_t b = sp[i].first;
-    if (r - i >= 2 && b >= A[0]) {
-      const bool on_start = std::binary_search(A.begin(), A.end(), b);   // b == a: records that end AT a are not fetched
-      const size_t held = r - (on_start ? ends_below(b + 1) : ends_below(b));
-      if (held > max_depth) refuse(b, held);
-    }
-    i = r;
-  }
-  // (2) starts in front of an interval's start a: among the records with start < a < end
-  for (uint32_t a : A) {
-    const size_t before = (size_t)(std::lower_bound(sp.begin(), sp.end(), a, [](auto& x, uint32_t v) { return x.first < v; }) - sp.begin());
-    if (before - std::min(before, ends_below(a + 1)) <= max_depth) continue;
-    size_t held = 0;
-    for (size_t i = 0; i < before;) {
-      size_t r = i, m = 0; while (r < before && sp[r].first == sp[i].first) { m += sp[r].second > a; r++; }
-      held += m;
-      if (m >= 2 && held > max_depth) refuse(sp[i].first, held);
-      i = r;
-    }
-  }
-  return wide;
 }
 
 // BGZF inflate on the device: mkp_inflate_wave4, one wave per block — speculative token decode, a scalar walk that only marks the chain,
@@ -271,519 +82,40 @@ namespace {
 hipError_t launch_inflate(hipStream_t st, const uint8_t* in, const void* blks, uint32_t n, uint8_t* out, uint32_t* status) {
   return mkp_launch_inflate_auto(st, in, blks, n, out, status); }
 
-// slot bitmap of a focus window (bit p - win_start + margin set where position p owns a tally column), its running popcount per word and —
-// slot pipeline — the slot positions.  Depends on the focus bytes only.
-void window_slots(mkp_ctx* c, bool hemi, bool stream, std::vector<uint32_t>& slotbm, std::vector<uint32_t>& wpfx, std::vector<uint32_t>& slot_pos_h) {
+// the plan's arrays into HBM, the buffers the kernels write, the fused reads' call plane (built once per resident shard — a re-launch on the
+// shard reuses it — and counted in the upload step), the LDS sizes and the key passes
+void upload_plan(mkp_ctx* c, const ShardPlan& pl, PlanTrace& trace) {
   const ShardHost& S = c->shard;
-  const int64_t win = (int64_t)S.win_end - (int64_t)S.win_start;
-  const size_t nbits = (size_t)win + 2 * MKP_SLOTBM_MARGIN, nwords = (nbits + 31) / 32 + 2;
-  slotbm.assign(nwords, 0);
-  const uint8_t* fz = c->focus.data();
-  // pileup-hemi: only the positions with a positive-strand motif hit own a column (positions_to_motifs.get(pos), duplex.rs:289-296)
-  uint8_t hemi_ok[64]; for (size_t k = 0; k < 64; k++) hemi_ok[k] = (k < c->combos.size() && c->combos[k].n_pos > 0) ? 1 : 0;
-  // pieces are multiples of 32 positions and the margin is 64: no two pieces share a word
-  host_parallel((size_t)win, (size_t)1 << 20, [&](size_t lo, size_t hi) {
-    for (size_t p = lo; p < hi; p++) if (hemi ? ((fz[p] & 1u) && hemi_ok[fz[p] >> 2]) : (fz[p] & 3u)) { const size_t b = p + MKP_SLOTBM_MARGIN;
-        slotbm[b >> 5] |= 1u << (b & 31); }
-  });
-  wpfx.assign(nwords + 1, 0);
-  {   // running popcount over the bitmap words: block sums on all cores, a short serial pass over the blocks, then the blocks again
-    const size_t blk = (size_t)1 << 16, nblk = (nwords + blk - 1) / blk; std::vector<uint32_t> bsum(nblk + 1, 0);
-    host_parallel(nblk, 1, [&](size_t lo, size_t hi) { for (size_t b = lo; b < hi; b++) { uint32_t t = 0;
-        for (size_t w = b * blk; w < std::min(nwords, (b + 1) * blk); w++) t += (uint32_t)__builtin_popcount(slotbm[w]);
-        bsum[b + 1] = t; } });
-    for (size_t b = 0; b < nblk; b++) bsum[b + 1] += bsum[b];
-    host_parallel(nblk, 1, [&](size_t lo, size_t hi) { for (size_t b = lo; b < hi; b++) { uint32_t run = bsum[b];
-        for (size_t w = b * blk; w < std::min(nwords, (b + 1) * blk); w++) { wpfx[w] = run;
-          run += (uint32_t)__builtin_popcount(slotbm[w]); } } });
-    wpfx[nwords] = bsum[nblk];
-  }
-  slot_pos_h.clear();
-  if (stream) {
-    slot_pos_h.resize(wpfx[nwords]);
-    host_parallel(nwords, (size_t)1 << 15, [&](size_t lo, size_t hi) {
-      for (size_t w = lo; w < hi; w++) { uint32_t at = wpfx[w];
-          for (uint32_t bits = slotbm[w]; bits; bits &= bits - 1u) slot_pos_h[at++] = (uint32_t)((int64_t)(w * 32 + (size_t)__builtin_ctz(bits)) - MKP_SLOTBM_MARGIN + S.win_start);
-          }
-    });
-  }
-}
-bool stream_pipeline(const mkp_ctx* c, bool hemi) { return c->has_focus && !hemi; }
-
-// derive tile geometry, tile read ranges and the run parameters; upload everything
-void make_resident(mkp_ctx* c) {
-  auto t0 = std::chrono::steady_clock::now();
-  ShardHost& S = c->shard;
-  const bool trace = getenv("MKP_TRACE_PLAN") != nullptr;   // host planning stages on stderr
-  auto lap = [&, last = t0](const char* what) mutable { if (trace) { auto now = std::chrono::steady_clock::now();
-      fprintf(stderr, "[mkpileup plan] %-28s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - last).count()); last = now; } };
-  // hazard: the reference's ReadCache is keyed by read NAME (read_cache.rs:28-35); two kept records with
-  // one name in one interval share a cache entry there: the later one is answered from the earlier one's calls.  Found here, planned
-  // behind the tile plan (it needs the focus positions), reproduced by mkp_dup_events (mkp_slots.hip).
-  std::vector<std::vector<uint32_t>> dup_groups;   // records of one name (and partition key) that meet inside an interval: planned below (plan_dups)
-  { const size_t nn = S.name_hash.size();
-    // every thread takes the names whose hash falls into its sixteenth and looks for a repeat in an open-addressing table of its own
-    // (value = the first record carrying the name); repeats are rare, so they are only collected here and judged below
-    std::mutex dmu; std::vector<std::pair<uint32_t, uint32_t>> dups;   // (first record with the name, a later one)
-    host_parallel(16, 1, [&](size_t lo, size_t hi) { for (size_t part = lo; part < hi; part++) {
-      size_t mine = 0; for (size_t i = 0; i < nn; i++) if ((S.name_hash[i] >> 60) == part) mine++;
-      if (mine < 2) continue;
-      size_t cap = 64; while (cap < 2 * mine) cap <<= 1;
-      std::vector<uint64_t> tab(cap, 0), key(cap, 0); std::vector<uint32_t> who(cap, 0); std::vector<uint8_t> used(cap, 0);
-      for (size_t i = 0; i < nn; i++) { const uint64_t hh = S.name_hash[i]; if ((hh >> 60) != part) continue;
-        const uint64_t kk = i < S.hdr.size() ? S.hdr[i].flags >> MKP_RF_KEY_SHIFT : 0u;   // per partition key: tallies of different keys never meet
-        size_t at = (size_t)((hh * 0x9e3779b97f4a7c15ull) >> 20) & (cap - 1);
-        for (;;) { if (!used[at]) { used[at] = 1; tab[at] = hh; key[at] = kk; who[at] = (uint32_t)i; break; }
-                   if (tab[at] == hh && key[at] == kk) { std::lock_guard<std::mutex> g(dmu); dups.push_back({who[at], (uint32_t)i}); break;
-                     } at = (at + 1) & (cap - 1); } }
-    } });
-    // The reference keys its read cache by NAME, one cache per interval (read_cache.rs:28-35, pileup/mod.rs:718-760): two kept records
-    // with one name meet only if they overlap a common interval — then the later one is answered from the earlier one's calls, which the
-    // device path does not reproduce.  Mates / split alignments that lie in different intervals never share a cache and are simply two reads.
-    // (No interval grid given: the shard is one interval.)
-    // Every pair of records of one name is judged (three records A, B, C: the table above names (A, B) and (A, C); B and C can meet too).
-    // A record that lies wholly outside the shard window — a halo record of the fetch — belongs to none of its intervals.
-    std::map<uint32_t, std::vector<uint32_t>> groups;
-    for (auto& d : dups) { if (d.first >= S.hdr.size() || d.second >= S.hdr.size()) continue; auto& g = groups[d.first];
-      if (g.empty()) g.push_back(d.first);
-      g.push_back(d.second); }
-    auto iv_range = [&](const MkpReadHdr& h, int64_t* a, int64_t* b) -> bool {   // false: outside the window
-      const int64_t s0 = h.ref_start, e0 = std::max<int64_t>(h.ref_end, (int64_t)h.ref_start + 1);
-      if (e0 <= (int64_t)S.win_start || s0 >= (int64_t)S.win_end) return false;
-      if (c->iv_starts.empty()) { *a = 0; *b = 0; return true; }
-      auto idx = [&](int64_t p) {
-        return (int64_t)(std::upper_bound(c->iv_starts.begin(), c->iv_starts.end(), (uint32_t)std::max<int64_t>(p, 0)) - c->iv_starts.begin()) - 1; };
-      *a = std::max<int64_t>(idx(std::max<int64_t>(s0, S.win_start)), 0); *b = std::max<int64_t>(idx(std::min<int64_t>(e0, S.win_end) - 1), 0);
-      return true;
-    };
-    for (auto& kv : groups) {
-      std::vector<uint32_t> g = kv.second; std::sort(g.begin(), g.end()); g.erase(std::unique(g.begin(), g.end()), g.end());
-      std::vector<std::pair<int64_t, int64_t>> rg; rg.reserve(g.size());
-      for (uint32_t r : g) { int64_t a, b; if (iv_range(S.hdr[r], &a, &b)) rg.push_back({a, b}); }
-      bool meet = false;
-      for (size_t x = 0; x < rg.size() && !meet; x++) for (size_t y = x + 1; y < rg.size(); y++) if (rg[x].first <= rg[y].second
-          && rg[y].first <= rg[x].second) {
-        meet = true; break; }
-      if (!meet) continue;
-      // pileup-hemi keys its DuplexReadCache by name as well (read_cache.rs:368-468); that form is not reproduced
-      if (c->hemi) throw Error(MKP_E_UNSUPPORTED,
-          "two primary records share a read name inside one interval (unmarked duplicates, or mates / split reads that overlap the same interval); pileup-hemi answers the later record from the earlier one's calls (its per-interval cache is keyed by name) and this is not reproduced on the device");
-      dup_groups.push_back(std::move(g));
-    }
-  }
-  lap("duplicate-name check");
-  // caller tables over the layouts this shard's reads use (not whatever the packer has interned before)
-  { std::vector<uint8_t> used(c->packer.layouts.size(), 0);
-    for (auto& h : S.hdr) if (!(h.flags & MKP_RF_BAD) && h.n_tags && h.layout < used.size()) used[h.layout] = 1;
-      c->tables.build(c->packer.layouts, c->caller, &used); }
-  MkpRunParams& P = c->prm; memset(&P, 0, sizeof(P));
-  P.win_start = S.win_start; P.win_end = S.win_end;
-  P.n_counters = c->tables.n_counters; P.n_slots = (uint32_t)c->tables.st.slots.size(); P.n_pb = (uint32_t)c->tables.st.can_pbs.size();
-  P.numeric_mode = c->caller.numeric_mode; P.combine_strands = c->caller.combine_strands; P.edge_filter = c->caller.edge;
-    P.edge_start = c->caller.edge_start;
-  P.edge_end = c->caller.edge_end; P.edge_inverted = c->caller.edge_inverted; P.force_allow = c->caller.force_allow;
-    P.max_depth = c->caller.max_depth;
-  P.has_focus = c->has_focus; P.n_combos = (uint32_t)c->combos.size();
-#ifdef MKP_DEBUG
-  if (const char* dbg = getenv("MKP_DEBUG_SKIP")) P.debug_skip = (uint32_t)strtoul(dbg, nullptr, 0);
-#endif
-  for (int b = 0; b < 4; b++) { P.can_of_pb[b] = 0xff; P.pb_of_can[b] = 0; }
-  for (size_t k = 0; k < c->tables.st.can_pbs.size(); k++) { P.can_of_pb[c->tables.st.can_pbs[k]] = (uint8_t)k;
-    P.pb_of_can[k] = (uint8_t)c->tables.st.can_pbs[k]; }
-  std::vector<int> order(P.n_slots); for (uint32_t i = 0; i < P.n_slots; i++) order[i] = (int)i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { const MkpSlot &x = c->tables.st.slots[(size_t)a],
-      &y = c->tables.st.slots[(size_t)b]; return x.code_repr != y.code_repr ? x.code_repr < y.code_repr : x.pb < y.pb; });
-  for (uint32_t i = 0; i < P.n_slots; i++) { P.slot_order[i] = (uint8_t)order[i]; P.slots[i] = c->tables.st.slots[i]; }
-  lap("caller tables + params");
-  if (P.combine_strands && !P.has_focus) throw Error(MKP_E_INVALID, "combine_strands needs motif focus positions");
-  if (c->hemi) {
-    // pileup-hemi counters: a pattern block of (1 + codes)^2 counters per primary base that has calls, elements in DuplexModCodeRepr
-    // order (Canonical < Code(char) < ChEbi(id) = 0 < the code_repr encoding's numeric order)
-    if (!c->has_focus) throw Error(MKP_E_INVALID, "pileup-hemi needs the focus positions of a palindromic motif");
-    if (!c->partition_tags.empty()) throw Error(MKP_E_INVALID, "pileup-hemi has no partition tags");
-    P.hemi = 1; P.hemi_off = c->hemi_off;
-    memset(P.hemi_el, 0xff, sizeof(P.hemi_el)); memset(c->hemi_codes, 0, sizeof(c->hemi_codes));
-    uint32_t next = MKP_H_PAT;
-    for (int b = 0; b < 4; b++) { P.hemi_pat_base[b] = 0xff; P.hemi_nel[b] = 0; }
-    for (size_t k = 0; k < c->tables.st.can_pbs.size(); k++) {
-      const int pb = c->tables.st.can_pbs[k];
-      std::vector<int> mine; for (size_t i = 0; i < c->tables.st.slots.size(); i++) if (c->tables.st.slots[i].pb == pb) mine.push_back((int)i);
-      std::sort(mine.begin(), mine.end(), [&](int x, int y) {
-        return c->tables.st.slots[(size_t)x].code_repr < c->tables.st.slots[(size_t)y].code_repr; });
-      const bool comb = P.numeric_mode == 1;   // DuplexModCall::into_combined: every modified element becomes the base's any-mod code
-      const uint32_t nel = comb ? (mine.empty() ? 1u : 2u) : 1u + (uint32_t)mine.size();
-      if (nel > MKP_KMAX + 1) throw Error(MKP_E_UNSUPPORTED, "more mod codes on one base than a pileup-hemi pattern block holds");
-      P.hemi_pat_base[pb] = (uint8_t)next; P.hemi_nel[pb] = (uint8_t)nel; next += nel * nel;
-      P.hemi_el[MKP_C_CAN + k] = 0;
-      for (size_t r = 0; r < mine.size(); r++) {
-        const MkpSlot& sl = c->tables.st.slots[(size_t)mine[r]];
-        P.hemi_el[sl.cid] = (uint8_t)(comb ? 1u : 1u + r);
-        c->hemi_codes[pb][comb ? 1u : 1u + r] = comb ? (uint32_t)"ACGT"[pb] : sl.code_repr;
-      }
-    }
-    if (next > MKP_H_MAX_COUNTERS) throw Error(MKP_E_UNSUPPORTED, "too many pileup-hemi pattern counters for one LDS tile");
-    P.hemi_counters = next;
-    // a record whose tags fail leaves one NoCall per interval it crosses (mkp_hemi_failed_reads), written into its own event slice:
-    // make every slice at least that long
-    if (c->hemi_iv.empty()) c->hemi_iv.push_back((uint32_t)S.win_start);
-    if (!std::is_sorted(c->hemi_iv.begin(), c->hemi_iv.end())) throw Error(MKP_E_INVALID, "interval starts must ascend");
-    for (auto& h : S.hdr) {
-      auto iv_of = [&](int64_t p) {
-        return (int64_t)(std::upper_bound(c->hemi_iv.begin(), c->hemi_iv.end(), (uint32_t)std::max<int64_t>(p, 0)) - c->hemi_iv.begin()); };
-      const int64_t need = iv_of((int64_t)h.ref_end - 1) - iv_of(h.ref_start) + 1;
-      h.event_cap = (uint32_t)std::max<int64_t>(h.event_cap, need);
-    }
-  }
-  // decode kernel classes; a duplex read decoded one group per wave needs room for both groups' lists behind the merged one
-  std::vector<uint32_t> class_list; class_ids(S, c->tables, &class_list, c->n_class, true);
-  lap("decode classes");
-  // SPARSE reads with two tags: combine_checked's test (mod_bam.rs:629-656) that a call's probabilities over both tags do not add up
-  // to more than 1.01 — every term is (2q + 1) / 512, so the f32 sum is exact and `> 1.01f` is "the numerators reach 518" — is made
-  // here over the ML bytes, on all cores, and handed to the slot decoder as a header flag
-  host_parallel(c->n_class[1], 2048, [&](size_t lo, size_t hi) {
-    for (size_t k = lo; k < hi; k++) {
-      MkpReadHdr& h = S.hdr[class_list[c->n_class[0] + k]];
-      if (S.dev_packed) { if (S.dev_sum2[class_list[c->n_class[0] + k]]) h.flags |= MKP_RF_SUMERR; else h.flags &= ~MKP_RF_SUMERR; continue; }
-      const MkpLayout& L = c->tables.dev[h.layout];
-      const MkpTagRef &t0 = S.tagref[h.tag_off], &t1 = S.tagref[h.tag_off + 1];
-      const uint32_t nc0 = L.tags[0].n_codes, nc1 = L.tags[1].n_codes;
-      bool bad = false;
-      for (uint32_t j = 0; j < t0.n && !bad; j++) {
-        uint32_t num = 0;
-        for (uint32_t i = 0; i < nc0; i++) num += 2u * S.ml[t0.ml_off + j * nc0 + i] + 1u;
-        for (uint32_t i = 0; i < nc1; i++) num += 2u * S.ml[t1.ml_off + j * nc1 + i] + 1u;
-        bad = num >= 518u;
-      }
-      if (bad) h.flags |= MKP_RF_SUMERR; else h.flags &= ~MKP_RF_SUMERR;
-    }
-  });
-  lap("probability-sum test");
-  { size_t at = 0; for (int k = 0; k < 5; k++) at += c->n_class[k];
-    for (; at < class_list.size(); at += 2) {
-      MkpReadHdr& h = S.hdr[class_list[at]];
-      const uint64_t need = 2ull * ((uint64_t)S.tagref[h.tag_off].n + S.tagref[h.tag_off + c->tables.dev[h.layout].pad].n);
-      if (need > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 call events in one read");
-      h.event_cap = std::max(h.event_cap, (uint32_t)need);
-    } }
-  { uint64_t off = 0;   // event slices laid out again (capacities may have grown above)
-    for (auto& h : S.hdr) {
-      if (off > 0xfffffff0ull - h.event_cap) throw Error(MKP_E_UNSUPPORTED, "shard exceeds 4 Gi call events; use smaller shards");
-        h.event_off = (uint32_t)off; off += h.event_cap; }
-    S.n_events_cap = off; }
-  P.readout_b_off = (uint32_t)S.hdr.size();
-  lap("decode classes + event slices");
-  const size_t n = S.hdr.size();
-  for (size_t i = 1; i < n; i++) if (S.hdr[i].ref_start < S.hdr[i - 1].ref_start) throw Error(MKP_E_INVALID, "records must be coordinate sorted");
-  c->wide = depth_guard(S, c->caller.max_depth, c->iv_starts, c->hemi);
-  lap(c->wide ? "sortedness + depth guard (wide tallies)" : "sortedness + depth guard (16-bit tallies)");
-
-  // ---- tile plan.  The accumulate kernel runs two 1024-thread workgroups per CU, each holding one tile in LDS: 76 KiB per
-  // workgroup including ~3.5 KiB of static LDS leaves slack for the allocation granule (at 80 KiB each one GPU box ran them one
-  // per CU and the kernel took 1.9x as long).  A tile = a run of reference positions; its tally columns ("slots") are all of
-  // its positions, or — when the run has focus positions — only those, so a --cpg tile spans ~50x more reference.  A wide shard holds
-  // two u32 planes per counter (one per strand): twice the tally words per slot, so about half the slots per tile.
-  const uint32_t words_per_slot = (c->hemi ? P.hemi_counters : P.n_counters + P.n_slots) * (c->wide ? 2u : 1u);
-  const uint32_t budget_words = (76u * 1024u - 3584u) / 4u;
-  const int64_t win = (int64_t)S.win_end - (int64_t)S.win_start;
-  std::vector<MkpTile> tiles; std::vector<uint32_t> slotbm; uint32_t Scap = 0, Wcap = 0;
-  // focus runs take the slot pipeline (mkp_slots.hip); pileup-hemi keeps the tile walk
-  const bool stream = stream_pipeline(c, c->hemi);
-  std::vector<uint32_t> slot_pos_h, wpfx; std::vector<MkpSTile> stiles; bool preplanned = false;
-  c->slot_mode = stream; P.slot_stream = stream ? 1u : 0u; c->cov_bytes = 0;
-  auto max_slots_for = [&](uint32_t W) { uint32_t best = 0; for (uint32_t s = 64; s <= 4160; s += 64) if (MKP_PILEUP_LDS_WORDS(words_per_slot, s,
-      W) <= budget_words) best = s;
-  return best; };
-  if (!c->has_focus) {
-    uint32_t Smax = max_slots_for(0);
-    if (Smax < 128) throw Error(MKP_E_UNSUPPORTED, "too many counters for one LDS tile");
-    uint32_t T = Smax - 2 * MKP_HALO;
-    if (c->cfg.tile_positions) T = std::min(T, std::max<uint32_t>(32u, c->cfg.tile_positions));
-    Scap = (T + 2 * MKP_HALO + 63u) & ~63u;
-    for (int64_t r0 = S.win_start; r0 < S.win_end; r0 += T) tiles.push_back({(int32_t)r0, (int32_t)std::min<int64_t>(r0 + T, S.win_end), 0, 0});
-  } else {
-    // slot bitmap + running popcount + slot positions: made ahead of the reads when the driver asked for it (mkp_internal_shard_preplan)
-    const size_t nbits = (size_t)win + 2 * MKP_SLOTBM_MARGIN, nwords = (nbits + 31) / 32 + 2;
-    preplanned = c->wplan.valid && stream && !c->hemi && c->wplan.slotbm.size() == nwords;
-    if (preplanned) { slotbm.swap(c->wplan.slotbm); wpfx.swap(c->wplan.wpfx); slot_pos_h.swap(c->wplan.slot_pos); c->wplan.valid = false; }
-    else window_slots(c, c->hemi, stream, slotbm, wpfx, slot_pos_h);
-    auto rank = [&](int64_t p) { const size_t b = (size_t)(p - S.win_start + MKP_SLOTBM_MARGIN);
-        return wpfx[b >> 5] + (uint32_t)__builtin_popcount(slotbm[b >> 5] & ((1u << (b & 31)) - 1u)); };
-    if (stream) {
-      // ---- slot pipeline plan (mkp_slots.hip): global slot numbering, per-read slot ranges and feature-stream offsets, tiles of slots
-      const int64_t lo_clamp = (int64_t)S.win_start - MKP_SLOTBM_MARGIN, hi_clamp = (int64_t)S.win_end + MKP_SLOTBM_MARGIN;
-      auto crank = [&](int64_t p) { return rank(std::min(std::max(p, lo_clamp), hi_clamp)); };
-      const uint32_t total = wpfx[nwords];
-      host_parallel(S.hdr.size(), 8192, [&](size_t lo, size_t hi) { for (size_t i = lo; i < hi; i++) { MkpReadHdr& h = S.hdr[i];
-          const uint32_t a = crank(h.ref_start), b = std::max(a, crank(h.ref_end)); h.gs0 = a; h.n_sl = b - a; } });
-      uint64_t off = 0;
-      for (auto& h : S.hdr) {   // (the stream offsets are a running sum: serial, but nothing else is left in the loop)
-        h.cov_off = (uint32_t)off;
-        off += ((uint64_t)h.n_sl + 3u) & ~3ull;
-        if (off > 0xffffff00ull) throw Error(MKP_E_UNSUPPORTED, "shard exceeds 4 GiB of per-read focus positions; use smaller shards");
-      }
-      c->cov_bytes = off;
-      // tile = a run of slots: rows for [g0, g1), tally columns for the slots within MKP_HALO positions of them (strand combining)
-      // LDS of mkp_pileup_stream: tallies + per slot its position and an emission word, + the row map (one thread per slot decides the rows)
-      const uint32_t Smax = std::min<uint32_t>(MKP_PILEUP_THREADS, ((budget_words - MKP_STREAM_ROWMAP_WORDS) / (words_per_slot + 2u)) & ~63u);
-      if (Smax < 128) throw Error(MKP_E_UNSUPPORTED, "too many counters for one LDS tile");
-      // as many slots per tile as LDS and the one-thread-per-slot emission allow, down to ~1024 tiles for small windows: a read is visited once per
-      // tile it crosses and the visits are most of the kernel (C3, round 6: 448 / 640 / 704 / 896 / 992 slots: 0.153 / 0.139 / 0.128 / 0.125 / 0.116
-      // ms)
-      uint32_t Te = std::min<uint32_t>(Smax - 2 * MKP_HALO, std::max<uint32_t>(256u, (total / 1024u + 63u) & ~63u));
-      // tests: many small tiles
-      if (c->cfg.tile_positions) Te = std::max<uint32_t>(32u, std::min<uint32_t>(Smax - 2 * MKP_HALO, c->cfg.tile_positions / 4u));
-      if (const char* e = getenv("MKP_STREAM_TILE")) Te = std::max<uint32_t>(32u,
-          std::min<uint32_t>(Smax - 2 * MKP_HALO, (uint32_t)strtoul(e, nullptr, 10)));
-          // experiments
-      uint32_t most = 0;
-      for (uint32_t g0 = 0; g0 < total; g0 += Te) {
-        MkpSTile t; t.g0 = g0; t.g1 = std::min(total, g0 + Te);
-        t.r0 = (int32_t)slot_pos_h[t.g0]; t.r1 = (int32_t)slot_pos_h[t.g1 - 1u] + 1;
-        t.gh0 = crank((int64_t)t.r0 - MKP_HALO); t.gh1 = crank((int64_t)t.r1 + MKP_HALO); t.first = t.last = 0;
-        stiles.push_back(t); most = std::max(most, t.gh1 - t.gh0);
-      }
-      if (most > Smax) throw Error(MKP_E_UNSUPPORTED, "internal: slot tile does not fit the LDS budget");
-      Scap = std::max<uint32_t>(64u, (most + 63u) & ~63u); Wcap = 0;
-    } else {
-    // span: enough tiles to balance 512 persistent workgroups, bounded by the bitmap the tile keeps in LDS
-    const uint32_t span_max = 32768 - 128;
-    // A read is visited once per tile it crosses: longer tiles mean fewer visits (10 kb reads: 1.64 per read at 16 kb, 1.41 at 24 kb),
-    // fewer tiles mean a coarser balance over the 512 resident workgroups.  Measured on C3: 2 600 tiles of 24 kb beat 4 100 of 16 kb by 9 %
-    // and 7 900 of 8 kb by 31 %.  Small windows keep >= 16 kb tiles (a handful of workgroups of little work each).
-    uint32_t span = (uint32_t)std::min<int64_t>(span_max, std::max<int64_t>(16384, ((win / 2600) + 63) & ~63ll));
-    if (c->cfg.tile_positions) span = std::max<uint32_t>(64u, std::min(span_max & ~63u, c->cfg.tile_positions & ~63u));
-        // explicit tile span (tests: many small tiles; experiments: larger ones)
-    Wcap = (span + 2 * MKP_HALO + 31 + 31) / 32 + 2;
-    const uint32_t Smax = std::min<uint32_t>(max_slots_for(Wcap), MKP_PILEUP_THREADS);   // row emission of a focus tile: one thread per slot
-    if (Smax < 128) throw Error(MKP_E_UNSUPPORTED, "too many counters for one LDS tile");
-    uint32_t most = 0;
-    for (int64_t r0 = S.win_start; r0 < S.win_end;) {
-      int64_t r1 = std::min<int64_t>(r0 + span, S.win_end);
-      auto halo_slots = [&](int64_t a, int64_t b) { return rank(std::min<int64_t>(b + MKP_HALO,
-          (int64_t)S.win_end + MKP_SLOTBM_MARGIN)) - rank(std::max<int64_t>(a - MKP_HALO, (int64_t)S.win_start - MKP_SLOTBM_MARGIN)); };
-      while (halo_slots(r0, r1) > Smax && r1 - r0 > 32) r1 = r0 + std::max<int64_t>(32, (r1 - r0) / 2);   // dense focus: shorter tile
-      if (halo_slots(r0, r1) > Smax) throw Error(MKP_E_UNSUPPORTED, "internal: focus tile does not fit the LDS budget");
-      if (rank(r1) > rank(r0)) { tiles.push_back({(int32_t)r0, (int32_t)r1, 0, 0}); most = std::max(most, halo_slots(r0, r1));
-          }   // a tile without focus positions emits nothing
-      r0 = r1;
-    }
-    Scap = std::max<uint32_t>(64u, (most + 63u) & ~63u);
-    }
-  }
-  lap("slot bitmap + tiles");
-  // tile -> [first, last) candidate reads (coordinate sorted; the prefix-max of ends bounds the first candidate)
-  {
-    std::vector<int32_t> pmax(n); int32_t m = INT32_MIN;
-    for (size_t i = 0; i < n; i++) { m = std::max(m, S.hdr[i].ref_end); pmax[i] = m; }
-    size_t first = 0, last = 0; std::vector<MkpTile> kept;
-    for (auto& tl : tiles) {
-      const int64_t lo = (int64_t)tl.r0 - MKP_HALO, hi = (int64_t)tl.r1 + MKP_HALO;
-      while (first < n && pmax[first] <= lo) first++;
-      if (last < first) last = first;
-      while (last < n && S.hdr[last].ref_start < hi) last++;
-      bool any = false; for (size_t i = first; i < last && !any; i++) any = S.hdr[i].ref_end > lo;
-      if (any) { tl.first = (uint32_t)first; tl.last = (uint32_t)last; kept.push_back(tl); }
-    }
-    tiles.swap(kept);
-  }
-  // slot tiles: reads are coordinate sorted, so their first slots ascend; the prefix-max of their slot ends bounds the first candidate
-  if (stream) {
-    std::vector<uint32_t> pmax(n); uint32_t m = 0;
-    for (size_t i = 0; i < n; i++) { m = std::max(m, S.hdr[i].gs0 + S.hdr[i].n_sl); pmax[i] = m; }
-    size_t first = 0, last = 0; std::vector<MkpSTile> kept;
-    for (auto& tl : stiles) {
-      while (first < n && pmax[first] <= tl.gh0) first++;
-      if (last < first) last = first;
-      while (last < n && S.hdr[last].gs0 < tl.gh1) last++;
-      bool any = false; for (size_t i = first; i < last && !any; i++) any = S.hdr[i].gs0 + S.hdr[i].n_sl > tl.gh0 && S.hdr[i].n_sl > 0;
-      if (any) { tl.first = (uint32_t)first; tl.last = (uint32_t)last; kept.push_back(tl); }
-    }
-    stiles.swap(kept);
-  }
-  // ---- records sharing a name inside an interval (dup_groups, found above): who answers for the name in which interval.
-  // The reference asks its per-interval cache about a record the first time the record shows up in a focus column of the interval as
-  // something other than a reference skip (add_mod_codes_for_record is called before the deletion check, pileup/mod.rs:783-835); columns
-  // ascend, records inside a column come in file order.  The first record asked OWNS the name in that interval: its tags are parsed, its
-  // calls (by reference position and read base), its codes and its failure answer for every record of the name (read_cache.rs:232-355).
-  std::vector<MkpDupCons> dup_cons; std::vector<MkpDupSeg> dup_segs; std::vector<uint8_t> dup_member(n, 0);
-  if (!dup_groups.empty()) {
-    auto cigar_of = [&](uint32_t r) {
-      const MkpReadHdr& h = S.hdr[r]; std::vector<uint32_t> cg(h.n_cigar);
-      if (!S.dev_packed) { for (uint32_t k = 0; k < h.n_cigar; k++) cg[k] = S.cigar[h.cigar_off + k]; }
-      else if (h.n_cigar) { hip_check(hipSetDevice(c->device), "hipSetDevice");
-        d2h_copy(cg.data(), c->d_cigar.as<uint32_t>() + h.cigar_off, (size_t)h.n_cigar * 4, c->stream); }
-      return cg;
-    };
-    const int64_t W0 = S.win_start, W1 = S.win_end;
-    auto iv_bounds = [&](int64_t k, int64_t* a, int64_t* b) {   // interval k of the shard's grid, clipped to the window
-      if (c->iv_starts.empty()) { *a = W0; *b = W1; return; }
-      *a = std::max<int64_t>(W0, k == 0 ? W0 : (int64_t)c->iv_starts[(size_t)k]);
-        *b = (size_t)k + 1 < c->iv_starts.size() ? std::min<int64_t>(W1, (int64_t)c->iv_starts[(size_t)k + 1]) : W1;
-    };
-    auto iv_index = [&](int64_t p) -> int64_t { if (c->iv_starts.empty()) return 0;
-      return std::max<int64_t>((int64_t)(std::upper_bound(c->iv_starts.begin(), c->iv_starts.end(),
-          (uint32_t)std::max<int64_t>(p, 0)) - c->iv_starts.begin()) - 1, 0);
-        };
-    uint64_t ev_off = S.n_events_cap;
-    for (auto& g : dup_groups) {
-      struct Mem { uint32_t r; int64_t beg, end; std::vector<std::pair<int64_t, int64_t>> skips; };
-      std::vector<Mem> ms;
-      for (uint32_t r : g) {
-        const MkpReadHdr& h = S.hdr[r]; Mem m; m.r = r; m.beg = h.ref_start; m.end = std::max<int64_t>(h.ref_end, (int64_t)h.ref_start + 1);
-        if (m.end <= W0 || m.beg >= W1) continue;   // a halo record of the fetch: in none of the shard's intervals
-        int64_t p = h.ref_start;
-        for (uint32_t w : cigar_of(r)) { const uint32_t op = w & 15u, len = w >> 4; if (op == 3u) m.skips.push_back({p, p + len});
-          if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) p += len;
-          }
-        ms.push_back(std::move(m)); dup_member[r] = 1;
-      }
-      // first column of [lo, hi) in which member m is asked about: a focus position that is not inside one of its reference skips
-      auto first_col = [&](const Mem& m, int64_t lo, int64_t hi) -> int64_t {
-        lo = std::max(lo, m.beg); hi = std::min(hi, m.end);
-        auto in_skip = [&](int64_t p, int64_t* e) {
-          for (auto& sk : m.skips) if (p >= sk.first && p < sk.second) { *e = sk.second; return true; }
-          return false; };
-        if (!c->has_focus) { int64_t p = lo, e; while (p < hi && in_skip(p, &e)) p = e; return p < hi ? p : -1; }
-        for (size_t k = (size_t)(std::lower_bound(slot_pos_h.begin(), slot_pos_h.end(),
-            (uint32_t)std::max<int64_t>(lo, 0)) - slot_pos_h.begin()); k < slot_pos_h.size() && (int64_t)slot_pos_h[k] < hi; k++) {
-          int64_t e; if (!in_skip((int64_t)slot_pos_h[k], &e)) return (int64_t)slot_pos_h[k]; }
-        return -1;
-      };
-      int64_t k_lo = INT64_MAX, k_hi = -1;
-      for (auto& m : ms) { k_lo = std::min(k_lo, iv_index(std::max(m.beg, W0))); k_hi = std::max(k_hi, iv_index(std::min(m.end, W1) - 1)); }
-      std::vector<std::vector<MkpDupSeg>> segs_of(ms.size());
-      for (int64_t k = k_lo; k <= k_hi; k++) {
-        int64_t a, b; iv_bounds(k, &a, &b);
-        int64_t best_p = -1; size_t best = 0; std::vector<uint8_t> present(ms.size(), 0);
-        for (size_t x = 0; x < ms.size(); x++) { const int64_t fc = first_col(ms[x], a, b); if (fc < 0) continue; present[x] = 1;
-          if (best_p < 0 || fc < best_p) { best_p = fc; best = x; } }   // (members are in file order: the first of equal columns stays)
-        if (best_p < 0) continue;
-        for (size_t x = 0; x < ms.size(); x++) if (present[x]) {
-          auto& sv = segs_of[x]; const uint32_t owner = ms[best].r;
-          if (!sv.empty() && sv.back().owner == owner && sv.back().p_hi == (int32_t)a) sv.back().p_hi = (int32_t)b;
-          else sv.push_back({(int32_t)a, (int32_t)b, S.hdr[owner].event_off, owner});
-        }
-      }
-      for (size_t x = 0; x < ms.size(); x++) {
-        bool foreign = false; for (auto& sg : segs_of[x]) if (sg.owner != ms[x].r) foreign = true;
-        if (!foreign) continue;   // asked about first wherever it shows up: an ordinary record (whose events others may read)
-        MkpDupCons dc; memset(&dc, 0, sizeof(dc)); dc.rid = ms[x].r; dc.seg_off = (uint32_t)dup_segs.size(); dc.n_seg = (uint32_t)segs_of[x].size();
-          dc.own_off = S.hdr[ms[x].r].event_off;
-        uint64_t cap = 0; for (auto& sg : segs_of[x]) { cap += S.hdr[sg.owner].event_cap; dup_segs.push_back(sg); }
-        if (ev_off + cap > 0xfffffff0ull) throw Error(MKP_E_UNSUPPORTED, "shard exceeds 4 Gi call events; use smaller shards");
-        dc.eff_off = (uint32_t)ev_off; dc.eff_cap = (uint32_t)cap; ev_off += cap;
-        dup_cons.push_back(dc);
-      }
-    }
-    S.n_events_cap = ev_off;
-    lap("records sharing a name: owners per interval");
-  }
-  c->n_dup_cons = (uint32_t)dup_cons.size();
-  // reads by kernel on the slot pipeline: the fused slot decoder takes the SPARSE classes when no edge filter is set (it never locates
-  // calls off the focus positions, which the edge filter's "any call left" test would need); every other read is decoded into events
-  // by its class kernel and then covered
-  c->read_ids_dec_off = 0; for (auto& x : c->n_slot_class) x = 0;
-  std::vector<uint32_t> slot_ids;
-  if (stream) {
-    const bool fused = !P.edge_filter && !(getenv("MKP_FUSED") && !strcmp(getenv("MKP_FUSED"), "0"));
-    uint32_t dup_forced[2] = {0, 0};
-    std::vector<uint8_t> is_fused(n, 0);
-    if (fused) {
-      // (records sharing a name inside an interval keep their event decoder: their events are what the others are answered from; they move
-      //  behind the fused reads of the class list, where the decode launch starts)
-      if (!dup_groups.empty()) {
-        std::vector<uint32_t> keep, f0, f1; const uint32_t n0 = c->n_class[0], n01 = c->n_class[0] + c->n_class[1]; uint32_t k0 = 0;
-        for (uint32_t k = 0; k < n01; k++) { const uint32_t r = class_list[k]; if (dup_member[r]) (k < n0 ? f0 : f1).push_back(r); else {
-            keep.push_back(r); if (k < n0) k0++; } }
-        std::vector<uint32_t> nl(keep); nl.insert(nl.end(), f0.begin(), f0.end()); nl.insert(nl.end(), f1.begin(), f1.end());
-          nl.insert(nl.end(), class_list.begin() + n01, class_list.end());
-        class_list.swap(nl); c->n_class[0] = k0; c->n_class[1] = (uint32_t)keep.size() - k0; dup_forced[0] = (uint32_t)f0.size();
-          dup_forced[1] = (uint32_t)f1.size();
-      }
-      const uint32_t nf = c->n_class[0] + c->n_class[1];
-      for (uint32_t k = 0; k < nf; k++) is_fused[class_list[k]] = 1;
-      // one list for both SPARSE classes, longest first (the longest reads start first: they do not make the launch's tail)
-      slot_ids.resize(nf);
-      auto longer = [&](uint32_t x, uint32_t y) { return S.hdr[x].l_seq > S.hdr[y].l_seq; };
-      std::merge(class_list.begin(), class_list.begin() + c->n_class[0], class_list.begin() + c->n_class[0], class_list.begin() + nf,
-          slot_ids.begin(), longer);
-      c->n_slot_class[0] = nf;
-      c->read_ids_dec_off = nf; c->n_class[0] = dup_forced[0]; c->n_class[1] = dup_forced[1];
-    }
-    std::vector<uint32_t> rest; rest.reserve(n);
-    for (size_t i = 0; i < n; i++) if (!is_fused[i]) rest.push_back((uint32_t)i);
-    stable_sort_desc(rest, [&](uint32_t x) { return S.hdr[x].n_sl; });
-    c->n_slot_class[2] = (uint32_t)rest.size();
-    slot_ids.insert(slot_ids.end(), rest.begin(), rest.end());
-  }
-  P.slot_cap = Scap; P.focus_words = Wcap;
-  c->lds_bytes = stream ? ((words_per_slot + 2u) * Scap + MKP_STREAM_ROWMAP_WORDS) * 4u : MKP_PILEUP_LDS_WORDS(words_per_slot, Scap, Wcap) * 4u;
-  c->n_tiles = stream ? (uint32_t)stiles.size() : (uint32_t)tiles.size();
-  c->n_slots_total = 0;
-  if (c->has_focus) { for (size_t w = 0; w < slotbm.size(); w++) c->n_slots_total += (uint64_t)__builtin_popcount(slotbm[w]); }
-  lap("candidate reads per tile");
-  c->stats.pack_ms += ms_since(t0);
-  auto t1 = std::chrono::steady_clock::now();
   hip_check(hipSetDevice(c->device), "hipSetDevice");
   upload(c->d_hdr, S.hdr);
-  if (!S.dev_packed) { upload(c->d_cigar, S.cigar); upload(c->d_cigar16, S.cigar16); upload(c->d_chunk, S.chunk_pfx); upload(c->d_seq, S.seq); upload(c->d_tagref, S.tagref);
-    upload(c->d_ranks, S.ranks); upload(c->d_ml, S.ml); }
+  if (!S.dev_packed) {
+    upload(c->d_cigar, S.cigar); upload(c->d_cigar16, S.cigar16); upload(c->d_chunk, S.chunk_pfx); upload(c->d_seq, S.seq);
+    upload(c->d_tagref, S.tagref); upload(c->d_ranks, S.ranks); upload(c->d_ml, S.ml);
+  }
   // (device ingest: those arrays were written in HBM by mkp_ingest_pack and handed over by mkp_internal_shard_attach)
-  lap("upload: packed reads");
-  upload(c->d_layouts, c->tables.dev); upload(c->d_tiles, tiles);
-  upload(c->d_read_ids, class_list);
-  if (c->has_focus && preplanned) { /* focus bytes, combos, slot bitmap and slot positions went up with the pre-plan */ }
-  else if (c->has_focus) { upload(c->d_focus, c->focus); upload(c->d_combos, c->combos); upload(c->d_slotbm, slotbm); } else { c->d_focus.ensure(16);
-    c->d_combos.ensure(64);
-      c->d_slotbm.ensure(16); }
+  trace.lap("upload: packed reads");
+  upload(c->d_layouts, c->tables.dev); upload(c->d_tiles, pl.tiles);
+  upload(c->d_read_ids, pl.class_list);
+  if (c->has_focus && pl.preplanned) { /* focus bytes, combos, slot bitmap and slot positions went up with the pre-plan */ }
+  else if (c->has_focus) { upload(c->d_focus, c->focus); upload(c->d_combos, c->combos); upload(c->d_slotbm, pl.slotbm); }
+  else { c->d_focus.ensure(16); c->d_combos.ensure(64); c->d_slotbm.ensure(16); }
   c->d_events.ensure(std::max<uint64_t>(S.n_events_cap, 1) * sizeof(MkpEvent));
-  if (c->n_dup_cons) { upload(c->d_dupcons, dup_cons); upload(c->d_dupsegs, dup_segs); }
+  if (c->n_dup_cons) { upload(c->d_dupcons, pl.dup_cons); upload(c->d_dupsegs, pl.dup_segs); }
   c->d_readout.ensure(std::max<size_t>(2 * S.hdr.size(), 1) * sizeof(MkpReadOut));   // second half: second-group summaries of duplex reads
   c->d_misc.ensure(64);
-  lap("upload: focus + event buffers");
-  // the fused reads' terms of the decoder's algorithmic bytes (below): what the SEQ sweep and rank marking read, what the plane lookups read
-  std::atomic<uint64_t> fused_swept{0}, fused_looked_up{0};
-  unsigned long long* d_seqn_bytes = nullptr;   // the plane builder's count of the SEQ bytes the decoder reads (MKP_RF_SEQN reads only)
-  if (stream) {
-    if (!preplanned) upload(c->d_slot_pos, slot_pos_h);
-    upload(c->d_stiles, stiles);
-    {   // the fused decoder's work records, in launch order; the cover kernel keeps a read-id list
-      const uint32_t nf = c->n_slot_class[0];
-      std::vector<MkpWork> work(nf);
-      host_parallel(nf, 8192, [&](size_t lo, size_t hi) {
-        uint64_t swept = 0, looked_up = 0;
-        for (size_t k = lo; k < hi; k++) {
-          const MkpReadHdr& h = S.hdr[slot_ids[k]]; MkpWork& w = work[k]; memset(&w, 0, sizeof(w));
-          w.ref_start = h.ref_start; w.l_seq = h.l_seq; w.n_cigar = h.n_cigar;
-          w.cigar_off = (h.flags & MKP_RF_CIGW) ? h.cigar_off : h.cigar16_off;   // the decoder's array of this read (MkpWork, mkp_device.h)
-          w.seq_off = h.seq_off; w.flags = h.flags;
-            w.gs0 = h.gs0;
-              w.n_sl = h.n_sl;
-          w.cov_off = h.cov_off; w.n_tags = h.n_tags; w.layout = h.layout; w.rid = slot_ids[k];
-          if (!(h.flags & MKP_RF_BAD) && h.n_tags) { const MkpTagRef& t0 = S.tagref[h.tag_off]; w.rank_off = t0.rank_off; w.n_calls = t0.n;
-            w.ml_off0 = t0.ml_off;
-              if (h.n_tags > 1) w.ml_off1 = S.tagref[h.tag_off + 1].ml_off; }
-          uint64_t n_rk = 0; if (!(h.flags & MKP_RF_BAD)) for (uint32_t t = 0; t < h.n_tags; t++) n_rk += S.tagref[h.tag_off + t].n;
-          swept += (h.l_seq + 1) / 2 + 2ull * n_rk + ((h.flags & MKP_RF_CIGW) ? 0ull : 2ull * h.n_cigar);   // (16-bit CIGAR: 2 of the 4 bytes per op)
-          looked_up += 16ull * std::min<uint64_t>(MKP_PLANE_WORDS(h.l_seq), h.n_sl);
-        }
-        fused_swept += swept; fused_looked_up += looked_up;
-      });
-      // the base-and-call plane: MKP_PLANE_WORDS(l_seq) 16-byte entries per fused read, in launch order
-      uint64_t pw = 0;
-      for (uint32_t k = 0; k < nf; k++) { if (pw > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "shard exceeds 2^32 call-plane words; use smaller shards");
-        work[k].pad = (uint32_t)pw; pw += MKP_PLANE_WORDS(work[k].l_seq); }
-      c->plane_bytes = pw * sizeof(MkpPlaneEnt);
-      c->d_plane.ensure(c->plane_bytes + 16);   // + the builder's SEQN byte count behind the entries
-      d_seqn_bytes = reinterpret_cast<unsigned long long*>(c->d_plane.as<char>() + c->plane_bytes);
-      hip_check(hipMemsetAsync(d_seqn_bytes, 0, sizeof(unsigned long long), c->stream), "plane counter reset");
-      upload(c->d_work, work);
-      std::vector<uint32_t> cover(slot_ids.begin() + nf, slot_ids.end()); upload(c->d_slot_ids, cover);
-    }
+  trace.lap("upload: focus + event buffers");
+  if (pl.stream) {
+    if (!pl.preplanned) upload(c->d_slot_pos, pl.slot_pos);
+    upload(c->d_stiles, pl.stiles);
+    const uint32_t nf = c->n_slot_class[0];   // the fused decoder takes work records, the cover kernel keeps a read-id list
+    c->d_plane.ensure(c->plane_bytes + 16);   // + the builder's count of the SEQ bytes the decoder reads (MKP_RF_SEQN reads only) behind the entries
+    unsigned long long* d_seqn_bytes = reinterpret_cast<unsigned long long*>(c->d_plane.as<char>() + c->plane_bytes);
+    hip_check(hipMemsetAsync(d_seqn_bytes, 0, sizeof(unsigned long long), c->stream), "plane counter reset");
+    upload(c->d_work, pl.work);
+    { std::vector<uint32_t> cover(pl.slot_ids.begin() + nf, pl.slot_ids.end()); upload(c->d_slot_ids, cover); }
     { std::vector<MkpFusedDesc> fd(c->tables.dev.size()); for (size_t i = 0; i < fd.size(); i++) fd[i] = fused_desc(c->tables.dev[i]);
       upload(c->d_fdesc, fd); }
-    // once per resident shard (a re-launch on the shard reuses it): counted in the upload step
-    hip_check(mkp_launch_call_plane(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], c->d_seq.as<uint8_t>(), c->d_ranks.as<uint32_t>(),
+    hip_check(mkp_launch_call_plane(c->stream, c->d_work.as<MkpWork>(), nf, c->d_seq.as<uint8_t>(), c->d_ranks.as<uint32_t>(),
         c->d_fdesc.as<MkpFusedDesc>(), c->d_plane.p, d_seqn_bytes), "call plane launch");
     c->d_cov.ensure(c->cov_bytes + 256); c->d_visits.ensure(std::max<size_t>(S.hdr.size(), 1) * sizeof(MkpVisit));
     hip_check(mkp_stream_set_lds(c->lds_bytes), "hipFuncSetAttribute(max dynamic LDS, stream)");
@@ -792,37 +124,87 @@ void make_resident(mkp_ctx* c) {
   // partition keys present in this shard: one accumulate pass each
   c->key_passes.clear();
   if (c->partition_tags.empty()) c->key_passes.push_back(MKP_NO_KEY_FILTER);
-  else { std::vector<uint8_t> seen(c->key_names.size(), 0); for (auto& h : S.hdr) { const uint32_t k = h.flags >> MKP_RF_KEY_SHIFT;
-      if (k < seen.size()) seen[k] = 1;
-      } for (uint32_t k = 0; k < seen.size(); k++) if (seen[k]) c->key_passes.push_back(k); if (c->key_passes.empty()) c->key_passes.push_back(0); }
+  else {
+    std::vector<uint8_t> seen(c->key_names.size(), 0);
+    for (auto& h : S.hdr) { const uint32_t k = h.flags >> MKP_RF_KEY_SHIFT; if (k < seen.size()) seen[k] = 1; }
+    for (uint32_t k = 0; k < seen.size(); k++) if (seen[k]) c->key_passes.push_back(k);
+    if (c->key_passes.empty()) c->key_passes.push_back(0);
+  }
   hip_check(mkp_pileup_set_lds(c->lds_bytes), "hipFuncSetAttribute(max dynamic LDS)");
   hip_check(hipDeviceSynchronize(), "upload sync");
-  lap("upload: slot plan + sync");
-  c->stats.h2d_ms = ms_since(t1);
-  c->resident = true; c->resident_hemi = c->hemi;
-  // algorithmic bytes
+  trace.lap("upload: slot plan + sync");
+}
+
+// algorithmic bytes and the shard's sizes in mkp_stats
+void account_bytes(mkp_ctx* c, const ShardPlan& pl) {
+  const ShardHost& S = c->shard;
   uint64_t b_reads = 0; for (auto& h : S.hdr) b_reads += 16 + 4ull * h.n_cigar + (h.l_seq + 1) / 2;
-  c->stats.n_reads = S.hdr.size(); c->stats.n_tiles = c->n_tiles; c->stats.n_positions = (uint64_t)win;
+  c->stats.n_reads = S.hdr.size(); c->stats.n_tiles = c->n_tiles; c->stats.n_positions = (uint64_t)((int64_t)S.win_end - (int64_t)S.win_start);
   // + 8*events added after the run
   c->stats.alg_bytes_decode = b_reads + (S.dev_packed ? S.dev_n_ranks : S.ranks.size()) * 2ull + (S.dev_packed ? S.dev_n_ml : S.ml.size());
   c->stats.alg_bytes_pileup = b_reads;                                          // + 8*events + 44*rows added after the run
-  c->stats.slot_pipeline = stream ? 1u : 0u; c->stats.stream_bytes = 0; c->stats.alg_bytes_agg_survey = 0;
-  if (stream) {
-    // slot pipeline: the decode side also reads the slot positions of every read's span and writes one feature byte per slot and a
-    // 32-byte visit record per read; the aggregation kernel reads exactly those (SEQ and CIGAR are read once per pass)
-    uint64_t n_rs = 0; for (auto& h : S.hdr) n_rs += h.n_sl;
-    c->stats.stream_bytes = n_rs;
-    c->stats.alg_bytes_decode += 4ull * n_rs + n_rs + 32ull * S.hdr.size();
-    // the fused decoder reads neither a read's whole SEQ nor its rank list, and 2 bytes per CIGAR op (4 of a read with an op longer than
-    // 4 095 bases): the 16-byte plane entry under each slot, and the SEQ byte only for a read with a base that is not A/C/G/T (the plane, resolved from SEQ and ranks once per resident shard, is not part of
-    // the pass)
-    unsigned long long seqn_bytes = 0;
-    hip_check(hipMemcpyAsync(&seqn_bytes, d_seqn_bytes, sizeof(seqn_bytes), hipMemcpyDeviceToHost, c->stream), "plane counter readback");
-    hip_check(hipStreamSynchronize(c->stream), "plane counter readback");   // (the shard's own stream: idle here, not the ingest ahead)
-    c->stats.alg_bytes_decode = c->stats.alg_bytes_decode - fused_swept.load() + fused_looked_up.load() + seqn_bytes;
-    c->stats.alg_bytes_pileup = n_rs + 32ull * S.hdr.size();               // + 44*rows added after the run
-    c->stats.alg_bytes_agg_survey = 8ull * n_rs;                            // 8 B per coverage event at a candidate position (+ call events, + 44*rows)
-  }
+  c->stats.slot_pipeline = pl.stream ? 1u : 0u; c->stats.stream_bytes = 0; c->stats.alg_bytes_agg_survey = 0;
+  if (!pl.stream) return;
+  // slot pipeline: the decode side also reads the slot positions of every read's span and writes one feature byte per slot and a
+  // 32-byte visit record per read; the aggregation kernel reads exactly those (SEQ and CIGAR are read once per pass)
+  uint64_t n_rs = 0; for (auto& h : S.hdr) n_rs += h.n_sl;
+  c->stats.stream_bytes = n_rs;
+  c->stats.alg_bytes_decode += 4ull * n_rs + n_rs + 32ull * S.hdr.size();
+  // the fused decoder reads neither a read's whole SEQ nor its rank list, and 2 bytes per CIGAR op (4 of a read with an op longer than
+  // 4 095 bases): the 16-byte plane entry under each slot, and the SEQ byte only for a read with a base that is not A/C/G/T (the plane,
+  // resolved from SEQ and ranks once per resident shard, is not part of the pass); the plane builder counted those SEQ bytes behind the plane
+  unsigned long long seqn_bytes = 0;
+  hip_check(hipMemcpyAsync(&seqn_bytes, c->d_plane.as<char>() + c->plane_bytes, sizeof(seqn_bytes), hipMemcpyDeviceToHost, c->stream),
+      "plane counter readback");
+  hip_check(hipStreamSynchronize(c->stream), "plane counter readback");   // (the shard's own stream: idle here, not the ingest ahead)
+  c->stats.alg_bytes_decode = c->stats.alg_bytes_decode - pl.fused_swept + pl.fused_looked_up + seqn_bytes;
+  c->stats.alg_bytes_pileup = n_rs + 32ull * S.hdr.size();               // + 44*rows added after the run
+  c->stats.alg_bytes_agg_survey = 8ull * n_rs;                            // 8 B per coverage event at a candidate position (+ call events, + 44*rows)
+}
+
+// plan the open shard (the stages of mkp_plan.hpp, in their order), keep the plan's scalars for the launches, upload everything
+void make_resident(mkp_ctx* c) {
+  const auto t0 = std::chrono::steady_clock::now();
+  PlanTrace trace(PlanTrace::wanted(), false, t0);   // host planning stages on stderr
+  ShardPlan pl;
+  const PlanInput in{c->shard, c->tables, c->packer.layouts, c->caller, c->has_focus, c->focus, c->combos, c->iv_starts, c->hemi, c->hemi_off,
+      c->hemi_iv, c->cfg.tile_positions, c->partition_tags.size(), c->wplan, PlanKnobs::from_env()};
+  find_shared_names(in, pl);
+  trace.lap("duplicate-name check");
+  build_params(in, pl);
+  trace.lap("caller tables + params");
+  class_ids(c->shard, c->tables, &pl.class_list, pl.n_class, true);
+  trace.lap("decode classes");
+  flag_sum_errors(in, pl);
+  trace.lap("probability-sum test");
+  layout_event_slices(in, pl);
+  trace.lap("decode classes + event slices");
+  check_sorted_and_depth(in, pl);
+  trace.lap(pl.wide ? "sortedness + depth guard (wide tallies)" : "sortedness + depth guard (16-bit tallies)");
+  plan_tiles(in, pl);
+  trace.lap("slot bitmap + tiles");
+  candidate_reads(in, pl);
+  plan_name_owners(in, pl, [c](uint32_t r) {   // the one device touch of planning: a member's CIGAR of a device-packed shard
+    const MkpReadHdr& h = c->shard.hdr[r]; std::vector<uint32_t> cg(h.n_cigar);
+    if (h.n_cigar) { hip_check(hipSetDevice(c->device), "hipSetDevice");
+      d2h_copy(cg.data(), c->d_cigar.as<uint32_t>() + h.cigar_off, (size_t)h.n_cigar * 4, c->stream); }
+    return cg; });
+  if (!pl.dup_groups.empty()) trace.lap("records sharing a name: owners per interval");
+  split_fused_and_cover(in, pl);
+  trace.lap("candidate reads per tile");
+  memcpy(&c->prm, &pl.prm, sizeof(c->prm));
+  if (c->hemi) memcpy(c->hemi_codes, pl.hemi_codes, sizeof(c->hemi_codes));
+  memcpy(c->n_class, pl.n_class, sizeof(c->n_class)); memcpy(c->n_slot_class, pl.n_slot_class, sizeof(c->n_slot_class));
+  c->read_ids_dec_off = pl.read_ids_dec_off; c->wide = pl.wide; c->slot_mode = pl.stream; c->n_dup_cons = (uint32_t)pl.dup_cons.size();
+  c->lds_bytes = pl.lds_bytes; c->n_tiles = pl.n_tiles; c->n_slots_total = pl.n_slots_total; c->cov_bytes = pl.cov_bytes;
+  c->stats.pack_ms += ms_since(t0);
+  const auto t1 = std::chrono::steady_clock::now();
+  build_work_records(in, pl);   // (counted in the upload step, as the plane they address is)
+  if (pl.stream) c->plane_bytes = pl.plane_bytes;
+  upload_plan(c, pl, trace);
+  c->stats.h2d_ms = ms_since(t1);
+  c->resident = true; c->resident_hemi = c->hemi;
+  account_bytes(c, pl);
 }
 
 void run_kernels(mkp_ctx* c, bool time_kernels) {
@@ -834,10 +216,7 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
     c->row_cap = std::max<uint64_t>(1u << 16, std::min<uint64_t>(guess * c->key_passes.size(), 1ull << 28));
   }
   const bool trace = time_kernels && getenv("MKP_TRACE_PLAN") != nullptr;
-  auto t_rk = std::chrono::steady_clock::now();
-  auto lap = [&](const char* what) { if (trace) { auto now = std::chrono::steady_clock::now();
-      fprintf(stderr, "[mkpileup plan]   kernels: %-20s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_rk).count()); t_rk = now;
-    } };
+  PlanTrace marks(trace, true);
   const uint32_t n_runs = c->n_tiles * (uint32_t)c->key_passes.size();   // row runs: one per (key pass, tile), ordered by key then genome
   // (slot pipeline: row_off holds the runs' 64-bit look-back words behind a 64-byte header — the pass's cursor / total / error words — so that
   //  ONE memset readies a pass: between two kernels of a 1 ms step every extra fill or copy is a 5-10 us launch of its own)
@@ -846,9 +225,9 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
   for (;;) {
     P.row_capacity = (uint32_t)c->row_cap;
     c->rows_src = carve_rows(c->d_rows_src, c->row_cap); c->rows_dst = carve_rows(c->d_rows_dst, c->row_cap);
-    lap("row buffers");
+    marks.lap("row buffers");
     // (trace runs: what the stream still had queued shows up here, not in the kernels' sync)
-    if (trace) { hip_check(hipStreamSynchronize(c->stream), "sync"); lap("stream drained"); }
+    if (trace) { hip_check(hipStreamSynchronize(c->stream), "sync"); marks.lap("stream drained"); }
     // [0] row cursor / tile ticket, [1] total rows, [2] error bits; the look-back words (slot pipeline) or row offsets start at +16 dwords
     uint32_t* misc = c->d_tile_row_off.as<uint32_t>();
     uint32_t* row_off = misc + 16;
@@ -912,15 +291,15 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
     else hip_check(mkp_launch_gather(c->stream, row_off, c->d_tile_row_cnt.as<uint32_t>(), c->d_tile_dst.as<uint32_t>(), n_runs, misc + 1,
         &c->rows_src, &c->rows_dst), "gather launch");
     if (time_kernels && !c->slot_mode) hip_check(hipEventRecord(c->ev[3], c->stream), "event");
-    lap("launches");
-    if (trace && time_kernels) { hip_check(hipEventSynchronize(c->ev[0]), "sync"); lap("first event reached");
-      hip_check(hipEventSynchronize(c->ev[2]), "sync"); lap("kernels done (event)"); }
+    marks.lap("launches");
+    if (trace && time_kernels) { hip_check(hipEventSynchronize(c->ev[0]), "sync"); marks.lap("first event reached");
+      hip_check(hipEventSynchronize(c->ev[2]), "sync"); marks.lap("kernels done (event)"); }
     if (!c->h_words && hipHostMalloc(reinterpret_cast<void**>(&c->h_words), 64, hipHostMallocDefault) != hipSuccess) { c->h_words = nullptr;
       throw Error(MKP_E_NOMEM, "hipHostMalloc failed"); }
     uint32_t* h = c->h_words;
     hip_check(hipMemcpyAsync(h, misc, 16, hipMemcpyDeviceToHost, c->stream), "D2H");
     hip_check(hipStreamSynchronize(c->stream), "kernel sync");
-    lap("sync");
+    marks.lap("sync");
     if (h[2] & 2u) { c->row_cap *= 2; if (c->row_cap > (1ull << 31)) throw Error(MKP_E_NOMEM, "row buffer would exceed 2^31 rows"); continue; }
     if (h[2] & 1u) throw Error(MKP_E_DEVICE, "internal: event segment overflow");
     if (h[2] & ERR_DUP_MIXED) throw Error(MKP_E_UNSUPPORTED,
@@ -1152,8 +531,8 @@ int mkp_internal_shard_preplan(mkp_ctx* c) {
   return guarded(c, [&]() {
     if (!c->shard_open) throw Error(MKP_E_INVALID, "mkp_shard_begin first");
     c->wplan.valid = false;
-    if (!stream_pipeline(c, false)) return;
-    window_slots(c, false, true, c->wplan.slotbm, c->wplan.wpfx, c->wplan.slot_pos);
+    if (!stream_pipeline(c->has_focus, false)) return;
+    window_slots(c->shard, c->focus.data(), c->combos, false, true, c->wplan.slotbm, c->wplan.wpfx, c->wplan.slot_pos);
     hip_check(hipSetDevice(c->device), "hipSetDevice");
     upload(c->d_focus, c->focus); upload(c->d_combos, c->combos); upload(c->d_slotbm, c->wplan.slotbm); upload(c->d_slot_pos, c->wplan.slot_pos);
     c->wplan.valid = true;
@@ -1231,17 +610,24 @@ void adopt_layouts(mkp_ctx* c, DevShard* sh) {
     h.layout = map[h.layout]; }
   sh->layouts_adopted = true;
 }
+// the seven arrays the device ingest packs in HBM change hands between the context and a DevShard
+void swap_packed_arrays(mkp_ctx* c, DevShard* sh) {
+  std::swap(c->d_cigar, sh->d_cigar); std::swap(c->d_cigar16, sh->d_cigar16); std::swap(c->d_chunk, sh->d_chunk); std::swap(c->d_seq, sh->d_seq);
+  std::swap(c->d_tagref, sh->d_tagref); std::swap(c->d_ranks, sh->d_ranks); std::swap(c->d_ml, sh->d_ml);
+}
+void ensure_packed_arrays(mkp_ctx* c) {   // (an empty shard: the kernels still take valid pointers)
+  for (DevBuf* b : {&c->d_cigar, &c->d_cigar16, &c->d_chunk, &c->d_seq, &c->d_tagref, &c->d_ranks, &c->d_ml}) b->ensure(16);
+}
 }  // namespace
 int mkp_internal_sample_bind(mkp_ctx* c, DevShard* sh) {
   if (!c || !sh) return MKP_E_INVALID;
   return guarded(c, [&]() {
     if (!sh->bound) adopt_layouts(c, sh);
     std::swap(c->shard, sh->S);
-    std::swap(c->d_cigar, sh->d_cigar); std::swap(c->d_cigar16, sh->d_cigar16); std::swap(c->d_chunk, sh->d_chunk); std::swap(c->d_seq, sh->d_seq); std::swap(c->d_tagref, sh->d_tagref);
-      std::swap(c->d_ranks, sh->d_ranks); std::swap(c->d_ml, sh->d_ml);
+    swap_packed_arrays(c, sh);
     sh->bound = !sh->bound;
     c->shard_open = sh->bound; c->resident = false; c->wplan.valid = false;
-    if (sh->bound) for (DevBuf* b : {&c->d_cigar, &c->d_cigar16, &c->d_chunk, &c->d_seq, &c->d_tagref, &c->d_ranks, &c->d_ml}) b->ensure(16);
+    if (sh->bound) ensure_packed_arrays(c);
   });
 }
 // Device ingest hand-over (mkp_ingest_host.cpp): the open shard takes the records the device packed.  Their big arrays are swapped into
@@ -1258,11 +644,8 @@ int mkp_internal_shard_attach(mkp_ctx* c, DevShard* sh) {
     adopt_layouts(c, sh);
     const int32_t tid = c->shard.tid, ws = c->shard.win_start, we = c->shard.win_end;
     c->shard = std::move(sh->S); c->shard.tid = tid; c->shard.win_start = ws; c->shard.win_end = we; c->shard.dev_packed = true;
-    std::swap(c->d_cigar, sh->d_cigar); std::swap(c->d_cigar16, sh->d_cigar16); std::swap(c->d_chunk, sh->d_chunk); std::swap(c->d_seq, sh->d_seq); std::swap(c->d_tagref, sh->d_tagref);
-      std::swap(c->d_ranks, sh->d_ranks);
-        std::swap(c->d_ml, sh->d_ml);
-    // (an empty shard: the kernels still take valid pointers)
-    for (DevBuf* b : {&c->d_cigar, &c->d_cigar16, &c->d_chunk, &c->d_seq, &c->d_tagref, &c->d_ranks, &c->d_ml}) b->ensure(16);
+    swap_packed_arrays(c, sh);
+    ensure_packed_arrays(c);
     c->resident = false; c->row_cap = 0;
     c->stats.pack_ms += ms_since(t0);
   });
@@ -1275,16 +658,13 @@ int mkp_shard_run(mkp_ctx* c, mkp_rows* out) {
     if (!c->shard_open) throw Error(MKP_E_INVALID, "mkp_shard_begin first");
     if (!c->caller_set) throw Error(MKP_E_INVALID, "mkp_set_caller first");
     c->hemi = false;
-    const bool trace = getenv("MKP_TRACE_PLAN") != nullptr;
-    auto t0 = std::chrono::steady_clock::now();
-    auto lap = [&, last = t0](const char* what) mutable { if (trace) { auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "[mkpileup plan] %-28s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - last).count()); last = now; } };
+    PlanTrace trace(PlanTrace::wanted());
     if (!c->resident || c->resident_hemi) { c->row_cap = 0; make_resident(c); }
-    lap("run: make_resident");
+    trace.lap("run: make_resident");
     run_kernels(c, true);
-    lap("run: kernels");
+    trace.lap("run: kernels");
     fetch_rows(c, out);
-    lap("run: fetch rows");
+    trace.lap("run: fetch rows");
     if (c->slot_mode) {   // n_events = call features + events of the reads the event decoders took
       c->stats.alg_bytes_pileup += 44ull * c->stats.n_rows;
       c->stats.alg_bytes_agg_survey += 44ull * c->stats.n_rows;

@@ -182,9 +182,7 @@ struct mkp_ctx {
   bool extract_mode = false;   // `extract calls`: the sampling kernels emit one record per call (forward position, classes, call_prob)
   bool summary_mode = false; mkp::DevBuf d_summary; std::vector<uint8_t> h_sum_base; std::vector<uint32_t> h_sum_code;
     std::vector<uint64_t> h_sum_pass, h_sum_fail;
-  // the read-independent part of a focus shard's plan (slot bitmap, its running popcount, the slot positions, their uploads), made ahead
-  // of the reads by mkp_internal_shard_preplan while the device ingest of the same shard is still running
-  struct WindowPlan { bool valid = false; std::vector<uint32_t> slotbm, wpfx, slot_pos; } wplan;
+  mkp::WindowPlan wplan;   // (mkp_pack.hpp; its arrays are uploaded when it is made)
   // What the sessions that reduce rows already in HBM share (region statistics, localize): the regions uploaded once and grouped by contig, the
   // slots' codes and error word in HBM between the calls, the per-call row ranges, the upload buffer of *_add_rows and the kernel timing
   struct RowTable {

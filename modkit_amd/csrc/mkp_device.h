@@ -51,7 +51,7 @@ struct MkpReadHdr {
   uint32_t event_cap;
   uint32_t chunk_off;   // index into chunk_pfx[]: one {query offset, reference offset} per 64 CIGAR ops of this read
   // focus runs (slot pipeline, mkp_slots.hip): the read's focus positions ("slots") are the global slots [gs0, gs0 + n_sl) of
-  // slot_pos[]; its features go to cov[cov_off .. cov_off + n_sl) (4-byte aligned).  Filled by the host planner (make_resident).
+  // slot_pos[]; its features go to cov[cov_off .. cov_off + n_sl) (4-byte aligned).  Filled by the host planner (plan_slot_tiles, mkp_plan.hpp).
   uint32_t gs0, n_sl, cov_off;
   // index into cigar16[] (a multiple of 4; straight from the device ingest, bit 0 carries the probability-sum test until the host moves it
   // into dev_sum2).  `pad` is the field's name from before it had a use: the ingest test harness still reads it under that name.
@@ -254,7 +254,7 @@ struct MkpWork {             // 64 B
 // The reference keeps ONE cache entry per name and interval (ReadCache, read_cache.rs:24-43): the record asked about first — the first focus
 // column of the interval that holds a record of the name, file order within a column — is parsed; every later record of the name is answered
 // from THAT record's call map, looked up by reference position and the asking record's own read base (get_mod_call, 232-297).  The host planner
-// works out, per interval, which record owns the name (make_resident); a record that is answered from another one in some interval is a
+// works out, per interval, which record owns the name (plan_name_owners, mkp_plan.hpp); a record that is answered from another one in some interval is a
 // CONSUMER: mkp_dup_events rebuilds its event list — its own events where it owns the name, the owner's events elsewhere, kept where its own
 // alignment shows the call's base — and the accumulate kernels then take that list as the record's own.
 // positions [p_lo, p_hi) of one consumer, ascending

@@ -234,7 +234,7 @@ struct ShardHost {
   std::vector<std::pair<int32_t, int32_t>> extra_spans;
   // Device ingest (mkp_ingest.hip): cigar / chunk_pfx / seq / ranks / ml were written in HBM and never existed on the host; hdr, tagref
   // (MKP_MAX_TAGS entries per read, pad = "same delta list as the tag before") and name_hash are the digest the planner works from.
-  // per read: the probability-sum test of a two-tag read (what make_resident computes from S.ml otherwise)
+  // per read: the probability-sum test of a two-tag read (what the planner computes from S.ml otherwise: flag_sum_errors, mkp_plan.hpp)
   bool dev_packed = false; std::vector<uint8_t> dev_sum2;
   uint64_t dev_n_ranks = 0, dev_n_ml = 0;
   std::vector<uint64_t> dev_name_hash2; std::vector<uint32_t> dev_win_idx;   // second name hash; place in the window (file order)
@@ -285,6 +285,10 @@ struct ShardHost {
                dev_packed = false; dev_sum2.clear(); dev_n_ranks = dev_n_ml = 0; dev_name_hash2.clear(); dev_win_idx.clear(); so_hdr.clear();
                  so_name_hash.clear(); so_name_hash2.clear(); so_win_idx.clear(); }
 };
+
+// the read-independent part of a focus shard's plan (slot bitmap, its running popcount, the slot positions), made ahead of the reads by
+// mkp_internal_shard_preplan while the device ingest of the same shard is still running; the planner (mkp_plan.hpp) takes it over
+struct WindowPlan { bool valid = false; std::vector<uint32_t> slotbm, wpfx, slot_pos; };
 
 class Packer {
  public:

@@ -6,7 +6,7 @@ reference that tile it without overlapping.  A forward read's calls sit on the C
 same bases, and its calls (the C's of the read's forward sequence) sit on the G of each unit (- strand), last call first.  Every C of a
 read is listed (MM deltas of 0), so no call is inferred.
 
-Layouts and the decode class each lands in (class_ids, mkp_api.cpp:97-131; the layout is `fast` when all its tags have one base and
+Layouts and the decode class each lands in (class_ids, mkp_plan.hpp; the layout is `fast` when all its tags have one base and
 strand and no code repeats, mkp_pack.hpp:117-121):
     m        C+m?                 one explicit tag                   -> class 0 (SPARSE, one tag)
     hm       C+hm?                one explicit tag, two codes        -> class 0

@@ -20,7 +20,7 @@ THRESHOLD = cases.THRESHOLD
 TILE = cases.TILE
 COMP = {"A": "T", "C": "G", "G": "C", "T": "A"}
 
-# name: (base of the own-strand group, codes of each tag of a group, decode class).  The class is what class_ids (mkp_api.cpp) gives a
+# name: (base of the own-strand group, codes of each tag of a group, decode class).  The class is what class_ids (mkp_plan.hpp) gives a
 # read of that layout under pileup-hemi: 5 = two groups of one tag each, 6 = two groups of two tags over one rank list each (both decoded
 # per group by a SPARSE wave and interleaved by mkp_merge_duplex), 4 = the general decoder (here: three tags per group, more than the
 # duplex classifier takes).

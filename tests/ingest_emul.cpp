@@ -289,7 +289,7 @@ int main(int argc, char** argv) {
             if ((a.pad != 0) != same) return fail("same-list flag", j, a.pad, same);
             calls += b.n; ml_used += mb;
           }
-          bool sum_bad = false;   // the planner's probability-sum test (make_resident, mkp_api.cpp)
+          bool sum_bad = false;   // the planner's probability-sum test (flag_sum_errors, mkp_plan.hpp)
           if (h.n_tags == 2 && tagref[d.tag_off + 1].pad) {
             const MkpTagRef &t0 = S.tagref[h.tag_off], &t1 = S.tagref[h.tag_off + 1];
               const uint32_t nc0 = (uint32_t)Lh.tags[0].codes.size(), nc1 = (uint32_t)Lh.tags[1].codes.size();

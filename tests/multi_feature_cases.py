@@ -55,7 +55,7 @@ PLAIN = ("m", "h_m")
 
 
 def decode_class(tags, rank_lists):
-    """The decode class class_ids (mkp_api.cpp) gives a good read of these tags when a shard is made resident, for `pileup` and for
+    """The decode class class_ids (mkp_plan.hpp) gives a good read of these tags when a shard is made resident, for `pileup` and for
     `pileup-hemi` alike (only the threshold sampler classifies without the duplex classes); restated from its rules and those of the
     layout tables (mkp_pack.hpp).  FAST: every tag on one (strand, base) that is not `N`, no code listed twice; with at most two tags it
     is class 0 / 1 (one / two tags) when every tag is explicit and two tags share one rank list, else class 2 / 3.  Duplex: a leading

@@ -1,5 +1,5 @@
 """GPU: columns deeper than 65 535 records.  The packed tallies hold a strand's count in 16 bits; a shard whose deepest column may exceed that
-runs the wide-tally accumulate kernels (depth_guard, mkp_api.cpp) and must equal the oracle byte for byte.  pileup-hemi has no wide kernel
+runs the wide-tally accumulate kernels (depth_guard, mkp_plan.hpp) and must equal the oracle byte for byte.  pileup-hemi has no wide kernel
 and refuses such a shard loudly."""
 import os
 import subprocess

@@ -1,5 +1,5 @@
 """GPU: `--max-depth` (htslib's maxcnt, pileup/mod.rs:755-759).  The device path does not drop records per (record, interval); it decides
-exactly whether htslib WOULD drop any (depth_guard, mkp_api.cpp) — if not, it runs and equals the oracle at any depth; if so, it refuses
+exactly whether htslib WOULD drop any (depth_guard, mkp_plan.hpp) — if not, it runs and equals the oracle at any depth; if so, it refuses
 loudly.  Rounds 1-5 refused every column deeper than the cap, although htslib only ever refuses records that share their start with the
 record buffered last."""
 import subprocess
