@@ -31,7 +31,8 @@ hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_
     const uint32_t* /*cover read ids*/,
     uint32_t, const uint32_t*, const uint8_t*, const MkpTagRef*,
                             const uint32_t*, const uint8_t*, const MkpLayout*, const MkpFusedDesc*, const MkpRunParams*,
-                                const uint32_t* /*slot positions*/, uint8_t* /*feature stream*/, MkpVisit*, MkpEvent*, MkpReadOut*, uint32_t*);
+                                const uint32_t* /*slot positions*/, const MkpSlotEnt* /*slot-entry lists*/, uint8_t* /*feature stream*/, MkpVisit*, MkpEvent*,
+                                MkpReadOut*, uint32_t*);
 hipError_t mkp_launch_call_plane(hipStream_t, MkpWork*, uint32_t, const uint8_t* /*SEQ*/, const uint32_t* /*ranks*/, const MkpFusedDesc*,
     void* /*plane*/, unsigned long long* /*SEQ bytes the decoder reads of MKP_RF_SEQN reads*/);
 hipError_t mkp_stream_set_lds(uint32_t bytes);
@@ -105,7 +106,7 @@ void upload_plan(mkp_ctx* c, const ShardPlan& pl, PlanTrace& trace) {
   c->d_misc.ensure(64);
   trace.lap("upload: focus + event buffers");
   if (pl.stream) {
-    if (!pl.preplanned) upload(c->d_slot_pos, pl.slot_pos);
+    if (!pl.preplanned) { upload(c->d_slot_pos, pl.slot_pos); upload(c->d_slot_ent, pl.lists.ent); }
     upload(c->d_stiles, pl.stiles);
     const uint32_t nf = c->n_slot_class[0];   // the fused decoder takes work records, the cover kernel keeps a read-id list
     c->d_plane.ensure(c->plane_bytes + 16);   // + the builder's count of the SEQ bytes the decoder reads (MKP_RF_SEQN reads only) behind the entries
@@ -118,6 +119,10 @@ void upload_plan(mkp_ctx* c, const ShardPlan& pl, PlanTrace& trace) {
     hip_check(mkp_launch_call_plane(c->stream, c->d_work.as<MkpWork>(), nf, c->d_seq.as<uint8_t>(), c->d_ranks.as<uint32_t>(),
         c->d_fdesc.as<MkpFusedDesc>(), c->d_plane.p, d_seqn_bytes), "call plane launch");
     c->d_cov.ensure(c->cov_bytes + 256); c->d_visits.ensure(std::max<size_t>(S.hdr.size(), 1) * sizeof(MkpVisit));
+    // A fused read writes the bytes of the slots it decodes — the same ones on every pass — and the buffer is reused from shard to shard:
+    // the whole stream starts as BLANK ("in the column, no feature": the stream kernel skips it and it opens no ref-skip boundary), so that
+    // the bytes no read writes tally nothing, on this pass and on every re-launch.
+    hip_check(hipMemsetAsync(c->d_cov.p, MKP_FB_BLANK, c->cov_bytes + 256, c->stream), "feature stream prefill");
     hip_check(mkp_stream_set_lds(c->lds_bytes), "hipFuncSetAttribute(max dynamic LDS, stream)");
   }
   if (c->hemi) upload(c->d_hemi_iv, c->hemi_iv);
@@ -201,6 +206,8 @@ void make_resident(mkp_ctx* c) {
   const auto t1 = std::chrono::steady_clock::now();
   build_work_records(in, pl);   // (counted in the upload step, as the plane they address is)
   if (pl.stream) c->plane_bytes = pl.plane_bytes;
+  if (trace.on && pl.fused_slots) fprintf(stderr, "[mkpileup plan] fused reads decode %llu of the %llu slots they span (%.3f)\n",
+      (unsigned long long)pl.fused_entries, (unsigned long long)pl.fused_slots, (double)pl.fused_entries / (double)pl.fused_slots);
   upload_plan(c, pl, trace);
   c->stats.h2d_ms = ms_since(t1);
   c->resident = true; c->resident_hemi = c->hemi;
@@ -265,7 +272,8 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
         c->d_slot_ids.as<uint32_t>(), c->n_slot_class[2],
                                               c->d_cigar.as<uint32_t>(), c->d_seq.as<uint8_t>(), c->d_tagref.as<MkpTagRef>(),
                                               c->d_ranks.as<uint32_t>(), c->d_ml.as<uint8_t>(), c->d_layouts.as<MkpLayout>(),
-                                                  c->d_fdesc.as<MkpFusedDesc>(), &P, c->d_slot_pos.as<uint32_t>(), c->d_cov.as<uint8_t>(),
+                                                  c->d_fdesc.as<MkpFusedDesc>(), &P, c->d_slot_pos.as<uint32_t>(), c->d_slot_ent.as<MkpSlotEnt>(),
+                                                  c->d_cov.as<uint8_t>(),
                                                   c->d_visits.as<MkpVisit>(),
                                               c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>(), misc + 2), "slot decode launch");
     if (time_kernels) hip_check(hipEventRecord(c->ev[1], c->stream), "event");
@@ -462,7 +470,8 @@ void mkp_ctx_destroy(mkp_ctx* c) {
       &c->d_focus, &c->d_combos, &c->d_tiles,
                     &c->d_slotbm, &c->d_prm, &c->d_read_ids, &c->d_chunk, &c->d_store, &c->d_hist0, &c->d_hist1, &c->d_sample_cursor, &c->d_take,
                         &c->d_tile_row_off, &c->d_tile_row_cnt, &c->d_tile_dst, &c->d_misc, &c->d_rows_src, &c->d_rows_dst, &c->d_hemi_iv,
-                        &c->d_slot_pos, &c->d_cov, &c->d_visits, &c->d_stiles, &c->d_slot_ids, &c->d_fdesc, &c->d_work, &c->d_plane, &c->d_zin, &c->d_zout,
+                        &c->d_slot_pos, &c->d_slot_ent, &c->d_cov, &c->d_visits, &c->d_stiles, &c->d_slot_ids, &c->d_fdesc, &c->d_work, &c->d_plane,
+                        &c->d_zin, &c->d_zout,
                         &c->d_zblk, &c->d_zstat, &c->d_summary, &c->d_bedmask, &c->d_hist64, &c->rstats.d_out, &c->rstats.d_seen,
                         &c->rstats.d_cnt, &c->rstats.d_off, &c->loc.d_tab}) b->release();
   for (mkp_ctx::RowTable* t : {static_cast<mkp_ctx::RowTable*>(&c->rstats), static_cast<mkp_ctx::RowTable*>(&c->loc)}) {
@@ -532,9 +541,10 @@ int mkp_internal_shard_preplan(mkp_ctx* c) {
     if (!c->shard_open) throw Error(MKP_E_INVALID, "mkp_shard_begin first");
     c->wplan.valid = false;
     if (!stream_pipeline(c->has_focus, false)) return;
-    window_slots(c->shard, c->focus.data(), c->combos, false, true, c->wplan.slotbm, c->wplan.wpfx, c->wplan.slot_pos);
+    window_slots(c->shard, c->focus.data(), c->combos, false, true, c->wplan.slotbm, c->wplan.wpfx, c->wplan.slot_pos, c->wplan.lists);
     hip_check(hipSetDevice(c->device), "hipSetDevice");
     upload(c->d_focus, c->focus); upload(c->d_combos, c->combos); upload(c->d_slotbm, c->wplan.slotbm); upload(c->d_slot_pos, c->wplan.slot_pos);
+    upload(c->d_slot_ent, c->wplan.lists.ent);
     c->wplan.valid = true;
     // a fresh context's first shard: page-locking the row arena costs ~25 ms per 100 MB — here it hides behind the ingest (the caller is
     // about to wait for it); two rows per focus position is what a two-code run can produce at most per strand rule

@@ -211,6 +211,8 @@ struct MkpPlaneEnt {         // 16 B: one global_load_dwordx4 per slot
   uint32_t before;           // listed calls at the bases before 32 w
 };
 #define MKP_STREAM_ROWMAP_WORDS 2048u   // mkp_pileup_stream: rows of a tile placed per emission round (a dword of LDS each)
+// one entry of the slot-entry lists (`all`, `plus`, `minus`, concatenated: window_slots, mkp_plan.hpp): the decoder's 8-byte load per slot
+struct MkpSlotEnt { uint32_t pos, g; };   // reference position, global slot index (its place in slot_pos[])
 #define MKP_FB_NONE 0xffu    // the read is not in this column (ref-skip)
 #define MKP_FB_BLANK 0xfeu   // in the column, no feature (non-ACGT base: pileup/mod.rs:864-874)
 struct MkpVisit {            // 32 B, written by the decode / cover kernels, read by mkp_pileup_stream
@@ -243,12 +245,15 @@ struct MkpFusedDesc {        // 64 B
 static_assert(sizeof(MkpFusedDesc) == 64, "MkpFusedDesc is one 64-byte scalar load");
 // one read as mkp_decode_slots* takes it: the header and tag fields the kernel needs, in launch order (longest reads first), so that a
 // wave starts from ONE 64-byte scalar load instead of the chain read id -> header -> tag table
-struct MkpWork {             // 64 B
+struct MkpWork {             // 72 B
   // cigar_off: index into cigar16[] (the header's cigar16_off), into cigar[] for a read with MKP_RF_CIGW
   int32_t ref_start; uint32_t l_seq, n_cigar, cigar_off, seq_off, flags, gs0, n_sl, cov_off;
   uint16_t n_tags, layout;
   uint32_t rank_off, n_calls, ml_off0, ml_off1;   // the shared rank list, the tags' ML bytes
   uint32_t rid, pad;                              // pad: the read's first plane entry (MKP_PLANE_WORDS(l_seq) of them)
+  // the slots the decoder visits: slot_ent[ent_off .. ent_off + n_ent), the read's run of the slot-entry list of its own strand — or of
+  // the list of every slot (n_ent == n_sl) when it needs both tally strands or its strand's list is no shorter (plan_read_entries, mkp_plan.hpp)
+  uint32_t ent_off, n_ent;
 };
 // Records that share a read NAME inside one interval of the reference's grid (unmarked duplicates, mates, split reads that kept the primary flag).
 // The reference keeps ONE cache entry per name and interval (ReadCache, read_cache.rs:24-43): the record asked about first — the first focus
@@ -295,6 +300,6 @@ struct MkpStatsRegion { uint32_t start, end; uint32_t rule /* 1 '+', 2 '-', 3 bo
 #define MKP_LOC_MAX_WINDOW 100000u
 struct MkpLocRegion { uint32_t ws, we, anchor; uint32_t rules /* fetch rule | region rule << 8, each 1 '+', 2 '-', 3 both */; };
 #ifdef __cplusplus
-static_assert(sizeof(MkpWork) == 64, "work record is 16 dwords");
+static_assert(sizeof(MkpWork) == 72 && sizeof(MkpSlotEnt) == 8, "work record is 18 dwords");
 static_assert(sizeof(MkpFusedDesc) == 64 && sizeof(MkpVisit) == 32 && sizeof(MkpPlaneEnt) == 16, "slot pipeline records");
 #endif

@@ -288,7 +288,17 @@ struct ShardHost {
 
 // the read-independent part of a focus shard's plan (slot bitmap, its running popcount, the slot positions), made ahead of the reads by
 // mkp_internal_shard_preplan while the device ingest of the same shard is still running; the planner (mkp_plan.hpp) takes it over
-struct WindowPlan { bool valid = false; std::vector<uint32_t> slotbm, wpfx, slot_pos; };
+// The slot-entry lists of a focus window (slot pipeline): `all` = every slot, `plus` / `minus` = the slots whose rule has bit 0 / bit 1, in
+// genome order, concatenated in that order into one array of {position, global slot index}.  rank[s][g] = entries of strand list s in
+// front of global slot g (n_all + 1 values): the run of the global slots [a, b) in list s is [rank[s][a], rank[s][b]).
+struct SlotLists {
+  PodVec<MkpSlotEnt> ent; PodVec<uint32_t> rank[2]; uint32_t n_all = 0, n_strand[2] = {0, 0};   // (every element is written by window_slots)
+  uint32_t list_off(int list) const { return list == 0 ? 0u : list == 1 ? n_all : n_all + n_strand[0]; }   // 0 all, 1 plus, 2 minus
+  void clear() { ent.clear(); rank[0].clear(); rank[1].clear(); n_all = n_strand[0] = n_strand[1] = 0; }
+  void swap(SlotLists& o) { ent.swap(o.ent); rank[0].swap(o.rank[0]); rank[1].swap(o.rank[1]); std::swap(n_all, o.n_all);
+    std::swap(n_strand[0], o.n_strand[0]); std::swap(n_strand[1], o.n_strand[1]); }
+};
+struct WindowPlan { bool valid = false; std::vector<uint32_t> slotbm, wpfx, slot_pos; SlotLists lists; };
 
 class Packer {
  public:

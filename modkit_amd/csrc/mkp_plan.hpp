@@ -40,9 +40,11 @@ struct PlanKnobs {
   bool fused_off = false;          // MKP_FUSED=0: every read takes its class's event decoder
   bool has_stream_tile = false; uint32_t stream_tile = 0;   // MKP_STREAM_TILE: slots per tile of the slot pipeline (experiments)
   uint32_t debug_skip = 0;         // MKP_DEBUG_SKIP (MKP_DEBUG builds only)
+  bool strand_slots_off = false;   // MKP_STRAND_SLOTS=0: every fused read decodes all of its slots, not only those of its own strand
   static PlanKnobs from_env() {
     PlanKnobs k;
     if (const char* e = getenv("MKP_FUSED")) k.fused_off = !strcmp(e, "0");
+    if (const char* e = getenv("MKP_STRAND_SLOTS")) k.strand_slots_off = !strcmp(e, "0");
     if (const char* e = getenv("MKP_STREAM_TILE")) { k.has_stream_tile = true; k.stream_tile = (uint32_t)strtoul(e, nullptr, 10); }
 #ifdef MKP_DEBUG
     if (const char* e = getenv("MKP_DEBUG_SKIP")) k.debug_skip = (uint32_t)strtoul(e, nullptr, 0);
@@ -261,7 +263,7 @@ struct SlotRank {
 
 // slot bitmap of a focus window, its running popcount per word and — slot pipeline — the slot positions.  Depends on the focus bytes only.
 inline void window_slots(const ShardHost& S, const uint8_t* fz, const std::vector<mkp_motif_combo>& combos, bool hemi, bool stream,
-                         std::vector<uint32_t>& slotbm, std::vector<uint32_t>& wpfx, std::vector<uint32_t>& slot_pos) {
+                         std::vector<uint32_t>& slotbm, std::vector<uint32_t>& wpfx, std::vector<uint32_t>& slot_pos, SlotLists& lists) {
   const int64_t win = (int64_t)S.win_end - (int64_t)S.win_start;
   const size_t nwords = SlotRank::words_for(win);
   slotbm.assign(nwords, 0);
@@ -292,6 +294,35 @@ inline void window_slots(const ShardHost& S, const uint8_t* fz, const std::vecto
           slot_pos[at++] = (uint32_t)((int64_t)(w * 32 + (size_t)__builtin_ctz(bits)) - MKP_SLOTBM_MARGIN + S.win_start); }
     });
   }
+  // The slot-entry lists (SlotLists, mkp_pack.hpp), from the same focus bytes: a row of strand s is emitted only where the rule has bit s
+  // (E1 of pileup_stream_body, mkp_slots.hip), so a read that feeds one tally strand is only ever asked about that strand's slots.  Blocks
+  // of bitmap words count their strand slots on all cores, a short serial pass sums the blocks, then every block writes its entries.
+  lists.clear();
+  if (stream) {
+    const uint32_t n_all = wpfx[nwords];
+    const size_t blk = (size_t)1 << 15, nblk = (nwords + blk - 1) / blk;
+    std::vector<uint32_t> bs[2]; bs[0].assign(nblk + 1, 0); bs[1].assign(nblk + 1, 0);
+    auto rule_at = [&](size_t w, uint32_t bit) { return (uint32_t)fz[w * 32 + bit - MKP_SLOTBM_MARGIN] & 3u; };   // (a set bit lies inside the window)
+    host_parallel(nblk, 1, [&](size_t lo, size_t hi) { for (size_t b = lo; b < hi; b++) { uint32_t t0 = 0, t1 = 0;
+        for (size_t w = b * blk; w < std::min(nwords, (b + 1) * blk); w++)
+          for (uint32_t bits = slotbm[w]; bits; bits &= bits - 1u) { const uint32_t r = rule_at(w, (uint32_t)__builtin_ctz(bits)); t0 += r & 1u; t1 += r >> 1; }
+        bs[0][b + 1] = t0; bs[1][b + 1] = t1; } });
+    for (size_t b = 0; b < nblk; b++) { bs[0][b + 1] += bs[0][b]; bs[1][b + 1] += bs[1][b]; }
+    lists.n_all = n_all; lists.n_strand[0] = bs[0][nblk]; lists.n_strand[1] = bs[1][nblk];
+    lists.ent.resize((size_t)n_all + lists.n_strand[0] + lists.n_strand[1]);
+    lists.rank[0].resize((size_t)n_all + 1); lists.rank[1].resize((size_t)n_all + 1);
+    lists.rank[0][n_all] = lists.n_strand[0]; lists.rank[1][n_all] = lists.n_strand[1];
+    MkpSlotEnt* const e_all = lists.ent.data(); MkpSlotEnt* const e_str[2] = {e_all + lists.list_off(1), e_all + lists.list_off(2)};
+    host_parallel(nblk, 1, [&](size_t lo, size_t hi) { for (size_t b = lo; b < hi; b++) { uint32_t at[2] = {bs[0][b], bs[1][b]};
+        for (size_t w = b * blk; w < std::min(nwords, (b + 1) * blk); w++) { uint32_t g = wpfx[w];
+          for (uint32_t bits = slotbm[w]; bits; bits &= bits - 1u, g++) {
+            const uint32_t bit = (uint32_t)__builtin_ctz(bits), r = rule_at(w, bit);
+            const MkpSlotEnt e = {slot_pos[g], g};
+            e_all[g] = e; lists.rank[0][g] = at[0]; lists.rank[1][g] = at[1];
+            if (r & 1u) e_str[0][at[0]++] = e;
+            if (r & 2u) e_str[1][at[1]++] = e;
+          } } } });
+  }
 }
 inline bool stream_pipeline(bool has_focus, bool hemi) { return has_focus && !hemi; }   // focus runs take the slot pipeline (mkp_slots.hip)
 
@@ -314,11 +345,14 @@ struct ShardPlan {
   std::vector<uint8_t> dup_member;                 // per read: in one of dup_groups and inside the window
   std::vector<uint32_t> class_list, slot_ids;
   std::vector<MkpTile> tiles; std::vector<MkpSTile> stiles; std::vector<uint32_t> slotbm, wpfx, slot_pos;
+  SlotLists lists;                                 // the slot-entry lists of the window (slot pipeline)
+  std::vector<uint32_t> ent_off, ent_cnt;          // per read of the fused decoder: its run of slot entries (plan_read_entries)
   std::vector<MkpDupCons> dup_cons; std::vector<MkpDupSeg> dup_segs;
   std::vector<MkpWork> work;
   uint32_t slot_cap = 0, focus_words = 0, words_per_slot = 0, lds_bytes = 0, n_tiles = 0;
   uint64_t n_slots_total = 0, cov_bytes = 0, plane_bytes = 0;
   uint64_t fused_swept = 0, fused_looked_up = 0;   // the fused reads' terms of the decoder's algorithmic bytes
+  uint64_t fused_entries = 0, fused_slots = 0;     // slot entries the fused reads decode, of the slots they span
 };
 
 // ---- stage 1.  Hazard: the reference's ReadCache is keyed by read NAME (read_cache.rs:28-35); two kept records with one name in one
@@ -595,8 +629,9 @@ inline void plan_tiles(const PlanInput& in, ShardPlan& pl) {
     // slot bitmap + running popcount + slot positions: made ahead of the reads when the driver asked for it (mkp_internal_shard_preplan)
     pl.preplanned = in.wplan.valid && pl.stream && !in.hemi
         && in.wplan.slotbm.size() == SlotRank::words_for((int64_t)S.win_end - (int64_t)S.win_start);
-    if (pl.preplanned) { pl.slotbm.swap(in.wplan.slotbm); pl.wpfx.swap(in.wplan.wpfx); pl.slot_pos.swap(in.wplan.slot_pos); in.wplan.valid = false; }
-    else window_slots(S, in.focus.data(), in.combos, in.hemi, pl.stream, pl.slotbm, pl.wpfx, pl.slot_pos);
+    if (pl.preplanned) { pl.slotbm.swap(in.wplan.slotbm); pl.wpfx.swap(in.wplan.wpfx); pl.slot_pos.swap(in.wplan.slot_pos);
+      pl.lists.swap(in.wplan.lists); in.wplan.valid = false; }
+    else window_slots(S, in.focus.data(), in.combos, in.hemi, pl.stream, pl.slotbm, pl.wpfx, pl.slot_pos, pl.lists);
     if (pl.stream) plan_slot_tiles(in, pl); else plan_focus_tiles(in, pl);
     for (size_t w = 0; w < pl.slotbm.size(); w++) pl.n_slots_total += (uint64_t)__builtin_popcount(pl.slotbm[w]);
   }
@@ -720,6 +755,27 @@ inline void plan_name_owners(const PlanInput& in, ShardPlan& pl, const CigarFetc
 // ---- stage 10: reads by kernel on the slot pipeline.  The fused slot decoder takes the SPARSE classes when no edge filter is set (it
 // never locates calls off the focus positions, which the edge filter's "any call left" test would need); every other read is decoded into
 // events by its class kernel and then covered.
+// The slot entries a fused read decodes.  It writes coverage features on tally strand `aln` and call features on `aln ^ sg0` (sg0: the mod
+// strand of its tags, MkpFusedDesc.misc bit 2), and a slot whose rule lacks bit s yields no row that reads a strand-s tally or a strand-s
+// observed-code plane.  A read that needs one tally strand s therefore decodes its run of strand s's list — where that list is strictly
+// shorter than `all` in this shard — and every other read (both strands needed; MKP_STRAND_SLOTS=0) its run of `all`.
+inline void plan_read_entries(const PlanInput& in, ShardPlan& pl, uint32_t nf) {
+  const ShardHost& S = in.S; const SlotLists& Ls = pl.lists;
+  pl.ent_off.assign(S.hdr.size(), 0); pl.ent_cnt.assign(S.hdr.size(), 0);
+  std::vector<uint8_t> sg0(in.tables.dev.size());
+  for (size_t i = 0; i < sg0.size(); i++) sg0[i] = (uint8_t)((fused_desc(in.tables.dev[i]).misc >> 2) & 1u);
+  host_parallel(nf, 8192, [&](size_t lo, size_t hi) { for (size_t k = lo; k < hi; k++) {
+      const uint32_t r = pl.slot_ids[k]; const MkpReadHdr& h = S.hdr[r];
+      const uint32_t aln = (h.flags & MKP_RF_REVERSE) ? 1u : 0u;
+      const bool may_call = !(h.flags & MKP_RF_BAD) && h.n_tags != 0 && h.layout < sg0.size();
+      const bool both = may_call && sg0[h.layout] != 0;   // calls go to the other tally strand
+      if (!in.knobs.strand_slots_off && !both && Ls.n_strand[aln] < Ls.n_all) {
+        const uint32_t a = Ls.rank[aln][h.gs0], b = Ls.rank[aln][h.gs0 + h.n_sl];
+        pl.ent_off[r] = Ls.list_off(1 + (int)aln) + a; pl.ent_cnt[r] = b - a;
+      } else { pl.ent_off[r] = h.gs0; pl.ent_cnt[r] = h.n_sl; }
+    } });
+}
+
 inline void split_fused_and_cover(const PlanInput& in, ShardPlan& pl) {
   const ShardHost& S = in.S; const size_t n = S.hdr.size();
   if (!pl.stream) return;
@@ -747,6 +803,9 @@ inline void split_fused_and_cover(const PlanInput& in, ShardPlan& pl) {
     pl.slot_ids.resize(nf);
     auto longer = [&](uint32_t x, uint32_t y) { return S.hdr[x].l_seq > S.hdr[y].l_seq; };
     std::merge(cl.begin(), cl.begin() + pl.n_class[0], cl.begin() + pl.n_class[0], cl.begin() + nf, pl.slot_ids.begin(), longer);
+    // a wave's time goes with the slots it decodes: the launch order is by entry count (reads of one count keep their order by length)
+    plan_read_entries(in, pl, nf);
+    stable_sort_desc(pl.slot_ids, [&](uint32_t x) { return pl.ent_cnt[x]; });
     pl.n_slot_class[0] = nf;
     pl.read_ids_dec_off = nf; pl.n_class[0] = dup_forced[0]; pl.n_class[1] = dup_forced[1];
   }
@@ -764,27 +823,30 @@ inline void build_work_records(const PlanInput& in, ShardPlan& pl) {
   const ShardHost& S = in.S;
   if (!pl.stream) return;
   const uint32_t nf = pl.n_slot_class[0];
-  std::atomic<uint64_t> fused_swept{0}, fused_looked_up{0};
+  std::atomic<uint64_t> fused_swept{0}, fused_looked_up{0}, fused_entries{0}, fused_slots{0};
   pl.work.resize(nf);
   host_parallel(nf, 8192, [&](size_t lo, size_t hi) {
-    uint64_t swept = 0, looked_up = 0;
+    uint64_t swept = 0, looked_up = 0, entries = 0, slots = 0;
     for (size_t k = lo; k < hi; k++) {
       const MkpReadHdr& h = S.hdr[pl.slot_ids[k]]; MkpWork& w = pl.work[k]; memset(&w, 0, sizeof(w));
       w.ref_start = h.ref_start; w.l_seq = h.l_seq; w.n_cigar = h.n_cigar;
       w.cigar_off = (h.flags & MKP_RF_CIGW) ? h.cigar_off : h.cigar16_off;   // the decoder's array of this read (MkpWork, mkp_device.h)
       w.seq_off = h.seq_off; w.flags = h.flags; w.gs0 = h.gs0; w.n_sl = h.n_sl;
       w.cov_off = h.cov_off; w.n_tags = h.n_tags; w.layout = h.layout; w.rid = pl.slot_ids[k];
+      w.ent_off = pl.ent_off[w.rid]; w.n_ent = pl.ent_cnt[w.rid];
       if (!(h.flags & MKP_RF_BAD) && h.n_tags) {
         const MkpTagRef& t0 = S.tagref[h.tag_off]; w.rank_off = t0.rank_off; w.n_calls = t0.n; w.ml_off0 = t0.ml_off;
         if (h.n_tags > 1) w.ml_off1 = S.tagref[h.tag_off + 1].ml_off;
       }
       uint64_t n_rk = 0; if (!(h.flags & MKP_RF_BAD)) for (uint32_t t = 0; t < h.n_tags; t++) n_rk += S.tagref[h.tag_off + t].n;
       swept += (h.l_seq + 1) / 2 + 2ull * n_rk + ((h.flags & MKP_RF_CIGW) ? 0ull : 2ull * h.n_cigar);   // (16-bit CIGAR: 2 of the 4 bytes per op)
-      looked_up += 16ull * std::min<uint64_t>(MKP_PLANE_WORDS(h.l_seq), h.n_sl);
+      looked_up += 16ull * std::min<uint64_t>(MKP_PLANE_WORDS(h.l_seq), w.n_ent);
+      entries += w.n_ent; slots += h.n_sl;
     }
-    fused_swept += swept; fused_looked_up += looked_up;
+    fused_swept += swept; fused_looked_up += looked_up; fused_entries += entries; fused_slots += slots;
   });
   pl.fused_swept = fused_swept.load(); pl.fused_looked_up = fused_looked_up.load();
+  pl.fused_entries = fused_entries.load(); pl.fused_slots = fused_slots.load();
   uint64_t pw = 0;
   for (uint32_t k = 0; k < nf; k++) {
     if (pw > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "shard exceeds 2^32 call-plane words; use smaller shards");

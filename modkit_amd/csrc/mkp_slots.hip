@@ -13,7 +13,10 @@
 //                         base, whether a call is listed there and as which call (one 16-byte plane gather; the SEQ byte only for a
 //                         read with a base that is not A/C/G/T),
 //                         ML -> f32 probabilities -> MultipleThresholdModCaller::call, and ONE FEATURE BYTE per slot goes to the
-//                         read's run of the feature stream.  Calls on non-focus positions are never located (their rows would be
+//                         read's run of the feature stream — for the slots of the read's own strand only where it feeds one tally
+//                         strand and the shard's rules tell the strands apart (the slot-entry lists, mkp_plan.hpp: under --cpg half of a
+//                         read's slots; the other bytes stay MKP_FB_BLANK from the prefill).
+//                         Calls on non-focus positions are never located (their rows would be
 //                         dropped, pileup/mod.rs:570-604); CIGAR is read once per pass, the plane only under the slots.
 //   mkp_cover_reads       every other read (implicit-mode / multi-group / duplex / `N` tags / failed tags, or any read when an edge
 //                         filter is set): the decode kernels of mkp_kernels.hip leave position-sorted call events; this kernel walks
@@ -249,7 +252,7 @@ __device__ __forceinline__ uint32_t cover_feature(uint32_t kind, uint32_t nib, u
 //   (o - count)-th flag of the word); the word's listed calls before it in stored order follow from the running count and a wave scan.  A
 //   delta list whose last entry is not below the base's occurrence count runs past its last occurrence (mod_bam.rs:705-727): entries are
 //   left unplaced, MKP_RF_RUNOVER in the work record.
-// seqn_bytes collects what the decoder will read of the SEQN reads' SEQ (one byte per slot, at most the read's bytes): algorithmic bytes.
+// seqn_bytes collects what the decoder will read of the SEQN reads' SEQ (one byte per decoded slot, at most the read's bytes): algorithmic bytes.
 // Reference: DeltaListConverter::new / to_positions (mod_bam.rs:667-733).
 extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __restrict__ work, uint32_t n_reads, const uint8_t* __restrict__ seqs,
     const uint32_t* __restrict__ ranks, const MkpFusedDesc* __restrict__ fdesc, uint4* __restrict__ plane, unsigned long long* __restrict__ seqn_bytes) {
@@ -371,7 +374,7 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
   if (__any(seqn)) flags |= MKP_RF_SEQN;
   if (lane == 0) {
     if (flags != h.flags) work[widx].flags = flags;
-    if (flags & MKP_RF_SEQN) atomicAdd(seqn_bytes, (unsigned long long)min((L + 1u) >> 1, h.n_sl));
+    if (flags & MKP_RF_SEQN) atomicAdd(seqn_bytes, (unsigned long long)min((L + 1u) >> 1, h.n_ent));
   }
 }
 
@@ -392,9 +395,9 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
 // now is fewer instructions per step, not more overlap.
 #define FUSED_PARAMS(PRM) const MkpWork* __restrict__ work, uint32_t n_reads, const uint32_t* __restrict__ cigar, const uint16_t* __restrict__ cigar16, \
     const uint8_t* __restrict__ seqs, \
-    const uint4* __restrict__ plane, const uint8_t* __restrict__ ml, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const uint32_t* __restrict__ slot_pos, \
+    const uint4* __restrict__ plane, const uint8_t* __restrict__ ml, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const MkpSlotEnt* __restrict__ slot_ent, \
     uint8_t* __restrict__ cov, MkpVisit* __restrict__ visits, MkpReadOut* __restrict__ readout
-#define FUSED_PASS work, n_reads, cigar, cigar16, seqs, plane, ml, fdesc, prm, slot_pos, cov, visits, readout
+#define FUSED_PASS work, n_reads, cigar, cigar16, seqs, plane, ml, fdesc, prm, slot_ent, cov, visits, readout
 __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParams&), SlotLds* __restrict__ lds_all) {
   const int lane = lane_id();
   const uint32_t wib = rfl(threadIdx.x >> 6);
@@ -417,9 +420,11 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   // made by the host planner over the ML bytes (the f32 sums are exact multiples of 1/512: an integer comparison); a delta list that runs
   // past the last occurrence of its base (mod_bam.rs:705-727) by mkp_call_plane
   const bool err_rec = (h.flags & (MKP_RF_SUMERR | MKP_RF_RUNOVER)) != 0;
-  const uint32_t n_sl = h.n_sl;
-  const uint32_t* __restrict__ spos = slot_pos + h.gs0;
-  uint32_t p_next = (uint32_t)lane < n_sl ? ldo<uint32_t>(spos, 4u * (uint32_t)lane) : 0u;
+  // the slots this read answers: its run of a slot-entry list — its own strand's, or every slot's (MkpWork.ent_off) — {position, global slot
+  // index} per entry; byte k of its stream run is global slot gs0 + k, so an entry's feature byte goes to cov[cov_off - gs0 + index]
+  const uint32_t n_ent = h.n_ent, cov_rel = h.cov_off - h.gs0;
+  const MkpSlotEnt* __restrict__ ents = slot_ent + h.ent_off;
+  uint2 p_next = (uint32_t)lane < n_ent ? ldo<uint2>(ents, 8u * (uint32_t)lane) : make_uint2(0u, 0u);
   RefWinS rw; refwin_s_init(rw, cg, cg_wide, h.n_cigar, h.ref_start);
 
   // ---- the read's one (mod strand, base) group.  The caller's walk over a call's map in iteration order is resolved once per
@@ -467,13 +472,14 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   // ---- the read's slots, 64 per step
   bool gaps = false; uint32_t n_callfeat = 0;
 #ifdef MKP_DEBUG
-  const uint32_t n_sl_walk = (prm.debug_skip & 512u) ? 0u : n_sl;   // ablation: no slot loop
+  const uint32_t n_ent_walk = (prm.debug_skip & 512u) ? 0u : n_ent;   // ablation: no slot loop
 #else
-  const uint32_t n_sl_walk = n_sl;
+  const uint32_t n_ent_walk = n_ent;
 #endif
   // The loop is a software pipeline, two steps deep.  A step is three stages:
-  //   A(s)  reference -> query of the step's 64 slots (refwin_s_map), then the plane gather pe(s) and the slot positions of step s + 1 are
-  //         requested.  Both addresses are unconditional — clamped into the read's own plane / slot run — and the entry is masked where it is
+  //   A(s)  reference -> query of the step's 64 slots (refwin_s_map), then the plane gather pe(s) and the slot entries of step s + 1 (one
+  //         8-byte request per lane: position and global index) are requested.
+  //         Both addresses are unconditional — clamped into the read's own plane / slot run — and the entry is masked where it is
   //         used: a load under a divergent branch is waited for on the spot.
   //   B(s)  `listed` and the call ordinal from pe(s), then the ML bytes of the step's calls (and the SEQ byte of a SEQN read) are requested;
   //         a step without a listed call requests nothing.  What C needs of the slot is packed into one register (st).
@@ -485,12 +491,16 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   // issue order, so the wait in front of C(s) is a counted one that leaves pe(s + 1) and the slot positions in flight.  A(s + 1) runs
   // behind the last step as well (every lane invalid: no mapping, two loads of addresses inside the read's rooms): a branch around it would
   // make that wait a full drain.  Carried across A(s + 1): the ML bytes, the SEQ byte and st; across C(s): pe(s + 1), kind, q.
-  const uint32_t pl_last = max(MKP_PLANE_WORDS(L), 1u) - 1u, sq_last = (max(L, 1u) - 1u) >> 1, sl_last = max(n_sl, 1u) - 1u;
-  uint32_t kind = 2u, q = 0u, fb_prev = 0u; uint4 pe = make_uint4(0u, 0u, 0u, 0u);
+  const uint32_t pl_last = max(MKP_PLANE_WORDS(L), 1u) - 1u, sq_last = (max(L, 1u) - 1u) >> 1, ent_last = max(n_ent, 1u) - 1u;
+  uint32_t kind = 2u, q = 0u, fb_prev = 0u, g_cur = 0u, g_prev = 0u; uint4 pe = make_uint4(0u, 0u, 0u, 0u);
   auto stage_a = [&](uint32_t s0) {
     const uint32_t i = s0 + (uint32_t)lane;
-    const bool valid = i < n_sl;
-    const int32_t p = (int32_t)p_next;
+    const bool valid = i < n_ent;
+    const int32_t p = (int32_t)p_next.x;
+    g_cur = p_next.y;
+    // (the index leaves the loaded pair here: left where the scheduler puts it, the copy keeps the pair alive past the next request, the
+    //  request in front of the loop lands in other registers, and the copy back is a wait on the loop's entry edge that nothing follows)
+    asm volatile("" : "+v"(g_cur));
 #ifdef MKP_DEBUG
     if (prm.debug_skip & 64u) { kind = 0u; q = min((uint32_t)(p - h.ref_start), L - 1u); } else   // ablation: no CIGAR mapping
 #endif
@@ -498,16 +508,16 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
     // the plane entry of the base: its 2-bit code, bit q & 31 of .listed = a listed call sits here, .before + the listed bits below it =
     // its stored-order ordinal
     pe = ldo<uint4>(pl, 16u * min(q >> 5, pl_last));
-    p_next = ldo<uint32_t>(spos, 4u * min(i + 64u, sl_last));   // (behind the gather: see the wait for pe at the head of B)
+    p_next = ldo<uint2>(ents, 8u * min(i + 64u, ent_last));   // (behind the gather: see the wait for pe at the head of B)
   };
   enum : uint32_t { ST_QODD = 1u << 8, ST_MATCH = 1u << 9, ST_LISTED = 1u << 10 };
-  if (n_sl_walk != 0u) stage_a(0u);
-  for (uint32_t s0 = 0; s0 < n_sl_walk; s0 += 64u) {
+  if (n_ent_walk != 0u) stage_a(0u);
+  for (uint32_t s0 = 0; s0 < n_ent_walk; s0 += 64u) {
     const uint32_t i = s0 + (uint32_t)lane;
-    const bool valid = i < n_sl;
+    const bool valid = i < n_ent;
     // ---- B(s)
-    // (pe(s) and the slot positions were requested back to back: both are waited for here, in front of the ML requests, not behind them)
-    asm volatile("" : "+v"(p_next));
+    // (pe(s) and the slot entries were requested back to back: both are waited for here, in front of the ML requests, not behind them)
+    asm volatile("" : "+v"(p_next.x), "+v"(p_next.y));
     uint32_t st;   // the coverage feature byte | ST_*
     uint32_t mlb[MKP_KMAX] = {0u, 0u, 0u, 0u}, mlx = 0, seq_byte = 0;
     {
@@ -542,7 +552,9 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
       }
     }
     // the feature bytes of step s - 1 leave here, behind the ML requests: by the next wait for a gather the store is a whole iteration old
-    if (i - 64u < n_sl) cov[h.cov_off + i - 64u] = (uint8_t)fb_prev;
+    // (at its own slot's place in the read's run: g_prev is the global index of step s - 1, g_cur that of step s until A(s + 1) replaces it)
+    if (i - 64u < n_ent) cov[cov_rel + g_prev] = (uint8_t)fb_prev;
+    g_prev = g_cur;
     // ---- A(s + 1)
     stage_a(s0 + 64u);
     // ---- C(s)
@@ -612,7 +624,7 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
     fb_prev = fb;
     gaps = gaps || (valid && fb == MKP_FB_NONE);
   }
-  if (n_sl_walk != 0u) { const uint32_t i = ((n_sl_walk - 1u) & ~63u) + (uint32_t)lane; if (i < n_sl) cov[h.cov_off + i] = (uint8_t)fb_prev; }
+  if (n_ent_walk != 0u) { const uint32_t i = ((n_ent_walk - 1u) & ~63u) + (uint32_t)lane; if (i < n_ent) cov[cov_rel + g_prev] = (uint8_t)fb_prev; }
   gaps = __any(gaps);
   const bool ok = have_calls;
   const uint32_t tally = aln ^ sg0u, ob_const = fmisc >> 16;
@@ -620,8 +632,8 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   if (lane == 0) {
     // (what the records below need of the work record is read again here rather than held in scalar registers through the slot loop)
     const MkpWork* hp = work + widx; asm volatile("" : "+s"(hp));
-    const uint32_t h_gs0 = hp->gs0, h_flags = hp->flags, h_cov_off = hp->cov_off, h_rid = hp->rid;
-    MkpVisit v; v.gs0 = h_gs0; v.n_sl = n_sl; v.cov_off = h_cov_off;
+    const uint32_t h_gs0 = hp->gs0, h_n_sl = hp->n_sl, h_flags = hp->flags, h_cov_off = hp->cov_off, h_rid = hp->rid;
+    MkpVisit v; v.gs0 = h_gs0; v.n_sl = h_n_sl; v.cov_off = h_cov_off;
     v.flags = (ok ? MKP_VF_OK : 0u) | (rev ? MKP_VF_REV : 0u) | (gaps ? MKP_VF_GAPS : 0u) | ((h_flags >> MKP_RF_KEY_SHIFT) << 8);
     v.obs0 = (ok && tally == 0u) ? ob_const : 0u; v.obs1 = (ok && tally == 1u) ? ob_const : 0u;
     v.over_off = 0; v.n_over = 0;
@@ -1159,10 +1171,10 @@ extern "C" hipError_t mkp_launch_slots(hipStream_t st, const MkpWork* work, uint
     const uint32_t* cover_ids, uint32_t n_cover, const uint32_t* cigar,
                                        const uint8_t* seqs, const MkpTagRef* tagref, const uint32_t* ranks, const uint8_t* ml,
                                            const MkpLayout* layouts, const MkpFusedDesc* fdesc, const MkpRunParams* prm,
-                                       const uint32_t* slot_pos, uint8_t* cov, MkpVisit* visits, MkpEvent* events, MkpReadOut* readout,
-                                           uint32_t* dev_err) {
+                                       const uint32_t* slot_pos, const MkpSlotEnt* slot_ent, uint8_t* cov, MkpVisit* visits, MkpEvent* events,
+                                           MkpReadOut* readout, uint32_t* dev_err) {
   if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, cigar, cigar16, seqs, static_cast<const uint4*>(plane), ml, fdesc, *prm,
-      slot_pos, cov, visits, readout);
+      slot_ent, cov, visits, readout);
   if (n_cover) hipLaunchKernelGGL(mkp_cover_reads, dim3((n_cover + 3u) / 4u), dim3(256), 0, st, hdrs, n_cover, cover_ids, cigar, seqs, tagref, ranks,
       ml, layouts, fdesc, *prm, slot_pos, cov, visits, events, readout, dev_err);
   return hipGetLastError();
