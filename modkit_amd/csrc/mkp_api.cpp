@@ -19,10 +19,10 @@ hipError_t mkp_launch_decode(hipStream_t, const MkpReadHdr*, const uint32_t* /*r
     const MkpTagRef*, const uint32_t*,
                              const uint8_t*, const MkpLayout*, const MkpRunParams*, MkpEvent*, MkpReadOut*, uint32_t*, const uint8_t*, float*);
 hipError_t mkp_pileup_set_lds(uint32_t accum_bytes);
-hipError_t mkp_launch_pileup(hipStream_t, uint32_t /*LDS bytes*/, int /*focus mode*/, const MkpReadHdr*, const uint32_t*, const uint8_t*,
+hipError_t mkp_launch_pileup(hipStream_t, uint32_t /*LDS bytes*/, bool /*pileup-hemi*/, const MkpReadHdr*, const uint32_t*, const uint8_t*,
     const MkpEvent*,
     const MkpReadOut*, const MkpTile*, uint32_t,
-                             const MkpRunParams* /*device*/, const uint32_t* /*slot bitmap*/, const uint8_t* /*focus bytes*/, const MkpCombo*,
+                             const MkpRunParams* /*device*/, const uint32_t* /*slot bitmap (pileup-hemi)*/,
                                  const MkpRowsDev*, uint32_t* /*row cursor*/,
                              uint32_t* /*tile row offsets*/, uint32_t* /*tile row counts*/, const uint32_t* /*chunk offsets*/,
                                  uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, bool /*wide tallies*/);
@@ -216,6 +216,8 @@ void make_resident(mkp_ctx* c) {
 
 void run_kernels(mkp_ctx* c, bool time_kernels) {
   MkpRunParams& P = c->prm;
+  // focus runs are the slot pipeline's; the tile kernels of the event pipeline serve runs without focus positions and pileup-hemi only
+  if (c->has_focus && !c->hemi && !c->slot_mode) throw Error(MKP_E_INVALID, "internal: a focus run outside the slot pipeline");
   if (c->row_cap == 0) {
     // focus runs: usually one strand rule per focus position and one row per observed code; otherwise two strands per position
     uint64_t guess = c->hemi ? c->n_slots_total * 3 + 4096 : c->has_focus ? c->n_slots_total * std::max<uint32_t>(1u,
@@ -286,11 +288,11 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
                                                  c->key_passes[kp], kp, (uint32_t)c->combos.size(), n_runs, P.slot_cap,
                                                      (P.n_counters + P.n_slots) * (c->wide ? 2u : 1u), c->wide),
                                                      "stream pileup launch");
-      else hip_check(mkp_launch_pileup(c->stream, c->lds_bytes, c->hemi ? 2 : c->has_focus ? 1 : 0, c->d_hdr.as<MkpReadHdr>(),
+      else hip_check(mkp_launch_pileup(c->stream, c->lds_bytes, c->hemi, c->d_hdr.as<MkpReadHdr>(),
           c->d_cigar.as<uint32_t>(),
           c->d_seq.as<uint8_t>(), c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>(),
                                   c->d_tiles.as<MkpTile>(), c->n_tiles, c->d_prm.as<MkpRunParams>(), c->d_slotbm.as<uint32_t>(),
-                                      c->d_focus.as<uint8_t>(), c->d_combos.as<MkpCombo>(), &c->rows_src, misc,
+                                      &c->rows_src, misc,
                                   row_off, c->d_tile_row_cnt.as<uint32_t>(), c->d_chunk.as<uint32_t>(), misc + 2, c->key_passes[kp], kp,
                                       c->wide),
                                       "pileup launch");

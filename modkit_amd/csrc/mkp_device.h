@@ -147,7 +147,9 @@ struct MkpRunParams {
   uint32_t row_capacity;
   uint32_t sample_mode;     // 1: threshold sampling pass — emit argmax probabilities instead of call events
   uint32_t only_mapped;     // sampling: keep only calls with an aligned reference position
-  uint32_t debug_skip;      // ablation only (-DMKP_DEBUG builds, env MKP_DEBUG_SKIP): 1 depth walk, 2 events, 4 rows
+  // ablation only (-DMKP_DEBUG builds, env MKP_DEBUG_SKIP).  Tile kernels: 1 no depth walk, 2 no events (dense), 4 no rows, 8 no SEQ
+  // phase (hemi); event decoders: 16, 32; slot pipeline: 64 ... 4096 (named where they are read)
+  uint32_t debug_skip;
   uint8_t pb_of_can[4];     // CAN counter k -> primary base
   uint8_t can_of_pb[4];     // primary base -> CAN counter k or 0xff
   uint8_t slot_order[MKP_MAX_SLOTS];   // slots sorted by (code_repr, pb)
@@ -173,23 +175,23 @@ struct MkpRunParams {
 // One tile of mkp_pileup_tiles: rows are emitted for reference positions [r0, r1) (inside the shard window); tallies are kept
 // for the slots of [r0 - MKP_HALO, r1 + MKP_HALO) (strand combining reads a partner up to MKP_HALO away); reads [first, last)
 // are the candidates overlapping that range.  A "slot" is a position that owns a tally column in LDS: every position of
-// the range when the run has no focus, the focus positions only (--cpg / --motif / --include-bed) when it has.
+// the range when the run has no focus (dense tiles), the '+' motif positions only for pileup-hemi.
 struct MkpTile { int32_t r0, r1; uint32_t first, last; };
 #define MKP_SLOTBM_MARGIN 64   // slot bitmap origin = win_start - MKP_SLOTBM_MARGIN
 
 // mkp_pileup_tiles geometry: 16 waves per tile.  Dynamic LDS, in dwords:
 //   tallies  [words_per_slot][S]            S = slot capacity of a tile (multiple of 64), 16-bit-packed strand tallies (wide shards:
 //                                           words_per_slot doubled, one u32 plane per strand)
-//   focus runs: bm[W] + pfx[W] (slot bitmap of the tile's reference range and its running popcount), fpos[S] (slot -> position)
-//   per wave: an op-start bitmap over the tile's slots (even number of dwords, 2 spare for the 64-bit window read) and a
-//   64 x 8-byte compaction buffer
+//   pileup-hemi (focus_words = W > 0): bm[W] + pfx[W] (slot bitmap of the tile's reference range and its running popcount),
+//                                           fpos[S] (slot -> position)
+//   per wave: dense = an op-start bitmap over the tile's slots (even number of dwords, 2 spare for the 64-bit window read) and a
+//   64 x 8-byte compaction buffer; hemi = one word per slot of a read's visit (the packed query index / kind the CIGAR phase
+//   leaves for the SEQ phase)
 #ifndef MKP_PILEUP_THREADS
 #define MKP_PILEUP_THREADS 1024
 #endif
 #define MKP_PILEUP_WAVE_SCRATCH 128
 #define MKP_PILEUP_BM_WORDS(S) (((((S) + 31u) >> 5) + 3u) & ~1u)
-// per-wave scratch: dense kernel = op-start bitmap + compaction buffer; focus kernel = one word per slot of a read's visit
-// (the packed query index / kind the CIGAR phase leaves for the SEQ phase)
 #define MKP_PILEUP_WAVE_WORDS(S, focus_words) ((focus_words) && (S) > MKP_PILEUP_BM_WORDS(S) + MKP_PILEUP_WAVE_SCRATCH ? (S) : MKP_PILEUP_BM_WORDS(S) + MKP_PILEUP_WAVE_SCRATCH)
 #define MKP_PILEUP_LDS_WORDS(words_per_slot, S, focus_words) ((words_per_slot) * (S) + ((focus_words) ? 2u * (focus_words) + (S) : 0u) + (MKP_PILEUP_THREADS / 64) * MKP_PILEUP_WAVE_WORDS(S, focus_words))
 

@@ -13,10 +13,11 @@
 //   epilogue are the shared helpers in front of them.  FAST and SPARSE run it on full batches of 64 queued calls.
 //   mkp_sample_* = the same walks emitting argmax probabilities / summary classes (threshold estimate, sample-probs, summary).
 //
-//   mkp_pileup_tiles[_focus|_hemi][_keyed]   accumulate + emit: one 1024-thread workgroup per tile, two per CU; LDS holds the
-//                            tile's 16-bit-packed strand tallies; waves draw the tile's reads from an LDS ticket (observed-code
-//                            difference arrays, the read's event slice, the depth walk over its CIGAR); rows are produced straight
-//                            from LDS (mkp_dev_rows.hpp).  Used for runs without focus positions and for pileup-hemi.
+//   mkp_pileup_tiles[_keyed][_wide]   runs without focus positions: accumulate + emit, one 1024-thread workgroup per tile, two per CU;
+//                            LDS holds the tile's 16-bit-packed (or _wide: u32) strand tallies; waves draw the tile's reads from an
+//                            LDS ticket (observed-code difference arrays, the read's event slice, the depth walk over its CIGAR);
+//                            rows are produced straight from LDS (mkp_dev_rows.hpp)
+//   mkp_pileup_tiles_hemi    pileup-hemi: the same frame over the '+' motif positions only, duplex pattern counters
 //   mkp_hemi_failed_reads    pileup-hemi: the one NoCall per interval a record with failing tags leaves
 //   mkp_scan_tiles, mkp_gather_rows   order the tiles' row runs (exclusive scan of the counts + coalesced copy).
 //   mkp_sample_accumulate / _hist1, mkp_summary_accumulate   summaries of the threshold sample (two-level histograms), summary counts.
@@ -25,6 +26,7 @@
 // with contraction off (-ffp-contract=off) and IEEE division.
 #include "mkp_dev_common.hpp"
 #include "mkp_dev_rows.hpp"
+#include "mkp_dev_tiles.hpp"
 
 // ----------------------------------------------------------------------------------------------
 // What the three wave-per-read decoders share.  They differ in how they locate a read's calls (the producers); the read
@@ -1105,103 +1107,276 @@ extern "C" __global__ void __launch_bounds__(256) mkp_sample_sparse1(DECODE_PARA
 extern "C" __global__ void __launch_bounds__(256) mkp_sample_sparse2(DECODE_PARAMS(MkpRunParams)) { decode_sparse_entry<true, 2>(DECODE_PASS); }
 
 // ----------------------------------------------------------------------------------------------
+// The accumulate kernels of the event pipeline: one 1024-thread workgroup per tile, two per CU (8 waves per SIMD).  The tile's tallies
+// live in dynamic LDS, laid out as the host planner sized it (MKP_PILEUP_LDS_WORDS): tallies, hemi's slot map, per-wave scratch.  Waves
+// draw the tile's candidate reads from an LDS ticket; after a barrier the rows are produced straight from LDS (mkp_dev_rows.hpp) and
+// mkp_scan_tiles / mkp_gather_rows put the tiles' row runs in genome order.  Two bodies, dense and hemi; mkp_dev_tiles.hpp holds the
+// little they share.  (Focus runs — --cpg / --motif / --include-bed — are the slot pipeline's, mkp_slots.hip.)
 
-// mkp_pileup_tiles — accumulate + emit.  Persistent 1024-thread workgroups, two per CU (8 waves per SIMD).  LDS holds one
-// tile's tallies as [row][slot] u32 with the '+' strand tally in the low and the '-' strand tally in the high 16 bits; rows = the
-// strand tally's counters followed by the observed-code slots; consecutive slots sit on consecutive banks.  WIDE (_wide kernels: the
-// host picks them for a shard whose deepest column may hold more than 65 535 records) gives every row one u32 plane per strand
-// instead, row r strand s at plane 2r + s, at twice the LDS per slot; pileup-hemi keeps its plain counters and has no wide kernel.  Waves draw the tile's reads from an LDS ticket:
-//   * observed codes: +1 / -1 at the slots bounding the read's span (and around ref-skips) — an interval-OR as a difference array;
-//   * the read's call events inside the tile (position-sorted slice): one LDS atomic on the call's counter and -1 on NoCall(read base);
-//   * depth walk (htslib pileup columns, pileup/mod.rs:783-939): per 64-op CIGAR window the reference-consuming ops that
-//     cover at least one slot are compacted through LDS and their first slots marked in the wave's bitmap; deletions are
-//     +1 / -1 on a difference array; then one lane per slot, 64 slots per step: op index = ballot over the compacted starts
-//     + mbcnt of the aligned 64-bit bitmap window, one ds_bpermute fetches the op's packed (query offset, kind), one byte load
-//     fetches the base, a 1 KB table in LDS maps (strand, query parity, SEQ byte) to the NoCall row, one LDS atomic.
-// With focus positions (FOCUS) the walk touches only the focus slots of each op — a --cpg run visits ~2 % of the aligned bases
-// and a tile covers ~50x more reference for the same LDS.  After a barrier the difference arrays are prefix-summed in place and
-// the rows of FeatureVector::decode (412-446) / add_tally_to_counts (283-410) / combine_strand_features (469-561) are produced
-// straight from LDS: counted, reserved in the row buffer with one atomic per tile, written.  mkp_scan_tiles / mkp_gather_rows
-// put the tiles' row runs in genome order.
-// HEMI (pileup-hemi, duplex.rs:241-339): the tally columns are the '+' motif positions; a read's '+' tally call at such a position
-// and its '-' tally call at the partner position form one pattern count; everything else about the walk is the focus kernel's.
-template <bool FOCUS, int UNROLL, bool KEYED, bool HEMI = false, bool WIDE = false>
-__device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__ hdrs, const uint32_t* __restrict__ cigar,
-    const uint8_t* __restrict__ seqs,
-                 const MkpEvent* __restrict__ events, const MkpReadOut* __restrict__ readout, const MkpTile* __restrict__ tiles, uint32_t n_tiles,
-                 const MkpRunParams* __restrict__ prmp, const uint32_t* __restrict__ slotbm, const uint8_t* __restrict__ focus,
-                     const MkpCombo* __restrict__ combos,
-                 uint32_t* __restrict__ rows_base, uint32_t* __restrict__ row_cursor, uint32_t* __restrict__ tile_row_off,
-                     uint32_t* __restrict__ tile_row_cnt,
-                 const uint2* __restrict__ chunk_pfx, uint32_t* __restrict__ dev_err, uint32_t key_arg) {
-  // --partition-tag (KEYED kernels): low 16 bits = the key this pass tallies, high 16 bits = index of the pass; otherwise unused
+#define PILEUP_PARAMS const MkpReadHdr* __restrict__ hdrs, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ seqs, \
+                 const MkpEvent* __restrict__ events, const MkpReadOut* __restrict__ readout, const MkpTile* __restrict__ tiles, uint32_t n_tiles, \
+                 const MkpRunParams* __restrict__ prmp, \
+                 uint32_t* __restrict__ rows_base /* 11 SoA arrays of row_capacity entries */, uint32_t* __restrict__ row_cursor, uint32_t* __restrict__ tile_row_off, uint32_t* __restrict__ tile_row_cnt, \
+                 const uint2* __restrict__ chunk_pfx, uint32_t* __restrict__ dev_err
+#define PILEUP_PASS hdrs, cigar, seqs, events, readout, tiles, n_tiles, prmp, rows_base, row_cursor, tile_row_off, tile_row_cnt, chunk_pfx, dev_err
+
+// Dense tiles (runs without focus positions): every position of the tile's halo'd range [T0h, T1h) owns a tally column, column = p - T0h.
+// Tallies are [row][column] u32 with the '+' strand tally in the low and the '-' strand tally in the high 16 bits; rows = the strand
+// tally's counters followed by the observed-code slots; consecutive columns sit on consecutive banks.  WIDE (_wide kernels: the host picks
+// them for a shard whose deepest column may hold more than 65 535 records) gives every row one u32 plane per strand instead, row r strand
+// s at plane 2r + s, at twice the LDS per column.  Per read:
+//   * observed codes: +1 / -1 at the columns bounding the read's span (and around ref-skips) — an interval-OR as a difference array;
+//   * the read's call events inside the tile: one LDS atomic on the call's counter and -1 on NoCall(read base);
+//   * depth walk (htslib pileup columns, pileup/mod.rs:783-939): per 64-op CIGAR window the reference-consuming ops that cover at
+//     least one column are compacted through LDS and their first columns marked in the wave's bitmap; deletions are +1 / -1 on a
+//     difference array; then one lane per column, 64 columns per step: op index = ballot over the compacted starts + mbcnt of the
+//     aligned 64-bit bitmap window, one ds_bpermute fetches the op's packed (query offset, kind), one byte load fetches the base, the
+//     1 KB table in LDS maps (strand, query parity, SEQ byte) to the NoCall row, one LDS atomic.
+// After a barrier the difference arrays are prefix-summed in place and emit_dense_rows produces the rows of FeatureVector::decode.
+// KEYED (--partition-tag): key_arg's low 16 bits = the key this launch tallies, high 16 bits = index of the key pass.
+constexpr int DENSE_UNROLL = 4;   // 64-column steps of the depth walk in flight together
+
+template <bool KEYED, bool WIDE>
+__device__ __forceinline__ void dense_tiles_body(PILEUP_PARAMS, uint32_t key_arg) {
   const uint32_t key_filter = KEYED ? (key_arg & 0xffffu) : 0u, key_run = KEYED ? (key_arg >> 16) : 0u;
-  static_assert(!WIDE || (!FOCUS && !HEMI), "wide tallies: dense tiles only");
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   __shared__ uint32_t next_read;
   __shared__ uint32_t wave_tot[PILEUP_WAVES];
-  __shared__ uint32_t row_base, scan_carry;
-  __shared__ StreamProg rowprog;   // dense tiles: the row program of the emission (mkp_dev_rows.hpp)
-  // SEQ byte -> NoCall row of the base a query index selects: rowlut[strand][query parity][byte]; 15 = not A/C/G/T.
-  // (BAM packs two bases per byte, high nibble first; on the '-' strand the tallied base is the complement.)
+  __shared__ uint32_t row_base, row_total;
+  __shared__ StreamProg rowprog;   // the row program of the emission (mkp_dev_rows.hpp)
   __shared__ uint8_t rowlut[2][2][256];
   __shared__ __attribute__((aligned(16))) uint32_t prm_lds[(sizeof(MkpRunParams) + 3) / 4];
-  __shared__ __attribute__((aligned(16))) uint32_t combo_lds[64 * sizeof(MkpCombo) / 4];   // <= 64 motif-id combos (checked at mkp_shard_begin)
-  {
-    static_assert(PILEUP_THREADS == 1024, "the row table below is filled one entry per thread");
-    const uint32_t t = threadIdx.x, byte = t & 255u, par = (t >> 8) & 1u, st = (t >> 9) & 1u;
-    const uint32_t nib = par ? (byte & 15u) : (byte >> 4);
-    const unsigned long long LUT = st ? 0xfffffff0fff1f23fULL : 0xfffffff3fff2f10fULL;
-    rowlut[st][par][byte] = (uint8_t)((LUT >> (4u * nib)) & 15u);
-    for (uint32_t kq = threadIdx.x; kq < sizeof(MkpRunParams) / 4; kq += PILEUP_THREADS) prm_lds[kq] = reinterpret_cast<const uint32_t*>(prmp)[kq];
-    if (prmp->has_focus) for (uint32_t kq = threadIdx.x; kq < prmp->n_combos * (sizeof(MkpCombo) / 4); kq += PILEUP_THREADS) combo_lds[kq] = reinterpret_cast<const uint32_t*>(combos)[kq];
-  }
+  tile_prologue(prmp, &rowlut[0][0][0], prm_lds);
   __syncthreads();
   const MkpRunParams& prm = *reinterpret_cast<const MkpRunParams*>(prm_lds);
-  const MkpCombo* combos_l = reinterpret_cast<const MkpCombo*>(combo_lds);
-  const uint32_t S = prm.slot_cap, W = prm.focus_words;
+  const uint32_t S = prm.slot_cap;
 #ifdef MKP_DEBUG
-  const uint32_t dbg = prm.debug_skip;   // ablation runs (env MKP_DEBUG_SKIP): 1 depth walk, 2 events, 4 row emission, 8 SEQ phase of the focus walk
+  const uint32_t dbg = prm.debug_skip;   // ablation runs (env MKP_DEBUG_SKIP): 1 no depth walk, 2 no events, 4 no row emission
 #else
   constexpr uint32_t dbg = 0;
 #endif
-  const uint32_t n_counters = HEMI ? prm.hemi_counters : prm.n_counters, n_oslots = HEMI ? 0u : prm.n_slots;
-  const uint32_t tal_words = (n_counters + n_oslots) * S * (WIDE ? 2u : 1u);
-  uint32_t* __restrict__ tal = lds;                       // [n_counters + n_oslots][S], packed (WIDE: [n_counters + n_oslots][2][S])
-  uint32_t* __restrict__ obs = lds + n_counters * S * (WIDE ? 2u : 1u);   // observed-code difference arrays
-  uint32_t* __restrict__ fbm = lds + tal_words;           // FOCUS: bitmap words [W], running popcount [W], slot -> position [S]
-  uint32_t* __restrict__ fpfx = fbm + W;
-  int32_t* __restrict__ fpos = reinterpret_cast<int32_t*>(fpfx + W);
-  const uint32_t focus_total = FOCUS ? 2u * W + S : 0u;
+  constexpr uint32_t NP = WIDE ? 2u : 1u;   // planes per row
+  const uint32_t n_counters = prm.n_counters, n_oslots = prm.n_slots;
+  const uint32_t tal_words = (n_counters + n_oslots) * S * NP;
+  uint32_t* __restrict__ tal = lds;                    // [n_counters + n_oslots][S], packed (WIDE: [n_counters + n_oslots][2][S])
+  uint32_t* __restrict__ obs = lds + n_counters * S * NP;   // its tail: the observed-code difference arrays
   const int lane = lane_id();
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  // per-wave scratch behind that: op-start bitmap over the tile's slots + CIGAR compaction buffer
-  const uint32_t bm_words = MKP_PILEUP_BM_WORDS(S), wave_words = MKP_PILEUP_WAVE_WORDS(S, W);
-  uint32_t* __restrict__ bm = lds + tal_words + focus_total + wave * wave_words;
+  const uint32_t wave = rfl_u(threadIdx.x >> 6);
+  // per-wave scratch behind the tallies: op-start bitmap over the tile's columns + CIGAR compaction buffer
+  const uint32_t bm_words = MKP_PILEUP_BM_WORDS(S), wave_words = MKP_PILEUP_WAVE_WORDS(S, 0u);
+  uint32_t* __restrict__ bm = lds + tal_words + wave * wave_words;
   uint2* __restrict__ comp = reinterpret_cast<uint2*>(bm + bm_words);
-  uint32_t* __restrict__ qk = bm;   // focus kernel: per slot of the current read's visit, (query index << 2) | kind
   const uint32_t TS4 = S * 4u;
-  // XCD-aware mapping: consecutive workgroups land on different XCDs (b % 8); give each XCD a
-  // contiguous run of tiles so the reads shared by neighbouring tiles stay in one L2.
-  // One workgroup per tile; the dispatcher hands tiles to CUs as workgroups retire (two fit a CU).
-  {
-  uint32_t tix = blockIdx.x;
-  { const uint32_t per = n_tiles / 8u; if (per && tix < per * 8u) tix = (tix & 7u) * per + (tix >> 3); }
+  const uint32_t tix = xcd_tile_index(n_tiles);
   const MkpTile tl = tiles[tix];
   const int32_t T0h = tl.r0 - MKP_HALO, T1h = tl.r1 + MKP_HALO;
-  // zero the tallies and the per-wave scratch (the focus arrays are rewritten below)
+  const uint32_t n_tslots = (uint32_t)(T1h - T0h);   // tally columns in use
+  for (uint32_t k = threadIdx.x; k < tal_words + PILEUP_WAVES * wave_words; k += PILEUP_THREADS) lds[k] = 0;
+  if (threadIdx.x == 0) next_read = tl.first;
+  __syncthreads();
+
+  const uint32_t rid_end = tl.last;
+  TileRead nx;
+  draw_read(&next_read, rid_end, hdrs, readout, nx);
+  for (;;) {
+    if (nx.rid >= rid_end) break;
+    const MkpReadHdr h = nx.h; const MkpReadOut ro = nx.ro;
+    draw_read(&next_read, rid_end, hdrs, readout, nx);
+    if (h.ref_end <= T0h || h.ref_start >= T1h) continue;
+    if (KEYED && (h.flags >> MKP_RF_KEY_SHIFT) != key_filter) continue;   // --partition-tag: one pass per key
+    const uint32_t rs_a = (uint32_t)(max(h.ref_start, T0h) - T0h), rs_b = (uint32_t)(min(h.ref_end, T1h) - T0h);   // the read's columns
+    const uint32_t aln = (h.flags & MKP_RF_REVERSE) ? 1u : 0u;
+    const uint8_t* __restrict__ seq = seqs + h.seq_off;
+    const CigarStart cs = skip_chunks_before(h, chunk_pfx, T0h);
+    uint32_t q_run = cs.q_run; int32_t r_run = cs.r_run;
+    // the first chunk's CIGAR words are requested now, ahead of the event work; every later chunk is requested one chunk ahead
+    uint32_t w_next = (cs.c_first + (uint32_t)lane < h.n_cigar) ? cigar[h.cigar_off + cs.c_first + lane] : 5u;
+    // observed mod codes: +1 over the read's span (add_mod_codes_for_record, pileup/mod.rs:831-835); lane = tally strand
+    if (ro.ok && lane < 2) {
+      uint32_t m = lane ? ro.obs[1] : ro.obs[0];
+      while (m) {
+        const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
+        obs_diff<WIDE>(obs, S, sl, (uint32_t)lane, rs_a, rs_b, n_tslots, false);
+      }
+    }
+    if (ro.ok && ro.n_events && !(dbg & 2u))
+      for_tile_events(events + h.event_off, ro.n_events, h.ref_start >= T0h, T0h, T1h, [&](uint32_t, const MkpEvent& e) {
+        const uint32_t i = (uint32_t)((int32_t)e.pos - T0h);
+        if (WIDE) {   // [8] tally strand of the call, [11] of the read's base
+          atomicAdd(&tal[(2u * (e.info & 0xffu) + ((e.info >> 8) & 1u)) * S + i], 1u);
+          if (e.info & (1u << 12)) atomicAdd(&tal[(2u * (MKP_C_NC + ((e.info >> 9) & 3u)) + ((e.info >> 11) & 1u)) * S + i], 0u - 1u);
+        } else {
+          atomicAdd(&tal[(e.info & 0xffu) * S + i], (e.info & 0x100u) ? 0x10000u : 1u);
+          if (e.info & (1u << 12))  // the base is a call, not a NoCall (pileup/mod.rs:889-938)
+            atomicAdd(&tal[(MKP_C_NC + ((e.info >> 9) & 3u)) * S + i], 0u - ((e.info & 0x800u) ? 0x10000u : 1u));
+        }
+      });
+    // depth walk: htslib pileup columns (match -> base, D -> delete, N -> ref-skip).  One lane per column;
+    // the op covering a column = (ops whose first column is at or before it) - 1, counted with the wave's op-start bitmap.
+    const uint32_t inc = WIDE ? 1u : (aln ? 0x10000u : 1u);   // this alignment strand's half of the packed tallies
+    // WIDE: this alignment strand's plane of a row (byte offset) and the distance between two rows' planes
+    const uint32_t aln_plane = WIDE ? aln * S * 4u : 0u, row_bytes = WIDE ? S * 8u : S * 4u;
+    const uint8_t* __restrict__ lut = &rowlut[0][0][0];
+    const uint32_t aln2 = aln << 1;
+    const uint32_t lanebase = lds_addr(tal) + 4u * (uint32_t)lane;   // LDS byte address of (row 0, column `lane`)
+    const uint32_t qbase = (uint32_t)(0 - h.ref_start) - (1u << 26);   // query index = position + qbase + packed offset
+    const uint32_t last_byte = (h.l_seq - 1u) >> 1;
+    if (!(dbg & 1u))
+    for (uint32_t c0 = cs.c_first; c0 < h.n_cigar; c0 += 64) {
+      if (r_run >= T1h) break;
+      const uint32_t w = w_next;
+      if (c0 + 64u < h.n_cigar) w_next = (c0 + 64u + (uint32_t)lane < h.n_cigar) ? cigar[h.cigar_off + c0 + 64u + lane] : 5u;
+      const uint32_t op = w & 15u, len = w >> 4;
+      const uint32_t qlen = op_consumes_query(op) ? len : 0u, rlen = op_consumes_ref(op) ? len : 0u;
+      const uint32_t qe = wave_incl_scan(qlen), re = wave_incl_scan(rlen);
+      const uint32_t qs = q_run + qe - qlen;
+      const int32_t rs = r_run + (int32_t)(re - rlen);
+      const uint32_t Qtot = (uint32_t)__builtin_amdgcn_readlane((int)qe, 63), Rtot = (uint32_t)__builtin_amdgcn_readlane((int)re, 63);
+      const int32_t c_lo = max(r_run, T0h), c_hi = min(r_run + (int32_t)Rtot, T1h);
+      if (c_lo < c_hi) {
+        // the op's columns inside the tile: [sa, sb)
+        const uint32_t sa = (uint32_t)(min(max(rs, c_lo), c_hi) - T0h), sb = (uint32_t)(min(max(rs + (int32_t)rlen, c_lo), c_hi) - T0h);
+        const bool covers = rlen > 0 && sa < sb;
+        if (op == 3 && ro.ok && covers) {  // ref-skip: the read is not in these columns (alignment.is_refskip())
+          for (uint32_t s = 0; s < 2; s++) {
+            uint32_t m = ro.obs[s];
+            while (m) {
+              const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
+              obs_diff<WIDE>(obs, S, sl, s, sa, sb, n_tslots, true);
+            }
+          }
+        }
+        if (op == 2 && covers) {  // deletion columns (alignment.is_del()): +1/-1 on the strand's DEL row, summed after the barrier
+          const uint32_t del_row = WIDE ? (2u * MKP_C_DEL + aln) * S : MKP_C_DEL * S;
+          atomicAdd(&tal[del_row + sa], inc);
+          if (sb < n_tslots) atomicAdd(&tal[del_row + sb], 0u - inc);
+        }
+        const uint32_t S_lo = (uint32_t)(c_lo - T0h), S_hi = (uint32_t)(c_hi - T0h);   // the chunk's columns
+        // compact the window's column-covering ops to the low lanes: {first column, packed(query offset, kind)}
+        const unsigned long long refbal = __ballot(covers);
+        const uint32_t nref = (uint32_t)__popcll(refbal);
+        const uint32_t ci = (uint32_t)__popcll(refbal & lanemask_lt());
+        const uint32_t kind = op_is_match(op) ? 0u : (op == 2 ? 1u : 2u);
+        // q = (pos - ref_start) + D; kind sits where it ORs into the row
+        const uint32_t pk = ((uint32_t)((int32_t)qs - (rs - h.ref_start) + (1 << 26)) << 5) | (kind << 3);
+        if (covers) comp[ci] = make_uint2(sa, pk);
+        wave_lds_sync();
+        const uint2 cc = comp[lane];
+        const bool cvalid = (uint32_t)lane < nref;
+        const uint32_t c_sa = cc.x; const uint32_t c_pk = cc.y;
+        const uint32_t c_key = cvalid ? c_sa : 0x7fffffffu;
+        const uint32_t e_lo = lds_addr(tal) + 4u * S_lo, e_span = 4u * (S_hi - S_lo);
+        const bool mark = cvalid && c_sa > S_lo;
+        const uint32_t mrel = c_sa - 1u;   // bit m set <=> an op's first column is m+1: "starts at or before column c" = bits strictly below c
+        if (mark) atomicOr(&bm[mrel >> 5], 1u << (mrel & 31u));
+        wave_lds_sync();
+        // 64 columns per step, aligned so a step reads one aligned 64-bit window of the bitmap;
+        // DENSE_UNROLL steps are issued together (bitmap read -> bpermute -> SEQ byte load) before any tally update.
+        // ops started at or before the first column of window kk: a ballot over the compacted starts (no LDS dependency)
+        const uint32_t k0 = S_lo >> 6, k1 = (S_hi - 1u) >> 6;
+        // Only the first and the last group of a chunk hold out-of-range lanes or repeated (clamped) windows; the groups in
+        // between run a version without the clamps and the range check.
+        auto group = [&](uint32_t kb, auto edge_c) {
+          constexpr bool EDGE = decltype(edge_c)::value;
+          constexpr int U = DENSE_UNROLL;
+          uint32_t pkv[U], byte[U], qq[U], idx[U], kk[U]; uint2 Wd[U];
+          // stage by stage across the U windows, so the LDS reads, the bpermutes and the global loads of the group overlap
+#pragma unroll
+          for (int j = 0; j < U; j++) kk[j] = EDGE ? min(kb + (uint32_t)j, k1) : kb + (uint32_t)j;
+#pragma unroll
+          for (int j = 0; j < U; j++) Wd[j] = *reinterpret_cast<const uint2*>(bm + 2u * kk[j]);
+#pragma unroll
+          for (int j = 0; j < U; j++) {
+            const uint32_t wstart = 64u * kk[j];
+            idx[j] = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(c_key <= (EDGE ? max(S_lo, wstart) : wstart))) - 1u;
+          }
+#pragma unroll
+          for (int j = 0; j < U; j++)
+            pkv[j] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((idx[j] + __builtin_amdgcn_mbcnt_hi(Wd[j].y,
+                __builtin_amdgcn_mbcnt_lo(Wd[j].x, 0u))) << 2), (int)c_pk);
+#pragma unroll
+          for (int j = 0; j < U; j++) {
+            qq[j] = (uint32_t)(T0h + (int32_t)(64u * kk[j]) + lane) + qbase + (pkv[j] >> 5);
+            byte[j] = seq[min(qq[j] >> 1, last_byte)];   // lanes on D/N ops or outside the span read a clamped (ignored) byte
+          }
+#pragma unroll
+          for (int j = 0; j < U; j++) {
+            const uint32_t t = (qq[j] & 1u) | aln2;
+            const uint32_t rowt = (uint32_t)lut[(t << 8) | byte[j]] | (pkv[j] & 0x18u);   // >= 8: not ACGT, or the lane sits on a D/N op
+            const uint32_t la = lanebase + 256u * kk[j];
+            bool ok = rowt < 8u;
+            if (EDGE) ok = ok && (la - e_lo) < e_span && kb + (uint32_t)j <= k1;
+            if (ok) lds_add(la + (WIDE ? __umul24(rowt, row_bytes) + aln_plane : __umul24(rowt, TS4)), inc);
+          }
+        };
+        for (uint32_t kb = k0; kb <= k1; kb += DENSE_UNROLL) {
+          if (kb == k0 || kb + DENSE_UNROLL > k1) group(kb, std::true_type{}); else group(kb, std::false_type{});
+        }
+        if (mark) bm[mrel >> 5] = 0;
+      }
+      q_run += Qtot; r_run += (int32_t)Rtot;
+    }
+  }
+  __syncthreads();
+  // difference arrays -> counts, one wave per array: the DEL row (WIDE: its two planes), then the observed-code rows, which are
+  // contiguous behind `obs` in either layout
+  for (uint32_t a = wave; a < NP * (n_oslots + 1u); a += PILEUP_WAVES)
+    prefix_sum_in_place(a < NP ? tal + (NP * MKP_C_DEL + a) * S : obs + (a - NP) * S, n_tslots);
+  __syncthreads();
+  // rows of the tile straight from LDS.  One tile per workgroup: nothing of the accumulate phase is live here and nothing of this phase
+  // is live there, so neither raises the other's register count.  The row map takes the per-wave scratch (dead behind the barrier).
+  if (!(dbg & 4u))
+    emit_dense_rows<WIDE>(tal, S, n_counters, n_tslots, T0h, tl, KEYED ? key_run * n_tiles + tix : tix, key_filter, prm, rowprog,
+        lds + tal_words, min(8192u, PILEUP_WAVES * wave_words), rows_base, row_cursor, tile_row_off, tile_row_cnt, dev_err, wave_tot,
+        &row_base, &row_total);
+}
+
+// pileup-hemi tiles (duplex.rs:241-339): only the '+' motif positions of [T0h, T1h) own a tally column (SlotMap, built from the run's
+// slot bitmap; the host caps a tile at one column per thread), so a tile covers ~50x more reference for the same LDS.  Counters are plain
+// u32 [counter][column] (MKP_H_*), every update a +1: a read's '+' tally call at a column and its '-' tally call at the partner
+// position form one pattern count.  The depth walk is driven by the columns, not by the ops: 128 CIGAR ops per window (two per lane).
+// Phase 1 leaves each column of the read's visit its packed (query index, kind) in the wave's scratch; phase 2 fetches the bases with
+// several SEQ loads in flight — they do not sit in the CIGAR dependency chain.  Then emit_hemi_rows.
+__device__ __forceinline__ void hemi_tiles_body(PILEUP_PARAMS, const uint32_t* __restrict__ slotbm) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  __shared__ uint32_t next_read;
+  __shared__ uint32_t wave_tot[PILEUP_WAVES];
+  __shared__ uint32_t row_base, scan_carry;   // scan_carry: running column count while the slot map is built, then the tile's row total
+  __shared__ uint8_t rowlut[2][2][256];
+  __shared__ __attribute__((aligned(16))) uint32_t prm_lds[(sizeof(MkpRunParams) + 3) / 4];
+  tile_prologue(prmp, &rowlut[0][0][0], prm_lds);
+  __syncthreads();
+  const MkpRunParams& prm = *reinterpret_cast<const MkpRunParams*>(prm_lds);
+  const uint32_t S = prm.slot_cap, W = prm.focus_words;
+#ifdef MKP_DEBUG
+  const uint32_t dbg = prm.debug_skip;   // ablation runs (env MKP_DEBUG_SKIP): 1 no depth walk, 4 no row emission, 8 no SEQ phase
+#else
+  constexpr uint32_t dbg = 0;
+#endif
+  const uint32_t tal_words = prm.hemi_counters * S;
+  uint32_t* __restrict__ tal = lds;                       // [hemi_counters][S]
+  uint32_t* __restrict__ fbm = lds + tal_words;           // slot map: bitmap words [W], running popcount [W], column -> position [S]
+  uint32_t* __restrict__ fpfx = fbm + W;
+  int32_t* __restrict__ fpos = reinterpret_cast<int32_t*>(fpfx + W);
+  const int lane = lane_id();
+  const uint32_t wave = rfl_u(threadIdx.x >> 6);
+  // per-wave scratch behind that: per column of the current read's visit, (query index << 2) | kind; kind 3 = no base
+  const uint32_t wave_words = MKP_PILEUP_WAVE_WORDS(S, W), scratch0 = tal_words + 2u * W + S;
+  uint32_t* __restrict__ qk = lds + scratch0 + wave * wave_words;
+  const uint32_t TS4 = S * 4u;
+  const uint32_t tix = xcd_tile_index(n_tiles);
+  const MkpTile tl = tiles[tix];
+  const int32_t T0h = tl.r0 - MKP_HALO, T1h = tl.r1 + MKP_HALO;
   for (uint32_t k = threadIdx.x; k < tal_words; k += PILEUP_THREADS) lds[k] = 0;
-  // focus: kind 3 = no base
-  for (uint32_t k = threadIdx.x; k < PILEUP_WAVES * wave_words; k += PILEUP_THREADS) lds[tal_words + focus_total + k] = FOCUS ? 3u : 0u;
+  for (uint32_t k = threadIdx.x; k < PILEUP_WAVES * wave_words; k += PILEUP_THREADS) lds[scratch0 + k] = 3u;
   if (threadIdx.x == 0) { next_read = tl.first; scan_carry = 0; }
-  SlotMap<FOCUS> sm; sm.bm = fbm; sm.pfx = fpfx; sm.fpos = fpos; sm.T0h = T0h; sm.lbase = T0h;
-  uint32_t n_tslots = (uint32_t)(T1h - T0h);   // tally columns in use
-  if (FOCUS) {
-    // the tile's slice of the slot bitmap: words masked to [T0h, T1h), their running popcount, and the slot -> position list
+  // the tile's slice of the slot bitmap: words masked to [T0h, T1h), their running popcount, and the column -> position list
+  SlotMap sm; sm.bm = fbm; sm.pfx = fpfx; sm.fpos = fpos;
+  {
     const uint32_t g0 = (uint32_t)(T0h - (prm.win_start - MKP_SLOTBM_MARGIN)), sh = g0 & 31u, nbits = (uint32_t)(T1h - T0h);
     const uint32_t nw = (sh + nbits + 31u) >> 5;
     sm.lbase = T0h - (int32_t)sh;
-    __syncthreads();   // scan_carry = 0 visible; previous tile's readers of the focus arrays are done
+    __syncthreads();   // scan_carry = 0 visible
     for (uint32_t k0 = 0; k0 < nw + 1u; k0 += PILEUP_THREADS) {
       const uint32_t k = k0 + threadIdx.x;
       uint32_t w = 0;
@@ -1223,324 +1398,112 @@ __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__
       if (threadIdx.x == PILEUP_THREADS - 1) scan_carry = woff + inc;
     }
     __syncthreads();
-    n_tslots = scan_carry;
   }
+  const uint32_t n_tslots = scan_carry;   // tally columns in use
   __syncthreads();
 
-  // reads are handed out one at a time (LDS ticket) so waves finish the tile together whatever the reads' spans; the next
-  // read's header and decode summary are requested while the current read is processed (one global round trip less per read)
   const uint32_t rid_end = tl.last;
-  uint32_t rid_nx; MkpReadHdr h_nx; MkpReadOut ro_nx;
-  { uint32_t ticket = 0; if (lane == 0) ticket = atomicAdd(&next_read, 1u); rid_nx = (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket); }
-  { const uint32_t r0 = min(rid_nx, rid_end - 1u); h_nx = hdrs[r0]; ro_nx = readout[r0]; }   // (tiles hold at least one candidate read)
+  TileRead nx;
+  draw_read(&next_read, rid_end, hdrs, readout, nx);
   if (n_tslots) for (;;) {
-    const uint32_t rid = rid_nx;
-    if (rid >= rid_end) break;
-    const MkpReadHdr h = h_nx; const MkpReadOut ro = ro_nx;
-    { uint32_t ticket = 0; if (lane == 0) ticket = atomicAdd(&next_read, 1u); rid_nx = (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket); }
-    { const uint32_t r0 = min(rid_nx, rid_end - 1u); h_nx = hdrs[r0]; ro_nx = readout[r0]; }
+    if (nx.rid >= rid_end) break;
+    const MkpReadHdr h = nx.h; const MkpReadOut ro = nx.ro;
+    draw_read(&next_read, rid_end, hdrs, readout, nx);
     if (h.ref_end <= T0h || h.ref_start >= T1h) continue;
-    if (KEYED && (h.flags >> MKP_RF_KEY_SHIFT) != key_filter) continue;   // --partition-tag: one pass per key
-    // the read's slot range in this tile; a read that covers no slot leaves nothing here
-    const int32_t span_a = max(h.ref_start, T0h), span_b = min(h.ref_end, T1h);
-    const uint32_t rs_a = sm.rank(span_a), rs_b = sm.rank(span_b);
-    if (FOCUS && rs_a == rs_b) continue;
-    const uint32_t aln = (h.flags & MKP_RF_REVERSE) ? 1u : 0u;
+    // the read's columns in this tile; a read that covers none leaves nothing here
+    const uint32_t rs_a = sm.rank(max(h.ref_start, T0h)), rs_b = sm.rank(min(h.ref_end, T1h));
+    if (rs_a == rs_b) continue;
     const uint8_t* __restrict__ seq = seqs + h.seq_off;
-    // depth walk: htslib pileup columns (match -> base, D -> delete, N -> ref-skip).  One lane per slot;
-    // the op covering a slot = (ops whose first slot is at or before it) - 1, counted with the wave's op-start bitmap.
-    uint32_t q_run = 0; int32_t r_run = h.ref_start; uint32_t c_first = 0;
-    {  // skip the 64-op CIGAR chunks that end before the tile: the host's per-chunk offsets say where the walk starts
-      const uint32_t nch = (h.n_cigar + 63u) >> 6;
-      if (nch > 1 && T0h > h.ref_start) {
-        const uint32_t rel = (uint32_t)(T0h - h.ref_start);
-        for (uint32_t b0 = 0; b0 < nch; b0 += 64) {
-          const uint32_t kidx = b0 + (uint32_t)lane;
-          const uint2 e = kidx < nch ? chunk_pfx[h.chunk_off + kidx] : make_uint2(0u, 0xffffffffu);
-          const uint32_t cnt = (uint32_t)__popcll(__ballot(kidx < nch && e.y <= rel));   // offsets ascend: a prefix of the lanes
-          if (cnt) {
-            q_run = (uint32_t)__builtin_amdgcn_readlane((int)e.x, (int)(cnt - 1u));
-            r_run = h.ref_start + (int32_t)__builtin_amdgcn_readlane((int)e.y, (int)(cnt - 1u));
-            c_first = 64u * (b0 + cnt - 1u);
-          }
-          if (cnt < 64u) break;
-        }
-      }
-    }
-    // the first chunk's CIGAR words are requested now, ahead of the event work; every later chunk is requested one chunk ahead
+    const CigarStart cs = skip_chunks_before(h, chunk_pfx, T0h);
+    uint32_t q_run = cs.q_run; int32_t r_run = cs.r_run;
+    // the first window's CIGAR words are requested now, ahead of the event work; every later window is requested one window ahead
     auto load2 = [&](uint32_t c) { uint2 r; const uint32_t i = c + 2u * (uint32_t)lane; r.x = i < h.n_cigar ? cigar[h.cigar_off + i] : 5u;
       r.y = i + 1u < h.n_cigar ? cigar[h.cigar_off + i + 1u] : 5u; return r; };
-    uint32_t w_next = 5u; uint2 w2_next = make_uint2(5u, 5u);   // focus kernel: two ops per lane
-    if (FOCUS) w2_next = load2(c_first); else w_next = (c_first + (uint32_t)lane < h.n_cigar) ? cigar[h.cigar_off + c_first + lane] : 5u;
-    // observed mod codes: +1 over the read's span (add_mod_codes_for_record, pileup/mod.rs:831-835)
-    if (!HEMI && ro.ok && lane < 2) {
-      uint32_t m = lane ? ro.obs[1] : ro.obs[0];
-      while (m) {
-        const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
-        if (WIDE) {
-          atomicAdd(&obs[(2u * sl + (uint32_t)lane) * S + rs_a], 1u);
-          if (rs_b < n_tslots) atomicAdd(&obs[(2u * sl + (uint32_t)lane) * S + rs_b], 0u - 1u);
-        } else {
-        atomicAdd(&obs[sl * S + rs_a], lane ? 0x10000u : 1u);
-        if (rs_b < n_tslots) atomicAdd(&obs[sl * S + rs_b], 0u - (lane ? 0x10000u : 1u));
-        }
-      }
-    }
-    if (HEMI) {
-      // get_duplex_mod_call (read_cache.rs:422-462) over the read's call events inside the tile (sorted by position): a '+' tally
-      // call at a slot = the positive-strand half; its partner is the read's '-' tally call on the same primary base at
-      // position + hemi_off (a few events away).  Both present -> one pattern (or Filtered) count and the NoCall the walk below
-      // adds for this base is taken back; otherwise the base stays a NoCall.  A record whose tags failed carries, instead of
-      // calls, the one NoCall per interval the reference's cache leaves for it (mkp_hemi_failed_reads).
-      if (ro.n_events) {
-        const MkpEvent* __restrict__ ev = events + h.event_off;
-        const uint32_t lo = h.ref_start >= T0h ? 0u : event_lower_bound(ev, ro.n_events, T0h);
-        const int32_t hoff = prm.hemi_off;
-        // threshold base of the call (read_cache.rs:147-150)
-        auto pb_of = [](uint32_t info) { const uint32_t b = (info >> 9) & 3u; return (((info >> 11) ^ (info >> 8)) & 1u) ? 3u - b : b; };
-        for (uint32_t k = lo + lane;; k += 64) {
-          bool in = k < ro.n_events;
-          MkpEvent e; e.pos = 0; e.info = 0;
-          if (in) { e = ev[k]; in = (int32_t)e.pos < T1h; }
-          if (in && sm.is_slot((int32_t)e.pos)) {
-            const uint32_t i = sm.rank((int32_t)e.pos);
-            if (!ro.ok) atomicAdd(&tal[(e.info & 0xffu) * S + i], 1u);
-            else if (!(e.info & 0x100u)) {
-              const uint32_t pbA = pb_of(e.info);
-              const int32_t q = (int32_t)e.pos + hoff;
-              uint32_t binfo = 0xffffffffu;
-              if (hoff >= 0) for (uint32_t j = k + 1u; j < ro.n_events; j++) {
-                const MkpEvent f = ev[j];
-                if ((int32_t)f.pos > q) break;
-                if ((int32_t)f.pos == q && (f.info & 0x100u) && pb_of(f.info) == pbA) { binfo = f.info; break; }
-              }
-              if (hoff <= 0 && binfo == 0xffffffffu) for (uint32_t j = k; j-- > 0u;) {
-                const MkpEvent f = ev[j];
-                if ((int32_t)f.pos < q) break;
-                if ((int32_t)f.pos == q && (f.info & 0x100u) && pb_of(f.info) == pbA) { binfo = f.info; break; }
-              }
-              if (binfo != 0xffffffffu && q >= 0) {
-                const uint32_t elA = prm.hemi_el[e.info & 0xffu], elB = prm.hemi_el[binfo & 0xffu];
-                const uint32_t cid = (elA == 0xffu || elB == 0xffu) ? (uint32_t)MKP_H_FAIL + pbA
-                    : (uint32_t)prm.hemi_pat_base[pbA] + elA * prm.hemi_nel[pbA] + elB;
-                atomicAdd(&tal[cid * S + i], 1u);
-                atomicAdd(&tal[(MKP_H_NC + pbA) * S + i], 0u - 1u);
-              }
-            }
-          }
-          if (!__any(in)) break;
-        }
-      }
-    } else
-    // the read's call events inside the tile (sorted by position)
-    if (ro.ok && ro.n_events && !(dbg & 2u)) {
+    uint2 w2_next = load2(cs.c_first);
+    // get_duplex_mod_call (read_cache.rs:422-462) over the read's call events inside the tile: a '+' tally call at a column = the
+    // positive-strand half; its partner is the read's '-' tally call on the same primary base at position + hemi_off (a few events
+    // away).  Both present -> one pattern (or Filtered) count and the NoCall the walk below adds for this base is taken back;
+    // otherwise the base stays a NoCall.  A record whose tags failed carries, instead of calls, the one NoCall per interval the
+    // reference's cache leaves for it (mkp_hemi_failed_reads).
+    if (ro.n_events) {
       const MkpEvent* __restrict__ ev = events + h.event_off;
-      const uint32_t lo = h.ref_start >= T0h ? 0u : event_lower_bound(ev, ro.n_events, T0h);   // a read that starts in the tile: no search
-      for (uint32_t k = lo + lane;; k += 64) {
-        bool in = k < ro.n_events;
-        MkpEvent e; e.pos = 0; e.info = 0;
-        if (in) { e = ev[k]; in = (int32_t)e.pos < T1h; }
-        if (in && sm.is_slot((int32_t)e.pos)) {
-          const uint32_t i = sm.rank((int32_t)e.pos);
-          if (WIDE) {   // [8] tally strand of the call, [11] of the read's base
-            atomicAdd(&tal[(2u * (e.info & 0xffu) + ((e.info >> 8) & 1u)) * S + i], 1u);
-            if (e.info & (1u << 12)) atomicAdd(&tal[(2u * (MKP_C_NC + ((e.info >> 9) & 3u)) + ((e.info >> 11) & 1u)) * S + i], 0u - 1u);
-          } else {
-          atomicAdd(&tal[(e.info & 0xffu) * S + i], (e.info & 0x100u) ? 0x10000u : 1u);
-          if (e.info & (1u << 12))  // the base is a call, not a NoCall (pileup/mod.rs:889-938)
-            atomicAdd(&tal[(MKP_C_NC + ((e.info >> 9) & 3u)) * S + i], 0u - ((e.info & 0x800u) ? 0x10000u : 1u));
-          }
+      const int32_t hoff = prm.hemi_off;
+      // threshold base of the call (read_cache.rs:147-150)
+      auto pb_of = [](uint32_t info) { const uint32_t b = (info >> 9) & 3u; return (((info >> 11) ^ (info >> 8)) & 1u) ? 3u - b : b; };
+      for_tile_events(ev, ro.n_events, h.ref_start >= T0h, T0h, T1h, [&](uint32_t k, const MkpEvent& e) {
+        if (!sm.is_slot((int32_t)e.pos)) return;
+        const uint32_t i = sm.rank((int32_t)e.pos);
+        if (!ro.ok) { atomicAdd(&tal[(e.info & 0xffu) * S + i], 1u); return; }
+        if (e.info & 0x100u) return;
+        const uint32_t pbA = pb_of(e.info);
+        const int32_t q = (int32_t)e.pos + hoff;
+        uint32_t binfo = 0xffffffffu;
+        if (hoff >= 0) for (uint32_t j = k + 1u; j < ro.n_events; j++) {
+          const MkpEvent f = ev[j];
+          if ((int32_t)f.pos > q) break;
+          if ((int32_t)f.pos == q && (f.info & 0x100u) && pb_of(f.info) == pbA) { binfo = f.info; break; }
         }
-        if (!__any(in)) break;
-      }
+        if (hoff <= 0 && binfo == 0xffffffffu) for (uint32_t j = k; j-- > 0u;) {
+          const MkpEvent f = ev[j];
+          if ((int32_t)f.pos < q) break;
+          if ((int32_t)f.pos == q && (f.info & 0x100u) && pb_of(f.info) == pbA) { binfo = f.info; break; }
+        }
+        if (binfo != 0xffffffffu && q >= 0) {
+          const uint32_t elA = prm.hemi_el[e.info & 0xffu], elB = prm.hemi_el[binfo & 0xffu];
+          const uint32_t cid = (elA == 0xffu || elB == 0xffu) ? (uint32_t)MKP_H_FAIL + pbA
+              : (uint32_t)prm.hemi_pat_base[pbA] + elA * prm.hemi_nel[pbA] + elB;
+          atomicAdd(&tal[cid * S + i], 1u);
+          atomicAdd(&tal[(MKP_H_NC + pbA) * S + i], 0u - 1u);
+        }
+      });
     }
-    const uint32_t inc = HEMI || WIDE ? 1u : (aln ? 0x10000u : 1u);   // this alignment strand's half of the packed tallies (hemi: plain counters)
-    // WIDE: this alignment strand's plane of a row (byte offset) and the distance between two rows' planes
-    const uint32_t aln_plane = WIDE ? aln * S * 4u : 0u, row_bytes = WIDE ? S * 8u : S * 4u;
-    const uint8_t* __restrict__ lut = &rowlut[0][0][0];
-    const uint32_t aln2 = HEMI ? 0u : aln << 1;   // hemi: the primary base is the SEQ base as stored, whatever the strand (duplex.rs:308-313)
-    const uint32_t lanebase = lds_addr(tal) + 4u * (uint32_t)lane;   // LDS byte address of (row 0, slot `lane`)
-    const uint32_t fposbase = lds_addr(fpos) + 4u * (uint32_t)lane;
+    const uint8_t* __restrict__ lut = &rowlut[0][0][0];   // (the primary base is the SEQ base as stored, whatever the strand: duplex.rs:308-313)
     const uint32_t qbase = (uint32_t)(0 - h.ref_start) - (1u << 26);   // query index = position + qbase + packed offset
     const uint32_t last_byte = (h.l_seq - 1u) >> 1;
-    if (FOCUS && (dbg & 1u)) {} else
-    if (FOCUS) {
-      // Focus runs: the walk is driven by the slots, not by the ops, 128 CIGAR ops per window (two per lane).  The window's slots
-      // [S_lo, S_hi) are enumerated 64 at a time (lane = slot, position from the tile's slot list); the lane holding a position's
-      // op is the number of lanes whose inclusive reference end is at or before it (6 ds_bpermute steps over the prefix sums the
-      // window has anyway), three more bpermutes bring that lane's split point and the packed (query offset, kind) of its two
-      // ops.  No per-op rank queries, no compaction, no op-start bitmap; deletions are counted directly.
-      // Phase 1 (here): the slots get their packed (query index, kind); phase 2 (after the loop) fetches the bases of all the
-      // read's slots with several loads in flight — the SEQ loads do not sit in the CIGAR dependency chain.
-      for (uint32_t c0 = c_first; c0 < h.n_cigar; c0 += 128) {
-        if (r_run >= T1h) break;
-        const uint2 w2 = w2_next;
-        if (c0 + 128u < h.n_cigar) w2_next = load2(c0 + 128u);
-        const uint32_t op0 = w2.x & 15u, len0 = w2.x >> 4, op1 = w2.y & 15u, len1 = w2.y >> 4;
-        const uint32_t ql0 = op_consumes_query(op0) ? len0 : 0u, rl0 = op_consumes_ref(op0) ? len0 : 0u;
-        const uint32_t ql1 = op_consumes_query(op1) ? len1 : 0u, rl1 = op_consumes_ref(op1) ? len1 : 0u;
-        const uint32_t qe = wave_incl_scan(ql0 + ql1), re = wave_incl_scan(rl0 + rl1);
-        const uint32_t Qtot = (uint32_t)__builtin_amdgcn_readlane((int)qe, 63), Rtot = (uint32_t)__builtin_amdgcn_readlane((int)re, 63);
-        const int32_t c_lo = max(r_run, T0h), c_hi = min(r_run + (int32_t)Rtot, T1h);
-        if (c_lo < c_hi) {
-          const uint32_t S_lo = sm.rank(c_lo), S_hi = sm.rank(c_hi);
-          if (S_lo < S_hi) {
-            const uint32_t qs0 = q_run + qe - (ql0 + ql1), qs1 = qs0 + ql0;
-            const uint32_t mid = re - rl1;                                     // window-relative reference offset where the lane's second op starts
-            const int32_t rs0 = r_run + (int32_t)(re - (rl0 + rl1)), rs1 = r_run + (int32_t)mid;
-            const uint32_t kind0 = op_is_match(op0) ? 0u : (op0 == 2 ? 1u : 2u), kind1 = op_is_match(op1) ? 0u : (op1 == 2 ? 1u : 2u);
-            const uint32_t pk0 = ((uint32_t)((int32_t)qs0 - (rs0 - h.ref_start) + (1 << 26)) << 5) | (kind0 << 3);  // q = (pos - ref_start) + D
-            const uint32_t pk1 = ((uint32_t)((int32_t)qs1 - (rs1 - h.ref_start) + (1 << 26)) << 5) | (kind1 << 3);
-            // ref-skips: the read is not in these columns (alignment.is_refskip())
-            if (!HEMI && ro.ok && __any((op0 == 3 && rl0 > 0) || (op1 == 3 && rl1 > 0))) {
-              for (int j = 0; j < 2; j++) {
-                const bool skipop = j ? (op1 == 3 && rl1 > 0) : (op0 == 3 && rl0 > 0);
-                const int32_t a0 = j ? rs1 : rs0, b0 = a0 + (int32_t)(j ? rl1 : rl0);
-                const int32_t pa = min(max(a0, c_lo), c_hi), pb = min(max(b0, c_lo), c_hi);
-                const uint32_t sa = sm.rank(pa), sb = sm.rank(pb);
-                if (skipop && sa < sb) for (uint32_t s = 0; s < 2; s++) {
-                  uint32_t m = ro.obs[s];
-                  while (m) {
-                    const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
-                    atomicAdd(&obs[sl * S + sa], 0u - (s ? 0x10000u : 1u));
-                    if (sb < n_tslots) atomicAdd(&obs[sl * S + sb], s ? 0x10000u : 1u);
-                  }
-                }
-              }
-            }
-            for (uint32_t s0 = S_lo; s0 < S_hi; s0 += 64) {
-              const uint32_t c = s0 + (uint32_t)lane;
-              const bool valid = c < S_hi;
-              const int32_t p = valid ? fpos[c] : c_lo;
-              const uint32_t rel = (uint32_t)(p - r_run);
-              const int ol = find_op(re, rel) & 63;
-              const uint32_t o_mid = (uint32_t)__shfl((int)mid, ol, 64), o_pk0 = (uint32_t)__shfl((int)pk0, ol, 64),
-                  o_pk1 = (uint32_t)__shfl((int)pk1, ol, 64);
-              const uint32_t my_pk = rel < o_mid ? o_pk0 : o_pk1;
-              const uint32_t qq = (uint32_t)p + qbase + (my_pk >> 5);
-              if (valid) qk[c - rs_a] = (qq << 2) | ((my_pk >> 3) & 3u);
-            }
-          }
-        }
-        q_run += Qtot; r_run += (int32_t)Rtot;
-      }
-    } else
-    for (uint32_t c0 = c_first; c0 < h.n_cigar; c0 += 64) {
+    // phase 1.  A window's columns [S_lo, S_hi) are enumerated 64 at a time (lane = column, position from the slot map's list); the lane
+    // holding a position's op is the number of lanes whose inclusive reference end is at or before it (6 ds_bpermute steps over the
+    // prefix sums the window has anyway), three more bpermutes bring that lane's split point and the packed (query offset, kind) of
+    // its two ops.  No per-op rank queries, no compaction, no op-start bitmap.
+    if (!(dbg & 1u))
+    for (uint32_t c0 = cs.c_first; c0 < h.n_cigar; c0 += 128) {
       if (r_run >= T1h) break;
-      const uint32_t w = w_next;
-      if (c0 + 64u < h.n_cigar) w_next = (c0 + 64u + (uint32_t)lane < h.n_cigar) ? cigar[h.cigar_off + c0 + 64u + lane] : 5u;
-      const uint32_t op = w & 15u, len = w >> 4;
-      const uint32_t qlen = op_consumes_query(op) ? len : 0u, rlen = op_consumes_ref(op) ? len : 0u;
-      const uint32_t qe = wave_incl_scan(qlen), re = wave_incl_scan(rlen);
-      const uint32_t qs = q_run + qe - qlen;
-      const int32_t rs = r_run + (int32_t)(re - rlen);
+      const uint2 w2 = w2_next;
+      if (c0 + 128u < h.n_cigar) w2_next = load2(c0 + 128u);
+      const uint32_t op0 = w2.x & 15u, len0 = w2.x >> 4, op1 = w2.y & 15u, len1 = w2.y >> 4;
+      const uint32_t ql0 = op_consumes_query(op0) ? len0 : 0u, rl0 = op_consumes_ref(op0) ? len0 : 0u;
+      const uint32_t ql1 = op_consumes_query(op1) ? len1 : 0u, rl1 = op_consumes_ref(op1) ? len1 : 0u;
+      const uint32_t qe = wave_incl_scan(ql0 + ql1), re = wave_incl_scan(rl0 + rl1);
       const uint32_t Qtot = (uint32_t)__builtin_amdgcn_readlane((int)qe, 63), Rtot = (uint32_t)__builtin_amdgcn_readlane((int)re, 63);
       const int32_t c_lo = max(r_run, T0h), c_hi = min(r_run + (int32_t)Rtot, T1h);
       if (c_lo < c_hi) {
-        // the op's slots inside the tile: [sa, sb)
-        const int32_t pa = min(max(rs, c_lo), c_hi), pb = min(max(rs + (int32_t)rlen, c_lo), c_hi);
-        const uint32_t sa = sm.rank(pa), sb = sm.rank(pb);
-        const bool covers = rlen > 0 && sa < sb;
-        if (op == 3 && ro.ok && covers) {  // ref-skip: the read is not in these columns (alignment.is_refskip())
-          for (uint32_t s = 0; s < 2; s++) {
-            uint32_t m = ro.obs[s];
-            while (m) {
-              const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
-              if (WIDE) {
-                atomicAdd(&obs[(2u * sl + s) * S + sa], 0u - 1u);
-                if (sb < n_tslots) atomicAdd(&obs[(2u * sl + s) * S + sb], 1u);
-              } else {
-              atomicAdd(&obs[sl * S + sa], 0u - (s ? 0x10000u : 1u));
-              if (sb < n_tslots) atomicAdd(&obs[sl * S + sb], s ? 0x10000u : 1u);
-              }
-            }
-          }
-        }
-        if (op == 2 && covers) {  // deletion columns (alignment.is_del()): +1/-1 on the strand's DEL row, summed after the barrier
-          const uint32_t del_row = WIDE ? (2u * MKP_C_DEL + aln) * S : MKP_C_DEL * S;
-          atomicAdd(&tal[del_row + sa], inc);
-          if (sb < n_tslots) atomicAdd(&tal[del_row + sb], 0u - inc);
-        }
-        const uint32_t S_lo = sm.rank(c_lo), S_hi = sm.rank(c_hi);   // the chunk's slots
+        const uint32_t S_lo = sm.rank(c_lo), S_hi = sm.rank(c_hi);
         if (S_lo < S_hi) {
-        // compact the window's slot-covering ops to the low lanes: {first slot, packed(query offset, kind)}
-        const unsigned long long refbal = __ballot(covers);
-        const uint32_t nref = (uint32_t)__popcll(refbal);
-        const uint32_t ci = (uint32_t)__popcll(refbal & lanemask_lt());
-        const uint32_t kind = op_is_match(op) ? 0u : (op == 2 ? 1u : 2u);
-        // q = (pos - ref_start) + D; kind sits where it ORs into the row
-        const uint32_t pk = ((uint32_t)((int32_t)qs - (rs - h.ref_start) + (1 << 26)) << 5) | (kind << 3);
-        if (covers) comp[ci] = make_uint2(sa, pk);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint2 cc = comp[lane];
-        const bool cvalid = (uint32_t)lane < nref;
-        const uint32_t c_sa = cc.x; const uint32_t c_pk = cc.y;
-        const uint32_t c_key = cvalid ? c_sa : 0x7fffffffu;
-        const uint32_t e_lo = lds_addr(tal) + 4u * S_lo, e_span = 4u * (S_hi - S_lo);
-        const bool mark = cvalid && c_sa > S_lo;
-        const uint32_t mrel = c_sa - 1u;   // bit m set <=> an op's first slot is m+1: "starts at or before slot c" = bits strictly below c
-        if (mark) atomicOr(&bm[mrel >> 5], 1u << (mrel & 31u));
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // 64 slots per step, aligned so a step reads one aligned 64-bit window of the bitmap;
-        // UNROLL steps are issued together (bitmap read -> bpermute -> SEQ byte load) before any tally update.
-        // ops started at or before the first slot of window kk: a ballot over the compacted starts (no LDS dependency)
-        const uint32_t k0 = S_lo >> 6, k1 = (S_hi - 1u) >> 6;
-        // Only the first and the last group of a chunk hold out-of-range lanes or repeated (clamped) windows; the groups in
-        // between run a version without the clamps and the range check.
-        auto group = [&](uint32_t kb, auto edge_c) {
-          constexpr bool EDGE = decltype(edge_c)::value;
-          uint32_t pkv[UNROLL], byte[UNROLL], qq[UNROLL], idx[UNROLL], kk[UNROLL]; uint2 Wd[UNROLL]; int32_t pp[UNROLL];
-          // stage by stage across the UNROLL windows, so the LDS reads, the bpermutes and the global loads of the group overlap
-#pragma unroll
-          for (int j = 0; j < UNROLL; j++) kk[j] = EDGE ? min(kb + (uint32_t)j, k1) : kb + (uint32_t)j;
-#pragma unroll
-          for (int j = 0; j < UNROLL; j++) Wd[j] = *reinterpret_cast<const uint2*>(bm + 2u * kk[j]);
-#pragma unroll
-          for (int j = 0; j < UNROLL; j++) {
-            if (FOCUS) pp[j] = (64u * kk[j] + (uint32_t)lane < n_tslots)
-                ? *(const __attribute__((address_space(3))) int32_t*)(uintptr_t)(fposbase + 256u * kk[j]) : T0h;
-            else pp[j] = T0h + (int32_t)(64u * kk[j]) + lane;
+          const uint32_t qs0 = q_run + qe - (ql0 + ql1), qs1 = qs0 + ql0;
+          const uint32_t mid = re - rl1;                                     // window-relative reference offset where the lane's second op starts
+          const int32_t rs0 = r_run + (int32_t)(re - (rl0 + rl1)), rs1 = r_run + (int32_t)mid;
+          const uint32_t kind0 = op_is_match(op0) ? 0u : (op0 == 2 ? 1u : 2u), kind1 = op_is_match(op1) ? 0u : (op1 == 2 ? 1u : 2u);
+          const uint32_t pk0 = ((uint32_t)((int32_t)qs0 - (rs0 - h.ref_start) + (1 << 26)) << 5) | (kind0 << 3);  // q = (pos - ref_start) + D
+          const uint32_t pk1 = ((uint32_t)((int32_t)qs1 - (rs1 - h.ref_start) + (1 << 26)) << 5) | (kind1 << 3);
+          for (uint32_t s0 = S_lo; s0 < S_hi; s0 += 64) {
+            const uint32_t c = s0 + (uint32_t)lane;
+            const bool valid = c < S_hi;
+            const int32_t p = valid ? fpos[c] : c_lo;
+            const uint32_t rel = (uint32_t)(p - r_run);
+            const int ol = find_op(re, rel) & 63;
+            const uint32_t o_mid = (uint32_t)__shfl((int)mid, ol, 64), o_pk0 = (uint32_t)__shfl((int)pk0, ol, 64),
+                o_pk1 = (uint32_t)__shfl((int)pk1, ol, 64);
+            const uint32_t my_pk = rel < o_mid ? o_pk0 : o_pk1;
+            const uint32_t qq = (uint32_t)p + qbase + (my_pk >> 5);
+            if (valid) qk[c - rs_a] = (qq << 2) | ((my_pk >> 3) & 3u);
           }
-#pragma unroll
-          for (int j = 0; j < UNROLL; j++) {
-            const uint32_t wstart = 64u * kk[j];
-            idx[j] = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(c_key <= (EDGE ? max(S_lo, wstart) : wstart))) - 1u;
-          }
-#pragma unroll
-          for (int j = 0; j < UNROLL; j++)
-            pkv[j] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((idx[j] + __builtin_amdgcn_mbcnt_hi(Wd[j].y,
-                __builtin_amdgcn_mbcnt_lo(Wd[j].x, 0u))) << 2), (int)c_pk);
-#pragma unroll
-          for (int j = 0; j < UNROLL; j++) {
-            qq[j] = (uint32_t)pp[j] + qbase + (pkv[j] >> 5);
-            byte[j] = seq[min(qq[j] >> 1, last_byte)];   // lanes on D/N ops or outside the span read a clamped (ignored) byte
-          }
-#pragma unroll
-          for (int j = 0; j < UNROLL; j++) {
-            const uint32_t t = (qq[j] & 1u) | aln2;
-            const uint32_t rowt = (uint32_t)lut[(t << 8) | byte[j]] | (pkv[j] & 0x18u);   // >= 8: not ACGT, or the lane sits on a D/N op
-            const uint32_t la = lanebase + 256u * kk[j];
-            bool ok = rowt < 8u;
-            if (EDGE) ok = ok && (la - e_lo) < e_span && kb + (uint32_t)j <= k1;
-            if (ok) lds_add(la + (WIDE ? __umul24(rowt, row_bytes) + aln_plane : __umul24(rowt, TS4)), inc);
-          }
-        };
-        for (uint32_t kb = k0; kb <= k1; kb += UNROLL) {
-          if (kb == k0 || kb + UNROLL > k1) group(kb, std::true_type{}); else group(kb, std::false_type{});
-        }
-        if (mark) bm[mrel >> 5] = 0;
         }
       }
       q_run += Qtot; r_run += (int32_t)Rtot;
     }
-    if (FOCUS && !(dbg & 9u)) {
-      // phase 2: bases of the read's slots [rs_a, rs_b) in this tile, 4 x 64 slots per round with their SEQ loads in flight together
-      // (slots the CIGAR phase did not reach — a read whose CIGAR ends early — keep kind 3 = nothing)
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (!(dbg & 9u)) {
+      // phase 2: bases of the read's columns [rs_a, rs_b), 4 x 64 columns per round with their SEQ loads in flight together
+      // (columns the CIGAR phase did not reach — a read whose CIGAR ends early — keep kind 3 = nothing)
+      wave_lds_sync();
       const uint32_t nsl = rs_b - rs_a;
       for (uint32_t g0 = 0; g0 < nsl; g0 += 256) {
         uint32_t v[4], byte[4];
@@ -1551,67 +1514,38 @@ __device__ __forceinline__ void pileup_tiles_body(const MkpReadHdr* __restrict__
 #pragma unroll
         for (int j = 0; j < 4; j++) {
           const uint32_t i = g0 + 64u * j + (uint32_t)lane, kind = v[j] & 3u;
-          const uint32_t t = ((v[j] >> 2) & 1u) | aln2;
-          const uint32_t rowt = (uint32_t)lut[(t << 8) | byte[j]];
+          const uint32_t rowt = (uint32_t)lut[(((v[j] >> 2) & 1u) << 8) | byte[j]];   // NoCall row of the base; >= 8: not ACGT
           const uint32_t a0 = lds_addr(tal) + 4u * (rs_a + i);
-          // hemi: a failed record gives no feature (its one NoCall came in as an event)
-          if (kind == 0u && rowt < 8u && (!HEMI || ro.ok)) lds_add(a0 + __umul24(rowt, TS4), inc);
-          if (kind == 1u) lds_add(a0 + __umul24((uint32_t)MKP_C_DEL, TS4), inc);   // alignment.is_del()
+          // a failed record gives no feature (its one NoCall came in as an event)
+          if (kind == 0u && rowt < 8u && ro.ok) lds_add(a0 + __umul24(rowt, TS4), 1u);
+          if (kind == 1u) lds_add(a0 + __umul24((uint32_t)MKP_H_DEL, TS4), 1u);   // alignment.is_del(): counted directly
           if (i < nsl) qk[i] = 3u;   // left clean for the wave's next read
         }
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_sync();
     }
   }
+  // (no difference arrays here, so no prefix-sum phase: deletions are counted per column above, and a duplex column has no
+  // observed-code rows)
   __syncthreads();
-  // difference arrays -> counts, in place and still packed (the sums are exact): deletions, then observed codes per slot (WIDE: per plane)
-  constexpr uint32_t NP = WIDE ? 2u : 1u;   // planes per row
-  for (uint32_t a = wave + (FOCUS ? 1u : 0u); a < NP * (n_oslots + 1u); a += PILEUP_WAVES) {   // (focus runs count deletions directly)
-    uint32_t* __restrict__ arr = WIDE ? (a < 2u ? tal + (2u * MKP_C_DEL + a) * S : obs + (a - 2u) * S) : a == 0 ? tal + MKP_C_DEL * S : obs + (a - 1u) * S;
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < n_tslots; b0 += 64) {
-      const uint32_t v = (b0 + lane < n_tslots) ? arr[b0 + lane] : 0u;
-      const uint32_t sc = wave_incl_scan(v);
-      if (b0 + lane < n_tslots) arr[b0 + lane] = sc + carry;
-      carry += (uint32_t)__builtin_amdgcn_readlane((int)sc, 63);
-    }
-  }
-  if (threadIdx.x == 0) scan_carry = 0;
-  __syncthreads();
-  // rows of the tile straight from LDS: count, reserve, write (slot order = position order).  One tile per workgroup: nothing of
-  // the accumulate phase is live here and nothing of this phase is live there, so neither raises the other's register count
-  if (dbg & 4u) {}
-  // dense tiles: row-major emission; the row map lives in the per-wave scratch of the accumulate phase (dead behind the barrier above)
-  else if (!FOCUS && !HEMI)
-    emit_dense_rows<WIDE>(tal, S, n_counters, n_tslots, T0h, tl, KEYED ? key_run * n_tiles + tix : tix, key_filter, prm, rowprog,
-        lds + tal_words + focus_total, min(8192u, PILEUP_WAVES * wave_words),
-                    rows_base, row_cursor, tile_row_off, tile_row_cnt, dev_err, wave_tot, &row_base, &scan_carry);
-  else emit_tile_rows<FOCUS, HEMI>(tal, sm, n_tslots, tl, KEYED ? key_run * n_tiles + tix : tix, key_filter, &prm, focus, combos_l, rows_base,
-      row_cursor, tile_row_off, tile_row_cnt, dev_err, wave_tot, &row_base, &scan_carry);
-  }
+  if (!(dbg & 4u))
+    emit_hemi_rows(tal, sm, n_tslots, tl, tix, prm, rows_base, row_cursor, tile_row_off, tile_row_cnt, dev_err, wave_tot, &row_base, &scan_carry);
 }
 
-#define PILEUP_PARAMS const MkpReadHdr* __restrict__ hdrs, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ seqs, \
-                 const MkpEvent* __restrict__ events, const MkpReadOut* __restrict__ readout, const MkpTile* __restrict__ tiles, uint32_t n_tiles, \
-                 const MkpRunParams* __restrict__ prmp, const uint32_t* __restrict__ slotbm, const uint8_t* __restrict__ focus, const MkpCombo* __restrict__ combos, \
-                 uint32_t* __restrict__ rows_base /* 11 SoA arrays of row_capacity entries */, uint32_t* __restrict__ row_cursor, uint32_t* __restrict__ tile_row_off, uint32_t* __restrict__ tile_row_cnt, \
-                 const uint2* __restrict__ chunk_pfx, uint32_t* __restrict__ dev_err, uint32_t key_arg /* KEYED kernels: partition key to tally | index of this key pass << 16 */
-#define PILEUP_PASS hdrs, cigar, seqs, events, readout, tiles, n_tiles, prmp, slotbm, focus, combos, rows_base, row_cursor, tile_row_off, tile_row_cnt, chunk_pfx, dev_err, key_arg
-// every position owns a tally column (no focus positions): the dense walk, 4 windows of 64 positions in flight
-extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles(PILEUP_PARAMS) { pileup_tiles_body<false, 4, false>(PILEUP_PASS); }
-// (focus positions — --cpg / --motif / --include-bed — go through the slot pipeline of mkp_slots.hip; the FOCUS instantiation of this body
-// serves pileup-hemi below)
+// every position owns a tally column (no focus positions)
+extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles(PILEUP_PARAMS, uint32_t key_arg /* unused */) {
+  dense_tiles_body<false, false>(PILEUP_PASS, key_arg); }
 // --partition-tag: the same kernel tallying only the reads of one partition key per launch
-extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_keyed(PILEUP_PARAMS) {
-  pileup_tiles_body<false, 4, true>(PILEUP_PASS); }
+extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_keyed(PILEUP_PARAMS, uint32_t key_arg) {
+  dense_tiles_body<true, false>(PILEUP_PASS, key_arg); }
 // shards whose deepest column may hold more than 65 535 records: u32 tallies per strand
-extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_wide(PILEUP_PARAMS) {
-  pileup_tiles_body<false, 4, false, false, true>(PILEUP_PASS); }
-extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_keyed_wide(PILEUP_PARAMS) {
-  pileup_tiles_body<false, 4, true, false, true>(PILEUP_PASS); }
-// pileup-hemi: the focus kernel with duplex pattern tallies
-extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_hemi(PILEUP_PARAMS) {
-  pileup_tiles_body<true, 1, false, true>(PILEUP_PASS); }
+extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_wide(PILEUP_PARAMS, uint32_t key_arg /* unused */) {
+  dense_tiles_body<false, true>(PILEUP_PASS, key_arg); }
+extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_keyed_wide(PILEUP_PARAMS, uint32_t key_arg) {
+  dense_tiles_body<true, true>(PILEUP_PASS, key_arg); }
+// pileup-hemi
+extern "C" __global__ void __launch_bounds__(PILEUP_THREADS, 8) mkp_pileup_tiles_hemi(PILEUP_PARAMS, const uint32_t* __restrict__ slotbm) {
+  hemi_tiles_body(PILEUP_PASS, slotbm); }
 
 // Duplex reads decoded one group per wave (decode_read_sparse): interleave the two position-sorted event lists of a read into the
 // front of its slice and combine the two summaries.  The record fails if either group failed (add_record returns at the first
@@ -1934,25 +1868,22 @@ extern "C" hipError_t mkp_pileup_set_lds(uint32_t accum_bytes) {
   return hipSuccess;
 }
 
-extern "C" hipError_t mkp_launch_pileup(hipStream_t st, uint32_t lds_bytes, int focus_mode, const MkpReadHdr* hdrs, const uint32_t* cigar,
-    const uint8_t* seqs,
-                                        const MkpEvent* events, const MkpReadOut* readout, const MkpTile* tiles, uint32_t n_tiles,
-                                            const MkpRunParams* prm_dev,
-                                        const uint32_t* slotbm, const uint8_t* focus, const MkpCombo* combos, const MkpRowsDev* rows,
-                                            uint32_t* row_cursor,
-                                        uint32_t* tile_row_off, uint32_t* tile_row_cnt, const uint32_t* chunk_pfx, uint32_t* dev_err,
-                                            uint32_t key_filter, uint32_t key_slot, bool wide) {
+// hemi: pileup-hemi (slotbm = the run's slot bitmap); otherwise a run without focus positions (slotbm unused)
+extern "C" hipError_t mkp_launch_pileup(hipStream_t st, uint32_t lds_bytes, bool hemi, const MkpReadHdr* hdrs, const uint32_t* cigar,
+                                        const uint8_t* seqs, const MkpEvent* events, const MkpReadOut* readout, const MkpTile* tiles,
+                                        uint32_t n_tiles, const MkpRunParams* prm_dev, const uint32_t* slotbm, const MkpRowsDev* rows,
+                                        uint32_t* row_cursor, uint32_t* tile_row_off, uint32_t* tile_row_cnt, const uint32_t* chunk_pfx,
+                                        uint32_t* dev_err, uint32_t key_filter, uint32_t key_slot, bool wide) {
   if (!n_tiles) return hipSuccess;
   const bool keyed = key_filter != MKP_NO_KEY_FILTER;
   const uint32_t key_arg = keyed ? ((key_filter & 0xffffu) | (key_slot << 16)) : 0u;
   const uint32_t grid = n_tiles;   // one workgroup per tile
   // ONE build of each accumulate kernel: what a one-shot shard pass launches is what a re-launch on the resident shard launches
-#define MKP_PILEUP_LAUNCH(K) hipLaunchKernelGGL(K, dim3(grid), dim3(PILEUP_THREADS), lds_bytes, st, hdrs, cigar, seqs, events, readout, tiles, n_tiles, prm_dev, slotbm, focus, combos, rows->pos, \
-                       row_cursor, tile_row_off, tile_row_cnt, reinterpret_cast<const uint2*>(chunk_pfx), dev_err, key_arg)
-  if (focus_mode == 2) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_hemi);   // pileup-hemi
-  else if (focus_mode) return hipErrorInvalidValue;   // (focus runs are the slot pipeline's: mkp_launch_stream)
-  else if (wide) { if (keyed) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_keyed_wide); else MKP_PILEUP_LAUNCH(mkp_pileup_tiles_wide); }   // u32 tallies
-  else { if (keyed) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_keyed); else MKP_PILEUP_LAUNCH(mkp_pileup_tiles); }
+#define MKP_PILEUP_LAUNCH(K, LAST) hipLaunchKernelGGL(K, dim3(grid), dim3(PILEUP_THREADS), lds_bytes, st, hdrs, cigar, seqs, events, readout, tiles, \
+                       n_tiles, prm_dev, rows->pos, row_cursor, tile_row_off, tile_row_cnt, reinterpret_cast<const uint2*>(chunk_pfx), dev_err, LAST)
+  if (hemi) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_hemi, slotbm);
+  else if (wide) { if (keyed) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_keyed_wide, key_arg); else MKP_PILEUP_LAUNCH(mkp_pileup_tiles_wide, key_arg); }   // u32 tallies
+  else { if (keyed) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_keyed, key_arg); else MKP_PILEUP_LAUNCH(mkp_pileup_tiles, key_arg); }
   return hipGetLastError();
 }
 

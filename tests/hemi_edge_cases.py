@@ -1,6 +1,6 @@
 """Directed duplex modBAMs for the `pileup-hemi` kernels: reads on the 64-entry rank windows of mkp_merge_duplex, '+' / '-' pairs whose
 halves sit in different 64-lane batches of a read's merged event list or either side of a tile, interval, region or shard seam, CIGARs
-on the 128-op window of the FOCUS walk and the 64-op window of the event decoders, reads on the 4096-base step of the SPARSE decoder,
+on the 128-op window of the hemi tile walk and the 64-op window of the event decoders, reads on the 4096-base step of the SPARSE decoder,
 and records whose tags fail over 1, 2 and 5 intervals.
 
 Built on the writers of tests/bamfuzz.py and the Case / Layer of tests/cigar_edge_cases.py, whose builders stay as they are.  Every
@@ -263,7 +263,7 @@ def keep_plus_half_at(index, motif, ref):
 
 
 def partner_edges(prefix):
-    """2. the partner search of the HEMI tile kernel: pairs whose '+' half has index 63 / 64 / 127 / 128 in the read's merged list, per
+    """2. the partner search of the hemi tile kernel: pairs whose '+' half has index 63 / 64 / 127 / 128 in the read's merged list, per
     motif; pairs either side of tile, interval, region and shard seams; every way a partner can be missing."""
     r = random.Random(71)
     ref = make_ref(r, 60_000)
@@ -335,7 +335,7 @@ CIGAR_EDGE_INDEXES = ([63, 127, 255], [64, 128, 256])     # the last op of a 64-
 
 
 def cigar_windows(prefix):
-    """3. op counts on the edges of the FOCUS walk's 128-op window (two ops per lane) and the event decoders' 64-op window; D / I / N / P
+    """3. op counts on the edges of the hemi tile walk's 128-op window (two ops per lane) and the event decoders' 64-op window; D / I / N / P
     on the last op of a window and the first of the next, a CpG on the match run on each side."""
     r = random.Random(81)
     ref = make_ref(r, 90_000)
