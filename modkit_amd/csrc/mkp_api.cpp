@@ -27,12 +27,9 @@ hipError_t mkp_launch_pileup(hipStream_t, uint32_t /*LDS bytes*/, bool /*pileup-
                              uint32_t* /*tile row offsets*/, uint32_t* /*tile row counts*/, const uint32_t* /*chunk offsets*/,
                                  uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, bool /*wide tallies*/);
 hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_t, const void* /*base-and-call plane*/,
-    const uint16_t* /*16-bit CIGAR*/, const MkpReadHdr*,
-    const uint32_t* /*cover read ids*/,
-    uint32_t, const uint32_t*, const uint8_t*, const MkpTagRef*,
-                            const uint32_t*, const uint8_t*, const MkpLayout*, const MkpFusedDesc*, const MkpRunParams*,
-                                const uint32_t* /*slot positions*/, const MkpSlotEnt* /*slot-entry lists*/, uint8_t* /*feature stream*/, MkpVisit*, MkpEvent*,
-                                MkpReadOut*, uint32_t*);
+    const uint16_t* /*16-bit CIGAR*/, const MkpReadHdr*, const uint32_t* /*cover read ids*/, uint32_t, const uint32_t* /*CIGAR*/,
+    const uint8_t* /*SEQ*/, const uint8_t* /*ML*/, const MkpFusedDesc*, const MkpRunParams*, const uint32_t* /*slot positions*/,
+    const MkpSlotEnt* /*slot-entry lists*/, uint8_t* /*feature stream*/, MkpVisit*, MkpEvent*, MkpReadOut*);
 hipError_t mkp_launch_call_plane(hipStream_t, MkpWork*, uint32_t, const uint8_t* /*SEQ*/, const uint32_t* /*ranks*/, const MkpFusedDesc*,
     void* /*plane*/, unsigned long long* /*SEQ bytes the decoder reads of MKP_RF_SEQN reads*/);
 hipError_t mkp_stream_set_lds(uint32_t bytes);
@@ -41,8 +38,8 @@ hipError_t mkp_launch_dup_events(hipStream_t, MkpReadHdr*, const uint32_t*, cons
     uint32_t, uint32_t* /*error bits*/);
 hipError_t mkp_launch_stream(hipStream_t, uint32_t /*LDS bytes*/, const MkpVisit*, const uint8_t*, const MkpEvent*, const MkpSTile*, uint32_t,
     const MkpRunParams* /*device*/, const uint32_t* /*slot positions*/,
-                             const uint8_t* /*focus bytes*/, const MkpCombo*, const MkpRowsDev*, uint32_t* /*row cursor*/, uint32_t*, uint32_t*,
-                                 uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, uint32_t /*motif combos*/,
+                             const uint8_t* /*focus bytes*/, const MkpCombo*, const MkpRowsDev*, uint32_t* /*row cursor*/,
+                                 uint32_t* /*look-back words*/, uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, uint32_t /*motif combos*/,
                                  uint32_t /*row runs of the launch sequence*/,
                              uint32_t /*slot capacity of a tile*/, uint32_t /*tally words per slot*/, bool /*wide tallies*/);
 hipError_t mkp_launch_gather(hipStream_t, const uint32_t*, const uint32_t*, uint32_t*, uint32_t, uint32_t*, const MkpRowsDev*, const MkpRowsDev*);
@@ -272,19 +269,18 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
     if (c->slot_mode) hip_check(mkp_launch_slots(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], c->d_plane.p,
         c->d_cigar16.as<uint16_t>(), c->d_hdr.as<MkpReadHdr>(),
         c->d_slot_ids.as<uint32_t>(), c->n_slot_class[2],
-                                              c->d_cigar.as<uint32_t>(), c->d_seq.as<uint8_t>(), c->d_tagref.as<MkpTagRef>(),
-                                              c->d_ranks.as<uint32_t>(), c->d_ml.as<uint8_t>(), c->d_layouts.as<MkpLayout>(),
+                                              c->d_cigar.as<uint32_t>(), c->d_seq.as<uint8_t>(), c->d_ml.as<uint8_t>(),
                                                   c->d_fdesc.as<MkpFusedDesc>(), &P, c->d_slot_pos.as<uint32_t>(), c->d_slot_ent.as<MkpSlotEnt>(),
                                                   c->d_cov.as<uint8_t>(),
                                                   c->d_visits.as<MkpVisit>(),
-                                              c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>(), misc + 2), "slot decode launch");
+                                              c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>()), "slot decode launch");
     if (time_kernels) hip_check(hipEventRecord(c->ev[1], c->stream), "event");
     for (uint32_t kp = 0; kp < c->key_passes.size(); kp++)   // one pass per partition key present (a single unfiltered pass without --partition-tag)
       if (c->slot_mode) hip_check(mkp_launch_stream(c->stream, c->lds_bytes, c->d_visits.as<MkpVisit>(), c->d_cov.as<uint8_t>(),
           c->d_events.as<MkpEvent>(),
           c->d_stiles.as<MkpSTile>(), c->n_tiles, c->d_prm.as<MkpRunParams>(),
                                                  c->d_slot_pos.as<uint32_t>(), c->d_focus.as<uint8_t>(), c->d_combos.as<MkpCombo>(), &c->rows_src,
-                                                     misc, row_off, c->d_tile_row_cnt.as<uint32_t>(), misc + 2,
+                                                     misc, row_off, misc + 2,
                                                  c->key_passes[kp], kp, (uint32_t)c->combos.size(), n_runs, P.slot_cap,
                                                      (P.n_counters + P.n_slots) * (c->wide ? 2u : 1u), c->wide),
                                                      "stream pileup launch");

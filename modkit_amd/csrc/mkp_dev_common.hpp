@@ -15,6 +15,9 @@
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 __device__ __forceinline__ unsigned long long lanemask_le() { int l = lane_id(); return l == 63 ? ~0ull : ((1ull << (l + 1)) - 1ull); }
 __device__ __forceinline__ unsigned long long lanemask_lt() { return (1ull << lane_id()) - 1ull; }
+__device__ __forceinline__ void wave_lds_sync() {   // LDS written by some lanes of the wave is read by others
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // Inclusive prefix sum over the wave: four row_shr steps inside each row of 16 lanes, then row_bcast:15 / row_bcast:31
 // carry the row totals across (lanes without a source add 0).  Six v_add_u32_dpp, no LDS traffic.

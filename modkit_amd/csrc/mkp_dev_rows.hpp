@@ -1,13 +1,72 @@
 // Row emission from a tile's LDS tallies, for the accumulate kernels of mkp_kernels.hip and mkp_slots.hip:
 //   the row program (StreamProg, stream_row_*, rowprog_build): FeatureVector::decode / add_tally_to_counts / combine_strand_features
 //     (pileup/mod.rs:283-561) as a table per workgroup — both files;
-//   emit_dense_rows: the tail of the dense mkp_pileup_tiles kernels;  lookback_reserve_wave: row runs in genome order (mkp_slots.hip);
+//   what the three emitters share: rows_view (the row buffer's columns), block_excl_scan (a thread's place among the tile's rows),
+//     store_row, rows_this_round;
+//   emit_dense_rows: the tail of the dense mkp_pileup_tiles kernels;
+//   StreamLds, lookback_reserve_wave, emit_stream_rows: the tail of the mkp_pileup_stream kernels, row runs in genome order (mkp_slots.hip);
 //   hemi_rows_at, SlotMap, emit_hemi_rows: the tail of mkp_pileup_tiles_hemi (DuplexFeatureVector::decode, duplex.rs:124-205);
-//   lds_add, event_lower_bound: small device helpers both files use.
+//   obs_diff, prefix_sum_in_place (observed codes as difference arrays), lds_add, event_lower_bound: small device helpers both files use.
 #pragma once
 #include "mkp_dev_common.hpp"
 
+#define PILEUP_THREADS MKP_PILEUP_THREADS
+#define PILEUP_WAVES (PILEUP_THREADS / 64)
+#define PILEUP_WAVE_SCRATCH MKP_PILEUP_WAVE_SCRATCH
+
 struct RowAcc { uint32_t n_valid, n_mod, n_can, n_other, n_del, n_fail, n_diff, n_nocall; };
+
+// the row buffer as columns: 11 SoA arrays of row_capacity entries behind rows_base
+__device__ __forceinline__ MkpRowsDev rows_view(uint32_t* __restrict__ q, size_t cap) {
+  MkpRowsDev rows;
+  rows.pos = q; rows.info = q + cap; rows.code = q + 2 * cap; rows.n_valid = q + 3 * cap; rows.n_mod = q + 4 * cap; rows.n_can = q + 5 * cap;
+  rows.n_other = q + 6 * cap; rows.n_del = q + 7 * cap; rows.n_fail = q + 8 * cap; rows.n_diff = q + 9 * cap; rows.n_nocall = q + 10 * cap;
+  return rows;
+}
+__device__ __forceinline__ void store_row(const MkpRowsDev& rows, size_t at, uint32_t pos, uint32_t info, uint32_t code, const RowAcc& acc) {
+  rows.pos[at] = pos; rows.info[at] = info; rows.code[at] = code;
+  rows.n_valid[at] = acc.n_valid; rows.n_mod[at] = acc.n_mod; rows.n_can[at] = acc.n_can; rows.n_other[at] = acc.n_other;
+  rows.n_del[at] = acc.n_del; rows.n_fail[at] = acc.n_fail; rows.n_diff[at] = acc.n_diff; rows.n_nocall[at] = acc.n_nocall;
+}
+// Block exclusive scan of a per-thread row count (thread order = row order): returns the rows of the threads before this one, *total = the
+// tile's rows.  wave_tot: a word of LDS per wave.  One barrier inside, between the waves' totals and their sum; a caller that runs it
+// again, or reuses wave_tot, puts its own barrier in between.
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t cnt, uint32_t* wave_tot, uint32_t* total) {
+  const uint32_t wave = threadIdx.x >> 6, incl = wave_incl_scan(cnt);
+  if (lane_id() == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  uint32_t off = incl - cnt, tot = 0;
+  for (uint32_t w2 = 0; w2 < PILEUP_WAVES; w2++) { const uint32_t t = wave_tot[w2]; if (w2 < wave) off += t; tot += t; }
+  *total = tot;
+  return off;
+}
+// rows are placed through a row map of `words` entries per round: the rows of the round that starts at row r0 of the tile
+__device__ __forceinline__ uint32_t rows_this_round(uint32_t total, uint32_t r0, uint32_t words) {
+  const uint32_t end = min(total, r0 + words);
+  return end > r0 ? end - r0 : 0u;
+}
+
+// Observed code `sl` of tally strand `s` over the columns [a, b): +1 at a, -1 at b — an interval-OR as a difference array
+// (`leave`: the reverse, a ref-skip inside the read's span).  Narrow: the strand's half of the packed word; WIDE: its plane.
+template <bool WIDE>
+__device__ __forceinline__ void obs_diff(uint32_t* __restrict__ obs, uint32_t S, uint32_t sl, uint32_t s, uint32_t a, uint32_t b, uint32_t n_tslots,
+    bool leave) {
+  uint32_t* __restrict__ row = obs + (WIDE ? 2u * sl + s : sl) * S;
+  const uint32_t one = WIDE ? 1u : (s ? 0x10000u : 1u), v = leave ? 0u - one : one;
+  atomicAdd(&row[a], v);
+  if (b < n_tslots) atomicAdd(&row[b], 0u - v);
+}
+// difference array -> counts, in place, by one wave (packed halves stay exact: neither half ever goes negative in the sum)
+__device__ __forceinline__ void prefix_sum_in_place(uint32_t* __restrict__ arr, uint32_t n) {
+  const uint32_t lane = (uint32_t)lane_id();
+  uint32_t carry = 0;
+  for (uint32_t b0 = 0; b0 < n; b0 += 64) {
+    const uint32_t v = (b0 + lane < n) ? arr[b0 + lane] : 0u;
+    const uint32_t sc = wave_incl_scan(v);
+    if (b0 + lane < n) arr[b0 + lane] = sc + carry;
+    carry += (uint32_t)__builtin_amdgcn_readlane((int)sc, 63);
+  }
+}
 
 // pileup-hemi rows of one '+' motif position whose counters sit in column i (DuplexFeatureVector::decode, duplex.rs:124-205, in the
 // writer's order: primary base, then pattern — writers.rs:196-207).  The pattern goes out as its two element indices
@@ -28,11 +87,9 @@ __device__ __forceinline__ uint32_t hemi_rows_at(const uint32_t* __restrict__ ta
       const uint32_t cnt = tal[(base + k) * S + i];
       if (!cnt) continue;
       if (WRITE) {
-        const uint32_t r = wr + n;
-        rows.pos[r] = (uint32_t)p; rows.info[r] = (uint32_t)pb; rows.code[r] = (k / nel) | ((k % nel) << 8);
-        rows.n_valid[r] = tot[pb]; rows.n_mod[r] = cnt; rows.n_can[r] = tal[base * S + i]; rows.n_other[r] = tot[pb] - cnt;
-        rows.n_del[r] = tal[MKP_H_DEL * S + i]; rows.n_fail[r] = tal[(MKP_H_FAIL + pb) * S + i];
-        rows.n_diff[r] = tot[0] + tot[1] + tot[2] + tot[3] - tot[pb]; rows.n_nocall[r] = tal[(MKP_H_NC + pb) * S + i];
+        const RowAcc acc = {tot[pb], cnt, tal[base * S + i], tot[pb] - cnt, tal[MKP_H_DEL * S + i], tal[(MKP_H_FAIL + pb) * S + i],
+            tot[0] + tot[1] + tot[2] + tot[3] - tot[pb], tal[(MKP_H_NC + pb) * S + i]};
+        store_row(rows, wr + n, (uint32_t)p, (uint32_t)pb, (k / nel) | ((k % nel) << 8), acc);
       }
       n++;
     }
@@ -111,10 +168,6 @@ __device__ __forceinline__ void rowprog_build(const MkpRunParams& prm, uint32_t 
   if (g == 0u) { prog.n_groups = ng; prog.totmask = ((1u << n_counters) - 1u) & ~((1u << MKP_C_DEL) | (1u << MKP_C_FAIL)); }
 }
 
-#define PILEUP_THREADS MKP_PILEUP_THREADS
-#define PILEUP_WAVES (PILEUP_THREADS / 64)
-#define PILEUP_WAVE_SCRATCH MKP_PILEUP_WAVE_SCRATCH
-
 // Rows of a DENSE tile (mkp_pileup_tiles without focus positions: every position of the tile's range owns a column, both strands of every
 // position are candidates, strands never combine): each thread takes a contiguous run of columns — rows keep position order — counts its
 // rows, the block scans, thread 0 reserves the tile's run of the row buffer (mkp_scan_tiles + mkp_gather_rows order the runs afterwards),
@@ -129,8 +182,6 @@ __device__ __forceinline__ void emit_dense_rows(const uint32_t* __restrict__ tal
                                                 uint32_t* __restrict__ row_cursor, uint32_t* __restrict__ tile_row_off,
                                                     uint32_t* __restrict__ tile_row_cnt, uint32_t* __restrict__ dev_err,
                                                 uint32_t* wave_tot, uint32_t* row_base_p, uint32_t* row_total_p) {
-  const int lane = lane_id();
-  const uint32_t wave = threadIdx.x >> 6;
   rowprog_build(prm, n_counters, prog);
   __syncthreads();
   const StreamProg& P = prog;
@@ -144,22 +195,15 @@ __device__ __forceinline__ void emit_dense_rows(const uint32_t* __restrict__ tal
     if (!in_rows(i)) continue;
     for (uint32_t s = 0; s < 2; s++) for (uint32_t g = 0; g < n_groups; g++) cnt += stream_row_exists<WIDE>(tal, S, n_counters, P, s, i, g) ? 1u : 0u;
   }
-  const uint32_t inc2 = wave_incl_scan(cnt);
-  if (lane == 63) wave_tot[wave] = inc2;
-  __syncthreads();
-  uint32_t off = inc2 - cnt, tile_rows = 0;
-  for (uint32_t w2 = 0; w2 < PILEUP_WAVES; w2++) { const uint32_t t = wave_tot[w2]; if (w2 < wave) off += t; tile_rows += t; }
+  uint32_t tile_rows;
+  const uint32_t off = block_excl_scan(cnt, wave_tot, &tile_rows);
   if (threadIdx.x == 0) {
     uint32_t s = tile_rows;
     const uint32_t base = s ? atomicAdd(row_cursor, s) : 0u;
     if (base + s > prm.row_capacity) { atomicOr(dev_err, ERR_ROW_CAP); s = 0; }
     *row_base_p = base; *row_total_p = s; tile_row_off[run] = base; tile_row_cnt[run] = s;
   }
-  MkpRowsDev rows;
-  { const size_t cap = prm.row_capacity; uint32_t* q = rows_base;
-    rows.pos = q; rows.info = q + cap; rows.code = q + 2 * cap; rows.n_valid = q + 3 * cap; rows.n_mod = q + 4 * cap; rows.n_can = q + 5 * cap;
-      rows.n_other = q + 6 * cap;
-    rows.n_del = q + 7 * cap; rows.n_fail = q + 8 * cap; rows.n_diff = q + 9 * cap; rows.n_nocall = q + 10 * cap; }
+  const MkpRowsDev rows = rows_view(rows_base, prm.row_capacity);
   for (uint32_t r0 = 0; r0 < tile_rows; r0 += map_words) {
     if (r0) __syncthreads();   // the round before has read the map
     if (cnt && off < r0 + map_words && off + cnt > r0) {
@@ -174,15 +218,13 @@ __device__ __forceinline__ void emit_dense_rows(const uint32_t* __restrict__ tal
       }
     }
     __syncthreads();
-    const uint32_t total = *row_total_p, n_here = min(total, r0 + map_words) > r0 ? min(total, r0 + map_words) - r0 : 0u;
+    const uint32_t n_here = rows_this_round(*row_total_p, r0, map_words);
     for (uint32_t rr = threadIdx.x; rr < n_here; rr += PILEUP_THREADS) {
       const uint32_t e = rowmap[rr], si = e & 8191u, g = (e >> 13) & 15u, s = (e >> 17) & 1u;
       RowAcc acc = {0, 0, 0, 0, 0, 0, 0, 0};
       stream_row_add<WIDE>(tal, S, P, s, si, g, acc);
-      const size_t at = (size_t)*row_base_p + r0 + rr;
-      rows.pos[at] = (uint32_t)(T0h + (int32_t)si); rows.info[at] = s | (key << 16); rows.code[at] = P.code[g];   // (no motif: info[8:15] = 0)
-      rows.n_valid[at] = acc.n_valid; rows.n_mod[at] = acc.n_mod; rows.n_can[at] = acc.n_can; rows.n_other[at] = acc.n_other;
-      rows.n_del[at] = acc.n_del; rows.n_fail[at] = acc.n_fail; rows.n_diff[at] = acc.n_diff; rows.n_nocall[at] = acc.n_nocall;
+      // (no motif: info[8:15] = 0)
+      store_row(rows, (size_t)*row_base_p + r0 + rr, (uint32_t)(T0h + (int32_t)si), s | (key << 16), P.code[g], acc);
     }
   }
 }
@@ -256,6 +298,155 @@ __device__ __forceinline__ uint32_t lookback_reserve_wave(unsigned long long* __
   return excl;
 }
 
+// The dynamic LDS of a mkp_pileup_stream tile of S columns, region by region (carved by pileup_stream_body, mkp_slots.hip)
+struct StreamLds {
+  uint32_t* tal;      // [counter | observed-code slot][S] packed tallies ('+' in the low, '-' in the high 16 bits); WIDE: [..][strand][S]
+  uint32_t* obs;      // the observed-code rows of `tal`: difference arrays while the reads are visited, counts behind the scans
+  int32_t* fpos;      // [S] the tile's slot positions
+  uint32_t* aux;      // [S] per slot: [0:7] focus byte, [8 + 6m ..] partner column of the m-th '+' motif (strand combining)
+  uint32_t* rowmap;   // [MKP_STREAM_ROWMAP_WORDS] the candidate reads of a round while reads are visited, then the row map
+  uint32_t S;
+};
+
+// Rows of a STREAM tile (the tail of the mkp_pileup_stream kernels; thread i holds slot i's position and focus word, the observed codes
+// are counts by now):
+//   E1  one thread per SLOT decides which rows exist: a bit per (strand | motif, code group) candidate — existence needs the coverage of
+//       the candidate's primary base and its observed-code count, a handful of LDS reads — and counts them;
+//   E2  block scan of the counts; wave 0 reserves the tile's run in the row buffer (decoupled look-back over the runs before, in ticket
+//       order) while every thread scatters (slot, candidate) words of its rows into the ROW MAP in LDS;
+//   E3  one thread per ROW fills its row from the tallies and stores it: every store instruction writes 64 consecutive rows of one column.
+// (One thread per slot running a parameter-driven interpreter twice — count, then write — cost ~800 VALU instructions per thread, 29
+// spilled registers, and wrote the rows of a slot with stride-2 stores.)
+template <bool WIDE>
+__device__ __forceinline__ void emit_stream_rows(const StreamLds& L, uint32_t n_counters, const MkpSTile& tl, int32_t my_pos, uint32_t my_fv,
+    uint32_t run, uint32_t n_runs, uint32_t key, const MkpRunParams& prm, const StreamProg& P, const MkpCombo* combos_l,
+    uint32_t* __restrict__ rows_base, uint32_t* __restrict__ row_cursor, uint32_t* __restrict__ tile_row_off, uint32_t* __restrict__ dev_err,
+    uint32_t* wave_tot, uint32_t* row_base_p, uint32_t* row_total_p) {
+  const uint32_t* __restrict__ tal = L.tal; const int32_t* __restrict__ fpos = L.fpos;
+  uint32_t* __restrict__ aux = L.aux; uint32_t* __restrict__ rowmap = L.rowmap;
+  const int lane = lane_id();
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const uint32_t S = L.S, n_tslots = tl.gh1 - tl.gh0;
+  // ---- E1: which rows does this thread's slot yield (FeatureVector::decode, pileup/mod.rs:412-446; combine_strand_features 469-561)
+  const uint32_t n_groups = P.n_groups;
+  const bool combine = prm.combine_strands != 0;
+  const uint32_t i = threadIdx.x;
+  unsigned long long em = 0; uint32_t cnt = 0, mult0 = 1, mult1 = 1;
+#ifdef MKP_DEBUG
+  const bool dbg_norows = (prm.debug_skip & 2048u) != 0;   // ablation: no rows (the look-back word is still published so that nothing waits)
+#else
+  constexpr bool dbg_norows = false;
+#endif
+  if (!dbg_norows && i < n_tslots && my_pos >= tl.r0 && my_pos < tl.r1 && (my_fv & 3u)) {
+    const uint32_t rule = my_fv & 3u, combo = my_fv >> 2;
+    if (!combine) {
+      if (combo) { const MkpCombo& cb = combos_l[combo]; mult0 = cb.n_pos ? cb.n_pos : 1u; mult1 = cb.n_neg ? cb.n_neg : 1u; }
+      for (uint32_t s = 0; s < 2; s++) {
+        if (!((rule >> s) & 1u)) continue;
+        for (uint32_t g = 0; g < n_groups; g++) if (stream_row_exists<WIDE>(tal, S, n_counters, P, s, i, g)) em |= 1ull << (16u * s + g);
+      }
+      cnt = (uint32_t)__popc((uint32_t)em & 0xffffu) * mult0 + (uint32_t)__popc((uint32_t)(em >> 16) & 0xffffu) * mult1;
+    } else if (combo) {   // only '+' motif positions produce rows
+      const MkpCombo& cb = combos_l[combo];
+      const bool pos_ok = (rule & 1u) != 0;
+      uint32_t part = 0;
+      for (uint32_t m = 0; m < cb.n_pos; m++) {
+        const int delta = cb.pos_delta[m];
+        if (delta == -128) continue;   // not a palindrome / negative_strand_position() == None
+        const int idx = cb.pos_ids[m];
+        const int32_t qpos = my_pos + delta;
+        bool neg_ok = false; uint32_t iq = i;
+        if (delta != -127 && qpos >= prm.win_start && qpos < prm.win_end) {   // -127: the mate position is in another interval
+          // the partner's column: a focus position at most MKP_HALO away — a few columns up or down
+          if (delta > 0) { while (iq + 1u < n_tslots && fpos[iq + 1u] <= qpos) iq++; } else { while (iq > 0u && fpos[iq - 1u] >= qpos) iq--; }
+          if (fpos[iq] == qpos) {
+            const uint32_t fq = aux[iq] & 0xffu;
+            if ((fq & 2u) && (fq >> 2)) { const MkpCombo& cq = combos_l[fq >> 2];
+              for (uint32_t k = 0; k < cq.n_neg; k++) neg_ok |= (cq.neg_ids[k] == idx);
+              }
+          }
+        }
+        if (neg_ok) part |= ((iq - i + 32u) & 63u) << (8u + 6u * m);
+        for (uint32_t g = 0; g < n_groups; g++) {
+          if (!((P.info[g] >> 18) & 1u)) continue;   // grouped by code (BTreeMap)
+          bool any = false;
+          for (uint32_t gj = g; gj < n_groups && (gj == g || !((P.info[gj] >> 18) & 1u)); gj++)
+            any = any || (pos_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 0, i, gj))
+                || (neg_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 1, iq, gj));
+          if (any) { em |= 1ull << (16u * m + g); cnt++; }
+        }
+      }
+      if (part) aux[i] = my_fv | part;   // (own word; the other threads only look at the focus byte, which stays)
+    }
+  }
+  // ---- E2: place of every slot's rows inside the tile, the tile's place in the row buffer
+  uint32_t tile_rows;
+  const uint32_t off = block_excl_scan(cnt, wave_tot, &tile_rows);
+  const MkpRowsDev rows = rows_view(rows_base, prm.row_capacity);
+  for (uint32_t r0 = 0; r0 == 0u || r0 < tile_rows; r0 += MKP_STREAM_ROWMAP_WORDS) {
+    if (r0) __syncthreads();   // the round before has read the map
+    // (slot, candidate) of every row of this round: [0:9] slot, [10:13] group, [14:15] strand | motif, [16:17] which of the position's motif ids
+    if (cnt && off < r0 + MKP_STREAM_ROWMAP_WORDS && off + cnt > r0) {
+      uint32_t r = off;
+      for (uint32_t sm = 0; sm < 4u; sm++) {
+        uint32_t bits = (uint32_t)(em >> (16u * sm)) & 0xffffu;
+        const uint32_t mult = combine ? 1u : (sm ? mult1 : mult0);
+        while (bits) {
+          const uint32_t g = (uint32_t)__ffs((int)bits) - 1u; bits &= bits - 1u;
+          for (uint32_t k = 0; k < mult; k++, r++) if (r >= r0
+              && r < r0 + MKP_STREAM_ROWMAP_WORDS) rowmap[r - r0] = i | (g << 10) | (sm << 14) | (k << 16);
+        }
+      }
+    }
+    if (r0 == 0u && wave == 0u) {   // tile_row_off = the runs' look-back words (two dwords each); row_cursor[1] = total rows, written by the last run
+#ifdef MKP_DEBUG
+      uint32_t base;
+      // ablation: no look-back (rows in completion order)
+      if (prm.debug_skip & 4096u) { uint32_t b0 = 0; if (lane == 0) b0 = atomicAdd(row_cursor + 1, tile_rows);
+        base = (uint32_t)__builtin_amdgcn_readfirstlane((int)b0); }
+      else base = lookback_reserve_wave(reinterpret_cast<unsigned long long*>(tile_row_off), run, tile_rows);
+#else
+      const uint32_t base = lookback_reserve_wave(reinterpret_cast<unsigned long long*>(tile_row_off), run, tile_rows);
+#endif
+      if (lane == 0) {
+#ifdef MKP_DEBUG
+        if (!(prm.debug_skip & 4096u))
+#endif
+        if (run + 1u == n_runs) row_cursor[1] = base + tile_rows;
+        uint32_t s = tile_rows;
+        if (base + s > prm.row_capacity) { atomicOr(dev_err, ERR_ROW_CAP); s = 0; }
+        *row_base_p = base; *row_total_p = s;
+      }
+    }
+    __syncthreads();
+    // ---- E3: one thread per row
+    const uint32_t n_here = rows_this_round(*row_total_p, r0, MKP_STREAM_ROWMAP_WORDS);
+    for (uint32_t rr = threadIdx.x; rr < n_here; rr += PILEUP_THREADS) {
+      const uint32_t e = rowmap[rr], si = e & 1023u, g = (e >> 10) & 15u, sm = (e >> 14) & 3u, k = (e >> 16) & 3u;
+      const uint32_t ax = aux[si], combo = (ax & 0xffu) >> 2;
+      RowAcc acc = {0, 0, 0, 0, 0, 0, 0, 0};
+      uint32_t strand, motif1;   // motif1 = motif id + 1 (0: none)
+      if (!combine) {
+        stream_row_add<WIDE>(tal, S, P, sm, si, g, acc);
+        strand = sm; motif1 = 0;
+        if (combo) { const MkpCombo& cb = combos_l[combo]; const uint32_t n_ids = sm ? cb.n_neg : cb.n_pos;
+          if (n_ids) motif1 = (uint32_t)(sm ? cb.neg_ids[k] : cb.pos_ids[k]) + 1u;
+          }
+      } else {
+        const MkpCombo& cb = combos_l[combo];
+        const uint32_t pd = (ax >> (8u + 6u * sm)) & 63u, iq = si + pd - 32u;
+        const bool pos_ok = (ax & 1u) != 0, neg_ok = pd != 0u;
+        for (uint32_t gj = g; gj < n_groups && (gj == g || !((P.info[gj] >> 18) & 1u)); gj++) {
+          if (pos_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 0, si, gj)) stream_row_add<WIDE>(tal, S, P, 0, si, gj, acc);
+          if (neg_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 1, iq, gj)) stream_row_add<WIDE>(tal, S, P, 1, iq, gj, acc);
+        }
+        strand = 2; motif1 = (uint32_t)cb.pos_ids[sm] + 1u;
+      }
+      store_row(rows, (size_t)*row_base_p + r0 + rr, (uint32_t)fpos[si], strand | (motif1 << 8) | (key << 16), P.code[g], acc);
+    }
+  }
+}
+
 // Rows of a pileup-hemi tile (the tail of mkp_pileup_tiles_hemi).  The host planner caps such a tile at one column per thread
 // (MKP_PILEUP_THREADS): every thread counts its column's rows once, the block scans (column order = position order), thread 0
 // reserves the tile's run of the row buffer with one atomic (mkp_scan_tiles + mkp_gather_rows order the runs afterwards), and the
@@ -263,33 +454,21 @@ __device__ __forceinline__ uint32_t lookback_reserve_wave(unsigned long long* __
 __device__ __forceinline__ void emit_hemi_rows(const uint32_t* __restrict__ tal, SlotMap sm, uint32_t n_tslots, MkpTile tl, uint32_t run,
     const MkpRunParams& prm, uint32_t* __restrict__ rows_base, uint32_t* __restrict__ row_cursor, uint32_t* __restrict__ tile_row_off,
     uint32_t* __restrict__ tile_row_cnt, uint32_t* __restrict__ dev_err, uint32_t* wave_tot, uint32_t* row_base_p, uint32_t* row_total_p) {
-  const int lane = lane_id();
-  const uint32_t wave = threadIdx.x >> 6;
-  MkpRowsDev rows;
-  { const size_t cap = prm.row_capacity; uint32_t* p = rows_base;
-    rows.pos = p; rows.info = p + cap; rows.code = p + 2 * cap; rows.n_valid = p + 3 * cap; rows.n_mod = p + 4 * cap; rows.n_can = p + 5 * cap;
-      rows.n_other = p + 6 * cap;
-    rows.n_del = p + 7 * cap; rows.n_fail = p + 8 * cap; rows.n_diff = p + 9 * cap; rows.n_nocall = p + 10 * cap; }
+  const MkpRowsDev rows = rows_view(rows_base, prm.row_capacity);
   const uint32_t i = threadIdx.x;
   uint32_t cnt = 0; int32_t p = 0;
   if (i < n_tslots) {
     p = sm.pos_of(i);
     if (p >= tl.r0 && p < tl.r1) cnt = hemi_rows_at<false>(tal, prm.slot_cap, prm, p, i, rows, 0);
   }
-  const uint32_t inc2 = wave_incl_scan(cnt);
-  if (lane == 63) wave_tot[wave] = inc2;
-  __syncthreads();
+  uint32_t tile_rows;
+  const uint32_t off = block_excl_scan(cnt, wave_tot, &tile_rows);
   if (threadIdx.x == 0) {
-    uint32_t s = 0;
-    for (uint32_t w2 = 0; w2 < PILEUP_WAVES; w2++) s += wave_tot[w2];
+    uint32_t s = tile_rows;
     const uint32_t base = s ? atomicAdd(row_cursor, s) : 0u;
     if (base + s > prm.row_capacity) { atomicOr(dev_err, ERR_ROW_CAP); s = 0; }
     *row_base_p = base; *row_total_p = s; tile_row_off[run] = base; tile_row_cnt[run] = s;
   }
   __syncthreads();
-  if (*row_total_p && cnt) {
-    uint32_t woff = *row_base_p + inc2 - cnt;
-    for (uint32_t w2 = 0; w2 < wave; w2++) woff += wave_tot[w2];
-    hemi_rows_at<true>(tal, prm.slot_cap, prm, p, i, rows, woff);
-  }
+  if (*row_total_p && cnt) hemi_rows_at<true>(tal, prm.slot_cap, prm, p, i, rows, *row_base_p + off);
 }

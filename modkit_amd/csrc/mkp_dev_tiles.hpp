@@ -1,6 +1,7 @@
 // What the two tile bodies of mkp_kernels.hip (dense_tiles_body, hemi_tiles_body) share: the workgroup prologue, the tile remap,
-// the read ticket, the skip over CIGAR chunks in front of the tile, the walk over a read's events inside the tile, and the
-// difference arrays.  One job each; the walks themselves differ and stay in the bodies.
+// the read ticket, the skip over CIGAR chunks in front of the tile and the walk over a read's events inside the tile (the
+// difference arrays of the observed codes are in mkp_dev_rows.hpp: the stream kernels use them too).  One job each; the walks
+// themselves differ and stay in the bodies.
 #pragma once
 #include "mkp_dev_rows.hpp"
 
@@ -70,28 +71,5 @@ __device__ __forceinline__ void for_tile_events(const MkpEvent* __restrict__ ev,
     if (in) { e = ev[k]; in = (int32_t)e.pos < T1h; }
     if (in) f(k, e);
     if (!__any(in)) break;
-  }
-}
-
-// Observed code `sl` of tally strand `s` over the columns [a, b): +1 at a, -1 at b — an interval-OR as a difference array
-// (`leave`: the reverse, a ref-skip inside the read's span).  Narrow: the strand's half of the packed word; WIDE: its plane.
-template <bool WIDE>
-__device__ __forceinline__ void obs_diff(uint32_t* __restrict__ obs, uint32_t S, uint32_t sl, uint32_t s, uint32_t a, uint32_t b, uint32_t n_tslots,
-    bool leave) {
-  uint32_t* __restrict__ row = obs + (WIDE ? 2u * sl + s : sl) * S;
-  const uint32_t one = WIDE ? 1u : (s ? 0x10000u : 1u), v = leave ? 0u - one : one;
-  atomicAdd(&row[a], v);
-  if (b < n_tslots) atomicAdd(&row[b], 0u - v);
-}
-
-// difference array -> counts, in place, by one wave (packed halves stay exact: neither half ever goes negative in the sum)
-__device__ __forceinline__ void prefix_sum_in_place(uint32_t* __restrict__ arr, uint32_t n) {
-  const uint32_t lane = (uint32_t)lane_id();
-  uint32_t carry = 0;
-  for (uint32_t b0 = 0; b0 < n; b0 += 64) {
-    const uint32_t v = (b0 + lane < n) ? arr[b0 + lane] : 0u;
-    const uint32_t sc = wave_incl_scan(v);
-    if (b0 + lane < n) arr[b0 + lane] = sc + carry;
-    carry += (uint32_t)__builtin_amdgcn_readlane((int)sc, 63);
   }
 }

@@ -33,9 +33,6 @@
 // prologue and epilogue, the per-call rules of the reference and the event append are written once, here.
 __device__ __forceinline__ uint32_t rfl_u(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ float rfl_f(float v) { return __uint_as_float(rfl_u(__float_as_uint(v))); }
-__device__ __forceinline__ void wave_lds_sync() {   // LDS written by some lanes of the wave is read by others
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Read prologue: the wave's read and its header; the read's layout (1216 B) goes to the wave's LDS slice once, every table
 // lookup afterwards is an LDS read.  False = nothing to decode: no read for this wave, or a bad / tag-less read, whose empty
@@ -875,7 +872,7 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
   //  w_a / w_b = (reference start - query start) << 1 | is-match of the two ops)
   // The window's running values (first op, query / reference offsets, totals) are kept in scalar registers — read back through readfirstlane
   // after every update; carried as vectors they were advanced with v_cndmask and copied at every loop head — and "nothing loaded yet" is an
-  // empty window in front of op 0: no flag, no conditional advance (the same rewrite as refwin_s_* of mkp_slots.hip).
+  // empty window in front of op 0: no flag, no conditional advance (as the slot walks' CigarWin, mkp_slots.hip).
   uint32_t c0 = 0u - 128u, wq0 = 0, wq1 = 0; int32_t wr0 = h.ref_start;
   uint32_t w_qe = 0, w_mid = 0, w_a = 0, w_b = 0, w_rtot = 0;
   auto cigar2 = [&](uint32_t c) { uint2 r; const uint32_t k = c + 2u * (uint32_t)lane; r.x = k < h.n_cigar ? cigar[h.cigar_off + k] : 5u /*0H*/;

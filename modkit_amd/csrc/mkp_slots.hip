@@ -24,8 +24,11 @@
 //   mkp_pileup_stream     accumulate + emit: one workgroup per tile of <= 1024 slots; the tile's reads' feature bytes are a
 //                         position-implicit stream (byte k of a read = global slot gs0 + k): four bytes per lane, one LDS atomic per
 //                         feature on 16-bit-packed strand tallies; observed codes as difference arrays; rows straight from LDS
-//                         (mkp_dev_rows.hpp).  This is the packed-event-stream histogram of BASELINE.json's north_star.
-//   (mkp_scan_tiles + mkp_gather_rows of mkp_kernels.hip order the row runs.)
+//                         (emit_stream_rows, mkp_dev_rows.hpp), the runs in genome order through a look-back.  This is the
+//                         packed-event-stream histogram of BASELINE.json's north_star.
+//   mkp_dup_restore / mkp_dup_events / mkp_dup_apply   records that share a read name inside one interval
+// and, in front of them, the one CIGAR window walker (CigarWin, cigwin_*: reference -> query) of the decoder, mkp_cover_reads and
+// mkp_dup_events; behind them the host-side launchers.
 //
 // Semantics follow /root/reference/src (cited inline).  f32 arithmetic is the reference's (contraction off, IEEE division).
 #include <cstdlib>
@@ -40,110 +43,30 @@
 struct SlotLds { int32_t ck_thr[4]; uint32_t ck_off[4]; uint32_t ck_str[4]; uint32_t ck_cid[4]; };
 
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ void wave_lds_fence() { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); }
 __device__ __forceinline__ uint32_t feat(uint32_t cid, uint32_t tally) { return cid | (tally << 5); }
 
-#define SLOT_PARAMS(PRM) const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads, const uint32_t* __restrict__ read_ids, const uint32_t* __restrict__ cigar, \
-    const uint8_t* __restrict__ seqs, const MkpTagRef* __restrict__ tagref, const uint32_t* __restrict__ ranks, const uint8_t* __restrict__ ml, \
-    const MkpLayout* __restrict__ layouts, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const uint32_t* __restrict__ slot_pos, uint8_t* __restrict__ cov, MkpVisit* __restrict__ visits, \
-    MkpEvent* __restrict__ events, MkpReadOut* __restrict__ readout, uint32_t* __restrict__ dev_err
-#define SLOT_PASS hdrs, n_reads, read_ids, cigar, seqs, tagref, ranks, ml, layouts, fdesc, prm, slot_pos, cov, visits, events, readout, dev_err
-
-// The CIGAR as the slot walk sees it: 256 ops per window (four per lane), reference -> query.  re = inclusive reference end of the
-// lane's four ops (window-relative), m1..m3 = where its second..fourth op start, pk[j] = ((query start - (reference start -
-// ref_start)) << 2) | kind (0 match: M = X, 1 deletion, 2 ref-skip / nothing) of op j.
-struct RefWin {
-  uint32_t c0, q_run, Rtot, Qtot, re, m1, m2, m3, pk[4]; int32_t r_run; uint4 pref; bool loaded;
-};
 // loads as `uniform base + 32-bit byte offset`: the address is one VALU instruction (global saddr form), not 64-bit arithmetic
 template <class T> __device__ __forceinline__ T ldo(const void* __restrict__ base, uint32_t byte_off) {
   return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off); }
-// four CIGAR words per lane; the address is clamped to the read's last op (the buffer has slack behind it), ops past the end read as 0H
-__device__ __forceinline__ uint4 cigar_quad(const uint32_t* __restrict__ cg, uint32_t n_cigar, uint32_t c) {
-  const uint32_t k = c + 4u * (uint32_t)lane_id();
-  uint4 r = ldo<uint4>(cg, 4u * min(k, n_cigar - 1u));
-  if (__any(k + 4u > n_cigar)) { if (k >= n_cigar) r.x = 5u; if (k + 1u >= n_cigar) r.y = 5u; if (k + 2u >= n_cigar) r.z = 5u;
-    if (k + 3u >= n_cigar) r.w = 5u;
-    }
-  return r;
-}
 // per op code (MIDNSHP=X): bit 0 consumes query, bit 1 consumes reference, bits 2-3 kind
 #define MKP_CIGAR_LUT 0x888888833889a693ull
-__device__ __forceinline__ void refwin_load(RefWin& w, const uint32_t* __restrict__ cg, uint32_t n_cigar, int32_t ref_start) {
-  const uint4 v = w.pref;
-  w.pref = cigar_quad(cg, n_cigar, w.c0 + 256u);   // requested one window ahead
-  const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-  uint32_t ql[4], rl[4], kind[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    const uint32_t f = (uint32_t)(MKP_CIGAR_LUT >> ((wd[j] & 15u) << 2)), len = wd[j] >> 4;
-    ql[j] = len & (0u - (f & 1u)); rl[j] = len & (0u - ((f >> 1) & 1u)); kind[j] = (f >> 2) & 3u;
-  }
-  const uint32_t qsum = ql[0] + ql[1] + ql[2] + ql[3], rsum = rl[0] + rl[1] + rl[2] + rl[3];
-  uint32_t qe;
-  if (!__any((v.x | v.y | v.z | v.w) >= (128u << 4))) {   // ops shorter than 128: both running sums fit 16 bits, one scan serves both
-    const uint32_t sc = wave_incl_scan(qsum | (rsum << 16));
-    qe = sc & 0xffffu; w.re = sc >> 16;
-  } else { qe = wave_incl_scan(qsum); w.re = wave_incl_scan(rsum); }
-  w.Qtot = (uint32_t)__builtin_amdgcn_readlane((int)qe, 63); w.Rtot = (uint32_t)__builtin_amdgcn_readlane((int)w.re, 63);
-  uint32_t qs = w.q_run + qe - qsum, rs = w.re - rsum;   // query offset / window-relative reference offset of the lane's first op
-  const int32_t rbase = w.r_run - ref_start;
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    w.pk[j] = ((uint32_t)((int32_t)qs - (rbase + (int32_t)rs)) << 2) | kind[j];
-    qs += ql[j]; rs += rl[j];
-    if (j == 0) w.m1 = rs; else if (j == 1) w.m2 = rs; else if (j == 2) w.m3 = rs;
-  }
-  w.loaded = true;
-}
-// (kind, query index) of the reference positions p (ascending over the lanes and from call to call; `valid` lanes lie inside the
-// read's reference span).  htslib pileup columns: M = X -> the base, D -> is_del, N -> is_refskip (pileup/mod.rs:783-851).
-__device__ __forceinline__ void refwin_map(RefWin& w, const uint32_t* __restrict__ cg, uint32_t n_cigar, int32_t ref_start, bool valid, int32_t p,
-    uint32_t* kind, uint32_t* q) {
-  bool pending = valid; *kind = 2u; *q = 0u;
-  for (;;) {
-    if (!__any(pending)) break;
-    const bool inw = pending && w.loaded && (uint32_t)(p - w.r_run) < w.Rtot;
-    if (!__any(inw)) {
-      if (w.loaded) { w.c0 += 256u; w.q_run += w.Qtot; w.r_run += (int32_t)w.Rtot; }
-      if (w.c0 >= n_cigar) break;   // (cannot happen for positions inside the span)
-      refwin_load(w, cg, n_cigar, ref_start);
-      continue;
-    }
-    const uint32_t rel = inw ? (uint32_t)(p - w.r_run) : 0u;
-    // the lane whose four ops hold `rel`: the number of lanes whose inclusive end is <= rel (six probes; the probe address is carried)
-    uint32_t probe = 31u << 2;
-#pragma unroll
-    for (int hstep = 16; hstep >= 1; hstep >>= 1) {
-      const uint32_t vv = (uint32_t)__builtin_amdgcn_ds_bpermute((int)probe, (int)w.re);
-      probe = vv <= rel ? probe + 4u * (uint32_t)hstep : probe - 4u * (uint32_t)hstep;
-    }
-    { const uint32_t vv = (uint32_t)__builtin_amdgcn_ds_bpermute((int)probe, (int)w.re); probe = vv <= rel ? probe + 4u : probe; }
-    const int oa = (int)(probe & 255u);
-    const uint32_t o_m1 = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)w.m1), o_m2 = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)w.m2),
-        o_m3 = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)w.m3);
-    const uint32_t o0 = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)w.pk[0]), o1 = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)w.pk[1]);
-    const uint32_t o2 = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)w.pk[2]), o3 = (uint32_t)__builtin_amdgcn_ds_bpermute(oa, (int)w.pk[3]);
-    const uint32_t pk = rel < o_m1 ? o0 : rel < o_m2 ? o1 : rel < o_m3 ? o2 : o3;
-    if (inw) { *kind = pk & 3u; *q = (uint32_t)((p - ref_start) + ((int32_t)pk >> 2)); pending = false; }
-  }
-}
 
-// The fused decoders' form of the same window (mkp_decode_slots*: VALU-issue bound, 42 % of their vector instructions were this mapping).
-// The window's running values live in scalar registers (read back through readfirstlane after every update: left to itself the compiler
-// carries them as vectors and advances them with v_cndmask), "nothing loaded yet" is a window of no reference bases in front of op 0 —
-// no flag, no conditional advance — and the slot step maps its lanes in a pass of straight-line code, with the loop only behind it for
-// the steps that straddle windows (the one loop of refwin_map kept every window register twice and copied 14 of them per iteration).
-struct RefWinS { uint32_t c0, q_run, Rtot, Qtot; int32_t r_run; uint32_t re, m1, m2, m3, pk[4]; uint4 pref; };
-// Their four ops per lane come from the read's 16-bit CIGAR (mkp_cigar_pack.hpp) as ONE 8-byte load — the read starts on a multiple of four
-// entries, and so does every lane; a read with an op that does not fit 16 bits (MKP_RF_CIGW: `wide`, uniform over the wave) takes the 16-byte
-// load of its 32-bit words instead.  cg = the read's first op in the array it is read from.  The address is clamped to the read's last quad
-// (inside its own room) / last op.  The branch is at the load only, and nothing touches the loaded registers before the window is opened
-// (the request stays one window ahead): cigar_quad_s_ops then widens the 16-bit ops back to BAM words — ops past the end read as 0H, as
-// cigar_quad's.
+// The CIGAR as the slot walks see it (the decoder, mkp_cover_reads, mkp_dup_events): 256 ops per window (four per lane), reference ->
+// query.  re = inclusive reference end of the lane's four ops (window-relative), m1..m3 = where its second..fourth op start, pk[j] =
+// ((query start - (reference start - ref_start)) << 2) | kind (0 match: M = X, 1 deletion, 2 ref-skip / nothing) of op j.
+// The decoder is VALU-issue bound and this mapping was 42 % of its vector instructions, hence: the window's running values live in scalar
+// registers (read back through readfirstlane after every update: left to itself the compiler carries them as vectors and advances them
+// with v_cndmask), "nothing loaded yet" is a window of no reference bases in front of op 0 — no flag, no conditional advance — and a step
+// maps its lanes in a pass of straight-line code, with the loop only behind it for the steps that straddle windows.
+struct CigarWin { uint32_t c0, q_run, Rtot, Qtot; int32_t r_run; uint32_t re, m1, m2, m3, pk[4]; uint4 pref; };
+// A lane's four ops come from the read's 16-bit CIGAR (mkp_cigar_pack.hpp) as ONE 8-byte load — the read starts on a multiple of four
+// entries, and so does every lane; a read with an op that does not fit 16 bits (MKP_RF_CIGW), and every read of the kernels that read the
+// BAM words (`wide`, uniform over the wave), takes the 16-byte load of its 32-bit words instead.  cg = the read's first op in the array it is
+// read from.  The address is clamped to the read's last quad (inside its own room) / last op (the buffer has slack behind it).  The branch
+// is at the load only, and nothing touches the loaded registers before the window is opened (the request stays one window ahead):
+// cigar_quad_ops then widens the 16-bit ops back to BAM words — ops past the end read as 0H.
 typedef const __attribute__((address_space(1))) char* MkpCigarPtr;   // (a pointer into global memory, whichever of the two arrays it came from)
-__device__ __forceinline__ uint4 cigar_quad_s_load(MkpCigarPtr cg, bool wide, uint32_t n_cigar, uint32_t c) {
+__device__ __forceinline__ uint4 cigar_quad_load(MkpCigarPtr cg, bool wide, uint32_t n_cigar, uint32_t c) {
   typedef uint32_t U2 __attribute__((ext_vector_type(2)));
   typedef const __attribute__((address_space(1))) U2* P2;
   const uint32_t k = c + 4u * (uint32_t)lane_id();
@@ -154,7 +77,7 @@ __device__ __forceinline__ uint4 cigar_quad_s_load(MkpCigarPtr cg, bool wide, ui
   if (wide) { const U2 hi = *reinterpret_cast<P2>(cg + off + 8u); r.z = hi.x; r.w = hi.y; }
   return r;
 }
-__device__ __forceinline__ uint4 cigar_quad_s_ops(uint4 r, bool wide, uint32_t n_cigar, uint32_t c) {
+__device__ __forceinline__ uint4 cigar_quad_ops(uint4 r, bool wide, uint32_t n_cigar, uint32_t c) {
   const uint32_t k = c + 4u * (uint32_t)lane_id();
   if (!wide) r = make_uint4(mkp_cigar16_unpack(r.x), mkp_cigar16_unpack(r.x >> 16), mkp_cigar16_unpack(r.y), mkp_cigar16_unpack(r.y >> 16));
   if (__any(k + 4u > n_cigar)) { if (k >= n_cigar) r.x = 5u; if (k + 1u >= n_cigar) r.y = 5u; if (k + 2u >= n_cigar) r.z = 5u;
@@ -162,17 +85,17 @@ __device__ __forceinline__ uint4 cigar_quad_s_ops(uint4 r, bool wide, uint32_t n
     }
   return r;
 }
-__device__ __forceinline__ void refwin_s_init(RefWinS& w, MkpCigarPtr cg, bool wide, uint32_t n_cigar, int32_t ref_start) {
+__device__ __forceinline__ void cigwin_init(CigarWin& w, MkpCigarPtr cg, bool wide, uint32_t n_cigar, int32_t ref_start) {
   w.c0 = 0u - 256u; w.q_run = 0; w.r_run = ref_start; w.Rtot = 0; w.Qtot = 0; w.re = w.m1 = w.m2 = w.m3 = 0;
     w.pk[0] = w.pk[1] = w.pk[2] = w.pk[3] = 0;
-  w.pref = cigar_quad_s_load(cg, wide, n_cigar, 0);
+  w.pref = cigar_quad_load(cg, wide, n_cigar, 0);
 }
 // the next 256 ops; false behind the last op
-__device__ __forceinline__ bool refwin_s_next(RefWinS& w, MkpCigarPtr cg, bool wide, uint32_t n_cigar, int32_t ref_start) {
+__device__ __forceinline__ bool cigwin_next(CigarWin& w, MkpCigarPtr cg, bool wide, uint32_t n_cigar, int32_t ref_start) {
   w.c0 = rfl(w.c0 + 256u); w.q_run = rfl(w.q_run + w.Qtot); w.r_run = (int32_t)rfl((uint32_t)w.r_run + w.Rtot);
   if (w.c0 >= n_cigar) { w.Rtot = 0; w.Qtot = 0; return false; }
-  const uint4 v = cigar_quad_s_ops(w.pref, wide, n_cigar, w.c0);
-  w.pref = cigar_quad_s_load(cg, wide, n_cigar, w.c0 + 256u);   // requested one window ahead
+  const uint4 v = cigar_quad_ops(w.pref, wide, n_cigar, w.c0);
+  w.pref = cigar_quad_load(cg, wide, n_cigar, w.c0 + 256u);   // requested one window ahead
   const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
   uint32_t ql[4], rl[4], kind[4];
 #pragma unroll
@@ -199,7 +122,7 @@ __device__ __forceinline__ bool refwin_s_next(RefWinS& w, MkpCigarPtr cg, bool w
   return true;
 }
 // one pass over the lanes whose position lies in the loaded window
-__device__ __forceinline__ void refwin_s_pass(const RefWinS& w, int32_t ref_start, bool& pending, int32_t p, uint32_t& kind, uint32_t& q) {
+__device__ __forceinline__ void cigwin_pass(const CigarWin& w, int32_t ref_start, bool& pending, int32_t p, uint32_t& kind, uint32_t& q) {
   const uint32_t rel0 = (uint32_t)(p - w.r_run);
   const bool inw = pending && rel0 < w.Rtot;
   if (!__any(inw)) return;
@@ -219,13 +142,13 @@ __device__ __forceinline__ void refwin_s_pass(const RefWinS& w, int32_t ref_star
   const uint32_t pk = rel < o_m1 ? o0 : rel < o_m2 ? o1 : rel < o_m3 ? o2 : o3;
   if (inw) { kind = pk & 3u; q = (uint32_t)((p - ref_start) + ((int32_t)pk >> 2)); pending = false; }
 }
-__device__ __forceinline__ void refwin_s_map(RefWinS& w, MkpCigarPtr cg, bool wide, uint32_t n_cigar, int32_t ref_start, bool valid, int32_t p,
+__device__ __forceinline__ void cigwin_map(CigarWin& w, MkpCigarPtr cg, bool wide, uint32_t n_cigar, int32_t ref_start, bool valid, int32_t p,
     uint32_t* kind_out, uint32_t* q_out) {
   bool pending = valid; uint32_t kind = 2u, q = 0u;
-  refwin_s_pass(w, ref_start, pending, p, kind, q);
+  cigwin_pass(w, ref_start, pending, p, kind, q);
   while (__any(pending)) {
-    if (!refwin_s_next(w, cg, wide, n_cigar, ref_start)) break;   // (cannot happen for positions inside the span)
-    refwin_s_pass(w, ref_start, pending, p, kind, q);
+    if (!cigwin_next(w, cg, wide, n_cigar, ref_start)) break;   // (cannot happen for positions inside the span)
+    cigwin_pass(w, ref_start, pending, p, kind, q);
   }
   *kind_out = kind; *q_out = q;
 }
@@ -324,7 +247,7 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
         const uint32_t incl = wave_incl_scan(c), cnt = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         const uint32_t j0 = j;
         bm[lane] = 0u;
-        wave_lds_fence();
+        wave_lds_sync();
         for (;;) {
           const uint32_t i = j + (uint32_t)lane;
           const bool valid = i < t_n;
@@ -354,7 +277,7 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
           j += nh;
           if (nh < 64u) break;
         }
-        wave_lds_fence();
+        wave_lds_sync();
         lw = bm[lane];
         const uint32_t lc = (uint32_t)__popc(lw), li = wave_incl_scan(lc);
         // listed calls at the stored bases before word w: on a forward read those walked before it; on a reverse read all of them but the
@@ -425,7 +348,7 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   const uint32_t n_ent = h.n_ent, cov_rel = h.cov_off - h.gs0;
   const MkpSlotEnt* __restrict__ ents = slot_ent + h.ent_off;
   uint2 p_next = (uint32_t)lane < n_ent ? ldo<uint2>(ents, 8u * (uint32_t)lane) : make_uint2(0u, 0u);
-  RefWinS rw; refwin_s_init(rw, cg, cg_wide, h.n_cigar, h.ref_start);
+  CigarWin rw; cigwin_init(rw, cg, cg_wide, h.n_cigar, h.ref_start);
 
   // ---- the read's one (mod strand, base) group.  The caller's walk over a call's map in iteration order is resolved once per
   // layout by the host (MkpFusedDesc: one scalar load): where the ML byte of the i-th code sits (tag + index: offset and stride
@@ -477,7 +400,7 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   const uint32_t n_ent_walk = n_ent;
 #endif
   // The loop is a software pipeline, two steps deep.  A step is three stages:
-  //   A(s)  reference -> query of the step's 64 slots (refwin_s_map), then the plane gather pe(s) and the slot entries of step s + 1 (one
+  //   A(s)  reference -> query of the step's 64 slots (cigwin_map), then the plane gather pe(s) and the slot entries of step s + 1 (one
   //         8-byte request per lane: position and global index) are requested.
   //         Both addresses are unconditional — clamped into the read's own plane / slot run — and the entry is masked where it is
   //         used: a load under a divergent branch is waited for on the spot.
@@ -504,7 +427,7 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
 #ifdef MKP_DEBUG
     if (prm.debug_skip & 64u) { kind = 0u; q = min((uint32_t)(p - h.ref_start), L - 1u); } else   // ablation: no CIGAR mapping
 #endif
-    refwin_s_map(rw, cg, cg_wide, h.n_cigar, h.ref_start, valid, p, &kind, &q);
+    cigwin_map(rw, cg, cg_wide, h.n_cigar, h.ref_start, valid, p, &kind, &q);
     // the plane entry of the base: its 2-bit code, bit q & 31 of .listed = a listed call sits here, .before + the listed bits below it =
     // its stored-order ordinal
     pe = ldo<uint4>(pl, 16u * min(q >> 5, pl_last));
@@ -657,7 +580,10 @@ extern "C" __global__ void __attribute__((amdgpu_num_sgpr(MKP_DECODE_SGPRS))) __
 // An event's counter id / tally strand are those the decode kernels computed; the first event on a position (bit 12) replaces the
 // NoCall of the base, a second one (pos_call and neg_call on one base, pileup/mod.rs:889-938) goes to the read's overflow list —
 // written over the front of its own event slice, which holds only events already consumed.
-extern "C" __global__ void __launch_bounds__(256) mkp_cover_reads(SLOT_PARAMS(MkpRunParams)) {
+extern "C" __global__ void __launch_bounds__(256) mkp_cover_reads(const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads,
+    const uint32_t* __restrict__ read_ids, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ seqs,
+    const uint32_t* __restrict__ slot_pos, uint8_t* __restrict__ cov, MkpVisit* __restrict__ visits, MkpEvent* __restrict__ events,
+    MkpReadOut* __restrict__ readout) {
   __shared__ uint32_t stage_all[4][64];
   const int lane = lane_id();
   const uint32_t wib = rfl(threadIdx.x >> 6);
@@ -670,15 +596,13 @@ extern "C" __global__ void __launch_bounds__(256) mkp_cover_reads(SLOT_PARAMS(Mk
   const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
   const uint32_t aln = rev ? 1u : 0u, L = h.l_seq;
   const uint8_t* __restrict__ seqb = seqs + h.seq_off;
-  const uint32_t* __restrict__ cg = cigar + h.cigar_off;
+  const MkpCigarPtr cg = (MkpCigarPtr)(cigar + h.cigar_off);   // (the BAM words: `wide`)
   const bool ok = ro.ok == 1u;
   const uint32_t n_ev = ok ? ro.n_events : 0u;
   MkpEvent* __restrict__ ev = events + h.event_off;
   const uint32_t n_sl = h.n_sl, gs0 = h.gs0;
   uint8_t* __restrict__ covp = cov + h.cov_off;
-  RefWin rw; rw.c0 = 0; rw.q_run = 0; rw.r_run = h.ref_start; rw.Rtot = 0; rw.Qtot = 0; rw.re = rw.m1 = rw.m2 = rw.m3 = 0;
-    rw.pk[0] = rw.pk[1] = rw.pk[2] = rw.pk[3] = 0; rw.loaded = false;
-  rw.pref = cigar_quad(cg, h.n_cigar, 0);
+  CigarWin rw; cigwin_init(rw, cg, true, h.n_cigar, h.ref_start);
   uint32_t p_next = (uint32_t)lane < n_sl ? slot_pos[gs0 + (uint32_t)lane] : 0u;
   uint32_t ec = 0, n_over = 0; bool gaps = false;
   stage[lane] = 0xffffffffu;
@@ -687,7 +611,7 @@ extern "C" __global__ void __launch_bounds__(256) mkp_cover_reads(SLOT_PARAMS(Mk
     const int32_t p = (int32_t)p_next;
     { const uint32_t in = i + 64u; p_next = in < n_sl ? slot_pos[gs0 + in] : 0u; }
     uint32_t kind, q;
-    refwin_map(rw, cg, h.n_cigar, h.ref_start, valid, p, &kind, &q);
+    cigwin_map(rw, cg, true, h.n_cigar, h.ref_start, valid, p, &kind, &q);
     const bool is_match = valid && kind == 0u && q < L;
     const uint32_t byte = is_match ? (uint32_t)seqb[q >> 1] : 0u;
     const uint32_t nib = (q & 1u) ? (byte & 15u) : (byte >> 4);
@@ -698,7 +622,7 @@ extern "C" __global__ void __launch_bounds__(256) mkp_cover_reads(SLOT_PARAMS(Mk
       const uint32_t nval = min(64u, n_sl - s0);
       const uint32_t pkey = valid ? (uint32_t)p : 0xffffffffu;
       const uint32_t p_hi = (uint32_t)__builtin_amdgcn_readlane((int)pkey, (int)(nval - 1u));
-      wave_lds_fence();
+      wave_lds_sync();
       for (;;) {
         const uint32_t k = ec + (uint32_t)lane; const bool in = k < n_ev;
         MkpEvent e; e.pos = 0xffffffffu; e.info = 0;
@@ -717,7 +641,7 @@ extern "C" __global__ void __launch_bounds__(256) mkp_cover_reads(SLOT_PARAMS(Mk
         ec += nt;
         if (nt < 64u) break;
       }
-      wave_lds_fence();
+      wave_lds_sync();
       const uint32_t sv = stage[lane];
       if (sv != 0xffffffffu) { fb = sv; stage[lane] = 0xffffffffu; }
     }
@@ -735,21 +659,142 @@ extern "C" __global__ void __launch_bounds__(256) mkp_cover_reads(SLOT_PARAMS(Mk
 }
 
 // ----------------------------------------------------------------------------------------------------------------------
-// mkp_pileup_stream: accumulate + emit over the feature stream.  LDS: [counter | observed-code slot][S] packed tallies ('+' tally
-// in the low, '-' in the high 16 bits; WIDE — the _wide kernels, for shards whose deepest column may hold more than 65 535 records — one
-// u32 plane per strand instead, [counter | observed-code slot][strand][S]), the tile's slot positions, a word per slot for the emission (focus byte | strand-combining partners) and the row map.  Waves draw the tile's candidate
-// reads from an LDS ticket; a visit = the read's MkpVisit (scalar loads), its bytes for the tile's slots (a dword per lane), one LDS
-// atomic per feature.  Observed codes: +1 / -1 at the ends of the read's slot range (and at every change between covered and not
-// covered when the read holds ref-skips).
-//
-// Row emission (round 6; rounds 2-5 ran the parameter-driven interpreter of mkp_dev_rows.hpp twice per slot — count, then write — with one
-// thread per slot: ~800 VALU instructions per thread, 29 spilled registers, rows of a slot written with stride-2 stores):
-//   E1  one thread per SLOT decides which rows exist: a bit per (strand | motif, code group) candidate — existence needs the coverage of
-//       the candidate's primary base and its observed-code count, a handful of LDS reads — and counts them;
-//   E2  block scan of the counts; wave 0 reserves the tile's run in the row buffer (decoupled look-back over the runs before, in ticket
-//       order) while every thread scatters (slot, candidate) words of its rows into the ROW MAP in LDS;
-//   E3  one thread per ROW fills its row from the tallies and stores it: every store instruction writes 64 consecutive rows of one column.
-// MkpRunParams is resolved once per workgroup into a small table (StreamProg) so that neither pass walks slot lists.
+// mkp_pileup_stream: accumulate + emit over the feature stream.  LDS: the regions of StreamLds (mkp_dev_rows.hpp) — packed strand tallies
+// per counter and observed-code slot (WIDE — the _wide kernels, for shards whose deepest column may hold more than 65 535 records — one
+// u32 plane per strand instead), the tile's slot positions, a word per slot for the emission and the row map.  Waves draw the tile's
+// candidate reads from an LDS ticket; a visit = the read's MkpVisit (scalar loads), its bytes for the tile's slots (a dword per lane), one
+// LDS atomic per feature.  Observed codes: +1 / -1 at the ends of the read's slot range (and at every change between covered and not
+// covered when the read holds ref-skips).  Rows: emit_stream_rows (mkp_dev_rows.hpp); MkpRunParams is resolved once per workgroup into a
+// small table (StreamProg) so that the emission does not walk slot lists.
+// The body reads top to bottom: prologue, then per round of candidates compaction and visits, the observed-code scans, the rows.
+
+// What does not hang on the tile's ticket: the tallies are cleared (their size is a kernel argument), the parameter block and the combos
+// come in.  Callers put a barrier behind it.
+__device__ __forceinline__ void stream_prologue(uint32_t* __restrict__ lds, uint32_t tal_words, const MkpRunParams* __restrict__ prmp,
+    uint32_t* __restrict__ prm_lds, const MkpCombo* __restrict__ combos, uint32_t n_combos, uint32_t* __restrict__ combo_lds) {
+  const uint32_t nv = tal_words >> 2; uint4* l4 = reinterpret_cast<uint4*>(lds);
+  for (uint32_t k = threadIdx.x; k < nv; k += PILEUP_THREADS) l4[k] = make_uint4(0u, 0u, 0u, 0u);
+  for (uint32_t k = (nv << 2) + threadIdx.x; k < tal_words; k += PILEUP_THREADS) lds[k] = 0;
+  for (uint32_t kq = threadIdx.x; kq < sizeof(MkpRunParams) / 4; kq += PILEUP_THREADS) prm_lds[kq] = reinterpret_cast<const uint32_t*>(prmp)[kq];
+  for (uint32_t kq = threadIdx.x; kq < n_combos * (sizeof(MkpCombo) / 4); kq += PILEUP_THREADS) combo_lds[kq] = reinterpret_cast<const uint32_t*>(combos)[kq];
+}
+
+// Where a feature of (counter `row`, tally strand `st`) is tallied: the byte offset of its LDS row (S4 = 4 * S) and the increment.  Narrow:
+// one multiply for the row, one multiply-add for the increment (1 or 1 << 16); WIDE: 1 on the strand's plane 2 * counter + strand.
+struct TallyAt { uint32_t off, inc; };
+template <bool WIDE> __device__ __forceinline__ TallyAt tally_at(uint32_t row, uint32_t st, uint32_t S4) {
+  if (WIDE) return {(uint32_t)__umul24(2u * row + st, S4), 1u};
+  return {(uint32_t)__umul24(row, S4), __umul24(st, 0xffffu) + 1u};
+}
+
+// one visit: the read's bytes for this tile's slots (first dword per lane already in `wcur`), its observed codes, its overflow events
+template <bool KEYED, bool WIDE>
+__device__ __forceinline__ void stream_visit(const MkpVisit& v, uint32_t wcur, const StreamLds& L, const MkpSTile& tl, uint32_t n_oslots,
+    uint32_t key_filter, const uint8_t* __restrict__ cov, const MkpEvent* __restrict__ events) {
+  const int lane = lane_id();
+  const uint32_t gh0 = tl.gh0, gh1 = tl.gh1, n_tslots = gh1 - gh0, S = L.S, S4 = S * 4u, talbase = lds_addr(L.tal);
+  uint32_t* __restrict__ obs = L.obs;
+  const uint32_t a = max(v.gs0, gh0), b = min(v.gs0 + v.n_sl, gh1);
+  if (a >= b) return;
+  if (KEYED && (v.flags >> 8) != key_filter) return;   // --partition-tag: one pass per key
+  const uint32_t k_lo = a - v.gs0, k_hi = b - v.gs0;      // the read's bytes for this tile
+  const uint32_t col0 = v.gs0 - gh0;                      // column of byte k = col0 + k (mod 2^32)
+  const uint8_t* __restrict__ cp = cov + v.cov_off;
+  const uint32_t kfirst = (k_lo & ~3u) + 4u * (uint32_t)lane;
+  // observed mod codes over the columns the read is in (add_mod_codes_for_record, pileup/mod.rs:831-835)
+  if ((v.flags & MKP_VF_OK) && (v.obs0 | v.obs1)) {
+    // one lane per (observed-code slot, tally strand): +1 where the read enters the tile's columns, -1 behind its last
+    if (!(v.flags & MKP_VF_GAPS)) {
+      const uint32_t sl = (uint32_t)lane >> 1, st = (uint32_t)lane & 1u;
+      if (sl < n_oslots && (((st ? v.obs1 : v.obs0) >> sl) & 1u)) obs_diff<WIDE>(obs, S, sl, st, a - gh0, b - gh0, n_tslots, false);
+    } else {   // ref-skips: the read is not in those columns (alignment.is_refskip()) — a change of state per boundary
+      for (uint32_t k = k_lo + (uint32_t)lane; k <= k_hi; k += 64) {
+        const bool cur = k < k_hi && cp[k] != MKP_FB_NONE, prev = k > k_lo && cp[k - 1u] != MKP_FB_NONE;
+        const uint32_t col = col0 + k;
+        if (cur != prev && col < n_tslots) for (uint32_t s = 0; s < 2; s++) {
+          uint32_t m = s ? v.obs1 : v.obs0;
+          const uint32_t inc = WIDE ? 1u : s ? 0x10000u : 1u;
+          while (m) { const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
+            atomicAdd(&obs[(WIDE ? 2u * sl + s : sl) * S + col], cur ? inc : 0u - inc); }
+        }
+      }
+    }
+  }
+  // bytes outside [k_lo, k_hi) — the ends of the read's first and last dword in this tile — become "no feature": the first dword's (lane 0 of
+  // the first round only) once per visit, the last dword's once per round
+  uint32_t lom = kfirst < k_lo ? ~(0xffffffffu << (8u * (k_lo - kfirst))) : 0u;
+  for (uint32_t k = kfirst;; k += 256u) {
+    uint32_t w = wcur | lom;
+    lom = 0;
+    const uint32_t kn = k + 256u;
+    wcur = kn < k_hi ? *reinterpret_cast<const uint32_t*>(cp + kn) : 0xffffffffu;
+    if (k + 4u > k_hi) w |= k >= k_hi ? 0xffffffffu : 0xffffffffu << (8u * (k_hi - k));
+    const uint32_t lane_base = talbase + 4u * (col0 + k);
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+      // feature byte: [0:4] counter, [5] tally strand, >= 0x40 none.  One multiply-add for the row address (the byte's column goes into the
+      // instruction's offset field), one for the increment (tally_at)
+      if (!(w & (0xc0u << (8u * j)))) {
+        const TallyAt t = tally_at<WIDE>((w >> (8u * j)) & 31u, (w >> (8u * j + 5u)) & 1u, S4);
+        lds_u32* col = (lds_u32*)(uintptr_t)(lane_base + t.off);
+        __hip_atomic_fetch_add(col + j, t.inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    }
+    if (!__any(kn < k_hi)) break;
+  }
+  for (uint32_t k = (uint32_t)lane; k < v.n_over; k += 64) {   // second features on one column
+    const MkpEvent e = events[v.over_off + k];
+    const TallyAt t = tally_at<WIDE>(e.info & 31u, (e.info >> 5) & 1u, S4);
+    if (e.pos >= gh0 && e.pos < gh1) lds_add(talbase + 4u * (e.pos - gh0) + t.off, t.inc);
+  }
+}
+
+// The tile's candidate reads [first, last) are a superset (everything that starts before the tile's end and behind the longest read's reach:
+// about half of them end before the tile starts, C3).  Every thread looks at one candidate of the round that starts at c0 — slot range
+// only, one 8-byte load — and the ones that reach into the tile are compacted into a list in LDS (the row map's words: the emission is not
+// running yet).  Returns the length of the list; the barriers around it are inside.
+template <bool KEYED>
+__device__ __forceinline__ uint32_t stream_candidates(const MkpVisit* __restrict__ visits, uint32_t c0, const MkpSTile& tl, uint32_t key_filter,
+    uint32_t* __restrict__ list, uint32_t* next_read, uint32_t* n_real) {
+  // (the round before is through with the list)
+  if (c0 != tl.first) { __syncthreads(); if (threadIdx.x == 0) { *next_read = 0; *n_real = 0; } __syncthreads(); }
+  const uint32_t cnd = c0 + threadIdx.x; bool reaches = false;
+  if (cnd < tl.last) {
+    const uint2 gr = *reinterpret_cast<const uint2*>(&visits[cnd]);   // gs0, n_sl
+    reaches = max(gr.x, tl.gh0) < min(gr.x + gr.y, tl.gh1);
+    if (KEYED && reaches) reaches = (visits[cnd].flags >> 8) == key_filter;   // --partition-tag: one pass per key
+  }
+  const unsigned long long bal = __ballot(reaches);
+  uint32_t w0 = 0; if (lane_id() == 0 && bal) w0 = atomicAdd(n_real, (uint32_t)__popcll(bal));
+  w0 = rfl(w0);
+  if (reaches) list[w0 + (uint32_t)__popcll(bal & lanemask_lt())] = cnd;
+  __syncthreads();
+  return *n_real;
+}
+// The waves draw from that list, VB at a time: the visit records and the first stream dword of each are requested before any of them is
+// used (a visit is a chain ticket -> 32-byte record -> one dword per lane -> LDS atomics).  With the emission row-major the visits are
+// the kernel — 0.077 of 0.133 ms (profiles/r06_stream_ablation.txt) — and every empty candidate used to cost a ticket, a scalar load and its wait.
+template <bool KEYED, uint32_t VB, bool WIDE>
+__device__ __forceinline__ void stream_draw_visits(const MkpVisit* __restrict__ visits, uint32_t n_here, const StreamLds& L, const MkpSTile& tl,
+    uint32_t n_oslots, uint32_t key_filter, const uint8_t* __restrict__ cov, const MkpEvent* __restrict__ events, uint32_t* next_read) {
+  const int lane = lane_id();
+  for (;;) {
+    uint32_t base; { uint32_t ticket = 0; if (lane == 0) ticket = atomicAdd(next_read, VB); base = rfl(ticket); }
+    if (base >= n_here) break;
+    MkpVisit vv[VB]; uint32_t ww[VB];
+#pragma unroll
+    for (uint32_t j = 0; j < VB; j++) vv[j] = visits[rfl(L.rowmap[min(base + j, n_here - 1u)])];   // (uniform: scalar loads)
+#pragma unroll
+    for (uint32_t j = 0; j < VB; j++) {
+      const uint32_t a = max(vv[j].gs0, tl.gh0), b = min(vv[j].gs0 + vv[j].n_sl, tl.gh1);
+      const uint32_t k_lo = a - vv[j].gs0, k_hi = b - vv[j].gs0, kfirst = (k_lo & ~3u) + 4u * (uint32_t)lane;
+      ww[j] = (a < b && kfirst < k_hi) ? *reinterpret_cast<const uint32_t*>(cov + vv[j].cov_off + kfirst) : 0xffffffffu;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < VB; j++) if (base + j < n_here) stream_visit<KEYED, WIDE>(vv[j], ww[j], L, tl, n_oslots, key_filter, cov, events);
+  }
+}
+
 template <bool KEYED, uint32_t VB /* visits drawn per ticket, their records and first stream dwords requested together */, bool WIDE = false>
 __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ visits, const uint8_t* __restrict__ cov,
     const MkpEvent* __restrict__ events,
@@ -765,296 +810,48 @@ __device__ __forceinline__ void pileup_stream_body(const MkpVisit* __restrict__ 
   __shared__ __attribute__((aligned(16))) uint32_t prm_lds[(sizeof(MkpRunParams) + 3) / 4];
   __shared__ __attribute__((aligned(16))) uint32_t combo_lds[64 * sizeof(MkpCombo) / 4];
   __shared__ StreamProg prog;
+  // ---- prologue
   // A workgroup takes the next TILE from an atomic ticket (row_cursor[0]; the host zeroes it before the first pass), not from blockIdx: rows
   // leave in genome order through a look-back over the runs before (mkp_dev_rows.hpp), and a run may only wait for runs whose workgroups
   // are already running — true for tickets whatever the dispatch order, with any number of contexts on the device.
   // The prologue is a chain of memory round trips in front of the first tally — ticket, tile record, visit records, stream dwords.  What does
-  // not hang on it starts beside the ticket: the tallies are cleared at once (their size is a kernel argument), the parameter block and the
-  // combos come in; the slot positions and focus bytes (needed by the emission only) are requested when the tile is known and land in LDS
-  // behind the visits.  ONE barrier stands between a workgroup's start and its first visit (round 5: two, the second behind the positions).
+  // not hang on it starts beside the ticket (stream_prologue); the slot positions and focus bytes (needed by the emission only) are
+  // requested when the tile is known and land in LDS behind the visits.  ONE barrier stands between a workgroup's start and its first visit.
   if (threadIdx.x == 0) { run_ticket = atomicAdd(row_cursor, 1u); next_read = 0; n_real = 0; }
-  { const uint32_t nv = tal_words >> 2; uint4* l4 = reinterpret_cast<uint4*>(lds);
-    for (uint32_t k = threadIdx.x; k < nv; k += PILEUP_THREADS) l4[k] = make_uint4(0u, 0u, 0u, 0u);
-    for (uint32_t k = (nv << 2) + threadIdx.x; k < tal_words; k += PILEUP_THREADS) lds[k] = 0; }
-  for (uint32_t kq = threadIdx.x; kq < sizeof(MkpRunParams) / 4; kq += PILEUP_THREADS) prm_lds[kq] = reinterpret_cast<const uint32_t*>(prmp)[kq];
-  for (uint32_t kq = threadIdx.x; kq < n_combos * (sizeof(MkpCombo) / 4); kq += PILEUP_THREADS) combo_lds[kq] = reinterpret_cast<const uint32_t*>(combos)[kq];
+  stream_prologue(lds, tal_words, prmp, prm_lds, combos, n_combos, combo_lds);
   __syncthreads();
   const MkpRunParams& prm = *reinterpret_cast<const MkpRunParams*>(prm_lds);
-  const MkpCombo* combos_l = reinterpret_cast<const MkpCombo*>(combo_lds);
   const uint32_t n_counters = rfl(prm.n_counters), n_oslots = rfl(prm.n_slots);
-  uint32_t* __restrict__ tal = lds;
-  uint32_t* __restrict__ obs = lds + n_counters * S * (WIDE ? 2u : 1u);
-  int32_t* __restrict__ fpos = reinterpret_cast<int32_t*>(lds + tal_words);
-  // per slot: [0:7] focus byte, [8 + 6m ..] partner column of the m-th '+' motif (strand combining)
-  uint32_t* __restrict__ aux = lds + tal_words + S;
-  uint32_t* __restrict__ rowmap = lds + tal_words + 2u * S;
-  const int lane = lane_id();
-  const uint32_t wave = rfl(threadIdx.x >> 6);
-  const uint32_t run = rfl(run_ticket);                               // row-run index: key pass * tiles + tile (passes run one after the other on the stream)
+  const StreamLds L = {lds, lds + n_counters * S * (WIDE ? 2u : 1u), reinterpret_cast<int32_t*>(lds + tal_words), lds + tal_words + S,
+      lds + tal_words + 2u * S, S};
+  const uint32_t run = rfl(run_ticket);   // row-run index: key pass * tiles + tile (passes run one after the other on the stream)
   const uint32_t tix = run - key_run * n_tiles;
   if (tix >= n_tiles) { if (threadIdx.x == 0) atomicOr(dev_err, ERR_ROW_CAP); return; }   // (cannot happen: one ticket per workgroup)
   const MkpSTile tl = tiles[tix];   // (uniform: scalar loads)
-  const uint32_t gh0 = tl.gh0, gh1 = tl.gh1, n_tslots = gh1 - gh0;
-  const uint32_t rid_first = tl.first, rid_end = tl.last;
+  const uint32_t n_tslots = tl.gh1 - tl.gh0;
   // this thread's slot: position now, focus byte behind the visits
   int32_t my_pos = 0;
-  if (threadIdx.x < n_tslots) my_pos = (int32_t)slot_pos[gh0 + threadIdx.x];
+  if (threadIdx.x < n_tslots) my_pos = (int32_t)slot_pos[tl.gh0 + threadIdx.x];
   rowprog_build(prm, n_counters, prog);   // (threads 0..15; read after the visits' barrier)
-  const uint32_t talbase = lds_addr(tal), S4 = S * 4u;
-  // one visit: the read's bytes for this tile's slots (first dword per lane already in `wcur`), its observed codes, its overflow events
-  auto visit = [&](const MkpVisit& v, uint32_t wcur) {
-    const uint32_t a = max(v.gs0, gh0), b = min(v.gs0 + v.n_sl, gh1);
-    if (a >= b) return;
-    if (KEYED && (v.flags >> 8) != key_filter) return;   // --partition-tag: one pass per key
-    const uint32_t k_lo = a - v.gs0, k_hi = b - v.gs0;      // the read's bytes for this tile
-    const uint32_t col0 = v.gs0 - gh0;                      // column of byte k = col0 + k (mod 2^32)
-    const uint8_t* __restrict__ cp = cov + v.cov_off;
-    const uint32_t kfirst = (k_lo & ~3u) + 4u * (uint32_t)lane;
-    // observed mod codes over the columns the read is in (add_mod_codes_for_record, pileup/mod.rs:831-835)
-    if ((v.flags & MKP_VF_OK) && (v.obs0 | v.obs1)) {
-      // one lane per (observed-code slot, tally strand): +1 where the read enters the tile's columns, -1 behind its last
-      if (!(v.flags & MKP_VF_GAPS)) {
-        const uint32_t sl = (uint32_t)lane >> 1, st = (uint32_t)lane & 1u;
-        if (sl < n_oslots && (((st ? v.obs1 : v.obs0) >> sl) & 1u)) {
-          const uint32_t inc = WIDE ? 1u : st ? 0x10000u : 1u, at = __umul24(WIDE ? 2u * sl + st : sl, S) + (a - gh0);
-          atomicAdd(&obs[at], inc);
-          if (b - gh0 < n_tslots) atomicAdd(&obs[at + (b - a)], 0u - inc);
-        }
-      } else {   // ref-skips: the read is not in those columns (alignment.is_refskip()) — a change of state per boundary
-        for (uint32_t k = k_lo + (uint32_t)lane; k <= k_hi; k += 64) {
-          const bool cur = k < k_hi && cp[k] != MKP_FB_NONE, prev = k > k_lo && cp[k - 1u] != MKP_FB_NONE;
-          const uint32_t col = col0 + k;
-          if (cur != prev && col < n_tslots) for (uint32_t s = 0; s < 2; s++) {
-            uint32_t m = s ? v.obs1 : v.obs0;
-            const uint32_t inc = WIDE ? 1u : s ? 0x10000u : 1u;
-            while (m) { const uint32_t sl = (uint32_t)__ffs((int)m) - 1u; m &= m - 1u;
-              atomicAdd(&obs[(WIDE ? 2u * sl + s : sl) * S + col], cur ? inc : 0u - inc); }
-          }
-        }
-      }
-    }
-    // bytes outside [k_lo, k_hi) — the ends of the read's first and last dword in this tile — become "no feature": the first dword's (lane 0 of
-    // the first round only) once per visit, the last dword's once per round
-    uint32_t lom = kfirst < k_lo ? ~(0xffffffffu << (8u * (k_lo - kfirst))) : 0u;
-    for (uint32_t k = kfirst;; k += 256u) {
-      uint32_t w = wcur | lom;
-      lom = 0;
-      const uint32_t kn = k + 256u;
-      wcur = kn < k_hi ? *reinterpret_cast<const uint32_t*>(cp + kn) : 0xffffffffu;
-      if (k + 4u > k_hi) w |= k >= k_hi ? 0xffffffffu : 0xffffffffu << (8u * (k_hi - k));
-      const uint32_t lane_base = talbase + 4u * (col0 + k);
-#pragma unroll
-      for (uint32_t j = 0; j < 4; j++) {
-        // feature byte: [0:4] counter, [5] tally strand, >= 0x40 none.  One multiply-add for the row address (the byte's column goes into the
-        // instruction's offset field), one for the increment (1 or 1 << 16; WIDE: 1 on the strand's plane 2 * counter + strand)
-        const uint32_t row = (w >> (8u * j)) & 31u, st = (w >> (8u * j + 5u)) & 1u;
-        if (!(w & (0xc0u << (8u * j)))) {
-          if (WIDE) {
-            lds_u32* col = (lds_u32*)(uintptr_t)(lane_base + __umul24(2u * row + st, S4));
-            __hip_atomic_fetch_add(col + j, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          } else {
-          lds_u32* col = (lds_u32*)(uintptr_t)(lane_base + __umul24(row, S4));
-          __hip_atomic_fetch_add(col + j, __umul24(st, 0xffffu) + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          }
-        }
-      }
-      if (!__any(kn < k_hi)) break;
-    }
-    if (v.n_over) {   // second features on one column
-      for (uint32_t k = (uint32_t)lane; k < v.n_over; k += 64) {
-        const MkpEvent e = events[v.over_off + k];
-        if (WIDE) { if (e.pos >= gh0 && e.pos < gh1) lds_add(talbase + 4u * (e.pos - gh0) + __umul24(2u * (e.info & 31u) + ((e.info >> 5) & 1u), S4), 1u); }
-        else
-        if (e.pos >= gh0 && e.pos < gh1) lds_add(talbase + 4u * (e.pos - gh0) + __umul24(e.info & 31u, S4), (e.info & 32u) ? 0x10000u : 1u);
-      }
-    }
-  };
-  // The tile's candidate reads [first, last) are a superset (everything that starts before the tile's end and behind the longest read's reach:
-  // about half of them end before the tile starts, C3).  Every thread looks at one candidate — slot range only, one 8-byte load — and the ones
-  // that reach into the tile are compacted into a list in LDS (the row map's words: the emission is not running yet); the waves then draw
-  // from that list, FOUR at a time: the visit records and the first stream dword of each are requested before any of them is used (a visit is
-  // a chain ticket -> 32-byte record -> one dword per lane -> LDS atomics).  Round 6 ablation (profiles/r06_stream_ablation.txt): with the
-  // emission rewritten the visits are the kernel — 0.077 of 0.133 ms — and every empty candidate used to cost a ticket, a scalar load and its wait.
-  for (uint32_t c0 = rid_first; c0 < rid_end; c0 += PILEUP_THREADS) {
+  // ---- candidates and visits, PILEUP_THREADS candidates per round
+  for (uint32_t c0 = tl.first; c0 < tl.last; c0 += PILEUP_THREADS) {
 #ifdef MKP_DEBUG
     if (prm.debug_skip & 1024u) break;   // ablation: no visits (prologue + scans + emission only)
 #endif
-    // (the round before is through with the list)
-    if (c0 != rid_first) { __syncthreads(); if (threadIdx.x == 0) { next_read = 0; n_real = 0; } __syncthreads(); }
-    { const uint32_t cnd = c0 + threadIdx.x; bool reaches = false;
-      if (cnd < rid_end) {
-        const uint2 gr = *reinterpret_cast<const uint2*>(&visits[cnd]);   // gs0, n_sl
-        reaches = max(gr.x, gh0) < min(gr.x + gr.y, gh1);
-        if (KEYED && reaches) reaches = (visits[cnd].flags >> 8) == key_filter;   // --partition-tag: one pass per key
-      }
-      const unsigned long long bal = __ballot(reaches);
-      uint32_t w0 = 0; if (lane == 0 && bal) w0 = atomicAdd(&n_real, (uint32_t)__popcll(bal));
-      w0 = rfl(w0);
-      if (reaches) rowmap[w0 + (uint32_t)__popcll(bal & lanemask_lt())] = cnd; }
-    __syncthreads();
-    const uint32_t n_here = n_real;
-    for (;;) {
-      uint32_t base; { uint32_t ticket = 0; if (lane == 0) ticket = atomicAdd(&next_read, VB); base = rfl(ticket); }
-      if (base >= n_here) break;
-      MkpVisit vv[VB]; uint32_t ww[VB];
-#pragma unroll
-      for (uint32_t j = 0; j < VB; j++) vv[j] = visits[rfl(rowmap[min(base + j, n_here - 1u)])];   // (uniform: scalar loads)
-#pragma unroll
-      for (uint32_t j = 0; j < VB; j++) {
-        const uint32_t a = max(vv[j].gs0, gh0), b = min(vv[j].gs0 + vv[j].n_sl, gh1);
-        const uint32_t k_lo = a - vv[j].gs0, k_hi = b - vv[j].gs0, kfirst = (k_lo & ~3u) + 4u * (uint32_t)lane;
-        ww[j] = (a < b && kfirst < k_hi) ? *reinterpret_cast<const uint32_t*>(cov + vv[j].cov_off + kfirst) : 0xffffffffu;
-      }
-#pragma unroll
-      for (uint32_t j = 0; j < VB; j++) if (base + j < n_here) visit(vv[j], ww[j]);
-    }
+    const uint32_t n_here = stream_candidates<KEYED>(visits, c0, tl, key_filter, L.rowmap, &next_read, &n_real);
+    stream_draw_visits<KEYED, VB, WIDE>(visits, n_here, L, tl, n_oslots, key_filter, cov, events, &next_read);
   }
   // the emission's per-slot words: position and focus byte (the byte's load overlaps the barrier and the scans below)
   uint32_t my_fv = 0;
-  if (threadIdx.x < n_tslots) { fpos[threadIdx.x] = my_pos; my_fv = prm.has_focus ? (uint32_t)focus[my_pos - prm.win_start] : 3u; }
+  if (threadIdx.x < n_tslots) { L.fpos[threadIdx.x] = my_pos; my_fv = prm.has_focus ? (uint32_t)focus[my_pos - prm.win_start] : 3u; }
   __syncthreads();
-  // observed-code difference arrays -> counts, in place and still packed (WIDE: one array per strand plane)
-  for (uint32_t a = wave; a < (WIDE ? 2u * n_oslots : n_oslots); a += PILEUP_WAVES) {
-    uint32_t* __restrict__ arr = obs + a * S;
-    uint32_t carry = 0;
-    for (uint32_t b0 = 0; b0 < n_tslots; b0 += 64) {
-      const uint32_t vv = (b0 + lane < n_tslots) ? arr[b0 + lane] : 0u;
-      const uint32_t sc = wave_incl_scan(vv);
-      if (b0 + lane < n_tslots) arr[b0 + lane] = sc + carry;
-      carry += (uint32_t)__builtin_amdgcn_readlane((int)sc, 63);
-    }
-  }
-  if (threadIdx.x < n_tslots) aux[threadIdx.x] = my_fv;
+  // ---- scans: observed-code difference arrays -> counts, in place and still packed (WIDE: one array per strand plane)
+  for (uint32_t a = rfl(threadIdx.x >> 6); a < (WIDE ? 2u * n_oslots : n_oslots); a += PILEUP_WAVES) prefix_sum_in_place(L.obs + a * S, n_tslots);
+  if (threadIdx.x < n_tslots) L.aux[threadIdx.x] = my_fv;
   __syncthreads();
-
-  // ---- E1: which rows does this thread's slot yield (FeatureVector::decode, pileup/mod.rs:412-446; combine_strand_features 469-561)
-  const StreamProg& P = prog;
-  const uint32_t n_groups = P.n_groups;
-  const bool combine = prm.combine_strands != 0;
-  const uint32_t i = threadIdx.x;
-  unsigned long long em = 0; uint32_t cnt = 0, mult0 = 1, mult1 = 1;
-#ifdef MKP_DEBUG
-  const bool dbg_norows = (prm.debug_skip & 2048u) != 0;   // ablation: no rows (the look-back word is still published so that nothing waits)
-#else
-  constexpr bool dbg_norows = false;
-#endif
-  if (!dbg_norows && i < n_tslots && my_pos >= tl.r0 && my_pos < tl.r1 && (my_fv & 3u)) {
-    const uint32_t rule = my_fv & 3u, combo = my_fv >> 2;
-    if (!combine) {
-      if (combo) { const MkpCombo& cb = combos_l[combo]; mult0 = cb.n_pos ? cb.n_pos : 1u; mult1 = cb.n_neg ? cb.n_neg : 1u; }
-      for (uint32_t s = 0; s < 2; s++) {
-        if (!((rule >> s) & 1u)) continue;
-        for (uint32_t g = 0; g < n_groups; g++) if (stream_row_exists<WIDE>(tal, S, n_counters, P, s, i, g)) em |= 1ull << (16u * s + g);
-      }
-      cnt = (uint32_t)__popc((uint32_t)em & 0xffffu) * mult0 + (uint32_t)__popc((uint32_t)(em >> 16) & 0xffffu) * mult1;
-    } else if (combo) {   // only '+' motif positions produce rows
-      const MkpCombo& cb = combos_l[combo];
-      const bool pos_ok = (rule & 1u) != 0;
-      uint32_t part = 0;
-      for (uint32_t m = 0; m < cb.n_pos; m++) {
-        const int delta = cb.pos_delta[m];
-        if (delta == -128) continue;   // not a palindrome / negative_strand_position() == None
-        const int idx = cb.pos_ids[m];
-        const int32_t qpos = my_pos + delta;
-        bool neg_ok = false; uint32_t iq = i;
-        if (delta != -127 && qpos >= prm.win_start && qpos < prm.win_end) {   // -127: the mate position is in another interval
-          // the partner's column: a focus position at most MKP_HALO away — a few columns up or down
-          if (delta > 0) { while (iq + 1u < n_tslots && fpos[iq + 1u] <= qpos) iq++; } else { while (iq > 0u && fpos[iq - 1u] >= qpos) iq--; }
-          if (fpos[iq] == qpos) {
-            const uint32_t fq = aux[iq] & 0xffu;
-            if ((fq & 2u) && (fq >> 2)) { const MkpCombo& cq = combos_l[fq >> 2];
-              for (uint32_t k = 0; k < cq.n_neg; k++) neg_ok |= (cq.neg_ids[k] == idx);
-              }
-          }
-        }
-        if (neg_ok) part |= ((iq - i + 32u) & 63u) << (8u + 6u * m);
-        for (uint32_t g = 0; g < n_groups; g++) {
-          if (!((P.info[g] >> 18) & 1u)) continue;   // grouped by code (BTreeMap)
-          bool any = false;
-          for (uint32_t gj = g; gj < n_groups && (gj == g || !((P.info[gj] >> 18) & 1u)); gj++)
-            any = any || (pos_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 0, i, gj))
-                || (neg_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 1, iq, gj));
-          if (any) { em |= 1ull << (16u * m + g); cnt++; }
-        }
-      }
-      if (part) aux[i] = my_fv | part;   // (own word; the other threads only look at the focus byte, which stays)
-    }
-  }
-  // ---- E2: place of every slot's rows inside the tile, the tile's place in the row buffer
-  const uint32_t inc2 = wave_incl_scan(cnt);
-  if (lane == 63) wave_tot[wave] = inc2;
-  __syncthreads();
-  uint32_t off = inc2 - cnt, tile_rows = 0;
-  for (uint32_t w2 = 0; w2 < PILEUP_WAVES; w2++) { const uint32_t t = wave_tot[w2]; if (w2 < wave) off += t; tile_rows += t; }
-  MkpRowsDev rows;
-  { const size_t cap = prm.row_capacity; uint32_t* q = rows_base;
-    rows.pos = q; rows.info = q + cap; rows.code = q + 2 * cap; rows.n_valid = q + 3 * cap; rows.n_mod = q + 4 * cap; rows.n_can = q + 5 * cap;
-      rows.n_other = q + 6 * cap;
-    rows.n_del = q + 7 * cap; rows.n_fail = q + 8 * cap; rows.n_diff = q + 9 * cap; rows.n_nocall = q + 10 * cap; }
-  for (uint32_t r0 = 0; r0 == 0u || r0 < tile_rows; r0 += MKP_STREAM_ROWMAP_WORDS) {
-    if (r0) __syncthreads();   // the round before has read the map
-    // (slot, candidate) of every row of this round: [0:9] slot, [10:13] group, [14:15] strand | motif, [16:17] which of the position's motif ids
-    if (cnt && off < r0 + MKP_STREAM_ROWMAP_WORDS && off + cnt > r0) {
-      uint32_t r = off;
-      for (uint32_t sm = 0; sm < 4u; sm++) {
-        uint32_t bits = (uint32_t)(em >> (16u * sm)) & 0xffffu;
-        const uint32_t mult = combine ? 1u : (sm ? mult1 : mult0);
-        while (bits) {
-          const uint32_t g = (uint32_t)__ffs((int)bits) - 1u; bits &= bits - 1u;
-          for (uint32_t k = 0; k < mult; k++, r++) if (r >= r0
-              && r < r0 + MKP_STREAM_ROWMAP_WORDS) rowmap[r - r0] = i | (g << 10) | (sm << 14) | (k << 16);
-        }
-      }
-    }
-    if (r0 == 0u && wave == 0u) {   // tile_row_off = the runs' look-back words (two dwords each); row_cursor[1] = total rows, written by the last run
-#ifdef MKP_DEBUG
-      uint32_t base;
-      // ablation: no look-back (rows in completion order)
-      if (prm.debug_skip & 4096u) { uint32_t b0 = 0; if (lane == 0) b0 = atomicAdd(row_cursor + 1, tile_rows); base = rfl(b0); }
-      else base = lookback_reserve_wave(reinterpret_cast<unsigned long long*>(tile_row_off), run, tile_rows);
-#else
-      const uint32_t base = lookback_reserve_wave(reinterpret_cast<unsigned long long*>(tile_row_off), run, tile_rows);
-#endif
-      if (lane == 0) {
-#ifdef MKP_DEBUG
-        if (!(prm.debug_skip & 4096u))
-#endif
-        if (run + 1u == n_runs) row_cursor[1] = base + tile_rows;
-        uint32_t s = tile_rows;
-        if (base + s > prm.row_capacity) { atomicOr(dev_err, ERR_ROW_CAP); s = 0; }
-        row_base_s = base; row_total_s = s;
-      }
-    }
-    __syncthreads();
-    // ---- E3: one thread per row
-    const uint32_t n_here = min(row_total_s, r0 + MKP_STREAM_ROWMAP_WORDS) > r0 ? min(row_total_s, r0 + MKP_STREAM_ROWMAP_WORDS) - r0 : 0u;
-    for (uint32_t rr = threadIdx.x; rr < n_here; rr += PILEUP_THREADS) {
-      const uint32_t e = rowmap[rr], si = e & 1023u, g = (e >> 10) & 15u, sm = (e >> 14) & 3u, k = (e >> 16) & 3u;
-      const uint32_t ax = aux[si], combo = (ax & 0xffu) >> 2;
-      RowAcc acc = {0, 0, 0, 0, 0, 0, 0, 0};
-      uint32_t strand, motif1;   // motif1 = motif id + 1 (0: none)
-      if (!combine) {
-        stream_row_add<WIDE>(tal, S, P, sm, si, g, acc);
-        strand = sm; motif1 = 0;
-        if (combo) { const MkpCombo& cb = combos_l[combo]; const uint32_t n_ids = sm ? cb.n_neg : cb.n_pos;
-          if (n_ids) motif1 = (uint32_t)(sm ? cb.neg_ids[k] : cb.pos_ids[k]) + 1u;
-          }
-      } else {
-        const MkpCombo& cb = combos_l[combo];
-        const uint32_t pd = (ax >> (8u + 6u * sm)) & 63u, iq = si + pd - 32u;
-        const bool pos_ok = (ax & 1u) != 0, neg_ok = pd != 0u;
-        for (uint32_t gj = g; gj < n_groups && (gj == g || !((P.info[gj] >> 18) & 1u)); gj++) {
-          if (pos_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 0, si, gj)) stream_row_add<WIDE>(tal, S, P, 0, si, gj, acc);
-          if (neg_ok && stream_row_exists<WIDE>(tal, S, n_counters, P, 1, iq, gj)) stream_row_add<WIDE>(tal, S, P, 1, iq, gj, acc);
-        }
-        strand = 2; motif1 = (uint32_t)cb.pos_ids[sm] + 1u;
-      }
-      const size_t at = (size_t)row_base_s + r0 + rr;
-      rows.pos[at] = (uint32_t)fpos[si]; rows.info[at] = strand | (motif1 << 8) | (key_filter << 16); rows.code[at] = P.code[g];
-      rows.n_valid[at] = acc.n_valid; rows.n_mod[at] = acc.n_mod; rows.n_can[at] = acc.n_can; rows.n_other[at] = acc.n_other;
-      rows.n_del[at] = acc.n_del; rows.n_fail[at] = acc.n_fail; rows.n_diff[at] = acc.n_diff; rows.n_nocall[at] = acc.n_nocall;
-    }
-  }
+  // ---- rows
+  emit_stream_rows<WIDE>(L, n_counters, tl, my_pos, my_fv, run, n_runs, key_filter, prm, prog, reinterpret_cast<const MkpCombo*>(combo_lds),
+      rows_base, row_cursor, tile_row_off, dev_err, wave_tot, &row_base_s, &row_total_s);
 }
 
 #define STREAM_PARAMS const MkpVisit* __restrict__ visits, const uint8_t* __restrict__ cov, const MkpEvent* __restrict__ events, const MkpSTile* __restrict__ tiles, uint32_t n_tiles, \
@@ -1110,10 +907,8 @@ extern "C" __global__ void __launch_bounds__(64) mkp_dup_events(const MkpReadHdr
   const MkpReadHdr h = hdrs[c.rid];
   const uint32_t aln = (h.flags & MKP_RF_REVERSE) ? 1u : 0u, L = h.l_seq;
   const uint8_t* __restrict__ seqb = seqs + h.seq_off;
-  const uint32_t* __restrict__ cg = cigar + h.cigar_off;
-  RefWin rw; rw.c0 = 0; rw.q_run = 0; rw.r_run = h.ref_start; rw.Rtot = 0; rw.Qtot = 0; rw.re = rw.m1 = rw.m2 = rw.m3 = 0;
-    rw.pk[0] = rw.pk[1] = rw.pk[2] = rw.pk[3] = 0; rw.loaded = false;
-  rw.pref = cigar_quad(cg, h.n_cigar, 0);
+  const MkpCigarPtr cg = (MkpCigarPtr)(cigar + h.cigar_off);   // (the BAM words: `wide`)
+  CigarWin rw; cigwin_init(rw, cg, true, h.n_cigar, h.ref_start);
   MkpEvent* __restrict__ dst = events + c.eff_off;
   uint32_t n_out = 0, st_ok = 0, st_o0 = 0, st_o1 = 0; bool have_st = false, mixed = false, over = false;
   for (uint32_t s = 0; s < c.n_seg; s++) {
@@ -1134,7 +929,7 @@ extern "C" __global__ void __launch_bounds__(64) mkp_dup_events(const MkpReadHdr
         // the consumer's own alignment at the call's reference position: a base (M / = / X), and the call's base in read orientation
         uint32_t kind = 2u, q = 0u;
         const bool inside = in && (int32_t)e.pos >= h.ref_start && (int32_t)e.pos < h.ref_end;
-        refwin_map(rw, cg, h.n_cigar, h.ref_start, inside, (int32_t)e.pos, &kind, &q);
+        cigwin_map(rw, cg, true, h.n_cigar, h.ref_start, inside, (int32_t)e.pos, &kind, &q);
         keep = false;
         if (inside && kind == 0u && q < L) {
           const uint32_t byte = (uint32_t)seqb[q >> 1], nib = (q & 1u) ? (byte & 15u) : (byte >> 4);
@@ -1167,16 +962,13 @@ extern "C" __global__ void __launch_bounds__(64) mkp_dup_events(const MkpReadHdr
 // host-side launchers (called from mkp_api.cpp)
 // work = the fused decoder's reads (longest first), cover_ids = the reads of mkp_cover_reads
 extern "C" hipError_t mkp_launch_slots(hipStream_t st, const MkpWork* work, uint32_t n_fused, const void* plane, const uint16_t* cigar16,
-    const MkpReadHdr* hdrs,
-    const uint32_t* cover_ids, uint32_t n_cover, const uint32_t* cigar,
-                                       const uint8_t* seqs, const MkpTagRef* tagref, const uint32_t* ranks, const uint8_t* ml,
-                                           const MkpLayout* layouts, const MkpFusedDesc* fdesc, const MkpRunParams* prm,
-                                       const uint32_t* slot_pos, const MkpSlotEnt* slot_ent, uint8_t* cov, MkpVisit* visits, MkpEvent* events,
-                                           MkpReadOut* readout, uint32_t* dev_err) {
+    const MkpReadHdr* hdrs, const uint32_t* cover_ids, uint32_t n_cover, const uint32_t* cigar, const uint8_t* seqs, const uint8_t* ml,
+    const MkpFusedDesc* fdesc, const MkpRunParams* prm, const uint32_t* slot_pos, const MkpSlotEnt* slot_ent, uint8_t* cov, MkpVisit* visits,
+    MkpEvent* events, MkpReadOut* readout) {
   if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, cigar, cigar16, seqs, static_cast<const uint4*>(plane), ml, fdesc, *prm,
       slot_ent, cov, visits, readout);
-  if (n_cover) hipLaunchKernelGGL(mkp_cover_reads, dim3((n_cover + 3u) / 4u), dim3(256), 0, st, hdrs, n_cover, cover_ids, cigar, seqs, tagref, ranks,
-      ml, layouts, fdesc, *prm, slot_pos, cov, visits, events, readout, dev_err);
+  if (n_cover) hipLaunchKernelGGL(mkp_cover_reads, dim3((n_cover + 3u) / 4u), dim3(256), 0, st, hdrs, n_cover, cover_ids, cigar, seqs, slot_pos, cov,
+      visits, events, readout);
   return hipGetLastError();
 }
 // the base-and-call plane of the fused reads (once per resident shard; it also marks the work records whose delta list runs past its base
@@ -1214,10 +1006,9 @@ extern "C" hipError_t mkp_launch_stream(hipStream_t st, uint32_t lds_bytes, cons
     const MkpSTile* tiles, uint32_t n_tiles,
                                         const MkpRunParams* prm_dev, const uint32_t* slot_pos, const uint8_t* focus, const MkpCombo* combos,
                                             const MkpRowsDev* rows, uint32_t* row_cursor,
-                                        uint32_t* tile_row_off, uint32_t* tile_row_cnt, uint32_t* dev_err, uint32_t key_filter, uint32_t key_slot,
+                                        uint32_t* tile_row_off, uint32_t* dev_err, uint32_t key_filter, uint32_t key_slot,
                                             uint32_t n_combos, uint32_t n_runs, uint32_t slot_cap, uint32_t words_per_slot, bool wide) {
   if (!n_tiles) return hipSuccess;
-  (void)tile_row_cnt;
   const bool keyed = key_filter != MKP_NO_KEY_FILTER;
   const uint32_t key_arg = keyed ? ((key_filter & 0xffffu) | (key_slot << 16)) : 0u;
 #define MKP_STREAM_LAUNCH(K) hipLaunchKernelGGL(K, dim3(n_tiles), dim3(PILEUP_THREADS), lds_bytes, st, visits, cov, events, tiles, n_tiles, prm_dev, slot_pos, focus, combos, rows->pos, row_cursor, \

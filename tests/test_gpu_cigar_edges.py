@@ -6,7 +6,7 @@ pairs on tile, interval, region and shard seams.
 Every BAM runs with every position a slot (--include-bed of the whole contig), --motif C 0, --cpg, --cpg --combine-strands and without a
 focus (the dense tile kernel); the indexed file (device ingest) and the unindexed one (host packer), each at the default tile and with
 --tile 256 (the two large BAMs: indexed + default tile and unindexed + --tile 256 only); each through the default path (fused slot decoder for classes 0 / 1, mkp_cover_reads + event decoders for 2-4) and with MKP_FUSED=0
-(every class through the event decoders and refwin_map).  The order of the assertions says where a failure is: device rows == model
+(every class through the event decoders and mkp_cover_reads, on the BAM words' form of the slot walks' CIGAR window, cigwin_map).  The order of the assertions says where a failure is: device rows == model
 column by column, then device text == oracle text.  No row and no column is left out.
 
 The floors were computed on the CPU from the model and are constants here: rows per flag set, rows with a deletion, rows with

@@ -5,6 +5,7 @@ add_mod_codes_for_record 299-355).  Rounds 1-5 refused such shards; now the host
 mkp_dup_events rebuilds the later records' event lists (mkp_slots.hip).  The checker is the oracle, whose cache is keyed by name like the
 reference's.  Still refused, loudly: a record whose owners in different intervals disagree in status or observed codes."""
 import os
+import random
 import subprocess
 
 import pytest
@@ -17,12 +18,14 @@ from bamfuzz import Fuzz, aux_bc, aux_z, bam_header, bam_record, bgzf_write
 pytestmark = pytest.mark.gpu
 
 
-def both(oracle_bin, tmp_path, bam, flags, extra_dev=()):
+def both(oracle_bin, tmp_path, bam, flags, extra_dev=(), oracle_must=None):
     dev, ora = str(tmp_path / "dev.bed"), str(tmp_path / "ora.bed")
     modkit_amd.pileup([bam, dev] + flags + list(extra_dev))
     p = subprocess.run([oracle_bin, "pileup", bam, ora] + flags, capture_output=True, text=True)
     assert p.returncode == 0, p.stderr[-400:]
     a, b = open(dev).read(), open(ora).read()
+    if oracle_must is not None:   # a condition on the INPUT, checked on the oracle's text before the two are compared
+        oracle_must(b)
     if a != b:
         al, bl = a.splitlines(), b.splitlines()
         for i in range(max(len(al), len(bl))):
@@ -79,6 +82,57 @@ def test_two_records_one_name_follow_the_first(oracle_bin, tmp_path):
     bam2 = str(tmp_path / "dup2.bam")
     bgzf_write(bam2, bytes(bam_header([("ctg", 1000)])) + b"".join(recs2))
     assert both(oracle_bin, tmp_path, bam2, ["--no-filtering", "-i", "35"]) != both(oracle_bin, tmp_path, bam2, ["--no-filtering"])
+
+
+def long_cigar_consumer(tmp_path):
+    """Two primary records of one name: the owner (plain M, a `C+m?` call on every CpG) and, five bases on, a consumer of 301 ops — M runs
+    of 2-4 bases between 1D / 1I, op 260 an M of 150 — whose bases follow the reference where it matches.  Returns (bam, fasta, the
+    reference position where the consumer's op 256 starts)."""
+    rnd = random.Random(11)
+    ref = "".join("CG" if rnd.random() < 0.2 else rnd.choice("ACGT") for _ in range(1100))[:1200]
+    o_start, o_len, c_start = 10, 1000, 15
+    o_seq = ref[o_start:o_start + o_len]
+    deltas, skipped = [], 0
+    for i, base in enumerate(o_seq):   # the MM delta list counts the read's C between two calls
+        if base != "C":
+            continue
+        if o_seq[i + 1:i + 2] == "G":
+            deltas.append(skipped); skipped = 0
+        else:
+            skipped += 1
+    o_aux = aux_z("MM", "C+m?,%s;" % ",".join(map(str, deltas))) + aux_bc("ML", [230] * len(deltas))
+    ops = [((150 if k == 260 else 2 + k % 3), "M") if k % 2 == 0 else (1, "DI"[(k // 2) % 2]) for k in range(301)]
+    c_seq, pos, p256 = "", c_start, None
+    for k, (n, op) in enumerate(ops):
+        if k == 256:
+            p256 = pos
+        if op == "M":
+            c_seq += ref[pos:pos + n]
+        if op == "I":
+            c_seq += "T"
+        if op in "MD":
+            pos += n
+    assert pos < o_start + o_len and "C" in c_seq
+    c_aux = aux_z("MM", "C+m?,0;") + aux_bc("ML", [200])   # (never looked at: the name is answered from the owner)
+    recs = [bam_record(0, o_start, 0, "same_name", [(o_len, "M")], o_seq, o_aux), bam_record(0, c_start, 0, "same_name", ops, c_seq, c_aux)]
+    bam, fa = str(tmp_path / "long.bam"), str(tmp_path / "long.fa")
+    bgzf_write(bam, bytes(bam_header([("ctg", len(ref))])) + b"".join(recs))
+    with open(fa, "w") as f:
+        f.write(">ctg\n" + "".join(ref[i:i + 60] + "\n" for i in range(0, len(ref), 60)))
+    return bam, fa, p256
+
+
+@pytest.mark.parametrize("flags", [["--no-filtering"], ["--cpg", "--ref", "{fa}", "--filter-threshold", "0.7"]], ids=["dense", "cpg"])
+def test_consumer_with_a_cigar_past_one_window(oracle_bin, tmp_path, flags):
+    # mkp_dup_events maps the owner's calls through the consumer's CIGAR: here past the first 256-op window, and over an op of 128 bases
+    # or more (the window's two-scan form).  The fuzz reads above have a few ops each.  --cpg also runs mkp_cover_reads on both records.
+    bam, fa, p256 = long_cigar_consumer(tmp_path)
+
+    def both_records_behind_op_256(text):
+        rows = [ln.split() for ln in text.splitlines()]
+        assert any(int(r[1]) >= p256 and int(r[9]) == 2 for r in rows), "no row with N_valid == 2 at or behind position %d" % p256
+    out = both(oracle_bin, tmp_path, bam, [f.format(fa=fa) for f in flags], oracle_must=both_records_behind_op_256)
+    assert len(out.splitlines()) > 50
 
 
 def test_owners_that_disagree_are_refused(tmp_path):
