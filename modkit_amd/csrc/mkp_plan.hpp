@@ -341,7 +341,7 @@ struct ShardPlan {
   MkpRunParams prm; uint32_t hemi_codes[4][MKP_KMAX + 2] = {};
   uint32_t n_class[7] = {}, n_slot_class[3] = {}, read_ids_dec_off = 0;
   bool wide = false, stream = false, preplanned = false;
-  std::vector<std::vector<uint32_t>> dup_groups;   // records of one name (and partition key) that meet inside an interval
+  std::vector<std::vector<uint32_t>> dup_groups;   // records of one name (of any partition key) that meet inside an interval
   std::vector<uint8_t> dup_member;                 // per read: in one of dup_groups and inside the window
   std::vector<uint32_t> class_list, slot_ids;
   std::vector<MkpTile> tiles; std::vector<MkpSTile> stiles; std::vector<uint32_t> slotbm, wpfx, slot_pos;
@@ -367,14 +367,16 @@ inline void find_shared_names(const PlanInput& in, ShardPlan& pl) {
     size_t mine = 0; for (size_t i = 0; i < nn; i++) if ((S.name_hash[i] >> 60) == part) mine++;
     if (mine < 2) continue;
     size_t cap = 64; while (cap < 2 * mine) cap <<= 1;
-    std::vector<uint64_t> tab(cap, 0), key(cap, 0); std::vector<uint32_t> who(cap, 0); std::vector<uint8_t> used(cap, 0);
+    std::vector<uint64_t> tab(cap, 0); std::vector<uint32_t> who(cap, 0); std::vector<uint8_t> used(cap, 0);
+    // (by name alone, whatever the records' partition keys: the reference builds ONE read cache per interval for all keys and asks it by
+    //  name, pileup/mod.rs:745, read_cache.rs:238; the key only chooses the tally a record's features and codes go to, mod.rs:795-835.  A
+    //  group may span keys: a consumer's rebuilt list is counted in the pass of the consumer's own key)
     for (size_t i = 0; i < nn; i++) {
       const uint64_t hh = S.name_hash[i]; if ((hh >> 60) != part) continue;
-      const uint64_t kk = i < S.hdr.size() ? S.hdr[i].flags >> MKP_RF_KEY_SHIFT : 0u;   // per partition key: tallies of different keys never meet
       size_t at = (size_t)((hh * 0x9e3779b97f4a7c15ull) >> 20) & (cap - 1);
       for (;;) {
-        if (!used[at]) { used[at] = 1; tab[at] = hh; key[at] = kk; who[at] = (uint32_t)i; break; }
-        if (tab[at] == hh && key[at] == kk) { std::lock_guard<std::mutex> g(dmu); dups.push_back({who[at], (uint32_t)i}); break; }
+        if (!used[at]) { used[at] = 1; tab[at] = hh; who[at] = (uint32_t)i; break; }
+        if (tab[at] == hh) { std::lock_guard<std::mutex> g(dmu); dups.push_back({who[at], (uint32_t)i}); break; }
         at = (at + 1) & (cap - 1);
       }
     }

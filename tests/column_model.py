@@ -1,5 +1,5 @@
-"""A plain per-base model of a pileup column, for the CIGAR-edge tests (tests/cigar_edge_cases.py) and the multi-tag, duplex-tag and
-edge-filter tests (tests/multi_feature_cases.py).
+"""A plain per-base model of a pileup column, for the CIGAR-edge tests (tests/cigar_edge_cases.py), the multi-tag, duplex-tag and
+edge-filter tests (tests/multi_feature_cases.py) and the tests of records that share a read name (tests/shared_name_cases.py).
 
 Pure Python + numpy; it imports neither the oracle nor modkit_amd.  It restates the reference's column loop (src/pileup/mod.rs) in one
 obvious walk: for every CIGAR op of every record, for every reference base of the op, one feature.  No windows, no chunks of ops, no
@@ -43,10 +43,26 @@ What it restates, with the reference's lines:
     combine      --combine-strands adds the '-' rows at the motif's other position to the '+' rows, per code, inside one interval
                  (mod.rs:469-561)
 
+    read names   the read cache is keyed by read NAME and built anew for every interval (ReadCache, read_cache.rs:24-43; one per
+                 process_region call, mod.rs:745).  shared_walk() restates it for the names that repeat, with nothing worked out in
+                 advance: for every interval the columns the reference visits (every position without a focus, the focus positions of
+                 either strand with one: PileupIter, mod.rs:761-763), ascending; at each column the kept records in file order, those
+                 with a base or a deletion there (a record inside an `N` op is never asked, mod.rs:785).  The first record asked about
+                 a name is parsed, filtered by the edge filter with ITS OWN length and called (add_record, read_cache.rs:111-211): it
+                 answers for the name until the interval ends.  A later record's feature is calls[mod strand][the ASKING record's read
+                 base].get(column) of that entry (get_mod_call, read_cache.rs:214-297) through the same four arms, on the asking
+                 record's alignment strand; its observed codes are the entry's, filed by the OWNER's reference strand
+                 (read_cache.rs:181-194, 299-355).  An owner that fails to parse, or is left with nothing by the edge filter, puts the
+                 NAME into the skip set (read_cache.rs:272-277): every record of the name is NoCall of its own base or Delete, no codes
+    partition    pileup(..., keys=[...]): one key per record.  Feature vectors and observed codes are per key (mod.rs:795-835); the
+                 read cache is ONE for all keys (mod.rs:745), asked by name alone.  Rows come back per key
+
 Scope: tags of any number of primary bases on either read strand (`C+m?`, `C+h?;C+m?;A+a?`, `C+m?;G-m?`, `C+m?;C-g?`, `N+b?`, ...),
 '?' and '.' modes, a caller that is --no-filtering or one --filter-threshold (the call class comes from tests/caller_model.py; a call
-whose class depends on the map's iteration order raises), --edge-filter / --invert-edge-filter, --combine-mods, unique read names.
-Out of scope: two motifs, --ignore, sampling, partition tags and max-depth.
+whose class depends on the map's iteration order raises), --edge-filter / --invert-edge-filter, --combine-mods, records that share a
+read name (names that repeat take shared_walk(), unique ones the vectorised walk()), partition keys as far as one key per record with
+the cache shared over the keys.
+Out of scope: two motifs, --ignore, sampling, how a partition key is read from a record's tags, and max-depth.
 """
 import bisect
 import re
@@ -388,46 +404,211 @@ def rows_of(t, pairs, combine_mods=False):
     return out
 
 
+def shared_entry(rec, threshold, edge_filter):
+    """add_record (read_cache.rs:111-211) for the record that is asked about first: None when the name joins the skip set (tags that do
+    not parse, a read too short to trim, nothing left by the edge filter), else (calls, codes) with calls = {mod strand: {base of the
+    owner's read: {reference position: (primary base, class)}}} over the owner's aligned pairs (util.rs:122-145) and codes = [(reference
+    strand 0 | 1, primary base, code)], the strand being the OWNER's alignment strand for a '+' tag and the other one for a '-' tag."""
+    start, flag, cigar, seq, mm, ml = rec
+    rev, L = bool(flag & 16), len(seq)
+    fwd = "".join(COMP.get(c, "N") for c in reversed(seq)) if rev else seq
+    groups = filter_groups(parse_tags(mm, list(ml), fwd) or {}, L, edge_filter)
+    if not groups:
+        return None
+    at, r, q = {}, int(start), 0          # forward-read position -> reference position
+    for n, op in cigar:
+        if op in "M=X":
+            for k in range(n):
+                at[L - 1 - (q + k) if rev else q + k] = r + k
+        if op in "M=XDN":
+            r += n
+        if op in "MIS=X":
+            q += n
+    calls, codes = {"+": {}, "-": {}}, []
+    for (strand, base), group in sorted(groups.items()):
+        on = base if strand == "+" else COMP[base]
+        dest = calls[strand].setdefault(base, {})
+        for p, c in call_classes(group, threshold, on).items():
+            if p in at:
+                dest[at[p]] = (on, c)
+        for c in sorted({c for probs in group.values() for c in probs}, key=code_key):
+            codes.append((int(rev) ^ (strand == "-"), on, c))
+    return calls, codes
+
+
+def shared_walk(members, start, end, visited, threshold, edge_filter, report):
+    """One interval [start, end) of the column loop for the records whose names repeat.  members: [(record index, name, key, record)] in
+    file order, kept records only; visited(pos): whether the reference visits the column.  -> {key: {(pos, strand 0 | 1): {kind: n}}}
+    with kinds "D", "F", ("N", base), ("C", base), ("M", (base, code)), ("O", (base, code)).  Nothing is planned: the cache and the skip
+    set are filled as the loop asks.  report: a dict that collects, under "asked", per record index [(interval start, owner's index,
+    owner is good, frozenset of the owner's codes)], and under "touched" / "kept" / "dropped" the cells a record answered from another
+    one counts in, the calls such a record found and the owner's calls at its bases that its own base did not match."""
+    spans = []
+    for i, name, key, (rs, flag, cigar, seq, mm, ml) in members:
+        state, q = [], 0                    # per reference position of the record: index into SEQ, -1 deletion, -2 ref-skip
+        for n, op in cigar:
+            if op in "M=X":
+                state += range(q, q + n)
+            elif op in "DN":
+                state += [-1 if op == "D" else -2] * n
+            if op in "MIS=X":
+                q += n
+        assert q == len(seq), "CIGAR and SEQ lengths differ"
+        spans.append((i, name, key, int(rs), bool(flag & 16), seq, state))
+    record_of = {i: rec for i, _, _, rec in members}
+    out, cache, skip, owner = {}, {}, set(), {}
+    lo = max(start, min(s[3] for s in spans))
+    hi = min(end, max(s[3] + len(s[6]) for s in spans))
+    for pos in range(lo, hi):
+        if not visited(pos):
+            continue
+        for i, name, key, rs, rev, seq, state in spans:          # file order
+            if not rs <= pos < rs + len(state) or state[pos - rs] == -2:
+                continue
+            if name not in cache and name not in skip:            # the first record asked owns the name in this interval
+                entry = shared_entry(record_of[i], threshold, edge_filter)
+                owner[name] = i
+                if entry is None:
+                    skip.add(name)
+                else:
+                    cache[name] = entry
+            entry = cache.get(name)
+            foreign = owner[name] != i
+            seen = report["asked"].setdefault(i, [])
+            if not seen or seen[-1][0] != start:
+                seen.append((start, owner[name], entry is not None, frozenset(entry[1]) if entry else frozenset()))
+            cells = out.setdefault(key, {})
+
+            def add(strand, kind, counts=True):
+                cell = cells.setdefault((pos, strand), {})
+                cell[kind] = cell.get(kind, 0) + 1
+                if foreign and counts:
+                    report["touched"].add((key, pos, strand))
+            if entry:
+                for strand, on, c in entry[1]:                    # add_mod_codes_for_record: the owner's maps as they are
+                    add(strand, ("O", (on, c)), counts=False)
+            aln = int(rev)
+            if state[pos - rs] == -1:
+                add(aln, "D")
+                continue
+            base = seq[state[pos - rs]]
+            base = COMP.get(base) if rev else base
+            found = []
+            for strand in "+-" if entry else "":
+                for b, at in entry[0][strand].items():
+                    if pos in at:
+                        if b == base:
+                            found.append((strand, at[pos]))
+                        elif foreign:
+                            report["dropped"] += 1
+            if base not in COMP:                                  # no read base: no feature (mod.rs:864-874)
+                continue
+            if foreign:
+                report["kept"] += len(found)
+            for strand, (on, c) in found:                         # a '-' call counts on the other strand's tally (mod.rs:254-259)
+                add(aln ^ (strand == "-"), "F" if c == "F" else ("C", on) if c == "-" else ("M", (on, c)))
+            if not found:
+                add(aln, ("N", base))
+    return out
+
+
+def kind_index(kind, pairs):
+    """the place of one of shared_walk()'s kinds in a tally of walk()'s layout"""
+    if kind in ("D", "F"):
+        return K_DELETE if kind == "D" else K_FAIL
+    if kind[0] in "NC":
+        return (K_NOCALL if kind[0] == "N" else K_CANONICAL) + "ACGT".index(kind[1])
+    return (K_MOD if kind[0] == "M" else K_OBSERVED) + pairs.index(kind[1])
+
+
+def new_report():
+    return {"asked": {}, "touched": set(), "kept": 0, "dropped": 0}
+
+
+def mixed_records(report):
+    """The records that are answered from another record in some interval and whose (owner is good, owner's codes) pairs over the intervals
+    they are asked in number more than one: what the device refuses (one set of codes and one status per record)."""
+    return sorted(i for i, seen in report["asked"].items()
+                  if any(o != i for _, o, _, _ in seen) and len({(ok, codes) for _, _, ok, codes in seen}) > 1)
+
+
 def pileup(records, ref, threshold=None, motif=None, bed=None, combine_strands=False, region=None, interval=100000, walked=None,
-           edge_filter=None, combine_mods=False):
-    """The bedMethyl rows of one contig: {(pos, strand, code): counts tuple in COUNTS order}.
+           edge_filter=None, combine_mods=False, names=None, keys=None, report=None, walk_cache=None):
+    """The bedMethyl rows of one contig: {(pos, strand, code): counts tuple in COUNTS order}; with `keys`, {key: such rows}.
     records: [(start, flag, cigar, seq, MM text, ML bytes)]; ref: the contig's text (upper case); threshold: None for --no-filtering,
     else the one --filter-threshold; motif: (text, offset) (--cpg is ("CG", 0)); bed: [(start, end, '+' | '-' | '.')] of --include-bed;
-    region: (start, end) of --region; interval: -i; walked: walk(records, threshold, edge_filter) when the caller already holds it;
-    edge_filter: an EdgeFilter (--edge-filter, --invert-edge-filter); combine_mods: --combine-mods."""
+    region: (start, end) of --region; interval: -i; walked: walk(records, threshold, edge_filter) when the caller already holds it
+    (without names and keys); walk_cache: with names or keys, a dict that keeps the walks of the records with unique names per key;
+    edge_filter: an EdgeFilter (--edge-filter, --invert-edge-filter); combine_mods: --combine-mods; names: one read name per record
+    (None: every name is unique); keys: one partition key per record; report: new_report(), filled by shared_walk()."""
     assert not (combine_strands and motif is None)
-    cols, pairs = walked or walk(records, threshold, edge_filter)
-    codes = sorted({b for b, _ in pairs} if combine_mods else {c for _, c in pairs}, key=code_key)
-    by_pos = {}
-    for (pos, strand), t in cols.items():
-        by_pos.setdefault(pos, {})[strand] = t
-    ordered = sorted(by_pos)
-    rows = {}
+    plain = names is None and keys is None
+    names = list(names) if names is not None else list(range(len(records)))
+    key_of = list(keys) if keys is not None else [None] * len(records)
+    kept = [i for i, rec in enumerate(records) if not (rec[1] & DROP_FLAGS) and rec[3]]
+    count = {}
+    for i in kept:
+        count[names[i]] = count.get(names[i], 0) + 1
+    members = [(i, names[i], key_of[i], records[i]) for i in kept if count[names[i]] > 1]
+    shared = {i for i, _, _, _ in members}
+    report = new_report() if report is None else report
+    assert walked is None or plain
+    by_key, cache = {}, {} if walk_cache is None else walk_cache
+    for key in sorted(set(key_of) if keys is not None else {None}, key=lambda k: (k is None, k)):
+        if plain:
+            cols, pairs = walked or walk(records, threshold, edge_filter)
+        else:
+            if key not in cache:
+                cache[key] = walk([rec for i, rec in enumerate(records) if key_of[i] == key and i not in shared], threshold, edge_filter)
+            cols, pairs = cache[key]
+        by_pos = {}
+        for (pos, strand), t in cols.items():
+            by_pos.setdefault(pos, {})[strand] = t
+        by_key[key] = (by_pos, sorted(by_pos), list(pairs), {})
     regions = [region]
     if bed is not None:   # --include-bed replaces the records to work on, a --region's ends included, by the BED's own spans
         regions = bed_regions(bed, interval)      # (optimize_reference_records, position_filter.rs:103-210)
     for start, end, focus in (u for reg in regions for u in intervals(ref, reg, interval, motif, combine_strands)):
-        here = {}
-        for pos in ordered[bisect.bisect_left(ordered, start):bisect.bisect_left(ordered, end)]:
-            allowed = {"+", "-"} if focus is None else focus.get(pos, set())
+        def allowed(pos):
+            ok = {"+", "-"} if focus is None else focus.get(pos, set())
             if bed is not None:
-                inside = {s for a, b, st in bed if a <= pos < b for s in ("+-" if st == "." else st)}
-                allowed = allowed & inside
-            for strand in sorted(allowed):
-                if strand in by_pos[pos]:
-                    for code, counts in rows_of(by_pos[pos][strand], pairs, combine_mods).items():
-                        here[(pos, strand, code)] = counts
-        if not combine_strands:
-            rows.update(here)
-            continue
-        text, offset = motif
-        for p in sorted(q for q, s in focus.items() if "+" in s):
-            other = p + len(text) - 1 - 2 * offset
-            for code in codes:
-                parts = [here[k] for k in ((p, "+", code), (other, "-", code)) if k in here]
-                if parts:
-                    rows[(p, ".", code)] = tuple(sum(x) for x in zip(*parts))
-    return rows
+                ok = ok & {s for a, b, st in bed if a <= pos < b for s in ("+-" if st == "." else st)}
+            return ok
+        extra = shared_walk(members, start, end, allowed, threshold, edge_filter, report) if members else {}
+        for key, (by_pos, ordered, pairs, rows) in by_key.items():
+            cells = {}                            # the records answered through the name cache, added to the others' tallies
+            for (pos, strand), kinds in extra.get(key, {}).items():
+                for kind in kinds:
+                    if kind[0] in "MO" and kind[1] not in pairs:
+                        pairs.append(kind[1])
+                assert K_MOD + len(pairs) <= K_OBSERVED, "too many (base, code) pairs for the key layout"
+                t = np.zeros(N_KINDS, dtype=np.int64)
+                for kind, n in kinds.items():
+                    t[kind_index(kind, pairs)] += n
+                cells.setdefault(pos, {})["+-"[strand]] = t
+            here, inside = {}, ordered[bisect.bisect_left(ordered, start):bisect.bisect_left(ordered, end)]
+            for pos in sorted(set(inside) | set(cells)) if cells else inside:
+                for strand in sorted(allowed(pos)):
+                    parts = [d[pos][strand] for d in (by_pos, cells) if strand in d.get(pos, ())]
+                    if parts:
+                        for code, counts in rows_of(parts[0] if len(parts) == 1 else parts[0] + parts[1], pairs, combine_mods).items():
+                            here[(pos, strand, code)] = counts
+            if not combine_strands:
+                rows.update(here)
+                continue
+            text, offset = motif
+            codes = sorted({b for b, _ in pairs} if combine_mods else {c for _, c in pairs}, key=code_key)
+            for p in sorted(q for q, s in focus.items() if "+" in s):
+                other = p + len(text) - 1 - 2 * offset
+                for code in codes:
+                    parts = [here[k] for k in ((p, "+", code), (other, "-", code)) if k in here]
+                    if parts:
+                        rows[(p, ".", code)] = tuple(sum(x) for x in zip(*parts))
+    far = len(motif[0]) - 1 - 2 * motif[1] if motif else 0       # a combined row holds (pos, '+') and (pos + far, '-')
+    report["rows_touched"] = sum(1 for key, (_, _, _, rows) in by_key.items() for (pos, strand, code) in rows
+                                 if (strand != "-" and (key, pos, 0) in report["touched"])
+                                 or (strand != "+" and (key, pos + (far if strand == "." else 0), 1) in report["touched"]))
+    return {key: rows for key, (_, _, _, rows) in by_key.items()} if keys is not None else by_key[None][3]
 
 
 def row_order(rows):

@@ -1,6 +1,7 @@
 """Pins tests/column_model.py on the CPU: against the reference's own golden bedMethyl files (the fixture BAMs read with a minimal BAM
-reader, gzip + struct), and against the oracle on every directed BAM of tests/cigar_edge_cases.py and tests/multi_feature_cases.py under
-every flag set the GPU tests (tests/test_gpu_cigar_edges.py, tests/test_gpu_multi_feature.py) run.  Every count column and the row set
+reader, gzip + struct), and against the oracle on every directed BAM of tests/cigar_edge_cases.py, tests/multi_feature_cases.py and
+tests/shared_name_cases.py under every flag set the GPU tests (tests/test_gpu_cigar_edges.py, tests/test_gpu_multi_feature.py,
+tests/test_gpu_shared_names.py) run.  Every count column and the row set
 must be equal; no row is left out.
 
 Goldens outside the model's scope, left out by name:
@@ -17,6 +18,7 @@ import pytest
 import cigar_edge_cases as cases
 import column_model as cm
 import multi_feature_cases as mf
+import shared_name_cases as sn
 from pileup_cases import GOLDEN_CASES, REF, fixture
 
 GOLDENS_IN_SCOPE = ["test_pileup_no_filt:23", "test_pileup_with_header:900", "test_pileup_with_region:194", "test_pileup_cpg_motif_filtering:237"] + \
@@ -247,3 +249,84 @@ def test_model_equals_oracle_on_multi_feature_bams(oracle_bin, built_mf, tmp_pat
     if name == "edge_filter":
         assert all(n[3] > 0 for n in numbers)
     assert all(n[1] > 0 for n in numbers) and any(n[2] > 0 for n in numbers)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# records that share a read name: the model's name-keyed cache vs the oracle's on tests/shared_name_cases.py
+
+@pytest.fixture(scope="module")
+def built_sn(tmp_path_factory):
+    cache = {}
+
+    def get(name):
+        if name not in cache:
+            cache[name] = sn.BUILDERS[name](str(tmp_path_factory.mktemp(name) / name))
+        return cache[name]
+    return get
+
+
+def check_against_oracle(oracle_bin, case, flags, want, out):
+    for bam in (case.bam, case.bam_unindexed):
+        got = oracle_rows(oracle_bin, bam, out, cases.oracle_flags(flags))
+        try:
+            assert_same(got, {case.contig: want} if want else {}, "oracle", {case.contig: case.records})
+        except AssertionError as e:
+            raise AssertionError("%s under %s: %s" % (case.name, " ".join(flags), e))
+
+
+@pytest.mark.parametrize("name", sorted(sn.BUILDERS))
+def test_model_equals_oracle_on_shared_name_bams(oracle_bin, built_sn, tmp_path, name):
+    """Every flag set of the GPU test, both files, every row and count column (`partition` excepted: the oracle has no partition tags);
+    the floors of shared_name_cases.FLOORS are the model's own numbers; no record of these BAMs meets owners that disagree."""
+    case = built_sn(name)
+    walked, numbers = {}, []
+    for fi, flags in enumerate(sn.flag_sets(case)):
+        want, stats, mixed = sn.model_rows(case, flags, walked)
+        assert not mixed, (flags, [case.read_names[i] for i in mixed])
+        numbers.append(stats)
+        if name != "partition":
+            check_against_oracle(oracle_bin, case, flags, want, str(tmp_path / ("o%d.bed" % fi)))
+    assert numbers == sn.FLOORS[name], numbers
+    assert all(n[0] > 100 and n[1] > 0 for n in numbers)
+    assert all(n[2] > 0 for n in numbers) or name == "status"
+    if name in ("bases_strands", "ownership"):
+        assert all(n[3] > 0 for n in numbers)
+
+
+@pytest.mark.parametrize("shape", sorted(sn.MIXED_SHAPES))
+def test_model_reports_owners_that_disagree(oracle_bin, tmp_path, shape):
+    """The model's mixed report on the shapes of shared_name_cases.MIXED_SHAPES; the oracle, which refuses nothing, equals the model on
+    all of them."""
+    case = sn.mixed(shape, str(tmp_path / shape))
+    want, stats, mixed = sn.model_rows(case, case.flags, {})
+    assert bool(mixed) == sn.MIXED[shape]
+    if mixed:                       # the later record of the name, and only it
+        assert [case.read_names[i] for i in mixed] == ["x"] and mixed == [case.index("x", 1)]
+    check_against_oracle(oracle_bin, case, case.flags, want, str(tmp_path / "o.bed"))
+
+
+def test_model_owners_equal_the_planner_table():
+    """The owners tests/test_plan_host.py works out by hand for its records A, B, C (window [1000, 4000), intervals of 1000, focus
+    positions 1100 1500 | 2500 | 3200 3600, B inside an `N` op over 2500) fall out of the model's loop: A owns the first interval for all
+    three, C the other two alone; B is never asked in the second."""
+    import test_plan_host as ph
+    ref = ["A"] * 5000
+    for p in ph.OWN_FOCUS:
+        ref[p] = "C"
+    ref = "".join(ref)
+    members = [ph.A, ph.B, ph.C]
+    records = []
+    for i in members:
+        start, end, _, _, cigar = ph.OWN_READS[i]
+        ops = [(n, "MIDN"[op]) for n, op in cigar]
+        seq, at = "", start
+        for n, op in ops:
+            seq += ref[at:at + n] if op == "M" else ""
+            at += n
+        assert at == end
+        records.append((start, 0, ops, seq, "C+m?,0;", [200]))
+    report = cm.new_report()
+    cm.pileup(records, ref, motif=("C", 0), region=ph.OWN_WIN, interval=1000, names=["n"] * 3, report=report)
+    got = {(members[i], (s - ph.OWN_WIN[0]) // 1000): members[o] for i, seen in report["asked"].items() for s, o, _, _ in seen}
+    assert got == ph.owners_by_brute_force() == {(ph.A, 0): ph.A, (ph.B, 0): ph.A, (ph.C, 0): ph.A, (ph.C, 1): ph.C, (ph.C, 2): ph.C}
+    assert cm.mixed_records(report) == []      # every owner is good and tagged alike
