@@ -26,12 +26,12 @@ hipError_t mkp_launch_pileup(hipStream_t, uint32_t /*LDS bytes*/, bool /*pileup-
                                  const MkpRowsDev*, uint32_t* /*row cursor*/,
                              uint32_t* /*tile row offsets*/, uint32_t* /*tile row counts*/, const uint32_t* /*chunk offsets*/,
                                  uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, bool /*wide tallies*/);
-hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_t, const void* /*base-and-call plane*/,
+hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_t, const MkpCallEnt* /*call plane*/, const MkpBaseEnt* /*base plane*/,
     const uint16_t* /*16-bit CIGAR*/, const MkpReadHdr*, const uint32_t* /*cover read ids*/, uint32_t, const uint32_t* /*CIGAR*/,
     const uint8_t* /*SEQ*/, const uint8_t* /*ML*/, const MkpFusedDesc*, const MkpRunParams*, const uint32_t* /*slot positions*/,
     const MkpSlotEnt* /*slot-entry lists*/, uint8_t* /*feature stream*/, MkpVisit*, MkpEvent*, MkpReadOut*);
 hipError_t mkp_launch_call_plane(hipStream_t, MkpWork*, uint32_t, const uint8_t* /*SEQ*/, const uint32_t* /*ranks*/, const MkpFusedDesc*,
-    void* /*plane*/, unsigned long long* /*SEQ bytes the decoder reads of MKP_RF_SEQN reads*/);
+    MkpCallEnt* /*call plane*/, MkpBaseEnt* /*base plane*/, unsigned long long* /*SEQ bytes the decoder reads of MKP_RF_SEQN reads*/);
 hipError_t mkp_stream_set_lds(uint32_t bytes);
 hipError_t mkp_launch_dup_restore(hipStream_t, MkpReadHdr*, const MkpDupCons*, uint32_t);
 hipError_t mkp_launch_dup_events(hipStream_t, MkpReadHdr*, const uint32_t*, const uint8_t*, MkpEvent*, MkpReadOut*, MkpDupCons*, const MkpDupSeg*,
@@ -80,7 +80,11 @@ namespace {
 hipError_t launch_inflate(hipStream_t st, const uint8_t* in, const void* blks, uint32_t n, uint8_t* out, uint32_t* status) {
   return mkp_launch_inflate_auto(st, in, blks, n, out, status); }
 
-// the plan's arrays into HBM, the buffers the kernels write, the fused reads' call plane (built once per resident shard — a re-launch on the
+// d_plane holds the fused reads' call plane, the base plane behind it (as many 8-byte entries each: plane_bytes / 16) and the builder's counter
+static MkpCallEnt* call_plane(mkp_ctx* c) { return c->d_plane.as<MkpCallEnt>(); }
+static MkpBaseEnt* base_plane(mkp_ctx* c) { return reinterpret_cast<MkpBaseEnt*>(c->d_plane.as<char>() + c->plane_bytes / 2); }
+
+// the plan's arrays into HBM, the buffers the kernels write, the fused reads' call and base planes (built once per resident shard — a re-launch on the
 // shard reuses it — and counted in the upload step), the LDS sizes and the key passes
 void upload_plan(mkp_ctx* c, const ShardPlan& pl, PlanTrace& trace) {
   const ShardHost& S = c->shard;
@@ -114,7 +118,7 @@ void upload_plan(mkp_ctx* c, const ShardPlan& pl, PlanTrace& trace) {
     { std::vector<MkpFusedDesc> fd(c->tables.dev.size()); for (size_t i = 0; i < fd.size(); i++) fd[i] = fused_desc(c->tables.dev[i]);
       upload(c->d_fdesc, fd); }
     hip_check(mkp_launch_call_plane(c->stream, c->d_work.as<MkpWork>(), nf, c->d_seq.as<uint8_t>(), c->d_ranks.as<uint32_t>(),
-        c->d_fdesc.as<MkpFusedDesc>(), c->d_plane.p, d_seqn_bytes), "call plane launch");
+        c->d_fdesc.as<MkpFusedDesc>(), call_plane(c), base_plane(c), d_seqn_bytes), "call plane launch");
     c->d_cov.ensure(c->cov_bytes + 256); c->d_visits.ensure(std::max<size_t>(S.hdr.size(), 1) * sizeof(MkpVisit));
     // A fused read writes the bytes of the slots it decodes — the same ones on every pass — and the buffer is reused from shard to shard:
     // the whole stream starts as BLANK ("in the column, no feature": the stream kernel skips it and it opens no ref-skip boundary), so that
@@ -153,8 +157,10 @@ void account_bytes(mkp_ctx* c, const ShardPlan& pl) {
   c->stats.stream_bytes = n_rs;
   c->stats.alg_bytes_decode += 4ull * n_rs + n_rs + 32ull * S.hdr.size();
   // the fused decoder reads neither a read's whole SEQ nor its rank list, and 2 bytes per CIGAR op (4 of a read with an op longer than
-  // 4 095 bases): the 16-byte plane entry under each slot, and the SEQ byte only for a read with a base that is not A/C/G/T (the plane,
-  // resolved from SEQ and ranks once per resident shard, is not part of the pass); the plane builder counted those SEQ bytes behind the plane
+  // 4 095 bases): the 8-byte entry of its plane under each slot (the call plane of a read with calls, the base plane of every other), 4
+  // bytes of the base plane per slot without a listed call of a read with calls (a bound: plane_lookup_bytes, mkp_plan.hpp), and the SEQ
+  // byte only for a read with a base that is not A/C/G/T (the planes, resolved from SEQ and ranks once per resident shard, are not part of
+  // the pass); the plane builder counted those SEQ bytes behind the planes
   unsigned long long seqn_bytes = 0;
   hip_check(hipMemcpyAsync(&seqn_bytes, c->d_plane.as<char>() + c->plane_bytes, sizeof(seqn_bytes), hipMemcpyDeviceToHost, c->stream),
       "plane counter readback");
@@ -266,7 +272,7 @@ void run_kernels(mkp_ctx* c, bool time_kernels) {
         c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>(),
                                                        c->d_dupcons.as<MkpDupCons>(), c->d_dupsegs.as<MkpDupSeg>(), c->n_dup_cons, misc + 2),
                                                            "dup events launch");
-    if (c->slot_mode) hip_check(mkp_launch_slots(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], c->d_plane.p,
+    if (c->slot_mode) hip_check(mkp_launch_slots(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], call_plane(c), base_plane(c),
         c->d_cigar16.as<uint16_t>(), c->d_hdr.as<MkpReadHdr>(),
         c->d_slot_ids.as<uint32_t>(), c->n_slot_class[2],
                                               c->d_cigar.as<uint32_t>(), c->d_seq.as<uint8_t>(), c->d_ml.as<uint8_t>(),

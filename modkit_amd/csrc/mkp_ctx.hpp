@@ -152,7 +152,7 @@ struct mkp_ctx {
   uint32_t n_dup_cons = 0; mkp::DevBuf d_dupcons, d_dupsegs;   // records answered from another record of their name (MkpDupCons / MkpDupSeg)
   mkp::DevBuf d_slot_pos, d_cov, d_visits, d_stiles, d_slot_ids, d_fdesc, d_work;
   mkp::DevBuf d_slot_ent;   // the slot-entry lists (SlotLists, mkp_pack.hpp): what the fused decoder reads instead of d_slot_pos
-  mkp::DevBuf d_plane; uint64_t plane_bytes = 0;   // the fused reads' base-and-call plane (mkp_call_plane, built when the shard becomes resident)
+  mkp::DevBuf d_plane; uint64_t plane_bytes = 0;   // the fused reads' call plane and, behind it, their base plane: plane_bytes together (mkp_call_plane, built when the shard becomes resident)
   // threshold sample, resident in HBM: keys = base << 30 | f32 bit pattern of an argmax probability; level-0 histogram per base
   mkp::ShardHost sample_shard; std::vector<MkpReadOut> sample_ro; uint64_t sample_n = 0;
   mkp::DevBuf d_store, d_hist0, d_hist1, d_sample_cursor, d_take, d_hist64;

@@ -20,7 +20,8 @@
 //   uint32      slotbm[]            focus runs only: one bit per reference position of the window (+64 positions of margin each
 //                                   side), set where the position is in focus — the positions that get a tally column ("slot")
 //   MkpRowsDev  rows                SoA row buffers (per tile, then gathered into genome order)
-//   uint2       plane[]             slot pipeline: the call plane of the fused reads (MKP_PLANE_WORDS below), built once per resident shard
+//   uint2       plane[]             slot pipeline: the call plane and, behind it, the base plane of the fused reads (MkpCallEnt, MkpBaseEnt,
+//                                   MKP_PLANE_WORDS below), built once per resident shard
 #pragma once
 #include <stdint.h>
 
@@ -201,16 +202,21 @@ struct MkpTile { int32_t r0, r1; uint32_t first, last; };
 // stream into LDS tallies.  Feature byte = what FeatureVector::add_feature receives for this alignment at this column
 // (pileup/mod.rs:783-939): [0:4] counter id (MKP_C_*), [5] tally strand, [6:7] the read base as tallied (so that a call of a
 // record that later fails can be counted as NoCall(base)).
-// mkp_decode_slots takes the base under a slot, and whether a call is listed there, from the BASE-AND-CALL PLANE (mkp_call_plane, built
-// once when the shard becomes resident): per fused read and 32 stored bases one 16-byte MkpPlaneEnt, stored order, four bits per base; the
-// read's plane starts at plane[MkpWork.pad].  A read whose SEQ holds a base that is not A/C/G/T (MKP_RF_SEQN) has code 0 there: the
-// decoder reads such a read's bases from the SEQ instead.
+// mkp_decode_slots takes whether a call is listed under a slot, and the base where none is, from TWO PLANES (mkp_call_plane, built once
+// when the shard becomes resident), each with one 8-byte entry per fused read and 32 stored bases, stored order: the CALL PLANE (one bit
+// per base, and the calls before the entry) and, behind the whole of it in the same buffer, the BASE PLANE (two bits per base).  A read's
+// entries start at index MkpWork.pad of either plane.  A slot with a listed call never needs its base (the call's feature replaces the
+// coverage feature), so a read with calls gathers its call entries and asks the base plane for one dword only under a match slot without a
+// listed call; every other read gathers its base entries and never touches the call plane.  A read whose SEQ holds a base that is not
+// A/C/G/T (MKP_RF_SEQN) has code 0 there: the decoder reads such a read's bases from the SEQ instead.
 #define MKP_PLANE_WORDS(l_seq) (((l_seq) + 31u) >> 5)
-struct MkpPlaneEnt {         // 16 B: one global_load_dwordx4 per slot
-  uint32_t base_lo, base_hi; // 2-bit codes of stored bases 32 w + b (A=0 C=1 G=2 T=3, not complemented): b < 16 at bits 2 b of base_lo,
-                             // b >= 16 at bits 2 (b - 16) of base_hi (mkp_pack_bases32, mkp_base_pack.hpp)
+struct MkpCallEnt {          // 8 B: one global_load_dwordx2 per slot of a read with calls
   uint32_t listed;           // bit b = a listed call of the read sits at base 32 w + b (0 for a read without calls or a run-over list)
   uint32_t before;           // listed calls at the bases before 32 w
+};
+struct MkpBaseEnt {          // 8 B: one global_load_dwordx2 per slot of a read without calls; a read with calls loads the half that holds its base
+  uint32_t base_lo, base_hi; // 2-bit codes of stored bases 32 w + b (A=0 C=1 G=2 T=3, not complemented): b < 16 at bits 2 b of base_lo,
+                             // b >= 16 at bits 2 (b - 16) of base_hi (mkp_pack_bases32, mkp_base_pack.hpp)
 };
 #define MKP_STREAM_ROWMAP_WORDS 2048u   // mkp_pileup_stream: rows of a tile placed per emission round (a dword of LDS each)
 // one entry of the slot-entry lists (`all`, `plus`, `minus`, concatenated: window_slots, mkp_plan.hpp): the decoder's 8-byte load per slot
@@ -252,7 +258,7 @@ struct MkpWork {             // 72 B
   int32_t ref_start; uint32_t l_seq, n_cigar, cigar_off, seq_off, flags, gs0, n_sl, cov_off;
   uint16_t n_tags, layout;
   uint32_t rank_off, n_calls, ml_off0, ml_off1;   // the shared rank list, the tags' ML bytes
-  uint32_t rid, pad;                              // pad: the read's first plane entry (MKP_PLANE_WORDS(l_seq) of them)
+  uint32_t rid, pad;                              // pad: the read's first entry in either plane (MKP_PLANE_WORDS(l_seq) of them)
   // the slots the decoder visits: slot_ent[ent_off .. ent_off + n_ent), the read's run of the slot-entry list of its own strand — or of
   // the list of every slot (n_ent == n_sl) when it needs both tally strands or its strand's list is no shorter (plan_read_entries, mkp_plan.hpp)
   uint32_t ent_off, n_ent;
@@ -303,5 +309,5 @@ struct MkpStatsRegion { uint32_t start, end; uint32_t rule /* 1 '+', 2 '-', 3 bo
 struct MkpLocRegion { uint32_t ws, we, anchor; uint32_t rules /* fetch rule | region rule << 8, each 1 '+', 2 '-', 3 both */; };
 #ifdef __cplusplus
 static_assert(sizeof(MkpWork) == 72 && sizeof(MkpSlotEnt) == 8, "work record is 18 dwords");
-static_assert(sizeof(MkpFusedDesc) == 64 && sizeof(MkpVisit) == 32 && sizeof(MkpPlaneEnt) == 16, "slot pipeline records");
+static_assert(sizeof(MkpFusedDesc) == 64 && sizeof(MkpVisit) == 32 && sizeof(MkpCallEnt) == 8 && sizeof(MkpBaseEnt) == 8, "slot pipeline records");
 #endif

@@ -933,7 +933,7 @@ class AheadIngest {
 
   // packed arrays of a shard ~ 1.9 x its compressed blocks on ONT-like data (SEQ nibbles + CIGAR words + 5 bytes per call; names and
   // qualities are not kept), the inflated window of the ingest object in flight on top: 2.5 x; once the shard is resident, the slot
-  // decoder's base-and-call plane (four bits per stored base = as many bytes as the SEQ nibbles, ~1 x): 3.5 x; and the 16-bit CIGAR next
+  // decoder's call and base planes (together four bits per stored base = as many bytes as the SEQ nibbles, ~1 x): 3.5 x; and the 16-bit CIGAR next
   // to the 32-bit one (half the CIGAR words' bytes, ~0.25 x): 3.75 x as the estimate
   static uint64_t est_of(uint64_t comp_bytes) { return comp_bytes * 15 / 4 + (64ull << 20); }
 

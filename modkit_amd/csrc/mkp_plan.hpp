@@ -818,9 +818,21 @@ inline void split_fused_and_cover(const PlanInput& in, ShardPlan& pl) {
   pl.slot_ids.insert(pl.slot_ids.end(), rest.begin(), rest.end());
 }
 
-// ---- stage 11: the fused decoder's work records, in launch order, with their places in the base-and-call plane
-// (MKP_PLANE_WORDS(l_seq) 16-byte entries per fused read); what the SEQ sweep and rank marking would read of these reads and what the
-// plane lookups read instead (the decoder's algorithmic bytes)
+// ---- stage 11: the fused decoder's work records, in launch order, with their places in the call plane and the base plane
+// (MKP_PLANE_WORDS(l_seq) 8-byte entries per fused read in either); what the SEQ sweep and rank marking would read of these reads and what
+// the plane lookups read instead (the decoder's algorithmic bytes)
+
+// What one pass reads of the planes for one fused read that decodes n_ent slots.  The gather is one 8-byte entry per slot, of the call
+// plane for a read with calls and of the base plane for every other: at most one per entry of the read.  A read with calls also asks the
+// base plane for 4 bytes under every match slot without a listed call.  The host does not know which slots those are; it knows that at
+// most n_calls of the n_ent slots carry a listed call, so n_ent - n_calls (0 when there are more calls than slots) is the fewest base
+// requests a read of matches makes.  This is a BOUND in the sense of the other algorithmic bytes — what the pass cannot do without, not
+// what the hardware moves: a slot under a deletion or a ref-skip asks for nothing, and calls away from focus positions leave more slots
+// unlisted than it counts.
+inline uint64_t plane_lookup_bytes(uint32_t l_seq, uint32_t n_ent, bool with_calls, uint32_t n_calls) {
+  const uint64_t gather = 8ull * std::min<uint64_t>(MKP_PLANE_WORDS(l_seq), n_ent);
+  return gather + (with_calls && n_ent > n_calls ? 4ull * (n_ent - n_calls) : 0ull);
+}
 inline void build_work_records(const PlanInput& in, ShardPlan& pl) {
   const ShardHost& S = in.S;
   if (!pl.stream) return;
@@ -842,7 +854,8 @@ inline void build_work_records(const PlanInput& in, ShardPlan& pl) {
       }
       uint64_t n_rk = 0; if (!(h.flags & MKP_RF_BAD)) for (uint32_t t = 0; t < h.n_tags; t++) n_rk += S.tagref[h.tag_off + t].n;
       swept += (h.l_seq + 1) / 2 + 2ull * n_rk + ((h.flags & MKP_RF_CIGW) ? 0ull : 2ull * h.n_cigar);   // (16-bit CIGAR: 2 of the 4 bytes per op)
-      looked_up += 16ull * std::min<uint64_t>(MKP_PLANE_WORDS(h.l_seq), w.n_ent);
+      // (a read with calls as the decoder sees it, but for a run-over delta list, which only mkp_call_plane finds)
+      looked_up += plane_lookup_bytes(h.l_seq, w.n_ent, w.n_calls != 0 && !(h.flags & MKP_RF_SUMERR), w.n_calls);
       entries += w.n_ent; slots += h.n_sl;
     }
     fused_swept += swept; fused_looked_up += looked_up; fused_entries += entries; fused_slots += slots;
@@ -854,7 +867,7 @@ inline void build_work_records(const PlanInput& in, ShardPlan& pl) {
     if (pw > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "shard exceeds 2^32 call-plane words; use smaller shards");
     pl.work[k].pad = (uint32_t)pw; pw += MKP_PLANE_WORDS(pl.work[k].l_seq);
   }
-  pl.plane_bytes = pw * sizeof(MkpPlaneEnt);
+  pl.plane_bytes = pw * (sizeof(MkpCallEnt) + sizeof(MkpBaseEnt));   // the call plane, the base plane behind it
 }
 
 }  // namespace mkp

@@ -3,15 +3,18 @@
 // the host numbers the window's slots in genome order (slot_pos[g] = position of global slot g) and gives every read the slot
 // range [gs0, gs0 + n_sl) of its reference span.  One device pass:
 //
-//   mkp_call_plane        once per resident shard: per fused read and 32 stored bases one 16-byte entry — the bases' 2-bit codes, one
-//                         bit per base "a listed call sits here" and the number of listed calls before the 32 bases (the SEQ and the
-//                         rank list resolved against each other: nothing of it depends on the pass)
+//   mkp_call_plane        once per resident shard: per fused read and 32 stored bases one 8-byte entry in each of TWO planes — the call
+//                         plane: one bit per base "a listed call sits here" and the number of listed calls before the 32 bases; the base
+//                         plane: the bases' 2-bit codes (the SEQ and the rank list resolved against each other: nothing of it depends on
+//                         the pass)
 //   mkp_decode_slots      one wave per read, reads whose MM tags form one explicit-mode ('?') group with one shared delta list
 //                         (`C+m?`, `C+hm?`, `C+h?;C+m?` as basecallers write them), no edge filter.  The walk is driven by the
 //                         read's SLOTS, not by its calls, 64 slots per step: CIGAR (256-op register window, reference -> query; read from
 //                         the 16-bit array, 8 bytes per lane and window, unless an op of the read is longer than 4 095 bases), the
-//                         base, whether a call is listed there and as which call (one 16-byte plane gather; the SEQ byte only for a
-//                         read with a base that is not A/C/G/T),
+//                         whether a call is listed there and as which call (one 8-byte gather from the call plane), the base only where
+//                         none is listed (one dword of the base plane: a listed call's feature replaces the coverage feature, so most
+//                         slots never touch the base plane; a read without calls gathers its base entries instead and never touches
+//                         the call plane; the SEQ byte only for a read with a base that is not A/C/G/T),
 //                         ML -> f32 probabilities -> MultipleThresholdModCaller::call, and ONE FEATURE BYTE per slot goes to the
 //                         read's run of the feature stream — for the slots of the read's own strand only where it feeds one tally
 //                         strand and the shard's rules tell the strands apart (the slot-entry lists, mkp_plan.hpp: under --cpg half of a
@@ -164,10 +167,10 @@ __device__ __forceinline__ uint32_t cover_feature(uint32_t kind, uint32_t nib, u
 }
 
 // ----------------------------------------------------------------------------------------------------------------------
-// mkp_call_plane: the base-and-call plane of the fused reads (MkpPlaneEnt, mkp_device.h), built once when the shard becomes resident —
-// what it answers (the base at this stored index; is a listed call there, and which one) depends on the SEQ, the rank list, the strand and
-// the tag's fundamental base only, never on the pass.  One wave per work record; every fused read gets its bases, the call fields are zero
-// for a read without calls:
+// mkp_call_plane: the call plane and the base plane of the fused reads (MkpCallEnt, MkpBaseEnt, mkp_device.h), built once when the shard
+// becomes resident — what they answer (is a listed call at this stored index, and which one; the base there) depends on the SEQ, the rank
+// list, the strand and the tag's fundamental base only, never on the pass.  One wave per work record; every fused read gets its bases, the
+// call entries are zero for a read without calls (two 8-byte stores per 32 bases, one into either plane):
 //   one walk over the read's words in the order the tag counts its base (a reverse read from its last word, its flag bitmaps bit-reversed),
 //   64 plane entries (2 048 bases) per step: the entries' 2-bit base codes (mkp_pack_bases32; a base that is not A/C/G/T sets MKP_RF_SEQN)
 //   and, for a read with calls, the words' flag bitmaps (mkp_bases_eq) and their occurrence counts (a wave scan), then the rank list's
@@ -178,7 +181,8 @@ __device__ __forceinline__ uint32_t cover_feature(uint32_t kind, uint32_t nib, u
 // seqn_bytes collects what the decoder will read of the SEQN reads' SEQ (one byte per decoded slot, at most the read's bytes): algorithmic bytes.
 // Reference: DeltaListConverter::new / to_positions (mod_bam.rs:667-733).
 extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __restrict__ work, uint32_t n_reads, const uint8_t* __restrict__ seqs,
-    const uint32_t* __restrict__ ranks, const MkpFusedDesc* __restrict__ fdesc, uint4* __restrict__ plane, unsigned long long* __restrict__ seqn_bytes) {
+    const uint32_t* __restrict__ ranks, const MkpFusedDesc* __restrict__ fdesc, MkpCallEnt* __restrict__ call_plane, MkpBaseEnt* __restrict__ base_plane,
+    unsigned long long* __restrict__ seqn_bytes) {
   __shared__ uint32_t bm_all[4][64];
   const int lane = lane_id();
   const uint32_t wib = rfl(threadIdx.x >> 6);
@@ -232,8 +236,9 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
       lo[j] = l; hi[j] = hh; f[j] = fl;
     }
   };
-  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-  uint4* __restrict__ pl = plane + h.pad;
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  u32x2* __restrict__ pl_call = reinterpret_cast<u32x2*>(call_plane + h.pad);
+  u32x2* __restrict__ pl_base = reinterpret_cast<u32x2*>(base_plane + h.pad);
   uint32_t occ = 0, j = 0;   // occurrences before the step, listed calls before the step (both in walk order)
   for (uint32_t k0 = 0; k0 < nw; k0 += 256u) {
     load_chunk(k0);
@@ -288,7 +293,10 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
       }
       // (non-temporal: the entries are written once here and read by the decoder passes much later; through the cache they only
       // displace the SEQ and the rank lists the builder is still reading)
-      if (k < nw) { const u32x4 v = {lo[jj], hi[jj], lw, before}; __builtin_nontemporal_store(v, reinterpret_cast<u32x4*>(pl) + w); }
+      if (k < nw) {
+        const u32x2 vb = {lo[jj], hi[jj]}, vc = {lw, before};
+        __builtin_nontemporal_store(vc, pl_call + w); __builtin_nontemporal_store(vb, pl_base + w);
+      }
     }
   }
   // a delta list runs past the base's last occurrence (mod_bam.rs:705-727) iff the walk leaves entries unplaced: MKP_RF_RUNOVER, and the
@@ -307,9 +315,12 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
 // into_collapsed (530-627), MultipleThresholdModCaller::call (threshold_mod_caller.rs:28-63), ReadCache::add_record
 // (read_cache.rs:111-211), get_aligned_pairs_forward (util.rs:122-145), process_region's alignment loop (pileup/mod.rs:783-939).
 // One wave runs one read start to end.  The per-slot instruction count matters (about 170 M VALU per C3 pass): the SEQ and the rank list
-// were resolved into the plane when the shard became resident (mkp_call_plane), so that a slot learns its base, whether a call is listed
-// there and as which call from one 16-byte gather and a popcount; the caller is resolved to a fixed walk per read.  No per-read LDS beyond
-// the caller constants and no base windows: reads of every length take the same code.
+// were resolved into the two planes when the shard became resident (mkp_call_plane), so that a slot learns whether a call is listed there
+// and as which call from one 8-byte gather and a popcount, and its base — needed only where no call is listed — from one dword more; the
+// caller is resolved to a fixed walk per read.  No per-read LDS beyond the caller constants and no base windows: reads of every length take
+// the same code.  The kernel sits between its issue rate and its memory traffic (profiles/strand_slots_c3.txt part 5), and two thirds of
+// that traffic was the one 16-byte plane entry per slot, half of it base codes that a slot with a listed call never looks at: hence the
+// split (profiles/split_plane_c3.txt).
 // With every step waiting in full for its gather and then for its ML bytes a wave was parked on s_waitcnt for 70 % of its life (SQ counters,
 // C3, eight waves per SIMD) and the kernel ran well short of its issue rate.  The slot loop is therefore a two-deep software pipeline
 // over the 64-slot steps — A: map, request the plane gather; B: request the ML bytes; C: call, feature byte — run as B(s), A(s + 1),
@@ -318,9 +329,9 @@ extern "C" __global__ void __launch_bounds__(256) mkp_call_plane(MkpWork* __rest
 // now is fewer instructions per step, not more overlap.
 #define FUSED_PARAMS(PRM) const MkpWork* __restrict__ work, uint32_t n_reads, const uint32_t* __restrict__ cigar, const uint16_t* __restrict__ cigar16, \
     const uint8_t* __restrict__ seqs, \
-    const uint4* __restrict__ plane, const uint8_t* __restrict__ ml, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const MkpSlotEnt* __restrict__ slot_ent, \
+    const MkpCallEnt* __restrict__ call_plane, const MkpBaseEnt* __restrict__ base_plane, const uint8_t* __restrict__ ml, const MkpFusedDesc* __restrict__ fdesc, PRM prm, const MkpSlotEnt* __restrict__ slot_ent, \
     uint8_t* __restrict__ cov, MkpVisit* __restrict__ visits, MkpReadOut* __restrict__ readout
-#define FUSED_PASS work, n_reads, cigar, cigar16, seqs, plane, ml, fdesc, prm, slot_ent, cov, visits, readout
+#define FUSED_PASS work, n_reads, cigar, cigar16, seqs, call_plane, base_plane, ml, fdesc, prm, slot_ent, cov, visits, readout
 __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParams&), SlotLds* __restrict__ lds_all) {
   const int lane = lane_id();
   const uint32_t wib = rfl(threadIdx.x >> 6);
@@ -331,7 +342,6 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
   const uint32_t aln = rev ? 1u : 0u;
   const uint32_t L = h.l_seq;
-  const uint4* __restrict__ pl = plane + h.pad;
   // the read's ops: 16 bits each, or its BAM words when one of them does not fit (the work record's offset is into the array it reads)
   const bool cg_wide = (h.flags & MKP_RF_CIGW) != 0;
   MkpCigarPtr cg = cg_wide ? (MkpCigarPtr)(cigar + h.cigar_off) : (MkpCigarPtr)(cigar16 + h.cigar_off);
@@ -391,6 +401,14 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
 #else
   const bool plane_calls = have_calls;
 #endif
+  // The plane the slot gather reads: a read with calls takes its call entries ({listed, before}) and asks the base plane for a dword only
+  // under a match slot without a listed call; every other read (no tags, a tag without calls, BAD, SUMERR, RUNOVER) takes its base entries
+  // ({base_lo, base_hi}) and never touches the call plane.  One pointer, uniform over the wave, chosen here and pinned as cg is: left to
+  // itself the compiler carries both and selects at every gather.
+  typedef const __attribute__((address_space(1))) char* MkpPlanePtr;
+  MkpPlanePtr pl_base = (MkpPlanePtr)(base_plane + h.pad);
+  MkpPlanePtr pl = plane_calls ? (MkpPlanePtr)(call_plane + h.pad) : pl_base;
+  asm volatile("" : "+s"(pl), "+s"(pl_base));   // (pl_base too: unpinned, its loads take a 64-bit vector address, not `scalar base + offset`)
 
   // ---- the read's slots, 64 per step
   bool gaps = false; uint32_t n_callfeat = 0;
@@ -400,22 +418,28 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
   const uint32_t n_ent_walk = n_ent;
 #endif
   // The loop is a software pipeline, two steps deep.  A step is three stages:
-  //   A(s)  reference -> query of the step's 64 slots (cigwin_map), then the plane gather pe(s) and the slot entries of step s + 1 (one
-  //         8-byte request per lane: position and global index) are requested.
+  //   A(s)  reference -> query of the step's 64 slots (cigwin_map), then the plane gather pe(s) — 8 bytes per lane from the read's plane:
+  //         the call plane for a read with calls, the base plane for every other — and the slot entries of step s + 1 (one 8-byte request
+  //         per lane: position and global index) are requested.
   //         Both addresses are unconditional — clamped into the read's own plane / slot run — and the entry is masked where it is
   //         used: a load under a divergent branch is waited for on the spot.
-  //   B(s)  `listed` and the call ordinal from pe(s), then the ML bytes of the step's calls (and the SEQ byte of a SEQN read) are requested;
-  //         a step without a listed call requests nothing.  What C needs of the slot is packed into one register (st).
-  //   C(s)  the caller on the ML bytes, the feature byte, `gaps` / `n_callfeat`.  The byte is stored in B(s + 1), behind its requests (and
+  //   B(s)  `listed` and the call ordinal from pe(s), then the ML bytes of the step's calls, the base-plane dword of its match slots without
+  //         a listed call (and the SEQ byte of a SEQN read) are requested; a step without a listed call requests no ML byte, one without
+  //         an unlisted match slot no base.  What C needs of the slot is packed into one register (st).  (A read without calls has its
+  //         bases in pe(s) and forms the coverage feature here.)
+  //   C(s)  the caller on the ML bytes, NoCall(base) from the base dword, the feature byte, `gaps` / `n_callfeat`.  The byte is stored in B(s + 1), behind its requests (and
   //         behind the loop for the last step): the wait for pe(s + 1) at the head of the next iteration is a full one — the compiler
   //         counts the loop's entry edge, where nothing follows the gather — and a store issued just before it would be waited for.
   // A(0) runs in front of the loop; an iteration runs B(s), A(s + 1), C(s): the ML round trip of step s passes under the mapping of step
   // s + 1 — the longest VALU and LDS stretch of an iteration — and the gather of step s + 1 under the caller of step s.  Loads return in
   // issue order, so the wait in front of C(s) is a counted one that leaves pe(s + 1) and the slot positions in flight.  A(s + 1) runs
   // behind the last step as well (every lane invalid: no mapping, two loads of addresses inside the read's rooms): a branch around it would
-  // make that wait a full drain.  Carried across A(s + 1): the ML bytes, the SEQ byte and st; across C(s): pe(s + 1), kind, q.
+  // make that wait a full drain.  Carried across A(s + 1): the ML bytes, the base dword, the SEQ byte and st; across C(s): pe(s + 1), kind, q.
   const uint32_t pl_last = max(MKP_PLANE_WORDS(L), 1u) - 1u, sq_last = (max(L, 1u) - 1u) >> 1, ent_last = max(n_ent, 1u) - 1u;
-  uint32_t kind = 2u, q = 0u, fb_prev = 0u, g_cur = 0u, g_prev = 0u; uint4 pe = make_uint4(0u, 0u, 0u, 0u);
+  uint32_t kind = 2u, q = 0u, fb_prev = 0u, g_cur = 0u, g_prev = 0u;
+  typedef uint32_t U2 __attribute__((ext_vector_type(2)));
+  typedef const __attribute__((address_space(1))) U2* PlaneP2; typedef const __attribute__((address_space(1))) uint32_t* PlaneP1;
+  U2 pe = {0u, 0u};
   auto stage_a = [&](uint32_t s0) {
     const uint32_t i = s0 + (uint32_t)lane;
     const bool valid = i < n_ent;
@@ -428,12 +452,13 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
     if (prm.debug_skip & 64u) { kind = 0u; q = min((uint32_t)(p - h.ref_start), L - 1u); } else   // ablation: no CIGAR mapping
 #endif
     cigwin_map(rw, cg, cg_wide, h.n_cigar, h.ref_start, valid, p, &kind, &q);
-    // the plane entry of the base: its 2-bit code, bit q & 31 of .listed = a listed call sits here, .before + the listed bits below it =
-    // its stored-order ordinal
-    pe = ldo<uint4>(pl, 16u * min(q >> 5, pl_last));
+    // the entry of the base in the read's plane (pl).  A read with calls: bit q & 31 of .listed = a listed call sits here, .before + the
+    // listed bits below it = its stored-order ordinal; every other read: the 2-bit code of the base
+    pe = *reinterpret_cast<PlaneP2>(pl + 8u * min(q >> 5, pl_last));
     p_next = ldo<uint2>(ents, 8u * min(i + 64u, ent_last));   // (behind the gather: see the wait for pe at the head of B)
   };
-  enum : uint32_t { ST_QODD = 1u << 8, ST_MATCH = 1u << 9, ST_LISTED = 1u << 10 };
+  // (ST_Q2: twice the base's index in its dword of the base plane, 2 * (q & 15): the shift that brings its code down)
+  enum : uint32_t { ST_QODD = 1u << 8, ST_MATCH = 1u << 9, ST_LISTED = 1u << 10, ST_BASE = 1u << 11, ST_Q2_SHIFT = 12u };
   if (n_ent_walk != 0u) stage_a(0u);
   for (uint32_t s0 = 0; s0 < n_ent_walk; s0 += 64u) {
     const uint32_t i = s0 + (uint32_t)lane;
@@ -442,19 +467,20 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
     // (pe(s) and the slot entries were requested back to back: both are waited for here, in front of the ML requests, not behind them)
     asm volatile("" : "+v"(p_next.x), "+v"(p_next.y));
     uint32_t st;   // the coverage feature byte | ST_*
-    uint32_t mlb[MKP_KMAX] = {0u, 0u, 0u, 0u}, mlx = 0, seq_byte = 0;
+    uint32_t mlb[MKP_KMAX] = {0u, 0u, 0u, 0u}, mlx = 0, seq_byte = 0, base_dw = 0;
     {
       const bool is_match = valid && kind == 0u && q < L;
-      const uint32_t code = (((q & 16u) ? pe.y : pe.x) >> (2u * (q & 15u))) & 3u;
-      uint32_t fb = cover_feature(valid ? kind : 2u, 1u << code, aln);   // (the BAM code of the base is one-hot for A/C/G/T)
-      if (valid && kind == 0u && q >= L) fb = MKP_FB_NONE;   // (a CIGAR longer than SEQ is refused by the packer)
-      st = fb;
       if (plane_calls) {
+        // pe = {listed, before}.  A deletion's feature and "not in the column" (a ref-skip, an entry past the read's last, a match past
+        // the SEQ: a CIGAR longer than SEQ is refused by the packer) need no base; a match slot's feature is formed in C, from its call or,
+        // without a listed one, from the dword of the base plane requested here.
+        st = (valid && kind == 1u) ? feat(MKP_C_DEL, aln) : MKP_FB_NONE;
         const uint32_t qb = q & 31u;
-        const bool listed = is_match && ((pe.z >> qb) & 1u);
+        const bool listed = is_match && ((pe.x >> qb) & 1u);
+        const bool want_base = is_match && !listed;
         if (__any(listed)) {
           // calls are listed in forward order: a reverse read's stored ordinal j is call n_calls - 1 - j
-          const uint32_t jrel = pe.w + (uint32_t)__popc(pe.z & ((1u << qb) - 1u));
+          const uint32_t jrel = pe.y + (uint32_t)__popc(pe.x & ((1u << qb) - 1u));
           const uint32_t jl = listed ? (rev ? t_n - 1u - jrel : jrel) : 0u;
           // All ML bytes of the call are requested before any is looked at (round 5 waited for each in turn: two to five dependent
           // memory round trips per 64 slots, the longest chain of the wave's life).
@@ -467,6 +493,22 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
           if (f_col & 1u) mlx = (uint32_t)ldo<uint8_t>(ml, __umul24(jl, mlx_s) + mlx_o);
           if (listed) st |= ST_LISTED;
         }
+        // The base of a match slot without a listed call: the dword of the read's base plane that holds base q, beside the ML requests and
+        // of their shape — unconditional within a uniform test, every other lane's address the read's first dword (hot in cache), the
+        // value masked where it is used.  Slots with a listed call never ask: on a read whose slots are mostly listed the base plane's
+        // lines stay in HBM.
+        if (__any(want_base)) {
+          // (8 (q >> 5) + 4 ((q >> 4) & 1), clamped with a min: a select of the offset against 0 is widened to 64 bits, and the load then takes a
+          //  64-bit vector address instead of `scalar base + 32-bit offset`)
+          base_dw = *reinterpret_cast<PlaneP1>(pl_base + min((q >> 2) & ~3u, want_base ? 0xffffffffu : 0u));
+          if (want_base) st |= ST_BASE | ((q & 15u) << (ST_Q2_SHIFT + 1u));
+        }
+      } else {
+        // pe = {base_lo, base_hi}: the base is at hand
+        const uint32_t code = (((q & 16u) ? pe.y : pe.x) >> (2u * (q & 15u))) & 3u;
+        uint32_t fb = cover_feature(valid ? kind : 2u, 1u << code, aln);   // (the BAM code of the base is one-hot for A/C/G/T)
+        if (valid && kind == 0u && q >= L) fb = MKP_FB_NONE;   // (a CIGAR longer than SEQ is refused by the packer)
+        st = fb;
       }
       // a SEQN read's base comes from its SEQ byte, so that a non-ACGT base stays one
       if (seqn_off != 0xffffffffu) {
@@ -540,6 +582,8 @@ __device__ __forceinline__ void decode_slots_body(FUSED_PARAMS(const MkpRunParam
       }
     }
     uint32_t fb = st & 0xffu;
+    // NoCall(base) of a match slot without a listed call, from the base plane's dword (the code complemented on a reverse read: cover_feature)
+    if (st & ST_BASE) { const uint32_t code = (base_dw >> ((st >> ST_Q2_SHIFT) & 30u)) & 3u; fb = feat((uint32_t)MKP_C_NC + (aln ? 3u - code : code), aln); }
     if (seqn_off != 0xffffffffu && (st & ST_MATCH)) {
       const uint32_t nib = (st & ST_QODD) ? (seq_byte & 15u) : (seq_byte >> 4); fb = cover_feature(0u, nib, aln); }
     // (a scalar count: no per-lane counter, no scan at the end)
@@ -961,21 +1005,23 @@ extern "C" __global__ void __launch_bounds__(64) mkp_dup_events(const MkpReadHdr
 // ----------------------------------------------------------------------------------------------------------------------
 // host-side launchers (called from mkp_api.cpp)
 // work = the fused decoder's reads (longest first), cover_ids = the reads of mkp_cover_reads
-extern "C" hipError_t mkp_launch_slots(hipStream_t st, const MkpWork* work, uint32_t n_fused, const void* plane, const uint16_t* cigar16,
+// (call_plane, base_plane: the fused reads' two planes, MkpWork.pad indexes both)
+extern "C" hipError_t mkp_launch_slots(hipStream_t st, const MkpWork* work, uint32_t n_fused, const MkpCallEnt* call_plane, const MkpBaseEnt* base_plane,
+    const uint16_t* cigar16,
     const MkpReadHdr* hdrs, const uint32_t* cover_ids, uint32_t n_cover, const uint32_t* cigar, const uint8_t* seqs, const uint8_t* ml,
     const MkpFusedDesc* fdesc, const MkpRunParams* prm, const uint32_t* slot_pos, const MkpSlotEnt* slot_ent, uint8_t* cov, MkpVisit* visits,
     MkpEvent* events, MkpReadOut* readout) {
-  if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, cigar, cigar16, seqs, static_cast<const uint4*>(plane), ml, fdesc, *prm,
+  if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, cigar, cigar16, seqs, call_plane, base_plane, ml, fdesc, *prm,
       slot_ent, cov, visits, readout);
   if (n_cover) hipLaunchKernelGGL(mkp_cover_reads, dim3((n_cover + 3u) / 4u), dim3(256), 0, st, hdrs, n_cover, cover_ids, cigar, seqs, slot_pos, cov,
       visits, events, readout);
   return hipGetLastError();
 }
-// the base-and-call plane of the fused reads (once per resident shard; it also marks the work records whose delta list runs past its base
+// the call plane and the base plane of the fused reads (once per resident shard; it also marks the work records whose delta list runs past its base
 // and those with a base that is not A/C/G/T, and adds the SEQ bytes the decoder reads of the latter to *seqn_bytes)
 extern "C" hipError_t mkp_launch_call_plane(hipStream_t st, MkpWork* work, uint32_t n_fused, const uint8_t* seqs, const uint32_t* ranks,
-    const MkpFusedDesc* fdesc, void* plane, unsigned long long* seqn_bytes) {
-  if (n_fused) hipLaunchKernelGGL(mkp_call_plane, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, seqs, ranks, fdesc, static_cast<uint4*>(plane),
+    const MkpFusedDesc* fdesc, MkpCallEnt* call_plane, MkpBaseEnt* base_plane, unsigned long long* seqn_bytes) {
+  if (n_fused) hipLaunchKernelGGL(mkp_call_plane, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, seqs, ranks, fdesc, call_plane, base_plane,
       seqn_bytes);
   return hipGetLastError();
 }
