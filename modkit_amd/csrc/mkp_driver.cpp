@@ -23,6 +23,7 @@
 #include "mkp_regions.hpp"
 #include "mkp_writer.hpp"
 #include "mkp_rand.hpp"
+#include "mkp_sample_schedule.hpp"
 
 using namespace mkp;
 
@@ -146,7 +147,6 @@ std::vector<Contig> targets(const BamSource& bam, const RegionSpec* r) {  // get
   return out;
 }
 
-struct IdxStats { std::map<int64_t, uint64_t> mapped_by_tid; uint64_t mapped = 0, unmapped = 0; };
 IdxStats idxstats(const BamSource& bam, const RegionSpec* region, const BedFilter* bf) {  // IdxStats::new_from_reader (sampling_schedule.rs:649-716)
   IdxStats st; int rt = region ? bam.tid_of(region->name) : -1;
   if (region && rt < 0) throw Error(MKP_E_INVALID, "did not find target_id for region");
@@ -160,47 +160,81 @@ IdxStats idxstats(const BamSource& bam, const RegionSpec* region, const BedFilte
 
 void must(mkp_ctx* ctx, int r) { if (r != MKP_OK) throw Error(r, mkp_last_error(ctx)); }
 
-struct Quota { bool all = false; size_t n = 0; };
-// SamplingSchedule::from_num_reads (sampling_schedule.rs:171-273): per contig ceil(N * its share of the reads), capped by its count; while the
-// sum overshoots N by more than half, contigs at or under a rising floor are dropped (the reference walks an FxHashMap there; ascending tid
-// here — order unpinned)
-std::map<uint32_t, Quota> quota_from_num_reads(const IdxStats& st, size_t num_reads, bool include_unmapped) {
-  const uint64_t total_u = include_unmapped ? st.mapped + st.unmapped : st.mapped;
-  if (total_u == 0) throw Error(MKP_E_THRESHOLD, "zero reads found in bam index");
-  std::map<uint32_t, Quota> quota;
-  const float total = (float)total_u; size_t sum = 0;
-  for (auto& kv : st.mapped_by_tid) if (kv.second) { Quota q;
-    q.n = std::min<size_t>((size_t)ceilf((float)num_reads * ((float)kv.second / total)), (size_t)kv.second);
-    sum += q.n; quota[(uint32_t)kv.first] = q; }
-  if (include_unmapped) sum += (size_t)ceilf((float)num_reads * ((float)st.unmapped / total));
-  size_t floor = 1;
-  while ((double)sum / (double)num_reads > 1.5) {
-    for (auto& kv : quota) { if (kv.second.n <= floor) { sum -= kv.second.n; kv.second.n = 0; } if (sum <= num_reads) break; }
-    sum = 0; for (auto& kv : quota) sum += kv.second.n; floor++;
-  }
-  for (auto it = quota.begin(); it != quota.end();) { if (!it->second.all && it->second.n == 0) it = quota.erase(it); else ++it; }
-  return quota;
+// The C ABI's epilogues: what a call's body throws becomes its status, the message going into the context (`ctx->err`), into the caller's
+// buffer, or nowhere
+int fail_into(char* errbuf, size_t errbuf_len, int st, const std::string& m) {
+  if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", m.c_str()); } return st; }
+template <class F> int guarded_ctx(mkp_ctx* ctx, F body) {
+  try { return body(); }
+  catch (const Error& e) { ctx->err = e.what(); return e.status; }
+  catch (const std::exception& e) { ctx->err = e.what(); return MKP_E_INVALID; }
 }
+template <class F> int guarded_buf(char* errbuf, size_t errbuf_len, F body) {
+  try { return body(); }
+  catch (const Error& e) { return fail_into(errbuf, errbuf_len, e.status, e.what()); }
+  catch (const std::exception& e) { return fail_into(errbuf, errbuf_len, MKP_E_INVALID, e.what()); }
+}
+template <class F> int guarded_status(F body) {
+  try { return body(); } catch (const Error& e) { return e.status; } catch (const std::exception&) { return MKP_E_INVALID; }
+}
+
+// --edge-filter / --invert-edge-filter into the caller config (parse_edge_filter_input, command_utils.rs:243-277)
+void parse_edge_filter(const Args& a, mkp_caller* kc) {
+  if (a.edge_filter.empty()) return;
+  kc->edge_filter = 1; kc->edge_inverted = a.invert_edge; size_t c = a.edge_filter.find(',');
+  if (c != std::string::npos) { kc->edge_start = (uint32_t)strtoul(a.edge_filter.c_str(), nullptr, 10);
+      kc->edge_end = (uint32_t)strtoul(a.edge_filter.c_str() + c + 1, nullptr, 10); }
+  else kc->edge_start = kc->edge_end = (uint32_t)strtoul(a.edge_filter.c_str(), nullptr, 10);
+}
+// --mod-thresholds <code>:<threshold>
+std::vector<mkp_mod_threshold> parse_mod_thresholds(const std::vector<std::string>& raws) {
+  std::vector<mkp_mod_threshold> per_mod;
+  for (auto& raw : raws) { size_t c = raw.find(':'); uint32_t code;
+      if (c == std::string::npos || raw.find(':', c + 1) != std::string::npos || !parse_code(raw.substr(0, c), &code)) throw Error(MKP_E_INVALID,
+      "encountered illegal per-mod threshold: " + raw);
+      per_mod.push_back({code, strtof(raw.c_str() + c + 1, nullptr)}); }
+  return per_mod;
+}
+
 struct SampleTimes { double fetch_ms = 0, device_ms = 0, decide_ms = 0; uint64_t rounds = 0, reads = 0; };
 SampleTimes g_sample_times;   // --stats: where the threshold estimate's time went (last run in this process)
 
-// Default threshold estimation: the reference's deterministic "first N qualifying reads per interval" schedule
-// (reads_sampler/mod.rs:30-257, sampling_schedule.rs:171-615); the per-call probabilities come from the decode kernel.
-// The values are accumulated in the context's HBM-resident sample (mkp_internal_sample_take); nothing but per-read counts
-// comes back to the host.  With --gpus-world W > 1 (full-data mode `-f 1.0` only) a rank walks just its own sampling intervals:
-// a read is taken in the first processed interval it overlaps, so the union over ranks is the single-rank sample.
-// The records of one fetch as the sampler sees them: a BamBatch of the indexed / whole-file reader, or — `res`: the shard the device ingest
+// the schedule header knows no status codes: its refusal leaves as the threshold error it always was
+std::map<uint32_t, Quota> num_reads_quotas(const IdxStats& st, size_t num_reads, bool include_unmapped) {
+  try { return quota_from_num_reads(st, num_reads, include_unmapped); } catch (const ScheduleRefusal& e) { throw Error(MKP_E_THRESHOLD, e.what()); }
+}
+
+// A read name as the resident shards know it: two 64-bit hashes
+struct NameKey { uint64_t a, b; bool operator==(const NameKey& o) const { return a == o.a && b == o.b; } };
+struct NameKeyHash { size_t operator()(const NameKey& k) const { return (size_t)(k.a ^ (k.b * 0x9e3779b97f4a7c15ull)); } };
+// Records of a resident shard are numbered kept reads first (index < hdr.size(), digest order), then the sampler-only reads (QC-fail ...: few)
+NameKey resident_name_key(const ShardHost& S, uint32_t k) {
+  const size_t n = S.hdr.size();
+  return k < n ? NameKey{S.name_hash[k], S.dev_name_hash2[k]} : NameKey{S.so_name_hash[k - n], S.so_name_hash2[k - n]};
+}
+// the records of resident shard S that satisfy `pred` — of the kept reads only [first, last) are looked at — in file order: the kept
+// records in digest order, the sampler-only records merged in by their place in the file (window index)
+template <class Pred> std::vector<uint32_t> resident_ids(const ShardHost& S, size_t first, size_t last, Pred pred) {
+  const size_t n = S.hdr.size();
+  std::vector<uint32_t> ids; ids.reserve(last - first + S.so_hdr.size());
+  for (size_t i = first; i < last; i++) if (pred(S.hdr[i])) ids.push_back((uint32_t)i);
+  bool any_so = false;
+  for (size_t k = 0; k < S.so_hdr.size(); k++) if (pred(S.so_hdr[k])) { ids.push_back((uint32_t)(n + k)); any_so = true; }
+  if (any_so) { auto wi = [&](uint32_t k) { return k < n ? S.dev_win_idx[k] : S.so_win_idx[k - n]; };
+    std::stable_sort(ids.begin(), ids.end(), [&](uint32_t x, uint32_t y) { return wi(x) < wi(y); }); }
+  return ids;
+}
+
+// The records of one fetch as the sampler sees them: a BamBatch of the indexed / whole-file reader, or — `S`: the shard the device ingest
 // attached to the context covers the contig — indices into that shard's digest (every kept record is a candidate; names are compared
 // through their two 64-bit hashes; the reads' bases and tags are in HBM already, mkp_internal_sample_resident).
 struct RecSet {
-  // complete: nothing was left out for a later fetch; resident: index < S->hdr.size() = a kept read, above = sampler-only read (index - hdr.size())
+  // complete: nothing was left out for a later fetch; resident: idx numbers the shard's records as resident_ids does
   std::unique_ptr<BamBatch> b; bool complete = false; const ShardHost* S = nullptr; std::vector<uint32_t> idx;
   size_t size() const { return S ? idx.size() : b->recs.size(); }
   bool truncated(size_t cap) const { return !S && !complete && b->recs.size() >= cap; }
   std::string name(size_t i) const {
-    if (S) { const uint32_t k = idx[i]; const size_t n = S->hdr.size(); char key[16];
-      memcpy(key, k < n ? &S->name_hash[k] : &S->so_name_hash[k - n], 8);
-      memcpy(key + 8, k < n ? &S->dev_name_hash2[k] : &S->so_name_hash2[k - n], 8);
+    if (S) { const NameKey k = resident_name_key(*S, idx[i]); char key[16]; memcpy(key, &k.a, 8); memcpy(key + 8, &k.b, 8);
       return std::string(key, 16); }
     return b->qname(b->recs[i]);
   }
@@ -223,6 +257,12 @@ struct BedMasks {
     return it->second.data();
   }
 };
+// the context keeps the device copies of a sampler's BED masks while this object lives: the host masks die with the sampler
+struct MaskSession {
+  mkp_ctx* c;
+  explicit MaskSession(mkp_ctx* ctx) : c(ctx) { mkp_internal_bedmask_reset(c); }
+  ~MaskSession() { mkp_internal_bedmask_reset(c); }
+};
 
 // what `bam::IndexedReader::from_path` finds (htslib: <bam>.bai, <bam>.csi, or the extension replaced)
 bool bam_index_file_exists(const std::string& path) {
@@ -233,220 +273,87 @@ bool bam_index_file_exists(const std::string& path) {
   return false;
 }
 
-// The sampler of a BAM WITHOUT an index (reads_sampler/mod.rs:129-158; `bam::IndexedReader::from_path(..).is_ok()` decides, so an index
-// ignored by `extract calls --ignore-index` still counts as one): no schedule — one pass over the file in file order, mapped and unmapped
-// records alike, under RecordSampler::new_from_options (record_sampler.rs:51-61): the first --num-reads records that yield values, or with
-// --sampling-frac one `gen_bool` per record the tag iterator yields (StdRng, --seed).  A region is an error there, as it is here.
-// Records go to the sampling kernels contig by contig (a round has one reference window and one BED mask); the sampler's state — reads
-// used, names seen — runs across the whole file.
-void sample_serial(mkp_ctx* ctx, const BamSource& bam, const Args& a, const RegionSpec* region, const BedFilter* bf) {
-  if (region) throw Error(MKP_E_INVALID, "cannot use region without indexed BAM");
-  const bool only_mapped = !a.include_unmapped;
-  const bool draws = a.have_frac && a.sampling_frac < 1.0;
-  if (a.have_frac && a.sampling_frac > 1.0) throw Error(MKP_E_INVALID, "sample fraction must be <= 1");
-  if (draws && !a.have_seed) throw Error(MKP_E_UNSUPPORTED,
-      "--sampling-frac < 1 on a BAM without an index draws from an entropy-seeded rand::StdRng (record_sampler.rs:29-38): give --seed");
-  // a draw is taken for every record whose tags parse and hold a position, whether or not a value survives the filters; the kernels report
-  // surviving values only — the two coincide while nothing can remove a record's every position
-  if (draws && (only_mapped || bf || !a.edge_filter.empty())) throw Error(MKP_E_UNSUPPORTED,
-      "--sampling-frac < 1 on a BAM without an index together with --only-mapped / --include-bed / --edge-filter: which records consume a draw is not reproduced");
-  SeededSampler rng(a.seed);
-  const long limit = a.have_frac ? -1 : (long)a.num_reads;
-  std::set<std::string> seen; size_t used = 0;
-  BedMasks mask_of{bf, bam, {}};
-  auto round = [&](const RecSet& set, int64_t tid) {
-    const BamBatch& b = *set.b;
-    std::vector<size_t> cand;
-    for (size_t i = 0; i < set.size(); i++) if (set.candidate(i, only_mapped || !a.edge_filter.empty())) cand.push_back(i);
-    const bool mapped = tid >= 0;
-    const uint8_t* mask = mapped ? mask_of((uint32_t)tid) : nullptr;
-    for (size_t next = 0; next < cand.size() && (limit < 0 || used < (size_t)limit);) {
-      const size_t want = limit < 0 ? std::min<size_t>(cand.size() - next, 1u << 18) : std::max<size_t>(256, 2 * ((size_t)limit - used));
-      const size_t hi = std::min(cand.size(), next + want);
-      std::vector<mkp_record> recs; recs.reserve(hi - next); for (size_t i = next; i < hi; i++) recs.push_back(b.view(b.recs[cand[i]]));
-      std::vector<uint32_t> nv;
-      must(ctx, mkp_internal_sample(ctx, mapped ? (int32_t)tid : -1, 0, mapped ? bam.ref_lens[(size_t)tid] : 1, mask, recs.data(),
-          (uint32_t)recs.size(),
-          only_mapped, &nv));
-      std::vector<uint8_t> keep(recs.size(), 0);
-      for (size_t i = next; i < hi; i++) {
-        if (limit >= 0 && used >= (size_t)limit) break;                               // RecordSampler::ask -> Done
-        const size_t k = i - next;
-        if (draws && nv[k] != 0 && !rng.keep(a.sampling_frac)) continue;               // check_sample_frac -> Skip
-        std::string name = set.name(cand[i]);
-        if (seen.count(name) || nv[k] == 0) continue;                                 // seen(); a record that keeps no value is not recorded
-        seen.insert(name); used++; keep[k] = 1;
-      }
-      must(ctx, mkp_internal_sample_take(ctx, keep));
-      next = hi;
-    }
-  };
-  for (size_t t = 0; t < bam.ref_names.size() && (limit < 0 || used < (size_t)limit); t++) {
-    RecSet set; set.b.reset(new BamBatch()); bam.fetch((uint32_t)t, 0, std::max<uint32_t>(bam.ref_lens[t], 1u), set.b.get());
-    round(set, (int64_t)t);
-  }
-  if (limit < 0 || used < (size_t)limit) { RecSet set; set.b.reset(new BamBatch()); bam.fetch_unmapped(set.b.get()); round(set, -1); }
-}
-
-struct Iv { uint32_t tid, start, end; };
-// ReferenceIntervalsFeeder over the sampling grid (interval_chunks.rs:563-643): the intervals of every super-batch of `batch_size` feeder
-// batches (MultiChromCoordinates in feeder order), by contig and start
-std::vector<std::vector<Iv>> sampling_super_batches(const std::vector<Contig>& contigs, uint32_t interval_size, size_t batch_size) {
-  std::vector<std::vector<Iv>> groups;
-  { std::vector<Iv> batch; uint32_t blen = 0;
-    for (auto& c : contigs) for (uint32_t p = c.start; p < c.end();) {
-      uint32_t e = (uint32_t)std::min<uint64_t>((uint64_t)p + interval_size, c.end());
-        batch.push_back({c.tid, p, e}); blen += e - p; if (blen >= interval_size) { groups.push_back(batch); batch.clear(); blen = 0;
-          } p = e; }
-    if (!batch.empty()) groups.push_back(batch); }
-  std::vector<std::vector<Iv>> out;
-  for (size_t g0 = 0; g0 < groups.size(); g0 += std::max<size_t>(batch_size, 1)) {
-    std::vector<Iv> all;
-      for (size_t g = g0; g < std::min(groups.size(), g0 + std::max<size_t>(batch_size, 1)); g++) for (auto& iv : groups[g]) all.push_back(iv);
-    std::stable_sort(all.begin(), all.end(), [](const Iv& x, const Iv& y) { return x.tid != y.tid ? x.tid < y.tid : x.start < y.start; });
-    out.push_back(std::move(all));
-  }
-  return out;
-}
-
-// accumulate_sample_counts (sampling_schedule.rs:440-615): the intervals of one super-batch with their quotas — what is left of each contig's
-// quota spread over its intervals by length, intervals whose share is under 50 reads merged with their neighbours
-struct SampleIv { Iv iv; Quota q; };
-std::vector<SampleIv> group_super_batch(const std::vector<Iv>& all, const std::map<uint32_t, uint32_t>& contig_size,
-    const std::map<uint32_t, Quota>& quota, const std::map<uint32_t, size_t>& sampled_so_far) {
-  std::map<uint32_t, uint32_t> len_per; for (auto& iv : all) len_per[iv.tid] += iv.end - iv.start;
-  std::map<uint32_t, Quota> per_chrom;
-  for (auto& kv : len_per) { auto cs = contig_size.find(kv.first); auto q = quota.find(kv.first);
-    if (cs == contig_size.end() || q == quota.end()) continue;
-      auto sf = sampled_so_far.find(kv.first); size_t so_far = sf != sampled_so_far.end() ? sf->second : 0;
-      float f = (float)kv.second / (float)cs->second;
-    if (q->second.all) per_chrom[kv.first] = q->second; else if (q->second.n > so_far) { Quota x;
-      x.n = (size_t)ceilf(f * (float)(q->second.n - so_far));
-        per_chrom[kv.first] = x; } }
-  std::vector<SampleIv> grouped; bool have_slack = false; Iv slack{0, 0, 0}; size_t slack_n = 0;
-  auto merged = [](const Iv& x, const Iv& y) { return Iv{x.tid, std::min(x.start, y.start), std::max(x.end, y.end)}; };
-  for (auto& iv : all) {
-    auto pc = per_chrom.find(iv.tid); if (pc == per_chrom.end()) continue;
-    if (pc->second.all) { grouped.push_back({iv, pc->second}); continue; }
-    float f = (float)(iv.end - iv.start) / (float)len_per[iv.tid]; size_t x = (size_t)ceilf((float)pc->second.n * f); Quota qx; qx.n = x;
-    if (x < 50) {
-      if (have_slack) { if (slack.tid == iv.tid) { Iv m = merged(slack, iv); size_t tot = x + slack_n; if (tot < 50) { slack = m; slack_n = tot;
-          } else { Quota q;
-          q.n = tot; grouped.push_back({m, q}); have_slack = false; } } else { Quota q; q.n = slack_n; grouped.push_back({slack, q}); slack = iv;
-            slack_n = x; } }
-      else { have_slack = true; slack = iv; slack_n = x; }
-    } else if (have_slack) { have_slack = false; if (slack.tid == iv.tid) { Quota q; q.n = slack_n + x; grouped.push_back({merged(slack, iv), q});
-      } else { Quota q;
-        q.n = slack_n; grouped.push_back({slack, q}); grouped.push_back({iv, qx}); } }
-    else grouped.push_back({iv, qx});
-  }
-  if (have_slack) { Quota q; q.n = slack_n; grouped.push_back({slack, q}); }
-  return grouped;
-}
-
 // `resident_of` (optional): the device-packed shard holding contig `tid`, bound to the context (mkp_internal_sample_bind) — the estimate then
 // samples from HBM; called whenever the schedule moves to another contig.
 using ResidentOf = std::function<const ShardHost*(uint32_t tid)>;
-void sample_probabilities(mkp_ctx* ctx, const BamSource& bam, const Args& a, const RegionSpec* region, const BedFilter* bf,
-    const ResidentOf& resident_of = ResidentOf()) {
-  const bool only_mapped = !a.include_unmapped;
-  const bool sharded = a.world > 1;
-  const bool resident_mode = (bool)resident_of;
-  if (resident_mode && (!only_mapped || sharded)) throw Error(MKP_E_INVALID, "internal: resident sampling needs mapped-only, single-rank sampling");
+
+// One fetched record set as the first-N logic walks it: the records, `idx` = those that are candidates, `skip` (rank-sharded mode; else
+// empty) = the candidates an earlier interval already took
+struct Fetched { RecSet set; std::vector<size_t> idx; std::vector<uint8_t> skip; };
+// process_records (read_ids_to_base_mod_probs.rs:223-362) over the candidate records of one interval, first-N semantics
+struct IntervalState { std::set<std::string> seen; size_t used = 0; };
+struct Draws { SeededSampler* rng = nullptr; double frac = 1.0; };   // --sampling-frac < 1: one seeded draw per record (none: every record)
+// Default threshold estimation: the reference's deterministic "first N qualifying reads per interval" schedule
+// (reads_sampler/mod.rs:30-257, sampling_schedule.rs:171-615); the per-call probabilities come from the decode kernel.
+// The values are accumulated in the context's HBM-resident sample (mkp_internal_sample_take); nothing but per-read counts
+// comes back to the host.  With --gpus-world W > 1 (full-data mode `-f 1.0` only) a rank walks just its own sampling intervals:
+// a read is taken in the first processed interval it overlaps, so the union over ranks is the single-rank sample.
+// The stages are the methods, in the order a run meets them.
+struct ThresholdSampler {
+  using G = SampleIv;
+  using Which = std::vector<std::pair<const RecSet*, size_t>>;          // records of a device round: indices into the sets' records, set by set
+
+  mkp_ctx* ctx; const BamSource& bam; const Args& a; const BedFilter* bf; const ResidentOf& resident_of;
+  const bool only_mapped, sharded, resident_mode;
+  MaskSession mask_session;
+  BedMasks bedmask_for;
+  SamplingGrid grid;                                        // the scheduled contigs (the owner of an interval; where a contig's grid starts)
   const ShardHost* res = nullptr; uint32_t res_tid = 0xffffffffu;
   std::vector<int32_t> res_pmax;   // resident shard: prefix maximum of the alignment ends (first record that can reach an interval)
-  auto use_contig = [&](uint32_t tid) {   // the shard of contig `tid` becomes the one sampled from
+  std::set<std::string> taken; std::map<uint32_t, size_t> sampled_so_far;
+
+  ThresholdSampler(mkp_ctx* c, const BamSource& b, const Args& args, const BedFilter* f, const ResidentOf& r)
+      : ctx(c), bam(b), a(args), bf(f), resident_of(r), only_mapped(!args.include_unmapped), sharded(args.world > 1), resident_mode((bool)r),
+        mask_session(c), bedmask_for{f, b, {}} {}
+
+  // ---- fetch a record set
+  void use_contig(uint32_t tid) {   // the shard of contig `tid` becomes the one sampled from
     if (res && res_tid == tid) return;
     res = resident_of(tid); res_tid = tid;
     if (!res || (int32_t)tid != res->tid) throw Error(MKP_E_INVALID, "internal: resident sampling outside the ingested contigs");
     res_pmax.resize(res->hdr.size()); int32_t m = INT32_MIN; for (size_t i = 0; i < res->hdr.size(); i++) {
       m = std::max(m, std::max(res->hdr[i].ref_end, res->hdr[i].ref_start + 1)); res_pmax[i] = m; }
-  };
-  auto fetch_set = [&](uint32_t tid, uint32_t s, uint32_t e, size_t cap) {
-    RecSet r;
-    if (resident_mode) {
-      use_contig(tid);
-      r.S = res;
-      const size_t first = (size_t)(std::upper_bound(res_pmax.begin(), res_pmax.end(),
-          (int32_t)std::min<uint32_t>(s, 0x7fffffffu)) - res_pmax.begin());
-      for (size_t i = first; i < res->hdr.size() && (int64_t)res->hdr[i].ref_start < (int64_t)e; i++) if ((int64_t)std::max(res->hdr[i].ref_end,
-          res->hdr[i].ref_start + 1) > (int64_t)s) r.idx.push_back((uint32_t)i);
-      // the sampler-only records of the window (QC-fail ...: few), merged in by their place in the file
-      bool any_so = false;
-      for (size_t k = 0; k < res->so_hdr.size(); k++) { const MkpReadHdr& h = res->so_hdr[k];
-        if ((int64_t)h.ref_start < (int64_t)e && (int64_t)std::max(h.ref_end, h.ref_start + 1) > (int64_t)s) {
-          r.idx.push_back((uint32_t)(res->hdr.size() + k)); any_so = true; } }
-      if (any_so) { const size_t n = res->hdr.size(); auto wi = [&](uint32_t k) { return k < n ? res->dev_win_idx[k] : res->so_win_idx[k - n]; };
-        std::stable_sort(r.idx.begin(), r.idx.end(), [&](uint32_t x, uint32_t y) { return wi(x) < wi(y); }); }
-      return r;
-    }
-    r.b.reset(new BamBatch());
-    if (bf) {
-      // under --include-bed a read counts only through calls on BED positions (the kernel masks the rest): a read that meets no BED span
-      // yields nothing, is not counted and not recorded — so only the records that can meet one are fetched (a sparse BED used to make
-      // the estimate inflate every sampling interval whole), all of them: there is no head to extend afterwards.  A record of the interval
-      // meets a span inside it, or reaches a span outside it — then it crosses the interval's first or last position.
-      std::vector<Span> sp = bf->spans_in(tid, s, e);
-      sp.push_back({s, (uint64_t)s + 1}); if (e > s + 1) sp.push_back({(uint64_t)e - 1, e});
-      std::sort(sp.begin(), sp.end(), [](const Span& x, const Span& y) { return x.s < y.s; });
-      merge_spans(sp);
-      FetchParts parts; for (auto& x : sp) parts.push_back({(int64_t)x.s, (int64_t)x.e});
-      if (!parts.empty()) bam.fetch_parts(tid, parts, r.b.get());
-      r.complete = true; return r;
-    }
-    bam.fetch(tid, s, e, r.b.get(), cap); return r;
-  };
-  mkp_internal_bedmask_reset(ctx);
-  struct MaskSession { mkp_ctx* c; ~MaskSession() { mkp_internal_bedmask_reset(c); } } mask_session{ctx};   // the host masks below die with this call
-  if (a.serial_sampler) { sample_serial(ctx, bam, a, region, bf); return; }
-  if (sharded && !(a.have_frac && a.sampling_frac >= 1.0)) throw Error(MKP_E_UNSUPPORTED,
-      "rank-sharded threshold sampling needs the full-data mode (-f 1.0): the count-based schedule carries quotas from interval to interval");
-  IdxStats st = idxstats(bam, region, bf);
-  const uint64_t total_u = only_mapped ? st.mapped : st.mapped + st.unmapped;
-  if (total_u == 0) throw Error(MKP_E_THRESHOLD, "zero reads found in bam index");
-  std::map<uint32_t, Quota> quota; bool sched_unmapped = !only_mapped;
-  if (a.have_frac) {  // from_sample_frac (321-381)
-    if (a.sampling_frac > 1.0) throw Error(MKP_E_INVALID, "sample fraction must be <= 1");
-    const float f = (float)a.sampling_frac;
-    for (auto& kv : st.mapped_by_tid) if (kv.second) { Quota q; if (f == 1.0f) q.all = true; else q.n = (size_t)ceilf((float)kv.second * f);
-        quota[(uint32_t)kv.first] = q; }
-  } else quota = quota_from_num_reads(st, a.num_reads, !only_mapped);
-  const size_t batch_size = (size_t)floorf((float)a.threads * 1.5f);
-  std::vector<Contig> contigs; for (auto& c : targets(bam, region)) if (quota.count(c.tid)) contigs.push_back(c);
-  std::map<uint32_t, uint32_t> contig_size; for (auto& c : contigs) contig_size[c.tid] = c.length;
-  std::map<uint32_t, uint64_t> contig_base, contig_start; uint64_t grid_bp = 0; for (auto& c : contigs) { contig_base[c.tid] = grid_bp;
-    contig_start[c.tid] = c.start;
-      grid_bp += c.length; }
-  std::set<std::string> taken; std::map<uint32_t, size_t> sampled_so_far;
-  BedMasks bedmask_for{bf, bam, {}};
-  // process_records (read_ids_to_base_mod_probs.rs:223-362) over the candidate records, first-N semantics
-  // One fetched batch of an interval: `cand` = indices into batch.recs that pass `candidates`, processed from cand[from] on.
-  // `skip` (rank-sharded mode): candidates an earlier interval already took.  State across calls: used / n_reads_out.
-  struct TakeState { size_t used = 0, n_reads_out = 0; };
-  // the sampler's verdict on candidates cand[lo, hi) whose value counts are nv[0 ..): mask[k] = 1 where the read's values enter the sample
-  auto decide = [&](const RecSet& batch, const std::vector<size_t>& cand, size_t lo, size_t hi, const uint32_t* nv, long limit,
-      std::set<std::string>* interval_seen,
-      TakeState* ts, const std::vector<uint8_t>* skip, uint8_t* mask, SeededSampler* draws = nullptr, double frac = 1.0) {
-    for (size_t i = lo; i < hi; i++) {
-      if (limit >= 0 && ts->used >= (size_t)limit) break;   // RecordSampler::ask -> Done
-      const size_t k = i - lo;
-      if (skip && (*skip)[i]) continue;
-      // check_sample_frac (record_sampler.rs:80-86): one draw per record the iterator yields, before anything else is looked at.  Only the
-      // unmapped leg draws, and there (no edge filter, no BED, no alignment) "the tags parse and hold a position" == "a value is left"
-      if (draws && nv[k] != 0 && !draws->keep(frac)) continue;
-      std::string name = batch.name(cand[i]);
-      // with_mod_base_info drops reads whose tags fail or are empty before the sampler is asked; a read that parses
-      // but keeps no position is asked, not counted, and not recorded
-      if (interval_seen->count(name)) continue;
-      if (nv[k] == 0) continue;
-      interval_seen->insert(name); ts->used++; ts->n_reads_out++;
-      if (taken.count(name)) continue;  // Moniod::op_mut keeps the first occurrence of a read id
-      taken.insert(name);
-      mask[k] = 1;
-    }
-  };
-  // decode the records `which` (indices into the sets' records, set by set) in sampling mode: one device round
-  auto sample_round = [&](const std::vector<std::pair<const RecSet*, size_t>>& which, uint32_t tid, bool mapped_contig, std::vector<uint32_t>* nv) {
+  }
+  RecSet fetch_resident(uint32_t tid, uint32_t s, uint32_t e) {
+    use_contig(tid);
+    RecSet r; r.S = res;
+    const size_t first = (size_t)(std::upper_bound(res_pmax.begin(), res_pmax.end(), (int32_t)std::min<uint32_t>(s, 0x7fffffffu)) - res_pmax.begin());
+    const size_t last = (size_t)(std::partition_point(res->hdr.begin() + (long)first, res->hdr.end(),
+        [&](const MkpReadHdr& h) { return (int64_t)h.ref_start < (int64_t)e; }) - res->hdr.begin());   // (the digest is sorted by start)
+    r.idx = resident_ids(*res, first, last, [&](const MkpReadHdr& h) {
+      return (int64_t)h.ref_start < (int64_t)e && (int64_t)std::max(h.ref_end, h.ref_start + 1) > (int64_t)s; });
+    return r;
+  }
+  // under --include-bed a read counts only through calls on BED positions (the kernel masks the rest): a read that meets no BED span
+  // yields nothing, is not counted and not recorded — so only the records that can meet one are fetched (a sparse BED used to make
+  // the estimate inflate every sampling interval whole), all of them: there is no head to extend afterwards.  A record of the interval
+  // meets a span inside it, or reaches a span outside it — then it crosses the interval's first or last position.
+  RecSet fetch_bed_parts(uint32_t tid, uint32_t s, uint32_t e) const {
+    RecSet r; r.b.reset(new BamBatch());
+    std::vector<Span> sp = bf->spans_in(tid, s, e);
+    sp.push_back({s, (uint64_t)s + 1}); if (e > s + 1) sp.push_back({(uint64_t)e - 1, e});
+    std::sort(sp.begin(), sp.end(), [](const Span& x, const Span& y) { return x.s < y.s; });
+    merge_spans(sp);
+    FetchParts parts; for (auto& x : sp) parts.push_back({(int64_t)x.s, (int64_t)x.e});
+    if (!parts.empty()) bam.fetch_parts(tid, parts, r.b.get());
+    r.complete = true; return r;
+  }
+  RecSet fetch(uint32_t tid, uint32_t s, uint32_t e, size_t cap) {
+    if (resident_mode) return fetch_resident(tid, s, e);
+    if (bf) return fetch_bed_parts(tid, s, e);
+    RecSet r; r.b.reset(new BamBatch()); bam.fetch(tid, s, e, r.b.get(), cap); return r;
+  }
+  static size_t cap_of(const G& g) { return g.q.all ? SIZE_MAX : 2 * g.q.n + 128; }
+
+  // ---- candidates, one device round, the verdict
+  Fetched with_candidates(RecSet set, const G* g = nullptr) {   // g: the interval the set was fetched for
+    Fetched F; F.set = std::move(set);
+    for (size_t i = 0; i < F.set.size(); i++) if (F.set.candidate(i, only_mapped || a.edge_filter.size())) F.idx.push_back(i);
+    if (sharded && g) F.skip = skip_list(*g, F);
+    return F;
+  }
+  // decode the records `which` in sampling mode: one device round
+  void device_round(const Which& which, uint32_t tid, bool mapped_contig, std::vector<uint32_t>* nv) {
     const uint32_t ws = 0, we = mapped_contig ? bam.ref_lens[tid] : 1; const uint8_t* mask = mapped_contig ? bedmask_for(tid) : nullptr;
     int rc;
     if (resident_mode) { std::vector<uint32_t> ids; ids.reserve(which.size()); for (auto& w : which) ids.push_back(w.first->idx[w.second]);
@@ -454,152 +361,219 @@ void sample_probabilities(mkp_ctx* ctx, const BamSource& bam, const Args& a, con
     else { std::vector<mkp_record> recs; recs.reserve(which.size());
       for (auto& w : which) recs.push_back(w.first->b->view(w.first->b->recs[w.second]));
       rc = mkp_internal_sample(ctx, mapped_contig ? (int32_t)tid : -1, ws, we, mask, recs.data(), (uint32_t)recs.size(), only_mapped, nv); }
-    if (rc != MKP_OK) throw Error(rc, mkp_last_error(ctx));
-  };
-  auto take = [&](const RecSet& batch, const std::vector<size_t>& cand, size_t from, long limit, uint32_t tid, bool mapped_contig,
-      std::set<std::string>* interval_seen,
-      TakeState* ts, const std::vector<uint8_t>* skip = nullptr, SeededSampler* draws = nullptr, double frac = 1.0) {
+    must(ctx, rc);
+  }
+  // the sampler's verdict on candidates F.idx[lo, hi) whose value counts are nv[0 ..): mask[k] = 1 where the read's values enter the sample
+  void verdict(const Fetched& F, size_t lo, size_t hi, const uint32_t* nv, long limit, IntervalState* st, uint8_t* mask, Draws draws = Draws()) {
+    for (size_t i = lo; i < hi; i++) {
+      if (limit >= 0 && st->used >= (size_t)limit) break;   // RecordSampler::ask -> Done
+      const size_t k = i - lo;
+      if (!F.skip.empty() && F.skip[i]) continue;
+      // check_sample_frac (record_sampler.rs:80-86): one draw per record the iterator yields, before anything else is looked at.  Only the
+      // unmapped leg and the serial pass draw, and there (the serial pass refuses the filters that could differ) "the tags parse and hold a
+      // position" == "a value is left"
+      if (draws.rng && nv[k] != 0 && !draws.rng->keep(draws.frac)) continue;    // check_sample_frac -> Skip
+      std::string name = F.set.name(F.idx[i]);
+      // with_mod_base_info drops reads whose tags fail or are empty before the sampler is asked; a read that parses
+      // but keeps no position is asked, not counted, and not recorded
+      if (st->seen.count(name)) continue;
+      if (nv[k] == 0) continue;
+      st->seen.insert(name); st->used++;
+      if (taken.count(name)) continue;  // Moniod::op_mut keeps the first occurrence of a read id
+      taken.insert(name);
+      mask[k] = 1;
+    }
+  }
+  // the candidates of one fetched set from F.idx[from] on, in device rounds until the limit is reached (limit < 0: all of them)
+  void take(const Fetched& F, size_t from, long limit, uint32_t tid, bool mapped_contig, IntervalState* st, Draws draws = Draws()) {
     size_t next = from;
-    while (next < cand.size() && (limit < 0 || ts->used < (size_t)limit)) {
-      size_t want = limit < 0 ? std::min<size_t>(cand.size() - next, 1u << 18) : std::max<size_t>(256, 2 * ((size_t)limit - ts->used));
-      size_t hi = std::min(cand.size(), next + want);
-      std::vector<std::pair<const RecSet*, size_t>> which; which.reserve(hi - next);
-        for (size_t i = next; i < hi; i++) which.push_back({&batch, cand[i]});
-      std::vector<uint32_t> nv; sample_round(which, tid, mapped_contig, &nv);
+    while (next < F.idx.size() && (limit < 0 || st->used < (size_t)limit)) {
+      size_t want = limit < 0 ? std::min<size_t>(F.idx.size() - next, 1u << 18) : std::max<size_t>(256, 2 * ((size_t)limit - st->used));
+      size_t hi = std::min(F.idx.size(), next + want);
+      Which which; which.reserve(hi - next);
+        for (size_t i = next; i < hi; i++) which.push_back({&F.set, F.idx[i]});
+      std::vector<uint32_t> nv; device_round(which, tid, mapped_contig, &nv);
       std::vector<uint8_t> mask(which.size(), 0);
-      decide(batch, cand, next, hi, nv.data(), limit, interval_seen, ts, skip, mask.data(), draws, frac);
+      verdict(F, next, hi, nv.data(), limit, st, mask.data(), draws);
       must(ctx, mkp_internal_sample_take(ctx, mask));
       next = hi;
     }
-  };
-  auto candidates = [&](const RecSet& batch, std::vector<size_t>* out) {
-    out->clear();
-    for (size_t i = 0; i < batch.size(); i++) if (batch.candidate(i, only_mapped || a.edge_filter.size())) out->push_back(i);
-  };
-  if (!contigs.empty()) {
-    for (const std::vector<Iv>& all : sampling_super_batches(contigs, a.sampling_interval_size, batch_size)) {
-      using G = SampleIv;
-      const std::vector<G> grouped = group_super_batch(all, contig_size, quota, sampled_so_far);
-      std::map<uint32_t, size_t> batch_counts;
-      // intervals this rank samples, in order; the head of the next one is fetched while the current one is decoded
-      std::vector<size_t> mine;
-      for (size_t gi = 0; gi < grouped.size(); gi++) {
-        const G& g = grouped[gi];
-        if (bf && !bf->overlaps(g.iv.tid, g.iv.start, g.iv.end)) continue;
-        if (sharded) {
-          // owner of the interval: contiguous runs of the sampling grid by base pairs (as the pileup shards are dealt)
-          const uint64_t mid = contig_base[g.iv.tid] + (g.iv.start - contig_start[g.iv.tid]) + (g.iv.end - g.iv.start) / 2;
-          if (std::min<uint64_t>(a.world - 1, mid * a.world / std::max<uint64_t>(grid_bp, 1)) != a.rank) continue;
-        }
-        mine.push_back(gi);
+  }
+
+  // ---- the intervals of a super batch
+  // rank-sharded mode: a read that reaches back into an earlier processed interval of this contig was taken there
+  std::vector<uint8_t> skip_list(const G& g, const Fetched& F) const {
+    std::vector<uint8_t> skip(F.idx.size(), 0);
+    const int64_t c_start = (int64_t)grid.start.at(g.iv.tid);
+    for (size_t i = 0; i < F.idx.size(); i++) {
+      const int64_t e_pos = F.set.pos(F.idx[i]);
+      for (int64_t s1 = g.iv.start; s1 > c_start && e_pos < s1;) {   // grid intervals before this one, nearest first
+        const int64_t s0 = std::max<int64_t>(c_start, s1 - (int64_t)a.sampling_interval_size);
+        if (!bf || bf->overlaps(g.iv.tid, (uint64_t)s0, (uint64_t)s1)) { skip[i] = 1; break; }
+        s1 = s0;
       }
-      auto cap_of = [&](const G& g) { return g.q.all ? SIZE_MAX : 2 * g.q.n + 128; };
-      auto head_of = [&](size_t gi) {
-        return std::unique_ptr<RecSet>(new RecSet(fetch_set(grouped[gi].iv.tid, grouped[gi].iv.start, grouped[gi].iv.end, cap_of(grouped[gi])))); };
-      auto skip_for = [&](const G& g, const RecSet& batch, const std::vector<size_t>& cand, std::vector<uint8_t>* skip) {
-        // rank-sharded mode: a read that reaches back into an earlier processed interval of this contig was taken there
-        skip->assign(cand.size(), 0);
-        for (size_t i = 0; i < cand.size(); i++) {
-          const int64_t e_pos = batch.pos(cand[i]);
-          for (int64_t s1 = g.iv.start; s1 > (int64_t)contig_start[g.iv.tid] && e_pos < s1;) {   // grid intervals before this one, nearest first
-            const int64_t s0 = std::max<int64_t>((int64_t)contig_start[g.iv.tid], s1 - (int64_t)a.sampling_interval_size);
-            if (!bf || bf->overlaps(g.iv.tid, (uint64_t)s0, (uint64_t)s1)) { (*skip)[i] = 1; break; }
-            s1 = s0;
-          }
-        }
-      };
-      // the rest of an interval after its head (or all of it in full-data mode): sequential device rounds
-      auto finish_interval = [&](const G& g, std::unique_ptr<RecSet>& head, const std::vector<size_t>& head_cand, size_t head_done,
-          const std::vector<uint8_t>& head_skip, std::set<std::string>* seen, TakeState* ts) {
-        const long limit = g.q.all ? -1 : (long)g.q.n;
-        take(*head, head_cand, head_done, limit, g.iv.tid, true, seen, ts, sharded ? &head_skip : nullptr);
-        const bool truncated = head->truncated(cap_of(g));
-        if (!truncated || (limit >= 0 && ts->used >= (size_t)limit)) return;
-        const size_t done = head->size();
-        head.reset();
-        // the head was not enough: the whole interval, records already seen skipped
-        const RecSet whole = fetch_set(g.iv.tid, g.iv.start, g.iv.end, SIZE_MAX);
-        std::vector<size_t> cand; candidates(whole, &cand);
-        std::vector<uint8_t> skip; if (sharded) skip_for(g, whole, cand, &skip);
-        size_t from = 0; while (from < cand.size() && cand[from] < done) from++;
-        take(whole, cand, from, limit, g.iv.tid, true, seen, ts, sharded ? &skip : nullptr);
-      };
-      // run_batch (reads_sampler/mod.rs:259-338).  The count-based schedule needs only the head of every interval: the heads of up to
-      // 8 consecutive intervals of one contig (32 when they are scans of a resident shard's digest) are fetched concurrently and decoded in ONE
-      // device round; the sampler's first-N logic
-      // then runs over them in interval order.  An interval its head does not satisfy is finished sequentially before the
-      // following ones are judged (their reads may already be taken by it), and the remaining heads are decoded again.
-      struct Pending { size_t gi; std::unique_ptr<RecSet> head; std::vector<size_t> cand; std::vector<uint8_t> skip; size_t n_first = 0; std::set<std::string> seen;
-          TakeState ts; };
-      for (size_t mi = 0; mi < mine.size();) {
-        const G& g0 = grouped[mine[mi]];
-        size_t mj = mi + 1;
-        // (resident: a head is a scan of the digest — more intervals per device round)
-        if (!g0.q.all) while (mj < mine.size() && mj - mi < (resident_mode ? 32u : 8u) && !grouped[mine[mj]].q.all
-            && grouped[mine[mj]].iv.tid == g0.iv.tid) mj++;
-        std::vector<std::future<std::unique_ptr<RecSet>>> futs;
-        // (resident: a scan of the digest, no fetch to overlap)
-        for (size_t k = mi; k < mj; k++) futs.push_back(std::async(resident_mode ? std::launch::deferred : std::launch::async, head_of, mine[k]));
-        std::vector<Pending> pend(mj - mi);
-        for (size_t k = mi; k < mj; k++) {
-          Pending& P = pend[k - mi]; P.gi = mine[k];
-          { auto t_f = std::chrono::steady_clock::now(); P.head = futs[k - mi].get(); g_sample_times.fetch_ms += ms_since(t_f); }
-          candidates(*P.head, &P.cand); if (sharded) skip_for(grouped[P.gi], *P.head, P.cand, &P.skip);
-          const G& g = grouped[P.gi];
-          P.n_first = g.q.all ? 0 : std::min(P.cand.size(), std::max<size_t>(256, 2 * g.q.n));
-        }
-        if (g0.q.all) { finish_interval(g0, pend[0].head, pend[0].cand, 0, pend[0].skip, &pend[0].seen, &pend[0].ts);
-          batch_counts[g0.iv.tid] += pend[0].ts.n_reads_out;
-            mi = mj; continue; }
-        for (size_t k0 = 0; k0 < pend.size();) {
-          std::vector<std::pair<const RecSet*, size_t>> recs; std::vector<size_t> at(pend.size() + 1, 0);
-          for (size_t k = k0; k < pend.size(); k++) { at[k] = recs.size();
-              for (size_t i = 0; i < pend[k].n_first; i++) recs.push_back({pend[k].head.get(), pend[k].cand[i]}); }
-          at[pend.size()] = recs.size();
-          std::vector<uint32_t> nv;
-          auto t_d = std::chrono::steady_clock::now();
-          sample_round(recs, g0.iv.tid, true, &nv);
-          g_sample_times.device_ms += ms_since(t_d); g_sample_times.rounds++; g_sample_times.reads += recs.size();
-          auto t_h = std::chrono::steady_clock::now();
-          std::vector<uint8_t> mask(recs.size(), 0);
-          size_t unsatisfied = pend.size();
-          for (size_t k = k0; k < pend.size(); k++) {
-            Pending& P = pend[k]; const G& g = grouped[P.gi];
-            decide(*P.head, P.cand, 0, P.n_first, nv.data() + at[k], (long)g.q.n, &P.seen, &P.ts, sharded ? &P.skip : nullptr, mask.data() + at[k]);
-            const bool more = P.n_first < P.cand.size() || P.head->truncated(cap_of(g));
-            if (P.ts.used < g.q.n && more) { unsatisfied = k; break; }   // the judgement of the later heads waits for this interval
-          }
-          g_sample_times.decide_ms += ms_since(t_h);
-          t_d = std::chrono::steady_clock::now();
-          must(ctx, mkp_internal_sample_take(ctx, mask));
-          g_sample_times.device_ms += ms_since(t_d);
-          if (unsatisfied == pend.size()) break;
-          Pending& P = pend[unsatisfied];
-          finish_interval(grouped[P.gi], P.head, P.cand, P.n_first, P.skip, &P.seen, &P.ts);
-          k0 = unsatisfied + 1;
-        }
-        for (auto& P : pend) batch_counts[grouped[P.gi].iv.tid] += P.ts.n_reads_out;
-        mi = mj;
+    }
+    return skip;
+  }
+  // the rest of an interval after its head (or all of it in full-data mode): sequential device rounds
+  void finish_interval(const G& g, Fetched& head, size_t head_done, IntervalState* st) {
+    const long limit = g.q.all ? -1 : (long)g.q.n;
+    take(head, head_done, limit, g.iv.tid, true, st);
+    if (!head.set.truncated(cap_of(g)) || (limit >= 0 && st->used >= (size_t)limit)) return;
+    const size_t done = head.set.size();
+    head.set = RecSet();
+    // the head was not enough: the whole interval, records already seen skipped
+    const Fetched whole = with_candidates(fetch(g.iv.tid, g.iv.start, g.iv.end, SIZE_MAX), &g);
+    size_t from = 0; while (from < whole.idx.size() && whole.idx[from] < done) from++;
+    take(whole, from, limit, g.iv.tid, true, st);
+  }
+  // intervals this rank samples, in order
+  std::vector<const G*> my_intervals(const std::vector<G>& grouped) const {
+    std::vector<const G*> mine;
+    for (const G& g : grouped) {
+      if (bf && !bf->overlaps(g.iv.tid, g.iv.start, g.iv.end)) continue;
+      // owner of the interval: contiguous runs of the sampling grid by base pairs (as the pileup shards are dealt)
+      if (sharded && grid.owner(g.iv, a.world) != a.rank) continue;
+      mine.push_back(&g);
+    }
+    return mine;
+  }
+  struct Pending { const G* g; Fetched head; size_t n_first = 0; IntervalState st; };
+  // the heads of the intervals gs[0, n), fetched concurrently (the head of the next one is fetched while the current one is looked at)
+  std::vector<Pending> fetch_heads(const G* const* gs, size_t n) {
+    std::vector<std::future<RecSet>> futs;
+    // (resident: a scan of the digest, no fetch to overlap)
+    for (size_t k = 0; k < n; k++) { const G* g = gs[k]; futs.push_back(std::async(resident_mode ? std::launch::deferred : std::launch::async,
+        [this, g]() { return fetch(g->iv.tid, g->iv.start, g->iv.end, cap_of(*g)); })); }
+    std::vector<Pending> pend(n);
+    for (size_t k = 0; k < n; k++) {
+      Pending& P = pend[k]; P.g = gs[k];
+      auto t_f = std::chrono::steady_clock::now(); RecSet set = futs[k].get(); g_sample_times.fetch_ms += ms_since(t_f);
+      P.head = with_candidates(std::move(set), P.g);
+      P.n_first = P.g->q.all ? 0 : std::min(P.head.idx.size(), std::max<size_t>(256, 2 * P.g->q.n));
+    }
+    return pend;
+  }
+  // The count-based schedule needs only the head of every interval: the heads of consecutive intervals of one contig are decoded in ONE
+  // device round; the sampler's first-N logic then runs over them in interval order.  An interval its head does not satisfy is finished
+  // sequentially before the following ones are judged (their reads may already be taken by it), and the remaining heads are decoded again.
+  void judge_heads(std::vector<Pending>& pend) {
+    const uint32_t tid = pend[0].g->iv.tid;
+    for (size_t k0 = 0; k0 < pend.size();) {
+      Which recs; std::vector<size_t> at(pend.size() + 1, 0);
+      for (size_t k = k0; k < pend.size(); k++) { at[k] = recs.size();
+          for (size_t i = 0; i < pend[k].n_first; i++) recs.push_back({&pend[k].head.set, pend[k].head.idx[i]}); }
+      at[pend.size()] = recs.size();
+      std::vector<uint32_t> nv;
+      auto t_d = std::chrono::steady_clock::now();
+      device_round(recs, tid, true, &nv);
+      g_sample_times.device_ms += ms_since(t_d); g_sample_times.rounds++; g_sample_times.reads += recs.size();
+      auto t_h = std::chrono::steady_clock::now();
+      std::vector<uint8_t> mask(recs.size(), 0);
+      size_t unsatisfied = pend.size();
+      for (size_t k = k0; k < pend.size(); k++) {
+        Pending& P = pend[k]; const G& g = *P.g;
+        verdict(P.head, 0, P.n_first, nv.data() + at[k], (long)g.q.n, &P.st, mask.data() + at[k]);
+        const bool more = P.n_first < P.head.idx.size() || P.head.set.truncated(cap_of(g));
+        if (P.st.used < g.q.n && more) { unsatisfied = k; break; }   // the judgement of the later heads waits for this interval
       }
-      for (auto& kv : batch_counts) sampled_so_far[kv.first] += kv.second;
+      g_sample_times.decide_ms += ms_since(t_h);
+      t_d = std::chrono::steady_clock::now();
+      must(ctx, mkp_internal_sample_take(ctx, mask));
+      g_sample_times.device_ms += ms_since(t_d);
+      if (unsatisfied == pend.size()) break;
+      Pending& P = pend[unsatisfied];
+      finish_interval(*P.g, P.head, P.n_first, &P.st);
+      k0 = unsatisfied + 1;
     }
   }
+  // run_batch (reads_sampler/mod.rs:259-338) over the grouped intervals of one super batch: the heads of up to 8 consecutive intervals of one
+  // contig (32 when they are scans of a resident shard's digest) go through fetch_heads / judge_heads together; an interval that takes all
+  // of its reads goes alone
+  void run_super_batch(const std::vector<G>& grouped) {
+    std::map<uint32_t, size_t> batch_counts;
+    const std::vector<const G*> mine = my_intervals(grouped);
+    for (size_t mi = 0; mi < mine.size();) {
+      const G& g0 = *mine[mi];
+      size_t mj = mi + 1;
+      // (resident: a head is a scan of the digest — more intervals per device round)
+      if (!g0.q.all) while (mj < mine.size() && mj - mi < (resident_mode ? 32u : 8u) && !mine[mj]->q.all && mine[mj]->iv.tid == g0.iv.tid) mj++;
+      std::vector<Pending> pend = fetch_heads(&mine[mi], mj - mi);
+      if (g0.q.all) finish_interval(g0, pend[0].head, 0, &pend[0].st);
+      else judge_heads(pend);
+      for (auto& P : pend) batch_counts[P.g->iv.tid] += P.st.used;
+      mi = mj;
+    }
+    for (auto& kv : batch_counts) sampled_so_far[kv.first] += kv.second;
+  }
+
+  // ---- the reads without a schedule
   // reads_sampler/mod.rs:89-125 (rank-sharded: rank 0 takes the unmapped reads)
-  if ((sched_unmapped || taken.size() < 100) && !only_mapped && a.rank == 0) {
-    RecSet batch; batch.b.reset(new BamBatch()); bam.fetch_unmapped(batch.b.get());
-    std::vector<size_t> cand; candidates(batch, &cand);
-    long limit;
-    if (!a.have_frac) limit = (long)(a.num_reads > taken.size() ? a.num_reads - taken.size() : 0);
-    else if (a.sampling_frac >= 1.0) limit = -1;
-    else limit = -1;
+  void unmapped_leg() {
+    if (only_mapped || a.rank != 0) return;
+    RecSet set; set.b.reset(new BamBatch()); bam.fetch_unmapped(set.b.get());
+    const Fetched F = with_candidates(std::move(set));
+    const long limit = a.have_frac ? -1 : (long)(a.num_reads > taken.size() ? a.num_reads - taken.size() : 0);
     // RecordSampler::new_from_options (record_sampler.rs:51-61): a fraction < 1 is a Bernoulli draw per record from StdRng — seeded by
     // --seed, else from entropy (no two runs of the reference agree: refused, --seed makes it a function of the input)
     const bool draws = a.have_frac && a.sampling_frac < 1.0;
-    if (draws && !cand.empty() && !a.have_seed) throw Error(MKP_E_UNSUPPORTED,
+    if (draws && !F.idx.empty() && !a.have_seed) throw Error(MKP_E_UNSUPPORTED,
         "unmapped-read sampling with --sampling-frac < 1 draws from an entropy-seeded rand::StdRng (record_sampler.rs:29-38): give --seed");
     SeededSampler rng(a.seed);
-    std::set<std::string> seen; TakeState ts; take(batch, cand, 0, limit, 0, false, &seen, &ts, nullptr, draws ? &rng : nullptr, a.sampling_frac);
+    IntervalState st;
+    take(F, 0, limit, 0, false, &st, draws ? Draws{&rng, a.sampling_frac} : Draws());
   }
+  // The sampler of a BAM WITHOUT an index (reads_sampler/mod.rs:129-158; `bam::IndexedReader::from_path(..).is_ok()` decides, so an index
+  // ignored by `extract calls --ignore-index` still counts as one): no schedule — one pass over the file in file order, mapped and unmapped
+  // records alike, under RecordSampler::new_from_options (record_sampler.rs:51-61): the first --num-reads records that yield values, or with
+  // --sampling-frac one `gen_bool` per record the tag iterator yields (StdRng, --seed).  A region is an error there, as it is here.
+  // Records go to the sampling kernels contig by contig (a round has one reference window and one BED mask); the sampler's state — reads
+  // used, names seen — runs across the whole file: it is `take` with one IntervalState for the file (so its `seen` equals `taken` at every
+  // step), no skip list, and the draws attached on every contig.
+  void serial_pass(const RegionSpec* region) {
+    if (region) throw Error(MKP_E_INVALID, "cannot use region without indexed BAM");
+    const bool draws = a.have_frac && a.sampling_frac < 1.0;
+    if (a.have_frac && a.sampling_frac > 1.0) throw Error(MKP_E_INVALID, "sample fraction must be <= 1");
+    if (draws && !a.have_seed) throw Error(MKP_E_UNSUPPORTED,
+        "--sampling-frac < 1 on a BAM without an index draws from an entropy-seeded rand::StdRng (record_sampler.rs:29-38): give --seed");
+    // a draw is taken for every record whose tags parse and hold a position, whether or not a value survives the filters; the kernels report
+    // surviving values only — the two coincide while nothing can remove a record's every position
+    if (draws && (only_mapped || bf || !a.edge_filter.empty())) throw Error(MKP_E_UNSUPPORTED,
+        "--sampling-frac < 1 on a BAM without an index together with --only-mapped / --include-bed / --edge-filter: which records consume a draw is not reproduced");
+    SeededSampler rng(a.seed);
+    const Draws d = draws ? Draws{&rng, a.sampling_frac} : Draws();
+    const long limit = a.have_frac ? -1 : (long)a.num_reads;
+    IntervalState st;
+    auto more = [&]() { return limit < 0 || st.used < (size_t)limit; };   // (nothing is fetched once the limit is reached)
+    for (size_t t = 0; t < bam.ref_names.size() && more(); t++) {
+      RecSet set; set.b.reset(new BamBatch()); bam.fetch((uint32_t)t, 0, std::max<uint32_t>(bam.ref_lens[t], 1u), set.b.get());
+      take(with_candidates(std::move(set)), 0, limit, (uint32_t)t, true, &st, d);
+    }
+    if (more()) { RecSet set; set.b.reset(new BamBatch()); bam.fetch_unmapped(set.b.get());
+      take(with_candidates(std::move(set)), 0, limit, 0, false, &st, d); }
+  }
+};
+
+// validate, build the quotas, then run the sampler's stages for every super batch
+void sample_probabilities(mkp_ctx* ctx, const BamSource& bam, const Args& a, const RegionSpec* region, const BedFilter* bf,
+    const ResidentOf& resident_of = ResidentOf()) {
+  const bool only_mapped = !a.include_unmapped, sharded = a.world > 1;
+  if (resident_of && (!only_mapped || sharded)) throw Error(MKP_E_INVALID, "internal: resident sampling needs mapped-only, single-rank sampling");
+  ThresholdSampler sampler(ctx, bam, a, bf, resident_of);
+  if (a.serial_sampler) { sampler.serial_pass(region); return; }
+  if (sharded && !(a.have_frac && a.sampling_frac >= 1.0)) throw Error(MKP_E_UNSUPPORTED,
+      "rank-sharded threshold sampling needs the full-data mode (-f 1.0): the count-based schedule carries quotas from interval to interval");
+  const IdxStats st = idxstats(bam, region, bf);
+  if ((only_mapped ? st.mapped : st.mapped + st.unmapped) == 0) throw Error(MKP_E_THRESHOLD, "zero reads found in bam index");
+  if (a.have_frac && a.sampling_frac > 1.0) throw Error(MKP_E_INVALID, "sample fraction must be <= 1");
+  const std::map<uint32_t, Quota> quota = a.have_frac ? quota_from_sample_frac(st, a.sampling_frac) : num_reads_quotas(st, a.num_reads, !only_mapped);
+  const size_t batch_size = (size_t)floorf((float)a.threads * 1.5f);
+  std::vector<Contig> contigs; for (auto& c : targets(bam, region)) if (quota.count(c.tid)) contigs.push_back(c);
+  std::map<uint32_t, uint32_t> contig_size; for (auto& c : contigs) contig_size[c.tid] = c.length;
+  sampler.grid = SamplingGrid(contigs);
+  for (const std::vector<Iv>& all : sampling_super_batches(contigs, a.sampling_interval_size, batch_size))
+    sampler.run_super_batch(group_super_batch(all, contig_size, quota, sampler.sampled_so_far));
+  sampler.unmapped_leg();
 }
 
 // Full-data mode (`-f 1.0`, thresholds.rs:121-159) over shards that are resident in HBM.  sample_probabilities' schedule degenerates there
@@ -609,11 +583,8 @@ void sample_probabilities(mkp_ctx* ctx, const BamSource& bam, const Args& a, con
 // contig belongs to the first one (`own_from`: the end of the previous shard's fetch), so the union over the shards — of one rank or of
 // all ranks — is the single-rank sample; names seen before are skipped as the reference's Moniod keeps the first occurrence of a read id.
 struct FullShard { uint32_t tid; int64_t own_from, ext_lo, ext_hi; std::function<const ShardHost*()> bind; };
-struct NameKey { uint64_t a, b; bool operator==(const NameKey& o) const { return a == o.a && b == o.b; } };
-struct NameKeyHash { size_t operator()(const NameKey& k) const { return (size_t)(k.a ^ (k.b * 0x9e3779b97f4a7c15ull)); } };
 void sample_resident_full(mkp_ctx* ctx, const BamSource& bam, const BedFilter* bf, std::vector<FullShard>& shards) {
-  mkp_internal_bedmask_reset(ctx);
-  struct MaskSession { mkp_ctx* c; ~MaskSession() { mkp_internal_bedmask_reset(c); } } mask_session{ctx};
+  MaskSession mask_session(ctx);
   BedMasks bedmask_for{bf, bam, {}};
   std::unordered_set<NameKey, NameKeyHash> taken;
   for (auto& fs : shards) {
@@ -621,14 +592,9 @@ void sample_resident_full(mkp_ctx* ctx, const BamSource& bam, const BedFilter* b
     const ShardHost* S = fs.bind();
     g_sample_times.fetch_ms += ms_since(t_f);
     if (!S || (int32_t)fs.tid != S->tid) throw Error(MKP_E_INVALID, "internal: resident sampling outside the ingested contigs");
-    const size_t n = S->hdr.size(), n_so = S->so_hdr.size();
-    auto owned = [&](const MkpReadHdr& h) { const int64_t pos = h.ref_start, end = std::max(h.ref_end, h.ref_start + 1);
-      return pos >= fs.own_from && pos < fs.ext_hi && end > fs.ext_lo; };
-    std::vector<uint32_t> ids; ids.reserve(n + n_so);
-    for (size_t i = 0; i < n; i++) if (owned(S->hdr[i])) ids.push_back((uint32_t)i);
-    { bool any_so = false; for (size_t k = 0; k < n_so; k++) if (owned(S->so_hdr[k])) { ids.push_back((uint32_t)(n + k)); any_so = true; }
-      if (any_so) { auto wi = [&](uint32_t k) { return k < n ? S->dev_win_idx[k] : S->so_win_idx[k - n]; };
-        std::stable_sort(ids.begin(), ids.end(), [&](uint32_t x, uint32_t y) { return wi(x) < wi(y); }); } }
+    const std::vector<uint32_t> ids = resident_ids(*S, 0, S->hdr.size(), [&](const MkpReadHdr& h) {
+      const int64_t pos = h.ref_start, end = std::max(h.ref_end, h.ref_start + 1);
+      return pos >= fs.own_from && pos < fs.ext_hi && end > fs.ext_lo; });
     const uint8_t* mask = bedmask_for(fs.tid);
     for (size_t at = 0; at < ids.size();) {
       const size_t hi = std::min(ids.size(), at + ((size_t)1 << 18));
@@ -640,9 +606,7 @@ void sample_resident_full(mkp_ctx* ctx, const BamSource& bam, const BedFilter* b
       std::vector<uint8_t> take(hi - at, 0);
       for (size_t i = at; i < hi; i++) {
         if (nv[i - at] == 0) continue;   // a read that keeps no position is asked, not counted and not recorded
-        const uint32_t k = ids[i];
-          NameKey key{k < n ? S->name_hash[k] : S->so_name_hash[k - n], k < n ? S->dev_name_hash2[k] : S->so_name_hash2[k - n]};
-        if (taken.insert(key).second) take[i - at] = 1;
+        if (taken.insert(resident_name_key(*S, ids[i])).second) take[i - at] = 1;
       }
       g_sample_times.decide_ms += ms_since(t_h);
       t_d = std::chrono::steady_clock::now();
@@ -658,18 +622,16 @@ void thresholds_from_sample(mkp_ctx* ctx, float q, float thr[4], uint8_t has[4],
   std::vector<uint64_t> h0(65536), h1(65536);
   for (uint32_t b = 0; b < 4; b++) {
     thr[b] = 0.f; has[b] = 0;
-    int rc = mkp_histogram_get(ctx, b, 0, 0, h0.data()); if (rc != MKP_OK) throw Error(rc, mkp_last_error(ctx));
+    must(ctx, mkp_histogram_get(ctx, b, 0, 0, h0.data()));
     uint32_t bins[2]; uint64_t rk[2], n = 0;
-    rc = mkp_histogram_locate(h0.data(), q, bins, rk, &n);
+    int rc = mkp_histogram_locate(h0.data(), q, bins, rk, &n);
     if (n_out) n_out[b] = n;
     if (n == 0) continue;   // no calls on this base
     if (rc != MKP_OK) throw Error(MKP_E_THRESHOLD, "not enough datapoints, got " + std::to_string(n));
     float y[2];
     for (int k = 0; k < 2; k++) {
       if (k == 1 && bins[1] == bins[0] && rk[1] == rk[0]) { y[1] = y[0]; break; }
-      if (k == 0 || bins[1] != bins[0]) { rc = mkp_histogram_get(ctx, b, 1, bins[k], h1.data());
-        if (rc != MKP_OK) throw Error(rc, mkp_last_error(ctx));
-        }
+      if (k == 0 || bins[1] != bins[0]) must(ctx, mkp_histogram_get(ctx, b, 1, bins[k], h1.data()));
       rc = mkp_histogram_resolve(bins[k], h1.data(), rk[k], &y[k]);
         if (rc != MKP_OK) throw Error(MKP_E_THRESHOLD, "internal: histogram levels disagree");
     }
@@ -736,16 +698,8 @@ Options::Options(const Args& a, const BamSource& bam) {
   if (have_region) region = parse_region(a.region, bam);
   if (have_sregion) sregion = parse_region(a.sample_region, bam);
   memset(&kc, 0, sizeof(kc)); kc.max_depth = a.max_depth; kc.force_allow_implicit = a.force_allow;
-  if (!a.edge_filter.empty()) {  // parse_edge_filter_input (command_utils.rs:243-277)
-    kc.edge_filter = 1; kc.edge_inverted = a.invert_edge; size_t c = a.edge_filter.find(',');
-    if (c != std::string::npos) { kc.edge_start = (uint32_t)strtoul(a.edge_filter.c_str(), nullptr, 10);
-        kc.edge_end = (uint32_t)strtoul(a.edge_filter.c_str() + c + 1, nullptr, 10); }
-    else kc.edge_start = kc.edge_end = (uint32_t)strtoul(a.edge_filter.c_str(), nullptr, 10);
-  }
-  for (auto& raw : a.mod_thresholds) { size_t c = raw.find(':'); uint32_t code;
-      if (c == std::string::npos || raw.find(':', c + 1) != std::string::npos || !parse_code(raw.substr(0, c), &code)) throw Error(MKP_E_INVALID,
-      "encountered illegal per-mod threshold: " + raw);
-      per_mod.push_back({code, strtof(raw.c_str() + c + 1, nullptr)}); }
+  parse_edge_filter(a, &kc);
+  per_mod = parse_mod_thresholds(a.mod_thresholds);
   records = targets(bam, region_or_null());
   if (!a.include_bed.empty()) { std::map<std::string, uint32_t> c2t; for (auto& r : records) c2t[r.name] = r.tid;
     bed_store = BedFilter::load(a.include_bed, c2t);
@@ -1696,28 +1650,26 @@ void parse_args(int argc, const char* const* argv, Args* out, bool need_position
 extern "C" int mkp_internal_bedgraph_write(const char* dir, const char* prefix, int groupings, const char* const* motif_labels, uint32_t n_labels,
     const char* chrom, const mkp_rows* rows) {
   if (!dir || !chrom || !rows) return MKP_E_INVALID;
-  try {
+  return guarded_status([&]() {
     BedGraphOut bg; bg.dir = dir; bg.prefix = prefix ? prefix : ""; bg.groupings = groupings != 0;
     for (uint32_t k = 0; k < n_labels; k++) bg.labels.push_back(motif_labels[k]);
     bg.write(chrom, *rows); bg.finish();
     return MKP_OK;
-  } catch (const Error& e) { return e.status; } catch (const std::exception&) { return MKP_E_INVALID; }
+  });
 }
 
 // `modkit stats`, host halves (include/mkpileup.h): the regions BED and the table, no device involved
 extern "C" int mkp_host_parse_regions(const char* bed_path, const char* const* contig_names, uint32_t n_contigs, mkp_region_set** out, char* errbuf,
     size_t errbuf_len) {
-  auto fail = [&](int st, const std::string& m) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", m.c_str()); } return st; };
-  if (!bed_path || !out || (!contig_names && n_contigs)) return fail(MKP_E_INVALID, "bad argument");
+  if (!bed_path || !out || (!contig_names && n_contigs)) return fail_into(errbuf, errbuf_len, MKP_E_INVALID, "bad argument");
   *out = nullptr;
-  try {
+  return guarded_buf(errbuf, errbuf_len, [&]() {
     std::map<std::string, int> tids; for (uint32_t k = 0; k < n_contigs; k++) tids.emplace(contig_names[k], (int)k);
     std::unique_ptr<mkp_region_set> set(new mkp_region_set(parse_regions_bed(bed_path, [&](const std::string& chrom) { auto it = tids.find(chrom);
       return it == tids.end() ? -1 : it->second; })));
     *out = set.release();
     return MKP_OK;
-  } catch (const Error& e) { return fail(e.status, e.what()); }
-  catch (const std::exception& e) { return fail(MKP_E_INVALID, e.what()); }
+  });
 }
 extern "C" uint32_t mkp_region_set_size(const mkp_region_set* set) { return set ? (uint32_t)set->regions.size() : 0u; }
 extern "C" const mkp_region* mkp_region_set_regions(const mkp_region_set* set) { return set ? set->regions.data() : nullptr; }
@@ -1726,25 +1678,20 @@ extern "C" const char* mkp_region_set_name(const mkp_region_set* set, uint32_t i
 extern "C" void mkp_region_set_free(mkp_region_set* set) { delete set; }
 extern "C" int mkp_host_parse_localize_regions(const char* bed_path, const char* const* contig_names, uint32_t n_contigs, mkp_region_set** out,
     uint32_t* n_skipped, char* errbuf, size_t errbuf_len) {
-  auto fail = [&](int st, const std::string& m) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", m.c_str()); } return st; };
-  if (!bed_path || !out || (!contig_names && n_contigs)) return fail(MKP_E_INVALID, "bad argument");
+  if (!bed_path || !out || (!contig_names && n_contigs)) return fail_into(errbuf, errbuf_len, MKP_E_INVALID, "bad argument");
   *out = nullptr;
-  try {
+  return guarded_buf(errbuf, errbuf_len, [&]() {
     std::map<std::string, int> tids; for (uint32_t k = 0; k < n_contigs; k++) tids.emplace(contig_names[k], (int)k);
     std::unique_ptr<mkp_region_set> set(new mkp_region_set(parse_localize_regions_bed(bed_path, [&](const std::string& chrom) {
       auto it = tids.find(chrom); return it == tids.end() ? -1 : it->second; }, n_skipped)));
     *out = set.release();
     return MKP_OK;
-  } catch (const Error& e) { return fail(e.status, e.what()); }
-  catch (const std::exception& e) { return fail(MKP_E_INVALID, e.what()); }
+  });
 }
 extern "C" int mkp_host_parse_genome_sizes(const char* path, mkp_genome_sizes** out, char* errbuf, size_t errbuf_len) {
-  auto fail = [&](int st, const std::string& m) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", m.c_str()); } return st; };
-  if (!path || !out) return fail(MKP_E_INVALID, "bad argument");
+  if (!path || !out) return fail_into(errbuf, errbuf_len, MKP_E_INVALID, "bad argument");
   *out = nullptr;
-  try { *out = new mkp_genome_sizes(parse_genome_sizes(path)); return MKP_OK; }
-  catch (const Error& e) { return fail(e.status, e.what()); }
-  catch (const std::exception& e) { return fail(MKP_E_INVALID, e.what()); }
+  return guarded_buf(errbuf, errbuf_len, [&]() { *out = new mkp_genome_sizes(parse_genome_sizes(path)); return MKP_OK; });
 }
 extern "C" uint32_t mkp_genome_sizes_size(const mkp_genome_sizes* z) { return z ? (uint32_t)z->name.size() : 0u; }
 extern "C" const char* mkp_genome_sizes_name(const mkp_genome_sizes* z, uint32_t i) { return z && i < z->name.size() ? z->name[i].c_str() : nullptr; }
@@ -1752,68 +1699,47 @@ extern "C" uint64_t mkp_genome_sizes_length(const mkp_genome_sizes* z, uint32_t 
 extern "C" void mkp_genome_sizes_free(mkp_genome_sizes* z) { delete z; }
 extern "C" int mkp_host_localize_table(const mkp_localize_out* counts, const char* out_path) {
   if (!counts || !out_path) return MKP_E_INVALID;
-  try { write_text_file(out_path, localize_table_text(*counts, f32_display)); return MKP_OK; }
-  catch (const Error& e) { return e.status; } catch (const std::exception&) { return MKP_E_INVALID; }
+  return guarded_status([&]() { write_text_file(out_path, localize_table_text(*counts, f32_display)); return MKP_OK; });
 }
 extern "C" int mkp_host_stats_table(const mkp_region_set* set, const mkp_stats_out* counts, int with_header, const char* out_path) {
   if (!set || !counts || !out_path) return MKP_E_INVALID;
-  try { write_text_file(out_path, stats_table_text(*set, *counts, with_header != 0, f32_display)); return MKP_OK; }
-  catch (const Error& e) { return e.status; } catch (const std::exception&) { return MKP_E_INVALID; }
+  return guarded_status([&]() { write_text_file(out_path, stats_table_text(*set, *counts, with_header != 0, f32_display)); return MKP_OK; });
 }
 
 extern "C" int mkp_pileup_main(int argc, const char* const* argv, char* errbuf, size_t errbuf_len) {
-  auto fail = [&](int st, const std::string& m) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", m.c_str()); } return st; };
-  try {
-    Args a; parse_args(argc, argv, &a, true);
-    return run(a, nullptr, nullptr);
-  } catch (const Error& e) { return fail(e.status, e.what()); }
-  catch (const std::exception& e) { return fail(MKP_E_INVALID, e.what()); }
+  return guarded_buf(errbuf, errbuf_len, [&]() { Args a; parse_args(argc, argv, &a, true); return run(a, nullptr, nullptr); });
 }
 
 extern "C" int mkp_pileup_hemi_main(int argc, const char* const* argv, char* errbuf, size_t errbuf_len) {
-  auto fail = [&](int st, const std::string& m) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", m.c_str()); } return st; };
-  try {
-    Args a; parse_args(argc, argv, &a, true, true);
-    return run(a, nullptr, nullptr);
-  } catch (const Error& e) { return fail(e.status, e.what()); }
-  catch (const std::exception& e) { return fail(MKP_E_INVALID, e.what()); }
+  return guarded_buf(errbuf, errbuf_len, [&]() { Args a; parse_args(argc, argv, &a, true, true); return run(a, nullptr, nullptr); });
 }
 
 extern "C" int mkp_pileup_hemi_run(mkp_ctx* ctx, int argc, const char* const* argv, mkp_run_report* report) {
   if (!ctx) return MKP_E_INVALID;
-  try {
-    Args a; parse_args(argc, argv, &a, true, true);
-    return run(a, ctx, report);
-  } catch (const Error& e) { ctx->err = e.what(); return e.status; }
-  catch (const std::exception& e) { ctx->err = e.what(); return MKP_E_INVALID; }
+  return guarded_ctx(ctx, [&]() { Args a; parse_args(argc, argv, &a, true, true); return run(a, ctx, report); });
 }
 
 // The same subcommand on a context the caller owns: the last shard stays resident in HBM afterwards (mkp_shard_rerun
 // re-launches the kernels on it) and the per-stage wall times come back in `report`.
 extern "C" int mkp_pileup_run(mkp_ctx* ctx, int argc, const char* const* argv, mkp_run_report* report) {
   if (!ctx) return MKP_E_INVALID;
-  try {
+  return guarded_ctx(ctx, [&]() {
     Args a; parse_args(argc, argv, &a, true);
     if (a.plan_only) throw Error(MKP_E_INVALID, "--plan-only needs no context: use mkp_pileup_main");
     return run(a, ctx, report);
-  } catch (const Error& e) { ctx->err = e.what(); return e.status; }
-  catch (const std::exception& e) { ctx->err = e.what(); return MKP_E_INVALID; }
+  });
 }
 
 extern "C" int mkp_pileup_run_cb(mkp_ctx* ctx, int argc, const char* const* argv, mkp_threshold_fn fn, void* user, mkp_run_report* report) {
   if (!ctx) return MKP_E_INVALID;
-  try {
+  return guarded_ctx(ctx, [&]() {
     Args a; parse_args(argc, argv, &a, true);
     if (a.plan_only) throw Error(MKP_E_INVALID, "--plan-only needs no context: use mkp_pileup_main");
     a.thr_cb = fn; a.thr_cb_user = user;
     return run(a, ctx, report);
-  } catch (const Error& e) { ctx->err = e.what(); return e.status; }
-  catch (const std::exception& e) { ctx->err = e.what(); return MKP_E_INVALID; }
+  });
 }
 
-// get_threshold_from_options (command_utils.rs:74-134) as a call: per-base pass thresholds from the
-// reference's sampling schedule; argv takes the sampling flags of `modkit pileup`
-// (-n -f -p -t --sampling-interval-size --region --sample-region --include-bed --include-unmapped --edge-filter --ignore --preset).
 namespace {
 // the sampling half of get_threshold_from_options: parse the sampling flags, set the caller's collapse / edge filter, walk the schedule
 void sample_bam(mkp_ctx* ctx, const char* bam_path, int argc, const char* const* argv, float* q_out, const mkp_caller* thresholds = nullptr,
@@ -1828,11 +1754,7 @@ void sample_bam(mkp_ctx* ctx, const char* bam_path, int argc, const char* const*
   if (hs) sregion = parse_region(a.sample_region, bam);
   if (!(a.filter_percentile >= 0.0f) || a.filter_percentile > 1.0f) throw Error(MKP_E_INVALID, "filter percentile must be in [0, 1]");
   mkp_caller kc; memset(&kc, 0, sizeof(kc)); kc.max_depth = a.max_depth;
-  if (!a.edge_filter.empty()) { kc.edge_filter = 1; kc.edge_inverted = a.invert_edge; size_t c = a.edge_filter.find(',');
-      if (c != std::string::npos) { kc.edge_start = (uint32_t)strtoul(a.edge_filter.c_str(), nullptr, 10);
-      kc.edge_end = (uint32_t)strtoul(a.edge_filter.c_str() + c + 1, nullptr, 10);
-        } else kc.edge_start = kc.edge_end = (uint32_t)strtoul(a.edge_filter.c_str(), nullptr,
-      10); }
+  parse_edge_filter(a, &kc);
   if (a.preset == "traditional") { kc.numeric_mode = 2; kc.collapse_code = 'h'; }
   else if (!a.ignore.empty()) { uint32_t code; if (!parse_code(a.ignore, &code)) throw Error(MKP_E_INVALID, "failed to parse mod code " + a.ignore);
     kc.numeric_mode = 2;
@@ -1850,6 +1772,41 @@ void sample_bam(mkp_ctx* ctx, const char* bam_path, int argc, const char* const*
   sample_probabilities(ctx, bam, a, hs ? &sregion : (hr ? &region : nullptr), bf);
   if (q_out) *q_out = a.filter_percentile;
 }
+
+// The pass thresholds of `summary` and `extract calls` into the caller config: explicit --filter-threshold, else --no-filtering
+// (MultipleThresholdModCaller::new_passthrough: nothing is set), else the estimate from the sample that `argv`'s sampling flags describe.
+// `per_mod` must outlive `k`.
+void pass_thresholds(mkp_ctx* ctx, const Args& a, const char* bam_path, int argc, const char* const* argv,
+    const std::vector<mkp_mod_threshold>& per_mod, mkp_caller* k) {
+  if (!a.filter_threshold.empty()) parse_base_thresholds(a.filter_threshold, k);
+  else if (a.no_filtering) return;
+  else {
+    must(ctx, mkp_histogram_begin(ctx));
+    float q = 0.1f; sample_bam(ctx, bam_path, argc, argv, &q, nullptr, true);
+    float thr[4]; uint8_t has[4]; thresholds_from_sample(ctx, q, thr, has, false);
+    for (int b = 0; b < 4; b++) if (has[b]) { k->has_per_base[b] = 1; k->per_base_threshold[b] = thr[b]; }
+  }
+  k->per_mod = per_mod.data(); k->n_per_mod = (uint32_t)per_mod.size();
+}
+
+// The sampling subcommands' (`sample-probs`, `summary`) own flag names into the sampling flags of `modkit pileup`.  `own(flag)`: the
+// subcommand's exceptions — true where it has dealt with the flag (or throws).
+template <class Own> std::vector<std::string> sampling_subcommand_flags(int argc, const char* const* argv, Own own) {
+  std::vector<std::string> tr; bool only_mapped = false, have_i = false;
+  for (int i = 0; i < argc; i++) {
+    const std::string s = argv[i];
+    if (s == "-i" || s == "--interval-size") { tr.push_back("--sampling-interval-size"); have_i = true; }
+    else if (s == "--no-sampling") { tr.push_back("-f"); tr.push_back("1.0"); }
+    else if (s == "--only-mapped") only_mapped = true;
+    else if (s == "--include-bed" || s == "--include-positions") { only_mapped = true; tr.push_back(s); }
+    else if (own(s)) {}
+    else tr.push_back(s);
+  }
+  if (!have_i) { tr.push_back("--sampling-interval-size"); tr.push_back("1000000"); }
+  if (!only_mapped) tr.push_back("--include-unmapped");
+  return tr;
+}
+std::vector<const char*> c_strs(const std::vector<std::string>& v) { std::vector<const char*> out; for (auto& x : v) out.push_back(x.c_str()); return out; }
 }  // namespace
 
 // get_threshold_from_options (command_utils.rs:74-134) as a call: per-base pass thresholds from the
@@ -1857,18 +1814,14 @@ void sample_bam(mkp_ctx* ctx, const char* bam_path, int argc, const char* const*
 // (-n -f -p -t --sampling-interval-size --region --sample-region --include-bed --include-unmapped --edge-filter --ignore --preset).
 extern "C" int mkp_estimate_thresholds(mkp_ctx* ctx, const char* bam_path, int argc, const char* const* argv, float thr[4], uint8_t has[4]) {
   if (!ctx || !bam_path || !thr || !has) return MKP_E_INVALID;
-  try {
+  return guarded_ctx(ctx, [&]() {
     int rc = mkp_histogram_begin(ctx); if (rc != MKP_OK) return rc;
     float q = 0.1f; sample_bam(ctx, bam_path, argc, argv, &q);
     thresholds_from_sample(ctx, q, thr, has, false);
-    return MKP_OK;
-  } catch (const Error& e) { ctx->err = e.what(); return e.status; }
-  catch (const std::exception& e) { ctx->err = e.what(); return MKP_E_INVALID; }
+    return (int)MKP_OK;
+  });
 }
 
-// The sampling half alone, for multi-GPU runs: add this rank's share of the sample (argv carries --gpus-rank R --gpus-world W
-// next to the sampling flags; W > 1 needs -f 1.0) to the context's histograms.  The caller then sums mkp_histogram_get's arrays
-// over the ranks (RCCL all-reduce) and finishes with mkp_histogram_locate / _resolve / mkp_percentile_from_histogram.
 // `modkit sample-probs` (SampleModBaseProbs::run, src/commands.rs:680-887), the percentiles table: the schedule's sample, per canonical
 // base the requested percentiles of the argmax probabilities (Percentiles::new -> percentile_linear_interp).  The subcommand's own
 // flag names: -i is the sampling interval (default 1 000 000), unmapped reads are sampled unless --only-mapped (or --include-bed).
@@ -1876,21 +1829,12 @@ extern "C" int mkp_sample_probs(mkp_ctx* ctx, const char* bam_path, int argc, co
     uint32_t n_percentiles,
                                 float* values /* [4][n_percentiles], bases A,C,G,T */, uint8_t has[4], uint64_t n_values[4]) {
   if (!ctx || !bam_path || (!percentiles && n_percentiles) || !values || !has || !n_values) return MKP_E_INVALID;
-  try {
-    std::vector<std::string> tr; bool only_mapped = false, have_i = false;
-    for (int i = 0; i < argc; i++) {
-      const std::string s = argv[i];
-      if (s == "-i" || s == "--interval-size") { tr.push_back("--sampling-interval-size"); have_i = true; }
-      else if (s == "--no-sampling") { tr.push_back("-f"); tr.push_back("1.0"); }
-      else if (s == "--only-mapped") only_mapped = true;
-      else if (s == "--include-bed" || s == "--include-positions") { only_mapped = true; tr.push_back(s); }
-      else if (s == "-p" || s == "--percentiles" || s == "--filter-percentile") throw Error(MKP_E_INVALID,
+  return guarded_ctx(ctx, [&]() {
+    const std::vector<std::string> tr = sampling_subcommand_flags(argc, argv, [](const std::string& s) -> bool {
+      if (s == "-p" || s == "--percentiles" || s == "--filter-percentile") throw Error(MKP_E_INVALID,
           "percentiles are an argument of this call, not a flag");
-      else tr.push_back(s);
-    }
-    if (!have_i) { tr.push_back("--sampling-interval-size"); tr.push_back("1000000"); }
-    if (!only_mapped) tr.push_back("--include-unmapped");
-    std::vector<const char*> av; for (auto& x : tr) av.push_back(x.c_str());
+      return false; });
+    const std::vector<const char*> av = c_strs(tr);
     int rc = mkp_histogram_begin(ctx); if (rc != MKP_OK) return rc;
     sample_bam(ctx, bam_path, (int)av.size(), av.data(), nullptr, nullptr, true);
     for (int b = 0; b < 4; b++) { has[b] = 0; n_values[b] = 0; }
@@ -1903,9 +1847,8 @@ extern "C" int mkp_sample_probs(mkp_ctx* ctx, const char* bam_path, int argc, co
     }
     if (n_percentiles == 0) { float thr[4]; uint64_t n[4] = {0, 0, 0, 0}; try { thresholds_from_sample(ctx, 0.5f, thr, has, false, n);
         } catch (const Error&) {} for (int b = 0; b < 4; b++) n_values[b] = n[b]; }
-    return MKP_OK;
-  } catch (const Error& e) { ctx->err = e.what(); return e.status; }
-  catch (const std::exception& e) { ctx->err = e.what(); return MKP_E_INVALID; }
+    return (int)MKP_OK;
+  });
 }
 
 // `modkit summary` (ModSummarize::run, src/commands.rs:1035-1189): ModSummary as counts.  Two walks of the same sampling schedule on the
@@ -1914,37 +1857,13 @@ extern "C" int mkp_sample_probs(mkp_ctx* ctx, const char* bam_path, int argc, co
 extern "C" int mkp_summary(mkp_ctx* ctx, const char* bam_path, int argc, const char* const* argv, mkp_summary_out* out) {
   if (!ctx || !bam_path || !out) return MKP_E_INVALID;
   struct ModeGuard { mkp_ctx* c; ~ModeGuard() { c->summary_mode = false; } } guard{ctx};
-  try {
-    std::vector<std::string> tr; bool only_mapped = false, have_i = false;
-    for (int i = 0; i < argc; i++) {
-      const std::string s = argv[i];
-      if (s == "-i" || s == "--interval-size") { tr.push_back("--sampling-interval-size"); have_i = true; }
-      else if (s == "--no-sampling") { tr.push_back("-f"); tr.push_back("1.0"); }
-      else if (s == "--only-mapped") only_mapped = true;
-      else if (s == "--include-bed" || s == "--include-positions") { only_mapped = true; tr.push_back(s); }
-      else if (s == "--tsv" || s == "--table") {}
-      else tr.push_back(s);
-    }
-    if (!have_i) { tr.push_back("--sampling-interval-size"); tr.push_back("1000000"); }
-    if (!only_mapped) tr.push_back("--include-unmapped");
-    std::vector<const char*> av; for (auto& x : tr) av.push_back(x.c_str());
+  return guarded_ctx(ctx, [&]() {
+    const std::vector<std::string> tr = sampling_subcommand_flags(argc, argv, [](const std::string& s) { return s == "--tsv" || s == "--table"; });
+    const std::vector<const char*> av = c_strs(tr);
     Args a; parse_args((int)av.size(), av.data(), &a, false);
     mkp_caller kt; memset(&kt, 0, sizeof(kt));
-    std::vector<mkp_mod_threshold> per_mod;
-    for (auto& raw : a.mod_thresholds) { size_t c = raw.find(':'); uint32_t code;
-        if (c == std::string::npos || raw.find(':', c + 1) != std::string::npos || !parse_code(raw.substr(0, c), &code)) throw Error(MKP_E_INVALID,
-        "encountered illegal per-mod threshold: " + raw);
-        per_mod.push_back({code, strtof(raw.c_str() + c + 1, nullptr)}); }
-    if (!a.filter_threshold.empty()) { parse_base_thresholds(a.filter_threshold, &kt); kt.per_mod = per_mod.data();
-      kt.n_per_mod = (uint32_t)per_mod.size(); }
-    else if (a.no_filtering) { /* MultipleThresholdModCaller::new_passthrough */ }
-    else {
-      int rc = mkp_histogram_begin(ctx); if (rc != MKP_OK) return rc;
-      float q = 0.1f; sample_bam(ctx, bam_path, (int)av.size(), av.data(), &q, nullptr, true);
-      float thr[4]; uint8_t has[4]; thresholds_from_sample(ctx, q, thr, has, false);
-      for (int b = 0; b < 4; b++) if (has[b]) { kt.has_per_base[b] = 1; kt.per_base_threshold[b] = thr[b]; }
-      kt.per_mod = per_mod.data(); kt.n_per_mod = (uint32_t)per_mod.size();
-    }
+    const std::vector<mkp_mod_threshold> per_mod = parse_mod_thresholds(a.mod_thresholds);
+    pass_thresholds(ctx, a, bam_path, (int)av.size(), av.data(), per_mod, &kt);
     ctx->summary_mode = true;
     int rc = mkp_internal_summary_begin(ctx); if (rc != MKP_OK) return rc;
     sample_bam(ctx, bam_path, (int)av.size(), av.data(), nullptr, &kt, true);
@@ -1969,23 +1888,23 @@ extern "C" int mkp_summary(mkp_ctx* ctx, const char* bam_path, int argc, const c
     out->n_rows = (uint32_t)ctx->h_sum_base.size(); out->base = ctx->h_sum_base.data(); out->code_repr = ctx->h_sum_code.data();
       out->pass_count = ctx->h_sum_pass.data();
         out->fail_count = ctx->h_sum_fail.data();
-    return MKP_OK;
-  } catch (const Error& e) { ctx->err = e.what(); return e.status; }
-  catch (const std::exception& e) { ctx->err = e.what(); return MKP_E_INVALID; }
+    return (int)MKP_OK;
+  });
 }
 
+// The sampling half alone, for multi-GPU runs: add this rank's share of the sample (argv carries --gpus-rank R --gpus-world W
+// next to the sampling flags; W > 1 needs -f 1.0) to the context's histograms.  The caller then sums mkp_histogram_get's arrays
+// over the ranks (RCCL all-reduce) and finishes with mkp_histogram_locate / _resolve / mkp_percentile_from_histogram.
 extern "C" int mkp_histogram_add_bam(mkp_ctx* ctx, const char* bam_path, int argc, const char* const* argv) {
   if (!ctx || !bam_path) return MKP_E_INVALID;
-  try { sample_bam(ctx, bam_path, argc, argv, nullptr); return MKP_OK; }
-  catch (const Error& e) { ctx->err = e.what(); return e.status; }
-  catch (const std::exception& e) { ctx->err = e.what(); return MKP_E_INVALID; }
+  return guarded_ctx(ctx, [&]() { sample_bam(ctx, bam_path, argc, argv, nullptr); return MKP_OK; });
 }
 
 // process_region_batch stand-in reading the BAM itself: an indexed BAM goes through the device ingest (compressed blocks up, records cut and
 // packed in HBM — what mkp_pileup_run does per shard), anything else through the host reader + packer
 extern "C" int mkp_process_region(mkp_ctx* ctx, const char* bam_path, const mkp_shard* shard, mkp_rows* out) {
   if (!ctx || !bam_path || !shard || !out) return MKP_E_INVALID;
-  try {
+  return guarded_ctx(ctx, [&]() {
     std::unique_ptr<BamSource> src = BamSource::open(bam_path, 0);
     if (src->indexed() && ctx->partition_tags.empty() && !Knobs().host_ingest && shard->tid >= 0 && shard->end > shard->start) {
       if (!ctx->ingest) { ctx->ingest = mkp_internal_ingest_create(ctx->device);
@@ -2002,8 +1921,7 @@ extern "C" int mkp_process_region(mkp_ctx* ctx, const char* bam_path, const mkp_
     std::vector<mkp_record> recs; for (auto& e : batch.recs) recs.push_back(batch.view(e));
     rc = mkp_shard_add_records(ctx, recs.data(), (uint32_t)recs.size()); if (rc != MKP_OK) return rc;
     return mkp_shard_run(ctx, out);
-  } catch (const Error& e) { ctx->err = e.what(); return e.status; }
-  catch (const std::exception& e) { ctx->err = e.what(); return MKP_E_INVALID; }
+  });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -2049,362 +1967,382 @@ std::string kmer_at(const char* seq, size_t n, size_t position, size_t size) {
   for (size_t off = 1; off <= after; off++) k.push_back(position + off < n ? seq[position + off] : '-');
   return k;
 }
+
+// ---- the stages of mkp_extract_calls_main
+
+// the subcommand's own flags; `rest`: everything else — the flags of the threshold estimate and the two positionals (parse_args)
+struct ExtractFlags {
+  std::string ref_path, exclude_bed; std::vector<std::string> motif_parts, rest; bool cpg = false, bgzf = false;
+  bool allow_np = false, mapped_only = false, pass_only = false, no_headers = false, stats = false, ignore_index = false, ignore_implicit = false;
+  size_t kmer = 5; int device = 0; long num_reads = -1;
+};
+ExtractFlags parse_extract_flags(int argc, const char* const* argv) {
+  ExtractFlags f;
+  for (int i = 0; i < argc; i++) {
+    const std::string s = argv[i];
+    auto val = [&]() { if (i + 1 >= argc) throw Error(MKP_E_INVALID, "missing value for " + s); return std::string(argv[++i]); };
+    if (s == "--ref" || s == "--reference") f.ref_path = val(); else if (s == "--allow-non-primary") f.allow_np = true;
+      else if (s == "--mapped-only") f.mapped_only = true;
+    else if (s == "--pass-only" || s == "--pass") f.pass_only = true; else if (s == "--no-headers") f.no_headers = true;
+      else if (s == "--kmer-size") f.kmer = std::stoul(val());
+    else if (s == "--force" || s == "--suppress-progress") {} else if (s == "--device") f.device = std::stoi(val());
+      else if (s == "--stats") f.stats = true;
+    else if (s == "--num-reads") f.num_reads = std::stol(val()); else if (s == "--ignore-index") f.ignore_index = true;
+    else if (s == "--ignore-implicit") f.ignore_implicit = true;
+    else if (s == "--exclude-bed" || s == "-v" || s == "--exclude-positions") f.exclude_bed = val();
+    else if (s == "--motif") { f.motif_parts.push_back(val()); f.motif_parts.push_back(val()); } else if (s == "--cpg") f.cpg = true;
+    else if (s == "--bgzf") f.bgzf = true; else if (s == "--out-threads") val();
+    else f.rest.push_back(s);
+  }
+  if (f.kmer == 0 || f.kmer > 50) throw Error(MKP_E_INVALID, "kmer size must be less than or equal to 50");
+  if (f.pass_only && std::find(f.rest.begin(), f.rest.end(), "--no-filtering") != f.rest.end()) throw Error(MKP_E_INVALID,
+      "the argument '--no-filtering' cannot be used with '--pass-only'");
+  return f;
+}
+
+BedFilter load_bed_for(const std::string& path, const BamData& bd) {
+  std::map<std::string, uint32_t> c2t; for (size_t t = 0; t < bd.ref_names.size(); t++) c2t[bd.ref_names[t]] = (uint32_t)t;
+  return BedFilter::load(path, c2t);
+}
+struct TempFile { std::string path; ~TempFile() { if (!path.empty()) unlink(path.c_str()); } };   // unlinked on every exit path
+// --motif / --cpg (load_regions, src/extract/util.rs:157-277): the include filter becomes the motif hits over every contig of the FASTA that
+// the header names — the whole sequence, lower case matching unless --mask — one position per hit and strand, intersected with the
+// --include-bed positions (`bed`) when both are given.  From there on it IS the include filter: rows, the estimate (handed over as a BED
+// file of its own, `tmp`), the schedule.
+BedFilter motif_include_filter(const ExtractFlags& f, bool mask, const BamData& bd, const Fasta& fasta, const BedFilter* bed, TempFile* tmp) {
+  if (f.ref_path.empty()) throw Error(MKP_E_INVALID, "--motif / --cpg need --ref");
+  std::vector<std::string> parts = f.motif_parts;   // RegexMotif::from_raw_parts (motif_bed.rs:152-195)
+  if (f.cpg) { bool has = false; for (size_t i = 0; i + 1 < parts.size(); i += 2) if (parts[i] == "CG" && parts[i + 1] == "0") has = true;
+    if (!has) { parts.push_back("CG"); parts.push_back("0"); } }
+  std::vector<Motif> motifs;
+  for (size_t i = 0; i + 1 < parts.size(); i += 2) motifs.push_back(Motif::parse(parts[i], std::stoul(parts[i + 1])));
+  BedFilter mf;
+  for (size_t t = 0; t < bd.ref_names.size(); t++) {
+    const FastaSeq* sq = fasta.get(bd.ref_names[t]); if (!sq) continue;
+    std::map<uint32_t, Rule> hits;
+    for (auto& m : motifs) motif_hits(sq->data(), sq->size(), m, 0, (uint32_t)t, bed, &hits, !mask);
+    auto& P = mf.pos[(uint32_t)t]; auto& N = mf.neg[(uint32_t)t];   // (a searched contig is in the filter even without a hit)
+    for (auto& kv : hits) { if (kv.second & R_POS) P.push_back({kv.first, (uint64_t)kv.first + 1});
+      if (kv.second & R_NEG) N.push_back({kv.first, (uint64_t)kv.first + 1}); }
+    merge_spans(P); merge_spans(N);
+  }
+  char tmpl[] = "/tmp/mkp_motif_bed_XXXXXX"; const int fd = mkstemp(tmpl);
+  if (fd < 0) throw Error(MKP_E_IO, "cannot create a temporary BED for the motif positions");
+  tmp->path = tmpl; FILE* bf_out = fdopen(fd, "w");
+  for (auto* mp : {&mf.pos, &mf.neg}) for (auto& kv : *mp) for (auto& x : kv.second)
+    fprintf(bf_out, "%s\t%llu\t%llu\t.\t0\t%c\n", bd.ref_names[kv.first].c_str(), (unsigned long long)x.s, (unsigned long long)x.e,
+        mp == &mf.pos ? '+' : '-');
+  fclose(bf_out);
+  return mf;
+}
+
+// the flags of the threshold estimate (get_threshold_from_options, command_utils.rs:74-134): calls without a reference position count
+// unless --mapped-only (ReferencePositionFilter::only_mapped_positions, src/extract/util.rs:39-41)
+std::vector<std::string> extract_estimate_flags(const ExtractFlags& f, const Args& a, const std::string& motif_bed_path, bool have_bed) {
+  std::vector<std::string> sf;
+  for (size_t i = 0; i < f.rest.size(); i++) {
+    if (f.rest[i] == a.in_bam || f.rest[i] == a.out_bed) continue;
+    // (the motif positions already hold the intersection with the BED: the estimate gets them as its only --include-bed)
+    if (!motif_bed_path.empty() && (f.rest[i] == "--include-bed" || f.rest[i] == "--include-positions")) { i++; continue; }
+    sf.push_back(f.rest[i]);
+  }
+  if (!motif_bed_path.empty()) { sf.push_back("--include-bed"); sf.push_back(motif_bed_path); }
+  // (--include-bed: "specifying include-only BED outputs only mapped sites", util.rs:136-142 — positions without a reference position do not count)
+  if (!f.mapped_only && !have_bed) sf.push_back("--include-unmapped");
+  return sf;
+}
+
+// What is decided before the first record: --include-bed (ReferencePositionFilter::keep, src/extract/util.rs:44-69), --region, --num-reads
+// (src/extract/util.rs:126-160, 329-575).  With an index (and without --ignore-index) the reference walks interval chunks of the targets:
+// --region then selects the records its fetches return — every record overlapping the region, once — where the serial scan looks at every
+// record of the file.  The reference's rows leave in the order its pool finishes the intervals; here in file order.  --num-reads: the
+// serial path's "first N records that reach process_record"; on an indexed BAM it follows the sampling schedule (iv_quota).
+struct ExtractPlan {
+  bool use_index = false, scheduled = false, remove_inferred = false, have_region = false, include_unmapped_reads = false;
+  int64_t reg_tid = -1, reg_s = 0, reg_e = 0;
+  // --num-reads with an index (run_extract_reads, src/extract/util.rs:329-470; subcommand.rs:662-683): SamplingSchedule::from_num_reads over the
+  // index counts; every interval of the feeder — threads * 1.5 groups of >= --interval-size bases per super batch — has a RecordSampler
+  // of its own (extract_interval_quotas).  An interval's records are the ones its fetch returns that do not start in front of the previous
+  // interval's end — in a sorted file: the records that start inside it (the first interval of a region also takes the records reaching
+  // into it) — and it takes the first that many whose process_record succeeds.  Then the records without coordinates, unless a region /
+  // --mapped-only excludes them: the first (N - used) that reach process_record.  Rows leave in interval order (the reference: in pool order).
+  std::map<uint32_t, std::vector<IvQuota>> iv_quota;
+};
+ExtractPlan plan_extract(const ExtractFlags& f, const Args& a, const BamData& bd, const BedFilter* bed) {
+  ExtractPlan p;
+  { FILE* probe = fopen((a.in_bam + ".bai").c_str(), "rb"); if (probe) { fclose(probe); p.use_index = !f.ignore_index; } }
+  p.scheduled = p.use_index && f.num_reads >= 0;
+  // --ignore-implicit: ReadBaseModProfile::remove_inferred runs in the reference's interval path only (src/extract/util.rs:413-419); its serial
+  // scan (no index, --ignore-index) takes the flag and never looks at it
+  p.remove_inferred = f.ignore_implicit && p.use_index;
+  p.have_region = !a.region.empty();
+  p.include_unmapped_reads = !p.have_region && !f.mapped_only && !bed;   // load_regions (util.rs:136-155)
+  if (!p.have_region && !p.scheduled) return p;
+  std::unique_ptr<BamSource> src = BamSource::open(a.in_bam, 0);
+  RegionSpec rg;
+  if (p.have_region) {
+    rg = parse_region(a.region, *src);
+    for (size_t t = 0; t < bd.ref_names.size(); t++) if (bd.ref_names[t] == rg.name) p.reg_tid = (int64_t)t;
+    p.reg_s = rg.start; p.reg_e = rg.end;
+  }
+  if (p.scheduled) {
+    const IdxStats st = idxstats(*src, p.have_region ? &rg : nullptr, bed);
+    const std::map<uint32_t, Quota> quota = num_reads_quotas(st, (size_t)f.num_reads, p.include_unmapped_reads);
+    const size_t batch_size = std::max<size_t>((size_t)floorf((float)a.threads * 1.5f), 1);
+    // (--include-bed: every run of BED spans is a reference record of its own — optimize_reference_records, util.rs:287-296)
+    std::vector<Contig> recs_t = targets(*src, p.have_region ? &rg : nullptr);
+    if (bed) recs_t = bed_contigs(*bed, recs_t, a.interval_size);
+    p.iv_quota = extract_interval_quotas(feeder_groups(recs_t, a.interval_size), batch_size, quota);
+  }
+  return p;
+}
+
+struct ExtractCounts { uint64_t n_used = 0, n_skipped = 0, n_failed = 0, n_rows = 0; };
+
+// The records of bd.recs[r0, r1) that go to the device (TrackingModRecordIter, mod_bam.rs:53-122, + process_records_to_chan's --mapped-only),
+// with their alignment ends (one past the last reference position; a record without reference span counts as one base)
+void select_records(const ExtractFlags& f, const ExtractPlan& p, const BamData& bd, const BamBatch& view, size_t r0, size_t r1,
+    std::vector<mkp_record>* recs, std::vector<int64_t>* ends, ExtractCounts* c) {
+  recs->clear(); ends->clear();
+  for (size_t i = r0; i < r1; i++) {
+    const mkp_record r = view.view(bd.recs[i]); const int64_t end = bd.recs[i].end;
+    // IndexedReader::fetch(tid, start, end): the records overlapping the region
+    if (p.use_index && p.have_region && (r.tid != p.reg_tid || (int64_t)r.pos >= p.reg_e || end <= p.reg_s)) continue;
+    if (p.scheduled && r.tid < 0) {   // the schedule's last leg: process_records_to_chan(.., only_mapped = false, allow_non_primary = false, ..)
+      if (!p.include_unmapped_reads) continue;
+      if (r.flag & (2048 | 256 | 1024)) { c->n_skipped++; continue; }
+    } else {
+      if ((r.flag & (2048 | 256 | 1024)) && !f.allow_np) { c->n_skipped++; continue; }
+    }
+    if (r.l_qseq <= 0) { c->n_failed++; continue; }
+    if ((r.flag & 4) && f.mapped_only && !p.scheduled) { c->n_skipped++; continue; }   // (the schedule's samplers never ask about mapping)
+    recs->push_back(r); ends->push_back(end);
+  }
+}
+
+// get_soft_clipped (read_ids_to_base_mod_probs.rs:803-824): the soft-clipped bases at either end of an aligned record, stored order; not
+// ok — process_record's own failure — when its CIGAR holds nothing else
+struct Clips { size_t start = 0, end = 0; bool ok = true; };
+uint32_t cigar_word(const mkp_record& r, uint32_t k) { uint32_t w; memcpy(&w, r.data + r.l_qname + 4 * (size_t)k, 4); return w; }
+Clips soft_clips(const mkp_record& r) {
+  Clips c; if (r.flag & 4) return c;
+  uint32_t k = 0; for (; k < r.n_cigar && (cigar_word(r, k) & 15u) == 4u; k++) c.start += cigar_word(r, k) >> 4;
+  if (k == r.n_cigar) { c.ok = false; return c; }
+  for (k = r.n_cigar; k-- > 0 && (cigar_word(r, k) & 15u) == 4u;) c.end += cigar_word(r, k) >> 4;
+  return c;
+}
+
+// --num-reads counts what reaches process_record: records whose tags parse and hold something (an unmapped record under --mapped-only
+// never gets that far: dropped in select_records).  Three ways of counting: a scheduled aligned record against its interval's sampler, a
+// scheduled record without coordinates against what the aligned ones left of N, any record of an unscheduled run against N.
+enum class Admit { Rows /* write its rows */, Silent /* dropped, counted nowhere */, Failed, Skipped };
+struct Admission {
+  const ExtractFlags& f; ExtractPlan& p; size_t aligned_used = 0; long n_sent = 0; bool done = false;   // done: no record after this one
+  Admit judge(const mkp_record& r, int64_t rend, const MkpReadHdr& h, const MkpReadOut& ro, const Clips& clips) {
+    const Admit not_offered = (h.flags & MKP_RF_BAD) ? Admit::Failed : Admit::Skipped;
+    if (p.scheduled && r.tid >= 0) {
+      auto qi = p.iv_quota.find((uint32_t)r.tid); if (qi == p.iv_quota.end() || qi->second.empty()) return Admit::Silent;
+      // the interval that takes the record: the first one (feeder order) whose fetch returns it and whose `cut` — the previous interval's
+      // end — does not lie behind its start: the first interval that ends behind the record's start, if the record reaches it at all
+      auto it = std::upper_bound(qi->second.begin(), qi->second.end(), (int64_t)r.pos,
+          [](int64_t pos, const IvQuota& q) { return pos < (int64_t)q.end; });
+      if (it == qi->second.end() || (int64_t)it->start >= rend) return Admit::Silent;
+      IvQuota& Q = *it;
+      if (Q.nr == -2) return Admit::Silent;                      // the schedule holds nothing for this contig
+      if (!ro.ok) return not_offered;                            // TrackingModRecordIter never offers it
+      if (Q.nr >= 0 && Q.used >= Q.nr) return Admit::Silent;     // RecordSampler::ask -> Done
+      if (!clips.ok) return Admit::Failed;                       // process_record's own failure: get_soft_clipped
+      Q.used++; aligned_used++;
+      if (f.mapped_only && (r.flag & 4)) return Admit::Silent;   // every row of an unmapped record lacks a reference position
+      return ro.n_events ? Admit::Rows : Admit::Silent;
+    }
+    const long n = !p.scheduled ? f.num_reads : f.num_reads > (long)aligned_used ? f.num_reads - (long)aligned_used : 0;
+    // (looked at after the record went to the writer: N = 0 lets one through)
+    if (ro.ok) { n_sent++; if (f.num_reads >= 0 && n_sent >= n) done = true; }
+    if (!ro.ok || !ro.n_events) return not_offered;
+    return clips.ok ? Admit::Rows : Admit::Failed;
+  }
+};
+
+// what the rows of a record are made from besides the record
+struct RowSource {
+  const ExtractFlags& f; const ExtractPlan& p; const BamData& bd; const Fasta& fasta; const BedFilter* bed; const BedFilter* exbed;
+  const std::vector<MkpSlot>& slots; const std::vector<MkpEvent>& ev; const std::vector<float>& vals;
+};
+// The rows of one admitted record (PositionModCalls::to_row, src/extract/writer.rs:46-132) appended to `text`: forward sequence, the CIGAR
+// walk to reference positions, the row filters, the text; *n_rows counts them.  True when the record is used: a call of it passed the position
+// filters (whether or not --ignore-implicit / --pass-only then left a row).
+bool record_rows(const RowSource& X, const mkp_record& r, const MkpReadHdr& h, const MkpReadOut& ro, const Clips& clips, std::string* text,
+    uint64_t* n_rows) {
+  static const char NT16[] = "=ACMGRSVTWYHKDBN";
+  const bool unmapped = (r.flag & 4) != 0, rev = (r.flag & 16) != 0, have_bed = X.bed != nullptr;
+  const size_t L = (size_t)r.l_qseq;
+  const uint8_t* sq = r.data + r.l_qname + 4 * (size_t)r.n_cigar; const uint8_t* ql = sq + (L + 1) / 2;
+  const size_t clip_start = rev ? clips.end : clips.start, clip_end = rev ? clips.start : clips.end;
+  auto within = [&](size_t qp) { return L >= clip_end && qp >= clip_start && qp < L - clip_end; };
+  // forward sequence and qualities
+  std::string fwd(L, 'N');
+  for (size_t k = 0; k < L; k++) { const uint8_t b = sq[k >> 1]; const char c = NT16[(k & 1) ? (b & 15) : (b >> 4)];
+    if (rev) fwd[L - 1 - k] = comp_char(c);
+    else fwd[k] = c;
+    }
+  const bool have_chrom = !unmapped && r.tid >= 0 && (size_t)r.tid < X.bd.ref_names.size();
+  const std::string chrom = have_chrom ? X.bd.ref_names[(size_t)r.tid] : std::string();
+  const FastaSeq* ref_seq = have_chrom ? X.fasta.get(chrom) : nullptr;
+  const bool primary_or_unmapped = r.flag == 0 || r.flag == 16 || r.flag == 4;
+  const std::string qname((const char*)r.data, r.l_qname ? (size_t)r.l_qname - 1 : 0);
+  // the record's calls come in stored order (ascending stored index): one CIGAR walk gives their reference positions
+  struct Row { size_t f; long ref; uint32_t info; float p; };
+  std::vector<Row> rows; rows.reserve(ro.n_events);
+  uint32_t ck = 0; size_t q_at = 0; long r_at = r.pos;   // op ck starts at stored index q_at / reference position r_at
+  for (uint32_t k = 0; k < ro.n_events; k++) {
+    const MkpEvent& e = X.ev[(size_t)h.event_off + k];
+    const size_t f = e.pos, q = rev ? L - 1 - f : f;
+    long ref = -1;
+    if (!unmapped) {
+      // an event behind the walk (the kernels emit a record's events in stored order; should that ever change, start over instead of
+      // underflowing)
+      if (q < q_at) { ck = 0; q_at = 0; r_at = r.pos; }
+      while (ck < r.n_cigar) {
+        const uint32_t w = cigar_word(r, ck), op = w & 15u, len = w >> 4;
+        const bool cq = op == 0 || op == 1 || op == 4 || op == 7 || op == 8, cr = op == 0 || op == 2 || op == 3 || op == 7 || op == 8;
+        if (cq && q < q_at + len) { if (op == 0 || op == 7 || op == 8) ref = r_at + (long)(q - q_at); break; }
+        if (cq) q_at += len;
+        if (cr) r_at += len;
+        ck++;
+      }
+    }
+    rows.push_back({f, ref, e.info, X.vals[(size_t)h.event_off + k]});
+  }
+  if (unmapped && rev) std::reverse(rows.begin(), rows.end());   // no alignment strand: ascending forward position
+  bool any = false;
+  for (const Row& w : rows) {
+    if ((X.f.mapped_only || have_bed) && (unmapped || w.ref < 0)) continue;   // filter_read_base_mod_probs (src/extract/util.rs:71-124)
+    // ... asked with the reference strand of the mod
+    if (have_bed && !X.bed->contains((uint32_t)r.tid, (uint64_t)w.ref, (((w.info >> 2) & 1u) != 0) != rev)) continue;
+    // --exclude-bed (load_regions, util.rs:177-187; ReferencePositionFilter::keep = include hit && !exclude hit): a row filter only
+    if (X.exbed && !unmapped && w.ref >= 0 && X.exbed->contains((uint32_t)r.tid, (uint64_t)w.ref, (((w.info >> 2) & 1u) != 0) != rev)) continue;
+    if (!primary_or_unmapped && !within(w.f)) continue;                   // iter_profiles (read_ids_to_base_mod_probs.rs:785-800)
+    any = true;
+    const uint32_t tb = w.info & 3u, sg = (w.info >> 2) & 1u, inferred = (w.info >> 3) & 1u, thr_cls = (w.info >> 4) & 15u,
+        arg_cls = (w.info >> 8) & 15u;
+    if (X.p.remove_inferred && inferred) continue;
+    const bool filtered = thr_cls == 0;
+    if (filtered && X.f.pass_only) continue;
+    std::string code = "-";
+    if (arg_cls >= 2) { const uint32_t cr = arg_cls - 2 < X.slots.size() ? X.slots[arg_cls - 2].code_repr : 0u;
+      code = (cr & 0x80000000u) ? std::to_string(cr & 0x7fffffffu) : std::string(1, (char)cr); }
+    std::string qk = kmer_at(fwd.data(), L, w.f, X.f.kmer);
+    if (sg) { std::string t; for (size_t k = qk.size(); k-- > 0;) t.push_back(qk[k] == '-' ? '-' : comp_char(qk[k])); qk.swap(t); }
+    std::string rk = ".";
+    if (w.ref >= 0 && ref_seq) rk = kmer_at(ref_seq->data(), ref_seq->size(), (size_t)w.ref, X.f.kmer);
+    const unsigned bq = ql[rev ? L - 1 - w.f : w.f];
+    char line[1200];
+    const int ln = snprintf(line, sizeof(line), "%s\t%zu\t%ld\t%s\t%c\t%c\t%c\t%zu\t%zu\t%zu\t%s\t%s\t%u\t%s\t%s\t%c\t%c\t%s\t%s\t%s\t%u\n",
+        qname.c_str(), w.f, w.ref >= 0 ? w.ref : -1L,
+             have_chrom ? chrom.c_str() : ".", sg ? '-' : '+', unmapped ? '.' : (rev ? '-' : '+'),
+                 unmapped ? '.' : ((sg != 0) != rev ? '-' : '+'), clip_start, clip_end, L,
+             f32_display(w.p).c_str(), code.c_str(), bq, rk.c_str(), qk.c_str(), "ACGT"[tb], "ACGT"[sg ? 3 - tb : tb],
+                 filtered ? "true" : "false", inferred ? "true" : "false",
+             (have_chrom && within(w.f)) ? "true" : "false", (unsigned)r.flag);
+    if (ln < 0 || (size_t)ln >= sizeof(line)) throw Error(MKP_E_UNSUPPORTED,
+        "extract calls: a row is longer than " + std::to_string(sizeof(line)) + " bytes (read or contig name of unusual length)");
+    text->append(line, (size_t)ln); (*n_rows)++;
+  }
+  return any;
+}
+}  // namespace
+
+namespace {
+// The table's sink: the output file (or stdout) as plain text, or — --bgzf (src/extract/subcommand.rs:629-660) — the same table as BGZF
+// blocks (SAM spec 4.1) cut at 0xff00 bytes, closed by the empty EOF block
+struct TableSink {
+  std::string path; bool bgzf; FILE* out; std::vector<uint8_t> pend, z;
+  TableSink(const std::string& p, bool bgzf_blocks) : path(p), bgzf(bgzf_blocks), out((p == "-" || p == "stdout") ? stdout : fopen(p.c_str(), "w+")) {
+    if (!out) throw Error(MKP_E_IO, "failed to make output file " + path); }
+  ~TableSink() { if (out && out != stdout) fclose(out); }
+  void write(const void* p, size_t n) { if (n && fwrite(p, 1, n, out) != n) throw Error(MKP_E_IO, "write error on " + path); }
+  void put(const char* p, size_t n) {
+    if (!bgzf) { write(p, n); return; }
+    pend.insert(pend.end(), (const uint8_t*)p, (const uint8_t*)p + n);
+    size_t at = 0; z.clear();
+    while (pend.size() - at >= MKP_BGZF_BLOCK) { bgzf_block(pend.data() + at, MKP_BGZF_BLOCK, &z); at += MKP_BGZF_BLOCK; }
+    pend.erase(pend.begin(), pend.begin() + (long)at);
+    write(z.data(), z.size());
+  }
+  void finish() {
+    if (!bgzf) return;
+    z.clear(); if (!pend.empty()) bgzf_block(pend.data(), pend.size(), &z);
+    static const uint8_t eof_block[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    z.insert(z.end(), eof_block, eof_block + 28);
+    write(z.data(), z.size());
+  }
+};
 }  // namespace
 
 extern "C" int mkp_extract_calls_main(int argc, const char* const* argv, char* errbuf, size_t errbuf_len) {
-  auto fail = [&](int st, const std::string& m) { if (errbuf && errbuf_len) { snprintf(errbuf, errbuf_len, "%s", m.c_str()); } return st; };
   mkp_ctx* ctx = nullptr;
   struct Guard { mkp_ctx** c; ~Guard() { if (*c) mkp_ctx_destroy(*c); } } guard{&ctx};
-  try {
-    std::string ref_path, exclude_bed; std::vector<std::string> motif_parts; bool cpg = false, bgzf = false;
-      bool allow_np = false, mapped_only = false, pass_only = false, no_headers = false, stats = false, ignore_index = false, ignore_implicit = false;
-      size_t kmer = 5; int device = 0; long num_reads = -1;
-    std::vector<std::string> rest;
-    for (int i = 0; i < argc; i++) {
-      const std::string s = argv[i];
-      auto val = [&]() { if (i + 1 >= argc) throw Error(MKP_E_INVALID, "missing value for " + s); return std::string(argv[++i]); };
-      if (s == "--ref" || s == "--reference") ref_path = val(); else if (s == "--allow-non-primary") allow_np = true;
-        else if (s == "--mapped-only") mapped_only = true;
-      else if (s == "--pass-only" || s == "--pass") pass_only = true; else if (s == "--no-headers") no_headers = true;
-        else if (s == "--kmer-size") kmer = std::stoul(val());
-      else if (s == "--force" || s == "--suppress-progress") {} else if (s == "--device") device = std::stoi(val());
-        else if (s == "--stats") stats = true;
-      else if (s == "--num-reads") num_reads = std::stol(val()); else if (s == "--ignore-index") ignore_index = true;
-      else if (s == "--ignore-implicit") ignore_implicit = true;
-      else if (s == "--exclude-bed" || s == "-v" || s == "--exclude-positions") exclude_bed = val();
-      else if (s == "--motif") { motif_parts.push_back(val()); motif_parts.push_back(val()); } else if (s == "--cpg") cpg = true;
-      else if (s == "--bgzf") bgzf = true; else if (s == "--out-threads") val();
-      else rest.push_back(s);
-    }
-    if (kmer == 0 || kmer > 50) throw Error(MKP_E_INVALID, "kmer size must be less than or equal to 50");
-    if (pass_only && std::find(rest.begin(), rest.end(), "--no-filtering") != rest.end()) throw Error(MKP_E_INVALID,
-        "the argument '--no-filtering' cannot be used with '--pass-only'");
-    std::vector<const char*> av; for (auto& x : rest) av.push_back(x.c_str());
+  return guarded_buf(errbuf, errbuf_len, [&]() {
+    const ExtractFlags f = parse_extract_flags(argc, argv);
+    const std::vector<const char*> av = c_strs(f.rest);
     Args a; parse_args((int)av.size(), av.data(), &a, true);
-    // the flags of the threshold estimate (get_threshold_from_options, command_utils.rs:74-134): calls without a reference position count
-    // unless --mapped-only (ReferencePositionFilter::only_mapped_positions, src/extract/util.rs:39-41)
     const BamData bd = load_bam(a.in_bam, 0, false);
-    Fasta fasta; if (!ref_path.empty()) fasta = Fasta::load(ref_path);
+    Fasta fasta; if (!f.ref_path.empty()) fasta = Fasta::load(f.ref_path);
+    // the include filter: --include-bed, or the motif positions (within the BED when both are given)
     BedFilter bed; bool have_bed = !a.include_bed.empty();
-    if (have_bed) { std::map<std::string, uint32_t> c2t; for (size_t t = 0; t < bd.ref_names.size(); t++) c2t[bd.ref_names[t]] = (uint32_t)t;
-      bed = BedFilter::load(a.include_bed, c2t); }
-    // --motif / --cpg (load_regions, src/extract/util.rs:157-277): the include filter becomes the motif hits over every contig of the FASTA that
-    // the header names — the whole sequence, lower case matching unless --mask — one position per hit and strand, intersected with the
-    // --include-bed positions when both are given.  From there on it IS the include filter: rows, the estimate (handed over as a BED file of
-    // its own), the schedule.
-    std::string motif_bed_path;
-    struct Unlink { std::string* p; ~Unlink() { if (!p->empty()) unlink(p->c_str()); } } unlink_motif_bed{&motif_bed_path};
-    if (cpg || !motif_parts.empty()) {
-      if (ref_path.empty()) throw Error(MKP_E_INVALID, "--motif / --cpg need --ref");
-      std::vector<std::string> parts = motif_parts;   // RegexMotif::from_raw_parts (motif_bed.rs:152-195)
-      if (cpg) { bool has = false; for (size_t i = 0; i + 1 < parts.size(); i += 2) if (parts[i] == "CG" && parts[i + 1] == "0") has = true;
-        if (!has) { parts.push_back("CG"); parts.push_back("0"); } }
-      std::vector<Motif> motifs;
-      for (size_t i = 0; i + 1 < parts.size(); i += 2) motifs.push_back(Motif::parse(parts[i], std::stoul(parts[i + 1])));
-      BedFilter mf;
-      for (size_t t = 0; t < bd.ref_names.size(); t++) {
-        const FastaSeq* sq = fasta.get(bd.ref_names[t]); if (!sq) continue;
-        std::map<uint32_t, Rule> hits;
-        for (auto& m : motifs) motif_hits(sq->data(), sq->size(), m, 0, (uint32_t)t, have_bed ? &bed : nullptr, &hits, !a.mask);
-        auto& P = mf.pos[(uint32_t)t]; auto& N = mf.neg[(uint32_t)t];   // (a searched contig is in the filter even without a hit)
-        for (auto& kv : hits) { if (kv.second & R_POS) P.push_back({kv.first, (uint64_t)kv.first + 1});
-          if (kv.second & R_NEG) N.push_back({kv.first, (uint64_t)kv.first + 1}); }
-        merge_spans(P); merge_spans(N);
-      }
-      bed = std::move(mf); have_bed = true;
-      char tmpl[] = "/tmp/mkp_motif_bed_XXXXXX"; const int fd = mkstemp(tmpl);
-      if (fd < 0) throw Error(MKP_E_IO, "cannot create a temporary BED for the motif positions");
-      motif_bed_path = tmpl; FILE* bf_out = fdopen(fd, "w");
-      for (auto* mp : {&bed.pos, &bed.neg}) for (auto& kv : *mp) for (auto& x : kv.second)
-        fprintf(bf_out, "%s\t%llu\t%llu\t.\t0\t%c\n", bd.ref_names[kv.first].c_str(), (unsigned long long)x.s, (unsigned long long)x.e,
-            mp == &bed.pos ? '+' : '-');
-      fclose(bf_out);
-    }
-    std::vector<std::string> sf;
-    for (size_t i = 0; i < rest.size(); i++) {
-      if (rest[i] == a.in_bam || rest[i] == a.out_bed) continue;
-      // (the motif positions already hold the intersection with the BED: the estimate gets them as its only --include-bed)
-      if (!motif_bed_path.empty() && (rest[i] == "--include-bed" || rest[i] == "--include-positions")) { i++; continue; }
-      sf.push_back(rest[i]);
-    }
-    if (!motif_bed_path.empty()) { sf.push_back("--include-bed"); sf.push_back(motif_bed_path); }
-    // (--include-bed: "specifying include-only BED outputs only mapped sites", util.rs:136-142 — positions without a reference position do not count)
-    if (!mapped_only && !have_bed) sf.push_back("--include-unmapped");
-    std::vector<const char*> sav; for (auto& x : sf) sav.push_back(x.c_str());
-    mkp_config cfg; memset(&cfg, 0, sizeof(cfg)); cfg.device = device;
+    if (have_bed) bed = load_bed_for(a.include_bed, bd);
+    TempFile motif_bed;
+    if (f.cpg || !f.motif_parts.empty()) { bed = motif_include_filter(f, a.mask, bd, fasta, have_bed ? &bed : nullptr, &motif_bed); have_bed = true; }
+    const std::vector<std::string> sf = extract_estimate_flags(f, a, motif_bed.path, have_bed);
+    const std::vector<const char*> sav = c_strs(sf);
+    // the device and its caller: thresholds, edge filter, --ignore
+    mkp_config cfg; memset(&cfg, 0, sizeof(cfg)); cfg.device = f.device;
     int rc = mkp_ctx_create(&cfg, &ctx);
     if (rc != MKP_OK) throw Error(rc, "no usable gfx950 device (libmkpileup has no CPU path)");
-    auto must = [&](int r) { if (r != MKP_OK) throw Error(r, mkp_last_error(ctx)); };
     mkp_caller kc; memset(&kc, 0, sizeof(kc)); kc.max_depth = a.max_depth;
-    std::vector<mkp_mod_threshold> per_mod;
-    for (auto& raw : a.mod_thresholds) { size_t c = raw.find(':'); uint32_t code;
-      if (c == std::string::npos || raw.find(':', c + 1) != std::string::npos || !parse_code(raw.substr(0, c), &code)) throw Error(MKP_E_INVALID,
-          "encountered illegal per-mod threshold: " + raw);
-      per_mod.push_back({code, strtof(raw.c_str() + c + 1, nullptr)}); }
-    if (!a.filter_threshold.empty()) { parse_base_thresholds(a.filter_threshold, &kc); kc.per_mod = per_mod.data();
-      kc.n_per_mod = (uint32_t)per_mod.size(); }
-    else if (a.no_filtering) { /* MultipleThresholdModCaller::new_passthrough */ }
-    else {
-      must(mkp_histogram_begin(ctx));
-      float q = 0.1f; sample_bam(ctx, a.in_bam.c_str(), (int)sav.size(), sav.data(), &q, nullptr, true);
-      float thr[4]; uint8_t has[4]; thresholds_from_sample(ctx, q, thr, has, false);
-      for (int b = 0; b < 4; b++) if (has[b]) { kc.has_per_base[b] = 1; kc.per_base_threshold[b] = thr[b]; }
-      kc.per_mod = per_mod.data(); kc.n_per_mod = (uint32_t)per_mod.size();
-    }
-    if (!a.edge_filter.empty()) { kc.edge_filter = 1; kc.edge_inverted = a.invert_edge; size_t c = a.edge_filter.find(',');
-      if (c != std::string::npos) { kc.edge_start = (uint32_t)strtoul(a.edge_filter.c_str(), nullptr, 10);
-        kc.edge_end = (uint32_t)strtoul(a.edge_filter.c_str() + c + 1, nullptr, 10); }
-      else kc.edge_start = kc.edge_end = (uint32_t)strtoul(a.edge_filter.c_str(), nullptr, 10); }
+    const std::vector<mkp_mod_threshold> per_mod = parse_mod_thresholds(a.mod_thresholds);
+    pass_thresholds(ctx, a, a.in_bam.c_str(), (int)sav.size(), sav.data(), per_mod, &kc);
+    parse_edge_filter(a, &kc);
     if (!a.ignore.empty()) { uint32_t code; if (!parse_code(a.ignore, &code)) throw Error(MKP_E_INVALID, "failed to parse mod code " + a.ignore);
       kc.numeric_mode = 2; kc.collapse_code = code; }
-    must(mkp_set_caller(ctx, &kc));
-    must(mkp_internal_set_extract(ctx, true));
-    // --include-bed (ReferencePositionFilter::keep, src/extract/util.rs:44-69), --region, --num-reads (src/extract/util.rs:126-160, 329-575).
-    // With an index (and without --ignore-index) the reference walks interval chunks of the targets: --region then selects the records its
-    // fetches return — every record overlapping the region, once — where the serial scan looks at every record of the file.  The reference's
-    // rows leave in the order its pool finishes the intervals; here in file order.  --num-reads: the serial path's "first N records that
-    // reach process_record"; on an indexed BAM it follows the sampling schedule (below).
-    // --exclude-bed (load_regions, util.rs:177-187; ReferencePositionFilter::keep = include hit && !exclude hit): a row filter only
-    BedFilter exbed; const bool have_ex = !exclude_bed.empty();
-    if (have_ex) { std::map<std::string, uint32_t> c2t; for (size_t t = 0; t < bd.ref_names.size(); t++) c2t[bd.ref_names[t]] = (uint32_t)t;
-      exbed = BedFilter::load(exclude_bed, c2t); }
-    bool use_index = false; { FILE* probe = fopen((a.in_bam + ".bai").c_str(), "rb"); if (probe) { fclose(probe); use_index = !ignore_index; } }
-    const bool scheduled = use_index && num_reads >= 0;
-    // --ignore-implicit: ReadBaseModProfile::remove_inferred runs in the reference's interval path only (src/extract/util.rs:413-419); its serial
-    // scan (no index, --ignore-index) takes the flag and never looks at it
-    const bool remove_inferred = ignore_implicit && use_index;
-    int64_t reg_tid = -1, reg_s = 0, reg_e = 0; const bool have_region = !a.region.empty();
-    if (have_region) {
-      std::unique_ptr<BamSource> src = BamSource::open(a.in_bam, 0); const RegionSpec rg = parse_region(a.region, *src);
-      for (size_t t = 0; t < bd.ref_names.size(); t++) if (bd.ref_names[t] == rg.name) reg_tid = (int64_t)t;
-      reg_s = rg.start; reg_e = rg.end;
-    }
-    // --num-reads with an index (run_extract_reads, src/extract/util.rs:329-470; subcommand.rs:662-683): SamplingSchedule::from_num_reads over the
-    // index counts; every interval of the feeder — threads * 1.5 groups of >= --interval-size bases per super batch — has a RecordSampler
-    // of its own: ceil(contig count * interval length / length of the whole super batch) records (get_record_sampler, sampling_schedule.rs:
-    // 417-438).  An interval's records are the ones its fetch returns that do not start in front of the previous interval's end — in a
-    // sorted file: the records that start inside it (the first interval of a region also takes the records reaching into it) — and it takes
-    // the first that many whose process_record succeeds.  Then the records without coordinates, unless a region / --mapped-only excludes
-    // them: the first (N - used) that reach process_record.  Rows leave in interval order (the reference: in pool order).
-    struct IvQuota { uint32_t start, end; long nr; long used; };   // nr == -2: the schedule holds nothing for the contig (never fetched)
-    std::map<uint32_t, std::vector<IvQuota>> iv_quota;              // per contig: the feeder's intervals, ascending and disjoint
-    const bool include_unmapped_reads = !have_region && !mapped_only && !have_bed;   // load_regions (util.rs:136-155)
-    size_t aligned_used = 0;
-    if (scheduled) {
-      std::unique_ptr<BamSource> src = BamSource::open(a.in_bam, 0);
-      RegionSpec rg; if (have_region) rg = parse_region(a.region, *src);
-      const IdxStats st = idxstats(*src, have_region ? &rg : nullptr, have_bed ? &bed : nullptr);
-      const std::map<uint32_t, Quota> quota = quota_from_num_reads(st, (size_t)num_reads, include_unmapped_reads);
-      const size_t batch_size = std::max<size_t>((size_t)floorf((float)a.threads * 1.5f), 1);
-      struct Iv { uint32_t tid, start, end; };
-      std::vector<std::vector<Iv>> groups;   // MultiChromCoordinates in feeder order (interval_chunks.rs:563-643)
-      { std::vector<Iv> g; uint32_t glen = 0;
-        // (--include-bed: every run of BED spans is a reference record of its own — optimize_reference_records, util.rs:287-296)
-        std::vector<Contig> recs_t = targets(*src, have_region ? &rg : nullptr);
-        if (have_bed) recs_t = bed_contigs(bed, recs_t, a.interval_size);
-        for (auto& c : recs_t) {
-          for (uint32_t p = c.start; p < c.end();) { const uint32_t e = (uint32_t)std::min<uint64_t>((uint64_t)p + a.interval_size, c.end());
-            g.push_back({c.tid, p, e}); glen += e - p;
-            if (glen >= a.interval_size) { groups.push_back(g); g.clear(); glen = 0; }
-            p = e; } }
-        if (!g.empty()) groups.push_back(g); }
-      for (size_t g0 = 0; g0 < groups.size(); g0 += batch_size) {
-        uint64_t total_len = 0;
-        for (size_t g = g0; g < std::min(groups.size(), g0 + batch_size); g++) for (auto& iv : groups[g]) total_len += iv.end - iv.start;
-        for (size_t g = g0; g < std::min(groups.size(), g0 + batch_size); g++) for (auto& iv : groups[g]) {
-          auto q = quota.find(iv.tid);
-          const long nr = q == quota.end() ? 0 /* chrom_has_reads: never fetched */
-              : (long)std::ceil((double)q->second.n * ((double)(iv.end - iv.start) / (double)(uint32_t)total_len));
-          iv_quota[iv.tid].push_back({iv.start, iv.end, q == quota.end() ? -2 : nr, 0});
-        }
-      }
-    }
-    long n_sent = 0; bool done = false;
-    FILE* out = (a.out_bed == "-" || a.out_bed == "stdout") ? stdout : fopen(a.out_bed.c_str(), "w+");
-    if (!out) throw Error(MKP_E_IO, "failed to make output file " + a.out_bed);
-    struct Close { FILE* f; ~Close() { if (f && f != stdout) fclose(f); } } closer{out};
-    // --bgzf (src/extract/subcommand.rs:629-660): the same table as BGZF blocks (SAM spec 4.1) cut at 0xff00 bytes, closed by the empty EOF block
-    std::vector<uint8_t> zpend, zout;
-    auto put = [&](const char* p, size_t n) {
-      if (!bgzf) { if (n && fwrite(p, 1, n, out) != n) throw Error(MKP_E_IO, "write error on " + a.out_bed); return; }
-      zpend.insert(zpend.end(), (const uint8_t*)p, (const uint8_t*)p + n);
-      size_t at = 0; zout.clear();
-      while (zpend.size() - at >= MKP_BGZF_BLOCK) { bgzf_block(zpend.data() + at, MKP_BGZF_BLOCK, &zout); at += MKP_BGZF_BLOCK; }
-      zpend.erase(zpend.begin(), zpend.begin() + (long)at);
-      if (!zout.empty() && fwrite(zout.data(), 1, zout.size(), out) != zout.size()) throw Error(MKP_E_IO, "write error on " + a.out_bed);
-    };
+    must(ctx, mkp_set_caller(ctx, &kc));
+    must(ctx, mkp_internal_set_extract(ctx, true));
+    BedFilter exbed; if (!f.exclude_bed.empty()) exbed = load_bed_for(f.exclude_bed, bd);
+    ExtractPlan plan = plan_extract(f, a, bd, have_bed ? &bed : nullptr);
+    Admission admission{f, plan};
+    TableSink sink(a.out_bed, f.bgzf);
     static const char EXTRACT_HEADER[] = "read_id\tforward_read_position\tref_position\tchrom\tmod_strand\tref_strand\tref_mod_strand\tfw_soft_clipped_start\tfw_soft_clipped_end\tread_length\tcall_prob\tcall_code\t"
                                          "base_qual\tref_kmer\tquery_kmer\tcanonical_base\tmodified_primary_base\tfail\tinferred\twithin_alignment\tflag\n";
-    if (!no_headers) put(EXTRACT_HEADER, sizeof(EXTRACT_HEADER) - 1);
+    if (!f.no_headers) sink.put(EXTRACT_HEADER, sizeof(EXTRACT_HEADER) - 1);
+    // records in file order, a batch per device round
     BamBatch view; view.base = bd.raw.data();
-    uint64_t n_used = 0, n_skipped = 0, n_failed = 0, n_rows = 0;
-    static const char NT16[] = "=ACMGRSVTWYHKDBN";
+    ExtractCounts c;
     const size_t BATCH = 1 << 15;
+    std::vector<mkp_record> recs; std::vector<int64_t> ends;
     std::vector<MkpEvent> ev; std::vector<float> vals; std::vector<uint32_t> n_vals;
-    for (size_t r0 = 0; r0 < bd.recs.size() && !done; r0 += BATCH) {
-      const size_t r1 = std::min(bd.recs.size(), r0 + BATCH);
-      std::vector<mkp_record> recs;
-      for (size_t i = r0; i < r1; i++) {   // TrackingModRecordIter (mod_bam.rs:53-122) + process_records_to_chan's --mapped-only
-        const mkp_record r = view.view(bd.recs[i]);
-        // IndexedReader::fetch(tid, start, end): the records overlapping the region (one without reference span counts as one base)
-        if (use_index && have_region) {
-          int64_t span = 0; const uint8_t* cgp = r.data + r.l_qname;
-          for (uint32_t k = 0; k < r.n_cigar; k++) { uint32_t w; memcpy(&w, cgp + 4 * (size_t)k, 4); const uint32_t op = w & 15u;
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += w >> 4;
-            }
-          const int64_t e = (int64_t)r.pos + std::max<int64_t>(span, 1);
-          if (r.tid != reg_tid || (int64_t)r.pos >= reg_e || e <= reg_s) continue;
-        }
-        if (scheduled && r.tid < 0) {   // the schedule's last leg: process_records_to_chan(.., only_mapped = false, allow_non_primary = false, ..)
-          if (!include_unmapped_reads) continue;
-          if (r.flag & (2048 | 256 | 1024)) { n_skipped++; continue; }
-          if (r.l_qseq <= 0) { n_failed++; continue; }
-          recs.push_back(r); continue;
-        }
-        if ((r.flag & (2048 | 256 | 1024)) && !allow_np) { n_skipped++; continue; }
-        if (r.l_qseq <= 0) { n_failed++; continue; }
-        if ((r.flag & 4) && mapped_only && !scheduled) { n_skipped++; continue; }   // (the schedule's samplers never ask about mapping)
-        recs.push_back(r);
-      }
+    for (size_t r0 = 0; r0 < bd.recs.size() && !admission.done; r0 += BATCH) {
+      select_records(f, plan, bd, view, r0, std::min(bd.recs.size(), r0 + BATCH), &recs, &ends, &c);
       if (recs.empty()) continue;
-      must(mkp_internal_sample(ctx, 0, 0, 1, nullptr, recs.data(), (uint32_t)recs.size(), false, &n_vals));
-      must(mkp_internal_extract_fetch(ctx, &ev, &vals));
-      const std::vector<MkpSlot>& slots = ctx->tables.st.slots;
+      must(ctx, mkp_internal_sample(ctx, 0, 0, 1, nullptr, recs.data(), (uint32_t)recs.size(), false, &n_vals));
+      must(ctx, mkp_internal_extract_fetch(ctx, &ev, &vals));
+      const RowSource rows{f, plan, bd, fasta, have_bed ? &bed : nullptr, f.exclude_bed.empty() ? nullptr : &exbed, ctx->tables.st.slots, ev, vals};
       std::string text;
-      for (size_t i = 0; i < recs.size(); i++) {
-        const mkp_record& r = recs[i];
+      for (size_t i = 0; i < recs.size() && !admission.done; i++) {
         const MkpReadHdr& h = ctx->sample_shard.hdr[i]; const MkpReadOut& ro = ctx->sample_ro[i];
-        if (done) break;
-        // --num-reads counts what reaches process_record: records whose tags parse and hold something (an unmapped record under --mapped-only
-        // never gets that far: dropped above)
-        if (scheduled && r.tid >= 0) {
-          auto qi = iv_quota.find((uint32_t)r.tid); if (qi == iv_quota.end() || qi->second.empty()) continue;
-          // the interval that takes the record: the first one (feeder order) whose fetch returns it and whose `cut` — the previous interval's
-          // end — does not lie behind its start: the first interval that ends behind the record's start, if the record reaches it at all
-          int64_t rspan = 0; { const uint8_t* cgp = r.data + r.l_qname;
-            for (uint32_t k = 0; k < r.n_cigar; k++) { uint32_t w; memcpy(&w, cgp + 4 * (size_t)k, 4); const uint32_t op = w & 15u;
-              if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rspan += w >> 4; } }
-          const int64_t rend = (int64_t)r.pos + std::max<int64_t>(rspan, 1);
-          auto it = std::upper_bound(qi->second.begin(), qi->second.end(), (int64_t)r.pos,
-              [](int64_t p, const IvQuota& q) { return p < (int64_t)q.end; });
-          if (it == qi->second.end() || (int64_t)it->start >= rend) continue;
-          IvQuota& Q = *it;
-          if (Q.nr == -2) continue;                                                        // the schedule holds nothing for this contig
-          if (!ro.ok) { if (h.flags & MKP_RF_BAD) n_failed++; else n_skipped++; continue; }  // TrackingModRecordIter never offers it
-          if (Q.nr >= 0 && Q.used >= Q.nr) continue;                                       // RecordSampler::ask -> Done
-          bool clips_ok = true;                                                            // process_record's own failure: get_soft_clipped
-          if (!(r.flag & 4)) { const uint8_t* cgp = r.data + r.l_qname; bool other = false;
-            for (uint32_t k = 0; k < r.n_cigar; k++) { uint32_t w; memcpy(&w, cgp + 4 * (size_t)k, 4); if ((w & 15u) != 4u) { other = true; break; } }
-            clips_ok = other; }
-          if (!clips_ok) { n_failed++; continue; }
-          Q.used++; aligned_used++;
-          if (mapped_only && (r.flag & 4)) continue;                                       // every row of an unmapped record lacks a reference position
-          if (!ro.n_events) continue;
-        } else if (scheduled) {
-          const long n_un = num_reads > (long)aligned_used ? num_reads - (long)aligned_used : 0;
-          if (ro.ok) { n_sent++; if (n_sent >= n_un) done = true; }   // (looked at after the record went to the writer: N = 0 lets one through)
-          if (!ro.ok || !ro.n_events) { if (h.flags & MKP_RF_BAD) n_failed++; else n_skipped++; continue; }
-        } else {
-        if (ro.ok) { n_sent++; if (num_reads >= 0 && n_sent >= num_reads) done = true; }
-        if (!ro.ok || !ro.n_events) { if (h.flags & MKP_RF_BAD) n_failed++; else n_skipped++; continue; }
+        const Clips clips = soft_clips(recs[i]);
+        switch (admission.judge(recs[i], ends[i], h, ro, clips)) {
+          case Admit::Silent: break;
+          case Admit::Failed: c.n_failed++; break;
+          case Admit::Skipped: c.n_skipped++; break;
+          case Admit::Rows: if (record_rows(rows, recs[i], h, ro, clips, &text, &c.n_rows)) c.n_used++; else c.n_skipped++; break;
         }
-        const bool unmapped = (r.flag & 4) != 0, rev = (r.flag & 16) != 0;
-        const size_t L = (size_t)r.l_qseq;
-        const uint8_t* cg = r.data + r.l_qname; const uint8_t* sq = cg + 4 * (size_t)r.n_cigar; const uint8_t* ql = sq + (L + 1) / 2;
-        auto cig = [&](uint32_t k) { uint32_t w; memcpy(&w, cg + 4 * (size_t)k, 4); return w; };
-        size_t sc_start = 0, sc_end = 0; bool cigar_ok = true;   // get_soft_clipped (read_ids_to_base_mod_probs.rs:803-824)
-        if (!unmapped) {
-          bool broke = false; for (uint32_t k = 0; k < r.n_cigar; k++) { const uint32_t w = cig(k); if ((w & 15u) == 4u) sc_start += w >> 4; else {
-              broke = true; break; } }
-          if (!broke) cigar_ok = false;
-          broke = false; for (uint32_t k = r.n_cigar; k-- > 0;) { const uint32_t w = cig(k); if ((w & 15u) == 4u) sc_end += w >> 4; else {
-              broke = true; break; } }
-          if (!broke) cigar_ok = false;
-        }
-        if (!cigar_ok) { n_failed++; continue; }
-        const size_t clip_start = rev ? sc_end : sc_start, clip_end = rev ? sc_start : sc_end;
-        auto within = [&](size_t qp) { return L >= clip_end && qp >= clip_start && qp < L - clip_end; };
-        // forward sequence and qualities
-        std::string fwd(L, 'N');
-        for (size_t k = 0; k < L; k++) { const uint8_t b = sq[k >> 1]; const char c = NT16[(k & 1) ? (b & 15) : (b >> 4)];
-          if (rev) fwd[L - 1 - k] = comp_char(c);
-          else fwd[k] = c;
-          }
-        const std::string chrom = (!unmapped && r.tid >= 0 && (size_t)r.tid < bd.ref_names.size()) ? bd.ref_names[(size_t)r.tid] : std::string();
-        const bool have_chrom = !unmapped && r.tid >= 0 && (size_t)r.tid < bd.ref_names.size();
-        const FastaSeq* ref_seq = have_chrom ? fasta.get(chrom) : nullptr;
-        const bool primary_or_unmapped = r.flag == 0 || r.flag == 16 || r.flag == 4;
-        const std::string qname((const char*)r.data, r.l_qname ? (size_t)r.l_qname - 1 : 0);
-        // the record's calls come in stored order (ascending stored index): one CIGAR walk gives their reference positions
-        struct Row { size_t f; long ref; uint32_t info; float p; };
-        std::vector<Row> rows; rows.reserve(ro.n_events);
-        uint32_t ck = 0; size_t q_at = 0; long r_at = r.pos;   // op ck starts at stored index q_at / reference position r_at
-        for (uint32_t k = 0; k < ro.n_events; k++) {
-          const MkpEvent& e = ev[(size_t)h.event_off + k];
-          const size_t f = e.pos, q = rev ? L - 1 - f : f;
-          long ref = -1;
-          if (!unmapped) {
-            // an event behind the walk (the kernels emit a record's events in stored order; should that ever change, start over instead of
-            // underflowing)
-            if (q < q_at) { ck = 0; q_at = 0; r_at = r.pos; }
-            while (ck < r.n_cigar) {
-              const uint32_t w = cig(ck), op = w & 15u, len = w >> 4;
-              const bool cq = op == 0 || op == 1 || op == 4 || op == 7 || op == 8, cr = op == 0 || op == 2 || op == 3 || op == 7 || op == 8;
-              if (cq && q < q_at + len) { if (op == 0 || op == 7 || op == 8) ref = r_at + (long)(q - q_at); break; }
-              if (cq) q_at += len;
-              if (cr) r_at += len;
-              ck++;
-            }
-          }
-          rows.push_back({f, ref, e.info, vals[(size_t)h.event_off + k]});
-        }
-        if (unmapped && rev) std::reverse(rows.begin(), rows.end());   // no alignment strand: ascending forward position
-        bool any = false;
-        for (const Row& w : rows) {
-          if ((mapped_only || have_bed) && (unmapped || w.ref < 0)) continue;   // filter_read_base_mod_probs (src/extract/util.rs:71-124)
-          // ... asked with the reference strand of the mod
-          if (have_bed && !bed.contains((uint32_t)r.tid, (uint64_t)w.ref, (((w.info >> 2) & 1u) != 0) != rev)) continue;
-          if (have_ex && !unmapped && w.ref >= 0 && exbed.contains((uint32_t)r.tid, (uint64_t)w.ref, (((w.info >> 2) & 1u) != 0) != rev)) continue;
-          if (!primary_or_unmapped && !within(w.f)) continue;                   // iter_profiles (read_ids_to_base_mod_probs.rs:785-800)
-          any = true;
-          const uint32_t tb = w.info & 3u, sg = (w.info >> 2) & 1u, inferred = (w.info >> 3) & 1u, thr_cls = (w.info >> 4) & 15u,
-              arg_cls = (w.info >> 8) & 15u;
-          if (remove_inferred && inferred) continue;
-          const bool filtered = thr_cls == 0;
-          if (filtered && pass_only) continue;
-          std::string code = "-";
-          if (arg_cls >= 2) { const uint32_t cr = arg_cls - 2 < slots.size() ? slots[arg_cls - 2].code_repr : 0u;
-            code = (cr & 0x80000000u) ? std::to_string(cr & 0x7fffffffu) : std::string(1, (char)cr); }
-          std::string qk = kmer_at(fwd.data(), L, w.f, kmer);
-          if (sg) { std::string t; for (size_t k = qk.size(); k-- > 0;) t.push_back(qk[k] == '-' ? '-' : comp_char(qk[k])); qk.swap(t); }
-          std::string rk = ".";
-          if (w.ref >= 0 && ref_seq) rk = kmer_at(ref_seq->data(), ref_seq->size(), (size_t)w.ref, kmer);
-          const unsigned bq = ql[rev ? L - 1 - w.f : w.f];
-          char line[1200];
-          const int ln = snprintf(line, sizeof(line), "%s\t%zu\t%ld\t%s\t%c\t%c\t%c\t%zu\t%zu\t%zu\t%s\t%s\t%u\t%s\t%s\t%c\t%c\t%s\t%s\t%s\t%u\n",
-              qname.c_str(), w.f, w.ref >= 0 ? w.ref : -1L,
-                   have_chrom ? chrom.c_str() : ".", sg ? '-' : '+', unmapped ? '.' : (rev ? '-' : '+'),
-                       unmapped ? '.' : ((sg != 0) != rev ? '-' : '+'), clip_start, clip_end, L,
-                   f32_display(w.p).c_str(), code.c_str(), bq, rk.c_str(), qk.c_str(), "ACGT"[tb], "ACGT"[sg ? 3 - tb : tb],
-                       filtered ? "true" : "false", inferred ? "true" : "false",
-                   (have_chrom && within(w.f)) ? "true" : "false", (unsigned)r.flag);
-          if (ln < 0 || (size_t)ln >= sizeof(line)) throw Error(MKP_E_UNSUPPORTED,
-              "extract calls: a row is longer than " + std::to_string(sizeof(line)) + " bytes (read or contig name of unusual length)");
-          text.append(line, (size_t)ln); n_rows++;
-        }
-        if (any) n_used++; else n_skipped++;
       }
-      put(text.data(), text.size());
+      sink.put(text.data(), text.size());
     }
-    if (bgzf) {
-      zout.clear(); if (!zpend.empty()) bgzf_block(zpend.data(), zpend.size(), &zout);
-      static const uint8_t eof_block[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-      zout.insert(zout.end(), eof_block, eof_block + 28);
-      if (fwrite(zout.data(), 1, zout.size(), out) != zout.size()) throw Error(MKP_E_IO, "write error on " + a.out_bed);
-    }
-    if (stats) fprintf(stderr, "[mkpileup] extract calls: reads=%llu rows=%llu skipped=%llu failed=%llu\n", (unsigned long long)n_used,
-        (unsigned long long)n_rows, (unsigned long long)n_skipped, (unsigned long long)n_failed);
-    return MKP_OK;
-  } catch (const Error& e) { return fail(e.status, e.what()); }
-  catch (const std::exception& e) { return fail(MKP_E_INVALID, e.what()); }
+    sink.finish();
+    if (f.stats) fprintf(stderr, "[mkpileup] extract calls: reads=%llu rows=%llu skipped=%llu failed=%llu\n", (unsigned long long)c.n_used,
+        (unsigned long long)c.n_rows, (unsigned long long)c.n_skipped, (unsigned long long)c.n_failed);
+    return (int)MKP_OK;
+  });
 }

@@ -123,3 +123,34 @@ def test_a_bam_without_an_index_is_sampled_serially(oracle_bin, tmp_path):
             ctx.sample_probs(bam, qs, ["-f", "0.3", "--seed", "5", "--only-mapped"])
     finally:
         ctx.close()
+
+
+@pytest.mark.parametrize("extra", [[], ["--include-unmapped"], ["--include-bed"]], ids=["mapped", "unmapped", "bed"])
+def test_rank_sharded_host_reader_sample_is_the_single_rank_sample(tmp_path, extra):
+    # `--gpus-world W` with -f 1.0 on the host-reader route: a rank walks only the sampling intervals it owns (contiguous runs of the grid by
+    # base pairs) and leaves out the reads that reach back into an earlier interval — taken there, by this rank or another.  With intervals
+    # of 1000 bases and reads of mean length 900 most reads cross an interval edge and many cross a rank edge; the ranks' level-0 histograms
+    # must sum, bin for bin, to those of one context that ran the same flags alone.  Rank 0 alone takes the unmapped reads.
+    import numpy as np
+    bam, _, bed = Fuzz(909, profile="hm_split", n_reads=400, mean_len=900, index=True).write(str(tmp_path / "fz"), bed=True)
+    flags = ["--sampling-interval-size", "1000", "-f", "1.0"] + (["--include-bed", bed] if extra == ["--include-bed"] else extra)
+
+    def histograms(more):
+        ctx = modkit_amd.Context()
+        try:
+            ctx.histogram_begin()
+            ctx.histogram_add_bam(bam, flags + more)
+            return np.stack([ctx.histogram_get(b, 0).astype(np.uint64) for b in "ACGT"])
+        finally:
+            ctx.close()
+
+    single = histograms([])
+    assert int(single[1].sum()) > 100   # the test is not empty: C holds the sample's values
+    for world in (2, 3):
+        total = np.zeros_like(single)
+        for rank in range(world):
+            total += histograms(["--gpus-rank", str(rank), "--gpus-world", str(world)])
+        for b in range(4):
+            diff = int((total[b] != single[b]).sum())
+            print("world %d base %s: %d values, %d differing bins" % (world, "ACGT"[b], int(single[b].sum()), diff))
+            assert diff == 0, (world, "ACGT"[b], diff)
