@@ -59,19 +59,6 @@ __device__ __forceinline__ int find_op(uint32_t incl, uint32_t j) {
   return idx;
 }
 
-__device__ __forceinline__ uint32_t sel4(const uint32_t* a, int x) { return x == 0 ? a[0] : x == 1 ? a[1] : x == 2 ? a[2] : a[3]; }
-__device__ __forceinline__ unsigned long long sel4b(const unsigned long long* a, int x) { return x == 0 ? a[0] : x == 1 ? a[1] : x == 2 ? a[2] : a[3];
-  }
-
-__device__ __forceinline__ int find_rank(const uint32_t* __restrict__ a, uint32_t n, uint32_t key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1; else hi = mid;
-  }
-  return (lo < n && a[lo] == key) ? (int)lo : -1;
-}
-
 // Four f32 values addressed by a small index, kept as named scalars: a `float[4]` indexed by a lane-varying value is
 // demoted to scratch memory by the compiler (a select chain over array elements becomes an indexed load), which put
 // scratch loads into the per-call path.  With scalars the selects stay v_cndmask.
@@ -238,8 +225,9 @@ __device__ __forceinline__ uint32_t match8(uint32_t xl, int k) {
   const uint32_t m = (t & 0x11111111u) ^ 0x11111111u;          // bit 4i set where nibble i matches
   return ((((m | (m >> 3)) & 0x03030303u) * 0x01041040u) >> 24);  // gather bits 4i -> i
 }
-// position of the r-th (0-based) set bit of an 8-bit mask
-__device__ __forceinline__ uint32_t select8(uint32_t m, uint32_t r) {
-  for (uint32_t k = 0; k < r; k++) m &= m - 1u;
-  return (uint32_t)__ffs((int)m) - 1u;
+// flag word of a SEQ dword as stored: bit 4i set where nibble i equals the BAM code in every nibble of pat (0x11111111 << base)
+__device__ __forceinline__ uint32_t nibble_eq(uint32_t x, uint32_t pat) {
+  uint32_t t = x ^ pat;
+  t |= t >> 1; t |= t >> 2;
+  return ~t & 0x11111111u;
 }

@@ -8,9 +8,10 @@
 //     mkp_decode_fast1/2     one group, any mode / differing delta lists: 1024-base steps, ordinal bitmap in LDS + 4-bit deposit
 //     mkp_decode_reads       everything else (<= 8 tags, `N` tags, duplex, repeated codes): combine_positions_to_probs per group
 //     mkp_merge_duplex       duplex reads decoded one group per wave: interleave the two position-sorted event lists
-//   The three decoders differ in how they locate calls; the per-call work (ML -> f32 BaseModProbs, edge filter, ReDistribute
-//   collapse, MultipleThresholdModCaller::call, CIGAR mapping, one packed 8-byte event per mapped call), the read prologue and
-//   epilogue are the shared helpers in front of them.  FAST and SPARSE run it on full batches of 64 queued calls.
+//   The three decoders differ in how they locate calls (their producers: drivers over named stages, on shared steps — rank_batch,
+//   window_take, mark_window, deposit_marks, stored_base_total); the per-call work (ML -> f32 BaseModProbs, classify_rule: edge filter,
+//   ReDistribute collapse, MultipleThresholdModCaller::call; CIGAR mapping, one packed 8-byte event per mapped call), the read prologue and
+//   epilogue are the shared helpers in front of them.  FAST and SPARSE run it in one consumer, consume_batch, on full batches of 64 calls.
 //   mkp_sample_* = the same walks emitting argmax probabilities / summary classes (threshold estimate, sample-probs, summary).
 //
 //   mkp_pileup_tiles[_keyed][_wide]   runs without focus positions: accumulate + emit, one 1024-thread workgroup per tile, two per CU;
@@ -124,6 +125,105 @@ __device__ __forceinline__ bool lacks_mode(uint32_t tagbits, uint32_t default_ma
 // by the join (mod_bam.rs:705-727, 750-756).  Reverse reads consume their list from its end.
 __device__ __forceinline__ bool list_left_over(bool rev, uint32_t cur, uint32_t n) { return rev ? (cur != 0u) : (cur != n); }
 
+#define DECODE_PARAMS(PRM) const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ seqs, \
+                    const MkpTagRef* __restrict__ tagref, const uint32_t* __restrict__ ranks, const uint8_t* __restrict__ ml, \
+                    const MkpLayout* __restrict__ layouts, PRM prm, MkpEvent* __restrict__ events, MkpReadOut* __restrict__ readout, \
+                    uint32_t* __restrict__ dev_err, const uint8_t* __restrict__ bedmask, float* __restrict__ sample_vals, const uint32_t* __restrict__ read_ids
+#define DECODE_PASS hdrs, n_reads, cigar, seqs, tagref, ranks, ml, layouts, prm, events, readout, dev_err, bedmask, sample_vals, read_ids
+
+// ---- producer steps.  A tag's calls are a sorted list of ranks (forward-order ordinals of the tag's base, or positions for `N` tags);
+// the read is walked in steps of stored bases, and every step takes the ranks of its window from the list's cursor.
+// The 64 entries of a rank list at its cursor, one per lane: forward reads go up from it, reverse reads (whose walk meets the list's end first) down.
+struct RankBatch { uint32_t e; bool valid; };
+__device__ __forceinline__ RankBatch rank_batch(const uint32_t* __restrict__ ranks, uint32_t off, uint32_t n, uint32_t cur, bool rev) {
+  const uint32_t i = (rev ? cur - 64u : cur) + (uint32_t)lane_id();
+  RankBatch b; b.valid = rev ? ((int32_t)i >= 0 && i < cur) : (i < n);
+  b.e = rev ? 0u : 0xffffffffu;
+  if (b.valid) b.e = ranks[off + i];
+  return b;
+}
+// The batch's entries inside the step's rank window [wlo, whi) are taken: hit, the lanes holding one, their number, the cursor moved
+// past them (a forward entry >= whi of the last step is past the last occurrence: never consumed, an error at the end).  SUFFIX: the
+// caller knows every entry to lie below whi (reverse reads of the SPARSE decoder) — the hits are a suffix of the batch.
+struct RankTake { bool hit; unsigned long long lanes; uint32_t nh; };
+template <bool SUFFIX = false>
+__device__ __forceinline__ RankTake window_take(const RankBatch& b, uint32_t wlo, uint32_t whi, bool rev, uint32_t& cur) {
+  RankTake t; t.hit = b.valid && (rev ? (b.e >= wlo && (SUFFIX || b.e < whi)) : (b.e < whi));
+  t.lanes = __ballot(t.hit); t.nh = (uint32_t)__popcll(t.lanes);
+  cur = rev ? cur - t.nh : cur + t.nh;
+  return t;
+}
+// step-relative stored ordinal of a taken rank e: tot = the read's total of that base, first = the ordinals in front of the step
+__device__ __forceinline__ uint32_t step_ordinal(uint32_t e, bool rev, uint32_t tot, uint32_t first) { return (rev ? (tot - 1u - e) : e) - first; }
+// Every rank of the window [wlo, whi) marked as a bit of the step's ordinal bitmap in LDS (cleared by the caller; a wave_lds_sync
+// before it is read).  `b` = the batch at the cursor, which the caller may have requested early.
+__device__ __forceinline__ void mark_window(const uint32_t* __restrict__ ranks, uint32_t off, uint32_t n, uint32_t& cur, bool rev, RankBatch b,
+    uint32_t wlo, uint32_t whi, uint32_t tot, uint32_t first, uint32_t* __restrict__ ordb) {
+  for (;;) {
+    const RankTake t = window_take(b, wlo, whi, rev, cur);
+    if (t.nh == 0) break;
+    const uint32_t ib = step_ordinal(b.e, rev, tot, first);
+    if (t.hit) atomicOr(&ordb[ib >> 5], 1u << (ib & 31u));
+    if (t.nh < 64) break;
+    b = rank_batch(ranks, off, n, cur, rev);
+  }
+}
+// Bits [ex, ex + popc(m)) of the ordinal bitmap deposited onto the set bits of the lane's W-base match mask m, four bases at a
+// time (pdep4); ex = the occurrences in the lanes below.  The bitmap ends with the words the 64-bit window read may touch.
+template <int W>
+__device__ __forceinline__ uint32_t deposit_marks(const uint32_t* __restrict__ ordb, const uint8_t* __restrict__ pdep4, uint32_t m, uint32_t ex) {
+  const uint32_t w0 = ordb[ex >> 5], w1 = ordb[(ex >> 5) + 1];
+  const uint32_t f = __builtin_amdgcn_alignbit(w1, w0, ex & 31u) & ((1u << __popc(m)) - 1u);
+  uint32_t bm = 0;
+#pragma unroll
+  for (int k = 0; k < W; k += 4)   // the mask's nibble at k takes the bits behind those of the nibbles below it
+    bm |= (uint32_t)pdep4[(((m >> k) & 15u) << 4) | ((f >> __popc(m & ((1u << k) - 1u))) & 15u)] << k;
+  return bm;
+}
+// The low nibble of a read's last byte is not a base when L is odd: the dword holding it and the mask that clears its flag
+struct OddTail { uint32_t dw, clear; };
+__device__ __forceinline__ OddTail odd_tail(uint32_t L) {
+  OddTail o; o.dw = (L & 1u) ? ((L - 1u) >> 3) : 0xffffffffu; o.clear = ~(1u << (8u * (((L - 1u) >> 1) & 3u)));
+  return o;
+}
+// Occurrences of stored base xs in the whole read, four loads in flight.  Reverse reads need it up front: forward rank =
+// total - inclusive count in stored order.  The SEQ invariant the decoders' nibble flags rely on, stated once: both packers
+// (mkp_pack.hpp, ingest_copy_record) zero-pad a read's SEQ to a dword and code 0 matches no base, so only the low nibble of an
+// odd read's last byte needs clearing (odd_tail); dwords past the read are not loaded.
+__device__ __forceinline__ uint32_t stored_base_total(const uint32_t* __restrict__ seqw, uint32_t nd, uint32_t L, int xs) {
+  const uint32_t lane = (uint32_t)lane_id(), pat = 0x11111111u << xs;
+  const OddTail odd = odd_tail(L);
+  uint32_t acc = 0;
+  for (uint32_t d0 = 0; d0 < nd; d0 += 256) {
+    uint32_t xw[4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { const uint32_t dd = d0 + 64u * j + lane; xw[j] = dd < nd ? seqw[dd] : 0u; }
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      uint32_t F = nibble_eq(xw[j], pat); if (d0 + 64u * j + lane == odd.dw) F &= odd.clear;
+      acc += (uint32_t)__popc(F);
+    }
+  }
+  return (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(acc), 63);
+}
+
+// The read as its producer walks it: step after step of stored bases.
+struct ReadWalk {
+  const uint32_t* __restrict__ seqw; uint32_t L, nd; bool rev;
+  uint32_t tot = 0;          // reverse reads: occurrences of the counted base in the whole read
+  uint32_t cum = 0, d0 = 0;  // occurrences in front of the step, the step's first SEQ dword
+};
+// the rank lists of the decoder's tags, their ML arrays and the merge join's cursors (reverse reads start at the end)
+template <int NT> struct TagLists { uint32_t off[NT], n[NT], ml[NT], cur[NT]; };
+template <int NT>
+__device__ __forceinline__ void tag_lists(const MkpTagRef* __restrict__ tagref, uint32_t first, int n_tags, bool rev, TagLists<NT>& T) {
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    T.off[t] = 0; T.n[t] = 0; T.ml[t] = 0; T.cur[t] = 0;
+    if (t < n_tags) { const MkpTagRef tr = tagref[first + t]; T.off[t] = tr.rank_off; T.n[t] = tr.n; T.ml[t] = tr.ml_off; T.cur[t] = rev ? tr.n : 0u; }
+  }
+}
+
 // What a read's calls add up to.  Per-lane while the read is walked; read_epilogue reduces it over the wave.
 struct ReadAcc { bool err = false, any_surviving = false; uint32_t obs0 = 0, obs1 = 0, n_ev = 0; };
 
@@ -155,6 +255,11 @@ __device__ __forceinline__ void cigar_map(CigarWin& w, const MkpReadHdr& h, cons
     if (!__any(pending)) break;
   }
 }
+
+// (CigarWin goes in and comes back by value: behind the reference mkp_decode_fast1 takes 67 VGPRs for 64 and loses its eighth wave)
+template <bool SAMPLE>
+__device__ __forceinline__ void map_window(CigarWin& w, const MkpReadHdr& h, const uint32_t* __restrict__ cigar, bool pending, uint32_t q,
+    bool& mapped, int32_t& rpos) { CigarWin v = w; cigar_map(v, h, cigar, pending, q, mapped, rpos); w = v; }
 
 // Call queue of the single-group decoders (N SoA columns of `stride` entries in LDS): move the (< 64) unconsumed entries to the front
 template <int N> __device__ __forceinline__ void queue_to_front(uint32_t* __restrict__ q, uint32_t stride, uint32_t& qhead, uint32_t& qcount) {
@@ -209,6 +314,36 @@ __device__ __forceinline__ bool ml_to_probs(const uint32_t (&mlq)[NT][MKP_KMAX],
   return check && s > 1.01f;
 }
 
+// The per-call rule every decoder shares: one call at forward position f / reference position rpos on group g (base b, mod
+// strand sg), pv = the group's entry for the call's hit pattern, pk = its probabilities.  Edge and trim gate, position filter
+// of the sampling passes, then the pass's output.  True = the lane has an event: info (without bit 12, "first event of its
+// position", which is the caller's), sample value in sv; ev_pos is touched only where the event's position is not rpos.
+template <bool SAMPLE>
+__device__ __forceinline__ bool classify_rule(const MkpRunParams& prm, const uint8_t* __restrict__ bedmask, const GroupRegs& g, uint32_t pv,
+    int kcodes, int b, int sg, uint32_t aln, uint32_t L, bool trimmable, bool inferred, F4& pk, uint32_t f, bool mapped, int32_t rpos,
+    ReadAcc& acc, uint32_t& ev_info, float& sv, int32_t& ev_pos) {
+  if (!trimmable || !edge_keep(prm, f, L)) return false;
+  const bool collapse = collapse_on(prm);
+  const uint32_t tally = aln ^ (uint32_t)sg;  // read_cache.rs:181-188 / FeatureVector::add_feature
+  uint32_t ob = 0;
+  if (SAMPLE) {
+    if (!sample_keep(prm, bedmask, mapped, rpos, tally)) return false;
+    acc.any_surviving = true;
+    if (prm.sample_mode < 2) { sv = argmax_group(g, pv, pk, collapse, kcodes); ev_info = MKP_G_TB(g.misc); return true; }
+    // 2 `summary`: thresholded + argmax class; 3 `extract calls`: + forward position, mod strand, inferred, call_prob
+    if (prm.sample_mode == 3 && ((pv >> 3) & 7u) == 0u) return false;   // the collapse left no code in the map: no profile row (iter_probs is empty)
+    float am = 0.f;
+    ev_info = summary_info(g, pv, pk, collapse, &ob, kcodes, &am); acc.obs0 |= ob;
+    if (prm.sample_mode == 3) { ev_info |= ((uint32_t)sg << 2) | ((inferred ? 1u : 0u) << 3); sv = am; ev_pos = (int32_t)f; }
+    return true;
+  }
+  acc.any_surviving = true;
+  const int cls = call_group(g, pv, pk, collapse, &ob, kcodes);
+  if (tally) acc.obs1 |= ob; else acc.obs0 |= ob;
+  if (mapped) ev_info = call_cid(g, cls) | (tally << 8) | ((uint32_t)b << 9) | (aln << 11);
+  return mapped;
+}
+
 // One call of a single-group decoder (group g, descriptor words at gp, on base b0 / mod strand sg0): SH = the members whose
 // tags list it, impl = the group's implicit-mode members, pk = its probabilities, f / rpos = its forward and reference
 // positions.  True = the lane has an event (info, position in rpos, sample value in sv).  INFER = false: the group has no
@@ -219,28 +354,13 @@ __device__ __forceinline__ bool classify_call(const MkpRunParams& prm, const uin
     uint32_t f, bool mapped, int32_t& rpos, ReadAcc& acc, uint32_t& contribH, uint32_t& ev_info, float& sv) {
   int pat = (int)SH; uint32_t member_contrib = SH;
   if (INFER) call_pattern(SH, impl, acc.err, pat, member_contrib);   // the caller saw to SH | impl
-  const uint32_t pv = gp[12 + pat];
   contribH |= member_contrib;
-  if (!trimmable || !edge_keep(prm, f, L)) return false;
-  const bool collapse = collapse_on(prm);
-  const uint32_t tally = aln ^ (uint32_t)sg0;  // read_cache.rs:181-188 / FeatureVector::add_feature
-  uint32_t ob = 0;
-  if (SAMPLE) {
-    if (!sample_keep(prm, bedmask, mapped, rpos, tally)) return false;
-    acc.any_surviving = true;
-    if (prm.sample_mode < 2) { sv = argmax_group(g, pv, pk, collapse, kcodes); ev_info = MKP_G_TB(g.misc); return true; }
-    // 2 `summary`: thresholded + argmax class; 3 `extract calls`: + forward position, mod strand, inferred, call_prob
-    if (prm.sample_mode == 3 && ((pv >> 3) & 7u) == 0u) return false;   // the collapse left no code in the map: no profile row
-    float am = 0.f;
-    ev_info = summary_info(g, pv, pk, collapse, &ob, kcodes, &am); acc.obs0 |= ob;
-    if (prm.sample_mode == 3) { ev_info |= ((uint32_t)sg0 << 2) | ((INFER && pat == MKP_PAT_INFERRED ? 1u : 0u) << 3); sv = am; rpos = (int32_t)f; }
-    return true;
-  }
-  acc.any_surviving = true;
-  const int cls = call_group(g, pv, pk, collapse, &ob, kcodes);
-  if (tally) acc.obs1 |= ob; else acc.obs0 |= ob;
-  if (mapped) ev_info = call_cid(g, cls) | (tally << 8) | ((uint32_t)b0 << 9) | (aln << 11) | (1u << 12);
-  return mapped;
+  int32_t pos = rpos;
+  const bool has_ev = classify_rule<SAMPLE>(prm, bedmask, g, gp[12 + pat], kcodes, b0, sg0, aln, L, trimmable, INFER && pat == MKP_PAT_INFERRED,
+                                            pk, f, mapped, rpos, acc, ev_info, sv, pos);
+  rpos = pos;
+  if (!SAMPLE && has_ev) ev_info |= 1u << 12;   // one event per position: it is the position's first
+  return has_ev;
 }
 
 // Ballot-compacted, position-ordered append of one batch's events, up to N per lane (cnt of them, all at pos), to the read's
@@ -276,17 +396,16 @@ __device__ __forceinline__ void read_epilogue(MkpReadOut* __restrict__ readout, 
   if (lane_id() == 0) readout[ro_idx] = out;
 }
 
-
 // ----------------------------------------------------------------------------------------------
 // Decode, general layouts.  One wave per read.  The read is walked 512 bases at a time (one SEQ dword = 8 bases per lane):
-//   1. per lane: match masks of the stored bases the read's MM tags count, popcounts, wave prefix sums
-//      (DeltaListConverter's cumulative counts, mod_bam.rs:667-684, 8 bases per instruction);
-//   2. per tag: the calls whose rank falls into the chunk's rank window are located (prefix search + select)
-//      and marked in a per-lane 8-bit "call here" mask held in LDS;
-//   3. the union of the masks (plus every occurrence of an implicit-mode base) is enumerated, 64 positions
-//      per batch: BaseModProbs are rebuilt in MM order, edge filter, ReDistribute collapse and
-//      MultipleThresholdModCaller::call in f32, CIGAR mapping through a 64-op window, and one packed
-//      8-byte event per mapped call is appended (ballot-compacted, position order).
+//   general_base_slots     once per read: the distinct stored bases its tags count, and which of them carry implicit calls;
+//   general_match_scan     per lane the match masks of those bases, popcounts, wave prefix sums (DeltaListConverter's cumulative
+//                          counts, mod_bam.rs:667-684, 8 bases per instruction);
+//   general_mark_deposit   per tag: the ranks of the chunk's window marked in an ordinal bitmap in LDS and deposited onto the lane's
+//                          match mask (`N` tags: a position bitmap, read back as is) — an 8-bit "call here" mask per tag;
+//   general_compact        the union of the masks (plus every occurrence of an implicit-mode base) as {lane, bit} slots in LDS;
+//   then 64 positions per batch: general_position_probs (BaseModProbs in MM order, merge_tag per tag), cigar_map, general_classify
+//   (classify_rule on the position's one or two groups), append_events.
 // SAMPLE = threshold-sampling pass: emits argmax probabilities instead of call events.
 // arr[j] for a wave-uniform j < N (N is tiny: a select chain, no scratch)
 template <int N> __device__ __forceinline__ uint32_t selN(const uint32_t* a, uint32_t j) {
@@ -295,16 +414,174 @@ template <int N> __device__ __forceinline__ uint32_t selN(const uint32_t* a, uin
   for (int i = 0; i < N; i++) r |= (j == (uint32_t)i) ? a[i] : 0u;
   return r;
 }
+// The read's tags: lists, descriptors, and their base slots — the nb distinct stored bases (A,C,G,T = 0..3) some tag counts; implslots =
+// the slots every occurrence of whose base is a call; per slot the read's total (reverse reads) and the occurrences in front of the chunk.
+template <int NT, int NB> struct GeneralTags {
+  TagLists<NT> T; MkpTagDesc desc[NT]; uint32_t tslot[NT];
+  uint32_t sbase[NB], nb, implslots, tot[NB], cum[NB];
+};
+template <int NT, int NB>
+__device__ __forceinline__ void general_base_slots(GeneralTags<NT, NB>& R, const MkpLayout* lay, const uint32_t* lds_lay, int n_tags, bool rev) {
+  uint32_t nb = 0;
+#pragma unroll
+  for (int j = 0; j < NB; j++) { R.sbase[j] = 0; R.tot[j] = 0; R.cum[j] = 0; }
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    R.tslot[t] = 0; R.desc[t] = lay->tags[t];
+    if (t < n_tags && R.desc[t].fb != 4) {
+      const uint32_t xb = (uint32_t)(rev ? 3 - R.desc[t].fb : R.desc[t].fb);
+      uint32_t found = nb;
+#pragma unroll
+      for (int j = 0; j < NB; j++) if ((uint32_t)j < nb && R.sbase[j] == xb) found = (uint32_t)j;
+      if (found == nb) {
+#pragma unroll
+        for (int j = 0; j < NB; j++) if ((uint32_t)j == nb) R.sbase[j] = xb;
+        nb++;
+      }
+      R.tslot[t] = rfl_u(found);
+    }
+  }
+  R.nb = rfl_u(nb);
+  uint32_t implslots = 0;   // groups with implicit-mode members (mod_bam.rs:1265-1292)
+#pragma unroll
+  for (int j = 0; j < NB; j++) {
+    R.sbase[j] = rfl_u(R.sbase[j]);
+    const uint32_t b = rev ? 3u - R.sbase[j] : R.sbase[j];
+    const uint32_t m0 = lds_lay[MKP_LAYOUT_GROUP_DW + b * 32], m1 = lds_lay[MKP_LAYOUT_GROUP_DW + (4 + b) * 32];
+    if ((uint32_t)j < R.nb && (MKP_G_IMPL(m0) | MKP_G_IMPL(m1))) implslots |= 1u << j;
+  }
+  R.implslots = rfl_u(implslots);
+}
+// One 512-base chunk: the lane's dword (linearized), its valid bases, per base slot the match mask, wave prefix sum and chunk total; per
+// tag the cursor before the chunk and pack = its 8-bit call mask | (its calls in the lanes below) << 8; U / H = the lane's / chunk's calls.
+template <int NT, int NB> struct GeneralStep {
+  uint32_t xl, vmask, m8[NB], incl[NB], cnt[NB], cur_before[NT], pack[NT], U, H;
+};
+template <int NT, int NB>
+__device__ __forceinline__ void general_match_scan(GeneralStep<NT, NB>& S, const GeneralTags<NT, NB>& R, const ReadWalk& W, uint32_t x) {
+  const uint32_t d = W.d0 + (uint32_t)lane_id();
+  S.xl = linearize(x);
+  S.vmask = (1u << min(max((int)W.L - (int)(8u * d), 0), 8)) - 1u;
+  S.U = 0;
+#pragma unroll
+  for (int j = 0; j < NB; j++) {
+    S.m8[j] = 0; S.incl[j] = 0; S.cnt[j] = 0;
+    if ((uint32_t)j < R.nb) {
+      S.m8[j] = match8(S.xl, (int)R.sbase[j]) & S.vmask; S.incl[j] = wave_incl_scan((uint32_t)__popc(S.m8[j]));
+      S.cnt[j] = (uint32_t)__builtin_amdgcn_readlane((int)S.incl[j], 63);
+      if ((R.implslots >> j) & 1u) S.U |= S.m8[j];
+    }
+  }
+}
+template <int NT, int NB>
+__device__ __forceinline__ void general_mark_deposit(GeneralStep<NT, NB>& S, GeneralTags<NT, NB>& R, const ReadWalk& W, int n_tags,
+    const MkpRunParams& prm, const uint32_t* __restrict__ ranks, uint32_t* __restrict__ ordb, const uint8_t* __restrict__ pdep4) {
+  const uint32_t lane = (uint32_t)lane_id(), qa = 8u * W.d0, qb = min(qa + 512u, W.L);
+  const bool rev = W.rev;
+#pragma unroll
+  for (int t = 0; t < NT; t++) { S.cur_before[t] = R.T.cur[t]; if (t < n_tags && lane < 18) ordb[t * 18 + lane] = 0; }
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    if (t >= n_tags) break;
+#ifdef MKP_DEBUG
+    if (prm.debug_skip & 32u) break;   // ablation: no calls marked
+#endif
+    const bool any_base = R.desc[t].fb == 4;   // an `N` tag: ranks are positions
+    const uint32_t sj = R.tslot[t];
+    // window of ranks this chunk can ask for (windows of successive chunks tile the rank space); the bit marked is the chunk-relative
+    // stored ordinal of the call's base, or its stored position
+    const uint32_t first = any_base ? qa : selN<NB>(R.cum, sj), n = any_base ? qb - qa : selN<NB>(S.cnt, sj);
+    const uint32_t tot = any_base ? W.L : selN<NB>(R.tot, sj);
+    const uint32_t wlo = rev ? (tot - first - n) : first;
+    mark_window(ranks, R.T.off[t], R.T.n[t], R.T.cur[t], rev, rank_batch(ranks, R.T.off[t], R.T.n[t], R.T.cur[t], rev), wlo, wlo + n, tot, first,
+                ordb + t * 18);
+  }
+  wave_lds_sync();
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    S.pack[t] = 0;
+    if (t < n_tags) {
+      uint32_t bm;
+      if (R.desc[t].fb == 4) bm = (ordb[t * 18 + (lane >> 2)] >> ((lane & 3) * 8)) & 0xffu & S.vmask;
+      else {
+        const uint32_t m = selN<NB>(S.m8, R.tslot[t]);
+        bm = deposit_marks<8>(ordb + t * 18, pdep4, m, selN<NB>(S.incl, R.tslot[t]) - (uint32_t)__popc(m));
+      }
+      S.U |= bm; const uint32_t c2 = (uint32_t)__popc(bm); S.pack[t] = bm | ((wave_incl_scan(c2) - c2) << 8);
+    }
+  }
+}
+// every lane writes {lane, bit} of its called positions into the wave's slot list, in read order
+template <int NT, int NB>
+__device__ __forceinline__ void general_compact(GeneralStep<NT, NB>& S, uint16_t* __restrict__ slots) {
+  const uint32_t ucnt = (uint32_t)__popc(S.U), uincl = wave_incl_scan(ucnt);
+  S.H = (uint32_t)__builtin_amdgcn_readlane((int)uincl, 63);
+  uint32_t ut = S.U, sidx = uincl - ucnt;
+  while (ut) { slots[sidx++] = (uint16_t)(((uint32_t)lane_id() << 3) | ((uint32_t)__ffs((int)ut) - 1u)); ut &= ut - 1u; }
+  wave_lds_sync();
+}
+// BaseModProbs of the lane's position (owner lane / bit of the chunk, base b) per mod strand: the tags that list it, in MM order
+template <int NT, int NB>
+__device__ __forceinline__ void general_position_probs(const GeneralStep<NT, NB>& S, const GeneralTags<NT, NB>& R, const MkpLayout* lay, int n_tags,
+    bool rev, const uint8_t* __restrict__ ml, bool active, int owner, uint32_t bit, int x, int b, GState& S0, GState& S1, bool& err) {
+#pragma unroll
+  for (int k = 0; k < MKP_KMAX; k++) { at(S0.pk, k) = 0.f; at(S1.pk, k) = 0.f; }
+  S0.H = S0.setmask = S1.H = S1.setmask = 0;
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    if (t >= n_tags) break;
+    const MkpTagDesc dsc = R.desc[t];
+    const uint32_t pt = __shfl(S.pack[t], owner, 64);
+    if (!(active && ((pt >> bit) & 1u))) continue;
+    if (x < 0) { err = true; continue; }  // a call listed on a non-ACGT base (DnaBase::try_from, mod_bam.rs:1245)
+    const uint32_t idx = (pt >> 8) + (uint32_t)__popc(pt & ((1u << bit) - 1u));  // index among the tag's calls of this chunk, read order
+    const uint32_t jx = rev ? (S.cur_before[t] - 1u - idx) : (S.cur_before[t] + idx);
+    const uint32_t tm = lay->tagmap[t][b];  // [0:3] member index, [4+4i : 8+4i) local code of the tag's i-th code
+    F4 ts = {0.f, 0.f, 0.f, 0.f};
+    uint32_t seen = 0;
+    for (int i = 0; i < (int)dsc.n_codes; i++) {   // as ml_prefetch / ml_to_probs, with a code the tag may list twice
+      const float p = ((float)ml[R.T.ml[t] + jx * dsc.n_codes + i] + 0.5f) / 256.0f;
+      const uint32_t kk = (tm >> (4 + 4 * i)) & 15u;
+#pragma unroll
+      for (int k = 0; k < MKP_KMAX; k++) if ((uint32_t)k == kk) {
+        if (seen & (1u << k)) { if (at(ts, k) + p > 1.01f) err = true; at(ts, k) = at(ts, k) + p; } else { at(ts, k) = p; seen |= 1u << k; }
+      }
+    }
+    if (merge_tag(dsc.neg ? S1 : S0, ts, seen, tm & 15u)) err = true;
+  }
+}
+// The position's groups, '+' then '-' mod strand of base b: hit pattern, the tags behind it (contrib: 8 groups x 8 tag bits, for
+// InvalidImplicitMode), classify_rule.  Up to two events; bit 12 marks the position's first.
+template <bool SAMPLE>
+__device__ __forceinline__ uint32_t general_classify(const MkpRunParams& prm, const uint8_t* __restrict__ bedmask, const uint32_t* lds_lay, int b,
+    uint32_t aln, uint32_t L, bool trimmable, GState& S0, GState& S1, uint32_t f, bool mapped, int32_t rpos, ReadAcc& acc, uint32_t& contrib_lo,
+    uint32_t& contrib_hi, uint32_t (&ev_info)[2], float (&sv)[2], int32_t& ev_pos) {
+  uint32_t ev_cnt = 0;
+#pragma unroll
+  for (int sg = 0; sg < 2; sg++) {
+    const int gi = sg * 4 + b;
+    const uint32_t* gp = lds_lay + MKP_LAYOUT_GROUP_DW + gi * 32;
+    const uint32_t gmisc = gp[0];
+    if (MKP_G_NMEM(gmisc) == 0) continue;
+    GState& S = sg ? S1 : S0;
+    int pat; uint32_t members;
+    if (!call_pattern(S.H, MKP_G_IMPL(gmisc), acc.err, pat, members)) continue;
+    const GroupRegs gr = load_group(gp);
+    const uint32_t tagbits = member_tagbits(members, gr.member_tags);
+    if (gi < 4) contrib_lo |= tagbits << (8 * gi); else contrib_hi |= tagbits << (8 * (gi - 4));
+    uint32_t info = 0; float v = 0.f;
+    if (!classify_rule<SAMPLE>(prm, bedmask, gr, gp[12 + pat], MKP_KMAX, b, sg, aln, L, trimmable, pat == MKP_PAT_INFERRED, S.pk, f, mapped, rpos,
+                               acc, info, v, ev_pos)) continue;
+    if (ev_cnt) { ev_info[1] = info; sv[1] = v; } else { ev_info[0] = SAMPLE ? info : (info | (1u << 12)); sv[0] = v; }
+    ev_cnt++;
+  }
+  return ev_cnt;
+}
 
-// NT = compile-time bound on the read's MM tag count (the entry point dispatches on it): every per-tag loop and
-// register array below is sized for the layout actually present instead of NT.
+// NT = compile-time bound on the read's MM tag count (the entry point dispatches on it): loops and register arrays are sized for it.
 template <bool SAMPLE, int NT>
-__device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads, const uint32_t* __restrict__ cigar,
-                 const uint8_t* __restrict__ seqs, const MkpTagRef* __restrict__ tagref, const uint32_t* __restrict__ ranks,
-                 const uint8_t* __restrict__ ml, const MkpLayout* __restrict__ layouts, const MkpRunParams& prm,
-                 MkpEvent* __restrict__ events, MkpReadOut* __restrict__ readout, uint32_t* __restrict__ dev_err,
-                 const uint8_t* __restrict__ bedmask, float* __restrict__ sample_vals, const uint32_t* __restrict__ read_ids,
-                     uint32_t* __restrict__ lds_layouts, uint32_t (*__restrict__ lds_marks)[64], const uint8_t* __restrict__ pdep4) {
+__device__ __forceinline__ void decode_read_body(DECODE_PARAMS(const MkpRunParams&), uint32_t* __restrict__ lds_layouts,
+    uint32_t (*__restrict__ lds_marks)[64], const uint8_t* __restrict__ pdep4) {
   const int lane = lane_id();
   uint32_t wib, rid; MkpReadHdr h; uint32_t* lds_lay;
   if (!read_prologue(hdrs, n_reads, read_ids, layouts, readout, lds_layouts, ~0u, wib, rid, h, lds_lay)) return;
@@ -312,256 +589,56 @@ __device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ 
   uint32_t* __restrict__ ordb = &lds_marks[wib * 7][0];                        // [NT][18] ordinal / position bitmaps of the chunk
   uint16_t* __restrict__ slots = reinterpret_cast<uint16_t*>(ordb + 192);                 // 512 compacted {lane, bit} entries
   const MkpLayout* lay = reinterpret_cast<const MkpLayout*>(lds_lay);
-  const uint32_t* __restrict__ seqw = reinterpret_cast<const uint32_t*>(seqs + h.seq_off);  // reads start 4-byte aligned
-  const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
-  const uint32_t L = h.l_seq;
-  const uint32_t nd = (L + 7u) >> 3;
-  const uint32_t aln = rev ? 1u : 0u;
   const int n_tags = (int)h.n_tags;
-
-  // per-tag cursors into the sorted rank lists: a merge join against the read's bases, 512 at a time
-  uint32_t t_off[NT], t_n[NT], t_ml[NT], t_cur[NT];
-  MkpTagDesc t_desc[NT];
-  uint32_t sbase[NB], tslot[NT], nb = 0;   // base slots: the distinct stored bases (A,C,G,T = 0..3) some tag counts
+  ReadWalk W; W.seqw = reinterpret_cast<const uint32_t*>(seqs + h.seq_off); W.L = h.l_seq; W.nd = (W.L + 7u) >> 3; W.rev = (h.flags & MKP_RF_REVERSE) != 0;
+  const bool rev = W.rev; const uint32_t L = W.L, aln = rev ? 1u : 0u;
+  GeneralTags<NT, NB> R; tag_lists<NT>(tagref, h.tag_off, n_tags, rev, R.T);
+  general_base_slots(R, lay, lds_lay, n_tags, rev);
+  if (rev) {
 #pragma unroll
-  for (int j = 0; j < NB; j++) sbase[j] = 0;
-#pragma unroll
-  for (int t = 0; t < NT; t++) {
-    t_off[t] = 0; t_n[t] = 0; t_ml[t] = 0; t_cur[t] = 0; tslot[t] = 0; t_desc[t] = lay->tags[t];
-    if (t < n_tags) {
-      const MkpTagRef tr = tagref[h.tag_off + t]; t_off[t] = tr.rank_off; t_n[t] = tr.n; t_ml[t] = tr.ml_off; t_cur[t] = rev ? tr.n : 0u;
-      if (t_desc[t].fb != 4) {
-        const uint32_t xb = (uint32_t)(rev ? 3 - t_desc[t].fb : t_desc[t].fb);
-        uint32_t found = nb;
-#pragma unroll
-        for (int j = 0; j < NB; j++) if ((uint32_t)j < nb && sbase[j] == xb) found = (uint32_t)j;
-        if (found == nb) {
-#pragma unroll
-          for (int j = 0; j < NB; j++) if ((uint32_t)j == nb) sbase[j] = xb;
-          nb++;
-        }
-        tslot[t] = (uint32_t)__builtin_amdgcn_readfirstlane((int)found);
-      }
-    }
-  }
-  nb = (uint32_t)__builtin_amdgcn_readfirstlane((int)nb);
-  // slots every occurrence of whose base is a call: groups with implicit-mode members (mod_bam.rs:1265-1292)
-  uint32_t implslots = 0;
-#pragma unroll
-  for (int j = 0; j < NB; j++) {
-    sbase[j] = (uint32_t)__builtin_amdgcn_readfirstlane((int)sbase[j]);
-    const uint32_t b = rev ? 3u - sbase[j] : sbase[j];
-    const uint32_t m0 = lds_lay[MKP_LAYOUT_GROUP_DW + b * 32], m1 = lds_lay[MKP_LAYOUT_GROUP_DW + (4 + b) * 32];
-    if ((uint32_t)j < nb && (MKP_G_IMPL(m0) | MKP_G_IMPL(m1))) implslots |= 1u << j;
-  }
-  implslots = (uint32_t)__builtin_amdgcn_readfirstlane((int)implslots);
-  // reverse reads need the totals up front (forward rank = total - inclusive count in stored order)
-  uint32_t tot[NB];
-#pragma unroll
-  for (int j = 0; j < NB; j++) tot[j] = 0;
-  if (rev && nb) {
-    uint32_t acc[NB];
-#pragma unroll
-    for (int j = 0; j < NB; j++) acc[j] = 0;
-    for (uint32_t d0 = 0; d0 < nd; d0 += 64) {
-      const uint32_t d = d0 + lane;
-      const uint32_t xl = linearize(d < nd ? seqw[d] : 0u);
-      const int nv = min(max((int)L - (int)(8u * d), 0), 8);
-      const uint32_t vmask = (1u << nv) - 1u;
-#pragma unroll
-      for (int j = 0; j < NB; j++) if ((uint32_t)j < nb) acc[j] += (uint32_t)__popc(match8(xl, (int)sbase[j]) & vmask);
-    }
-#pragma unroll
-    for (int j = 0; j < NB; j++) if ((uint32_t)j < nb) tot[j] = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(acc[j]), 63);
+    for (int j = 0; j < NB; j++) if ((uint32_t)j < R.nb) R.tot[j] = stored_base_total(W.seqw, W.nd, L, (int)R.sbase[j]);
   }
   ReadAcc acc; bool& err = acc.err;
-  const bool trimmable = read_trimmable(prm, L), collapse = collapse_on(prm);
-  uint32_t contrib_lo = 0, contrib_hi = 0;  // contrib: 8 groups x 8 tag bits
-  uint32_t cum[NB];
-#pragma unroll
-  for (int j = 0; j < NB; j++) cum[j] = 0;
-  uint32_t x_next = (uint32_t)lane < nd ? seqw[lane] : 0u;   // the next step's SEQ dword is always in flight
+  const bool trimmable = read_trimmable(prm, L);
+  uint32_t contrib_lo = 0, contrib_hi = 0;
+  uint32_t x_next = (uint32_t)lane < W.nd ? W.seqw[lane] : 0u;   // the next step's SEQ dword is always in flight
   CigarWin win; win.wr0 = h.ref_start;
 
-  for (uint32_t d0 = 0; d0 < nd && !err; d0 += 64) {
-    const uint32_t d = d0 + lane;
-    const uint32_t xl = linearize(x_next);
-    { const uint32_t dn = d + 64u; x_next = dn < nd ? seqw[dn] : 0u; }
-    const int nv = min(max((int)L - (int)(8u * d), 0), 8);
-    const uint32_t vmask = (1u << nv) - 1u;
-    uint32_t m8[NB], incl[NB], cnt[NB];
-    uint32_t U = 0;
-#pragma unroll
-    for (int j = 0; j < NB; j++) {
-      m8[j] = 0; incl[j] = 0; cnt[j] = 0;
-      if ((uint32_t)j < nb) {
-        m8[j] = match8(xl, (int)sbase[j]) & vmask; incl[j] = wave_incl_scan((uint32_t)__popc(m8[j]));
-          cnt[j] = (uint32_t)__builtin_amdgcn_readlane((int)incl[j], 63);
-        if ((implslots >> j) & 1u) U |= m8[j];
-      }
-    }
-    const uint32_t qa = 8u * d0, qb = min(qa + 512u, L);
-    uint32_t cur_before[NT];
-#pragma unroll
-    for (int t = 0; t < NT; t++) { cur_before[t] = t_cur[t]; if (t < n_tags && lane < 18) ordb[t * 18 + lane] = 0; }
-    // ---- 2. mark the calls of every tag that fall into this chunk
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-      if (t >= n_tags) break;
-#ifdef MKP_DEBUG
-      if (prm.debug_skip & 32u) break;   // ablation: no calls marked
-#endif
-      const MkpTagDesc dsc = t_desc[t];
-      const uint32_t sj = tslot[t];
-      uint32_t wlo, whi;   // window of keys this chunk can ask for (windows of successive chunks tile the key space)
-      if (dsc.fb == 4) { wlo = rev ? (L - qb) : qa; whi = rev ? (L - qa) : qb; }
-      else { const uint32_t c = selN<NB>(cum, sj), n = selN<NB>(cnt, sj); wlo = rev ? (selN<NB>(tot, sj) - c - n) : c; whi = wlo + n; }
-      const uint32_t kbase = dsc.fb == 4 ? qa : selN<NB>(cum, sj), ktot = dsc.fb == 4 ? L : selN<NB>(tot, sj);
-      for (;;) {
-        uint32_t e; bool hit; uint32_t nh;
-        if (!rev) { const uint32_t i = t_cur[t] + lane; const bool valid = i < t_n[t]; e = valid ? ranks[t_off[t] + i] : 0xffffffffu;
-          hit = valid && e < whi; nh = (uint32_t)__popcll(__ballot(hit)); t_cur[t] += nh; }
-        // an entry >= whi is past the last occurrence: never consumed -> error at the end
-        else { const uint32_t i = t_cur[t] - 64u + lane; const bool valid = (int32_t)i >= 0 && i < t_cur[t]; e = valid ? ranks[t_off[t] + i] : 0u;
-          hit = valid && e >= wlo && e < whi; nh = (uint32_t)__popcll(__ballot(hit)); t_cur[t] -= nh; }
-        if (nh == 0) break;
-        // chunk-relative stored ordinal of the call's base (specific-base tags) or stored position (`N` tags): one bit in LDS
-        const uint32_t ib = (rev ? (ktot - 1u - e) : e) - kbase;
-        if (hit) atomicOr(&ordb[t * 18 + (ib >> 5)], 1u << (ib & 31u));
-        if (nh < 64) break;
-      }
-    }
-    wave_lds_sync();
-    uint32_t pack_t[NT];
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-      pack_t[t] = 0;
-      if (t < n_tags) {
-        uint32_t bm;
-        if (t_desc[t].fb == 4) bm = (ordb[t * 18 + (lane >> 2)] >> ((lane & 3) * 8)) & 0xffu & vmask;
-        else {  // bits [excl, excl+cnt) of the ordinal bitmap deposited onto the set bits of the lane's match mask
-          const uint32_t m = selN<NB>(m8, tslot[t]), c = (uint32_t)__popc(m), ex = selN<NB>(incl, tslot[t]) - c;
-          const uint32_t w0 = ordb[t * 18 + (ex >> 5)], w1 = ordb[t * 18 + (ex >> 5) + 1];
-          const uint32_t f = __builtin_amdgcn_alignbit(w1, w0, ex & 31u) & ((1u << c) - 1u);
-          const uint32_t clo = (uint32_t)__popc(m & 15u);
-          bm = (uint32_t)pdep4[((m & 15u) << 4) | (f & 15u)] | ((uint32_t)pdep4[(m & 0xf0u) | ((f >> clo) & 15u)] << 4);
-        }
-        U |= bm; const uint32_t c2 = (uint32_t)__popc(bm); pack_t[t] = bm | ((wave_incl_scan(c2) - c2) << 8);
-      }
-    }
-    const uint32_t ucnt = (uint32_t)__popc(U);
-    const uint32_t uincl = wave_incl_scan(ucnt);
-    const uint32_t H = (uint32_t)__builtin_amdgcn_readlane((int)uincl, 63);
-    // compaction: every lane writes {lane, bit} of its called positions into the wave's slot list, in read order
-    { uint32_t ut = U, sidx = uincl - ucnt;
-      while (ut) { slots[sidx++] = (uint16_t)(((uint32_t)lane << 3) | ((uint32_t)__ffs((int)ut) - 1u)); ut &= ut - 1u; } }
-    wave_lds_sync();
-    // ---- 3. the called positions, 64 per batch, in read order
-    for (uint32_t g0 = 0; g0 < H && !err; g0 += 64) {
+  for (; W.d0 < W.nd && !err; W.d0 += 64) {
+    GeneralStep<NT, NB> S;
+    general_match_scan(S, R, W, x_next);
+    { const uint32_t dn = W.d0 + 64u + (uint32_t)lane; x_next = dn < W.nd ? W.seqw[dn] : 0u; }
+    general_mark_deposit(S, R, W, n_tags, prm, ranks, ordb, pdep4);
+    general_compact(S, slots);
+    for (uint32_t g0 = 0; g0 < S.H && !err; g0 += 64) {   // the called positions, 64 per batch, in read order
 #ifdef MKP_DEBUG
       if (prm.debug_skip & 16u) break;   // ablation: producer only
 #endif
-      const uint32_t g = g0 + lane;
-      const bool active = g < H;
-      const uint32_t slot = active ? (uint32_t)slots[g] : 0u;
+      const bool active = g0 + lane < S.H;
+      const uint32_t slot = active ? (uint32_t)slots[g0 + lane] : 0u;
       const int owner = (int)(slot >> 3);
-      const uint32_t bit = slot & 7u;
-      const uint32_t xo = __shfl(xl, owner, 64);
-      const uint32_t q = 8u * (d0 + (uint32_t)owner) + bit;
+      const uint32_t bit = slot & 7u, q = 8u * (W.d0 + (uint32_t)owner) + bit;
+      const uint32_t xo = __shfl(S.xl, owner, 64);   // from every lane: an owner may be inactive in the chunk's last batch
       const int x = active ? nib2base((xo >> (4u * bit)) & 15u) : -1;
       const uint32_t f = rev ? (L - 1 - q) : q;  // forward (as-sequenced) position
       const int b = x < 0 ? -1 : (rev ? 3 - x : x);
       GState S0, S1;
-#pragma unroll
-      for (int k = 0; k < MKP_KMAX; k++) { at(S0.pk, k) = 0.f; at(S1.pk, k) = 0.f; }
-      S0.H = S0.setmask = S1.H = S1.setmask = 0;
-      {
-#pragma unroll
-      for (int t = 0; t < NT; t++) {
-        if (t >= n_tags) break;
-        const MkpTagDesc dsc = t_desc[t];
-        const uint32_t pt = __shfl(pack_t[t], owner, 64);
-        const bool found = active && ((pt >> bit) & 1u);
-        if (!found) continue;
-        if (x < 0) { err = true; continue; }  // a call listed on a non-ACGT base (DnaBase::try_from, mod_bam.rs:1245)
-        const uint32_t idx = (pt >> 8) + (uint32_t)__popc(pt & ((1u << bit) - 1u));  // index among the tag's calls of this chunk, read order
-        const uint32_t jx = rev ? (cur_before[t] - 1u - idx) : (cur_before[t] + idx);
-        const uint32_t tm = lay->tagmap[t][b];  // [0:3] member index, [4+4i : 8+4i) local code of the tag's i-th code
-        const uint32_t mi = tm & 15u;
-        // get_base_mod_probs (mod_bam.rs:1242-1263): stride = #codes of the tag
-        F4 ts = {0.f, 0.f, 0.f, 0.f};
-        uint32_t seen = 0;
-        for (int i = 0; i < (int)dsc.n_codes; i++) {
-          const float p = ((float)ml[t_ml[t] + jx * dsc.n_codes + i] + 0.5f) / 256.0f;  // quals_to_probs 808-816
-          const uint32_t kk = (tm >> (4 + 4 * i)) & 15u;
-#pragma unroll
-          for (int k = 0; k < MKP_KMAX; k++) if ((uint32_t)k == kk) {
-            if (seen & (1u << k)) { if (at(ts, k) + p > 1.01f) err = true; at(ts, k) = at(ts, k) + p; } else { at(ts, k) = p; seen |= 1u << k; }
-          }
-        }
-        if (dsc.neg) { if (merge_tag(S1, ts, seen, mi)) err = true; } else { if (merge_tag(S0, ts, seen, mi)) err = true; }
-      }
-      }
-      // reference position of the call's base (CigarWin)
+      general_position_probs(S, R, lay, n_tags, rev, ml, active, owner, bit, x, b, S0, S1, err);
       bool mapped = false; int32_t rpos = 0;
       cigar_map(win, h, cigar, active && x >= 0, q, mapped, rpos);
-      uint32_t ev_info[2]; float sv[2] = {0.f, 0.f}; uint32_t ev_cnt = 0; int32_t ev_pos = 0;
-      if (active && x >= 0) {
-        const bool keep_edge = edge_keep(prm, f, L);
-        bool dec_done = false;
-#pragma unroll
-        for (int sg = 0; sg < 2; sg++) {
-          const uint32_t* gp = lds_lay + MKP_LAYOUT_GROUP_DW + (sg * 4 + b) * 32;
-          const uint32_t gmisc = gp[0];
-          const int nm = (int)MKP_G_NMEM(gmisc);
-          if (nm == 0) continue;
-          F4& spk = sg ? S1.pk : S0.pk;
-          const uint32_t SH = sg ? S1.H : S0.H;
-          const uint32_t impl = MKP_G_IMPL(gmisc);
-          int pat; uint32_t member_contrib;
-          if (!call_pattern(SH, impl, err, pat, member_contrib)) continue;
-          const GroupRegs gr = load_group(gp);
-          const uint32_t pv = gp[12 + pat];
-          const uint32_t tagbits = member_tagbits(member_contrib, gr.member_tags);
-          const int gi = sg * 4 + b;
-          if (gi < 4) contrib_lo |= tagbits << (8 * gi); else contrib_hi |= tagbits << (8 * (gi - 4));
-          if (!trimmable || !keep_edge) continue;
-          const uint32_t tally = aln ^ (uint32_t)sg;  // read_cache.rs:181-188 / FeatureVector::add_feature
-          if (SAMPLE) {
-            if (!sample_keep(prm, bedmask, mapped, rpos, tally)) continue;
-            acc.any_surviving = true;
-            // 2 `summary`: thresholded + argmax class; 3 `extract calls`: + forward position, mod strand, inferred, call_prob
-            if (prm.sample_mode >= 2) {
-              // the collapse left no code in the map: no profile row (iter_probs is empty)
-              if (prm.sample_mode == 3 && ((pv >> 3) & 7u) == 0u) continue;
-              uint32_t ob = 0; float am = 0.f; uint32_t inf = summary_info(gr, pv, spk, collapse, &ob, MKP_KMAX, &am);
-              if (prm.sample_mode == 3) { inf |= ((uint32_t)sg << 2) | ((pat == MKP_PAT_INFERRED ? 1u : 0u) << 3); ev_pos = (int32_t)f; }
-              sv[ev_cnt] = prm.sample_mode == 3 ? am : 0.f; ev_info[ev_cnt++] = inf; acc.obs0 |= ob; continue;
-            }
-            sv[ev_cnt] = argmax_group(gr, pv, spk, collapse);
-            ev_info[ev_cnt++] = MKP_G_TB(gr.misc);
-            continue;
-          }
-          acc.any_surviving = true;
-          uint32_t ob = 0;
-          const int cls = call_group(gr, pv, spk, collapse, &ob);
-          if (tally) acc.obs1 |= ob; else acc.obs0 |= ob;
-          if (mapped) {
-            ev_info[ev_cnt++] = call_cid(gr, cls) | (tally << 8) | ((uint32_t)b << 9) | (aln << 11) | (dec_done ? 0u : (1u << 12));
-            dec_done = true;
-            ev_pos = rpos;
-          }
-        }
-      }
+      uint32_t ev_info[2]; float sv[2] = {0.f, 0.f}; uint32_t ev_cnt = 0; int32_t ev_pos = SAMPLE ? 0 : rpos;
+      if (active && x >= 0)
+        ev_cnt = general_classify<SAMPLE>(prm, bedmask, lds_lay, b, aln, L, trimmable, S0, S1, f, mapped, rpos, acc, contrib_lo, contrib_hi,
+                                          ev_info, sv, ev_pos);
       append_events<SAMPLE, 2>(events, sample_vals, dev_err, h.event_off, h.event_cap, ev_cnt, (uint32_t)ev_pos, ev_info, sv, acc);
       err = __any(err);
     }
 #pragma unroll
-    for (int j = 0; j < NB; j++) cum[j] += cnt[j];
+    for (int j = 0; j < NB; j++) R.cum[j] += S.cnt[j];
     err = __any(err);
   }
 #pragma unroll
-  for (int t = 0; t < NT; t++) if (t < n_tags && list_left_over(rev, t_cur[t], t_n[t])) err = true;
+  for (int t = 0; t < NT; t++) if (t < n_tags && list_left_over(rev, R.T.cur[t], R.T.n[t])) err = true;
   if (!prm.force_allow && !SAMPLE) {   // InvalidImplicitMode, per group
     contrib_lo = wave_or(contrib_lo); contrib_hi = wave_or(contrib_hi);
     for (int gi = 0; gi < 8; gi++)
@@ -570,235 +647,349 @@ __device__ __forceinline__ void decode_read_body(const MkpReadHdr* __restrict__ 
   read_epilogue(readout, rid, acc, false);
 }
 
+// ----------------------------------------------------------------------------------------------
+// The single-group decoders, FAST and SPARSE: a producer/consumer inside the wave.  The producer's steps only *locate* calls and append
+// {stored position, ML call index per tag} to a queue in LDS (SoA columns); whenever 64 calls are queued consume_batch runs the per-call
+// work on a full batch (a 1024-base step of CpG data finds ~13 calls).  Group descriptor, thresholds, code maps: wave-uniform (SGPRs).
+// The one (mod strand, base) group of the decoder's tags tb .. tb+n_tags: descriptor (words at gp), stored base counted, the
+// tags' constants (tag_setup), and the hit pattern / code set of a call that every tag lists.  Wave-uniform.
+template <int NT> struct GroupCalls {
+  GroupRegs g; const uint32_t* gp; int b0, sg0, xs; uint32_t kcodes, impl, SH_all, setmask_all;
+  uint32_t t_nc[NT], tmu[NT], codes_t[NT];
+};
+template <int NT>
+__device__ __forceinline__ void group_setup(const MkpLayout* lay, const uint32_t* lds_lay, int tb, int n_tags, bool rev, GroupCalls<NT>& G) {
+  G.b0 = (int)lay->tags[tb].fb & 3; G.sg0 = (int)lay->tags[tb].neg & 1;
+  G.xs = rev ? 3 - G.b0 : G.b0;
+  G.gp = lds_lay + MKP_LAYOUT_GROUP_DW + (G.sg0 * 4 + G.b0) * 32;
+  G.g = load_group_uniform(G.gp);
+  G.impl = MKP_G_IMPL(G.g.misc);
+  G.kcodes = (G.g.misc >> 20) & 7u;   // codes of the group: bounds every per-code loop
+  tag_setup<NT>(lay, tb, n_tags, G.b0, G.t_nc, G.tmu, G.codes_t);
+  G.SH_all = 0; G.setmask_all = 0;
+#pragma unroll
+  for (int t = 0; t < NT; t++) if (t < n_tags) { G.SH_all |= 1u << (G.tmu[t] & 15u); G.setmask_all |= G.codes_t[t]; }
+}
+// where a read's events go: its slice of the event list
+struct EventSink { MkpEvent* __restrict__ events; float* __restrict__ sample_vals; uint32_t* __restrict__ dev_err; uint32_t ev_base, ev_cap; };
+
+// Consumer: up to 64 queued calls, in read order, one per lane: ml_prefetch, CIGAR mapping (map_window on the decoder's window),
+// ml_to_probs, classify_call, append_events.  q_j[t] = the queue column holding tag t's ML call index.  INFER: the group may
+// have implicit-mode members and a tag may not list a call (index ~0); else every tag lists every call and never infers.
+template <bool SAMPLE, bool INFER, int NT, class Win>
+__device__ __forceinline__ void consume_batch(const MkpRunParams& prm, const uint8_t* __restrict__ bedmask, const uint8_t* __restrict__ ml,
+    const GroupCalls<NT>& G, const uint32_t (&t_ml)[NT], int n_tags, const ReadWalk& W, bool trimmable, const uint32_t* __restrict__ q_pos,
+    uint32_t* const (&q_j)[NT], uint32_t& qhead, uint32_t qcount, Win& win, const MkpReadHdr& h, const uint32_t* __restrict__ cigar,
+    const EventSink& out, ReadAcc& acc, uint32_t& contribH) {
+  const uint32_t lane = (uint32_t)lane_id(), nb = min(64u, qcount - qhead);
+  const bool active = lane < nb;
+  const uint32_t q = active ? q_pos[qhead + lane] : 0u;
+  const uint32_t f = W.rev ? (W.L - 1 - q) : q;  // forward (as-sequenced) position
+  uint32_t mlq[NT][MKP_KMAX], jx[NT]; bool found[NT];
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    if (INFER) { jx[t] = (t < n_tags && active) ? q_j[t][qhead + lane] : 0xffffffffu; found[t] = jx[t] != 0xffffffffu; }
+    else { jx[t] = active ? q_j[t][qhead + lane] : 0u; found[t] = active; }
+  }
+  ml_prefetch<NT>(ml, n_tags, t_ml, G.t_nc, found, jx, mlq);
+  bool mapped = false; int32_t rpos = 0;
+#ifdef MKP_DEBUG
+  if (!INFER && (prm.debug_skip & 32u)) { mapped = active; rpos = h.ref_start + (int32_t)q; } else   // ablation: no CIGAR mapping
+#endif
+  map_window<SAMPLE>(win, h, cigar, active, q, mapped, rpos);
+  F4 pk = {0.f, 0.f, 0.f, 0.f};
+  uint32_t SH = G.SH_all, setmask = G.setmask_all;   // the members whose tags list the call, their local codes
+  bool check = active && n_tags > 1;
+  if (INFER) {
+    SH = 0; setmask = 0;
+#pragma unroll
+    for (int t = 0; t < NT; t++) { SH |= found[t] ? (1u << (G.tmu[t] & 15u)) : 0u; setmask |= found[t] ? G.codes_t[t] : 0u; }
+    check = __popc(SH) >= 2;
+  }
+  if (ml_to_probs<NT>(mlq, n_tags, G.t_nc, G.tmu, found, setmask, check, pk)) acc.err = true;
+  uint32_t ev_info[1] = {0}; float sv[1] = {0.f}; bool has_ev = false;
+  if (active && (!INFER || (SH | G.impl)))
+    has_ev = classify_call<SAMPLE, INFER>(prm, bedmask, G.g, G.gp, (int)G.kcodes, G.b0, G.sg0, W.rev ? 1u : 0u, W.L, trimmable, SH, G.impl, pk, f,
+                                          mapped, rpos, acc, contribH, ev_info[0], sv[0]);
+  append_events<SAMPLE, 1>(out.events, out.sample_vals, out.dev_err, out.ev_base, out.ev_cap, has_ev ? 1u : 0u, (uint32_t)rpos, ev_info, sv, acc);
+  acc.err = __any(acc.err);
+  qhead += nb;
+}
+// InvalidImplicitMode of the one group, once the read is walked
+template <bool SAMPLE, int NT>
+__device__ __forceinline__ void group_epilogue(const MkpRunParams& prm, const MkpLayout* lay, const GroupCalls<NT>& G, uint32_t contribH,
+    ReadAcc& acc) {
+  if (!prm.force_allow && !SAMPLE && lacks_mode(member_tagbits(wave_or(contribH), G.g.member_tags), lay->default_mask)) acc.err = true;
+}
 
 // ----------------------------------------------------------------------------------------------
 // Decode, FAST layouts (MkpLayout::fast: every tag on the same specific base and mod strand, no code listed twice —
-// `C+m?`, `C+hm?`, `C+h?;C+m?`, ...; NT <= 2 tags).  Same semantics as decode_read_body, restructured as a
-// producer/consumer inside the wave: the 1024-base steps (16 bases per lane) only *locate* calls and append {stored position, ML index per
-// tag} to a queue in LDS; whenever 64 calls are queued one full batch runs the per-call work: ml_prefetch, cigar_map,
-// ml_to_probs, classify_call<SAMPLE, INFER = true>, append_events.  With CpG data a step finds ~13 calls, so batches run at full
-// lane occupancy instead of ~20 %.  The group descriptor, thresholds and code maps are wave-uniform (SGPRs).
+// `C+m?`, `C+hm?`, `C+h?;C+m?`, ...; NT <= 2 tags).  Same semantics as decode_read_body.  1024-base steps, 16 bases per lane:
+//   fast_locate_step    match mask and wave scan of the counted base, the tags' ranks of the step's window marked in the ordinal
+//                       bitmap and deposited onto the match mask, scan of the union (plus every occurrence for implicit members);
+//   fast_append_half    the located calls go to the queue in two halves (lanes 0-31, then 32-63), so that the queue never has
+//                       to take more than 512 entries at once;
+//   consume_batch<INFER = true>.
 #define MKP_QCAP 576   // 63 left over + up to 512 from half a step (32 lanes x 16 bases)
 #define MKP_ORD_WORDS 34   // ordinal bitmap of a 1024-base step: 32 words + 2 for the 64-bit window read
+template <int NT> struct FastStep {
+  uint32_t xn0, xn1;                      // the next step's SEQ dwords (two per lane), always in flight
+  bool pend = false;                      // the located step's upper lanes still hold calls
+  uint32_t cntT = 0;                      // occurrences of the base in the step
+  uint32_t U = 0, uexcl = 0;              // the lane's calls (bit per base), the calls of the lanes below
+  uint32_t H = 0, HA = 0;                 // calls of the step, of its lanes 0-31
+  uint32_t bm[NT], texcl[NT], cur[NT];    // per tag: the lane's listed calls, those of the lanes below, the cursor before the step
+};
+template <int NT>
+__device__ __forceinline__ void fast_fetch_seq(FastStep<NT>& S, const ReadWalk& W, uint32_t dstep) {
+  const uint32_t d = dstep + 2u * (uint32_t)lane_id();
+  S.xn0 = d < W.nd ? W.seqw[d] : 0u; S.xn1 = d + 1u < W.nd ? W.seqw[d + 1u] : 0u;
+}
+template <int NT>
+__device__ __forceinline__ void fast_locate_step(FastStep<NT>& S, const ReadWalk& W, TagLists<NT>& T, int n_tags, int xs, bool implicit,
+    const uint32_t* __restrict__ ranks, uint32_t* __restrict__ ordb, const uint8_t* __restrict__ pdep4) {
+  const uint32_t lane = (uint32_t)lane_id();
+  const uint32_t d = W.d0 + 2u * lane;          // this lane's first dword: bases [8d, 8d+16)
+  const uint32_t xl0 = linearize(S.xn0), xl1 = linearize(S.xn1);
+  fast_fetch_seq(S, W, W.d0 + 128u);
+  // the first 64 ranks at every tag's cursor are requested now, ahead of the match/scan work that decides how many are used
+  RankBatch pre[NT];
+#pragma unroll
+  for (int t = 0; t < NT; t++) { pre[t].e = 0; pre[t].valid = false; if (t < n_tags) pre[t] = rank_batch(ranks, T.off[t], T.n[t], T.cur[t], W.rev); }
+  const int nv = min(max((int)W.L - (int)(8u * d), 0), 16);
+  const uint32_t m16 = (match8(xl0, xs) | (match8(xl1, xs) << 8)) & ((1u << nv) - 1u);
+  const uint32_t c = (uint32_t)__popc(m16), incl = wave_incl_scan(c);
+  const uint32_t cntT = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  const uint32_t wlo = W.rev ? (W.tot - W.cum - cntT) : W.cum, whi = wlo + cntT;   // rank window of this step
+#pragma unroll
+  for (int t = 0; t < NT; t++) { S.cur[t] = T.cur[t]; if (t < n_tags && lane < MKP_ORD_WORDS) ordb[t * MKP_ORD_WORDS + lane] = 0; }
+#pragma unroll
+  for (int t = 0; t < NT; t++)
+    if (t < n_tags) mark_window(ranks, T.off[t], T.n[t], T.cur[t], W.rev, pre[t], wlo, whi, W.tot, W.cum, ordb + t * MKP_ORD_WORDS);
+  wave_lds_sync();
+  uint32_t U = implicit ? m16 : 0u, uincl = 0, ucnt = 0;
+#pragma unroll
+  for (int t = 0; t < NT; t++) {
+    S.bm[t] = 0; S.texcl[t] = 0;
+    if (t < n_tags) {
+      S.bm[t] = deposit_marks<16>(ordb + t * MKP_ORD_WORDS, pdep4, m16, incl - c);
+      U |= S.bm[t];
+      const uint32_t c2 = (uint32_t)__popc(S.bm[t]);
+      uincl = wave_incl_scan(c2); ucnt = c2; S.texcl[t] = uincl - c2;
+    }
+  }
+  if (NT > 1 || implicit) { ucnt = (uint32_t)__popc(U); uincl = wave_incl_scan(ucnt); }   // else U == bm[0]: its scan is already there
+  S.U = U; S.uexcl = uincl - ucnt; S.cntT = cntT;
+  S.H = (uint32_t)__builtin_amdgcn_readlane((int)uincl, 63); S.HA = (uint32_t)__builtin_amdgcn_readlane((int)uincl, 31);
+}
+// append one half's calls: lanes 0-31 first, lanes 32-63 on the next visit; the step is done when no half is left
+template <int NT>
+__device__ __forceinline__ void fast_append_half(FastStep<NT>& S, ReadWalk& W, uint32_t* __restrict__ q_pos, uint32_t* const (&q_j)[NT],
+    uint32_t& qcount) {
+  const bool mine = S.pend ? (lane_id() >= 32) : (lane_id() < 32);
+  const uint32_t d = W.d0 + 2u * (uint32_t)lane_id();   // the lane's first dword, as the step was located
+  uint32_t ut = mine ? S.U : 0u, sidx = qcount + S.uexcl - (S.pend ? S.HA : 0u);
+  while (ut) {
+    const uint32_t bit = (uint32_t)__ffs((int)ut) - 1u, below = (1u << bit) - 1u;
+    q_pos[sidx] = 8u * d + bit;
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+      const uint32_t idx = S.texcl[t] + (uint32_t)__popc(S.bm[t] & below);
+      const uint32_t jx = W.rev ? (S.cur[t] - 1u - idx) : (S.cur[t] + idx);
+      q_j[t][sidx] = ((S.bm[t] >> bit) & 1u) ? jx : 0xffffffffu;
+    }
+    sidx++; ut &= ut - 1u;
+  }
+  wave_lds_sync();
+  qcount += S.pend ? (S.H - S.HA) : S.HA;
+  if (!S.pend && S.H > S.HA) S.pend = true;
+  else { S.pend = false; W.cum += S.cntT; W.d0 += 128; }
+}
+
 template <bool SAMPLE, int NT>
-__device__ __forceinline__ void decode_read_fast(const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads, const uint32_t* __restrict__ cigar,
-                 const uint8_t* __restrict__ seqs, const MkpTagRef* __restrict__ tagref, const uint32_t* __restrict__ ranks,
-                 const uint8_t* __restrict__ ml, const MkpLayout* __restrict__ layouts, const MkpRunParams& prm,
-                 MkpEvent* __restrict__ events, MkpReadOut* __restrict__ readout, uint32_t* __restrict__ dev_err,
-                 const uint8_t* __restrict__ bedmask, float* __restrict__ sample_vals, uint32_t* __restrict__ lds_layouts,
-                 const uint32_t* __restrict__ read_ids, uint32_t* __restrict__ lds_ord, const uint8_t* __restrict__ pdep4,
-                     uint32_t* __restrict__ lds_queue) {
+__device__ __forceinline__ void decode_read_fast(DECODE_PARAMS(const MkpRunParams&), uint32_t* __restrict__ lds_layouts,
+    uint32_t* __restrict__ lds_ord, const uint8_t* __restrict__ pdep4, uint32_t* __restrict__ lds_queue) {
   static_assert(NT <= 2, "the call queue holds two ML indices per entry");
-  const int lane = lane_id();
   uint32_t wib, rid; MkpReadHdr h; uint32_t* lds_lay;
   if (!read_prologue(hdrs, n_reads, read_ids, layouts, readout, lds_layouts, ~0u, wib, rid, h, lds_lay)) return;
   uint32_t* __restrict__ ordb = lds_ord + wib * (NT * MKP_ORD_WORDS);   // [NT][MKP_ORD_WORDS] ordinal bitmaps of the step
   // queue, SoA: stored position, ML call index of tag 0 / 1 (~0 = not listed)
   uint32_t* __restrict__ q_pos = lds_queue + wib * ((1 + NT) * MKP_QCAP);
-  uint32_t* __restrict__ q_j0 = q_pos + MKP_QCAP;
-  uint32_t* __restrict__ q_j1 = q_pos + (NT > 1 ? 2 : 1) * MKP_QCAP;
+  uint32_t* q_j[NT];
+  for (int t = 0; t < NT; t++) q_j[t] = q_pos + (1 + t) * MKP_QCAP;
   const MkpLayout* lay = reinterpret_cast<const MkpLayout*>(lds_lay);
-  const uint32_t* __restrict__ seqw = reinterpret_cast<const uint32_t*>(seqs + h.seq_off);
-  const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
-  const uint32_t L = h.l_seq, nd = (L + 7u) >> 3, aln = rev ? 1u : 0u;
   const int n_tags = (int)h.n_tags;
-  const int b0 = (int)lay->tags[0].fb & 3, sg0 = (int)lay->tags[0].neg & 1;
-  const int xs = rev ? 3 - b0 : b0;                                   // the stored base the tags count
-  const uint32_t* gp0 = lds_lay + MKP_LAYOUT_GROUP_DW + (sg0 * 4 + b0) * 32;
-  const GroupRegs grp0 = load_group_uniform(gp0);
-  const uint32_t impl0 = MKP_G_IMPL(grp0.misc);
-  const int kcodes0 = (int)((grp0.misc >> 20) & 7u);   // codes of the group: bounds every per-code loop
-  uint32_t t_off[NT], t_n[NT], t_ml[NT], t_cur[NT], t_nc[NT], tmu[NT], codes_t[NT];
-  tag_setup<NT>(lay, 0, n_tags, b0, t_nc, tmu, codes_t);
-#pragma unroll
-  for (int t = 0; t < NT; t++) {
-    t_off[t] = 0; t_n[t] = 0; t_ml[t] = 0; t_cur[t] = 0;
-    if (t < n_tags) { const MkpTagRef tr = tagref[h.tag_off + t]; t_off[t] = tr.rank_off; t_n[t] = tr.n; t_ml[t] = tr.ml_off; t_cur[t] = rev ? tr.n : 0u; }
-  }
-  // reverse reads need the total up front (forward rank = total - inclusive count in stored order); 4 loads in flight
-  uint32_t tot = 0;
-  if (rev) {
-    uint32_t acc = 0;
-    for (uint32_t d0 = 0; d0 < nd; d0 += 256) {
-      uint32_t xw[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) { const uint32_t dd = d0 + 64u * j + lane; xw[j] = dd < nd ? seqw[dd] : 0u; }
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint32_t dd = d0 + 64u * j + lane;
-        const int nv = min(max((int)L - (int)(8u * dd), 0), 8);
-        acc += (uint32_t)__popc(match8(linearize(xw[j]), xs) & ((1u << nv) - 1u));
-      }
-    }
-    tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(acc), 63);
-  }
-  ReadAcc acc; bool& err = acc.err;
-  const bool trimmable = read_trimmable(prm, L);
-  uint32_t contribH = 0, cum = 0;
+  ReadWalk W; W.seqw = reinterpret_cast<const uint32_t*>(seqs + h.seq_off); W.L = h.l_seq; W.nd = (W.L + 7u) >> 3; W.rev = (h.flags & MKP_RF_REVERSE) != 0;
+  GroupCalls<NT> G; group_setup<NT>(lay, lds_lay, 0, n_tags, W.rev, G);
+  TagLists<NT> T; tag_lists<NT>(tagref, h.tag_off, n_tags, W.rev, T);
+  if (W.rev) W.tot = stored_base_total(W.seqw, W.nd, W.L, G.xs);
+  ReadAcc acc;
+  const bool trimmable = read_trimmable(prm, W.L);
+  const EventSink out = {events, sample_vals, dev_err, h.event_off, h.event_cap};
+  uint32_t contribH = 0, qhead = 0, qcount = 0;
   CigarWin win; win.wr0 = h.ref_start;
-  uint32_t qhead = 0, qcount = 0, d0 = 0;
-  // the next step's SEQ dwords (two per lane = 16 bases) are always in flight
-  uint32_t x_next0 = 2u * (uint32_t)lane < nd ? seqw[2u * lane] : 0u, x_next1 = 2u * (uint32_t)lane + 1u < nd ? seqw[2u * lane + 1u] : 0u;
-  // a step's located calls are appended in two halves (lanes 0-31, then 32-63) so the queue never has to take more than
-  // 512 entries at once; these hold the step's state between the halves
-  bool pend = false;
-  uint32_t st_U = 0, st_uincl = 0, st_ucnt = 0, st_HA = 0, st_H = 0, st_cntT = 0, st_d = 0;
-  uint32_t st_bm[NT], st_texcl[NT], st_cur[NT];
-#pragma unroll
-  for (int t = 0; t < NT; t++) { st_bm[t] = 0; st_texcl[t] = 0; st_cur[t] = 0; }
+  FastStep<NT> S; fast_fetch_seq(S, W, 0);
+  for (int t = 0; t < NT; t++) { S.bm[t] = 0; S.texcl[t] = 0; S.cur[t] = 0; }
 
-  for (;;) {
-    if (err) break;
-    if (qcount - qhead < 64u && (pend || d0 < nd)) {
-      // ---- producer: one 1024-base step locates its calls; each half of the lanes appends them to the queue
+  while (!acc.err) {
+    if (qcount - qhead < 64u && (S.pend || W.d0 < W.nd)) {   // producer
       if (qhead) queue_to_front<1 + NT>(q_pos, MKP_QCAP, qhead, qcount);
-      if (!pend) {
-        const uint32_t d = d0 + 2u * (uint32_t)lane;          // this lane's first dword: bases [8d, 8d+16)
-        const uint32_t xl0 = linearize(x_next0), xl1 = linearize(x_next1);
-        { const uint32_t dn = d + 128u; x_next0 = dn < nd ? seqw[dn] : 0u; x_next1 = dn + 1u < nd ? seqw[dn + 1u] : 0u; }
-        // the first 64 ranks at every tag's cursor are requested now, ahead of the match/scan work that decides how many are used
-        uint32_t e_pre[NT]; bool v_pre[NT];
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-          e_pre[t] = rev ? 0u : 0xffffffffu; v_pre[t] = false;
-          if (t < n_tags) {
-            const uint32_t i = rev ? (t_cur[t] - 64u + lane) : (t_cur[t] + lane);
-            v_pre[t] = rev ? ((int32_t)i >= 0 && i < t_cur[t]) : (i < t_n[t]);
-            if (v_pre[t]) e_pre[t] = ranks[t_off[t] + i];
-          }
-        }
-        const int nv = min(max((int)L - (int)(8u * d), 0), 16);
-        const uint32_t m16 = (match8(xl0, xs) | (match8(xl1, xs) << 8)) & ((1u << nv) - 1u);
-        const uint32_t c = (uint32_t)__popc(m16), incl = wave_incl_scan(c);
-        const uint32_t cntT = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-        const uint32_t wlo = rev ? (tot - cum - cntT) : cum, whi = wlo + cntT;   // rank window of this step
-#pragma unroll
-        for (int t = 0; t < NT; t++) { st_cur[t] = t_cur[t]; if (t < n_tags && lane < MKP_ORD_WORDS) ordb[t * MKP_ORD_WORDS + lane] = 0; }
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-          if (t >= n_tags) break;
-          for (bool first = true;; first = false) {
-            uint32_t e; bool hit, valid; uint32_t nh;
-            if (first) { e = e_pre[t]; valid = v_pre[t]; }
-            else if (!rev) { const uint32_t i = t_cur[t] + lane; valid = i < t_n[t]; e = valid ? ranks[t_off[t] + i] : 0xffffffffu; }
-            else { const uint32_t i = t_cur[t] - 64u + lane; valid = (int32_t)i >= 0 && i < t_cur[t]; e = valid ? ranks[t_off[t] + i] : 0u; }
-            if (!rev) { hit = valid && e < whi; nh = (uint32_t)__popcll(__ballot(hit)); t_cur[t] += nh; }
-            // an entry >= whi is past the last occurrence: never consumed -> error at the end
-            else { hit = valid && e >= wlo && e < whi; nh = (uint32_t)__popcll(__ballot(hit)); t_cur[t] -= nh; }
-            if (nh == 0) break;
-            const uint32_t ib = (rev ? (tot - 1u - e) : e) - cum;   // step-relative stored ordinal of the called base (< 1024)
-            if (hit) atomicOr(&ordb[t * MKP_ORD_WORDS + (ib >> 5)], 1u << (ib & 31u));
-            if (nh < 64) break;
-          }
-        }
-        wave_lds_sync();
-        uint32_t U = impl0 ? m16 : 0u, uincl = 0, ucnt = 0;
-        const uint32_t ex = incl - c;
-        const uint32_t n0 = m16 & 15u, n1 = (m16 >> 4) & 15u, n2 = (m16 >> 8) & 15u, n3 = m16 >> 12;
-        const uint32_t c0n = (uint32_t)__popc(n0), c1n = c0n + (uint32_t)__popc(n1), c2n = c1n + (uint32_t)__popc(n2);
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-          st_bm[t] = 0; st_texcl[t] = 0;
-          if (t < n_tags) {  // bits [excl, excl+cnt) of the ordinal bitmap deposited onto the set bits of the lane's 16-base match mask
-            const uint32_t w0 = ordb[t * MKP_ORD_WORDS + (ex >> 5)], w1 = ordb[t * MKP_ORD_WORDS + (ex >> 5) + 1];
-            const uint32_t f = __builtin_amdgcn_alignbit(w1, w0, ex & 31u) & ((1u << c) - 1u);
-            st_bm[t] = (uint32_t)pdep4[(n0 << 4) | (f & 15u)] | ((uint32_t)pdep4[(n1 << 4) | ((f >> c0n) & 15u)] << 4) |
-                       ((uint32_t)pdep4[(n2 << 4) | ((f >> c1n) & 15u)] << 8) | ((uint32_t)pdep4[(n3 << 4) | ((f >> c2n) & 15u)] << 12);
-            U |= st_bm[t];
-            const uint32_t c2 = (uint32_t)__popc(st_bm[t]);
-            uincl = wave_incl_scan(c2); ucnt = c2; st_texcl[t] = uincl - c2;
-          }
-        }
-        if (NT > 1 || impl0) { ucnt = (uint32_t)__popc(U); uincl = wave_incl_scan(ucnt); }   // else U == bm[0]: its scan is already there
-        st_U = U; st_uincl = uincl; st_ucnt = ucnt; st_d = d; st_cntT = cntT;
-        st_H = (uint32_t)__builtin_amdgcn_readlane((int)uincl, 63); st_HA = (uint32_t)__builtin_amdgcn_readlane((int)uincl, 31);
-      }
-      {  // append this half's calls: lanes 0-31 first, lanes 32-63 on the next visit
-        const bool mine = pend ? (lane >= 32) : (lane < 32);
-        uint32_t ut = mine ? st_U : 0u, sidx = qcount + st_uincl - st_ucnt - (pend ? st_HA : 0u);
-        while (ut) {
-          const uint32_t bit = (uint32_t)__ffs((int)ut) - 1u, below = (1u << bit) - 1u;
-          q_pos[sidx] = 8u * st_d + bit;
-#pragma unroll
-          for (int t = 0; t < NT; t++) {
-            const uint32_t idx = st_texcl[t] + (uint32_t)__popc(st_bm[t] & below);
-            const uint32_t jx = rev ? (st_cur[t] - 1u - idx) : (st_cur[t] + idx);
-            (t == 0 ? q_j0 : q_j1)[sidx] = ((st_bm[t] >> bit) & 1u) ? jx : 0xffffffffu;
-          }
-          sidx++; ut &= ut - 1u;
-        }
-        wave_lds_sync();
-        qcount += pend ? (st_H - st_HA) : st_HA;
-        if (!pend && st_H > st_HA) pend = true;                  // the upper lanes still hold calls
-        else { pend = false; cum += st_cntT; d0 += 128; }        // step done
-      }
+      if (!S.pend) fast_locate_step(S, W, T, n_tags, G.xs, G.impl != 0u, ranks, ordb, pdep4);
+      fast_append_half(S, W, q_pos, q_j, qcount);
       continue;
     }
     if (qcount == qhead) break;
 #ifdef MKP_DEBUG
     if (prm.debug_skip & 16u) { qhead = qcount; continue; }   // ablation: producer only
 #endif
-    // ---- consumer: up to 64 queued calls, in read order
-    const uint32_t nb = min(64u, qcount - qhead);
-    const bool active = (uint32_t)lane < nb;
-    const uint32_t q = active ? q_pos[qhead + lane] : 0u;
-    const uint32_t f = rev ? (L - 1 - q) : q;  // forward (as-sequenced) position
-    uint32_t mlq[NT][MKP_KMAX], jx[NT]; bool found_t[NT];
-#pragma unroll
-    for (int t = 0; t < NT; t++) {
-      jx[t] = (t < n_tags && active) ? (t == 0 ? q_j0 : q_j1)[qhead + lane] : 0xffffffffu;
-      found_t[t] = jx[t] != 0xffffffffu;
-    }
-    ml_prefetch<NT>(ml, n_tags, t_ml, t_nc, found_t, jx, mlq);
-    bool mapped = false; int32_t rpos = 0;
-    cigar_map(win, h, cigar, active, q, mapped, rpos);
-    F4 pk = {0.f, 0.f, 0.f, 0.f};
-    uint32_t SH = 0, setmask = 0;   // the members whose tags list the call, their local codes
-#pragma unroll
-    for (int t = 0; t < NT; t++) { SH |= found_t[t] ? (1u << (tmu[t] & 15u)) : 0u; setmask |= found_t[t] ? codes_t[t] : 0u; }
-    if (ml_to_probs<NT>(mlq, n_tags, t_nc, tmu, found_t, setmask, __popc(SH) >= 2, pk)) err = true;
-    uint32_t ev_info[1] = {0}; float sv[1] = {0.f}; bool has_ev = false;
-    if (active && (SH | impl0))
-      has_ev = classify_call<SAMPLE, true>(prm, bedmask, grp0, gp0, kcodes0, b0, sg0, aln, L, trimmable, SH, impl0, pk, f, mapped, rpos, acc,
-                                           contribH, ev_info[0], sv[0]);
-    append_events<SAMPLE, 1>(events, sample_vals, dev_err, h.event_off, h.event_cap, has_ev ? 1u : 0u, (uint32_t)rpos, ev_info, sv, acc);
-    err = __any(err);
-    qhead += nb;
+    consume_batch<SAMPLE, true, NT>(prm, bedmask, ml, G, T.ml, n_tags, W, trimmable, q_pos, q_j, qhead, qcount, win, h, cigar, out, acc, contribH);
   }
 #pragma unroll
-  for (int t = 0; t < NT; t++) if (t < n_tags && list_left_over(rev, t_cur[t], t_n[t])) err = true;
-  if (!prm.force_allow && !SAMPLE && lacks_mode(member_tagbits(wave_or(contribH), grp0.member_tags), lay->default_mask)) err = true;
+  for (int t = 0; t < NT; t++) if (t < n_tags && list_left_over(W.rev, T.cur[t], T.n[t])) acc.err = true;
+  group_epilogue<SAMPLE, NT>(prm, lay, G, contribH, acc);
   read_epilogue(readout, rid, acc, false);
 }
 
 // ----------------------------------------------------------------------------------------------
 // Decode, SPARSE layouts: FAST layouts whose tags are all explicit ('?': only the listed bases are calls) and, when there are
 // two tags, list the same bases (`C+h?,..;C+m?,..` with one delta list — checked by the host).  The calls are then a few
-// percent of the bases, and locating them must not cost per base.  Per 4096-base step (64 bases = 8 SEQ dwords per lane) the
-// wave only counts: per dword a nibble-equality flag word (7 VALU for 8 bases) and its popcount, byte-packed running counts
-// inside the lane, one wave prefix sum; the flag words go to LDS.  The ranks that fall into the step's window are taken 64 at a
-// time from the sorted rank list; every lane owning one finds the lane whose bases contain that occurrence (6 ds_bpermute steps
-// over the prefix sums), the dword inside that lane (one SWAR compare over the packed counts) and the base inside the dword
-// (select on the flag word read back from LDS) — {stored position, call index} goes straight into the call queue, in read
-// order.  No per-base marks, no bitmap deposit, no per-bit loops.  The consumer (per-call work on full batches of 64) calls the
-// helpers the FAST kernels call, as the case "every tag lists every call, no implicit members" (classify_call<SAMPLE, INFER = false>)
-// and on descriptor words made opaque per batch; the CIGAR mapping is its own (a scalar 128-op window).
-// flag word of a SEQ dword: bit 4i set where nibble i equals the BAM code of base k (A,C,G,T = 1,2,4,8)
-__device__ __forceinline__ uint32_t nibble_eq(uint32_t x, uint32_t pat) {
-  uint32_t t = x ^ pat;
-  t |= t >> 1; t |= t >> 2;
-  return ~t & 0x11111111u;
-}
+// percent of the bases, and locating them must not cost per base.  4096-base steps, 64 bases = 8 SEQ dwords per lane:
+//   sparse_count_step   the wave only counts: per dword a nibble-equality flag word (7 VALU for 8 bases) and its popcount,
+//                       byte-packed running counts inside the lane, one wave prefix sum; the flag words go to LDS;
+//   sparse_locate       the window's ranks are taken 64 at a time from the sorted list; every lane owning one finds the lane whose
+//                       bases contain that occurrence (6 ds_bpermute steps over the prefix sums), the dword inside that lane (one SWAR
+//                       compare over the packed counts) and the base inside the dword (select on the flag word read back from LDS) —
+//                       {stored position, call index} goes straight into the queue, in read order.  No per-base marks, no deposit;
+//   consume_batch<INFER = false>: "every tag lists every call, no implicit members", on descriptor words made opaque per batch and
+//                       with a CIGAR window of the decoder's own (PairWin: 128 ops, scalar running values).
 #define MKP_SQCAP 128   // call queue of the SPARSE kernels: < 64 left over + one round of <= 64
+struct SparseStep {
+  uint4 xa, xb;                 // the next step's SEQ dwords (eight per lane, two 16-byte loads), always in flight
+  bool loaded = false;          // the step below is counted and still holds ranks
+  uint32_t incl = 0, excl = 0;  // wave prefix sums of the lanes' counts
+  uint32_t cumlo = 0, cumhi = 0;   // byte-packed exclusive running counts of the lane's 8 dwords
+  uint32_t cntT = 0, wlo = 0, whi = 0;   // occurrences in the step, its rank window
+};
+// SEQ buffers end with slack, so whole vectors are loaded and the dwords past the read are discarded here; reads start 4-byte
+// aligned: vector loads may be unaligned (fine on global memory)
+__device__ __forceinline__ void sparse_fetch_seq(SparseStep& S, const ReadWalk& W, uint32_t dstep) {
+  const uint32_t d = dstep + 8u * (uint32_t)lane_id(), nd = W.nd; const uint32_t* __restrict__ seqw = W.seqw;
+  if (d + 4u <= nd) S.xa = *reinterpret_cast<const uint4*>(seqw + d);
+  else { S.xa.x = d < nd ? seqw[d] : 0u; S.xa.y = d + 1u < nd ? seqw[d + 1u] : 0u; S.xa.z = d + 2u < nd ? seqw[d + 2u] : 0u; S.xa.w = 0u; }
+  if (d + 8u <= nd) S.xb = *reinterpret_cast<const uint4*>(seqw + d + 4u);
+  else { S.xb.x = d + 4u < nd ? seqw[d + 4u] : 0u; S.xb.y = d + 5u < nd ? seqw[d + 5u] : 0u; S.xb.z = d + 6u < nd ? seqw[d + 6u] : 0u; S.xb.w = 0u; }
+}
+__device__ __forceinline__ void sparse_count_step(SparseStep& S, const ReadWalk& W, uint32_t pat, const OddTail& odd, uint32_t* __restrict__ flg) {
+  const uint32_t lane = (uint32_t)lane_id(), d = W.d0 + 8u * lane;          // this lane's first dword: bases [8d, 8d+64)
+  uint32_t F[8] = {nibble_eq(S.xa.x, pat), nibble_eq(S.xa.y, pat), nibble_eq(S.xa.z, pat), nibble_eq(S.xa.w, pat),
+                   nibble_eq(S.xb.x, pat), nibble_eq(S.xb.y, pat), nibble_eq(S.xb.z, pat), nibble_eq(S.xb.w, pat)};
+  if (odd.dw - d < 8u) {   // the read's last dword sits in this lane and L is odd
+#pragma unroll
+    for (int j = 0; j < 8; j++) if (d + (uint32_t)j == odd.dw) F[j] &= odd.clear;
+  }
+  sparse_fetch_seq(S, W, W.d0 + 512u);
+  __builtin_amdgcn_wave_barrier();   // the previous step's readers of the flag words are done (same wave: program order)
+  *reinterpret_cast<uint4*>(flg + 8u * lane) = make_uint4(F[0], F[1], F[2], F[3]);
+  *reinterpret_cast<uint4*>(flg + 8u * lane + 4u) = make_uint4(F[4], F[5], F[6], F[7]);
+  // byte-packed counts, then running counts inside the lane (byte k = count of the dwords before k)
+  const uint32_t clo = (uint32_t)__popc(F[0]) | ((uint32_t)__popc(F[1]) << 8) | ((uint32_t)__popc(F[2]) << 16) | ((uint32_t)__popc(F[3]) << 24);
+  const uint32_t chi = (uint32_t)__popc(F[4]) | ((uint32_t)__popc(F[5]) << 8) | ((uint32_t)__popc(F[6]) << 16) | ((uint32_t)__popc(F[7]) << 24);
+  const uint32_t plo = clo + (clo << 8) + (clo << 16) + (clo << 24);   // inclusive prefix per byte (sums stay below 256)
+  const uint32_t tlo = plo >> 24;                                     // count of dwords 0..3
+  const uint32_t phi = chi + (chi << 8) + (chi << 16) + (chi << 24) + tlo * 0x01010101u;
+  S.cumlo = plo << 8; S.cumhi = (phi << 8) | tlo;                      // exclusive
+  const uint32_t c = phi >> 24;                                       // the lane's 64 bases
+  S.incl = wave_incl_scan(c); S.excl = S.incl - c;
+  S.cntT = (uint32_t)__builtin_amdgcn_readlane((int)S.incl, 63);
+  S.wlo = W.rev ? (W.tot - W.cum - S.cntT) : W.cum; S.whi = S.wlo + S.cntT;   // rank window of this step
+  S.loaded = true;
+  wave_lds_sync();
+}
+// stored position of the lane's taken rank e
+__device__ __forceinline__ uint32_t sparse_locate(const SparseStep& S, const ReadWalk& W, bool hit, uint32_t e, const uint32_t* __restrict__ flg) {
+  const uint32_t ib = hit ? step_ordinal(e, W.rev, W.tot, W.cum) : 0u;    // step-relative stored ordinal of the called base (< cntT)
+  const int owner = find_op(S.incl, ib) & 63;                             // the lane whose 64 bases hold that occurrence
+  const uint32_t o_excl = (uint32_t)__shfl((int)S.excl, owner, 64), o_lo = (uint32_t)__shfl((int)S.cumlo, owner, 64),
+      o_hi = (uint32_t)__shfl((int)S.cumhi, owner, 64);
+  const uint32_t k = ib - o_excl;                                         // occurrence inside the owner's 64 bases
+  // dword: the last of the 8 running counts that is <= k (SWAR: byte i of t keeps 0x80 where count_i > k; counts < 128)
+  const uint32_t kk1 = (k + 1u) * 0x01010101u;
+  const uint32_t t_lo = ((o_lo | 0x80808080u) - kk1) & 0x80808080u, t_hi = ((o_hi | 0x80808080u) - kk1) & 0x80808080u;
+  const uint32_t jd = 7u - (uint32_t)__popc(t_lo) - (uint32_t)__popc(t_hi);
+  const uint32_t cj = ((jd < 4u ? o_lo : o_hi) >> (8u * (jd & 3u))) & 0xffu;
+  uint32_t r = k - cj;
+  uint32_t Fw = hit ? flg[8u * (uint32_t)owner + jd] : 1u;
+  Fw = ((Fw & 0x01010101u) << 4) | ((Fw >> 4) & 0x01010101u);           // base order: bit 4b = base b of the dword
+  uint32_t bpos = 0, cc;
+  cc = (uint32_t)__popc(Fw & 0xffffu); if (r >= cc) { r -= cc; bpos += 4u; Fw >>= 16; }
+  cc = (uint32_t)__popc(Fw & 0xffu);   if (r >= cc) { r -= cc; bpos += 2u; Fw >>= 8; }
+  cc = Fw & 1u;                         if (r >= cc) { bpos += 1u; }
+  return 8u * (W.d0 + 8u * (uint32_t)owner + jd) + bpos;
+}
+
+// Query -> reference through the SPARSE decoder's own CIGAR window, advanced as the batches move along the read.  128 ops per window,
+// two per lane: qe = inclusive query end of the lane's pair, mid = where its second op starts, a / b = (reference start - query
+// start) << 1 | is-match of the two ops.  The running values (first op, query / reference offsets, totals) are kept in scalar registers,
+// read back through readfirstlane after every update (as vectors they were advanced with v_cndmask and copied at every loop head);
+// "nothing loaded yet" is an empty window in front of op 0: no flag, no conditional advance (as the slot walks' CigarWin, mkp_slots.hip).
+struct PairWin {
+  uint32_t c0 = 0u - 128u, wq0 = 0, wq1 = 0; int32_t wr0; uint32_t rtot = 0;
+  uint32_t qe = 0, mid = 0, a = 0, b = 0;
+  uint2 pref;   // the next window's ops, requested one window ahead: the load is off the mapping's dependency chain
+};
+__device__ __forceinline__ uint2 pairwin_fetch(const MkpReadHdr& h, const uint32_t* __restrict__ cigar, uint32_t c) {
+  uint2 r; const uint32_t k = c + 2u * (uint32_t)lane_id();
+  r.x = k < h.n_cigar ? cigar[h.cigar_off + k] : 5u /*0H*/; r.y = k + 1u < h.n_cigar ? cigar[h.cigar_off + k + 1u] : 5u;
+  return r;
+}
+// the next 128 ops; false behind the last op (cannot happen for positions inside SEQ: the packer checks the lengths)
+__device__ __forceinline__ bool pairwin_next(PairWin& w, const MkpReadHdr& h, const uint32_t* __restrict__ cigar) {
+  w.c0 = rfl_u(w.c0 + 128u); w.wq0 = w.wq1; w.wr0 = (int32_t)rfl_u((uint32_t)w.wr0 + w.rtot);
+  if (w.c0 >= h.n_cigar) { w.rtot = 0; return false; }
+  const uint2 p = w.pref;
+  w.pref = pairwin_fetch(h, cigar, w.c0 + 128u);
+  const uint32_t op0 = p.x & 15u, len0 = p.x >> 4, op1 = p.y & 15u, len1 = p.y >> 4;
+  const uint32_t ql0 = op_consumes_query(op0) ? len0 : 0u, rl0 = op_consumes_ref(op0) ? len0 : 0u;
+  const uint32_t ql1 = op_consumes_query(op1) ? len1 : 0u, rl1 = op_consumes_ref(op1) ? len1 : 0u;
+  w.qe = wave_incl_scan(ql0 + ql1); const uint32_t re = wave_incl_scan(rl0 + rl1);
+  w.mid = w.qe - ql1;                                                       // window-relative query offset of the second op
+  const int32_t dl0 = (w.wr0 + (int32_t)(re - rl0 - rl1)) - (int32_t)(w.wq0 + w.qe - ql0 - ql1);   // ref start - query start of the first op
+  const int32_t dl1 = (w.wr0 + (int32_t)(re - rl1)) - (int32_t)(w.wq0 + w.mid);
+  w.a = ((uint32_t)dl0 << 1) | (op_is_match(op0) ? 1u : 0u); w.b = ((uint32_t)dl1 << 1) | (op_is_match(op1) ? 1u : 0u);
+  w.wq1 = w.wq0 + (uint32_t)__builtin_amdgcn_readlane((int)w.qe, 63); w.rtot = (uint32_t)__builtin_amdgcn_readlane((int)re, 63);
+  return true;
+}
+// the lanes whose position lies in the loaded window (positions ascend from batch to batch: none lies before it)
+__device__ __forceinline__ void pairwin_pass(const PairWin& w, bool& pending, uint32_t q, bool& mapped, int32_t& rpos) {
+  const bool ready = pending && q < w.wq1;
+  if (!__any(ready)) return;
+  const uint32_t qrel = ready ? q - w.wq0 : 0u;
+  const int oi = find_op(w.qe, qrel) & 63;
+  const uint32_t o_mid = (uint32_t)__shfl((int)w.mid, oi, 64), o_a = (uint32_t)__shfl((int)w.a, oi, 64), o_b = (uint32_t)__shfl((int)w.b, oi, 64);
+  const uint32_t pick = qrel < o_mid ? o_a : o_b;
+  if (ready) { mapped = (pick & 1u) != 0u; rpos = (int32_t)q + ((int32_t)pick >> 1); pending = false; }
+}
+// BY_VALUE: the window is copied in, advanced and copied back.  The sample kernels, which have no launch bound, keep their eighth wave
+// only in this form (behind the reference 65 VGPRs for 57 / 63); the event kernels are faster behind the reference
+// (profiles/decoder_stages_isa.txt, decoder_stages_ab.txt).
+template <bool BY_VALUE>
+__device__ __forceinline__ void pairwin_map(PairWin& win, const MkpReadHdr& h, const uint32_t* __restrict__ cigar, bool pending, uint32_t q,
+    bool& mapped, int32_t& rpos) {
+  PairWin copy; if (BY_VALUE) copy = win;
+  PairWin& w = BY_VALUE ? copy : win;
+  pairwin_pass(w, pending, q, mapped, rpos);
+  while (__any(pending)) { if (!pairwin_next(w, h, cigar)) break; pairwin_pass(w, pending, q, mapped, rpos); }
+  if (BY_VALUE) win = copy;
+}
+template <bool SAMPLE>
+__device__ __forceinline__ void map_window(PairWin& w, const MkpReadHdr& h, const uint32_t* __restrict__ cigar, bool pending, uint32_t q,
+    bool& mapped, int32_t& rpos) { pairwin_map<SAMPLE>(w, h, cigar, pending, q, mapped, rpos); }
+
 template <bool SAMPLE, int NT>
-__device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads, const uint32_t* __restrict__ cigar,
-                 const uint8_t* __restrict__ seqs, const MkpTagRef* __restrict__ tagref, const uint32_t* __restrict__ ranks,
-                 const uint8_t* __restrict__ ml, const MkpLayout* __restrict__ layouts, const MkpRunParams& prm,
-                 MkpEvent* __restrict__ events, MkpReadOut* __restrict__ readout, uint32_t* __restrict__ dev_err,
-                 const uint8_t* __restrict__ bedmask, float* __restrict__ sample_vals, uint32_t* __restrict__ lds_layouts,
-                 const uint32_t* __restrict__ read_ids, uint32_t* __restrict__ lds_queue, uint32_t* __restrict__ lds_flags) {
+__device__ __forceinline__ void decode_read_sparse(DECODE_PARAMS(const MkpRunParams&), uint32_t* __restrict__ lds_layouts,
+    uint32_t* __restrict__ lds_queue, uint32_t* __restrict__ lds_flags) {
   static_assert(NT <= 2, "one or two tags");
-  const int lane = lane_id();
+  const uint32_t lane = (uint32_t)lane_id();
   // Duplex reads (layout.fast == 2: two (strand, base) groups on different bases) are listed twice, once per group (bit 31 = the
   // second); each listing decodes its group's tags exactly like a single-group read, into its own half of the read's event slice
   // behind the room for the merged list, with its own summary; mkp_merge_duplex interleaves the two by position afterwards.
@@ -806,245 +997,81 @@ __device__ __forceinline__ void decode_read_sparse(const MkpReadHdr* __restrict_
   if (!read_prologue(hdrs, n_reads, read_ids, layouts, readout, lds_layouts, 0x7fffffffu, wib, rid_raw, h, lds_lay)) return;
   const uint32_t rid = rid_raw & 0x7fffffffu; const bool half_b = (rid_raw >> 31) != 0u;
   uint32_t* __restrict__ q_pos = lds_queue + wib * (2 * MKP_SQCAP);   // queue, SoA: stored position, call index (the same for both tags)
-  uint32_t* __restrict__ q_j = q_pos + MKP_SQCAP;
+  uint32_t* __restrict__ q_idx = q_pos + MKP_SQCAP;
+  uint32_t* q_j[NT];
+  for (int t = 0; t < NT; t++) q_j[t] = q_idx;
   uint32_t* __restrict__ flg = lds_flags + wib * 512u;                 // the step's 512 flag words
   const MkpLayout* lay = reinterpret_cast<const MkpLayout*>(lds_lay);
-  const uint32_t* __restrict__ seqw = reinterpret_cast<const uint32_t*>(seqs + h.seq_off);
-  const bool rev = (h.flags & MKP_RF_REVERSE) != 0;
-  const uint32_t L = h.l_seq, nd = (L + 7u) >> 3, aln = rev ? 1u : 0u;
-  const bool duplex = rfl_u(lay->fast) == 2u;
+  ReadWalk W; W.seqw = reinterpret_cast<const uint32_t*>(seqs + h.seq_off); W.L = h.l_seq; W.nd = (W.L + 7u) >> 3; W.rev = (h.flags & MKP_RF_REVERSE) != 0;
+  const bool rev = W.rev, duplex = rfl_u(lay->fast) == 2u;
   const int n_first = (int)rfl_u(lay->pad);
   const int tb = (duplex && half_b) ? n_first : 0;                     // first tag of the group this wave decodes
   const int n_tags = duplex ? (half_b ? (int)h.n_tags - n_first : n_first) : (int)h.n_tags;
-  uint32_t ev_base = h.event_off, ev_cap = h.event_cap, ro_idx = rid;
+  EventSink out = {events, sample_vals, dev_err, h.event_off, h.event_cap};
+  uint32_t ro_idx = rid;
   if (duplex) {
     const uint32_t nA = tagref[h.tag_off].n, nB = tagref[h.tag_off + n_first].n;   // calls listed per group (one shared rank list each)
-    ev_base = h.event_off + nA + nB + (half_b ? nA : 0u); ev_cap = half_b ? nB : nA;
+    out.ev_base = h.event_off + nA + nB + (half_b ? nA : 0u); out.ev_cap = half_b ? nB : nA;
     if (half_b) ro_idx = prm.readout_b_off + rid;
   }
-  const int b0 = (int)lay->tags[tb].fb & 3, sg0 = (int)lay->tags[tb].neg & 1;
-  const int xs = rev ? 3 - b0 : b0;                                   // the stored base the tags count
-  const uint32_t* gp0 = lds_lay + MKP_LAYOUT_GROUP_DW + (sg0 * 4 + b0) * 32;
-  const GroupRegs grp0 = load_group_uniform(gp0);
-  const int kcodes0 = (int)((grp0.misc >> 20) & 7u);   // codes of the group: bounds every per-code loop
-  uint32_t t_ml[NT], t_nc[NT], tmu[NT], codes_t[NT];
-  tag_setup<NT>(lay, tb, n_tags, b0, t_nc, tmu, codes_t);
-  uint32_t t_off = 0, t_n = 0, t_cur = 0;   // the (shared) rank list
-  uint32_t SH_all = 0, setmask_all = 0;     // every call is listed by every tag: hit pattern and code set are wave constants
-#pragma unroll
-  for (int t = 0; t < NT; t++) {
-    t_ml[t] = 0;
-    if (t < n_tags) {
-      const MkpTagRef tr = tagref[h.tag_off + tb + t]; t_ml[t] = tr.ml_off;
-      if (t == 0) { t_off = tr.rank_off; t_n = tr.n; t_cur = rev ? tr.n : 0u; }
-      SH_all |= 1u << (tmu[t] & 15u); setmask_all |= codes_t[t];
-    }
-  }
-  const uint32_t pat = 0x11111111u << xs;
-  // the low nibble of the last byte is not a base when L is odd: its flag is cleared wherever that dword is looked at
-  const uint32_t odd_dw = (L & 1u) ? ((L - 1u) >> 3) : 0xffffffffu, odd_clear = ~(1u << (8u * (((L - 1u) >> 1) & 3u)));
-  // reverse reads need the total up front (forward rank = total - inclusive count in stored order); 4 loads in flight.
-  // (SEQ is zero-padded to a dword per read and code 0 matches no base; dwords past the read are not loaded.)
-  uint32_t tot = 0;
-  if (rev) {
-    uint32_t acc = 0;
-    for (uint32_t d0 = 0; d0 < nd; d0 += 256) {
-      uint32_t xw[4];
-#pragma unroll
-      for (int j = 0; j < 4; j++) { const uint32_t dd = d0 + 64u * j + lane; xw[j] = dd < nd ? seqw[dd] : 0u; }
-#pragma unroll
-      for (int j = 0; j < 4; j++) {
-        const uint32_t dd = d0 + 64u * j + lane;
-        uint32_t F = nibble_eq(xw[j], pat); if (dd == odd_dw) F &= odd_clear;
-        acc += (uint32_t)__popc(F);
-      }
-    }
-    tot = (uint32_t)__builtin_amdgcn_readlane((int)wave_incl_scan(acc), 63);
-  }
-  ReadAcc acc; bool& err = acc.err;
+  GroupCalls<NT> G; group_setup<NT>(lay, lds_lay, tb, n_tags, rev, G);
+  TagLists<NT> T; tag_lists<NT>(tagref, h.tag_off + tb, n_tags, rev, T);   // list 0 is the shared one
+  const uint32_t pat = 0x11111111u << G.xs;
+  const OddTail odd = odd_tail(W.L);
+  if (rev) W.tot = stored_base_total(W.seqw, W.nd, W.L, G.xs);
+  ReadAcc acc;
   // reverse reads consume the (ascending) rank list from its end: a last entry past the last occurrence of the base
   // (mod_bam.rs:705-727) would never be consumed — the read is rejected here so that hits always form a suffix of the cursor window
-  if (rev && t_n && ranks[t_off + t_n - 1u] >= tot) err = true;
-  const bool trimmable = read_trimmable(prm, L);
-  uint32_t contribH = 0, cum = 0;
-  // CIGAR window of this decoder, advanced as the batches move along the read
-  // (128 ops per window, two per lane: w_qe = inclusive query end of the lane's pair, w_mid = where its second op starts,
-  //  w_a / w_b = (reference start - query start) << 1 | is-match of the two ops)
-  // The window's running values (first op, query / reference offsets, totals) are kept in scalar registers — read back through readfirstlane
-  // after every update; carried as vectors they were advanced with v_cndmask and copied at every loop head — and "nothing loaded yet" is an
-  // empty window in front of op 0: no flag, no conditional advance (as the slot walks' CigarWin, mkp_slots.hip).
-  uint32_t c0 = 0u - 128u, wq0 = 0, wq1 = 0; int32_t wr0 = h.ref_start;
-  uint32_t w_qe = 0, w_mid = 0, w_a = 0, w_b = 0, w_rtot = 0;
-  auto cigar2 = [&](uint32_t c) { uint2 r; const uint32_t k = c + 2u * (uint32_t)lane; r.x = k < h.n_cigar ? cigar[h.cigar_off + k] : 5u /*0H*/;
-    r.y = k + 1u < h.n_cigar ? cigar[h.cigar_off + k + 1u] : 5u; return r; };
-  uint2 w_pref = cigar2(0);   // the first CIGAR window, requested before the read is walked
-  uint32_t qhead = 0, qcount = 0, d0 = 0;
-  // the next step's SEQ dwords (eight per lane = 64 bases, two 16-byte loads) are always in flight; SEQ buffers end with
-  // slack, so whole vectors are loaded and the dwords past the read are discarded when the flags are made
-  // reads start 4-byte aligned: vector loads may be unaligned (fine on global memory)
-  uint4 xa = make_uint4(0, 0, 0, 0), xb = make_uint4(0, 0, 0, 0);
-  auto load_step = [&](uint32_t dstep) {
-    const uint32_t d = dstep + 8u * (uint32_t)lane;
-    if (d + 4u <= nd) xa = *reinterpret_cast<const uint4*>(seqw + d);
-    else { xa.x = d < nd ? seqw[d] : 0u; xa.y = d + 1u < nd ? seqw[d + 1u] : 0u; xa.z = d + 2u < nd ? seqw[d + 2u] : 0u; xa.w = 0u; }
-    if (d + 8u <= nd) xb = *reinterpret_cast<const uint4*>(seqw + d + 4u);
-    else { xb.x = d + 4u < nd ? seqw[d + 4u] : 0u; xb.y = d + 5u < nd ? seqw[d + 5u] : 0u; xb.z = d + 6u < nd ? seqw[d + 6u] : 0u; xb.w = 0u; }
-  };
-  load_step(0);
-  // the current step: per-lane counts (byte-packed running counts of its 8 dwords), wave prefix sums, the step's rank window
-  bool step_loaded = false;
-  uint32_t st_incl = 0, st_excl = 0, st_cumlo = 0, st_cumhi = 0, st_cntT = 0, st_wlo = 0, st_whi = 0;
+  if (rev && T.n[0] && ranks[T.off[0] + T.n[0] - 1u] >= W.tot) acc.err = true;
+  const bool trimmable = read_trimmable(prm, W.L);
+  uint32_t contribH = 0, qhead = 0, qcount = 0;
+  PairWin win; win.wr0 = h.ref_start; win.pref = pairwin_fetch(h, cigar, 0);   // the first CIGAR window, requested before the read is walked
+  SparseStep S; sparse_fetch_seq(S, W, 0);
 
-  for (;;) {
-    if (err) break;
+  while (!acc.err) {
     // ---- producer: a loop of its own — the steps and rank batches that refill the queue touch none of the consumer's state, and as
     // iterations of the one outer loop each of them went through that loop's head with all of it
-    while (qcount - qhead < 64u && (step_loaded || d0 < nd)) {
+    while (qcount - qhead < 64u && (S.loaded || W.d0 < W.nd)) {
       // the next 64 ranks at the cursor are requested first: the flag / scan work below hides the load
-      uint32_t e; bool valid;
-      if (!rev) { const uint32_t i = t_cur + lane; valid = i < t_n; e = valid ? ranks[t_off + i] : 0xffffffffu; }
-      else { const uint32_t i = t_cur - 64u + lane; valid = (int32_t)i >= 0 && i < t_cur; e = valid ? ranks[t_off + i] : 0u; }
-      if (!step_loaded) {
-        const uint32_t d = d0 + 8u * (uint32_t)lane;          // this lane's first dword: bases [8d, 8d+64)
-        uint32_t F[8] = {nibble_eq(xa.x, pat), nibble_eq(xa.y, pat), nibble_eq(xa.z, pat), nibble_eq(xa.w, pat),
-                         nibble_eq(xb.x, pat), nibble_eq(xb.y, pat), nibble_eq(xb.z, pat), nibble_eq(xb.w, pat)};
-        if (odd_dw - d < 8u) {   // the read's last dword sits in this lane and L is odd
-#pragma unroll
-          for (int j = 0; j < 8; j++) if (d + (uint32_t)j == odd_dw) F[j] &= odd_clear;
-        }
-        load_step(d0 + 512u);
-        __builtin_amdgcn_wave_barrier();   // the previous step's readers of the flag words are done (same wave: program order)
-        *reinterpret_cast<uint4*>(flg + 8u * (uint32_t)lane) = make_uint4(F[0], F[1], F[2], F[3]);
-        *reinterpret_cast<uint4*>(flg + 8u * (uint32_t)lane + 4u) = make_uint4(F[4], F[5], F[6], F[7]);
-        // byte-packed counts, then running counts inside the lane (byte k = count of the dwords before k)
-        const uint32_t clo = (uint32_t)__popc(F[0]) | ((uint32_t)__popc(F[1]) << 8) | ((uint32_t)__popc(F[2]) << 16) | ((uint32_t)__popc(F[3]) << 24);
-        const uint32_t chi = (uint32_t)__popc(F[4]) | ((uint32_t)__popc(F[5]) << 8) | ((uint32_t)__popc(F[6]) << 16) | ((uint32_t)__popc(F[7]) << 24);
-        const uint32_t plo = clo + (clo << 8) + (clo << 16) + (clo << 24);   // inclusive prefix per byte (sums stay below 256)
-        const uint32_t tlo = plo >> 24;                                     // count of dwords 0..3
-        const uint32_t phi = chi + (chi << 8) + (chi << 16) + (chi << 24) + tlo * 0x01010101u;
-        st_cumlo = plo << 8; st_cumhi = (phi << 8) | tlo;                    // exclusive
-        const uint32_t c = phi >> 24;                                       // the lane's 64 bases
-        st_incl = wave_incl_scan(c); st_excl = st_incl - c;
-        st_cntT = (uint32_t)__builtin_amdgcn_readlane((int)st_incl, 63);
-        st_wlo = rev ? (tot - cum - st_cntT) : cum; st_whi = st_wlo + st_cntT;   // rank window of this step
-        step_loaded = true;
-        wave_lds_sync();
-      }
+      const RankBatch b = rank_batch(ranks, T.off[0], T.n[0], T.cur[0], rev);
+      if (!S.loaded) sparse_count_step(S, W, pat, odd, flg);
       // (reverse reads: the list's last entry was checked against the total, so every entry is below the first window's end)
-      const bool hit = valid && (rev ? (e >= st_wlo) : (e < st_whi));
-      const unsigned long long hb = __ballot(hit);
-      const uint32_t nh = (uint32_t)__popcll(hb);
-      if (nh) {
+      const uint32_t cur0 = T.cur[0];
+      const RankTake tk = window_take<true>(b, S.wlo, S.whi, rev, T.cur[0]);
+      if (tk.nh) {
         if (qhead) queue_to_front<2>(q_pos, MKP_SQCAP, qhead, qcount);
-        const uint32_t ib = hit ? ((rev ? (tot - 1u - e) : e) - cum) : 0u;   // step-relative stored ordinal of the called base (< cntT)
-        const int owner = find_op(st_incl, ib) & 63;                          // the lane whose 64 bases hold that occurrence
-        const uint32_t o_excl = (uint32_t)__shfl((int)st_excl, owner, 64), o_lo = (uint32_t)__shfl((int)st_cumlo, owner, 64),
-            o_hi = (uint32_t)__shfl((int)st_cumhi, owner, 64);
-        const uint32_t k = ib - o_excl;                                       // occurrence inside the owner's 64 bases
-        // dword: the last of the 8 running counts that is <= k (SWAR: byte i of t keeps 0x80 where count_i > k; counts < 128)
-        const uint32_t kk1 = (k + 1u) * 0x01010101u;
-        const uint32_t t_lo = ((o_lo | 0x80808080u) - kk1) & 0x80808080u, t_hi = ((o_hi | 0x80808080u) - kk1) & 0x80808080u;
-        const uint32_t jd = 7u - (uint32_t)__popc(t_lo) - (uint32_t)__popc(t_hi);
-        const uint32_t cj = ((jd < 4u ? o_lo : o_hi) >> (8u * (jd & 3u))) & 0xffu;
-        uint32_t r = k - cj;
-        uint32_t Fw = hit ? flg[8u * (uint32_t)owner + jd] : 1u;
-        Fw = ((Fw & 0x01010101u) << 4) | ((Fw >> 4) & 0x01010101u);         // base order: bit 4b = base b of the dword
-        uint32_t bpos = 0, cc;
-        cc = (uint32_t)__popc(Fw & 0xffffu); if (r >= cc) { r -= cc; bpos += 4u; Fw >>= 16; }
-        cc = (uint32_t)__popc(Fw & 0xffu);   if (r >= cc) { r -= cc; bpos += 2u; Fw >>= 8; }
-        cc = Fw & 1u;                         if (r >= cc) { bpos += 1u; }
+        const uint32_t pos = sparse_locate(S, W, tk.hit, b.e, flg);
         // read order: forward reads hit on the low lanes with ascending positions, reverse reads on the high lanes with descending ones
-        const uint32_t slot = qcount + (uint32_t)__popcll(rev ? (hb & ~lanemask_le()) : (hb & lanemask_lt()));
-        if (hit) { q_pos[slot] = 8u * (d0 + 8u * (uint32_t)owner + jd) + bpos;
-          q_j[slot] = rev ? (t_cur - 64u + (uint32_t)lane) : (t_cur + (uint32_t)lane); }
+        const uint32_t slot = qcount + (uint32_t)__popcll(rev ? (tk.lanes & ~lanemask_le()) : (tk.lanes & lanemask_lt()));
+        if (tk.hit) { q_pos[slot] = pos; q_idx[slot] = (rev ? cur0 - 64u : cur0) + lane; }
         wave_lds_sync();
-        qcount += nh;
-        if (rev) t_cur -= nh; else t_cur += nh;
+        qcount += tk.nh;
       }
-      if (nh < 64u) {   // the window holds no further rank: step done; nothing left in the list: the rest of the read holds no call
-        cum += st_cntT; d0 += 512; step_loaded = false;
-        if (rev ? (t_cur == 0u) : (t_cur == t_n)) d0 = nd;
+      if (tk.nh < 64u) {   // the window holds no further rank: step done; nothing left in the list: the rest of the read holds no call
+        W.cum += S.cntT; W.d0 += 512; S.loaded = false;
+        if (!list_left_over(rev, T.cur[0], T.n[0])) W.d0 = W.nd;
       }
     }
     if (qcount == qhead) break;
-    // ---- consumer: up to 64 queued calls, in read order
-    const uint32_t nb = min(64u, qcount - qhead);
 #ifdef MKP_DEBUG
-    if (prm.debug_skip & 16u) { qhead += nb; acc.any_surviving = true; continue; }   // ablation: producer only
+    if (prm.debug_skip & 16u) { qhead += min(64u, qcount - qhead); acc.any_surviving = true; continue; }   // ablation: producer only
 #endif
-    const bool active = (uint32_t)lane < nb;
     // The descriptor words the per-call code branches on are made opaque here, once per batch: left visible as loop invariants, every
     // uniform compare derived from them (which code a slot holds, how many codes a tag lists, ...) was hoisted out of the loop as a 64-bit
     // lane mask, dozens of them, spilled to VGPR lanes and read back with two v_readlane each inside the loop — VALU instructions in a
     // VALU-bound kernel; derived in place they are a few scalar instructions that live for a handful of cycles.
-    GroupRegs g0 = grp0; uint32_t kc_l = (uint32_t)kcodes0, SH_l = SH_all, sm_l = setmask_all, tmu_l[NT], tnc_l[NT];
-    asm volatile("" : "+s"(g0.misc), "+s"(g0.slots), "+s"(g0.cids), "+s"(kc_l), "+s"(SH_l), "+s"(sm_l));
+    GroupCalls<NT> Gb = G;
+    asm volatile("" : "+s"(Gb.g.misc), "+s"(Gb.g.slots), "+s"(Gb.g.cids), "+s"(Gb.kcodes), "+s"(Gb.SH_all), "+s"(Gb.setmask_all));
 #pragma unroll
-    for (int t = 0; t < NT; t++) { tmu_l[t] = tmu[t]; tnc_l[t] = t_nc[t]; asm volatile("" : "+s"(tmu_l[t]), "+s"(tnc_l[t])); }
-    const uint32_t q = active ? q_pos[qhead + lane] : 0u;
-    const uint32_t f = rev ? (L - 1 - q) : q;  // forward (as-sequenced) position
-    uint32_t mlq[NT][MKP_KMAX], jx[NT]; bool listed[NT];   // every tag lists every call, as its jx-th
-#pragma unroll
-    for (int t = 0; t < NT; t++) { jx[t] = active ? q_j[qhead + lane] : 0u; listed[t] = active; }
-    ml_prefetch<NT>(ml, n_tags, t_ml, tnc_l, listed, jx, mlq);
-    // reference position through this decoder's own CIGAR window (aligned pairs: M/=/X only, util.rs:122-145)
-    bool mapped = false; int32_t rpos = 0;
-#ifdef MKP_DEBUG
-    if (prm.debug_skip & 32u) { mapped = active; rpos = h.ref_start + (int32_t)q; } else   // ablation: no CIGAR mapping
-#endif
-    {
-      bool pending = active;
-      // the next 128 ops; false behind the last op (cannot happen for positions inside SEQ: the packer checks the lengths)
-      auto win_next = [&]() -> bool {
-        c0 = rfl_u(c0 + 128u); wq0 = wq1; wr0 = (int32_t)rfl_u((uint32_t)wr0 + w_rtot);
-        if (c0 >= h.n_cigar) { w_rtot = 0; return false; }
-        const uint2 w = w_pref;   // requested one window ahead: the load is off the mapping's dependency chain
-        w_pref = cigar2(c0 + 128u);
-        const uint32_t op0 = w.x & 15u, len0 = w.x >> 4, op1 = w.y & 15u, len1 = w.y >> 4;
-        const uint32_t ql0 = op_consumes_query(op0) ? len0 : 0u, rl0 = op_consumes_ref(op0) ? len0 : 0u;
-        const uint32_t ql1 = op_consumes_query(op1) ? len1 : 0u, rl1 = op_consumes_ref(op1) ? len1 : 0u;
-        w_qe = wave_incl_scan(ql0 + ql1); const uint32_t re = wave_incl_scan(rl0 + rl1);
-        w_mid = w_qe - ql1;                                                       // window-relative query offset of the second op
-        const int32_t dl0 = (wr0 + (int32_t)(re - rl0 - rl1)) - (int32_t)(wq0 + w_qe - ql0 - ql1);   // ref start - query start of the first op
-        const int32_t dl1 = (wr0 + (int32_t)(re - rl1)) - (int32_t)(wq0 + w_mid);
-        w_a = ((uint32_t)dl0 << 1) | (op_is_match(op0) ? 1u : 0u); w_b = ((uint32_t)dl1 << 1) | (op_is_match(op1) ? 1u : 0u);
-        wq1 = wq0 + (uint32_t)__builtin_amdgcn_readlane((int)w_qe, 63); w_rtot = (uint32_t)__builtin_amdgcn_readlane((int)re, 63);
-        return true;
-      };
-      auto win_pass = [&]() {   // the lanes whose position lies in the loaded window (positions ascend from batch to batch: none lies before it)
-        const bool ready = pending && q < wq1;
-        if (!__any(ready)) return;
-        const uint32_t qrel = ready ? q - wq0 : 0u;
-        const int oi = find_op(w_qe, qrel) & 63;
-        const uint32_t o_mid = (uint32_t)__shfl((int)w_mid, oi, 64), o_a = (uint32_t)__shfl((int)w_a, oi, 64),
-            o_b = (uint32_t)__shfl((int)w_b, oi, 64);
-        const uint32_t pick = qrel < o_mid ? o_a : o_b;
-        if (ready) { mapped = (pick & 1u) != 0u; rpos = (int32_t)q + ((int32_t)pick >> 1); pending = false; }
-      };
-      win_pass();
-      while (__any(pending)) { if (!win_next()) break; win_pass(); }
-    }
-    F4 pk = {0.f, 0.f, 0.f, 0.f};
-    if (ml_to_probs<NT>(mlq, n_tags, tnc_l, tmu_l, listed, sm_l, active && n_tags > 1, pk)) err = true;
-    uint32_t ev_info[1] = {0}; float sv[1] = {0.f}; bool has_ev = false;
-    if (active)   // explicit tags: no implicit members, never inferred
-      has_ev = classify_call<SAMPLE, false>(prm, bedmask, g0, gp0, (int)kc_l, b0, sg0, aln, L, trimmable, SH_l, 0u, pk, f, mapped, rpos, acc,
-                                            contribH, ev_info[0], sv[0]);
-    append_events<SAMPLE, 1>(events, sample_vals, dev_err, ev_base, ev_cap, has_ev ? 1u : 0u, (uint32_t)rpos, ev_info, sv, acc);
-    err = __any(err);
-    qhead += nb;
+    for (int t = 0; t < NT; t++) asm volatile("" : "+s"(Gb.tmu[t]), "+s"(Gb.t_nc[t]));
+    consume_batch<SAMPLE, false, NT>(prm, bedmask, ml, Gb, T.ml, n_tags, W, trimmable, q_pos, q_j, qhead, qcount, win, h, cigar, out, acc, contribH);
   }
-  if (list_left_over(rev, t_cur, t_n)) err = true;
+  if (list_left_over(rev, T.cur[0], T.n[0])) acc.err = true;
   // InvalidImplicitMode cannot arise (every tag carries '?'), kept for symmetry with the FAST kernels
-  if (!prm.force_allow && !SAMPLE && lacks_mode(member_tagbits(wave_or(contribH), grp0.member_tags), lay->default_mask)) err = true;
+  group_epilogue<SAMPLE, NT>(prm, lay, G, contribH, acc);
   read_epilogue(readout, ro_idx, acc, duplex);
 }
 
-#define DECODE_PARAMS(PRM) const MkpReadHdr* __restrict__ hdrs, uint32_t n_reads, const uint32_t* __restrict__ cigar, const uint8_t* __restrict__ seqs, \
-                    const MkpTagRef* __restrict__ tagref, const uint32_t* __restrict__ ranks, const uint8_t* __restrict__ ml, \
-                    const MkpLayout* __restrict__ layouts, PRM prm, MkpEvent* __restrict__ events, MkpReadOut* __restrict__ readout, \
-                    uint32_t* __restrict__ dev_err, const uint8_t* __restrict__ bedmask, float* __restrict__ sample_vals, const uint32_t* __restrict__ read_ids
-#define DECODE_PASS hdrs, n_reads, cigar, seqs, tagref, ranks, ml, layouts, prm, events, readout, dev_err, bedmask, sample_vals, read_ids
 // pdep4[(mask << 4) | bits]: the low bits of `bits` deposited onto the set bits of a 4-bit mask
 __device__ __forceinline__ void init_pdep4(uint8_t* pdep4) {
   const uint32_t m = (threadIdx.x >> 4) & 15u; uint32_t f = threadIdx.x & 15u, o = 0;
@@ -1061,25 +1088,23 @@ template <bool SAMPLE, int NT> __device__ __forceinline__ void decode_fast_entry
   __shared__ uint32_t lds_ord[4][NT * MKP_ORD_WORDS];
   __shared__ uint8_t pdep4[256];
   init_pdep4(pdep4);
-  decode_read_fast<SAMPLE, NT>(hdrs, n_reads, cigar, seqs, tagref, ranks, ml, layouts, prm, events, readout, dev_err, bedmask, sample_vals,
-                               &lds_layouts[0][0], read_ids, &lds_ord[0][0], pdep4, &lds_queue[0][0]);
+  decode_read_fast<SAMPLE, NT>(DECODE_PASS, &lds_layouts[0][0], &lds_ord[0][0], pdep4, &lds_queue[0][0]);
 }
 template <bool SAMPLE, int NT> __device__ __forceinline__ void decode_sparse_entry(DECODE_PARAMS(const MkpRunParams&)) {
   __shared__ uint32_t lds_queue[4][2 * MKP_SQCAP];
   __shared__ __attribute__((aligned(16))) uint32_t lds_layouts[4][MKP_LAYOUT_DWORDS];
   __shared__ __attribute__((aligned(16))) uint32_t lds_flags[4][512];
-  decode_read_sparse<SAMPLE, NT>(hdrs, n_reads, cigar, seqs, tagref, ranks, ml, layouts, prm, events, readout, dev_err, bedmask, sample_vals,
-      &lds_layouts[0][0], read_ids, &lds_queue[0][0], &lds_flags[0][0]);
+  decode_read_sparse<SAMPLE, NT>(DECODE_PASS, &lds_layouts[0][0], &lds_queue[0][0], &lds_flags[0][0]);
 }
 template <bool SAMPLE> __device__ __forceinline__ void decode_general_entry(DECODE_PARAMS(const MkpRunParams&)) {
   __shared__ __attribute__((aligned(16))) uint32_t lds_layouts[4][MKP_LAYOUT_DWORDS];
   __shared__ uint32_t lds_marks[4 * 7][64];   // per wave 448 dwords: ordinal bitmaps [<=8][18] at 0, 512 u16 slots at 192
   __shared__ uint8_t pdep4[256];
   init_pdep4(pdep4);
-  const uint32_t widx = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)));
+  const uint32_t widx = rfl_u(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
   if (widx >= n_reads) return;
-  const uint32_t nt = (uint32_t)__builtin_amdgcn_readfirstlane((int)hdrs[read_ids[widx]].n_tags);
-#define DECODE_CALL(S, N) decode_read_body<S, N>(hdrs, n_reads, cigar, seqs, tagref, ranks, ml, layouts, prm, events, readout, dev_err, bedmask, sample_vals, read_ids, &lds_layouts[0][0], lds_marks, pdep4)
+  const uint32_t nt = rfl_u(hdrs[read_ids[widx]].n_tags);
+#define DECODE_CALL(S, N) decode_read_body<S, N>(DECODE_PASS, &lds_layouts[0][0], lds_marks, pdep4)
   if (nt <= 2) DECODE_CALL(SAMPLE, 2); else if (nt <= 4) DECODE_CALL(SAMPLE, 4); else DECODE_CALL(SAMPLE, MKP_MAX_TAGS);
 }
 extern "C" __global__ void __launch_bounds__(256) mkp_decode_reads(DECODE_PARAMS(MkpRunParams)) { decode_general_entry<false>(DECODE_PASS); }

@@ -97,12 +97,13 @@ def _mix(*v):
     return x
 
 
-def make_read(r, ref, start, cigar, layout, reverse, seed, flag=0, force=None, force_fwd=None, keep=None):
+def make_read(r, ref, start, cigar, layout, reverse, seed, flag=0, force=None, force_fwd=None, keep=None, without=()):
     """One record (start, flag, cigar, seq, MM, ML) and its listed events [(reference position, 1: a '+' tag | 2: a '-' tag)].
     force: {reference position: base} written into SEQ where the read has a base there; force_fwd: {forward-read position: base};
     keep: f(tag index, tag, candidates) -> the candidates to list, of candidates = [(rank among the tag's bases, forward position,
     reference position or None, the base equals the reference's)]; default: every base of a '?' tag (an `N` tag: every fifth aligned base
-    that matches the reference), two of every three of a '.' tag."""
+    that matches the reference), two of every three of a '.' tag.  without: [(base, lo, hi)]: no as-sequenced `base` at the forward
+    positions [lo, hi) (applied before force and force_fwd)."""
     start, flag, cigar, seq, _, _ = cases.make_read(r, ref, start, cigar, "m", reverse, seed, flag)
     L = len(seq)
     where, p, q = {}, start, 0          # index into SEQ -> reference position
@@ -115,6 +116,12 @@ def make_read(r, ref, start, cigar, layout, reverse, seed, flag=0, force=None, f
         if op in "MIS=X":
             q += n
     seq = list(seq)
+    for base, lo, hi in without:
+        for i in range(max(lo, 0), min(hi, L)):
+            q = L - 1 - i if reverse else i
+            if (COMP.get(seq[q]) if reverse else seq[q]) == base:
+                other = "A" if base == "T" else "T"
+                seq[q] = COMP[other] if reverse else other
     for q, p in where.items():
         if force and p in force:
             seq[q] = force[p]
@@ -551,7 +558,133 @@ def many_tags(prefix):
     return c
 
 
-BUILDERS = {"event_merge": event_merge, "edge_filter": edge_filter, "many_tags": many_tags}
+# ---------------------------------------------------------------------------------------------------------------------------------
+WINDOW_CALLS = (63, 64, 65, 127, 128, 129)      # listed calls inside one step window: the 64-entry rank batches of the producers, +- 1
+# decode class -> (layout, stored bases per step of its decoder, read length); "3d": the explicit pair with two different delta lists
+SEAM_CLASSES = {0: ("m", 4096, 4200), 1: ("h_m", 4096, 4200), 2: ("m_dot", 1024, 3100), 3: ("h_m_dot", 1024, 3100), "3d": ("h_m", 1024, 3100),
+                4: ("c4tags", 512, 1600)}
+SEAM_WINDOW = {4096: 0, 1024: 1, 512: 1}        # which step holds the counted window
+QCAP = 576                                      # MKP_QCAP, the FAST decoders' call queue
+
+
+def stored(i, n, rev):
+    """forward position <-> stored (SEQ) position of a read of n bases"""
+    return n - 1 - i if rev else i
+
+
+def fwd_span(lo, hi, n, rev):
+    """the forward positions of the stored bases [lo, hi)"""
+    return (n - hi, n - lo) if rev else (lo, hi)
+
+
+def keep_window(count, lo, hi, n, rev, differ=False):
+    """every tag lists exactly `count` bases among the stored bases [lo, hi) and every 40th candidate outside; differ: tag t skips the
+    first t candidates of the window, so the tags' delta lists differ"""
+    def keep(t, tag, cand):
+        inside = sorted((c for c in cand if lo <= stored(c[1], n, rev) < hi), key=lambda c: stored(c[1], n, rev))
+        skip = t if differ else 0
+        assert len(inside) >= count + skip, (len(inside), count)
+        return inside[skip:skip + count] + [c for c in cand if not lo <= stored(c[1], n, rev) < hi][::40]
+    return keep
+
+
+def keep_past_by_one(t, tag, cand):
+    """every base of the tag, and one entry more: the list runs past the last occurrence by exactly one"""
+    return cand + [(len(cand), cand[-1][1], None, False)]
+
+
+def keep_all_but_first(t, tag, cand):
+    return cand[t:]
+
+
+def stored_calls(rec, listed_only=False):
+    """per tag (or over all tags) the stored positions of the record's calls, from the record as written"""
+    n, rev = len(rec[3]), bool(rec[1] & 16)
+    if listed_only:
+        return [{stored(i, n, rev) for i in at} for _, _, at in written_calls(rec)[0]]
+    return {stored(i, n, rev) for i in called_positions(rec)}
+
+
+def producer_seams(prefix):
+    """4. the seams inside the producers of the three event decoders, every shape forward and reverse, one layout per decode class 0 - 4
+    (SEAM_CLASSES; classes 0 / 1 reach the event decoders with MKP_FUSED=0 and under the edge filter):
+    (a) exactly 63 / 64 / 65 / 127 / 128 / 129 listed calls inside one step window of the class's decoder (512, 1024 or 4096 stored
+        bases), sparse calls outside it: a rank batch of exactly 64, the first batch against the reloaded ones, a list ending on a batch end;
+    (b) FAST steps whose calls all lie in the step's stored bases [512, 1024), all in [0, 512), and in both (the half-step append);
+    (c) the FAST queue at its capacity: an implicit-mode read whose first step leaves 63 calls queued (127 calls, all in its lower half) and
+        whose next step holds 512 occurrences of the base in its first 512 stored bases: 575 entries of MKP_QCAP = 576;
+    (d) SPARSE: an odd length and a length 8k + 1, the last stored base a listed call;
+    (e) a delta list that runs past the last occurrence of its base by exactly one: the read leaves no calls."""
+    r = random.Random(141)
+    ref = cases.make_ref(r, CONTIG_LEN)
+    L = Layer(142, ref, stride=16)
+    for cls, (layout, step, n) in SEAM_CLASSES.items():                       # (a)
+        lo = SEAM_WINDOW[step] * step
+        for count in WINDOW_CALLS:
+            for rev in (False, True):
+                a, b = fwd_span(lo, lo + step, n, rev)
+                L.add([(n, "M")], layout, rev, force_fwd={i: "C" for i in range(a, b, 3)}, keep=keep_window(count, lo, lo + step, n, rev, cls == "3d"),
+                      name="win%s_%03d_%d" % (cls, count, rev))
+    n = 3_100
+    for layout, keep in (("m_dot", None), ("h_m_dot", None), ("h_m", keep_all_but_first)):   # (b)
+        for rev in (False, True):
+            gone = [("C",) + fwd_span(0, 512, n, rev), ("C",) + fwd_span(1536, 2048, n, rev)]
+            L.add([(n, "M")], layout, rev, without=gone, keep=keep, name="half_%s_%d" % (layout, rev))
+    n = 2_100
+    for layout in ("m_dot", "h_m_dot"):                                        # (c)
+        for rev in (False, True):
+            on = [i for q in list(range(0, 508, 4)) + list(range(1024, 1536)) for i in (stored(q, n, rev),)]
+            L.add([(n, "M")], layout, rev, without=[("C",) + fwd_span(0, 1024, n, rev)], force_fwd={i: "C" for i in on}, name="qcap_%s_%d" % (layout, rev))
+    for n in (1_235, 1_601):                                                   # (d)
+        for layout in ("m", "h_m"):
+            for rev in (False, True):
+                L.add([(n, "M")], layout, rev, force_fwd={stored(n - 1, n, rev): "C"}, name="odd%d_%s_%d" % (n, layout, rev))
+    for layout in ("m", "h_m", "m_dot", "h_m_dot", "c4tags"):                  # (e)
+        for rev in (False, True):
+            L.add([(300, "M")], layout, rev, keep=keep_past_by_one, name="past_%s_%d" % (layout, rev))
+    for rev in (False, True):                                                  # two features on one column, as every BAM of this module has
+        L.add([(600, "M")], "dup_c", rev)
+    assert L.at + MAX_READ < CONTIG_LEN
+    L.background(0, L.at + 4_300, depth=2)
+    c = L.finish("producer_seams", "ps", prefix)
+    assert {0, 1, 2, 3, 4} <= set(c.classes)
+    by_name = {nm: (rec, cl) for rec, nm, cl in zip(c.records, c.read_names, c.classes)}
+    for cls, (layout, step, n) in SEAM_CLASSES.items():                       # from the records as written
+        lo = SEAM_WINDOW[step] * step
+        for count in WINDOW_CALLS:
+            for rev in (False, True):
+                rec, cl = by_name["win%s_%03d_%d" % (cls, count, rev)]
+                per_tag = stored_calls(rec, listed_only=True)
+                assert cl == (3 if cls == "3d" else cls) and len(rec[3]) == n and bool(rec[1] & 16) == rev
+                assert all(sum(1 for q in at if lo <= q < lo + step) == count for at in per_tag), (cls, count, rev)
+                assert all(any(not lo <= q < lo + step for q in at) for at in per_tag)
+                assert cls != "3d" or per_tag[0] != per_tag[1]
+    for layout in ("m_dot", "h_m_dot", "h_m"):
+        for rev in (False, True):
+            rec, cl = by_name["half_%s_%d" % (layout, rev)]
+            halves = [sum(1 for q in stored_calls(rec) if 512 * k <= q < 512 * k + 512) for k in range(6)]
+            assert cl in (2, 3) and halves[0] == 0 and halves[1] > 0 and halves[2] > 0 and halves[3] == 0 and halves[4] > 0 and halves[5] > 0, halves
+    for layout in ("m_dot", "h_m_dot"):
+        for rev in (False, True):
+            rec, cl = by_name["qcap_%s_%d" % (layout, rev)]
+            halves = [sum(1 for q in stored_calls(rec) if 512 * k <= q < 512 * k + 512) for k in range(3)]
+            assert cl in (2, 3) and halves == [127, 0, 512] and halves[0] - 64 + halves[2] == QCAP - 1, halves
+    for n in (1_235, 1_601):
+        assert n % 2 == 1 and (n == 1_235 or n % 8 == 1)
+        for layout in ("m", "h_m"):
+            for rev in (False, True):
+                rec, cl = by_name["odd%d_%s_%d" % (n, layout, rev)]
+                assert cl in (0, 1) and len(rec[3]) == n and all(n - 1 in at for at in stored_calls(rec, listed_only=True))
+    for layout in ("m", "h_m", "m_dot", "h_m_dot", "c4tags"):
+        for rev in (False, True):
+            rec, _ = by_name["past_%s_%d" % (layout, rev)]
+            fwd = revcomp(rec[3]) if rev else rec[3]
+            for part in rec[4].split(";")[:-1]:
+                assert sum(int(d) + 1 for d in part.split(",")[1:]) == fwd.count(part[0]) + 1      # the last rank is the number of bases
+    return c
+
+
+BUILDERS = {"event_merge": event_merge, "edge_filter": edge_filter, "many_tags": many_tags, "producer_seams": producer_seams}
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -570,6 +703,8 @@ def flag_sets(case):
                 for f in focus:
                     out.append(f + ["--edge-filter", text] + inv + (thr if len(out) % 3 == 1 else nof))
         return out
+    if case.name == "producer_seams":  # no focus, unfiltered; --cpg; --filter-threshold; one edge filter (every class through its event decoder)
+        return [focus[3] + nof, focus[1] + nof, focus[3] + thr, focus[3] + ["--edge-filter", "50"] + nof]
     out = [focus[0] + thr, focus[1] + nof, focus[2] + nof, focus[3] + thr,
            focus[0] + ["--combine-mods"] + nof, focus[1] + ["--combine-mods"] + thr, focus[2] + ["--combine-mods"] + thr,
            focus[3] + ["--combine-mods"] + nof]
@@ -633,4 +768,5 @@ FLOORS = {
     "event_merge": [(29858, 1703, 20356, 0), (4863, 276, 20356, 0), (2820, 261, 20356, 0), (29858, 1703, 20356, 0), (26206, 1531, 20356, 0), (2808, 140, 20356, 0), (1526, 132, 20356, 0), (26206, 1531, 20356, 0), (29858, 1703, 20356, 0), (4859, 276, 20356, 0), (1125, 54, 20356, 0), (8584, 393, 20356, 0)],
     "edge_filter": [(39641, 10741, 13909, 9937), (5734, 877, 13909, 9937), (3082, 918, 13909, 9937), (39641, 10741, 13909, 9937), (6897, 1737, 910, 96212), (2379, 352, 910, 96212), (1719, 340, 910, 96212), (6897, 1737, 910, 96212), (40800, 11478, 14338, 5112), (5904, 994, 14338, 5112), (3044, 842, 14338, 5112), (40800, 11478, 14338, 5112), (5583, 1350, 481, 101037), (1018, 133, 481, 101037), (1094, 199, 481, 101037), (5583, 1350, 481, 101037), (34477, 8227, 14341, 5087), (5911, 986, 14341, 5087), (3127, 926, 14341, 5087), (34477, 8227, 14341, 5087), (5601, 1490, 478, 101062), (1449, 213, 478, 101062), (858, 136, 478, 101062), (5601, 1490, 478, 101062), (21530, 4917, 5214, 74195), (3940, 595, 5214, 74195), (2250, 629, 5214, 74195), (21530, 4917, 5214, 74195), (23549, 5348, 7498, 51032), (5216, 827, 7498, 51032), (2790, 779, 7498, 51032), (23549, 5348, 7498, 51032), (3371, 690, 49, 103864), (1077, 144, 49, 103864), (675, 104, 49, 103864), (3371, 690, 49, 103864), (17872, 4663, 4077, 74316), (3261, 502, 4077, 74316), (1986, 508, 4077, 74316), (17872, 4663, 4077, 74316)],
     "many_tags": [(23586, 2533, 6321, 0), (5302, 415, 6321, 0), (3055, 399, 6321, 0), (23586, 2533, 6321, 0), (16755, 2069, 6321, 0), (2309, 170, 6321, 0), (1304, 164, 6321, 0), (16755, 2069, 6321, 0)],
+    "producer_seams": [(43492, 29584, 314, 0), (7538, 2678, 314, 0), (38390, 25867, 314, 0), (41705, 28740, 261, 4787)],
 }
