@@ -229,7 +229,9 @@ int mkp_process_region(mkp_ctx* ctx, const char* bam_path, const mkp_shard* shar
  * over the run's rows while they are in HBM (mkp_stats_* below); with --region-stats-only the rows are neither read back nor written
  * (the out.bed positional is still required, the file is not created); plus --localize <regions.bed> --localize-out <table.tsv>
  * [--localize-window N (2000)] [--localize-stranded same|opposite] [--localize-stranded-features +|-|.] [--localize-only]: `modkit localize`
- * over the run's rows (mkp_localize_* below; contig lengths from the BAM header), combinable with --region-stats. */
+ * over the run's rows (mkp_localize_* below; contig lengths from the BAM header), combinable with --region-stats; plus
+ * --merge-bedmethyl <prior.bed> (repeatable): out.bed is `modkit bedmethyl merge` of the run's rows with the prior plain-text tables,
+ * joined on the device (mkp_merge_* below; contig lengths and order from the BAM header; the run's rows are not read back per shard). */
 int mkp_pileup_main(int argc, const char* const* argv, char* errbuf, size_t errbuf_len);
 
 /* The same subcommand on a context the caller owns (so the device named by the ctx is used and --device is ignored):
@@ -502,6 +504,46 @@ const char* mkp_genome_sizes_name(const mkp_genome_sizes* sizes, uint32_t i);
 uint64_t mkp_genome_sizes_length(const mkp_genome_sizes* sizes, uint32_t i);
 void mkp_genome_sizes_free(mkp_genome_sizes* sizes);
 int mkp_host_localize_table(const mkp_localize_out* counts, const char* out_path);
+
+/* ---- `modkit bedmethyl merge` (merge_data, src/bedmethyl_util/subcommands.rs:136-195) on the device (mkp_merge.hip): an outer join of
+ * bedMethyl row sets on (start, mod code, strand) that sums valid_coverage and the seven other counts.  One merged row table per contig
+ * lives in HBM from mkp_merge_begin on; every add is one two-way merge of the contig's table with the rows added.
+ *   mkp_merge_begin         contig_len_by_tid = the genome-sizes table (or the BAM header's lengths); frees the tables of the session
+ *                           before.  A contig longer than 2^32 - 1 is MKP_E_UNSUPPORTED.
+ *   mkp_merge_add_rows      rows of ONE contig, all eleven columns (pos, strand, code_repr, n_valid .. n_nocall), ascending pos
+ *                           (MKP_E_INVALID otherwise), in any order inside a position; motif_idx is not read.  Rows that share a key are
+ *                           summed even inside one call, as the reference puts every line of every input into one map (two motifs at one
+ *                           position collapse).  Rows at pos >= the contig's length, or on a tid the sizes do not list, are dropped and
+ *                           counted (the reference's feeder walks [0, length) of the listed contigs).
+ *   mkp_merge_add_resident  the rows the last mkp_shard_run / mkp_shard_rerun on this ctx left in HBM (their motif is dropped); refusals as
+ *                           mkp_stats_add_resident.
+ *   mkp_merge_get           the merged rows of one contig, ordered by start, then strand ('+' < '-' < '.'), then code (ModCodeRepr's derived Ord,
+ *                           which the reference's sort calls: letters by code point, then ChEBI numbers by number): all columns of mkp_rows, motif_idx = -1, no
+ *                           partition keys.  A contig without rows gives n_rows = 0.  *n_dropped (may be NULL) = the rows dropped since
+ *                           mkp_merge_begin.  A summed count beyond 2^32 - 1 is MKP_E_UNSUPPORTED (rows carry 32-bit counts, the reference
+ *                           sums in 64 bits; a wrapped value is never returned), as is a position that holds more rows than a tile of
+ *                           the merge kernel has room for (over a thousand; reported by the add that meets it).  Arrays owned by the ctx
+ *                           until its next mkp_merge_begin / mkp_merge_get of the same contig.
+ *   mkp_merge_tile_rows     the rows between two tile cuts of the merge kernel (for tests that put a run of equal keys on a tile edge).
+ * The written line follows to_line (src/tabix.rs:33-74): the bare code as the name, score = column 10 = the summed valid_coverage,
+ * percent = (n_mod as f32 / n_valid as f32) * 100 with {:.2}, `NaN` when n_valid is 0.
+ * Host-only half: mkp_host_read_bedmethyl reads a PLAIN-TEXT bedMethyl (tabs and / or blanks; '#' lines skipped) into runs of lines on
+ * one contig; a line that does not parse is MKP_E_IO with the line named (the reference drops its 100 kb chunk silently), a gzip / bgzip
+ * file MKP_E_UNSUPPORTED.  mkp_bedmethyl_file_rows fills the eleven columns of run `run` (arrays owned by the file object).
+ * mkp_bedmethyl_merge_main = `mkpileup bedmethyl merge a.bed b.bed [..] -g sizes.tsv -o out.bed [--force] [--bgzf] [--device N] [--stats]`:
+ * contigs come out in the order of the sizes file, those without a row are not written; *n_written / *n_dropped may be NULL. */
+int mkp_merge_begin(mkp_ctx* ctx, const uint64_t* contig_len_by_tid, uint32_t n_contigs);
+int mkp_merge_add_rows(mkp_ctx* ctx, int32_t tid, const mkp_rows* rows);
+int mkp_merge_add_resident(mkp_ctx* ctx);
+int mkp_merge_get(mkp_ctx* ctx, int32_t tid, mkp_rows* out, uint64_t* n_dropped);
+uint32_t mkp_merge_tile_rows(void);
+typedef struct mkp_bedmethyl_file mkp_bedmethyl_file;
+int mkp_host_read_bedmethyl(const char* path, mkp_bedmethyl_file** out, char* errbuf, size_t errbuf_len);
+uint32_t mkp_bedmethyl_file_runs(const mkp_bedmethyl_file* file);
+const char* mkp_bedmethyl_file_chrom(const mkp_bedmethyl_file* file, uint32_t run);
+int mkp_bedmethyl_file_rows(const mkp_bedmethyl_file* file, uint32_t run, mkp_rows* out);
+void mkp_bedmethyl_file_free(mkp_bedmethyl_file* file);
+int mkp_bedmethyl_merge_main(int argc, const char* const* argv, uint64_t* n_written, uint64_t* n_dropped, char* errbuf, size_t errbuf_len);
 
 /* ---- BGZF inflate on the device as a call of its own.  On the pileup path the same kernels run inside the device ingest
  * (`mkp_pileup_main` on an indexed BAM: compressed blocks up, inflate + CRC-32 + record cut + MM/ML tokeniser + packing in HBM, a digest

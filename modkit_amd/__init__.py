@@ -112,6 +112,22 @@ def lib():
             L.mkp_genome_sizes_free.argtypes = [ctypes.c_void_p]
             L.mkp_genome_sizes_free.restype = None
             L.mkp_host_localize_table.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
+        if hasattr(L, "mkp_merge_begin"):
+            L.mkp_merge_begin.argtypes = [ctypes.c_void_p, u64p, ctypes.c_uint32]
+            L.mkp_merge_add_rows.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]
+            L.mkp_merge_add_resident.argtypes = [ctypes.c_void_p]
+            L.mkp_merge_get.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, u64p]
+            L.mkp_merge_tile_rows.argtypes = []
+            L.mkp_merge_tile_rows.restype = ctypes.c_uint32
+            L.mkp_host_read_bedmethyl.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.c_size_t]
+            L.mkp_bedmethyl_file_runs.argtypes = [ctypes.c_void_p]
+            L.mkp_bedmethyl_file_runs.restype = ctypes.c_uint32
+            L.mkp_bedmethyl_file_chrom.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+            L.mkp_bedmethyl_file_chrom.restype = ctypes.c_char_p
+            L.mkp_bedmethyl_file_rows.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
+            L.mkp_bedmethyl_file_free.argtypes = [ctypes.c_void_p]
+            L.mkp_bedmethyl_file_free.restype = None
+            L.mkp_bedmethyl_merge_main.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), u64p, u64p, ctypes.c_char_p, ctypes.c_size_t]
         # the structs this binding allocates mirror ONE revision of include/mkpileup.h: a library of another revision would write past them
         if os.environ.get("MKP_LIB_PATH") and not hasattr(L, "mkp_abi_version"):
             _lib = L   # (A/B runs against a build from before the query existed, tools/dbg/ab.sh)
@@ -141,7 +157,9 @@ EXPORTS = ["mkp_ctx_create", "mkp_ctx_destroy", "mkp_last_error", "mkp_version",
            "mkp_region_set_chrom", "mkp_region_set_name", "mkp_region_set_free", "mkp_host_stats_table",
            "mkp_localize_begin", "mkp_localize_add_resident", "mkp_localize_add_rows", "mkp_localize_get", "mkp_localize_tile_offsets",
            "mkp_host_parse_localize_regions", "mkp_host_parse_genome_sizes", "mkp_genome_sizes_size", "mkp_genome_sizes_name",
-           "mkp_genome_sizes_free", "mkp_host_localize_table"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
+           "mkp_genome_sizes_free", "mkp_host_localize_table",
+           "mkp_merge_begin", "mkp_merge_add_rows", "mkp_merge_add_resident", "mkp_merge_get", "mkp_merge_tile_rows", "mkp_host_read_bedmethyl",
+           "mkp_bedmethyl_file_runs", "mkp_bedmethyl_file_chrom", "mkp_bedmethyl_file_rows", "mkp_bedmethyl_file_free", "mkp_bedmethyl_merge_main"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
 
 
 def pileup(argv):
@@ -166,6 +184,21 @@ def pileup_hemi(argv):
     if rc != MKP_OK:
         raise MkpError(rc, err.value.decode(errors="replace"))
     return rc
+
+
+def bedmethyl_merge(argv):
+    """`modkit bedmethyl merge` (EntryMergeBedMethyl::run, src/bedmethyl_util/subcommands.rs:198-371) on the device: argv = [a.bed, b.bed, ...,
+    "-g", sizes.tsv, "-o", out.bed, "--force", "--bgzf"]; the inputs are PLAIN-TEXT bedMethyl tables.  Returns (rows written, rows dropped):
+    a row is dropped when its contig is not in the sizes file or its start is not below the contig's length."""
+    L = lib()
+    args = [str(a).encode() for a in argv]
+    arr = (ctypes.c_char_p * max(1, len(args)))(*args)
+    err = ctypes.create_string_buffer(2048)
+    written, dropped = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    rc = L.mkp_bedmethyl_merge_main(len(args), arr, ctypes.byref(written), ctypes.byref(dropped), err, len(err))
+    if rc != MKP_OK:
+        raise MkpError(rc, err.value.decode(errors="replace"))
+    return int(written.value), int(dropped.value)
 
 
 def extract_calls(argv):
@@ -317,6 +350,32 @@ def localize_tile_offsets():
     return int(lib().mkp_localize_tile_offsets())
 
 
+def merge_tile_rows():
+    """mkp_merge_tile_rows: the rows between two tile cuts of the merge kernel."""
+    return int(lib().mkp_merge_tile_rows())
+
+
+def read_bedmethyl_runs(path):
+    """mkp_host_read_bedmethyl: a PLAIN-TEXT bedMethyl (tabs and / or blanks, '#' lines skipped, the code = the name up to its first comma,
+    n_valid = the score column) as [(chrom, rows dict with all eleven columns), ...], one entry per run of lines on one contig, file order."""
+    L = lib()
+    h = ctypes.c_void_p()
+    err = ctypes.create_string_buffer(2048)
+    rc = L.mkp_host_read_bedmethyl(str(path).encode(), ctypes.byref(h), err, len(err))
+    if rc != MKP_OK:
+        raise MkpError(rc, err.value.decode(errors="replace"))
+    try:
+        out = []
+        for k in range(L.mkp_bedmethyl_file_runs(h)):
+            r = Rows()
+            if L.mkp_bedmethyl_file_rows(h, k, ctypes.byref(r)) != MKP_OK:
+                raise MkpError(-1, "mkp_bedmethyl_file_rows failed")
+            out.append((L.mkp_bedmethyl_file_chrom(h, k).decode(), rows_to_numpy(r)))
+        return out
+    finally:
+        L.mkp_bedmethyl_file_free(h)
+
+
 def genome_sizes(path):
     """mkp_host_parse_genome_sizes: [(contig, length), ...] of a `chrom<whitespace>length` file; a later line for a contig replaces its length."""
     L = lib()
@@ -401,11 +460,14 @@ def _region_array(regions):
     return arr, n
 
 
-def _rows_struct(rows):
-    """(Rows over the five columns the row reducers read, the arrays it points into) of a dict of arrays."""
+MERGE_COUNT_FIELDS = ("n_valid", "n_mod", "n_canonical", "n_other", "n_delete", "n_fail", "n_diff", "n_nocall")
+
+
+def _rows_struct(rows, all_columns=False):
+    """(Rows over the five columns the row reducers read — or all eleven, for the merge —, the arrays it points into) of a dict of arrays."""
     import numpy as np
     cols = {f: np.ascontiguousarray(np.asarray(rows[f], dtype=np.uint8 if f == "strand" else np.uint32))
-            for f in ("pos", "strand", "code_repr", "n_valid", "n_mod")}
+            for f in ("pos", "strand", "code_repr") + (MERGE_COUNT_FIELDS if all_columns else ("n_valid", "n_mod"))}
     r = Rows()
     r.n_rows = len(cols["pos"])
     for f, a in cols.items():
@@ -643,6 +705,27 @@ class Context:
         k, n, arr = int(o.n_codes), 2 * int(o.window) + 1, _copy_out
         return {"codes": arr(o.code_repr, (k,), "u4"), "window": int(o.window), "n_mod": arr(o.n_mod, (k, n), "u8"),
                 "n_valid": arr(o.n_valid, (k, n), "u8"), "n_rows": arr(o.n_rows, (k, n), "u8")}
+
+    def merge_begin(self, contig_lengths):
+        """mkp_merge_begin: contig_lengths[tid] = the genome-sizes table; drops the tables of the session before."""
+        lens = (ctypes.c_uint64 * max(1, len(contig_lengths)))(*[int(x) for x in contig_lengths])
+        self._check(self.L.mkp_merge_begin(self.h, lens, len(contig_lengths)))
+
+    def merge_add_rows(self, tid, rows):
+        """mkp_merge_add_rows: rows of ONE contig, ascending pos (any order inside a position), as a dict of arrays with all eleven columns
+        (what read_bedmethyl / read_bedmethyl_runs / rows_to_numpy give); joined into the contig's table on the device."""
+        r, _keep = _rows_struct(rows, all_columns=True)
+        self._check(self.L.mkp_merge_add_rows(self.h, int(tid), ctypes.byref(r)))
+
+    def merge_add_resident(self):
+        """mkp_merge_add_resident: join the rows the last shard run left in HBM into their contig's table."""
+        self._check(self.L.mkp_merge_add_resident(self.h))
+
+    def merge_get(self, tid):
+        """mkp_merge_get: (the merged rows of contig `tid` as rows_to_numpy gives them — motif_idx = -1 —, rows dropped since merge_begin)."""
+        rows, dropped = Rows(), ctypes.c_uint64(0)
+        self._check(self.L.mkp_merge_get(self.h, int(tid), ctypes.byref(rows), ctypes.byref(dropped)))
+        return rows_to_numpy(rows), int(dropped.value)
 
     def rerun(self, iters, fetch=False):
         rows = Rows()

@@ -478,7 +478,10 @@ void mkp_ctx_destroy(mkp_ctx* c) {
                         &c->d_zin, &c->d_zout,
                         &c->d_zblk, &c->d_zstat, &c->d_summary, &c->d_bedmask, &c->d_hist64, &c->rstats.d_out, &c->rstats.d_seen,
                         &c->rstats.d_cnt, &c->rstats.d_off, &c->loc.d_tab}) b->release();
-  for (mkp_ctx::RowTable* t : {static_cast<mkp_ctx::RowTable*>(&c->rstats), static_cast<mkp_ctx::RowTable*>(&c->loc)}) {
+  for (auto& kv : c->merge.contigs) for (DevBuf& b : kv.second.buf) b.release();
+  for (DevBuf* b : {&c->merge.d_stage, &c->merge.d_cuts, &c->merge.d_counts, &c->merge.d_offsets}) b->release();
+  for (mkp_ctx::RowTable* t : {static_cast<mkp_ctx::RowTable*>(&c->rstats), static_cast<mkp_ctx::RowTable*>(&c->loc),
+      static_cast<mkp_ctx::RowTable*>(&c->merge)}) {
     for (DevBuf* b : {&t->d_regions, &t->d_misc, &t->d_lo, &t->d_hi, &t->d_rows}) b->release();
     for (auto& e : t->ev) if (e) (void)hipEventDestroy(e);
   }
@@ -1293,8 +1296,10 @@ namespace {
 struct RowTableWords { const char *begin, *needs, *launch, *inside, *holds; };
 constexpr RowTableWords kStatsWords = {"mkp_stats_begin", "region statistics need", "region stats", "regions", "region statistics hold"};
 constexpr RowTableWords kLocWords = {"mkp_localize_begin", "localize needs", "localize", "windows", "localize holds"};
-// the five columns the reducers read, on the device; info = 0 '+', 1 '-', 2 '.' in its low bits
-struct RowCols { const uint32_t *pos, *info, *code, *n_valid, *n_mod; uint64_t n; };
+constexpr RowTableWords kMergeWords = {"mkp_merge_begin", "bedmethyl merge needs", "bedmethyl merge", "tables", "bedmethyl merge holds"};
+// the five columns the reducers read, on the device; info = 0 '+', 1 '-', 2 '.' in its low bits; rest = n_canonical, n_other, n_delete,
+// n_fail, n_diff, n_nocall, which only the merge reads (not uploaded for the reducers)
+struct RowCols { const uint32_t *pos, *info, *code, *n_valid, *n_mod; uint64_t n; const uint32_t* rest[6]; };
 
 void rt_need_open(const mkp_ctx::RowTable& T, const RowTableWords& W) { if (!T.open) throw Error(MKP_E_INVALID, std::string(W.begin) + " first"); }
 
@@ -1318,16 +1323,18 @@ RowCols rt_resident_rows(mkp_ctx* c, const mkp_ctx::RowTable& T, const RowTableW
       "no pileup rows are resident: call mkp_shard_run first (pileup-hemi rows are pattern counts, not bedMethyl rows)");
   hip_check(hipSetDevice(c->device), "hipSetDevice");
   const MkpRowsDev& r = c->rows_dst;
-  return {r.pos, r.info, r.code, r.n_valid, r.n_mod, c->stats.n_rows};
+  return {r.pos, r.info, r.code, r.n_valid, r.n_mod, c->stats.n_rows, {r.n_can, r.n_other, r.n_del, r.n_fail, r.n_diff, r.n_nocall}};
 }
 
-// the caller's rows, checked and uploaded into the session's own buffer (five columns, each padded to 64 rows)
-RowCols rt_upload_rows(mkp_ctx* c, mkp_ctx::RowTable& T, const RowTableWords& W, const mkp_rows* rows) {
+// the caller's rows, checked and uploaded into the session's own buffer (five columns, or all eleven, each padded to 64 rows)
+RowCols rt_upload_rows(mkp_ctx* c, mkp_ctx::RowTable& T, const RowTableWords& W, const mkp_rows* rows, bool all_columns = false) {
   rt_need_open(T, W);
   const uint64_t n = rows->n_rows;
   if (n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
   if (n && (!rows->pos || !rows->strand || !rows->code_repr || !rows->n_valid || !rows->n_mod)) throw Error(MKP_E_INVALID,
       "pos, strand, code_repr, n_valid and n_mod are needed");
+  if (n && all_columns && (!rows->n_canonical || !rows->n_other || !rows->n_delete || !rows->n_fail || !rows->n_diff || !rows->n_nocall))
+    throw Error(MKP_E_INVALID, "all eleven row columns are needed");
   std::vector<uint32_t> info(n);
   for (uint64_t i = 0; i < n; i++) {
     if (i && rows->pos[i] < rows->pos[i - 1]) throw Error(MKP_E_INVALID, "rows must be ascending in pos (row " + std::to_string(i) + ")");
@@ -1339,11 +1346,25 @@ RowCols rt_upload_rows(mkp_ctx* c, mkp_ctx::RowTable& T, const RowTableWords& W,
   hip_check(hipSetDevice(c->device), "hipSetDevice");
   hip_check(hipStreamSynchronize(c->stream), "sync");   // the previous call's kernels read the upload buffer
   const size_t col = ((size_t)n + 63) & ~(size_t)63;
-  T.d_rows.ensure(std::max<size_t>(col, 64) * 20);
+  const int n_cols = all_columns ? 11 : 5;
+  T.d_rows.ensure(std::max<size_t>(col, 64) * 4 * (size_t)n_cols);
   uint32_t* d = T.d_rows.as<uint32_t>();
-  const uint32_t* src[5] = {rows->pos, info.data(), rows->code_repr, rows->n_valid, rows->n_mod};
-  for (int k = 0; k < 5; k++) h2d_copy(d + (size_t)k * col, src[k], (size_t)n * 4);
-  return {d, d + col, d + 2 * col, d + 3 * col, d + 4 * col, n};
+  const uint32_t* src[11] = {rows->pos, info.data(), rows->code_repr, rows->n_valid, rows->n_mod, rows->n_canonical, rows->n_other,
+      rows->n_delete, rows->n_fail, rows->n_diff, rows->n_nocall};
+  for (int k = 0; k < n_cols; k++) h2d_copy(d + (size_t)k * col, src[k], (size_t)n * 4);
+  RowCols r = {d, d + col, d + 2 * col, d + 3 * col, d + 4 * col, n, {}};
+  for (int k = 0; k < 6; k++) r.rest[k] = all_columns ? d + (size_t)(5 + k) * col : nullptr;
+  return r;
+}
+
+// launch(ev) queues the feature's kernels; with timing on it records three events around their two spans, which are waited for and summed
+template <class Launch> void rt_timed(mkp_ctx::RowTable& T, const RowTableWords& W, Launch launch) {
+  hip_check(launch(T.timing ? T.ev : nullptr), (std::string(W.launch) + " launch").c_str());
+  if (T.timing) {
+    hip_check(hipEventSynchronize(T.ev[2]), (std::string(W.launch) + " sync").c_str());
+    float a = 0, b = 0; hip_check(hipEventElapsedTime(&a, T.ev[0], T.ev[1]), "event"); hip_check(hipEventElapsedTime(&b, T.ev[1], T.ev[2]), "event");
+    T.kernel_ms[0] += a; T.kernel_ms[1] += b;
+  }
 }
 
 // one piece of contig `tid`: launch(first, n, ev) runs the feature's kernels over its regions [first, first + n) of d_regions
@@ -1352,12 +1373,7 @@ template <class Launch> void rt_launch(mkp_ctx* c, mkp_ctx::RowTable& T, const R
   if (n_rows) T.tids_with_rows.insert(tid);
   auto it = T.tid_range.find(tid);
   if (!n_rows || it == T.tid_range.end()) return;
-  hip_check(launch(it->second.first, it->second.second - it->second.first, T.timing ? T.ev : nullptr), (std::string(W.launch) + " launch").c_str());
-  if (T.timing) {
-    hip_check(hipEventSynchronize(T.ev[2]), (std::string(W.launch) + " sync").c_str());
-    float a = 0, b = 0; hip_check(hipEventElapsedTime(&a, T.ev[0], T.ev[1]), "event"); hip_check(hipEventElapsedTime(&b, T.ev[1], T.ev[2]), "event");
-    T.kernel_ms[0] += a; T.kernel_ms[1] += b;
-  }
+  rt_timed(T, W, [&](hipEvent_t* ev) { return launch(it->second.first, it->second.second - it->second.first, ev); });
 }
 
 int rt_timing(mkp_ctx* c, mkp_ctx::RowTable& T, int on, double ms_out[2]) {
@@ -1606,6 +1622,135 @@ int mkp_localize_get(mkp_ctx* c, mkp_localize_out* out) {
         L.h_mod[k * n_off + o] = e[0]; L.h_valid[k * n_off + o] = e[1]; L.h_rows[k * n_off + o] = e[2]; } }
     out->n_codes = (uint32_t)nc; out->window = L.window; out->code_repr = L.h_codes.data(); out->n_mod = L.h_mod.data();
     out->n_valid = L.h_valid.data(); out->n_rows = L.h_rows.data();
+  });
+}
+
+}  // extern "C"
+
+// ---- bedmethyl merge (`modkit bedmethyl merge`, include/mkpileup.h): one merged row table per contig stays in HBM between mkp_merge_begin
+// and the mkp_merge_get calls; every add is one two-way merge (mkp_merge.hip)
+extern "C" hipError_t mkp_launch_merge(hipStream_t, const MkpRowsDev* /*table*/, uint32_t, const MkpRowsDev* /*added rows*/, uint32_t,
+    const MkpRowsDev* /*staging*/, const MkpRowsDev* /*new table*/, MkpMergeCut* /*cuts*/, uint32_t* /*tile counts*/, uint32_t* /*tile offsets*/,
+    uint32_t* /*rows of the new table*/, uint32_t* /*error bits*/, hipEvent_t* /*3 timing events or NULL*/);
+extern "C" hipError_t mkp_launch_merge_rows_below(hipStream_t, const uint32_t* /*pos*/, uint32_t, uint32_t /*limit*/, uint32_t* /*out*/);
+extern "C" uint32_t mkp_merge_tiles(uint64_t n_rows);
+
+namespace {
+// d_misc: rows of the new table, the error word (kept over the session), the rows below the contig's length, a pad word
+constexpr size_t kMergeMiscBytes = 16;
+MkpRowsDev rows_at(uint32_t* p, uint64_t stride) {
+  return {p, p + stride, p + 2 * stride, p + 3 * stride, p + 4 * stride, p + 5 * stride, p + 6 * stride, p + 7 * stride, p + 8 * stride,
+      p + 9 * stride, p + 10 * stride};
+}
+// r: rows of contig `tid` on the device, ascending pos; those at pos >= the contig's length (n_kept on) are dropped and counted
+void merge_add(mkp_ctx* c, int32_t tid, const RowCols& r, uint64_t n_kept) {
+  mkp_ctx::Merge& M = c->merge;
+  if (r.n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one piece");
+  M.n_dropped += r.n - n_kept;
+  if (!n_kept) return;
+  mkp_ctx::Merge::Contig& C = M.contigs[tid];
+  const uint64_t total = (uint64_t)C.n + n_kept;
+  if (total > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows on one contig");
+  const int to = C.cur ^ 1;
+  const uint64_t stride = (total + 63) & ~(uint64_t)63;
+  C.buf[to].ensure(stride * 44); C.stride[to] = stride;
+  M.d_stage.ensure(stride * 44);
+  const size_t n_tiles = mkp_merge_tiles(total);
+  M.d_cuts.ensure((n_tiles + 1) * sizeof(MkpMergeCut)); M.d_counts.ensure(n_tiles * 4); M.d_offsets.ensure(n_tiles * 4);
+  const MkpRowsDev a = rows_at(C.buf[C.cur].as<uint32_t>(), C.stride[C.cur]), out = rows_at(C.buf[to].as<uint32_t>(), stride),
+      stage = rows_at(M.d_stage.as<uint32_t>(), stride);
+  const MkpRowsDev b = {const_cast<uint32_t*>(r.pos), const_cast<uint32_t*>(r.info), const_cast<uint32_t*>(r.code), const_cast<uint32_t*>(r.n_valid),
+      const_cast<uint32_t*>(r.n_mod), const_cast<uint32_t*>(r.rest[0]), const_cast<uint32_t*>(r.rest[1]), const_cast<uint32_t*>(r.rest[2]),
+      const_cast<uint32_t*>(r.rest[3]), const_cast<uint32_t*>(r.rest[4]), const_cast<uint32_t*>(r.rest[5])};
+  uint32_t* misc = M.d_misc.as<uint32_t>();
+  rt_timed(M, kMergeWords, [&](hipEvent_t* ev) {
+    return mkp_launch_merge(c->stream, &a, C.n, &b, (uint32_t)n_kept, &stage, &out, M.d_cuts.as<MkpMergeCut>(), M.d_counts.as<uint32_t>(),
+        M.d_offsets.as<uint32_t>(), misc, misc + 1, ev);
+  });
+  // the one round trip of an add: the new table's size (the next add's buffers are sized by it) and the error word
+  uint32_t words[2] = {0, 0};
+  d2h_copy(words, misc, sizeof(words), c->stream);
+  M.err_bits |= words[1];
+  if (words[1] & MKP_MERGE_ERR_TILE) throw Error(MKP_E_UNSUPPORTED, "bedmethyl merge: one position of contig " + std::to_string(tid)
+      + " holds more than " + std::to_string(MKP_MERGE_CAP - MKP_MERGE_TILE) + " rows: more than a tile of the merge kernel has room for");
+  C.n = words[0]; C.cur = to;
+}
+uint64_t merge_contig_len(const mkp_ctx::Merge& M, int32_t tid) { return tid >= 0 && (size_t)tid < M.contig_len.size() ? M.contig_len[(size_t)tid] : 0ull; }
+}  // namespace
+
+extern "C" {
+
+int mkp_internal_merge_timing(mkp_ctx* c, int on, double ms_out[2]) { return c ? rt_timing(c, c->merge, on, ms_out) : MKP_E_INVALID; }
+
+int mkp_merge_begin(mkp_ctx* c, const uint64_t* contig_len_by_tid, uint32_t n_contigs) {
+  if (!c || (!contig_len_by_tid && n_contigs)) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Merge& M = c->merge;
+    M.open = false;
+    for (uint32_t k = 0; k < n_contigs; k++) if (contig_len_by_tid[k] > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED,
+        "contig " + std::to_string(k) + " is longer than 2^32 - 1");
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    hip_check(hipStreamSynchronize(c->stream), "sync");   // (a previous session's kernels)
+    for (auto& kv : M.contigs) for (DevBuf& b : kv.second.buf) b.release();
+    M.contigs.clear(); M.contig_len.assign(contig_len_by_tid, contig_len_by_tid + n_contigs); M.n_dropped = 0; M.err_bits = 0;
+    M.d_misc.ensure(kMergeMiscBytes);
+    hip_check(hipMemsetAsync(M.d_misc.p, 0, kMergeMiscBytes, c->stream), "memset");
+    hip_check(hipStreamSynchronize(c->stream), "sync");
+    M.open = true;
+  });
+}
+
+int mkp_merge_add_resident(mkp_ctx* c) {
+  if (!c) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Merge& M = c->merge;
+    const RowCols r = rt_resident_rows(c, M, kMergeWords);
+    if (r.n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one piece");
+    const uint64_t len = merge_contig_len(M, c->shard.tid);
+    uint64_t n_kept = r.n;
+    if (!len) n_kept = 0;
+    else if (r.n && (int64_t)c->shard.win_end > (int64_t)len) {   // the shard's window reaches beyond the sizes' length: count the rows in front of it
+      uint32_t* misc = M.d_misc.as<uint32_t>();
+      hip_check(mkp_launch_merge_rows_below(c->stream, r.pos, (uint32_t)r.n, (uint32_t)len, misc + 2), "bedmethyl merge launch");
+      uint32_t below = 0; d2h_copy(&below, misc + 2, 4, c->stream); n_kept = below;
+    }
+    merge_add(c, c->shard.tid, r, n_kept);
+  });
+}
+
+int mkp_merge_add_rows(mkp_ctx* c, int32_t tid, const mkp_rows* rows) {
+  if (!c || !rows) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Merge& M = c->merge;
+    const RowCols r = rt_upload_rows(c, M, kMergeWords, rows, true);
+    const uint64_t len = merge_contig_len(M, tid);
+    const uint64_t n_kept = len > 0xffffffffull ? r.n : (uint64_t)(std::lower_bound(rows->pos, rows->pos + r.n, (uint32_t)len) - rows->pos);
+    merge_add(c, tid, r, n_kept);
+  });
+}
+
+int mkp_merge_get(mkp_ctx* c, int32_t tid, mkp_rows* out, uint64_t* n_dropped) {
+  if (!c || !out) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Merge& M = c->merge;
+    rt_need_open(M, kMergeWords);
+    if (M.err_bits & MKP_MERGE_ERR_TILE) throw Error(MKP_E_UNSUPPORTED, "bedmethyl merge: a position held more rows than a tile of the merge kernel has room for");
+    if (M.err_bits & MKP_MERGE_ERR_SUM) throw Error(MKP_E_UNSUPPORTED,
+        "bedmethyl merge: a summed count does not fit in 32 bits (rows carry 32-bit counts; the reference sums in 64 bits)");
+    memset(out, 0, sizeof(*out));
+    if (n_dropped) *n_dropped = M.n_dropped;
+    auto it = M.contigs.find(tid);
+    if (it == M.contigs.end() || !it->second.n) return;
+    mkp_ctx::Merge::Contig& C = it->second;
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    const uint32_t* d = C.buf[C.cur].as<uint32_t>();
+    for (int k = 0; k < 11; k++) { C.h_col[k].resize(C.n); d2h_copy(C.h_col[k].data(), d + (size_t)k * C.stride[C.cur], (size_t)C.n * 4, c->stream); }
+    C.h_strand.resize(C.n); C.h_motif.assign(C.n, -1);
+    for (uint32_t i = 0; i < C.n; i++) C.h_strand[i] = (uint8_t)"+-."[C.h_col[1][i] & 3u];
+    out->n_rows = C.n; out->pos = C.h_col[0].data(); out->strand = C.h_strand.data(); out->code_repr = C.h_col[2].data();
+    out->motif_idx = C.h_motif.data(); out->n_valid = C.h_col[3].data(); out->n_mod = C.h_col[4].data(); out->n_canonical = C.h_col[5].data();
+    out->n_other = C.h_col[6].data(); out->n_delete = C.h_col[7].data(); out->n_fail = C.h_col[8].data(); out->n_diff = C.h_col[9].data();
+    out->n_nocall = C.h_col[10].data();
   });
 }
 

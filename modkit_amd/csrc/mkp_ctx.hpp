@@ -209,6 +209,16 @@ struct mkp_ctx {
     mkp::DevBuf d_tab;
     std::vector<uint32_t> h_codes; std::vector<uint64_t> h_mod, h_valid, h_rows;   // mkp_localize_get
   } loc;
+  // bedmethyl merge (mkp_merge_begin .. mkp_merge_get, mkp_merge.hip): one merged row table per contig in HBM, ping-pong: an add merges
+  // `cur` with the added rows into `alt` through the staging table and swaps.  Of RowTable: open, the upload buffer, the error word, timing
+  // ([partition, tile + scan + compaction])
+  struct Merge : RowTable {
+    struct Contig { mkp::DevBuf buf[2]; uint64_t stride[2] = {0, 0}; int cur = 0; uint32_t n = 0;
+      std::vector<uint32_t> h_col[11]; std::vector<uint8_t> h_strand; std::vector<int32_t> h_motif; };   // mkp_merge_get
+    std::vector<uint64_t> contig_len; std::map<int32_t, Contig> contigs;
+    mkp::DevBuf d_stage, d_cuts, d_counts, d_offsets;
+    uint64_t n_dropped = 0; uint32_t err_bits = 0;
+  } merge;
   bool skip_row_fetch = false;   // `--region-stats-only`: mkp_shard_run leaves the rows in HBM (no column read-back, n_rows = 0 in its output)
   // device ingest of indexed BAMs (mkp_ingest_host.cpp): created on first use, lives with the context (staging + window buffers are reused)
   struct mkp_dev_ingest* ingest = nullptr;
@@ -249,3 +259,5 @@ extern "C" int mkp_internal_stats_timing(mkp_ctx* c, int on, double ms_out[2]);
 extern "C" int mkp_internal_skip_row_fetch(mkp_ctx* c, int on);
 // localize: the same for its two kernels [bounds, reduce]
 extern "C" int mkp_internal_localize_timing(mkp_ctx* c, int on, double ms_out[2]);
+// bedmethyl merge: the same for [partition, tile + scan + compaction]
+extern "C" int mkp_internal_merge_timing(mkp_ctx* c, int on, double ms_out[2]);

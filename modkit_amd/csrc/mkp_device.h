@@ -307,6 +307,15 @@ struct MkpStatsRegion { uint32_t start, end; uint32_t rule /* 1 '+', 2 '-', 3 bo
 #define MKP_LOC_BATCH 256u          // regions per batch = threads per workgroup
 #define MKP_LOC_MAX_WINDOW 100000u
 struct MkpLocRegion { uint32_t ws, we, anchor; uint32_t rules /* fetch rule | region rule << 8, each 1 '+', 2 '-', 3 both */; };
+// ---- bedmethyl merge (mkp_merge.hip): the output is cut into tiles at the merge-path diagonals k * MKP_MERGE_TILE, each cut moved back to
+// the start of the position it lands in; a workgroup sorts up to MKP_MERGE_CAP rows in LDS (16 B a row: 32 KiB).  A tile is its
+// MKP_MERGE_TILE rows plus what the position at its front holds behind the diagonal, so with the step a little under half the capacity
+// most tiles sort 1024 entries and a single position may hold up to MKP_MERGE_CAP - MKP_MERGE_TILE rows.
+#define MKP_MERGE_TILE 960u
+#define MKP_MERGE_CAP 2048u
+struct MkpMergeCut { uint32_t a, b; };   // rows of the table / of the added rows in front of a tile
+#define MKP_MERGE_ERR_TILE 1u       // device error bit: one position holds more rows than a tile has room for
+#define MKP_MERGE_ERR_SUM 2u        // device error bit: a summed count does not fit in 32 bits
 #ifdef __cplusplus
 static_assert(sizeof(MkpWork) == 72 && sizeof(MkpSlotEnt) == 8, "work record is 18 dwords");
 static_assert(sizeof(MkpFusedDesc) == 64 && sizeof(MkpVisit) == 32 && sizeof(MkpCallEnt) == 8 && sizeof(MkpBaseEnt) == 8, "slot pipeline records");

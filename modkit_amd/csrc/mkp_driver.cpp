@@ -21,6 +21,7 @@
 #include "mkp_ingest_host.hpp"
 #include "mkp_focus.hpp"
 #include "mkp_regions.hpp"
+#include "mkp_bedmethyl_in.hpp"
 #include "mkp_writer.hpp"
 #include "mkp_rand.hpp"
 #include "mkp_sample_schedule.hpp"
@@ -105,6 +106,9 @@ struct Args {
      -stranded-features = its --window / --stranded / --stranded-features; --localize-only: as --region-stats-only */
   std::string localize, localize_out; uint32_t localize_window = 2000; bool have_localize_window = false;
   int localize_stranded = 0, localize_stranded_features = 0; bool localize_only = false;
+  /* --merge-bedmethyl <prior.bed> (repeatable): the output is `bedmethyl merge` of this run's rows with the prior plain-text tables,
+     joined on the device from the rows in HBM (mkp_merge.hip); contig lengths and order from the BAM header */
+  std::vector<std::string> merge_bedmethyl;
   bool rows_stay() const { return region_stats_only || localize_only; }   // the rows are neither read back nor written
 };
 
@@ -1414,6 +1418,7 @@ void run_shards(const Args& a, Options& o, mkp_ctx* ctx, const ShardReader& read
       if (a.rerun) must(ctx, mkp_shard_rerun(ctx, a.rerun, &rows));   // measurement aid: warm, averaged kernel times in --stats
       if (!a.region_stats.empty()) must(ctx, mkp_stats_add_resident(ctx));   // the rows are still in HBM: this shard's share of every region
       if (!a.localize.empty()) must(ctx, mkp_localize_add_resident(ctx));     // ... and of every window
+      if (!a.merge_bedmethyl.empty()) must(ctx, mkp_merge_add_resident(ctx));  // --merge-bedmethyl: joined into the contig's table, not read back
       auto t_w = std::chrono::steady_clock::now();
       out.write(rec.name, rows);
       c.write_ms += ms_since(t_w);
@@ -1493,7 +1498,7 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
   // --region-stats: the regions (contigs by the BAM header's names) and the run-long table in HBM; --region-stats-only: no row read-back
   mkp_region_set rset;
   struct RowFetchGuard { mkp_ctx* c; ~RowFetchGuard() { if (c) { mkp_internal_skip_row_fetch(c, 0); mkp_internal_stats_timing(c, 0, nullptr);
-      mkp_internal_localize_timing(c, 0, nullptr); } } } fetch_guard{nullptr};
+      mkp_internal_localize_timing(c, 0, nullptr); mkp_internal_merge_timing(c, 0, nullptr); } } } fetch_guard{nullptr};
   if (!a.region_stats.empty()) {
     rset = parse_regions_bed(a.region_stats, [&](const std::string& chrom) { return bam.tid_of(chrom); });
     must(ctx, mkp_stats_begin(ctx, rset.regions.data(), (uint32_t)rset.regions.size(), a.region_stats_codes.data(),
@@ -1514,12 +1519,47 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
     if (a.stats) must(ctx, mkp_internal_localize_timing(ctx, 1, nullptr));
     if (skipped) mark("  localize: regions BED lines skipped");
   }
-  if (a.rows_stay()) must(ctx, mkp_internal_skip_row_fetch(ctx, 1));
+  // --merge-bedmethyl: the prior tables go up before the first shard; every shard's rows are then joined where they are
+  double merge_upload_ms = 0; uint64_t merge_prior_rows = 0;
+  if (!a.merge_bedmethyl.empty()) {
+    auto t_m = std::chrono::steady_clock::now();
+    std::vector<uint64_t> lens(bam.ref_lens.begin(), bam.ref_lens.end());
+    must(ctx, mkp_merge_begin(ctx, lens.data(), (uint32_t)lens.size()));
+    fetch_guard.c = ctx;
+    if (a.stats) must(ctx, mkp_internal_merge_timing(ctx, 1, nullptr));
+    for (const std::string& path : a.merge_bedmethyl) {
+      const mkp_bedmethyl_file prior = read_bedmethyl_text(path);
+      merge_prior_rows += prior.n_rows();
+      for (size_t k = 0; k < prior.runs.size(); k++) { const mkp_rows rows = prior.rows_of(k);
+        must(ctx, mkp_merge_add_rows(ctx, bam.tid_of(prior.runs[k].chrom), &rows)); }
+    }
+    merge_upload_ms = ms_since(t_m);
+    mark("prior bedMethyl tables uploaded");
+  }
+  if (a.rows_stay() || !a.merge_bedmethyl.empty()) must(ctx, mkp_internal_skip_row_fetch(ctx, 1));
   build_plan(plan, a, kn, bam, o, g, size, !ahead.empty(), mark);
   // (thresholds known before the plan: the shards go ahead of the loop from here)
   if (ahead.empty() && plan.shards.size() > 1 && !kn.no_ahead) ahead.from_plan(plan.shards, records, o.bf);
   run_shards(a, o, ctx, reader, g, ahead, plan, early, out, c, mark);
   c.load_ms += c.fetch_wait_ms;   // what the shard loop waited for blocks to be read and inflated (the rest overlapped with pack / run / write)
+  if (!a.merge_bedmethyl.empty()) {   // the merged contigs, in the BAM header's order, through the writer of a plain run
+    uint64_t dropped = 0; double get_ms = 0, wr_ms = 0;
+    for (size_t tid = 0; tid < bam.ref_names.size(); tid++) {
+      auto t_g = std::chrono::steady_clock::now();
+      mkp_rows rows; must(ctx, mkp_merge_get(ctx, (int32_t)tid, &rows, &dropped));
+      get_ms += ms_since(t_g);
+      auto t_w = std::chrono::steady_clock::now();
+      out.write(bam.ref_names[tid], rows);
+      wr_ms += ms_since(t_w);
+    }
+    c.d2h_ms += get_ms; c.write_ms += wr_ms;
+    if (dropped) fprintf(stderr, "[mkpileup] bedmethyl merge: %llu rows dropped (beyond their contig's length, or on a contig the BAM header does not list)\n",
+        (unsigned long long)dropped);
+    if (a.stats) { double ms[2] = {0, 0}; mkp_internal_merge_timing(ctx, 0, ms);
+      fprintf(stderr, "[mkpileup] bedmethyl merge: %zu prior tables, %llu prior rows, upload + join of the priors %.1f ms; kernels partition %.3f ms, tile + scan + compaction %.3f ms (summed over the adds); merged rows d2h %.1f ms, formatted %.1f ms\n",
+          a.merge_bedmethyl.size(), (unsigned long long)merge_prior_rows, merge_upload_ms, ms[0], ms[1], get_ms, wr_ms); }
+    mark("merged rows with the writer");
+  }
   { auto t_w = std::chrono::steady_clock::now(); out.finish(); c.write_ms += ms_since(t_w); }
   out.close();
   mark("output closed");
@@ -1556,7 +1596,8 @@ void parse_args(int argc, const char* const* argv, Args* out, bool need_position
     std::string s = argv[i];
     auto val = [&]() { if (i + 1 >= argc) throw Error(MKP_E_INVALID, "missing value for " + s); return std::string(argv[++i]); };
     if (hemi && (s == "--preset" || s == "--combine-strands" || s == "--with-header" || s == "--header" || s == "--partition-tag" || s == "--prefix"
-        || s == "--bedgraph" || s == "--plan-only" || s.compare(0, 14, "--region-stats") == 0 || s.compare(0, 10, "--localize") == 0))
+        || s == "--bedgraph" || s == "--plan-only" || s.compare(0, 14, "--region-stats") == 0 || s.compare(0, 10, "--localize") == 0
+        || s == "--merge-bedmethyl"))
       throw Error(MKP_E_INVALID, "unexpected argument '" + s + "' for pileup-hemi");
     if (hemi && (s == "-o" || s == "--out-bed")) { a.out_bed = val(); continue; }
     if (s == "--region") a.region = val(); else if (s == "--max-depth") a.max_depth = (uint32_t)std::stoul(val());
@@ -1609,6 +1650,7 @@ void parse_args(int argc, const char* const* argv, Args* out, bool need_position
       a.localize_stranded_features = v == "+" || v == "positive" ? 1 : v == "-" || v == "negative" ? 2 : v == "." || v == "both" ? 3 : 0;
       if (!a.localize_stranded_features) throw Error(MKP_E_INVALID, "--localize-stranded-features takes +, - or ., not '" + v + "'"); }
     else if (s == "--localize-only") a.localize_only = true;
+    else if (s == "--merge-bedmethyl") a.merge_bedmethyl.push_back(val());
     else if (!s.empty() && s[0] == '-' && s != "-") throw Error(MKP_E_INVALID, "unknown flag " + s);
     else pos.push_back(s);
   }
@@ -1641,6 +1683,16 @@ void parse_args(int argc, const char* const* argv, Args* out, bool need_position
     if (a.localize_window > MKP_LOC_MAX_WINDOW) throw Error(MKP_E_UNSUPPORTED, "--localize-window beyond " + std::to_string(MKP_LOC_MAX_WINDOW));
     if (a.world > 1) throw Error(MKP_E_UNSUPPORTED,
         "--localize with --gpus-world > 1: the ranks' tables would have to be summed (an all-reduce that is not implemented)");
+  }
+  if (!a.merge_bedmethyl.empty()) {
+    if (!a.partition_tags.empty()) throw Error(MKP_E_INVALID,
+        "--merge-bedmethyl cannot be combined with --partition-tag: the rows of a partitioned run come grouped by key, not in genome order");
+    if (a.bedgraph) throw Error(MKP_E_INVALID, "--merge-bedmethyl cannot be combined with --bedgraph: the merged rows are bedMethyl lines");
+    if (!a.region_stats.empty() || !a.localize.empty()) throw Error(MKP_E_INVALID,
+        "--merge-bedmethyl cannot be combined with --region-stats / --localize: they reduce the run's own rows, not the merged ones");
+    if (a.plan_only) throw Error(MKP_E_INVALID, "--merge-bedmethyl cannot be combined with --plan-only");
+    if (a.world > 1) throw Error(MKP_E_UNSUPPORTED,
+        "--merge-bedmethyl with --gpus-world > 1: every rank would have to hold the prior tables and the ranks' outputs be joined");
   }
 }
 
@@ -1704,6 +1756,89 @@ extern "C" int mkp_host_localize_table(const mkp_localize_out* counts, const cha
 extern "C" int mkp_host_stats_table(const mkp_region_set* set, const mkp_stats_out* counts, int with_header, const char* out_path) {
   if (!set || !counts || !out_path) return MKP_E_INVALID;
   return guarded_status([&]() { write_text_file(out_path, stats_table_text(*set, *counts, with_header != 0, f32_display)); return MKP_OK; });
+}
+
+// `modkit bedmethyl merge`, host half (include/mkpileup.h): the plain-text reader, no device involved
+extern "C" int mkp_host_read_bedmethyl(const char* path, mkp_bedmethyl_file** out, char* errbuf, size_t errbuf_len) {
+  if (!path || !out) return fail_into(errbuf, errbuf_len, MKP_E_INVALID, "bad argument");
+  *out = nullptr;
+  return guarded_buf(errbuf, errbuf_len, [&]() { *out = new mkp_bedmethyl_file(read_bedmethyl_text(path)); return MKP_OK; });
+}
+extern "C" uint32_t mkp_bedmethyl_file_runs(const mkp_bedmethyl_file* f) { return f ? (uint32_t)f->runs.size() : 0u; }
+extern "C" const char* mkp_bedmethyl_file_chrom(const mkp_bedmethyl_file* f, uint32_t run) {
+  return f && run < f->runs.size() ? f->runs[run].chrom.c_str() : nullptr; }
+extern "C" int mkp_bedmethyl_file_rows(const mkp_bedmethyl_file* f, uint32_t run, mkp_rows* out) {
+  if (!f || !out || run >= f->runs.size()) return MKP_E_INVALID;
+  *out = f->rows_of(run); return MKP_OK;
+}
+extern "C" void mkp_bedmethyl_file_free(mkp_bedmethyl_file* f) { delete f; }
+
+// `mkpileup bedmethyl merge` (EntryMergeBedMethyl::run, src/bedmethyl_util/subcommands.rs:198-371): the inputs' contig runs are uploaded and
+// joined one after the other, the merged contigs come back in the order of the sizes file.  --mixed-delim and --header are parsed by the
+// reference and never used: they are not offered.
+extern "C" int mkp_bedmethyl_merge_main(int argc, const char* const* argv, uint64_t* n_written, uint64_t* n_dropped, char* errbuf, size_t errbuf_len) {
+  return guarded_buf(errbuf, errbuf_len, [&]() {
+    std::vector<std::string> inputs; std::string sizes_path, out_path; bool force = false, bgzf = false, stats = false; int device = 0;
+    for (int i = 0; i < argc; i++) {
+      const std::string s = argv[i];
+      auto val = [&]() { if (i + 1 >= argc) throw Error(MKP_E_INVALID, "missing value for " + s); return std::string(argv[++i]); };
+      if (s == "-g" || s == "--genome-sizes") sizes_path = val(); else if (s == "-o" || s == "--out-bed") out_path = val();
+      else if (s == "-f" || s == "--force") force = true; else if (s == "--bgzf") bgzf = true; else if (s == "--stats") stats = true;
+      else if (s == "--device") device = std::stoi(val());
+      else if (s == "-t" || s == "--threads" || s == "--io-threads" || s == "--chunk-size" || s == "--interval-size" || s == "--queue-size"
+          || s == "--log-filepath") val();   // (the reference's compute options: nothing here is sized by them)
+      else if (!s.empty() && s[0] == '-' && s != "-") throw Error(MKP_E_INVALID, "unexpected argument '" + s + "' for bedmethyl merge");
+      else inputs.push_back(s);
+    }
+    if (inputs.size() < 2) throw Error(MKP_E_INVALID, "usage: bedmethyl merge <a.bed> <b.bed> [..] -g <sizes.tsv> -o <out.bed> [--force] [--bgzf]");
+    if (sizes_path.empty()) throw Error(MKP_E_INVALID, "bedmethyl merge needs -g <sizes.tsv>");
+    if (out_path.empty()) throw Error(MKP_E_INVALID, "bedmethyl merge needs -o <out.bed>");
+    const bool to_stdout = out_path == "-" || out_path == "stdout";
+    if (bgzf && to_stdout) throw Error(MKP_E_INVALID, "--bgzf writes a file and its index: it needs an output path");
+    auto t_all = std::chrono::steady_clock::now();
+    const mkp_genome_sizes sizes = parse_genome_sizes(sizes_path);
+    std::vector<mkp_bedmethyl_file> files; for (auto& p : inputs) files.push_back(read_bedmethyl_text(p));
+    const double read_ms = ms_since(t_all);
+    // the output is opened before any device work, as the reference opens it (File::create_new without --force)
+    RowWriter wr;
+    if (to_stdout) wr.f = stdout;
+    else {
+      struct stat sb;
+      if (!force && stat(out_path.c_str(), &sb) == 0) throw Error(MKP_E_IO, "refusing to overwrite " + out_path + " without --force");
+      wr.f = fopen(out_path.c_str(), "w+");
+      if (!wr.f) throw Error(MKP_E_IO, "failed to make output file " + out_path);
+    }
+    struct CloseFile { FILE* f; ~CloseFile() { if (f && f != stdout) fclose(f); } } close_file{wr.f};
+    if (bgzf) { wr.bz.reset(new BgzfTabixSink()); wr.bz->f = wr.f; wr.bz->index_path = out_path + ".tbi"; }
+    mkp_config cfg; memset(&cfg, 0, sizeof(cfg)); cfg.device = device;
+    mkp_ctx* ctx = nullptr;
+    if (mkp_ctx_create(&cfg, &ctx) != MKP_OK) throw Error(MKP_E_DEVICE, "no usable gfx950 device (libmkpileup has no CPU path)");
+    struct OwnedCtx { mkp_ctx* c; ~OwnedCtx() { mkp_ctx_destroy(c); } } owned{ctx};
+    auto t_dev = std::chrono::steady_clock::now();
+    must(ctx, mkp_merge_begin(ctx, sizes.length.data(), (uint32_t)sizes.length.size()));
+    if (stats) must(ctx, mkp_internal_merge_timing(ctx, 1, nullptr));
+    std::map<std::string, int32_t> tid_of; for (size_t k = 0; k < sizes.name.size(); k++) tid_of.emplace(sizes.name[k], (int32_t)k);
+    for (const mkp_bedmethyl_file& f : files) for (size_t k = 0; k < f.runs.size(); k++) {
+      auto it = tid_of.find(f.runs[k].chrom); const mkp_rows rows = f.rows_of(k);
+      must(ctx, mkp_merge_add_rows(ctx, it == tid_of.end() ? -1 : it->second, &rows));
+    }
+    const double add_ms = ms_since(t_dev);
+    uint64_t dropped = 0;
+    auto t_out = std::chrono::steady_clock::now();
+    for (size_t tid = 0; tid < sizes.name.size(); tid++) {
+      mkp_rows rows; must(ctx, mkp_merge_get(ctx, (int32_t)tid, &rows, &dropped));
+      wr.write(sizes.name[tid], rows);
+    }
+    wr.finish();
+    if (dropped) fprintf(stderr, "[mkpileup] bedmethyl merge: %llu rows dropped (beyond their contig's length, or on a contig the sizes do not list)\n",
+        (unsigned long long)dropped);
+    if (stats) { double ms[2] = {0, 0}; mkp_internal_merge_timing(ctx, 0, ms);
+      fprintf(stderr, "[mkpileup] bedmethyl merge: %zu inputs, rows written=%llu dropped=%llu; read_ms=%.1f upload+join_ms=%.1f (kernels partition %.3f ms, tile + scan + compaction %.3f ms) d2h+write_ms=%.1f total_ms=%.1f\n",
+          inputs.size(), (unsigned long long)wr.n, (unsigned long long)dropped, read_ms, add_ms, ms[0], ms[1], ms_since(t_out), ms_since(t_all)); }
+    if (n_written) *n_written = wr.n;
+    if (n_dropped) *n_dropped = dropped;
+    return MKP_OK;
+  });
 }
 
 extern "C" int mkp_pileup_main(int argc, const char* const* argv, char* errbuf, size_t errbuf_len) {

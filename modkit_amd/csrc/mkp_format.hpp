@@ -27,6 +27,9 @@ inline char* put_u32(char* p, uint32_t v) {
 // formatting and glibc's printf agree on this).  pct has a 24-bit significand, so pct * 100 is exact in double and
 // nearbyint (round-to-nearest-even) of it is the correctly rounded number of hundredths.
 inline char* put_pct2(char* p, float pct) {
+  // a row without valid coverage (only `bedmethyl merge` can hold one): 0 / 0, or n / 0 — Rust prints `NaN` and `inf`
+  if (pct != pct) { memcpy(p, "NaN", 3); return p + 3; }
+  if (std::isinf(pct)) { memcpy(p, "inf", 3); return p + 3; }
   const double x = (double)pct * 100.0;
   const uint64_t h = (uint64_t)std::nearbyint(x);
   p = put_u32(p, (uint32_t)(h / 100u));
