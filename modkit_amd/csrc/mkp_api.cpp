@@ -1,7 +1,7 @@
-// libmkpileup C ABI (include/mkpileup.h): context, shard residency in HBM, kernel launches,
-// row read-back.  No CPU fallback lives here: the only way rows are produced is the three HIP
-// kernels of mkp_kernels.hip; without a gfx950 device every compute entry point fails with
-// MKP_E_DEVICE.
+// libmkpileup C ABI (include/mkpileup.h): the context, a shard's plan and residency in HBM (make_resident), the pileup pass over it
+// (run_kernels) and its row read-back, BGZF inflate, threshold sampling / summary / extract, region statistics, localize and bedmethyl
+// merge.  Every kernel is reached through a launcher of mkp_launch.h.  No CPU fallback lives here: rows and counts come from the HIP
+// kernels only; without a gfx950 device every compute entry point fails with MKP_E_DEVICE.
 #include <atomic>
 #include <climits>
 #include <memory>
@@ -9,47 +9,22 @@
 
 #include "mkp_ctx.hpp"
 #include "mkp_ingest_host.hpp"
+#include "mkp_launch.h"
 #include "mkp_plan.hpp"
 
 using namespace mkp;
 
-extern "C" {
-hipError_t mkp_launch_decode(hipStream_t, const MkpReadHdr*, const uint32_t* /*read ids by class*/, const uint32_t* /*n_class[7]*/, const uint32_t*,
-    const uint8_t*,
-    const MkpTagRef*, const uint32_t*,
-                             const uint8_t*, const MkpLayout*, const MkpRunParams*, MkpEvent*, MkpReadOut*, uint32_t*, const uint8_t*, float*);
-hipError_t mkp_pileup_set_lds(uint32_t accum_bytes);
-hipError_t mkp_launch_pileup(hipStream_t, uint32_t /*LDS bytes*/, bool /*pileup-hemi*/, const MkpReadHdr*, const uint32_t*, const uint8_t*,
-    const MkpEvent*,
-    const MkpReadOut*, const MkpTile*, uint32_t,
-                             const MkpRunParams* /*device*/, const uint32_t* /*slot bitmap (pileup-hemi)*/,
-                                 const MkpRowsDev*, uint32_t* /*row cursor*/,
-                             uint32_t* /*tile row offsets*/, uint32_t* /*tile row counts*/, const uint32_t* /*chunk offsets*/,
-                                 uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, bool /*wide tallies*/);
-hipError_t mkp_launch_slots(hipStream_t, const MkpWork* /*fused reads*/, uint32_t, const MkpCallEnt* /*call plane*/, const MkpBaseEnt* /*base plane*/,
-    const uint16_t* /*16-bit CIGAR*/, const MkpReadHdr*, const uint32_t* /*cover read ids*/, uint32_t, const uint32_t* /*CIGAR*/,
-    const uint8_t* /*SEQ*/, const uint8_t* /*ML*/, const MkpFusedDesc*, const MkpRunParams*, const uint32_t* /*slot positions*/,
-    const MkpSlotEnt* /*slot-entry lists*/, uint8_t* /*feature stream*/, MkpVisit*, MkpEvent*, MkpReadOut*);
-hipError_t mkp_launch_call_plane(hipStream_t, MkpWork*, uint32_t, const uint8_t* /*SEQ*/, const uint32_t* /*ranks*/, const MkpFusedDesc*,
-    MkpCallEnt* /*call plane*/, MkpBaseEnt* /*base plane*/, unsigned long long* /*SEQ bytes the decoder reads of MKP_RF_SEQN reads*/);
-hipError_t mkp_stream_set_lds(uint32_t bytes);
-hipError_t mkp_launch_dup_restore(hipStream_t, MkpReadHdr*, const MkpDupCons*, uint32_t);
-hipError_t mkp_launch_dup_events(hipStream_t, MkpReadHdr*, const uint32_t*, const uint8_t*, MkpEvent*, MkpReadOut*, MkpDupCons*, const MkpDupSeg*,
-    uint32_t, uint32_t* /*error bits*/);
-hipError_t mkp_launch_stream(hipStream_t, uint32_t /*LDS bytes*/, const MkpVisit*, const uint8_t*, const MkpEvent*, const MkpSTile*, uint32_t,
-    const MkpRunParams* /*device*/, const uint32_t* /*slot positions*/,
-                             const uint8_t* /*focus bytes*/, const MkpCombo*, const MkpRowsDev*, uint32_t* /*row cursor*/,
-                                 uint32_t* /*look-back words*/, uint32_t* /*error bits*/, uint32_t /*key filter*/, uint32_t /*key pass*/, uint32_t /*motif combos*/,
-                                 uint32_t /*row runs of the launch sequence*/,
-                             uint32_t /*slot capacity of a tile*/, uint32_t /*tally words per slot*/, bool /*wide tallies*/);
-hipError_t mkp_launch_gather(hipStream_t, const uint32_t*, const uint32_t*, uint32_t*, uint32_t, uint32_t*, const MkpRowsDev*, const MkpRowsDev*);
-hipError_t mkp_launch_hemi_failed(hipStream_t, const MkpReadHdr*, const uint32_t*, const uint8_t*, MkpEvent*, MkpReadOut*, uint32_t,
-    const uint32_t* /*slot bitmap*/,
-    const uint32_t* /*interval starts*/,
-                                  uint32_t, int32_t, int32_t, uint32_t* /*error bits*/);
-}
-
 namespace {
+
+// the packed shard's arrays in HBM as the launchers take them: the one place these buffers are cast (built once per pass)
+MkpShardArrays shard_arrays(const mkp_ctx* c) {
+  MkpShardArrays sh;
+  sh.hdr = c->d_hdr.as<MkpReadHdr>(); sh.cigar = c->d_cigar.as<uint32_t>(); sh.cigar16 = c->d_cigar16.as<uint16_t>();
+  sh.chunk_pfx = c->d_chunk.as<uint32_t>(); sh.seq = c->d_seq.as<uint8_t>(); sh.tagref = c->d_tagref.as<MkpTagRef>();
+  sh.ranks = c->d_ranks.as<uint32_t>(); sh.ml = c->d_ml.as<uint8_t>(); sh.layouts = c->d_layouts.as<MkpLayout>();
+  sh.events = c->d_events.as<MkpEvent>(); sh.readout = c->d_readout.as<MkpReadOut>();
+  return sh;
+}
 
 MkpRowsDev carve_rows(DevBuf& b, uint64_t cap) {
   b.ensure(cap * 44 + 64);
@@ -64,21 +39,18 @@ template <class V> void upload(DevBuf& b, const V& v) {
   b.ensure(std::max<size_t>(bytes, 16));
   if (!v.empty()) h2d_copy(b.p, v.data(), bytes);   // (through the library's page-locked staging: mkp_ctx.hpp)
 }
+}  // namespace
 
 // BGZF inflate on the device: mkp_inflate_wave4, one wave per block — speculative token decode, a scalar walk that only marks the chain,
 // all output of a pass placed at once; 4 KiB ring, sixteen waves per CU (round 5; it replaced the five kernels of rounds 2-4 at every
 // launch size).  MKP_INFLATE_KERNEL=wave4_8k|wave4_2k picks another ring size (A/B runs; --stats names it).
-}  // namespace
-extern "C" hipError_t mkp_launch_inflate_wave4(hipStream_t, const uint8_t*, const void* /*MkpBgzfBlock[]*/, uint32_t, uint8_t*, uint32_t*, int);
-hipError_t mkp_launch_inflate_auto(hipStream_t st, const uint8_t* in, const void* blks, uint32_t n, uint8_t* out, uint32_t* status) {
+hipError_t mkp_launch_inflate_auto(hipStream_t st, const uint8_t* in, const MkpBgzfBlock* blks, uint32_t n, uint8_t* out, uint32_t* status) {
   static const char* force = getenv("MKP_INFLATE_KERNEL");
   if (force && !strcmp(force, "wave4_8k")) return mkp_launch_inflate_wave4(st, in, blks, n, out, status, 8);
   if (force && !strcmp(force, "wave4_2k")) return mkp_launch_inflate_wave4(st, in, blks, n, out, status, 2);
   return mkp_launch_inflate_wave4(st, in, blks, n, out, status, 4);
 }
 namespace {
-hipError_t launch_inflate(hipStream_t st, const uint8_t* in, const void* blks, uint32_t n, uint8_t* out, uint32_t* status) {
-  return mkp_launch_inflate_auto(st, in, blks, n, out, status); }
 
 // d_plane holds the fused reads' call plane, the base plane behind it (as many 8-byte entries each: plane_bytes / 16) and the builder's counter
 static MkpCallEnt* call_plane(mkp_ctx* c) { return c->d_plane.as<MkpCallEnt>(); }
@@ -117,8 +89,8 @@ void upload_plan(mkp_ctx* c, const ShardPlan& pl, PlanTrace& trace) {
     { std::vector<uint32_t> cover(pl.slot_ids.begin() + nf, pl.slot_ids.end()); upload(c->d_slot_ids, cover); }
     { std::vector<MkpFusedDesc> fd(c->tables.dev.size()); for (size_t i = 0; i < fd.size(); i++) fd[i] = fused_desc(c->tables.dev[i]);
       upload(c->d_fdesc, fd); }
-    hip_check(mkp_launch_call_plane(c->stream, c->d_work.as<MkpWork>(), nf, c->d_seq.as<uint8_t>(), c->d_ranks.as<uint32_t>(),
-        c->d_fdesc.as<MkpFusedDesc>(), call_plane(c), base_plane(c), d_seqn_bytes), "call plane launch");
+    hip_check(mkp_launch_call_plane(c->stream, c->d_work.as<MkpWork>(), nf, shard_arrays(c), c->d_fdesc.as<MkpFusedDesc>(), call_plane(c),
+        base_plane(c), d_seqn_bytes), "call plane launch");
     c->d_cov.ensure(c->cov_bytes + 256); c->d_visits.ensure(std::max<size_t>(S.hdr.size(), 1) * sizeof(MkpVisit));
     // A fused read writes the bytes of the slots it decodes — the same ones on every pass — and the buffer is reused from shard to shard:
     // the whole stream starts as BLANK ("in the column, no feature": the stream kernel skips it and it opens no ref-skip boundary), so that
@@ -195,7 +167,7 @@ void make_resident(mkp_ctx* c) {
   plan_name_owners(in, pl, [c](uint32_t r) {   // the one device touch of planning: a member's CIGAR of a device-packed shard
     const MkpReadHdr& h = c->shard.hdr[r]; std::vector<uint32_t> cg(h.n_cigar);
     if (h.n_cigar) { hip_check(hipSetDevice(c->device), "hipSetDevice");
-      d2h_copy(cg.data(), c->d_cigar.as<uint32_t>() + h.cigar_off, (size_t)h.n_cigar * 4, c->stream); }
+      d2h_copy(cg.data(), shard_arrays(c).cigar + h.cigar_off, (size_t)h.n_cigar * 4, c->stream); }
     return cg; });
   if (!pl.dup_groups.empty()) trace.lap("records sharing a name: owners per interval");
   split_fused_and_cover(in, pl);
@@ -217,113 +189,148 @@ void make_resident(mkp_ctx* c) {
   account_bytes(c, pl);
 }
 
+// ---- one pileup pass over the resident shard: the stages of run_kernels, in the order they run.  `words` are the pass words in HBM
+// (mkp_launch.h) with the runs' look-back words (slot pipeline) or row offsets (tile pipeline) behind them; `sh` the shard's arrays.
+
+// the first guess of the row capacity (a pass that outgrows it is run again with twice as much)
+uint64_t first_row_capacity(const mkp_ctx* c) {
+  const MkpRunParams& P = c->prm;
+  // focus runs: usually one strand rule per focus position and one row per observed code; otherwise two strands per position
+  uint64_t guess = c->hemi ? c->n_slots_total * 3 + 4096 : c->has_focus ? c->n_slots_total * std::max<uint32_t>(1u,
+      P.numeric_mode == 1 ? P.n_pb : P.n_slots) + 4096 : (uint64_t)c->stats.n_positions * 2 + 1024;
+  return std::max<uint64_t>(1u << 16, std::min<uint64_t>(guess * c->key_passes.size(), 1ull << 28));
+}
+
+// the buffers with one entry per row run
+void size_run_buffers(mkp_ctx* c, uint32_t n_runs) {
+  // (slot pipeline: row_off holds the runs' 64-bit look-back words behind a 64-byte header — the pass's cursor / total / error words — so that
+  //  ONE memset readies a pass: between two kernels of a 1 ms step every extra fill or copy is a 5-10 us launch of its own)
+  c->d_tile_row_off.ensure(MKP_PW_HEADER_BYTES + (size_t)(n_runs + 1) * 8); c->d_tile_row_cnt.ensure((size_t)(n_runs + 1) * 4);
+    c->d_tile_dst.ensure((size_t)(n_runs + 1) * 4);
+}
+
+// the row buffers at the capacity of this try
+void size_row_buffers(mkp_ctx* c) {
+  c->prm.row_capacity = (uint32_t)c->row_cap;
+  c->rows_src = carve_rows(c->d_rows_src, c->row_cap); c->rows_dst = carve_rows(c->d_rows_dst, c->row_cap);
+}
+
+// ready a pass: the one memset, and the parameter block when it changed
+void ready_pass(mkp_ctx* c, uint32_t* words, uint32_t n_runs) {
+  const MkpRunParams& P = c->prm;
+  // rows leave mkp_pileup_stream in genome order (look-back over the runs): the words start at zero, the number of runs is a kernel argument
+  hip_check(hipMemsetAsync(words, 0, c->slot_mode ? MKP_PW_HEADER_BYTES + (size_t)(n_runs + 1) * 8 : MKP_PW_HEADER_BYTES, c->stream), "memset");
+  c->d_prm.ensure(sizeof(MkpRunParams));
+  // (re-launches on a resident shard: unchanged)
+  if (c->prm_uploaded.size() != sizeof(MkpRunParams) || c->prm_uploaded_to != c->d_prm.p
+      || memcmp(c->prm_uploaded.data(), &P, sizeof(MkpRunParams)) != 0) {
+    c->prm_uploaded.assign(reinterpret_cast<const uint8_t*>(&P), reinterpret_cast<const uint8_t*>(&P) + sizeof(MkpRunParams));
+      c->prm_uploaded_to = c->d_prm.p;
+    hip_check(hipMemcpyAsync(c->d_prm.p, c->prm_uploaded.data(), sizeof(MkpRunParams), hipMemcpyHostToDevice, c->stream), "params H2D");
+  }
+}
+
+// the decoders: events and read summaries of every read (both pipelines), the feature stream and visits of the slot pipeline
+void launch_decoders(mkp_ctx* c, const MkpShardArrays& sh, uint32_t* words) {
+  const MkpRunParams& P = c->prm;
+  uint32_t* dev_err = words + MKP_PW_ERR;
+  if (c->n_dup_cons) hip_check(mkp_launch_dup_restore(c->stream, sh, c->d_dupcons.as<MkpDupCons>(), c->n_dup_cons), "dup restore launch");
+  hip_check(mkp_launch_decode(c->stream, sh, c->d_read_ids.as<uint32_t>() + c->read_ids_dec_off, c->n_class, &P, dev_err,
+      c->d_focus.as<uint8_t>(), nullptr), "decode launch");
+  if (c->hemi) hip_check(mkp_launch_hemi_failed(c->stream, sh, (uint32_t)c->shard.hdr.size(), c->d_slotbm.as<uint32_t>(),
+      c->d_hemi_iv.as<uint32_t>(), (uint32_t)c->hemi_iv.size(), P.win_start, P.win_end, dev_err), "hemi failed-reads launch");
+  // records answered from another record of their name: their event lists are rebuilt from the owners' (behind every event decoder, in front of
+  // whatever consumes events: mkp_cover_reads / mkp_pileup_tiles)
+  if (c->n_dup_cons) hip_check(mkp_launch_dup_events(c->stream, sh, c->d_dupcons.as<MkpDupCons>(), c->d_dupsegs.as<MkpDupSeg>(), c->n_dup_cons,
+      dev_err), "dup events launch");
+  if (c->slot_mode) hip_check(mkp_launch_slots(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], call_plane(c), base_plane(c), sh,
+      c->d_slot_ids.as<uint32_t>(), c->n_slot_class[2], c->d_fdesc.as<MkpFusedDesc>(), &P, c->d_slot_pos.as<uint32_t>(),
+      c->d_slot_ent.as<MkpSlotEnt>(), c->d_cov.as<uint8_t>(), c->d_visits.as<MkpVisit>()), "slot decode launch");
+}
+
+// the accumulate passes: one per partition key present (a single unfiltered pass without --partition-tag)
+void launch_accumulate(mkp_ctx* c, const MkpShardArrays& sh, uint32_t* words, uint32_t n_runs) {
+  const MkpRunParams& P = c->prm;
+  uint32_t* row_off = words + MKP_PW_RUNS;
+  for (uint32_t kp = 0; kp < c->key_passes.size(); kp++)
+    if (c->slot_mode) hip_check(mkp_launch_stream(c->stream, c->lds_bytes, c->d_visits.as<MkpVisit>(), c->d_cov.as<uint8_t>(), sh.events,
+        c->d_stiles.as<MkpSTile>(), c->n_tiles, c->d_prm.as<MkpRunParams>(), c->d_slot_pos.as<uint32_t>(), c->d_focus.as<uint8_t>(),
+        c->d_combos.as<MkpCombo>(), &c->rows_src, words + MKP_PW_CURSOR, row_off, words + MKP_PW_ERR, c->key_passes[kp], kp,
+        (uint32_t)c->combos.size(), n_runs, P.slot_cap, (P.n_counters + P.n_slots) * (c->wide ? 2u : 1u), c->wide), "stream pileup launch");
+    else hip_check(mkp_launch_pileup(c->stream, c->lds_bytes, c->hemi, sh, c->d_tiles.as<MkpTile>(), c->n_tiles, c->d_prm.as<MkpRunParams>(),
+        c->d_slotbm.as<uint32_t>(), &c->rows_src, words + MKP_PW_CURSOR, row_off, c->d_tile_row_cnt.as<uint32_t>(), words + MKP_PW_ERR,
+        c->key_passes[kp], kp, c->wide), "pileup launch");
+}
+
+// the gather: the tiles' row runs into genome order (tile pipeline only)
+void launch_gather(mkp_ctx* c, uint32_t* words, uint32_t n_runs) {
+  if (c->slot_mode) c->rows_dst = c->rows_src;   // already in genome order
+  else hip_check(mkp_launch_gather(c->stream, words + MKP_PW_RUNS, c->d_tile_row_cnt.as<uint32_t>(), c->d_tile_dst.as<uint32_t>(), n_runs,
+      words + MKP_PW_ROW_TOTAL, &c->rows_src, &c->rows_dst), "gather launch");
+}
+
+// the pass words, back on the host behind everything the pass enqueued
+const uint32_t* read_pass_words(mkp_ctx* c, const uint32_t* words) {
+  if (!c->h_words && hipHostMalloc(reinterpret_cast<void**>(&c->h_words), 64, hipHostMallocDefault) != hipSuccess) { c->h_words = nullptr;
+    throw Error(MKP_E_NOMEM, "hipHostMalloc failed"); }
+  hip_check(hipMemcpyAsync(c->h_words, words, 16, hipMemcpyDeviceToHost, c->stream), "D2H");
+  hip_check(hipStreamSynchronize(c->stream), "kernel sync");
+  return c->h_words;
+}
+
+// what the error word says of the pass: true = it stands; false = the rows outgrew their buffers, which are doubled for another try; every
+// other error refuses the shard
+bool pass_stands(mkp_ctx* c, uint32_t err) {
+  if (err & ERR_ROW_CAP) { c->row_cap *= 2; if (c->row_cap > (1ull << 31)) throw Error(MKP_E_NOMEM, "row buffer would exceed 2^31 rows");
+    return false; }
+  if (err & ERR_EVENT_CAP) throw Error(MKP_E_DEVICE, "internal: event segment overflow");
+  if (err & ERR_DUP_MIXED) throw Error(MKP_E_UNSUPPORTED,
+      "records sharing a read name inside one interval are answered from the first one's calls (the reference's per-interval cache is keyed by name); here the records one of them is answered from in different intervals disagree in status or observed mod codes, which is not reproduced on the device");
+  return true;
+}
+
+// the kernel times of a timed pass, from its events
+void record_kernel_times(mkp_ctx* c) {
+  float a = 0, b = 0, d = 0; hip_check(hipEventElapsedTime(&a, c->ev[0], c->ev[1]), "event");
+    hip_check(hipEventElapsedTime(&b, c->ev[1], c->ev[2]), "event");
+  if (!c->slot_mode) hip_check(hipEventElapsedTime(&d, c->ev[2], c->ev[3]), "event");   // (the slot pipeline has no gather pass)
+  c->stats.decode_kernel_ms = a; c->stats.pileup_kernel_ms = b; c->stats.rows_kernel_ms = 0; c->stats.gather_kernel_ms = d;
+    c->stats.kernel_ms = a + b + d;
+}
+
+// the pileup pass over the resident shard, tried again with twice the rows while they outgrow their buffers
 void run_kernels(mkp_ctx* c, bool time_kernels) {
-  MkpRunParams& P = c->prm;
   // focus runs are the slot pipeline's; the tile kernels of the event pipeline serve runs without focus positions and pileup-hemi only
   if (c->has_focus && !c->hemi && !c->slot_mode) throw Error(MKP_E_INVALID, "internal: a focus run outside the slot pipeline");
-  if (c->row_cap == 0) {
-    // focus runs: usually one strand rule per focus position and one row per observed code; otherwise two strands per position
-    uint64_t guess = c->hemi ? c->n_slots_total * 3 + 4096 : c->has_focus ? c->n_slots_total * std::max<uint32_t>(1u,
-        P.numeric_mode == 1 ? P.n_pb : P.n_slots) + 4096 : (uint64_t)c->stats.n_positions * 2 + 1024;
-    c->row_cap = std::max<uint64_t>(1u << 16, std::min<uint64_t>(guess * c->key_passes.size(), 1ull << 28));
-  }
+  if (c->row_cap == 0) c->row_cap = first_row_capacity(c);
   const bool trace = time_kernels && getenv("MKP_TRACE_PLAN") != nullptr;
   PlanTrace marks(trace, true);
   const uint32_t n_runs = c->n_tiles * (uint32_t)c->key_passes.size();   // row runs: one per (key pass, tile), ordered by key then genome
-  // (slot pipeline: row_off holds the runs' 64-bit look-back words behind a 64-byte header — the pass's cursor / total / error words — so that
-  //  ONE memset readies a pass: between two kernels of a 1 ms step every extra fill or copy is a 5-10 us launch of its own)
-  c->d_tile_row_off.ensure(64 + (size_t)(n_runs + 1) * 8); c->d_tile_row_cnt.ensure((size_t)(n_runs + 1) * 4);
-    c->d_tile_dst.ensure((size_t)(n_runs + 1) * 4);
+  size_run_buffers(c, n_runs);
+  const MkpShardArrays sh = shard_arrays(c);
+  uint32_t* words = c->d_tile_row_off.as<uint32_t>();
+  auto mark = [&](int k) { if (time_kernels) hip_check(hipEventRecord(c->ev[k], c->stream), "event"); };
   for (;;) {
-    P.row_capacity = (uint32_t)c->row_cap;
-    c->rows_src = carve_rows(c->d_rows_src, c->row_cap); c->rows_dst = carve_rows(c->d_rows_dst, c->row_cap);
+    size_row_buffers(c);
     marks.lap("row buffers");
     // (trace runs: what the stream still had queued shows up here, not in the kernels' sync)
     if (trace) { hip_check(hipStreamSynchronize(c->stream), "sync"); marks.lap("stream drained"); }
-    // [0] row cursor / tile ticket, [1] total rows, [2] error bits; the look-back words (slot pipeline) or row offsets start at +16 dwords
-    uint32_t* misc = c->d_tile_row_off.as<uint32_t>();
-    uint32_t* row_off = misc + 16;
-    // rows leave mkp_pileup_stream in genome order (look-back over the runs): the words start at zero, the number of runs is a kernel argument
-    hip_check(hipMemsetAsync(misc, 0, c->slot_mode ? 64 + (size_t)(n_runs + 1) * 8 : 64, c->stream), "memset");
-    c->d_prm.ensure(sizeof(MkpRunParams));
-    // (re-launches on a resident shard: unchanged)
-    if (c->prm_uploaded.size() != sizeof(MkpRunParams) || c->prm_uploaded_to != c->d_prm.p
-        || memcmp(c->prm_uploaded.data(), &P, sizeof(MkpRunParams)) != 0) {
-      c->prm_uploaded.assign(reinterpret_cast<const uint8_t*>(&P), reinterpret_cast<const uint8_t*>(&P) + sizeof(MkpRunParams));
-        c->prm_uploaded_to = c->d_prm.p;
-      hip_check(hipMemcpyAsync(c->d_prm.p, c->prm_uploaded.data(), sizeof(MkpRunParams), hipMemcpyHostToDevice, c->stream), "params H2D");
-    }
-    if (time_kernels) hip_check(hipEventRecord(c->ev[0], c->stream), "event");
-    if (c->n_dup_cons) hip_check(mkp_launch_dup_restore(c->stream, c->d_hdr.as<MkpReadHdr>(), c->d_dupcons.as<MkpDupCons>(), c->n_dup_cons),
-        "dup restore launch");
-    hip_check(mkp_launch_decode(c->stream, c->d_hdr.as<MkpReadHdr>(), c->d_read_ids.as<uint32_t>() + c->read_ids_dec_off, c->n_class,
-        c->d_cigar.as<uint32_t>(),
-        c->d_seq.as<uint8_t>(), c->d_tagref.as<MkpTagRef>(),
-                                c->d_ranks.as<uint32_t>(), c->d_ml.as<uint8_t>(), c->d_layouts.as<MkpLayout>(), &P, c->d_events.as<MkpEvent>(),
-                                    c->d_readout.as<MkpReadOut>(), misc + 2, c->d_focus.as<uint8_t>(), nullptr), "decode launch");
-    if (c->hemi) hip_check(mkp_launch_hemi_failed(c->stream, c->d_hdr.as<MkpReadHdr>(), c->d_cigar.as<uint32_t>(), c->d_seq.as<uint8_t>(),
-        c->d_events.as<MkpEvent>(),
-        c->d_readout.as<MkpReadOut>(),
-                                                  (uint32_t)c->shard.hdr.size(), c->d_slotbm.as<uint32_t>(), c->d_hemi_iv.as<uint32_t>(),
-                                                      (uint32_t)c->hemi_iv.size(), P.win_start, P.win_end, misc + 2), "hemi failed-reads launch");
-    // records answered from another record of their name: their event lists are rebuilt from the owners' (behind every event decoder, in front of
-    // whatever consumes events: mkp_cover_reads / mkp_pileup_tiles)
-    if (c->n_dup_cons) hip_check(mkp_launch_dup_events(c->stream, c->d_hdr.as<MkpReadHdr>(), c->d_cigar.as<uint32_t>(), c->d_seq.as<uint8_t>(),
-        c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>(),
-                                                       c->d_dupcons.as<MkpDupCons>(), c->d_dupsegs.as<MkpDupSeg>(), c->n_dup_cons, misc + 2),
-                                                           "dup events launch");
-    if (c->slot_mode) hip_check(mkp_launch_slots(c->stream, c->d_work.as<MkpWork>(), c->n_slot_class[0], call_plane(c), base_plane(c),
-        c->d_cigar16.as<uint16_t>(), c->d_hdr.as<MkpReadHdr>(),
-        c->d_slot_ids.as<uint32_t>(), c->n_slot_class[2],
-                                              c->d_cigar.as<uint32_t>(), c->d_seq.as<uint8_t>(), c->d_ml.as<uint8_t>(),
-                                                  c->d_fdesc.as<MkpFusedDesc>(), &P, c->d_slot_pos.as<uint32_t>(), c->d_slot_ent.as<MkpSlotEnt>(),
-                                                  c->d_cov.as<uint8_t>(),
-                                                  c->d_visits.as<MkpVisit>(),
-                                              c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>()), "slot decode launch");
-    if (time_kernels) hip_check(hipEventRecord(c->ev[1], c->stream), "event");
-    for (uint32_t kp = 0; kp < c->key_passes.size(); kp++)   // one pass per partition key present (a single unfiltered pass without --partition-tag)
-      if (c->slot_mode) hip_check(mkp_launch_stream(c->stream, c->lds_bytes, c->d_visits.as<MkpVisit>(), c->d_cov.as<uint8_t>(),
-          c->d_events.as<MkpEvent>(),
-          c->d_stiles.as<MkpSTile>(), c->n_tiles, c->d_prm.as<MkpRunParams>(),
-                                                 c->d_slot_pos.as<uint32_t>(), c->d_focus.as<uint8_t>(), c->d_combos.as<MkpCombo>(), &c->rows_src,
-                                                     misc, row_off, misc + 2,
-                                                 c->key_passes[kp], kp, (uint32_t)c->combos.size(), n_runs, P.slot_cap,
-                                                     (P.n_counters + P.n_slots) * (c->wide ? 2u : 1u), c->wide),
-                                                     "stream pileup launch");
-      else hip_check(mkp_launch_pileup(c->stream, c->lds_bytes, c->hemi, c->d_hdr.as<MkpReadHdr>(),
-          c->d_cigar.as<uint32_t>(),
-          c->d_seq.as<uint8_t>(), c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>(),
-                                  c->d_tiles.as<MkpTile>(), c->n_tiles, c->d_prm.as<MkpRunParams>(), c->d_slotbm.as<uint32_t>(),
-                                      &c->rows_src, misc,
-                                  row_off, c->d_tile_row_cnt.as<uint32_t>(), c->d_chunk.as<uint32_t>(), misc + 2, c->key_passes[kp], kp,
-                                      c->wide),
-                                      "pileup launch");
-    if (time_kernels) hip_check(hipEventRecord(c->ev[2], c->stream), "event");
-    if (c->slot_mode) c->rows_dst = c->rows_src;   // already in genome order
-    else hip_check(mkp_launch_gather(c->stream, row_off, c->d_tile_row_cnt.as<uint32_t>(), c->d_tile_dst.as<uint32_t>(), n_runs, misc + 1,
-        &c->rows_src, &c->rows_dst), "gather launch");
-    if (time_kernels && !c->slot_mode) hip_check(hipEventRecord(c->ev[3], c->stream), "event");
+    ready_pass(c, words, n_runs);
+    mark(0);
+    launch_decoders(c, sh, words);
+    mark(1);
+    launch_accumulate(c, sh, words, n_runs);
+    mark(2);
+    launch_gather(c, words, n_runs);
+    if (!c->slot_mode) mark(3);
     marks.lap("launches");
     if (trace && time_kernels) { hip_check(hipEventSynchronize(c->ev[0]), "sync"); marks.lap("first event reached");
       hip_check(hipEventSynchronize(c->ev[2]), "sync"); marks.lap("kernels done (event)"); }
-    if (!c->h_words && hipHostMalloc(reinterpret_cast<void**>(&c->h_words), 64, hipHostMallocDefault) != hipSuccess) { c->h_words = nullptr;
-      throw Error(MKP_E_NOMEM, "hipHostMalloc failed"); }
-    uint32_t* h = c->h_words;
-    hip_check(hipMemcpyAsync(h, misc, 16, hipMemcpyDeviceToHost, c->stream), "D2H");
-    hip_check(hipStreamSynchronize(c->stream), "kernel sync");
+    const uint32_t* h = read_pass_words(c, words);
     marks.lap("sync");
-    if (h[2] & 2u) { c->row_cap *= 2; if (c->row_cap > (1ull << 31)) throw Error(MKP_E_NOMEM, "row buffer would exceed 2^31 rows"); continue; }
-    if (h[2] & 1u) throw Error(MKP_E_DEVICE, "internal: event segment overflow");
-    if (h[2] & ERR_DUP_MIXED) throw Error(MKP_E_UNSUPPORTED,
-        "records sharing a read name inside one interval are answered from the first one's calls (the reference's per-interval cache is keyed by name); here the records one of them is answered from in different intervals disagree in status or observed mod codes, which is not reproduced on the device");
-    c->stats.n_rows = h[1];
-    if (time_kernels) {
-      float a = 0, b = 0, d = 0; hip_check(hipEventElapsedTime(&a, c->ev[0], c->ev[1]), "event");
-        hip_check(hipEventElapsedTime(&b, c->ev[1], c->ev[2]), "event");
-      if (!c->slot_mode) hip_check(hipEventElapsedTime(&d, c->ev[2], c->ev[3]), "event");   // (the slot pipeline has no gather pass)
-      c->stats.decode_kernel_ms = a; c->stats.pileup_kernel_ms = b; c->stats.rows_kernel_ms = 0; c->stats.gather_kernel_ms = d;
-        c->stats.kernel_ms = a + b + d;
-    }
+    if (!pass_stands(c, h[MKP_PW_ERR])) continue;
+    c->stats.n_rows = h[MKP_PW_ROW_TOTAL];
+    if (time_kernels) record_kernel_times(c);
     return;
   }
 }
@@ -822,8 +829,7 @@ int mkp_percentile(const float* xs, uint64_t n, float q, float* out) {  // perce
 int mkp_bgzf_inflate(mkp_ctx* c, const uint8_t* bgzf, uint64_t n_bytes, const uint8_t** out, uint64_t* out_len, double* kernel_ms) {
   if (!c || (!bgzf && n_bytes) || !out || !out_len) return MKP_E_INVALID;
   return guarded(c, [&]() {
-    struct Blk { unsigned long long in_off, out_off; uint32_t in_len, out_len; };   // == MkpBgzfBlock (mkp_inflate_wave4.hip)
-    std::vector<Blk> blks; std::vector<uint32_t> crcs; uint64_t o = 0, total = 0;
+    std::vector<MkpBgzfBlock> blks; std::vector<uint32_t> crcs; uint64_t o = 0, total = 0;
     while (o < n_bytes) {   // header walk, as in load_bam (mkp_bam.hpp): gzip magic, FEXTRA with a BC subfield holding BSIZE
       if (o + 18 > n_bytes || bgzf[o] != 31 || bgzf[o + 1] != 139 || bgzf[o + 2] != 8 || !(bgzf[o + 3] & 4)) throw Error(MKP_E_IO, "not BGZF");
       uint16_t xlen; memcpy(&xlen, bgzf + o + 10, 2);
@@ -841,15 +847,14 @@ int mkp_bgzf_inflate(mkp_ctx* c, const uint8_t* bgzf, uint64_t n_bytes, const ui
     if (blks.size() > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "too many BGZF blocks");
     hip_check(hipSetDevice(c->device), "hipSetDevice");
     c->d_zin.ensure(std::max<uint64_t>(n_bytes, 16)); c->d_zout.ensure(std::max<uint64_t>(total, 16));
-      c->d_zblk.ensure(std::max<size_t>(blks.size(), 1) * sizeof(Blk));
+      c->d_zblk.ensure(std::max<size_t>(blks.size(), 1) * sizeof(MkpBgzfBlock));
         c->d_zstat.ensure(std::max<size_t>(blks.size(), 1) * 4);
     h2d_copy(c->d_zin.p, bgzf, n_bytes);   // (caller memory and a temporary: through the library's page-locked staging, mkp_ctx.hpp)
-    h2d_copy(c->d_zblk.p, blks.data(), blks.size() * sizeof(Blk));
+    h2d_copy(c->d_zblk.p, blks.data(), blks.size() * sizeof(MkpBgzfBlock));
     hip_check(hipMemsetAsync(c->d_zstat.p, 0xff, std::max<size_t>(blks.size(), 1) * 4, c->stream), "memset");
     hip_check(hipEventRecord(c->ev[0], c->stream), "event");
-    hip_check(launch_inflate(c->stream, c->d_zin.as<uint8_t>(), c->d_zblk.p, (uint32_t)blks.size(), c->d_zout.as<uint8_t>(),
-        c->d_zstat.as<uint32_t>()),
-        "inflate launch");
+    hip_check(mkp_launch_inflate_auto(c->stream, c->d_zin.as<uint8_t>(), c->d_zblk.as<MkpBgzfBlock>(), (uint32_t)blks.size(),
+        c->d_zout.as<uint8_t>(), c->d_zstat.as<uint32_t>()), "inflate launch");
     hip_check(hipEventRecord(c->ev[1], c->stream), "event");
     std::vector<uint32_t> st(blks.size());
     c->h_inflated.resize(total);
@@ -910,7 +915,8 @@ bool mkp_internal_device_inflate(void* user, const InflateJob& j) {
     ok(hipMemcpyAsync(d->zin.p, pin, j.comp_len, hipMemcpyHostToDevice, d->stream));
     ok(hipMemcpyAsync(d->zblk.p, pin + j.comp_len, j.n_blks * sizeof(InflateBlk), hipMemcpyHostToDevice, d->stream));
     ok(hipMemsetAsync(d->zstat.p, 0xff, j.n_blks * 4, d->stream));
-    ok(launch_inflate(d->stream, d->zin.as<uint8_t>(), d->zblk.p, (uint32_t)j.n_blks, d->zout.as<uint8_t>(), d->zstat.as<uint32_t>()));
+    ok(mkp_launch_inflate_auto(d->stream, d->zin.as<uint8_t>(), d->zblk.as<MkpBgzfBlock>(), (uint32_t)j.n_blks, d->zout.as<uint8_t>(),
+        d->zstat.as<uint32_t>()));
     uint8_t* pout = (uint8_t*)d->pin_out.p;
     ok(hipMemcpyAsync(pout, d->zout.p, j.dtotal, hipMemcpyDeviceToHost, d->stream));
     ok(hipMemcpyAsync(pout + j.dtotal, d->zstat.p, j.n_blks * 4, hipMemcpyDeviceToHost, d->stream));
@@ -972,16 +978,6 @@ int mkp_host_map_order(const uint32_t* code_reprs, uint32_t n, uint32_t* order_o
 }  // extern "C"
 
 // ---- threshold sampling on the device (decode kernels in sampling mode; the values stay in HBM)
-extern "C" {
-hipError_t mkp_launch_sample_accumulate(hipStream_t, const MkpReadHdr*, const MkpReadOut*, const uint8_t*, uint32_t, const float*, const MkpEvent*,
-    uint32_t*,
-    unsigned long long, unsigned long long*, uint32_t*, uint32_t*);
-hipError_t mkp_launch_sample_hist1(hipStream_t, const uint32_t*, unsigned long long, uint32_t, uint32_t, uint32_t*);
-hipError_t mkp_launch_summary_accumulate(hipStream_t, const MkpReadHdr*, const MkpReadOut*, const uint8_t*, uint32_t, const MkpEvent*,
-    unsigned long long*,
-    unsigned long long*);
-}
-
 // Decode `recs` in sampling mode.  n_vals[i] = number of argmax probabilities record i yields after the filters (0: rejected or
 // nothing kept).  The values themselves stay on the device until mkp_internal_sample_take says which reads the schedule took.
 namespace {
@@ -1016,19 +1012,16 @@ void sample_decode(mkp_ctx* c, ShardHost& S, bool resident, const uint8_t* bedma
   c->d_events.ensure(cap * sizeof(MkpEvent)); c->d_vals.ensure(cap * sizeof(float));
     c->d_readout.ensure(std::max<size_t>(S.hdr.size(), 1) * sizeof(MkpReadOut));
       c->d_misc.ensure(64);
-  uint32_t* misc = c->d_misc.as<uint32_t>();
-  hip_check(hipMemsetAsync(misc, 0, 16, c->stream), "memset");
-  hip_check(mkp_launch_decode(c->stream, c->d_hdr.as<MkpReadHdr>(), c->d_read_ids.as<uint32_t>(), c->n_class, c->d_cigar.as<uint32_t>(),
-      c->d_seq.as<uint8_t>(),
-      c->d_tagref.as<MkpTagRef>(), c->d_ranks.as<uint32_t>(),
-                              c->d_ml.as<uint8_t>(), c->d_layouts.as<MkpLayout>(), &P, c->d_events.as<MkpEvent>(), c->d_readout.as<MkpReadOut>(),
-                                  misc + 2, d_mask, c->d_vals.as<float>()), "decode(sample) launch");
-  uint32_t h[4]; hip_check(hipMemcpyAsync(h, misc, 16, hipMemcpyDeviceToHost, c->stream), "D2H");
+  uint32_t* words = c->d_misc.as<uint32_t>();   // a sampling pass's own pass words (mkp_launch.h): the error word is the one in use
+  hip_check(hipMemsetAsync(words, 0, 16, c->stream), "memset");
+  hip_check(mkp_launch_decode(c->stream, shard_arrays(c), c->d_read_ids.as<uint32_t>(), c->n_class, &P, words + MKP_PW_ERR, d_mask,
+      c->d_vals.as<float>()), "decode(sample) launch");
+  uint32_t h[4]; hip_check(hipMemcpyAsync(h, words, 16, hipMemcpyDeviceToHost, c->stream), "D2H");
   c->sample_ro.resize(S.hdr.size());
   if (!S.hdr.empty()) hip_check(hipMemcpyAsync(c->sample_ro.data(), c->d_readout.p, S.hdr.size() * sizeof(MkpReadOut), hipMemcpyDeviceToHost,
       c->stream), "D2H");
   hip_check(hipStreamSynchronize(c->stream), "sample sync");
-  if (h[2] & 1u) throw Error(MKP_E_DEVICE, "internal: event segment overflow");
+  if (h[MKP_PW_ERR] & ERR_EVENT_CAP) throw Error(MKP_E_DEVICE, "internal: event segment overflow");
   if (S.hdr.size() != n_expected) throw Error(MKP_E_INVALID, "internal: sampler packed a different number of records");
   n_vals->resize(n_expected);
   for (size_t i = 0; i < n_expected; i++) (*n_vals)[i] = c->sample_ro[i].ok ? c->sample_ro[i].n_events : 0u;
@@ -1121,11 +1114,8 @@ int mkp_internal_sample_take(mkp_ctx* c, const std::vector<uint8_t>& take) {
       if (!c->d_summary.p) throw Error(MKP_E_INVALID, "internal: summary table not set up");
       c->d_take.ensure(std::max<size_t>(n, 16));
       hip_check(hipMemcpyAsync(c->d_take.p, take.data(), n, hipMemcpyHostToDevice, c->stream), "H2D");
-      hip_check(mkp_launch_summary_accumulate(c->stream, c->d_hdr.as<MkpReadHdr>(), c->d_readout.as<MkpReadOut>(), c->d_take.as<uint8_t>(),
-          (uint32_t)n,
-          c->d_events.as<MkpEvent>(),
-                                              c->d_summary.as<unsigned long long>(), c->d_summary.as<unsigned long long>() + 128),
-                                                  "summary accumulate launch");
+      hip_check(mkp_launch_summary_accumulate(c->stream, shard_arrays(c), c->d_take.as<uint8_t>(), (uint32_t)n,
+          c->d_summary.as<unsigned long long>(), c->d_summary.as<unsigned long long>() + 128), "summary accumulate launch");
       hip_check(hipStreamSynchronize(c->stream), "summary accumulate sync");
       return;
     }
@@ -1144,11 +1134,9 @@ int mkp_internal_sample_take(mkp_ctx* c, const std::vector<uint8_t>& take) {
     }
     c->d_take.ensure(std::max<size_t>(n, 16));
     hip_check(hipMemcpyAsync(c->d_take.p, take.data(), n, hipMemcpyHostToDevice, c->stream), "H2D");
-    uint32_t* misc = c->d_misc.as<uint32_t>();
-    hip_check(mkp_launch_sample_accumulate(c->stream, c->d_hdr.as<MkpReadHdr>(), c->d_readout.as<MkpReadOut>(), c->d_take.as<uint8_t>(), (uint32_t)n,
-        c->d_vals.as<float>(), c->d_events.as<MkpEvent>(),
-                                           c->d_store.as<uint32_t>(), c->d_store.cap / 4, c->d_sample_cursor.as<unsigned long long>(),
-                                               c->d_hist0.as<uint32_t>(), misc + 2), "sample accumulate launch");
+    hip_check(mkp_launch_sample_accumulate(c->stream, shard_arrays(c), c->d_take.as<uint8_t>(), (uint32_t)n, c->d_vals.as<float>(),
+        c->d_store.as<uint32_t>(), c->d_store.cap / 4, c->d_sample_cursor.as<unsigned long long>(), c->d_hist0.as<uint32_t>(),
+        c->d_misc.as<uint32_t>() + MKP_PW_ERR), "sample accumulate launch");
     hip_check(hipStreamSynchronize(c->stream), "sample accumulate sync");
     c->sample_n = need;
   });
@@ -1193,7 +1181,6 @@ int mkp_histogram_get(mkp_ctx* c, uint32_t base, uint32_t level, uint32_t prefix
 // run time (dlopen): a single-GPU build of the caller needs no RCCL.
 }  // extern "C"
 #include <dlfcn.h>
-extern "C" hipError_t mkp_launch_widen(hipStream_t, const uint32_t*, unsigned long long*, uint32_t);
 namespace {
 typedef int (*nccl_allreduce_fn)(const void*, void*, size_t, int, int, void*, hipStream_t);
 // the HIP runtime this library is bound to (its device pointers mean something to that copy only): a process that also imports torch
@@ -1399,12 +1386,6 @@ std::vector<std::pair<uint32_t, uint32_t>> rt_columns(const uint32_t* misc, uint
 }  // namespace
 
 // ---- region statistics (`modkit stats`, include/mkpileup.h): the table stays in HBM between mkp_stats_begin and mkp_stats_get
-extern "C" hipError_t mkp_launch_region_stats(hipStream_t, const uint32_t* /*pos*/, const uint32_t* /*info*/, const uint32_t* /*code*/,
-    const uint32_t* /*n_valid*/, const uint32_t* /*n_mod*/, uint32_t /*rows*/, const MkpStatsRegion*, uint32_t, uint32_t* /*first row*/,
-    uint32_t* /*row behind the last*/, uint32_t* /*chunks*/, unsigned long long* /*chunk offsets*/, unsigned long long* /*their total*/,
-    unsigned long long* /*table*/, uint32_t* /*seen masks*/, uint32_t* /*slot codes*/, uint32_t* /*error bits*/, unsigned long long /*min coverage*/,
-    uint32_t /*fixed code list*/, hipEvent_t* /*3 timing events or NULL*/);
-
 namespace {
 // d_misc: 16 slot codes, the error word, a pad word, the chunk total (u64)
 constexpr size_t kStatsMiscBytes = 4 * MKP_STATS_MAX_CODES + 16;
@@ -1506,11 +1487,6 @@ int mkp_stats_get(mkp_ctx* c, mkp_stats_out* out) {
 }  // extern "C"
 
 // ---- localize (`modkit localize`, include/mkpileup.h): the offset table stays in HBM between mkp_localize_begin and mkp_localize_get
-extern "C" hipError_t mkp_launch_localize(hipStream_t, const uint32_t* /*pos*/, const uint32_t* /*info*/, const uint32_t* /*code*/,
-    const uint32_t* /*n_valid*/, const uint32_t* /*n_mod*/, uint32_t /*rows*/, const MkpLocRegion*, uint32_t, uint32_t* /*first row*/,
-    uint32_t* /*row behind the last*/, uint32_t /*window*/, uint32_t /*stranded*/, unsigned long long* /*table*/, uint32_t* /*slot codes*/,
-    uint32_t* /*error bits*/, hipEvent_t* /*3 timing events or NULL*/);
-
 namespace {
 // d_misc: 16 slot codes, the error word, a pad word
 constexpr size_t kLocMiscBytes = 4 * MKP_STATS_MAX_CODES + 8;
@@ -1629,12 +1605,6 @@ int mkp_localize_get(mkp_ctx* c, mkp_localize_out* out) {
 
 // ---- bedmethyl merge (`modkit bedmethyl merge`, include/mkpileup.h): one merged row table per contig stays in HBM between mkp_merge_begin
 // and the mkp_merge_get calls; every add is one two-way merge (mkp_merge.hip)
-extern "C" hipError_t mkp_launch_merge(hipStream_t, const MkpRowsDev* /*table*/, uint32_t, const MkpRowsDev* /*added rows*/, uint32_t,
-    const MkpRowsDev* /*staging*/, const MkpRowsDev* /*new table*/, MkpMergeCut* /*cuts*/, uint32_t* /*tile counts*/, uint32_t* /*tile offsets*/,
-    uint32_t* /*rows of the new table*/, uint32_t* /*error bits*/, hipEvent_t* /*3 timing events or NULL*/);
-extern "C" hipError_t mkp_launch_merge_rows_below(hipStream_t, const uint32_t* /*pos*/, uint32_t, uint32_t /*limit*/, uint32_t* /*out*/);
-extern "C" uint32_t mkp_merge_tiles(uint64_t n_rows);
-
 namespace {
 // d_misc: rows of the new table, the error word (kept over the session), the rows below the contig's length, a pad word
 constexpr size_t kMergeMiscBytes = 16;

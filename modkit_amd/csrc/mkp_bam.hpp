@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "../../include/mkpileup.h"
+#include "mkp_device.h"
 
 namespace mkp {
 
@@ -485,7 +486,7 @@ static inline bool overlaps_parts(const FetchParts& parts, int64_t pos, int64_t 
 
 // Optional device stage of the indexed fetch (--device-inflate): one window's BGZF blocks inflated on the GPU (mkp_inflate_wave4.hip) straight
 // into the window's host buffer.  false = not done (any block failed, or no device): the host decoder then runs and reports.
-struct InflateBlk { unsigned long long in_off, out_off; uint32_t in_len, out_len; };   // == MkpBgzfBlock
+using InflateBlk = ::MkpBgzfBlock;   // (mkp_device.h)
 struct InflateJob { const uint8_t* comp; size_t comp_len; const InflateBlk* blks; size_t n_blks; uint8_t* dst; size_t dtotal; };
 using DeviceInflateFn = bool (*)(void* user, const InflateJob& job);
 

@@ -8,10 +8,6 @@
 
 #include "mkp_device.h"
 
-#define ERR_EVENT_CAP 1u
-#define ERR_ROW_CAP 2u
-#define ERR_DEPTH 4u
-
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63u); }
 __device__ __forceinline__ unsigned long long lanemask_le() { int l = lane_id(); return l == 63 ? ~0ull : ((1ull << (l + 1)) - 1ull); }
 __device__ __forceinline__ unsigned long long lanemask_lt() { return (1ull << lane_id()) - 1ull; }

@@ -279,6 +279,10 @@ struct MkpDupCons {
   uint32_t out_n, out_ok, out_obs0, out_obs1;   // written by mkp_dup_events, moved into the record's header / summary by mkp_dup_apply
   uint32_t pad[6];
 };
+// the error word of a pass (the kernels' dev_err; mkp_launch.h says where it lies)
+#define ERR_EVENT_CAP 1u   // device error bit: a read's events (a sampling pass: the sampled values) outgrew their slice
+#define ERR_ROW_CAP 2u     // device error bit: the rows outgrew row_capacity (the host doubles it and runs the pass again)
+#define ERR_DEPTH 4u       // (no kernel raises it)
 #define ERR_DUP_MIXED 8u   // device error bit: the records a consumer is answered from disagree in status or observed codes (refused, not approximated)
 #define MKP_VF_OK 1u
 #define MKP_VF_REV 2u
@@ -286,6 +290,10 @@ struct MkpDupCons {
 // one tile of mkp_pileup_stream: rows for the global slots [g0, g1) (positions [r0, r1)), tally columns for [gh0, gh1) (+- MKP_HALO
 // positions for strand combining), candidate reads [first, last)
 struct MkpSTile { uint32_t g0, g1, gh0, gh1; int32_t r0, r1; uint32_t first, last; };
+
+// one BGZF block of an inflate launch (mkp_inflate_wave4.hip; mkp_crc32_blocks and mkp_bgzf_layout of mkp_ingest.hip): where its DEFLATE
+// payload lies in the compressed bytes and where its inflated bytes go
+struct MkpBgzfBlock { unsigned long long in_off; unsigned long long out_off; uint32_t in_len; uint32_t out_len; };
 
 struct MkpRowsDev {  // SoA row buffers (44 B / row)
   uint32_t* pos; uint32_t* info; uint32_t* code;

@@ -20,8 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "mkp_inflate_tok.hpp"
-
-struct MkpBgzfBlock { unsigned long long in_off; unsigned long long out_off; uint32_t in_len; uint32_t out_len; };
+#include "mkp_launch.h"
 
 namespace {
 constexpr uint32_t LIT_BITS = MKP_W4_LIT_BITS, DIST_BITS = MKP_W4_DIST_BITS, INW = MKP_W4_INW;
@@ -420,12 +419,13 @@ mkp_inflate_wave4_2k(const uint8_t* __restrict__ in_bytes, const MkpBgzfBlock* _
   inflate_wave_par<2048u, true>(in_bytes, blocks, n_blocks, out, status);
 }
 
-extern "C" hipError_t mkp_launch_inflate_wave4(hipStream_t st, const uint8_t* in, const void* blocks, uint32_t n_blocks, uint8_t* out,
+// host-side launcher (declared in mkp_launch.h)
+extern "C" hipError_t mkp_launch_inflate_wave4(hipStream_t st, const uint8_t* in, const MkpBgzfBlock* blocks, uint32_t n_blocks, uint8_t* out,
     uint32_t* status, int variant) {
   if (!n_blocks) return hipSuccess;
-  if (variant == 8) hipLaunchKernelGGL(mkp_inflate_wave4_8k, dim3(n_blocks), dim3(64), 0, st, in, (const MkpBgzfBlock*)blocks, n_blocks, out, status);
-  else if (variant == 2) hipLaunchKernelGGL(mkp_inflate_wave4_2k, dim3(n_blocks), dim3(64), 0, st, in, (const MkpBgzfBlock*)blocks, n_blocks, out,
+  if (variant == 8) hipLaunchKernelGGL(mkp_inflate_wave4_8k, dim3(n_blocks), dim3(64), 0, st, in, blocks, n_blocks, out, status);
+  else if (variant == 2) hipLaunchKernelGGL(mkp_inflate_wave4_2k, dim3(n_blocks), dim3(64), 0, st, in, blocks, n_blocks, out,
       status);
-  else hipLaunchKernelGGL(mkp_inflate_wave4, dim3(n_blocks), dim3(64), 0, st, in, (const MkpBgzfBlock*)blocks, n_blocks, out, status);
+  else hipLaunchKernelGGL(mkp_inflate_wave4, dim3(n_blocks), dim3(64), 0, st, in, blocks, n_blocks, out, status);
   return hipGetLastError();
 }

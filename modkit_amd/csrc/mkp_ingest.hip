@@ -10,9 +10,7 @@
 #include <stdint.h>
 
 #include "mkp_ingest_dev.hpp"
-
-struct MkpBgzfBlock { unsigned long long in_off; unsigned long long out_off; uint32_t in_len; uint32_t out_len; };
-
+#include "mkp_launch.h"
 
 // CRC-32 of every inflated block against the word behind its payload.  One wave per BGZF block: the block's bytes split into 64 slices, every
 // lane runs a slicing-by-4 table CRC over its slice — one dword per step: four independent LDS probes instead of four dependent ones; the
@@ -289,6 +287,7 @@ mkp_widen_u32_u64(const uint32_t* __restrict__ in, unsigned long long* __restric
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) out[i] = in[i];
 }
 
+// host-side launchers (declared in mkp_launch.h)
 extern "C" {
 hipError_t mkp_launch_widen(hipStream_t st, const uint32_t* in, unsigned long long* out, uint32_t n) {
   if (n) hipLaunchKernelGGL(mkp_widen_u32_u64, dim3((n + 255u) / 256u), dim3(256), 0, st, in, out, n);
@@ -305,13 +304,14 @@ hipError_t mkp_launch_bgzf_chain_write(hipStream_t st, const uint8_t* z, const M
   return hipGetLastError();
 }
 hipError_t mkp_launch_bgzf_layout(hipStream_t st, const MkpZBlk* zb, uint32_t n, unsigned long long* raw_cursor, unsigned long long raw_cap,
-    void* out, uint32_t* err) {
-  hipLaunchKernelGGL(mkp_bgzf_layout, dim3(1), dim3(1024), 0, st, zb, n, raw_cursor, raw_cap, (MkpBgzfBlock*)out, err);
+    MkpBgzfBlock* out, uint32_t* err) {
+  hipLaunchKernelGGL(mkp_bgzf_layout, dim3(1), dim3(1024), 0, st, zb, n, raw_cursor, raw_cap, out, err);
   return hipGetLastError();
 }
-hipError_t mkp_launch_crc32(hipStream_t st, const uint8_t* zin, const void* blocks, uint32_t n_blocks, const uint8_t* raw, uint32_t* status) {
+hipError_t mkp_launch_crc32(hipStream_t st, const uint8_t* zin, const MkpBgzfBlock* blocks, uint32_t n_blocks, const uint8_t* raw,
+    uint32_t* status) {
   if (!n_blocks) return hipSuccess;
-  hipLaunchKernelGGL(mkp_crc32_blocks, dim3((n_blocks + 3u) / 4u), dim3(256), 0, st, zin, (const MkpBgzfBlock*)blocks, n_blocks, raw, status);
+  hipLaunchKernelGGL(mkp_crc32_blocks, dim3((n_blocks + 3u) / 4u), dim3(256), 0, st, zin, blocks, n_blocks, raw, status);
   return hipGetLastError();
 }
 hipError_t mkp_launch_ingest_count(hipStream_t st, const uint8_t* raw, const MkpIngestParams* P, const MkpSeg* segs, uint32_t* seg_cnt,

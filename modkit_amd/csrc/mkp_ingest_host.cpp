@@ -12,21 +12,10 @@
 
 #include "mkp_ingest_dev.hpp"
 #include "mkp_ingest_host.hpp"
+#include "mkp_launch.h"
 #include <cmath>
 
 using namespace mkp;
-
-extern "C" {
-hipError_t mkp_launch_crc32(hipStream_t, const uint8_t*, const void*, uint32_t, const uint8_t*, uint32_t*);
-hipError_t mkp_launch_bgzf_chain_count(hipStream_t, const uint8_t*, const MkpZChain*, uint32_t, uint32_t*, uint32_t*);
-hipError_t mkp_launch_bgzf_chain_write(hipStream_t, const uint8_t*, const MkpZChain*, uint32_t, const uint32_t*, uint32_t, MkpZBlk*, uint32_t*);
-hipError_t mkp_launch_bgzf_layout(hipStream_t, const MkpZBlk*, uint32_t, unsigned long long*, unsigned long long, void*, uint32_t*);
-hipError_t mkp_launch_ingest_count(hipStream_t, const uint8_t*, const MkpIngestParams*, const MkpSeg*, uint32_t*, MkpIngestTotals*);
-hipError_t mkp_launch_ingest_parse(hipStream_t, const uint8_t*, const MkpIngestParams*, const int32_t*, const MkpSeg*, const uint32_t*,
-    unsigned long long*, MkpRecInfo*, uint32_t*, int32_t*, MkpIngestTotals*);
-hipError_t mkp_launch_ingest_pack(hipStream_t, const uint8_t*, uint32_t, const MkpRecInfo*, const uint32_t*, MkpReadHdr*, uint32_t*, uint16_t*,
-    uint32_t*, uint8_t*, MkpTagRef*, uint32_t*, uint8_t*, MkpRecDigest*, MkpIngestTotals*);
-}
 
 #define MKP_INGEST_SPARES 20
 namespace {
@@ -36,7 +25,6 @@ struct Pinned {
       throw Error(MKP_E_NOMEM, "hipHostMalloc failed"); } cap = n; }
   void release() { if (p) (void)hipHostFree(p); p = nullptr; cap = 0; }
 };
-struct BgzfBlk { unsigned long long in_off, out_off; uint32_t in_len, out_len; };   // == MkpBgzfBlock
 uint64_t fnv64(const std::string& s) { uint64_t h = 1469598103934665603ull; for (unsigned char ch : s) { h ^= ch; h *= 1099511628211ull; } return h; }
 }  // namespace
 
@@ -281,9 +269,9 @@ std::unique_ptr<DevShard> mkp_internal_ingest_run(mkp_dev_ingest* d, const BamSo
     lap("small buffers + events");   // (a temporary: through the library's page-locked staging, mkp_ctx.hpp)
     ok(hipMemsetAsync(d->tot.p, 0, sizeof(MkpIngestTotals), d->stream), "memset");
     ok(hipMemsetAsync(d->rawcur.p, 0, 16, d->stream), "memset");
-    size_t blk_cap = std::max<size_t>({d->zblk.cap / sizeof(BgzfBlk), d->ztab.cap / sizeof(MkpZBlk), (size_t)(plan.comp_total / 8192 + 4096)});
-    d->zblk.ensure(blk_cap * sizeof(BgzfBlk)); d->ztab.ensure(blk_cap * sizeof(MkpZBlk)); d->zstat.ensure(blk_cap * 4 + 16);
-    blk_cap = std::min({d->zblk.cap / sizeof(BgzfBlk), d->ztab.cap / sizeof(MkpZBlk), (d->zstat.cap - 16) / 4});
+    size_t blk_cap = std::max<size_t>({d->zblk.cap / sizeof(MkpBgzfBlock), d->ztab.cap / sizeof(MkpZBlk), (size_t)(plan.comp_total / 8192 + 4096)});
+    d->zblk.ensure(blk_cap * sizeof(MkpBgzfBlock)); d->ztab.ensure(blk_cap * sizeof(MkpZBlk)); d->zstat.ensure(blk_cap * 4 + 16);
+    blk_cap = std::min({d->zblk.cap / sizeof(MkpBgzfBlock), d->ztab.cap / sizeof(MkpZBlk), (d->zstat.cap - 16) / 4});
     // (a window of unusually small blocks: the tables grow, keeping what the stages before wrote)
     auto grow = [&](DevBuf& b, size_t need, size_t keep) {
       DevBuf nb; nb.ensure(need); ok(hipStreamSynchronize(d->stream), "sync"); for (auto& st : d->inf_stream) ok(hipStreamSynchronize(st), "sync");
@@ -322,11 +310,11 @@ std::unique_ptr<DevShard> mkp_internal_ingest_run(mkp_dev_ingest* d, const BamSo
       const uint32_t nblk = h_small[1]; stage_nblk[j] = nblk;
       if (blkbase + nblk > 0xfffffff0ull) throw Error(MKP_E_UNSUPPORTED, "shard window holds too many BGZF blocks; use smaller shards");
       if (blkbase + nblk > blk_cap) { const size_t want = std::max<size_t>(2 * blk_cap, blkbase + nblk + 4096);
-        grow(d->zblk, want * sizeof(BgzfBlk), blkbase * sizeof(BgzfBlk)); { Pinned nt; nt.ensure(want * sizeof(MkpZBlk));
+        grow(d->zblk, want * sizeof(MkpBgzfBlock), blkbase * sizeof(MkpBgzfBlock)); { Pinned nt; nt.ensure(want * sizeof(MkpZBlk));
           ok(hipStreamSynchronize(d->stream), "sync"); if (blkbase) memcpy(nt.p, d->ztab.p, blkbase * sizeof(MkpZBlk)); d->ztab.release();
           d->ztab = nt; } grow(d->zstat, want * 4 + 16, blkbase * 4); blk_cap = want; }
       if (!nblk) continue;
-      MkpZBlk* ztab = (MkpZBlk*)d->ztab.p + blkbase; BgzfBlk* zblk = d->zblk.as<BgzfBlk>() + blkbase;
+      MkpZBlk* ztab = (MkpZBlk*)d->ztab.p + blkbase; MkpBgzfBlock* zblk = d->zblk.as<MkpBgzfBlock>() + blkbase;
         uint32_t* zst = d->zstat.as<uint32_t>() + blkbase;
       ok(mkp_launch_bgzf_chain_write(d->stream, d->zin.as<uint8_t>(), zc + c0, (uint32_t)n, cnt, nblk, ztab, d->tot.as<uint32_t>()),
           "block table launch");
@@ -388,7 +376,7 @@ std::unique_ptr<DevShard> mkp_internal_ingest_run(mkp_dev_ingest* d, const BamSo
       "shard window holds too many BGZF blocks; use smaller shards");
   // ---- tables: BGZF blocks, chain segments
   const size_t nb = plan.blks.size(), ns = plan.entries.size();
-  std::vector<BgzfBlk> blks(nb);
+  std::vector<MkpBgzfBlock> blks(nb);
   for (size_t r = 0; r < plan.ranges.size(); r++) for (size_t k = plan.ranges[r].blk0; k < plan.ranges[r].blk1; k++) {
     const BamSource::IngestBlk& b = plan.blks[k];
     if (b.isize > 65536u) throw Error(MKP_E_IO, "BGZF block inflates to more than 64 KiB in " + bam.path());
@@ -396,30 +384,31 @@ std::unique_ptr<DevShard> mkp_internal_ingest_run(mkp_dev_ingest* d, const BamSo
   }
   const std::vector<MkpSeg> segs = mkp_plan_segments<MkpSeg>(plan);
   lap("segments");
-  d->zblk.ensure(nb * sizeof(BgzfBlk)); d->zstat.ensure(nb * 4 + 16); d->raw.ensure(plan.raw_total + 64); d->segs.ensure(ns * sizeof(MkpSeg));
+  d->zblk.ensure(nb * sizeof(MkpBgzfBlock)); d->zstat.ensure(nb * 4 + 16); d->raw.ensure(plan.raw_total + 64); d->segs.ensure(ns * sizeof(MkpSeg));
     d->seg_cnt.ensure((ns + 1) * 4); d->tot.ensure(sizeof(MkpIngestTotals));
-  const size_t small_need = nb * sizeof(BgzfBlk) + ns * sizeof(MkpSeg) + 2 * (nb * 4 + 64) + sizeof(MkpIngestTotals) + 256;
+  const size_t small_need = nb * sizeof(MkpBgzfBlock) + ns * sizeof(MkpSeg) + 2 * (nb * 4 + 64) + sizeof(MkpIngestTotals) + 256;
   d->small.ensure(small_need + small_need / 4);
-  uint8_t* sm = (uint8_t*)d->small.p; uint8_t* sm_blk = sm; uint8_t* sm_seg = sm + nb * sizeof(BgzfBlk);
+  uint8_t* sm = (uint8_t*)d->small.p; uint8_t* sm_blk = sm; uint8_t* sm_seg = sm + nb * sizeof(MkpBgzfBlock);
     uint8_t* sm_tot = sm_seg + ns * sizeof(MkpSeg); uint8_t* sm_stat = sm_tot + ((sizeof(MkpIngestTotals) + 63) & ~(size_t)63);
     uint8_t* sm_stat0 = sm_stat + ((nb * 4 + 63) & ~(size_t)63);
-  memcpy(sm_blk, blks.data(), nb * sizeof(BgzfBlk)); memcpy(sm_seg, segs.data(), ns * sizeof(MkpSeg));
+  memcpy(sm_blk, blks.data(), nb * sizeof(MkpBgzfBlock)); memcpy(sm_seg, segs.data(), ns * sizeof(MkpSeg));
   ok(hipMemcpyAsync(d->segs.p, sm_seg, ns * sizeof(MkpSeg), hipMemcpyHostToDevice, d->stream), "H2D");
   ok(hipMemsetAsync(d->tot.p, 0, sizeof(MkpIngestTotals), d->stream), "memset");
   auto t_inf = staged_done ? t_inf_staged : std::chrono::steady_clock::now();
   if (!staged_done) {   // the whole window in one launch: the host-table path, or a window that outgrew the staged path's estimate
-    ok(hipMemcpyAsync(d->zblk.p, sm_blk, nb * sizeof(BgzfBlk), hipMemcpyHostToDevice, d->stream), "H2D");
+    ok(hipMemcpyAsync(d->zblk.p, sm_blk, nb * sizeof(MkpBgzfBlock), hipMemcpyHostToDevice, d->stream), "H2D");
     ok(hipMemsetAsync(d->zstat.p, 0xff, nb * 4, d->stream), "memset");
     ok(hipStreamWaitEvent(d->stream, d->up_done, 0), "wait for the upload");
     // ---- inflate + CRC
     ok(hipEventRecord(d->kev[0], d->stream), "event");
-    ok(mkp_launch_inflate_auto(d->stream, d->zin.as<uint8_t>(), d->zblk.p, (uint32_t)nb, d->raw.as<uint8_t>(), d->zstat.as<uint32_t>()),
-        "inflate launch");
+    ok(mkp_launch_inflate_auto(d->stream, d->zin.as<uint8_t>(), d->zblk.as<MkpBgzfBlock>(), (uint32_t)nb, d->raw.as<uint8_t>(),
+        d->zstat.as<uint32_t>()), "inflate launch");
     // the CRC-32 of every block runs on a stream of its own, beside the record kernels below: its verdict — and the decoders'
     // status words it is OR-ed into — is only read when something has gone wrong, or at the very end (corrupt())
     ok(hipEventRecord(d->inf_done, d->stream), "event");
     ok(hipStreamWaitEvent(d->crc_stream, d->inf_done, 0), "wait for the inflate");
-    ok(mkp_launch_crc32(d->crc_stream, d->zin.as<uint8_t>(), d->zblk.p, (uint32_t)nb, d->raw.as<uint8_t>(), d->zstat.as<uint32_t>()), "crc launch");
+    ok(mkp_launch_crc32(d->crc_stream, d->zin.as<uint8_t>(), d->zblk.as<MkpBgzfBlock>(), (uint32_t)nb, d->raw.as<uint8_t>(),
+        d->zstat.as<uint32_t>()), "crc launch");
   } else {   // the record kernels read what the stages' inflate launches wrote
     (void)copy_stage();   // (this thread's page-locked copy staging, needed for the digest: allocated while the last stages inflate)
     for (hipEvent_t e : last_inf) if (e) ok(hipStreamWaitEvent(d->stream, e, 0), "wait for the inflate");

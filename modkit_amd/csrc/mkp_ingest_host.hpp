@@ -28,9 +28,10 @@ template <class Seg> inline std::vector<Seg> mkp_plan_segments(const mkp::BamSou
   return segs;
 }
 
-// the BGZF inflate kernel for a launch of n blocks (mkp_api.cpp): one wave per block (speculative token decode) below 28 000 blocks, one thread per
-// block (second edition) from there; MKP_INFLATE_KERNEL=wave|thread|thread2 forces one
-hipError_t mkp_launch_inflate_auto(hipStream_t st, const uint8_t* in, const void* blks, uint32_t n, uint8_t* out, uint32_t* status);
+// the BGZF inflate launch of n blocks (a host function of mkp_api.cpp over mkp_launch_inflate_wave4, one wave per block): blks[i] says where
+// block i's payload lies in `in` and where its bytes go in `out`, status[i] = 0 where it inflated; the 4 KiB ring unless
+// MKP_INFLATE_KERNEL=wave4_8k|wave4_2k asks for another ring size
+hipError_t mkp_launch_inflate_auto(hipStream_t st, const uint8_t* in, const MkpBgzfBlock* blks, uint32_t n, uint8_t* out, uint32_t* status);
 
 mkp_dev_ingest* mkp_internal_ingest_create(int device);
 void mkp_internal_ingest_destroy(mkp_dev_ingest* d);

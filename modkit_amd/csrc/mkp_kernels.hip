@@ -28,6 +28,7 @@
 #include "mkp_dev_common.hpp"
 #include "mkp_dev_rows.hpp"
 #include "mkp_dev_tiles.hpp"
+#include "mkp_launch.h"
 
 // ----------------------------------------------------------------------------------------------
 // What the three wave-per-read decoders share.  They differ in how they locate a read's calls (the producers); the read
@@ -1812,23 +1813,21 @@ mkp_summary_accumulate(const MkpReadHdr* __restrict__ hdrs, const MkpReadOut* __
   if (threadIdx.x < 5 && lr[threadIdx.x]) atomicAdd(&reads_with[threadIdx.x], (unsigned long long)lr[threadIdx.x]);
   if (threadIdx.x == 5 && lr[5]) atomicOr(&reads_with[5], (unsigned long long)lr[5]);
 }
-extern "C" hipError_t mkp_launch_summary_accumulate(hipStream_t st, const MkpReadHdr* hdrs, const MkpReadOut* readout, const uint8_t* take,
-    uint32_t n_reads, const MkpEvent* events,
-                                                    unsigned long long* table, unsigned long long* reads_with) {
+// host-side launchers of the sampling kernels (declared in mkp_launch.h)
+extern "C" hipError_t mkp_launch_summary_accumulate(hipStream_t st, const MkpShardArrays& sh, const uint8_t* take, uint32_t n_reads,
+    unsigned long long* table, unsigned long long* reads_with) {
   if (!n_reads) return hipSuccess;
   const uint32_t grid = std::min<uint32_t>((n_reads + 3u) / 4u, 1024u);
-  hipLaunchKernelGGL(mkp_summary_accumulate, dim3(grid), dim3(256), 0, st, hdrs, readout, take, n_reads, events, table, reads_with);
+  hipLaunchKernelGGL(mkp_summary_accumulate, dim3(grid), dim3(256), 0, st, sh.hdr, sh.readout, take, n_reads, sh.events, table, reads_with);
   return hipGetLastError();
 }
 
-extern "C" hipError_t mkp_launch_sample_accumulate(hipStream_t st, const MkpReadHdr* hdrs, const MkpReadOut* readout, const uint8_t* take,
-    uint32_t n_reads, const float* vals,
-                                                   const MkpEvent* events, uint32_t* store, unsigned long long store_cap,
-                                                       unsigned long long* store_cursor, uint32_t* hist0, uint32_t* dev_err) {
+extern "C" hipError_t mkp_launch_sample_accumulate(hipStream_t st, const MkpShardArrays& sh, const uint8_t* take, uint32_t n_reads,
+    const float* vals, uint32_t* store, unsigned long long store_cap, unsigned long long* store_cursor, uint32_t* hist0, uint32_t* dev_err) {
   if (!n_reads) return hipSuccess;
   const uint32_t grid = std::min<uint32_t>((n_reads + 3u) / 4u, 1024u);
-  hipLaunchKernelGGL(mkp_sample_accumulate, dim3(grid), dim3(256), 0, st, hdrs, readout, take, n_reads, vals, events, store, store_cap, store_cursor,
-      hist0, dev_err);
+  hipLaunchKernelGGL(mkp_sample_accumulate, dim3(grid), dim3(256), 0, st, sh.hdr, sh.readout, take, n_reads, vals, sh.events, store, store_cap,
+      store_cursor, hist0, dev_err);
   return hipGetLastError();
 }
 extern "C" hipError_t mkp_launch_sample_hist1(hipStream_t st, const uint32_t* store, unsigned long long n, uint32_t base, uint32_t prefix,
@@ -1840,13 +1839,13 @@ extern "C" hipError_t mkp_launch_sample_hist1(hipStream_t st, const uint32_t* st
 }
 
 // ----------------------------------------------------------------------------------------------
-// host-side launchers (called from mkp_api.cpp)
+// host-side launchers (declared in mkp_launch.h)
 // read_ids = [SPARSE one tag | SPARSE two tags | FAST one tag | FAST two tags | all other reads], n_class = the five list lengths
-extern "C" hipError_t mkp_launch_decode(hipStream_t st, const MkpReadHdr* hdrs, const uint32_t* read_ids, const uint32_t* n_class /* [7] */,
-    const uint32_t* cigar, const uint8_t* seqs,
-                                        const MkpTagRef* tagref, const uint32_t* ranks, const uint8_t* ml, const MkpLayout* layouts,
-                                        const MkpRunParams* prm, MkpEvent* events, MkpReadOut* readout, uint32_t* dev_err,
-                                        const uint8_t* bedmask, float* sample_vals) {
+extern "C" hipError_t mkp_launch_decode(hipStream_t st, const MkpShardArrays& sh, const uint32_t* read_ids, const uint32_t* n_class /* [7] */,
+    const MkpRunParams* prm, uint32_t* dev_err, const uint8_t* bedmask, float* sample_vals) {
+  const MkpReadHdr* hdrs = sh.hdr; const uint32_t* cigar = sh.cigar; const uint8_t* seqs = sh.seq; const MkpTagRef* tagref = sh.tagref;
+  const uint32_t* ranks = sh.ranks; const uint8_t* ml = sh.ml; const MkpLayout* layouts = sh.layouts; MkpEvent* events = sh.events;
+  MkpReadOut* readout = sh.readout;
   const uint32_t waves_per_block = 4;
   const uint32_t* ids = read_ids;
   for (int cls = 0; cls < 7; cls++) {
@@ -1891,31 +1890,27 @@ extern "C" hipError_t mkp_pileup_set_lds(uint32_t accum_bytes) {
 }
 
 // hemi: pileup-hemi (slotbm = the run's slot bitmap); otherwise a run without focus positions (slotbm unused)
-extern "C" hipError_t mkp_launch_pileup(hipStream_t st, uint32_t lds_bytes, bool hemi, const MkpReadHdr* hdrs, const uint32_t* cigar,
-                                        const uint8_t* seqs, const MkpEvent* events, const MkpReadOut* readout, const MkpTile* tiles,
-                                        uint32_t n_tiles, const MkpRunParams* prm_dev, const uint32_t* slotbm, const MkpRowsDev* rows,
-                                        uint32_t* row_cursor, uint32_t* tile_row_off, uint32_t* tile_row_cnt, const uint32_t* chunk_pfx,
-                                        uint32_t* dev_err, uint32_t key_filter, uint32_t key_slot, bool wide) {
+extern "C" hipError_t mkp_launch_pileup(hipStream_t st, uint32_t lds_bytes, bool hemi, const MkpShardArrays& sh, const MkpTile* tiles,
+    uint32_t n_tiles, const MkpRunParams* prm_dev, const uint32_t* slotbm, const MkpRowsDev* rows, uint32_t* row_cursor, uint32_t* tile_row_off,
+    uint32_t* tile_row_cnt, uint32_t* dev_err, uint32_t key_filter, uint32_t key_slot, bool wide) {
   if (!n_tiles) return hipSuccess;
   const bool keyed = key_filter != MKP_NO_KEY_FILTER;
   const uint32_t key_arg = keyed ? ((key_filter & 0xffffu) | (key_slot << 16)) : 0u;
   const uint32_t grid = n_tiles;   // one workgroup per tile
   // ONE build of each accumulate kernel: what a one-shot shard pass launches is what a re-launch on the resident shard launches
-#define MKP_PILEUP_LAUNCH(K, LAST) hipLaunchKernelGGL(K, dim3(grid), dim3(PILEUP_THREADS), lds_bytes, st, hdrs, cigar, seqs, events, readout, tiles, \
-                       n_tiles, prm_dev, rows->pos, row_cursor, tile_row_off, tile_row_cnt, reinterpret_cast<const uint2*>(chunk_pfx), dev_err, LAST)
+#define MKP_PILEUP_LAUNCH(K, LAST) hipLaunchKernelGGL(K, dim3(grid), dim3(PILEUP_THREADS), lds_bytes, st, sh.hdr, sh.cigar, sh.seq, sh.events, sh.readout, \
+                       tiles, n_tiles, prm_dev, rows->pos, row_cursor, tile_row_off, tile_row_cnt, reinterpret_cast<const uint2*>(sh.chunk_pfx), dev_err, LAST)
   if (hemi) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_hemi, slotbm);
   else if (wide) { if (keyed) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_keyed_wide, key_arg); else MKP_PILEUP_LAUNCH(mkp_pileup_tiles_wide, key_arg); }   // u32 tallies
   else { if (keyed) MKP_PILEUP_LAUNCH(mkp_pileup_tiles_keyed, key_arg); else MKP_PILEUP_LAUNCH(mkp_pileup_tiles, key_arg); }
   return hipGetLastError();
 }
 
-extern "C" hipError_t mkp_launch_hemi_failed(hipStream_t st, const MkpReadHdr* hdrs, const uint32_t* cigar, const uint8_t* seqs, MkpEvent* events,
-    MkpReadOut* readout, uint32_t n_reads,
-                                             const uint32_t* slotbm, const uint32_t* iv_start, uint32_t n_iv, int32_t win_start, int32_t win_end,
-                                                 uint32_t* dev_err) {
+extern "C" hipError_t mkp_launch_hemi_failed(hipStream_t st, const MkpShardArrays& sh, uint32_t n_reads, const uint32_t* slotbm,
+    const uint32_t* iv_start, uint32_t n_iv, int32_t win_start, int32_t win_end, uint32_t* dev_err) {
   if (!n_reads) return hipSuccess;
-  hipLaunchKernelGGL(mkp_hemi_failed_reads, dim3((n_reads + 255u) / 256u), dim3(256), 0, st, hdrs, cigar, seqs, events, readout, n_reads, slotbm,
-      iv_start, n_iv, win_start, win_end, dev_err);
+  hipLaunchKernelGGL(mkp_hemi_failed_reads, dim3((n_reads + 255u) / 256u), dim3(256), 0, st, sh.hdr, sh.cigar, sh.seq, sh.events, sh.readout,
+      n_reads, slotbm, iv_start, n_iv, win_start, win_end, dev_err);
   return hipGetLastError();
 }
 

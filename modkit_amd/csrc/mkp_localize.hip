@@ -18,6 +18,7 @@
 // Code slots are claimed by resolve_slot of mkp_dev_codeslots.hpp, shared with mkp_stats.hip (the first counted row of a code, one lane per
 // wave and code); a code whose slot is beyond the LDS ones adds to HBM per row (rare, exact); a seventeenth code sets the error bit.
 #include "mkp_dev_codeslots.hpp"
+#include "mkp_launch.h"
 
 namespace {
 
@@ -121,7 +122,8 @@ __global__ __launch_bounds__(256) void mkp_localize_reduce(const uint32_t* __res
 
 extern "C" uint32_t mkp_localize_tile_offsets(void) { return kTile; }
 
-// ev (may be NULL): three events recorded in front of the bounds kernel, in front of the reduce kernel and behind it
+// host-side launcher (declared in mkp_launch.h).  ev (may be NULL): three events recorded in front of the bounds kernel, in front of the reduce
+// kernel and behind it
 extern "C" hipError_t mkp_launch_localize(hipStream_t st, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
     const uint32_t* n_mod, uint32_t n_rows, const MkpLocRegion* regions, uint32_t n_regions, uint32_t* row_lo, uint32_t* row_hi, uint32_t window,
     uint32_t stranded, unsigned long long* tab, uint32_t* codes, uint32_t* err, hipEvent_t* ev) {

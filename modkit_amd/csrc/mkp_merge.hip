@@ -26,6 +26,7 @@
 //   mkp_merge_compact    a workgroup per tile copies its staged rows to their place in the new table, all eleven columns, coalesced.
 // No global atomic per row (the error word is touched only when something is wrong), vector stores only.
 #include "mkp_dev_codeslots.hpp"
+#include "mkp_launch.h"
 
 namespace {
 
@@ -185,6 +186,7 @@ ColsOut cols_out_of(const MkpRowsDev& r) {
 
 extern "C" uint32_t mkp_merge_tile_rows(void) { return kStep; }
 
+// host-side entry points (declared in mkp_launch.h)
 extern "C" uint32_t mkp_merge_tiles(uint64_t n_rows) { return (uint32_t)((n_rows + kStep - 1u) / kStep); }
 
 extern "C" hipError_t mkp_launch_merge_rows_below(hipStream_t st, const uint32_t* pos, uint32_t n, uint32_t limit, uint32_t* out) {

@@ -40,6 +40,7 @@
 #include "mkp_cigar_pack.hpp"
 #include "mkp_dev_common.hpp"
 #include "mkp_dev_rows.hpp"
+#include "mkp_launch.h"
 
 // per-wave LDS of mkp_decode_slots: the read's caller constants per code (integer pass threshold, offset and stride of its ML bytes,
 // counter of Modified(code)) — uniform, but the kernel is short of scalar registers: every lane reads them back as vectors once per slot batch
@@ -1003,39 +1004,36 @@ extern "C" __global__ void __launch_bounds__(64) mkp_dup_events(const MkpReadHdr
 }
 
 // ----------------------------------------------------------------------------------------------------------------------
-// host-side launchers (called from mkp_api.cpp)
+// host-side launchers (declared in mkp_launch.h)
 // work = the fused decoder's reads (longest first), cover_ids = the reads of mkp_cover_reads
 // (call_plane, base_plane: the fused reads' two planes, MkpWork.pad indexes both)
 extern "C" hipError_t mkp_launch_slots(hipStream_t st, const MkpWork* work, uint32_t n_fused, const MkpCallEnt* call_plane, const MkpBaseEnt* base_plane,
-    const uint16_t* cigar16,
-    const MkpReadHdr* hdrs, const uint32_t* cover_ids, uint32_t n_cover, const uint32_t* cigar, const uint8_t* seqs, const uint8_t* ml,
-    const MkpFusedDesc* fdesc, const MkpRunParams* prm, const uint32_t* slot_pos, const MkpSlotEnt* slot_ent, uint8_t* cov, MkpVisit* visits,
-    MkpEvent* events, MkpReadOut* readout) {
-  if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, cigar, cigar16, seqs, call_plane, base_plane, ml, fdesc, *prm,
-      slot_ent, cov, visits, readout);
-  if (n_cover) hipLaunchKernelGGL(mkp_cover_reads, dim3((n_cover + 3u) / 4u), dim3(256), 0, st, hdrs, n_cover, cover_ids, cigar, seqs, slot_pos, cov,
-      visits, events, readout);
+    const MkpShardArrays& sh, const uint32_t* cover_ids, uint32_t n_cover, const MkpFusedDesc* fdesc, const MkpRunParams* prm,
+    const uint32_t* slot_pos, const MkpSlotEnt* slot_ent, uint8_t* cov, MkpVisit* visits) {
+  if (n_fused) hipLaunchKernelGGL(mkp_decode_slots, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, sh.cigar, sh.cigar16, sh.seq, call_plane,
+      base_plane, sh.ml, fdesc, *prm, slot_ent, cov, visits, sh.readout);
+  if (n_cover) hipLaunchKernelGGL(mkp_cover_reads, dim3((n_cover + 3u) / 4u), dim3(256), 0, st, sh.hdr, n_cover, cover_ids, sh.cigar, sh.seq, slot_pos, cov,
+      visits, sh.events, sh.readout);
   return hipGetLastError();
 }
 // the call plane and the base plane of the fused reads (once per resident shard; it also marks the work records whose delta list runs past its base
 // and those with a base that is not A/C/G/T, and adds the SEQ bytes the decoder reads of the latter to *seqn_bytes)
-extern "C" hipError_t mkp_launch_call_plane(hipStream_t st, MkpWork* work, uint32_t n_fused, const uint8_t* seqs, const uint32_t* ranks,
-    const MkpFusedDesc* fdesc, MkpCallEnt* call_plane, MkpBaseEnt* base_plane, unsigned long long* seqn_bytes) {
-  if (n_fused) hipLaunchKernelGGL(mkp_call_plane, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, seqs, ranks, fdesc, call_plane, base_plane,
-      seqn_bytes);
+extern "C" hipError_t mkp_launch_call_plane(hipStream_t st, MkpWork* work, uint32_t n_fused, const MkpShardArrays& sh, const MkpFusedDesc* fdesc,
+    MkpCallEnt* call_plane, MkpBaseEnt* base_plane, unsigned long long* seqn_bytes) {
+  if (n_fused) hipLaunchKernelGGL(mkp_call_plane, dim3((n_fused + 3u) / 4u), dim3(256), 0, st, work, n_fused, sh.seq, sh.ranks, fdesc, call_plane,
+      base_plane, seqn_bytes);
   return hipGetLastError();
 }
 
-extern "C" hipError_t mkp_launch_dup_restore(hipStream_t st, MkpReadHdr* hdrs, const MkpDupCons* cons, uint32_t n) {
-  if (n) hipLaunchKernelGGL(mkp_dup_restore, dim3((n + 63u) / 64u), dim3(64), 0, st, hdrs, cons, n);
+extern "C" hipError_t mkp_launch_dup_restore(hipStream_t st, const MkpShardArrays& sh, const MkpDupCons* cons, uint32_t n) {
+  if (n) hipLaunchKernelGGL(mkp_dup_restore, dim3((n + 63u) / 64u), dim3(64), 0, st, sh.hdr, cons, n);
   return hipGetLastError();
 }
-extern "C" hipError_t mkp_launch_dup_events(hipStream_t st, MkpReadHdr* hdrs, const uint32_t* cigar, const uint8_t* seqs, MkpEvent* events,
-    MkpReadOut* readout, MkpDupCons* cons, const MkpDupSeg* segs,
-                                            uint32_t n, uint32_t* dev_err) {
+extern "C" hipError_t mkp_launch_dup_events(hipStream_t st, const MkpShardArrays& sh, MkpDupCons* cons, const MkpDupSeg* segs, uint32_t n,
+    uint32_t* dev_err) {
   if (!n) return hipSuccess;
-  hipLaunchKernelGGL(mkp_dup_events, dim3(n), dim3(64), 0, st, hdrs, cigar, seqs, events, readout, cons, segs, n, dev_err);
-  hipLaunchKernelGGL(mkp_dup_apply, dim3((n + 63u) / 64u), dim3(64), 0, st, hdrs, readout, cons, n);
+  hipLaunchKernelGGL(mkp_dup_events, dim3(n), dim3(64), 0, st, sh.hdr, sh.cigar, sh.seq, sh.events, sh.readout, cons, segs, n, dev_err);
+  hipLaunchKernelGGL(mkp_dup_apply, dim3((n + 63u) / 64u), dim3(64), 0, st, sh.hdr, sh.readout, cons, n);
   return hipGetLastError();
 }
 

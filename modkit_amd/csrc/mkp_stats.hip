@@ -16,6 +16,7 @@
 // one, the first counted row of a code claims a free entry with a compare-and-swap (order does not matter, the host sorts): resolve_slot
 // of mkp_dev_codeslots.hpp, which also holds the two searches of the bounds kernel; both are shared with mkp_localize.hip.
 #include "mkp_dev_codeslots.hpp"
+#include "mkp_launch.h"
 
 namespace {
 
@@ -108,7 +109,8 @@ __global__ __launch_bounds__(256) void mkp_stats_reduce(const uint32_t* __restri
 
 }  // namespace
 
-// ev (may be NULL): three events recorded in front of the bounds kernel, in front of the reduce kernel and behind it
+// host-side launcher (declared in mkp_launch.h).  ev (may be NULL): three events recorded in front of the bounds kernel, in front of the reduce
+// kernel and behind it
 extern "C" hipError_t mkp_launch_region_stats(hipStream_t st, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
     const uint32_t* n_mod, uint32_t n_rows, const MkpStatsRegion* regions, uint32_t n_regions, uint32_t* row_lo, uint32_t* row_hi, uint32_t* n_chunks,
     unsigned long long* off, unsigned long long* total, unsigned long long* out, uint32_t* seen, uint32_t* codes, uint32_t* err,
