@@ -27,7 +27,7 @@
 #define MKP_ATOMIC_ADD64(p, v) atomicAdd((p), (unsigned long long)(v))
 #endif
 
-// error bits of one ingest (host: DevIngest::check turns them into the Error the host path would throw)
+// error bits of one ingest (host: ingest_throw_error_bits, mkp_ingest_stages.hpp, turns them into the Error the host path would throw)
 #define MKP_IE_CORRUPT 1u        // "corrupt BAM record" (block_size < 32, fields longer than the record, ids / positions out of range)
 #define MKP_IE_TRUNCATED 2u      // a record runs past the inflated window
 #define MKP_IE_CHAIN 4u          // a record chain does not land on the next entry point (index does not match the file)

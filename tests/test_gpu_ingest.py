@@ -175,3 +175,67 @@ def test_window_that_outgrows_its_buffer_is_inflated_again(oracle_bin, tmp_path)
             assert (L.mkp_internal_ingest_staged() > staged) == (not overflow), cap
     finally:
         L.mkp_internal_ingest_tune(0, 0, 0)
+
+
+HOST_TABLE_FLAGS = [[], ["--cpg", "--ref", "{fa}"], ["--include-bed", "{bed}"], ["--shard-bp", "3000"]]
+
+
+@pytest.mark.parametrize("fi", range(len(HOST_TABLE_FLAGS)))
+def test_host_block_table_knob_gives_the_same_rows(tmp_path, fi):
+    """MKP_HOST_BLOCK_TABLE=1 (README's A/B knob): the host walks the BGZF headers beside the upload and the whole window is inflated in one
+    launch.  Same bytes as the default device run and as the host ingest; it is still the device ingest that ran.  (The knob is read once per
+    process: the CLI is one.)"""
+    bam, fa, bed = Fuzz(57 + fi, n_reads=500, index=True).write(str(tmp_path / "fz"), bed=True)
+    flags = [f.format(fa=fa, bed=bed) for f in HOST_TABLE_FLAGS[fi]]
+    dev, host, _ = both(tmp_path, "pileup", bam, flags)
+    assert dev == host and len(dev) > 0
+    out = str(tmp_path / "knob.bed")
+    p = cli(["pileup", bam, out] + flags + ["--stats"], {"MKP_HOST_BLOCK_TABLE": "1"})
+    assert p.returncode == 0, p.stderr[-1500:]
+    assert "device ingest:" in p.stderr
+    assert open(out, "rb").read() == dev
+    # and it is the host-table branch that ran: the trace of the staged path has a "stages issued" lap, the host-table path has none
+    laps = {}
+    for knob in ("0", "1"):
+        p = cli(["pileup", bam, str(tmp_path / "t.bed")] + flags, {"MKP_HOST_BLOCK_TABLE": knob, "MKP_TRACE_PLAN": "1"})
+        assert p.returncode == 0, p.stderr[-1500:]
+        laps[knob] = [ln.split("laps:")[1] for ln in p.stderr.splitlines() if ln.startswith("[mkpileup ingest]")]
+        assert laps[knob], p.stderr[-1500:]
+    assert all("stages issued" in ln for ln in laps["0"]) and not any("stages issued" in ln for ln in laps["1"])
+    assert all("count+sync" in ln for ln in laps["1"])
+
+
+def test_many_stages_and_several_windows(tmp_path):
+    """16 KiB pieces, one round per stage: a few-MB BAM goes through four stages and more, as one window and as the three windows of a
+    fetch made of separated BED spans (with -i 5000 every span is a reference record of its own: under the default interval the three
+    would be joined into one record, fetched as one window).  Rows equal the host ingest's; the staged inflate stands (nothing is
+    inflated again)."""
+    import ctypes
+    bam, fa = gen(tmp_path, "st", [("c1", 200000)], 3000, ["--mean-len", "3000"])
+    assert os.path.getsize(bam) > 4 * 16 * 16384
+    bed = str(tmp_path / "spans.bed")
+    open(bed, "w").write("c1\t10000\t30000\nc1\t80000\t100000\nc1\t150000\t170000\n")
+    L = modkit_amd.lib()
+    L.mkp_internal_ingest_tune.argtypes = [ctypes.c_uint64] * 3
+    L.mkp_internal_ingest_tune.restype = None
+    L.mkp_internal_ingest_reinflated.restype = ctypes.c_uint64
+    L.mkp_internal_ingest_staged.restype = ctypes.c_uint64
+    for k, flags in enumerate(([], ["--include-bed", bed, "-i", "5000"])):
+        host = str(tmp_path / ("host%d.bed" % k))
+        modkit_amd.pileup([bam, host] + flags + ["--host-ingest"])
+        want = open(host, "rb").read()
+        assert len(want) > 10000
+        if flags:
+            trace = cli(["pileup", bam, str(tmp_path / "t.bed")] + flags, {"MKP_TRACE_PLAN": "1"}).stderr
+            m = re.findall(r"\[mkpileup ingest\].* in (\d+) window\(s\)", trace)
+            assert m and all(int(n) > 1 for n in m), trace[-1500:]
+        try:
+            before, staged = L.mkp_internal_ingest_reinflated(), L.mkp_internal_ingest_staged()
+            L.mkp_internal_ingest_tune(16384, 1, 0)
+            out = str(tmp_path / ("dev%d.bed" % k))
+            modkit_amd.pileup([bam, out] + flags)
+            assert open(out, "rb").read() == want
+            assert L.mkp_internal_ingest_staged() > staged
+            assert L.mkp_internal_ingest_reinflated() == before
+        finally:
+            L.mkp_internal_ingest_tune(0, 0, 0)

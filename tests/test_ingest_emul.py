@@ -2,7 +2,10 @@
 tokeniser, packing) compiled for the host and run thread by thread over whole BAMs by tests/ingest_emul.cpp, against the host path it
 replaces (mkp_bam.hpp's record index, Packer::add): record offsets, kept / supplementary classification per region, headers, CIGAR
 words and chunk prefixes, SEQ bytes, per-tag rank lists and ML bytes, name and layout-key hashes, the same-list and probability-sum
-flags — and the same refusals.  The sliced CRC-32 join of mkp_crc32_blocks is checked against zlib over the same streams."""
+flags — and the same refusals.  The sliced CRC-32 join of mkp_crc32_blocks is checked against zlib over the same streams.
+
+The host-only steps of the ingest (modkit_amd/csrc/mkp_ingest_stages.hpp: upload layout, chain table, stage cut, block lists, error mapping,
+layout interning) are the product's own functions here, driven by the emulated kernels or by hand-written input."""
 import os
 import struct
 import subprocess
@@ -44,6 +47,18 @@ def test_fuzzed_bams(emul, tmp_path, profile):
         bam, _, _ = Fuzz(seed, profile=profile, n_reads=300, tie_rate=0.2, weird_rate=0.25).write(str(tmp_path / ("fz%d" % seed)))
         out = run(emul, bam, 5)
         assert "compared=0" not in out
+        # the product's layout interning over the emulated digest: every packed record with tags got the host packer's key string
+        assert int(out.split("interned=")[1].split()[0]) > 0
+
+
+def test_forged_key_hash_is_refused(emul, tmp_path):
+    """Two records of different MM header structures under one 64-bit key hash (the harness hands ingest_intern_layouts a digest in which
+    the first record's hash is the second's): the "disagree" / "share a 64-bit key hash" error, never the wrong caller tables.  It is the
+    "disagree on a record's MM header structure" throw that this reaches (the forged record is interned first and its own key hashes to
+    something else); "share a 64-bit key hash" needs two real keys with one FNV-64 value and is reached by no forged digest."""
+    bam, _, _ = Fuzz(3, profile="mixed", n_reads=300, tie_rate=0.2, weird_rate=0.25).write(str(tmp_path / "fz"))
+    out = run(emul, bam, 5)
+    assert int(out.split("forged=")[1].split()[0]) > 0
 
 
 def test_generated_long_reads(emul, tmp_path):
@@ -103,7 +118,8 @@ def test_handwritten_mm_strings(emul, tmp_path):
 @pytest.mark.parametrize("mm", sorted(THROWERS))
 def test_refusals_match_the_host_packer(emul, tmp_path, mm):
     """Five codes in one tag, nine tags, a non-ASCII code: the host packer throws MKP_E_UNSUPPORTED; the device sets the matching error bit
-    (checked inside the harness: a host throw without the bit, or a bit without the throw, fails)."""
+    (checked inside the harness: a host throw without the bit, or a bit without the throw, fails), and the product's mapping of that bit
+    (ingest_throw_error_bits) gives the host's status and words."""
     bam = str(tmp_path / "t.bam")
     _mm_bam(bam, ["C+m?,1,2;", mm, "C+h?,3;"], "fit", 0)
     run(emul, bam, 2)
@@ -112,11 +128,13 @@ def test_refusals_match_the_host_packer(emul, tmp_path, mm):
     run(emul, bam, 1)
 
 
-def run_plan(emul, bam):
-    p = subprocess.run([emul, "--plan", bam], capture_output=True, text=True, timeout=600)
+def run_plan(emul, bam, piece=None, stage_rounds=None):
+    """the plan checks, the block table built in stages of `stage_rounds` upload rounds of sixteen `piece`-byte pieces (default: the
+    product's 1 MiB pieces, one stage); returns (stdout, its key=value figures)"""
+    p = subprocess.run([emul, "--plan", bam] + ([str(piece), str(stage_rounds)] if piece else []), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     assert p.stdout.startswith("ok"), p.stdout
-    return p.stdout
+    return p.stdout, {k: int(v) for k, v in (w.split("=") for w in p.stdout.split() if "=" in w)}
 
 
 def test_index_plans_select_the_fetch_records(emul, tmp_path):
@@ -124,11 +142,66 @@ def test_index_plans_select_the_fetch_records(emul, tmp_path):
     region test == BamSource::fetch, for whole contigs and sub-regions."""
     for f in sorted(os.listdir(FIX)):
         if f.endswith(".bam") and os.path.exists(os.path.join(FIX, f + ".bai")):
-            run_plan(emul, os.path.join(FIX, f))
+            _, fig = run_plan(emul, os.path.join(FIX, f))
+            assert fig["boundaries"] == 0 and fig["stages"] > 0      # one round, one stage per window
     from test_host_ingest import gen
     bam, _ = gen(tmp_path, "g", [("c1", 900000), ("c2", 250000)], 4000, ["--mean-len", "6000"])
-    out = run_plan(emul, bam)
+    out, fig = run_plan(emul, bam)
     assert int(out.split("segments=")[1]) > 50      # the linear index supplied entry points
+    # The staged block table (the product's upload layout, stage cut and block lists around the emulated chain kernels; what has not been
+    # uploaded when a stage is cut holds filler) must be the host walk's plan field by field — checked inside the harness — with 1 MiB stages
+    # (64 KiB pieces, one round each) and with 192 KiB ones (4 KiB pieces, three rounds).  In both, every round boundary lies inside a chain.
+    windows = fig["stages"]
+    for piece, rounds in ((65536, 1), (4096, 3)):
+        _, fig = run_plan(emul, bam, piece, rounds)
+        assert fig["stages"] > 2 * windows and fig["boundaries"] > 0 and fig["inside"] == fig["boundaries"], fig
+    # A stage that ends on no chain needs a chain longer than the stage: this file has none at 192 KiB, so the pieces shrink to 1 KiB
+    # (48 KiB stages).  A stage WITH chains but without a block does not exist for a BAM whose index matches it: a
+    # chain begins at a block start at or before its chunk's end block and lies wholly in the uploaded range, so it holds that block
+    # (no_block == 0 at every piece size down to 64 bytes, and for every fixture); the bookkeeping of such a stage is checked on a
+    # hand-written table in test_upload_layout_and_stage_bookkeeping_by_brute_force.
+    _, fig = run_plan(emul, bam, 1024, 3)
+    assert fig["no_chain"] >= 1 and fig["inside"] >= 1 and fig["no_block"] == 0, fig
     for seed in (0, 1):
         bam, _, _ = Fuzz(seed, contigs=(("ctgA", 90000), ("ctgB", 20000)), n_reads=900, mean_len=2500, index=True).write(str(tmp_path / ("fz%d" % seed)))
         run_plan(emul, bam)
+        run_plan(emul, bam, 4096, 1)
+
+
+def test_upload_layout_and_stage_bookkeeping_by_brute_force(emul):
+    """UploadLayout over three hand-written range lists (one range shorter than a piece; one of exactly a round of pieces; two ranges, the
+    first ending mid-round): every byte of every range in exactly one piece, z_off against zbase, round ends ascending up to zbytes, and the
+    copies of every round carried out on a model of the staging half — they must reproduce the window byte for byte, write nothing twice and
+    no padding, and merge pieces only where they are back to back in staging and in the window.  Then ingest_stage_cut on a hand-written
+    chain list and ingest_chain_blocks on four stages, one of them without a chain and one with two chains and no block."""
+    p = subprocess.run([emul, "--layout"], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert p.stdout.startswith("ok layout") and "merged=0" not in p.stdout, p.stdout
+
+
+# status and message of every refusal, as mkp_internal_ingest_run worded them before the mapping moved to mkp_ingest_stages.hpp
+ERROR_BITS = {
+    0: (0, "-"),
+    1: (-2, "corrupt BAM record"),
+    2: (-2, "truncated BAM record at the end of {path}"),
+    4: (-2, "the BAM index does not match the file (a record chain misses an indexed record start): {path}.bai"),
+    8: (-3, "shard exceeds 4 GiB of packed bases; use smaller shards"),
+    16: (-1, "CIGAR query length does not match SEQ length"),
+    32: (-3, "a read or its alignment spans 2^26 bases or more (the depth walk packs query offsets in 27 bits)"),
+    64: (-3, "non-ASCII mod code"),
+    128: (-3, "more than 4 mod codes in one MM tag"),
+    256: (-3, "more than 8 MM tags in one read"),
+    512: (-3, "shard exceeds 4 GiB of packed bases; use smaller shards"),
+    3: (-2, "truncated BAM record at the end of {path}"),       # TRUNCATED | CORRUPT: the truncation is what gets reported
+}
+
+
+def test_error_bits_map_to_the_host_path_errors(emul):
+    path = "/data/run 7/reads.bam"
+    p = subprocess.run([emul, "--errors", path], capture_output=True, text=True, timeout=60)
+    assert p.returncode == 0, p.stderr[-2000:]
+    got = {}
+    for ln in p.stdout.splitlines():
+        bits, status, msg = ln.split(" ", 2)
+        got[int(bits)] = (int(status), msg)
+    assert got == {b: (st, m.format(path=path)) for b, (st, m) in ERROR_BITS.items()}
