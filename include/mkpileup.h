@@ -160,7 +160,7 @@ const char* mkp_version(void);
  * revision 2; round 6 = 3).  The library writes whole structs of its own revision, so a caller built against another header must not
  * hand it its structs: compare once at start-up —  `mkp_abi_version() == MKP_ABI_VERSION && mkp_run_report_size() == sizeof(mkp_run_report)`
  * (the Rust binding asserts the same on its #[repr(C)] mirror). */
-#define MKP_ABI_VERSION 3u
+#define MKP_ABI_VERSION 4u
 uint32_t mkp_abi_version(void);
 size_t mkp_run_report_size(void);
 /* Threads of the library's host pool (BGZF inflate, packing, planning, text): the CPUs this process may use — affinity mask and
@@ -230,7 +230,7 @@ int mkp_process_region(mkp_ctx* ctx, const char* bam_path, const mkp_shard* shar
  * (the out.bed positional is still required, the file is not created); plus --localize <regions.bed> --localize-out <table.tsv>
  * [--localize-window N (2000)] [--localize-stranded same|opposite] [--localize-stranded-features +|-|.] [--localize-only]: `modkit localize`
  * over the run's rows (mkp_localize_* below; contig lengths from the BAM header), combinable with --region-stats; plus
- * --merge-bedmethyl <prior.bed> (repeatable): out.bed is `modkit bedmethyl merge` of the run's rows with the prior plain-text tables,
+ * --merge-bedmethyl <prior.bed> (repeatable): out.bed is `modkit bedmethyl merge` of the run's rows with the prior tables (plain text or bgzip),
  * joined on the device (mkp_merge_* below; contig lengths and order from the BAM header; the run's rows are not read back per shard). */
 int mkp_pileup_main(int argc, const char* const* argv, char* errbuf, size_t errbuf_len);
 
@@ -527,9 +527,20 @@ int mkp_host_localize_table(const mkp_localize_out* counts, const char* out_path
  *   mkp_merge_tile_rows     the rows between two tile cuts of the merge kernel (for tests that put a run of equal keys on a tile edge).
  * The written line follows to_line (src/tabix.rs:33-74): the bare code as the name, score = column 10 = the summed valid_coverage,
  * percent = (n_mod as f32 / n_valid as f32) * 100 with {:.2}, `NaN` when n_valid is 0.
- * Host-only half: mkp_host_read_bedmethyl reads a PLAIN-TEXT bedMethyl (tabs and / or blanks; '#' lines skipped) into runs of lines on
- * one contig; a line that does not parse is MKP_E_IO with the line named (the reference drops its 100 kb chunk silently), a gzip / bgzip
- * file MKP_E_UNSUPPORTED.  mkp_bedmethyl_file_rows fills the eleven columns of run `run` (arrays owned by the file object).
+ * Input files are plain text or bgzip (BGZF) compressed, as the reference takes them (tabs and / or blanks; '#' lines skipped; the .tbi is
+ * neither needed nor read).  A line that does not parse is MKP_E_IO with the line named (the reference drops its 100 kb chunk silently); a
+ * truncated, damaged or CRC-failing BGZF block is MKP_E_IO with the block named; a gzip stream without BGZF blocks is MKP_E_UNSUPPORTED.
+ *   mkp_merge_add_file      a whole bedMethyl file through the device reader (mkp_bedmethyl.hip): compressed blocks (or the plain bytes) go
+ *                           up, are inflated, CRC-checked, cut into lines and parsed in HBM, and every run of lines on one contig is joined
+ *                           where it lies; neither text nor rows visit the host.  contig_names[tid] = the names of the sizes table given to
+ *                           mkp_merge_begin: rows of a chrom not among them, or at pos >= the contig's length, are dropped and counted.
+ *                           pos must not descend inside a run of lines on one contig (MKP_E_INVALID, the line named).  The file is read in
+ *                           pieces of at most MKP_BEDMETHYL_PIECE_KB KiB of text (default 131072, least 64); a line that does not fit one is
+ *                           MKP_E_UNSUPPORTED (the host reader has no such limit).  *n_rows (may be NULL) = the file's rows.
+ *   mkp_bedmethyl_read_device  the same reader, the rows copied back into a mkp_bedmethyl_file (a run cut by a piece seam comes back as one).
+ *   mkp_bedmethyl_chunk_bytes  the bytes of text a workgroup of the reader's line kernels takes (for tests that put line ends on its edges).
+ * Host-only half: mkp_host_read_bedmethyl reads the same files on the CPU (BGZF through the host's own inflate, CRC checked) into runs of
+ * lines on one contig.  mkp_bedmethyl_file_rows fills the eleven columns of run `run` (arrays owned by the file object).
  * mkp_bedmethyl_merge_main = `mkpileup bedmethyl merge a.bed b.bed [..] -g sizes.tsv -o out.bed [--force] [--bgzf] [--device N] [--stats]`:
  * contigs come out in the order of the sizes file, those without a row are not written; *n_written / *n_dropped may be NULL. */
 int mkp_merge_begin(mkp_ctx* ctx, const uint64_t* contig_len_by_tid, uint32_t n_contigs);
@@ -543,6 +554,9 @@ uint32_t mkp_bedmethyl_file_runs(const mkp_bedmethyl_file* file);
 const char* mkp_bedmethyl_file_chrom(const mkp_bedmethyl_file* file, uint32_t run);
 int mkp_bedmethyl_file_rows(const mkp_bedmethyl_file* file, uint32_t run, mkp_rows* out);
 void mkp_bedmethyl_file_free(mkp_bedmethyl_file* file);
+int mkp_merge_add_file(mkp_ctx* ctx, const char* path, const char* const* contig_names, uint32_t n_names, uint64_t* n_rows);
+int mkp_bedmethyl_read_device(mkp_ctx* ctx, const char* path, mkp_bedmethyl_file** out);
+uint32_t mkp_bedmethyl_chunk_bytes(void);
 int mkp_bedmethyl_merge_main(int argc, const char* const* argv, uint64_t* n_written, uint64_t* n_dropped, char* errbuf, size_t errbuf_len);
 
 /* ---- BGZF inflate on the device as a call of its own.  On the pileup path the same kernels run inside the device ingest

@@ -127,6 +127,10 @@ def lib():
             L.mkp_bedmethyl_file_rows.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
             L.mkp_bedmethyl_file_free.argtypes = [ctypes.c_void_p]
             L.mkp_bedmethyl_file_free.restype = None
+            L.mkp_merge_add_file.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, u64p]
+            L.mkp_bedmethyl_read_device.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(ctypes.c_void_p)]
+            L.mkp_bedmethyl_chunk_bytes.argtypes = []
+            L.mkp_bedmethyl_chunk_bytes.restype = ctypes.c_uint32
             L.mkp_bedmethyl_merge_main.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), u64p, u64p, ctypes.c_char_p, ctypes.c_size_t]
         # the structs this binding allocates mirror ONE revision of include/mkpileup.h: a library of another revision would write past them
         if os.environ.get("MKP_LIB_PATH") and not hasattr(L, "mkp_abi_version"):
@@ -141,7 +145,7 @@ def lib():
     return _lib
 
 
-ABI_VERSION = 3   # MKP_ABI_VERSION of include/mkpileup.h
+ABI_VERSION = 4   # MKP_ABI_VERSION of include/mkpileup.h
 READ_WIDE_CIGAR = 32   # MKP_READ_WIDE_CIGAR
 
 
@@ -159,7 +163,8 @@ EXPORTS = ["mkp_ctx_create", "mkp_ctx_destroy", "mkp_last_error", "mkp_version",
            "mkp_host_parse_localize_regions", "mkp_host_parse_genome_sizes", "mkp_genome_sizes_size", "mkp_genome_sizes_name",
            "mkp_genome_sizes_free", "mkp_host_localize_table",
            "mkp_merge_begin", "mkp_merge_add_rows", "mkp_merge_add_resident", "mkp_merge_get", "mkp_merge_tile_rows", "mkp_host_read_bedmethyl",
-           "mkp_bedmethyl_file_runs", "mkp_bedmethyl_file_chrom", "mkp_bedmethyl_file_rows", "mkp_bedmethyl_file_free", "mkp_bedmethyl_merge_main"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
+           "mkp_bedmethyl_file_runs", "mkp_bedmethyl_file_chrom", "mkp_bedmethyl_file_rows", "mkp_bedmethyl_file_free", "mkp_bedmethyl_merge_main",
+           "mkp_merge_add_file", "mkp_bedmethyl_read_device", "mkp_bedmethyl_chunk_bytes"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
 
 
 def pileup(argv):
@@ -188,8 +193,10 @@ def pileup_hemi(argv):
 
 def bedmethyl_merge(argv):
     """`modkit bedmethyl merge` (EntryMergeBedMethyl::run, src/bedmethyl_util/subcommands.rs:198-371) on the device: argv = [a.bed, b.bed, ...,
-    "-g", sizes.tsv, "-o", out.bed, "--force", "--bgzf"]; the inputs are PLAIN-TEXT bedMethyl tables.  Returns (rows written, rows dropped):
-    a row is dropped when its contig is not in the sizes file or its start is not below the contig's length."""
+    "-g", sizes.tsv, "-o", out.bed, "--force", "--bgzf"]; the inputs are bedMethyl tables, plain text or bgzip compressed (its own --bgzf output
+    included; a .tbi is not needed), each read by the device reader (Context.merge_add_file; MKP_HOST_BEDMETHYL=1: by the host reader).
+    Returns (rows written, rows dropped): a row is dropped when its contig is not in the sizes file or its start is not below the contig's
+    length."""
     L = lib()
     args = [str(a).encode() for a in argv]
     arr = (ctypes.c_char_p * max(1, len(args)))(*args)
@@ -355,15 +362,8 @@ def merge_tile_rows():
     return int(lib().mkp_merge_tile_rows())
 
 
-def read_bedmethyl_runs(path):
-    """mkp_host_read_bedmethyl: a PLAIN-TEXT bedMethyl (tabs and / or blanks, '#' lines skipped, the code = the name up to its first comma,
-    n_valid = the score column) as [(chrom, rows dict with all eleven columns), ...], one entry per run of lines on one contig, file order."""
-    L = lib()
-    h = ctypes.c_void_p()
-    err = ctypes.create_string_buffer(2048)
-    rc = L.mkp_host_read_bedmethyl(str(path).encode(), ctypes.byref(h), err, len(err))
-    if rc != MKP_OK:
-        raise MkpError(rc, err.value.decode(errors="replace"))
+def _bedmethyl_file_runs(L, h):
+    """the runs of a mkp_bedmethyl_file handle as [(chrom, rows dict), ...]; frees the handle"""
     try:
         out = []
         for k in range(L.mkp_bedmethyl_file_runs(h)):
@@ -374,6 +374,25 @@ def read_bedmethyl_runs(path):
         return out
     finally:
         L.mkp_bedmethyl_file_free(h)
+
+
+def read_bedmethyl_runs(path):
+    """mkp_host_read_bedmethyl: a bedMethyl file, plain text or bgzip compressed (inflated by the host's own decoder, every block's CRC-32
+    checked; tabs and / or blanks, '#' lines skipped, the code = the name up to its first comma, n_valid = the score column) as
+    [(chrom, rows dict with all eleven columns), ...], one entry per run of lines on one contig, file order.  No device is used:
+    Context.read_bedmethyl_runs reads the same files on the GPU."""
+    L = lib()
+    h = ctypes.c_void_p()
+    err = ctypes.create_string_buffer(2048)
+    rc = L.mkp_host_read_bedmethyl(str(path).encode(), ctypes.byref(h), err, len(err))
+    if rc != MKP_OK:
+        raise MkpError(rc, err.value.decode(errors="replace"))
+    return _bedmethyl_file_runs(L, h)
+
+
+def bedmethyl_chunk_bytes():
+    """mkp_bedmethyl_chunk_bytes: the bytes of text a workgroup of the device bedMethyl reader's line kernels takes."""
+    return int(lib().mkp_bedmethyl_chunk_bytes())
 
 
 def genome_sizes(path):
@@ -716,6 +735,23 @@ class Context:
         (what read_bedmethyl / read_bedmethyl_runs / rows_to_numpy give); joined into the contig's table on the device."""
         r, _keep = _rows_struct(rows, all_columns=True)
         self._check(self.L.mkp_merge_add_rows(self.h, int(tid), ctypes.byref(r)))
+
+    def merge_add_file(self, path, names):
+        """mkp_merge_add_file: a whole bedMethyl file (plain text or bgzip) read on the device and joined run by run where its rows lie in
+        HBM; names[tid] = the contig names of the table given to merge_begin (rows of another chrom are dropped and counted).  Returns the
+        file's rows."""
+        enc = [str(n).encode() for n in names]
+        arr = (ctypes.c_char_p * max(1, len(enc)))(*enc)
+        n = ctypes.c_uint64(0)
+        self._check(self.L.mkp_merge_add_file(self.h, str(path).encode(), arr, len(enc), ctypes.byref(n)))
+        return int(n.value)
+
+    def read_bedmethyl_runs(self, path):
+        """mkp_bedmethyl_read_device: what the module-level read_bedmethyl_runs returns, read by the device reader (inflate, line cut and
+        parse on the GPU) and copied back."""
+        h = ctypes.c_void_p()
+        self._check(self.L.mkp_bedmethyl_read_device(self.h, str(path).encode(), ctypes.byref(h)))
+        return _bedmethyl_file_runs(self.L, h)
 
     def merge_add_resident(self):
         """mkp_merge_add_resident: join the rows the last shard run left in HBM into their contig's table."""

@@ -1,12 +1,13 @@
 // libmkpileup C ABI (include/mkpileup.h): the context, a shard's plan and residency in HBM (make_resident), the pileup pass over it
-// (run_kernels) and its row read-back, BGZF inflate, threshold sampling / summary / extract, region statistics, localize and bedmethyl
-// merge.  Every kernel is reached through a launcher of mkp_launch.h.  No CPU fallback lives here: rows and counts come from the HIP
+// (run_kernels) and its row read-back, BGZF inflate, threshold sampling / summary / extract, region statistics, localize, bedmethyl
+// merge and the device bedMethyl reader.  Every kernel is reached through a launcher of mkp_launch.h.  No CPU fallback lives here: rows and counts come from the HIP
 // kernels only; without a gfx950 device every compute entry point fails with MKP_E_DEVICE.
 #include <atomic>
 #include <climits>
 #include <memory>
 #include <thread>
 
+#include "mkp_bedmethyl_in.hpp"
 #include "mkp_ctx.hpp"
 #include "mkp_ingest_host.hpp"
 #include "mkp_launch.h"
@@ -487,6 +488,10 @@ void mkp_ctx_destroy(mkp_ctx* c) {
                         &c->rstats.d_cnt, &c->rstats.d_off, &c->loc.d_tab}) b->release();
   for (auto& kv : c->merge.contigs) for (DevBuf& b : kv.second.buf) b.release();
   for (DevBuf* b : {&c->merge.d_stage, &c->merge.d_cuts, &c->merge.d_counts, &c->merge.d_offsets}) b->release();
+  { mkp_ctx::BedIn& B = c->bedin;
+    for (DevBuf* b : {&B.d_zin, &B.d_text[0], &B.d_text[1], &B.d_blk, &B.d_stat, &B.d_cnt, &B.d_words, &B.d_lines, &B.d_rows, &B.d_runs, &B.d_names})
+      b->release();
+    for (auto& e : B.ev) if (e) (void)hipEventDestroy(e); }
   for (mkp_ctx::RowTable* t : {static_cast<mkp_ctx::RowTable*>(&c->rstats), static_cast<mkp_ctx::RowTable*>(&c->loc),
       static_cast<mkp_ctx::RowTable*>(&c->merge)}) {
     for (DevBuf* b : {&t->d_regions, &t->d_misc, &t->d_lo, &t->d_hi, &t->d_rows}) b->release();
@@ -1721,6 +1726,260 @@ int mkp_merge_get(mkp_ctx* c, int32_t tid, mkp_rows* out, uint64_t* n_dropped) {
     out->motif_idx = C.h_motif.data(); out->n_valid = C.h_col[3].data(); out->n_mod = C.h_col[4].data(); out->n_canonical = C.h_col[5].data();
     out->n_other = C.h_col[6].data(); out->n_delete = C.h_col[7].data(); out->n_fail = C.h_col[8].data(); out->n_diff = C.h_col[9].data();
     out->n_nocall = C.h_col[10].data();
+  });
+}
+
+}  // extern "C"
+
+// ---- the device bedMethyl reader (mkp_bedmethyl.hip; mkp_merge_add_file and mkp_bedmethyl_read_device of include/mkpileup.h): a plain or
+// BGZF bedMethyl file becomes row columns in HBM piece by piece; compressed blocks (or the plain bytes) go up, the text and the rows stay there
+namespace {
+
+struct PinnedFile {   // the whole file in page-locked memory (16 readable bytes behind it)
+  uint8_t* p = nullptr; size_t n = 0;
+  ~PinnedFile() { if (p) (void)hipHostFree(p); }
+  void read(const std::string& path) {
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) throw Error(MKP_E_IO, "failed to open bedMethyl " + path);
+    struct Close { FILE* f; ~Close() { fclose(f); } } close{f};
+    if (fseeko(f, 0, SEEK_END) != 0) throw Error(MKP_E_IO, "failed to read bedMethyl " + path);
+    const off_t size = ftello(f);
+    if (size < 0 || fseeko(f, 0, SEEK_SET) != 0) throw Error(MKP_E_IO, "failed to read bedMethyl " + path);
+    if (hipHostMalloc(reinterpret_cast<void**>(&p), (size_t)size + 16, hipHostMallocDefault) != hipSuccess) { p = nullptr;
+      throw Error(MKP_E_NOMEM, "hipHostMalloc of " + std::to_string((size_t)size + 16) + " bytes for " + path + " failed"); }
+    while (n < (size_t)size) { const size_t got = fread(p + n, 1, (size_t)size - n, f); if (!got) break; n += got; }
+    if (n != (size_t)size) throw Error(MKP_E_IO, "failed to read bedMethyl " + path);
+    memset(p + n, 0, 16);
+  }
+};
+
+// MKP_BEDMETHYL_PIECE_KB: the text a piece holds at most (KiB; default 131072 = the ingest's 128 MiB stages; 64 .. 1048576)
+uint64_t bedin_piece_bytes() {
+  uint64_t kb = 131072;
+  if (const char* e = getenv("MKP_BEDMETHYL_PIECE_KB")) { char* end = nullptr; const unsigned long long v = strtoull(e, &end, 10);
+    if (end != e && *end == 0) kb = v; }
+  return std::min<uint64_t>(std::max<uint64_t>(kb, 64), 1048576) * 1024;
+}
+
+// What the device found in a piece, said by the host reader: text[0, limit) of the piece comes back and is read again.  A line that does not
+// parse throws the host reader's own message (line numbers count on from line_base); then a line too long for a piece, then a pos that
+// descends inside a contig run (across the seam too: last_chrom / last_pos, the row in front of the piece).  Nothing found: the two readers disagree.
+[[noreturn]] void bedin_fail(mkp_ctx* c, const uint8_t* d_text, uint32_t limit, uint64_t line_base, const std::string& path, uint32_t bits,
+    uint64_t err_off, uint64_t max_line, const std::string* last_chrom, uint32_t last_pos) {
+  std::vector<uint8_t> text(limit);
+  d2h_copy(text.data(), d_text, limit, c->stream);
+  mkp_bedmethyl_file f; std::vector<uint64_t> line_nos;
+  parse_bedmethyl_text(text.data(), text.size(), path, line_base, f, &line_nos);
+  if (bits & MKP_BEDIN_ERR_LONG) {
+    uint64_t line_no = line_base;
+    for (size_t p = 0; p < text.size();) { const uint8_t* nl = (const uint8_t*)memchr(text.data() + p, '\n', text.size() - p);
+      const size_t e = nl ? (size_t)(nl - text.data()) : text.size(); line_no++;
+      if (e - p > max_line && text[p] != '#') throw Error(MKP_E_UNSUPPORTED, "line " + std::to_string(line_no) + " of " + path + " is longer than "
+          + std::to_string(max_line) + " bytes: it does not fit a piece of the device reader (MKP_BEDMETHYL_PIECE_KB)");
+      p = e + 1; }
+  }
+  for (size_t k = 0; k < f.runs.size(); k++) {
+    const mkp_bedmethyl_file::Run& u = f.runs[k];
+    const bool goes_on = k == 0 && last_chrom && *last_chrom == u.chrom;
+    for (uint64_t i = u.first; i < u.first + u.n; i++) {
+      const bool first = i == u.first;
+      if (first && !goes_on) continue;
+      if (f.col[0][i] < (first ? last_pos : f.col[0][i - 1])) throw Error(MKP_E_INVALID, "line " + std::to_string(line_nos[i]) + " of " + path
+          + ": rows must be ascending in pos inside a run of lines on one contig (" + std::to_string(f.col[0][i]) + " follows "
+          + std::to_string(first ? last_pos : f.col[0][i - 1]) + " on " + u.chrom + ")");
+    }
+  }
+  throw Error(MKP_E_DEVICE, "device and host readers disagree on " + path + ": the device reader reports error bits " + std::to_string(bits)
+      + " at byte " + std::to_string(err_off) + " of the piece behind line " + std::to_string(line_base) + ", the host reader finds nothing wrong there");
+}
+
+float bedin_elapsed(hipEvent_t a, hipEvent_t b) { float ms = 0; hip_check(hipEventElapsedTime(&ms, a, b), "event"); return ms; }
+
+// The file at `path` through the device reader.  sink(chrom, rows, goes_on) takes every contig run of every piece in file order, its rows
+// on the device (the next piece overwrites them: sink is done with them when it returns); goes_on: the run continues the one handed over
+// last (a run cut by a piece seam).
+template <class Sink> void bedin_read_file(mkp_ctx* c, const std::string& path, Sink sink) {
+  mkp_ctx::BedIn& B = c->bedin;
+  hip_check(hipSetDevice(c->device), "hipSetDevice");
+  for (auto& e : B.ev) if (!e) hip_check(hipEventCreate(&e), "hipEventCreate");
+  auto t_read = std::chrono::steady_clock::now();
+  PinnedFile file; file.read(path);
+  const bool gz = is_gzip(file.p, file.n);
+  std::vector<BgzfBlk> blks; if (gz) blks = bgzf_walk(file.p, file.n, path);
+  uint64_t text_total = file.n;
+  if (gz) { text_total = 0; for (const BgzfBlk& b : blks) text_total += b.isize; }
+  B.ms[0] += ms_since(t_read);
+  const uint64_t P = bedin_piece_bytes(), max_line = P - 1;
+  // a BGZF piece takes whole blocks, at least one: up to 64 KiB more than P
+  const size_t text_cap = (size_t)(((std::min(P, text_total) + 65536u + MKP_BEDIN_CHUNK - 1) / MKP_BEDIN_CHUNK + 1) * MKP_BEDIN_CHUNK);
+  B.d_words.ensure(MKP_BEDIN_WORDS * 4);
+  uint32_t* words = B.d_words.as<uint32_t>();
+  auto too_long = [&](uint64_t line_base) { return Error(MKP_E_UNSUPPORTED, "line " + std::to_string(line_base + 1) + " of " + path + " is longer than "
+      + std::to_string(max_line) + " bytes: it does not fit a piece of the device reader (MKP_BEDMETHYL_PIECE_KB)"); };
+  // an empty block is checked here and never handed to the inflate kernel
+  auto skip_empty = [&](size_t& bi) { while (bi < blks.size() && !blks[bi].isize) { bgzf_inflate_block_host(file.p, blks[bi], bi, nullptr, path); bi++; } };
+
+  uint64_t pos = 0, line_base = 0; size_t bi = 0; uint32_t carry = 0; int cur = 0;
+  bool have_last = false; std::string last_chrom; uint32_t last_pos = 0;
+  skip_empty(bi);
+  for (bool final_piece = gz ? bi == blks.size() : file.n == 0; !final_piece || carry;) {
+    hip_check(hipStreamSynchronize(c->stream), "sync");   // the last piece's rows and text are done with
+    B.d_text[cur].ensure(text_cap);
+    uint8_t* text = B.d_text[cur].as<uint8_t>();
+    uint32_t n = carry; std::vector<MkpBgzfBlock> dev_blks; std::vector<size_t> blk_index; uint64_t z_lo = 0, z_hi = 0;
+    if (!gz) {
+      if (carry >= P) throw too_long(line_base);
+      const uint64_t take = std::min<uint64_t>(P - carry, file.n - pos);
+      hip_check(hipEventRecord(B.ev[0], c->stream), "event");
+      if (take) hip_check(hipMemcpyAsync(text + carry, file.p + pos, take, hipMemcpyHostToDevice, c->stream), "H2D");
+      hip_check(hipEventRecord(B.ev[1], c->stream), "event");
+      pos += take; n += (uint32_t)take; final_piece = pos == file.n;
+    } else {
+      if (carry > P) throw too_long(line_base);
+      z_lo = bi < blks.size() ? blks[bi].start : 0; z_hi = z_lo;
+      while (bi < blks.size() && (dev_blks.empty() || (uint64_t)n + blks[bi].isize <= P)) {
+        const BgzfBlk& b = blks[bi];
+        dev_blks.push_back({b.in_off - z_lo, (unsigned long long)n, b.in_len, b.isize}); blk_index.push_back(bi);
+        n += b.isize; z_hi = b.start + b.bsize; bi++;
+        skip_empty(bi);
+      }
+      final_piece = bi == blks.size();
+      if (!dev_blks.empty()) {
+        B.d_zin.ensure((size_t)(z_hi - z_lo) + 16); B.d_blk.ensure(dev_blks.size() * sizeof(MkpBgzfBlock)); B.d_stat.ensure(dev_blks.size() * 4);
+        h2d_copy(B.d_blk.p, dev_blks.data(), dev_blks.size() * sizeof(MkpBgzfBlock));
+      }
+      hip_check(hipEventRecord(B.ev[0], c->stream), "event");
+      if (!dev_blks.empty()) hip_check(hipMemcpyAsync(B.d_zin.p, file.p + z_lo, (size_t)(z_hi - z_lo), hipMemcpyHostToDevice, c->stream), "H2D");
+      hip_check(hipEventRecord(B.ev[1], c->stream), "event");
+      if (!dev_blks.empty()) {
+        hip_check(hipMemsetAsync(B.d_stat.p, 0xff, dev_blks.size() * 4, c->stream), "memset");
+        hip_check(mkp_launch_inflate_auto(c->stream, B.d_zin.as<uint8_t>(), B.d_blk.as<MkpBgzfBlock>(), (uint32_t)dev_blks.size(), text,
+            B.d_stat.as<uint32_t>()), "inflate launch");
+        hip_check(mkp_launch_crc32(c->stream, B.d_zin.as<uint8_t>(), B.d_blk.as<MkpBgzfBlock>(), (uint32_t)dev_blks.size(), text,
+            B.d_stat.as<uint32_t>()), "crc32 launch");
+      }
+    }
+    hip_check(hipEventRecord(B.ev[2], c->stream), "event");
+    if (!n) break;   // (nothing but empty blocks)
+    B.pieces++;
+    const uint32_t n_chunks = (n + MKP_BEDIN_CHUNK - 1) / MKP_BEDIN_CHUNK;
+    B.d_cnt.ensure((size_t)n_chunks * 12);
+    hip_check(hipMemsetAsync(words, 0, MKP_BEDIN_WORDS * 4, c->stream), "memset");
+    hip_check(hipMemsetAsync(words + MKP_BEDIN_W_ERR_OFF, 0xff, 8, c->stream), "memset");
+    hip_check(mkp_launch_bedmethyl_lines(c->stream, text, n, final_piece ? 1u : 0u, B.d_cnt.as<uint32_t>(), words), "bedMethyl line count launch");
+    hip_check(hipEventRecord(B.ev[3], c->stream), "event");
+    uint32_t w[MKP_BEDIN_WORDS];
+    d2h_copy(w, words, sizeof(w), c->stream);
+    if (!dev_blks.empty()) {
+      std::vector<uint32_t> st(dev_blks.size());
+      d2h_copy(st.data(), B.d_stat.p, st.size() * 4, c->stream);
+      for (size_t k = 0; k < st.size(); k++) if (st[k]) throw Error(MKP_E_IO, "corrupt BGZF data: block " + std::to_string(blk_index[k]) + " of " + path
+          + (st[k] == 0x100u ? " (CRC-32 mismatch)" : " (decoder status " + std::to_string(st[k]) + ")"));
+    }
+    const uint32_t n_lines = w[MKP_BEDIN_W_LINES], n_rows = w[MKP_BEDIN_W_ROWS], limit = w[MKP_BEDIN_W_LIMIT];
+    if (n_rows > n_lines || n_lines > n || limit > n) throw Error(MKP_E_DEVICE, "device bedMethyl reader: inconsistent line counts for " + path);
+    const size_t stride = ((size_t)std::max(n_rows, 1u) + 63) & ~(size_t)63;
+    B.d_lines.ensure(((size_t)n_lines + 1) * 4); B.d_rows.ensure(stride * 44); B.d_runs.ensure(std::max<size_t>(n_rows, 1) * sizeof(MkpBedRun));
+    B.d_names.ensure(n);
+    const MkpRowsDev rows = rows_at(B.d_rows.as<uint32_t>(), stride);
+    hip_check(mkp_launch_bedmethyl_parse(c->stream, text, n, n_lines, n_rows, limit, (uint32_t)std::min<uint64_t>(max_line, 0xffffffffu),
+        B.d_cnt.as<uint32_t>(), B.d_lines.as<uint32_t>(), &rows, B.d_runs.as<MkpBedRun>(), B.d_names.as<uint8_t>(), words), "bedMethyl parse launch");
+    hip_check(hipEventRecord(B.ev[4], c->stream), "event");
+    d2h_copy(w, words, sizeof(w), c->stream);
+    B.ms[1] += bedin_elapsed(B.ev[0], B.ev[1]); B.ms[2] += bedin_elapsed(B.ev[1], B.ev[2]);
+    B.ms[3] += bedin_elapsed(B.ev[2], B.ev[3]) + bedin_elapsed(B.ev[3], B.ev[4]);
+    // the runs of the piece, in file order
+    const uint32_t n_runs = w[MKP_BEDIN_W_RUNS], name_bytes = w[MKP_BEDIN_W_NAME_BYTES];
+    if (n_runs > n_rows || name_bytes > n) throw Error(MKP_E_DEVICE, "device bedMethyl reader: inconsistent run counts for " + path);
+    std::vector<MkpBedRun> runs(n_runs); std::vector<uint8_t> names(name_bytes);
+    d2h_copy(runs.data(), B.d_runs.p, runs.size() * sizeof(MkpBedRun), c->stream);
+    d2h_copy(names.data(), B.d_names.p, names.size(), c->stream);
+    std::sort(runs.begin(), runs.end(), [](const MkpBedRun& a, const MkpBedRun& b) { return a.row < b.row; });
+    for (const MkpBedRun& r : runs) if ((uint64_t)r.name_off + r.name_len > name_bytes || r.row >= n_rows) throw Error(MKP_E_DEVICE,
+        "device bedMethyl reader: a run outside its piece for " + path);
+    uint32_t bits = w[MKP_BEDIN_W_ERR];
+    std::string first_chrom; if (n_runs) first_chrom.assign((const char*)names.data() + runs[0].name_off, runs[0].name_len);
+    const bool goes_on = n_runs && have_last && first_chrom == last_chrom;
+    if (goes_on && w[MKP_BEDIN_W_FIRST_POS] < last_pos) bits |= MKP_BEDIN_ERR_ORDER;
+    if (bits) { uint64_t off; memcpy(&off, w + MKP_BEDIN_W_ERR_OFF, 8);
+      bedin_fail(c, text, limit, line_base, path, bits, off, max_line, have_last ? &last_chrom : nullptr, last_pos); }
+    for (uint32_t k = 0; k < n_runs; k++) {
+      const uint32_t first = runs[k].row, cnt = (k + 1 < n_runs ? runs[k + 1].row : n_rows) - first;
+      const std::string chrom((const char*)names.data() + runs[k].name_off, runs[k].name_len);
+      const uint32_t* p = B.d_rows.as<uint32_t>() + first;
+      const RowCols r = {p, p + stride, p + 2 * stride, p + 3 * stride, p + 4 * stride, cnt,
+          {p + 5 * stride, p + 6 * stride, p + 7 * stride, p + 8 * stride, p + 9 * stride, p + 10 * stride}};
+      sink(chrom, r, k == 0 && goes_on);
+      if (k + 1 == n_runs) { last_chrom = chrom; last_pos = w[MKP_BEDIN_W_LAST_POS]; have_last = true; }
+    }
+    // the unfinished tail to the front of the other buffer
+    carry = final_piece ? 0u : n - limit;
+    line_base += w[MKP_BEDIN_W_NL];
+    if (carry) {
+      B.d_text[cur ^ 1].ensure(text_cap);
+      hip_check(hipMemcpyAsync(B.d_text[cur ^ 1].p, text + limit, carry, hipMemcpyDeviceToDevice, c->stream), "D2D");
+      cur ^= 1;
+    }
+  }
+  hip_check(hipStreamSynchronize(c->stream), "sync");
+}
+
+}  // namespace
+
+extern "C" {
+
+int mkp_internal_bedmethyl_in_stats(mkp_ctx* c, int reset, double ms_out[4], uint64_t* pieces) {
+  if (!c) return MKP_E_INVALID;
+  if (ms_out) for (int k = 0; k < 4; k++) ms_out[k] = c->bedin.ms[k];
+  if (pieces) *pieces = c->bedin.pieces;
+  if (reset) { for (double& v : c->bedin.ms) v = 0; c->bedin.pieces = 0; }
+  return MKP_OK;
+}
+
+int mkp_merge_add_file(mkp_ctx* c, const char* path, const char* const* contig_names, uint32_t n_names, uint64_t* n_rows) {
+  if (!c || !path || (!contig_names && n_names)) return MKP_E_INVALID;
+  if (n_rows) *n_rows = 0;
+  return guarded(c, [&]() {
+    mkp_ctx::Merge& M = c->merge;
+    rt_need_open(M, kMergeWords);
+    std::map<std::string, int32_t> tid_of;   // (the first of two equal names, as the sizes table of the command)
+    for (uint32_t k = 0; k < n_names; k++) { if (!contig_names[k]) throw Error(MKP_E_INVALID, "contig name " + std::to_string(k) + " is NULL");
+      tid_of.emplace(contig_names[k], (int32_t)k); }
+    uint64_t total = 0;
+    bedin_read_file(c, path, [&](const std::string& chrom, const RowCols& r, bool) {
+      auto it = tid_of.find(chrom); const int32_t tid = it == tid_of.end() ? -1 : it->second;
+      const uint64_t len = merge_contig_len(M, tid);
+      uint64_t n_kept = 0;
+      if (len && r.n) {   // the rows in front of the contig's length
+        uint32_t* misc = M.d_misc.as<uint32_t>();
+        hip_check(mkp_launch_merge_rows_below(c->stream, r.pos, (uint32_t)r.n, (uint32_t)len, misc + 2), "bedmethyl merge launch");
+        uint32_t below = 0; d2h_copy(&below, misc + 2, 4, c->stream); n_kept = below;
+      }
+      merge_add(c, tid, r, n_kept);
+      total += r.n;
+    });
+    if (n_rows) *n_rows = total;
+  });
+}
+
+int mkp_bedmethyl_read_device(mkp_ctx* c, const char* path, mkp_bedmethyl_file** out) {
+  if (!c || !path || !out) return MKP_E_INVALID;
+  *out = nullptr;
+  return guarded(c, [&]() {
+    std::unique_ptr<mkp_bedmethyl_file> f(new mkp_bedmethyl_file());
+    std::vector<uint32_t> tmp;
+    bedin_read_file(c, path, [&](const std::string& chrom, const RowCols& r, bool goes_on) {
+      if (goes_on && !f->runs.empty()) f->runs.back().n += r.n;
+      else { mkp_bedmethyl_file::Run u; u.chrom = chrom; u.first = f->n_rows(); u.n = r.n; f->runs.push_back(u); }
+      const size_t n = (size_t)r.n; tmp.resize(n);
+      // file columns: pos, code_repr, n_valid, n_mod, then the six other counts
+      const uint32_t* src[10] = {r.pos, r.code, r.n_valid, r.n_mod, r.rest[0], r.rest[1], r.rest[2], r.rest[3], r.rest[4], r.rest[5]};
+      for (int k = 0; k < 10; k++) { d2h_copy(tmp.data(), src[k], n * 4, c->stream); f->col[k].insert(f->col[k].end(), tmp.begin(), tmp.end()); }
+      d2h_copy(tmp.data(), r.info, n * 4, c->stream);
+      for (size_t i = 0; i < n; i++) f->strand.push_back((uint8_t)"+-."[tmp[i] < 3u ? tmp[i] : 2u]);
+      f->motif.insert(f->motif.end(), n, -1);
+    });
+    *out = f.release();
   });
 }
 

@@ -219,6 +219,15 @@ struct mkp_ctx {
     mkp::DevBuf d_stage, d_cuts, d_counts, d_offsets;
     uint64_t n_dropped = 0; uint32_t err_bits = 0;
   } merge;
+  // device bedMethyl reader (mkp_merge_add_file / mkp_bedmethyl_read_device, mkp_bedmethyl.hip): the buffers of a piece of text — compressed
+  // blocks, the text (two buffers: a piece's unfinished tail goes to the front of the other one), block table and status, chunk counts, the
+  // piece's words, line starts, row columns, runs and their names —, kept across pieces and files; the read stage's times, summed
+  struct BedIn {
+    mkp::DevBuf d_zin, d_text[2], d_blk, d_stat, d_cnt, d_words, d_lines, d_rows, d_runs, d_names;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    double ms[4] = {0, 0, 0, 0};   // file read (+ block table walk), upload, inflate + CRC, line count + parse + runs
+    uint64_t pieces = 0;
+  } bedin;
   bool skip_row_fetch = false;   // `--region-stats-only`: mkp_shard_run leaves the rows in HBM (no column read-back, n_rows = 0 in its output)
   // device ingest of indexed BAMs (mkp_ingest_host.cpp): created on first use, lives with the context (staging + window buffers are reused)
   struct mkp_dev_ingest* ingest = nullptr;
@@ -261,3 +270,5 @@ extern "C" int mkp_internal_skip_row_fetch(mkp_ctx* c, int on);
 extern "C" int mkp_internal_localize_timing(mkp_ctx* c, int on, double ms_out[2]);
 // bedmethyl merge: the same for [partition, tile + scan + compaction]
 extern "C" int mkp_internal_merge_timing(mkp_ctx* c, int on, double ms_out[2]);
+// device bedMethyl reader: the read stage's summed times [file read, upload, inflate + CRC, parse] in ms and the pieces read; reset = zero them
+extern "C" int mkp_internal_bedmethyl_in_stats(mkp_ctx* c, int reset, double ms_out[4], uint64_t* pieces);

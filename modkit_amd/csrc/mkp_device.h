@@ -324,6 +324,27 @@ struct MkpLocRegion { uint32_t ws, we, anchor; uint32_t rules /* fetch rule | re
 struct MkpMergeCut { uint32_t a, b; };   // rows of the table / of the added rows in front of a tile
 #define MKP_MERGE_ERR_TILE 1u       // device error bit: one position holds more rows than a tile has room for
 #define MKP_MERGE_ERR_SUM 2u        // device error bit: a summed count does not fit in 32 bits
+// ---- device bedMethyl reader (mkp_bedmethyl.hip): a piece of text is cut into chunks of MKP_BEDIN_CHUNK bytes, a workgroup each, a lane
+// 16 bytes.  The piece's words (dwords of one small buffer; the host zeroes them in front of a piece, MKP_BEDIN_W_ERR_OFF to all ones):
+#define MKP_BEDIN_CHUNK 4096u
+enum {
+  MKP_BEDIN_W_LINES = 0,       // data lines that start in the piece, the unfinished one behind its last line end included
+  MKP_BEDIN_W_LAST_NL = 1,     // the offset behind the piece's last '\n' (0: the piece holds none)
+  MKP_BEDIN_W_NL = 2,          // '\n' bytes of the piece: its physical lines
+  MKP_BEDIN_W_ROWS = 3,        // data lines that end in the piece: its rows
+  MKP_BEDIN_W_LIMIT = 4,       // where the last of them ends: LAST_NL, or the piece's length when it is the file's last
+  MKP_BEDIN_W_ERR = 5,         // MKP_BEDIN_ERR_* bits
+  MKP_BEDIN_W_RUNS = 6,        // contig runs of the piece
+  MKP_BEDIN_W_NAME_BYTES = 7,  // bytes of their names
+  MKP_BEDIN_W_ERR_OFF = 8,     // u64: the least offset of a line with an error bit
+  MKP_BEDIN_W_FIRST_POS = 10, MKP_BEDIN_W_LAST_POS = 11,   // pos of the first and of the last row (the host checks the order across a seam)
+  MKP_BEDIN_WORDS = 16
+};
+#define MKP_BEDIN_ERR_PARSE 1u      // a line does not parse
+#define MKP_BEDIN_ERR_RANGE 2u      // a decimal field beyond 2^32 - 1
+#define MKP_BEDIN_ERR_ORDER 4u      // pos descends inside a contig run
+#define MKP_BEDIN_ERR_LONG 8u       // a line longer than a piece may hold
+struct MkpBedRun { uint32_t row, name_off, name_len; };   // a contig run: its first row, its name's bytes in the names buffer
 #ifdef __cplusplus
 static_assert(sizeof(MkpWork) == 72 && sizeof(MkpSlotEnt) == 8, "work record is 18 dwords");
 static_assert(sizeof(MkpFusedDesc) == 64 && sizeof(MkpVisit) == 32 && sizeof(MkpCallEnt) == 8 && sizeof(MkpBaseEnt) == 8, "slot pipeline records");

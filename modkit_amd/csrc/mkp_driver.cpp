@@ -106,7 +106,7 @@ struct Args {
      -stranded-features = its --window / --stranded / --stranded-features; --localize-only: as --region-stats-only */
   std::string localize, localize_out; uint32_t localize_window = 2000; bool have_localize_window = false;
   int localize_stranded = 0, localize_stranded_features = 0; bool localize_only = false;
-  /* --merge-bedmethyl <prior.bed> (repeatable): the output is `bedmethyl merge` of this run's rows with the prior plain-text tables,
+  /* --merge-bedmethyl <prior.bed> (repeatable): the output is `bedmethyl merge` of this run's rows with the prior tables (plain text or bgzip),
      joined on the device from the rows in HBM (mkp_merge.hip); contig lengths and order from the BAM header */
   std::vector<std::string> merge_bedmethyl;
   bool rows_stay() const { return region_stats_only || localize_only; }   // the rows are neither read back nor written
@@ -1527,11 +1527,14 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
     must(ctx, mkp_merge_begin(ctx, lens.data(), (uint32_t)lens.size()));
     fetch_guard.c = ctx;
     if (a.stats) must(ctx, mkp_internal_merge_timing(ctx, 1, nullptr));
+    std::vector<const char*> names; for (const std::string& s : bam.ref_names) names.push_back(s.c_str());
     for (const std::string& path : a.merge_bedmethyl) {
-      const mkp_bedmethyl_file prior = read_bedmethyl_text(path);
-      merge_prior_rows += prior.n_rows();
-      for (size_t k = 0; k < prior.runs.size(); k++) { const mkp_rows rows = prior.rows_of(k);
-        must(ctx, mkp_merge_add_rows(ctx, bam.tid_of(prior.runs[k].chrom), &rows)); }
+      if (Knobs::one("MKP_HOST_BEDMETHYL")) {   // the host reader and mkp_merge_add_rows (the stage's earlier form)
+        const mkp_bedmethyl_file prior = read_bedmethyl_text(path);
+        merge_prior_rows += prior.n_rows();
+        for (size_t k = 0; k < prior.runs.size(); k++) { const mkp_rows rows = prior.rows_of(k);
+          must(ctx, mkp_merge_add_rows(ctx, bam.tid_of(prior.runs[k].chrom), &rows)); }
+      } else { uint64_t n = 0; must(ctx, mkp_merge_add_file(ctx, path.c_str(), names.data(), (uint32_t)names.size(), &n)); merge_prior_rows += n; }
     }
     merge_upload_ms = ms_since(t_m);
     mark("prior bedMethyl tables uploaded");
@@ -1556,6 +1559,9 @@ int run(const Args& a, mkp_ctx* ext_ctx, mkp_run_report* rep) {
     if (dropped) fprintf(stderr, "[mkpileup] bedmethyl merge: %llu rows dropped (beyond their contig's length, or on a contig the BAM header does not list)\n",
         (unsigned long long)dropped);
     if (a.stats) { double ms[2] = {0, 0}; mkp_internal_merge_timing(ctx, 0, ms);
+      double in_ms[4] = {0, 0, 0, 0}; uint64_t pieces = 0; mkp_internal_bedmethyl_in_stats(ctx, 1, in_ms, &pieces);
+      fprintf(stderr, "[mkpileup] bedmethyl merge: device reader of the priors: file read %.1f ms, upload %.1f, inflate %.1f, parse %.1f (%llu pieces)\n", in_ms[0], in_ms[1],
+          in_ms[2], in_ms[3], (unsigned long long)pieces);
       fprintf(stderr, "[mkpileup] bedmethyl merge: %zu prior tables, %llu prior rows, upload + join of the priors %.1f ms; kernels partition %.3f ms, tile + scan + compaction %.3f ms (summed over the adds); merged rows d2h %.1f ms, formatted %.1f ms\n",
           a.merge_bedmethyl.size(), (unsigned long long)merge_prior_rows, merge_upload_ms, ms[0], ms[1], get_ms, wr_ms); }
     mark("merged rows with the writer");
@@ -1758,7 +1764,7 @@ extern "C" int mkp_host_stats_table(const mkp_region_set* set, const mkp_stats_o
   return guarded_status([&]() { write_text_file(out_path, stats_table_text(*set, *counts, with_header != 0, f32_display)); return MKP_OK; });
 }
 
-// `modkit bedmethyl merge`, host half (include/mkpileup.h): the plain-text reader, no device involved
+// `modkit bedmethyl merge`, host half (include/mkpileup.h): the host reader (plain text or BGZF), no device involved
 extern "C" int mkp_host_read_bedmethyl(const char* path, mkp_bedmethyl_file** out, char* errbuf, size_t errbuf_len) {
   if (!path || !out) return fail_into(errbuf, errbuf_len, MKP_E_INVALID, "bad argument");
   *out = nullptr;
@@ -1773,8 +1779,8 @@ extern "C" int mkp_bedmethyl_file_rows(const mkp_bedmethyl_file* f, uint32_t run
 }
 extern "C" void mkp_bedmethyl_file_free(mkp_bedmethyl_file* f) { delete f; }
 
-// `mkpileup bedmethyl merge` (EntryMergeBedMethyl::run, src/bedmethyl_util/subcommands.rs:198-371): the inputs' contig runs are uploaded and
-// joined one after the other, the merged contigs come back in the order of the sizes file.  --mixed-delim and --header are parsed by the
+// `mkpileup bedmethyl merge` (EntryMergeBedMethyl::run, src/bedmethyl_util/subcommands.rs:198-371): the inputs are read on the device and their
+// contig runs joined one after the other (mkp_merge_add_file), the merged contigs come back in the order of the sizes file.  --mixed-delim and --header are parsed by the
 // reference and never used: they are not offered.
 extern "C" int mkp_bedmethyl_merge_main(int argc, const char* const* argv, uint64_t* n_written, uint64_t* n_dropped, char* errbuf, size_t errbuf_len) {
   return guarded_buf(errbuf, errbuf_len, [&]() {
@@ -1797,7 +1803,11 @@ extern "C" int mkp_bedmethyl_merge_main(int argc, const char* const* argv, uint6
     if (bgzf && to_stdout) throw Error(MKP_E_INVALID, "--bgzf writes a file and its index: it needs an output path");
     auto t_all = std::chrono::steady_clock::now();
     const mkp_genome_sizes sizes = parse_genome_sizes(sizes_path);
-    std::vector<mkp_bedmethyl_file> files; for (auto& p : inputs) files.push_back(read_bedmethyl_text(p));
+    // MKP_HOST_BEDMETHYL=1: the host reader and mkp_merge_add_rows (the stage's earlier form); otherwise the device reader takes each file
+    const bool host_read = Knobs::one("MKP_HOST_BEDMETHYL");
+    std::vector<mkp_bedmethyl_file> files;
+    if (host_read) for (auto& p : inputs) files.push_back(read_bedmethyl_text(p));
+    else for (auto& p : inputs) { std::ifstream f(p, std::ios::binary); if (!f) throw Error(MKP_E_IO, "failed to open bedMethyl " + p); }
     const double read_ms = ms_since(t_all);
     // the output is opened before any device work, as the reference opens it (File::create_new without --force)
     RowWriter wr;
@@ -1817,10 +1827,15 @@ extern "C" int mkp_bedmethyl_merge_main(int argc, const char* const* argv, uint6
     auto t_dev = std::chrono::steady_clock::now();
     must(ctx, mkp_merge_begin(ctx, sizes.length.data(), (uint32_t)sizes.length.size()));
     if (stats) must(ctx, mkp_internal_merge_timing(ctx, 1, nullptr));
-    std::map<std::string, int32_t> tid_of; for (size_t k = 0; k < sizes.name.size(); k++) tid_of.emplace(sizes.name[k], (int32_t)k);
-    for (const mkp_bedmethyl_file& f : files) for (size_t k = 0; k < f.runs.size(); k++) {
-      auto it = tid_of.find(f.runs[k].chrom); const mkp_rows rows = f.rows_of(k);
-      must(ctx, mkp_merge_add_rows(ctx, it == tid_of.end() ? -1 : it->second, &rows));
+    if (host_read) {
+      std::map<std::string, int32_t> tid_of; for (size_t k = 0; k < sizes.name.size(); k++) tid_of.emplace(sizes.name[k], (int32_t)k);
+      for (const mkp_bedmethyl_file& f : files) for (size_t k = 0; k < f.runs.size(); k++) {
+        auto it = tid_of.find(f.runs[k].chrom); const mkp_rows rows = f.rows_of(k);
+        must(ctx, mkp_merge_add_rows(ctx, it == tid_of.end() ? -1 : it->second, &rows));
+      }
+    } else {
+      std::vector<const char*> names; for (const std::string& s : sizes.name) names.push_back(s.c_str());
+      for (auto& p : inputs) must(ctx, mkp_merge_add_file(ctx, p.c_str(), names.data(), (uint32_t)names.size(), nullptr));
     }
     const double add_ms = ms_since(t_dev);
     uint64_t dropped = 0;
@@ -1833,8 +1848,13 @@ extern "C" int mkp_bedmethyl_merge_main(int argc, const char* const* argv, uint6
     if (dropped) fprintf(stderr, "[mkpileup] bedmethyl merge: %llu rows dropped (beyond their contig's length, or on a contig the sizes do not list)\n",
         (unsigned long long)dropped);
     if (stats) { double ms[2] = {0, 0}; mkp_internal_merge_timing(ctx, 0, ms);
-      fprintf(stderr, "[mkpileup] bedmethyl merge: %zu inputs, rows written=%llu dropped=%llu; read_ms=%.1f upload+join_ms=%.1f (kernels partition %.3f ms, tile + scan + compaction %.3f ms) d2h+write_ms=%.1f total_ms=%.1f\n",
-          inputs.size(), (unsigned long long)wr.n, (unsigned long long)dropped, read_ms, add_ms, ms[0], ms[1], ms_since(t_out), ms_since(t_all)); }
+      // the read stage: the host reader's wall time, or the device reader's four steps (the join's kernels run between its pieces)
+      double in_ms[4] = {0, 0, 0, 0}; uint64_t pieces = 0; mkp_internal_bedmethyl_in_stats(ctx, 1, in_ms, &pieces);
+      const double stage_ms = host_read ? read_ms : in_ms[0] + in_ms[1] + in_ms[2] + in_ms[3];
+      std::string ov; for (char** e = ::environ; e && *e; e++) if (!strncmp(*e, "MKP_", 4)) { ov += ' '; ov += *e; }
+      fprintf(stderr, "[mkpileup] bedmethyl merge: %zu inputs, rows written=%llu dropped=%llu; reader=%s read_stage_ms=%.1f (file read %.1f, upload %.1f, inflate %.1f, parse %.1f; %llu pieces) read_ms=%.1f upload+join_ms=%.1f (kernels partition %.3f ms, tile + scan + compaction %.3f ms) d2h+write_ms=%.1f total_ms=%.1f env overrides:%s\n",
+          inputs.size(), (unsigned long long)wr.n, (unsigned long long)dropped, host_read ? "host" : "device", stage_ms, host_read ? read_ms : in_ms[0],
+          in_ms[1], in_ms[2], in_ms[3], (unsigned long long)pieces, read_ms, add_ms, ms[0], ms[1], ms_since(t_out), ms_since(t_all), ov.c_str()); }
     if (n_written) *n_written = wr.n;
     if (n_dropped) *n_dropped = dropped;
     return MKP_OK;

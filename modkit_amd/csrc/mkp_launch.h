@@ -127,4 +127,14 @@ hipError_t mkp_launch_merge(hipStream_t st, const MkpRowsDev* a, uint32_t n_a, c
 hipError_t mkp_launch_merge_rows_below(hipStream_t st, const uint32_t* pos, uint32_t n, uint32_t limit, uint32_t* out);
 uint32_t mkp_merge_tiles(uint64_t n_rows);
 
+// ---- mkp_bedmethyl.hip.  text: n > 0 bytes of bedMethyl text, the buffer reaching to the next multiple of MKP_BEDIN_CHUNK; words: the piece's
+// MKP_BEDIN_WORDS words (mkp_device.h), zeroed, MKP_BEDIN_W_ERR_OFF set to all ones; final_piece: a last line without '\n' is a line
+// count + scan: cnt = three words per chunk, the first n_chunks left as the chunks' first data lines; the host reads the words next
+hipError_t mkp_launch_bedmethyl_lines(hipStream_t st, const uint8_t* text, uint32_t n, uint32_t final_piece, uint32_t* cnt, uint32_t* words);
+// line starts + parse + runs.  n_lines / n_rows / limit: as read from the words; chunk_off: the cnt of the call above; line_start: n_lines + 1
+// words; rows: n_rows rows a column; runs: n_rows entries, names: n bytes (both in the order the runs were met, not file order); max_line: a
+// longer line (without its '\n') sets MKP_BEDIN_ERR_LONG
+hipError_t mkp_launch_bedmethyl_parse(hipStream_t st, const uint8_t* text, uint32_t n, uint32_t n_lines, uint32_t n_rows, uint32_t limit,
+    uint32_t max_line, const uint32_t* chunk_off, uint32_t* line_start, const MkpRowsDev* rows, MkpBedRun* runs, uint8_t* names, uint32_t* words);
+
 }  // extern "C"
