@@ -559,6 +559,65 @@ int mkp_bedmethyl_read_device(mkp_ctx* ctx, const char* path, mkp_bedmethyl_file
 uint32_t mkp_bedmethyl_chunk_bytes(void);
 int mkp_bedmethyl_merge_main(int argc, const char* const* argv, uint64_t* n_written, uint64_t* n_dropped, char* errbuf, size_t errbuf_len);
 
+/* ---- `modkit dmr pair -a a.bed.gz -b b.bed.gz -r regions.bed --ref ref.fa --base C` (PairwiseDmr::run with -r, src/dmr/subcommands.rs;
+ * pairwise.rs, bedmethyl.rs:172-267, llr_model.rs, genome_positions.rs:91-127): every region scored for differential methylation between
+ * two bedMethyl tables.  The rows are filtered, grouped by position, checked and summed on the device from row columns that are in HBM
+ * (mkp_dmr.hip); the table of sums lives there from mkp_dmr_begin to mkp_dmr_get and every add call adds into it.  Only the region form
+ * of one `a` against one `b`: single-site mode, --segment and `dmr multi` are not offered.
+ *   mkp_dmr_begin           regions as mkp_stats_begin takes them; bases = the `--base` letters (each of ACGT, at least one); codes /
+ *                           code_bases = the code -> base table, n_lookup entries (mkp_dmr_default_lookup gives MOD_CODE_TO_DNA_BASE; a
+ *                           later entry for a code replaces an earlier one, as `--assign-code` does; at most 64 distinct codes);
+ *                           min_valid_coverage = `--min-valid-coverage`; respect_mask = `--mask` (a lower-case reference byte is no base).
+ *   mkp_dmr_set_reference   the reference bytes [offset, offset + len) of contig tid, uploaded once; positions outside have no base.  The
+ *                           command uploads the span from the contig's lowest region start to its highest region end.  A contig without
+ *                           this call is one the FASTA does not hold: its regions are not written.  Before the contig's rows.
+ *   mkp_dmr_add_rows        rows of sample 0 (a) or 1 (b) the caller holds, one contig per call, ascending pos, as mkp_stats_add_rows; pos,
+ *                           strand, code_repr, n_valid, n_mod and n_canonical are read.  A row takes part when N_valid_cov >=
+ *                           min_valid_coverage, its code is in the table, the reference base at pos is the code's base ('+' and '.' rows)
+ *                           or its complement ('-' rows), and get_positions lists that base on that strand for the region's rule (a base
+ *                           of the positive set counts as positive where the rule covers '+').  The rows of a position that take part
+ *                           must agree on N_valid_cov and N_canonical, and N_canonical + sum N_mod must equal N_valid_cov; otherwise the
+ *                           (sample, region) is bad.  Pieces of a contig come in ascending order; a position may be cut by a seam (its
+ *                           rows are held back until the next piece, another contig or mkp_dmr_get), with at most 64 rows a position.
+ *   mkp_dmr_add_file        a whole bedMethyl file, plain or bgzip, through the device reader (mkp_merge_add_file): the rows never reach
+ *                           the host; contig_names[tid]; rows of another chrom are not counted.  *n_rows (may be NULL) = the file's rows.
+ *   mkp_dmr_add_resident    the rows the last mkp_shard_run left in HBM, as sample `sample`; refusals as mkp_stats_add_resident.
+ *   mkp_dmr_get             waits for the device and returns, per sample (a, b) and region: n_mod per code column (columns = the codes a
+ *                           participating row carried in some region, ModCodeRepr order; at most 16 per run, more is MKP_E_UNSUPPORTED),
+ *                           has_code (the sample's key set holds the code: a participating row carried it, N_mod == 0 too), total (the
+ *                           N_valid_cov of every position once), n_rows (participating rows), bad, contig_has_rows (an add call brought
+ *                           a row on the region's contig); has_reference; score = llk_ratio, computed on the host in f64; state = why a
+ *                           region is not written (MKP_DMR_*; a region with no participating row is written: `.` counts, score 0).
+ *                           Arrays owned by the ctx until its next mkp_dmr_begin.
+ * Host-only: mkp_host_parse_dmr_regions = parse_roi_bed (src/dmr/util.rs:389-428): as mkp_host_parse_regions, but the '#' lines in front
+ *   are skipped and a quote in a name is kept.  mkp_host_dmr_table writes ModificationCounts::header (names a and b) / to_row of the regions
+ *   whose state is MKP_DMR_WRITTEN, in file order: a line without a name gets chrom:start-end, the score goes through f64 Display (shortest
+ *   digits that round-trip, never an exponent), percentages `{:.2}` of (n as f32 / total as f32) * 100, pct_modified through f32 Display
+ *   (`NaN` at total 0).  score and state are read as given: a caller that fills the counts itself calls mkp_host_dmr_judge first.
+ * mkp_dmr_pair_main = `mkpileup dmr pair -a a.bed[.gz] -b b.bed[.gz] -r regions.bed --ref ref.fa --base C [--base A ..] [-o out.bed] [-f]
+ *   [--header] [--min-valid-coverage N] [--assign-code x:C] [--mask] [--missing quiet|warn|fail] [--device N] [--stats]`; *n_written (may be
+ *   NULL) = the regions written.  A region that ends beyond its contig in the FASTA is MKP_E_INVALID (the reference panics). */
+enum { MKP_DMR_WRITTEN = 0, MKP_DMR_NO_CONTIG = 1 /* absent from a table */, MKP_DMR_NO_REFERENCE = 2, MKP_DMR_BAD = 3 /* an inconsistent
+       position in a sample */, MKP_DMR_MODEL = 4 /* llk_ratio fails: one code against a different code */ };
+typedef struct { uint32_t n_regions, n_codes; const uint32_t* code_repr;       /* sorted */
+                 const uint64_t* n_mod[2]; const uint8_t* has_code[2];         /* per sample: [region * n_codes + code] */
+                 const uint64_t* total[2]; const uint64_t* n_rows[2];          /* per sample: [region] */
+                 const uint8_t* bad[2]; const uint8_t* contig_has_rows[2];
+                 const uint8_t* has_reference; const double* score; const uint8_t* state; } mkp_dmr_out;
+uint32_t mkp_dmr_default_lookup(uint32_t* codes, uint8_t* code_bases, uint32_t cap);   /* returns the entries (17) */
+int mkp_dmr_begin(mkp_ctx* ctx, const mkp_region* regions, uint32_t n, const char* bases, uint32_t n_bases, const uint32_t* codes,
+                  const uint8_t* code_bases, uint32_t n_lookup, uint64_t min_valid_coverage, int respect_mask);
+int mkp_dmr_set_reference(mkp_ctx* ctx, int32_t tid, const uint8_t* bytes, uint32_t offset, uint32_t len);
+int mkp_dmr_add_rows(mkp_ctx* ctx, int sample, int32_t tid, const mkp_rows* rows);
+int mkp_dmr_add_file(mkp_ctx* ctx, int sample, const char* path, const char* const* contig_names, uint32_t n_names, uint64_t* n_rows);
+int mkp_dmr_add_resident(mkp_ctx* ctx, int sample);
+int mkp_dmr_get(mkp_ctx* ctx, mkp_dmr_out* out);
+int mkp_host_parse_dmr_regions(const char* bed_path, const char* const* contig_names, uint32_t n_contigs, mkp_region_set** out, char* errbuf,
+                               size_t errbuf_len);
+int mkp_host_dmr_judge(const mkp_dmr_out* counts, double* score, uint8_t* state);
+int mkp_host_dmr_table(const mkp_region_set* set, const mkp_dmr_out* counts, int with_header, const char* out_path);
+int mkp_dmr_pair_main(int argc, const char* const* argv, uint64_t* n_written, char* errbuf, size_t errbuf_len);
+
 /* ---- BGZF inflate on the device as a call of its own.  On the pileup path the same kernels run inside the device ingest
  * (`mkp_pileup_main` on an indexed BAM: compressed blocks up, inflate + CRC-32 + record cut + MM/ML tokeniser + packing in HBM, a digest
  * back — DESIGN.md §3.6); this entry point exists so that the decoders are tested and measured alone.  Stands in for what htslib does

@@ -132,6 +132,21 @@ def lib():
             L.mkp_bedmethyl_chunk_bytes.argtypes = []
             L.mkp_bedmethyl_chunk_bytes.restype = ctypes.c_uint32
             L.mkp_bedmethyl_merge_main.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), u64p, u64p, ctypes.c_char_p, ctypes.c_size_t]
+        if hasattr(L, "mkp_dmr_begin"):
+            u32p, u8p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint8)
+            L.mkp_dmr_default_lookup.argtypes = [u32p, u8p, ctypes.c_uint32]
+            L.mkp_dmr_default_lookup.restype = ctypes.c_uint32
+            L.mkp_dmr_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32, u32p, u8p, ctypes.c_uint32,
+                                        ctypes.c_uint64, ctypes.c_int]
+            L.mkp_dmr_set_reference.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32]
+            L.mkp_dmr_add_rows.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p]
+            L.mkp_dmr_add_file.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, u64p]
+            L.mkp_dmr_add_resident.argtypes = [ctypes.c_void_p, ctypes.c_int]
+            L.mkp_dmr_get.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            L.mkp_host_parse_dmr_regions.argtypes = L.mkp_host_parse_regions.argtypes
+            L.mkp_host_dmr_judge.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), u8p]
+            L.mkp_host_dmr_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p]
+            L.mkp_dmr_pair_main.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), u64p, ctypes.c_char_p, ctypes.c_size_t]
         # the structs this binding allocates mirror ONE revision of include/mkpileup.h: a library of another revision would write past them
         if os.environ.get("MKP_LIB_PATH") and not hasattr(L, "mkp_abi_version"):
             _lib = L   # (A/B runs against a build from before the query existed, tools/dbg/ab.sh)
@@ -164,7 +179,9 @@ EXPORTS = ["mkp_ctx_create", "mkp_ctx_destroy", "mkp_last_error", "mkp_version",
            "mkp_genome_sizes_free", "mkp_host_localize_table",
            "mkp_merge_begin", "mkp_merge_add_rows", "mkp_merge_add_resident", "mkp_merge_get", "mkp_merge_tile_rows", "mkp_host_read_bedmethyl",
            "mkp_bedmethyl_file_runs", "mkp_bedmethyl_file_chrom", "mkp_bedmethyl_file_rows", "mkp_bedmethyl_file_free", "mkp_bedmethyl_merge_main",
-           "mkp_merge_add_file", "mkp_bedmethyl_read_device", "mkp_bedmethyl_chunk_bytes"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
+           "mkp_merge_add_file", "mkp_bedmethyl_read_device", "mkp_bedmethyl_chunk_bytes",
+           "mkp_dmr_default_lookup", "mkp_dmr_begin", "mkp_dmr_set_reference", "mkp_dmr_add_rows", "mkp_dmr_add_file", "mkp_dmr_add_resident", "mkp_dmr_get",
+           "mkp_host_parse_dmr_regions", "mkp_host_dmr_judge", "mkp_host_dmr_table", "mkp_dmr_pair_main"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
 
 
 def pileup(argv):
@@ -206,6 +223,22 @@ def bedmethyl_merge(argv):
     if rc != MKP_OK:
         raise MkpError(rc, err.value.decode(errors="replace"))
     return int(written.value), int(dropped.value)
+
+
+def dmr_pair(argv):
+    """`modkit dmr pair` over regions (PairwiseDmr::run with -r, src/dmr/subcommands.rs) on the device: argv = ["-a", a.bed[.gz], "-b", b.bed[.gz],
+    "-r", regions.bed, "--ref", ref.fa, "--base", "C", "-o", out.bed, "-f", "--header", "--min-valid-coverage", N, "--assign-code", "x:C", "--mask",
+    "--missing", "quiet|warn|fail"]; the tables are read by the device reader (Context.dmr_add_file; MKP_HOST_BEDMETHYL=1: by the host reader).
+    Single-site mode (no -r), --segment and more than one -a / -b are refused.  Returns the number of regions written."""
+    L = lib()
+    args = [str(a).encode() for a in argv]
+    arr = (ctypes.c_char_p * max(1, len(args)))(*args)
+    err = ctypes.create_string_buffer(2048)
+    written = ctypes.c_uint64(0)
+    rc = L.mkp_dmr_pair_main(len(args), arr, ctypes.byref(written), err, len(err))
+    if rc != MKP_OK:
+        raise MkpError(rc, err.value.decode(errors="replace"))
+    return int(written.value)
 
 
 def extract_calls(argv):
@@ -266,6 +299,16 @@ class StatsOut(ctypes.Structure):
                 ("n_mod", ctypes.POINTER(ctypes.c_uint64)), ("n_valid", ctypes.POINTER(ctypes.c_uint64)), ("contig_has_rows", ctypes.POINTER(ctypes.c_uint8))]
 
 
+class DmrOut(ctypes.Structure):
+    """mkp_dmr_out: per sample (a, b) and region the sums of `modkit dmr pair`, the scores and why a region is not written."""
+    _fields_ = [("n_regions", ctypes.c_uint32), ("n_codes", ctypes.c_uint32), ("code_repr", ctypes.POINTER(ctypes.c_uint32)),
+                ("n_mod", ctypes.POINTER(ctypes.c_uint64) * 2), ("has_code", ctypes.POINTER(ctypes.c_uint8) * 2),
+                ("total", ctypes.POINTER(ctypes.c_uint64) * 2), ("n_rows", ctypes.POINTER(ctypes.c_uint64) * 2),
+                ("bad", ctypes.POINTER(ctypes.c_uint8) * 2), ("contig_has_rows", ctypes.POINTER(ctypes.c_uint8) * 2),
+                ("has_reference", ctypes.POINTER(ctypes.c_uint8)), ("score", ctypes.POINTER(ctypes.c_double)), ("state", ctypes.POINTER(ctypes.c_uint8))]
+
+
+DMR_WRITTEN, DMR_NO_CONTIG, DMR_NO_REFERENCE, DMR_BAD, DMR_MODEL = 0, 1, 2, 3, 4   # MKP_DMR_* (mkp_dmr_out.state)
 STRAND_RULES = {"+": 1, "-": 2, ".": 3}
 
 
@@ -279,8 +322,9 @@ def code_repr(code):
 class RegionSet:
     """A parsed regions BED (mkp_host_parse_regions): `regions` = [(chrom, start, end, name or ".", strand "+-."), ...], tids by `contig_names`."""
 
-    def __init__(self, bed_path, contig_names, localize=False):
-        """localize=True: the tolerant loader of `modkit localize` (mkp_host_parse_localize_regions); `skipped` = the lines that failed to parse."""
+    def __init__(self, bed_path, contig_names, localize=False, dmr=False):
+        """localize=True: the tolerant loader of `modkit localize` (mkp_host_parse_localize_regions); `skipped` = the lines that failed to parse.
+        dmr=True: the loader of `modkit dmr pair` (mkp_host_parse_dmr_regions: leading '#' lines skipped)."""
         self.L = lib()
         names = [str(n).encode() for n in contig_names]
         arr = (ctypes.c_char_p * max(1, len(names)))(*names)
@@ -292,7 +336,8 @@ class RegionSet:
             rc = self.L.mkp_host_parse_localize_regions(str(bed_path).encode(), arr, len(names), ctypes.byref(self.h), ctypes.byref(skipped), err, len(err))
             self.skipped = int(skipped.value)
         else:
-            rc = self.L.mkp_host_parse_regions(str(bed_path).encode(), arr, len(names), ctypes.byref(self.h), err, len(err))
+            parse = self.L.mkp_host_parse_dmr_regions if dmr else self.L.mkp_host_parse_regions
+            rc = parse(str(bed_path).encode(), arr, len(names), ctypes.byref(self.h), err, len(err))
         if rc != MKP_OK:
             raise MkpError(rc, err.value.decode(errors="replace"))
         self.n = self.L.mkp_region_set_size(self.h)
@@ -317,6 +362,15 @@ class RegionSet:
         if rc != MKP_OK:
             raise MkpError(rc, "mkp_host_stats_table failed")
 
+    def write_dmr_table(self, counts, out_path, header=False):
+        """The `modkit dmr pair` table of `counts` (the dict Context.dmr_get returns, or one a caller filled: "score" / "state" may be left out
+        and are then worked out by mkp_host_dmr_judge) for these regions (mkp_host_dmr_table)."""
+        o, keep = dmr_out_from(counts)
+        rc = self.L.mkp_host_dmr_table(self.h, ctypes.byref(o), int(bool(header)), str(out_path).encode())
+        del keep
+        if rc != MKP_OK:
+            raise MkpError(rc, "mkp_host_dmr_table failed")
+
     def close(self):
         if self.h:
             self.L.mkp_region_set_free(self.h)
@@ -340,6 +394,42 @@ def stats_out_from(d):
                  n_mod=n_mod.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n_valid=n_valid.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
                  contig_has_rows=has.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
     return o, (codes, n_mod, n_valid, has)
+
+
+def dmr_out_from(d):
+    """A DmrOut over numpy copies of the dict Context.dmr_get returns; without "score" / "state" they come from mkp_host_dmr_judge.  Returns
+    (struct, arrays to keep alive)."""
+    import numpy as np
+    u8p, u64p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint64)
+    keep = {"codes": np.ascontiguousarray(np.asarray(d["codes"], dtype=np.uint32))}
+    n, k = len(d["has_reference"]), len(keep["codes"])
+    o = DmrOut(n_regions=n, n_codes=k, code_repr=keep["codes"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    for f, dt, pt in (("n_mod", np.uint64, u64p), ("has_code", np.uint8, u8p), ("total", np.uint64, u64p), ("n_rows", np.uint64, u64p),
+                      ("bad", np.uint8, u8p), ("contig_has_rows", np.uint8, u8p)):
+        for s in range(2):
+            a = keep[f, s] = np.ascontiguousarray(np.asarray(d[f][s], dtype=dt))
+            getattr(o, f)[s] = a.ctypes.data_as(pt)
+    keep["ref"] = np.ascontiguousarray(np.asarray(d["has_reference"], dtype=np.uint8))
+    o.has_reference = keep["ref"].ctypes.data_as(u8p)
+    if "score" in d and "state" in d:
+        keep["score"] = np.ascontiguousarray(np.asarray(d["score"], dtype=np.float64))
+        keep["state"] = np.ascontiguousarray(np.asarray(d["state"], dtype=np.uint8))
+    else:
+        keep["score"], keep["state"] = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.uint8)
+        rc = lib().mkp_host_dmr_judge(ctypes.byref(o), keep["score"].ctypes.data_as(ctypes.POINTER(ctypes.c_double)), keep["state"].ctypes.data_as(u8p))
+        if rc != MKP_OK:
+            raise MkpError(rc, "mkp_host_dmr_judge failed")
+    o.score, o.state = keep["score"].ctypes.data_as(ctypes.POINTER(ctypes.c_double)), keep["state"].ctypes.data_as(u8p)
+    return o, keep
+
+
+def dmr_default_lookup():
+    """MOD_CODE_TO_DNA_BASE as {code_repr: base letter} (mkp_dmr_default_lookup)."""
+    L = lib()
+    n = L.mkp_dmr_default_lookup(None, None, 0)
+    codes, bases = (ctypes.c_uint32 * n)(), (ctypes.c_uint8 * n)()
+    L.mkp_dmr_default_lookup(codes, bases, n)
+    return {int(codes[k]): "ACGT"[bases[k]] for k in range(n)}
 
 
 class LocalizeOut(ctypes.Structure):
@@ -762,6 +852,51 @@ class Context:
         rows, dropped = Rows(), ctypes.c_uint64(0)
         self._check(self.L.mkp_merge_get(self.h, int(tid), ctypes.byref(rows), ctypes.byref(dropped)))
         return rows_to_numpy(rows), int(dropped.value)
+
+    def dmr_begin(self, regions, bases=("C",), lookup=None, min_valid_coverage=0, mask=False):
+        """mkp_dmr_begin: regions as stats_begin takes them; bases = the `--base` letters; lookup = {code: base letter} (None:
+        MOD_CODE_TO_DNA_BASE; `--assign-code` entries are added to dmr_default_lookup()); mask = `--mask`."""
+        arr, n = _region_array(regions)
+        lk = dmr_default_lookup() if lookup is None else {code_repr(c): b for c, b in lookup.items()}
+        codes = (ctypes.c_uint32 * max(1, len(lk)))(*lk.keys())
+        cb = (ctypes.c_uint8 * max(1, len(lk)))(*["ACGT".index(b) for b in lk.values()])
+        bs = "".join(bases).encode()
+        self._check(self.L.mkp_dmr_begin(self.h, arr, n, bs, len(bs), codes, cb, len(lk), int(min_valid_coverage), int(bool(mask))))
+
+    def dmr_set_reference(self, tid, seq, offset=0):
+        """mkp_dmr_set_reference: seq = the reference bytes of contig tid from `offset` on; before the contig's rows."""
+        b = seq if isinstance(seq, bytes) else str(seq).encode()
+        self._check(self.L.mkp_dmr_set_reference(self.h, int(tid), b, int(offset), len(b)))
+
+    def dmr_add_rows(self, sample, tid, rows):
+        """mkp_dmr_add_rows: rows of ONE contig of sample 0 (a) or 1 (b), ascending pos, as a dict of arrays with all eleven columns."""
+        r, _keep = _rows_struct(rows, all_columns=True)
+        self._check(self.L.mkp_dmr_add_rows(self.h, int(sample), int(tid), ctypes.byref(r)))
+
+    def dmr_add_file(self, sample, path, names):
+        """mkp_dmr_add_file: a whole bedMethyl file (plain text or bgzip) of sample 0 / 1 through the device reader; names[tid]."""
+        enc = [str(n).encode() for n in names]
+        arr = (ctypes.c_char_p * max(1, len(enc)))(*enc)
+        n = ctypes.c_uint64(0)
+        self._check(self.L.mkp_dmr_add_file(self.h, int(sample), str(path).encode(), arr, len(enc), ctypes.byref(n)))
+        return int(n.value)
+
+    def dmr_add_resident(self, sample):
+        """mkp_dmr_add_resident: the rows the last shard run left in HBM, as sample 0 / 1."""
+        self._check(self.L.mkp_dmr_add_resident(self.h, int(sample)))
+
+    def dmr_get(self):
+        """mkp_dmr_get: {"codes": u32[k] sorted; per sample s in (0, 1): "n_mod"[s] u64[n, k], "has_code"[s] u8[n, k], "total"[s] / "n_rows"[s]
+        u64[n], "bad"[s] / "contig_has_rows"[s] u8[n]; "has_reference" u8[n], "score" f64[n], "state" u8[n] (DMR_*)}."""
+        o = DmrOut()
+        self._check(self.L.mkp_dmr_get(self.h, ctypes.byref(o)))
+        n, k, arr = int(o.n_regions), int(o.n_codes), _copy_out
+        d = {"codes": arr(o.code_repr, (k,), "u4"), "has_reference": arr(o.has_reference, (n,), "u1"), "score": arr(o.score, (n,), "f8"),
+             "state": arr(o.state, (n,), "u1")}
+        for f, shape, dt in (("n_mod", (n, k), "u8"), ("has_code", (n, k), "u1"), ("total", (n,), "u8"), ("n_rows", (n,), "u8"), ("bad", (n,), "u1"),
+                             ("contig_has_rows", (n,), "u1")):
+            d[f] = [arr(getattr(o, f)[s], shape, dt) for s in range(2)]
+        return d
 
     def rerun(self, iters, fetch=False):
         rows = Rows()

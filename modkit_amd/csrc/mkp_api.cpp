@@ -9,6 +9,7 @@
 
 #include "mkp_bedmethyl_in.hpp"
 #include "mkp_ctx.hpp"
+#include "mkp_dmr.hpp"
 #include "mkp_ingest_host.hpp"
 #include "mkp_launch.h"
 #include "mkp_plan.hpp"
@@ -488,12 +489,14 @@ void mkp_ctx_destroy(mkp_ctx* c) {
                         &c->rstats.d_cnt, &c->rstats.d_off, &c->loc.d_tab}) b->release();
   for (auto& kv : c->merge.contigs) for (DevBuf& b : kv.second.buf) b.release();
   for (DevBuf* b : {&c->merge.d_stage, &c->merge.d_cuts, &c->merge.d_counts, &c->merge.d_offsets}) b->release();
+  for (auto& kv : c->dmr.ref) kv.second.buf.release();
+  for (DevBuf* b : {&c->dmr.d_out, &c->dmr.d_seen, &c->dmr.d_cnt, &c->dmr.d_off, &c->dmr.carry[0].buf, &c->dmr.carry[1].buf}) b->release();
   { mkp_ctx::BedIn& B = c->bedin;
     for (DevBuf* b : {&B.d_zin, &B.d_text[0], &B.d_text[1], &B.d_blk, &B.d_stat, &B.d_cnt, &B.d_words, &B.d_lines, &B.d_rows, &B.d_runs, &B.d_names})
       b->release();
     for (auto& e : B.ev) if (e) (void)hipEventDestroy(e); }
   for (mkp_ctx::RowTable* t : {static_cast<mkp_ctx::RowTable*>(&c->rstats), static_cast<mkp_ctx::RowTable*>(&c->loc),
-      static_cast<mkp_ctx::RowTable*>(&c->merge)}) {
+      static_cast<mkp_ctx::RowTable*>(&c->merge), static_cast<mkp_ctx::RowTable*>(&c->dmr)}) {
     for (DevBuf* b : {&t->d_regions, &t->d_misc, &t->d_lo, &t->d_hi, &t->d_rows}) b->release();
     for (auto& e : t->ev) if (e) (void)hipEventDestroy(e);
   }
@@ -1288,6 +1291,7 @@ namespace {
 struct RowTableWords { const char *begin, *needs, *launch, *inside, *holds; };
 constexpr RowTableWords kStatsWords = {"mkp_stats_begin", "region statistics need", "region stats", "regions", "region statistics hold"};
 constexpr RowTableWords kLocWords = {"mkp_localize_begin", "localize needs", "localize", "windows", "localize holds"};
+constexpr RowTableWords kDmrWords = {"mkp_dmr_begin", "dmr pair needs", "dmr pair", "regions", "dmr pair holds"};
 constexpr RowTableWords kMergeWords = {"mkp_merge_begin", "bedmethyl merge needs", "bedmethyl merge", "tables", "bedmethyl merge holds"};
 // the five columns the reducers read, on the device; info = 0 '+', 1 '-', 2 '.' in its low bits; rest = n_canonical, n_other, n_delete,
 // n_fail, n_diff, n_nocall, which only the merge reads (not uploaded for the reducers)
@@ -1318,13 +1322,16 @@ RowCols rt_resident_rows(mkp_ctx* c, const mkp_ctx::RowTable& T, const RowTableW
   return {r.pos, r.info, r.code, r.n_valid, r.n_mod, c->stats.n_rows, {r.n_can, r.n_other, r.n_del, r.n_fail, r.n_diff, r.n_nocall}};
 }
 
-// the caller's rows, checked and uploaded into the session's own buffer (five columns, or all eleven, each padded to 64 rows)
-RowCols rt_upload_rows(mkp_ctx* c, mkp_ctx::RowTable& T, const RowTableWords& W, const mkp_rows* rows, bool all_columns = false) {
+// the caller's rows, checked and uploaded into the session's own buffer (the first n_cols columns: the five the reducers read, with
+// n_canonical the six of dmr, or all eleven; each padded to 64 rows)
+RowCols rt_upload_rows(mkp_ctx* c, mkp_ctx::RowTable& T, const RowTableWords& W, const mkp_rows* rows, int n_cols = 5) {
+  const bool all_columns = n_cols == 11;
   rt_need_open(T, W);
   const uint64_t n = rows->n_rows;
   if (n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one call");
   if (n && (!rows->pos || !rows->strand || !rows->code_repr || !rows->n_valid || !rows->n_mod)) throw Error(MKP_E_INVALID,
       "pos, strand, code_repr, n_valid and n_mod are needed");
+  if (n && n_cols == 6 && !rows->n_canonical) throw Error(MKP_E_INVALID, "n_canonical is needed as well");
   if (n && all_columns && (!rows->n_canonical || !rows->n_other || !rows->n_delete || !rows->n_fail || !rows->n_diff || !rows->n_nocall))
     throw Error(MKP_E_INVALID, "all eleven row columns are needed");
   std::vector<uint32_t> info(n);
@@ -1338,14 +1345,13 @@ RowCols rt_upload_rows(mkp_ctx* c, mkp_ctx::RowTable& T, const RowTableWords& W,
   hip_check(hipSetDevice(c->device), "hipSetDevice");
   hip_check(hipStreamSynchronize(c->stream), "sync");   // the previous call's kernels read the upload buffer
   const size_t col = ((size_t)n + 63) & ~(size_t)63;
-  const int n_cols = all_columns ? 11 : 5;
   T.d_rows.ensure(std::max<size_t>(col, 64) * 4 * (size_t)n_cols);
   uint32_t* d = T.d_rows.as<uint32_t>();
   const uint32_t* src[11] = {rows->pos, info.data(), rows->code_repr, rows->n_valid, rows->n_mod, rows->n_canonical, rows->n_other,
       rows->n_delete, rows->n_fail, rows->n_diff, rows->n_nocall};
   for (int k = 0; k < n_cols; k++) h2d_copy(d + (size_t)k * col, src[k], (size_t)n * 4);
   RowCols r = {d, d + col, d + 2 * col, d + 3 * col, d + 4 * col, n, {}};
-  for (int k = 0; k < 6; k++) r.rest[k] = all_columns ? d + (size_t)(5 + k) * col : nullptr;
+  for (int k = 0; k < 6; k++) r.rest[k] = 5 + k < n_cols ? d + (size_t)(5 + k) * col : nullptr;
   return r;
 }
 
@@ -1697,7 +1703,7 @@ int mkp_merge_add_rows(mkp_ctx* c, int32_t tid, const mkp_rows* rows) {
   if (!c || !rows) return MKP_E_INVALID;
   return guarded(c, [&]() {
     mkp_ctx::Merge& M = c->merge;
-    const RowCols r = rt_upload_rows(c, M, kMergeWords, rows, true);
+    const RowCols r = rt_upload_rows(c, M, kMergeWords, rows, 11);
     const uint64_t len = merge_contig_len(M, tid);
     const uint64_t n_kept = len > 0xffffffffull ? r.n : (uint64_t)(std::lower_bound(rows->pos, rows->pos + r.n, (uint32_t)len) - rows->pos);
     merge_add(c, tid, r, n_kept);
@@ -1980,6 +1986,240 @@ int mkp_bedmethyl_read_device(mkp_ctx* c, const char* path, mkp_bedmethyl_file**
       f->motif.insert(f->motif.end(), n, -1);
     });
     *out = f.release();
+  });
+}
+
+}  // extern "C"
+
+// ---- dmr pair (`modkit dmr pair` over regions, include/mkpileup.h): the table of sums stays in HBM between mkp_dmr_begin and mkp_dmr_get
+namespace {
+
+void dmr_need_sample(int sample) { if (sample != 0 && sample != 1) throw Error(MKP_E_INVALID, "sample must be 0 (a) or 1 (b)"); }
+
+// the kernels over rows of contig `tid` that begin and end at position boundaries
+void dmr_launch(mkp_ctx* c, int sample, int32_t tid, const RowCols& r) {
+  mkp_ctx::Dmr& D = c->dmr;
+  auto ref = D.ref.find(tid);
+  if (ref == D.ref.end()) return;   // (no reference for the contig: its regions are not written)
+  rt_launch(c, D, kDmrWords, tid, r.n, [&](uint32_t first, uint32_t n, hipEvent_t* ev) {
+    uint32_t* misc = D.d_misc.as<uint32_t>();
+    return mkp_launch_dmr(c->stream, r.pos, r.info, r.code, r.n_valid, r.n_mod, r.rest[0], (uint32_t)r.n, D.d_regions.as<MkpStatsRegion>() + first, n,
+        D.d_lo.as<uint32_t>(), D.d_hi.as<uint32_t>(), D.d_cnt.as<uint32_t>(), D.d_off.as<unsigned long long>(),
+        reinterpret_cast<unsigned long long*>(misc + MKP_STATS_MAX_CODES + 2), ref->second.buf.as<uint8_t>(), ref->second.off, ref->second.len, &D.prm,
+        D.d_out.as<unsigned long long>() + (size_t)sample * D.n_regions * MKP_DMR_CELLS, D.d_seen.as<uint32_t>() + (size_t)sample * D.n_regions, misc,
+        misc + MKP_STATS_MAX_CODES, ev);
+  });
+}
+
+RowCols dmr_carry_rows(const mkp_ctx::Dmr::Carry& K) {
+  const uint32_t* p = K.buf.as<uint32_t>(); const size_t s = mkp_ctx::Dmr::kCarryCap;
+  return {p, p + s, p + 2 * s, p + 3 * s, p + 4 * s, K.n, {p + 5 * s, nullptr, nullptr, nullptr, nullptr, nullptr}};
+}
+
+// the rows held back of the sample's last piece: their position is whole now
+void dmr_flush(mkp_ctx* c, int sample) {
+  mkp_ctx::Dmr::Carry& K = c->dmr.carry[sample];
+  if (K.n) dmr_launch(c, sample, K.tid, dmr_carry_rows(K));
+  K.n = 0; K.tid = -1;
+}
+
+// rows [from, from + n) of r behind the carry's rows
+void dmr_carry_append(mkp_ctx* c, mkp_ctx::Dmr::Carry& K, const RowCols& r, uint64_t from, uint32_t n) {
+  if (K.n + n > mkp_ctx::Dmr::kCarryCap) throw Error(MKP_E_UNSUPPORTED, "dmr pair: more than " + std::to_string(mkp_ctx::Dmr::kCarryCap)
+      + " rows at position " + std::to_string(K.pos) + " across a seam");
+  K.buf.ensure((size_t)mkp_ctx::Dmr::kCarryCap * 6 * 4);
+  uint32_t* d = K.buf.as<uint32_t>();
+  const uint32_t* src[6] = {r.pos, r.info, r.code, r.n_valid, r.n_mod, r.rest[0]};
+  for (int k = 0; k < 6; k++) hip_check(hipMemcpyAsync(d + (size_t)k * mkp_ctx::Dmr::kCarryCap + K.n, src[k] + from, (size_t)n * 4, hipMemcpyDeviceToDevice,
+      c->stream), "D2D");
+  K.n += n;
+}
+
+// One piece of contig `tid` of a sample, its rows on the device.  A seam may cut a position: the rows of the piece's last position are held
+// back, and the rows at the front that continue the position held back join it first.  The kernels only ever see whole positions.
+void dmr_add_piece(mkp_ctx* c, int sample, int32_t tid, const RowCols& r) {
+  mkp_ctx::Dmr& D = c->dmr; mkp_ctx::Dmr::Carry& K = D.carry[sample];
+  if (r.n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows in one piece");
+  if (!r.n) return;
+  D.sample_tids[sample].insert(tid);
+  constexpr uint32_t kEdge = 64;   // a position holds at most this many rows
+  const uint32_t ne = (uint32_t)std::min<uint64_t>(r.n, kEdge);
+  uint32_t front[kEdge], back[kEdge];
+  d2h_copy(front, r.pos, (size_t)ne * 4, c->stream); d2h_copy(back, r.pos + (r.n - ne), (size_t)ne * 4, c->stream);
+  auto too_many = [&](uint32_t pos) { return Error(MKP_E_UNSUPPORTED, "dmr pair: more than " + std::to_string(kEdge) + " rows at position "
+      + std::to_string(pos) + " at the edge of a piece"); };
+  uint64_t head = 0;
+  if (K.n && K.tid == tid) {
+    if (front[0] < K.pos) throw Error(MKP_E_INVALID, "dmr pair: the pieces of a contig must come in ascending order (" + std::to_string(front[0])
+        + " follows " + std::to_string(K.pos) + ")");
+    while (head < ne && front[head] == K.pos) head++;
+    if (head == kEdge && r.n > kEdge) throw too_many(K.pos);
+    if (head) dmr_carry_append(c, K, r, 0, (uint32_t)head);
+    if (head == r.n) return;
+  }
+  dmr_flush(c, sample);
+  const uint32_t last = back[ne - 1];
+  uint64_t tail = 1;
+  while (tail < ne && tail < r.n - head && back[ne - 1 - tail] == last) tail++;
+  if (tail == kEdge && r.n - head > kEdge) throw too_many(last);
+  K.tid = tid; K.pos = last;
+  dmr_carry_append(c, K, r, r.n - tail, (uint32_t)tail);
+  const uint64_t n = r.n - head - tail;
+  if (n) dmr_launch(c, sample, tid, {r.pos + head, r.info + head, r.code + head, r.n_valid + head, r.n_mod + head, n,
+      {r.rest[0] + head, nullptr, nullptr, nullptr, nullptr, nullptr}});
+}
+
+}  // namespace
+
+extern "C" {
+
+int mkp_internal_dmr_timing(mkp_ctx* c, int on, double ms_out[2]) { return c ? rt_timing(c, c->dmr, on, ms_out) : MKP_E_INVALID; }
+
+uint32_t mkp_dmr_default_lookup(uint32_t* codes, uint8_t* code_bases, uint32_t cap) {
+  const std::vector<DmrLookupEntry>& t = dmr_default_lookup();
+  for (uint32_t k = 0; k < t.size() && k < cap; k++) { if (codes) codes[k] = t[k].code; if (code_bases) code_bases[k] = t[k].base; }
+  return (uint32_t)t.size();
+}
+
+int mkp_dmr_begin(mkp_ctx* c, const mkp_region* regions, uint32_t n, const char* bases, uint32_t n_bases, const uint32_t* codes,
+    const uint8_t* code_bases, uint32_t n_lookup, uint64_t min_valid_coverage, int respect_mask) {
+  if (!c || (!regions && n) || (!bases && n_bases) || ((!codes || !code_bases) && n_lookup)) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Dmr& D = c->dmr;
+    D.open = false;
+    if (n > 0x7fffffffu) throw Error(MKP_E_UNSUPPORTED, "more than 2^31 - 1 regions");
+    for (uint32_t i = 0; i < n; i++) {
+      if (regions[i].start > regions[i].end) throw Error(MKP_E_INVALID, "region " + std::to_string(i) + ": start > end");
+      if (regions[i].strand_rule < 1 || regions[i].strand_rule > 3) throw Error(MKP_E_INVALID, "region " + std::to_string(i)
+          + ": strand_rule must be 1 ('+'), 2 ('-') or 3 (both)");
+    }
+    MkpDmrParams P; memset(&P, 0, sizeof(P));
+    P.min_cov = min_valid_coverage; P.mask = respect_mask ? 1u : 0u;
+    if (!n_bases) throw Error(MKP_E_INVALID, "need to specify at least 1 modified base");
+    for (uint32_t k = 0; k < n_bases; k++) {
+      const char* at = strchr("ACGT", bases[k]);
+      if (!at || !bases[k]) throw Error(MKP_E_INVALID, "modified base needs to be A, C, G, or T.");
+      const uint32_t b = (uint32_t)(at - "ACGT");
+      P.pos_set |= 1u << b; P.neg_set |= 1u << (3u - b);
+    }
+    for (uint32_t k = 0; k < n_lookup; k++) {   // a later entry for a code replaces an earlier one
+      if (!codes[k]) throw Error(MKP_E_INVALID, "0 is not a mod code");
+      if (code_bases[k] > 3) throw Error(MKP_E_INVALID, "a code's base is an index into ACGT");
+      uint32_t at = 0; while (at < P.n_lookup && P.code[at] != codes[k]) at++;
+      if (at == MKP_DMR_MAX_LOOKUP) throw Error(MKP_E_UNSUPPORTED, "dmr pair holds at most " + std::to_string(MKP_DMR_MAX_LOOKUP)
+          + " codes in its code -> base table");
+      P.code[at] = codes[k]; P.base[at] = code_bases[k]; if (at == P.n_lookup) P.n_lookup++;
+    }
+    // Only a code of one of the --base letters can ever take part: a '+' row needs its base under it, listed '+', a '-' row its complement,
+    // listed '-', and either way that is a base of the positive set.  The kernel searches the table per row: keep what can match.
+    uint32_t kept = 0;
+    for (uint32_t k = 0; k < P.n_lookup; k++) if ((P.pos_set >> P.base[k]) & 1u) { P.code[kept] = P.code[k]; P.base[kept] = P.base[k]; kept++; }
+    for (uint32_t k = kept; k < P.n_lookup; k++) { P.code[k] = 0; P.base[k] = 0; }
+    P.n_lookup = kept;
+    D.prm = P; D.n_regions = n; D.region_tid.resize(n);
+    // the regions grouped by contig, caller order inside a contig; `out` = the caller's index
+    std::vector<uint32_t> order(n); for (uint32_t i = 0; i < n; i++) { order[i] = i; D.region_tid[i] = regions[i].tid; }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return regions[a].tid < regions[b].tid; });
+    std::vector<MkpStatsRegion> dev(n); std::vector<int32_t> dev_tid(n);
+    for (uint32_t k = 0; k < n; k++) { const mkp_region& g = regions[order[k]]; dev[k] = {g.start, g.end, g.strand_rule, order[k]}; dev_tid[k] = g.tid; }
+    rt_group_by_tid(D, dev_tid);
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    hip_check(hipStreamSynchronize(c->stream), "sync");   // (a previous session's kernels)
+    for (auto& kv : D.ref) kv.second.buf.release();
+    D.ref.clear();
+    for (int s = 0; s < 2; s++) { D.carry[s].n = 0; D.carry[s].tid = -1; D.sample_tids[s].clear(); }
+    const size_t n1 = std::max<size_t>(n, 1), m1 = std::max<size_t>(D.most_per_tid, 1);
+    D.d_regions.ensure(n1 * sizeof(MkpStatsRegion)); D.d_out.ensure(2 * n1 * MKP_DMR_CELLS * 8); D.d_seen.ensure(2 * n1 * 4);
+    D.d_misc.ensure(kStatsMiscBytes); D.d_lo.ensure(m1 * 4); D.d_hi.ensure(m1 * 4); D.d_cnt.ensure(m1 * 4); D.d_off.ensure((m1 + 1) * 8);
+    h2d_copy(D.d_regions.p, dev.data(), (size_t)n * sizeof(MkpStatsRegion));
+    hip_check(hipMemsetAsync(D.d_misc.p, 0, kStatsMiscBytes, c->stream), "memset");
+    hip_check(hipMemsetAsync(D.d_out.p, 0, 2 * n1 * MKP_DMR_CELLS * 8, c->stream), "memset");
+    hip_check(hipMemsetAsync(D.d_seen.p, 0, 2 * n1 * 4, c->stream), "memset");
+    hip_check(hipStreamSynchronize(c->stream), "sync");
+    D.open = true;
+  });
+}
+
+int mkp_dmr_set_reference(mkp_ctx* c, int32_t tid, const uint8_t* bytes, uint32_t offset, uint32_t len) {
+  if (!c || (!bytes && len)) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Dmr& D = c->dmr;
+    rt_need_open(D, kDmrWords);
+    if (tid < 0) throw Error(MKP_E_INVALID, "the reference of a contig needs its tid");
+    if ((uint64_t)offset + len > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "reference span beyond 2^32 - 1");
+    if (D.sample_tids[0].count(tid) || D.sample_tids[1].count(tid)) throw Error(MKP_E_INVALID, "mkp_dmr_set_reference comes before the contig's rows");
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    mkp_ctx::Dmr::Ref& R = D.ref[tid];
+    R.buf.ensure(std::max<size_t>(len, 1)); R.off = offset; R.len = len;
+    h2d_copy(R.buf.p, bytes, len);
+  });
+}
+
+int mkp_dmr_add_rows(mkp_ctx* c, int sample, int32_t tid, const mkp_rows* rows) {
+  if (!c || !rows) return MKP_E_INVALID;
+  return guarded(c, [&]() { dmr_need_sample(sample); dmr_add_piece(c, sample, tid, rt_upload_rows(c, c->dmr, kDmrWords, rows, 6)); });
+}
+
+int mkp_dmr_add_resident(mkp_ctx* c, int sample) {
+  if (!c) return MKP_E_INVALID;
+  return guarded(c, [&]() { dmr_need_sample(sample); dmr_add_piece(c, sample, c->shard.tid, rt_resident_rows(c, c->dmr, kDmrWords)); });
+}
+
+int mkp_dmr_add_file(mkp_ctx* c, int sample, const char* path, const char* const* contig_names, uint32_t n_names, uint64_t* n_rows) {
+  if (!c || !path || (!contig_names && n_names)) return MKP_E_INVALID;
+  if (n_rows) *n_rows = 0;
+  return guarded(c, [&]() {
+    dmr_need_sample(sample);
+    rt_need_open(c->dmr, kDmrWords);
+    std::map<std::string, int32_t> tid_of;   // (the first of two equal names)
+    for (uint32_t k = 0; k < n_names; k++) { if (!contig_names[k]) throw Error(MKP_E_INVALID, "contig name " + std::to_string(k) + " is NULL");
+      tid_of.emplace(contig_names[k], (int32_t)k); }
+    uint64_t total = 0;
+    bedin_read_file(c, path, [&](const std::string& chrom, const RowCols& r, bool) {
+      auto it = tid_of.find(chrom);
+      total += r.n;
+      if (it != tid_of.end()) dmr_add_piece(c, sample, it->second, r);
+    });
+    dmr_flush(c, sample);   // (the reader's buffers are the next file's)
+    if (n_rows) *n_rows = total;
+  });
+}
+
+int mkp_dmr_get(mkp_ctx* c, mkp_dmr_out* out) {
+  if (!c || !out) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::Dmr& D = c->dmr;
+    rt_need_open(D, kDmrWords);
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    for (int s = 0; s < 2; s++) dmr_flush(c, s);
+    uint32_t misc[kStatsMiscBytes / 4];
+    d2h_copy(misc, D.d_misc.p, sizeof(misc), c->stream);
+    rt_check_codes(misc, kDmrWords);
+    const uint32_t n = D.n_regions;
+    std::vector<uint64_t> tab((size_t)2 * n * MKP_DMR_CELLS); std::vector<uint32_t> seen((size_t)2 * n);
+    d2h_copy(tab.data(), D.d_out.p, tab.size() * 8, c->stream); d2h_copy(seen.data(), D.d_seen.p, seen.size() * 4, c->stream);
+    uint32_t any = 0; for (uint32_t m : seen) any |= m & ~MKP_DMR_SEEN_BAD;
+    const std::vector<std::pair<uint32_t, uint32_t>> cols = rt_columns(misc, any);   // code, slot
+    const size_t nc = cols.size();
+    D.h_codes.resize(nc); for (size_t k = 0; k < nc; k++) D.h_codes[k] = cols[k].first;
+    D.h_ref.resize(n); D.h_state.resize(n); D.h_score.resize(n);
+    for (uint32_t r = 0; r < n; r++) D.h_ref[r] = D.region_tid[r] >= 0 && D.ref.count(D.region_tid[r]) ? 1 : 0;
+    for (int s = 0; s < 2; s++) {
+      D.h_mod[s].assign((size_t)n * nc, 0); D.h_has_code[s].assign((size_t)n * nc, 0); D.h_total[s].resize(n); D.h_rows[s].resize(n);
+      D.h_bad[s].resize(n); D.h_contig[s].resize(n);
+      for (uint32_t r = 0; r < n; r++) {
+        const uint64_t* line = &tab[((size_t)s * n + r) * MKP_DMR_CELLS]; const uint32_t m = seen[(size_t)s * n + r];
+        for (size_t k = 0; k < nc; k++) { D.h_mod[s][(size_t)r * nc + k] = line[cols[k].second]; D.h_has_code[s][(size_t)r * nc + k] = (m >> cols[k].second) & 1u; }
+        D.h_total[s][r] = line[MKP_DMR_CELL_TOTAL]; D.h_rows[s][r] = line[MKP_DMR_CELL_ROWS]; D.h_bad[s][r] = (m & MKP_DMR_SEEN_BAD) ? 1 : 0;
+        D.h_contig[s][r] = D.region_tid[r] >= 0 && D.sample_tids[s].count(D.region_tid[r]) ? 1 : 0;
+      }
+    }
+    out->n_regions = n; out->n_codes = (uint32_t)nc; out->code_repr = D.h_codes.data();
+    for (int s = 0; s < 2; s++) { out->n_mod[s] = D.h_mod[s].data(); out->has_code[s] = D.h_has_code[s].data(); out->total[s] = D.h_total[s].data();
+      out->n_rows[s] = D.h_rows[s].data(); out->bad[s] = D.h_bad[s].data(); out->contig_has_rows[s] = D.h_contig[s].data(); }
+    out->has_reference = D.h_ref.data();
+    dmr_judge(*out, D.h_score.data(), D.h_state.data());
+    out->score = D.h_score.data(); out->state = D.h_state.data();
   });
 }
 

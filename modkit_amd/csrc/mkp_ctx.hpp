@@ -202,6 +202,20 @@ struct mkp_ctx {
     mkp::DevBuf d_out, d_seen, d_cnt, d_off;
     std::vector<uint32_t> h_codes; std::vector<uint64_t> h_mod, h_valid; std::vector<uint8_t> h_has;   // mkp_stats_get
   } rstats;
+  // dmr pair (mkp_dmr_begin .. mkp_dmr_get, mkp_dmr.hip): the run-long table out[sample][region][MKP_DMR_CELLS] (u64) and a mask per line;
+  // the reference bytes of every contig; per sample the rows of the last position of the piece before, held back until the position is whole
+  struct Dmr : RowTable {
+    static constexpr uint32_t kCarryCap = 128;                          // rows a column of the carry buffer
+    uint32_t n_regions = 0; MkpDmrParams prm;
+    std::vector<int32_t> region_tid;                                    // caller order
+    struct Ref { mkp::DevBuf buf; uint32_t off = 0, len = 0; };
+    std::map<int32_t, Ref> ref;
+    struct Carry { mkp::DevBuf buf; int32_t tid = -1; uint32_t n = 0, pos = 0; } carry[2];
+    std::set<int32_t> sample_tids[2];                                   // contigs an add call brought a row on
+    mkp::DevBuf d_out, d_seen, d_cnt, d_off;
+    std::vector<uint32_t> h_codes; std::vector<uint64_t> h_mod[2], h_total[2], h_rows[2]; std::vector<uint8_t> h_has_code[2], h_bad[2], h_contig[2],
+        h_ref, h_state; std::vector<double> h_score;                    // mkp_dmr_get
+  } dmr;
   // localize (mkp_localize_begin .. mkp_localize_get, mkp_localize.hip): the run-long table tab[slot][2 window + 1]{n_mod, n_valid, n_rows} (u64)
   struct Localize : RowTable {
     uint32_t window = 0, stranded = 0;
@@ -270,5 +284,7 @@ extern "C" int mkp_internal_skip_row_fetch(mkp_ctx* c, int on);
 extern "C" int mkp_internal_localize_timing(mkp_ctx* c, int on, double ms_out[2]);
 // bedmethyl merge: the same for [partition, tile + scan + compaction]
 extern "C" int mkp_internal_merge_timing(mkp_ctx* c, int on, double ms_out[2]);
+// dmr pair: the same for [bounds + scan, reduce]
+extern "C" int mkp_internal_dmr_timing(mkp_ctx* c, int on, double ms_out[2]);
 // device bedMethyl reader: the read stage's summed times [file read, upload, inflate + CRC, parse] in ms and the pieces read; reset = zero them
 extern "C" int mkp_internal_bedmethyl_in_stats(mkp_ctx* c, int reset, double ms_out[4], uint64_t* pieces);

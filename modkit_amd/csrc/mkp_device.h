@@ -307,6 +307,18 @@ struct MkpRowsDev {  // SoA row buffers (44 B / row)
 #define MKP_STATS_MAX_CODES 16      // distinct mod codes per run (the pileup itself allows MKP_MAX_SLOTS (base, code) pairs)
 #define MKP_STATS_ERR_CODES 1u      // device error bit: a seventeenth code
 struct MkpStatsRegion { uint32_t start, end; uint32_t rule /* 1 '+', 2 '-', 3 both */; uint32_t out /* index into the run's table */; };
+// ---- dmr pair (mkp_dmr.hip): regions as MkpStatsRegion (`out` = the region's line of one sample's table).  A line holds MKP_DMR_CELLS
+// u64: the sum of N_mod per code slot, then the total (the N_valid_cov of every good position once) and the participating rows; beside
+// it a 32-bit mask per line: bit s = a participating row of slot s, MKP_DMR_SEEN_BAD = an inconsistent position.
+#define MKP_DMR_CELLS (MKP_STATS_MAX_CODES + 2)
+#define MKP_DMR_CELL_TOTAL MKP_STATS_MAX_CODES
+#define MKP_DMR_CELL_ROWS (MKP_STATS_MAX_CODES + 1)
+#define MKP_DMR_SEEN_BAD 0x80000000u
+#define MKP_DMR_MAX_LOOKUP 64       // entries of the code -> base table (the reference's own holds 17)
+// base sets: bit b of a set = base b of "ACGT"; base[k] = the index in "ACGT" of the base code[k] modifies; mask != 0: a lower-case
+// reference byte is no base (--mask), otherwise it counts as its upper-case form
+struct MkpDmrParams { unsigned long long min_cov; uint32_t n_lookup, pos_set, neg_set, mask; uint32_t code[MKP_DMR_MAX_LOOKUP];
+  uint8_t base[MKP_DMR_MAX_LOOKUP]; };
 // ---- localize (mkp_localize.hip): one expanded window [ws, we) of the contig whose rows are being added and the anchor its offsets are
 // taken from (offset = anchor - pos).  The run-long table holds MKP_STATS_MAX_CODES slots of 2 * window + 1 cells {n_mod, n_valid, n_rows}
 // (u64 each); the codes of the slots (0 = free) are a table of the run's own.

@@ -18,6 +18,7 @@
 #include <unistd.h>
 
 #include "mkp_ctx.hpp"
+#include "mkp_dmr.hpp"
 #include "mkp_ingest_host.hpp"
 #include "mkp_focus.hpp"
 #include "mkp_regions.hpp"
@@ -1857,6 +1858,188 @@ extern "C" int mkp_bedmethyl_merge_main(int argc, const char* const* argv, uint6
           in_ms[1], in_ms[2], in_ms[3], (unsigned long long)pieces, read_ms, add_ms, ms[0], ms[1], ms_since(t_out), ms_since(t_all), ov.c_str()); }
     if (n_written) *n_written = wr.n;
     if (n_dropped) *n_dropped = dropped;
+    return MKP_OK;
+  });
+}
+
+// `modkit dmr pair`, host halves (include/mkpileup.h): the regions BED, the score and the table, no device involved
+extern "C" int mkp_host_parse_dmr_regions(const char* bed_path, const char* const* contig_names, uint32_t n_contigs, mkp_region_set** out, char* errbuf,
+    size_t errbuf_len) {
+  if (!bed_path || !out || (!contig_names && n_contigs)) return fail_into(errbuf, errbuf_len, MKP_E_INVALID, "bad argument");
+  *out = nullptr;
+  return guarded_buf(errbuf, errbuf_len, [&]() {
+    std::map<std::string, int> tids; for (uint32_t k = 0; k < n_contigs; k++) tids.emplace(contig_names[k], (int)k);
+    std::unique_ptr<mkp_region_set> set(new mkp_region_set(parse_dmr_regions_bed(bed_path, [&](const std::string& chrom) { auto it = tids.find(chrom);
+      return it == tids.end() ? -1 : it->second; })));
+    *out = set.release();
+    return MKP_OK;
+  });
+}
+extern "C" int mkp_host_dmr_judge(const mkp_dmr_out* counts, double* score, uint8_t* state) {
+  if (!counts || !score || !state) return MKP_E_INVALID;
+  return guarded_status([&]() { dmr_judge(*counts, score, state); return MKP_OK; });
+}
+extern "C" int mkp_host_dmr_table(const mkp_region_set* set, const mkp_dmr_out* counts, int with_header, const char* out_path) {
+  if (!set || !counts || !out_path) return MKP_E_INVALID;
+  return guarded_status([&]() {
+    if (counts->n_regions != set->regions.size()) throw Error(MKP_E_INVALID, "the counts are not those of this region set");
+    write_text_file(out_path, dmr_table_text(*set, *counts, with_header != 0, f32_display)); return MKP_OK; });
+}
+
+// `mkpileup dmr pair` (PairwiseDmr::run with --regions-bed, src/dmr/subcommands.rs:371-560) in stages: arguments, regions, reference, the two
+// tables through the device reader (mkp_dmr_add_file), score and text.
+namespace {
+
+struct DmrArgs {
+  std::vector<std::string> a, b, assign; std::string regions, ref, out, missing = "warn", bases;
+  bool force = false, header = false, mask = false, stats = false, segment = false; uint64_t min_cov = 0; int device = 0;
+};
+
+DmrArgs parse_dmr_args(int argc, const char* const* argv) {
+  DmrArgs d;
+  for (int i = 0; i < argc; i++) {
+    const std::string s = argv[i];
+    auto val = [&]() { if (i + 1 >= argc) throw Error(MKP_E_INVALID, "missing value for " + s); return std::string(argv[++i]); };
+    if (s == "-a") d.a.push_back(val()); else if (s == "-b") d.b.push_back(val());
+    else if (s == "-r" || s == "--regions-bed") d.regions = val(); else if (s == "--ref") d.ref = val();
+    else if (s == "-o" || s == "--out-path") d.out = val(); else if (s == "-f" || s == "--force") d.force = true;
+    else if (s == "--header" || s == "--with-header") d.header = true; else if (s == "-k" || s == "--mask") d.mask = true;
+    else if (s == "-m" || s == "--base") { const std::string v = val();
+      if (v.size() != 1) throw Error(MKP_E_INVALID, "modified base needs to be A, C, G, or T.");
+      d.bases += v; }
+    else if (s == "--assign-code") d.assign.push_back(val());
+    else if (s == "--min-valid-coverage") d.min_cov = std::stoull(val()); else if (s == "--missing") d.missing = val();
+    else if (s == "--segment") { d.segment = true; val(); }
+    else if (s == "--device") d.device = std::stoi(val()); else if (s == "--stats") d.stats = true;
+    else if (s == "-t" || s == "--threads" || s == "--io-threads" || s == "--batch-size" || s == "--log-filepath" || s == "--index-a" || s == "--index-b")
+      val();   // (the reference's compute options and tabix indices: nothing here is sized by them, no index is read)
+    else if (s == "--suppress-progress") continue;
+    else throw Error(MKP_E_INVALID, "unexpected argument '" + s + "' for dmr pair");
+  }
+  if (d.a.empty() || d.b.empty()) throw Error(MKP_E_INVALID, "need to provide at least 1 'a' sample and 'b' sample");
+  if (d.segment) throw Error(MKP_E_UNSUPPORTED, "--segment (single-site segmentation) is not offered: dmr pair scores the regions of -r");
+  if (d.regions.empty()) throw Error(MKP_E_UNSUPPORTED, "single-site mode (dmr pair without -r / --regions-bed) is not offered: give the regions with -r");
+  if (d.a.size() > 1 || d.b.size() > 1) throw Error(MKP_E_UNSUPPORTED,
+      "in order to perform multiple comparisons over regions use modkit dmr multi (which is not offered: one -a and one -b)");
+  if (d.ref.empty()) throw Error(MKP_E_INVALID, "the following required arguments were not provided: --ref <REFERENCE_FASTA>");
+  if (d.bases.empty()) throw Error(MKP_E_INVALID, "need to specify at least 1 modified base");
+  for (char b : d.bases) if (!strchr("ACGT", b)) throw Error(MKP_E_INVALID, "modified base needs to be A, C, G, or T.");
+  if (d.missing != "quiet" && d.missing != "warn" && d.missing != "fail") throw Error(MKP_E_INVALID, "--missing takes quiet, warn or fail");
+  return d;
+}
+
+// MOD_CODE_TO_DNA_BASE, then the --assign-code entries (parse_raw_assignments, subcommands.rs:302-352): a later entry replaces an earlier one
+void dmr_code_lookup(const DmrArgs& d, std::vector<uint32_t>* codes, std::vector<uint8_t>* bases) {
+  for (const DmrLookupEntry& e : dmr_default_lookup()) { codes->push_back(e.code); bases->push_back(e.base); }
+  for (const std::string& raw : d.assign) {
+    const size_t colon = raw.find(':');
+    const char* base = colon != std::string::npos && raw.find(':', colon + 1) == std::string::npos && raw.size() == colon + 2
+        ? strchr("ACGT", raw[colon + 1]) : nullptr;
+    uint32_t code = 0;
+    if (!base || !raw[colon + 1] || !parse_code(raw.substr(0, colon), &code)) throw Error(MKP_E_INVALID, "invalid assignment " + raw
+        + ", should be <code>:<DNA>, such as m:C");
+    codes->push_back(code); bases->push_back((uint8_t)(base - "ACGT"));
+  }
+}
+
+// the regions, tids = their chroms in order of first appearance
+struct DmrRegions { mkp_region_set set; std::vector<std::string> chroms; };
+DmrRegions dmr_load_regions(const std::string& path) {
+  DmrRegions R; std::map<std::string, int> tids;
+  R.set = parse_dmr_regions_bed(path, [&](const std::string& chrom) {
+    auto it = tids.find(chrom);
+    if (it == tids.end()) { it = tids.emplace(chrom, (int)R.chroms.size()).first; R.chroms.push_back(chrom); }
+    return it->second; });
+  return R;
+}
+
+// per contig of the regions that the FASTA holds: the bytes from its lowest region start to its highest region end, once
+void dmr_upload_reference(mkp_ctx* ctx, const DmrRegions& R, const Fasta& fasta) {
+  for (size_t tid = 0; tid < R.chroms.size(); tid++) {
+    const FastaSeq* seq = fasta.get(R.chroms[tid]);
+    if (!seq) continue;
+    uint32_t lo = 0xffffffffu, hi = 0;
+    for (const mkp_region& g : R.set.regions) if (g.tid == (int32_t)tid) {
+      if (g.end > seq->size()) throw Error(MKP_E_INVALID, "region " + R.chroms[tid] + ":" + std::to_string(g.start) + "-" + std::to_string(g.end)
+          + " ends beyond the contig in the reference FASTA (" + std::to_string(seq->size()) + " bases)");
+      lo = std::min(lo, g.start); hi = std::max(hi, g.end);
+    }
+    if (hi < lo) hi = lo;
+    must(ctx, mkp_dmr_set_reference(ctx, (int32_t)tid, (const uint8_t*)seq->data() + lo, lo, hi - lo));
+  }
+}
+
+// MKP_HOST_BEDMETHYL=1: the host reader and mkp_dmr_add_rows; otherwise the device reader takes the file
+void dmr_read_table(mkp_ctx* ctx, int sample, const std::string& path, const DmrRegions& R, bool host_read) {
+  if (!host_read) {
+    std::vector<const char*> names; for (const std::string& s : R.chroms) names.push_back(s.c_str());
+    must(ctx, mkp_dmr_add_file(ctx, sample, path.c_str(), names.data(), (uint32_t)names.size(), nullptr));
+    return;
+  }
+  const mkp_bedmethyl_file f = read_bedmethyl_text(path);
+  for (size_t k = 0; k < f.runs.size(); k++) {
+    const auto it = std::find(R.chroms.begin(), R.chroms.end(), f.runs[k].chrom);
+    if (it == R.chroms.end()) continue;
+    const mkp_rows rows = f.rows_of(k);
+    must(ctx, mkp_dmr_add_rows(ctx, sample, (int32_t)(it - R.chroms.begin()), &rows));
+  }
+}
+
+// RoiIter::new (src/dmr/util.rs:180-248): a region on a contig that a table lacks is dropped, with a word (warn) or fatally (fail)
+void dmr_handle_missing(const DmrArgs& d, const DmrRegions& R, const mkp_dmr_out& t) {
+  std::set<std::string> said; uint32_t kept = 0;
+  for (uint32_t r = 0; r < t.n_regions; r++) {
+    if (t.contig_has_rows[0][r] && t.contig_has_rows[1][r]) { kept++; continue; }
+    const std::string which = t.contig_has_rows[1][r] ? "a" : "'a' and 'b'";
+    if (d.missing == "fail") throw Error(MKP_E_INVALID, "chrom " + R.set.chrom[r] + " is missing from " + which + " bedMethyl index, fatal error");
+    if (d.missing == "warn" && said.insert(R.set.chrom[r]).second) fprintf(stderr, "[mkpileup] dmr pair: chrom %s is missing from %s bedMethyl, discarding\n",
+        R.set.chrom[r].c_str(), which.c_str());
+  }
+  if (!kept) throw Error(MKP_E_INVALID, "no valid regions in input");
+}
+
+}  // namespace
+
+extern "C" int mkp_dmr_pair_main(int argc, const char* const* argv, uint64_t* n_written, char* errbuf, size_t errbuf_len) {
+  if (n_written) *n_written = 0;
+  return guarded_buf(errbuf, errbuf_len, [&]() {
+    const DmrArgs d = parse_dmr_args(argc, argv);
+    std::vector<uint32_t> codes; std::vector<uint8_t> code_bases; dmr_code_lookup(d, &codes, &code_bases);
+    const bool to_stdout = d.out.empty() || d.out == "-" || d.out == "stdout";
+    struct stat sb;
+    if (!to_stdout && !d.force && stat(d.out.c_str(), &sb) == 0) throw Error(MKP_E_IO, "refusing to overwrite existing file " + d.out);
+    auto t_all = std::chrono::steady_clock::now();
+    const DmrRegions R = dmr_load_regions(d.regions);
+    const Fasta fasta = Fasta::load(d.ref);
+    const double load_ms = ms_since(t_all);
+    mkp_config cfg; memset(&cfg, 0, sizeof(cfg)); cfg.device = d.device;
+    mkp_ctx* ctx = nullptr;
+    if (mkp_ctx_create(&cfg, &ctx) != MKP_OK) throw Error(MKP_E_DEVICE, "no usable gfx950 device (libmkpileup has no CPU path)");
+    struct OwnedCtx { mkp_ctx* c; ~OwnedCtx() { mkp_ctx_destroy(c); } } owned{ctx};
+    must(ctx, mkp_dmr_begin(ctx, R.set.regions.data(), (uint32_t)R.set.regions.size(), d.bases.data(), (uint32_t)d.bases.size(), codes.data(),
+        code_bases.data(), (uint32_t)codes.size(), d.min_cov, d.mask ? 1 : 0));
+    if (d.stats) must(ctx, mkp_internal_dmr_timing(ctx, 1, nullptr));
+    auto t_ref = std::chrono::steady_clock::now();
+    dmr_upload_reference(ctx, R, fasta);
+    const double ref_ms = ms_since(t_ref);
+    auto t_read = std::chrono::steady_clock::now();
+    const bool host_read = Knobs::one("MKP_HOST_BEDMETHYL");
+    dmr_read_table(ctx, 0, d.a[0], R, host_read);
+    dmr_read_table(ctx, 1, d.b[0], R, host_read);
+    const double read_ms = ms_since(t_read);
+    auto t_out = std::chrono::steady_clock::now();
+    mkp_dmr_out t; must(ctx, mkp_dmr_get(ctx, &t));
+    dmr_handle_missing(d, R, t);
+    const std::string text = dmr_table_text(R.set, t, d.header, f32_display);
+    if (to_stdout) { if (fwrite(text.data(), 1, text.size(), stdout) != text.size()) throw Error(MKP_E_IO, "short write on stdout"); fflush(stdout); }
+    else write_text_file(d.out, text);
+    uint64_t written = 0; for (uint32_t r = 0; r < t.n_regions; r++) if (t.state[r] == MKP_DMR_WRITTEN) written++;
+    if (n_written) *n_written = written;
+    if (d.stats) { double ms[2] = {0, 0}; mkp_internal_dmr_timing(ctx, 0, ms);
+      double in_ms[4] = {0, 0, 0, 0}; uint64_t pieces = 0; mkp_internal_bedmethyl_in_stats(ctx, 1, in_ms, &pieces);
+      fprintf(stderr, "[mkpileup] dmr pair: %u regions, written=%llu; reader=%s regions+fasta_ms=%.1f reference_upload_ms=%.1f read_ms=%.1f (file read %.1f, upload %.1f, inflate %.1f, parse %.1f; %llu pieces) kernels: bounds+scan %.3f ms, reduce %.3f ms; score+text_ms=%.1f total_ms=%.1f\n",
+          t.n_regions, (unsigned long long)written, host_read ? "host" : "device", load_ms, ref_ms, read_ms, in_ms[0], in_ms[1], in_ms[2], in_ms[3],
+          (unsigned long long)pieces, ms[0], ms[1], ms_since(t_out), ms_since(t_all)); }
     return MKP_OK;
   });
 }

@@ -106,7 +106,7 @@ hipError_t mkp_launch_ingest_pack(hipStream_t st, const uint8_t* raw, uint32_t r
     uint32_t* cigar, uint16_t* cigar16, uint32_t* chunk_pfx, uint8_t* seq, MkpTagRef* tagref, uint32_t* ranks, uint8_t* ml, MkpRecDigest* dig,
     MkpIngestTotals* tot);
 
-// ---- mkp_stats.hip, mkp_localize.hip: pos .. n_mod are row columns, n_rows rows; row_lo / row_hi: first row of a region and the row behind
+// ---- mkp_stats.hip, mkp_dmr.hip, mkp_localize.hip: pos .. n_mod are row columns, n_rows rows; row_lo / row_hi: first row of a region and the row behind
 // its last; ev: 3 timing events or NULL
 // n_chunks / off / total: chunks per region, their offsets and total; out: the run's table, seen: its masks, codes: its slot codes;
 // min_cov: least coverage of a counted row; fixed_codes: the code list is fixed
@@ -114,6 +114,12 @@ hipError_t mkp_launch_region_stats(hipStream_t st, const uint32_t* pos, const ui
     const uint32_t* n_mod, uint32_t n_rows, const MkpStatsRegion* regions, uint32_t n_regions, uint32_t* row_lo, uint32_t* row_hi, uint32_t* n_chunks,
     unsigned long long* off, unsigned long long* total, unsigned long long* out, uint32_t* seen, uint32_t* codes, uint32_t* err,
     unsigned long long min_cov, uint32_t fixed_codes, hipEvent_t* ev);
+// mkp_dmr.hip: as mkp_launch_region_stats, with the n_canonical column; ref: the contig's reference bytes [ref_off, ref_off + ref_len) (NULL
+// with ref_len 0: no position has a base); prm: host copy; out / seen: ONE sample's lines of the run's table
+hipError_t mkp_launch_dmr(hipStream_t st, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
+    const uint32_t* n_mod, const uint32_t* n_can, uint32_t n_rows, const MkpStatsRegion* regions, uint32_t n_regions, uint32_t* row_lo,
+    uint32_t* row_hi, uint32_t* n_chunks, unsigned long long* off, unsigned long long* total, const uint8_t* ref, uint32_t ref_off, uint32_t ref_len,
+    const MkpDmrParams* prm, unsigned long long* out, uint32_t* seen, uint32_t* codes, uint32_t* err, hipEvent_t* ev);
 // tab: the run's table, codes: its slot codes
 hipError_t mkp_launch_localize(hipStream_t st, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
     const uint32_t* n_mod, uint32_t n_rows, const MkpLocRegion* regions, uint32_t n_regions, uint32_t* row_lo, uint32_t* row_hi, uint32_t window,

@@ -69,13 +69,17 @@ struct BedLineParser {
   }
 };
 
-// The regions BED as the reference's two loaders read it: the same line loop under two sets of rules.
+// The regions BED as the reference's three loaders read it: the same line loop under three sets of rules.
 //   stats (EntryStats::run): the parser is picked by the TAB-separated fields of the first line that does not start with '#'; a line that
 //     fails is fatal; start <= end is checked, and a quote in a name is refused (the table writer does not quote).
 //   localize (load_focus_regions up to its contig filters, src/localise/subcommand.rs:105-162): picked by the WHITESPACE-separated fields
 //     (split_whitespace: runs of any blank count once, leading ones not at all); a line that fails is counted, not fatal; there is no
 //     start <= end check, so start is held to 32 bits as well.
-template <class TidOf> mkp_region_set parse_bed_regions(const std::string& path, TidOf tid_of, bool localize, uint32_t* n_skipped) {
+//   dmr (parse_roi_bed, src/dmr/util.rs:389-428): as stats, but the '#' lines in front of the first other line are skipped, not parsed,
+//     and a quote in a name is written as it is (the table goes through format!, not the csv writer).
+enum class BedRules { stats, localize, dmr };
+template <class TidOf> mkp_region_set parse_bed_regions(const std::string& path, TidOf tid_of, BedRules rules, uint32_t* n_skipped) {
+  const bool localize = rules == BedRules::localize;
   std::ifstream f(path, std::ios::binary);
   if (!f) throw Error(MKP_E_IO, "failed to open regions BED " + path);
   std::vector<std::string> lines; std::string line;
@@ -90,7 +94,7 @@ template <class TidOf> mkp_region_set parse_bed_regions(const std::string& path,
   } else { fields = 1; for (char c : lines[first]) if (c == '\t') fields++; }
   const bool stranded = fields > 4;
   mkp_region_set out; uint32_t skipped = 0;
-  for (size_t k = 0; k < lines.size(); k++) {
+  for (size_t k = rules == BedRules::dmr ? first : 0; k < lines.size(); k++) {
     BedLineParser p(lines[k]); std::string chrom, name; uint64_t s = 0, e = 0; uint8_t rule = 3;
     bool ok = p.string(&chrom) && p.digits(&s) && p.digits(&e);
     bool has_name = false;
@@ -103,7 +107,7 @@ template <class TidOf> mkp_region_set parse_bed_regions(const std::string& path,
     }
     if (!localize && s > e) throw Error(MKP_E_INVALID, where() + ": start > end");
     if (e > 0xffffffffull || (localize && s > 0xffffffffull)) throw Error(MKP_E_UNSUPPORTED, where() + ": coordinate beyond 2^32 - 1");
-    if (!localize) for (const std::string* t : {&chrom, &name}) if (t->find('"') != std::string::npos) throw Error(MKP_E_UNSUPPORTED, where()
+    if (rules == BedRules::stats) for (const std::string* t : {&chrom, &name}) if (t->find('"') != std::string::npos) throw Error(MKP_E_UNSUPPORTED, where()
         + ": a quote in the contig or region name needs csv quoting, which is not written");
     mkp_region g; memset(&g, 0, sizeof(g)); g.tid = (int32_t)tid_of(chrom); g.start = (uint32_t)s; g.end = (uint32_t)e; g.strand_rule = rule;
     out.regions.push_back(g); out.chrom.push_back(chrom); out.name.push_back(has_name ? name : ".");
@@ -114,10 +118,13 @@ template <class TidOf> mkp_region_set parse_bed_regions(const std::string& path,
   return out;
 }
 template <class TidOf> mkp_region_set parse_regions_bed(const std::string& path, TidOf tid_of) {
-  return parse_bed_regions(path, tid_of, false, nullptr);
+  return parse_bed_regions(path, tid_of, BedRules::stats, nullptr);
 }
 template <class TidOf> mkp_region_set parse_localize_regions_bed(const std::string& path, TidOf tid_of, uint32_t* n_skipped) {
-  return parse_bed_regions(path, tid_of, true, n_skipped);
+  return parse_bed_regions(path, tid_of, BedRules::localize, n_skipped);
+}
+template <class TidOf> mkp_region_set parse_dmr_regions_bed(const std::string& path, TidOf tid_of) {
+  return parse_bed_regions(path, tid_of, BedRules::dmr, nullptr);
 }
 
 inline std::string code_text(uint32_t code) { return (code & 0x80000000u) ? std::to_string(code & 0x7fffffffu) : std::string(1, (char)code); }

@@ -14,53 +14,12 @@
 // The table out[region][slot] lives for the whole run: pieces (shards) add into it, so a region that straddles seams gets every row once.
 // Code slots: at most MKP_STATS_MAX_CODES per run.  With a fixed list the host uploads the table and other codes are not counted; without
 // one, the first counted row of a code claims a free entry with a compare-and-swap (order does not matter, the host sorts): resolve_slot
-// of mkp_dev_codeslots.hpp, which also holds the two searches of the bounds kernel; both are shared with mkp_localize.hip.
-#include "mkp_dev_codeslots.hpp"
+// of mkp_dev_codeslots.hpp, which also holds the two searches of the bounds kernel; both are shared with mkp_localize.hip.  The bounds and
+// scan kernels and the butterfly live in mkp_dev_chunks.hpp: mkp_dmr.hip runs the same scheme.
+#include "mkp_dev_chunks.hpp"
 #include "mkp_launch.h"
 
 namespace {
-
-constexpr uint32_t kChunk = MKP_STATS_CHUNK;
-
-__global__ __launch_bounds__(256) void mkp_stats_bounds(const uint32_t* __restrict__ pos, uint32_t n_rows, const MkpStatsRegion* __restrict__ regions,
-    uint32_t n_regions, uint32_t* __restrict__ row_lo, uint32_t* __restrict__ row_hi, uint32_t* __restrict__ n_chunks) {
-  const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n_regions) return;
-  const MkpStatsRegion g = regions[r];
-  uint32_t lo, hi;
-  row_range(pos, n_rows, g.start, g.end, &lo, &hi);
-  row_lo[r] = lo; row_hi[r] = hi; n_chunks[r] = (hi - lo + kChunk - 1) / kChunk;
-}
-
-// off[r] = chunks of the regions before r, off[n_regions] = *total = all of them (64-bit: a million regions of a whole chromosome each)
-__global__ __launch_bounds__(1024) void mkp_stats_scan(const uint32_t* __restrict__ n_chunks, uint32_t n_regions, unsigned long long* __restrict__ off,
-    unsigned long long* __restrict__ total) {
-  __shared__ unsigned long long part[1024];
-  const uint32_t t = threadIdx.x, per = (n_regions + 1023u) / 1024u;
-  const uint32_t r0 = min(t * per, n_regions), r1 = min(r0 + per, n_regions);
-  unsigned long long mine = 0;
-  for (uint32_t r = r0; r < r1; r++) mine += n_chunks[r];
-  part[t] = mine;
-  __syncthreads();
-  for (uint32_t d = 1; d < 1024u; d <<= 1) {
-    const unsigned long long add = t >= d ? part[t - d] : 0ull;
-    __syncthreads();
-    part[t] += add;
-    __syncthreads();
-  }
-  unsigned long long run = part[t] - mine;
-  for (uint32_t r = r0; r < r1; r++) { off[r] = run; run += n_chunks[r]; }
-  if (t == 1023u) { off[n_regions] = part[t]; *total = part[t]; }
-}
-
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, d, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), d, 64);
-    v += ((unsigned long long)hi << 32) | lo;
-  }
-  return v;
-}
 
 __global__ __launch_bounds__(256) void mkp_stats_reduce(const uint32_t* __restrict__ info, const uint32_t* __restrict__ code,
     const uint32_t* __restrict__ n_valid, const uint32_t* __restrict__ n_mod, const MkpStatsRegion* __restrict__ regions, uint32_t n_regions,
@@ -71,9 +30,7 @@ __global__ __launch_bounds__(256) void mkp_stats_reduce(const uint32_t* __restri
   const unsigned long long n_waves = (unsigned long long)gridDim.x * (blockDim.x >> 6), total = *total_p;
   uint32_t tab = load_codes(codes, lane);   // the code table as this wave last saw it
   for (unsigned long long w = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); w < total; w += n_waves) {
-    // the region of item w: the last one whose offset is <= w (regions without rows share their successor's offset and are never found)
-    uint32_t a = 0, b = n_regions;   // off[a] <= w < off[b]
-    while (b - a > 1) { const uint32_t mid = a + ((b - a) >> 1); if (off[mid] <= w) a = mid; else b = mid; }
+    const uint32_t a = item_region(off, n_regions, w);
     const MkpStatsRegion g = regions[a];
     const uint32_t first = row_lo[a] + (uint32_t)(w - off[a]) * kChunk, last = min(first + kChunk, row_hi[a]);
     unsigned long long am[kSlots], av[kSlots];

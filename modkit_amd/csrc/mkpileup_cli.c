@@ -1,6 +1,7 @@
 /* mkpileup — command-line front end of libmkpileup: `mkpileup pileup in.bam out.bed [modkit pileup flags]`,
  * `mkpileup pileup-hemi in.bam -o out.bed [modkit pileup-hemi flags]`, `mkpileup extract calls in.bam out.tsv [flags]`,
- * `mkpileup bedmethyl merge a.bed b.bed [c.bed ..] -g sizes.tsv -o out.bed [--force] [--bgzf]`. */
+ * `mkpileup bedmethyl merge a.bed b.bed [c.bed ..] -g sizes.tsv -o out.bed [--force] [--bgzf]`,
+ * `mkpileup dmr pair -a a.bed -b b.bed -r regions.bed --ref ref.fa --base C [-o out.bed] [flags of the region form of modkit dmr pair]`. */
 #include <stdio.h>
 #include <string.h>
 #include "mkpileup.h"
@@ -13,6 +14,13 @@ int main(int argc, char** argv) {
     if (rc != MKP_OK) { fprintf(stderr, "Error! %s (status %d)\n", err, rc); return 1; }
     return 0;
   }
+  if (argc >= 3 && strcmp(argv[1], "dmr") == 0) {
+    int rc = MKP_E_UNSUPPORTED;
+    if (strcmp(argv[2], "pair") == 0) rc = mkp_dmr_pair_main(argc - 3, (const char* const*)(argv + 3), NULL, err, sizeof(err));
+    else snprintf(err, sizeof(err), "dmr %s is not offered: only `dmr pair` over the regions of -r", argv[2]);
+    if (rc != MKP_OK) { fprintf(stderr, "Error! %s (status %d)\n", err, rc); return 1; }
+    return 0;
+  }
   if (extract) {
     int rc = mkp_extract_calls_main(argc - 3, (const char* const*)(argv + 3), err, sizeof(err));
     if (rc != MKP_OK) { fprintf(stderr, "Error! %s (status %d)\n", err, rc); return 1; }
@@ -22,7 +30,9 @@ int main(int argc, char** argv) {
     fprintf(stderr, "usage: mkpileup pileup <in.bam> <out.bed> [flags of `modkit pileup`] [--device N] [--stats]\n"
                     "       mkpileup pileup-hemi <in.bam> -o <out.bed> [flags of `modkit pileup-hemi`] [--device N] [--stats]\n"
                     "       mkpileup extract calls <in.bam> <out.tsv> [flags of `modkit extract calls`] [--device N] [--stats]\n"
-                    "       mkpileup bedmethyl merge <a.bed> <b.bed> [..] -g <sizes.tsv> -o <out.bed> [--force] [--bgzf] [--device N] [--stats]\n");
+                    "       mkpileup bedmethyl merge <a.bed> <b.bed> [..] -g <sizes.tsv> -o <out.bed> [--force] [--bgzf] [--device N] [--stats]\n"
+                    "       mkpileup dmr pair -a <a.bed[.gz]> -b <b.bed[.gz]> -r <regions.bed> --ref <ref.fa> --base C [--base A ..] [-o <out.bed>] [-f]\n"
+                    "                [--header] [--min-valid-coverage N] [--assign-code x:C] [--mask] [--missing quiet|warn|fail] [--device N] [--stats]\n");
     return 2;
   }
   int rc = hemi ? mkp_pileup_hemi_main(argc - 2, (const char* const*)(argv + 2), err, sizeof(err)) : mkp_pileup_main(argc - 2,
