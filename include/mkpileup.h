@@ -563,7 +563,7 @@ int mkp_bedmethyl_merge_main(int argc, const char* const* argv, uint64_t* n_writ
  * pairwise.rs, bedmethyl.rs:172-267, llr_model.rs, genome_positions.rs:91-127): every region scored for differential methylation between
  * two bedMethyl tables.  The rows are filtered, grouped by position, checked and summed on the device from row columns that are in HBM
  * (mkp_dmr.hip); the table of sums lives there from mkp_dmr_begin to mkp_dmr_get and every add call adds into it.  Only the region form
- * of one `a` against one `b`: single-site mode, --segment and `dmr multi` are not offered.
+ * of one `a` against one `b`: single-site mode is mkp_dmr_sites_* below, --segment and `dmr multi` are not offered.
  *   mkp_dmr_begin           regions as mkp_stats_begin takes them; bases = the `--base` letters (each of ACGT, at least one); codes /
  *                           code_bases = the code -> base table, n_lookup entries (mkp_dmr_default_lookup gives MOD_CODE_TO_DNA_BASE; a
  *                           later entry for a code replaces an earlier one, as `--assign-code` does; at most 64 distinct codes);
@@ -617,6 +617,66 @@ int mkp_host_parse_dmr_regions(const char* bed_path, const char* const* contig_n
 int mkp_host_dmr_judge(const mkp_dmr_out* counts, double* score, uint8_t* state);
 int mkp_host_dmr_table(const mkp_region_set* set, const mkp_dmr_out* counts, int with_header, const char* out_path);
 int mkp_dmr_pair_main(int argc, const char* const* argv, uint64_t* n_written, char* errbuf, size_t errbuf_len);
+
+/* ---- `modkit dmr pair -a a.bed.gz -b b.bed.gz --ref ref.fa --base C` without -r (SingleSiteDmrAnalysis::run, src/dmr/single_site.rs;
+ * beta_diff.rs, llr_model.rs): the two tables compared position by position; every site both hold gets the likelihood-ratio score and the
+ * MAP-based p-value with its effect size, in f64 on the device (mkp_dmr_sites.hip, one lane a site).  One `a` against one `b`; replicates
+ * and --segment are not offered.  Both tables' row columns stay in HBM per contig from the add calls to mkp_dmr_sites_get (24 B a row); a
+ * pair of tables beyond the budget of 3/4 of the device's memory is MKP_E_UNSUPPORTED.
+ *   mkp_dmr_sites_begin          cfg: contig_names[tid] (contigs are walked in byte order of their names); bases / codes / code_bases /
+ *                                min_valid_coverage / respect_mask as mkp_dmr_begin; prior Beta(prior_alpha, prior_beta) (alpha + beta < 1
+ *                                is MKP_E_INVALID); delta = the region of practical equivalence; have_max_coverages != 0: max_coverages =
+ *                                `--max-coverages`, otherwise they are estimated from the first n_sample_records participating rows
+ *                                (calculate_max_coverages); either way capped at 300; interval_size and batch_size shape the reference's
+ *                                batches (below).
+ *   mkp_dmr_sites_set_reference  the WHOLE sequence of contig tid, any time before mkp_dmr_sites_get.  A contig without it is one the FASTA lacks.
+ *   mkp_dmr_sites_add_rows       rows of sample 0 (a) or 1 (b), one contig per call, ascending pos, pieces of a contig in ascending order (a
+ *                                seam may cut a position: the contig's pieces are joined in HBM); the six columns mkp_dmr_add_rows reads.
+ *   mkp_dmr_sites_add_file       a whole bedMethyl file, plain or bgzip, through the device reader, as mkp_dmr_add_file.
+ *   mkp_dmr_sites_get            runs the stages and returns the written sites by contig (sorted by name), then position.  The contigs are
+ *                                those with a reference and rows in both samples; none is MKP_E_INVALID ("need at least 1 contig").  A row
+ *                                takes part as in mkp_dmr_add_rows under a '.' rule.  The reference's walk cuts every contig into windows
+ *                                of interval_size bp; a batch collects windows until it holds interval_size listed positions (it may run
+ *                                on into the next contig), batch_size batches are a super-batch.  A position whose participating rows
+ *                                fail aggregate_counts drops its whole batch for both samples (n_batches_dropped).  A site whose score or
+ *                                p-value fails in the reference is not written (n_model_failures).  n_mod[s][site * n_codes + k],
+ *                                has_code[s][site] = mask of the code columns in the sample's key set; n_sampled = the coverages the
+ *                                estimate drew per sample (0 with given max coverages).  Arrays owned by the ctx until its next
+ *                                mkp_dmr_sites_begin; the session stays open and may be run again.
+ * Host-only: mkp_host_dmr_site_score = the arithmetic of one site as the kernel does it (mkp_dmr_site_math.hpp): values[5] = score,
+ *   ln_effect, ln_null, map_pvalue, effect_size (NaN where the reference does not compute one); *failed = the reference fails on the site.
+ *   mkp_host_dmr_sites_batches = the batch planner alone: contig_len[c] and, one contig behind the other, the listed positions per window
+ *   (max(1, ceil(len / interval_size)) windows a contig); entries (at most one per window; cap of them are written) say where a batch
+ *   begins inside a contig; returns their number (or a negative status), *n_batches the batches.  mkp_host_dmr_sites_gauss_legendre = the 16 nodes and weights.
+ *   mkp_host_dmr_sites_table writes SingleSiteDmrScore::header(false, false) / to_row_pair: 16 tab-separated columns, the three f64 values
+ *   through f64 Display.
+ * mkp_dmr_sites_main = `mkpileup dmr sites -a a.bed[.gz] -b b.bed[.gz] --ref ref.fa --base C [--base A ..] [-o out.bed] [-f] [--header]
+ *   [--min-valid-coverage N] [--assign-code x:C] [--mask] [--prior ALPHA BETA] [--delta D] [--max-coverages A B] [-N/--n-sample-records N]
+ *   [--cap-coverages] [-i/--interval-size BP] [--batch-size N | -t/--threads T] [--device N] [--stats]`; *n_written (may be NULL) = the sites
+ *   written.  -r is MKP_E_INVALID (that is `dmr pair`), --segment and more than one -a / -b are MKP_E_UNSUPPORTED. */
+typedef struct { const char* const* contig_names; uint32_t n_contigs; const char* bases; uint32_t n_bases; const uint32_t* codes;
+                 const uint8_t* code_bases; uint32_t n_lookup; uint32_t respect_mask; uint64_t min_valid_coverage; double prior_alpha, prior_beta,
+                 delta; uint32_t have_max_coverages; uint32_t max_coverages[2]; uint32_t reserved; uint64_t n_sample_records, interval_size,
+                 batch_size; } mkp_dmr_sites_config;
+typedef struct { uint64_t n_sites; uint32_t n_codes, reserved; const uint32_t* code_repr;   /* sorted */
+                 const int32_t* tid; const uint32_t* pos; const uint8_t* strand;             /* per site; strand '+' or '-' */
+                 const uint32_t* total[2]; const uint32_t* n_mod[2]; const uint32_t* has_code[2];
+                 const double* score; const double* map_pvalue; const double* effect_size;
+                 uint32_t max_coverages[2]; uint64_t n_sampled[2]; uint64_t n_batches, n_batches_dropped, n_model_failures; } mkp_dmr_sites_out;
+typedef struct { uint32_t contig, reserved; uint64_t start, batch; } mkp_dmr_sites_batch;
+int mkp_dmr_sites_begin(mkp_ctx* ctx, const mkp_dmr_sites_config* cfg);
+int mkp_dmr_sites_set_reference(mkp_ctx* ctx, int32_t tid, const uint8_t* bytes, uint64_t len);
+int mkp_dmr_sites_add_rows(mkp_ctx* ctx, int sample, int32_t tid, const mkp_rows* rows);
+int mkp_dmr_sites_add_file(mkp_ctx* ctx, int sample, const char* path, uint64_t* n_rows);
+int mkp_dmr_sites_get(mkp_ctx* ctx, mkp_dmr_sites_out* out);
+int mkp_host_dmr_site_score(const uint64_t* a_mod, uint32_t a_has, uint64_t a_total, const uint64_t* b_mod, uint32_t b_has, uint64_t b_total,
+                            uint32_t n_codes, double prior_alpha, double prior_beta, double delta, const uint32_t max_coverages[2], double values[5],
+                            int* failed);
+int mkp_host_dmr_sites_batches(const uint64_t* contig_len, const uint32_t* window_counts, uint32_t n_contigs, uint64_t interval_size,
+                               mkp_dmr_sites_batch* entries, uint64_t cap, uint64_t* n_batches);
+int mkp_host_dmr_sites_gauss_legendre(double nodes[16], double weights[16]);
+int mkp_host_dmr_sites_table(const mkp_dmr_sites_out* sites, const char* const* contig_names, uint32_t n_contigs, int with_header, const char* out_path);
+int mkp_dmr_sites_main(int argc, const char* const* argv, uint64_t* n_written, char* errbuf, size_t errbuf_len);
 
 /* ---- BGZF inflate on the device as a call of its own.  On the pileup path the same kernels run inside the device ingest
  * (`mkp_pileup_main` on an indexed BAM: compressed blocks up, inflate + CRC-32 + record cut + MM/ML tokeniser + packing in HBM, a digest

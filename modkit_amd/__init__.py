@@ -147,6 +147,19 @@ def lib():
             L.mkp_host_dmr_judge.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), u8p]
             L.mkp_host_dmr_table.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p]
             L.mkp_dmr_pair_main.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), u64p, ctypes.c_char_p, ctypes.c_size_t]
+        if hasattr(L, "mkp_dmr_sites_begin"):
+            u32p, f64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)
+            L.mkp_dmr_sites_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            L.mkp_dmr_sites_set_reference.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_uint64]
+            L.mkp_dmr_sites_add_rows.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p]
+            L.mkp_dmr_sites_add_file.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, u64p]
+            L.mkp_dmr_sites_get.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            L.mkp_host_dmr_site_score.argtypes = [u64p, ctypes.c_uint32, ctypes.c_uint64, u64p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32,
+                                                  ctypes.c_double, ctypes.c_double, ctypes.c_double, u32p, f64p, ctypes.POINTER(ctypes.c_int)]
+            L.mkp_host_dmr_sites_batches.argtypes = [u64p, u32p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, u64p]
+            L.mkp_host_dmr_sites_gauss_legendre.argtypes = [f64p, f64p]
+            L.mkp_host_dmr_sites_table.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p]
+            L.mkp_dmr_sites_main.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), u64p, ctypes.c_char_p, ctypes.c_size_t]
         # the structs this binding allocates mirror ONE revision of include/mkpileup.h: a library of another revision would write past them
         if os.environ.get("MKP_LIB_PATH") and not hasattr(L, "mkp_abi_version"):
             _lib = L   # (A/B runs against a build from before the query existed, tools/dbg/ab.sh)
@@ -181,7 +194,9 @@ EXPORTS = ["mkp_ctx_create", "mkp_ctx_destroy", "mkp_last_error", "mkp_version",
            "mkp_bedmethyl_file_runs", "mkp_bedmethyl_file_chrom", "mkp_bedmethyl_file_rows", "mkp_bedmethyl_file_free", "mkp_bedmethyl_merge_main",
            "mkp_merge_add_file", "mkp_bedmethyl_read_device", "mkp_bedmethyl_chunk_bytes",
            "mkp_dmr_default_lookup", "mkp_dmr_begin", "mkp_dmr_set_reference", "mkp_dmr_add_rows", "mkp_dmr_add_file", "mkp_dmr_add_resident", "mkp_dmr_get",
-           "mkp_host_parse_dmr_regions", "mkp_host_dmr_judge", "mkp_host_dmr_table", "mkp_dmr_pair_main"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
+           "mkp_host_parse_dmr_regions", "mkp_host_dmr_judge", "mkp_host_dmr_table", "mkp_dmr_pair_main",
+           "mkp_dmr_sites_begin", "mkp_dmr_sites_set_reference", "mkp_dmr_sites_add_rows", "mkp_dmr_sites_add_file", "mkp_dmr_sites_get",
+           "mkp_host_dmr_site_score", "mkp_host_dmr_sites_batches", "mkp_host_dmr_sites_gauss_legendre", "mkp_host_dmr_sites_table", "mkp_dmr_sites_main"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
 
 
 def pileup(argv):
@@ -236,6 +251,23 @@ def dmr_pair(argv):
     err = ctypes.create_string_buffer(2048)
     written = ctypes.c_uint64(0)
     rc = L.mkp_dmr_pair_main(len(args), arr, ctypes.byref(written), err, len(err))
+    if rc != MKP_OK:
+        raise MkpError(rc, err.value.decode(errors="replace"))
+    return int(written.value)
+
+
+def dmr_sites(argv):
+    """`modkit dmr pair` without -r (SingleSiteDmrAnalysis::run, src/dmr/single_site.rs) on the device: argv = ["-a", a.bed[.gz], "-b", b.bed[.gz],
+    "--ref", ref.fa, "--base", "C", "-o", out.bed, "-f", "--header", "--min-valid-coverage", N, "--assign-code", "x:C", "--mask", "--prior", A, B,
+    "--delta", D, "--max-coverages", A, B, "-N", N, "--cap-coverages", "-i", BP, "--batch-size", N, "-t", T]; the tables are read by the device
+    reader (Context.dmr_sites_add_file; MKP_HOST_BEDMETHYL=1: by the host reader).  -r, --segment and more than one -a / -b are refused.
+    Returns the number of sites written."""
+    L = lib()
+    args = [str(a).encode() for a in argv]
+    arr = (ctypes.c_char_p * max(1, len(args)))(*args)
+    err = ctypes.create_string_buffer(2048)
+    written = ctypes.c_uint64(0)
+    rc = L.mkp_dmr_sites_main(len(args), arr, ctypes.byref(written), err, len(err))
     if rc != MKP_OK:
         raise MkpError(rc, err.value.decode(errors="replace"))
     return int(written.value)
@@ -306,6 +338,95 @@ class DmrOut(ctypes.Structure):
                 ("total", ctypes.POINTER(ctypes.c_uint64) * 2), ("n_rows", ctypes.POINTER(ctypes.c_uint64) * 2),
                 ("bad", ctypes.POINTER(ctypes.c_uint8) * 2), ("contig_has_rows", ctypes.POINTER(ctypes.c_uint8) * 2),
                 ("has_reference", ctypes.POINTER(ctypes.c_uint8)), ("score", ctypes.POINTER(ctypes.c_double)), ("state", ctypes.POINTER(ctypes.c_uint8))]
+
+
+class DmrSitesConfig(ctypes.Structure):
+    """mkp_dmr_sites_config"""
+    _fields_ = [("contig_names", ctypes.POINTER(ctypes.c_char_p)), ("n_contigs", ctypes.c_uint32), ("bases", ctypes.c_char_p), ("n_bases", ctypes.c_uint32),
+                ("codes", ctypes.POINTER(ctypes.c_uint32)), ("code_bases", ctypes.POINTER(ctypes.c_uint8)), ("n_lookup", ctypes.c_uint32),
+                ("respect_mask", ctypes.c_uint32), ("min_valid_coverage", ctypes.c_uint64), ("prior_alpha", ctypes.c_double),
+                ("prior_beta", ctypes.c_double), ("delta", ctypes.c_double), ("have_max_coverages", ctypes.c_uint32),
+                ("max_coverages", ctypes.c_uint32 * 2), ("reserved", ctypes.c_uint32), ("n_sample_records", ctypes.c_uint64),
+                ("interval_size", ctypes.c_uint64), ("batch_size", ctypes.c_uint64)]
+
+
+class DmrSitesOut(ctypes.Structure):
+    """mkp_dmr_sites_out: the written sites of `modkit dmr pair` without -r and the session's counters."""
+    _fields_ = [("n_sites", ctypes.c_uint64), ("n_codes", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("code_repr", ctypes.POINTER(ctypes.c_uint32)),
+                ("tid", ctypes.POINTER(ctypes.c_int32)), ("pos", ctypes.POINTER(ctypes.c_uint32)), ("strand", ctypes.POINTER(ctypes.c_uint8)),
+                ("total", ctypes.POINTER(ctypes.c_uint32) * 2), ("n_mod", ctypes.POINTER(ctypes.c_uint32) * 2),
+                ("has_code", ctypes.POINTER(ctypes.c_uint32) * 2), ("score", ctypes.POINTER(ctypes.c_double)),
+                ("map_pvalue", ctypes.POINTER(ctypes.c_double)), ("effect_size", ctypes.POINTER(ctypes.c_double)),
+                ("max_coverages", ctypes.c_uint32 * 2), ("n_sampled", ctypes.c_uint64 * 2), ("n_batches", ctypes.c_uint64),
+                ("n_batches_dropped", ctypes.c_uint64), ("n_model_failures", ctypes.c_uint64)]
+
+
+class DmrSitesBatch(ctypes.Structure):
+    """mkp_dmr_sites_batch: where a batch of the reference's walk begins inside a contig."""
+    _fields_ = [("contig", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("start", ctypes.c_uint64), ("batch", ctypes.c_uint64)]
+
+
+def host_dmr_site_score(a_mod, a_has, a_total, b_mod, b_has, b_total, prior=(0.55, 0.55), delta=0.05, max_coverages=(300, 300)):
+    """mkp_host_dmr_site_score: one site's arithmetic as the kernel does it; a_mod / b_mod = counts per code column (ascending code), a_has /
+    b_has = masks of the columns in the key set.  Returns ({"score", "ln_effect", "ln_null", "map_pvalue", "effect_size"}, failed)."""
+    n = len(a_mod)
+    am, bm = (ctypes.c_uint64 * max(1, n))(*a_mod), (ctypes.c_uint64 * max(1, n))(*b_mod)
+    mc, vals, failed = (ctypes.c_uint32 * 2)(*max_coverages), (ctypes.c_double * 5)(), ctypes.c_int(0)
+    rc = lib().mkp_host_dmr_site_score(am, int(a_has), int(a_total), bm, int(b_has), int(b_total), n, prior[0], prior[1], delta, mc, vals, ctypes.byref(failed))
+    if rc != MKP_OK:
+        raise MkpError(rc, "mkp_host_dmr_site_score failed")
+    return dict(zip(("score", "ln_effect", "ln_null", "map_pvalue", "effect_size"), list(vals))), bool(failed.value)
+
+
+def host_dmr_sites_batches(contig_lens, window_counts, interval_size):
+    """mkp_host_dmr_sites_batches: the batch planner alone; window_counts = per contig the listed positions per window.  Returns
+    ([(contig, start, batch)], number of batches)."""
+    flat = [x for w in window_counts for x in w]
+    lens = (ctypes.c_uint64 * max(1, len(contig_lens)))(*contig_lens)
+    cnt = (ctypes.c_uint32 * max(1, len(flat)))(*flat)
+    ent, nb = (DmrSitesBatch * max(1, len(flat)))(), ctypes.c_uint64(0)
+    n = lib().mkp_host_dmr_sites_batches(lens, cnt, len(contig_lens), int(interval_size), ent, len(flat), ctypes.byref(nb))
+    if n < 0:
+        raise MkpError(int(n), "mkp_host_dmr_sites_batches failed")
+    return [(int(ent[k].contig), int(ent[k].start), int(ent[k].batch)) for k in range(n)], int(nb.value)
+
+
+def host_dmr_sites_gauss_legendre():
+    """mkp_host_dmr_sites_gauss_legendre: (nodes, weights) of the 16-point rule on [-1, 1], nodes ascending."""
+    x, w = (ctypes.c_double * 16)(), (ctypes.c_double * 16)()
+    lib().mkp_host_dmr_sites_gauss_legendre(x, w)
+    return list(x), list(w)
+
+
+def dmr_sites_out_from(d):
+    """A DmrSitesOut over numpy copies of the dict Context.dmr_sites_get returns; returns (struct, arrays to keep alive)."""
+    import numpy as np
+    u32p, f64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)
+    keep = {"codes": np.ascontiguousarray(np.asarray(d["codes"], dtype=np.uint32)), "tid": np.ascontiguousarray(np.asarray(d["tid"], dtype=np.int32)),
+            "pos": np.ascontiguousarray(np.asarray(d["pos"], dtype=np.uint32)),
+            "strand": np.ascontiguousarray(np.asarray([ord(c) if isinstance(c, str) else int(c) for c in d["strand"]], dtype=np.uint8))}
+    o = DmrSitesOut(n_sites=len(keep["pos"]), n_codes=len(keep["codes"]), code_repr=keep["codes"].ctypes.data_as(u32p),
+                    tid=keep["tid"].ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), pos=keep["pos"].ctypes.data_as(u32p),
+                    strand=keep["strand"].ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    for f in ("total", "n_mod", "has_code"):
+        for s in range(2):
+            a = keep[f, s] = np.ascontiguousarray(np.asarray(d[f][s], dtype=np.uint32))
+            getattr(o, f)[s] = a.ctypes.data_as(u32p)
+    for f in ("score", "map_pvalue", "effect_size"):
+        keep[f] = np.ascontiguousarray(np.asarray(d[f], dtype=np.float64))
+        setattr(o, f, keep[f].ctypes.data_as(f64p))
+    return o, keep
+
+
+def write_dmr_sites_table(sites, contig_names, out_path, header=False):
+    """mkp_host_dmr_sites_table: the 16-column table of `sites` (the dict Context.dmr_sites_get returns, or one a caller filled)."""
+    o, keep = dmr_sites_out_from(sites)
+    enc = [str(n).encode() for n in contig_names]
+    arr = (ctypes.c_char_p * max(1, len(enc)))(*enc)
+    rc = lib().mkp_host_dmr_sites_table(ctypes.byref(o), arr, len(enc), int(bool(header)), str(out_path).encode())
+    del keep
+    if rc != MKP_OK:
+        raise MkpError(rc, "mkp_host_dmr_sites_table failed")
 
 
 DMR_WRITTEN, DMR_NO_CONTIG, DMR_NO_REFERENCE, DMR_BAD, DMR_MODEL = 0, 1, 2, 3, 4   # MKP_DMR_* (mkp_dmr_out.state)
@@ -896,6 +1017,55 @@ class Context:
         for f, shape, dt in (("n_mod", (n, k), "u8"), ("has_code", (n, k), "u1"), ("total", (n,), "u8"), ("n_rows", (n,), "u8"), ("bad", (n,), "u1"),
                              ("contig_has_rows", (n,), "u1")):
             d[f] = [arr(getattr(o, f)[s], shape, dt) for s in range(2)]
+        return d
+
+    def dmr_sites_begin(self, contig_names, bases=("C",), lookup=None, min_valid_coverage=0, mask=False, prior=(0.55, 0.55), delta=0.05,
+                        max_coverages=None, n_sample_records=10042, interval_size=100000, batch_size=6):
+        """mkp_dmr_sites_begin: contig_names[tid]; bases / lookup / mask as dmr_begin; prior = Beta(alpha, beta); max_coverages = (a, b) or None
+        (estimated from the first n_sample_records participating rows); interval_size / batch_size shape the reference's batches."""
+        lk = dmr_default_lookup() if lookup is None else {code_repr(c): b for c, b in lookup.items()}
+        enc = [str(n).encode() for n in contig_names]
+        bs = "".join(bases).encode()
+        cfg = DmrSitesConfig(contig_names=(ctypes.c_char_p * max(1, len(enc)))(*enc), n_contigs=len(enc), bases=bs, n_bases=len(bs),
+                             codes=(ctypes.c_uint32 * max(1, len(lk)))(*lk.keys()),
+                             code_bases=(ctypes.c_uint8 * max(1, len(lk)))(*["ACGT".index(b) for b in lk.values()]), n_lookup=len(lk),
+                             respect_mask=int(bool(mask)), min_valid_coverage=int(min_valid_coverage), prior_alpha=float(prior[0]),
+                             prior_beta=float(prior[1]), delta=float(delta), have_max_coverages=int(max_coverages is not None),
+                             n_sample_records=int(n_sample_records), interval_size=int(interval_size), batch_size=int(batch_size))
+        if max_coverages is not None:
+            cfg.max_coverages[0], cfg.max_coverages[1] = int(max_coverages[0]), int(max_coverages[1])
+        self._check(self.L.mkp_dmr_sites_begin(self.h, ctypes.byref(cfg)))
+
+    def dmr_sites_set_reference(self, tid, seq):
+        """mkp_dmr_sites_set_reference: seq = the whole sequence of contig tid."""
+        b = seq if isinstance(seq, bytes) else str(seq).encode()
+        self._check(self.L.mkp_dmr_sites_set_reference(self.h, int(tid), b, len(b)))
+
+    def dmr_sites_add_rows(self, sample, tid, rows):
+        """mkp_dmr_sites_add_rows: rows of ONE contig of sample 0 (a) or 1 (b), ascending pos, as a dict of arrays with all eleven columns."""
+        r, _keep = _rows_struct(rows, all_columns=True)
+        self._check(self.L.mkp_dmr_sites_add_rows(self.h, int(sample), int(tid), ctypes.byref(r)))
+
+    def dmr_sites_add_file(self, sample, path):
+        """mkp_dmr_sites_add_file: a whole bedMethyl file (plain text or bgzip) of sample 0 / 1 through the device reader; returns its rows."""
+        n = ctypes.c_uint64(0)
+        self._check(self.L.mkp_dmr_sites_add_file(self.h, int(sample), str(path).encode(), ctypes.byref(n)))
+        return int(n.value)
+
+    def dmr_sites_get(self):
+        """mkp_dmr_sites_get: {"codes": u32[k] sorted; per written site "tid" i32[n], "pos" u32[n], "strand" (str of '+' / '-'), "score" /
+        "map_pvalue" / "effect_size" f64[n]; per sample s in (0, 1): "total"[s] u32[n], "n_mod"[s] u32[n, k], "has_code"[s] u32[n] (column
+        masks); "max_coverages" (a, b), "n_sampled" (a, b), "n_batches", "n_batches_dropped", "n_model_failures"}."""
+        o = DmrSitesOut()
+        self._check(self.L.mkp_dmr_sites_get(self.h, ctypes.byref(o)))
+        n, k, arr = int(o.n_sites), int(o.n_codes), _copy_out
+        d = {"codes": arr(o.code_repr, (k,), "u4"), "tid": arr(o.tid, (n,), "i4"), "pos": arr(o.pos, (n,), "u4"),
+             "strand": arr(o.strand, (n,), "u1").tobytes().decode(), "score": arr(o.score, (n,), "f8"), "map_pvalue": arr(o.map_pvalue, (n,), "f8"),
+             "effect_size": arr(o.effect_size, (n,), "f8"), "max_coverages": (int(o.max_coverages[0]), int(o.max_coverages[1])),
+             "n_sampled": (int(o.n_sampled[0]), int(o.n_sampled[1])), "n_batches": int(o.n_batches), "n_batches_dropped": int(o.n_batches_dropped),
+             "n_model_failures": int(o.n_model_failures)}
+        for f, shape in (("total", (n,)), ("n_mod", (n, k)), ("has_code", (n,))):
+            d[f] = [arr(getattr(o, f)[s], shape, "u4") for s in range(2)]
         return d
 
     def rerun(self, iters, fetch=False):

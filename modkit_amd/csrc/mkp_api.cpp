@@ -10,6 +10,7 @@
 #include "mkp_bedmethyl_in.hpp"
 #include "mkp_ctx.hpp"
 #include "mkp_dmr.hpp"
+#include "mkp_dmr_sites.hpp"
 #include "mkp_ingest_host.hpp"
 #include "mkp_launch.h"
 #include "mkp_plan.hpp"
@@ -491,12 +492,13 @@ void mkp_ctx_destroy(mkp_ctx* c) {
   for (DevBuf* b : {&c->merge.d_stage, &c->merge.d_cuts, &c->merge.d_counts, &c->merge.d_offsets}) b->release();
   for (auto& kv : c->dmr.ref) kv.second.buf.release();
   for (DevBuf* b : {&c->dmr.d_out, &c->dmr.d_seen, &c->dmr.d_cnt, &c->dmr.d_off, &c->dmr.carry[0].buf, &c->dmr.carry[1].buf}) b->release();
+  for (auto& kv : c->dsites.contigs) { kv.second.ref.release(); for (auto& r : kv.second.rows) r.buf.release(); }
   { mkp_ctx::BedIn& B = c->bedin;
     for (DevBuf* b : {&B.d_zin, &B.d_text[0], &B.d_text[1], &B.d_blk, &B.d_stat, &B.d_cnt, &B.d_words, &B.d_lines, &B.d_rows, &B.d_runs, &B.d_names})
       b->release();
     for (auto& e : B.ev) if (e) (void)hipEventDestroy(e); }
   for (mkp_ctx::RowTable* t : {static_cast<mkp_ctx::RowTable*>(&c->rstats), static_cast<mkp_ctx::RowTable*>(&c->loc),
-      static_cast<mkp_ctx::RowTable*>(&c->merge), static_cast<mkp_ctx::RowTable*>(&c->dmr)}) {
+      static_cast<mkp_ctx::RowTable*>(&c->merge), static_cast<mkp_ctx::RowTable*>(&c->dmr), static_cast<mkp_ctx::RowTable*>(&c->dsites)}) {
     for (DevBuf* b : {&t->d_regions, &t->d_misc, &t->d_lo, &t->d_hi, &t->d_rows}) b->release();
     for (auto& e : t->ev) if (e) (void)hipEventDestroy(e);
   }
@@ -1292,6 +1294,7 @@ struct RowTableWords { const char *begin, *needs, *launch, *inside, *holds; };
 constexpr RowTableWords kStatsWords = {"mkp_stats_begin", "region statistics need", "region stats", "regions", "region statistics hold"};
 constexpr RowTableWords kLocWords = {"mkp_localize_begin", "localize needs", "localize", "windows", "localize holds"};
 constexpr RowTableWords kDmrWords = {"mkp_dmr_begin", "dmr pair needs", "dmr pair", "regions", "dmr pair holds"};
+constexpr RowTableWords kDsitesWords = {"mkp_dmr_sites_begin", "dmr sites needs", "dmr sites", "tables", "dmr sites holds"};
 constexpr RowTableWords kMergeWords = {"mkp_merge_begin", "bedmethyl merge needs", "bedmethyl merge", "tables", "bedmethyl merge holds"};
 // the five columns the reducers read, on the device; info = 0 '+', 1 '-', 2 '.' in its low bits; rest = n_canonical, n_other, n_delete,
 // n_fail, n_diff, n_nocall, which only the merge reads (not uploaded for the reducers)
@@ -2220,6 +2223,358 @@ int mkp_dmr_get(mkp_ctx* c, mkp_dmr_out* out) {
     out->has_reference = D.h_ref.data();
     dmr_judge(*out, D.h_score.data(), D.h_state.data());
     out->score = D.h_score.data(); out->state = D.h_state.data();
+  });
+}
+
+}  // extern "C"
+
+// ---- dmr sites (`modkit dmr pair` without -r, include/mkpileup.h): both tables' row columns stay in HBM per contig between
+// mkp_dmr_sites_begin and mkp_dmr_sites_get, which runs the stages of mkp_dmr_sites.hip
+namespace {
+
+// device buffers of one mkp_dmr_sites_get, released when it returns or throws
+struct ScopedBufs {
+  std::vector<std::unique_ptr<DevBuf>> all;
+  template <class T> T* get(size_t n) { all.emplace_back(new DevBuf()); all.back()->ensure(std::max<size_t>(n, 1) * sizeof(T)); return all.back()->as<T>(); }
+  ~ScopedBufs() { for (auto& b : all) b->release(); }
+};
+
+// rows on the device behind the rows of (sample, tid); a contig's pieces come in ascending order
+void dsites_append(mkp_ctx* c, int sample, int32_t tid, const RowCols& r) {
+  mkp_ctx::DmrSites& D = c->dsites;
+  if (tid < 0 || (size_t)tid >= D.names.size()) throw Error(MKP_E_INVALID, "dmr sites: rows of an unknown tid (" + std::to_string(tid) + ")");
+  if (!r.n) return;
+  mkp_ctx::DmrSites::Rows& R = D.contigs[tid].rows[sample];
+  if ((uint64_t)R.n + r.n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows on one contig");
+  uint32_t first = 0, last = 0;
+  d2h_copy(&first, r.pos, 4, c->stream); d2h_copy(&last, r.pos + (r.n - 1), 4, c->stream);
+  if (R.n && first < R.last_pos) throw Error(MKP_E_INVALID, "dmr sites: the pieces of a contig must come in ascending order (" + std::to_string(first)
+      + " follows " + std::to_string(R.last_pos) + ")");
+  const uint32_t* src[6] = {r.pos, r.info, r.code, r.n_valid, r.n_mod, r.rest[0]};
+  const uint64_t need = (uint64_t)R.n + r.n;
+  if (need > R.cap) {
+    const uint64_t cap = ((std::max<uint64_t>(need, R.cap + R.cap / 2) + 63) & ~63ull);
+    size_t free_b = 0, total_b = 0; hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
+    if (D.row_bytes + (cap - R.cap) * 24 > (uint64_t)total_b / 4 * 3) throw Error(MKP_E_UNSUPPORTED, "dmr sites: the two tables need more than "
+        + std::to_string(total_b / 4 * 3 >> 20) + " MiB of device memory (24 bytes a row, both resident)");
+    DevBuf grown; grown.ensure((size_t)cap * 24);
+    for (int k = 0; k < 6 && R.n; k++) hip_check(hipMemcpyAsync(grown.as<uint32_t>() + (size_t)k * cap, R.col(k), (size_t)R.n * 4, hipMemcpyDeviceToDevice,
+        c->stream), "D2D");
+    hip_check(hipStreamSynchronize(c->stream), "sync");
+    R.buf.release(); R.buf = grown; D.row_bytes += (cap - R.cap) * 24; R.cap = cap;
+  }
+  for (int k = 0; k < 6; k++) hip_check(hipMemcpyAsync(R.buf.as<uint32_t>() + (size_t)k * R.cap + R.n, src[k], (size_t)r.n * 4, hipMemcpyDeviceToDevice,
+      c->stream), "D2D");
+  hip_check(hipStreamSynchronize(c->stream), "sync");   // (the source is the next call's upload buffer)
+  R.n = (uint32_t)need; R.last_pos = last;
+}
+
+double ms_between(std::chrono::steady_clock::time_point& t) {
+  const auto now = std::chrono::steady_clock::now();
+  const double ms = std::chrono::duration<double, std::milli>(now - t).count();
+  t = now;
+  return ms;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mkp_internal_dmr_sites_timing(mkp_ctx* c, double ms_out[7]) {
+  if (!c || !ms_out) return MKP_E_INVALID;
+  for (int k = 0; k < 7; k++) ms_out[k] = c->dsites.stage_ms[k];
+  return MKP_OK;
+}
+
+// measurement aid: the sites of the last mkp_dmr_sites_get scored again by the same arithmetic on the host pool; *ms = the wall time, returns
+// the number of sites whose three values differ in a bit from the device's (another libm: expected to be many, none an error)
+int64_t mkp_internal_dmr_sites_host_ms(mkp_ctx* c, double* ms) {
+  if (!c || !ms) return MKP_E_INVALID;
+  mkp_ctx::DmrSites& D = c->dsites;
+  const size_t n = D.h_pos.size(), nc = D.h_codes.size(), piece = 4096, np = (n + piece - 1) / piece;
+  MkpDmrSiteMath M = D.math; M.max_cov[0] = D.used_max_cov[0]; M.max_cov[1] = D.used_max_cov[1];
+  std::vector<uint64_t> differ(np, 0);
+  auto t0 = std::chrono::steady_clock::now();
+  HostPool::get().parallel(np, [&](size_t i) {
+    for (size_t k = i * piece; k < std::min(n, (i + 1) * piece); k++) {
+      uint64_t am[MKP_DMR_SITE_MAX_CODES] = {0}, bm[MKP_DMR_SITE_MAX_CODES] = {0}; double v[5];
+      for (size_t j = 0; j < nc; j++) { am[j] = D.h_mod[0][k * nc + j]; bm[j] = D.h_mod[1][k * nc + j]; }
+      dmr_site_score(am, D.h_has[0][k], D.h_total[0][k], bm, D.h_has[1][k], D.h_total[1][k], (uint32_t)nc, M, v);
+      if (memcmp(&v[0], &D.h_score[k], 8) || memcmp(&v[3], &D.h_p[k], 8) || memcmp(&v[4], &D.h_effect[k], 8)) differ[i]++;
+    }
+  });
+  *ms = ms_between(t0);
+  uint64_t total = 0; for (uint64_t d : differ) total += d;
+  return (int64_t)total;
+}
+
+int mkp_dmr_sites_begin(mkp_ctx* c, const mkp_dmr_sites_config* cfg) {
+  if (!c || !cfg || (!cfg->contig_names && cfg->n_contigs) || (!cfg->bases && cfg->n_bases) || ((!cfg->codes || !cfg->code_bases) && cfg->n_lookup))
+    return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::DmrSites& D = c->dsites;
+    D.open = false;
+    if (cfg->n_contigs > 0x7fffffffu) throw Error(MKP_E_UNSUPPORTED, "more than 2^31 - 1 contigs");
+    MkpDmrParams P; memset(&P, 0, sizeof(P));
+    P.min_cov = cfg->min_valid_coverage; P.mask = cfg->respect_mask ? 1u : 0u;
+    if (!cfg->n_bases) throw Error(MKP_E_INVALID, "need to specify at least 1 modified base");
+    for (uint32_t k = 0; k < cfg->n_bases; k++) {
+      const char* at = strchr("ACGT", cfg->bases[k]);
+      if (!at || !cfg->bases[k]) throw Error(MKP_E_INVALID, "modified base needs to be A, C, G, or T.");
+      const uint32_t b = (uint32_t)(at - "ACGT");
+      P.pos_set |= 1u << b; P.neg_set |= 1u << (3u - b);
+    }
+    for (uint32_t k = 0; k < cfg->n_lookup; k++) {   // a later entry for a code replaces an earlier one
+      if (!cfg->codes[k]) throw Error(MKP_E_INVALID, "0 is not a mod code");
+      if (cfg->code_bases[k] > 3) throw Error(MKP_E_INVALID, "a code's base is an index into ACGT");
+      uint32_t at = 0; while (at < P.n_lookup && P.code[at] != cfg->codes[k]) at++;
+      if (at == MKP_DMR_MAX_LOOKUP) throw Error(MKP_E_UNSUPPORTED, "dmr sites holds at most " + std::to_string(MKP_DMR_MAX_LOOKUP)
+          + " codes in its code -> base table");
+      P.code[at] = cfg->codes[k]; P.base[at] = cfg->code_bases[k]; if (at == P.n_lookup) P.n_lookup++;
+    }
+    // (only a code of one of the --base letters can ever take part: mkp_dmr_begin)
+    uint32_t kept = 0;
+    for (uint32_t k = 0; k < P.n_lookup; k++) if ((P.pos_set >> P.base[k]) & 1u) { P.code[kept] = P.code[k]; P.base[kept] = P.base[k]; kept++; }
+    for (uint32_t k = kept; k < P.n_lookup; k++) { P.code[k] = 0; P.base[k] = 0; }
+    P.n_lookup = kept;
+    if (cfg->prior_alpha + cfg->prior_beta < 1.0) throw Error(MKP_E_INVALID, "alpha + beta must be > 1.0 for numerical stability");
+    if (!(cfg->prior_alpha > 0.0) || !(cfg->prior_beta > 0.0) || std::isinf(cfg->prior_alpha) || std::isinf(cfg->prior_beta))
+      throw Error(MKP_E_INVALID, "invalid beta parameters " + std::to_string(cfg->prior_alpha) + ", " + std::to_string(cfg->prior_beta));
+    if (cfg->delta != cfg->delta) throw Error(MKP_E_INVALID, "--delta is not a number");
+    if (!cfg->interval_size || cfg->interval_size > 0xffffffffull) throw Error(MKP_E_INVALID, "the interval size must be in [1, 2^32 - 1]");
+    if (!cfg->batch_size) throw Error(MKP_E_INVALID, "the batch size must be at least 1");
+    if (!cfg->have_max_coverages && !cfg->n_sample_records) throw Error(MKP_E_INVALID, "the number of sample records must be at least 1");
+    D.names.clear();
+    for (uint32_t k = 0; k < cfg->n_contigs; k++) { if (!cfg->contig_names[k]) throw Error(MKP_E_INVALID, "contig name " + std::to_string(k) + " is NULL");
+      D.names.push_back(cfg->contig_names[k]); }
+    D.prm = P; D.have_max = cfg->have_max_coverages != 0; D.max_cov[0] = cfg->max_coverages[0]; D.max_cov[1] = cfg->max_coverages[1];
+    D.math = dmr_site_math(cfg->prior_alpha, cfg->prior_beta, cfg->delta, D.max_cov);
+    D.n_sample = cfg->n_sample_records; D.interval = cfg->interval_size; D.batch_size = cfg->batch_size;
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    hip_check(hipStreamSynchronize(c->stream), "sync");   // (a previous session's kernels)
+    for (auto& kv : D.contigs) { kv.second.ref.release(); for (auto& r : kv.second.rows) r.buf.release(); }
+    D.contigs.clear(); D.row_bytes = 0;
+    D.d_misc.ensure(kStatsMiscBytes);
+    D.open = true;
+  });
+}
+
+int mkp_dmr_sites_set_reference(mkp_ctx* c, int32_t tid, const uint8_t* bytes, uint64_t len) {
+  if (!c || (!bytes && len)) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::DmrSites& D = c->dsites;
+    rt_need_open(D, kDsitesWords);
+    if (tid < 0 || (size_t)tid >= D.names.size()) throw Error(MKP_E_INVALID, "dmr sites: the reference of an unknown tid (" + std::to_string(tid) + ")");
+    if (len > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "a contig beyond 2^32 - 1 bases");
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    mkp_ctx::DmrSites::Contig& K = D.contigs[tid];
+    K.ref.ensure(std::max<size_t>((size_t)len, 1)); K.len = (uint32_t)len; K.has_ref = true;
+    h2d_copy(K.ref.p, bytes, (size_t)len);
+  });
+}
+
+int mkp_dmr_sites_add_rows(mkp_ctx* c, int sample, int32_t tid, const mkp_rows* rows) {
+  if (!c || !rows) return MKP_E_INVALID;
+  return guarded(c, [&]() { dmr_need_sample(sample); dsites_append(c, sample, tid, rt_upload_rows(c, c->dsites, kDsitesWords, rows, 6)); });
+}
+
+int mkp_dmr_sites_add_file(mkp_ctx* c, int sample, const char* path, uint64_t* n_rows) {
+  if (!c || !path) return MKP_E_INVALID;
+  if (n_rows) *n_rows = 0;
+  return guarded(c, [&]() {
+    dmr_need_sample(sample);
+    mkp_ctx::DmrSites& D = c->dsites;
+    rt_need_open(D, kDsitesWords);
+    std::map<std::string, int32_t> tid_of;   // (the first of two equal names)
+    for (size_t k = 0; k < D.names.size(); k++) tid_of.emplace(D.names[k], (int32_t)k);
+    uint64_t total = 0;
+    bedin_read_file(c, path, [&](const std::string& chrom, const RowCols& r, bool) {
+      auto it = tid_of.find(chrom);
+      total += r.n;
+      if (it != tid_of.end()) dsites_append(c, sample, it->second, r);
+    });
+    if (n_rows) *n_rows = total;
+  });
+}
+
+int mkp_dmr_sites_get(mkp_ctx* c, mkp_dmr_sites_out* out) {
+  if (!c || !out) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::DmrSites& D = c->dsites;
+    rt_need_open(D, kDsitesWords);
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t st = c->stream;
+    for (double& m : D.stage_ms) m = 0;
+    auto clk = std::chrono::steady_clock::now();
+    // the contigs of the walk: in the FASTA and in both tables, in byte order of their names
+    std::vector<int32_t> tids;
+    for (auto& kv : D.contigs) if (kv.second.has_ref && kv.second.rows[0].n && kv.second.rows[1].n) tids.push_back(kv.first);
+    std::sort(tids.begin(), tids.end(), [&](int32_t a, int32_t b) { return D.names[a] != D.names[b] ? D.names[a] < D.names[b] : a < b; });
+    if (tids.empty()) throw Error(MKP_E_INVALID, "need at least 1 contig");
+    const size_t nt = tids.size();
+    ScopedBufs bufs;
+
+    // ---- listed counts, then the batch table
+    std::vector<uint64_t> lens(nt), win_off(nt + 1, 0);
+    for (size_t k = 0; k < nt; k++) { lens[k] = D.contigs[tids[k]].len; win_off[k + 1] = win_off[k] + dmr_sites_windows(lens[k], D.interval); }
+    std::vector<uint32_t> counts((size_t)win_off[nt]);
+    { uint32_t* d_counts = bufs.get<uint32_t>(counts.size());
+      for (size_t k = 0; k < nt; k++) { const auto& K = D.contigs[tids[k]];
+        hip_check(mkp_launch_dmr_sites_listed(st, K.ref.as<uint8_t>(), K.len, D.interval, (uint32_t)(win_off[k + 1] - win_off[k]), &D.prm,
+            d_counts + win_off[k]), "dmr sites listed launch"); }
+      d2h_copy(counts.data(), d_counts, counts.size() * 4, st); }
+    std::vector<mkp_dmr_sites_batch> plan;
+    const uint64_t n_batches = dmr_sites_plan(lens.data(), counts.data(), (uint32_t)nt, D.interval, &plan);
+    if (n_batches > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 batches");
+    std::vector<size_t> ent_off(nt + 1, 0);
+    std::vector<MkpDmrSitesBatch> table(plan.size());
+    for (size_t e = 0; e < plan.size(); e++) { table[e] = {(uint32_t)plan[e].start, (uint32_t)plan[e].batch}; ent_off[plan[e].contig + 1] = e + 1; }
+    MkpDmrSitesBatch* d_table = bufs.get<MkpDmrSitesBatch>(table.size());
+    h2d_copy(d_table, table.data(), table.size() * sizeof(MkpDmrSitesBatch));
+    D.stage_ms[0] = ms_between(clk);
+
+    // ---- heads: row flags and sites per (sample, contig); the slots' codes are the run's
+    hip_check(hipMemsetAsync(D.d_misc.p, 0, kStatsMiscBytes, st), "memset");
+    uint32_t* misc_d = D.d_misc.as<uint32_t>();
+    struct Side { uint8_t* rowflag; uint32_t *tile, *totals, *s_pos, *s_first, *s_total, *s_info; uint32_t n_sites = 0, n_part = 0; };
+    std::vector<Side> sides(2 * nt);
+    for (size_t k = 0; k < nt; k++) for (int s = 0; s < 2; s++) {
+      const auto& K = D.contigs[tids[k]]; const auto& R = K.rows[s]; Side& S = sides[2 * k + s];
+      const size_t n = R.n, n_tiles = (n + MKP_DMRS_TILE - 1) / MKP_DMRS_TILE;
+      S.rowflag = bufs.get<uint8_t>(n); S.tile = bufs.get<uint32_t>(2 * n_tiles); S.totals = bufs.get<uint32_t>(2);
+      S.s_pos = bufs.get<uint32_t>(n); S.s_first = bufs.get<uint32_t>(n); S.s_total = bufs.get<uint32_t>(n); S.s_info = bufs.get<uint32_t>(n);
+      hip_check(mkp_launch_dmr_sites_heads(st, R.col(0), R.col(1), R.col(2), R.col(3), R.col(4), R.col(5), R.n, K.ref.as<uint8_t>(), K.len, &D.prm,
+          misc_d, misc_d + MKP_STATS_MAX_CODES, S.rowflag, S.tile, S.totals, S.s_pos, S.s_first, S.s_total, S.s_info), "dmr sites heads launch");
+    }
+    for (Side& S : sides) { uint32_t t[2]; d2h_copy(t, S.totals, 8, st); S.n_sites = t[0]; S.n_part = t[1]; }
+    uint32_t misc[kStatsMiscBytes / 4];
+    d2h_copy(misc, D.d_misc.p, sizeof(misc), st);
+    rt_check_codes(misc, kDsitesWords);
+    uint32_t any = 0; for (uint32_t s = 0; s < MKP_STATS_MAX_CODES; s++) if (misc[s]) any |= 1u << s;
+    const std::vector<std::pair<uint32_t, uint32_t>> cols = rt_columns(misc, any);   // code, slot
+    const uint32_t nc = (uint32_t)cols.size();
+    unsigned long long col_of_slot = 0;
+    D.h_codes.resize(nc);
+    for (uint32_t k = 0; k < nc; k++) { D.h_codes[k] = cols[k].first; col_of_slot |= (unsigned long long)k << (4u * cols[k].second); }
+    D.stage_ms[1] = ms_between(clk);
+
+    // ---- the max coverages: given, or the 95th percentile of the coverages of the participating rows of the first super-batches
+    uint32_t max_cov[2] = {D.max_cov[0], D.max_cov[1]}; uint64_t n_sampled[2] = {0, 0};
+    if (!D.have_max) {
+      const size_t ne = plan.size();
+      std::vector<uint32_t> row_at[2], before[2];
+      for (int s = 0; s < 2; s++) { row_at[s].resize(ne); before[s].resize(ne); }
+      { uint32_t* d_at = bufs.get<uint32_t>(2 * ne); uint32_t* d_before = bufs.get<uint32_t>(2 * ne);
+        for (size_t k = 0; k < nt; k++) for (int s = 0; s < 2; s++) { const auto& R = D.contigs[tids[k]].rows[s]; const Side& S = sides[2 * k + s];
+          hip_check(mkp_launch_dmr_sites_bounds(st, R.col(0), S.rowflag, R.n, S.tile, S.totals, d_table + ent_off[k], (uint32_t)(ent_off[k + 1] - ent_off[k]),
+              d_at + s * ne + ent_off[k], d_before + s * ne + ent_off[k]), "dmr sites bounds launch"); }
+        for (int s = 0; s < 2; s++) { d2h_copy(row_at[s].data(), d_at + s * ne, ne * 4, st); d2h_copy(before[s].data(), d_before + s * ne, ne * 4, st); } }
+      // the first super-batch behind which both samples hold n_sample values; the entries up to it are a prefix of the walk
+      size_t stop = ne;   // entries [0, stop) are sampled
+      { uint64_t have[2] = {0, 0}; size_t e = 0;
+        while (e < ne) {
+          const uint64_t sb = plan[e].batch / D.batch_size;
+          for (; e < ne && plan[e].batch / D.batch_size == sb; e++) for (int s = 0; s < 2; s++) {
+            const size_t k = plan[e].contig; const bool last_of_contig = e + 1 == ent_off[k + 1];
+            have[s] += (last_of_contig ? sides[2 * k + s].n_part : before[s][e + 1]) - before[s][e];
+          }
+          if (std::min(have[0], have[1]) >= D.n_sample) { stop = e; break; }
+        }
+        n_sampled[0] = have[0]; n_sampled[1] = have[1]; }
+      for (int s = 0; s < 2; s++) {
+        if (n_sampled[s] < 2) throw Error(MKP_E_INVALID, "too few data points to calculate percentile, got " + std::to_string(n_sampled[s])
+            + " (the max coverages are estimated from the participating rows of sample " + (s ? "b" : "a") + ": give --max-coverages)");
+        if (n_sampled[s] > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 sampled coverages");
+        uint32_t* d_cov = bufs.get<uint32_t>((size_t)n_sampled[s]); uint32_t* d_cursor = bufs.get<uint32_t>(1);
+        hip_check(hipMemsetAsync(d_cursor, 0, 4, st), "memset");
+        for (size_t k = 0; k < nt; k++) {
+          const auto& R = D.contigs[tids[k]].rows[s];
+          const uint32_t n_front = stop >= ent_off[k + 1] ? R.n : stop <= ent_off[k] ? 0u : row_at[s][stop];
+          hip_check(mkp_launch_dmr_sites_coverages(st, sides[2 * k + s].rowflag, R.col(3), n_front, d_cursor, d_cov, (uint32_t)n_sampled[s]),
+              "dmr sites coverages launch");
+        }
+        std::vector<uint32_t> cov((size_t)n_sampled[s]); uint32_t got = 0;
+        d2h_copy(&got, d_cursor, 4, st); d2h_copy(cov.data(), d_cov, cov.size() * 4, st);
+        if (got != n_sampled[s]) throw Error(MKP_E_DEVICE, "dmr sites: the coverage sample holds " + std::to_string(got) + " values, "
+            + std::to_string(n_sampled[s]) + " were counted");
+        std::vector<float> xs(cov.size()); for (size_t i = 0; i < cov.size(); i++) xs[i] = (float)cov[i];
+        std::sort(xs.begin(), xs.end());
+        float q = 0; if (mkp_percentile(xs.data(), xs.size(), 0.95f, &q) != MKP_OK) throw Error(MKP_E_INVALID, "percentile of the sampled coverages failed");
+        max_cov[s] = (uint32_t)floorf(q);
+      }
+    }
+    MkpDmrSiteMath math = D.math;
+    for (int s = 0; s < 2; s++) { max_cov[s] = std::min<uint32_t>(max_cov[s], MKP_DMR_SITE_MAX_COV); math.max_cov[s] = max_cov[s]; }
+    D.stage_ms[2] = ms_between(clk);
+
+    // ---- bad batches of either sample, then per contig the join and the score
+    uint32_t* d_bad = bufs.get<uint32_t>((size_t)n_batches);
+    hip_check(hipMemsetAsync(d_bad, 0, std::max<size_t>((size_t)n_batches, 1) * 4, st), "memset");
+    for (size_t k = 0; k < nt; k++) for (int s = 0; s < 2; s++) { const Side& S = sides[2 * k + s];
+      hip_check(mkp_launch_dmr_sites_bad(st, S.s_pos, S.s_info, S.n_sites, d_table + ent_off[k], (uint32_t)(ent_off[k + 1] - ent_off[k]), d_bad),
+          "dmr sites bad launch"); }
+    std::vector<uint32_t> bad((size_t)n_batches);
+    d2h_copy(bad.data(), d_bad, bad.size() * 4, st);
+    uint64_t n_dropped = 0; for (uint32_t b : bad) if (b) n_dropped++;
+    struct Joined { uint32_t *pair_a, *pair_b, n_pairs = 0; };
+    std::vector<Joined> joined(nt); std::vector<MkpDmrSitesPairs> outs(nt);
+    for (size_t k = 0; k < nt; k++) {
+      const Side &A = sides[2 * k], &B = sides[2 * k + 1]; Joined& J = joined[k];
+      const size_t n_tiles = ((size_t)A.n_sites + MKP_DMRS_TILE - 1) / MKP_DMRS_TILE;
+      uint32_t* partner = bufs.get<uint32_t>(A.n_sites); uint32_t* tile = bufs.get<uint32_t>(2 * n_tiles); uint32_t* totals = bufs.get<uint32_t>(2);
+      J.pair_a = bufs.get<uint32_t>(A.n_sites); J.pair_b = bufs.get<uint32_t>(A.n_sites);
+      hip_check(mkp_launch_dmr_sites_join(st, A.s_pos, A.n_sites, B.s_pos, B.n_sites, d_table + ent_off[k], (uint32_t)(ent_off[k + 1] - ent_off[k]), d_bad,
+          partner, tile, totals, J.pair_a, J.pair_b), "dmr sites join launch");
+      uint32_t t[2]; d2h_copy(t, totals, 8, st); J.n_pairs = t[0];
+      const size_t n = J.n_pairs; MkpDmrSitesPairs& O = outs[k];   // (the pairs' output, allocated outside the score stage's clock)
+      O.pos = bufs.get<uint32_t>(n); O.info = bufs.get<uint32_t>(n); O.has = bufs.get<uint32_t>(n); O.total_a = bufs.get<uint32_t>(n);
+      O.total_b = bufs.get<uint32_t>(n); O.cnt = bufs.get<uint32_t>(n * 2 * nc); O.score = bufs.get<double>(n); O.pvalue = bufs.get<double>(n);
+      O.effect = bufs.get<double>(n);
+    }
+    D.stage_ms[3] = ms_between(clk);
+
+    for (size_t k = 0; k < nt; k++) {
+      const auto& K = D.contigs[tids[k]]; const Side &A = sides[2 * k], &B = sides[2 * k + 1]; const Joined& J = joined[k];
+      const MkpDmrSitesPairs& O = outs[k];
+      const MkpDmrSitesSample sa = {K.rows[0].col(0), K.rows[0].col(4), A.rowflag, K.rows[0].n, A.s_pos, A.s_first, A.s_total, A.s_info};
+      const MkpDmrSitesSample sb = {K.rows[1].col(0), K.rows[1].col(4), B.rowflag, K.rows[1].n, B.s_pos, B.s_first, B.s_total, B.s_info};
+      hip_check(mkp_launch_dmr_sites_score(st, &sa, &sb, J.pair_a, J.pair_b, J.n_pairs, col_of_slot, nc, &math, &O), "dmr sites score launch");
+    }
+    hip_check(hipStreamSynchronize(st), "dmr sites score sync");
+    D.stage_ms[4] = ms_between(clk);
+
+    // ---- read-back, and the written sites in walk order
+    uint64_t n_all = 0; for (const Joined& J : joined) n_all += J.n_pairs;
+    D.h_tid.clear(); D.h_pos.clear(); D.h_strand.clear(); D.h_score.clear(); D.h_p.clear(); D.h_effect.clear();
+    for (int s = 0; s < 2; s++) { D.h_total[s].clear(); D.h_mod[s].clear(); D.h_has[s].clear(); }
+    D.h_tid.reserve(n_all); D.h_pos.reserve(n_all); D.h_score.reserve(n_all);
+    uint64_t n_failed = 0; double read_ms = 0;
+    std::vector<uint32_t> pos, info, has, ta, tb, cnt; std::vector<double> score, pv, eff;
+    for (size_t k = 0; k < nt; k++) {
+      const size_t n = joined[k].n_pairs; const MkpDmrSitesPairs& O = outs[k];
+      auto t_read = std::chrono::steady_clock::now();
+      pos.resize(n); info.resize(n); has.resize(n); ta.resize(n); tb.resize(n); cnt.resize(n * 2 * nc); score.resize(n); pv.resize(n); eff.resize(n);
+      d2h_copy(pos.data(), O.pos, n * 4, st); d2h_copy(info.data(), O.info, n * 4, st); d2h_copy(has.data(), O.has, n * 4, st);
+      d2h_copy(ta.data(), O.total_a, n * 4, st); d2h_copy(tb.data(), O.total_b, n * 4, st); d2h_copy(cnt.data(), O.cnt, n * 2 * nc * 4, st);
+      d2h_copy(score.data(), O.score, n * 8, st); d2h_copy(pv.data(), O.pvalue, n * 8, st); d2h_copy(eff.data(), O.effect, n * 8, st);
+      read_ms += ms_between(t_read);
+      for (size_t i = 0; i < n; i++) {
+        if (info[i] & MKP_DMRS_PAIR_FAILED) { n_failed++; continue; }
+        D.h_tid.push_back(tids[k]); D.h_pos.push_back(pos[i]); D.h_strand.push_back((info[i] & MKP_DMRS_SITE_MINUS) ? '-' : '+');
+        D.h_total[0].push_back(ta[i]); D.h_total[1].push_back(tb[i]); D.h_has[0].push_back(has[i] & 0xffffu); D.h_has[1].push_back(has[i] >> 16);
+        for (int s = 0; s < 2; s++) D.h_mod[s].insert(D.h_mod[s].end(), cnt.begin() + (i * 2 + s) * nc, cnt.begin() + (i * 2 + s + 1) * nc);
+        D.h_score.push_back(score[i]); D.h_p.push_back(pv[i]); D.h_effect.push_back(eff[i]);
+      }
+    }
+    D.stage_ms[5] = read_ms; D.stage_ms[6] = ms_between(clk) - read_ms;
+    memset(out, 0, sizeof(*out));
+    out->n_sites = D.h_pos.size(); out->n_codes = nc; out->code_repr = D.h_codes.data();
+    out->tid = D.h_tid.data(); out->pos = D.h_pos.data(); out->strand = D.h_strand.data();
+    for (int s = 0; s < 2; s++) { out->total[s] = D.h_total[s].data(); out->n_mod[s] = D.h_mod[s].data(); out->has_code[s] = D.h_has[s].data();
+      out->max_coverages[s] = max_cov[s]; out->n_sampled[s] = n_sampled[s]; }
+    out->score = D.h_score.data(); out->map_pvalue = D.h_p.data(); out->effect_size = D.h_effect.data();
+    out->n_batches = n_batches; out->n_batches_dropped = n_dropped; out->n_model_failures = n_failed;
+    D.used_max_cov[0] = max_cov[0]; D.used_max_cov[1] = max_cov[1];
   });
 }
 

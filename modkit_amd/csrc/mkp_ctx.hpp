@@ -9,6 +9,7 @@
 #include <set>
 #include <vector>
 
+#include "mkp_dmr_site_math.hpp"
 #include "mkp_pack.hpp"
 
 namespace mkp {
@@ -216,6 +217,21 @@ struct mkp_ctx {
     std::vector<uint32_t> h_codes; std::vector<uint64_t> h_mod[2], h_total[2], h_rows[2]; std::vector<uint8_t> h_has_code[2], h_bad[2], h_contig[2],
         h_ref, h_state; std::vector<double> h_score;                    // mkp_dmr_get
   } dmr;
+  // dmr sites (mkp_dmr_sites_begin .. mkp_dmr_sites_get, mkp_dmr_sites.hip): per contig the whole reference and both samples' six row columns,
+  // resident until the next begin (an add call appends to its contig's columns); the sites and everything else is made by get.  Of RowTable:
+  // open, the upload buffer, the slots' codes and error word
+  struct DmrSites : RowTable {
+    MkpDmrParams prm; MkpDmrSiteMath math; std::vector<std::string> names;
+    bool have_max = false; uint32_t max_cov[2] = {0, 0}, used_max_cov[2] = {0, 0}; uint64_t n_sample = 0, interval = 0, batch_size = 0, row_bytes = 0;
+    struct Rows { mkp::DevBuf buf; uint64_t cap = 0; uint32_t n = 0, last_pos = 0;   // six columns of `cap` rows
+      const uint32_t* col(int k) const { return buf.as<uint32_t>() + (size_t)k * cap; } };
+    struct Contig { mkp::DevBuf ref; uint32_t len = 0; bool has_ref = false; Rows rows[2]; };
+    std::map<int32_t, Contig> contigs;
+    // mkp_dmr_sites_get
+    std::vector<uint32_t> h_codes, h_pos, h_total[2], h_mod[2], h_has[2]; std::vector<int32_t> h_tid; std::vector<uint8_t> h_strand;
+    std::vector<double> h_score, h_p, h_effect;
+    double stage_ms[7] = {0, 0, 0, 0, 0, 0, 0};   // listed counts, heads, estimate, bad + join, score, read-back, host assembly (the last get)
+  } dsites;
   // localize (mkp_localize_begin .. mkp_localize_get, mkp_localize.hip): the run-long table tab[slot][2 window + 1]{n_mod, n_valid, n_rows} (u64)
   struct Localize : RowTable {
     uint32_t window = 0, stranded = 0;
@@ -286,5 +302,7 @@ extern "C" int mkp_internal_localize_timing(mkp_ctx* c, int on, double ms_out[2]
 extern "C" int mkp_internal_merge_timing(mkp_ctx* c, int on, double ms_out[2]);
 // dmr pair: the same for [bounds + scan, reduce]
 extern "C" int mkp_internal_dmr_timing(mkp_ctx* c, int on, double ms_out[2]);
+// dmr sites: the wall times of the last mkp_dmr_sites_get in ms [listed counts, heads, estimate, bad + join, score, read-back, host assembly]
+extern "C" int mkp_internal_dmr_sites_timing(mkp_ctx* c, double ms_out[7]);
 // device bedMethyl reader: the read stage's summed times [file read, upload, inflate + CRC, parse] in ms and the pieces read; reset = zero them
 extern "C" int mkp_internal_bedmethyl_in_stats(mkp_ctx* c, int reset, double ms_out[4], uint64_t* pieces);

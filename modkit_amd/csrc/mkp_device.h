@@ -319,6 +319,24 @@ struct MkpStatsRegion { uint32_t start, end; uint32_t rule /* 1 '+', 2 '-', 3 bo
 // reference byte is no base (--mask), otherwise it counts as its upper-case form
 struct MkpDmrParams { unsigned long long min_cov; uint32_t n_lookup, pos_set, neg_set, mask; uint32_t code[MKP_DMR_MAX_LOOKUP];
   uint8_t base[MKP_DMR_MAX_LOOKUP]; };
+// ---- dmr sites (mkp_dmr_sites.hip): the rows of one contig of one sample are cut into tiles of MKP_DMRS_TILE rows, a workgroup each, a
+// lane a row.  A row's flag byte: its code slot, whether it takes part, whether it is the head (first participating row) of its position.
+// A site = the participating rows of a position: its pos, first row, total (the head's N_valid_cov) and info bits.  A contig's batch table
+// lists, ascending in start, where each batch of the reference's walk begins inside it.
+#define MKP_DMRS_TILE 256u
+#define MKP_DMRS_ROW_SLOT 0x0fu
+#define MKP_DMRS_ROW_PART 0x20u
+#define MKP_DMRS_ROW_HEAD 0x40u
+#define MKP_DMRS_SITE_MINUS 1u      // site info: listed '-'
+#define MKP_DMRS_SITE_BAD 2u        // site info: aggregate_counts fails on the position
+#define MKP_DMRS_NO_PAIR 0xffffffffu
+#define MKP_DMRS_PAIR_FAILED 2u     // pair info (beside MKP_DMRS_SITE_MINUS): the score or the p-value fails in the reference
+struct MkpDmrSitesBatch { uint32_t start, batch; };
+// one sample's rows and sites of the contig, as the score kernel reads them
+struct MkpDmrSitesSample { const uint32_t *pos, *n_mod; const uint8_t* rowflag; uint32_t n_rows; const uint32_t *s_pos, *s_first, *s_total, *s_info; };
+// per pair: pos, info (MKP_DMRS_SITE_MINUS | MKP_DMRS_PAIR_FAILED), has = a's column mask | b's << 16, the totals, cnt[(pair * 2 + sample) *
+// n_cols + column], and the three f64 values
+struct MkpDmrSitesPairs { uint32_t *pos, *info, *has, *total_a, *total_b, *cnt; double *score, *pvalue, *effect; };
 // ---- localize (mkp_localize.hip): one expanded window [ws, we) of the contig whose rows are being added and the anchor its offsets are
 // taken from (offset = anchor - pos).  The run-long table holds MKP_STATS_MAX_CODES slots of 2 * window + 1 cells {n_mod, n_valid, n_rows}
 // (u64 each); the codes of the slots (0 = free) are a table of the run's own.

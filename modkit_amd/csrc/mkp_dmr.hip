@@ -20,33 +20,10 @@
 // (its sums are then never read).  Every row that takes part claims its code's slot, N_mod == 0 too: the reference's key set holds it.
 // Per item: one butterfly per touched slot, ONE 64-bit atomic add instruction (lane s: slot s, then total and rows) and one atomic OR.
 #include "mkp_dev_chunks.hpp"
+#include "mkp_dev_dmr_filter.hpp"
 #include "mkp_launch.h"
 
 namespace {
-
-// index in "ACGT" of a reference byte, 4 = no base
-__device__ __forceinline__ uint32_t base_index(uint32_t b, bool mask) {
-  if (!mask && b >= 'a' && b <= 'z') b -= 32u;
-  return b == 'A' ? 0u : b == 'C' ? 1u : b == 'G' ? 2u : b == 'T' ? 3u : 4u;
-}
-
-// the strand get_positions lists a reference base on: 0 '+', 1 '-', 2 = not listed
-__device__ __forceinline__ uint32_t listed_strand(const MkpDmrParams& P, uint32_t bidx, uint32_t rule) {
-  if (bidx > 3u) return 2u;
-  if (((P.pos_set >> bidx) & 1u) && (rule & 1u)) return 0u;
-  if (((P.neg_set >> bidx) & 1u) && (rule & 2u)) return 1u;
-  return 2u;
-}
-
-// a row at a position whose reference base is bidx, listed on strand `listed`
-__device__ __forceinline__ bool takes_part(const MkpDmrParams& P, uint32_t bidx, uint32_t listed, uint32_t sidx, uint32_t c, uint32_t nv) {
-  if (listed > 1u || (unsigned long long)nv < P.min_cov) return false;
-  uint32_t cb = 4u;
-  for (uint32_t k = 0; k < P.n_lookup; k++) if (P.code[k] == c) cb = P.base[k];
-  if (cb > 3u) return false;
-  const uint32_t cls = sidx == 1u ? 1u : 0u;   // get_stranded_position: '-' is negative, '+' and '.' positive
-  return cls == listed && (cls ? 3u - cb : cb) == bidx;
-}
 
 __global__ __launch_bounds__(256) void mkp_dmr_reduce(const uint32_t* __restrict__ pos, const uint32_t* __restrict__ info,
     const uint32_t* __restrict__ code, const uint32_t* __restrict__ n_valid, const uint32_t* __restrict__ n_mod, const uint32_t* __restrict__ n_can,

@@ -19,6 +19,7 @@
 
 #include "mkp_ctx.hpp"
 #include "mkp_dmr.hpp"
+#include "mkp_dmr_sites.hpp"
 #include "mkp_ingest_host.hpp"
 #include "mkp_focus.hpp"
 #include "mkp_regions.hpp"
@@ -2040,6 +2041,181 @@ extern "C" int mkp_dmr_pair_main(int argc, const char* const* argv, uint64_t* n_
       fprintf(stderr, "[mkpileup] dmr pair: %u regions, written=%llu; reader=%s regions+fasta_ms=%.1f reference_upload_ms=%.1f read_ms=%.1f (file read %.1f, upload %.1f, inflate %.1f, parse %.1f; %llu pieces) kernels: bounds+scan %.3f ms, reduce %.3f ms; score+text_ms=%.1f total_ms=%.1f\n",
           t.n_regions, (unsigned long long)written, host_read ? "host" : "device", load_ms, ref_ms, read_ms, in_ms[0], in_ms[1], in_ms[2], in_ms[3],
           (unsigned long long)pieces, ms[0], ms[1], ms_since(t_out), ms_since(t_all)); }
+    return MKP_OK;
+  });
+}
+
+// ---- `mkpileup dmr sites` = `modkit dmr pair` without -r (SingleSiteDmrAnalysis::run, src/dmr/single_site.rs) in stages: arguments,
+// reference, the two tables through the device reader (mkp_dmr_sites_add_file), the device stages (mkp_dmr_sites_get) and the text.  It is
+// not reached through `dmr pair` because that command's refusal of a run without -r is pinned by the suite.
+extern "C" int mkp_host_dmr_site_score(const uint64_t* a_mod, uint32_t a_has, uint64_t a_total, const uint64_t* b_mod, uint32_t b_has, uint64_t b_total,
+    uint32_t n_codes, double prior_alpha, double prior_beta, double delta, const uint32_t max_coverages[2], double values[5], int* failed) {
+  if ((!a_mod || !b_mod) && n_codes) return MKP_E_INVALID;
+  if (!max_coverages || !values || !failed || n_codes > MKP_DMR_SITE_MAX_CODES) return MKP_E_INVALID;
+  return guarded_status([&]() {
+    const MkpDmrSiteMath M = dmr_site_math(prior_alpha, prior_beta, delta, max_coverages);
+    *failed = dmr_site_score(a_mod, a_has, a_total, b_mod, b_has, b_total, n_codes, M, values) ? 0 : 1;
+    return MKP_OK; });
+}
+extern "C" int mkp_host_dmr_sites_batches(const uint64_t* contig_len, const uint32_t* window_counts, uint32_t n_contigs, uint64_t interval_size,
+    mkp_dmr_sites_batch* entries, uint64_t cap, uint64_t* n_batches) {
+  if ((!contig_len || !window_counts) && n_contigs) return MKP_E_INVALID;
+  if (!interval_size || (!entries && cap)) return MKP_E_INVALID;
+  int n = 0;
+  const int rc = guarded_status([&]() {
+    std::vector<mkp_dmr_sites_batch> plan;
+    const uint64_t nb = dmr_sites_plan(contig_len, window_counts, n_contigs, interval_size, &plan);
+    for (size_t e = 0; e < plan.size() && e < cap; e++) entries[e] = plan[e];
+    if (n_batches) *n_batches = nb;
+    if (plan.size() > 0x7fffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^31 - 1 batch entries");
+    n = (int)plan.size();
+    return MKP_OK; });
+  return rc == MKP_OK ? n : rc;
+}
+extern "C" int mkp_host_dmr_sites_gauss_legendre(double nodes[16], double weights[16]) {
+  if (!nodes || !weights) return MKP_E_INVALID;
+  dmr_gauss_legendre(nodes, weights);
+  return MKP_OK;
+}
+
+namespace {
+// the table in pieces on the host pool (30 000 f64 Display lines take 80 ms on one thread), joined in order
+std::string dmr_sites_table_text(const mkp_dmr_sites_out& t, const char* const* contig_names, bool header) {
+  const uint64_t piece = 8192, np = (t.n_sites + piece - 1) / piece;
+  std::vector<std::string> parts((size_t)np);
+  HostPool::get().parallel((size_t)np, [&](size_t i) { dmr_sites_rows_text(parts[i], t, contig_names, i * piece, std::min<uint64_t>(t.n_sites, (i + 1) * piece),
+      f32_display); });
+  size_t total = 0; for (const std::string& p : parts) total += p.size();
+  std::string s; s.reserve(total + 256);
+  if (header) s = dmr_sites_header();
+  for (const std::string& p : parts) s += p;
+  return s;
+}
+
+struct DmrSitesArgs {
+  std::vector<std::string> a, b, assign; std::string ref, out, bases, regions;
+  bool force = false, header = false, mask = false, stats = false, segment = false, have_prior = false, have_max = false, have_n = false, have_batch = false;
+  uint64_t min_cov = 0, n_sample = 10042, interval = 100000, batch_size = 0, threads = 4; double prior[2] = {0.55, 0.55}, delta = 0.05;
+  uint32_t max_cov[2] = {0, 0}; int device = 0;
+};
+
+DmrSitesArgs parse_dmr_sites_args(int argc, const char* const* argv) {
+  DmrSitesArgs d;
+  for (int i = 0; i < argc; i++) {
+    const std::string s = argv[i];
+    auto val = [&]() { if (i + 1 >= argc) throw Error(MKP_E_INVALID, "missing value for " + s); return std::string(argv[++i]); };
+    auto num = [&](const std::string& v) { try { size_t used = 0; const double x = std::stod(v, &used); if (used != v.size()) throw 0; return x; }
+      catch (...) { throw Error(MKP_E_INVALID, "invalid value '" + v + "' for " + s); } };
+    auto whole = [&](const std::string& v) { try { size_t used = 0; if (v.empty() || v[0] == '-') throw 0; const uint64_t x = std::stoull(v, &used);
+        if (used != v.size()) throw 0; return x; }
+      catch (...) { throw Error(MKP_E_INVALID, "invalid value '" + v + "' for " + s); } };
+    if (s == "-a") d.a.push_back(val()); else if (s == "-b") d.b.push_back(val());
+    else if (s == "-r" || s == "--regions-bed") d.regions = val(); else if (s == "--ref") d.ref = val();
+    else if (s == "-o" || s == "--out-path") d.out = val(); else if (s == "-f" || s == "--force") d.force = true;
+    else if (s == "--header" || s == "--with-header") d.header = true; else if (s == "-k" || s == "--mask") d.mask = true;
+    else if (s == "-m" || s == "--base") { const std::string v = val();
+      if (v.size() != 1) throw Error(MKP_E_INVALID, "modified base needs to be A, C, G, or T.");
+      d.bases += v; }
+    else if (s == "--assign-code") d.assign.push_back(val());
+    else if (s == "--min-valid-coverage") d.min_cov = whole(val());
+    else if (s == "--prior") { d.prior[0] = num(val()); d.prior[1] = num(val()); d.have_prior = true; }
+    else if (s == "--delta") d.delta = num(val());
+    else if (s == "--max-coverages") { for (int k = 0; k < 2; k++) { const uint64_t v = whole(val()); d.max_cov[k] = (uint32_t)std::min<uint64_t>(v, 0xffffffffu); }
+      d.have_max = true; }
+    else if (s == "-N" || s == "--n-sample-records") { d.n_sample = whole(val()); d.have_n = true; }
+    else if (s == "--cap-coverages") continue;   // (one sample a side: nothing to cap)
+    else if (s == "-i" || s == "--interval-size") d.interval = whole(val());
+    else if (s == "--batch-size") { d.batch_size = whole(val()); d.have_batch = true; }
+    else if (s == "-t" || s == "--threads") d.threads = whole(val());
+    else if (s == "--segment") { d.segment = true; val(); }
+    else if (s == "--device") d.device = std::stoi(val()); else if (s == "--stats") d.stats = true;
+    else if (s == "--io-threads" || s == "--log-filepath" || s == "--index-a" || s == "--index-b" || s == "--missing")
+      val();   // (the reference's tabix indices and io threads: no index is read)
+    else if (s == "--suppress-progress") continue;
+    else throw Error(MKP_E_INVALID, "unexpected argument '" + s + "' for dmr sites");
+  }
+  if (d.a.empty() || d.b.empty()) throw Error(MKP_E_INVALID, "need to provide at least 1 'a' sample and 'b' sample");
+  if (!d.regions.empty()) throw Error(MKP_E_INVALID, "-r / --regions-bed is the region form: use dmr pair (dmr sites scores every site of the two tables)");
+  if (d.segment) throw Error(MKP_E_UNSUPPORTED, "--segment (single-site segmentation) is not offered");
+  if (d.a.size() > 1 || d.b.size() > 1) throw Error(MKP_E_UNSUPPORTED,
+      "replicates (more than one -a or -b: balanced columns and per-replicate p-values) are not offered: one -a and one -b");
+  if (d.ref.empty()) throw Error(MKP_E_INVALID, "the following required arguments were not provided: --ref <REFERENCE_FASTA>");
+  if (d.bases.empty()) throw Error(MKP_E_INVALID, "need to specify at least 1 modified base");
+  for (char b : d.bases) if (!strchr("ACGT", b)) throw Error(MKP_E_INVALID, "modified base needs to be A, C, G, or T.");
+  if (d.have_prior && d.prior[0] + d.prior[1] < 1.0) throw Error(MKP_E_INVALID, "alpha + beta must be > 1.0 for numerical stability");
+  if (d.have_max && d.have_n) throw Error(MKP_E_INVALID,
+      "the argument '--max-coverages <MAX_COVERAGES> <MAX_COVERAGES>' cannot be used with '--n-sample-records <N_SAMPLE_RECORDS>'");
+  if (!d.have_batch) d.batch_size = (uint64_t)std::floor(1.5 * (double)d.threads);
+  return d;
+}
+}  // namespace
+
+extern "C" int mkp_host_dmr_sites_table(const mkp_dmr_sites_out* sites, const char* const* contig_names, uint32_t n_contigs, int with_header,
+    const char* out_path) {
+  if (!sites || !out_path || (!contig_names && n_contigs)) return MKP_E_INVALID;
+  return guarded_status([&]() {
+    for (uint64_t i = 0; i < sites->n_sites; i++) if (sites->tid[i] < 0 || (uint32_t)sites->tid[i] >= n_contigs) throw Error(MKP_E_INVALID,
+        "site " + std::to_string(i) + " lies on a contig without a name");
+    write_text_file(out_path, dmr_sites_table_text(*sites, contig_names, with_header != 0)); return MKP_OK; });
+}
+
+extern "C" int mkp_dmr_sites_main(int argc, const char* const* argv, uint64_t* n_written, char* errbuf, size_t errbuf_len) {
+  if (n_written) *n_written = 0;
+  return guarded_buf(errbuf, errbuf_len, [&]() {
+    const DmrSitesArgs d = parse_dmr_sites_args(argc, argv);
+    std::vector<uint32_t> codes; std::vector<uint8_t> code_bases;
+    { DmrArgs lookup_args; lookup_args.assign = d.assign; dmr_code_lookup(lookup_args, &codes, &code_bases); }
+    const bool to_stdout = d.out.empty() || d.out == "-" || d.out == "stdout";
+    struct stat sb;
+    if (!to_stdout && !d.force && stat(d.out.c_str(), &sb) == 0) throw Error(MKP_E_IO, "refusing to overwrite existing file " + d.out);
+    auto t_all = std::chrono::steady_clock::now();
+    const Fasta fasta = Fasta::load(d.ref);
+    const double load_ms = ms_since(t_all);
+    std::vector<std::string> names; std::vector<const char*> name_ptrs;
+    for (const auto& kv : fasta.seqs) names.push_back(kv.first);
+    for (const std::string& s : names) name_ptrs.push_back(s.c_str());
+    mkp_config cfg; memset(&cfg, 0, sizeof(cfg)); cfg.device = d.device;
+    mkp_ctx* ctx = nullptr;
+    if (mkp_ctx_create(&cfg, &ctx) != MKP_OK) throw Error(MKP_E_DEVICE, "no usable gfx950 device (libmkpileup has no CPU path)");
+    struct OwnedCtx { mkp_ctx* c; ~OwnedCtx() { mkp_ctx_destroy(c); } } owned{ctx};
+    mkp_dmr_sites_config sc; memset(&sc, 0, sizeof(sc));
+    sc.contig_names = name_ptrs.data(); sc.n_contigs = (uint32_t)name_ptrs.size(); sc.bases = d.bases.data(); sc.n_bases = (uint32_t)d.bases.size();
+    sc.codes = codes.data(); sc.code_bases = code_bases.data(); sc.n_lookup = (uint32_t)codes.size(); sc.respect_mask = d.mask ? 1 : 0;
+    sc.min_valid_coverage = d.min_cov; sc.prior_alpha = d.prior[0]; sc.prior_beta = d.prior[1]; sc.delta = d.delta;
+    sc.have_max_coverages = d.have_max ? 1 : 0; sc.max_coverages[0] = d.max_cov[0]; sc.max_coverages[1] = d.max_cov[1];
+    sc.n_sample_records = d.n_sample; sc.interval_size = d.interval; sc.batch_size = d.batch_size;
+    must(ctx, mkp_dmr_sites_begin(ctx, &sc));
+    auto t_ref = std::chrono::steady_clock::now();
+    for (size_t tid = 0; tid < names.size(); tid++) { const FastaSeq* seq = fasta.get(names[tid]);
+      must(ctx, mkp_dmr_sites_set_reference(ctx, (int32_t)tid, (const uint8_t*)seq->data(), seq->size())); }
+    const double ref_ms = ms_since(t_ref);
+    auto t_read = std::chrono::steady_clock::now();
+    const bool host_read = Knobs::one("MKP_HOST_BEDMETHYL");
+    for (int sample = 0; sample < 2; sample++) {
+      const std::string& path = sample ? d.b[0] : d.a[0];
+      if (!host_read) { must(ctx, mkp_dmr_sites_add_file(ctx, sample, path.c_str(), nullptr)); continue; }
+      const mkp_bedmethyl_file f = read_bedmethyl_text(path);
+      for (size_t k = 0; k < f.runs.size(); k++) {
+        const auto it = std::find(names.begin(), names.end(), f.runs[k].chrom);
+        if (it == names.end()) continue;
+        const mkp_rows rows = f.rows_of(k);
+        must(ctx, mkp_dmr_sites_add_rows(ctx, sample, (int32_t)(it - names.begin()), &rows));
+      }
+    }
+    const double read_ms = ms_since(t_read);
+    auto t_get = std::chrono::steady_clock::now();
+    mkp_dmr_sites_out t; must(ctx, mkp_dmr_sites_get(ctx, &t));
+    const double get_ms = ms_since(t_get);
+    auto t_out = std::chrono::steady_clock::now();
+    const std::string text = dmr_sites_table_text(t, name_ptrs.data(), d.header);
+    if (to_stdout) { if (fwrite(text.data(), 1, text.size(), stdout) != text.size()) throw Error(MKP_E_IO, "short write on stdout"); fflush(stdout); }
+    else write_text_file(d.out, text);
+    if (n_written) *n_written = t.n_sites;
+    if (d.stats) { double ms[7] = {0, 0, 0, 0, 0, 0, 0}; mkp_internal_dmr_sites_timing(ctx, ms);
+      fprintf(stderr, "[mkpileup] dmr sites: written=%llu model_failures=%llu batches=%llu dropped=%llu max_coverages=%u,%u sampled=%llu,%llu; reader=%s fasta_ms=%.1f reference_upload_ms=%.1f read_ms=%.1f get_ms=%.1f (listed %.3f, heads %.3f, estimate %.3f, bad+join %.3f, score %.3f, read-back %.3f, assembly %.3f) text_ms=%.1f total_ms=%.1f\n",
+          (unsigned long long)t.n_sites, (unsigned long long)t.n_model_failures, (unsigned long long)t.n_batches, (unsigned long long)t.n_batches_dropped,
+          t.max_coverages[0], t.max_coverages[1], (unsigned long long)t.n_sampled[0], (unsigned long long)t.n_sampled[1], host_read ? "host" : "device",
+          load_ms, ref_ms, read_ms, get_ms, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6], ms_since(t_out), ms_since(t_all)); }
     return MKP_OK;
   });
 }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "mkp_device.h"
+#include "mkp_dmr_site_math.hpp"
 
 // mkp_ingest_dev.hpp (the ingest launchers take these by pointer only; the header itself stays out of the other translation units)
 struct MkpZChain; struct MkpZBlk; struct MkpSeg; struct MkpIngestParams; struct MkpIngestTotals; struct MkpRecInfo; struct MkpRecDigest;
@@ -124,6 +125,32 @@ hipError_t mkp_launch_dmr(hipStream_t st, const uint32_t* pos, const uint32_t* i
 hipError_t mkp_launch_localize(hipStream_t st, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
     const uint32_t* n_mod, uint32_t n_rows, const MkpLocRegion* regions, uint32_t n_regions, uint32_t* row_lo, uint32_t* row_hi, uint32_t window,
     uint32_t stranded, unsigned long long* tab, uint32_t* codes, uint32_t* err, hipEvent_t* ev);
+
+// ---- mkp_dmr_sites.hip: the rows of ONE contig of one sample (pos .. n_can: row columns, n_rows rows), the contig's reference bytes [0, ref_len)
+// counts: n_windows words, the listed positions per window of `interval` bp
+hipError_t mkp_launch_dmr_sites_listed(hipStream_t st, const uint8_t* ref, uint32_t ref_len, unsigned long long interval, uint32_t n_windows,
+    const MkpDmrParams* prm, uint32_t* counts);
+// flags + scan + heads.  codes / err: the run's slot codes and error word; rowflag: a byte a row; tile_cnt: two words per tile of MKP_DMRS_TILE
+// rows, left as the exclusive prefixes of heads and participating rows; totals: two words, sites and participating rows; s_*: the sites
+hipError_t mkp_launch_dmr_sites_heads(hipStream_t st, const uint32_t* pos, const uint32_t* info, const uint32_t* code, const uint32_t* n_valid,
+    const uint32_t* n_mod, const uint32_t* n_can, uint32_t n_rows, const uint8_t* ref, uint32_t ref_len, const MkpDmrParams* prm, uint32_t* codes,
+    uint32_t* err, uint8_t* rowflag, uint32_t* tile_cnt, uint32_t* totals, uint32_t* s_pos, uint32_t* s_first, uint32_t* s_total, uint32_t* s_info);
+// per entry of the contig's batch table: the first row at or behind its start, and the participating rows in front of that row
+hipError_t mkp_launch_dmr_sites_bounds(hipStream_t st, const uint32_t* pos, const uint8_t* rowflag, uint32_t n_rows, const uint32_t* tile_off,
+    const uint32_t* totals, const MkpDmrSitesBatch* batches, uint32_t n_entries, uint32_t* row_at, uint32_t* part_before);
+// out[*cursor ++] = N_valid_cov of every participating row among the first n_front (any order; a value past `cap` is dropped)
+hipError_t mkp_launch_dmr_sites_coverages(hipStream_t st, const uint8_t* rowflag, const uint32_t* n_valid, uint32_t n_front, uint32_t* cursor,
+    uint32_t* out, uint32_t cap);
+// bad_batch: a word per batch of the run, set by a bad site of either sample
+hipError_t mkp_launch_dmr_sites_bad(hipStream_t st, const uint32_t* s_pos, const uint32_t* s_info, uint32_t n_sites, const MkpDmrSitesBatch* batches,
+    uint32_t n_entries, uint32_t* bad_batch);
+// join + scan + pairs.  partner: n_a words; tile_cnt: two words per tile of a's sites; totals[0]: the pairs; pair_a / pair_b: site indices
+hipError_t mkp_launch_dmr_sites_join(hipStream_t st, const uint32_t* a_pos, uint32_t n_a, const uint32_t* b_pos, uint32_t n_b,
+    const MkpDmrSitesBatch* batches, uint32_t n_entries, const uint32_t* bad_batch, uint32_t* partner, uint32_t* tile_cnt, uint32_t* totals,
+    uint32_t* pair_a, uint32_t* pair_b);
+// col_of_slot: 4 bits a slot, its code column (columns ascend in code); a, b, math, out: host copies
+hipError_t mkp_launch_dmr_sites_score(hipStream_t st, const MkpDmrSitesSample* a, const MkpDmrSitesSample* b, const uint32_t* pair_a,
+    const uint32_t* pair_b, uint32_t n_pairs, unsigned long long col_of_slot, uint32_t n_cols, const MkpDmrSiteMath* math, const MkpDmrSitesPairs* out);
 
 // ---- mkp_merge.hip.  a: the table, b: the added rows, stage: staging, out: the new table, *n_out its rows; cuts: mkp_merge_tiles(n_a + n_b) + 1
 // entries, counts / offsets: mkp_merge_tiles(n_a + n_b) each; ev: 3 timing events or NULL
