@@ -160,7 +160,7 @@ const char* mkp_version(void);
  * revision 2; round 6 = 3).  The library writes whole structs of its own revision, so a caller built against another header must not
  * hand it its structs: compare once at start-up —  `mkp_abi_version() == MKP_ABI_VERSION && mkp_run_report_size() == sizeof(mkp_run_report)`
  * (the Rust binding asserts the same on its #[repr(C)] mirror). */
-#define MKP_ABI_VERSION 4u
+#define MKP_ABI_VERSION 5u
 uint32_t mkp_abi_version(void);
 size_t mkp_run_report_size(void);
 /* Threads of the library's host pool (BGZF inflate, packing, planning, text): the CPUs this process may use — affinity mask and
@@ -620,8 +620,8 @@ int mkp_dmr_pair_main(int argc, const char* const* argv, uint64_t* n_written, ch
 
 /* ---- `modkit dmr pair -a a.bed.gz -b b.bed.gz --ref ref.fa --base C` without -r (SingleSiteDmrAnalysis::run, src/dmr/single_site.rs;
  * beta_diff.rs, llr_model.rs): the two tables compared position by position; every site both hold gets the likelihood-ratio score and the
- * MAP-based p-value with its effect size, in f64 on the device (mkp_dmr_sites.hip, one lane a site).  One `a` against one `b`; replicates
- * and --segment are not offered.  Both tables' row columns stay in HBM per contig from the add calls to mkp_dmr_sites_get (24 B a row); a
+ * MAP-based p-value with its effect size, in f64 on the device (mkp_dmr_sites.hip, one lane a site).  One `a` against one `b`: replicates
+ * are mkp_dmr_reps_* below; --segment is not offered.  Both tables' row columns stay in HBM per contig from the add calls to mkp_dmr_sites_get (24 B a row); a
  * pair of tables beyond the budget of 3/4 of the device's memory is MKP_E_UNSUPPORTED.
  *   mkp_dmr_sites_begin          cfg: contig_names[tid] (contigs are walked in byte order of their names); bases / codes / code_bases /
  *                                min_valid_coverage / respect_mask as mkp_dmr_begin; prior Beta(prior_alpha, prior_beta) (alpha + beta < 1
@@ -653,7 +653,8 @@ int mkp_dmr_pair_main(int argc, const char* const* argv, uint64_t* n_written, ch
  * mkp_dmr_sites_main = `mkpileup dmr sites -a a.bed[.gz] -b b.bed[.gz] --ref ref.fa --base C [--base A ..] [-o out.bed] [-f] [--header]
  *   [--min-valid-coverage N] [--assign-code x:C] [--mask] [--prior ALPHA BETA] [--delta D] [--max-coverages A B] [-N/--n-sample-records N]
  *   [--cap-coverages] [-i/--interval-size BP] [--batch-size N | -t/--threads T] [--device N] [--stats]`; *n_written (may be NULL) = the sites
- *   written.  -r is MKP_E_INVALID (that is `dmr pair`), --segment and more than one -a / -b are MKP_E_UNSUPPORTED. */
+ *   written.  -r is MKP_E_INVALID (that is `dmr pair`), --segment and more than one -a / -b (replicates: that is `dmr replicates`) are
+ *   MKP_E_UNSUPPORTED. */
 typedef struct { const char* const* contig_names; uint32_t n_contigs; const char* bases; uint32_t n_bases; const uint32_t* codes;
                  const uint8_t* code_bases; uint32_t n_lookup; uint32_t respect_mask; uint64_t min_valid_coverage; double prior_alpha, prior_beta,
                  delta; uint32_t have_max_coverages; uint32_t max_coverages[2]; uint32_t reserved; uint64_t n_sample_records, interval_size,
@@ -677,6 +678,55 @@ int mkp_host_dmr_sites_batches(const uint64_t* contig_len, const uint32_t* windo
 int mkp_host_dmr_sites_gauss_legendre(double nodes[16], double weights[16]);
 int mkp_host_dmr_sites_table(const mkp_dmr_sites_out* sites, const char* const* contig_names, uint32_t n_contigs, int with_header, const char* out_path);
 int mkp_dmr_sites_main(int argc, const char* const* argv, uint64_t* n_written, char* errbuf, size_t errbuf_len);
+
+/* ---- `modkit dmr pair -a a1.bed.gz -a a2.bed.gz .. -b b1.bed.gz -b b2.bed.gz .. --ref ref.fa --base C` without -r: replicates
+ * (SingleSiteDmrScore::new_multi, collapse_counts, to_row, src/dmr/single_site.rs; SingleSiteSampleIndex, src/dmr/tabix.rs).  n_a >= 1 and
+ * n_b >= 1 tables, at most 16 a side (more is MKP_E_UNSUPPORTED); multiple = n_a > 1 || n_b > 1, matched = n_a == n_b && n_a > 1.  Everything
+ * mkp_dmr_sites_* says about rows, groups, batches, the contig walk and the two counters holds per sample; beyond it (mkp_dmr_reps.hip):
+ *   - the contigs are those with a reference, rows in at least one `a` table and rows in at least one `b` table; a position whose group fails in
+ *     ANY sample of EITHER side drops its batch for every sample;
+ *   - a site is a position at least one `a` and one `b` sample hold; its present samples are listed in ascending command-line index (the
+ *     reference takes the iteration order of an FxHashMap: a deliberate, deterministic departure);
+ *   - total / n_mod / has_code, score, map_pvalue and effect_size come from the counts summed over the present samples (collapse_counts(_,
+ *     false)); balanced_map_pvalue / balanced_effect_size from the coverage-balanced counts (collapse_counts(_, true), f32 arithmetic,
+ *     mkp_dmr_reps_math.hpp); pct_samples[side][site] = floor(present / n * 100) in f32;
+ *   - with matched sides and as many present `a` as `b` samples, n_rep[site] = that number and rep_pvalue / rep_effect[site * n_a + i] = the
+ *     i-th present `a` sample against the i-th present `b` sample (pairing by rank); otherwise n_rep[site] = 0.  rep_pvalue and rep_effect
+ *     are NULL unless matched;
+ *   - a site any of whose evaluations fails (each replicate pair, the balanced p-value and likelihood ratio, the collapsed p-value and
+ *     likelihood ratio) is not written and counted once in n_model_failures; where a sample's balanced counts sum beyond its balanced total
+ *     the reference aborts (try_new(..).unwrap()): here that is a model failure as well;
+ *   - the max coverages, given or estimated, are multiplied by the side's number of tables unless cap_coverages != 0 (`--cap-coverages`), then
+ *     capped at 300 (PMapEstimator::new): sites.max_coverages reports these values;
+ *   - estimated max coverages pool the coverages of the participating rows of all `a` samples, and of all `b` samples; sampling stops
+ *     behind the super-batch at which both pools hold n_sample_records values;
+ *   - a summed coverage beyond 2^32 - 1 is MKP_E_UNSUPPORTED.
+ * mkp_dmr_reps_add_rows / _add_file take the side (0 = a, 1 = b) and the replicate (the table's index among the side's -a / -b); tables may
+ * be added in any order, a contig's pieces of one table in ascending order.  All tables' row columns stay in HBM (24 B a row, 3/4 of the
+ * device's memory at most).  With n_a == n_b == 1 the sites and the text are what mkp_dmr_sites_* give.
+ * Host-only: mkp_host_dmr_reps_balance = collapse_counts(_, true) of one side of one site: n_samples present samples with
+ *   n_mod[s * n_codes + k], has_code[s], total[s]; out_mod[n_codes], *out_has, *out_total; *failed = a sample's balanced counts exceed its
+ *   balanced total.  mkp_host_dmr_reps_pct = the share of samples.  mkp_host_dmr_reps_table writes SingleSiteDmrScore::header(multiple,
+ *   matched) / to_row: the 16 columns of mkp_host_dmr_sites_table, with `multiple` balanced_map_pvalue, balanced_effect_size, pct_a_samples,
+ *   pct_b_samples, with `matched` replicate_map_pvalues and replicate_effect_sizes (comma-joined f64 Display, `-` where n_rep is 0).
+ * mkp_dmr_reps_main = `mkpileup dmr replicates -a a1.bed[.gz] [-a a2.bed[.gz] ..] -b b1.bed[.gz] [-b ..] --ref ref.fa --base C` and every
+ *   other flag of mkp_dmr_sites_main; -r is MKP_E_INVALID, --segment and more than 16 tables a side MKP_E_UNSUPPORTED. */
+#define MKP_DMR_REPS_MAX_SIDE 16u
+typedef struct { mkp_dmr_sites_out sites;   /* the 16 columns' values; total / n_mod / has_code = the collapsed counts */
+                 uint32_t n_a, n_b;
+                 const double* balanced_map_pvalue; const double* balanced_effect_size;
+                 const uint32_t* pct_samples[2];
+                 const uint32_t* n_rep; const double* rep_pvalue; const double* rep_effect; } mkp_dmr_reps_out;
+int mkp_dmr_reps_begin(mkp_ctx* ctx, const mkp_dmr_sites_config* cfg, uint32_t n_a, uint32_t n_b, int cap_coverages);
+int mkp_dmr_reps_set_reference(mkp_ctx* ctx, int32_t tid, const uint8_t* bytes, uint64_t len);
+int mkp_dmr_reps_add_rows(mkp_ctx* ctx, int side, int replicate, int32_t tid, const mkp_rows* rows);
+int mkp_dmr_reps_add_file(mkp_ctx* ctx, int side, int replicate, const char* path, uint64_t* n_rows);
+int mkp_dmr_reps_get(mkp_ctx* ctx, mkp_dmr_reps_out* out);
+int mkp_host_dmr_reps_balance(const uint64_t* n_mod, const uint32_t* has_code, const uint64_t* total, uint32_t n_samples, uint32_t n_codes,
+                              uint64_t* out_mod, uint32_t* out_has, uint64_t* out_total, int* failed);
+uint32_t mkp_host_dmr_reps_pct(uint32_t n_present, uint32_t n_samples);
+int mkp_host_dmr_reps_table(const mkp_dmr_reps_out* sites, const char* const* contig_names, uint32_t n_contigs, int with_header, const char* out_path);
+int mkp_dmr_reps_main(int argc, const char* const* argv, uint64_t* n_written, char* errbuf, size_t errbuf_len);
 
 /* ---- BGZF inflate on the device as a call of its own.  On the pileup path the same kernels run inside the device ingest
  * (`mkp_pileup_main` on an indexed BAM: compressed blocks up, inflate + CRC-32 + record cut + MM/ML tokeniser + packing in HBM, a digest

@@ -160,6 +160,18 @@ def lib():
             L.mkp_host_dmr_sites_gauss_legendre.argtypes = [f64p, f64p]
             L.mkp_host_dmr_sites_table.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p]
             L.mkp_dmr_sites_main.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), u64p, ctypes.c_char_p, ctypes.c_size_t]
+        if hasattr(L, "mkp_dmr_reps_begin"):
+            u32p = ctypes.POINTER(ctypes.c_uint32)
+            L.mkp_dmr_reps_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int]
+            L.mkp_dmr_reps_set_reference.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.c_char_p, ctypes.c_uint64]
+            L.mkp_dmr_reps_add_rows.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int32, ctypes.c_void_p]
+            L.mkp_dmr_reps_add_file.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_char_p, u64p]
+            L.mkp_dmr_reps_get.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            L.mkp_host_dmr_reps_balance.argtypes = [u64p, u32p, u64p, ctypes.c_uint32, ctypes.c_uint32, u64p, u32p, u64p, ctypes.POINTER(ctypes.c_int)]
+            L.mkp_host_dmr_reps_pct.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+            L.mkp_host_dmr_reps_pct.restype = ctypes.c_uint32
+            L.mkp_host_dmr_reps_table.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32, ctypes.c_int, ctypes.c_char_p]
+            L.mkp_dmr_reps_main.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_char_p), u64p, ctypes.c_char_p, ctypes.c_size_t]
         # the structs this binding allocates mirror ONE revision of include/mkpileup.h: a library of another revision would write past them
         if os.environ.get("MKP_LIB_PATH") and not hasattr(L, "mkp_abi_version"):
             _lib = L   # (A/B runs against a build from before the query existed, tools/dbg/ab.sh)
@@ -173,7 +185,7 @@ def lib():
     return _lib
 
 
-ABI_VERSION = 4   # MKP_ABI_VERSION of include/mkpileup.h
+ABI_VERSION = 5   # MKP_ABI_VERSION of include/mkpileup.h
 READ_WIDE_CIGAR = 32   # MKP_READ_WIDE_CIGAR
 
 
@@ -196,7 +208,9 @@ EXPORTS = ["mkp_ctx_create", "mkp_ctx_destroy", "mkp_last_error", "mkp_version",
            "mkp_dmr_default_lookup", "mkp_dmr_begin", "mkp_dmr_set_reference", "mkp_dmr_add_rows", "mkp_dmr_add_file", "mkp_dmr_add_resident", "mkp_dmr_get",
            "mkp_host_parse_dmr_regions", "mkp_host_dmr_judge", "mkp_host_dmr_table", "mkp_dmr_pair_main",
            "mkp_dmr_sites_begin", "mkp_dmr_sites_set_reference", "mkp_dmr_sites_add_rows", "mkp_dmr_sites_add_file", "mkp_dmr_sites_get",
-           "mkp_host_dmr_site_score", "mkp_host_dmr_sites_batches", "mkp_host_dmr_sites_gauss_legendre", "mkp_host_dmr_sites_table", "mkp_dmr_sites_main"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
+           "mkp_host_dmr_site_score", "mkp_host_dmr_sites_batches", "mkp_host_dmr_sites_gauss_legendre", "mkp_host_dmr_sites_table", "mkp_dmr_sites_main",
+           "mkp_dmr_reps_begin", "mkp_dmr_reps_set_reference", "mkp_dmr_reps_add_rows", "mkp_dmr_reps_add_file", "mkp_dmr_reps_get",
+           "mkp_host_dmr_reps_balance", "mkp_host_dmr_reps_pct", "mkp_host_dmr_reps_table", "mkp_dmr_reps_main"]   # (mkp_genome_sizes_length returns a uint64_t, as mkp_region_set_regions a pointer: not listed)
 
 
 def pileup(argv):
@@ -260,7 +274,8 @@ def dmr_sites(argv):
     """`modkit dmr pair` without -r (SingleSiteDmrAnalysis::run, src/dmr/single_site.rs) on the device: argv = ["-a", a.bed[.gz], "-b", b.bed[.gz],
     "--ref", ref.fa, "--base", "C", "-o", out.bed, "-f", "--header", "--min-valid-coverage", N, "--assign-code", "x:C", "--mask", "--prior", A, B,
     "--delta", D, "--max-coverages", A, B, "-N", N, "--cap-coverages", "-i", BP, "--batch-size", N, "-t", T]; the tables are read by the device
-    reader (Context.dmr_sites_add_file; MKP_HOST_BEDMETHYL=1: by the host reader).  -r, --segment and more than one -a / -b are refused.
+    reader (Context.dmr_sites_add_file; MKP_HOST_BEDMETHYL=1: by the host reader).  -r, --segment and more than one -a / -b (that is
+    dmr_replicates) are refused.
     Returns the number of sites written."""
     L = lib()
     args = [str(a).encode() for a in argv]
@@ -268,6 +283,23 @@ def dmr_sites(argv):
     err = ctypes.create_string_buffer(2048)
     written = ctypes.c_uint64(0)
     rc = L.mkp_dmr_sites_main(len(args), arr, ctypes.byref(written), err, len(err))
+    if rc != MKP_OK:
+        raise MkpError(rc, err.value.decode(errors="replace"))
+    return int(written.value)
+
+
+def dmr_replicates(argv):
+    """`modkit dmr pair` without -r over replicates (SingleSiteDmrScore::new_multi, src/dmr/single_site.rs) on the device: argv = ["-a", a1.bed[.gz],
+    "-a", a2.bed[.gz], .., "-b", b1.bed[.gz], "-b", b2.bed[.gz], .., "--ref", ref.fa, "--base", "C", ..] with every other flag of dmr_sites; at most
+    16 tables a side.  With several tables on a side the rows gain balanced_map_pvalue, balanced_effect_size, pct_a_samples and pct_b_samples,
+    with as many -a as -b (more than one) also replicate_map_pvalues and replicate_effect_sizes.  -r and --segment are refused.  Returns the
+    number of sites written."""
+    L = lib()
+    args = [str(a).encode() for a in argv]
+    arr = (ctypes.c_char_p * max(1, len(args)))(*args)
+    err = ctypes.create_string_buffer(2048)
+    written = ctypes.c_uint64(0)
+    rc = L.mkp_dmr_reps_main(len(args), arr, ctypes.byref(written), err, len(err))
     if rc != MKP_OK:
         raise MkpError(rc, err.value.decode(errors="replace"))
     return int(written.value)
@@ -361,6 +393,14 @@ class DmrSitesOut(ctypes.Structure):
                 ("n_batches_dropped", ctypes.c_uint64), ("n_model_failures", ctypes.c_uint64)]
 
 
+class DmrRepsOut(ctypes.Structure):
+    """mkp_dmr_reps_out: mkp_dmr_sites_out over the collapsed counts, then what replicates add."""
+    _fields_ = [("sites", DmrSitesOut), ("n_a", ctypes.c_uint32), ("n_b", ctypes.c_uint32), ("balanced_map_pvalue", ctypes.POINTER(ctypes.c_double)),
+                ("balanced_effect_size", ctypes.POINTER(ctypes.c_double)), ("pct_samples", ctypes.POINTER(ctypes.c_uint32) * 2),
+                ("n_rep", ctypes.POINTER(ctypes.c_uint32)), ("rep_pvalue", ctypes.POINTER(ctypes.c_double)),
+                ("rep_effect", ctypes.POINTER(ctypes.c_double))]
+
+
 class DmrSitesBatch(ctypes.Structure):
     """mkp_dmr_sites_batch: where a batch of the reference's walk begins inside a contig."""
     _fields_ = [("contig", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("start", ctypes.c_uint64), ("batch", ctypes.c_uint64)]
@@ -427,6 +467,53 @@ def write_dmr_sites_table(sites, contig_names, out_path, header=False):
     del keep
     if rc != MKP_OK:
         raise MkpError(rc, "mkp_host_dmr_sites_table failed")
+
+
+def host_dmr_reps_balance(n_mod, has_code, total):
+    """mkp_host_dmr_reps_balance: collapse_counts(_, true) of one side of one site.  n_mod[s] = sample s's counts per code column, has_code[s] the
+    mask of the columns in its key set, total[s] its total.  Returns (counts per column, column mask, total, failed)."""
+    n, k = len(total), (len(n_mod[0]) if n_mod else 0)
+    flat = [int(x) for row in n_mod for x in row]
+    nm, hs, tt = (ctypes.c_uint64 * max(1, len(flat)))(*flat), (ctypes.c_uint32 * max(1, n))(*has_code), (ctypes.c_uint64 * max(1, n))(*total)
+    om, oh, ot, failed = (ctypes.c_uint64 * max(1, k))(), ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_int(0)
+    rc = lib().mkp_host_dmr_reps_balance(nm, hs, tt, n, k, om, ctypes.byref(oh), ctypes.byref(ot), ctypes.byref(failed))
+    if rc != MKP_OK:
+        raise MkpError(rc, "mkp_host_dmr_reps_balance failed")
+    return list(om)[:k], int(oh.value), int(ot.value), bool(failed.value)
+
+
+def host_dmr_reps_pct(n_present, n_samples):
+    """mkp_host_dmr_reps_pct: floor(n_present / n_samples * 100) in f32, the pct_a_samples / pct_b_samples of a site."""
+    return int(lib().mkp_host_dmr_reps_pct(int(n_present), int(n_samples)))
+
+
+def write_dmr_reps_table(sites, contig_names, out_path, header=False):
+    """mkp_host_dmr_reps_table: the table of `sites` (the dict Context.dmr_reps_get returns, or one a caller filled: the keys of
+    write_dmr_sites_table's, "n_a", "n_b", "balanced_map_pvalue", "balanced_effect_size", "pct_samples" (a, b), "n_rep" and, with matched sides,
+    "rep_pvalue" / "rep_effect" of shape [n, n_a])."""
+    import numpy as np
+    u32p, f64p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_double)
+    inner, keep = dmr_sites_out_from(sites)
+    o = DmrRepsOut(sites=inner, n_a=int(sites["n_a"]), n_b=int(sites["n_b"]))
+    n = len(keep["pos"])
+    for f in ("balanced_map_pvalue", "balanced_effect_size"):
+        keep[f] = np.ascontiguousarray(np.asarray(sites[f], dtype=np.float64))
+        setattr(o, f, keep[f].ctypes.data_as(f64p))
+    for s in range(2):
+        a = keep["pct", s] = np.ascontiguousarray(np.asarray(sites["pct_samples"][s], dtype=np.uint32))
+        o.pct_samples[s] = a.ctypes.data_as(u32p)
+    keep["n_rep"] = np.ascontiguousarray(np.asarray(sites["n_rep"], dtype=np.uint32))
+    o.n_rep = keep["n_rep"].ctypes.data_as(u32p)
+    if o.n_a == o.n_b and o.n_a > 1:
+        for f in ("rep_pvalue", "rep_effect"):
+            keep[f] = np.ascontiguousarray(np.asarray(sites[f], dtype=np.float64).reshape(n, o.n_a))
+            setattr(o, f, keep[f].ctypes.data_as(f64p))
+    enc = [str(x).encode() for x in contig_names]
+    arr = (ctypes.c_char_p * max(1, len(enc)))(*enc)
+    rc = lib().mkp_host_dmr_reps_table(ctypes.byref(o), arr, len(enc), int(bool(header)), str(out_path).encode())
+    del keep
+    if rc != MKP_OK:
+        raise MkpError(rc, "mkp_host_dmr_reps_table failed")
 
 
 DMR_WRITTEN, DMR_NO_CONTIG, DMR_NO_REFERENCE, DMR_BAD, DMR_MODEL = 0, 1, 2, 3, 4   # MKP_DMR_* (mkp_dmr_out.state)
@@ -1066,6 +1153,62 @@ class Context:
              "n_model_failures": int(o.n_model_failures)}
         for f, shape in (("total", (n,)), ("n_mod", (n, k)), ("has_code", (n,))):
             d[f] = [arr(getattr(o, f)[s], shape, "u4") for s in range(2)]
+        return d
+
+    def dmr_reps_begin(self, contig_names, n_a, n_b, bases=("C",), lookup=None, min_valid_coverage=0, mask=False, prior=(0.55, 0.55), delta=0.05,
+                       max_coverages=None, n_sample_records=10042, interval_size=100000, batch_size=6, cap_coverages=False):
+        """mkp_dmr_reps_begin: n_a / n_b = the tables of a side (1 .. 16); the max coverages (given or estimated) are multiplied by the side's
+        number of tables unless cap_coverages, then capped at 300; everything else as dmr_sites_begin."""
+        lk = dmr_default_lookup() if lookup is None else {code_repr(c): b for c, b in lookup.items()}
+        enc = [str(n).encode() for n in contig_names]
+        bs = "".join(bases).encode()
+        cfg = DmrSitesConfig(contig_names=(ctypes.c_char_p * max(1, len(enc)))(*enc), n_contigs=len(enc), bases=bs, n_bases=len(bs),
+                             codes=(ctypes.c_uint32 * max(1, len(lk)))(*lk.keys()),
+                             code_bases=(ctypes.c_uint8 * max(1, len(lk)))(*["ACGT".index(b) for b in lk.values()]), n_lookup=len(lk),
+                             respect_mask=int(bool(mask)), min_valid_coverage=int(min_valid_coverage), prior_alpha=float(prior[0]),
+                             prior_beta=float(prior[1]), delta=float(delta), have_max_coverages=int(max_coverages is not None),
+                             n_sample_records=int(n_sample_records), interval_size=int(interval_size), batch_size=int(batch_size))
+        if max_coverages is not None:
+            cfg.max_coverages[0], cfg.max_coverages[1] = int(max_coverages[0]), int(max_coverages[1])
+        self._check(self.L.mkp_dmr_reps_begin(self.h, ctypes.byref(cfg), int(n_a), int(n_b), int(bool(cap_coverages))))
+
+    def dmr_reps_set_reference(self, tid, seq):
+        """mkp_dmr_reps_set_reference: seq = the whole sequence of contig tid."""
+        b = seq if isinstance(seq, bytes) else str(seq).encode()
+        self._check(self.L.mkp_dmr_reps_set_reference(self.h, int(tid), b, len(b)))
+
+    def dmr_reps_add_rows(self, side, replicate, tid, rows):
+        """mkp_dmr_reps_add_rows: rows of ONE contig of table `replicate` of side 0 (a) or 1 (b), ascending pos, a dict of arrays with all eleven
+        columns."""
+        r, _keep = _rows_struct(rows, all_columns=True)
+        self._check(self.L.mkp_dmr_reps_add_rows(self.h, int(side), int(replicate), int(tid), ctypes.byref(r)))
+
+    def dmr_reps_add_file(self, side, replicate, path):
+        """mkp_dmr_reps_add_file: a whole bedMethyl file (plain text or bgzip) through the device reader; returns its rows."""
+        n = ctypes.c_uint64(0)
+        self._check(self.L.mkp_dmr_reps_add_file(self.h, int(side), int(replicate), str(path).encode(), ctypes.byref(n)))
+        return int(n.value)
+
+    def dmr_reps_get(self):
+        """mkp_dmr_reps_get: the dict of dmr_sites_get over the collapsed counts, and "n_a", "n_b", "balanced_map_pvalue" / "balanced_effect_size"
+        f64[n], "pct_samples" (u32[n], u32[n]), "n_rep" u32[n] and, with matched sides, "rep_pvalue" / "rep_effect" f64[n, n_a] (row i holds
+        n_rep[i] values); otherwise those two are None."""
+        o = DmrRepsOut()
+        self._check(self.L.mkp_dmr_reps_get(self.h, ctypes.byref(o)))
+        t = o.sites
+        n, k, arr = int(t.n_sites), int(t.n_codes), _copy_out
+        d = {"codes": arr(t.code_repr, (k,), "u4"), "tid": arr(t.tid, (n,), "i4"), "pos": arr(t.pos, (n,), "u4"),
+             "strand": arr(t.strand, (n,), "u1").tobytes().decode(), "score": arr(t.score, (n,), "f8"), "map_pvalue": arr(t.map_pvalue, (n,), "f8"),
+             "effect_size": arr(t.effect_size, (n,), "f8"), "max_coverages": (int(t.max_coverages[0]), int(t.max_coverages[1])),
+             "n_sampled": (int(t.n_sampled[0]), int(t.n_sampled[1])), "n_batches": int(t.n_batches), "n_batches_dropped": int(t.n_batches_dropped),
+             "n_model_failures": int(t.n_model_failures), "n_a": int(o.n_a), "n_b": int(o.n_b),
+             "balanced_map_pvalue": arr(o.balanced_map_pvalue, (n,), "f8"), "balanced_effect_size": arr(o.balanced_effect_size, (n,), "f8"),
+             "pct_samples": tuple(arr(o.pct_samples[s], (n,), "u4") for s in range(2)), "n_rep": arr(o.n_rep, (n,), "u4")}
+        for f, shape in (("total", (n,)), ("n_mod", (n, k)), ("has_code", (n,))):
+            d[f] = [arr(getattr(t, f)[s], shape, "u4") for s in range(2)]
+        matched = o.n_a == o.n_b and o.n_a > 1
+        d["rep_pvalue"] = arr(o.rep_pvalue, (n, int(o.n_a)), "f8") if matched else None
+        d["rep_effect"] = arr(o.rep_effect, (n, int(o.n_a)), "f8") if matched else None
         return d
 
     def rerun(self, iters, fetch=False):

@@ -10,6 +10,7 @@
 #include "mkp_bedmethyl_in.hpp"
 #include "mkp_ctx.hpp"
 #include "mkp_dmr.hpp"
+#include "mkp_dmr_reps.hpp"
 #include "mkp_dmr_sites.hpp"
 #include "mkp_ingest_host.hpp"
 #include "mkp_launch.h"
@@ -493,12 +494,14 @@ void mkp_ctx_destroy(mkp_ctx* c) {
   for (auto& kv : c->dmr.ref) kv.second.buf.release();
   for (DevBuf* b : {&c->dmr.d_out, &c->dmr.d_seen, &c->dmr.d_cnt, &c->dmr.d_off, &c->dmr.carry[0].buf, &c->dmr.carry[1].buf}) b->release();
   for (auto& kv : c->dsites.contigs) { kv.second.ref.release(); for (auto& r : kv.second.rows) r.buf.release(); }
+  for (auto& kv : c->dreps.contigs) { kv.second.ref.release(); for (auto& r : kv.second.rows) r.buf.release(); }
   { mkp_ctx::BedIn& B = c->bedin;
     for (DevBuf* b : {&B.d_zin, &B.d_text[0], &B.d_text[1], &B.d_blk, &B.d_stat, &B.d_cnt, &B.d_words, &B.d_lines, &B.d_rows, &B.d_runs, &B.d_names})
       b->release();
     for (auto& e : B.ev) if (e) (void)hipEventDestroy(e); }
   for (mkp_ctx::RowTable* t : {static_cast<mkp_ctx::RowTable*>(&c->rstats), static_cast<mkp_ctx::RowTable*>(&c->loc),
-      static_cast<mkp_ctx::RowTable*>(&c->merge), static_cast<mkp_ctx::RowTable*>(&c->dmr), static_cast<mkp_ctx::RowTable*>(&c->dsites)}) {
+      static_cast<mkp_ctx::RowTable*>(&c->merge), static_cast<mkp_ctx::RowTable*>(&c->dmr), static_cast<mkp_ctx::RowTable*>(&c->dsites),
+      static_cast<mkp_ctx::RowTable*>(&c->dreps)}) {
     for (DevBuf* b : {&t->d_regions, &t->d_misc, &t->d_lo, &t->d_hi, &t->d_rows}) b->release();
     for (auto& e : t->ev) if (e) (void)hipEventDestroy(e);
   }
@@ -1295,6 +1298,7 @@ constexpr RowTableWords kStatsWords = {"mkp_stats_begin", "region statistics nee
 constexpr RowTableWords kLocWords = {"mkp_localize_begin", "localize needs", "localize", "windows", "localize holds"};
 constexpr RowTableWords kDmrWords = {"mkp_dmr_begin", "dmr pair needs", "dmr pair", "regions", "dmr pair holds"};
 constexpr RowTableWords kDsitesWords = {"mkp_dmr_sites_begin", "dmr sites needs", "dmr sites", "tables", "dmr sites holds"};
+constexpr RowTableWords kDrepsWords = {"mkp_dmr_reps_begin", "dmr replicates needs", "dmr replicates", "tables", "dmr replicates holds"};
 constexpr RowTableWords kMergeWords = {"mkp_merge_begin", "bedmethyl merge needs", "bedmethyl merge", "tables", "bedmethyl merge holds"};
 // the five columns the reducers read, on the device; info = 0 '+', 1 '-', 2 '.' in its low bits; rest = n_canonical, n_other, n_delete,
 // n_fail, n_diff, n_nocall, which only the merge reads (not uploaded for the reducers)
@@ -2239,34 +2243,91 @@ struct ScopedBufs {
   ~ScopedBufs() { for (auto& b : all) b->release(); }
 };
 
-// rows on the device behind the rows of (sample, tid); a contig's pieces come in ascending order
-void dsites_append(mkp_ctx* c, int sample, int32_t tid, const RowCols& r) {
-  mkp_ctx::DmrSites& D = c->dsites;
-  if (tid < 0 || (size_t)tid >= D.names.size()) throw Error(MKP_E_INVALID, "dmr sites: rows of an unknown tid (" + std::to_string(tid) + ")");
+// rows on the device behind the rows R of one (sample, contig); a contig's pieces come in ascending order.  what: the command; *row_bytes: the
+// bytes of all the session's row columns, held to 3/4 of the device's memory
+void dsites_rows_append(mkp_ctx* c, const char* what, mkp_ctx::DmrSites::Rows& R, uint64_t* row_bytes, const RowCols& r) {
   if (!r.n) return;
-  mkp_ctx::DmrSites::Rows& R = D.contigs[tid].rows[sample];
   if ((uint64_t)R.n + r.n > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 rows on one contig");
   uint32_t first = 0, last = 0;
   d2h_copy(&first, r.pos, 4, c->stream); d2h_copy(&last, r.pos + (r.n - 1), 4, c->stream);
-  if (R.n && first < R.last_pos) throw Error(MKP_E_INVALID, "dmr sites: the pieces of a contig must come in ascending order (" + std::to_string(first)
-      + " follows " + std::to_string(R.last_pos) + ")");
+  if (R.n && first < R.last_pos) throw Error(MKP_E_INVALID, std::string(what) + ": the pieces of a contig must come in ascending order ("
+      + std::to_string(first) + " follows " + std::to_string(R.last_pos) + ")");
   const uint32_t* src[6] = {r.pos, r.info, r.code, r.n_valid, r.n_mod, r.rest[0]};
   const uint64_t need = (uint64_t)R.n + r.n;
   if (need > R.cap) {
     const uint64_t cap = ((std::max<uint64_t>(need, R.cap + R.cap / 2) + 63) & ~63ull);
     size_t free_b = 0, total_b = 0; hip_check(hipMemGetInfo(&free_b, &total_b), "hipMemGetInfo");
-    if (D.row_bytes + (cap - R.cap) * 24 > (uint64_t)total_b / 4 * 3) throw Error(MKP_E_UNSUPPORTED, "dmr sites: the two tables need more than "
-        + std::to_string(total_b / 4 * 3 >> 20) + " MiB of device memory (24 bytes a row, both resident)");
+    if (*row_bytes + (cap - R.cap) * 24 > (uint64_t)total_b / 4 * 3) throw Error(MKP_E_UNSUPPORTED, std::string(what) + ": the tables need more than "
+        + std::to_string(total_b / 4 * 3 >> 20) + " MiB of device memory (24 bytes a row, all resident)");
     DevBuf grown; grown.ensure((size_t)cap * 24);
     for (int k = 0; k < 6 && R.n; k++) hip_check(hipMemcpyAsync(grown.as<uint32_t>() + (size_t)k * cap, R.col(k), (size_t)R.n * 4, hipMemcpyDeviceToDevice,
         c->stream), "D2D");
     hip_check(hipStreamSynchronize(c->stream), "sync");
-    R.buf.release(); R.buf = grown; D.row_bytes += (cap - R.cap) * 24; R.cap = cap;
+    R.buf.release(); R.buf = grown; *row_bytes += (cap - R.cap) * 24; R.cap = cap;
   }
   for (int k = 0; k < 6; k++) hip_check(hipMemcpyAsync(R.buf.as<uint32_t>() + (size_t)k * R.cap + R.n, src[k], (size_t)r.n * 4, hipMemcpyDeviceToDevice,
       c->stream), "D2D");
   hip_check(hipStreamSynchronize(c->stream), "sync");   // (the source is the next call's upload buffer)
   R.n = (uint32_t)need; R.last_pos = last;
+}
+
+void dsites_append(mkp_ctx* c, int sample, int32_t tid, const RowCols& r) {
+  mkp_ctx::DmrSites& D = c->dsites;
+  if (tid < 0 || (size_t)tid >= D.names.size()) throw Error(MKP_E_INVALID, "dmr sites: rows of an unknown tid (" + std::to_string(tid) + ")");
+  if (!r.n) return;
+  dsites_rows_append(c, "dmr sites", D.contigs[tid].rows[sample], &D.row_bytes, r);
+}
+
+void dreps_append(mkp_ctx* c, uint32_t sample, int32_t tid, const RowCols& r) {
+  mkp_ctx::DmrReps& D = c->dreps;
+  if (tid < 0 || (size_t)tid >= D.names.size()) throw Error(MKP_E_INVALID, "dmr replicates: rows of an unknown tid (" + std::to_string(tid) + ")");
+  if (!r.n) return;
+  mkp_ctx::DmrReps::Contig& K = D.contigs[tid];
+  K.rows.resize(D.n_side[0] + D.n_side[1]);
+  dsites_rows_append(c, "dmr replicates", K.rows[sample], &D.row_bytes, r);
+}
+
+// a's sample `replicate` is sample `replicate` of the session, b's follows a's
+uint32_t dreps_sample(const mkp_ctx::DmrReps& D, int side, int replicate) {
+  if (side != 0 && side != 1) throw Error(MKP_E_INVALID, "side must be 0 (a) or 1 (b)");
+  if (replicate < 0 || (uint32_t)replicate >= D.n_side[side]) throw Error(MKP_E_INVALID, "replicate " + std::to_string(replicate) + " of side "
+      + (side ? "b" : "a") + ": the session holds " + std::to_string(D.n_side[side]));
+  return (side ? D.n_side[0] : 0u) + (uint32_t)replicate;
+}
+
+// the checks of a mkp_dmr_sites_config and its row filter (mkp_dmr_sites_begin, mkp_dmr_reps_begin)
+MkpDmrParams dsites_checked_params(const mkp_dmr_sites_config* cfg) {
+  if (cfg->n_contigs > 0x7fffffffu) throw Error(MKP_E_UNSUPPORTED, "more than 2^31 - 1 contigs");
+  MkpDmrParams P; memset(&P, 0, sizeof(P));
+  P.min_cov = cfg->min_valid_coverage; P.mask = cfg->respect_mask ? 1u : 0u;
+  if (!cfg->n_bases) throw Error(MKP_E_INVALID, "need to specify at least 1 modified base");
+  for (uint32_t k = 0; k < cfg->n_bases; k++) {
+    const char* at = strchr("ACGT", cfg->bases[k]);
+    if (!at || !cfg->bases[k]) throw Error(MKP_E_INVALID, "modified base needs to be A, C, G, or T.");
+    const uint32_t b = (uint32_t)(at - "ACGT");
+    P.pos_set |= 1u << b; P.neg_set |= 1u << (3u - b);
+  }
+  for (uint32_t k = 0; k < cfg->n_lookup; k++) {   // a later entry for a code replaces an earlier one
+    if (!cfg->codes[k]) throw Error(MKP_E_INVALID, "0 is not a mod code");
+    if (cfg->code_bases[k] > 3) throw Error(MKP_E_INVALID, "a code's base is an index into ACGT");
+    uint32_t at = 0; while (at < P.n_lookup && P.code[at] != cfg->codes[k]) at++;
+    if (at == MKP_DMR_MAX_LOOKUP) throw Error(MKP_E_UNSUPPORTED, "dmr sites holds at most " + std::to_string(MKP_DMR_MAX_LOOKUP)
+        + " codes in its code -> base table");
+    P.code[at] = cfg->codes[k]; P.base[at] = cfg->code_bases[k]; if (at == P.n_lookup) P.n_lookup++;
+  }
+  // (only a code of one of the --base letters can ever take part: mkp_dmr_begin)
+  uint32_t kept = 0;
+  for (uint32_t k = 0; k < P.n_lookup; k++) if ((P.pos_set >> P.base[k]) & 1u) { P.code[kept] = P.code[k]; P.base[kept] = P.base[k]; kept++; }
+  for (uint32_t k = kept; k < P.n_lookup; k++) { P.code[k] = 0; P.base[k] = 0; }
+  P.n_lookup = kept;
+  if (cfg->prior_alpha + cfg->prior_beta < 1.0) throw Error(MKP_E_INVALID, "alpha + beta must be > 1.0 for numerical stability");
+  if (!(cfg->prior_alpha > 0.0) || !(cfg->prior_beta > 0.0) || std::isinf(cfg->prior_alpha) || std::isinf(cfg->prior_beta))
+    throw Error(MKP_E_INVALID, "invalid beta parameters " + std::to_string(cfg->prior_alpha) + ", " + std::to_string(cfg->prior_beta));
+  if (cfg->delta != cfg->delta) throw Error(MKP_E_INVALID, "--delta is not a number");
+  if (!cfg->interval_size || cfg->interval_size > 0xffffffffull) throw Error(MKP_E_INVALID, "the interval size must be in [1, 2^32 - 1]");
+  if (!cfg->batch_size) throw Error(MKP_E_INVALID, "the batch size must be at least 1");
+  if (!cfg->have_max_coverages && !cfg->n_sample_records) throw Error(MKP_E_INVALID, "the number of sample records must be at least 1");
+  return P;
 }
 
 double ms_between(std::chrono::steady_clock::time_point& t) {
@@ -2314,36 +2375,7 @@ int mkp_dmr_sites_begin(mkp_ctx* c, const mkp_dmr_sites_config* cfg) {
   return guarded(c, [&]() {
     mkp_ctx::DmrSites& D = c->dsites;
     D.open = false;
-    if (cfg->n_contigs > 0x7fffffffu) throw Error(MKP_E_UNSUPPORTED, "more than 2^31 - 1 contigs");
-    MkpDmrParams P; memset(&P, 0, sizeof(P));
-    P.min_cov = cfg->min_valid_coverage; P.mask = cfg->respect_mask ? 1u : 0u;
-    if (!cfg->n_bases) throw Error(MKP_E_INVALID, "need to specify at least 1 modified base");
-    for (uint32_t k = 0; k < cfg->n_bases; k++) {
-      const char* at = strchr("ACGT", cfg->bases[k]);
-      if (!at || !cfg->bases[k]) throw Error(MKP_E_INVALID, "modified base needs to be A, C, G, or T.");
-      const uint32_t b = (uint32_t)(at - "ACGT");
-      P.pos_set |= 1u << b; P.neg_set |= 1u << (3u - b);
-    }
-    for (uint32_t k = 0; k < cfg->n_lookup; k++) {   // a later entry for a code replaces an earlier one
-      if (!cfg->codes[k]) throw Error(MKP_E_INVALID, "0 is not a mod code");
-      if (cfg->code_bases[k] > 3) throw Error(MKP_E_INVALID, "a code's base is an index into ACGT");
-      uint32_t at = 0; while (at < P.n_lookup && P.code[at] != cfg->codes[k]) at++;
-      if (at == MKP_DMR_MAX_LOOKUP) throw Error(MKP_E_UNSUPPORTED, "dmr sites holds at most " + std::to_string(MKP_DMR_MAX_LOOKUP)
-          + " codes in its code -> base table");
-      P.code[at] = cfg->codes[k]; P.base[at] = cfg->code_bases[k]; if (at == P.n_lookup) P.n_lookup++;
-    }
-    // (only a code of one of the --base letters can ever take part: mkp_dmr_begin)
-    uint32_t kept = 0;
-    for (uint32_t k = 0; k < P.n_lookup; k++) if ((P.pos_set >> P.base[k]) & 1u) { P.code[kept] = P.code[k]; P.base[kept] = P.base[k]; kept++; }
-    for (uint32_t k = kept; k < P.n_lookup; k++) { P.code[k] = 0; P.base[k] = 0; }
-    P.n_lookup = kept;
-    if (cfg->prior_alpha + cfg->prior_beta < 1.0) throw Error(MKP_E_INVALID, "alpha + beta must be > 1.0 for numerical stability");
-    if (!(cfg->prior_alpha > 0.0) || !(cfg->prior_beta > 0.0) || std::isinf(cfg->prior_alpha) || std::isinf(cfg->prior_beta))
-      throw Error(MKP_E_INVALID, "invalid beta parameters " + std::to_string(cfg->prior_alpha) + ", " + std::to_string(cfg->prior_beta));
-    if (cfg->delta != cfg->delta) throw Error(MKP_E_INVALID, "--delta is not a number");
-    if (!cfg->interval_size || cfg->interval_size > 0xffffffffull) throw Error(MKP_E_INVALID, "the interval size must be in [1, 2^32 - 1]");
-    if (!cfg->batch_size) throw Error(MKP_E_INVALID, "the batch size must be at least 1");
-    if (!cfg->have_max_coverages && !cfg->n_sample_records) throw Error(MKP_E_INVALID, "the number of sample records must be at least 1");
+    const MkpDmrParams P = dsites_checked_params(cfg);
     D.names.clear();
     for (uint32_t k = 0; k < cfg->n_contigs; k++) { if (!cfg->contig_names[k]) throw Error(MKP_E_INVALID, "contig name " + std::to_string(k) + " is NULL");
       D.names.push_back(cfg->contig_names[k]); }
@@ -2575,6 +2607,330 @@ int mkp_dmr_sites_get(mkp_ctx* c, mkp_dmr_sites_out* out) {
     out->score = D.h_score.data(); out->map_pvalue = D.h_p.data(); out->effect_size = D.h_effect.data();
     out->n_batches = n_batches; out->n_batches_dropped = n_dropped; out->n_model_failures = n_failed;
     D.used_max_cov[0] = max_cov[0]; D.used_max_cov[1] = max_cov[1];
+  });
+}
+
+}  // extern "C"
+
+// ---- dmr replicates (`modkit dmr pair` without -r over several -a / -b tables, include/mkpileup.h): every table's row columns stay in HBM per
+// contig between mkp_dmr_reps_begin and mkp_dmr_reps_get, which runs dmr sites' stages per sample and the stages of mkp_dmr_reps.hip
+static_assert(MKP_DMRR_MAX_SIDE == MKP_DMR_REPS_MAX_SIDE, "the device's sample limit is the public one");
+
+extern "C" {
+
+int mkp_internal_dmr_reps_timing(mkp_ctx* c, double ms_out[9]) {
+  if (!c || !ms_out) return MKP_E_INVALID;
+  for (int k = 0; k < 9; k++) ms_out[k] = c->dreps.stage_ms[k];
+  return MKP_OK;
+}
+
+int mkp_dmr_reps_begin(mkp_ctx* c, const mkp_dmr_sites_config* cfg, uint32_t n_a, uint32_t n_b, int cap_coverages) {
+  if (!c || !cfg || (!cfg->contig_names && cfg->n_contigs) || (!cfg->bases && cfg->n_bases) || ((!cfg->codes || !cfg->code_bases) && cfg->n_lookup))
+    return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::DmrReps& D = c->dreps;
+    D.open = false;
+    if (!n_a || !n_b) throw Error(MKP_E_INVALID, "must be at least 1 sample for 'a' and 'b'");
+    if (n_a > MKP_DMRR_MAX_SIDE || n_b > MKP_DMRR_MAX_SIDE) throw Error(MKP_E_UNSUPPORTED, "dmr replicates holds at most "
+        + std::to_string(MKP_DMRR_MAX_SIDE) + " tables a side (" + std::to_string(n_a) + " -a, " + std::to_string(n_b) + " -b)");
+    const MkpDmrParams P = dsites_checked_params(cfg);
+    D.names.clear();
+    for (uint32_t k = 0; k < cfg->n_contigs; k++) { if (!cfg->contig_names[k]) throw Error(MKP_E_INVALID, "contig name " + std::to_string(k) + " is NULL");
+      D.names.push_back(cfg->contig_names[k]); }
+    D.prm = P; D.have_max = cfg->have_max_coverages != 0; D.max_cov[0] = cfg->max_coverages[0]; D.max_cov[1] = cfg->max_coverages[1];
+    D.math = dmr_site_math(cfg->prior_alpha, cfg->prior_beta, cfg->delta, D.max_cov);
+    D.n_sample = cfg->n_sample_records; D.interval = cfg->interval_size; D.batch_size = cfg->batch_size;
+    D.n_side[0] = n_a; D.n_side[1] = n_b; D.cap = cap_coverages != 0;
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    hip_check(hipStreamSynchronize(c->stream), "sync");   // (a previous session's kernels)
+    for (auto& kv : D.contigs) { kv.second.ref.release(); for (auto& r : kv.second.rows) r.buf.release(); }
+    D.contigs.clear(); D.row_bytes = 0;
+    D.d_misc.ensure(kStatsMiscBytes);
+    D.open = true;
+  });
+}
+
+int mkp_dmr_reps_set_reference(mkp_ctx* c, int32_t tid, const uint8_t* bytes, uint64_t len) {
+  if (!c || (!bytes && len)) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::DmrReps& D = c->dreps;
+    rt_need_open(D, kDrepsWords);
+    if (tid < 0 || (size_t)tid >= D.names.size()) throw Error(MKP_E_INVALID, "dmr replicates: the reference of an unknown tid (" + std::to_string(tid) + ")");
+    if (len > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "a contig beyond 2^32 - 1 bases");
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    mkp_ctx::DmrReps::Contig& K = D.contigs[tid];
+    K.ref.ensure(std::max<size_t>((size_t)len, 1)); K.len = (uint32_t)len; K.has_ref = true;
+    h2d_copy(K.ref.p, bytes, (size_t)len);
+  });
+}
+
+int mkp_dmr_reps_add_rows(mkp_ctx* c, int side, int replicate, int32_t tid, const mkp_rows* rows) {
+  if (!c || !rows) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    rt_need_open(c->dreps, kDrepsWords);
+    const uint32_t sample = dreps_sample(c->dreps, side, replicate);
+    dreps_append(c, sample, tid, rt_upload_rows(c, c->dreps, kDrepsWords, rows, 6));
+  });
+}
+
+int mkp_dmr_reps_add_file(mkp_ctx* c, int side, int replicate, const char* path, uint64_t* n_rows) {
+  if (!c || !path) return MKP_E_INVALID;
+  if (n_rows) *n_rows = 0;
+  return guarded(c, [&]() {
+    mkp_ctx::DmrReps& D = c->dreps;
+    rt_need_open(D, kDrepsWords);
+    const uint32_t sample = dreps_sample(D, side, replicate);
+    std::map<std::string, int32_t> tid_of;   // (the first of two equal names)
+    for (size_t k = 0; k < D.names.size(); k++) tid_of.emplace(D.names[k], (int32_t)k);
+    uint64_t total = 0;
+    bedin_read_file(c, path, [&](const std::string& chrom, const RowCols& r, bool) {
+      auto it = tid_of.find(chrom);
+      total += r.n;
+      if (it != tid_of.end()) dreps_append(c, sample, it->second, r);
+    });
+    if (n_rows) *n_rows = total;
+  });
+}
+
+int mkp_dmr_reps_get(mkp_ctx* c, mkp_dmr_reps_out* out) {
+  if (!c || !out) return MKP_E_INVALID;
+  return guarded(c, [&]() {
+    mkp_ctx::DmrReps& D = c->dreps;
+    rt_need_open(D, kDrepsWords);
+    hip_check(hipSetDevice(c->device), "hipSetDevice");
+    hipStream_t st = c->stream;
+    for (double& m : D.stage_ms) m = 0;
+    auto clk = std::chrono::steady_clock::now();
+    const uint32_t n_a = D.n_side[0], n_b = D.n_side[1], ns = n_a + n_b;
+    const bool matched = n_a == n_b && n_a > 1;
+    const uint32_t rep_stride = matched ? n_a : 0u;
+    auto side_of = [&](uint32_t s) { return s < n_a ? 0 : 1; };
+    // the contigs of the walk: in the FASTA, in at least one table of a and in at least one of b, in byte order of their names
+    std::vector<int32_t> tids;
+    for (auto& kv : D.contigs) {
+      bool has[2] = {false, false};
+      kv.second.rows.resize(ns);
+      for (uint32_t s = 0; s < ns; s++) if (kv.second.rows[s].n) has[side_of(s)] = true;
+      if (kv.second.has_ref && has[0] && has[1]) tids.push_back(kv.first);
+    }
+    std::sort(tids.begin(), tids.end(), [&](int32_t a, int32_t b) { return D.names[a] != D.names[b] ? D.names[a] < D.names[b] : a < b; });
+    if (tids.empty()) throw Error(MKP_E_INVALID, "need at least 1 contig");
+    const size_t nt = tids.size();
+    ScopedBufs bufs;
+
+    // ---- listed counts, then the batch table (the walk depends on the reference alone)
+    std::vector<uint64_t> lens(nt), win_off(nt + 1, 0);
+    for (size_t k = 0; k < nt; k++) { lens[k] = D.contigs[tids[k]].len; win_off[k + 1] = win_off[k] + dmr_sites_windows(lens[k], D.interval); }
+    std::vector<uint32_t> counts((size_t)win_off[nt]);
+    { uint32_t* d_counts = bufs.get<uint32_t>(counts.size());
+      for (size_t k = 0; k < nt; k++) { const auto& K = D.contigs[tids[k]];
+        hip_check(mkp_launch_dmr_sites_listed(st, K.ref.as<uint8_t>(), K.len, D.interval, (uint32_t)(win_off[k + 1] - win_off[k]), &D.prm,
+            d_counts + win_off[k]), "dmr replicates listed launch"); }
+      d2h_copy(counts.data(), d_counts, counts.size() * 4, st); }
+    std::vector<mkp_dmr_sites_batch> plan;
+    const uint64_t n_batches = dmr_sites_plan(lens.data(), counts.data(), (uint32_t)nt, D.interval, &plan);
+    if (n_batches > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 batches");
+    std::vector<size_t> ent_off(nt + 1, 0);
+    std::vector<MkpDmrSitesBatch> table(plan.size());
+    for (size_t e = 0; e < plan.size(); e++) { table[e] = {(uint32_t)plan[e].start, (uint32_t)plan[e].batch}; ent_off[plan[e].contig + 1] = e + 1; }
+    MkpDmrSitesBatch* d_table = bufs.get<MkpDmrSitesBatch>(table.size());
+    h2d_copy(d_table, table.data(), table.size() * sizeof(MkpDmrSitesBatch));
+    D.stage_ms[0] = ms_between(clk);
+
+    // ---- heads: row flags and sites per (contig, sample); the slots' codes are the run's
+    hip_check(hipMemsetAsync(D.d_misc.p, 0, kStatsMiscBytes, st), "memset");
+    uint32_t* misc_d = D.d_misc.as<uint32_t>();
+    struct Sample { uint8_t* rowflag; uint32_t *tile, *totals, *s_pos, *s_first, *s_total, *s_info; uint32_t n_sites = 0, n_part = 0; };
+    std::vector<Sample> smp(ns * nt);   // [contig * ns + sample]
+    for (size_t k = 0; k < nt; k++) for (uint32_t s = 0; s < ns; s++) {
+      const auto& K = D.contigs[tids[k]]; const auto& R = K.rows[s]; Sample& S = smp[k * ns + s];
+      const size_t n = R.n, n_tiles = (n + MKP_DMRS_TILE - 1) / MKP_DMRS_TILE;
+      S.rowflag = bufs.get<uint8_t>(n); S.tile = bufs.get<uint32_t>(2 * n_tiles); S.totals = bufs.get<uint32_t>(2);
+      S.s_pos = bufs.get<uint32_t>(n); S.s_first = bufs.get<uint32_t>(n); S.s_total = bufs.get<uint32_t>(n); S.s_info = bufs.get<uint32_t>(n);
+      hip_check(mkp_launch_dmr_sites_heads(st, R.col(0), R.col(1), R.col(2), R.col(3), R.col(4), R.col(5), R.n, K.ref.as<uint8_t>(), K.len, &D.prm,
+          misc_d, misc_d + MKP_STATS_MAX_CODES, S.rowflag, S.tile, S.totals, S.s_pos, S.s_first, S.s_total, S.s_info), "dmr replicates heads launch");
+    }
+    for (Sample& S : smp) { uint32_t t[2]; d2h_copy(t, S.totals, 8, st); S.n_sites = t[0]; S.n_part = t[1]; }
+    uint32_t misc[kStatsMiscBytes / 4];
+    d2h_copy(misc, D.d_misc.p, sizeof(misc), st);
+    rt_check_codes(misc, kDrepsWords);
+    uint32_t any = 0; for (uint32_t s = 0; s < MKP_STATS_MAX_CODES; s++) if (misc[s]) any |= 1u << s;
+    const std::vector<std::pair<uint32_t, uint32_t>> cols = rt_columns(misc, any);   // code, slot
+    const uint32_t nc = (uint32_t)cols.size();
+    unsigned long long col_of_slot = 0;
+    D.h_codes.resize(nc);
+    for (uint32_t k = 0; k < nc; k++) { D.h_codes[k] = cols[k].first; col_of_slot |= (unsigned long long)k << (4u * cols[k].second); }
+    D.stage_ms[1] = ms_between(clk);
+
+    // ---- the max coverages: given, or the 95th percentile of the coverages of the participating rows of the first super-batches, pooled
+    // over a side's samples
+    uint32_t max_cov[2] = {D.max_cov[0], D.max_cov[1]}; uint64_t n_sampled[2] = {0, 0};
+    if (!D.have_max) {
+      const size_t ne = plan.size();
+      std::vector<std::vector<uint32_t>> row_at(ns, std::vector<uint32_t>(ne)), before(ns, std::vector<uint32_t>(ne));
+      { uint32_t* d_at = bufs.get<uint32_t>((size_t)ns * ne); uint32_t* d_before = bufs.get<uint32_t>((size_t)ns * ne);
+        for (size_t k = 0; k < nt; k++) for (uint32_t s = 0; s < ns; s++) { const auto& R = D.contigs[tids[k]].rows[s]; const Sample& S = smp[k * ns + s];
+          hip_check(mkp_launch_dmr_sites_bounds(st, R.col(0), S.rowflag, R.n, S.tile, S.totals, d_table + ent_off[k], (uint32_t)(ent_off[k + 1] - ent_off[k]),
+              d_at + s * ne + ent_off[k], d_before + s * ne + ent_off[k]), "dmr replicates bounds launch"); }
+        for (uint32_t s = 0; s < ns; s++) { d2h_copy(row_at[s].data(), d_at + s * ne, ne * 4, st); d2h_copy(before[s].data(), d_before + s * ne, ne * 4, st); } }
+      // the first super-batch behind which both sides hold n_sample values; the entries up to it are a prefix of the walk
+      size_t stop = ne;   // entries [0, stop) are sampled
+      { uint64_t have[2] = {0, 0}; size_t e = 0;
+        while (e < ne) {
+          const uint64_t sb = plan[e].batch / D.batch_size;
+          for (; e < ne && plan[e].batch / D.batch_size == sb; e++) for (uint32_t s = 0; s < ns; s++) {
+            const size_t k = plan[e].contig; const bool last_of_contig = e + 1 == ent_off[k + 1];
+            have[side_of(s)] += (last_of_contig ? smp[k * ns + s].n_part : before[s][e + 1]) - before[s][e];
+          }
+          if (std::min(have[0], have[1]) >= D.n_sample) { stop = e; break; }
+        }
+        n_sampled[0] = have[0]; n_sampled[1] = have[1]; }
+      for (int side = 0; side < 2; side++) {
+        if (n_sampled[side] < 2) throw Error(MKP_E_INVALID, "too few data points to calculate percentile, got " + std::to_string(n_sampled[side])
+            + " (the max coverages are estimated from the participating rows of the " + (side ? "b" : "a") + " samples: give --max-coverages)");
+        if (n_sampled[side] > 0xffffffffull) throw Error(MKP_E_UNSUPPORTED, "more than 2^32 - 1 sampled coverages");
+        uint32_t* d_cov = bufs.get<uint32_t>((size_t)n_sampled[side]); uint32_t* d_cursor = bufs.get<uint32_t>(1);
+        hip_check(hipMemsetAsync(d_cursor, 0, 4, st), "memset");
+        for (size_t k = 0; k < nt; k++) for (uint32_t s = side ? n_a : 0u; s < (side ? ns : n_a); s++) {
+          const auto& R = D.contigs[tids[k]].rows[s];
+          const uint32_t n_front = stop >= ent_off[k + 1] ? R.n : stop <= ent_off[k] ? 0u : row_at[s][stop];
+          hip_check(mkp_launch_dmr_sites_coverages(st, smp[k * ns + s].rowflag, R.col(3), n_front, d_cursor, d_cov, (uint32_t)n_sampled[side]),
+              "dmr replicates coverages launch");
+        }
+        std::vector<uint32_t> cov((size_t)n_sampled[side]); uint32_t got = 0;
+        d2h_copy(&got, d_cursor, 4, st); d2h_copy(cov.data(), d_cov, cov.size() * 4, st);
+        if (got != n_sampled[side]) throw Error(MKP_E_DEVICE, "dmr replicates: the coverage sample holds " + std::to_string(got) + " values, "
+            + std::to_string(n_sampled[side]) + " were counted");
+        std::vector<float> xs(cov.size()); for (size_t i = 0; i < cov.size(); i++) xs[i] = (float)cov[i];
+        std::sort(xs.begin(), xs.end());
+        float q = 0; if (mkp_percentile(xs.data(), xs.size(), 0.95f, &q) != MKP_OK) throw Error(MKP_E_INVALID, "percentile of the sampled coverages failed");
+        max_cov[side] = (uint32_t)floorf(q);
+      }
+    }
+    // PMapEstimator::new: a side's max coverage times its number of tables unless --cap-coverages, then the cap of 300
+    MkpDmrSiteMath math = D.math;
+    for (int s = 0; s < 2; s++) {
+      const uint64_t m = (uint64_t)max_cov[s] * (D.cap ? 1u : D.n_side[s]);
+      max_cov[s] = (uint32_t)std::min<uint64_t>(m, MKP_DMR_SITE_MAX_COV); math.max_cov[s] = max_cov[s];
+    }
+    D.stage_ms[2] = ms_between(clk);
+
+    // ---- bad batches of any sample, then per contig the two bitmaps, their join and the joined positions
+    uint32_t* d_bad = bufs.get<uint32_t>((size_t)n_batches);
+    hip_check(hipMemsetAsync(d_bad, 0, std::max<size_t>((size_t)n_batches, 1) * 4, st), "memset");
+    for (size_t k = 0; k < nt; k++) for (uint32_t s = 0; s < ns; s++) { const Sample& S = smp[k * ns + s];
+      hip_check(mkp_launch_dmr_sites_bad(st, S.s_pos, S.s_info, S.n_sites, d_table + ent_off[k], (uint32_t)(ent_off[k + 1] - ent_off[k]), d_bad),
+          "dmr replicates bad launch"); }
+    std::vector<uint32_t> bad((size_t)n_batches);
+    d2h_copy(bad.data(), d_bad, bad.size() * 4, st);
+    uint64_t n_dropped = 0; for (uint32_t b : bad) if (b) n_dropped++;
+    uint64_t max_len = 0; for (uint64_t l : lens) max_len = std::max(max_len, l);
+    const size_t max_words = (size_t)((max_len + 31) / 32), max_tiles = (max_words + MKP_DMRS_TILE - 1) / MKP_DMRS_TILE;
+    uint32_t* d_bits[2] = {bufs.get<uint32_t>(max_words), bufs.get<uint32_t>(max_words)};   // (one pair, a contig after the other in stream order)
+    uint32_t* d_word_tile = bufs.get<uint32_t>(2 * max_tiles); uint32_t* d_totals = bufs.get<uint32_t>(2);
+    struct Joined { uint32_t* j_pos = nullptr; uint32_t n = 0; };
+    std::vector<Joined> joined(nt);
+    for (size_t k = 0; k < nt; k++) {
+      Joined& J = joined[k];
+      const uint32_t n_words = (uint32_t)((lens[k] + 31) / 32);
+      for (int side = 0; side < 2; side++) hip_check(hipMemsetAsync(d_bits[side], 0, std::max<size_t>(n_words, 1) * 4, st), "memset");
+      for (uint32_t s = 0; s < ns; s++) { const Sample& S = smp[k * ns + s];
+        hip_check(mkp_launch_dmr_reps_mark(st, S.s_pos, S.n_sites, d_bits[side_of(s)], n_words), "dmr replicates mark launch"); }
+      hip_check(mkp_launch_dmr_reps_join(st, d_bits[0], d_bits[1], n_words, d_table + ent_off[k], (uint32_t)(ent_off[k + 1] - ent_off[k]), d_bad, d_word_tile,
+          d_totals), "dmr replicates join launch");
+      uint32_t t[2]; d2h_copy(t, d_totals, 8, st); J.n = t[0];
+      J.j_pos = bufs.get<uint32_t>(J.n);
+      hip_check(mkp_launch_dmr_reps_list(st, d_bits[0], n_words, d_word_tile, J.j_pos, J.n), "dmr replicates list launch");
+    }
+    D.stage_ms[3] = ms_between(clk);
+
+    // ---- gather: the collapsed and balanced counts and the replicates' counts of every joined site
+    std::vector<MkpDmrRepsSites> outs(nt);
+    MkpDmrRepsSample* d_samples = bufs.get<MkpDmrRepsSample>((size_t)nt * ns);
+    { std::vector<MkpDmrRepsSample> h(nt * ns);
+      for (size_t k = 0; k < nt; k++) for (uint32_t s = 0; s < ns; s++) { const auto& R = D.contigs[tids[k]].rows[s]; const Sample& S = smp[k * ns + s];
+        h[k * ns + s] = {{R.col(0), R.col(4), S.rowflag, R.n, S.s_pos, S.s_first, S.s_total, S.s_info}, S.n_sites, 0u}; }
+      h2d_copy(d_samples, h.data(), h.size() * sizeof(MkpDmrRepsSample)); }
+    for (size_t k = 0; k < nt; k++) {
+      const size_t n = joined[k].n; MkpDmrRepsSites& O = outs[k];
+      O.pos = bufs.get<uint32_t>(n); O.info = bufs.get<uint32_t>(n); O.present = bufs.get<uint32_t>(n); O.pct = bufs.get<uint32_t>(n);
+      O.has = bufs.get<uint32_t>(n); O.total = bufs.get<uint32_t>(2 * n); O.bal_total = bufs.get<uint32_t>(2 * n); O.cnt = bufs.get<uint32_t>(n * 2 * nc);
+      O.bal_cnt = bufs.get<uint32_t>(n * 2 * nc); O.msum = bufs.get<uint32_t>(4 * n); O.rep = bufs.get<uint32_t>(n * 4 * rep_stride);
+      O.n_rep = bufs.get<uint32_t>(n); O.score = bufs.get<double>(n); O.pvalue = bufs.get<double>(n); O.effect = bufs.get<double>(n);
+      O.bal_pvalue = bufs.get<double>(n); O.bal_effect = bufs.get<double>(n); O.rep_pvalue = bufs.get<double>(n * rep_stride);
+      O.rep_effect = bufs.get<double>(n * rep_stride);
+      hip_check(mkp_launch_dmr_reps_gather(st, d_samples + k * ns, n_a, n_b, joined[k].j_pos, joined[k].n, col_of_slot, nc, rep_stride, &O),
+          "dmr replicates gather launch");
+    }
+    hip_check(hipStreamSynchronize(st), "dmr replicates gather sync");
+    D.stage_ms[4] = ms_between(clk);
+
+    // ---- the task lists, then the p-values and the ratios
+    struct Tasks { uint32_t* off = nullptr; uint32_t n[2] = {0, 0}; };
+    std::vector<Tasks> tasks(nt);
+    for (size_t k = 0; k < nt; k++) {
+      const size_t n = joined[k].n, n_tiles = (n + MKP_DMRS_TILE - 1) / MKP_DMRS_TILE;
+      uint32_t* tile = bufs.get<uint32_t>(2 * n_tiles); uint32_t* totals = bufs.get<uint32_t>(2);
+      tasks[k].off = bufs.get<uint32_t>(2 * n);
+      hip_check(mkp_launch_dmr_reps_tasks(st, outs[k].present, joined[k].n, rep_stride, tile, totals, tasks[k].off), "dmr replicates tasks launch");
+      d2h_copy(tasks[k].n, totals, 8, st);
+    }
+    D.stage_ms[5] = ms_between(clk);
+    for (size_t k = 0; k < nt; k++)
+      hip_check(mkp_launch_dmr_reps_score(st, tasks[k].off, tasks[k].n[0], tasks[k].n[1], joined[k].n, nc, rep_stride, &math, &outs[k]),
+          "dmr replicates score launch");
+    hip_check(hipStreamSynchronize(st), "dmr replicates score sync");
+    D.stage_ms[6] = ms_between(clk);
+
+    // ---- read-back, and the written sites in walk order
+    uint64_t n_all = 0; for (const Joined& J : joined) n_all += J.n;
+    D.h_tid.clear(); D.h_pos.clear(); D.h_strand.clear(); D.h_score.clear(); D.h_p.clear(); D.h_effect.clear(); D.h_bal_p.clear(); D.h_bal_effect.clear();
+    D.h_rep_p.clear(); D.h_rep_effect.clear(); D.h_n_rep.clear();
+    for (int s = 0; s < 2; s++) { D.h_total[s].clear(); D.h_mod[s].clear(); D.h_has[s].clear(); D.h_pct[s].clear(); }
+    D.h_tid.reserve(n_all); D.h_pos.reserve(n_all); D.h_score.reserve(n_all);
+    uint64_t n_failed = 0; double read_ms = 0;
+    std::vector<uint32_t> pos, info, has, pct, tot, cnt, n_rep; std::vector<double> score, pv, eff, bpv, beff, rpv, reff;
+    for (size_t k = 0; k < nt; k++) {
+      const size_t n = joined[k].n; const MkpDmrRepsSites& O = outs[k];
+      auto t_read = std::chrono::steady_clock::now();
+      pos.resize(n); info.resize(n); has.resize(n); pct.resize(n); tot.resize(2 * n); cnt.resize(n * 2 * nc); n_rep.resize(n); score.resize(n); pv.resize(n);
+      eff.resize(n); bpv.resize(n); beff.resize(n); rpv.resize(n * rep_stride); reff.resize(n * rep_stride);
+      d2h_copy(pos.data(), O.pos, n * 4, st); d2h_copy(info.data(), O.info, n * 4, st); d2h_copy(has.data(), O.has, n * 4, st);
+      d2h_copy(pct.data(), O.pct, n * 4, st); d2h_copy(tot.data(), O.total, n * 8, st); d2h_copy(cnt.data(), O.cnt, n * 2 * nc * 4, st);
+      d2h_copy(n_rep.data(), O.n_rep, n * 4, st); d2h_copy(score.data(), O.score, n * 8, st); d2h_copy(pv.data(), O.pvalue, n * 8, st);
+      d2h_copy(eff.data(), O.effect, n * 8, st); d2h_copy(bpv.data(), O.bal_pvalue, n * 8, st); d2h_copy(beff.data(), O.bal_effect, n * 8, st);
+      d2h_copy(rpv.data(), O.rep_pvalue, n * rep_stride * 8, st); d2h_copy(reff.data(), O.rep_effect, n * rep_stride * 8, st);
+      read_ms += ms_between(t_read);
+      for (size_t i = 0; i < n; i++) {
+        if (info[i] & MKP_DMRR_SITE_OVERFLOW) throw Error(MKP_E_UNSUPPORTED, "dmr replicates: the summed coverage of " + D.names[tids[k]] + ":"
+            + std::to_string(pos[i]) + " does not fit 32 bits");
+        if (info[i] & MKP_DMRS_PAIR_FAILED) { n_failed++; continue; }
+        D.h_tid.push_back(tids[k]); D.h_pos.push_back(pos[i]); D.h_strand.push_back((info[i] & MKP_DMRS_SITE_MINUS) ? '-' : '+');
+        for (int s = 0; s < 2; s++) {
+          D.h_total[s].push_back(tot[2 * i + s]); D.h_has[s].push_back(s ? has[i] >> 16 : has[i] & 0xffffu);
+          D.h_pct[s].push_back(s ? pct[i] >> 16 : pct[i] & 0xffffu);
+          D.h_mod[s].insert(D.h_mod[s].end(), cnt.begin() + (i * 2 + s) * nc, cnt.begin() + (i * 2 + s + 1) * nc);
+        }
+        D.h_score.push_back(score[i]); D.h_p.push_back(pv[i]); D.h_effect.push_back(eff[i]); D.h_bal_p.push_back(bpv[i]); D.h_bal_effect.push_back(beff[i]);
+        D.h_n_rep.push_back(n_rep[i]);
+        for (uint32_t r = 0; r < rep_stride; r++) {   // (ranks behind n_rep were never written on the device)
+          const bool on = r < n_rep[i];
+          D.h_rep_p.push_back(on ? rpv[i * rep_stride + r] : 0.0); D.h_rep_effect.push_back(on ? reff[i * rep_stride + r] : 0.0);
+        }
+      }
+    }
+    D.stage_ms[7] = read_ms; D.stage_ms[8] = ms_between(clk) - read_ms;
+    memset(out, 0, sizeof(*out));
+    mkp_dmr_sites_out& T = out->sites;
+    T.n_sites = D.h_pos.size(); T.n_codes = nc; T.code_repr = D.h_codes.data();
+    T.tid = D.h_tid.data(); T.pos = D.h_pos.data(); T.strand = D.h_strand.data();
+    for (int s = 0; s < 2; s++) { T.total[s] = D.h_total[s].data(); T.n_mod[s] = D.h_mod[s].data(); T.has_code[s] = D.h_has[s].data();
+      T.max_coverages[s] = max_cov[s]; T.n_sampled[s] = n_sampled[s]; out->pct_samples[s] = D.h_pct[s].data(); }
+    T.score = D.h_score.data(); T.map_pvalue = D.h_p.data(); T.effect_size = D.h_effect.data();
+    T.n_batches = n_batches; T.n_batches_dropped = n_dropped; T.n_model_failures = n_failed;
+    out->n_a = n_a; out->n_b = n_b; out->balanced_map_pvalue = D.h_bal_p.data(); out->balanced_effect_size = D.h_bal_effect.data();
+    out->n_rep = D.h_n_rep.data();
+    if (matched) { out->rep_pvalue = D.h_rep_p.data(); out->rep_effect = D.h_rep_effect.data(); }
   });
 }
 

@@ -232,6 +232,18 @@ struct mkp_ctx {
     std::vector<double> h_score, h_p, h_effect;
     double stage_ms[7] = {0, 0, 0, 0, 0, 0, 0};   // listed counts, heads, estimate, bad + join, score, read-back, host assembly (the last get)
   } dsites;
+  // dmr replicates (mkp_dmr_reps_begin .. mkp_dmr_reps_get, mkp_dmr_reps.hip): as dmr sites with n_side[0] `a` and n_side[1] `b` samples; a
+  // contig's rows[] holds a's samples, then b's (a sample without rows on the contig has none)
+  struct DmrReps : RowTable {
+    MkpDmrParams prm; MkpDmrSiteMath math; std::vector<std::string> names; uint32_t n_side[2] = {0, 0};
+    bool have_max = false, cap = false; uint32_t max_cov[2] = {0, 0}; uint64_t n_sample = 0, interval = 0, batch_size = 0, row_bytes = 0;
+    struct Contig { mkp::DevBuf ref; uint32_t len = 0; bool has_ref = false; std::vector<DmrSites::Rows> rows; };
+    std::map<int32_t, Contig> contigs;
+    // mkp_dmr_reps_get
+    std::vector<uint32_t> h_codes, h_pos, h_total[2], h_mod[2], h_has[2], h_pct[2], h_n_rep; std::vector<int32_t> h_tid; std::vector<uint8_t> h_strand;
+    std::vector<double> h_score, h_p, h_effect, h_bal_p, h_bal_effect, h_rep_p, h_rep_effect;
+    double stage_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};   // listed counts, heads, estimate, bad + join, gather, tasks, score, read-back, host assembly
+  } dreps;
   // localize (mkp_localize_begin .. mkp_localize_get, mkp_localize.hip): the run-long table tab[slot][2 window + 1]{n_mod, n_valid, n_rows} (u64)
   struct Localize : RowTable {
     uint32_t window = 0, stranded = 0;
@@ -304,5 +316,7 @@ extern "C" int mkp_internal_merge_timing(mkp_ctx* c, int on, double ms_out[2]);
 extern "C" int mkp_internal_dmr_timing(mkp_ctx* c, int on, double ms_out[2]);
 // dmr sites: the wall times of the last mkp_dmr_sites_get in ms [listed counts, heads, estimate, bad + join, score, read-back, host assembly]
 extern "C" int mkp_internal_dmr_sites_timing(mkp_ctx* c, double ms_out[7]);
+// dmr replicates: the same for mkp_dmr_reps_get [listed counts, heads, estimate, bad + join, gather, tasks, score, read-back, host assembly]
+extern "C" int mkp_internal_dmr_reps_timing(mkp_ctx* c, double ms_out[9]);
 // device bedMethyl reader: the read stage's summed times [file read, upload, inflate + CRC, parse] in ms and the pieces read; reset = zero them
 extern "C" int mkp_internal_bedmethyl_in_stats(mkp_ctx* c, int reset, double ms_out[4], uint64_t* pieces);

@@ -337,6 +337,19 @@ struct MkpDmrSitesSample { const uint32_t *pos, *n_mod; const uint8_t* rowflag; 
 // per pair: pos, info (MKP_DMRS_SITE_MINUS | MKP_DMRS_PAIR_FAILED), has = a's column mask | b's << 16, the totals, cnt[(pair * 2 + sample) *
 // n_cols + column], and the three f64 values
 struct MkpDmrSitesPairs { uint32_t *pos, *info, *has, *total_a, *total_b, *cnt; double *score, *pvalue, *effect; };
+// ---- dmr replicates (mkp_dmr_reps.hip): up to MKP_DMRR_MAX_SIDE samples a side, each with its rows and sites as dmr sites makes them.  A side's
+// site set of a contig is a bitmap of one bit a position; a joined site = a position at least one sample of each side holds, outside the
+// dropped batches.
+#define MKP_DMRR_MAX_SIDE 16u
+#define MKP_DMRR_SITE_OVERFLOW 4u   // joined-site info (beside MKP_DMRS_SITE_MINUS and MKP_DMRS_PAIR_FAILED): a summed total beyond 2^32 - 1
+struct MkpDmrRepsSample { MkpDmrSitesSample s; uint32_t n_sites, pad; };
+// per joined site: pos, info, present = a's sample mask | b's << 16, pct = the two shares of samples likewise, has = the column masks likewise;
+// total / bal_total[site * 2 + side]; cnt / bal_cnt[(site * 2 + side) * n_cols + column] (collapsed and balanced counts); msum[site * 4 + ..] =
+// the modified counts {collapsed a, collapsed b, balanced a, balanced b}; rep[((site * 2 + side) * rep_stride + rank) * 2 + ..] = {modified,
+// total} of the side's present samples by rank (matched runs only: rep_stride = the samples a side, otherwise 0 and the rep arrays unused);
+// the f64 values, rep_pvalue / rep_effect[site * rep_stride + rank] for rank < n_rep[site]
+struct MkpDmrRepsSites { uint32_t *pos, *info, *present, *pct, *has, *total, *bal_total, *cnt, *bal_cnt, *msum, *rep, *n_rep;
+  double *score, *pvalue, *effect, *bal_pvalue, *bal_effect, *rep_pvalue, *rep_effect; };
 // ---- localize (mkp_localize.hip): one expanded window [ws, we) of the contig whose rows are being added and the anchor its offsets are
 // taken from (offset = anchor - pos).  The run-long table holds MKP_STATS_MAX_CODES slots of 2 * window + 1 cells {n_mod, n_valid, n_rows}
 // (u64 each); the codes of the slots (0 = free) are a table of the run's own.

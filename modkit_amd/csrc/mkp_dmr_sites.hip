@@ -18,25 +18,13 @@
 //   score      a lane a pair: walks both groups' rows, sums N_mod per code column, then llk_ratio and the p-value
 #include "mkp_dev_codeslots.hpp"
 #include "mkp_dev_dmr_filter.hpp"
+#include "mkp_dev_dmr_sites.hpp"
 #include "mkp_dmr_site_math.hpp"
 #include "mkp_launch.h"
 
 namespace {
 
 constexpr uint32_t kTile = MKP_DMRS_TILE;
-
-// the number of set flags among the workgroup's lanes in front of this one, and (in *total) among all of them; sh: 2 * 4 words of LDS
-__device__ __forceinline__ uint32_t block_rank(bool f, uint32_t* sh, uint32_t* total) {
-  const unsigned long long m = __ballot(f);
-  const uint32_t wave = threadIdx.x >> 6;
-  if (lane_id() == 0) sh[wave] = (uint32_t)__popcll(m);
-  __syncthreads();
-  uint32_t before = 0, all = 0;
-  for (uint32_t w = 0; w < (blockDim.x >> 6); w++) { const uint32_t v = sh[w]; if (w < wave) before += v; all += v; }
-  __syncthreads();
-  *total = all;
-  return before + (uint32_t)__popcll(m & lanemask_lt());
-}
 
 __global__ __launch_bounds__(256) void mkp_dmr_sites_listed(const uint8_t* __restrict__ ref, uint32_t ref_len, unsigned long long interval,
     uint32_t n_windows, const MkpDmrParams P, uint32_t* __restrict__ counts) {
@@ -119,13 +107,6 @@ __global__ __launch_bounds__(256) void mkp_dmr_sites_heads(const uint32_t* __res
   s_info[site] = ((info[i] & 3u) == 1u ? MKP_DMRS_SITE_MINUS : 0u) | (bad ? MKP_DMRS_SITE_BAD : 0u);
 }
 
-// the entry of the contig's batch table a position lies in (the first entry starts at 0)
-__device__ __forceinline__ uint32_t batch_entry(const MkpDmrSitesBatch* __restrict__ batches, uint32_t n_entries, uint32_t p) {
-  uint32_t lo = 0, hi = n_entries;   // the last entry with start <= p
-  while (hi - lo > 1u) { const uint32_t mid = lo + ((hi - lo) >> 1); if (batches[mid].start <= p) lo = mid; else hi = mid; }
-  return lo;
-}
-
 __global__ __launch_bounds__(256) void mkp_dmr_sites_bounds(const uint32_t* __restrict__ pos, const uint8_t* __restrict__ rowflag, uint32_t n_rows,
     const uint32_t* __restrict__ tile_off, const uint32_t* __restrict__ totals, const MkpDmrSitesBatch* __restrict__ batches, uint32_t n_entries,
     uint32_t* __restrict__ row_at, uint32_t* __restrict__ part_before) {
@@ -182,20 +163,6 @@ __global__ __launch_bounds__(256) void mkp_dmr_sites_pairs(const uint32_t* __res
   if (j != MKP_DMRS_NO_PAIR) { pair_a[at] = i; pair_b[at] = j; }
 }
 
-// the participating rows of site `s` of a sample summed per code column: cnt[col] += N_mod, has |= 1 << col.  col_of_slot: 4 bits a slot
-__device__ __forceinline__ void sum_group(const MkpDmrSitesSample& S, uint32_t s, unsigned long long col_of_slot, uint32_t (&cnt)[MKP_DMR_SITE_MAX_CODES],
-    uint32_t* has) {
-  const uint32_t p = S.s_pos[s];
-  for (uint32_t j = S.s_first[s]; j < S.n_rows && S.pos[j] == p; j++) {
-    const uint32_t f = S.rowflag[j];
-    if (!(f & MKP_DMRS_ROW_PART)) continue;
-    const uint32_t col = (uint32_t)(col_of_slot >> (4u * (f & MKP_DMRS_ROW_SLOT))) & 15u, nm = S.n_mod[j];
-    *has |= 1u << col;
-#pragma unroll
-    for (uint32_t k = 0; k < MKP_DMR_SITE_MAX_CODES; k++) cnt[k] += col == k ? nm : 0u;
-  }
-}
-
 __global__ __launch_bounds__(256) void mkp_dmr_sites_score(const MkpDmrSitesSample A, const MkpDmrSitesSample B, const uint32_t* __restrict__ pair_a,
     const uint32_t* __restrict__ pair_b, uint32_t n_pairs, unsigned long long col_of_slot, uint32_t n_cols, const MkpDmrSiteMath M,
     const MkpDmrSitesPairs out) {
@@ -244,6 +211,11 @@ extern "C" hipError_t mkp_launch_dmr_sites_heads(hipStream_t st, const uint32_t*
   mkp_dmr_sites_flags<<<n_tiles, 256, 0, st>>>(pos, info, code, n_valid, n_rows, ref, ref_len, *prm, codes, err, rowflag, tile_cnt);
   mkp_dmr_sites_scan<<<1, 1024, 0, st>>>(tile_cnt, n_tiles, totals);
   mkp_dmr_sites_heads<<<n_tiles, 256, 0, st>>>(pos, info, n_valid, n_mod, n_can, rowflag, n_rows, tile_cnt, s_pos, s_first, s_total, s_info);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t mkp_launch_dmr_sites_scan(hipStream_t st, uint32_t* cnt, uint32_t n_tiles, uint32_t* totals) {
+  mkp_dmr_sites_scan<<<1, 1024, 0, st>>>(cnt, n_tiles, totals);
   return hipGetLastError();
 }
 

@@ -72,21 +72,24 @@ inline void dmr_sites_counts_text(std::string& s, const mkp_dmr_sites_out& t, in
   if (!any) s += '.';
 }
 
+// the 16 fields of site i, without the line end
+template <class F32Text> void dmr_sites_row_text(std::string& s, const mkp_dmr_sites_out& t, const char* const* contig_names, uint64_t i, F32Text f32_text) {
+  s += contig_names[t.tid[i]]; s += '\t'; s += std::to_string(t.pos[i]); s += '\t'; s += std::to_string((uint64_t)t.pos[i] + 1); s += "\t.\t";
+  s += f64_display(t.score[i]); s += '\t'; s += (char)t.strand[i];
+  for (int sample = 0; sample < 2; sample++) { s += '\t'; dmr_sites_counts_text(s, t, sample, i, false); s += '\t'; s += std::to_string(t.total[sample][i]); }
+  for (int sample = 0; sample < 2; sample++) { s += '\t'; dmr_sites_counts_text(s, t, sample, i, true); }
+  for (int sample = 0; sample < 2; sample++) {   // pct_modified: modified / total as f32, a fraction; 0 / 0 prints NaN
+    uint64_t m = 0; for (uint32_t k = 0; k < t.n_codes; k++) if ((t.has_code[sample][i] >> k) & 1u) m += t.n_mod[sample][i * t.n_codes + k];
+    const float f = (float)m / (float)t.total[sample][i];
+    s += '\t'; s += f != f ? std::string("NaN") : std::isinf(f) ? std::string("inf") : f32_text(f);
+  }
+  s += '\t'; s += f64_display(t.map_pvalue[i]); s += '\t'; s += f64_display(t.effect_size[i]);
+}
+
 // the rows of sites [from, to)
 template <class F32Text> void dmr_sites_rows_text(std::string& s, const mkp_dmr_sites_out& t, const char* const* contig_names, uint64_t from, uint64_t to,
     F32Text f32_text) {
-  for (uint64_t i = from; i < to; i++) {
-    s += contig_names[t.tid[i]]; s += '\t'; s += std::to_string(t.pos[i]); s += '\t'; s += std::to_string((uint64_t)t.pos[i] + 1); s += "\t.\t";
-    s += f64_display(t.score[i]); s += '\t'; s += (char)t.strand[i];
-    for (int sample = 0; sample < 2; sample++) { s += '\t'; dmr_sites_counts_text(s, t, sample, i, false); s += '\t'; s += std::to_string(t.total[sample][i]); }
-    for (int sample = 0; sample < 2; sample++) { s += '\t'; dmr_sites_counts_text(s, t, sample, i, true); }
-    for (int sample = 0; sample < 2; sample++) {   // pct_modified: modified / total as f32, a fraction; 0 / 0 prints NaN
-      uint64_t m = 0; for (uint32_t k = 0; k < t.n_codes; k++) if ((t.has_code[sample][i] >> k) & 1u) m += t.n_mod[sample][i * t.n_codes + k];
-      const float f = (float)m / (float)t.total[sample][i];
-      s += '\t'; s += f != f ? std::string("NaN") : std::isinf(f) ? std::string("inf") : f32_text(f);
-    }
-    s += '\t'; s += f64_display(t.map_pvalue[i]); s += '\t'; s += f64_display(t.effect_size[i]); s += '\n';
-  }
+  for (uint64_t i = from; i < to; i++) { dmr_sites_row_text(s, t, contig_names, i, f32_text); s += '\n'; }
 }
 
 }  // namespace mkp

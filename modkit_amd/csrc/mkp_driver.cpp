@@ -19,6 +19,7 @@
 
 #include "mkp_ctx.hpp"
 #include "mkp_dmr.hpp"
+#include "mkp_dmr_reps.hpp"
 #include "mkp_dmr_sites.hpp"
 #include "mkp_ingest_host.hpp"
 #include "mkp_focus.hpp"
@@ -2094,12 +2095,14 @@ std::string dmr_sites_table_text(const mkp_dmr_sites_out& t, const char* const* 
 
 struct DmrSitesArgs {
   std::vector<std::string> a, b, assign; std::string ref, out, bases, regions;
-  bool force = false, header = false, mask = false, stats = false, segment = false, have_prior = false, have_max = false, have_n = false, have_batch = false;
+  bool force = false, header = false, mask = false, stats = false, segment = false, cap = false, have_prior = false, have_max = false, have_n = false, have_batch = false;
   uint64_t min_cov = 0, n_sample = 10042, interval = 100000, batch_size = 0, threads = 4; double prior[2] = {0.55, 0.55}, delta = 0.05;
   uint32_t max_cov[2] = {0, 0}; int device = 0;
 };
 
-DmrSitesArgs parse_dmr_sites_args(int argc, const char* const* argv) {
+// replicates: the command takes several -a / -b (`dmr replicates`); otherwise a second one is refused (`dmr sites`)
+DmrSitesArgs parse_dmr_sites_args(int argc, const char* const* argv, bool replicates = false) {
+  const std::string cmd = replicates ? "dmr replicates" : "dmr sites";
   DmrSitesArgs d;
   for (int i = 0; i < argc; i++) {
     const std::string s = argv[i];
@@ -2123,7 +2126,7 @@ DmrSitesArgs parse_dmr_sites_args(int argc, const char* const* argv) {
     else if (s == "--max-coverages") { for (int k = 0; k < 2; k++) { const uint64_t v = whole(val()); d.max_cov[k] = (uint32_t)std::min<uint64_t>(v, 0xffffffffu); }
       d.have_max = true; }
     else if (s == "-N" || s == "--n-sample-records") { d.n_sample = whole(val()); d.have_n = true; }
-    else if (s == "--cap-coverages") continue;   // (one sample a side: nothing to cap)
+    else if (s == "--cap-coverages") d.cap = true;   // (dmr sites: one sample a side, nothing to cap)
     else if (s == "-i" || s == "--interval-size") d.interval = whole(val());
     else if (s == "--batch-size") { d.batch_size = whole(val()); d.have_batch = true; }
     else if (s == "-t" || s == "--threads") d.threads = whole(val());
@@ -2132,13 +2135,15 @@ DmrSitesArgs parse_dmr_sites_args(int argc, const char* const* argv) {
     else if (s == "--io-threads" || s == "--log-filepath" || s == "--index-a" || s == "--index-b" || s == "--missing")
       val();   // (the reference's tabix indices and io threads: no index is read)
     else if (s == "--suppress-progress") continue;
-    else throw Error(MKP_E_INVALID, "unexpected argument '" + s + "' for dmr sites");
+    else throw Error(MKP_E_INVALID, "unexpected argument '" + s + "' for " + cmd);
   }
   if (d.a.empty() || d.b.empty()) throw Error(MKP_E_INVALID, "need to provide at least 1 'a' sample and 'b' sample");
-  if (!d.regions.empty()) throw Error(MKP_E_INVALID, "-r / --regions-bed is the region form: use dmr pair (dmr sites scores every site of the two tables)");
+  if (!d.regions.empty()) throw Error(MKP_E_INVALID, "-r / --regions-bed is the region form: use dmr pair (" + cmd + " scores every site of the tables)");
   if (d.segment) throw Error(MKP_E_UNSUPPORTED, "--segment (single-site segmentation) is not offered");
-  if (d.a.size() > 1 || d.b.size() > 1) throw Error(MKP_E_UNSUPPORTED,
-      "replicates (more than one -a or -b: balanced columns and per-replicate p-values) are not offered: one -a and one -b");
+  if (!replicates && (d.a.size() > 1 || d.b.size() > 1)) throw Error(MKP_E_UNSUPPORTED,
+      "replicates (more than one -a or -b: balanced columns and per-replicate p-values) are not offered by dmr sites: use dmr replicates");
+  if (d.a.size() > MKP_DMR_REPS_MAX_SIDE || d.b.size() > MKP_DMR_REPS_MAX_SIDE) throw Error(MKP_E_UNSUPPORTED, "dmr replicates holds at most "
+      + std::to_string(MKP_DMR_REPS_MAX_SIDE) + " tables a side (" + std::to_string(d.a.size()) + " -a, " + std::to_string(d.b.size()) + " -b)");
   if (d.ref.empty()) throw Error(MKP_E_INVALID, "the following required arguments were not provided: --ref <REFERENCE_FASTA>");
   if (d.bases.empty()) throw Error(MKP_E_INVALID, "need to specify at least 1 modified base");
   for (char b : d.bases) if (!strchr("ACGT", b)) throw Error(MKP_E_INVALID, "modified base needs to be A, C, G, or T.");
@@ -2216,6 +2221,106 @@ extern "C" int mkp_dmr_sites_main(int argc, const char* const* argv, uint64_t* n
           (unsigned long long)t.n_sites, (unsigned long long)t.n_model_failures, (unsigned long long)t.n_batches, (unsigned long long)t.n_batches_dropped,
           t.max_coverages[0], t.max_coverages[1], (unsigned long long)t.n_sampled[0], (unsigned long long)t.n_sampled[1], host_read ? "host" : "device",
           load_ms, ref_ms, read_ms, get_ms, ms[0], ms[1], ms[2], ms[3], ms[4], ms[5], ms[6], ms_since(t_out), ms_since(t_all)); }
+    return MKP_OK;
+  });
+}
+
+// ---- `mkpileup dmr replicates` = `modkit dmr pair` without -r over several -a / -b tables, in the stages of mkp_dmr_sites_main.  A command of
+// its own because `dmr sites` with a second -a or -b is refused, and the suite pins that refusal.
+extern "C" int mkp_host_dmr_reps_balance(const uint64_t* n_mod, const uint32_t* has_code, const uint64_t* total, uint32_t n_samples, uint32_t n_codes,
+    uint64_t* out_mod, uint32_t* out_has, uint64_t* out_total, int* failed) {
+  if (!has_code || !total || !out_has || !out_total || !failed || !n_samples || n_codes > MKP_DMR_SITE_MAX_CODES) return MKP_E_INVALID;
+  if ((!n_mod || !out_mod) && n_codes) return MKP_E_INVALID;
+  *failed = dmr_reps_balance<uint64_t>(n_mod, has_code, total, n_samples, n_codes, out_mod, out_has, out_total) ? 0 : 1;
+  return MKP_OK;
+}
+extern "C" uint32_t mkp_host_dmr_reps_pct(uint32_t n_present, uint32_t n_samples) { return dmr_reps_pct_samples(n_present, n_samples); }
+
+namespace {
+std::string dmr_reps_table_text(const mkp_dmr_reps_out& t, const char* const* contig_names, bool header) {
+  const uint64_t n = t.sites.n_sites, piece = 8192, np = (n + piece - 1) / piece;
+  std::vector<std::string> parts((size_t)np);
+  HostPool::get().parallel((size_t)np, [&](size_t i) { dmr_reps_rows_text(parts[i], t, contig_names, i * piece, std::min<uint64_t>(n, (i + 1) * piece),
+      f32_display); });
+  size_t total = 0; for (const std::string& p : parts) total += p.size();
+  std::string s; s.reserve(total + 512);
+  if (header) s = dmr_reps_header(dmr_reps_multiple(t), dmr_reps_matched(t));
+  for (const std::string& p : parts) s += p;
+  return s;
+}
+}  // namespace
+
+extern "C" int mkp_host_dmr_reps_table(const mkp_dmr_reps_out* sites, const char* const* contig_names, uint32_t n_contigs, int with_header,
+    const char* out_path) {
+  if (!sites || !out_path || (!contig_names && n_contigs)) return MKP_E_INVALID;
+  if (!sites->n_a || !sites->n_b) return MKP_E_INVALID;
+  return guarded_status([&]() {
+    const mkp_dmr_sites_out& T = sites->sites;
+    for (uint64_t i = 0; i < T.n_sites; i++) {
+      if (T.tid[i] < 0 || (uint32_t)T.tid[i] >= n_contigs) throw Error(MKP_E_INVALID, "site " + std::to_string(i) + " lies on a contig without a name");
+      if (dmr_reps_matched(*sites) && sites->n_rep[i] > sites->n_a) throw Error(MKP_E_INVALID, "site " + std::to_string(i) + " lists more replicate pairs than samples");
+    }
+    write_text_file(out_path, dmr_reps_table_text(*sites, contig_names, with_header != 0)); return MKP_OK; });
+}
+
+extern "C" int mkp_dmr_reps_main(int argc, const char* const* argv, uint64_t* n_written, char* errbuf, size_t errbuf_len) {
+  if (n_written) *n_written = 0;
+  return guarded_buf(errbuf, errbuf_len, [&]() {
+    const DmrSitesArgs d = parse_dmr_sites_args(argc, argv, true);
+    std::vector<uint32_t> codes; std::vector<uint8_t> code_bases;
+    { DmrArgs lookup_args; lookup_args.assign = d.assign; dmr_code_lookup(lookup_args, &codes, &code_bases); }
+    const bool to_stdout = d.out.empty() || d.out == "-" || d.out == "stdout";
+    struct stat sb;
+    if (!to_stdout && !d.force && stat(d.out.c_str(), &sb) == 0) throw Error(MKP_E_IO, "refusing to overwrite existing file " + d.out);
+    auto t_all = std::chrono::steady_clock::now();
+    const Fasta fasta = Fasta::load(d.ref);
+    const double load_ms = ms_since(t_all);
+    std::vector<std::string> names; std::vector<const char*> name_ptrs;
+    for (const auto& kv : fasta.seqs) names.push_back(kv.first);
+    for (const std::string& s : names) name_ptrs.push_back(s.c_str());
+    mkp_config cfg; memset(&cfg, 0, sizeof(cfg)); cfg.device = d.device;
+    mkp_ctx* ctx = nullptr;
+    if (mkp_ctx_create(&cfg, &ctx) != MKP_OK) throw Error(MKP_E_DEVICE, "no usable gfx950 device (libmkpileup has no CPU path)");
+    struct OwnedCtx { mkp_ctx* c; ~OwnedCtx() { mkp_ctx_destroy(c); } } owned{ctx};
+    mkp_dmr_sites_config sc; memset(&sc, 0, sizeof(sc));
+    sc.contig_names = name_ptrs.data(); sc.n_contigs = (uint32_t)name_ptrs.size(); sc.bases = d.bases.data(); sc.n_bases = (uint32_t)d.bases.size();
+    sc.codes = codes.data(); sc.code_bases = code_bases.data(); sc.n_lookup = (uint32_t)codes.size(); sc.respect_mask = d.mask ? 1 : 0;
+    sc.min_valid_coverage = d.min_cov; sc.prior_alpha = d.prior[0]; sc.prior_beta = d.prior[1]; sc.delta = d.delta;
+    sc.have_max_coverages = d.have_max ? 1 : 0; sc.max_coverages[0] = d.max_cov[0]; sc.max_coverages[1] = d.max_cov[1];
+    sc.n_sample_records = d.n_sample; sc.interval_size = d.interval; sc.batch_size = d.batch_size;
+    must(ctx, mkp_dmr_reps_begin(ctx, &sc, (uint32_t)d.a.size(), (uint32_t)d.b.size(), d.cap ? 1 : 0));
+    auto t_ref = std::chrono::steady_clock::now();
+    for (size_t tid = 0; tid < names.size(); tid++) { const FastaSeq* seq = fasta.get(names[tid]);
+      must(ctx, mkp_dmr_reps_set_reference(ctx, (int32_t)tid, (const uint8_t*)seq->data(), seq->size())); }
+    const double ref_ms = ms_since(t_ref);
+    auto t_read = std::chrono::steady_clock::now();
+    const bool host_read = Knobs::one("MKP_HOST_BEDMETHYL");
+    for (int side = 0; side < 2; side++) for (size_t rep = 0; rep < (side ? d.b : d.a).size(); rep++) {
+      const std::string& path = (side ? d.b : d.a)[rep];
+      if (!host_read) { must(ctx, mkp_dmr_reps_add_file(ctx, side, (int)rep, path.c_str(), nullptr)); continue; }
+      const mkp_bedmethyl_file f = read_bedmethyl_text(path);
+      for (size_t k = 0; k < f.runs.size(); k++) {
+        const auto it = std::find(names.begin(), names.end(), f.runs[k].chrom);
+        if (it == names.end()) continue;
+        const mkp_rows rows = f.rows_of(k);
+        must(ctx, mkp_dmr_reps_add_rows(ctx, side, (int)rep, (int32_t)(it - names.begin()), &rows));
+      }
+    }
+    const double read_ms = ms_since(t_read);
+    auto t_get = std::chrono::steady_clock::now();
+    mkp_dmr_reps_out t; must(ctx, mkp_dmr_reps_get(ctx, &t));
+    const double get_ms = ms_since(t_get);
+    auto t_out = std::chrono::steady_clock::now();
+    const std::string text = dmr_reps_table_text(t, name_ptrs.data(), d.header);
+    if (to_stdout) { if (fwrite(text.data(), 1, text.size(), stdout) != text.size()) throw Error(MKP_E_IO, "short write on stdout"); fflush(stdout); }
+    else write_text_file(d.out, text);
+    if (n_written) *n_written = t.sites.n_sites;
+    if (d.stats) { double ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; mkp_internal_dmr_reps_timing(ctx, ms);
+      fprintf(stderr, "[mkpileup] dmr replicates: a=%u b=%u written=%llu model_failures=%llu batches=%llu dropped=%llu max_coverages=%u,%u sampled=%llu,%llu; reader=%s fasta_ms=%.1f reference_upload_ms=%.1f read_ms=%.1f get_ms=%.1f (listed %.3f, heads %.3f, estimate %.3f, bad+join %.3f, gather %.3f, tasks %.3f, score %.3f, read-back %.3f, assembly %.3f) text_ms=%.1f total_ms=%.1f\n",
+          t.n_a, t.n_b, (unsigned long long)t.sites.n_sites, (unsigned long long)t.sites.n_model_failures, (unsigned long long)t.sites.n_batches,
+          (unsigned long long)t.sites.n_batches_dropped, t.sites.max_coverages[0], t.sites.max_coverages[1], (unsigned long long)t.sites.n_sampled[0],
+          (unsigned long long)t.sites.n_sampled[1], host_read ? "host" : "device", load_ms, ref_ms, read_ms, get_ms, ms[0], ms[1], ms[2], ms[3], ms[4],
+          ms[5], ms[6], ms[7], ms[8], ms_since(t_out), ms_since(t_all)); }
     return MKP_OK;
   });
 }

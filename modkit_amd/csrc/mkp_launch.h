@@ -152,6 +152,28 @@ hipError_t mkp_launch_dmr_sites_join(hipStream_t st, const uint32_t* a_pos, uint
 hipError_t mkp_launch_dmr_sites_score(hipStream_t st, const MkpDmrSitesSample* a, const MkpDmrSitesSample* b, const uint32_t* pair_a,
     const uint32_t* pair_b, uint32_t n_pairs, unsigned long long col_of_slot, uint32_t n_cols, const MkpDmrSiteMath* math, const MkpDmrSitesPairs* out);
 
+// the scan alone: cnt = two counters per tile -> their exclusive prefixes, totals[0 .. 2) = the sums
+hipError_t mkp_launch_dmr_sites_scan(hipStream_t st, uint32_t* cnt, uint32_t n_tiles, uint32_t* totals);
+
+// ---- mkp_dmr_reps.hip: ONE contig; bits: a side's site bitmap, n_words words of 32 positions, zeroed by the caller
+hipError_t mkp_launch_dmr_reps_mark(hipStream_t st, const uint32_t* s_pos, uint32_t n_sites, uint32_t* bits, uint32_t n_words);
+// join + scan.  a_bits is left as the joined bitmap; tile_cnt: two words per tile of MKP_DMRS_TILE words, left as exclusive prefixes;
+// totals[0]: the joined sites
+hipError_t mkp_launch_dmr_reps_join(hipStream_t st, uint32_t* a_bits, const uint32_t* b_bits, uint32_t n_words, const MkpDmrSitesBatch* batches,
+    uint32_t n_entries, const uint32_t* bad_batch, uint32_t* tile_cnt, uint32_t* totals);
+// j_pos: the n_joined joined positions, ascending
+hipError_t mkp_launch_dmr_reps_list(hipStream_t st, const uint32_t* bits, uint32_t n_words, const uint32_t* tile_off, uint32_t* j_pos, uint32_t n_joined);
+// samples: DEVICE array, the n_a samples of a then the n_b of b; rep_stride: the samples a side of a matched run, otherwise 0; out: host copy
+hipError_t mkp_launch_dmr_reps_gather(hipStream_t st, const MkpDmrRepsSample* samples, uint32_t n_a, uint32_t n_b, const uint32_t* j_pos,
+    uint32_t n_joined, unsigned long long col_of_slot, uint32_t n_cols, uint32_t rep_stride, const MkpDmrRepsSites* out);
+// count + scan + first tasks.  present: the joined sites' presence masks; tile_cnt: two words per tile of MKP_DMRS_TILE sites; totals[0 .. 2):
+// the p-value tasks and the ratio tasks; task_off[2 * site + {0, 1}]: the site's first task of either kind
+hipError_t mkp_launch_dmr_reps_tasks(hipStream_t st, const uint32_t* present, uint32_t n_joined, uint32_t rep_stride, uint32_t* tile_cnt,
+    uint32_t* totals, uint32_t* task_off);
+// the p-value kernel over its tasks, then the ratio kernel over its own
+hipError_t mkp_launch_dmr_reps_score(hipStream_t st, const uint32_t* task_off, uint32_t n_pmap_tasks, uint32_t n_ratio_tasks, uint32_t n_joined,
+    uint32_t n_cols, uint32_t rep_stride, const MkpDmrSiteMath* math, const MkpDmrRepsSites* out);
+
 // ---- mkp_merge.hip.  a: the table, b: the added rows, stage: staging, out: the new table, *n_out its rows; cuts: mkp_merge_tiles(n_a + n_b) + 1
 // entries, counts / offsets: mkp_merge_tiles(n_a + n_b) each; ev: 3 timing events or NULL
 hipError_t mkp_launch_merge(hipStream_t st, const MkpRowsDev* a, uint32_t n_a, const MkpRowsDev* b, uint32_t n_b, const MkpRowsDev* stage,

@@ -2,7 +2,8 @@
  * `mkpileup pileup-hemi in.bam -o out.bed [modkit pileup-hemi flags]`, `mkpileup extract calls in.bam out.tsv [flags]`,
  * `mkpileup bedmethyl merge a.bed b.bed [c.bed ..] -g sizes.tsv -o out.bed [--force] [--bgzf]`,
  * `mkpileup dmr pair -a a.bed -b b.bed -r regions.bed --ref ref.fa --base C [-o out.bed] [flags of the region form of modkit dmr pair]`,
- * `mkpileup dmr sites -a a.bed -b b.bed --ref ref.fa --base C [-o out.bed] [flags of modkit dmr pair without -r]`. */
+ * `mkpileup dmr sites -a a.bed -b b.bed --ref ref.fa --base C [-o out.bed] [flags of modkit dmr pair without -r]`,
+ * `mkpileup dmr replicates -a a1.bed -a a2.bed .. -b b1.bed -b b2.bed .. --ref ref.fa --base C [-o out.bed] [the flags of dmr sites]`. */
 #include <stdio.h>
 #include <string.h>
 #include "mkpileup.h"
@@ -19,6 +20,7 @@ int main(int argc, char** argv) {
     int rc = MKP_E_UNSUPPORTED;
     if (strcmp(argv[2], "pair") == 0) rc = mkp_dmr_pair_main(argc - 3, (const char* const*)(argv + 3), NULL, err, sizeof(err));
     else if (strcmp(argv[2], "sites") == 0) rc = mkp_dmr_sites_main(argc - 3, (const char* const*)(argv + 3), NULL, err, sizeof(err));
+    else if (strcmp(argv[2], "replicates") == 0) rc = mkp_dmr_reps_main(argc - 3, (const char* const*)(argv + 3), NULL, err, sizeof(err));
     else snprintf(err, sizeof(err), "dmr %s is not offered: only `dmr pair` over the regions of -r", argv[2]);
     if (rc != MKP_OK) { fprintf(stderr, "Error! %s (status %d)\n", err, rc); return 1; }
     return 0;
@@ -37,7 +39,8 @@ int main(int argc, char** argv) {
                     "                [--header] [--min-valid-coverage N] [--assign-code x:C] [--mask] [--missing quiet|warn|fail] [--device N] [--stats]\n"
                     "       mkpileup dmr sites -a <a.bed[.gz]> -b <b.bed[.gz]> --ref <ref.fa> --base C [--base A ..] [-o <out.bed>] [-f] [--header]\n"
                     "                [--min-valid-coverage N] [--assign-code x:C] [--mask] [--prior ALPHA BETA] [--delta D] [--max-coverages A B]\n"
-                    "                [-N N] [--cap-coverages] [-i BP] [--batch-size N | -t T] [--device N] [--stats]\n");
+                    "                [-N N] [--cap-coverages] [-i BP] [--batch-size N | -t T] [--device N] [--stats]\n"
+                    "       mkpileup dmr replicates -a <a1.bed[.gz]> [-a <a2.bed[.gz]> ..] -b <b1.bed[.gz]> [-b ..] --ref <ref.fa> --base C [the flags of dmr sites]\n");
     return 2;
   }
   int rc = hemi ? mkp_pileup_hemi_main(argc - 2, (const char* const*)(argv + 2), err, sizeof(err)) : mkp_pileup_main(argc - 2,
